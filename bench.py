@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark of the forward-backward sweep (BASELINE.json metric:
 individual x marker fwd-bwd steps/sec on the synthetic 10k-individual x 50k-SNP F2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one full sweep (cnf2_sweep through the C ABI: forward + backward over all 8
@@ -10,6 +10,15 @@ shift modes, likelihoods and the per-locus dosage rows) over the rank's individu
 resident in HBM.  Individuals shard across ranks with no data-path collective (weak scaling:
 every rank owns --inds individuals); after the sweep the posteriors are gathered on rank 0
 with one RCCL gather inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (with the roofline of the
+timed launches).  --full adds what takes work of its own beside the headline: the property
+checks on a re-run of the sweep, the CNF2_MERGE_MODES probe, the shader-clock probe, the CPU
+baseline and the iteration probe (with --iterations: the CPU baseline and the accuracy on the
+withheld genotypes).  --dump-outputs DIR writes, after the timed steps, what the last timed
+step computed as DIR/<name>.npy (float64; a fixed, seeded sample where the whole would pass
+64 MB, see dump_outputs); the inputs are generated from fixed seeds, so equal arguments give
+equal inputs.
 
 `--gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset): this process starts the N
 ranks itself -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node N bench.py <same
@@ -164,7 +173,51 @@ def parse():
                          "accumulators on the rank's block of individuals, one all-reduce of the accumulators, the update passes) "
                          "instead of plain sweeps; --inds = analysed individuals in all (not per GPU: iterations do not shard, "
                          "individuals do)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, also the checks, probes and CPU baseline that take work of their own "
+                         "(see the module docstring); a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (at most 64 MB in all)")
     return ap.parse_args()
+
+
+DUMP_BYTES = 60 * 10 ** 6       # the cap of --dump-outputs is 64 MB: room for the .npy headers
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES):
+    """Write `arrays` (name -> torch tensor or numpy array whose first two axes are individuals or records x chromosomes
+    or markers) as outdir/<name>.npy in float64, at most `budget` bytes in all.  Smallest first, each array gets an even
+    share of what is left: an array that fits its share is written whole; a larger one as the positions of a fixed sample
+    over its first two axes (numpy's generator seeded with 0, so equal shapes give equal positions), `<name>.npy` with the
+    values [k, ...] and `<name>_index.npy` with the positions [k, 2] beside it.  Returns {name: what was written}."""
+    os.makedirs(outdir, exist_ok=True)
+    names = sorted(arrays, key=lambda k: (arrays[k].numel() if torch.is_tensor(arrays[k]) else arrays[k].size, k))
+    left, written = budget, {}
+    for i, name in enumerate(names):
+        a = arrays[name]
+        shape = tuple(a.shape)
+        size = int(np.prod(shape))
+        share = left // (len(names) - i)
+        if size * 8 <= share:
+            v = (a.detach().to(torch.float64).cpu().numpy() if torch.is_tensor(a) else np.asarray(a, np.float64))
+            np.save(os.path.join(outdir, name + ".npy"), v)
+            written[name] = {"shape": list(shape), "sampled": False}
+            left -= v.nbytes
+            continue
+        inner = size // (shape[0] * shape[1])
+        k = min(share // (8 * inner + 16), shape[0] * shape[1])
+        flat = np.sort(np.random.default_rng(0).choice(shape[0] * shape[1], size=k, replace=False))
+        idx = np.stack([flat // shape[1], flat % shape[1]], axis=1)
+        if torch.is_tensor(a):
+            it = torch.from_numpy(idx).to(a.device)
+            v = a[it[:, 0], it[:, 1]].to(torch.float64).cpu().numpy()
+        else:
+            v = np.asarray(a[idx[:, 0], idx[:, 1]], np.float64)
+        np.save(os.path.join(outdir, name + ".npy"), v)
+        np.save(os.path.join(outdir, name + "_index.npy"), idx.astype(np.float64))
+        written[name] = {"shape": list(shape), "sampled": int(k)}
+        left -= v.nbytes + idx.size * 8
+    return written
 
 
 def generate_on_gpu(ctx, args, rank, device, pos, starts):
@@ -524,9 +577,11 @@ def main_iterations(args):
     t0 = time.perf_counter()
     run = cdist.start_iterations(ped, device=local)
     t_setup = time.perf_counter() - t0
-    st0 = run.state()                 # (a collective once iterations have run: every rank calls it)
-    before = synth.dosage_accuracy(ped, st0) if rank == 0 else None
-    del st0
+    before = None
+    if args.full:
+        st0 = run.state()             # (a collective once iterations have run: every rank calls it)
+        before = synth.dosage_accuracy(ped, st0) if rank == 0 else None
+        del st0
     for _ in range(args.warmup):
         run.iteration()
     if world > 1:
@@ -553,6 +608,9 @@ def main_iterations(args):
     os.dup2(saved_stdout, 1)
     os.close(saved_stdout)
     st = run.state()                  # gathers every rank's private records: a collective, outside the timed region
+    if args.dump_outputs and rank == 0:
+        # the parameters the last timed iteration left for its caller (the rows of every record)
+        dump_outputs(args.dump_outputs, {k: st[k] for k in ("allele", "sure", "hw", "variances")})
     if rank == 0:
         plan = run.plan
         out = {
@@ -578,9 +636,9 @@ def main_iterations(args):
             "units_per_s": float(n) * M * args.iterations / dt,
             "iteration_s": per_it, "block": list(run.block), "setup_s": t_setup,
             "scalefactor": st["scalefactor"], "last_hits": st["hits"],
-            "withheld_genotypes_before": before, "withheld_genotypes_after": synth.dosage_accuracy(ped, st),
+            "withheld_genotypes_before": before, "withheld_genotypes_after": synth.dosage_accuracy(ped, st) if args.full else None,
         }
-        if args.cpu_seconds > 0:          # CPU baseline leg: rank 0, after the timed region, at every N
+        if args.full and args.cpu_seconds > 0:          # CPU baseline leg: rank 0, after the timed region, at every N
             try:
                 out["cpu_baseline"] = cpu_baseline_iterations(args)
                 if out["cpu_baseline"]["value"]:
@@ -762,6 +820,9 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller on this rank, before anything below sweeps into the same buffers
+        dump_outputs(args.dump_outputs, {"factors": factors, "loglik": loglik, "dosage": dosage})
     # every rank's own launch time and kernel clock (roofline per rank: the ranks run the same launch on their own GPU)
     sweep_clock_mhz = ctx.sweep_clock()          # the last timed launch's own shader / wall clock stamps
     k_ms = float(np.mean(kernel_ms)) if kernel_ms else float("nan")
@@ -787,38 +848,40 @@ def main():
                 traffic = tj.get("bytes_per_launch")
         except Exception:
             traffic = None
-        # outside the timed region: the outputs are overwritten with NaN and the sweep is run once more -- the waves of a
-        # launch take their jobs from a counter, and a job nobody took would leave the previous step's (equal) values in
-        # place unnoticed.  Every output must be written again and the likelihoods must equal the timed step's to the bit.
-        ll_timed = loglik.clone()
-        for t in (loglik, dosage, factors):
-            t.fill_(float("nan"))
-        ctx.sweep_device(0, n, factors.data_ptr(), loglik.data_ptr(), dosage.data_ptr(),
-                         (capi.FULL_SPILL if args.full_spill else 0) | args.extra_flags)
-        ctx.sync()
-        every_output_rewritten = bool(torch.equal(loglik, ll_timed) and not torch.isnan(dosage).any().item()
-                                      and not torch.isnan(factors).any().item())
-        del ll_timed
-        # size-independent checks on the full output of that step:
-        # every row is a distribution, every likelihood is finite and negative, and the logsumexp
-        # identity between per-mode and total likelihoods holds
-        rs = dosage.sum(dim=2)
-        fmx = factors.max(dim=2, keepdim=True).values
-        lse = (fmx.squeeze(2) + torch.log(torch.exp(factors - fmx).sum(dim=2)))
-        checks = {
-            "rows_sum_to_one": bool(((rs - 1.0).abs() < 1e-9).all().item()),
-            "rows_nonnegative": bool((dosage >= 0).all().item()),
-            "loglik_finite_negative": bool((torch.isfinite(loglik) & (loglik < 0)).all().item()),
-            "logsumexp_identity": bool(((lse - loglik).abs() < 1e-9 * loglik.abs().clamp(min=1.0)).all().item()),
-            "every_output_rewritten": every_output_rewritten,
-        }
-        del rs, fmx, lse
+        checks = None
+        if args.full:
+            # outside the timed region: the outputs are overwritten with NaN and the sweep is run once more -- the waves of a
+            # launch take their jobs from a counter, and a job nobody took would leave the previous step's (equal) values in
+            # place unnoticed.  Every output must be written again and the likelihoods must equal the timed step's to the bit.
+            ll_timed = loglik.clone()
+            for t in (loglik, dosage, factors):
+                t.fill_(float("nan"))
+            ctx.sweep_device(0, n, factors.data_ptr(), loglik.data_ptr(), dosage.data_ptr(),
+                             (capi.FULL_SPILL if args.full_spill else 0) | args.extra_flags)
+            ctx.sync()
+            every_output_rewritten = bool(torch.equal(loglik, ll_timed) and not torch.isnan(dosage).any().item()
+                                          and not torch.isnan(factors).any().item())
+            del ll_timed
+            # size-independent checks on the full output of that step:
+            # every row is a distribution, every likelihood is finite and negative, and the logsumexp
+            # identity between per-mode and total likelihoods holds
+            rs = dosage.sum(dim=2)
+            fmx = factors.max(dim=2, keepdim=True).values
+            lse = (fmx.squeeze(2) + torch.log(torch.exp(factors - fmx).sum(dim=2)))
+            checks = {
+                "rows_sum_to_one": bool(((rs - 1.0).abs() < 1e-9).all().item()),
+                "rows_nonnegative": bool((dosage >= 0).all().item()),
+                "loglik_finite_negative": bool((torch.isfinite(loglik) & (loglik < 0)).all().item()),
+                "logsumexp_identity": bool(((lse - loglik).abs() < 1e-9 * loglik.abs().clamp(min=1.0)).all().item()),
+                "every_output_rewritten": every_output_rewritten,
+            }
+            del rs, fmx, lse
         ll = loglik.cpu().numpy()
         # outside the timed region and after the checks, rank 0 at N = 1: the same sweep with CNF2_MERGE_MODES
         # (exact; the F2's empty F1 parents make the four shift modes that share s0 bit-identical, see DESIGN.md
         # 5b) -- reported next to the headline, never as the headline
         merge_info = None
-        if world == 1 and not args.extra_flags and not args.full_spill and not args.no_merge_probe and args.workload == "f2":
+        if args.full and world == 1 and not args.extra_flags and not args.full_spill and not args.no_merge_probe and args.workload == "f2":
             ns = min(n, 512)
             rows_h = dosage[:ns].clone()
             ll_h = loglik.clone()
@@ -839,7 +902,7 @@ def main():
         # the shader clock this device runs at under a vector load (boxes differ by several per cent and the sweep is
         # issue-bound, so its time tracks the clock); VALU instructions per unit from the SQ counters where they were
         # measured for these kernel sources (profiles/hbm_traffic.json)
-        probe_mhz = ctx.clock_probe()
+        probe_mhz = ctx.clock_probe() if args.full else None
         # the kernel's own stamps when its shader-clock counter really counts shader cycles (a constant-rate counter would
         # read as the wall clock's 100 MHz), else the FMA-loop probe
         clock_mhz = sweep_clock_mhz if sweep_clock_mhz > 500.0 else probe_mhz
@@ -851,7 +914,7 @@ def main():
         except Exception:
             pass
         n_simd = 256 * 4
-        valu_issue_frac = (valu_per_unit * float(n) * M / n_simd * 4.0 / (k_ms * 1e-3 * clock_mhz * 1e6)) if valu_per_unit else None
+        valu_issue_frac = (valu_per_unit * float(n) * M / n_simd * 4.0 / (k_ms * 1e-3 * clock_mhz * 1e6)) if valu_per_unit and clock_mhz else None
         out = {
             "metric": "individual*marker fwd-bwd steps/sec (all 8 shift modes, forward+backward, dosage rows)",
             "value": value, "unit": "individual*marker/s", "n_gpus": world, "steps": args.steps,
@@ -900,14 +963,14 @@ def main():
         }
         if merge_info:
             out["merge_modes"] = merge_info
-        if args.cpu_seconds > 0 and sample is not None:      # CPU baseline leg: rank 0, after the timed region, at every N
+        if args.full and args.cpu_seconds > 0 and sample is not None:      # CPU baseline leg: rank 0, after the timed region, at every N
             try:
                 out["cpu_baseline"] = cpu_baseline(sample, pos, starts, args)
                 out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]      # whole job over the CPU path
             except Exception as e:  # the baseline must never take the GPU line down
                 out["cpu_baseline"] = {"value": None, "unit": "individual*marker/s", "cores": 0, "kind": "port",
                                        "sample": "failed: %r" % (e,)}
-        if not args.no_iteration_probe:
+        if args.full and not args.no_iteration_probe:
             # the other unit of work of the path (BASELINE config 5: whole haplotyping iterations) into the driver-observed
             # line; the headline's context is closed first so that the probe sees the memory a run of its own would
             ctx.close()

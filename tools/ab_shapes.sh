@@ -7,7 +7,7 @@ for w in $wl; do
     for v in "$@"; do
         if [ "$v" = base ]; then lib=$PWD/cnf2freq_amd/libcnf2hip.so; else lib=$PWD/cnf2freq_amd/libcnf2hip_x_$v.so; fi
         log=gpurun_out/abs_${w}_${v}.log
-        CNF2HIP_LIB=$lib timeout -k 10 240 python bench.py --workload $w --steps 3 --warmup 1 --cpu-seconds 0 --no-iteration-probe --no-merge-probe ${AB_EXTRA} \
+        CNF2HIP_LIB=$lib timeout -k 10 240 python bench.py --full --workload $w --steps 3 --warmup 1 --cpu-seconds 0 --no-iteration-probe --no-merge-probe ${AB_EXTRA} \
             > $log 2>&1 || { echo "$w $v failed"; tail -3 $log; continue; }
         python - "$w" "$v" "$log" "${AB_EXTRA}" <<'PY'
 import json, sys

@@ -28,12 +28,12 @@ profile)
     cp $R/gpurun_out/prof_$tag/${tag}_hbm_traffic.json $R/profiles/hbm_traffic.json ;;
 bench)
     cd $R
-    timeout -k 10 400 python bench.py > $o/${tag}_bench_f2.json.log 2> $o/bench_f2.err; echo "f2 exit $?"; summ $o/${tag}_bench_f2.json.log
-    timeout -k 10 300 python bench.py --workload ail --cpu-seconds 0 --no-iteration-probe > $o/${tag}_bench_ail.json.log 2> $o/bench_ail.err; echo "ail exit $?"; summ $o/${tag}_bench_ail.json.log
-    timeout -k 10 300 python bench.py --workload outbred --cpu-seconds 0 --no-iteration-probe > $o/${tag}_bench_outbred.json.log 2> $o/bench_outbred.err; echo "outbred exit $?"; summ $o/${tag}_bench_outbred.json.log
-    timeout -k 10 300 python bench.py --gpus 2 --backend gloo --single-device --inds 2000 --no-iteration-probe > $o/${tag}_bench_rehearsal_2rank_gloo_single_device.json.log 2> $o/bench_2rank.err; echo "2-rank exit $?"; summ $o/${tag}_bench_rehearsal_2rank_gloo_single_device.json.log
-    timeout -k 10 400 python bench.py --workload outbred --iterations 5 --warmup 2 > $o/${tag}_bench_iterations_outbred.json.log 2> $o/bench_it.err; echo "iterations exit $?"; summ $o/${tag}_bench_iterations_outbred.json.log
-    timeout -k 10 400 python bench.py --gpus 2 --backend gloo --single-device --workload outbred --iterations 3 --warmup 1 --inds 2000 > $o/${tag}_bench_iterations_rehearsal_2rank_gloo_single_device.json.log 2> $o/bench_it2.err; echo "2-rank iterations exit $?"; summ $o/${tag}_bench_iterations_rehearsal_2rank_gloo_single_device.json.log ;;
+    timeout -k 10 400 python bench.py --full > $o/${tag}_bench_f2.json.log 2> $o/bench_f2.err; echo "f2 exit $?"; summ $o/${tag}_bench_f2.json.log
+    timeout -k 10 300 python bench.py --full --workload ail --cpu-seconds 0 --no-iteration-probe > $o/${tag}_bench_ail.json.log 2> $o/bench_ail.err; echo "ail exit $?"; summ $o/${tag}_bench_ail.json.log
+    timeout -k 10 300 python bench.py --full --workload outbred --cpu-seconds 0 --no-iteration-probe > $o/${tag}_bench_outbred.json.log 2> $o/bench_outbred.err; echo "outbred exit $?"; summ $o/${tag}_bench_outbred.json.log
+    timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --single-device --inds 2000 --no-iteration-probe > $o/${tag}_bench_rehearsal_2rank_gloo_single_device.json.log 2> $o/bench_2rank.err; echo "2-rank exit $?"; summ $o/${tag}_bench_rehearsal_2rank_gloo_single_device.json.log
+    timeout -k 10 400 python bench.py --full --workload outbred --iterations 5 --warmup 2 > $o/${tag}_bench_iterations_outbred.json.log 2> $o/bench_it.err; echo "iterations exit $?"; summ $o/${tag}_bench_iterations_outbred.json.log
+    timeout -k 10 400 python bench.py --full --gpus 2 --backend gloo --single-device --workload outbred --iterations 3 --warmup 1 --inds 2000 > $o/${tag}_bench_iterations_rehearsal_2rank_gloo_single_device.json.log 2> $o/bench_it2.err; echo "2-rank iterations exit $?"; summ $o/${tag}_bench_iterations_rehearsal_2rank_gloo_single_device.json.log ;;
 iter)
     (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_probe -o probe -- python3 $R/tools/probe_iterations.py 500 2500 4 2 5 > $o/${tag}_iteration_probe.log 2>&1)
     python3 - $o $tag <<'PY'
@@ -52,7 +52,7 @@ cli)
     cat $o/${tag}_cli_5000_individuals_x_10004_markers.log | cut -c1-200 ;;
 c4)
     cd $R
-    timeout -k 10 600 python bench.py --inds 12500 --chroms 80 --steps 2 --warmup 1 --cpu-seconds 0 --no-iteration-probe --no-merge-probe > $o/${tag}_bench_c4_shard_12500x200080.json.log 2> $o/bench_c4.err; echo "c4 exit $?"; summ $o/${tag}_bench_c4_shard_12500x200080.json.log ;;
+    timeout -k 10 600 python bench.py --full --inds 12500 --chroms 80 --steps 2 --warmup 1 --cpu-seconds 0 --no-iteration-probe --no-merge-probe > $o/${tag}_bench_c4_shard_12500x200080.json.log 2> $o/bench_c4.err; echo "c4 exit $?"; summ $o/${tag}_bench_c4_shard_12500x200080.json.log ;;
 config5)
     cd $R
     timeout -k 10 700 python tools/run_config5.py 2500 2500 4 100 600 > $o/${tag}_config5_100_iterations.log 2>&1; echo "config5 exit $?"
