@@ -41,6 +41,7 @@ SYMBOLS = [
     "cnf2_set_grid_reserve", "cnf2_set_batch_jobs", "cnf2_window_table", "cnf2_update_pass_records", "cnf2_exchange_buffer", "cnf2_exchange_download", "cnf2_exchange_upload", "cnf2_exchange_read", "cnf2_exchange_write",
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
+    "cnf2_crossover_rows", "cnf2_sweep_crossovers",
 ]
 
 
@@ -102,6 +103,8 @@ def load():
         L.cnf2_turn_scan.argtypes = [vp, i32, i32, i32, vp]
         L.cnf2_turn_scan_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_state_posterior.argtypes = [vp, i32, i32, vp, C.c_uint32]
+        L.cnf2_crossover_rows.argtypes = [vp, i32, i32, vp]
+        L.cnf2_sweep_crossovers.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -323,6 +326,32 @@ class Context:
         v = np.zeros((mc, 64))
         self._chk(self.L.cnf2_state_posterior(self.h, ind, chrom, _p(v), 0 if ties else NO_TIES), "cnf2_state_posterior")
         return v
+
+    def crossover_rows(self, ind, chrom=0):
+        """[mc][6] crossover posteriors of one individual and chromosome from the alpha/beta store, brute force (the
+        cross-check of sweep_crossovers); column t = state bit t (include/cnf2hip.h: meiosis per column)."""
+        mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])
+        v = np.zeros((mc, 6))
+        self._chk(self.L.cnf2_crossover_rows(self.h, ind, chrom, _p(v)), "cnf2_crossover_rows")
+        return v
+
+    def sweep_crossovers(self, ind_begin=0, ind_end=None, rows=True, full_spill=False, ties_general=False,
+                         static_jobs=False):
+        """cnf2_sweep_crossovers: factors / loglik as sweep(), the per-individual crossover posteriors xo[n][M][6] (None
+        with rows=False), their sum over the range xo_sum[M][6] and the contributing individuals per chromosome."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        xo = np.zeros((n, self.n_markers, 6)) if rows else None
+        xs = np.zeros((self.n_markers, 6))
+        cnt = np.zeros(self.n_chrom, np.int32)
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0))
+        self._chk(self.L.cnf2_sweep_crossovers(self.h, ind_begin, ind_end, _p(factors), _p(loglik),
+                                               _p(xo) if rows else None, _p(xs), _p(cnt), flags),
+                  "cnf2_sweep_crossovers")
+        return dict(factors=factors, loglik=loglik, xo=xo, xo_sum=xs, n_contrib=cnt)
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

@@ -72,6 +72,17 @@ struct cnf2_ctx {
     double* d_scratch = nullptr;     // small parity buffers
     size_t  scratch_cap = 0;
 
+    // crossover posteriors (cnf2_sweep_crossovers)
+    double*  d_xo_f = nullptr;            // likelihoods of the general kernel's crossover pass (not reported)
+    size_t   xo_f_cap = 0;
+    int      xo_blocks_per_cu = 1;        // occupancy of the general kernel's crossover instantiation
+    double*  d_xo = nullptr;              // [n][n_markers][6] per-individual rows (host-output calls that ask for them)
+    size_t   xo_cap = 0;
+    double*  d_xo_sum = nullptr;          // [n_markers][6]
+    size_t   xo_sum_cap = 0;
+    int32_t* d_xo_cnt = nullptr;          // [n_chrom]
+    size_t   xo_cnt_cap = 0;
+
     // batched HOT LOOP 2 (cnf2_sweep_accumulate)
     std::vector<int32_t> slot_rec;   // [n_dous][7] record per window slot (derive_window), -1 none
     int32_t* d_slot_rec = nullptr;
@@ -194,6 +205,7 @@ int cnf2_ctx_create(int device, cnf2_ctx** out)
     ctx->n_cu          = prop.multiProcessorCount;
     ctx->blocks_per_cu = fb_blocks_per_cu();
     ctx->fast_blocks_per_cu = fb_fast_blocks_per_cu();
+    ctx->xo_blocks_per_cu = fb_xo_blocks_per_cu();
     *out = ctx;
     return CNF2_OK;
 }
@@ -221,6 +233,10 @@ void cnf2_ctx_destroy(cnf2_ctx* ctx)
     (void)hipFree(ctx->d_jobnext);
     (void)hipFree(ctx->d_dosage);
     (void)hipFree(ctx->d_scratch);
+    (void)hipFree(ctx->d_xo);
+    (void)hipFree(ctx->d_xo_f);
+    (void)hipFree(ctx->d_xo_sum);
+    (void)hipFree(ctx->d_xo_cnt);
     (void)hipFree(ctx->d_slot_rec);
     (void)hipFree(ctx->d_desc);
     (void)hipFree(ctx->d_rec_empty);
@@ -596,14 +612,25 @@ static std::vector<int> chrom_order(const cnf2_ctx* ctx)
     return o;
 }
 
-int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
-               uint32_t flags)
+// crossover mode of a sweep (cnf2_sweep_crossovers): device outputs of the posteriors
+struct XoArgs {
+    double*  xo;     // [n][n_markers][6] or null
+    double*  sum;    // [n_markers][6], zeroed by the caller
+    int32_t* cnt;    // [n_chrom], zeroed by the caller
+};
+
+// cnf2_sweep, and with xo its crossover mode: the untied windows through the fast kernel's crossover instantiation (one
+// pass: likelihoods and posteriors), the tied ones through the tied kernel without rows (their likelihoods, as cnf2_sweep
+// forms them) and then the general kernel's crossover instantiation (their posteriors)
+static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
+                      uint32_t flags, const XoArgs* xo)
 {
     int rc = ready(ctx);
     if (rc) return rc;
     const int n_all = (int)ctx->windows.size();
     if (ind_begin < 0 || ind_end > n_all || ind_begin > ind_end) return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
-    const bool want_dosage = !(flags & CNF2_NO_DOSAGE);
+    if (xo) flags &= ~(uint32_t)(CNF2_MERGE_MODES | CNF2_XPOSE | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_RAW_DOSAGE);
+    const bool want_dosage = !(flags & CNF2_NO_DOSAGE) && !xo;
     if (!factors_out || !loglik_out || (want_dosage && !dosage_out)) return fail(ctx, CNF2_ERR_ARG, "output pointer is NULL");
     const int n = ind_end - ind_begin;
     if (n == 0) return CNF2_OK;
@@ -760,6 +787,12 @@ int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, d
     p.flags        = (want_dosage ? 0 : KP_NO_DOSAGE) | ((flags & CNF2_RAW_DOSAGE) ? KP_RAW_DOSAGE : 0) |
               ((flags & CNF2_NO_TIES) ? KP_NO_TIES : 0);
     if (flags & CNF2_STATIC_JOBS) p.job_next = nullptr;
+    if (xo) {
+        p.flags  = 0;           // (the crossover instantiations form no rows; KP_NO_DOSAGE would stop them after the forward pass)
+        p.xo     = xo->xo;
+        p.xo_sum = xo->sum;
+        p.xo_cnt = xo->cnt;
+    }
     if (flags & CNF2_LOG_PATHS) {
         if ((rc = ensure(ctx, &ctx->d_pathlog, &ctx->pathlog_cap, nl))) return rc;
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pathlog, 0xff, nl * sizeof(int32_t), ctx->stream));
@@ -782,9 +815,21 @@ int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, d
         // the tile-producer kernel with a pass per tie combination; the general kernel (one lane per table entry, per-marker
         // producer) with the full spill and where asked for
         if (flags & CNF2_FLUSH_TINY) pt.flags |= KP_FLUSH_TINY;
+        if (xo) pt.flags = KP_NO_DOSAGE;    // crossover mode: likelihoods only here, the posteriors from the general kernel below
         if ((flags & CNF2_FULL_SPILL) || (flags & (CNF2_TIES_GENERAL | CNF2_FLUSH_TINY))) launch_fb(pt, grid_gen, false, ctx->stream2);
         else launch_fb_fast_tied(pt, grid_gen, ctx->stream2);
         HIP_TRY(ctx, hipGetLastError());
+        if (xo) {
+            // the general kernel's crossover instantiation in the same spill slots (after the pass above on this stream); its
+            // own likelihoods go to scratch (the ones reported are the tied kernel's); its occupancy is its own
+            KernelParams px = pt;
+            px.factors = ctx->d_xo_f;
+            px.loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
+            int gx = ctx->n_cu * ctx->xo_blocks_per_cu - ctx->reserve_blocks;
+            if (gx < 1) gx = 1;
+            launch_fb_xo(px, gx < grid_gen ? gx : grid_gen, ctx->stream2);
+            HIP_TRY(ctx, hipGetLastError());
+        }
         HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream2));
     }
     if (n_packed > 0) {
@@ -799,7 +844,8 @@ int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, d
     if (n_fast > 0) {
         int gf = (int)((n_fast + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
         p.clock_out = ctx->d_clock;
-        if ((flags & CNF2_XPOSE) && !(flags & CNF2_FULL_SPILL)) launch_fb_fast_xpose(p, gf < grid_fast ? gf : grid_fast, ctx->stream);
+        if (xo) launch_fb_fast_xo(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
+        else if ((flags & CNF2_XPOSE) && !(flags & CNF2_FULL_SPILL)) launch_fb_fast_xpose(p, gf < grid_fast ? gf : grid_fast, ctx->stream);
         else launch_fb_fast(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
         p.clock_out = nullptr;
         HIP_TRY(ctx, hipGetLastError());
@@ -816,6 +862,12 @@ int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, d
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return CNF2_OK;
+}
+
+int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
+               uint32_t flags)
+{
+    return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, dosage_out, flags, nullptr);
 }
 
 int cnf2_last_paths(cnf2_ctx* ctx, int32_t* paths_out, int n)
@@ -1020,6 +1072,66 @@ int cnf2_state_posterior(cnf2_ctx* ctx, int ind, int chrom, double* rows_out, ui
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+int cnf2_crossover_rows(cnf2_ctx* ctx, int ind, int chrom, double* rows_out)
+{
+    if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad crossover_rows arguments");
+    Stage2Params q;
+    double*      d_out = nullptr;
+    int rc = ready(ctx);
+    if (rc) return rc;
+    if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
+    const size_t n = (size_t)(ctx->chromstarts[chrom + 1] - ctx->chromstarts[chrom]) * 6;
+    rc = run_store(ctx, ind, chrom, &q, n, &d_out);
+    if (rc) return rc;
+    launch_crossover_rows(q, d_out, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// one pass of sweep_impl's crossover mode: the sums are zeroed first and added to by the kernels
+int cnf2_sweep_crossovers(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out,
+                          double* xo_out, double* xo_sum_out, int32_t* n_contrib_out, uint32_t flags)
+{
+    int rc = ready(ctx);
+    if (rc) return rc;
+    if (!xo_sum_out || !n_contrib_out) return fail(ctx, CNF2_ERR_ARG, "xo_sum_out and n_contrib_out must not be NULL");
+    if (ind_begin < 0 || ind_end > (int)ctx->windows.size() || ind_begin > ind_end)
+        return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    n   = ind_end - ind_begin;
+    const size_t M = ctx->n_markers, C = ctx->n_chrom;
+    const size_t nx = (size_t)n * M * 6;
+    XoArgs x;
+    x.xo  = xo_out;
+    x.sum = xo_sum_out;
+    x.cnt = n_contrib_out;
+    if (!dev) {
+        if ((rc = ensure(ctx, &ctx->d_xo_sum, &ctx->xo_sum_cap, M * 6))) return rc;
+        if ((rc = ensure(ctx, &ctx->d_xo_cnt, &ctx->xo_cnt_cap, C))) return rc;
+        x.sum = ctx->d_xo_sum;
+        x.cnt = ctx->d_xo_cnt;
+        x.xo  = nullptr;
+        if (xo_out && nx > 0) {
+            if ((rc = ensure(ctx, &ctx->d_xo, &ctx->xo_cap, nx))) return rc;
+            x.xo = ctx->d_xo;
+        }
+    }
+    if ((rc = ensure(ctx, &ctx->d_xo_f, &ctx->xo_f_cap, (size_t)n * C * 9 + 1))) return rc;   // the general kernel's likelihoods
+    HIP_TRY(ctx, hipMemsetAsync(x.sum, 0, M * 6 * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(x.cnt, 0, C * sizeof(int32_t), ctx->stream));
+    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+    if ((rc = sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, &x))) return rc;
+    if (!dev) {
+        HIP_TRY(ctx, hipMemcpyAsync(xo_sum_out, x.sum, M * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(n_contrib_out, x.cnt, C * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (x.xo) HIP_TRY(ctx, hipMemcpyAsync(xo_out, x.xo, nx * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     return CNF2_OK;
 }
 

@@ -83,6 +83,9 @@ struct KernelParams {
     // time -- whichever waves are resident share the list evenly, whatever the jobs' lengths and whenever their blocks
     // got onto the machine; NULL = wave w sweeps jobs w, w + waves, ...
     int*           job_next;
+    double*        xo;         // crossover mode: [n_ind][n_markers][6] per-individual crossover posteriors, or null
+    double*        xo_sum;     // crossover mode: [n_markers][6] summed over the jobs' individuals (f64 atomics)
+    int32_t*       xo_cnt;     // crossover mode: [n_chrom] individuals that contribute (not skipped)
 };
 #define CNF2_LEXP_IGNORED (-2147483647 - 1)   /* shift mode not analysed: CNF2_IGNORED_D */
 #define CNF2_LEXP_DEAD    (-2147483647)       /* no likelihood left: CNF2_MINFACTOR_F */
@@ -198,6 +201,10 @@ void launch_infprobs(const Stage2Params& q, int marker, uint32_t flags, double* 
 void launch_infprobs_rows(const Stage2Params& q, uint32_t flags, double* out, hipStream_t stream);
 void launch_addvariance(const KernelParams& p, int first, int len, double* out, hipStream_t stream);
 void launch_fb(const KernelParams& p, int grid, bool debug_store, hipStream_t stream);
+void launch_fb_xo(const KernelParams& p, int grid, hipStream_t stream);
+void launch_fb_fast_xo(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
+int  fb_xo_blocks_per_cu();
+void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream);
 void launch_fb_fast(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
 void launch_fb_fast_xpose(const KernelParams& p, int grid, hipStream_t stream);
 void launch_fb_packed(const KernelParams& p, int grid, hipStream_t stream);

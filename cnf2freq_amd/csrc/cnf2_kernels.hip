@@ -397,8 +397,125 @@ __device__ __forceinline__ double chain_normaliser(const double (&v)[8], double*
     return inv;
 }
 
+// ------------------------------------------------------------------ crossover posteriors (STOREW == 4)
+// Single Kronecker factors of the transition on one state bit: x' = (1-r) x + r partner (general kernel), or with
+// SC the fast kernel's scaled butterfly x' = x + t partner, t = r / (1-r) (the dropped (1-r) is common to every state).
+template <bool SC, int BIT>
+__device__ __forceinline__ void xo_lane_stage(double (&v)[8], double r)
+{
+    double q[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) q[j] = BIT == 0 ? lane_xor1(v[j]) : BIT == 1 ? lane_flip_b1(v[j]) : lane_flip_b2(v[j]);
+#pragma unroll
+    for (int j = 0; j < 8; j++) v[j] = SC ? fma(r, q[j], v[j]) : (1.0 - r) * v[j] + r * q[j];
+}
+template <bool SC, int BIT>
+__device__ __forceinline__ void xo_reg_stage(double (&v)[8], double r)
+{
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        if (j & (1 << BIT)) continue;
+        const double x = v[j], y = v[j + (1 << BIT)];
+        v[j]              = SC ? fma(r, y, x) : (1.0 - r) * x + r * y;
+        v[j + (1 << BIT)] = SC ? fma(r, x, y) : (1.0 - r) * y + r * x;
+    }
+}
+template <int N>
+__device__ __forceinline__ void xo_copy(double (&d)[N], const double (&s)[N])
+{
+#pragma unroll
+    for (int j = 0; j < N; j++) d[j] = s[j];
+}
+
+// Numerators of the pairwise posterior of one gap m -> m+1 for this lane's chain: n[t] = sum over (g, g') with state bit t
+// flipped of al(g) T(g, g') eb(g'), divided by the flipped factor of bit t (r_t; t_t = r_t / (1-r_t) with SC), which the
+// caller multiplies back.  al = alpha after emission at m, eb = e_{m+1} . beta_{m+1}, both in the sweep's layout (state
+// g = j * 8 + lo).  T is the Kronecker product of six commuting symmetric 2 x 2 factors, so with X_t on bit t
+//     n[t] = < T_A al , X_t T_B eb >   for ANY split A + B of the other five bits.
+// Register bits t = 3..5: B = the three lane bits (shared), A = the two other register bits; lane bits t = 0..2: A = the
+// three register bits (al in place: it is destroyed), B = the two other lane bits.  Two arrays of temporaries.
+// With SC every factor carries the same dropped constant prod (1 - r_u): it cancels against the normaliser <al, T' eb>.
+template <bool SC>
+__device__ __forceinline__ void xo_numerators(double (&al)[8], const double (&eb)[8], double r0, double r1, double (&n)[6])
+{
+    // TYPEGENS = {1,0,0,1,0,0}: bits 0 and 3 use r1 (genrec[1]), the other four r0
+    double R[8], L[8];
+    xo_copy(R, eb);
+    xo_lane_stage<SC, 0>(R, r1);
+    xo_lane_stage<SC, 1>(R, r0);
+    xo_lane_stage<SC, 2>(R, r0);             // R = T_{0,1,2} eb
+    double s3 = 0.0, s4 = 0.0, s5 = 0.0;
+    xo_copy(L, al);
+    xo_reg_stage<SC, 1>(L, r0);
+    xo_reg_stage<SC, 2>(L, r0);              // T_{4,5} al
+#pragma unroll
+    for (int j = 0; j < 8; j++) s3 += L[j] * R[j ^ 1];
+    xo_copy(L, al);
+    xo_reg_stage<SC, 0>(L, r1);
+    xo_reg_stage<SC, 2>(L, r0);              // T_{3,5} al
+#pragma unroll
+    for (int j = 0; j < 8; j++) s4 += L[j] * R[j ^ 2];
+    xo_copy(L, al);
+    xo_reg_stage<SC, 0>(L, r1);
+    xo_reg_stage<SC, 1>(L, r0);              // T_{3,4} al
+#pragma unroll
+    for (int j = 0; j < 8; j++) s5 += L[j] * R[j ^ 4];
+    xo_reg_stage<SC, 0>(al, r1);
+    xo_reg_stage<SC, 1>(al, r0);
+    xo_reg_stage<SC, 2>(al, r0);             // al := T_{3,4,5} al
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+    xo_copy(R, eb);
+    xo_lane_stage<SC, 1>(R, r0);
+    xo_lane_stage<SC, 2>(R, r0);             // T_{1,2} eb
+#pragma unroll
+    for (int j = 0; j < 8; j++) s0 += al[j] * lane_xor1(R[j]);
+    xo_copy(R, eb);
+    xo_lane_stage<SC, 0>(R, r1);
+    xo_lane_stage<SC, 2>(R, r0);             // T_{0,2} eb
+#pragma unroll
+    for (int j = 0; j < 8; j++) s1 += al[j] * lane_flip_b1(R[j]);
+    xo_copy(R, eb);
+    xo_lane_stage<SC, 0>(R, r1);
+    xo_lane_stage<SC, 1>(R, r0);             // T_{0,1} eb
+#pragma unroll
+    for (int j = 0; j < 8; j++) s2 += al[j] * lane_flip_b2(R[j]);
+    n[0] = s0;
+    n[1] = s1;
+    n[2] = s2;
+    n[3] = s3;
+    n[4] = s4;
+    n[5] = s5;
+}
+
+// Crossover posteriors of one gap m -> m+1 from the chain's numerators: xi_t = sum over chains of w_s f_t n_t / D_s
+// (f_t = r_t, or t_t in the scaled form; w_s = the chain's posterior weight, 0 for a chain that does not count; D_s = <al,
+// T eb>, the chain's normaliser at m).  Lanes 0..5 write column t of the individual's row and add it to the interval's sum.
+__device__ __forceinline__ void xo_store(const KernelParams& p, int ind, int m, const double (&nn)[6], double f0, double f1,
+                                         double sw, int lane)
+{
+    const double ft[6] = {f1, f0, f0, f1, f0, f0};
+    double       xt[6];
+#pragma unroll
+    for (int t = 0; t < 6; t++) {
+        const double v = chain_sum(nn[t]);
+        xt[t] = across_chains_sum(sw != 0.0 ? sw * ft[t] * v : 0.0);
+    }
+    const double xv = lane == 0 ? xt[0] : lane == 1 ? xt[1] : lane == 2 ? xt[2] : lane == 3 ? xt[3] : lane == 4 ? xt[4] : xt[5];
+    if (lane < 6) {
+        if (p.xo) p.xo[((size_t)ind * p.n_markers + m) * 6 + lane] = xv;
+        if (xv != 0.0) atomicAdd(&p.xo_sum[(size_t)m * 6 + lane], xv);
+    }
+}
+// the row of the last marker of a chromosome (no gap)
+__device__ __forceinline__ void xo_store_zero(const KernelParams& p, int ind, int m, int lane)
+{
+    if (lane < 6 && p.xo) p.xo[((size_t)ind * p.n_markers + m) * 6 + lane] = 0.0;
+}
+
 // STOREW: 0 = plain sweep; 1 = accumulate mode (posterior weights of every marker into p.wbuf); 2 = turn-scan mode
-// (alpha after emission and beta of every marker with their scales into p.wbuf, CNF2_TURN_ROW doubles per marker)
+// (alpha after emission and beta of every marker with their scales into p.wbuf, CNF2_TURN_ROW doubles per marker);
+// 4 = crossover mode (posterior probability that each state bit flips across each gap into p.xo / p.xo_sum / p.xo_cnt;
+// run with KP_NO_DOSAGE: the dosage rows are not formed)
 template <bool DEBUG_STORE, int STOREW = 0>
 __global__ __launch_bounds__(CNF2_BLOCK) void fb_kernel(KernelParams p)
 {
@@ -502,10 +619,13 @@ __global__ __launch_bounds__(CNF2_BLOCK) void fb_kernel(KernelParams p)
         // weight of this chain in the per-locus row; cnF2freq.cpp:5421 drops modes 40 log units down
         const double ws = (c.active && !skip && !(factor - fs > 40.0)) ? exp(fs - factor) : 0.0;
 
-        if ((p.flags & KP_NO_DOSAGE) && !DEBUG_STORE) continue;
+        if (STOREW == 4 && lane == 0 && !skip) atomicAdd(&p.xo_cnt[jb.chrom], 1);
+        if ((p.flags & KP_NO_DOSAGE) && !DEBUG_STORE && STOREW != 4) continue;
 
         // ---------------------------------------------------------------- backward + rows
         double b[8];
+        double eb[8];                                            // crossover mode: e_{m+1} . beta_{m+1} of the marker after m
+        (void)eb;
 #pragma unroll
         for (int j = 0; j < 8; j++) b[j] = 1.0;                  // cnF2freq.cpp:2111-2114
         double bmant = 1.0;
@@ -527,6 +647,25 @@ __global__ __launch_bounds__(CNF2_BLOCK) void fb_kernel(KernelParams p)
                 for (int j = 0; j < 8; j++)
                     p.dbg_fwbw[(((size_t)s * len + (m - first)) * 3 + 1) * 64 + j * 8 + c.lo] = b[j];
                 if (c.lo == 0) p.dbg_factors[((size_t)s * len + (m - first)) * 3 + 1] = dbg_bfactor;
+            }
+
+            if (STOREW == 4) {
+                // pairwise posterior of the gap m -> m+1 (the last marker has no gap; a gap with rho 0 gives 0).
+                // D = <alpha-minus e, beta> is the chain's normaliser at m, and beta_m = T eb exactly (no rescale between)
+                if (m < last) {
+                    const double* sp = spill + (size_t)(m - first) * 512 + lane;
+                    double        al[8], D = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        al[j] = sp[j * 64] * e[j];
+                        D += al[j] * b[j];
+                    }
+                    D = chain_sum(D);
+                    const double2 r = p.rho[m];
+                    double        nn[6];
+                    xo_numerators<false>(al, eb, r.x, r.y, nn);
+                    xo_store(p, jb.ind, m, nn, r.x, r.y, (D > 0.0 && ws != 0.0) ? ws / D : 0.0, lane);
+                } else xo_store_zero(p, jb.ind, m, lane);
             }
 
             if (!(p.flags & KP_NO_DOSAGE)) {
@@ -631,6 +770,7 @@ __global__ __launch_bounds__(CNF2_BLOCK) void fb_kernel(KernelParams p)
                     if (bdead) dbg_bfactor = (double)CNF2_MINFACTOR_F;
                     else dbg_bfactor += log(sum);
                 }
+                if (STOREW == 4) xo_copy(eb, b);
                 const double2 r = p.rho[m - 1];
                 transition(b, r.x, r.y);
             }
@@ -866,6 +1006,7 @@ struct BwdState {
     bool   bdead;
     double ec[8];         // emission of the even marker of the pair: formed for the odd marker's rebuild, reused when
                           // the even marker itself is reached (it is the next one; measured +2.2 %)
+    double eb[8];         // crossover mode: e . beta of the marker above (the vector the last beta step transitioned)
 };
 
 // HALF: alpha-minus is spilled for every second marker only; the backward pass rebuilds the odd ones
@@ -884,7 +1025,8 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
 {
     static_assert(!XPOSE || (HALF && STOREW == 0), "the transposing variant exists for the plain half-spill sweep");
     // STOREW: 0 plain sweep; 1 accumulate mode (also stores the posterior weights wg); 2 turn-scan mode (stores alpha e, beta
-    // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only)
+    // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only); 4 crossover
+    // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows)
     constexpr bool ROWS = STOREW == 0 || STOREW == 1;      // class sums, restricted tables, tile epilogue, p.dosage
     constexpr bool WG   = STOREW == 1 || STOREW == 3;
     static_assert(!TIED || (!XPOSE && ROWS), "tie combinations only matter to the rows");
@@ -1085,6 +1227,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 p.lexp[e]   = any_alive ? emax : CNF2_LEXP_DEAD;
             }
         }
+        if (STOREW == 4 && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
         if (p.flags & KP_NO_DOSAGE) continue;
 
         // ---------------------------------------------------------------- backward + rows
@@ -1105,6 +1248,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         const double xm  = any_alive ? 1.0 / T : 0.0;
         const int    xe  = -emax;
         const bool   chain_on = alive && !(tmine * 2.3538526683701998e17 < T);        // factor - fs > 40: cnF2freq.cpp:5420-5421
+        const double xo_w     = (STOREW == 4 && chain_on) ? tmine * xm : 0.0;           // crossover mode: P(mode s | data)
         // software pipeline: the spill row (and its reciprocals) is requested one row ahead, straight into
         // the registers it is used from; nothing else in the marker loop is a vector memory operation
         auto load_row = [&](int idx) {
@@ -1132,7 +1276,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             constexpr bool ODD = decltype(odd_tag)::value;
             const int      ml  = m - first;
             double         wj[8];
-            double         aw[STOREW == 2 ? 8 : 1];                 // turn-scan mode: alpha-minus of this marker, unscaled
+            double         aw[STOREW == 2 || STOREW == 4 ? 8 : 1];  // turn-scan / crossover mode: alpha-minus of this marker, unscaled
             const double2 r_m = *(const double2*)(row + TAB_T);     // gap m-1 -> m
             double        inv_m;
             if (ODD) {
@@ -1140,7 +1284,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 // forward step (cnF2freq.cpp:2238-2367); marker m-1 is the previous row of this tile
                 double ep[8];
                 emission_from_row(row - TS, c, ep);
-                if (!TIED) {                       // (TIED: the 16 registers are needed elsewhere; the even marker forms its own)
+                if (!TIED && STOREW != 4) {        // (TIED, crossover mode: the 16 registers are needed elsewhere; the even marker forms its own)
 #pragma unroll
                     for (int j = 0; j < 8; j++) S.ec[j] = ep[j];
                 }
@@ -1150,7 +1294,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 // it is applied to the three class sums (`scale`) instead of to the eight states
                 if (XPOSE) transition_xpose(wj, r_m.x, r_m.y, xb, lane);
                 else transition_scaled(wj, r_m.x, r_m.y);
-                if (STOREW == 2) {
+                if (STOREW == 2 || STOREW == 4) {
 #pragma unroll
                     for (int j = 0; j < 8; j++) aw[j] = wj[j];
                 }
@@ -1158,7 +1302,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 for (int j = 0; j < 8; j++) wj[j] *= S.b[j];
                 inv_m = S.inv_odd;
             } else {
-                if (STOREW == 2) {
+                if (STOREW == 2 || STOREW == 4) {
 #pragma unroll
                     for (int j = 0; j < 8; j++) aw[j] = S.am[j];
                 }
@@ -1286,6 +1430,26 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 }
             }
 #endif
+            if (STOREW == 4) {
+                // crossover mode, gap m -> m+1: al = alpha-minus e (up to a per-chain scalar), S.b = T' eb exactly, so the
+                // normaliser D = <al, S.b> and the flipped masses carry the same scalars and the same dropped (1 - r)
+                // constants; the flipped factor of bit t is t_t = r_t / (1 - r_t) of the gap (p.tq[m])
+                // (the marker's emission is formed here for al and once more below for the beta step: not held across)
+                if (m < last) {
+                    double al[8], D = 0.0;
+                    emission_from_row(row, c, al);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) {
+                        al[j] *= aw[j];
+                        D += al[j] * S.b[j];
+                    }
+                    D = chain_sum(D);
+                    const double2 tq = p.tq[m];
+                    double        nn[6];
+                    xo_numerators<true>(al, S.eb, tq.x, tq.y, nn);
+                    xo_store(p, jb.ind, m, nn, tq.x, tq.y, (D > 0.0 && xo_w != 0.0) ? xo_w / D : 0.0, lane);
+                } else xo_store_zero(p, jb.ind, m, lane);
+            }
             // this marker's own emission is only needed for the beta step: formed here, after the sums, so
             // that it does not occupy registers across them
             double e[8];
@@ -1328,6 +1492,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 const double bsum = scale_chain(S.b, &S.bmant, &S.bexpo, &S.bdead);
                 if (HALF && __ballot(bsum > 0.0 && bsum * CNF2_RESCALE_GUARD < 1.0)) bmask = 1;
             }
+            if (STOREW == 4) xo_copy(S.eb, S.b);
             if (XPOSE) transition_xpose(S.b, r_m.x, r_m.y, xb, lane);
             else transition_scaled(S.b, r_m.x, r_m.y);
         };
@@ -1397,7 +1562,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 }
                 for (; i >= 1; i -= 2) {
                     marker(odd_t(), tab + i * TS, m0 + i);
-                    marker(even_t(), tab + (i - 1) * TS, m0 + i - 1, !TIED);
+                    marker(even_t(), tab + (i - 1) * TS, m0 + i - 1, !TIED && STOREW != 4);
                 }
             } else {
                 for (; i >= 0; i--) marker(even_t(), tab + i * TS, m0 + i);
@@ -1995,6 +2160,85 @@ __global__ __launch_bounds__(64) void state_rows_kernel(Stage2Params q, uint32_t
         acc += s2_fw(q, s, ml, 0, g) * s2_fw(q, s, ml, 1, g) * sc * e;
     }
     out[(size_t)ml * 64 + g] = acc;
+}
+
+
+// Crossover posteriors from the store, brute force (the cross-check of the sweep's crossover mode): one block per gap
+// ml -> ml+1, thread g.  For every admissible shift mode s within 40 log units (cnF2freq.cpp:5421) the pairwise posterior
+// alpha_ml(g) T(g, g') e_{ml+1}(g') beta_{ml+1}(g') is summed with the explicit 64 x 64 transition and normalised by its own
+// total; xi_t = sum_s exp(factors[s] - factor) * (mass with state bit t flipped) / total.  out[len][6]; row len-1 and gaps
+// with rho 0 are zero.
+__global__ __launch_bounds__(64) void crossover_rows_kernel(Stage2Params q, double* out)
+{
+    __shared__ double tab[64];
+    __shared__ double ebs[64];
+    const int    g  = threadIdx.x;
+    const int    ml = blockIdx.x;
+    const Window w  = q.kp.windows[0];
+    const double factor = q.loglik[0];
+    double xi[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const double2 r = q.kp.rho[q.first + ml];
+    const bool skip = isnan(factor) || factor < (double)CNF2_MINFACTOR_F;
+    if (ml + 1 < q.len && !skip && (r.x > 0.0 || r.y > 0.0)) {
+        const int m = q.first + ml + 1;
+        // e_{ml+1} of all 8 modes through the sweep's producer / consumer code (as emission_kernel)
+        LaneCtx c;
+        make_lane(w, g, &c.L);
+        c.row_root   = w.row[0];
+        c.root_attop = (w.flags[0] & SLOT_FOUNDER) != 0;
+        const int sl = g >> 3;
+        c.s0 = sl & 1;
+        c.s1 = (sl >> 1) & 1;
+        c.s2 = (sl >> 2) & 1;
+        c.lo = state_lo(g);
+        c.active  = true;
+        c.n_combo = 1;
+        const Slot root = load_slot(q.kp, c.row_root, m);
+        LineTerms  T;
+        tab[g] = produce_entry(q.kp, c, root, m, &T);
+        __syncthreads();
+        double c0, c1, e[8];
+        root_weights(c, root, &c0, &c1);
+        emission_from_table(tab, c, c0, c1, e);
+        __syncthreads();
+        const double rt[6] = {r.y, r.x, r.x, r.y, r.x, r.x};
+        for (int s = 0; s < 8; s++) {
+            // e of mode s, state g' = j * 8 + lo sits in lane s * 8 + (the lane holding lo), register j
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if (sl == s) ebs[j * 8 + c.lo] = e[j];
+            __syncthreads();
+            const double eg = ebs[g];
+            __syncthreads();
+            ebs[g] = eg * s2_fw(q, s, ml + 1, 1, g);
+            __syncthreads();
+            const bool use = !((s & w.shiftignore) || s >= w.shiftend) && !(factor - q.factors[s] > 40.0);
+            if (use) {
+                const double a = s2_fw(q, s, ml, 2, g);
+                double acc[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, tot = 0.0;
+                for (int g2 = 0; g2 < 64; g2++) {
+                    const int d = g ^ g2;
+                    double    tr = 1.0;
+#pragma unroll
+                    for (int t = 0; t < 6; t++) tr *= ((d >> t) & 1) ? rt[t] : 1.0 - rt[t];
+                    const double v = a * tr * ebs[g2];
+                    tot += v;
+#pragma unroll
+                    for (int t = 0; t < 6; t++)
+                        if ((d >> t) & 1) acc[t] += v;
+                }
+                tot = across_chains_sum(chain_sum(tot));
+                const double ws = exp(q.factors[s] - factor);
+#pragma unroll
+                for (int t = 0; t < 6; t++) {
+                    const double v = across_chains_sum(chain_sum(acc[t]));
+                    if (tot > 0.0) xi[t] += ws * v / tot;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (g < 6) out[(size_t)ml * 6 + g] = xi[g];
 }
 
 
@@ -3637,6 +3881,19 @@ void launch_fb_w(const KernelParams& p, int grid, hipStream_t stream)
 {
     hipLaunchKernelGGL((fb_kernel<false, 1>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
 }
+void launch_fb_fast_xo(const KernelParams& p, int grid, bool half_spill, hipStream_t stream)
+{
+    zero_job_counter(p, stream);
+    if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
+    else hipLaunchKernelGGL((fb_fast_kernel<false, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
+    launch_likelihood_logs(p, stream);
+}
+int fb_xo_blocks_per_cu()
+{
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fb_kernel<false, 4>, CNF2_BLOCK, 0) != hipSuccess) n = 1;
+    return n < 1 ? 1 : n;
+}
 void launch_fb_fast_ab(const KernelParams& p, int grid, hipStream_t stream)
 {
     zero_job_counter(p, stream);
@@ -4016,6 +4273,16 @@ void launch_fb(const KernelParams& p, int grid, bool debug_store, hipStream_t st
 {
     if (debug_store) hipLaunchKernelGGL(fb_kernel<true>, dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
     else hipLaunchKernelGGL(fb_kernel<false>, dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
+}
+
+void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(crossover_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
+}
+
+void launch_fb_xo(const KernelParams& p, int grid, hipStream_t stream)
+{
+    hipLaunchKernelGGL((fb_kernel<false, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
 }
 
 void launch_emission(const KernelParams& p, int ind, int marker, double* out, hipStream_t stream)

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "cnf2_engine.h"
+#include "cnf2_remap.h"
 
 using namespace cnf2host;
 
@@ -240,6 +241,26 @@ int cnf2h_get_passes(cnf2h_run* run, int32_t* hits, double* haplobase, double* h
     if (!run) return -2;
     if (hits) std::copy(run->E->pass_hits().begin(), run->E->pass_hits().end(), hits);
     if (haplobase || haplocount) return guarded([&] { run->E->accumulators(haplobase, haplocount); });
+    return 0;
+}
+
+int cnf2h_map_mstep(const double* pos, int n_markers, const int32_t* chromstarts, int n_chrom, const double* genrec,
+                    const double* xo_sum, const int32_t* n_contrib, double* new_pos)
+{
+    if (!pos || !chromstarts || !xo_sum || !n_contrib || !new_pos || n_markers <= 0 || n_chrom <= 0) return -2;
+    if (chromstarts[0] != 0 || chromstarts[n_chrom] != n_markers) return -2;
+    cnf2host::map_mstep(pos, n_markers, chromstarts, n_chrom, genrec, xo_sum, n_contrib, new_pos);
+    return 0;
+}
+
+int cnf2h_write_map(const char* path, const double* pos, int n_markers, const int32_t* chromstarts, int n_chrom)
+{
+    if (!path || !pos || !chromstarts || n_markers <= 0 || n_chrom <= 0) return -2;
+    std::string err;
+    if (!cnf2host::write_map_checked(path, pos, n_markers, chromstarts, n_chrom, &err)) {
+        g_err = err;
+        return -3;
+    }
     return 0;
 }
 

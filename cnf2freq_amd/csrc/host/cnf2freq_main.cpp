@@ -1,7 +1,7 @@
 // cnf2freq_main.cpp -- drop-in command line for the PlantImpute invocation of the reference
 // (demo.sh:37):
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
-//            [--deserialize F] [--gpus N]
+//            [--deserialize F] [--gpus N] [--crossovers F] [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
 // haplotyping sweep (doit) before its dump.  Rows of the last round go to --output, earlier ones to stdout; every
@@ -14,6 +14,12 @@
 // files, forks N ranks -- before anything has touched a GPU --, rank r takes GPU r, its block of the analysed individuals and
 // the records it owns (cnf2_partition.h), the ranks exchange through shared memory (cnf2_shm_transport.h), and rank 0
 // writes ONE output in the order of a single-GPU run: the other ranks' rows reach it through files in --tmppath.
+//
+// --crossovers F / --remap F (not flags of the reference, whose DOREMAPDISTANCES path is compiled out): after the last round,
+// the crossover posteriors of every analysed individual (cnf2_sweep_crossovers; per chromosome and individual "name:chrom",
+// one "%.5lf" tab-separated line of the 6 meioses per marker, a blank line) and / or K EM steps of the marker map
+// (cnf2_remap.h) written as a .map file that is read back and checked.  The summed log-likelihood of every step goes to
+// stderr; --output is the same with or without these flags.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
 // has no compute path of its own and fails if no GPU is present.  Out of scope: the toulbar2
@@ -35,6 +41,7 @@
 #include "cnf2_engine.h"
 #include "cnf2_readers.h"
 #include "cnf2_rccl_transport.h"
+#include "cnf2_remap.h"
 #include "cnf2_shm_transport.h"
 #include "cnf2hip.h"
 
@@ -59,6 +66,10 @@ struct Options {
     std::string transport;               // --transport rccl|shm: what the ranks exchange through (default: rccl when every rank has
                                          // a GPU of its own, shm -- staging through a shared region on the host -- with --single-device)
     bool        rccl_selftest = false;   // --rccl-selftest: the RCCL transport's collectives with a world of one on GPU 0, then stop
+    std::string crossovers;              // --crossovers F: crossover posteriors of the last round's state
+    std::string remap;                   // --remap F: the map after --remap-iterations EM steps
+    int         remap_iterations = 1;
+    bool        remap_iterations_set = false;
 };
 
 static bool parse(int argc, char** argv, Options& o)
@@ -101,6 +112,12 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--single-device") o.single_device = true;
         else if (a == "--transport") o.transport = val();
         else if (a == "--rccl-selftest") o.rccl_selftest = true;
+        else if (a == "--crossovers") o.crossovers = val();
+        else if (a == "--remap") o.remap = val();
+        else if (a == "--remap-iterations") {
+            o.remap_iterations = atoi(val().c_str());
+            o.remap_iterations_set = true;
+        }
         else {
             fprintf(stderr, "unsupported option %s (this build covers the PlantImpute path only)\n", a.c_str());
             return false;
@@ -108,6 +125,8 @@ static bool parse(int argc, char** argv, Options& o)
     }
     return true;
 }
+
+static void crossovers_and_remap(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -193,6 +212,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
         fflush(out);
     }
     if (out != stdout) fclose(out);
+    if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
         if (world > 1) return 4;                          // the parent stops the other ranks and aborts
@@ -200,6 +220,58 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     }
     cnf2_ctx_destroy(ctx);
     return 0;
+}
+
+// summed window log-likelihood of a sweep (the quantity an EM step of the map cannot decrease): loglik of every
+// (individual, chromosome) that is not skipped (cnF2freq.cpp:5403)
+static double summed_loglik(const std::vector<double>& ll)
+{
+    double s = 0.0;
+    for (double v : ll)
+        if (!(v != v) && !(v < (double)CNF2_MINFACTOR)) s += v;
+    return s;
+}
+
+// --crossovers / --remap after the last round (single GPU): the context holds the last round's rows
+static void crossovers_and_remap(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    std::vector<double>  f((size_t)N * C * 8), ll((size_t)N * C), xs((size_t)M * 6);
+    std::vector<int32_t> cnt(C);
+    auto sweep = [&](double* xo) {
+        if (cnf2_sweep_crossovers(ctx, 0, N, f.data(), ll.data(), xo, xs.data(), cnt.data(), 0) != CNF2_OK)
+            throw EngineError(CNF2_ERR_STATE, std::string("cnf2_sweep_crossovers: ") + cnf2_last_error(ctx));
+    };
+    if (!opt.crossovers.empty()) {
+        std::vector<double> xo((size_t)N * M * 6);
+        sweep(xo.data());
+        FILE* out = fopen(opt.crossovers.c_str(), "w");
+        if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.crossovers);
+        for (int c = 0; c < C; c++)
+            for (int j = 0; j < N; j++) {
+                fprintf(out, "%s:%d\n", P.inds[P.dous[j]].name.c_str(), c + 1);
+                for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                    const double* r = &xo[((size_t)j * M + m) * 6];
+                    fprintf(out, "%.5lf\t%.5lf\t%.5lf\t%.5lf\t%.5lf\t%.5lf\n", r[0], r[1], r[2], r[3], r[4], r[5]);
+                }
+                fprintf(out, "\n");
+            }
+        if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.crossovers);
+    }
+    if (opt.remap.empty()) return;
+    std::vector<double> pos(P.pos.begin(), P.pos.end()), npos(M);
+    const double genrec[3] = {-0.02, -0.02, -0.02};       // what the engine uploads (cnf2_upload_map with NULL)
+    for (int k = 0; k <= opt.remap_iterations; k++) {
+        sweep(nullptr);
+        fprintf(stderr, "remap step %d: summed loglik %.10f\n", k, summed_loglik(ll));
+        if (k == opt.remap_iterations) break;
+        map_mstep(pos.data(), M, P.chromstarts.data(), C, genrec, xs.data(), cnt.data(), npos.data());
+        pos.swap(npos);
+        if (cnf2_upload_map(ctx, pos.data(), M, P.chromstarts.data(), C, nullptr) != CNF2_OK)
+            throw EngineError(CNF2_ERR_STATE, std::string("cnf2_upload_map: ") + cnf2_last_error(ctx));
+    }
+    std::string err;
+    if (!write_map_checked(opt.remap.c_str(), pos.data(), M, P.chromstarts.data(), C, &err)) throw EngineError(CNF2_ERR_STATE, err);
 }
 
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
@@ -296,6 +368,18 @@ int main(int argc, char** argv)
     }
     if (opt.gpus < 1 || opt.gpus > 64) {
         fprintf(stderr, "--gpus must be between 1 and 64\n");
+        return 2;
+    }
+    if (opt.gpus > 1 && (!opt.crossovers.empty() || !opt.remap.empty())) {
+        fprintf(stderr, "--crossovers and --remap need a single GPU (--gpus 1): their sums are not reduced across ranks\n");
+        return 2;
+    }
+    if (opt.remap_iterations_set && opt.remap.empty()) {
+        fprintf(stderr, "--remap-iterations needs --remap FILE\n");
+        return 2;
+    }
+    if (opt.remap_iterations < 1) {
+        fprintf(stderr, "--remap-iterations must be at least 1\n");
         return 2;
     }
     // main() trims dous only after postmarkerdata (cnF2freq.cpp:8083, 8124); the analysed list is fixed at upload here,

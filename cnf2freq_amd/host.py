@@ -12,7 +12,7 @@ LIB_PATH = os.environ.get("CNF2HOST_LIB") or os.path.join(_HERE, "libcnf2host.so
 
 SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_destroy", "cnf2h_last_error", "cnf2h_postmarkerdata", "cnf2h_iteration",
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
-           "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes"]
+           "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -51,12 +51,40 @@ def load():
         L.cnf2h_dump.argtypes = [vp, C.c_char_p, i32]
         L.cnf2h_deserialize.argtypes = [vp, C.c_char_p]
         L.cnf2h_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_map_mstep.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
+        L.cnf2h_write_map.argtypes = [C.c_char_p, vp, i32, vp, i32]
         _lib = L
     return _lib
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def map_mstep(pos, chromstarts, xo_sum, n_contrib, genrec=None):
+    """cnf2h_map_mstep (include/cnf2host.h): new marker positions from the summed crossover posteriors of a sweep
+    (Context.sweep_crossovers: xo_sum[M][6], n_contrib[n_chrom]).  CPU only."""
+    L = load()
+    pos = np.ascontiguousarray(pos, np.float64)
+    cs = np.ascontiguousarray(chromstarts, np.int32)
+    xs = np.ascontiguousarray(xo_sum, np.float64).reshape(len(pos), 6)
+    cnt = np.ascontiguousarray(n_contrib, np.int32)
+    g = None if genrec is None else np.ascontiguousarray(genrec, np.float64)
+    out = np.zeros_like(pos)
+    rc = L.cnf2h_map_mstep(_p(pos), len(pos), _p(cs), len(cs) - 1, None if g is None else _p(g), _p(xs), _p(cnt), _p(out))
+    if rc != 0:
+        raise RuntimeError("cnf2h_map_mstep failed (%d)" % rc)
+    return out
+
+
+def write_map(path, pos, chromstarts):
+    """cnf2h_write_map: the map as a .map file, read back and checked (RuntimeError if it does not round-trip)."""
+    L = load()
+    pos = np.ascontiguousarray(pos, np.float64)
+    cs = np.ascontiguousarray(chromstarts, np.int32)
+    rc = L.cnf2h_write_map(os.fsencode(path), _p(pos), len(pos), _p(cs), len(cs) - 1)
+    if rc != 0:
+        raise RuntimeError("cnf2h_write_map failed (%d): %s" % (rc, (L.cnf2h_last_error() or b"").decode()))
 
 
 class Run:

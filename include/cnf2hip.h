@@ -221,6 +221,40 @@ int cnf2_infprobs(cnf2_ctx *ctx, int ind, int chrom, int marker, double *inf_out
  *                       a path depends on one line of descent only, the other line enters as its restricted
  *                       total) instead of the 128-path fan-out. */
 int cnf2_infprobs_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out, uint32_t flags);
+/*  cnf2_crossover_rows  rows_out[mc][6]: the crossover posteriors of cnf2_sweep_crossovers for one individual and
+ *                       chromosome, from the store by brute force (explicit 64 x 64 transition, one thread per state):
+ *                       the cross-check of the sweep's fused form. */
+int cnf2_crossover_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
+
+/* Crossover posteriors (Baum-Welch pairwise posterior of the transition; not a port of the reference's disabled
+ * DOREMAPDISTANCES path).  For analysed individual i, marker m and state bit t, xi_t(m) = posterior probability that
+ * bit t differs between markers m and m+1, given the individual's window data, summed over the shift modes with the
+ * weights and the 40-log-unit rule of the dosage rows (cnF2freq.cpp:5421).  Column t is one meiosis:
+ *   0  the first parent's meiosis that made the individual    (genrec[1], TYPEGENS = 1)
+ *   1  the first parent's first parent's meiosis that made the first parent   (genrec[0])
+ *   2  the first parent's second parent's meiosis that made the first parent  (genrec[0])
+ *   3  the second parent's meiosis that made the individual   (genrec[1])
+ *   4  the second parent's first parent's meiosis that made the second parent (genrec[0])
+ *   5  the second parent's second parent's meiosis that made the second parent (genrec[0])
+ * ("first" / "second" parent in the order of the pedigree's par columns; bits 1-2 and 4-5 trace the grandparents.)
+ * xi = 0 where pos[m+1] - pos[m] <= 0, at the last marker of every chromosome and for a skipped individual
+ * (loglik <= CNF2_MINFACTOR or NaN).  xi depends on alpha / beta only: ties, CNF2_NO_TIES and ignoreflag2 do not enter.
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal (the same forward passes)
+ *   xo_out        [n][n_markers][6] per individual, or NULL
+ *   xo_sum_out    [n_markers][6] the same summed over the individuals of the range (reduced on the device, f64 atomics:
+ *                 equal to the host sum of xo_out to rounding, not to the bit)
+ *   n_contrib_out [n_chrom] (int32) individuals of the range with a likelihood on that chromosome (not skipped)
+ * Outputs are overwritten, not accumulated; a range split [a,b) + [b,c) adds up to [a,c).
+ * One pass: untied windows through the fast kernel's crossover instantiation (likelihoods and posteriors together), tied
+ * windows through the tied kernel without rows (likelihoods) and the general kernel's crossover instantiation.
+ * Flags: CNF2_OUT_DEVICE (all five pointers are device pointers; xo_sum_out / n_contrib_out must be ordinary device
+ * memory as for CNF2_ACC_DEVICE), CNF2_STATIC_JOBS, CNF2_FULL_SPILL (fast kernel with the full spill) and
+ * CNF2_TIES_GENERAL (tied likelihoods from the general kernel) as in cnf2_sweep: same values to rounding.
+ * CNF2_MERGE_MODES, CNF2_XPOSE and the dosage flags are ignored.  The call synchronises the context's stream once (the
+ * job list), also with CNF2_OUT_DEVICE.  To re-estimate the map, call cnf2_upload_map again with new positions
+ * (same marker count and chromstarts: the rows stay) and sweep again; cnf2h_map_mstep of cnf2host.h is the M-step. */
+int cnf2_sweep_crossovers(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out,
+                          double *xo_out, double *xo_sum_out, int32_t *n_contrib_out, uint32_t flags);
 
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU

@@ -108,6 +108,20 @@ int cnf2h_deserialize(cnf2h_run *run, const char *path);
 int cnf2h_get_state(cnf2h_run *run, uint8_t *allele, double *sure, double *hw, int32_t *descendants, int32_t *children,
                     double *variances, double *scalefactor, int32_t *last_hits);
 
+/* Map M-step from summed crossover posteriors (cnf2_sweep_crossovers of cnf2hip.h: xo_sum[n_markers][6],
+ * n_contrib[n_chrom]).  For every interval m -> m+1 with pos[m+1] - pos[m] > 0 and a contributing individual, the length d
+ * that maximises sum_t S_t log r_t(d) + (C - S_t) log(1 - r_t(d)), r_t(d) = 0.5 (1 - exp(genrec[TYPEGENS[t]] d)),
+ * TYPEGENS = {1,0,0,1,0,0}: closed form r = sum S / 6C when genrec[0] == genrec[1], a safeguarded Newton iteration
+ * otherwise.  r is clamped to [1e-9, 0.499] (an interval neither closes -- a zero-length gap is frozen -- nor opens to
+ * infinity).  Other intervals keep their length; new_pos[n_markers] starts every chromosome at its old first position.
+ * genrec NULL = {-0.02, -0.02, -0.02}.  With the summed window log-likelihood of the sweep this is an exact EM step. */
+int cnf2h_map_mstep(const double *pos, int n_markers, const int32_t *chromstarts, int n_chrom, const double *genrec,
+                    const double *xo_sum, const int32_t *n_contrib, double *new_pos);
+/* the map in the .map format the readers parse (one position per line), read back and compared: -3 (text in
+ * cnf2h_last_error) when it does not give the same positions and chromstarts, e.g. a chromosome grown past the next one's
+ * first position (a new chromosome starts where a value decreases) */
+int cnf2h_write_map(const char *path, const double *pos, int n_markers, const int32_t *chromstarts, int n_chrom);
+
 #ifdef __cplusplus
 }
 #endif
