@@ -41,7 +41,7 @@ SYMBOLS = [
     "cnf2_set_grid_reserve", "cnf2_set_batch_jobs", "cnf2_window_table", "cnf2_update_pass_records", "cnf2_exchange_buffer", "cnf2_exchange_download", "cnf2_exchange_upload", "cnf2_exchange_read", "cnf2_exchange_write",
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
-    "cnf2_crossover_rows", "cnf2_sweep_crossovers",
+    "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi",
 ]
 
 
@@ -105,6 +105,7 @@ def load():
         L.cnf2_state_posterior.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_crossover_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_sweep_crossovers.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_sweep_viterbi.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -352,6 +353,25 @@ class Context:
                                                _p(xo) if rows else None, _p(xs), _p(cnt), flags),
                   "cnf2_sweep_crossovers")
         return dict(factors=factors, loglik=loglik, xo=xo, xo_sum=xs, n_contrib=cnt)
+
+    def sweep_viterbi(self, ind_begin=0, ind_end=None, full_spill=False, ties_general=False, static_jobs=False):
+        """cnf2_sweep_viterbi: factors / loglik as sweep(), logmax[n][C][8], the MAP state path state[n][M] (uint8, 0xFF
+        where skipped), the MAP shift mode shift[n][C] (-1 where skipped) and path_logpost[n][C] = logmax[s*] - loglik,
+        the log posterior probability of the decoded (mode, path) (NaN where skipped)."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        logmax = np.zeros((n, self.n_chrom, 8))
+        state = np.zeros((n, self.n_markers), np.uint8)
+        shift = np.zeros((n, self.n_chrom), np.int32)
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0))
+        self._chk(self.L.cnf2_sweep_viterbi(self.h, ind_begin, ind_end, _p(factors), _p(loglik), _p(logmax),
+                                            _p(state), _p(shift), flags), "cnf2_sweep_viterbi")
+        best = np.take_along_axis(logmax, np.maximum(shift, 0)[..., None], axis=2)[..., 0]
+        path_logpost = np.where(shift >= 0, best - loglik, np.nan)
+        return dict(factors=factors, loglik=loglik, logmax=logmax, state=state, shift=shift, path_logpost=path_logpost)
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

@@ -73,7 +73,7 @@ struct cnf2_ctx {
     size_t  scratch_cap = 0;
 
     // crossover posteriors (cnf2_sweep_crossovers)
-    double*  d_xo_f = nullptr;            // likelihoods of the general kernel's crossover pass (not reported)
+    double*  d_xo_f = nullptr;            // likelihoods of the second pass over tied windows (crossover or Viterbi; not reported)
     size_t   xo_f_cap = 0;
     int      xo_blocks_per_cu = 1;        // occupancy of the general kernel's crossover instantiation
     double*  d_xo = nullptr;              // [n][n_markers][6] per-individual rows (host-output calls that ask for them)
@@ -82,6 +82,14 @@ struct cnf2_ctx {
     size_t   xo_sum_cap = 0;
     int32_t* d_xo_cnt = nullptr;          // [n_chrom]
     size_t   xo_cnt_cap = 0;
+
+    // Viterbi decoding (cnf2_sweep_viterbi), host-output calls
+    double*  d_vit_lm = nullptr;          // [n][n_chrom][8]
+    size_t   vit_lm_cap = 0;
+    uint8_t* d_vit_st = nullptr;          // [n][n_markers]
+    size_t   vit_st_cap = 0;
+    int32_t* d_vit_sh = nullptr;          // [n][n_chrom]
+    size_t   vit_sh_cap = 0;
 
     // batched HOT LOOP 2 (cnf2_sweep_accumulate)
     std::vector<int32_t> slot_rec;   // [n_dous][7] record per window slot (derive_window), -1 none
@@ -237,6 +245,9 @@ void cnf2_ctx_destroy(cnf2_ctx* ctx)
     (void)hipFree(ctx->d_xo_f);
     (void)hipFree(ctx->d_xo_sum);
     (void)hipFree(ctx->d_xo_cnt);
+    (void)hipFree(ctx->d_vit_lm);
+    (void)hipFree(ctx->d_vit_st);
+    (void)hipFree(ctx->d_vit_sh);
     (void)hipFree(ctx->d_slot_rec);
     (void)hipFree(ctx->d_desc);
     (void)hipFree(ctx->d_rec_empty);
@@ -618,19 +629,26 @@ struct XoArgs {
     double*  sum;    // [n_markers][6], zeroed by the caller
     int32_t* cnt;    // [n_chrom], zeroed by the caller
 };
+// Viterbi mode of a sweep (cnf2_sweep_viterbi): device outputs
+struct VitArgs {
+    double*  logmax;   // [n][n_chrom][8]
+    uint8_t* state;    // [n][n_markers]
+    int32_t* shift;    // [n][n_chrom]
+};
 
 // cnf2_sweep, and with xo its crossover mode: the untied windows through the fast kernel's crossover instantiation (one
 // pass: likelihoods and posteriors), the tied ones through the tied kernel without rows (their likelihoods, as cnf2_sweep
-// forms them) and then the general kernel's crossover instantiation (their posteriors)
+// forms them) and then the general kernel's crossover instantiation (their posteriors).  With vit its Viterbi mode: the same
+// routing, with the fast kernel's Viterbi instantiation in place of both crossover instantiations
 static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
-                      uint32_t flags, const XoArgs* xo)
+                      uint32_t flags, const XoArgs* xo, const VitArgs* vit = nullptr)
 {
     int rc = ready(ctx);
     if (rc) return rc;
     const int n_all = (int)ctx->windows.size();
     if (ind_begin < 0 || ind_end > n_all || ind_begin > ind_end) return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
-    if (xo) flags &= ~(uint32_t)(CNF2_MERGE_MODES | CNF2_XPOSE | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_RAW_DOSAGE);
-    const bool want_dosage = !(flags & CNF2_NO_DOSAGE) && !xo;
+    if (xo || vit) flags &= ~(uint32_t)(CNF2_MERGE_MODES | CNF2_XPOSE | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_RAW_DOSAGE);
+    const bool want_dosage = !(flags & CNF2_NO_DOSAGE) && !xo && !vit;
     if (!factors_out || !loglik_out || (want_dosage && !dosage_out)) return fail(ctx, CNF2_ERR_ARG, "output pointer is NULL");
     const int n = ind_end - ind_begin;
     if (n == 0) return CNF2_OK;
@@ -793,6 +811,12 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         p.xo_sum = xo->sum;
         p.xo_cnt = xo->cnt;
     }
+    if (vit) {
+        p.flags      = KP_NO_DOSAGE;
+        p.vit_logmax = vit->logmax;
+        p.vit_state  = vit->state;
+        p.vit_shift  = vit->shift;
+    }
     if (flags & CNF2_LOG_PATHS) {
         if ((rc = ensure(ctx, &ctx->d_pathlog, &ctx->pathlog_cap, nl))) return rc;
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pathlog, 0xff, nl * sizeof(int32_t), ctx->stream));
@@ -815,7 +839,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         // the tile-producer kernel with a pass per tie combination; the general kernel (one lane per table entry, per-marker
         // producer) with the full spill and where asked for
         if (flags & CNF2_FLUSH_TINY) pt.flags |= KP_FLUSH_TINY;
-        if (xo) pt.flags = KP_NO_DOSAGE;    // crossover mode: likelihoods only here, the posteriors from the general kernel below
+        if (xo || vit) pt.flags = KP_NO_DOSAGE;    // crossover / Viterbi mode: likelihoods only here, the rest from the pass below
         if ((flags & CNF2_FULL_SPILL) || (flags & (CNF2_TIES_GENERAL | CNF2_FLUSH_TINY))) launch_fb(pt, grid_gen, false, ctx->stream2);
         else launch_fb_fast_tied(pt, grid_gen, ctx->stream2);
         HIP_TRY(ctx, hipGetLastError());
@@ -828,6 +852,17 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
             int gx = ctx->n_cu * ctx->xo_blocks_per_cu - ctx->reserve_blocks;
             if (gx < 1) gx = 1;
             launch_fb_xo(px, gx < grid_gen ? gx : grid_gen, ctx->stream2);
+            HIP_TRY(ctx, hipGetLastError());
+        }
+        if (vit) {
+            // the fast kernel's Viterbi instantiation over the tied jobs in the same spill slots (after the pass above on this
+            // stream; the forward pass and the max-product recursion do not see the tie rule); its likelihoods go to scratch
+            KernelParams px = pt;
+            px.factors = ctx->d_xo_f;
+            px.loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
+            int gx = ctx->n_cu * ctx->fast_blocks_per_cu - ctx->reserve_blocks;
+            if (gx < 1) gx = 1;
+            launch_fb_fast_vit(px, gx < grid_gen ? gx : grid_gen, !(flags & CNF2_FULL_SPILL), ctx->stream2);
             HIP_TRY(ctx, hipGetLastError());
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream2));
@@ -845,6 +880,19 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         int gf = (int)((n_fast + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
         p.clock_out = ctx->d_clock;
         if (xo) launch_fb_fast_xo(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
+        else if (vit) {
+            // the likelihoods from cnf2_sweep's own launch without rows (the Viterbi instantiation runs the same recursion,
+            // but compiled without the backward pass it does not round every job's factors the same way: DESIGN.md 8c), then
+            // the Viterbi instantiation in the same spill slots with its likelihoods to scratch
+            KernelParams pl = p;
+            pl.flags = KP_NO_DOSAGE;
+            launch_fb_fast(pl, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
+            KernelParams pv = p;
+            pv.clock_out = nullptr;
+            pv.factors   = ctx->d_xo_f;
+            pv.loglik    = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
+            launch_fb_fast_vit(pv, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
+        }
         else if ((flags & CNF2_XPOSE) && !(flags & CNF2_FULL_SPILL)) launch_fb_fast_xpose(p, gf < grid_fast ? gf : grid_fast, ctx->stream);
         else launch_fb_fast(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
         p.clock_out = nullptr;
@@ -1130,6 +1178,43 @@ int cnf2_sweep_crossovers(cnf2_ctx* ctx, int ind_begin, int ind_end, double* fac
         HIP_TRY(ctx, hipMemcpyAsync(xo_sum_out, x.sum, M * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(n_contrib_out, x.cnt, C * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         if (x.xo) HIP_TRY(ctx, hipMemcpyAsync(xo_out, x.xo, nx * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return CNF2_OK;
+}
+
+// one pass of sweep_impl's Viterbi mode
+int cnf2_sweep_viterbi(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* logmax_out,
+                       uint8_t* state_out, int32_t* shift_out, uint32_t flags)
+{
+    int rc = ready(ctx);
+    if (rc) return rc;
+    if (!logmax_out || !state_out || !shift_out) return fail(ctx, CNF2_ERR_ARG, "logmax_out, state_out and shift_out must not be NULL");
+    if (ind_begin < 0 || ind_end > (int)ctx->windows.size() || ind_begin > ind_end)
+        return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    n   = ind_end - ind_begin;
+    if (n == 0) return CNF2_OK;
+    const size_t nlm = (size_t)n * ctx->n_chrom * 8, nst = (size_t)n * ctx->n_markers, nsh = (size_t)n * ctx->n_chrom;
+    VitArgs v;
+    v.logmax = logmax_out;
+    v.state  = state_out;
+    v.shift  = shift_out;
+    if (!dev) {
+        if ((rc = ensure(ctx, &ctx->d_vit_lm, &ctx->vit_lm_cap, nlm))) return rc;
+        if ((rc = ensure(ctx, &ctx->d_vit_st, &ctx->vit_st_cap, nst))) return rc;
+        if ((rc = ensure(ctx, &ctx->d_vit_sh, &ctx->vit_sh_cap, nsh))) return rc;
+        v.logmax = ctx->d_vit_lm;
+        v.state  = ctx->d_vit_st;
+        v.shift  = ctx->d_vit_sh;
+    }
+    if ((rc = ensure(ctx, &ctx->d_xo_f, &ctx->xo_f_cap, (size_t)n * ctx->n_chrom * 9 + 1))) return rc;   // tied windows' second pass
+    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+    if ((rc = sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, nullptr, &v))) return rc;
+    if (!dev) {
+        HIP_TRY(ctx, hipMemcpyAsync(logmax_out, v.logmax, nlm * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(state_out, v.state, nst, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(shift_out, v.shift, nsh * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return CNF2_OK;

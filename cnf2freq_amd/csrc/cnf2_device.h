@@ -86,6 +86,9 @@ struct KernelParams {
     double*        xo;         // crossover mode: [n_ind][n_markers][6] per-individual crossover posteriors, or null
     double*        xo_sum;     // crossover mode: [n_markers][6] summed over the jobs' individuals (f64 atomics)
     int32_t*       xo_cnt;     // crossover mode: [n_chrom] individuals that contribute (not skipped)
+    double*        vit_logmax; // Viterbi mode: [n_ind][n_chrom][8] log max-product per shift mode
+    uint8_t*       vit_state;  // Viterbi mode: [n_ind][n_markers] MAP state g = j*8 + lo of every marker
+    int32_t*       vit_shift;  // Viterbi mode: [n_ind][n_chrom] MAP shift mode, -1 where skipped
 };
 #define CNF2_LEXP_IGNORED (-2147483647 - 1)   /* shift mode not analysed: CNF2_IGNORED_D */
 #define CNF2_LEXP_DEAD    (-2147483647)       /* no likelihood left: CNF2_MINFACTOR_F */
@@ -203,6 +206,7 @@ void launch_addvariance(const KernelParams& p, int first, int len, double* out, 
 void launch_fb(const KernelParams& p, int grid, bool debug_store, hipStream_t stream);
 void launch_fb_xo(const KernelParams& p, int grid, hipStream_t stream);
 void launch_fb_fast_xo(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
+void launch_fb_fast_vit(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
 int  fb_xo_blocks_per_cu();
 void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream);
 void launch_fb_fast(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);

@@ -512,6 +512,81 @@ __device__ __forceinline__ void xo_store_zero(const KernelParams& p, int ind, in
     if (lane < 6 && p.xo) p.xo[((size_t)ind * p.n_markers + m) * 6 + lane] = 0.0;
 }
 
+// ------------------------------------------------------------------ Viterbi decoding (fast kernel, STOREW == 5)
+// Max-product form of transition_scaled: every butterfly x' = max(x, t partner), the state keeping its own value unless
+// the flipped partner is strictly larger.  The decision (1 = the partner won) of every stage and register is shifted into
+// d, first stage / register first: decision (stage k, register j) ends at bit vit_pos(k, j) of the lane's 64-bit word
+// (stages 0-3 in the low half, 4-5 in the high half).  A decision belongs to the state the value is written to.
+__device__ __forceinline__ int vit_pos(int k, int j) { return k < 4 ? 31 - 8 * k - j : 47 - 8 * (k - 4) - j; }
+__device__ __forceinline__ void vit_pick(double& x, double p, uint32_t& d)
+{
+    const bool c = p > x;
+    x = c ? p : x;
+    d = d + d + (c ? 1u : 0u);
+}
+template <int BIT>
+__device__ __forceinline__ void vit_lane_stage(double (&v)[8], double t, uint32_t& d)
+{
+    double q[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) q[j] = BIT == 0 ? lane_xor1(v[j]) : BIT == 1 ? lane_flip_b1(v[j]) : lane_flip_b2(v[j]);
+#pragma unroll
+    for (int j = 0; j < 8; j++) vit_pick(v[j], t * q[j], d);
+}
+template <int BIT>
+__device__ __forceinline__ void vit_reg_stage(double (&v)[8], double t, uint32_t& d)
+{
+    double q[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) q[j] = v[j ^ (1 << BIT)];
+#pragma unroll
+    for (int j = 0; j < 8; j++) vit_pick(v[j], t * q[j], d);
+}
+__device__ __forceinline__ unsigned long long vit_transition(double (&v)[8], double t0, double t1)
+{
+    uint32_t lo = 0, hi = 0;
+    vit_lane_stage<0>(v, t1, lo);          // state bit order and factors of transition_scaled
+    vit_lane_stage<1>(v, t0, lo);
+    vit_lane_stage<2>(v, t0, lo);
+    vit_reg_stage<0>(v, t1, lo);
+    vit_reg_stage<1>(v, t0, hi);
+    vit_reg_stage<2>(v, t0, hi);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// per-chain maximum (the three DPP steps of chain_sum)
+__device__ __forceinline__ double chain_max(double v)
+{
+    v = fmax(v, lane_xor1(v));
+    v = fmax(v, lane_xor2(v));
+    v = fmax(v, dpp_mov_all<0x141>(v));
+    return v;
+}
+__device__ __forceinline__ int chain_min_int(int v)
+{
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0xB1, 0xF, 0xF, true));
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x4E, 0xF, 0xF, true));
+    v = min(v, __builtin_amdgcn_mov_dpp(v, 0x141, 0xF, 0xF, true));
+    return v;
+}
+// the lane (within its chain) that holds low state bits lo: lane(lo) = b0 ^ 2 b1 ^ 7 b2 (state_lo is its own inverse)
+__device__ __forceinline__ int vit_lane_of(int lo) { return lo ^ ((lo & 4) ? 3 : 0); }
+// One gap of the backtrace: the state at marker m from the state x at marker m+1 and the chain's eight decision words of
+// the gap (W[lane of lo]).  The stages are undone in reverse order, each decision read at the state the walk has reached.
+__device__ __forceinline__ int vit_undo(const unsigned long long* W, int x)
+{
+    int j = x >> 3, lo = x & 7;
+    unsigned long long w = W[vit_lane_of(lo)];
+    j ^= (int)((w >> vit_pos(5, j)) & 1) << 2;
+    j ^= (int)((w >> vit_pos(4, j)) & 1) << 1;
+    j ^= (int)((w >> vit_pos(3, j)) & 1);
+    lo ^= (int)((w >> vit_pos(2, j)) & 1) << 2;
+    w = W[vit_lane_of(lo)];
+    lo ^= (int)((w >> vit_pos(1, j)) & 1) << 1;
+    w = W[vit_lane_of(lo)];
+    lo ^= (int)((w >> vit_pos(0, j)) & 1);
+    return j * 8 + lo;
+}
+
 // STOREW: 0 = plain sweep; 1 = accumulate mode (posterior weights of every marker into p.wbuf); 2 = turn-scan mode
 // (alpha after emission and beta of every marker with their scales into p.wbuf, CNF2_TURN_ROW doubles per marker);
 // 4 = crossover mode (posterior probability that each state bit flips across each gap into p.xo / p.xo_sum / p.xo_cnt;
@@ -1026,9 +1101,13 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
     static_assert(!XPOSE || (HALF && STOREW == 0), "the transposing variant exists for the plain half-spill sweep");
     // STOREW: 0 plain sweep; 1 accumulate mode (also stores the posterior weights wg); 2 turn-scan mode (stores alpha e, beta
     // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only); 4 crossover
-    // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows)
+    // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows);
+    // 5 Viterbi mode (no alpha spill: the max-product recursion beside the forward pass stores its decisions in the spill
+    // slot, and a backtrace replaces the backward pass: p.vit_logmax / p.vit_state / p.vit_shift; no rows)
     constexpr bool ROWS = STOREW == 0 || STOREW == 1;      // class sums, restricted tables, tile epilogue, p.dosage
     constexpr bool WG   = STOREW == 1 || STOREW == 3;
+    constexpr bool VIT  = STOREW == 5;
+    static_assert(!VIT || (!XPOSE && !TIED), "the Viterbi mode is an instantiation of the untied DPP kernel");
     static_assert(!TIED || (!XPOSE && ROWS), "tie combinations only matter to the rows");
     // Spill row (528 doubles): [k = 0..3][lane][2] = registers 2k, 2k+1 of every lane (one 16-byte access
     // per lane and k), then [chain][2] = reciprocal normaliser of the (even) marker and, HALF only, of
@@ -1125,6 +1204,14 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         bool   dead = false;
         double pend = 1.0;     // reciprocal normaliser not yet applied to a[] (folded into the next emission)
         int    rmask = CNF2_RESCALE_MASK, bmask = CNF2_RESCALE_MASK;   // rescaling pattern of the forward / backward pass
+        // Viterbi mode: the max-product vector of the same chains.  It takes the same emission products as a[] (HALF: with
+        // the folded reciprocals, so it lives in a[]'s scale; full spill: unscaled), and its own power-of-two rescaling by
+        // the chain maximum (exact: no decision changes), whose exponents sum to vexpo.  Decisions: [gap][lane] words.
+        double vt[8];
+        int    vexpo = 0;
+        unsigned long long* const vbits = (unsigned long long*)spill;
+#pragma unroll
+        for (int j = 0; j < 8; j++) vt[j] = 1.0 / 64.0;
         // One marker of the forward pass.  ODD (HALF only): nothing is spilled and, except at the last
         // marker of the chromosome, nothing is rescaled: two emission products in a row cannot underflow a
         // double.  A skipped step has normaliser 1 (the reference rescales at every marker,
@@ -1137,7 +1224,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             const double2 r  = *(const double2*)(row + TAB_T);
             const int     ml = m - first;
             double*       sp = spill + (size_t)(HALF ? (ml >> 1) : ml) * ROW;
-            if (!ODD) {
+            if (!ODD && !VIT) {
 #ifndef CNF2_X_NOSTORE   /* timing ablation only: results are wrong */
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
@@ -1150,6 +1237,19 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             }
 #pragma unroll
             for (int j = 0; j < 8; j++) a[j] *= e[j];
+            if (VIT) {
+#pragma unroll
+                for (int j = 0; j < 8; j++) vt[j] *= e[j];
+                if (!ODD) {
+                    // (HALF: every second marker; two markers cannot lose 300 decades against a[])
+                    const double vm = fmax(fmax(fmax(vt[0], vt[1]), fmax(vt[2], vt[3])), fmax(fmax(vt[4], vt[5]), fmax(vt[6], vt[7])));
+                    int ex;
+                    (void)frexp(chain_max(vm), &ex);
+#pragma unroll
+                    for (int j = 0; j < 8; j++) vt[j] = ldexp(vt[j], -ex);
+                    vexpo += ex;
+                }
+            }
             pend = 1.0;
             // HALF: the vectors are rescaled at every CNF2_RESCALE-th marker only (and at the last one): a few emission
             // products in a row cannot underflow a double, and a skipped step simply has normaliser 1
@@ -1166,13 +1266,17 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 } else {
                     scale_chain(a, &mant, &expo, &dead, &inv);     // full spill: the stored rows are normalised at once
                 }
-                if (c.lo == 0) sp[512 + 2 * s + (ODD ? 1 : 0)] = inv;
-            } else if (!ODD) {
+                if (c.lo == 0 && !VIT) sp[512 + 2 * s + (ODD ? 1 : 0)] = inv;
+            } else if (!ODD && !VIT) {
                 if (c.lo == 0) sp[512 + 2 * s] = 1.0;
             }
             if (m < last) {
                 if (XPOSE) transition_xpose(a, r.x, r.y, xb, lane);
                 else transition_scaled(a, r.x, r.y);
+                if (VIT) {
+                    const unsigned long long d = vit_transition(vt, r.x, r.y);
+                    __builtin_nontemporal_store(d, vbits + (size_t)ml * 64 + lane);
+                }
             }
         };
         RawSlots raw;
@@ -1228,6 +1332,71 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             }
         }
         if (STOREW == 4 && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
+        if (VIT) {
+            // ------------------------------------------------------------ Viterbi: logmax, MAP mode, backtrace
+            // logmax_s = log(max-product) + the chromosome's dropped butterfly constants, as likelihood_logs_kernel finishes
+            // the factors.  HALF: vt[] carries a[]'s scale F, and F = mant 2^expo / (last normaliser) = mant 2^expo pend.
+            const size_t e    = (size_t)jb.ind * p.n_chrom + jb.chrom;
+            uint8_t*     st   = p.vit_state + (size_t)jb.ind * p.n_markers + first;
+            double       vm   = vt[0];
+#pragma unroll
+            for (int j = 1; j < 8; j++) vm = fmax(vm, vt[j]);
+            vm = chain_max(vm);
+            int          qe;
+            const double qm   = frexp(vm * (HALF ? pend * mant : 1.0), &qe);
+            const bool   live = alive && vm > 0.0;
+            const double lm   = live ? log(qm) + (double)(qe + vexpo + (HALF ? expo : 0)) * 0.69314718055994530942 +
+                                           p.chrom_logk[jb.chrom]
+                                     : (c.active ? (double)CNF2_MINFACTOR_F : CNF2_IGNORED_D);
+            const double best = across_chains_max(live ? lm : -INFINITY);
+            if (!any_alive || !(best > -INFINITY)) {
+                // skipped, as the sweep skips it: no state, no mode, every logmax CNF2_IGNORED
+                if (c.lo == 0) p.vit_logmax[e * 8 + s] = CNF2_IGNORED_D;
+                if (lane == 0) p.vit_shift[e] = -1;
+                for (int ml = lane; ml <= last - first; ml += 64) st[ml] = 0xFF;
+                continue;
+            }
+            if (c.lo == 0) p.vit_logmax[e * 8 + s] = lm;
+            // MAP mode: the lowest chain among the maxima; its final state: the lowest state index among the maxima
+            const int sstar = __builtin_amdgcn_readfirstlane(__builtin_ctzll(__ballot((lane & 7) == 0 && live && lm == best)) >> 3);
+            int       g     = 64;
+#pragma unroll
+            for (int j = 7; j >= 0; j--)
+                if (vt[j] == vm) g = j * 8 + c.lo;
+            int x = __builtin_amdgcn_readlane(chain_min_int(g), sstar * 8);
+            if (lane == 0) {
+                p.vit_shift[e]    = sstar;
+                st[last - first] = (uint8_t)x;
+            }
+            // backtrace: 64 gaps at a time, lane i fetches the 64 B of chain s* of gap top - i into LDS (the tile below
+            // is requested before the walk of this one); the walk itself is wave-uniform, three LDS reads a gap
+            using u2v = unsigned long long __attribute__((ext_vector_type(2)));
+            unsigned long long* tl   = (unsigned long long*)tab;
+            const unsigned long long* vsrc = vbits + sstar * 8;
+            u2v w4[4];
+            auto load_tile = [&](int top) {
+                const int gi = top - lane < 0 ? 0 : top - lane;
+#pragma unroll
+                for (int k = 0; k < 4; k++) w4[k] = __builtin_nontemporal_load((const u2v*)(vsrc + (size_t)gi * 64) + k);
+            };
+            const int ngap = last - first;
+            if (ngap > 0) load_tile(ngap - 1);
+            for (int top = ngap - 1; top >= 0; top -= 64) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) *(u2v*)(tl + lane * 8 + 2 * k) = w4[k];
+                wave_lds_fence();
+                if (top >= 64) load_tile(top - 64);
+                const int cnt  = top < 63 ? top + 1 : 64;
+                int       mine = 0;
+                for (int i = 0; i < cnt; i++) {
+                    x    = vit_undo(tl + i * 8, x);
+                    mine = lane == i ? x : mine;
+                }
+                if (lane < cnt) st[top - lane] = (uint8_t)mine;
+                wave_lds_fence();
+            }
+            continue;
+        }
         if (p.flags & KP_NO_DOSAGE) continue;
 
         // ---------------------------------------------------------------- backward + rows
@@ -3886,6 +4055,13 @@ void launch_fb_fast_xo(const KernelParams& p, int grid, bool half_spill, hipStre
     zero_job_counter(p, stream);
     if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
     else hipLaunchKernelGGL((fb_fast_kernel<false, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
+    launch_likelihood_logs(p, stream);
+}
+void launch_fb_fast_vit(const KernelParams& p, int grid, bool half_spill, hipStream_t stream)
+{
+    zero_job_counter(p, stream);
+    if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 5>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
+    else hipLaunchKernelGGL((fb_fast_kernel<false, 5>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
     launch_likelihood_logs(p, stream);
 }
 int fb_xo_blocks_per_cu()

@@ -1,7 +1,7 @@
 // cnf2freq_main.cpp -- drop-in command line for the PlantImpute invocation of the reference
 // (demo.sh:37):
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
-//            [--deserialize F] [--gpus N] [--crossovers F] [--remap F [--remap-iterations K]]
+//            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
 // haplotyping sweep (doit) before its dump.  Rows of the last round go to --output, earlier ones to stdout; every
@@ -20,6 +20,12 @@
 // one "%.5lf" tab-separated line of the 6 meioses per marker, a blank line) and / or K EM steps of the marker map
 // (cnf2_remap.h) written as a .map file that is read back and checked.  The summed log-likelihood of every step goes to
 // stderr; --output is the same with or without these flags.  Single GPU only.
+//
+// --viterbi F (not a flag of the reference): after the last round, and before a --remap changes the map, the MAP
+// inheritance path of every analysed individual (cnf2_sweep_viterbi): per chromosome and individual a header
+// "name:chrom<TAB>s*<TAB>log posterior of the path" ("%.6lf"; "-<TAB>-" where the individual is skipped), one line per
+// marker of the 6 state bits as 0 / 1 in the column order of --crossovers ("-" where skipped), a blank line.  --output is
+// the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
 // has no compute path of its own and fails if no GPU is present.  Out of scope: the toulbar2
@@ -67,6 +73,7 @@ struct Options {
                                          // a GPU of its own, shm -- staging through a shared region on the host -- with --single-device)
     bool        rccl_selftest = false;   // --rccl-selftest: the RCCL transport's collectives with a world of one on GPU 0, then stop
     std::string crossovers;              // --crossovers F: crossover posteriors of the last round's state
+    std::string viterbi;                 // --viterbi F: MAP inheritance paths of the last round's state
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
     int         remap_iterations = 1;
     bool        remap_iterations_set = false;
@@ -113,6 +120,7 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--transport") o.transport = val();
         else if (a == "--rccl-selftest") o.rccl_selftest = true;
         else if (a == "--crossovers") o.crossovers = val();
+        else if (a == "--viterbi") o.viterbi = val();
         else if (a == "--remap") o.remap = val();
         else if (a == "--remap-iterations") {
             o.remap_iterations = atoi(val().c_str());
@@ -127,6 +135,7 @@ static bool parse(int argc, char** argv, Options& o)
 }
 
 static void crossovers_and_remap(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void viterbi_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -212,6 +221,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
         fflush(out);
     }
     if (out != stdout) fclose(out);
+    if (world == 1 && !opt.viterbi.empty()) viterbi_paths(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -272,6 +282,33 @@ static void crossovers_and_remap(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     }
     std::string err;
     if (!write_map_checked(opt.remap.c_str(), pos.data(), M, P.chromstarts.data(), C, &err)) throw EngineError(CNF2_ERR_STATE, err);
+}
+
+// --viterbi after the last round (single GPU): the context holds the last round's rows and the map they were swept with
+static void viterbi_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    std::vector<double>  f((size_t)N * C * 8), ll((size_t)N * C), lm((size_t)N * C * 8);
+    std::vector<uint8_t> st((size_t)N * M);
+    std::vector<int32_t> sh((size_t)N * C);
+    if (cnf2_sweep_viterbi(ctx, 0, N, f.data(), ll.data(), lm.data(), st.data(), sh.data(), 0) != CNF2_OK)
+        throw EngineError(CNF2_ERR_STATE, std::string("cnf2_sweep_viterbi: ") + cnf2_last_error(ctx));
+    FILE* out = fopen(opt.viterbi.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.viterbi);
+    for (int c = 0; c < C; c++)
+        for (int j = 0; j < N; j++) {
+            const size_t e = (size_t)j * C + c;
+            const int    s = sh[e];
+            if (s < 0) fprintf(out, "%s:%d\t-\t-\n", P.inds[P.dous[j]].name.c_str(), c + 1);
+            else fprintf(out, "%s:%d\t%d\t%.6lf\n", P.inds[P.dous[j]].name.c_str(), c + 1, s, lm[e * 8 + s] - ll[e]);
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const int g = st[(size_t)j * M + m];
+                if (s < 0) fprintf(out, "-\t-\t-\t-\t-\t-\n");
+                else fprintf(out, "%d\t%d\t%d\t%d\t%d\t%d\n", g & 1, (g >> 1) & 1, (g >> 2) & 1, (g >> 3) & 1, (g >> 4) & 1, (g >> 5) & 1);
+            }
+            fprintf(out, "\n");
+        }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.viterbi);
 }
 
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
@@ -372,6 +409,10 @@ int main(int argc, char** argv)
     }
     if (opt.gpus > 1 && (!opt.crossovers.empty() || !opt.remap.empty())) {
         fprintf(stderr, "--crossovers and --remap need a single GPU (--gpus 1): their sums are not reduced across ranks\n");
+        return 2;
+    }
+    if (opt.gpus > 1 && !opt.viterbi.empty()) {
+        fprintf(stderr, "--viterbi needs a single GPU (--gpus 1): the ranks' paths are not gathered\n");
         return 2;
     }
     if (opt.remap_iterations_set && opt.remap.empty()) {

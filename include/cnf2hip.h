@@ -256,6 +256,32 @@ int cnf2_crossover_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
 int cnf2_sweep_crossovers(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out,
                           double *xo_out, double *xo_sum_out, int32_t *n_contrib_out, uint32_t flags);
 
+/* Viterbi decoding: the maximum a-posteriori (MAP) inheritance path of every analysed individual on every chromosome.
+ * For shift mode s, logmax[s] = log max over state paths g_1..g_n of pi(g_1) prod_m e_s,m(g_m) prod_m T_m(g_m, g_m+1),
+ * the max-product twin of factors[s] (pi = 1/64, e the sweep's path-free emission, T the 64 x 64 Kronecker transition;
+ * it includes the same dropped per-gap constants as factors).  The MAP mode s* is the argmax of logmax over the active
+ * modes; the MAP path is the argmax state sequence in mode s*, and exp(logmax[s*] - loglik) is the posterior probability
+ * of the decoded (mode, path).  Ties, of which the model has many exactly symmetric ones, are broken as follows: at every
+ * butterfly stage a state keeps its own value unless the flipped partner is strictly larger; at the last marker the
+ * lowest state index among the maxima; across modes the lowest mode index.
+ * A state is g = j*8 + lo as in cnf2_state_posterior; bit t of g is the meiosis of column t of cnf2_sweep_crossovers.
+ * The path is in the frame of mode s*; its bit flips between markers m and m+1 (the crossover calls) do not depend on it.
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal (the same forward passes)
+ *   logmax_out  [n][n_chrom][8]  CNF2_IGNORED for masked modes, CNF2_MINFACTOR for a mode without likelihood
+ *   state_out   [n][n_markers]   (uint8) MAP state of every marker
+ *   shift_out   [n][n_chrom]     (int32) s*
+ * An individual is skipped on a chromosome where the sweep skips it (no shift mode with a likelihood): its states there
+ * are 0xFF, its shift -1 and its logmax CNF2_IGNORED.  A range split [a,b) + [b,c) gives [a,c) bit for bit.
+ * One pass: untied windows through the fast kernel's Viterbi instantiation (likelihoods, max-product recursion, decision
+ * bits in the wave's spill slot, backtrace in the same wave), tied windows through the tied kernel without rows
+ * (likelihoods) and then the same Viterbi instantiation.
+ * Flags: CNF2_OUT_DEVICE (all five pointers are device pointers), CNF2_STATIC_JOBS, CNF2_FULL_SPILL (the fast kernel
+ * without the half spill) and CNF2_TIES_GENERAL (tied likelihoods from the general kernel) as in cnf2_sweep.
+ * CNF2_MERGE_MODES, CNF2_XPOSE, CNF2_FLUSH_TINY and the dosage flags are ignored.  The call synchronises the context's
+ * stream once (the job list), also with CNF2_OUT_DEVICE. */
+int cnf2_sweep_viterbi(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out,
+                       double *logmax_out, uint8_t *state_out, int32_t *shift_out, uint32_t flags);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every
