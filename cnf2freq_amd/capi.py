@@ -41,7 +41,7 @@ SYMBOLS = [
     "cnf2_set_grid_reserve", "cnf2_set_batch_jobs", "cnf2_window_table", "cnf2_update_pass_records", "cnf2_exchange_buffer", "cnf2_exchange_download", "cnf2_exchange_upload", "cnf2_exchange_read", "cnf2_exchange_write",
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
-    "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi",
+    "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
 ]
 
 
@@ -106,6 +106,7 @@ def load():
         L.cnf2_crossover_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_sweep_crossovers.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_viterbi.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_sweep_sample.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -372,6 +373,26 @@ class Context:
         best = np.take_along_axis(logmax, np.maximum(shift, 0)[..., None], axis=2)[..., 0]
         path_logpost = np.where(shift >= 0, best - loglik, np.nan)
         return dict(factors=factors, loglik=loglik, logmax=logmax, state=state, shift=shift, path_logpost=path_logpost)
+
+    def sweep_sample(self, ind_begin=0, ind_end=None, draws=1, seed=0, full_spill=False, ties_general=False,
+                     static_jobs=False):
+        """cnf2_sweep_sample: factors / loglik as sweep(), and `draws` (mode, path) draws from the posterior per individual
+        and chromosome: state[n][K][M] (uint8, 0xFF where skipped), shift[n][K][C] (the drawn mode, -1 where skipped) and
+        logp[n][K][C] = log P(mode, path | data) (NaN where skipped).  Draw k depends on (seed, individual, k) only."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        state = np.zeros((n, draws, self.n_markers), np.uint8)
+        shift = np.zeros((n, draws, self.n_chrom), np.int32)
+        logp = np.zeros((n, draws, self.n_chrom))
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0))
+        self._chk(self.L.cnf2_sweep_sample(self.h, ind_begin, ind_end, draws, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           _p(factors), _p(loglik), _p(state), _p(shift), _p(logp), flags),
+                  "cnf2_sweep_sample")
+        logp = np.where(shift >= 0, logp, np.nan)
+        return dict(factors=factors, loglik=loglik, state=state, shift=shift, logp=logp)
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

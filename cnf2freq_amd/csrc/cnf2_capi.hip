@@ -91,6 +91,14 @@ struct cnf2_ctx {
     int32_t* d_vit_sh = nullptr;          // [n][n_chrom]
     size_t   vit_sh_cap = 0;
 
+    // posterior sampling (cnf2_sweep_sample), host-output calls
+    uint8_t* d_smp_st = nullptr;          // [n][K][n_markers]
+    size_t   smp_st_cap = 0;
+    int32_t* d_smp_sh = nullptr;          // [n][K][n_chrom]
+    size_t   smp_sh_cap = 0;
+    double*  d_smp_lp = nullptr;          // [n][K][n_chrom]
+    size_t   smp_lp_cap = 0;
+
     // batched HOT LOOP 2 (cnf2_sweep_accumulate)
     std::vector<int32_t> slot_rec;   // [n_dous][7] record per window slot (derive_window), -1 none
     int32_t* d_slot_rec = nullptr;
@@ -248,6 +256,9 @@ void cnf2_ctx_destroy(cnf2_ctx* ctx)
     (void)hipFree(ctx->d_vit_lm);
     (void)hipFree(ctx->d_vit_st);
     (void)hipFree(ctx->d_vit_sh);
+    (void)hipFree(ctx->d_smp_st);
+    (void)hipFree(ctx->d_smp_sh);
+    (void)hipFree(ctx->d_smp_lp);
     (void)hipFree(ctx->d_slot_rec);
     (void)hipFree(ctx->d_desc);
     (void)hipFree(ctx->d_rec_empty);
@@ -635,20 +646,30 @@ struct VitArgs {
     uint8_t* state;    // [n][n_markers]
     int32_t* shift;    // [n][n_chrom]
 };
+// sampling mode of a sweep (cnf2_sweep_sample): device outputs and the generator's arguments
+struct SmpArgs {
+    uint8_t*           state;   // [n][K][n_markers]
+    int32_t*           shift;   // [n][K][n_chrom]
+    double*            logp;    // [n][K][n_chrom] or null
+    int                draws;   // K
+    unsigned long long seed;
+};
 
 // cnf2_sweep, and with xo its crossover mode: the untied windows through the fast kernel's crossover instantiation (one
 // pass: likelihoods and posteriors), the tied ones through the tied kernel without rows (their likelihoods, as cnf2_sweep
 // forms them) and then the general kernel's crossover instantiation (their posteriors).  With vit its Viterbi mode: the same
-// routing, with the fast kernel's Viterbi instantiation in place of both crossover instantiations
+// routing, with the fast kernel's Viterbi instantiation in place of both crossover instantiations.  With smp its sampling
+// mode: the untied windows through the fast kernel's sampling instantiation (one pass: likelihoods and draws), the tied ones
+// through the tied kernel without rows (likelihoods) and then the same sampling instantiation (draws)
 static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
-                      uint32_t flags, const XoArgs* xo, const VitArgs* vit = nullptr)
+                      uint32_t flags, const XoArgs* xo, const VitArgs* vit = nullptr, const SmpArgs* smp = nullptr)
 {
     int rc = ready(ctx);
     if (rc) return rc;
     const int n_all = (int)ctx->windows.size();
     if (ind_begin < 0 || ind_end > n_all || ind_begin > ind_end) return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
-    if (xo || vit) flags &= ~(uint32_t)(CNF2_MERGE_MODES | CNF2_XPOSE | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_RAW_DOSAGE);
-    const bool want_dosage = !(flags & CNF2_NO_DOSAGE) && !xo && !vit;
+    if (xo || vit || smp) flags &= ~(uint32_t)(CNF2_MERGE_MODES | CNF2_XPOSE | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_RAW_DOSAGE);
+    const bool want_dosage = !(flags & CNF2_NO_DOSAGE) && !xo && !vit && !smp;
     if (!factors_out || !loglik_out || (want_dosage && !dosage_out)) return fail(ctx, CNF2_ERR_ARG, "output pointer is NULL");
     const int n = ind_end - ind_begin;
     if (n == 0) return CNF2_OK;
@@ -817,6 +838,15 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         p.vit_state  = vit->state;
         p.vit_shift  = vit->shift;
     }
+    if (smp) {
+        p.flags     = KP_NO_DOSAGE;
+        p.smp_state = smp->state;
+        p.smp_shift = smp->shift;
+        p.smp_logp  = smp->logp;
+        p.smp_draws = smp->draws;
+        p.smp_seed  = smp->seed;
+        p.smp_ind0  = ind_begin;
+    }
     if (flags & CNF2_LOG_PATHS) {
         if ((rc = ensure(ctx, &ctx->d_pathlog, &ctx->pathlog_cap, nl))) return rc;
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pathlog, 0xff, nl * sizeof(int32_t), ctx->stream));
@@ -839,7 +869,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         // the tile-producer kernel with a pass per tie combination; the general kernel (one lane per table entry, per-marker
         // producer) with the full spill and where asked for
         if (flags & CNF2_FLUSH_TINY) pt.flags |= KP_FLUSH_TINY;
-        if (xo || vit) pt.flags = KP_NO_DOSAGE;    // crossover / Viterbi mode: likelihoods only here, the rest from the pass below
+        if (xo || vit || smp) pt.flags = KP_NO_DOSAGE;    // crossover / Viterbi / sampling mode: likelihoods only here, the rest from the pass below
         if ((flags & CNF2_FULL_SPILL) || (flags & (CNF2_TIES_GENERAL | CNF2_FLUSH_TINY))) launch_fb(pt, grid_gen, false, ctx->stream2);
         else launch_fb_fast_tied(pt, grid_gen, ctx->stream2);
         HIP_TRY(ctx, hipGetLastError());
@@ -865,6 +895,17 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
             launch_fb_fast_vit(px, gx < grid_gen ? gx : grid_gen, !(flags & CNF2_FULL_SPILL), ctx->stream2);
             HIP_TRY(ctx, hipGetLastError());
         }
+        if (smp) {
+            // the fast kernel's sampling instantiation over the tied jobs, likewise (the forward pass and the draws do not
+            // see the tie rule); its likelihoods go to scratch
+            KernelParams px = pt;
+            px.factors = ctx->d_xo_f;
+            px.loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
+            int gx = ctx->n_cu * ctx->fast_blocks_per_cu - ctx->reserve_blocks;
+            if (gx < 1) gx = 1;
+            launch_fb_fast_smp(px, gx < grid_gen ? gx : grid_gen, !(flags & CNF2_FULL_SPILL), ctx->stream2);
+            HIP_TRY(ctx, hipGetLastError());
+        }
         HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream2));
     }
     if (n_packed > 0) {
@@ -880,6 +921,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         int gf = (int)((n_fast + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
         p.clock_out = ctx->d_clock;
         if (xo) launch_fb_fast_xo(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
+        else if (smp) launch_fb_fast_smp(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
         else if (vit) {
             // the likelihoods from cnf2_sweep's own launch without rows (the Viterbi instantiation runs the same recursion,
             // but compiled without the backward pass it does not round every job's factors the same way: DESIGN.md 8c), then
@@ -1215,6 +1257,48 @@ int cnf2_sweep_viterbi(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factor
         HIP_TRY(ctx, hipMemcpyAsync(logmax_out, v.logmax, nlm * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(state_out, v.state, nst, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipMemcpyAsync(shift_out, v.shift, nsh * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    return CNF2_OK;
+}
+
+// one pass of sweep_impl's sampling mode
+int cnf2_sweep_sample(cnf2_ctx* ctx, int ind_begin, int ind_end, int n_draws, uint64_t seed, double* factors_out,
+                      double* loglik_out, uint8_t* state_out, int32_t* shift_out, double* logp_out, uint32_t flags)
+{
+    int rc = ready(ctx);
+    if (rc) return rc;
+    if (n_draws < 1 || n_draws > 1024) return fail(ctx, CNF2_ERR_ARG, "n_draws must be in 1 .. 1024, not %d", n_draws);
+    if (!state_out || !shift_out) return fail(ctx, CNF2_ERR_ARG, "state_out and shift_out must not be NULL");
+    if (ind_begin < 0 || ind_end > (int)ctx->windows.size() || ind_begin > ind_end)
+        return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
+    const bool dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int  n   = ind_end - ind_begin;
+    if (n == 0) return CNF2_OK;
+    const size_t nd  = (size_t)n * n_draws;
+    const size_t nst = nd * ctx->n_markers, nsh = nd * ctx->n_chrom;
+    SmpArgs a;
+    a.state = state_out;
+    a.shift = shift_out;
+    a.logp  = logp_out;
+    a.draws = n_draws;
+    a.seed  = (unsigned long long)seed;
+    if (!dev) {
+        // host outputs are staged whole (callers with many draws split the individual range: the draws do not change)
+        if ((rc = ensure(ctx, &ctx->d_smp_st, &ctx->smp_st_cap, nst))) return rc;
+        if ((rc = ensure(ctx, &ctx->d_smp_sh, &ctx->smp_sh_cap, nsh))) return rc;
+        if (logp_out && (rc = ensure(ctx, &ctx->d_smp_lp, &ctx->smp_lp_cap, nsh))) return rc;
+        a.state = ctx->d_smp_st;
+        a.shift = ctx->d_smp_sh;
+        a.logp  = logp_out ? ctx->d_smp_lp : nullptr;
+    }
+    if ((rc = ensure(ctx, &ctx->d_xo_f, &ctx->xo_f_cap, (size_t)n * ctx->n_chrom * 9 + 1))) return rc;   // tied windows' second pass
+    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+    if ((rc = sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, nullptr, nullptr, &a))) return rc;
+    if (!dev) {
+        HIP_TRY(ctx, hipMemcpyAsync(state_out, a.state, nst, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(shift_out, a.shift, nsh * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+        if (logp_out) HIP_TRY(ctx, hipMemcpyAsync(logp_out, a.logp, nsh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     return CNF2_OK;

@@ -89,6 +89,12 @@ struct KernelParams {
     double*        vit_logmax; // Viterbi mode: [n_ind][n_chrom][8] log max-product per shift mode
     uint8_t*       vit_state;  // Viterbi mode: [n_ind][n_markers] MAP state g = j*8 + lo of every marker
     int32_t*       vit_shift;  // Viterbi mode: [n_ind][n_chrom] MAP shift mode, -1 where skipped
+    uint8_t*       smp_state;  // sampling mode: [n_ind][smp_draws][n_markers] drawn state g = j*8 + lo of every marker
+    int32_t*       smp_shift;  // sampling mode: [n_ind][smp_draws][n_chrom] drawn shift mode, -1 where skipped
+    double*        smp_logp;   // sampling mode: [n_ind][smp_draws][n_chrom] log P(mode, path | data), or null
+    unsigned long long smp_seed;   // sampling mode: the generator's seed
+    int            smp_draws;  // sampling mode: draws per individual and chromosome (1..1024)
+    int            smp_ind0;   // sampling mode: absolute index of the individual at windows[0] (the generator's i)
 };
 #define CNF2_LEXP_IGNORED (-2147483647 - 1)   /* shift mode not analysed: CNF2_IGNORED_D */
 #define CNF2_LEXP_DEAD    (-2147483647)       /* no likelihood left: CNF2_MINFACTOR_F */
@@ -207,6 +213,7 @@ void launch_fb(const KernelParams& p, int grid, bool debug_store, hipStream_t st
 void launch_fb_xo(const KernelParams& p, int grid, hipStream_t stream);
 void launch_fb_fast_xo(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
 void launch_fb_fast_vit(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
+void launch_fb_fast_smp(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
 int  fb_xo_blocks_per_cu();
 void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream);
 void launch_fb_fast(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);

@@ -587,6 +587,107 @@ __device__ __forceinline__ int vit_undo(const unsigned long long* W, int x)
     return j * 8 + lo;
 }
 
+// ------------------------------------------------------------------ posterior sampling (fast kernel, STOREW == 6)
+// The counter-based generator of cnf2_sweep_sample (include/cnf2hip.h): SplitMix64's mixing function, and a uniform in
+// [0, 1) from the top 53 bits of mix(key ^ j).
+__device__ __forceinline__ unsigned long long smp_mix(unsigned long long z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+__device__ __forceinline__ double smp_uniform(unsigned long long key, unsigned long long j)
+{
+    return (double)(smp_mix(key ^ j) >> 11) * 0x1.0p-53;
+}
+__device__ __forceinline__ double readlane_d(double v, int l)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+// Transition factors of one triple of state bits towards the state x drawn at the marker above: f[v] = prod over the bits
+// b where v and x differ of t_b (first bit: ta, the other two: tb; the scaled butterflies' T, whose dropped constant is
+// common to every weight of a draw).  ta = tb = 1 and x = 0: no transition (the last marker).
+__device__ __forceinline__ void smp_factors(int x, double ta, double tb, double (&f)[8])
+{
+    const double p0 = (x & 1) ? ta : 1.0, q0 = (x & 1) ? 1.0 : ta;        // value of bit 0 is 0 / 1
+    const double p1 = (x & 2) ? tb : 1.0, q1 = (x & 2) ? 1.0 : tb;
+    const double p2 = (x & 4) ? tb : 1.0, q2 = (x & 4) ? 1.0 : tb;
+    const double b01[4] = {p0 * p1, q0 * p1, p0 * q1, q0 * q1};
+#pragma unroll
+    for (int v = 0; v < 4; v++) {
+        f[v]     = b01[v] * p2;
+        f[v + 4] = b01[v] * q2;
+    }
+}
+// One draw of the backward walk: the state g of a marker with weights w(g) = al(g) T(g, x), al = the 64 alpha values of
+// the draw's chain (g = j*8 + lo, in LDS), x = the state drawn at the marker above; t0 / t1 the gap's factors (state bits
+// 0 and 3: t1, the other four: t0).  Inverse CDF in ascending state order (STATE_ORDER is the identity): the group sums
+// G_j over the states j*8 .. j*8 + 7 first, then the states of the chosen group -- the first whose running sum exceeds
+// u W, or else the last one with a positive weight.  *ratio = w(g) / W.
+__device__ __forceinline__ int smp_draw(const double* al, int x, double t0, double t1, double u, double* ratio)
+{
+    double fl[8];
+    smp_factors(x, t1, t0, fl);
+    const int    xh = x >> 3;
+    double       G[8], W = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        double sj = 0.0;
+#pragma unroll
+        for (int l = 0; l < 8; l += 2) {
+            const double2 v = *(const double2*)(al + j * 8 + l);
+            sj = fma(v.x, fl[l], sj);
+            sj = fma(v.y, fl[l + 1], sj);
+        }
+        const int d = j ^ xh;
+        G[j] = sj * (((d & 1) ? t1 : 1.0) * ((d & 2) ? t0 : 1.0) * ((d & 4) ? t0 : 1.0));
+        W += G[j];
+    }
+    const double target = u * W;
+    int    jj = -1, jl = 0;
+    double base = 0.0, cum = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const double nc = cum + G[j];
+        if (jj < 0 && nc > target) {
+            jj   = j;
+            base = cum;
+        }
+        if (G[j] > 0.0) jl = j;
+        cum = nc;
+    }
+    double tg = target;
+    if (jj < 0) {
+        jj = jl;
+        tg = INFINITY;     // (the walk below then takes the group's last positive state)
+    }
+    const int     d  = jj ^ xh;
+    const double  fj = ((d & 1) ? t1 : 1.0) * ((d & 2) ? t0 : 1.0) * ((d & 4) ? t0 : 1.0);
+    const double* ag = al + jj * 8;
+    int    lp = -1, ll = 0;
+    double wp = 0.0, wl = 0.0, run = base;
+#pragma unroll
+    for (int l = 0; l < 8; l++) {
+        const double w = ag[l] * fl[l] * fj;
+        run += w;
+        if (lp < 0 && run > tg) {
+            lp = l;
+            wp = w;
+        }
+        if (w > 0.0) {
+            ll = l;
+            wl = w;
+        }
+    }
+    if (lp < 0) {
+        lp = ll;
+        wp = wl;
+    }
+    *ratio = W > 0.0 ? wp * fast_rcp(W) : 0.0;
+    return jj * 8 + lp;
+}
+
 // STOREW: 0 = plain sweep; 1 = accumulate mode (posterior weights of every marker into p.wbuf); 2 = turn-scan mode
 // (alpha after emission and beta of every marker with their scales into p.wbuf, CNF2_TURN_ROW doubles per marker);
 // 4 = crossover mode (posterior probability that each state bit flips across each gap into p.xo / p.xo_sum / p.xo_cnt;
@@ -1103,11 +1204,15 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
     // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only); 4 crossover
     // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows);
     // 5 Viterbi mode (no alpha spill: the max-product recursion beside the forward pass stores its decisions in the spill
-    // slot, and a backtrace replaces the backward pass: p.vit_logmax / p.vit_state / p.vit_shift; no rows)
+    // slot, and a backtrace replaces the backward pass: p.vit_logmax / p.vit_state / p.vit_shift; no rows); 6 sampling mode
+    // (the plain forward pass; backward walks that rebuild alpha and draw whole paths from the posterior, one draw per
+    // lane: p.smp_state / p.smp_shift / p.smp_logp; no beta, no rows)
     constexpr bool ROWS = STOREW == 0 || STOREW == 1;      // class sums, restricted tables, tile epilogue, p.dosage
     constexpr bool WG   = STOREW == 1 || STOREW == 3;
     constexpr bool VIT  = STOREW == 5;
+    constexpr bool SMP  = STOREW == 6;
     static_assert(!VIT || (!XPOSE && !TIED), "the Viterbi mode is an instantiation of the untied DPP kernel");
+    static_assert(!SMP || (!XPOSE && !TIED), "the sampling mode is an instantiation of the untied DPP kernel");
     static_assert(!TIED || (!XPOSE && ROWS), "tie combinations only matter to the rows");
     // Spill row (528 doubles): [k = 0..3][lane][2] = registers 2k, 2k+1 of every lane (one 16-byte access
     // per lane and k), then [chain][2] = reciprocal normaliser of the (even) marker and, HALF only, of
@@ -1394,6 +1499,145 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 }
                 if (lane < cnt) st[top - lane] = (uint8_t)mine;
                 wave_lds_fence();
+            }
+            continue;
+        }
+        if (SMP) {
+            // ------------------------------------------------------------ sampling: forward filtering, backward sampling
+            // Lane k of a walk makes draw k0 + k: a mode from P(s | data) over the modes the dosage rows count, then the
+            // states from the last marker down, each from w(g) = alpha_m(g) T(g, g_m+1) in the drawn mode's chain.  At
+            // every marker the wave rebuilds alpha (= alpha-minus e up to a per-chain factor, which cancels in a draw) as
+            // the crossover mode does and parks the 8 chains' vectors in the tile rows' free restricted-table space (row s,
+            // [TAB_R, TAB_R + 64): chain s), from where each lane reads its own chain.  More than 64 draws: further walks
+            // over the same spill rows.  logp = log P(s | data) + the log of every pick's w / W, carried as mantissa and
+            // exponent; one log per draw and chromosome.
+            const int K   = p.smp_draws;
+            const int len = last - first + 1;
+            if (!any_alive) {
+                // skipped, as the sweep skips it: no mode, no state
+                for (int k = lane; k < K; k += 64) {
+                    const size_t o = ((size_t)jb.ind * K + k) * p.n_chrom + jb.chrom;
+                    p.smp_shift[o] = -1;
+                    if (p.smp_logp) p.smp_logp[o] = CNF2_IGNORED_D;
+                }
+                for (int k = 0; k < K; k++) {
+                    uint8_t* st = p.smp_state + ((size_t)jb.ind * K + k) * p.n_markers + first;
+                    for (int ml = lane; ml < len; ml += 64) st[ml] = 0xFF;
+                }
+                continue;
+            }
+            // P(s | data) of the counted modes (factor - fs <= 40: cnF2freq.cpp:5420-5421), wave-uniform
+            const bool   on_s = alive && !(tmine * 2.3538526683701998e17 < T);
+            const double pws  = on_s ? tmine / T : 0.0;
+            double       pw[8];
+#pragma unroll
+            for (int m8 = 0; m8 < 8; m8++) pw[m8] = readlane_d(pws, m8 * 8);
+            const unsigned long long key0 = smp_mix(smp_mix(p.smp_seed) ^ (unsigned long long)(long long)(p.smp_ind0 + jb.ind));
+            double* const al0 = tab + TAB_R;
+            for (int k0 = 0; k0 < K; k0 += 64) {
+                const int                k   = k0 + lane;
+                const bool               on  = k < K;
+                const unsigned long long key = smp_mix(key0 ^ (unsigned long long)k);
+                // the mode: inverse CDF over the 8 chains in ascending order
+                int sm = -1, sl = 0;
+                {
+                    double W = 0.0;
+#pragma unroll
+                    for (int m8 = 0; m8 < 8; m8++) W += pw[m8];
+                    const double tg = smp_uniform(key, (unsigned long long)(p.n_markers + jb.chrom)) * W;
+                    double       cum = 0.0;
+#pragma unroll
+                    for (int m8 = 0; m8 < 8; m8++) {
+                        cum += pw[m8];
+                        if (sm < 0 && cum > tg) sm = m8;
+                        if (pw[m8] > 0.0) sl = m8;
+                    }
+                    if (sm < 0) sm = sl;
+                }
+                double pmant = 0.0;
+#pragma unroll
+                for (int m8 = 0; m8 < 8; m8++) pmant = sm == m8 ? pw[m8] : pmant;
+                int pexp = 0;
+                pmant    = frexp(pmant, &pexp);
+                const double* al = al0 + sm * TS;
+                uint8_t*      st = p.smp_state + ((size_t)jb.ind * K + (on ? k : 0)) * p.n_markers;
+                int           x  = 0;                    // state drawn at the marker above
+                double        rt0 = 1.0, rt1 = 1.0;      // factors of the gap to it (none at the last marker)
+                double        am[8];                     // alpha-minus of the spill row in flight
+                auto load_am = [&](int idx) {
+                    const double* sp = spill + (size_t)idx * ROW;
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const d2v v = __builtin_nontemporal_load((const d2v*)(sp + q * 128 + lane * 2));
+                        am[2 * q]     = v.x;
+                        am[2 * q + 1] = v.y;
+                    }
+                };
+                // One marker of the walk.  ODD (HALF only): alpha-minus rebuilt from the even neighbour's row.
+                auto smp_marker = [&](auto odd_tag, const double* row, int m) {
+                    constexpr bool ODD = decltype(odd_tag)::value;
+                    const int      ml  = m - first;
+                    const double2  r_m = *(const double2*)(row + TAB_T);     // gap m-1 -> m
+                    double         av[8];
+                    if (ODD) {
+                        double ep[8];
+                        emission_from_row(row - TS, c, ep);
+#pragma unroll
+                        for (int j = 0; j < 8; j++) av[j] = am[j] * ep[j];
+                        transition_scaled(av, r_m.x, r_m.y);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 8; j++) av[j] = am[j];
+                        asm volatile("" : "+v"(av[0]), "+v"(av[1]), "+v"(av[2]), "+v"(av[3]), "+v"(av[4]), "+v"(av[5]),
+                                     "+v"(av[6]), "+v"(av[7]) : : "memory");
+                        const int idx = HALF ? (ml >> 1) - 1 : ml - 1;
+                        load_am(idx < 0 ? 0 : idx);
+                    }
+                    double e[8];
+                    emission_from_row(row, c, e);
+                    wave_lds_fence();                    // the previous marker's draws have read their chains
+                    double* ap = al0 + s * TS + c.lo;
+#pragma unroll
+                    for (int j = 0; j < 8; j++) ap[j * 8] = av[j] * e[j];
+                    wave_lds_fence();
+                    double ratio;
+                    x = smp_draw(al, x, rt0, rt1, smp_uniform(key, (unsigned long long)m), &ratio);
+                    int ex;
+                    pmant = frexp(pmant * ratio, &ex);
+                    pexp += ex;
+                    if (on) st[m] = (uint8_t)x;
+                    rt0 = r_m.x;
+                    rt1 = r_m.y;
+                };
+                load_raw<-1>(p, c, first + (ntile - 1) * 8, first, last, &raw);
+                load_am(HALF ? ((last - first) >> 1) : (last - first));
+                for (int t = ntile - 1; t >= 0; t--) {
+                    const int m0 = first + t * 8;
+                    produce_tile<false, false, TS>(p, c, tab, m0, last, raw, hom);
+                    wave_lds_fence();
+                    const int mend = (m0 + 7 < last) ? m0 + 7 : last;
+                    int       i    = mend - m0;
+                    if (HALF) {
+                        if (!(i & 1)) {
+                            smp_marker(even_t(), tab + i * TS, m0 + i);
+                            i--;
+                        }
+                        for (; i >= 1; i -= 2) {
+                            smp_marker(odd_t(), tab + i * TS, m0 + i);
+                            smp_marker(even_t(), tab + (i - 1) * TS, m0 + i - 1);
+                        }
+                    } else {
+                        for (; i >= 0; i--) smp_marker(even_t(), tab + i * TS, m0 + i);
+                    }
+                    wave_lds_fence();
+                    if (t > 0) load_raw<-1>(p, c, m0 - 8, first, last, &raw);
+                }
+                if (on) {
+                    const size_t o = ((size_t)jb.ind * K + k) * p.n_chrom + jb.chrom;
+                    p.smp_shift[o] = sm;
+                    if (p.smp_logp)
+                        p.smp_logp[o] = pmant > 0.0 ? log(pmant) + (double)pexp * 0.69314718055994530942 : -INFINITY;
+                }
             }
             continue;
         }
@@ -4062,6 +4306,13 @@ void launch_fb_fast_vit(const KernelParams& p, int grid, bool half_spill, hipStr
     zero_job_counter(p, stream);
     if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 5>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
     else hipLaunchKernelGGL((fb_fast_kernel<false, 5>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
+    launch_likelihood_logs(p, stream);
+}
+void launch_fb_fast_smp(const KernelParams& p, int grid, bool half_spill, hipStream_t stream)
+{
+    zero_job_counter(p, stream);
+    if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 6>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
+    else hipLaunchKernelGGL((fb_fast_kernel<false, 6>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
     launch_likelihood_logs(p, stream);
 }
 int fb_xo_blocks_per_cu()

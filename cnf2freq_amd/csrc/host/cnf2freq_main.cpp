@@ -1,7 +1,8 @@
 // cnf2freq_main.cpp -- drop-in command line for the PlantImpute invocation of the reference
 // (demo.sh:37):
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
-//            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--remap F [--remap-iterations K]]
+//            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
+//            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
 // haplotyping sweep (doit) before its dump.  Rows of the last round go to --output, earlier ones to stdout; every
@@ -26,6 +27,13 @@
 // "name:chrom<TAB>s*<TAB>log posterior of the path" ("%.6lf"; "-<TAB>-" where the individual is skipped), one line per
 // marker of the 6 state bits as 0 / 1 in the column order of --crossovers ("-" where skipped), a blank line.  --output is
 // the same with or without it.  Single GPU only.
+//
+// --sample F [--draws K] [--seed S] (not flags of the reference): after the last round, and before a --remap changes the
+// map, K (1 .. 1024, default 1) inheritance paths of every analysed individual drawn from the posterior with seed S
+// (default 0; cnf2_sweep_sample).  Per chromosome, individual and draw a header "name:chrom<TAB>k<TAB>s<TAB>logp" (s the
+// drawn shift mode, logp "%.6lf" the log posterior probability of the drawn (mode, path); "-<TAB>-" where the individual is
+// skipped), one line per marker of the 6 state bits as for --viterbi, a blank line.  --output is the same with or without
+// it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
 // has no compute path of its own and fails if no GPU is present.  Out of scope: the toulbar2
@@ -74,6 +82,10 @@ struct Options {
     bool        rccl_selftest = false;   // --rccl-selftest: the RCCL transport's collectives with a world of one on GPU 0, then stop
     std::string crossovers;              // --crossovers F: crossover posteriors of the last round's state
     std::string viterbi;                 // --viterbi F: MAP inheritance paths of the last round's state
+    std::string sample;                  // --sample F: inheritance paths drawn from the posterior of the last round's state
+    int         draws = 1;               // --draws K
+    unsigned long long seed = 0;         // --seed S
+    bool        draws_set = false, seed_set = false;
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
     int         remap_iterations = 1;
     bool        remap_iterations_set = false;
@@ -121,6 +133,15 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--rccl-selftest") o.rccl_selftest = true;
         else if (a == "--crossovers") o.crossovers = val();
         else if (a == "--viterbi") o.viterbi = val();
+        else if (a == "--sample") o.sample = val();
+        else if (a == "--draws") {
+            o.draws     = atoi(val().c_str());
+            o.draws_set = true;
+        }
+        else if (a == "--seed") {
+            o.seed     = strtoull(val().c_str(), nullptr, 0);
+            o.seed_set = true;
+        }
         else if (a == "--remap") o.remap = val();
         else if (a == "--remap-iterations") {
             o.remap_iterations = atoi(val().c_str());
@@ -136,6 +157,7 @@ static bool parse(int argc, char** argv, Options& o)
 
 static void crossovers_and_remap(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void viterbi_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -222,6 +244,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     }
     if (out != stdout) fclose(out);
     if (world == 1 && !opt.viterbi.empty()) viterbi_paths(opt, P, ctx);
+    if (world == 1 && !opt.sample.empty()) sample_paths(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -309,6 +332,34 @@ static void viterbi_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
             fprintf(out, "\n");
         }
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.viterbi);
+}
+
+// --sample after the last round (single GPU), like --viterbi
+static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1, K = opt.draws;
+    std::vector<double>  f((size_t)N * C * 8), ll((size_t)N * C), lp((size_t)N * K * C);
+    std::vector<uint8_t> st((size_t)N * K * M);
+    std::vector<int32_t> sh((size_t)N * K * C);
+    if (cnf2_sweep_sample(ctx, 0, N, K, (uint64_t)opt.seed, f.data(), ll.data(), st.data(), sh.data(), lp.data(), 0) != CNF2_OK)
+        throw EngineError(CNF2_ERR_STATE, std::string("cnf2_sweep_sample: ") + cnf2_last_error(ctx));
+    FILE* out = fopen(opt.sample.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.sample);
+    for (int c = 0; c < C; c++)
+        for (int j = 0; j < N; j++)
+            for (int k = 0; k < K; k++) {
+                const size_t d = (size_t)j * K + k, e = d * C + c;
+                const int    s = sh[e];
+                if (s < 0) fprintf(out, "%s:%d\t%d\t-\t-\n", P.inds[P.dous[j]].name.c_str(), c + 1, k);
+                else fprintf(out, "%s:%d\t%d\t%d\t%.6lf\n", P.inds[P.dous[j]].name.c_str(), c + 1, k, s, lp[e]);
+                for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                    const int g = st[d * M + m];
+                    if (s < 0) fprintf(out, "-\t-\t-\t-\t-\t-\n");
+                    else fprintf(out, "%d\t%d\t%d\t%d\t%d\t%d\n", g & 1, (g >> 1) & 1, (g >> 2) & 1, (g >> 3) & 1, (g >> 4) & 1, (g >> 5) & 1);
+                }
+                fprintf(out, "\n");
+            }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.sample);
 }
 
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
@@ -413,6 +464,18 @@ int main(int argc, char** argv)
     }
     if (opt.gpus > 1 && !opt.viterbi.empty()) {
         fprintf(stderr, "--viterbi needs a single GPU (--gpus 1): the ranks' paths are not gathered\n");
+        return 2;
+    }
+    if (opt.gpus > 1 && !opt.sample.empty()) {
+        fprintf(stderr, "--sample needs a single GPU (--gpus 1): the ranks' draws are not gathered\n");
+        return 2;
+    }
+    if ((opt.draws_set || opt.seed_set) && opt.sample.empty()) {
+        fprintf(stderr, "--draws and --seed need --sample FILE\n");
+        return 2;
+    }
+    if (opt.draws < 1 || opt.draws > 1024) {
+        fprintf(stderr, "--draws must be between 1 and 1024\n");
         return 2;
     }
     if (opt.remap_iterations_set && opt.remap.empty()) {

@@ -282,6 +282,41 @@ int cnf2_sweep_crossovers(cnf2_ctx *ctx, int ind_begin, int ind_end, double *fac
 int cnf2_sweep_viterbi(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out,
                        double *logmax_out, uint8_t *state_out, int32_t *shift_out, uint32_t flags);
 
+/* Posterior sampling: n_draws whole (mode, path) draws from P(mode, path | data) for every analysed individual on every
+ * chromosome, by forward filtering and backward sampling in the model of the Viterbi and crossover calls (the sweep's
+ * path-free emission; no tie rule).  Draw k of individual i on a chromosome:
+ *   1. the mode s with weights exp(factors[s] - loglik) over the modes the dosage rows count (active, with a likelihood,
+ *      not 40 log-units below the total), renormalised over them;
+ *   2. the state at the last marker with weights alpha_last(g), alpha the forward vector after the marker's emission in
+ *      mode s;
+ *   3. for m = last-1 down to first the state g_m with weights alpha_m(g) T_m(g, g_m+1) (T the 64 x 64 Kronecker
+ *      transition of the gap; where the marker distance is <= 0 it is the identity and g_m = g_m+1).
+ * logp = log P(mode, path | data) = factors[s] - loglik + the log of w(chosen) / sum w of every state pick; it is comparable
+ * with the Viterbi path's log posterior (logmax[s*] - loglik) and never above it.
+ * Random numbers (all arithmetic mod 2^64): mix(z) = SplitMix64's output function of z (z += 0x9E3779B97F4A7C15, then the
+ * two xor-shift-multiply steps and a final xor-shift), key = mix(mix(mix(seed) ^ i) ^ k), u = (mix(key ^ j) >> 11) 2^-53,
+ * with i the absolute index of the analysed individual, k the draw, j = m for the state at marker m and j = n_markers + c
+ * for the mode on chromosome c.  A pick is an inverse CDF: weights laid on [0, W) in a fixed order, the first state whose
+ * running sum exceeds u W, or else (rounding) the last one with a positive weight; a weight of 0 is never chosen.  Modes
+ * are laid in ascending order, and so are the 64 states (STATE_ORDER of cnf2freq_amd/sampling.py is the identity).
+ * A draw depends on (seed, i, k) only: range splits, job order, CNF2_STATIC_JOBS and n_draws do not change it.
+ * A state is g = j*8 + lo as in cnf2_state_posterior; bit t of g is the meiosis of column t of cnf2_sweep_crossovers; the
+ * path is in the frame of the drawn mode.
+ *   n_draws      K, 1 .. 1024 (else CNF2_ERR_ARG, nothing written)
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal
+ *   state_out    [n][K][n_markers] (uint8), not NULL
+ *   shift_out    [n][K][n_chrom]   (int32) the drawn mode, not NULL
+ *   logp_out     [n][K][n_chrom]   (double) or NULL
+ * An individual is skipped on a chromosome where the sweep skips it: every draw there has states 0xFF, shift -1 and logp
+ * CNF2_IGNORED.  Host outputs are staged whole on the device (CNF2_ERR_NOMEM if that fails: split the individual range).
+ * One pass: untied windows through the fast kernel's sampling instantiation (likelihoods, then backward walks of up to 64
+ * draws in the same wave), tied windows through the tied kernel without rows (likelihoods) and then the same sampling
+ * instantiation.  Flags: CNF2_OUT_DEVICE (all five pointers are device pointers), CNF2_STATIC_JOBS, CNF2_FULL_SPILL and
+ * CNF2_TIES_GENERAL as in cnf2_sweep_viterbi; CNF2_MERGE_MODES, CNF2_XPOSE, CNF2_FLUSH_TINY and the dosage flags are
+ * ignored.  The call synchronises the context's stream once (the job list), also with CNF2_OUT_DEVICE. */
+int cnf2_sweep_sample(cnf2_ctx *ctx, int ind_begin, int ind_end, int n_draws, uint64_t seed, double *factors_out,
+                      double *loglik_out, uint8_t *state_out, int32_t *shift_out, double *logp_out, uint32_t flags);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every
