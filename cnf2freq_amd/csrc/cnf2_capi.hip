@@ -17,8 +17,54 @@
 
 #include "cnf2_device.h"
 #include "cnf2_emission.h"
+#include "cnf2_plan.h"
 
 using namespace cnf2;
+
+struct cnf2_ctx;
+static int fail(cnf2_ctx* ctx, int code, const char* fmt, ...);
+
+#define HIP_TRY(ctx, call)                                                                     \
+    do {                                                                                       \
+        hipError_t e_ = (call);                                                                \
+        if (e_ != hipSuccess)                                                                  \
+            return fail(ctx, e_ == hipErrorOutOfMemory ? CNF2_ERR_NOMEM : CNF2_ERR_HIP,        \
+                        "%s failed: %s", #call, hipGetErrorString(e_));                        \
+    } while (0)
+#define RC_TRY(call)                                                                           \
+    do {                                                                                       \
+        const int rc_ = (call);                                                                \
+        if (rc_) return rc_;                                                                   \
+    } while (0)
+
+// A device buffer the context owns: freed with the context (cnf2_ctx_destroy), so a new one cannot be forgotten there.
+template <class T>
+struct DevBuf {
+    T*     ptr = nullptr;
+    size_t cap = 0;          // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { (void)hipFree(ptr); }
+    operator T*() const { return ptr; }
+    int release(cnf2_ctx* ctx)
+    {
+        if (ptr) HIP_TRY(ctx, hipFree(ptr));
+        ptr = nullptr;
+        cap = 0;
+        return CNF2_OK;
+    }
+    // exactly `count` elements, whatever was held (freed first)
+    int alloc(cnf2_ctx* ctx, size_t count)
+    {
+        RC_TRY(release(ctx));
+        HIP_TRY(ctx, hipMalloc((void**)&ptr, count * sizeof(T)));
+        cap = count;
+        return CNF2_OK;
+    }
+    // at least `count` elements: what is held if it suffices, else exactly `count`
+    int ensure(cnf2_ctx* ctx, size_t count) { return (cap >= count && ptr) ? CNF2_OK : alloc(ctx, count); }
+};
 
 struct cnf2_ctx {
     int         device = -1;
@@ -34,118 +80,82 @@ struct cnf2_ctx {
     int                  n_markers = 0, n_chrom = 0;
     std::vector<int32_t> chromstarts;
     double               genrec[3] = {-0.02, -0.02, -0.02};
-    double2*             d_rho = nullptr;
-    double2*             d_tq = nullptr;
-    double*              d_logk = nullptr;
+    DevBuf<double2>      d_rho, d_tq;
+    DevBuf<double>       d_logk;
 
     // rows
-    int      n_rows = 0;
-    uint8_t* d_allele8 = nullptr;
-    double2* d_sure = nullptr;
-    double*  d_hw = nullptr;
+    int             n_rows = 0;
+    DevBuf<uint8_t> d_allele8;
+    DevBuf<double2> d_sure;
+    DevBuf<double>  d_hw;
 
     // pedigree
     HostPedigree        ped;
     std::vector<Window> windows;     // one per analysed individual
-    Window*             d_windows = nullptr;
+    DevBuf<Window>      d_windows;
     bool                windows_dirty = true;   // rows or pedigree changed since the last derivation
-    uint8_t*            d_rowflags = nullptr;
+    DevBuf<uint8_t>     d_rowflags;
     int                 fast_blocks_per_cu = 1;
     int                 reserve_blocks = 0;     // workgroup slots left free for concurrent kernels (RCCL)
     int                 batch_jobs = 0;         // cap on the jobs per batch of the batched consumers (0 = what memory allows)
 
     // workspace
-    Job*    d_jobs = nullptr;
-    size_t  jobs_cap = 0;
-    PackedJob* d_pjobs = nullptr;
-    size_t  pjobs_cap = 0;
-    double* d_spill = nullptr;
-    size_t  spill_bytes = 0;
-    double *d_factors = nullptr, *d_loglik = nullptr, *d_dosage = nullptr;
-    size_t  factors_cap = 0, loglik_cap = 0, dosage_cap = 0;
-    int32_t* d_lexp = nullptr;                 // binary exponents of the fast kernel's likelihoods: [n][C][8] then [n][C]
-    size_t   lexp_cap = 0;
-    unsigned long long* d_clock = nullptr;     // [4] clock stamps of the last plain fast-kernel launch
-    int*     d_jobnext = nullptr;              // [4] job counters of the fast-kernel launches in flight (KernelParams::job_next)
-    size_t   jobnext_cap = 0;
-    size_t   clock_cap = 0;
-    double* d_scratch = nullptr;     // small parity buffers
-    size_t  scratch_cap = 0;
+    DevBuf<Job>       d_jobs;
+    DevBuf<PackedJob> d_pjobs;
+    DevBuf<double>    d_spill;
+    DevBuf<double>    d_factors, d_loglik, d_dosage;
+    DevBuf<int32_t>   d_lexp;                  // binary exponents of the fast kernel's likelihoods: [n][C][8] then [n][C]
+    DevBuf<unsigned long long> d_clock;        // [4] clock stamps of the last plain fast-kernel launch
+    DevBuf<int>       d_jobnext;               // [4] job counters of the fast-kernel launches in flight (KernelParams::job_next)
+    DevBuf<double>    d_scratch;               // small parity buffers
 
     // crossover posteriors (cnf2_sweep_crossovers)
-    double*  d_xo_f = nullptr;            // likelihoods of the second pass over tied windows (crossover or Viterbi; not reported)
-    size_t   xo_f_cap = 0;
-    int      xo_blocks_per_cu = 1;        // occupancy of the general kernel's crossover instantiation
-    double*  d_xo = nullptr;              // [n][n_markers][6] per-individual rows (host-output calls that ask for them)
-    size_t   xo_cap = 0;
-    double*  d_xo_sum = nullptr;          // [n_markers][6]
-    size_t   xo_sum_cap = 0;
-    int32_t* d_xo_cnt = nullptr;          // [n_chrom]
-    size_t   xo_cnt_cap = 0;
+    DevBuf<double>  d_xo_f;               // likelihoods of the second pass over tied windows (any mode; not reported)
+    int             xo_blocks_per_cu = 1; // occupancy of the general kernel's crossover instantiation
+    DevBuf<double>  d_xo;                 // [n][n_markers][6] per-individual rows (host-output calls that ask for them)
+    DevBuf<double>  d_xo_sum;             // [n_markers][6]
+    DevBuf<int32_t> d_xo_cnt;             // [n_chrom]
 
     // Viterbi decoding (cnf2_sweep_viterbi), host-output calls
-    double*  d_vit_lm = nullptr;          // [n][n_chrom][8]
-    size_t   vit_lm_cap = 0;
-    uint8_t* d_vit_st = nullptr;          // [n][n_markers]
-    size_t   vit_st_cap = 0;
-    int32_t* d_vit_sh = nullptr;          // [n][n_chrom]
-    size_t   vit_sh_cap = 0;
+    DevBuf<double>  d_vit_lm;             // [n][n_chrom][8]
+    DevBuf<uint8_t> d_vit_st;             // [n][n_markers]
+    DevBuf<int32_t> d_vit_sh;             // [n][n_chrom]
 
     // posterior sampling (cnf2_sweep_sample), host-output calls
-    uint8_t* d_smp_st = nullptr;          // [n][K][n_markers]
-    size_t   smp_st_cap = 0;
-    int32_t* d_smp_sh = nullptr;          // [n][K][n_chrom]
-    size_t   smp_sh_cap = 0;
-    double*  d_smp_lp = nullptr;          // [n][K][n_chrom]
-    size_t   smp_lp_cap = 0;
+    DevBuf<uint8_t> d_smp_st;             // [n][K][n_markers]
+    DevBuf<int32_t> d_smp_sh;             // [n][K][n_chrom]
+    DevBuf<double>  d_smp_lp;             // [n][K][n_chrom]
 
     // batched HOT LOOP 2 (cnf2_sweep_accumulate)
     std::vector<int32_t> slot_rec;   // [n_dous][7] record per window slot (derive_window), -1 none
-    int32_t* d_slot_rec = nullptr;
-    int32_t* d_desc = nullptr;
-    uint8_t* d_rec_empty = nullptr;
-    size_t   rec_cap = 0;
-    double*  d_wbuf = nullptr;
-    size_t   wbuf_cap = 0;
-    double * d_acc_inf = nullptr, *d_acc_hb = nullptr, *d_acc_hc = nullptr, *d_acc_hz = nullptr;
-    size_t   acc_inf_cap = 0, acc_hb_cap = 0, acc_hc_cap = 0, acc_hz_cap = 0;
+    DevBuf<int32_t> d_slot_rec;
+    DevBuf<int32_t> d_desc;          // [n_rec]; allocated together with d_rec_empty (ensure_rec_tables)
+    DevBuf<uint8_t> d_rec_empty;
+    DevBuf<double>  d_wbuf;
+    DevBuf<double>  d_acc_inf, d_acc_hb, d_acc_hc, d_acc_hz;
 
     // per-iteration updates (cnf2_update_pass) and pre-processing scans
-    uint8_t* d_prior_allele8 = nullptr;
-    double2* d_prior_sure = nullptr;
-    uint8_t* d_has_prior = nullptr;      // [n_rec]
-    bool     priors_set = false;
-    int32_t* d_row_of = nullptr;
-    int32_t* d_children = nullptr;
-    int32_t* d_chromstarts = nullptr;
-    size_t   upd_rec_cap = 0;
-    uint8_t* d_anyinfo = nullptr;
-    size_t   anyinfo_cap = 0;
-    double * d_fw = nullptr, *d_ratio = nullptr;
-    size_t   fw_cap = 0, ratio_cap = 0;
-    int*     d_hits = nullptr;
-    unsigned long long* d_flow_next = nullptr;
-    double*  d_flow_out = nullptr;
-    double*  d_todo = nullptr;            // flows set aside by the scouts (3 doubles each)
-    size_t   todo_cap = 0;
-    double*  d_part = nullptr;            // CNF2_DETERMINISTIC rows
-    size_t   part_cap = 0;
-    int32_t* d_gather = nullptr;          // rec_start [n_rec + 1] followed by the list
-    size_t   gather_cap = 0;
-    size_t   flow_out_cap = 0;
-    int32_t* d_pathlog = nullptr;
-    size_t   pathlog_cap = 0;
-    int      pathlog_n = 0;
-    int32_t* d_updrecs = nullptr;         // the records an update pass is restricted to
-    size_t   updrecs_cap = 0;
-    int32_t* d_xidx = nullptr;            // index lists of the exchange packers
-    size_t   xidx_cap = 0;
-    uint8_t* d_xbuf = nullptr;            // staging buffer of the exchanges (cnf2_exchange_buffer)
-    size_t   xbuf_cap = 0;
-    Window*  d_scanwin = nullptr;
-    size_t   scanwin_cap = 0;
-    uint8_t* d_okout = nullptr;
-    size_t   okout_cap = 0;
+    DevBuf<uint8_t> d_prior_allele8;
+    DevBuf<double2> d_prior_sure;
+    DevBuf<uint8_t> d_has_prior;         // [n_rec]
+    bool            priors_set = false;
+    DevBuf<int32_t> d_row_of, d_children;    // [n_rec], allocated together
+    DevBuf<int32_t> d_chromstarts;       // [65536]
+    DevBuf<uint8_t> d_anyinfo;
+    DevBuf<double>  d_fw, d_ratio;
+    DevBuf<int>     d_hits;              // [1]
+    DevBuf<unsigned long long> d_flow_next;   // [32]
+    DevBuf<double>  d_flow_out;
+    DevBuf<double>  d_todo;              // flows set aside by the scouts (3 doubles each)
+    DevBuf<double>  d_part;              // CNF2_DETERMINISTIC rows
+    DevBuf<int32_t> d_gather;            // rec_start [n_rec + 1] followed by the list
+    DevBuf<int32_t> d_pathlog;
+    int             pathlog_n = 0;
+    DevBuf<int32_t> d_updrecs;           // the records an update pass is restricted to
+    DevBuf<int32_t> d_xidx;              // index lists of the exchange packers
+    DevBuf<uint8_t> d_xbuf;              // staging buffer of the exchanges (cnf2_exchange_buffer)
+    DevBuf<Window>  d_scanwin;
+    DevBuf<uint8_t> d_okout;
 };
 
 static std::string g_create_error;
@@ -162,23 +172,84 @@ static int fail(cnf2_ctx* ctx, int code, const char* fmt, ...)
     return code;
 }
 
-#define HIP_TRY(ctx, call)                                                                     \
-    do {                                                                                       \
-        hipError_t e_ = (call);                                                                \
-        if (e_ != hipSuccess)                                                                  \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? CNF2_ERR_NOMEM : CNF2_ERR_HIP,        \
-                        "%s failed: %s", #call, hipGetErrorString(e_));                        \
-    } while (0)
+// ------------------------------------------------------------------------------------------------
+// Function templates of the entry points below (outside their extern "C" block), and what they use of it
+// ------------------------------------------------------------------------------------------------
+static int ready(cnf2_ctx* ctx);
+static int run_store(cnf2_ctx* ctx, int ind, int chrom, Stage2Params* q, size_t extra, double** extra_ptr);
 
-template <class T>
-static int ensure(cnf2_ctx* ctx, T** ptr, size_t* cap, size_t count)
+// The body the stage-2 queries share: the store of (ind, chrom), `launch(q, d_out)` fills n doubles behind it, and they are
+// copied to `out`.  marker (the single-marker queries) must lie on the chromosome.
+template <class Launch>
+static int stage2_query(cnf2_ctx* ctx, int ind, int chrom, const int* marker, size_t n, double* out, Launch launch)
 {
-    if (*cap >= count && *ptr) return CNF2_OK;
-    if (*ptr) HIP_TRY(ctx, hipFree(*ptr));
-    *ptr = nullptr;
-    *cap = 0;
-    HIP_TRY(ctx, hipMalloc((void**)ptr, count * sizeof(T)));
-    *cap = count;
+    Stage2Params q;
+    double*      d_out = nullptr;
+    RC_TRY(run_store(ctx, ind, chrom, &q, n, &d_out));
+    if (marker && (*marker < q.first || *marker >= q.first + q.len))
+        return fail(ctx, CNF2_ERR_ARG, "marker not on this chromosome");
+    launch(q, d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// ... with per_marker doubles for every marker of the chromosome
+template <class Launch>
+static int stage2_rows(cnf2_ctx* ctx, int ind, int chrom, size_t per_marker, double* rows_out, Launch launch)
+{
+    RC_TRY(ready(ctx));
+    if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
+    const size_t n = (size_t)(ctx->chromstarts[chrom + 1] - ctx->chromstarts[chrom]) * per_marker;
+    return stage2_query(ctx, ind, chrom, nullptr, n, rows_out, launch);
+}
+
+// An output of a sweep mode.  With CNF2_OUT_DEVICE (`dev`) the caller's pointer is device memory and the kernels write
+// through it; else it is host memory (null: not asked for) and the output is staged whole in `buf`.  *field = where the
+// kernels write, null for none.
+template <class T>
+static int stage_out(cnf2_ctx* ctx, bool dev, T* user, DevBuf<T>& buf, size_t count, T** field)
+{
+    *field = user;
+    if (dev || !user) return CNF2_OK;
+    *field = nullptr;
+    if (count == 0) return CNF2_OK;
+    RC_TRY(buf.ensure(ctx, count));
+    *field = buf;
+    return CNF2_OK;
+}
+// ... and a staged output back to the caller's host memory
+template <class T>
+static int fetch_out(cnf2_ctx* ctx, T* user, const T* staged, size_t count)
+{
+    if (staged) HIP_TRY(ctx, hipMemcpyAsync(user, staged, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+    return CNF2_OK;
+}
+
+// What the two batched consumers (cnf2_sweep_accumulate, cnf2_sweep_turn_scan) share before their launches: the job list on
+// the device, the plan of grid and batches from the memory that is free (cnf2_plan.h), and the spill slots
+struct Batched {
+    JobPlan   list;        // untied windows (fast kernel) first, tied ones after
+    BatchPlan plan;
+    int       max_len = 0; // longest chromosome
+};
+// The launches of a batched consumer: the untied windows' jobs (pass 0), then the tied ones' (pass 1), in batches.  Sets
+// p->jobs / p->n_jobs and hands `body` -- the sweep launch and the consumer's -- the pass, the sweep's grid and the length
+// of the batch's longest job, which is its first (chrom_order)
+template <class Body>
+static int for_each_batch(cnf2_ctx* ctx, const Batched& b, KernelParams* p, Body body)
+{
+    const std::vector<Job>& jobs = b.list.jobs;
+    for (int pass = 0; pass < 2; pass++) {
+        const size_t lo = pass ? b.list.n_fast : 0, hi = pass ? jobs.size() : b.list.n_fast;
+        for (size_t b0 = lo; b0 < hi; b0 += b.plan.batch) {
+            const size_t nb = std::min(hi - b0, b.plan.batch);
+            p->jobs   = ctx->d_jobs + b0;
+            p->n_jobs = (int)nb;
+            RC_TRY(body(pass, grid_for(nb, b.plan.grid_cap), jobs[b0].last - jobs[b0].first + 1));
+        }
+    }
     return CNF2_OK;
 }
 
@@ -231,69 +302,14 @@ void cnf2_ctx_destroy(cnf2_ctx* ctx)
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    (void)hipFree(ctx->d_rho);
-    (void)hipFree(ctx->d_tq);
-    (void)hipFree(ctx->d_logk);
-    (void)hipFree(ctx->d_allele8);
-    (void)hipFree(ctx->d_sure);
-    (void)hipFree(ctx->d_hw);
-    (void)hipFree(ctx->d_windows);
-    (void)hipFree(ctx->d_rowflags);
-    (void)hipFree(ctx->d_jobs);
-    (void)hipFree(ctx->d_pjobs);
-    (void)hipFree(ctx->d_spill);
-    (void)hipFree(ctx->d_factors);
-    (void)hipFree(ctx->d_loglik);
-    (void)hipFree(ctx->d_lexp);
-    (void)hipFree(ctx->d_clock);
-    (void)hipFree(ctx->d_jobnext);
-    (void)hipFree(ctx->d_dosage);
-    (void)hipFree(ctx->d_scratch);
-    (void)hipFree(ctx->d_xo);
-    (void)hipFree(ctx->d_xo_f);
-    (void)hipFree(ctx->d_xo_sum);
-    (void)hipFree(ctx->d_xo_cnt);
-    (void)hipFree(ctx->d_vit_lm);
-    (void)hipFree(ctx->d_vit_st);
-    (void)hipFree(ctx->d_vit_sh);
-    (void)hipFree(ctx->d_smp_st);
-    (void)hipFree(ctx->d_smp_sh);
-    (void)hipFree(ctx->d_smp_lp);
-    (void)hipFree(ctx->d_slot_rec);
-    (void)hipFree(ctx->d_desc);
-    (void)hipFree(ctx->d_rec_empty);
-    (void)hipFree(ctx->d_wbuf);
-    (void)hipFree(ctx->d_acc_inf);
-    (void)hipFree(ctx->d_acc_hb);
-    (void)hipFree(ctx->d_acc_hc);
-    (void)hipFree(ctx->d_acc_hz);
-    (void)hipFree(ctx->d_prior_allele8);
-    (void)hipFree(ctx->d_prior_sure);
-    (void)hipFree(ctx->d_has_prior);
-    (void)hipFree(ctx->d_row_of);
-    (void)hipFree(ctx->d_children);
-    (void)hipFree(ctx->d_chromstarts);
-    (void)hipFree(ctx->d_anyinfo);
-    (void)hipFree(ctx->d_fw);
-    (void)hipFree(ctx->d_ratio);
-    (void)hipFree(ctx->d_hits);
-    (void)hipFree(ctx->d_flow_next);
-    (void)hipFree(ctx->d_flow_out);
-    (void)hipFree(ctx->d_todo);
-    (void)hipFree(ctx->d_part);
-    (void)hipFree(ctx->d_gather);
-    (void)hipFree(ctx->d_updrecs);
-    (void)hipFree(ctx->d_xidx);
-    (void)hipFree(ctx->d_xbuf);
-    (void)hipFree(ctx->d_scanwin);
-    (void)hipFree(ctx->d_pathlog);
-    (void)hipFree(ctx->d_okout);
-    (void)hipEventDestroy(ctx->ev0);
-    (void)hipEventDestroy(ctx->ev1);
-    (void)hipEventDestroy(ctx->ev2);
-    (void)hipStreamDestroy(ctx->stream2);
-    (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    const hipStream_t stream = ctx->stream, stream2 = ctx->stream2;
+    const hipEvent_t  ev0 = ctx->ev0, ev1 = ctx->ev1, ev2 = ctx->ev2;
+    delete ctx;                      // frees every device buffer (DevBuf) before the streams and events go
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    (void)hipEventDestroy(ev2);
+    (void)hipStreamDestroy(stream2);
+    (void)hipStreamDestroy(stream);
 }
 
 void* cnf2_stream(cnf2_ctx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
@@ -348,9 +364,7 @@ int cnf2_upload_map(cnf2_ctx* ctx, const double* pos, int n_markers, const int32
         }
         rho[m] = r;
     }
-    if (ctx->d_rho) HIP_TRY(ctx, hipFree(ctx->d_rho));
-    ctx->d_rho = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_rho, sizeof(double2) * n_markers));
+    RC_TRY(ctx->d_rho.alloc(ctx, n_markers));
     HIP_TRY(ctx, hipMemcpy(ctx->d_rho, rho.data(), sizeof(double2) * n_markers, hipMemcpyHostToDevice));
     // fast kernel: butterflies x' = x + t * partner with t = r / (1 - r); the dropped scalar
     // (1-r0)^4 (1-r1)^2 per gap (bits with TYPEGENS 0: four, TYPEGENS 1: two, settings.h:23) is
@@ -362,12 +376,10 @@ int cnf2_upload_map(cnf2_ctx* ctx, const double* pos, int n_markers, const int32
             tq[m] = make_double2(rho[m].x / (1.0 - rho[m].x), rho[m].y / (1.0 - rho[m].y));
             if (m + 1 < chromstarts[c + 1]) logk[c] += 4.0 * log1p(-rho[m].x) + 2.0 * log1p(-rho[m].y);
         }
-    if (ctx->d_tq) HIP_TRY(ctx, hipFree(ctx->d_tq));
-    if (ctx->d_logk) HIP_TRY(ctx, hipFree(ctx->d_logk));
-    ctx->d_tq = nullptr;
-    ctx->d_logk = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_tq, sizeof(double2) * n_markers));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_logk, sizeof(double) * n_chrom));
+    RC_TRY(ctx->d_tq.release(ctx));
+    RC_TRY(ctx->d_logk.release(ctx));
+    RC_TRY(ctx->d_tq.alloc(ctx, n_markers));
+    RC_TRY(ctx->d_logk.alloc(ctx, n_chrom));
     HIP_TRY(ctx, hipMemcpy(ctx->d_tq, tq.data(), sizeof(double2) * n_markers, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_logk, logk.data(), sizeof(double) * n_chrom, hipMemcpyHostToDevice));
     return CNF2_OK;
@@ -418,17 +430,14 @@ int cnf2_upload_rows(cnf2_ctx* ctx, int n_rows, const uint8_t* allele, const dou
     if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "upload the map before the rows");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_allele8) HIP_TRY(ctx, hipFree(ctx->d_allele8));
-    if (ctx->d_sure) HIP_TRY(ctx, hipFree(ctx->d_sure));
-    if (ctx->d_hw) HIP_TRY(ctx, hipFree(ctx->d_hw));
-    ctx->d_allele8 = nullptr;
-    ctx->d_sure = nullptr;
-    ctx->d_hw = nullptr;
+    RC_TRY(ctx->d_allele8.release(ctx));
+    RC_TRY(ctx->d_sure.release(ctx));
+    RC_TRY(ctx->d_hw.release(ctx));
     ctx->n_rows = 0;
     size_t cnt = (size_t)n_rows * ctx->n_markers;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_allele8, cnt));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_sure, cnt * sizeof(double2)));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_hw, cnt * sizeof(double)));
+    RC_TRY(ctx->d_allele8.alloc(ctx, cnt));
+    RC_TRY(ctx->d_sure.alloc(ctx, cnt));
+    RC_TRY(ctx->d_hw.alloc(ctx, cnt));
     ctx->n_rows = n_rows;
     ctx->windows_dirty = true;
     ctx->priors_set = false;
@@ -508,9 +517,7 @@ static int prepare_windows(cnf2_ctx* ctx)
     if (!ctx->windows_dirty) return CNF2_OK;
     HostPedigree& P = ctx->ped;
     const int n_dous = (int)P.dous.size();
-    if (ctx->d_rowflags) HIP_TRY(ctx, hipFree(ctx->d_rowflags));
-    ctx->d_rowflags = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_rowflags, ctx->n_rows));
+    RC_TRY(ctx->d_rowflags.alloc(ctx, ctx->n_rows));
     launch_row_flags(ctx->d_allele8, ctx->d_sure, ctx->n_rows, ctx->n_markers, ctx->d_rowflags, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     P.row_hom.assign(ctx->n_rows, 0);
@@ -519,14 +526,12 @@ static int prepare_windows(cnf2_ctx* ctx)
     ctx->windows.resize(n_dous);
     ctx->slot_rec.assign((size_t)n_dous * 7, -1);
     for (int j = 0; j < n_dous; j++) derive_window(P, P.dous[j], &ctx->windows[j], ctx->slot_rec.data() + (size_t)j * 7);
-    if (ctx->d_windows) HIP_TRY(ctx, hipFree(ctx->d_windows));
-    if (ctx->d_slot_rec) HIP_TRY(ctx, hipFree(ctx->d_slot_rec));
-    ctx->d_windows = nullptr;
-    ctx->d_slot_rec = nullptr;
+    RC_TRY(ctx->d_windows.release(ctx));
+    RC_TRY(ctx->d_slot_rec.release(ctx));
     if (n_dous > 0) {
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_windows, sizeof(Window) * n_dous));
+        RC_TRY(ctx->d_windows.alloc(ctx, n_dous));
         HIP_TRY(ctx, hipMemcpy(ctx->d_windows, ctx->windows.data(), sizeof(Window) * n_dous, hipMemcpyHostToDevice));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_slot_rec, sizeof(int32_t) * 7 * n_dous));
+        RC_TRY(ctx->d_slot_rec.alloc(ctx, (size_t)7 * n_dous));
         HIP_TRY(ctx, hipMemcpy(ctx->d_slot_rec, ctx->slot_rec.data(), sizeof(int32_t) * 7 * n_dous, hipMemcpyHostToDevice));
     }
     ctx->windows_dirty = false;
@@ -561,10 +566,19 @@ int cnf2_window_table(cnf2_ctx* ctx, int32_t* out17_all)
     if (!ctx || !out17_all) return CNF2_ERR_ARG;
     const int n = (int)ctx->windows.size();
     for (int j = 0; j < n; j++) {
-        const int rc = cnf2_window_info(ctx, j, out17_all + (size_t)j * 17);
-        if (rc) return rc;
+        RC_TRY(cnf2_window_info(ctx, j, out17_all + (size_t)j * 17));
     }
     return CNF2_OK;
+}
+
+// the per-record tables of the accumulate and update kernels: one capacity, freed and allocated together
+static int ensure_rec_tables(cnf2_ctx* ctx, size_t n_rec)
+{
+    if (ctx->d_desc.cap >= n_rec && ctx->d_rec_empty.cap >= n_rec) return CNF2_OK;
+    RC_TRY(ctx->d_desc.release(ctx));
+    RC_TRY(ctx->d_rec_empty.release(ctx));
+    RC_TRY(ctx->d_desc.alloc(ctx, n_rec));
+    return ctx->d_rec_empty.alloc(ctx, n_rec);
 }
 
 static int ready(cnf2_ctx* ctx)
@@ -573,15 +587,14 @@ static int ready(cnf2_ctx* ctx)
     if (!ctx->d_rho || !ctx->d_allele8 || ctx->ped.n_rec == 0)
         return fail(ctx, CNF2_ERR_STATE, "map, rows and pedigree must be uploaded first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = prepare_windows(ctx);
-    if (rc) return rc;
+    RC_TRY(prepare_windows(ctx));
     const size_t ne = ctx->windows.size() * (size_t)ctx->n_chrom;
-    if ((rc = ensure(ctx, &ctx->d_lexp, &ctx->lexp_cap, ne * 9 + 1))) return rc;
+    RC_TRY(ctx->d_lexp.ensure(ctx, ne * 9 + 1));
     if (!ctx->d_clock) {
-        if ((rc = ensure(ctx, &ctx->d_clock, &ctx->clock_cap, (size_t)4))) return rc;
+        RC_TRY(ctx->d_clock.ensure(ctx, (size_t)4));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_clock, 0, 4 * sizeof(unsigned long long), ctx->stream));
     }
-    if ((rc = ensure(ctx, &ctx->d_jobnext, &ctx->jobnext_cap, (size_t)4))) return rc;
+    RC_TRY(ctx->d_jobnext.ensure(ctx, (size_t)4));
     return CNF2_OK;
 }
 
@@ -602,201 +615,73 @@ static void base_params(cnf2_ctx* ctx, KernelParams* p)
     p->job_next  = ctx->d_jobnext;
 }
 
-static int max_chrom_len(const cnf2_ctx* ctx)
+static int longest_chrom(const cnf2_ctx* ctx) { return max_chrom_len(ctx->chromstarts.data(), ctx->n_chrom); }
+
+// the job list (cnf2_plan.h) of the analysed individuals [ind_begin, ind_begin + n)
+static JobPlan job_plan(const cnf2_ctx* ctx, int ind_begin, int n, uint32_t flags)
 {
-    int mx = 0;
-    for (int c = 0; c < ctx->n_chrom; c++) {
-        int l = ctx->chromstarts[c + 1] - ctx->chromstarts[c];
-        if (l > mx) mx = l;
-    }
-    return mx;
+    return plan_jobs(ctx->windows.data(), ctx->chromstarts.data(), ctx->n_chrom, ind_begin, n, flags, ctx->ped.row_hom.data());
 }
 
-// A batch of the batched consumers is swept by the resident waves in rounds (a wave takes the next job when it has finished
-// one): 6.1 rounds take the time of 7.  When the jobs do not fit one batch, a batch is a whole number of rounds.
-static size_t whole_rounds(size_t batch, size_t n_jobs, int grid_cap)
-{
-    const size_t waves = (size_t)grid_cap * CNF2_WAVES_PER_BLOCK;
-    if (batch >= n_jobs || batch < waves) return batch;
-    return batch / waves * waves;
-}
-
-// The chromosomes in the order their jobs are listed: longest first (ties in map order).  The waves of a launch take the
-// jobs in list order (KernelParams::job_next), so the long jobs start first and a launch ends on the short ones; the jobs of
-// one chromosome keep the order of the individuals, so nothing that adds up over individuals sees a difference.
-static std::vector<int> chrom_order(const cnf2_ctx* ctx)
-{
-    std::vector<int> o(ctx->n_chrom);
-    for (int c = 0; c < ctx->n_chrom; c++) o[c] = c;
-    std::stable_sort(o.begin(), o.end(), [&](int a, int b) {
-        return ctx->chromstarts[a + 1] - ctx->chromstarts[a] > ctx->chromstarts[b + 1] - ctx->chromstarts[b];
-    });
-    return o;
-}
-
-// crossover mode of a sweep (cnf2_sweep_crossovers): device outputs of the posteriors
-struct XoArgs {
-    double*  xo;     // [n][n_markers][6] or null
-    double*  sum;    // [n_markers][6], zeroed by the caller
-    int32_t* cnt;    // [n_chrom], zeroed by the caller
-};
-// Viterbi mode of a sweep (cnf2_sweep_viterbi): device outputs
-struct VitArgs {
-    double*  logmax;   // [n][n_chrom][8]
-    uint8_t* state;    // [n][n_markers]
-    int32_t* shift;    // [n][n_chrom]
-};
-// sampling mode of a sweep (cnf2_sweep_sample): device outputs and the generator's arguments
-struct SmpArgs {
-    uint8_t*           state;   // [n][K][n_markers]
-    int32_t*           shift;   // [n][K][n_chrom]
-    double*            logp;    // [n][K][n_chrom] or null
-    int                draws;   // K
-    unsigned long long seed;
+// What a sweep leaves besides the likelihoods: its mode with that mode's device outputs
+struct SweepMode {
+    SweepVariant variant = SW_PLAIN;   // SW_PLAIN (cnf2_sweep: the rows), SW_CROSSOVERS, SW_VITERBI or SW_SAMPLING
+    // SW_CROSSOVERS (cnf2_sweep_crossovers)
+    double*  xo = nullptr;             // [n][n_markers][6] or null
+    double*  xo_sum = nullptr;         // [n_markers][6], zeroed by the caller
+    int32_t* xo_cnt = nullptr;         // [n_chrom], zeroed by the caller
+    // SW_VITERBI (cnf2_sweep_viterbi) and, with a leading [K] of draws per individual, SW_SAMPLING (cnf2_sweep_sample)
+    uint8_t* state = nullptr;          // [n][n_markers]
+    int32_t* shift = nullptr;          // [n][n_chrom]
+    double*  logmax = nullptr;         // Viterbi: [n][n_chrom][8]
+    double*  logp = nullptr;           // sampling: [n][K][n_chrom] or null
+    int      draws = 0;                // sampling: K
+    unsigned long long seed = 0;       // sampling: the generator's seed
 };
 
-// cnf2_sweep, and with xo its crossover mode: the untied windows through the fast kernel's crossover instantiation (one
+// cnf2_sweep, and its modes.  Crossover mode: the untied windows through the fast kernel's crossover instantiation (one
 // pass: likelihoods and posteriors), the tied ones through the tied kernel without rows (their likelihoods, as cnf2_sweep
-// forms them) and then the general kernel's crossover instantiation (their posteriors).  With vit its Viterbi mode: the same
-// routing, with the fast kernel's Viterbi instantiation in place of both crossover instantiations.  With smp its sampling
-// mode: the untied windows through the fast kernel's sampling instantiation (one pass: likelihoods and draws), the tied ones
-// through the tied kernel without rows (likelihoods) and then the same sampling instantiation (draws)
+// forms them) and then the general kernel's crossover instantiation (their posteriors).  Viterbi mode: the same routing,
+// with the fast kernel's Viterbi instantiation in place of both crossover instantiations.  Sampling mode: the untied windows
+// through the fast kernel's sampling instantiation (one pass: likelihoods and draws), the tied ones through the tied kernel
+// without rows (likelihoods) and then the same sampling instantiation (draws)
 static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
-                      uint32_t flags, const XoArgs* xo, const VitArgs* vit = nullptr, const SmpArgs* smp = nullptr)
+                      uint32_t flags, const SweepMode& mode)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     const int n_all = (int)ctx->windows.size();
     if (ind_begin < 0 || ind_end > n_all || ind_begin > ind_end) return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
-    if (xo || vit || smp) flags &= ~(uint32_t)(CNF2_MERGE_MODES | CNF2_XPOSE | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_RAW_DOSAGE);
-    const bool want_dosage = !(flags & CNF2_NO_DOSAGE) && !xo && !vit && !smp;
+    const bool plain = mode.variant == SW_PLAIN;
+    if (!plain) flags &= ~(uint32_t)(CNF2_MERGE_MODES | CNF2_XPOSE | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_RAW_DOSAGE);
+    const bool want_dosage = !(flags & CNF2_NO_DOSAGE) && plain;
     if (!factors_out || !loglik_out || (want_dosage && !dosage_out)) return fail(ctx, CNF2_ERR_ARG, "output pointer is NULL");
     const int n = ind_end - ind_begin;
     if (n == 0) return CNF2_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
-    const size_t n_jobs = (size_t)n * ctx->n_chrom;
-    if (n_jobs > 0x7fffffff) return fail(ctx, CNF2_ERR_ARG, "too many jobs in one call");
-    // job list: individuals x chromosomes (the loops at cnF2freq.cpp:5283 and 5294), windows
-    // without an active tie group first (fast kernel), tied windows after (general kernel)
-    // CNF2_MERGE_MODES: windows whose two parents are homozygous with equal sure everywhere go four to a
-    // wavefront (fb_packed_kernel); groups are formed per chromosome, what does not fill a group of four
-    // stays with the ordinary kernel
-    const bool merge = (flags & CNF2_MERGE_MODES) && !(flags & (CNF2_FULL_SPILL | CNF2_FLUSH_TINY));
-    auto mergeable = [&](const Window& w) {
-        if (w.n_groups > 0 && !(flags & CNF2_NO_TIES)) return false;
-        if (w.shiftignore != 0 || w.shiftend != 8 || (w.flags[0] & SLOT_FOUNDER)) return false;
-        for (int k = 1; k <= 4; k += 3) {
-            if (!(w.flags[k] & SLOT_PRESENT) || w.row[k] < 0) return false;
-            if (!ctx->ped.row_hom[w.row[k]]) return false;
-        }
-        return true;
-    };
-    std::vector<uint8_t>   packed(merge ? n : 0, 0);
-    std::vector<PackedJob> pjobs;
-    if (merge) {
-        // a group shares the producer's instantiation: windows whose grandparents are all present and
-        // homozygous everywhere (SLOT_HOM) are grouped apart from the others
-        auto homleaf = [&](const Window& w) {
-            const int gp = w.flags[2] & w.flags[3] & w.flags[5] & w.flags[6];
-            return (gp & SLOT_HOM) && (gp & SLOT_PRESENT);
-        };
-        for (int cls = 0; cls < 2; cls++) {
-            std::vector<int> el;
-            for (int j = 0; j < n; j++) {
-                const Window& w = ctx->windows[ind_begin + j];
-                if (mergeable(w) && (homleaf(w) ? 1 : 0) == cls) el.push_back(j);
-            }
-            const size_t full = el.size() / 4 * 4;
-            for (size_t k = 0; k < full; k++) packed[el[k]] = 1;
-            for (int c : chrom_order(ctx))
-                for (size_t k = 0; k < full; k += 4) {
-                    PackedJob pj;
-                    for (int i = 0; i < 4; i++) pj.ind[i] = el[k + i];
-                    pj.first   = ctx->chromstarts[c];
-                    pj.last    = ctx->chromstarts[c + 1] - 1;
-                    pj.chrom   = c;
-                    pj.homleaf = cls;
-                    pjobs.push_back(pj);
-                }
-        }
-    }
-    const size_t n_packed = pjobs.size();
-    std::vector<Job> jobs;
-    jobs.reserve(n_jobs);
-    size_t n_fast = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        for (int c : chrom_order(ctx))
-            for (int j = 0; j < n; j++) {
-                if (merge && packed[j]) continue;
-                // (CNF2_FLUSH_TINY: every window takes the general kernel's route, the second list)
-                const bool tied = (ctx->windows[ind_begin + j].n_groups > 0 && !(flags & CNF2_NO_TIES)) || (flags & CNF2_FLUSH_TINY);
-                if (tied != (pass == 1)) continue;
-                Job jb;
-                jb.ind   = j;
-                jb.first = ctx->chromstarts[c];
-                jb.last  = ctx->chromstarts[c + 1] - 1;
-                jb.chrom = c;
-                jobs.push_back(jb);
-            }
-        if (pass == 0) n_fast = jobs.size();
-    }
-    const size_t n_general = jobs.size() - n_fast;
-    rc = ensure(ctx, &ctx->d_jobs, &ctx->jobs_cap, jobs.size() + 1);
-    if (rc) return rc;
-    if (!jobs.empty())
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice, ctx->stream));
+    if ((size_t)n * ctx->n_chrom > 0x7fffffff) return fail(ctx, CNF2_ERR_ARG, "too many jobs in one call");
+    const JobPlan jp = job_plan(ctx, ind_begin, n, flags);
+    const size_t  n_fast = jp.n_fast, n_general = jp.jobs.size() - n_fast, n_packed = jp.pjobs.size();
+    RC_TRY(ctx->d_jobs.ensure(ctx, jp.jobs.size() + 1));
+    if (!jp.jobs.empty())
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_jobs, jp.jobs.data(), sizeof(Job) * jp.jobs.size(), hipMemcpyHostToDevice, ctx->stream));
     if (n_packed > 0) {
-        rc = ensure(ctx, &ctx->d_pjobs, &ctx->pjobs_cap, n_packed);
-        if (rc) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pjobs, pjobs.data(), sizeof(PackedJob) * n_packed, hipMemcpyHostToDevice, ctx->stream));
+        RC_TRY(ctx->d_pjobs.ensure(ctx, n_packed));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pjobs, jp.pjobs.data(), sizeof(PackedJob) * n_packed, hipMemcpyHostToDevice, ctx->stream));
     }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // the job vectors go out of scope
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copies have read the job vectors)
 
-    // grids: one wave per job in flight, capped at what is resident so that the spill stays small
-    auto grid_for = [&](size_t nj, int per_cu) {
-        int g   = (int)((nj + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
-        int cap = ctx->n_cu * per_cu - ctx->reserve_blocks;
-        if (cap < 1) cap = 1;
-        return g > cap ? cap : g;
-    };
-    // the packed kernel runs before the ordinary fast kernel on the same stream and in the same spill slots
-    int grid_fast = grid_for(n_fast > n_packed ? n_fast : n_packed, ctx->fast_blocks_per_cu);
-    int grid_gen  = grid_for(n_general, ctx->blocks_per_cu);
-    const size_t stride = (size_t)max_chrom_len(ctx) * 528;   // covers every layout: 520 or 528 doubles per (pair of) marker(s), 512 in the general kernel
-    {
-        // One spill slot per resident wave.  Long chromosomes make slots big: keep the spill within
-        // ~60 % of what is free (plus what the context already holds) by running fewer waves.
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-        const size_t budget   = (size_t)((double)(free_b + ctx->spill_bytes) * 0.6);
-        const size_t per_blk  = (size_t)CNF2_WAVES_PER_BLOCK * stride * sizeof(double);
-        const size_t max_blks = budget / per_blk;
-        if (max_blks < 1)
-            return fail(ctx, CNF2_ERR_NOMEM, "a chromosome of %d markers needs %zu MB of spill per block, %zu MB free",
-                        max_chrom_len(ctx), per_blk >> 20, free_b >> 20);
-        if ((size_t)grid_fast > max_blks) grid_fast = (int)max_blks;
-        if ((size_t)grid_gen > max_blks) grid_gen = (int)max_blks;
-    }
-    if ((n_fast > 0 || n_packed > 0) && n_general > 0) {
-        // both kernels run side by side on two streams with disjoint spill slots: share the budget
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-        const size_t budget   = (size_t)((double)(free_b + ctx->spill_bytes) * 0.6);
-        const size_t per_blk  = (size_t)CNF2_WAVES_PER_BLOCK * stride * sizeof(double);
-        while ((size_t)(grid_fast + grid_gen) * per_blk > budget && grid_fast + grid_gen > 2) {
-            if (grid_fast > 1) grid_fast--;
-            if (grid_gen > 1 && (size_t)(grid_fast + grid_gen) * per_blk > budget) grid_gen--;
-        }
-    }
-    const int    grid = grid_fast + grid_gen;
-    const size_t need = (size_t)grid * CNF2_WAVES_PER_BLOCK * stride;
-    {
-        size_t capd = ctx->spill_bytes / sizeof(double);
-        rc = ensure(ctx, &ctx->d_spill, &capd, need);
-        ctx->spill_bytes = capd * sizeof(double);
-        if (rc) return rc;
-    }
+    // grids and spill: one slot per resident wave, the fast kernel's slots first
+    const int    mlen = longest_chrom(ctx);
+    const size_t stride = spill_stride(mlen);
+    int          grid_fast = 0, grid_gen = 0;
+    size_t       free_b = 0, total_b = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+    if (!plan_sweep_grids(ctx->n_cu, ctx->fast_blocks_per_cu, ctx->blocks_per_cu, ctx->reserve_blocks, std::max(n_fast, n_packed),
+                          n_general, free_b, ctx->d_spill.cap * sizeof(double), mlen, &grid_fast, &grid_gen))
+        return fail(ctx, CNF2_ERR_NOMEM, "a chromosome of %d markers needs %zu MB of spill per block, %zu MB free", mlen,
+                    spill_block_bytes(mlen) >> 20, free_b >> 20);
+    RC_TRY(ctx->d_spill.ensure(ctx, (size_t)(grid_fast + grid_gen) * CNF2_WAVES_PER_BLOCK * stride));
 
     double *d_f, *d_l, *d_d = nullptr;
     const size_t nf = (size_t)n * ctx->n_chrom * 8, nl = (size_t)n * ctx->n_chrom, nd = (size_t)n * ctx->n_markers * 3;
@@ -805,9 +690,9 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         d_l = loglik_out;
         d_d = dosage_out;
     } else {
-        if ((rc = ensure(ctx, &ctx->d_factors, &ctx->factors_cap, nf))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_loglik, &ctx->loglik_cap, nl))) return rc;
-        if (want_dosage && (rc = ensure(ctx, &ctx->d_dosage, &ctx->dosage_cap, nd))) return rc;
+        RC_TRY(ctx->d_factors.ensure(ctx, nf));
+        RC_TRY(ctx->d_loglik.ensure(ctx, nl));
+        if (want_dosage) RC_TRY(ctx->d_dosage.ensure(ctx, nd));
         d_f = ctx->d_factors;
         d_l = ctx->d_loglik;
         d_d = ctx->d_dosage;
@@ -826,33 +711,48 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     p.flags        = (want_dosage ? 0 : KP_NO_DOSAGE) | ((flags & CNF2_RAW_DOSAGE) ? KP_RAW_DOSAGE : 0) |
               ((flags & CNF2_NO_TIES) ? KP_NO_TIES : 0);
     if (flags & CNF2_STATIC_JOBS) p.job_next = nullptr;
-    if (xo) {
+    // per mode: the outputs, the flags of its own launches, and the occupancy of the kernel that makes the tied windows'
+    // second pass (the general kernel's crossover instantiation; the fast kernel's Viterbi or sampling instantiation)
+    int follow_per_cu = 0;
+    switch (mode.variant) {
+    case SW_CROSSOVERS:
         p.flags  = 0;           // (the crossover instantiations form no rows; KP_NO_DOSAGE would stop them after the forward pass)
-        p.xo     = xo->xo;
-        p.xo_sum = xo->sum;
-        p.xo_cnt = xo->cnt;
-    }
-    if (vit) {
+        p.xo     = mode.xo;
+        p.xo_sum = mode.xo_sum;
+        p.xo_cnt = mode.xo_cnt;
+        follow_per_cu = ctx->xo_blocks_per_cu;
+        break;
+    case SW_VITERBI:
         p.flags      = KP_NO_DOSAGE;
-        p.vit_logmax = vit->logmax;
-        p.vit_state  = vit->state;
-        p.vit_shift  = vit->shift;
-    }
-    if (smp) {
+        p.vit_logmax = mode.logmax;
+        p.vit_state  = mode.state;
+        p.vit_shift  = mode.shift;
+        follow_per_cu = ctx->fast_blocks_per_cu;
+        break;
+    case SW_SAMPLING:
         p.flags     = KP_NO_DOSAGE;
-        p.smp_state = smp->state;
-        p.smp_shift = smp->shift;
-        p.smp_logp  = smp->logp;
-        p.smp_draws = smp->draws;
-        p.smp_seed  = smp->seed;
+        p.smp_state = mode.state;
+        p.smp_shift = mode.shift;
+        p.smp_logp  = mode.logp;
+        p.smp_draws = mode.draws;
+        p.smp_seed  = mode.seed;
         p.smp_ind0  = ind_begin;
+        follow_per_cu = ctx->fast_blocks_per_cu;
+        break;
+    default: break;
     }
     if (flags & CNF2_LOG_PATHS) {
-        if ((rc = ensure(ctx, &ctx->d_pathlog, &ctx->pathlog_cap, nl))) return rc;
+        RC_TRY(ctx->d_pathlog.ensure(ctx, nl));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_pathlog, 0xff, nl * sizeof(int32_t), ctx->stream));
         p.path_log     = ctx->d_pathlog;
         ctx->pathlog_n = (int)nl;
     }
+    const bool half = !(flags & CNF2_FULL_SPILL);
+    // a launch whose likelihoods are not the ones reported (the tied windows' second pass, the Viterbi instantiation)
+    auto likelihoods_to_scratch = [&](KernelParams* q) {
+        q->factors = ctx->d_xo_f;
+        q->loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
+    };
 
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if (n_general > 0) {
@@ -869,76 +769,47 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         // the tile-producer kernel with a pass per tie combination; the general kernel (one lane per table entry, per-marker
         // producer) with the full spill and where asked for
         if (flags & CNF2_FLUSH_TINY) pt.flags |= KP_FLUSH_TINY;
-        if (xo || vit || smp) pt.flags = KP_NO_DOSAGE;    // crossover / Viterbi / sampling mode: likelihoods only here, the rest from the pass below
-        if ((flags & CNF2_FULL_SPILL) || (flags & (CNF2_TIES_GENERAL | CNF2_FLUSH_TINY))) launch_fb(pt, grid_gen, false, ctx->stream2);
-        else launch_fb_fast_tied(pt, grid_gen, ctx->stream2);
-        HIP_TRY(ctx, hipGetLastError());
-        if (xo) {
-            // the general kernel's crossover instantiation in the same spill slots (after the pass above on this stream); its
-            // own likelihoods go to scratch (the ones reported are the tied kernel's); its occupancy is its own
+        if (!plain) pt.flags = KP_NO_DOSAGE;    // crossover / Viterbi / sampling mode: likelihoods only here, the rest from the pass below
+        if (flags & (CNF2_FULL_SPILL | CNF2_TIES_GENERAL | CNF2_FLUSH_TINY))
+            HIP_TRY(ctx, launch_fb(pt, grid_gen, SW_PLAIN, ctx->stream2));
+        else HIP_TRY(ctx, launch_fb_fast(pt, grid_gen, {SW_PLAIN, true, false, true}, ctx->stream2));
+        if (!plain) {
+            // the mode's instantiation over the tied jobs in the same spill slots (after the pass above on this stream): the
+            // general kernel's for the crossovers; the fast kernel's for Viterbi and sampling (the forward pass, the
+            // max-product recursion and the draws do not see the tie rule).  Its own likelihoods go to scratch (the ones
+            // reported are the tied kernel's); its occupancy is its own
             KernelParams px = pt;
-            px.factors = ctx->d_xo_f;
-            px.loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
-            int gx = ctx->n_cu * ctx->xo_blocks_per_cu - ctx->reserve_blocks;
-            if (gx < 1) gx = 1;
-            launch_fb_xo(px, gx < grid_gen ? gx : grid_gen, ctx->stream2);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        if (vit) {
-            // the fast kernel's Viterbi instantiation over the tied jobs in the same spill slots (after the pass above on this
-            // stream; the forward pass and the max-product recursion do not see the tie rule); its likelihoods go to scratch
-            KernelParams px = pt;
-            px.factors = ctx->d_xo_f;
-            px.loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
-            int gx = ctx->n_cu * ctx->fast_blocks_per_cu - ctx->reserve_blocks;
-            if (gx < 1) gx = 1;
-            launch_fb_fast_vit(px, gx < grid_gen ? gx : grid_gen, !(flags & CNF2_FULL_SPILL), ctx->stream2);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        if (smp) {
-            // the fast kernel's sampling instantiation over the tied jobs, likewise (the forward pass and the draws do not
-            // see the tie rule); its likelihoods go to scratch
-            KernelParams px = pt;
-            px.factors = ctx->d_xo_f;
-            px.loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
-            int gx = ctx->n_cu * ctx->fast_blocks_per_cu - ctx->reserve_blocks;
-            if (gx < 1) gx = 1;
-            launch_fb_fast_smp(px, gx < grid_gen ? gx : grid_gen, !(flags & CNF2_FULL_SPILL), ctx->stream2);
-            HIP_TRY(ctx, hipGetLastError());
+            likelihoods_to_scratch(&px);
+            const int gx = std::min(resident_blocks(ctx->n_cu, follow_per_cu, ctx->reserve_blocks), grid_gen);
+            if (mode.variant == SW_CROSSOVERS) HIP_TRY(ctx, launch_fb(px, gx, SW_CROSSOVERS, ctx->stream2));
+            else HIP_TRY(ctx, launch_fb_fast(px, gx, {mode.variant, half}, ctx->stream2));
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev2, ctx->stream2));
     }
     if (n_packed > 0) {
         p.pjobs   = ctx->d_pjobs;
         p.n_pjobs = (int)n_packed;
-        int gp    = (int)((n_packed + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
         KernelParams pp = p;
         if (pp.job_next) pp.job_next = ctx->d_jobnext + 2;    // (the fast kernel behind it on the stream zeroes its own)
-        launch_fb_packed(pp, gp < grid_fast ? gp : grid_fast, ctx->stream);
+        launch_fb_packed(pp, grid_for(n_packed, grid_fast), ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (n_fast > 0) {
-        int gf = (int)((n_fast + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
+        const int gf = grid_for(n_fast, grid_fast);
         p.clock_out = ctx->d_clock;
-        if (xo) launch_fb_fast_xo(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
-        else if (smp) launch_fb_fast_smp(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
-        else if (vit) {
+        if (mode.variant == SW_VITERBI) {
             // the likelihoods from cnf2_sweep's own launch without rows (the Viterbi instantiation runs the same recursion,
             // but compiled without the backward pass it does not round every job's factors the same way: DESIGN.md 8c), then
             // the Viterbi instantiation in the same spill slots with its likelihoods to scratch
             KernelParams pl = p;
             pl.flags = KP_NO_DOSAGE;
-            launch_fb_fast(pl, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
+            HIP_TRY(ctx, launch_fb_fast(pl, gf, {SW_PLAIN, half}, ctx->stream));
             KernelParams pv = p;
             pv.clock_out = nullptr;
-            pv.factors   = ctx->d_xo_f;
-            pv.loglik    = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
-            launch_fb_fast_vit(pv, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
-        }
-        else if ((flags & CNF2_XPOSE) && !(flags & CNF2_FULL_SPILL)) launch_fb_fast_xpose(p, gf < grid_fast ? gf : grid_fast, ctx->stream);
-        else launch_fb_fast(p, gf < grid_fast ? gf : grid_fast, !(flags & CNF2_FULL_SPILL), ctx->stream);
+            likelihoods_to_scratch(&pv);
+            HIP_TRY(ctx, launch_fb_fast(pv, gf, {SW_VITERBI, half}, ctx->stream));
+        } else HIP_TRY(ctx, launch_fb_fast(p, gf, {mode.variant, half, half && (flags & CNF2_XPOSE)}, ctx->stream));
         p.clock_out = nullptr;
-        HIP_TRY(ctx, hipGetLastError());
     }
     if (n_general > 0) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev2, 0));
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
@@ -957,7 +828,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
 int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
                uint32_t flags)
 {
-    return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, dosage_out, flags, nullptr);
+    return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, dosage_out, flags, SweepMode());
 }
 
 int cnf2_last_paths(cnf2_ctx* ctx, int32_t* paths_out, int n)
@@ -1001,8 +872,7 @@ int cnf2_clock_probe(cnf2_ctx* ctx, double* mhz_out)
 {
     if (!ctx || !mhz_out) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, (size_t)8);
-    if (rc) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, (size_t)8));
     const int iters = 1 << 20;
     hipEvent_t e0, e1;
     HIP_TRY(ctx, hipEventCreate(&e0));
@@ -1024,16 +894,16 @@ int cnf2_clock_probe(cnf2_ctx* ctx, double* mhz_out)
 size_t cnf2_workspace_bytes(cnf2_ctx* ctx)
 {
     if (!ctx) return 0;
-    return ctx->spill_bytes + ctx->jobs_cap * sizeof(Job) +
-           (ctx->factors_cap + ctx->loglik_cap + ctx->dosage_cap + ctx->scratch_cap + ctx->wbuf_cap) * sizeof(double);
+    const size_t doubles = ctx->d_spill.cap + ctx->d_factors.cap + ctx->d_loglik.cap + ctx->d_dosage.cap + ctx->d_scratch.cap +
+                           ctx->d_wbuf.cap;
+    return ctx->d_jobs.cap * sizeof(Job) + doubles * sizeof(double);
 }
 
 // Runs fb_kernel<true> for one individual x chromosome and leaves the reference-layout store in the
 // context's scratch buffer; fills the Stage2Params view of it.  extra = doubles reserved after it.
 static int run_store(cnf2_ctx* ctx, int ind, int chrom, Stage2Params* q, size_t extra, double** extra_ptr)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (ind < 0 || ind >= (int)ctx->windows.size() || chrom < 0 || chrom >= ctx->n_chrom)
         return fail(ctx, CNF2_ERR_ARG, "individual or chromosome out of range");
     const int    first = ctx->chromstarts[chrom], last = ctx->chromstarts[chrom + 1] - 1, len = last - first + 1;
@@ -1041,7 +911,7 @@ static int run_store(cnf2_ctx* ctx, int ind, int chrom, Stage2Params* q, size_t 
     const size_t stride = (size_t)len * 512;
     // scratch: fwbw | factors | spill(4 waves) | out factors(8) | loglik(8) | dosage(n_markers*3) | job(8) | extra
     const size_t total = nfw + nff + stride * CNF2_WAVES_PER_BLOCK + 16 + (size_t)ctx->n_markers * 3 + 8 + extra;
-    if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, total))) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, total));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_scratch, 0, (nfw + nff) * sizeof(double), ctx->stream));
     double* d_fw  = ctx->d_scratch;
     double* d_ff  = d_fw + nfw;
@@ -1072,8 +942,7 @@ static int run_store(cnf2_ctx* ctx, int ind, int chrom, Stage2Params* q, size_t 
     p.flags        = KP_NO_DOSAGE;
     p.dbg_fwbw     = d_fw;
     p.dbg_factors  = d_ff;
-    launch_fb(p, 1, true, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, launch_fb(p, 1, SW_PLAIN, ctx->stream, true));
     q->kp          = p;
     q->fwbw        = d_fw;
     q->fwbwfactors = d_ff;
@@ -1088,8 +957,7 @@ int cnf2_fwbw_store(cnf2_ctx* ctx, int ind, int chrom, double* fwbw_out, double*
 {
     if (!ctx || !fwbw_out || !fwbwfactors_out) return fail(ctx, CNF2_ERR_ARG, "bad fwbw_store arguments");
     Stage2Params q;
-    int rc = run_store(ctx, ind, chrom, &q, 0, nullptr);
-    if (rc) return rc;
+    RC_TRY(run_store(ctx, ind, chrom, &q, 0, nullptr));
     const size_t nfw = (size_t)8 * q.len * 3 * 64, nff = (size_t)8 * q.len * 3;
     HIP_TRY(ctx, hipMemcpyAsync(fwbw_out, q.fwbw, nfw * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(fwbwfactors_out, q.fwbwfactors, nff * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -1100,128 +968,83 @@ int cnf2_fwbw_store(cnf2_ctx* ctx, int ind, int chrom, double* fwbw_out, double*
 int cnf2_locked_query(cnf2_ctx* ctx, int ind, int chrom, int marker, double* val_out)
 {
     if (!ctx || !val_out) return fail(ctx, CNF2_ERR_ARG, "bad locked_query arguments");
-    Stage2Params q;
-    double*      d_out = nullptr;
-    const size_t n = (size_t)8 * 64 * 128;
-    int rc = run_store(ctx, ind, chrom, &q, n, &d_out);
-    if (rc) return rc;
-    if (marker < q.first || marker >= q.first + q.len) return fail(ctx, CNF2_ERR_ARG, "marker not on this chromosome");
-    launch_locked_query(q, marker, d_out, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(val_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return stage2_query(ctx, ind, chrom, &marker, (size_t)8 * 64 * 128, val_out,
+                        [&](const Stage2Params& q, double* d_out) { launch_locked_query(q, marker, d_out, ctx->stream); });
 }
 
 int cnf2_turn_scan(cnf2_ctx* ctx, int ind, int chrom, int marker, double* rawervals_out)
 {
     if (!ctx || !rawervals_out) return fail(ctx, CNF2_ERR_ARG, "bad turn_scan arguments");
-    Stage2Params q;
-    double*      d_out = nullptr;
-    const size_t n = 128 * 8;
-    int rc = run_store(ctx, ind, chrom, &q, n, &d_out);
-    if (rc) return rc;
-    if (marker < q.first || marker >= q.first + q.len) return fail(ctx, CNF2_ERR_ARG, "marker not on this chromosome");
-    launch_turn_scan(q, marker, d_out, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(rawervals_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return stage2_query(ctx, ind, chrom, &marker, 128 * 8, rawervals_out,
+                        [&](const Stage2Params& q, double* d_out) { launch_turn_scan(q, marker, d_out, ctx->stream); });
 }
 
 int cnf2_turn_scan_rows(cnf2_ctx* ctx, int ind, int chrom, double* rows_out)
 {
     if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad turn_scan_rows arguments");
-    Stage2Params q;
-    double*      d_out = nullptr;
-    int rc = ready(ctx);
-    if (rc) return rc;
-    if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
-    const size_t n = (size_t)(ctx->chromstarts[chrom + 1] - ctx->chromstarts[chrom]) * 1024;
-    rc = run_store(ctx, ind, chrom, &q, n, &d_out);
-    if (rc) return rc;
-    launch_turn_scan_rows(q, d_out, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return stage2_rows(ctx, ind, chrom, 1024, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_turn_scan_rows(q, d_out, ctx->stream); });
 }
 
 int cnf2_state_posterior(cnf2_ctx* ctx, int ind, int chrom, double* rows_out, uint32_t flags)
 {
     if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad state_posterior arguments");
-    Stage2Params q;
-    double*      d_out = nullptr;
-    int rc = ready(ctx);
-    if (rc) return rc;
-    if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
-    const size_t n = (size_t)(ctx->chromstarts[chrom + 1] - ctx->chromstarts[chrom]) * 64;
-    rc = run_store(ctx, ind, chrom, &q, n, &d_out);
-    if (rc) return rc;
-    launch_state_rows(q, (flags & CNF2_NO_TIES) ? KP_NO_TIES : 0, d_out, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    const uint32_t kp = (flags & CNF2_NO_TIES) ? KP_NO_TIES : 0;
+    return stage2_rows(ctx, ind, chrom, 64, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_state_rows(q, kp, d_out, ctx->stream); });
 }
 
 int cnf2_crossover_rows(cnf2_ctx* ctx, int ind, int chrom, double* rows_out)
 {
     if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad crossover_rows arguments");
-    Stage2Params q;
-    double*      d_out = nullptr;
-    int rc = ready(ctx);
-    if (rc) return rc;
-    if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
-    const size_t n = (size_t)(ctx->chromstarts[chrom + 1] - ctx->chromstarts[chrom]) * 6;
-    rc = run_store(ctx, ind, chrom, &q, n, &d_out);
-    if (rc) return rc;
-    launch_crossover_rows(q, d_out, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return stage2_rows(ctx, ind, chrom, 6, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_crossover_rows(q, d_out, ctx->stream); });
+}
+
+// One pass of sweep_impl in a mode, for its three entry points (which have checked their arguments and staged their
+// outputs): the scratch of the tied windows' second pass, the crossover sums zeroed (the kernels add to them), the flags
+// that mean something to a mode
+static int mode_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, uint32_t flags,
+                      const SweepMode& mode)
+{
+    const size_t n = (size_t)(ind_end - ind_begin);
+    RC_TRY(ctx->d_xo_f.ensure(ctx, n * ctx->n_chrom * 9 + 1));
+    if (mode.variant == SW_CROSSOVERS) {
+        HIP_TRY(ctx, hipMemsetAsync(mode.xo_sum, 0, (size_t)ctx->n_markers * 6 * sizeof(double), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(mode.xo_cnt, 0, (size_t)ctx->n_chrom * sizeof(int32_t), ctx->stream));
+    }
+    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+    return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, mode);
+}
+
+static int mode_range(cnf2_ctx* ctx, int ind_begin, int ind_end)
+{
+    if (ind_begin < 0 || ind_end > (int)ctx->windows.size() || ind_begin > ind_end)
+        return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
     return CNF2_OK;
 }
 
-// one pass of sweep_impl's crossover mode: the sums are zeroed first and added to by the kernels
+// one pass of sweep_impl's crossover mode: the sums are zeroed first and added to by the kernels (an empty range reports
+// them as zeros)
 int cnf2_sweep_crossovers(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out,
                           double* xo_out, double* xo_sum_out, int32_t* n_contrib_out, uint32_t flags)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (!xo_sum_out || !n_contrib_out) return fail(ctx, CNF2_ERR_ARG, "xo_sum_out and n_contrib_out must not be NULL");
-    if (ind_begin < 0 || ind_end > (int)ctx->windows.size() || ind_begin > ind_end)
-        return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
     const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const int    n   = ind_end - ind_begin;
-    const size_t M = ctx->n_markers, C = ctx->n_chrom;
-    const size_t nx = (size_t)n * M * 6;
-    XoArgs x;
-    x.xo  = xo_out;
-    x.sum = xo_sum_out;
-    x.cnt = n_contrib_out;
-    if (!dev) {
-        if ((rc = ensure(ctx, &ctx->d_xo_sum, &ctx->xo_sum_cap, M * 6))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_xo_cnt, &ctx->xo_cnt_cap, C))) return rc;
-        x.sum = ctx->d_xo_sum;
-        x.cnt = ctx->d_xo_cnt;
-        x.xo  = nullptr;
-        if (xo_out && nx > 0) {
-            if ((rc = ensure(ctx, &ctx->d_xo, &ctx->xo_cap, nx))) return rc;
-            x.xo = ctx->d_xo;
-        }
-    }
-    if ((rc = ensure(ctx, &ctx->d_xo_f, &ctx->xo_f_cap, (size_t)n * C * 9 + 1))) return rc;   // the general kernel's likelihoods
-    HIP_TRY(ctx, hipMemsetAsync(x.sum, 0, M * 6 * sizeof(double), ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(x.cnt, 0, C * sizeof(int32_t), ctx->stream));
-    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
-    if ((rc = sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, &x))) return rc;
-    if (!dev) {
-        HIP_TRY(ctx, hipMemcpyAsync(xo_sum_out, x.sum, M * 6 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(n_contrib_out, x.cnt, C * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (x.xo) HIP_TRY(ctx, hipMemcpyAsync(xo_out, x.xo, nx * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    const size_t M = ctx->n_markers, C = ctx->n_chrom, nx = (size_t)(ind_end - ind_begin) * M * 6;
+    SweepMode    m;
+    m.variant = SW_CROSSOVERS;
+    RC_TRY(stage_out(ctx, dev, xo_sum_out, ctx->d_xo_sum, M * 6, &m.xo_sum));
+    RC_TRY(stage_out(ctx, dev, n_contrib_out, ctx->d_xo_cnt, C, &m.xo_cnt));
+    RC_TRY(stage_out(ctx, dev, xo_out, ctx->d_xo, nx, &m.xo));
+    RC_TRY(mode_sweep(ctx, ind_begin, ind_end, factors_out, loglik_out, flags, m));
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, xo_sum_out, m.xo_sum, M * 6));
+    RC_TRY(fetch_out(ctx, n_contrib_out, m.xo_cnt, C));
+    RC_TRY(fetch_out(ctx, xo_out, m.xo, nx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
 }
 
@@ -1229,36 +1052,24 @@ int cnf2_sweep_crossovers(cnf2_ctx* ctx, int ind_begin, int ind_end, double* fac
 int cnf2_sweep_viterbi(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* logmax_out,
                        uint8_t* state_out, int32_t* shift_out, uint32_t flags)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (!logmax_out || !state_out || !shift_out) return fail(ctx, CNF2_ERR_ARG, "logmax_out, state_out and shift_out must not be NULL");
-    if (ind_begin < 0 || ind_end > (int)ctx->windows.size() || ind_begin > ind_end)
-        return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
     const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const int    n   = ind_end - ind_begin;
+    const size_t n   = (size_t)(ind_end - ind_begin);
     if (n == 0) return CNF2_OK;
-    const size_t nlm = (size_t)n * ctx->n_chrom * 8, nst = (size_t)n * ctx->n_markers, nsh = (size_t)n * ctx->n_chrom;
-    VitArgs v;
-    v.logmax = logmax_out;
-    v.state  = state_out;
-    v.shift  = shift_out;
-    if (!dev) {
-        if ((rc = ensure(ctx, &ctx->d_vit_lm, &ctx->vit_lm_cap, nlm))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_vit_st, &ctx->vit_st_cap, nst))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_vit_sh, &ctx->vit_sh_cap, nsh))) return rc;
-        v.logmax = ctx->d_vit_lm;
-        v.state  = ctx->d_vit_st;
-        v.shift  = ctx->d_vit_sh;
-    }
-    if ((rc = ensure(ctx, &ctx->d_xo_f, &ctx->xo_f_cap, (size_t)n * ctx->n_chrom * 9 + 1))) return rc;   // tied windows' second pass
-    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
-    if ((rc = sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, nullptr, &v))) return rc;
-    if (!dev) {
-        HIP_TRY(ctx, hipMemcpyAsync(logmax_out, v.logmax, nlm * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(state_out, v.state, nst, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(shift_out, v.shift, nsh * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    const size_t nlm = n * ctx->n_chrom * 8, nst = n * ctx->n_markers, nsh = n * ctx->n_chrom;
+    SweepMode    m;
+    m.variant = SW_VITERBI;
+    RC_TRY(stage_out(ctx, dev, logmax_out, ctx->d_vit_lm, nlm, &m.logmax));
+    RC_TRY(stage_out(ctx, dev, state_out, ctx->d_vit_st, nst, &m.state));
+    RC_TRY(stage_out(ctx, dev, shift_out, ctx->d_vit_sh, nsh, &m.shift));
+    RC_TRY(mode_sweep(ctx, ind_begin, ind_end, factors_out, loglik_out, flags, m));
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, logmax_out, m.logmax, nlm));
+    RC_TRY(fetch_out(ctx, state_out, m.state, nst));
+    RC_TRY(fetch_out(ctx, shift_out, m.shift, nsh));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
 }
 
@@ -1266,60 +1077,37 @@ int cnf2_sweep_viterbi(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factor
 int cnf2_sweep_sample(cnf2_ctx* ctx, int ind_begin, int ind_end, int n_draws, uint64_t seed, double* factors_out,
                       double* loglik_out, uint8_t* state_out, int32_t* shift_out, double* logp_out, uint32_t flags)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (n_draws < 1 || n_draws > 1024) return fail(ctx, CNF2_ERR_ARG, "n_draws must be in 1 .. 1024, not %d", n_draws);
     if (!state_out || !shift_out) return fail(ctx, CNF2_ERR_ARG, "state_out and shift_out must not be NULL");
-    if (ind_begin < 0 || ind_end > (int)ctx->windows.size() || ind_begin > ind_end)
-        return fail(ctx, CNF2_ERR_ARG, "individual range out of bounds");
-    const bool dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const int  n   = ind_end - ind_begin;
-    if (n == 0) return CNF2_OK;
-    const size_t nd  = (size_t)n * n_draws;
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t nd  = (size_t)(ind_end - ind_begin) * n_draws;
+    if (nd == 0) return CNF2_OK;
     const size_t nst = nd * ctx->n_markers, nsh = nd * ctx->n_chrom;
-    SmpArgs a;
-    a.state = state_out;
-    a.shift = shift_out;
-    a.logp  = logp_out;
-    a.draws = n_draws;
-    a.seed  = (unsigned long long)seed;
-    if (!dev) {
-        // host outputs are staged whole (callers with many draws split the individual range: the draws do not change)
-        if ((rc = ensure(ctx, &ctx->d_smp_st, &ctx->smp_st_cap, nst))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_smp_sh, &ctx->smp_sh_cap, nsh))) return rc;
-        if (logp_out && (rc = ensure(ctx, &ctx->d_smp_lp, &ctx->smp_lp_cap, nsh))) return rc;
-        a.state = ctx->d_smp_st;
-        a.shift = ctx->d_smp_sh;
-        a.logp  = logp_out ? ctx->d_smp_lp : nullptr;
-    }
-    if ((rc = ensure(ctx, &ctx->d_xo_f, &ctx->xo_f_cap, (size_t)n * ctx->n_chrom * 9 + 1))) return rc;   // tied windows' second pass
-    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
-    if ((rc = sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, nullptr, nullptr, &a))) return rc;
-    if (!dev) {
-        HIP_TRY(ctx, hipMemcpyAsync(state_out, a.state, nst, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(shift_out, a.shift, nsh * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-        if (logp_out) HIP_TRY(ctx, hipMemcpyAsync(logp_out, a.logp, nsh * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    }
+    SweepMode    m;
+    m.variant = SW_SAMPLING;
+    m.draws   = n_draws;
+    m.seed    = (unsigned long long)seed;
+    // host outputs are staged whole (callers with many draws split the individual range: the draws do not change)
+    RC_TRY(stage_out(ctx, dev, state_out, ctx->d_smp_st, nst, &m.state));
+    RC_TRY(stage_out(ctx, dev, shift_out, ctx->d_smp_sh, nsh, &m.shift));
+    RC_TRY(stage_out(ctx, dev, logp_out, ctx->d_smp_lp, nsh, &m.logp));
+    RC_TRY(mode_sweep(ctx, ind_begin, ind_end, factors_out, loglik_out, flags, m));
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, state_out, m.state, nst));
+    RC_TRY(fetch_out(ctx, shift_out, m.shift, nsh));
+    RC_TRY(fetch_out(ctx, logp_out, m.logp, nsh));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
 }
 
 int cnf2_haplos(cnf2_ctx* ctx, int ind, int chrom, double* rows_out, uint32_t flags)
 {
     if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad haplos arguments");
-    Stage2Params q;
-    double*      d_out = nullptr;
-    int rc = ready(ctx);
-    if (rc) return rc;
-    if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
-    const size_t n = (size_t)(ctx->chromstarts[chrom + 1] - ctx->chromstarts[chrom]) * 14;
-    rc = run_store(ctx, ind, chrom, &q, n, &d_out);
-    if (rc) return rc;
-    launch_haplos_rows(q, (flags & CNF2_NO_TIES) ? KP_NO_TIES : 0, d_out, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    const uint32_t kp = (flags & CNF2_NO_TIES) ? KP_NO_TIES : 0;
+    return stage2_rows(ctx, ind, chrom, 14, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_haplos_rows(q, kp, d_out, ctx->stream); });
 }
 
 int cnf2_infprobs(cnf2_ctx* ctx, int ind, int chrom, int marker, double* inf_out, double* hz_out, uint32_t flags)
@@ -1327,13 +1115,11 @@ int cnf2_infprobs(cnf2_ctx* ctx, int ind, int chrom, int marker, double* inf_out
     if (!ctx || !inf_out || !hz_out) return fail(ctx, CNF2_ERR_ARG, "bad infprobs arguments");
     Stage2Params q;
     double*      d_out = nullptr;
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
     if (marker < ctx->chromstarts[chrom] || marker >= ctx->chromstarts[chrom + 1])
         return fail(ctx, CNF2_ERR_ARG, "marker not on the chromosome");
-    rc = run_store(ctx, ind, chrom, &q, 32, &d_out);
-    if (rc) return rc;
+    RC_TRY(run_store(ctx, ind, chrom, &q, 32, &d_out));
     launch_infprobs(q, marker, (flags & CNF2_NO_TIES) ? KP_NO_TIES : 0, d_out, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     double h[30];
@@ -1348,19 +1134,9 @@ int cnf2_infprobs(cnf2_ctx* ctx, int ind, int chrom, int marker, double* inf_out
 int cnf2_infprobs_rows(cnf2_ctx* ctx, int ind, int chrom, double* rows_out, uint32_t flags)
 {
     if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad infprobs_rows arguments");
-    Stage2Params q;
-    double*      d_out = nullptr;
-    int rc = ready(ctx);
-    if (rc) return rc;
-    if (chrom < 0 || chrom >= ctx->n_chrom) return fail(ctx, CNF2_ERR_ARG, "chromosome out of range");
-    const size_t n = (size_t)(ctx->chromstarts[chrom + 1] - ctx->chromstarts[chrom]) * 30;
-    rc = run_store(ctx, ind, chrom, &q, n, &d_out);
-    if (rc) return rc;
-    launch_infprobs_rows(q, (flags & CNF2_NO_TIES) ? KP_NO_TIES : 0, d_out, ctx->stream);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    const uint32_t kp = (flags & CNF2_NO_TIES) ? KP_NO_TIES : 0;
+    return stage2_rows(ctx, ind, chrom, 30, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_infprobs_rows(q, kp, d_out, ctx->stream); });
 }
 
 int cnf2_descendants(cnf2_ctx* ctx, int32_t* desc_out)
@@ -1390,6 +1166,23 @@ static size_t todo_chunk(size_t n_rec, size_t chrom_len, size_t markers_upto)
 #endif
 static size_t todo_doubles(size_t chunk) { return chunk * 3 * TODO_LISTS + chunk / 256 + 8; }
 
+// row_doubles: doubles of the batch buffer per job and marker; part_need: doubles the caller allocates for itself between
+// the spill and the batch buffer.  Leaves plan.fit to the caller where it is BATCH_NO_PART or BATCH_NO_ROWS.
+static int batched_setup(cnf2_ctx* ctx, int ind_begin, int n, uint32_t flags, size_t row_doubles, size_t part_need, Batched* b)
+{
+    b->list = job_plan(ctx, ind_begin, n, flags & CNF2_NO_TIES);
+    const std::vector<Job>& jobs = b->list.jobs;
+    RC_TRY(ctx->d_jobs.ensure(ctx, jobs.size() + 1));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice));
+    b->max_len = longest_chrom(ctx);
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+    const size_t held_b = (ctx->d_spill.cap + ctx->d_wbuf.cap) * sizeof(double);
+    b->plan = plan_batches(ctx->n_cu, ctx->fast_blocks_per_cu, ctx->reserve_blocks, free_b, held_b, b->max_len, row_doubles, jobs.size(), ctx->batch_jobs, part_need, ctx->d_part.cap);
+    if (b->plan.fit == BATCH_NO_SPILL) return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the spill of one block");
+    return ctx->d_spill.ensure(ctx, (size_t)b->plan.grid_cap * CNF2_WAVES_PER_BLOCK * spill_stride(b->max_len));
+}
+
 enum : uint32_t { ACC_RESERVE_ONLY = 1u << 31 };     // internal flag of cnf2_sweep_accumulate (not in the header)
 
 // Batched HOT LOOP 2 with its reductions (cnF2freq.cpp:5416-5577, 5876-5902 with moveinfprobs / movehaplos
@@ -1401,8 +1194,7 @@ int cnf2_sweep_accumulate(cnf2_ctx* ctx, int ind_begin, int ind_end, const int32
                           double* loglik_out, double* dosage_out, double* infprobs, double* haplobase,
                           double* haplocount, double* homozyg, uint32_t flags)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     const int n_all = (int)ctx->windows.size();
     const bool out_dev = (flags & CNF2_OUT_DEVICE) != 0, acc_dev = (flags & CNF2_ACC_DEVICE) != 0;
     const bool acc_given = infprobs && haplobase && haplocount && homozyg;
@@ -1417,26 +1209,17 @@ int cnf2_sweep_accumulate(cnf2_ctx* ctx, int ind_begin, int ind_end, const int32
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     // per-record tables
-    if (ctx->rec_cap < R) {
-        if (ctx->d_desc) HIP_TRY(ctx, hipFree(ctx->d_desc));
-        if (ctx->d_rec_empty) HIP_TRY(ctx, hipFree(ctx->d_rec_empty));
-        ctx->d_desc = nullptr;
-        ctx->d_rec_empty = nullptr;
-        ctx->rec_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_desc, sizeof(int32_t) * R));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_rec_empty, R));
-        ctx->rec_cap = R;
-    }
+    RC_TRY(ensure_rec_tables(ctx, R));
     if (descendants) HIP_TRY(ctx, hipMemcpy(ctx->d_desc, descendants, sizeof(int32_t) * R, hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_rec_empty, P.empty.data(), R, hipMemcpyHostToDevice));
 
     // accumulators and sweep outputs
     double *a_inf = infprobs, *a_hb = haplobase, *a_hc = haplocount, *a_hz = homozyg;
     if (!acc_dev) {
-        if ((rc = ensure(ctx, &ctx->d_acc_inf, &ctx->acc_inf_cap, R * M * 4))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_acc_hb, &ctx->acc_hb_cap, R * M))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_acc_hc, &ctx->acc_hc_cap, R * M))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_acc_hz, &ctx->acc_hz_cap, (size_t)(n > 0 ? n : 1) * M * 2))) return rc;
+        RC_TRY(ctx->d_acc_inf.ensure(ctx, R * M * 4));
+        RC_TRY(ctx->d_acc_hb.ensure(ctx, R * M));
+        RC_TRY(ctx->d_acc_hc.ensure(ctx, R * M));
+        RC_TRY(ctx->d_acc_hz.ensure(ctx, (size_t)(n > 0 ? n : 1) * M * 2));
         a_inf = ctx->d_acc_inf;
         a_hb  = ctx->d_acc_hb;
         a_hc  = ctx->d_acc_hc;
@@ -1451,9 +1234,9 @@ int cnf2_sweep_accumulate(cnf2_ctx* ctx, int ind_begin, int ind_end, const int32
     const size_t nf = (size_t)n * ctx->n_chrom * 8, nl = (size_t)n * ctx->n_chrom, nd = (size_t)n * M * 3;
     double *d_f = factors_out, *d_l = loglik_out, *d_d = dosage_out;
     if (!out_dev) {
-        if ((rc = ensure(ctx, &ctx->d_factors, &ctx->factors_cap, nf ? nf : 1))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_loglik, &ctx->loglik_cap, nl ? nl : 1))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_dosage, &ctx->dosage_cap, nd ? nd : 1))) return rc;
+        RC_TRY(ctx->d_factors.ensure(ctx, nf ? nf : 1));
+        RC_TRY(ctx->d_loglik.ensure(ctx, nl ? nl : 1));
+        RC_TRY(ctx->d_dosage.ensure(ctx, nd ? nd : 1));
         d_f = ctx->d_factors;
         d_l = ctx->d_loglik;
         d_d = ctx->d_dosage;
@@ -1464,77 +1247,34 @@ int cnf2_sweep_accumulate(cnf2_ctx* ctx, int ind_begin, int ind_end, const int32
     // as well (their accumulators do see the rule: they stay a pass of their own).
     const bool want_rows = dosage_out != nullptr;
     if (n > 0) {
-        // job list: untied windows (fast kernel) first, tied ones (general kernel) after
-        std::vector<Job> jobs;
-        size_t           n_fast = 0;
-        for (int pass = 0; pass < 2; pass++) {
-            for (int c : chrom_order(ctx))
-                for (int j = 0; j < n; j++) {
-                    const bool tied = ctx->windows[ind_begin + j].n_groups > 0 && !(flags & CNF2_NO_TIES);
-                    if (tied != (pass == 1)) continue;
-                    Job jb;
-                    jb.ind = j;
-                    jb.first = ctx->chromstarts[c];
-                    jb.last = ctx->chromstarts[c + 1] - 1;
-                    jb.chrom = c;
-                    jobs.push_back(jb);
-                }
-            if (pass == 0) n_fast = jobs.size();
-        }
-        if ((rc = ensure(ctx, &ctx->d_jobs, &ctx->jobs_cap, jobs.size() + 1))) return rc;
-        HIP_TRY(ctx, hipMemcpy(ctx->d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice));
-
-        const int    mlen = max_chrom_len(ctx);
-        const size_t stride = (size_t)mlen * 528;
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-        free_b += ctx->spill_bytes + ctx->wbuf_cap * sizeof(double);
-        // spill: one slot per resident wave, at most a quarter of what is free
-        int          grid_cap = ctx->n_cu * ctx->fast_blocks_per_cu - ctx->reserve_blocks;
-        if (grid_cap < 1) grid_cap = 1;
-        const size_t per_blk = (size_t)CNF2_WAVES_PER_BLOCK * stride * sizeof(double);
-        if ((size_t)grid_cap * per_blk > free_b / 4) grid_cap = (int)(free_b / 4 / per_blk);
-        if (grid_cap < 1) return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the spill of one block");
-        {
-            size_t capd = ctx->spill_bytes / sizeof(double);
-            rc = ensure(ctx, &ctx->d_spill, &capd, (size_t)grid_cap * CNF2_WAVES_PER_BLOCK * stride);
-            ctx->spill_bytes = capd * sizeof(double);
-            if (rc) return rc;
-        }
         // CNF2_DETERMINISTIC: the per-individual rows (336 B per individual x marker) are taken out of what is free BEFORE the
         // batch buffer is sized -- and allocated now, also by cnf2_reserve_accumulate -- so that the batch buffer cannot
         // leave them without memory
         const size_t part_need = (flags & CNF2_DETERMINISTIC) ? (size_t)n * M * 42 : 0;
-        if (part_need) {
-            const size_t have = ctx->part_cap * sizeof(double);
-            if (part_need * sizeof(double) > free_b / 2 + have)
-                return fail(ctx, CNF2_ERR_NOMEM, "CNF2_DETERMINISTIC needs %zu MB for the per-individual rows", (part_need * 8) >> 20);
-            if ((rc = ensure(ctx, &ctx->d_part, &ctx->part_cap, part_need))) return rc;
-            free_b -= (part_need * sizeof(double) > have) ? part_need * sizeof(double) - have : 0;
-        }
-        // weights: 512 doubles per (job, marker); batch = what fits in half of the rest
-        const size_t per_job = (size_t)mlen * 512;
-        size_t       batch = (free_b - (size_t)grid_cap * per_blk) / 2 / (per_job * sizeof(double));
-        if (batch < 1) return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the weights of one job (%zu MB)", per_job >> 17);
-        if (batch > jobs.size()) batch = jobs.size();
-        if (batch > 1000000) batch = 1000000;
-        batch = whole_rounds(batch, jobs.size(), grid_cap);
-        if (ctx->batch_jobs > 0 && batch > (size_t)ctx->batch_jobs) batch = (size_t)ctx->batch_jobs;
+        Batched      b;
+        RC_TRY(batched_setup(ctx, ind_begin, n, flags, 512, part_need, &b));     // weights: 512 doubles per (job, marker)
+        if (b.plan.fit == BATCH_NO_PART)
+            return fail(ctx, CNF2_ERR_NOMEM, "CNF2_DETERMINISTIC needs %zu MB for the per-individual rows", (part_need * 8) >> 20);
+        if (part_need) RC_TRY(ctx->d_part.ensure(ctx, part_need));
+        const int    mlen = b.max_len;
+        const size_t stride = spill_stride(mlen), per_job = (size_t)mlen * 512, batch = b.plan.batch;
+        if (b.plan.fit == BATCH_NO_ROWS)
+            return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the weights of one job (%zu MB)", per_job >> 17);
         {
             // CNF2_TIMING: the first call of a run allocates the batch buffer (up to half the free memory) -- seconds
-            const bool timing = getenv("CNF2_TIMING") != nullptr && ctx->wbuf_cap < batch * per_job;
+            const bool timing = getenv("CNF2_TIMING") != nullptr && ctx->d_wbuf.cap < batch * per_job;
             const auto t0 = std::chrono::steady_clock::now();
-            if ((rc = ensure(ctx, &ctx->d_wbuf, &ctx->wbuf_cap, batch * per_job))) return rc;
+            RC_TRY(ctx->d_wbuf.ensure(ctx, batch * per_job));
             if (timing)
                 fprintf(stderr, "  [sweep_accumulate] batch buffer of %.1f GB allocated in %.3f s (%zu jobs per batch of %zu)\n",
                         batch * per_job * 8 / 1e9, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), batch,
-                        jobs.size());
+                        b.list.jobs.size());
         }
         if (reserve_only) {
             // ... and the buffers of the update passes (cnf2_update_pass): results of a chromosome's flows, the scouts' list
-            if (!ctx->d_flow_next) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_flow_next, 32 * sizeof(unsigned long long)));
-            if ((rc = ensure(ctx, &ctx->d_flow_out, &ctx->flow_out_cap, R * (size_t)mlen * 4))) return rc;
-            if ((rc = ensure(ctx, &ctx->d_todo, &ctx->todo_cap, todo_doubles(todo_chunk(R, (size_t)mlen, M))))) return rc;
+            RC_TRY(ctx->d_flow_next.ensure(ctx, 32));
+            RC_TRY(ctx->d_flow_out.ensure(ctx, R * (size_t)mlen * 4));
+            RC_TRY(ctx->d_todo.ensure(ctx, todo_doubles(todo_chunk(R, (size_t)mlen, M))));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             return CNF2_OK;
         }
@@ -1585,31 +1325,23 @@ int cnf2_sweep_accumulate(cnf2_ctx* ctx, int ind_begin, int ind_end, const int32
             std::copy(count.begin(), count.end(), gather.begin());
             std::vector<int32_t> fill(count.begin(), count.end() - 1);
             for (int j = 0; j < n; j++) first_slots(j, [&](int r, int k) { gather[R + 1 + fill[r]++] = j * 8 + k; });
-            if ((rc = ensure(ctx, &ctx->d_gather, &ctx->gather_cap, gather.size()))) return rc;
+            RC_TRY(ctx->d_gather.ensure(ctx, gather.size()));
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_gather, gather.data(), gather.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         }
         HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-        for (int pass = 0; pass < 2; pass++) {
-            const size_t lo = pass ? n_fast : 0, hi = pass ? jobs.size() : n_fast;
-            for (size_t b0 = lo; b0 < hi; b0 += batch) {
-                const size_t nb = (hi - b0 < batch) ? hi - b0 : batch;
-                p.jobs   = ctx->d_jobs + b0;
-                p.n_jobs = (int)nb;
-                int grid = (int)((nb + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
-                if (grid > grid_cap) grid = grid_cap;
-                if (pass == 0) launch_fb_fast_w(p, grid, ctx->stream, want_rows);
-                else if (flags & CNF2_TIES_GENERAL) launch_fb_w(p, grid, ctx->stream);
-                else if (!want_rows) launch_fb_fast_w(p, grid, ctx->stream, false);
-                else launch_fb_fast_tied_w(p, grid, ctx->stream);
-                HIP_TRY(ctx, hipGetLastError());
-                q.kp     = p;
-                q.n_jobs = (int)nb;
-                q.max_len = jobs[b0].last - jobs[b0].first + 1;      // the batch's longest job is its first (chrom_order)
-                q.flags  = (q.flags & ~(uint32_t)KP_ACC_LANES) | ((pass == 1 || (flags & CNF2_ACC_LANES)) ? KP_ACC_LANES : 0);
-                launch_acc_rows(q, ctx->stream);
-                HIP_TRY(ctx, hipGetLastError());
-            }
-        }
+        RC_TRY(for_each_batch(ctx, b, &p, [&](int pass, int grid, int max_len) -> int {
+            // tied windows: the general kernel where asked for; without rows the untied instantiation; else the tied one
+            const FastVariant v = {want_rows ? SW_WEIGHTS_ROWS : SW_WEIGHTS, true, false, pass == 1 && want_rows};
+            if (pass == 1 && (flags & CNF2_TIES_GENERAL)) HIP_TRY(ctx, launch_fb(p, grid, SW_WEIGHTS_ROWS, ctx->stream));
+            else HIP_TRY(ctx, launch_fb_fast(p, grid, v, ctx->stream));
+            q.kp      = p;
+            q.n_jobs  = p.n_jobs;
+            q.max_len = max_len;
+            q.flags   = (q.flags & ~(uint32_t)KP_ACC_LANES) | ((pass == 1 || (flags & CNF2_ACC_LANES)) ? KP_ACC_LANES : 0);
+            launch_acc_rows(q, ctx->stream);
+            HIP_TRY(ctx, hipGetLastError());
+            return CNF2_OK;
+        }));
         if (q.part) {
             launch_acc_gather(q, ctx->d_gather, ctx->d_gather + R + 1, (int)R, ctx->stream);
             HIP_TRY(ctx, hipGetLastError());
@@ -1650,8 +1382,7 @@ int cnf2_reserve_accumulate(cnf2_ctx* ctx, int ind_begin, int ind_end, uint32_t 
 int cnf2_sweep_turn_scan(cnf2_ctx* ctx, int ind_begin, int ind_end, double* rawervals_out, double* turn_lse_out,
                          uint32_t flags)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     const int n_all = (int)ctx->windows.size();
     if ((!rawervals_out && !turn_lse_out) || ind_begin < 0 || ind_end > n_all || ind_begin > ind_end)
         return fail(ctx, CNF2_ERR_ARG, "bad turn scan arguments");
@@ -1661,15 +1392,15 @@ int cnf2_sweep_turn_scan(cnf2_ctx* ctx, int ind_begin, int ind_end, double* rawe
     if (n == 0) return CNF2_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t nf = (size_t)n * ctx->n_chrom * 8, nl = (size_t)n * ctx->n_chrom, nd = (size_t)n * M * 3;
-    if ((rc = ensure(ctx, &ctx->d_factors, &ctx->factors_cap, nf))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_loglik, &ctx->loglik_cap, nl))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_dosage, &ctx->dosage_cap, nd))) return rc;
+    RC_TRY(ctx->d_factors.ensure(ctx, nf));
+    RC_TRY(ctx->d_loglik.ensure(ctx, nl));
+    RC_TRY(ctx->d_dosage.ensure(ctx, nd));
     double *d_full = rawervals_out, *d_lse = turn_lse_out;
     if (!out_dev) {
         // staging for the whole range: 9 KB per individual x marker -- callers with large ranges use device buffers
         d_full = d_lse = nullptr;
         const size_t need = (rawervals_out ? (size_t)n * M * 1024 : 0) + (turn_lse_out ? (size_t)n * M * 128 : 0);
-        if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, need))) return rc;
+        RC_TRY(ctx->d_scratch.ensure(ctx, need));
         double* q0 = ctx->d_scratch;
         if (rawervals_out) {
             d_full = q0;
@@ -1677,54 +1408,17 @@ int cnf2_sweep_turn_scan(cnf2_ctx* ctx, int ind_begin, int ind_end, double* rawe
         }
         if (turn_lse_out) d_lse = q0;
     }
-    std::vector<Job> jobs;
-    size_t           n_fast = 0;
-    for (int pass = 0; pass < 2; pass++) {
-        for (int c : chrom_order(ctx))
-            for (int j = 0; j < n; j++) {
-                const bool tied = ctx->windows[ind_begin + j].n_groups > 0 && !(flags & CNF2_NO_TIES);
-                if (tied != (pass == 1)) continue;
-                Job jb;
-                jb.ind = j;
-                jb.first = ctx->chromstarts[c];
-                jb.last = ctx->chromstarts[c + 1] - 1;
-                jb.chrom = c;
-                jobs.push_back(jb);
-            }
-        if (pass == 0) n_fast = jobs.size();
-    }
-    if ((rc = ensure(ctx, &ctx->d_jobs, &ctx->jobs_cap, jobs.size() + 1))) return rc;
-    HIP_TRY(ctx, hipMemcpy(ctx->d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice));
-    const int    mlen = max_chrom_len(ctx);
-    const size_t stride = (size_t)mlen * 528;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-    free_b += ctx->spill_bytes + ctx->wbuf_cap * sizeof(double);
-    int          grid_cap = ctx->n_cu * ctx->fast_blocks_per_cu - ctx->reserve_blocks;
-    if (grid_cap < 1) grid_cap = 1;
-    const size_t per_blk = (size_t)CNF2_WAVES_PER_BLOCK * stride * sizeof(double);
-    if ((size_t)grid_cap * per_blk > free_b / 4) grid_cap = (int)(free_b / 4 / per_blk);
-    if (grid_cap < 1) return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the spill of one block");
-    {
-        size_t capd = ctx->spill_bytes / sizeof(double);
-        rc = ensure(ctx, &ctx->d_spill, &capd, (size_t)grid_cap * CNF2_WAVES_PER_BLOCK * stride);
-        ctx->spill_bytes = capd * sizeof(double);
-        if (rc) return rc;
-    }
-    const size_t per_job = (size_t)mlen * CNF2_TURN_ROW;
-    size_t       batch = (free_b - (size_t)grid_cap * per_blk) / 2 / (per_job * sizeof(double));
-    if (batch < 1) return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the alpha/beta rows of one job");
-    if (batch > jobs.size()) batch = jobs.size();
-    if (batch > 1000000) batch = 1000000;
-    batch = whole_rounds(batch, jobs.size(), grid_cap);
-    if (ctx->batch_jobs > 0 && batch > (size_t)ctx->batch_jobs) batch = (size_t)ctx->batch_jobs;
-    if ((rc = ensure(ctx, &ctx->d_wbuf, &ctx->wbuf_cap, batch * per_job))) return rc;
+    Batched b;
+    RC_TRY(batched_setup(ctx, ind_begin, n, flags, CNF2_TURN_ROW, 0, &b));
+    if (b.plan.fit == BATCH_NO_ROWS) return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the alpha/beta rows of one job");
+    const int mlen = b.max_len;
+    RC_TRY(ctx->d_wbuf.ensure(ctx, b.plan.batch * (size_t)mlen * CNF2_TURN_ROW));
     KernelParams p;
     base_params(ctx, &p);
     if (flags & CNF2_STATIC_JOBS) p.job_next = nullptr;
     p.windows      = ctx->d_windows + ind_begin;
     p.spill        = ctx->d_spill;
-    p.spill_stride = stride;
+    p.spill_stride = spill_stride(mlen);
     p.factors      = ctx->d_factors;
     p.loglik       = ctx->d_loglik;
     p.dosage       = ctx->d_dosage;
@@ -1738,28 +1432,20 @@ int cnf2_sweep_turn_scan(cnf2_ctx* ctx, int ind_begin, int ind_end, double* rawe
     q.turn_lse  = d_lse;
     q.valu_form = (flags & CNF2_TURN_VALU) ? 1 : 0;
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    for (int pass = 0; pass < 2; pass++) {
-        const size_t lo = pass ? n_fast : 0, hi = pass ? jobs.size() : n_fast;
-        for (size_t b0 = lo; b0 < hi; b0 += batch) {
-            const size_t nb = (hi - b0 < batch) ? hi - b0 : batch;
-            p.jobs   = ctx->d_jobs + b0;
-            p.n_jobs = (int)nb;
-            int grid = (int)((nb + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
-            if (grid > grid_cap) grid = grid_cap;
-            // alpha and beta do not see the tie rule: tied windows take the tile-producer kernel too (its rows, which
-            // would need the rule, go to the context's scratch and are not an output of this call)
-            const bool fast = pass == 0 || !(flags & CNF2_TIES_GENERAL);
-            if (fast) launch_fb_fast_ab(p, grid, ctx->stream);
-            else launch_fb_ab(p, grid, ctx->stream);
-            HIP_TRY(ctx, hipGetLastError());
-            q.kp     = p;
-            q.n_jobs = (int)nb;
-            q.max_len = jobs[b0].last - jobs[b0].first + 1;          // the batch's longest job is its first (chrom_order)
-            q.scaled_transitions = fast;
-            launch_turn_rows(q, ctx->stream);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-    }
+    RC_TRY(for_each_batch(ctx, b, &p, [&](int pass, int grid, int max_len) -> int {
+        // alpha and beta do not see the tie rule: tied windows take the tile-producer kernel too (its rows, which
+        // would need the rule, go to the context's scratch and are not an output of this call)
+        const bool fast = pass == 0 || !(flags & CNF2_TIES_GENERAL);
+        if (fast) HIP_TRY(ctx, launch_fb_fast(p, grid, {SW_ALPHA_BETA}, ctx->stream));
+        else HIP_TRY(ctx, launch_fb(p, grid, SW_ALPHA_BETA, ctx->stream));
+        q.kp      = p;
+        q.n_jobs  = p.n_jobs;
+        q.max_len = max_len;
+        q.scaled_transitions = fast;
+        launch_turn_rows(q, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+        return CNF2_OK;
+    }));
     HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
     ctx->timed = true;
     if (!out_dev) {
@@ -1789,16 +1475,13 @@ int cnf2_snapshot_priors(cnf2_ctx* ctx, const uint8_t* has_prior)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const size_t cnt = (size_t)ctx->n_rows * ctx->n_markers;
-    if (ctx->d_prior_allele8) HIP_TRY(ctx, hipFree(ctx->d_prior_allele8));
-    if (ctx->d_prior_sure) HIP_TRY(ctx, hipFree(ctx->d_prior_sure));
-    if (ctx->d_has_prior) HIP_TRY(ctx, hipFree(ctx->d_has_prior));
-    ctx->d_prior_allele8 = nullptr;
-    ctx->d_prior_sure = nullptr;
-    ctx->d_has_prior = nullptr;
+    RC_TRY(ctx->d_prior_allele8.release(ctx));
+    RC_TRY(ctx->d_prior_sure.release(ctx));
+    RC_TRY(ctx->d_has_prior.release(ctx));
     ctx->priors_set = false;
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_prior_allele8, cnt));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_prior_sure, cnt * sizeof(double2)));
-    HIP_TRY(ctx, hipMalloc((void**)&ctx->d_has_prior, ctx->ped.n_rec));
+    RC_TRY(ctx->d_prior_allele8.alloc(ctx, cnt));
+    RC_TRY(ctx->d_prior_sure.alloc(ctx, cnt));
+    RC_TRY(ctx->d_has_prior.alloc(ctx, ctx->ped.n_rec));
     HIP_TRY(ctx, hipMemcpy(ctx->d_prior_allele8, ctx->d_allele8, cnt, hipMemcpyDeviceToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_prior_sure, ctx->d_sure, cnt * sizeof(double2), hipMemcpyDeviceToDevice));
     HIP_TRY(ctx, hipMemcpy(ctx->d_has_prior, has_prior, ctx->ped.n_rec, hipMemcpyHostToDevice));
@@ -1840,29 +1523,16 @@ static int update_pass_impl(cnf2_ctx* ctx, int chrom, const int32_t* recs, int n
         }
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if (ctx->upd_rec_cap < R) {
-        if (ctx->d_row_of) HIP_TRY(ctx, hipFree(ctx->d_row_of));
-        if (ctx->d_children) HIP_TRY(ctx, hipFree(ctx->d_children));
-        ctx->d_row_of = ctx->d_children = nullptr;
-        ctx->upd_rec_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_row_of, sizeof(int32_t) * R));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_children, sizeof(int32_t) * R));
-        ctx->upd_rec_cap = R;
+    if (ctx->d_row_of.cap < R || ctx->d_children.cap < R) {
+        RC_TRY(ctx->d_row_of.release(ctx));
+        RC_TRY(ctx->d_children.release(ctx));
+        RC_TRY(ctx->d_row_of.alloc(ctx, R));
+        RC_TRY(ctx->d_children.alloc(ctx, R));
     }
-    if (ctx->rec_cap < R) {
-        if (ctx->d_desc) HIP_TRY(ctx, hipFree(ctx->d_desc));
-        if (ctx->d_rec_empty) HIP_TRY(ctx, hipFree(ctx->d_rec_empty));
-        ctx->d_desc = nullptr;
-        ctx->d_rec_empty = nullptr;
-        ctx->rec_cap = 0;
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_desc, sizeof(int32_t) * R));
-        HIP_TRY(ctx, hipMalloc((void**)&ctx->d_rec_empty, R));
-        ctx->rec_cap = R;
-    }
-    if (!ctx->d_chromstarts) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_chromstarts, sizeof(int32_t) * 65536));
+    RC_TRY(ensure_rec_tables(ctx, R));
+    RC_TRY(ctx->d_chromstarts.ensure(ctx, 65536));
     if (ctx->n_chrom + 1 > 65536) return fail(ctx, CNF2_ERR_ARG, "too many chromosomes");
-    if (!ctx->d_hits) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_hits, sizeof(int)));
+    RC_TRY(ctx->d_hits.ensure(ctx, 1));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_row_of, P.row_of.data(), sizeof(int32_t) * R, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_children, children, sizeof(int32_t) * R, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_desc, descendants, sizeof(int32_t) * R, hipMemcpyHostToDevice, ctx->stream));
@@ -1870,14 +1540,14 @@ static int update_pass_impl(cnf2_ctx* ctx, int chrom, const int32_t* recs, int n
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_chromstarts, ctx->chromstarts.data(), sizeof(int32_t) * (ctx->n_chrom + 1),
                                 hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_hits, 0, sizeof(int), ctx->stream));
-    if ((rc = ensure(ctx, &ctx->d_anyinfo, &ctx->anyinfo_cap, R * ctx->n_chrom))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_fw, &ctx->fw_cap, R * M * 2))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_ratio, &ctx->ratio_cap, R * M))) return rc;
+    RC_TRY(ctx->d_anyinfo.ensure(ctx, R * ctx->n_chrom));
+    RC_TRY(ctx->d_fw.ensure(ctx, R * M * 2));
+    RC_TRY(ctx->d_ratio.ensure(ctx, R * M));
     double *a_inf = infprobs, *a_hb = haplobase, *a_hc = haplocount;
     if (!acc_dev) {
-        if ((rc = ensure(ctx, &ctx->d_acc_inf, &ctx->acc_inf_cap, R * M * 4))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_acc_hb, &ctx->acc_hb_cap, R * M))) return rc;
-        if ((rc = ensure(ctx, &ctx->d_acc_hc, &ctx->acc_hc_cap, R * M))) return rc;
+        RC_TRY(ctx->d_acc_inf.ensure(ctx, R * M * 4));
+        RC_TRY(ctx->d_acc_hb.ensure(ctx, R * M));
+        RC_TRY(ctx->d_acc_hc.ensure(ctx, R * M));
         a_inf = ctx->d_acc_inf;
         a_hb  = ctx->d_acc_hb;
         a_hc  = ctx->d_acc_hc;
@@ -1891,7 +1561,7 @@ static int update_pass_impl(cnf2_ctx* ctx, int chrom, const int32_t* recs, int n
     memset(&u, 0, sizeof(u));
     u.n_rec = P.n_rec;
     if (recs) {
-        if ((rc = ensure(ctx, &ctx->d_updrecs, &ctx->updrecs_cap, (size_t)(n_recs > 0 ? n_recs : 1)))) return rc;
+        RC_TRY(ctx->d_updrecs.ensure(ctx, (size_t)(n_recs > 0 ? n_recs : 1)));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_updrecs, recs, sizeof(int32_t) * n_recs, hipMemcpyHostToDevice, ctx->stream));
         u.n_rec = n_recs;
         u.rec_list = ctx->d_updrecs;
@@ -1925,13 +1595,13 @@ static int update_pass_impl(cnf2_ctx* ctx, int chrom, const int32_t* recs, int n
     u.entropyfactor = entropyfactor;
     u.hits = ctx->d_hits;
     if (!(flags & CNF2_UPDATE_PLAIN)) {
-        if (!ctx->d_flow_next) HIP_TRY(ctx, hipMalloc((void**)&ctx->d_flow_next, 32 * sizeof(unsigned long long)));
-        if ((rc = ensure(ctx, &ctx->d_flow_out, &ctx->flow_out_cap, (RU ? RU : 1) * (size_t)(u.last - u.first + 1) * 4))) return rc;
+        RC_TRY(ctx->d_flow_next.ensure(ctx, 32));
+        RC_TRY(ctx->d_flow_out.ensure(ctx, (RU ? RU : 1) * (size_t)(u.last - u.first + 1) * 4));
         // the scouts work through their flows in chunks; a chunk's worth of set-aside entries (24 bytes each), no more
         // than the pass has flows (certainties: 4 per record and marker of the chromosome; weights: 1 per record and marker
         // of the chromosomes so far)
         const size_t chunk = todo_chunk(RU, (size_t)(u.last - u.first + 1), (size_t)u.chromstarts_host_upto);
-        if ((rc = ensure(ctx, &ctx->d_todo, &ctx->todo_cap, todo_doubles(chunk)))) return rc;
+        RC_TRY(ctx->d_todo.ensure(ctx, todo_doubles(chunk)));
         u.flow_next = ctx->d_flow_next;
         u.flow_out = ctx->d_flow_out;
         u.stats = getenv("CNF2_UPDATE_STATS") ? ctx->d_flow_next + 2 : nullptr;     // diagnostics only (no effect on results): a few atomics per wavefront
@@ -1982,8 +1652,7 @@ int cnf2_exchange_buffer(cnf2_ctx* ctx, size_t bytes, void** d_buf)
     if (!ctx || !d_buf) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    int rc = ensure(ctx, &ctx->d_xbuf, &ctx->xbuf_cap, bytes ? bytes : 1);
-    if (rc) return rc;
+    RC_TRY(ctx->d_xbuf.ensure(ctx, bytes ? bytes : 1));
     *d_buf = ctx->d_xbuf;
     return CNF2_OK;
 }
@@ -1991,7 +1660,7 @@ int cnf2_exchange_buffer(cnf2_ctx* ctx, size_t bytes, void** d_buf)
 int cnf2_exchange_read(cnf2_ctx* ctx, size_t offset, void* host_dst, size_t bytes)
 {
     if (!ctx || (!host_dst && bytes)) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
-    if (offset + bytes > ctx->xbuf_cap || !ctx->d_xbuf) return fail(ctx, CNF2_ERR_ARG, "beyond the exchange buffer");
+    if (offset + bytes > ctx->d_xbuf.cap || !ctx->d_xbuf) return fail(ctx, CNF2_ERR_ARG, "beyond the exchange buffer");
     if (!bytes) return CNF2_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2002,7 +1671,7 @@ int cnf2_exchange_read(cnf2_ctx* ctx, size_t offset, void* host_dst, size_t byte
 int cnf2_exchange_write(cnf2_ctx* ctx, size_t offset, const void* host_src, size_t bytes)
 {
     if (!ctx || (!host_src && bytes)) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
-    if (offset + bytes > ctx->xbuf_cap || !ctx->d_xbuf) return fail(ctx, CNF2_ERR_ARG, "beyond the exchange buffer");
+    if (offset + bytes > ctx->d_xbuf.cap || !ctx->d_xbuf) return fail(ctx, CNF2_ERR_ARG, "beyond the exchange buffer");
     if (!bytes) return CNF2_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2029,8 +1698,7 @@ static int exchange_lists(cnf2_ctx* ctx, const int32_t* recs, int n, bool rows)
         if (rows && idx[(size_t)n + i] == 0) return fail(ctx, CNF2_ERR_ARG, "record %d sits on the shared blank row", recs[i]);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc = ensure(ctx, &ctx->d_xidx, &ctx->xidx_cap, (size_t)(n > 0 ? n : 1) * 2);
-    if (rc) return rc;
+    RC_TRY(ctx->d_xidx.ensure(ctx, (size_t)(n > 0 ? n : 1) * 2));
     if (n > 0) {
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_xidx, idx.data(), sizeof(int32_t) * idx.size(), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // idx goes out of scope
@@ -2041,19 +1709,18 @@ static int exchange_lists(cnf2_ctx* ctx, const int32_t* recs, int n, bool rows)
 static int have_accumulators(cnf2_ctx* ctx)
 {
     const size_t R = (size_t)ctx->ped.n_rec, M = (size_t)ctx->n_markers;
-    if (!ctx->d_acc_inf || !ctx->d_acc_hb || !ctx->d_acc_hc || ctx->acc_inf_cap < R * M * 4 || ctx->acc_hb_cap < R * M ||
-        ctx->acc_hc_cap < R * M)
+    if (!ctx->d_acc_inf || !ctx->d_acc_hb || !ctx->d_acc_hc || ctx->d_acc_inf.cap < R * M * 4 || ctx->d_acc_hb.cap < R * M ||
+        ctx->d_acc_hc.cap < R * M)
         return fail(ctx, CNF2_ERR_STATE, "the context holds no accumulators (cnf2_sweep_accumulate with NULL accumulator pointers first)");
     return CNF2_OK;
 }
 
 int cnf2_pack_accumulators(cnf2_ctx* ctx, const int32_t* recs, int n, double* d_packed)
 {
-    int rc = exchange_lists(ctx, recs, n, false);
-    if (rc) return rc;
+    RC_TRY(exchange_lists(ctx, recs, n, false));
     if (n == 0) return CNF2_OK;
     if (!d_packed) return fail(ctx, CNF2_ERR_ARG, "packed buffer is NULL");
-    if ((rc = have_accumulators(ctx))) return rc;
+    RC_TRY(have_accumulators(ctx));
     const size_t M = (size_t)ctx->n_markers, S = M * 6;
     launch_copy_rows_f64(ctx->d_acc_inf, M * 4, ctx->d_xidx, d_packed, S, nullptr, n, M * 4, ctx->stream);
     launch_copy_rows_f64(ctx->d_acc_hb, M, ctx->d_xidx, d_packed + M * 4, S, nullptr, n, M, ctx->stream);
@@ -2065,11 +1732,10 @@ int cnf2_pack_accumulators(cnf2_ctx* ctx, const int32_t* recs, int n, double* d_
 
 int cnf2_unpack_accumulators(cnf2_ctx* ctx, const int32_t* recs, int n, const double* d_packed)
 {
-    int rc = exchange_lists(ctx, recs, n, false);
-    if (rc) return rc;
+    RC_TRY(exchange_lists(ctx, recs, n, false));
     if (n == 0) return CNF2_OK;
     if (!d_packed) return fail(ctx, CNF2_ERR_ARG, "packed buffer is NULL");
-    if ((rc = have_accumulators(ctx))) return rc;
+    RC_TRY(have_accumulators(ctx));
     const size_t M = (size_t)ctx->n_markers, S = M * 6;
     launch_copy_rows_f64(d_packed, S, nullptr, ctx->d_acc_inf, M * 4, ctx->d_xidx, n, M * 4, ctx->stream);
     launch_copy_rows_f64(d_packed + M * 4, S, nullptr, ctx->d_acc_hb, M, ctx->d_xidx, n, M, ctx->stream);
@@ -2081,14 +1747,13 @@ int cnf2_unpack_accumulators(cnf2_ctx* ctx, const int32_t* recs, int n, const do
 
 int cnf2_pack_rows(cnf2_ctx* ctx, const int32_t* recs, int n, void* d_packed)
 {
-    int rc = exchange_lists(ctx, recs, n, true);
-    if (rc) return rc;
+    RC_TRY(exchange_lists(ctx, recs, n, true));
     if (n == 0) return CNF2_OK;
     if (!d_packed) return fail(ctx, CNF2_ERR_ARG, "packed buffer is NULL");
     const size_t   M = (size_t)ctx->n_markers, B = cnf2_packed_row_bytes(ctx);
     const int32_t* rows = ctx->d_xidx + n;
     uint8_t*       q = (uint8_t*)d_packed;
-    launch_copy_rows_f64((const double*)ctx->d_sure, M * 2, rows, (double*)q, B / 8, nullptr, n, M * 2, ctx->stream);
+    launch_copy_rows_f64((const double*)ctx->d_sure.ptr, M * 2, rows, (double*)q, B / 8, nullptr, n, M * 2, ctx->stream);
     launch_copy_rows_f64(ctx->d_hw, M, rows, (double*)(q + M * 16), B / 8, nullptr, n, M, ctx->stream);
     launch_copy_rows_u8(ctx->d_allele8, M, rows, q + M * 24, B, nullptr, n, M, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
@@ -2098,14 +1763,13 @@ int cnf2_pack_rows(cnf2_ctx* ctx, const int32_t* recs, int n, void* d_packed)
 
 int cnf2_unpack_rows(cnf2_ctx* ctx, const int32_t* recs, int n, const void* d_packed)
 {
-    int rc = exchange_lists(ctx, recs, n, true);
-    if (rc) return rc;
+    RC_TRY(exchange_lists(ctx, recs, n, true));
     if (n == 0) return CNF2_OK;
     if (!d_packed) return fail(ctx, CNF2_ERR_ARG, "packed buffer is NULL");
     const size_t   M = (size_t)ctx->n_markers, B = cnf2_packed_row_bytes(ctx);
     const int32_t* rows = ctx->d_xidx + n;
     const uint8_t* q = (const uint8_t*)d_packed;
-    launch_copy_rows_f64((const double*)q, B / 8, nullptr, (double*)ctx->d_sure, M * 2, rows, n, M * 2, ctx->stream);
+    launch_copy_rows_f64((const double*)q, B / 8, nullptr, (double*)ctx->d_sure.ptr, M * 2, rows, n, M * 2, ctx->stream);
     launch_copy_rows_f64((const double*)(q + M * 16), B / 8, nullptr, ctx->d_hw, M, rows, n, M, ctx->stream);
     launch_copy_rows_u8(q + M * 24, B, nullptr, ctx->d_allele8, M, rows, n, M, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
@@ -2118,8 +1782,8 @@ int cnf2_download_accumulators(cnf2_ctx* ctx, double* infprobs, double* haplobas
 {
     if (!ctx) return fail(ctx, CNF2_ERR_ARG, "ctx is NULL");
     const size_t R = (size_t)ctx->ped.n_rec, M = (size_t)ctx->n_markers;
-    if (!ctx->d_acc_inf || !ctx->d_acc_hb || !ctx->d_acc_hc || ctx->acc_inf_cap < R * M * 4 || ctx->acc_hb_cap < R * M ||
-        ctx->acc_hc_cap < R * M)
+    if (!ctx->d_acc_inf || !ctx->d_acc_hb || !ctx->d_acc_hc || ctx->d_acc_inf.cap < R * M * 4 || ctx->d_acc_hb.cap < R * M ||
+        ctx->d_acc_hc.cap < R * M)
         return fail(ctx, CNF2_ERR_STATE, "the context holds no accumulators (cnf2_sweep_accumulate with NULL accumulator pointers first)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -2133,8 +1797,8 @@ int cnf2_accumulator_ptrs(cnf2_ctx* ctx, double** infprobs, double** haplobase, 
 {
     if (!ctx || !infprobs || !haplobase || !haplocount) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
     const size_t R = (size_t)ctx->ped.n_rec, M = (size_t)ctx->n_markers;
-    if (!ctx->d_acc_inf || !ctx->d_acc_hb || !ctx->d_acc_hc || ctx->acc_inf_cap < R * M * 4 || ctx->acc_hb_cap < R * M ||
-        ctx->acc_hc_cap < R * M)
+    if (!ctx->d_acc_inf || !ctx->d_acc_hb || !ctx->d_acc_hc || ctx->d_acc_inf.cap < R * M * 4 || ctx->d_acc_hb.cap < R * M ||
+        ctx->d_acc_hc.cap < R * M)
         return fail(ctx, CNF2_ERR_STATE, "the context holds no accumulators (cnf2_sweep_accumulate with NULL accumulator pointers first)");
     *infprobs = ctx->d_acc_inf;
     *haplobase = ctx->d_acc_hb;
@@ -2148,10 +1812,9 @@ int cnf2_upload_accumulators(cnf2_ctx* ctx, const double* infprobs, const double
     const size_t R = (size_t)ctx->ped.n_rec, M = (size_t)ctx->n_markers;
     if (R == 0 || M == 0) return fail(ctx, CNF2_ERR_STATE, "map and pedigree must be uploaded first");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    int rc;
-    if ((rc = ensure(ctx, &ctx->d_acc_inf, &ctx->acc_inf_cap, R * M * 4))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_acc_hb, &ctx->acc_hb_cap, R * M))) return rc;
-    if ((rc = ensure(ctx, &ctx->d_acc_hc, &ctx->acc_hc_cap, R * M))) return rc;
+    RC_TRY(ctx->d_acc_inf.ensure(ctx, R * M * 4));
+    RC_TRY(ctx->d_acc_hb.ensure(ctx, R * M));
+    RC_TRY(ctx->d_acc_hc.ensure(ctx, R * M));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (infprobs) HIP_TRY(ctx, hipMemcpy(ctx->d_acc_inf, infprobs, R * M * 4 * sizeof(double), hipMemcpyHostToDevice));
     if (haplobase) HIP_TRY(ctx, hipMemcpy(ctx->d_acc_hb, haplobase, R * M * sizeof(double), hipMemcpyHostToDevice));
@@ -2218,8 +1881,7 @@ static int scan_windows(cnf2_ctx* ctx, const int32_t* recs, int n, int mode)
             if (mode == 0 || (mode == 1 && slot_rec[k] > recs[i])) ws[i].flags[k] &= (uint8_t)~SLOT_FOUNDER;
         }
     }
-    int rc = ensure(ctx, &ctx->d_scanwin, &ctx->scanwin_cap, (size_t)n);
-    if (rc) return rc;
+    RC_TRY(ctx->d_scanwin.ensure(ctx, (size_t)n));
     HIP_TRY(ctx, hipMemcpy(ctx->d_scanwin, ws.data(), sizeof(Window) * n, hipMemcpyHostToDevice));
     return CNF2_OK;
 }
@@ -2233,11 +1895,10 @@ int cnf2_fixparents_scan(cnf2_ctx* ctx, const int32_t* recs, int n, uint8_t* ok_
     // grid.y holds the record index: slabs of at most 65 535 records (a pedigree of config 4's size has ~300 000)
     const int    slab = 65535;
     const size_t per = (size_t)ctx->n_markers * 2;
-    int rc;
-    if ((rc = ensure(ctx, &ctx->d_okout, &ctx->okout_cap, (size_t)(n < slab ? n : slab) * per))) return rc;
+    RC_TRY(ctx->d_okout.ensure(ctx, (size_t)(n < slab ? n : slab) * per));
     for (int i0 = 0; i0 < n; i0 += slab) {
         const int k = n - i0 < slab ? n - i0 : slab;
-        if ((rc = scan_windows(ctx, recs + i0, k, 0))) return rc;
+        RC_TRY(scan_windows(ctx, recs + i0, k, 0));
         KernelParams p;
         base_params(ctx, &p);
         p.windows = ctx->d_scanwin;
@@ -2261,11 +1922,10 @@ int cnf2_variances(cnf2_ctx* ctx, const int32_t* recs, int n, int ordered, doubl
     const bool brute = (ordered & 2) != 0;
     ordered &= 1;
     const int slab = brute ? 4096 : 65535;       // grid.y
-    int rc;
-    if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, (size_t)(n < slab ? n : slab) * M))) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, (size_t)(n < slab ? n : slab) * M));
     for (int i0 = 0; i0 < n; i0 += slab) {
         const int k = n - i0 < slab ? n - i0 : slab;
-        if ((rc = scan_windows(ctx, recs + i0, k, ordered ? 1 : 2))) return rc;
+        RC_TRY(scan_windows(ctx, recs + i0, k, ordered ? 1 : 2));
         KernelParams p;
         base_params(ctx, &p);
         p.windows = ctx->d_scanwin;
@@ -2288,12 +1948,11 @@ int cnf2_variances_exact(cnf2_ctx* ctx, const int32_t* recs, const int32_t* mark
         if (markers[q] < 0 || markers[q] >= ctx->n_markers) return fail(ctx, CNF2_ERR_ARG, "marker out of range at %d", q);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int slab = 1 << 20;
-    int       rc;
     // per entry: the result, then (behind all results) its marker
-    if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, (size_t)(n < slab ? n : slab) * 2))) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, (size_t)(n < slab ? n : slab) * 2));
     for (int i0 = 0; i0 < n; i0 += slab) {
         const int k = n - i0 < slab ? n - i0 : slab;
-        if ((rc = scan_windows(ctx, recs + i0, k, (ordered & 1) ? 1 : 2))) return rc;
+        RC_TRY(scan_windows(ctx, recs + i0, k, (ordered & 1) ? 1 : 2));
         int32_t* d_markers = (int32_t*)(ctx->d_scratch + k);
         HIP_TRY(ctx, hipMemcpyAsync(d_markers, markers + i0, (size_t)k * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
         KernelParams p;
@@ -2309,13 +1968,12 @@ int cnf2_variances_exact(cnf2_ctx* ctx, const int32_t* recs, const int32_t* mark
 
 int cnf2_addvariance(cnf2_ctx* ctx, int ind, int chrom, double* var_out)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (!var_out || ind < 0 || ind >= (int)ctx->windows.size() || chrom < 0 || chrom >= ctx->n_chrom)
         return fail(ctx, CNF2_ERR_ARG, "bad addvariance arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int first = ctx->chromstarts[chrom], len = ctx->chromstarts[chrom + 1] - first;
-    if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, (size_t)len))) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, (size_t)len));
     KernelParams p;
     base_params(ctx, &p);
     p.windows = ctx->d_windows + ind;
@@ -2328,12 +1986,11 @@ int cnf2_addvariance(cnf2_ctx* ctx, int ind, int chrom, double* var_out)
 
 int cnf2_emission(cnf2_ctx* ctx, int ind, int marker, double* e_out)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (ind < 0 || ind >= (int)ctx->windows.size() || marker < 0 || marker >= ctx->n_markers || !e_out)
         return fail(ctx, CNF2_ERR_ARG, "bad emission arguments");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, (size_t)512))) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, (size_t)512));
     KernelParams p;
     base_params(ctx, &p);
     launch_emission(p, ind, marker, ctx->d_scratch, ctx->stream);
@@ -2345,12 +2002,11 @@ int cnf2_emission(cnf2_ctx* ctx, int ind, int marker, double* e_out)
 
 int cnf2_emission_paths(cnf2_ctx* ctx, int ind, int marker, double* e_out)
 {
-    int rc = ready(ctx);
-    if (rc) return rc;
+    RC_TRY(ready(ctx));
     if (ind < 0 || ind >= (int)ctx->windows.size() || marker < 0 || marker >= ctx->n_markers || !e_out)
         return fail(ctx, CNF2_ERR_ARG, "bad emission arguments");
     const size_t n = (size_t)8 * 64 * 128;
-    if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, n))) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, n));
     KernelParams p;
     base_params(ctx, &p);
     p.windows = ctx->d_windows + ind;
@@ -2364,9 +2020,8 @@ int cnf2_emission_paths(cnf2_ctx* ctx, int ind, int marker, double* e_out)
 int cnf2_selftest_lane_xor(cnf2_ctx* ctx, double* out384)
 {
     if (!ctx || !out384) return CNF2_ERR_ARG;
-    int rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = ensure(ctx, &ctx->d_scratch, &ctx->scratch_cap, (size_t)512))) return rc;
+    RC_TRY(ctx->d_scratch.ensure(ctx, (size_t)512));
     launch_xor_selftest(ctx->d_scratch, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out384, ctx->d_scratch, 384 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));

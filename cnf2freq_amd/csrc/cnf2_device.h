@@ -6,35 +6,30 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cnf2_job.h"
 #include "cnf2_window.h"
 
 namespace cnf2 {
 
-#define CNF2_BLOCK 256
-#define CNF2_WAVES_PER_BLOCK (CNF2_BLOCK / 64)
 #define CNF2_MINFACTOR_F (-1e15f)  /* settings.h:29 */
 #define CNF2_IGNORED_D (-1e30)     /* cnF2freq.cpp:5378 */
 
 enum { KP_NO_DOSAGE = 1, KP_RAW_DOSAGE = 2, KP_NO_TIES = 4,
-       KP_ACC_TABLE = 8,    // accumulate: the table-form kernel does every window
-       KP_ACC_ATTOP = 16,
-       KP_ACC_LANES = 32,
-       KP_FLUSH_TINY = 64 };  // general sweep kernel: a state under 1e-300 of its vector is set to 0 before the emission (cnF2freq.cpp:1607-1611) // accumulate: path form with one lane per path (acc_paths_kernel) instead of the tile form // accumulate: the batch holds windows whose root is the top of its lines (table form)
+       KP_ACC_TABLE = 8,      // accumulate: the table-form kernel does every window
+       KP_ACC_ATTOP = 16,     // accumulate: the batch holds windows whose root is the top of its lines (table form)
+       KP_ACC_LANES = 32,     // accumulate: path form with one lane per path (acc_paths_kernel) instead of the tile form
+       KP_FLUSH_TINY = 64 };  // general sweep kernel: a state under 1e-300 of its vector is set to 0 before the emission (cnF2freq.cpp:1607-1611)
 
-// One unit of sequential work: an analysed individual on one chromosome
-// (the body of the loops at cnF2freq.cpp:5283 and 5294).
-struct Job {
-    int32_t ind;     // index into windows[] / output rows (local to the call)
-    int32_t first;   // chromstarts[c]
-    int32_t last;    // chromstarts[c+1] - 1
-    int32_t chrom;
-};
-
-// Four jobs of the same chromosome swept by one wavefront (fb_packed_kernel).
-struct PackedJob {
-    int32_t ind[4];
-    int32_t first, last, chrom;
-    int32_t homleaf;   // all four jobs: the grandparents are present and homozygous everywhere too (HOMLEAF)
+// What a sweep kernel leaves behind besides the likelihoods: the STOREW template argument of fb_kernel / fb_fast_kernel
+// (an int there, so that the kernels' names stay what the tools and logs in profiles/ match on)
+enum SweepVariant : int {
+    SW_PLAIN        = 0,   // the per-locus rows (p.dosage) unless KP_NO_DOSAGE
+    SW_WEIGHTS_ROWS = 1,   // accumulate mode: also the posterior weights wg of every marker into p.wbuf
+    SW_ALPHA_BETA   = 2,   // turn-scan mode: alpha e, beta and their scales into p.wbuf (CNF2_TURN_ROW doubles per marker); no rows
+    SW_WEIGHTS      = 3,   // accumulate mode of a call that did not ask for the per-locus rows (wg only)
+    SW_CROSSOVERS   = 4,   // posterior probability of a flip of every state bit across every gap (p.xo / p.xo_sum / p.xo_cnt); no rows
+    SW_VITERBI      = 5,   // max-product recursion and backtrace in place of the backward pass (p.vit_*); no rows
+    SW_SAMPLING     = 6    // whole paths drawn from the posterior, one draw per lane (p.smp_*); no beta, no rows
 };
 
 struct KernelParams {
@@ -120,8 +115,6 @@ struct AccParams {
 };
 void launch_acc_rows(const AccParams& q, hipStream_t stream);
 void launch_acc_gather(const AccParams& q, const int32_t* rec_start, const int32_t* list, int n_rec, hipStream_t stream);
-void launch_fb_fast_tied(const KernelParams& p, int grid, hipStream_t stream);
-void launch_fb_fast_tied_w(const KernelParams& p, int grid, hipStream_t stream);
 
 // Inputs of the per-iteration update kernels (cnf2_update.h): what doit does after the sweep of chromosome `chrom`
 // (cnF2freq.cpp:6232-6392): processinfprobs for the markers of that chromosome, updatehaploweights for every marker
@@ -171,12 +164,6 @@ void launch_okvals(const KernelParams& p, int n_windows, uint8_t* out, hipStream
 void launch_addvariance_batch(const KernelParams& p, int n_windows, double* out, hipStream_t stream);
 void launch_variance_exact(const KernelParams& p, const int32_t* markers, int n, double* out, hipStream_t stream);
 void launch_variance_closed(const KernelParams& p, int n_windows, double* out, hipStream_t stream);
-// rows = false: the instantiation that forms no per-locus rows (p.dosage is not written; windows with tie groups can take
-// it too: the posterior weights do not see the tie rule)
-void launch_fb_fast_w(const KernelParams& p, int grid, hipStream_t stream, bool rows = true);
-void launch_fb_w(const KernelParams& p, int grid, hipStream_t stream);
-void launch_fb_fast_ab(const KernelParams& p, int grid, hipStream_t stream);
-void launch_fb_ab(const KernelParams& p, int grid, hipStream_t stream);
 // Inputs of the batched turn scan (turn_rows_kernel): what a turn-scan sweep (STOREW == 2) left in kp.wbuf
 // Row of the turn-scan mode's batch buffer (doubles per job and marker): A = alphaminus e [4][64 lanes][2], B = beta
 // likewise, then per shift mode s the scales that make them absolute as mantissa and binary exponent
@@ -209,15 +196,24 @@ void launch_haplos_rows(const Stage2Params& q, uint32_t flags, double* out, hipS
 void launch_infprobs(const Stage2Params& q, int marker, uint32_t flags, double* out, hipStream_t stream);
 void launch_infprobs_rows(const Stage2Params& q, uint32_t flags, double* out, hipStream_t stream);
 void launch_addvariance(const KernelParams& p, int first, int len, double* out, hipStream_t stream);
-void launch_fb(const KernelParams& p, int grid, bool debug_store, hipStream_t stream);
-void launch_fb_xo(const KernelParams& p, int grid, hipStream_t stream);
-void launch_fb_fast_xo(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
-void launch_fb_fast_vit(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
-void launch_fb_fast_smp(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
+// The general kernel's instantiation for `variant` (SW_PLAIN, SW_WEIGHTS_ROWS, SW_ALPHA_BETA, SW_CROSSOVERS); debug_store: the
+// reference-layout store of ONE job (SW_PLAIN only).  Returns the launch's error; a combination that is not instantiated is
+// hipErrorInvalidValue, never another kernel.
+hipError_t launch_fb(const KernelParams& p, int grid, SweepVariant variant, hipStream_t stream, bool debug_store = false);
 int  fb_xo_blocks_per_cu();
 void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream);
-void launch_fb_fast(const KernelParams& p, int grid, bool half_spill, hipStream_t stream);
-void launch_fb_fast_xpose(const KernelParams& p, int grid, hipStream_t stream);
+// Which instantiation of fb_fast_kernel a launch takes.  half: alpha-minus spilled at every second marker (not
+// CNF2_FULL_SPILL); xpose: the transposing variant of the plain sweep; tied: the tile producer with a pass per tie
+// combination (windows with tie groups).  SW_WEIGHTS forms no per-locus rows: windows with tie groups can take it untied
+// (the posterior weights do not see the tie rule).
+struct FastVariant {
+    SweepVariant storew;
+    bool         half = true, xpose = false, tied = false;
+};
+// Zeroes the launch's job counter, launches the instantiation (asking once for the tied instantiations' dynamic LDS) and
+// the kernel that takes the logarithms of its likelihoods.  Returns the launches' error; a combination that is not
+// instantiated is hipErrorInvalidValue, never another kernel.
+hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStream_t stream);
 void launch_fb_packed(const KernelParams& p, int grid, hipStream_t stream);
 void launch_row_flags(const uint8_t* allele8, const double2* sure, int n_rows, int n_markers, uint8_t* flags,
                       hipStream_t stream);

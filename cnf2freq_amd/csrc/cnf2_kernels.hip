@@ -1199,7 +1199,8 @@ struct BwdState {
 template <bool HALF, int STOREW = 0, bool XPOSE = false, bool TIED = false>
 __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
 {
-    static_assert(!XPOSE || (HALF && STOREW == 0), "the transposing variant exists for the plain half-spill sweep");
+    static_assert(!XPOSE || (HALF && STOREW == SW_PLAIN), "the transposing variant exists for the plain half-spill sweep");
+    // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_SAMPLING); by value:
     // STOREW: 0 plain sweep; 1 accumulate mode (also stores the posterior weights wg); 2 turn-scan mode (stores alpha e, beta
     // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only); 4 crossover
     // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows);
@@ -1207,10 +1208,10 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
     // slot, and a backtrace replaces the backward pass: p.vit_logmax / p.vit_state / p.vit_shift; no rows); 6 sampling mode
     // (the plain forward pass; backward walks that rebuild alpha and draw whole paths from the posterior, one draw per
     // lane: p.smp_state / p.smp_shift / p.smp_logp; no beta, no rows)
-    constexpr bool ROWS = STOREW == 0 || STOREW == 1;      // class sums, restricted tables, tile epilogue, p.dosage
-    constexpr bool WG   = STOREW == 1 || STOREW == 3;
-    constexpr bool VIT  = STOREW == 5;
-    constexpr bool SMP  = STOREW == 6;
+    constexpr bool ROWS = STOREW == SW_PLAIN || STOREW == SW_WEIGHTS_ROWS;      // class sums, restricted tables, tile epilogue, p.dosage
+    constexpr bool WG   = STOREW == SW_WEIGHTS_ROWS || STOREW == SW_WEIGHTS;
+    constexpr bool VIT  = STOREW == SW_VITERBI;
+    constexpr bool SMP  = STOREW == SW_SAMPLING;
     static_assert(!VIT || (!XPOSE && !TIED), "the Viterbi mode is an instantiation of the untied DPP kernel");
     static_assert(!SMP || (!XPOSE && !TIED), "the sampling mode is an instantiation of the untied DPP kernel");
     static_assert(!TIED || (!XPOSE && ROWS), "tie combinations only matter to the rows");
@@ -4240,41 +4241,60 @@ void launch_fb_packed(const KernelParams& p, int grid, hipStream_t stream)
 
 // dynamic LDS of the tied instantiations: 8 table rows per wave, each with the restricted tables of two tie combinations
 #define CNF2_TIED_LDS_BYTES (CNF2_WAVES_PER_BLOCK * 8 * (TAB_STRIDE + 128) * (int)sizeof(double))
-template <class K>
-static void allow_tied_lds(K kernel)
+template <bool HALF, int STOREW, bool XPOSE = false, bool TIED = false>
+static void launch_fast_as(const KernelParams& p, int grid, hipStream_t stream)
 {
-    static bool done = false;        // (per instantiation; more than 64 KB of dynamic LDS has to be asked for once)
-    if (!done) {
+    const auto kernel = fb_fast_kernel<HALF, STOREW, XPOSE, TIED>;
+    static bool asked = false;       // (per instantiation; more than 64 KB of dynamic LDS has to be asked for once)
+    if (TIED && !asked) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CNF2_TIED_LDS_BYTES);
-        done = true;
+        asked = true;
     }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(CNF2_BLOCK), TIED ? CNF2_TIED_LDS_BYTES : 0, stream, p);
 }
-void launch_fb_fast_tied(const KernelParams& p, int grid, hipStream_t stream)
+static constexpr int fast_key(int storew, bool half, bool xpose = false, bool tied = false)
+{
+    return storew | (half ? 8 : 0) | (xpose ? 16 : 0) | (tied ? 32 : 0);
+}
+hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStream_t stream)
 {
     zero_job_counter(p, stream);
-    allow_tied_lds(fb_fast_kernel<true, 0, false, true>);
-    hipLaunchKernelGGL((fb_fast_kernel<true, 0, false, true>), dim3(grid), dim3(CNF2_BLOCK), CNF2_TIED_LDS_BYTES, stream, p);
+    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the fourteen instantiations there are
+    case fast_key(SW_PLAIN, true): launch_fast_as<true, SW_PLAIN>(p, grid, stream); break;
+    case fast_key(SW_PLAIN, false): launch_fast_as<false, SW_PLAIN>(p, grid, stream); break;
+    case fast_key(SW_PLAIN, true, true): launch_fast_as<true, SW_PLAIN, true>(p, grid, stream); break;
+    case fast_key(SW_PLAIN, true, false, true): launch_fast_as<true, SW_PLAIN, false, true>(p, grid, stream); break;
+    case fast_key(SW_WEIGHTS_ROWS, true): launch_fast_as<true, SW_WEIGHTS_ROWS>(p, grid, stream); break;
+    case fast_key(SW_WEIGHTS_ROWS, true, false, true): launch_fast_as<true, SW_WEIGHTS_ROWS, false, true>(p, grid, stream); break;
+    case fast_key(SW_ALPHA_BETA, true): launch_fast_as<true, SW_ALPHA_BETA>(p, grid, stream); break;
+    case fast_key(SW_WEIGHTS, true): launch_fast_as<true, SW_WEIGHTS>(p, grid, stream); break;
+    case fast_key(SW_CROSSOVERS, true): launch_fast_as<true, SW_CROSSOVERS>(p, grid, stream); break;
+    case fast_key(SW_CROSSOVERS, false): launch_fast_as<false, SW_CROSSOVERS>(p, grid, stream); break;
+    case fast_key(SW_VITERBI, true): launch_fast_as<true, SW_VITERBI>(p, grid, stream); break;
+    case fast_key(SW_VITERBI, false): launch_fast_as<false, SW_VITERBI>(p, grid, stream); break;
+    case fast_key(SW_SAMPLING, true): launch_fast_as<true, SW_SAMPLING>(p, grid, stream); break;
+    case fast_key(SW_SAMPLING, false): launch_fast_as<false, SW_SAMPLING>(p, grid, stream); break;
+    default: return hipErrorInvalidValue;
+    }
     launch_likelihood_logs(p, stream);
+    return hipGetLastError();
 }
-void launch_fb_fast_tied_w(const KernelParams& p, int grid, hipStream_t stream)
+
+hipError_t launch_fb(const KernelParams& p, int grid, SweepVariant variant, hipStream_t stream, bool debug_store)
 {
-    zero_job_counter(p, stream);
-    allow_tied_lds(fb_fast_kernel<true, 1, false, true>);
-    hipLaunchKernelGGL((fb_fast_kernel<true, 1, false, true>), dim3(grid), dim3(CNF2_BLOCK), CNF2_TIED_LDS_BYTES, stream, p);
-    launch_likelihood_logs(p, stream);
-}
-void launch_fb_fast_xpose(const KernelParams& p, int grid, hipStream_t stream)
-{
-    zero_job_counter(p, stream);
-    hipLaunchKernelGGL((fb_fast_kernel<true, 0, true>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    launch_likelihood_logs(p, stream);
-}
-void launch_fb_fast(const KernelParams& p, int grid, bool half_spill, hipStream_t stream)
-{
-    zero_job_counter(p, stream);
-    if (half_spill) hipLaunchKernelGGL(fb_fast_kernel<true>, dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    else hipLaunchKernelGGL(fb_fast_kernel<false>, dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    launch_likelihood_logs(p, stream);
+    const dim3 g(grid), b(CNF2_BLOCK);
+    if (debug_store && variant != SW_PLAIN) return hipErrorInvalidValue;
+    switch (variant) {                                               // the five instantiations there are
+    case SW_PLAIN:
+        if (debug_store) hipLaunchKernelGGL(fb_kernel<true>, g, b, 0, stream, p);
+        else hipLaunchKernelGGL(fb_kernel<false>, g, b, 0, stream, p);
+        break;
+    case SW_WEIGHTS_ROWS: hipLaunchKernelGGL((fb_kernel<false, SW_WEIGHTS_ROWS>), g, b, 0, stream, p); break;
+    case SW_ALPHA_BETA: hipLaunchKernelGGL((fb_kernel<false, SW_ALPHA_BETA>), g, b, 0, stream, p); break;
+    case SW_CROSSOVERS: hipLaunchKernelGGL((fb_kernel<false, SW_CROSSOVERS>), g, b, 0, stream, p); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
 }
 
 void launch_row_flags(const uint8_t* allele8, const double2* sure, int n_rows, int n_markers, uint8_t* flags,
@@ -4283,53 +4303,11 @@ void launch_row_flags(const uint8_t* allele8, const double2* sure, int n_rows, i
     hipLaunchKernelGGL(row_flags_kernel, dim3(n_rows), dim3(256), 0, stream, allele8, sure, n_markers, flags);
 }
 
-void launch_fb_fast_w(const KernelParams& p, int grid, hipStream_t stream, bool rows)
-{
-    zero_job_counter(p, stream);
-    if (rows) hipLaunchKernelGGL((fb_fast_kernel<true, 1>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    else hipLaunchKernelGGL((fb_fast_kernel<true, 3>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    launch_likelihood_logs(p, stream);
-}
-void launch_fb_w(const KernelParams& p, int grid, hipStream_t stream)
-{
-    hipLaunchKernelGGL((fb_kernel<false, 1>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-}
-void launch_fb_fast_xo(const KernelParams& p, int grid, bool half_spill, hipStream_t stream)
-{
-    zero_job_counter(p, stream);
-    if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    else hipLaunchKernelGGL((fb_fast_kernel<false, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    launch_likelihood_logs(p, stream);
-}
-void launch_fb_fast_vit(const KernelParams& p, int grid, bool half_spill, hipStream_t stream)
-{
-    zero_job_counter(p, stream);
-    if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 5>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    else hipLaunchKernelGGL((fb_fast_kernel<false, 5>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    launch_likelihood_logs(p, stream);
-}
-void launch_fb_fast_smp(const KernelParams& p, int grid, bool half_spill, hipStream_t stream)
-{
-    zero_job_counter(p, stream);
-    if (half_spill) hipLaunchKernelGGL((fb_fast_kernel<true, 6>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    else hipLaunchKernelGGL((fb_fast_kernel<false, 6>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    launch_likelihood_logs(p, stream);
-}
 int fb_xo_blocks_per_cu()
 {
     int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fb_kernel<false, 4>, CNF2_BLOCK, 0) != hipSuccess) n = 1;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fb_kernel<false, SW_CROSSOVERS>, CNF2_BLOCK, 0) != hipSuccess) n = 1;
     return n < 1 ? 1 : n;
-}
-void launch_fb_fast_ab(const KernelParams& p, int grid, hipStream_t stream)
-{
-    zero_job_counter(p, stream);
-    hipLaunchKernelGGL((fb_fast_kernel<true, 2>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    launch_likelihood_logs(p, stream);
-}
-void launch_fb_ab(const KernelParams& p, int grid, hipStream_t stream)
-{
-    hipLaunchKernelGGL((fb_kernel<false, 2>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
 }
 
 // =====================================================================================
@@ -4696,20 +4674,9 @@ int fb_fast_blocks_per_cu()
     return n < 1 ? 1 : n;
 }
 
-void launch_fb(const KernelParams& p, int grid, bool debug_store, hipStream_t stream)
-{
-    if (debug_store) hipLaunchKernelGGL(fb_kernel<true>, dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-    else hipLaunchKernelGGL(fb_kernel<false>, dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
-}
-
 void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream)
 {
     hipLaunchKernelGGL(crossover_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
-}
-
-void launch_fb_xo(const KernelParams& p, int grid, hipStream_t stream)
-{
-    hipLaunchKernelGGL((fb_kernel<false, 4>), dim3(grid), dim3(CNF2_BLOCK), 0, stream, p);
 }
 
 void launch_emission(const KernelParams& p, int ind, int marker, double* out, hipStream_t stream)

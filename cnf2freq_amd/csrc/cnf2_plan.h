@@ -1,0 +1,217 @@
+// cnf2_plan.h -- what the sweep entry points of cnf2_capi.hip decide on the host before they launch: the job list, the
+// grids and the split of free memory between spill slots and batch buffers.  Pure functions of the window tables, the map
+// and a few numbers of the device; plain C++ (no HIP) so that they are unit-tested without a GPU (tests/test_host_plan.py).
+#ifndef CNF2_PLAN_H
+#define CNF2_PLAN_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/cnf2hip.h"
+#include "cnf2_emission.h"
+#include "cnf2_job.h"
+#include "cnf2_window.h"
+
+namespace cnf2 {
+
+// ------------------------------------------------------------------------------------------------ job list
+// The chromosomes in the order their jobs are listed: longest first (ties in map order).  The waves of a launch take the
+// jobs in list order (KernelParams::job_next), so the long jobs start first and a launch ends on the short ones; the jobs of
+// one chromosome keep the order of the individuals, so nothing that adds up over individuals sees a difference.
+inline std::vector<int> chrom_order(const int32_t* chromstarts, int n_chrom)
+{
+    std::vector<int> o(n_chrom);
+    for (int c = 0; c < n_chrom; c++) o[c] = c;
+    std::stable_sort(o.begin(), o.end(), [&](int a, int b) {
+        return chromstarts[a + 1] - chromstarts[a] > chromstarts[b + 1] - chromstarts[b];
+    });
+    return o;
+}
+
+inline int max_chrom_len(const int32_t* chromstarts, int n_chrom)
+{
+    int mx = 0;
+    for (int c = 0; c < n_chrom; c++) mx = std::max(mx, (int)(chromstarts[c + 1] - chromstarts[c]));
+    return mx;
+}
+
+struct JobPlan {
+    std::vector<Job>       jobs;         // [0, n_fast): windows without an active tie group (fast kernel); the tied ones after
+    size_t                 n_fast = 0;
+    std::vector<PackedJob> pjobs;        // CNF2_MERGE_MODES: four windows to a wavefront (fb_packed_kernel)
+};
+
+// Job list of the individuals [ind_begin, ind_begin + n): individuals x chromosomes (the loops at cnF2freq.cpp:5283 and
+// 5294), windows without an active tie group first (fast kernel), tied windows after (general or tied kernel).  Of `flags`
+// CNF2_NO_TIES (no window counts as tied), CNF2_FLUSH_TINY (every window takes the general kernel's route, the second list)
+// and CNF2_MERGE_MODES matter: windows whose two parents are homozygous with equal sure everywhere (row_hom) go four to a
+// wavefront; groups are formed per chromosome, what does not fill a group of four stays with the ordinary kernel.
+inline JobPlan plan_jobs(const Window* windows, const int32_t* chromstarts, int n_chrom, int ind_begin, int n, uint32_t flags,
+                         const uint8_t* row_hom)
+{
+    JobPlan                plan;
+    const std::vector<int> order = chrom_order(chromstarts, n_chrom);
+    const bool             merge = (flags & CNF2_MERGE_MODES) && !(flags & (CNF2_FULL_SPILL | CNF2_FLUSH_TINY));
+    auto tied = [&](const Window& w) { return (w.n_groups > 0 && !(flags & CNF2_NO_TIES)) || (flags & CNF2_FLUSH_TINY); };
+    auto mergeable = [&](const Window& w) {
+        if (w.n_groups > 0 && !(flags & CNF2_NO_TIES)) return false;
+        if (w.shiftignore != 0 || w.shiftend != 8 || (w.flags[0] & SLOT_FOUNDER)) return false;
+        for (int k = 1; k <= 4; k += 3) {
+            if (!(w.flags[k] & SLOT_PRESENT) || w.row[k] < 0) return false;
+            if (!row_hom[w.row[k]]) return false;
+        }
+        return true;
+    };
+    // a group shares the producer's instantiation: windows whose grandparents are all present and homozygous everywhere
+    // (SLOT_HOM) are grouped apart from the others
+    auto homleaf = [](const Window& w) {
+        const int gp = w.flags[2] & w.flags[3] & w.flags[5] & w.flags[6];
+        return (gp & SLOT_HOM) && (gp & SLOT_PRESENT);
+    };
+    std::vector<uint8_t> packed(merge ? n : 0, 0);
+    for (int cls = 0; merge && cls < 2; cls++) {
+        std::vector<int> el;
+        for (int j = 0; j < n; j++) {
+            const Window& w = windows[ind_begin + j];
+            if (mergeable(w) && (homleaf(w) ? 1 : 0) == cls) el.push_back(j);
+        }
+        const size_t full = el.size() / 4 * 4;
+        for (size_t k = 0; k < full; k++) packed[el[k]] = 1;
+        for (int c : order)
+            for (size_t k = 0; k < full; k += 4) {
+                PackedJob pj;
+                for (int i = 0; i < 4; i++) pj.ind[i] = el[k + i];
+                pj.first   = chromstarts[c];
+                pj.last    = chromstarts[c + 1] - 1;
+                pj.chrom   = c;
+                pj.homleaf = cls;
+                plan.pjobs.push_back(pj);
+            }
+    }
+    for (int pass = 0; pass < 2; pass++) {
+        for (int c : order)
+            for (int j = 0; j < n; j++) {
+                if (merge && packed[j]) continue;
+                if (tied(windows[ind_begin + j]) != (pass == 1)) continue;
+                Job jb;
+                jb.ind   = j;
+                jb.first = chromstarts[c];
+                jb.last  = chromstarts[c + 1] - 1;
+                jb.chrom = c;
+                plan.jobs.push_back(jb);
+            }
+        if (pass == 0) plan.n_fast = plan.jobs.size();
+    }
+    return plan;
+}
+
+// ------------------------------------------------------------------------------------------------ grids and spill
+// Doubles of a wave's spill slot per marker of the longest chromosome: covers every layout (520 or 528 doubles per (pair
+// of) marker(s) in the fast kernel, 512 in the general kernel)
+constexpr size_t PLAN_SPILL_ROW = 528;
+inline size_t spill_stride(int max_len) { return (size_t)max_len * PLAN_SPILL_ROW; }
+inline size_t spill_block_bytes(int max_len) { return (size_t)CNF2_WAVES_PER_BLOCK * spill_stride(max_len) * sizeof(double); }
+
+// blocks of a kernel with `per_cu` blocks to a compute unit that are resident at once, less the workgroup slots left free
+// for concurrent kernels
+inline int resident_blocks(int n_cu, int per_cu, int reserve_blocks) { return std::max(1, n_cu * per_cu - reserve_blocks); }
+// one wave per job in flight, capped (at what is resident: the spill stays small)
+inline int grid_for(size_t n_jobs, int cap)
+{
+    const size_t blocks = (n_jobs + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK;
+    return (int)std::min(blocks, (size_t)cap);
+}
+
+// cnf2_sweep and its modes: the share of free memory (plus what the context already holds of it) the spill slots may take
+constexpr double PLAN_SWEEP_SPILL_SHARE = 0.6;
+
+// Grids of the two kernels of a sweep: n_fast jobs of the untied windows (or packed jobs, whichever are more: the packed
+// kernel runs before the ordinary fast kernel on the same stream and in the same spill slots) and n_general of the tied
+// ones.  One spill slot per resident wave; long chromosomes make slots big: the spill stays within the share by running
+// fewer waves, and when both kernels run -- side by side on two streams with disjoint slots -- they share the budget.
+// false: not even one block's slots fit.
+inline bool plan_sweep_grids(int n_cu, int fast_per_cu, int gen_per_cu, int reserve_blocks, size_t n_fast, size_t n_general,
+                             size_t free_bytes, size_t held_bytes, int max_len, int* grid_fast, int* grid_gen)
+{
+    const size_t budget = (size_t)((double)(free_bytes + held_bytes) * PLAN_SWEEP_SPILL_SHARE);
+    const size_t per_blk = spill_block_bytes(max_len);
+    const size_t max_blks = budget / per_blk;
+    if (max_blks < 1) return false;
+    int gf = (int)std::min((size_t)grid_for(n_fast, resident_blocks(n_cu, fast_per_cu, reserve_blocks)), max_blks);
+    int gg = (int)std::min((size_t)grid_for(n_general, resident_blocks(n_cu, gen_per_cu, reserve_blocks)), max_blks);
+    if (n_fast > 0 && n_general > 0)
+        while ((size_t)(gf + gg) * per_blk > budget && gf + gg > 2) {
+            if (gf > 1) gf--;
+            if (gg > 1 && (size_t)(gf + gg) * per_blk > budget) gg--;
+        }
+    *grid_fast = gf;
+    *grid_gen  = gg;
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ batched consumers
+// cnf2_sweep_accumulate and cnf2_sweep_turn_scan: the spill takes at most a quarter of what is free, the batch buffer half of
+// the rest; a batch holds at most PLAN_BATCH_MAX_JOBS jobs
+constexpr size_t PLAN_BATCH_SPILL_PART = 4;
+constexpr size_t PLAN_BATCH_ROWS_PART  = 2;
+constexpr size_t PLAN_BATCH_MAX_JOBS   = 1000000;
+
+// A batch of the batched consumers is swept by the resident waves in rounds (a wave takes the next job when it has finished
+// one): 6.1 rounds take the time of 7.  When the jobs do not fit one batch, a batch is a whole number of rounds.
+inline size_t whole_rounds(size_t batch, size_t n_jobs, int grid_cap)
+{
+    const size_t waves = (size_t)grid_cap * CNF2_WAVES_PER_BLOCK;
+    if (batch >= n_jobs || batch < waves) return batch;
+    return batch / waves * waves;
+}
+
+enum BatchFit { BATCH_FITS = 0, BATCH_NO_SPILL, BATCH_NO_PART, BATCH_NO_ROWS };   // what memory did not suffice for
+struct BatchPlan {
+    BatchFit fit = BATCH_FITS;
+    int      grid_cap = 0;     // blocks of a sweep launch (one spill slot per wave)
+    size_t   batch = 0;        // jobs per batch
+};
+
+// free_bytes: what the device reports free; held_bytes: the spill and the batch buffer the context already holds (they are
+// reused or replaced).  row_doubles: doubles of the batch buffer per job and marker (512 for the accumulate weights,
+// CNF2_TURN_ROW for the turn scan).  part_need / part_held: doubles of the per-individual rows of CNF2_DETERMINISTIC (0 without)
+// and what the context holds of them; they are taken out of what is free BEFORE the batch buffer is sized, so that the batch
+// buffer cannot leave them without memory.  batch_jobs: the caller's cap on a batch (0 = none).
+inline BatchPlan plan_batches(int n_cu, int per_cu, int reserve_blocks, size_t free_bytes, size_t held_bytes, int max_len,
+                              size_t row_doubles, size_t n_jobs, int batch_jobs, size_t part_need, size_t part_held)
+{
+    BatchPlan    plan;
+    size_t       free_b = free_bytes + held_bytes;
+    const size_t per_blk = spill_block_bytes(max_len);
+    plan.grid_cap = resident_blocks(n_cu, per_cu, reserve_blocks);
+    const size_t spill_max = free_b / PLAN_BATCH_SPILL_PART;
+    if ((size_t)plan.grid_cap * per_blk > spill_max) plan.grid_cap = (int)(spill_max / per_blk);
+    if (plan.grid_cap < 1) {
+        plan.fit = BATCH_NO_SPILL;
+        return plan;
+    }
+    if (part_need) {
+        const size_t need = part_need * sizeof(double), have = part_held * sizeof(double);
+        if (need > free_b / 2 + have) {
+            plan.fit = BATCH_NO_PART;
+            return plan;
+        }
+        free_b -= need > have ? need - have : 0;
+    }
+    const size_t per_job = (size_t)max_len * row_doubles;
+    plan.batch = (free_b - (size_t)plan.grid_cap * per_blk) / PLAN_BATCH_ROWS_PART / (per_job * sizeof(double));
+    if (plan.batch < 1) {
+        plan.fit = BATCH_NO_ROWS;
+        return plan;
+    }
+    plan.batch = std::min(std::min(plan.batch, n_jobs), PLAN_BATCH_MAX_JOBS);
+    plan.batch = whole_rounds(plan.batch, n_jobs, plan.grid_cap);
+    if (batch_jobs > 0 && plan.batch > (size_t)batch_jobs) plan.batch = (size_t)batch_jobs;
+    return plan;
+}
+
+} // namespace cnf2
+#endif

@@ -28,6 +28,7 @@ static HostPedigree make_ped(int n_rec, const int32_t* par, const uint8_t* empty
 
 #include "cnf2_update.h"
 #include "cnf2_variance.h"
+#include "cnf2_plan.h"
 #include "host/cnf2_partition.h"
 #include "host/cnf2_shm_transport.h"
 #include "host/cnf2_format.h"
@@ -245,6 +246,48 @@ int shim_shm_transport_selftest(int world, int seg_doubles, int seg_bytes, int s
     }
     return failed;
 }
+
+// ---- the sweep entry points' planner (cnf2_plan.h) ----
+// the 64-byte window records of the analysed records dous[0..n_dous), as the context derives them (row_hom: optional [n_rows])
+void shim_windows(int n_rec, const int32_t* par, const uint8_t* empty, const int32_t* gen, const int32_t* row_of,
+                  const int32_t* dous, int n_dous, const uint8_t* row_hom, int n_rows, uint8_t* out)
+{
+    HostPedigree P = make_ped(n_rec, par, empty, gen, row_of);
+    if (row_hom) P.row_hom.assign(row_hom, row_hom + n_rows);
+    for (int j = 0; j < n_dous; j++) derive_window(P, dous[j], (Window*)out + j, nullptr);
+}
+// jobs_out[.][4] = ind, first, last, chrom; pjobs_out[.][8] = ind[4], first, last, chrom, homleaf; returns the number of jobs
+int shim_plan_jobs(const uint8_t* windows, const int32_t* chromstarts, int n_chrom, int ind_begin, int n, uint32_t flags,
+                   const uint8_t* row_hom, int32_t* jobs_out, int32_t* n_fast, int32_t* pjobs_out, int32_t* n_pjobs)
+{
+    const JobPlan plan = plan_jobs((const Window*)windows, chromstarts, n_chrom, ind_begin, n, flags, row_hom);
+    static_assert(sizeof(Job) == 16 && sizeof(PackedJob) == 32, "the tests read the job records as int32 rows");
+    if (!plan.jobs.empty()) memcpy(jobs_out, plan.jobs.data(), plan.jobs.size() * sizeof(Job));
+    if (!plan.pjobs.empty()) memcpy(pjobs_out, plan.pjobs.data(), plan.pjobs.size() * sizeof(PackedJob));
+    *n_fast  = (int32_t)plan.n_fast;
+    *n_pjobs = (int32_t)plan.pjobs.size();
+    return (int)plan.jobs.size();
+}
+// grids[2] = fast, general; returns 0 when not even one block's spill fits
+int shim_plan_sweep_grids(int n_cu, int fast_per_cu, int gen_per_cu, int reserve_blocks, uint64_t n_fast, uint64_t n_general,
+                          uint64_t free_bytes, uint64_t held_bytes, int max_len, int32_t* grids)
+{
+    int gf = -1, gg = -1;
+    const bool ok = plan_sweep_grids(n_cu, fast_per_cu, gen_per_cu, reserve_blocks, n_fast, n_general, free_bytes, held_bytes, max_len, &gf, &gg);
+    grids[0] = gf;
+    grids[1] = gg;
+    return ok ? 1 : 0;
+}
+// out[3] = fit (BatchFit), grid_cap, batch
+void shim_plan_batches(int n_cu, int per_cu, int reserve_blocks, uint64_t free_bytes, uint64_t held_bytes, int max_len,
+                       uint64_t row_doubles, uint64_t n_jobs, int batch_jobs, uint64_t part_need, uint64_t part_held, int64_t* out)
+{
+    const BatchPlan b = plan_batches(n_cu, per_cu, reserve_blocks, free_bytes, held_bytes, max_len, row_doubles, n_jobs, batch_jobs, part_need, part_held);
+    out[0] = b.fit;
+    out[1] = b.grid_cap;
+    out[2] = (int64_t)b.batch;
+}
+uint64_t shim_whole_rounds(uint64_t batch, uint64_t n_jobs, int grid_cap) { return whole_rounds(batch, n_jobs, grid_cap); }
 
 int shim_founders(int n_rec, const int32_t* par, const uint8_t* empty, const int32_t* gen,
                   const int32_t* row_of, uint8_t* out)
