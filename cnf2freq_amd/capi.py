@@ -42,6 +42,7 @@ SYMBOLS = [
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
+    "cnf2_sweep_place",
 ]
 
 
@@ -107,6 +108,7 @@ def load():
         L.cnf2_sweep_crossovers.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_viterbi.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_sample.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_sweep_place.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -393,6 +395,49 @@ class Context:
                   "cnf2_sweep_sample")
         logp = np.where(shift >= 0, logp, np.nan)
         return dict(factors=factors, loglik=loglik, state=state, shift=shift, logp=logp)
+
+    def _candidate_rows(self, cand_allele, cand_sure, cand_hw):
+        a = np.ascontiguousarray(cand_allele, np.uint8)
+        s = np.ascontiguousarray(cand_sure, np.float64)
+        h = None if cand_hw is None else np.ascontiguousarray(cand_hw, np.float64)
+        assert a.ndim == 3 and a.shape[2] == 2 and a.shape == s.shape and (h is None or h.shape == a.shape[:2])
+        return a, s, h
+
+    def sweep_place(self, cand_allele, cand_sure, cand_hw=None, ind_begin=0, ind_end=None, per_individual=False,
+                    full_spill=False, ties_general=False, static_jobs=False):
+        """cnf2_sweep_place: where Q unmapped markers go.  cand_allele / cand_sure [n_rows][Q][2] and cand_hw [n_rows][Q]
+        (None = 0.5) are the candidates' rows in the row index space of upload_rows.  Returns factors / loglik as sweep(),
+        place_sum[Q][M] (the growth of the range's log-likelihood with candidate q laid at marker m, over the individuals
+        that are neither skipped nor impossible there), n_zero[Q][M] (the impossible ones), null[Q] (the unlinked
+        baseline), n_contrib[C], and with per_individual=True place[n][Q][M] (MINFACTOR where impossible, IGNORED where
+        skipped), else None.  placement.best_positions reads the profile."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        a, s, h = self._candidate_rows(cand_allele, cand_sure, cand_hw)
+        Q = a.shape[1]
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        place = np.zeros((n, Q, self.n_markers)) if per_individual else None
+        psum = np.zeros((Q, self.n_markers))
+        nz = np.zeros((Q, self.n_markers), np.int32)
+        null = np.zeros(Q)
+        cnt = np.zeros(self.n_chrom, np.int32)
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0))
+        self._chk(self.L.cnf2_sweep_place(self.h, ind_begin, ind_end, Q, _p(a), _p(s), None if h is None else _p(h),
+                                          _p(factors), _p(loglik), _p(place) if per_individual else None, _p(psum),
+                                          _p(nz), _p(null), _p(cnt), flags), "cnf2_sweep_place")
+        return dict(factors=factors, loglik=loglik, place=place, place_sum=psum, n_zero=nz, null=null, n_contrib=cnt)
+
+    def sweep_place_device(self, cand_allele, cand_sure, cand_hw, ind_begin, ind_end, d_factors, d_loglik, d_place,
+                           d_place_sum, d_n_zero, d_null, d_n_contrib, flags=0):
+        """Device-pointer form (ints; d_place may be None); the candidate rows stay host arrays."""
+        a, s, h = self._candidate_rows(cand_allele, cand_sure, cand_hw)
+        self._chk(self.L.cnf2_sweep_place(self.h, ind_begin, ind_end, a.shape[1], _p(a), _p(s), None if h is None else _p(h),
+                                          C.c_void_p(d_factors), C.c_void_p(d_loglik),
+                                          C.c_void_p(d_place) if d_place else None, C.c_void_p(d_place_sum),
+                                          C.c_void_p(d_n_zero), C.c_void_p(d_null), C.c_void_p(d_n_contrib),
+                                          flags | OUT_DEVICE), "cnf2_sweep_place")
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

@@ -126,6 +126,15 @@ struct cnf2_ctx {
     DevBuf<int32_t> d_smp_sh;             // [n][K][n_chrom]
     DevBuf<double>  d_smp_lp;             // [n][K][n_chrom]
 
+    // marker placement (cnf2_sweep_place)
+    DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
+    DevBuf<double2> d_pl_sure;
+    DevBuf<double>  d_pl_hw;
+    DevBuf<double>  d_pl_emis;            // [n][qcap][512] candidate emission tables
+    DevBuf<double>  d_pl_out;             // [n][Q][n_markers] (host-output calls that ask for it)
+    DevBuf<double>  d_pl_sum, d_pl_null;  // [Q][n_markers], [Q]
+    DevBuf<int32_t> d_pl_nz;              // [Q][n_markers]
+
     // batched HOT LOOP 2 (cnf2_sweep_accumulate)
     std::vector<int32_t> slot_rec;   // [n_dous][7] record per window slot (derive_window), -1 none
     DevBuf<int32_t> d_slot_rec;
@@ -1184,6 +1193,8 @@ static int batched_setup(cnf2_ctx* ctx, int ind_begin, int n, uint32_t flags, si
 }
 
 enum : uint32_t { ACC_RESERVE_ONLY = 1u << 31 };     // internal flag of cnf2_sweep_accumulate (not in the header)
+// internal flags of cnf2_sweep_place (not in the header; A/B of its two routes to the likelihoods, see there)
+enum : uint32_t { PLACE_SWEEP_LIKELIHOODS = 1u << 30, PLACE_OWN_LIKELIHOODS = 1u << 29 };
 
 // Batched HOT LOOP 2 with its reductions (cnF2freq.cpp:5416-5577, 5876-5902 with moveinfprobs / movehaplos
 // 3577-3616) for the analysed individuals [ind_begin, ind_end): the sweep kernels run in their accumulate
@@ -1453,6 +1464,165 @@ int cnf2_sweep_turn_scan(cnf2_ctx* ctx, int ind_begin, int ind_end, double* rawe
         if (turn_lse_out) HIP_TRY(ctx, hipMemcpyAsync(turn_lse_out, d_lse, (size_t)n * M * 128 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return CNF2_OK;
+}
+
+// Candidates whose emission tables are held at once (a multiple of 16): more are processed in tiles over the same weights
+#define CNF2_PLACE_TILE 256
+// Whether a range without tied windows reports the placement instantiation's own likelihoods (one forward pass fewer)
+#ifndef PLACE_OWN_DEFAULT
+#define PLACE_OWN_DEFAULT true
+#endif
+
+// Marker placement: in batches, the placement sweep (the fast kernel's SW_POSTERIOR instantiation for every window: alpha
+// and beta do not see the tie rule) and, per tile of candidates, place_rows_kernel over the batch's state posteriors.  The
+// sweep runs once per batch, not once per tile.  The likelihoods: see below.
+int cnf2_sweep_place(cnf2_ctx* ctx, int ind_begin, int ind_end, int n_cand, const uint8_t* cand_allele, const double* cand_sure,
+                     const double* cand_hw, double* factors_out, double* loglik_out, double* place_out, double* place_sum_out,
+                     int32_t* n_zero_out, double* null_out, int32_t* n_contrib_out, uint32_t flags)
+{
+    RC_TRY(ready(ctx));
+    if (n_cand < 1 || !cand_allele || !cand_sure) return fail(ctx, CNF2_ERR_ARG, "n_cand must be >= 1 and cand_allele / cand_sure not NULL");
+    if (!factors_out || !loglik_out || !place_sum_out || !n_zero_out || !null_out || !n_contrib_out)
+        return fail(ctx, CNF2_ERR_ARG, "only place_out may be NULL");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    n = ind_end - ind_begin;
+    const size_t M = ctx->n_markers, C = ctx->n_chrom, Q = (size_t)n_cand, R = (size_t)ctx->n_rows;
+    if (Q * M > 0x7fffffff) return fail(ctx, CNF2_ERR_ARG, "too many candidates x markers in one call");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    // the candidate rows, in the row index space of cnf2_upload_rows
+    {
+        std::vector<uint8_t> packed(R * Q);
+        for (size_t i = 0; i < R * Q; i++) {
+            const uint8_t a0 = cand_allele[2 * i], a1 = cand_allele[2 * i + 1];
+            if (a0 > 15 || a1 > 15) return fail(ctx, CNF2_ERR_ARG, "allele value out of range");
+            packed[i] = (uint8_t)(a0 | (a1 << 4));
+        }
+        RC_TRY(ctx->d_pl_allele8.ensure(ctx, R * Q));
+        RC_TRY(ctx->d_pl_sure.ensure(ctx, R * Q));
+        RC_TRY(ctx->d_pl_hw.ensure(ctx, R * Q));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (an earlier call's kernels may still read the buffers)
+        HIP_TRY(ctx, hipMemcpy(ctx->d_pl_allele8, packed.data(), R * Q, hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMemcpy(ctx->d_pl_sure, cand_sure, R * Q * sizeof(double2), hipMemcpyHostToDevice));
+        if (cand_hw) HIP_TRY(ctx, hipMemcpy(ctx->d_pl_hw, cand_hw, R * Q * sizeof(double), hipMemcpyHostToDevice));
+        else {
+            const std::vector<double> half(R * Q, 0.5);
+            HIP_TRY(ctx, hipMemcpy(ctx->d_pl_hw, half.data(), R * Q * sizeof(double), hipMemcpyHostToDevice));
+        }
+    }
+
+    double * d_place, *d_sum, *d_null;
+    int32_t *d_nz, *d_cnt;
+    const size_t np = (size_t)n * Q * M;
+    RC_TRY(stage_out(ctx, dev, place_out, ctx->d_pl_out, np, &d_place));
+    RC_TRY(stage_out(ctx, dev, place_sum_out, ctx->d_pl_sum, Q * M, &d_sum));
+    RC_TRY(stage_out(ctx, dev, n_zero_out, ctx->d_pl_nz, Q * M, &d_nz));
+    RC_TRY(stage_out(ctx, dev, null_out, ctx->d_pl_null, Q, &d_null));
+    RC_TRY(stage_out(ctx, dev, n_contrib_out, ctx->d_xo_cnt, C, &d_cnt));
+    HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, Q * M * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_nz, 0, Q * M * sizeof(int32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_null, 0, Q * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, C * sizeof(int32_t), ctx->stream));
+
+    if (n > 0) {
+        // The likelihoods.  A range without tied windows: the placement instantiation's own (its forward pass is the plain sweep's: bit-equal).  With tied windows,
+        // or with PLACE_SWEEP_LIKELIHOODS: cnf2_sweep's launches without rows first, the placement instantiation's to scratch
+        bool tied_any = false;
+        for (int j = 0; j < n && !tied_any; j++) tied_any = ctx->windows[ind_begin + j].n_groups > 0;
+        const bool own = !tied_any && ((flags & PLACE_OWN_LIKELIHOODS) || (PLACE_OWN_DEFAULT && !(flags & PLACE_SWEEP_LIKELIHOODS)));
+        const size_t nf = (size_t)n * C * 8, nl = (size_t)n * C;
+        if (!own) {
+            const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+            RC_TRY(sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass | CNF2_NO_DOSAGE, SweepMode()));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the job list and the spill are replaced below)
+        } else if (!dev) {
+            RC_TRY(ctx->d_factors.ensure(ctx, nf));
+            RC_TRY(ctx->d_loglik.ensure(ctx, nl));
+        }
+        RC_TRY(ctx->d_xo_f.ensure(ctx, nf + nl + 1));
+
+        // the candidates' emission tables: all of them at once up to CNF2_PLACE_TILE, and an eighth of what is free
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+        const size_t per16 = (size_t)n * 16 * 512 * sizeof(double);
+        size_t       qcap = std::min((Q + 15) / 16 * 16, (size_t)CNF2_PLACE_TILE);
+        qcap = std::min(qcap, std::max((size_t)1, (free_b + ctx->d_pl_emis.cap * sizeof(double)) / 8 / per16) * 16);
+        RC_TRY(ctx->d_pl_emis.ensure(ctx, (size_t)n * qcap * 512));
+        const int n_tiles = (int)((Q + qcap - 1) / qcap);
+
+        // every window takes the untied instantiation: one list, by chromosome
+        Batched b;
+        RC_TRY(batched_setup(ctx, ind_begin, n, CNF2_NO_TIES, 512, 0, &b));
+        const int    mlen = b.max_len;
+        const size_t per_job = (size_t)mlen * 512;
+        if (b.plan.fit == BATCH_NO_ROWS)
+            return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the state posteriors of one job (%zu MB)", per_job >> 17);
+        RC_TRY(ctx->d_wbuf.ensure(ctx, b.plan.batch * per_job));
+
+        KernelParams p;
+        base_params(ctx, &p);
+        if (flags & CNF2_STATIC_JOBS) p.job_next = nullptr;
+        p.windows      = ctx->d_windows + ind_begin;
+        p.spill        = ctx->d_spill;
+        p.spill_stride = spill_stride(mlen);
+        p.factors      = own ? (dev ? factors_out : (double*)ctx->d_factors) : (double*)ctx->d_xo_f;
+        p.loglik       = own ? (dev ? loglik_out : (double*)ctx->d_loglik) : ctx->d_xo_f + nf;
+        p.wbuf         = ctx->d_wbuf;
+        p.wstride      = (size_t)mlen;
+        p.xo_cnt       = d_cnt;
+        KernelParams pc = p;             // the candidate rows: Q "markers"
+        pc.allele8   = ctx->d_pl_allele8;
+        pc.sure      = ctx->d_pl_sure;
+        pc.hw        = ctx->d_pl_hw;
+        pc.n_markers = n_cand;
+        PlaceParams q;
+        memset(&q, 0, sizeof(q));
+        q.n_cand    = n_cand;
+        q.qcap      = (int)qcap;
+        q.emis      = ctx->d_pl_emis;
+        q.place     = d_place;
+        q.place_sum = d_sum;
+        q.n_zero    = d_nz;
+        const bool half = !(flags & CNF2_FULL_SPILL);
+        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        if (n_tiles == 1) launch_place_emission(pc, n, 0, n_cand, (int)qcap, ctx->d_pl_emis, d_null, ctx->stream);
+        bool first_batch = true;
+        RC_TRY(for_each_batch(ctx, b, &p, [&](int, int grid, int max_len) -> int {
+            HIP_TRY(ctx, launch_fb_fast(p, grid, {SW_POSTERIOR, half}, ctx->stream));
+            q.kp      = p;
+            q.n_jobs  = p.n_jobs;
+            q.max_len = max_len;
+            for (int t = 0; t < n_tiles; t++) {
+                q.q0 = t * (int)qcap;
+                q.qn = std::min((int)qcap, n_cand - q.q0);
+                // (more than one tile: the tables of this tile for the whole range again; the baseline only once)
+                if (n_tiles > 1)
+                    launch_place_emission(pc, n, q.q0, q.qn, (int)qcap, ctx->d_pl_emis, first_batch ? d_null : nullptr, ctx->stream);
+                // jobs a block walks with its tile's sums in registers: as many as still leave the device some thousand blocks
+                const size_t units = (size_t)p.n_jobs * ((max_len + 63) / 64) * ((q.qn + 31) / 32);
+                q.group = (int)std::max((size_t)1, std::min((size_t)256, units / 8192));
+                launch_place_rows(q, ctx->stream);
+            }
+            HIP_TRY(ctx, hipGetLastError());
+            first_batch = false;
+            return CNF2_OK;
+        }));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+        if (own && !dev) {
+            RC_TRY(fetch_out(ctx, factors_out, (const double*)ctx->d_factors, nf));
+            RC_TRY(fetch_out(ctx, loglik_out, (const double*)ctx->d_loglik, nl));
+        }
+    }
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, place_out, d_place, np));
+    RC_TRY(fetch_out(ctx, place_sum_out, d_sum, Q * M));
+    RC_TRY(fetch_out(ctx, n_zero_out, d_nz, Q * M));
+    RC_TRY(fetch_out(ctx, null_out, d_null, Q));
+    RC_TRY(fetch_out(ctx, n_contrib_out, d_cnt, C));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
 }
 

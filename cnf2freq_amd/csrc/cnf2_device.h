@@ -29,7 +29,9 @@ enum SweepVariant : int {
     SW_WEIGHTS      = 3,   // accumulate mode of a call that did not ask for the per-locus rows (wg only)
     SW_CROSSOVERS   = 4,   // posterior probability of a flip of every state bit across every gap (p.xo / p.xo_sum / p.xo_cnt); no rows
     SW_VITERBI      = 5,   // max-product recursion and backtrace in place of the backward pass (p.vit_*); no rows
-    SW_SAMPLING     = 6    // whole paths drawn from the posterior, one draw per lane (p.smp_*); no beta, no rows
+    SW_SAMPLING     = 6,   // whole paths drawn from the posterior, one draw per lane (p.smp_*); no beta, no rows
+    SW_POSTERIOR    = 7    // placement mode: the state posteriors gamma = wg e of every marker into p.wbuf (SW_WEIGHTS' row and
+                           // layout), the jobs with a likelihood counted in p.xo_cnt; no rows
 };
 
 struct KernelParams {
@@ -80,7 +82,7 @@ struct KernelParams {
     int*           job_next;
     double*        xo;         // crossover mode: [n_ind][n_markers][6] per-individual crossover posteriors, or null
     double*        xo_sum;     // crossover mode: [n_markers][6] summed over the jobs' individuals (f64 atomics)
-    int32_t*       xo_cnt;     // crossover mode: [n_chrom] individuals that contribute (not skipped)
+    int32_t*       xo_cnt;     // crossover / placement mode: [n_chrom] individuals that contribute (not skipped)
     double*        vit_logmax; // Viterbi mode: [n_ind][n_chrom][8] log max-product per shift mode
     uint8_t*       vit_state;  // Viterbi mode: [n_ind][n_markers] MAP state g = j*8 + lo of every marker
     int32_t*       vit_shift;  // Viterbi mode: [n_ind][n_chrom] MAP shift mode, -1 where skipped
@@ -178,6 +180,28 @@ struct TurnParams {
     double*      turn_lse;    // [n_ind][n_markers][128] or NULL
 };
 void launch_turn_rows(const TurnParams& q, hipStream_t stream);
+
+// Inputs of the placement kernels: what a placement sweep (SW_POSTERIOR) left in kp.wbuf for the `n_jobs` jobs at kp.jobs,
+// and the candidates' emission tables.  place_emission_kernel fills `emis` for candidates [q0, q0 + qn) of every
+// individual of the call from the candidate rows (a KernelParams whose row pointers are the candidates', n_markers = Q);
+// place_rows_kernel contracts the two: place[i][q][m] = log sum_(s, g) gamma_(s, m)(g) e'_(s, q)(g).
+struct PlaceParams {
+    KernelParams kp;           // windows (offset to ind_begin), jobs (offset to the batch), wbuf / wstride, lexp
+    int          n_jobs;       // jobs in this batch
+    int          max_len;      // longest chromosome of the batch (grid.y)
+    int          group;        // consecutive jobs a block walks, carrying its tile's sums while the chromosome stays the same
+    int          n_cand;       // Q
+    int          q0, qn;       // the candidates `emis` holds: [q0, q0 + qn)
+    int          qcap;         // candidates per individual `emis` has room for (a multiple of 16)
+    const double* emis;        // [n_ind][qcap][512] in a weight row's (k, lane, register) order
+    double*      place;        // [n_ind][Q][n_markers] or null
+    double*      place_sum;    // [Q][n_markers], added to (f64 atomics)
+    int32_t*     n_zero;       // [Q][n_markers], added to
+};
+// cand: the candidate rows (allele8 / sure / hw with n_markers = Q; windows offset to ind_begin); null_sum [Q] is added to, or null
+void launch_place_emission(const KernelParams& cand, int n_ind, int q0, int qn, int qcap, double* emis, double* null_sum,
+                           hipStream_t stream);
+void launch_place_rows(const PlaceParams& q, hipStream_t stream);
 
 // Inputs of the stage-2 parity kernels: the reference-layout store of ONE individual x chromosome.
 struct Stage2Params {

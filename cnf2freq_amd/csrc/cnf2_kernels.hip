@@ -1207,11 +1207,14 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
     // 5 Viterbi mode (no alpha spill: the max-product recursion beside the forward pass stores its decisions in the spill
     // slot, and a backtrace replaces the backward pass: p.vit_logmax / p.vit_state / p.vit_shift; no rows); 6 sampling mode
     // (the plain forward pass; backward walks that rebuild alpha and draw whole paths from the posterior, one draw per
-    // lane: p.smp_state / p.smp_shift / p.smp_logp; no beta, no rows)
+    // lane: p.smp_state / p.smp_shift / p.smp_logp; no beta, no rows); 7 placement mode (stores the state posteriors
+    // gamma = wg e of every marker where the accumulate mode stores wg; counts the jobs with a likelihood in p.xo_cnt; no rows)
     constexpr bool ROWS = STOREW == SW_PLAIN || STOREW == SW_WEIGHTS_ROWS;      // class sums, restricted tables, tile epilogue, p.dosage
     constexpr bool WG   = STOREW == SW_WEIGHTS_ROWS || STOREW == SW_WEIGHTS;
     constexpr bool VIT  = STOREW == SW_VITERBI;
     constexpr bool SMP  = STOREW == SW_SAMPLING;
+    constexpr bool POST = STOREW == SW_POSTERIOR;
+    static_assert(!POST || (!XPOSE && !TIED), "the placement mode is an instantiation of the untied DPP kernel");
     static_assert(!VIT || (!XPOSE && !TIED), "the Viterbi mode is an instantiation of the untied DPP kernel");
     static_assert(!SMP || (!XPOSE && !TIED), "the sampling mode is an instantiation of the untied DPP kernel");
     static_assert(!TIED || (!XPOSE && ROWS), "tie combinations only matter to the rows");
@@ -1437,7 +1440,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 p.lexp[e]   = any_alive ? emax : CNF2_LEXP_DEAD;
             }
         }
-        if (STOREW == 4 && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
+        if ((STOREW == 4 || POST) && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
         if (VIT) {
             // ------------------------------------------------------------ Viterbi: logmax, MAP mode, backtrace
             // logmax_s = log(max-product) + the chromosome's dropped butterfly constants, as likelihood_logs_kernel finishes
@@ -1873,6 +1876,17 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 for (int j = 0; j < 8; j++) e[j] = S.ec[j];
             }
             else emission_from_row(row, c, e);
+            if (POST) {
+                // placement mode: gamma(s, g) = wg e, the posterior of state g in mode s at this marker, where the accumulate
+                // mode stores wg (same row, same layout); sums to the weight of the modes the rows count
+                double* wp = p.wbuf + ((size_t)job * p.wstride + ml) * 512;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const d2v v = {scale != 0.0 ? scale * wj[2 * k] * e[2 * k] : 0.0,
+                                   scale != 0.0 ? scale * wj[2 * k + 1] * e[2 * k + 1] : 0.0};
+                    __builtin_nontemporal_store(v, (d2v*)(wp + k * 128 + lane * 2));
+                }
+            }
             if (STOREW == 2) {
                 // turn-scan mode: A = alphaminus e and B = beta as held here, with the log2 of the scales that make them
                 // absolute (alphaminus: Fpre, and the stored normaliser of the even neighbour for a rebuilt odd marker)
@@ -4259,7 +4273,7 @@ static constexpr int fast_key(int storew, bool half, bool xpose = false, bool ti
 hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStream_t stream)
 {
     zero_job_counter(p, stream);
-    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the fourteen instantiations there are
+    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the sixteen instantiations there are
     case fast_key(SW_PLAIN, true): launch_fast_as<true, SW_PLAIN>(p, grid, stream); break;
     case fast_key(SW_PLAIN, false): launch_fast_as<false, SW_PLAIN>(p, grid, stream); break;
     case fast_key(SW_PLAIN, true, true): launch_fast_as<true, SW_PLAIN, true>(p, grid, stream); break;
@@ -4274,6 +4288,8 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     case fast_key(SW_VITERBI, false): launch_fast_as<false, SW_VITERBI>(p, grid, stream); break;
     case fast_key(SW_SAMPLING, true): launch_fast_as<true, SW_SAMPLING>(p, grid, stream); break;
     case fast_key(SW_SAMPLING, false): launch_fast_as<false, SW_SAMPLING>(p, grid, stream); break;
+    case fast_key(SW_POSTERIOR, true): launch_fast_as<true, SW_POSTERIOR>(p, grid, stream); break;
+    case fast_key(SW_POSTERIOR, false): launch_fast_as<false, SW_POSTERIOR>(p, grid, stream); break;
     default: return hipErrorInvalidValue;
     }
     launch_likelihood_logs(p, stream);
@@ -4665,6 +4681,200 @@ void launch_turn_rows(const TurnParams& q, hipStream_t stream)
     dim3 grid(q.n_jobs, (q.max_len + per_block - 1) / per_block);
     if (q.valu_form) hipLaunchKernelGGL(turn_rows_kernel<false>, grid, dim3(CNF2_BLOCK), 0, stream, q);
     else hipLaunchKernelGGL(turn_rows_kernel<true>, grid, dim3(CNF2_BLOCK), 0, stream, q);
+}
+
+// =====================================================================================
+// Marker placement (cnf2_sweep_place): place[i][q][m] = log sum_(s, g) gamma_(s, m)(g) e'_(s, q)(g), the growth of individual
+// i's log-likelihood when candidate marker q is laid on the map at mapped marker m.  gamma comes from a placement sweep
+// (SW_POSTERIOR: 512 doubles per job and marker in p.wbuf), e' from place_emission_kernel in the same (k, lane, register)
+// order, so the contraction index needs no permutation.
+// =====================================================================================
+// Emission tables of the candidates: one wave per (individual, candidate), through the producer / consumer code of
+// emission_kernel on the candidate rows (p.n_markers = Q).  null_sum[q] += log of the mean over the individual's analysed
+// shift modes of (1 / 64) sum_g e'(s, g), the unlinked baseline; an individual whose mean is 0 is left out.
+__global__ __launch_bounds__(64) void place_emission_kernel(KernelParams p, int q0, int qcap, double* emis, double* null_sum)
+{
+    __shared__ double tab[64];
+    const int    lane = threadIdx.x, ind = blockIdx.x, cand = q0 + blockIdx.y;
+    const Window w    = p.windows[ind];
+    LaneCtx      c;
+    make_lane(w, lane, &c.L);
+    c.row_root   = w.row[0];
+    c.root_attop = (w.flags[0] & SLOT_FOUNDER) != 0;
+    const int s  = lane >> 3;
+    c.s0 = s & 1;
+    c.s1 = (s >> 1) & 1;
+    c.s2 = (s >> 2) & 1;
+    c.lo = state_lo(lane);
+    c.active = true;
+    c.n_combo = 1;
+    const Slot root = load_slot(p, c.row_root, cand);
+    LineTerms  T;
+    tab[lane] = produce_entry(p, c, root, cand, &T);
+    wave_lds_fence();
+    double c0, c1, e[8];
+    root_weights(c, root, &c0, &c1);
+    emission_from_table(tab, c, c0, c1, e);
+    double* out = emis + ((size_t)ind * qcap + blockIdx.y) * 512;
+#pragma unroll
+    for (int k = 0; k < 4; k++) *(d2v*)(out + k * 128 + lane * 2) = d2v{e[2 * k], e[2 * k + 1]};
+    if (null_sum) {
+        const bool   on   = !(s & w.shiftignore) && s < w.shiftend;
+        const double mine = chain_sum(((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7])));
+        const double tot  = across_chains_sum(on ? mine : 0.0);
+        const int    n_on = __builtin_popcountll(__ballot(on)) >> 3;
+        if (lane == 0 && n_on > 0 && tot > 0.0) atomicAdd(&null_sum[cand], log(tot / (64.0 * n_on)));
+    }
+}
+void launch_place_emission(const KernelParams& cand, int n_ind, int q0, int qn, int qcap, double* emis, double* null_sum,
+                           hipStream_t stream)
+{
+    if (n_ind > 0 && qn > 0)
+        hipLaunchKernelGGL(place_emission_kernel, dim3(n_ind, qn), dim3(64), 0, stream, cand, q0, qcap, emis, null_sum);
+}
+
+// The contraction.  A wave owns a tile of 16 markers x 32 candidates of a chromosome (the four waves of a block: four
+// consecutive marker tiles and the same candidates, so that no wave idles when Q is small and the four read the same
+// candidate tables at the same time) and walks `group` consecutive jobs
+// (individuals; the batch lists its jobs by chromosome): per job a [32 x 512] x [512 x 16] product as 2 x 128
+// v_mfma_f64_16x16x4_f64 (A: row = lane & 15, k = lane >> 4; B: column = lane & 15, k = lane >> 4; D: column = lane & 15,
+// row = (lane >> 4) + 4 reg) with the candidates as rows and the markers as columns, so that the 16 lanes of a result
+// register hold 16 consecutive markers of one candidate: 128 contiguous bytes of place[] and of the sums.  Then a logarithm
+// per cell, the cell into place[] where asked for -- and the tile's sums and
+// zero counts stay in registers until the chromosome changes or the group ends: one f64 atomic per cell and group, not per
+// cell and job.  The operands go through LDS in chunks of 32 of the 512 (coalesced 16-byte loads, the next chunk requested
+// while this one is multiplied; rows 34 doubles apart: the 32 lanes a ds_read_b64 serves cover the 64 banks).  Markers past
+// the chromosome's end and candidates past Q are zeros in the operands and masked in the outputs: nothing is padded in HBM.
+constexpr int PLACE_KC = 32;                 // of the 512 per chunk
+constexpr int PLACE_RS = PLACE_KC + 2;       // doubles per LDS row
+constexpr int PLACE_NT = 2;                  // candidate tiles of 16 per wave
+__global__ __launch_bounds__(CNF2_BLOCK) void place_rows_kernel(PlaceParams q)
+{
+    __shared__ __attribute__((aligned(16))) double lds[CNF2_WAVES_PER_BLOCK][16 * (1 + PLACE_NT) * PLACE_RS];
+    const KernelParams& p = q.kp;
+    const int lane = threadIdx.x & 63;
+    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int qend = (q.q0 + q.qn < q.n_cand) ? q.q0 + q.qn : q.n_cand;
+    const int qa   = q.q0 + blockIdx.z * 16 * PLACE_NT;      // the block's candidates; its waves take four marker tiles
+    if (qa >= qend) return;
+    const int ml0 = (blockIdx.y * CNF2_WAVES_PER_BLOCK + wib) * 16;
+    const int j0  = blockIdx.x * q.group;
+    const int j1  = (j0 + q.group < q.n_jobs) ? j0 + q.group : q.n_jobs;
+    double*   LA  = lds[wib];
+    double*   LB  = LA + 16 * PLACE_RS;
+    const int lr = lane >> 4, lc = (lane & 15) * 2;      // loading role: row within a group of four, column pair
+    const int oi = lane & 15, ok = lane >> 4;            // operand role
+
+    d4v sum[PLACE_NT];
+    int nz[PLACE_NT][4];
+#pragma unroll
+    for (int nt = 0; nt < PLACE_NT; nt++) {
+        sum[nt] = d4v{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) nz[nt][reg] = 0;
+    }
+    int cur_chrom = -1, cur_first = 0, cur_len = 0;
+    auto flush = [&]() {
+        if (cur_chrom < 0) return;
+#pragma unroll
+        for (int nt = 0; nt < PLACE_NT; nt++)
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const int m = ml0 + oi, cand = qa + nt * 16 + ok + 4 * reg;
+                if (m < cur_len && cand < qend) {
+                    const size_t o = (size_t)cand * p.n_markers + cur_first + m;
+                    if (sum[nt][reg] != 0.0) atomicAdd(&q.place_sum[o], sum[nt][reg]);
+                    if (nz[nt][reg]) atomicAdd(&q.n_zero[o], nz[nt][reg]);
+                }
+                sum[nt][reg] = 0.0;
+                nz[nt][reg]  = 0;
+            }
+    };
+#pragma unroll 1
+    for (int job = j0; job < j1; job++) {
+        const Job jb  = p.jobs[job];
+        const int len = jb.last - jb.first + 1;
+        if (jb.chrom != cur_chrom) {
+            flush();
+            cur_chrom = jb.chrom;
+            cur_first = jb.first;
+            cur_len   = len;
+        }
+        if (ml0 >= len) continue;
+        // a job without a likelihood is skipped, as the sweep skips it: no sums, CNF2_IGNORED in its cells
+        if (p.lexp[(size_t)jb.ind * p.n_chrom + jb.chrom] == CNF2_LEXP_DEAD) {
+            if (q.place) {
+#pragma unroll
+                for (int nt = 0; nt < PLACE_NT; nt++)
+#pragma unroll
+                    for (int reg = 0; reg < 4; reg++) {
+                        const int m = ml0 + oi, cand = qa + nt * 16 + ok + 4 * reg;
+                        if (m < len && cand < qend) q.place[((size_t)jb.ind * q.n_cand + cand) * p.n_markers + jb.first + m] = CNF2_IGNORED_D;
+                    }
+            }
+            continue;
+        }
+        const double* A = p.wbuf + ((size_t)job * p.wstride + ml0) * 512;
+        const double* B = q.emis + ((size_t)jb.ind * q.qcap + (qa - q.q0)) * 512;
+        d2v ra[4], rb[4 * PLACE_NT];
+        auto request = [&](int c) {
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                const int row = 4 * i + lr;
+                ra[i] = d2v{0.0, 0.0};
+                if (ml0 + row < len) ra[i] = __builtin_nontemporal_load((const d2v*)(A + (size_t)row * 512 + c * PLACE_KC + lc));
+            }
+#pragma unroll
+            for (int i = 0; i < 4 * PLACE_NT; i++) {
+                const int row = 4 * i + lr;
+                rb[i] = d2v{0.0, 0.0};
+                if (qa + row < qend) rb[i] = *(const d2v*)(B + (size_t)row * 512 + c * PLACE_KC + lc);
+            }
+        };
+        d4v acc[PLACE_NT];
+#pragma unroll
+        for (int nt = 0; nt < PLACE_NT; nt++) acc[nt] = d4v{0.0, 0.0, 0.0, 0.0};
+        request(0);
+#pragma unroll 1
+        for (int c = 0; c < 512 / PLACE_KC; c++) {
+            wave_lds_fence();                   // the previous chunk's operand reads are done
+#pragma unroll
+            for (int i = 0; i < 4; i++) *(d2v*)(LA + (4 * i + lr) * PLACE_RS + lc) = ra[i];
+#pragma unroll
+            for (int i = 0; i < 4 * PLACE_NT; i++) *(d2v*)(LB + (4 * i + lr) * PLACE_RS + lc) = rb[i];
+            wave_lds_fence();
+            if (c + 1 < 512 / PLACE_KC) request(c + 1);
+#pragma unroll
+            for (int t = 0; t < PLACE_KC / 4; t++) {
+                const double a = LA[oi * PLACE_RS + 4 * t + ok];
+#pragma unroll
+                for (int nt = 0; nt < PLACE_NT; nt++)
+                    acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(LB[(nt * 16 + oi) * PLACE_RS + 4 * t + ok], a, acc[nt], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < PLACE_NT; nt++)
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const int m = ml0 + oi, cand = qa + nt * 16 + ok + 4 * reg;
+                if (m < len && cand < qend) {
+                    const double v = acc[nt][reg];
+                    double       r = (double)CNF2_MINFACTOR_F;       // the sum is exactly 0: impossible here
+                    if (v > 0.0) {
+                        r = v >= 2.2250738585072014e-308 ? log_pos(v) : log(v);
+                        sum[nt][reg] += r;
+                    } else nz[nt][reg]++;
+                    if (q.place) q.place[((size_t)jb.ind * q.n_cand + cand) * p.n_markers + jb.first + m] = r;
+                }
+            }
+    }
+    flush();
+}
+void launch_place_rows(const PlaceParams& q, hipStream_t stream)
+{
+    const int m_block = CNF2_WAVES_PER_BLOCK * 16, q_block = 16 * PLACE_NT;
+    const dim3 grid((q.n_jobs + q.group - 1) / q.group, (q.max_len + m_block - 1) / m_block, (q.qn + q_block - 1) / q_block);
+    if (q.n_jobs > 0 && q.qn > 0) hipLaunchKernelGGL(place_rows_kernel, grid, dim3(CNF2_BLOCK), 0, stream, q);
 }
 
 int fb_fast_blocks_per_cu()

@@ -2,7 +2,7 @@
 // (demo.sh:37):
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
 //            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
-//            [--remap F [--remap-iterations K]]
+//            [--place F --place-genfile G --place-markers Q] [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
 // haplotyping sweep (doit) before its dump.  Rows of the last round go to --output, earlier ones to stdout; every
@@ -34,6 +34,15 @@
 // drawn shift mode, logp "%.6lf" the log posterior probability of the drawn (mode, path); "-<TAB>-" where the individual is
 // skipped), one line per marker of the 6 state bits as for --viterbi, a blank line.  --output is the same with or without
 // it.  Single GPU only.
+//
+// --place F --place-genfile G --place-markers Q (not flags of the reference): after the last round, and before a --remap
+// changes the map, where Q markers that are not on the map go (cnf2_sweep_place).  G is a genotype file in the readers'
+// format with Q markers per individual, read against the same pedfile.  F holds one line per candidate,
+// "index<TAB>chrom<TAB>marker<TAB>pos<TAB>LOD<TAB>support_lo<TAB>support_hi<TAB>n_zero": the candidate (from 0), the
+// chromosome (from 1), map index (from 0) and position of the best marker among those at which the fewest individuals are
+// impossible, the LOD there against "unlinked", the positions that bound the contiguous stretch within 1 LOD of it on that
+// chromosome, and that fewest number; after a blank line the LOD at every marker of the map, one "%.5lf" tab-separated
+// line per candidate.  --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
 // has no compute path of its own and fails if no GPU is present.  Out of scope: the toulbar2
@@ -86,6 +95,8 @@ struct Options {
     int         draws = 1;               // --draws K
     unsigned long long seed = 0;         // --seed S
     bool        draws_set = false, seed_set = false;
+    std::string place, place_genfile;    // --place F --place-genfile G: where the Q markers of G go on the map
+    int         place_markers = 0;       // --place-markers Q
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
     int         remap_iterations = 1;
     bool        remap_iterations_set = false;
@@ -142,6 +153,9 @@ static bool parse(int argc, char** argv, Options& o)
             o.seed     = strtoull(val().c_str(), nullptr, 0);
             o.seed_set = true;
         }
+        else if (a == "--place") o.place = val();
+        else if (a == "--place-genfile") o.place_genfile = val();
+        else if (a == "--place-markers") o.place_markers = atoi(val().c_str());
         else if (a == "--remap") o.remap = val();
         else if (a == "--remap-iterations") {
             o.remap_iterations = atoi(val().c_str());
@@ -158,6 +172,7 @@ static bool parse(int argc, char** argv, Options& o)
 static void crossovers_and_remap(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void viterbi_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -245,6 +260,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (out != stdout) fclose(out);
     if (world == 1 && !opt.viterbi.empty()) viterbi_paths(opt, P, ctx);
     if (world == 1 && !opt.sample.empty()) sample_paths(opt, P, ctx);
+    if (world == 1 && !opt.place.empty()) place_markers(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -362,6 +378,61 @@ static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.sample);
 }
 
+// --place after the last round (single GPU), like --viterbi: the candidates' genotypes are read against the same pedfile
+// into a pedigree of their own, whose individuals are matched to the run's by name (the context's rows: record r in row
+// r + 1, row 0 blank; an individual the file does not mention has no data at the candidates)
+static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1, Q = opt.place_markers;
+    Pedigree G;
+    for (int q = 0; q < Q; q++) G.pos.push_back((double)q);
+    G.chromstarts = {0, Q};
+    FILE* f = fopen(opt.pedfile.c_str(), "rt");
+    if (!read_alpha_ped(f, G)) throw EngineError(CNF2_ERR_STATE, "cannot read " + opt.pedfile);
+    fclose(f);
+    f = fopen(opt.place_genfile.c_str(), "rt");
+    if (!read_alpha_gen(f, G)) throw EngineError(CNF2_ERR_STATE, "cannot read " + opt.place_genfile);
+    fclose(f);
+    const size_t R = P.inds.size(), per = (size_t)Q * 2;
+    std::vector<uint8_t> ca((R + 1) * per, 0);
+    std::vector<double>  cs((R + 1) * per, 0.0);
+    for (size_t r = 0; r < R; r++) {
+        const auto it = G.index.find(P.inds[r].name);
+        if (it == G.index.end() || it->second < 0) continue;
+        const Individual& I = G.inds[it->second];
+        std::copy(I.allele.begin(), I.allele.end(), ca.begin() + (r + 1) * per);
+        std::copy(I.sure.begin(), I.sure.end(), cs.begin() + (r + 1) * per);
+    }
+    std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), ps((size_t)Q * M), null(Q);
+    std::vector<int32_t> nz((size_t)Q * M), cnt(C);
+    if (cnf2_sweep_place(ctx, 0, N, Q, ca.data(), cs.data(), nullptr, fa.data(), ll.data(), nullptr, ps.data(), nz.data(),
+                         null.data(), cnt.data(), 0) != CNF2_OK)
+        throw EngineError(CNF2_ERR_STATE, std::string("cnf2_sweep_place: ") + cnf2_last_error(ctx));
+    FILE* out = fopen(opt.place.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.place);
+    const double ln10 = 2.30258509299404568402, drop = 1.0;
+    std::vector<double> lod((size_t)Q * M);
+    for (int q = 0; q < Q; q++) {
+        double*        L = &lod[(size_t)q * M];
+        const int32_t* Z = &nz[(size_t)q * M];
+        for (int m = 0; m < M; m++) L[m] = (ps[(size_t)q * M + m] - null[q]) / ln10;
+        const int32_t fewest = *std::min_element(Z, Z + M);
+        int best = -1, c = 0;
+        for (int m = 0; m < M; m++)
+            if (Z[m] == fewest && (best < 0 || L[m] > L[best])) best = m;
+        while (P.chromstarts[c + 1] <= best) c++;
+        auto inside = [&](int m) { return Z[m] == fewest && L[m] >= L[best] - drop; };
+        int lo = best, hi = best;
+        while (lo - 1 >= P.chromstarts[c] && inside(lo - 1)) lo--;
+        while (hi + 1 < P.chromstarts[c + 1] && inside(hi + 1)) hi++;
+        fprintf(out, "%d\t%d\t%d\t%.5lf\t%.5lf\t%.5lf\t%.5lf\t%d\n", q, c + 1, best, P.pos[best], L[best], P.pos[lo], P.pos[hi], (int)fewest);
+    }
+    fprintf(out, "\n");
+    for (int q = 0; q < Q; q++)
+        for (int m = 0; m < M; m++) fprintf(out, "%.5lf%c", lod[(size_t)q * M + m], m + 1 < M ? '\t' : '\n');
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.place);
+}
+
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
 // reduce-scatter, all-gather, the hit-counter sum, a barrier and the host broadcast on the context's exchange buffer, through
 // the same entry the engine calls.  (Two ranks need two GPUs: RCCL refuses two ranks on one device.)
@@ -468,6 +539,18 @@ int main(int argc, char** argv)
     }
     if (opt.gpus > 1 && !opt.sample.empty()) {
         fprintf(stderr, "--sample needs a single GPU (--gpus 1): the ranks' draws are not gathered\n");
+        return 2;
+    }
+    if (opt.gpus > 1 && !opt.place.empty()) {
+        fprintf(stderr, "--place needs a single GPU (--gpus 1): the ranks' sums are not reduced\n");
+        return 2;
+    }
+    if (opt.place.empty() != opt.place_genfile.empty() || opt.place.empty() != (opt.place_markers == 0)) {
+        fprintf(stderr, "--place FILE, --place-genfile FILE and --place-markers Q go together\n");
+        return 2;
+    }
+    if (opt.place_markers < 0) {
+        fprintf(stderr, "--place-markers must be at least 1\n");
         return 2;
     }
     if ((opt.draws_set || opt.seed_set) && opt.sample.empty()) {

@@ -317,6 +317,43 @@ int cnf2_sweep_viterbi(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factor
 int cnf2_sweep_sample(cnf2_ctx *ctx, int ind_begin, int ind_end, int n_draws, uint64_t seed, double *factors_out,
                       double *loglik_out, uint8_t *state_out, int32_t *shift_out, double *logp_out, uint32_t flags);
 
+/* Marker placement: where on the map does an unmapped marker go?  For n_cand candidate markers, given by rows of their own
+ * in the row index space of cnf2_upload_rows, and every mapped marker m,
+ *   place[i][q][m] = log( sum_s w_s sum_g gamma_s,m(g) e'_s,q(g) )
+ * is the growth of individual i's window log-likelihood when candidate q is laid on the map at the position of m (zero
+ * distance: the identity transition).  gamma_s,m(g) is the posterior of state g at marker m in shift mode s (alpha after
+ * the emission x beta, normalised within the mode), w_s = exp(factors[s] - loglik) over the modes the dosage rows count
+ * (active, with a likelihood, not 40 log-units below the total), e'_s,q(g) the candidate's path-free emission for the
+ * window, what cnf2_emission returns for a mapped marker.  Ties, CNF2_NO_TIES and ignoreflag2 do not enter.
+ *   n_cand        Q >= 1 (else CNF2_ERR_ARG, nothing written)
+ *   cand_allele   [n_rows][Q][2] (uint8), cand_sure [n_rows][Q][2], cand_hw [n_rows][Q] or NULL (= 0.5 everywhere):
+ *                 host pointers, also with CNF2_OUT_DEVICE; a NULL allele / sure pointer is CNF2_ERR_ARG
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal (the placement sweep's forward pass is cnf2_sweep's; a range that
+ *                 holds tied windows takes them from cnf2_sweep's own launches without rows)
+ *   place_out     [n][Q][n_markers] or NULL (the normal case of a large run).  CNF2_MINFACTOR where the sum is exactly 0
+ *                 (the candidate's data is impossible at that position for that individual), CNF2_IGNORED where the
+ *                 individual is skipped on that chromosome.  A host buffer is staged whole on the device (CNF2_ERR_NOMEM if
+ *                 that fails: split the individual range)
+ *   place_sum_out [Q][n_markers] the sum of place over the individuals of the range that are neither skipped nor impossible
+ *                 there (reduced on the device, f64 atomics: equal to the host sum to rounding, not to the bit)
+ *   n_zero_out    [Q][n_markers] (int32) the impossible individuals
+ *   null_out      [Q] the unlinked baseline: the sum over the range's individuals of log( mean over the individual's
+ *                 active shift modes of (1/64) sum_g e'_s,q(g) ); an individual whose mean is 0 is left out
+ *   n_contrib_out [n_chrom] (int32) individuals of the range with a likelihood on that chromosome (not skipped)
+ * (place_sum - null) / ln 10 is the LOD of the position against "unlinked"; cnf2freq_amd/placement.py reads the profile.
+ * Outputs are overwritten, not accumulated; a range split [a,b) + [b,c) adds up to [a,c) (sums to rounding, counts exactly).
+ * The result does not depend on cnf2_set_batch_jobs.  Launches: per batch
+ * the fast kernel's placement instantiation for every window (the state posteriors, 4 KB per individual x marker) and, per
+ * tile of up to 256 candidates, the contraction on the matrix cores; the sweep runs once per batch, not once per tile.
+ * Flags: CNF2_OUT_DEVICE (the seven output pointers are device pointers; the sums and counts must be ordinary device
+ * memory as for CNF2_ACC_DEVICE), CNF2_STATIC_JOBS, CNF2_FULL_SPILL and CNF2_TIES_GENERAL as in cnf2_sweep_crossovers;
+ * CNF2_MERGE_MODES, CNF2_XPOSE, CNF2_FLUSH_TINY and the dosage flags are ignored.  The call synchronises the context's
+ * stream, also with CNF2_OUT_DEVICE (its outputs are then complete when the stream is). */
+int cnf2_sweep_place(cnf2_ctx *ctx, int ind_begin, int ind_end, int n_cand, const uint8_t *cand_allele,
+                     const double *cand_sure, const double *cand_hw, double *factors_out, double *loglik_out,
+                     double *place_out, double *place_sum_out, int32_t *n_zero_out, double *null_out,
+                     int32_t *n_contrib_out, uint32_t flags);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every
