@@ -25,6 +25,7 @@ UPDATE_LITERAL_FINISH = 1 << 19   # the set-aside flows one literal bisection st
 DETERMINISTIC = 16384
 TURN_VALU = 32768
 FLUSH_TINY = 1 << 20              # cnf2_sweep: general kernel with adjustprobs' 1e-300 rule (the reference's behaviour to the letter)
+ALL_STATES = 1 << 21              # windows of crosses of inbred lines through the fast kernel's ordinary instantiation (A/B, cross-check)
 STATIC_JOBS = 1 << 18             # wave w sweeps jobs w, w + waves, ... instead of taking jobs from the launch's counter (A/B)
 MINFACTOR = float(np.float32(-1e15))
 IGNORED = -1e30
@@ -259,7 +260,7 @@ class Context:
 
     # -- the sweep -------------------------------------------------------------
     def sweep(self, ind_begin=0, ind_end=None, dosage=True, raw=False, ties=True, full_spill=False,
-              merge_modes=False, xpose=False, log_paths=False, ties_general=False, static_jobs=False, flush_tiny=False):
+              merge_modes=False, xpose=False, log_paths=False, ties_general=False, static_jobs=False, flush_tiny=False, all_states=False):
         ind_end = self.n_ind if ind_end is None else ind_end
         n = ind_end - ind_begin
         factors = np.zeros((n, self.n_chrom, 8))
@@ -267,7 +268,7 @@ class Context:
         dos = np.zeros((n, self.n_markers, 3)) if dosage else None
         flags = ((0 if dosage else NO_DOSAGE) | (RAW_DOSAGE if raw else 0) | (0 if ties else NO_TIES)
                  | (FULL_SPILL if full_spill else 0) | (MERGE_MODES if merge_modes else 0) | (XPOSE if xpose else 0)
-                 | (LOG_PATHS if log_paths else 0) | (TIES_GENERAL if ties_general else 0) | (STATIC_JOBS if static_jobs else 0)
+                 | (LOG_PATHS if log_paths else 0) | (TIES_GENERAL if ties_general else 0) | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0)
                  | (FLUSH_TINY if flush_tiny else 0))
         self._chk(self.L.cnf2_sweep(self.h, ind_begin, ind_end, _p(factors), _p(loglik),
                                     _p(dos) if dosage else None, flags), "cnf2_sweep")
@@ -340,7 +341,7 @@ class Context:
         return v
 
     def sweep_crossovers(self, ind_begin=0, ind_end=None, rows=True, full_spill=False, ties_general=False,
-                         static_jobs=False):
+                         static_jobs=False, all_states=False):
         """cnf2_sweep_crossovers: factors / loglik as sweep(), the per-individual crossover posteriors xo[n][M][6] (None
         with rows=False), their sum over the range xo_sum[M][6] and the contributing individuals per chromosome."""
         ind_end = self.n_ind if ind_end is None else ind_end
@@ -351,13 +352,13 @@ class Context:
         xs = np.zeros((self.n_markers, 6))
         cnt = np.zeros(self.n_chrom, np.int32)
         flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
-                 | (STATIC_JOBS if static_jobs else 0))
+                 | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0))
         self._chk(self.L.cnf2_sweep_crossovers(self.h, ind_begin, ind_end, _p(factors), _p(loglik),
                                                _p(xo) if rows else None, _p(xs), _p(cnt), flags),
                   "cnf2_sweep_crossovers")
         return dict(factors=factors, loglik=loglik, xo=xo, xo_sum=xs, n_contrib=cnt)
 
-    def sweep_viterbi(self, ind_begin=0, ind_end=None, full_spill=False, ties_general=False, static_jobs=False):
+    def sweep_viterbi(self, ind_begin=0, ind_end=None, full_spill=False, ties_general=False, static_jobs=False, all_states=False):
         """cnf2_sweep_viterbi: factors / loglik as sweep(), logmax[n][C][8], the MAP state path state[n][M] (uint8, 0xFF
         where skipped), the MAP shift mode shift[n][C] (-1 where skipped) and path_logpost[n][C] = logmax[s*] - loglik,
         the log posterior probability of the decoded (mode, path) (NaN where skipped)."""
@@ -369,7 +370,7 @@ class Context:
         state = np.zeros((n, self.n_markers), np.uint8)
         shift = np.zeros((n, self.n_chrom), np.int32)
         flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
-                 | (STATIC_JOBS if static_jobs else 0))
+                 | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0))
         self._chk(self.L.cnf2_sweep_viterbi(self.h, ind_begin, ind_end, _p(factors), _p(loglik), _p(logmax),
                                             _p(state), _p(shift), flags), "cnf2_sweep_viterbi")
         best = np.take_along_axis(logmax, np.maximum(shift, 0)[..., None], axis=2)[..., 0]
@@ -377,7 +378,7 @@ class Context:
         return dict(factors=factors, loglik=loglik, logmax=logmax, state=state, shift=shift, path_logpost=path_logpost)
 
     def sweep_sample(self, ind_begin=0, ind_end=None, draws=1, seed=0, full_spill=False, ties_general=False,
-                     static_jobs=False):
+                     static_jobs=False, all_states=False):
         """cnf2_sweep_sample: factors / loglik as sweep(), and `draws` (mode, path) draws from the posterior per individual
         and chromosome: state[n][K][M] (uint8, 0xFF where skipped), shift[n][K][C] (the drawn mode, -1 where skipped) and
         logp[n][K][C] = log P(mode, path | data) (NaN where skipped).  Draw k depends on (seed, individual, k) only."""
@@ -389,7 +390,7 @@ class Context:
         shift = np.zeros((n, draws, self.n_chrom), np.int32)
         logp = np.zeros((n, draws, self.n_chrom))
         flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
-                 | (STATIC_JOBS if static_jobs else 0))
+                 | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0))
         self._chk(self.L.cnf2_sweep_sample(self.h, ind_begin, ind_end, draws, int(seed) & 0xFFFFFFFFFFFFFFFF,
                                            _p(factors), _p(loglik), _p(state), _p(shift), _p(logp), flags),
                   "cnf2_sweep_sample")
@@ -404,7 +405,7 @@ class Context:
         return a, s, h
 
     def sweep_place(self, cand_allele, cand_sure, cand_hw=None, ind_begin=0, ind_end=None, per_individual=False,
-                    full_spill=False, ties_general=False, static_jobs=False):
+                    full_spill=False, ties_general=False, static_jobs=False, all_states=False):
         """cnf2_sweep_place: where Q unmapped markers go.  cand_allele / cand_sure [n_rows][Q][2] and cand_hw [n_rows][Q]
         (None = 0.5) are the candidates' rows in the row index space of upload_rows.  Returns factors / loglik as sweep(),
         place_sum[Q][M] (the growth of the range's log-likelihood with candidate q laid at marker m, over the individuals
@@ -423,7 +424,7 @@ class Context:
         null = np.zeros(Q)
         cnt = np.zeros(self.n_chrom, np.int32)
         flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
-                 | (STATIC_JOBS if static_jobs else 0))
+                 | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0))
         self._chk(self.L.cnf2_sweep_place(self.h, ind_begin, ind_end, Q, _p(a), _p(s), None if h is None else _p(h),
                                           _p(factors), _p(loglik), _p(place) if per_individual else None, _p(psum),
                                           _p(nz), _p(null), _p(cnt), flags), "cnf2_sweep_place")
@@ -482,7 +483,7 @@ class Context:
         return dict(infprobs=inf, haplobase=hb, haplocount=hc, homozyg=hz)
 
     def sweep_accumulate(self, desc, ind_begin=0, ind_end=None, ties=True, raw=False, table_form=False, lane_form=False,
-                         ties_general=False, deterministic=False, static_jobs=False, rows=True):
+                         ties_general=False, deterministic=False, static_jobs=False, rows=True, all_states=False):
         """One haplotyping sweep: the outputs of sweep() and the per-record accumulators, batched on the device.
         rows=False: no dosage pointer is passed (what an iteration that prints no rows does): "dosage" comes back as zeros."""
         ind_end = self.n_ind if ind_end is None else ind_end
@@ -500,7 +501,7 @@ class Context:
                                                (0 if ties else NO_TIES) | (RAW_DOSAGE if raw else 0)
                                                | (ACC_TABLE if table_form else 0) | (ACC_LANES if lane_form else 0)
                                                | (TIES_GENERAL if ties_general else 0)
-                                               | (DETERMINISTIC if deterministic else 0) | (STATIC_JOBS if static_jobs else 0)),
+                                               | (DETERMINISTIC if deterministic else 0) | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0)),
                   "cnf2_sweep_accumulate")
         return dict(factors=factors, loglik=loglik, dosage=dos, infprobs=inf, haplobase=hb, haplocount=hc, homozyg=hz)
 
@@ -514,7 +515,7 @@ class Context:
                                                flags | OUT_DEVICE | ACC_DEVICE), "cnf2_sweep_accumulate")
 
     def sweep_turn_scan(self, ind_begin=0, ind_end=None, full=True, lse=True, ties=True, ties_general=False, valu=False,
-                        static_jobs=False):
+                        static_jobs=False, all_states=False):
         """Batched turn scan: rawervals [n][M][128][8] and / or their log-sum-exp over the admissible modes [n][M][128]."""
         ind_end = self.n_ind if ind_end is None else ind_end
         n = ind_end - ind_begin
@@ -522,7 +523,7 @@ class Context:
         ls = np.zeros((n, self.n_markers, 128)) if lse else None
         self._chk(self.L.cnf2_sweep_turn_scan(self.h, ind_begin, ind_end, _p(raw) if full else None, _p(ls) if lse else None,
                                               (0 if ties else NO_TIES) | (TIES_GENERAL if ties_general else 0)
-                                              | (TURN_VALU if valu else 0) | (STATIC_JOBS if static_jobs else 0)),
+                                              | (TURN_VALU if valu else 0) | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0)),
                   "cnf2_sweep_turn_scan")
         return raw, ls
 

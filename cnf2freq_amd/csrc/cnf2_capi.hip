@@ -96,6 +96,7 @@ struct cnf2_ctx {
     bool                windows_dirty = true;   // rows or pedigree changed since the last derivation
     DevBuf<uint8_t>     d_rowflags;
     int                 fast_blocks_per_cu = 1;
+    int                 uni_blocks_per_cu = 1;   // the fast kernel's instantiation for uniform windows
     int                 reserve_blocks = 0;     // workgroup slots left free for concurrent kernels (RCCL)
     int                 batch_jobs = 0;         // cap on the jobs per batch of the batched consumers (0 = what memory allows)
 
@@ -301,6 +302,7 @@ int cnf2_ctx_create(int device, cnf2_ctx** out)
     ctx->n_cu          = prop.multiProcessorCount;
     ctx->blocks_per_cu = fb_blocks_per_cu();
     ctx->fast_blocks_per_cu = fb_fast_blocks_per_cu();
+    ctx->uni_blocks_per_cu  = fb_fast_uniform_blocks_per_cu();
     ctx->xo_blocks_per_cu = fb_xo_blocks_per_cu();
     *out = ctx;
     return CNF2_OK;
@@ -686,7 +688,15 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     int          grid_fast = 0, grid_gen = 0;
     size_t       free_b = 0, total_b = 0;
     HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-    if (!plan_sweep_grids(ctx->n_cu, ctx->fast_blocks_per_cu, ctx->blocks_per_cu, ctx->reserve_blocks, std::max(n_fast, n_packed),
+    // the plain half-spill sweep: the fast jobs of uniform windows (slots_uniform: crosses of inbred lines) take the fast
+    // kernel's instantiation for them (launch_fb_fast), which has an occupancy of its own; the spill slots cover the larger grid
+    size_t n_uniform = 0;
+    if (!(flags & (CNF2_ALL_STATES | CNF2_FULL_SPILL | CNF2_XPOSE)) && (plain || mode.variant == SW_VITERBI))
+        for (size_t j = 0; j < n_fast; j++) n_uniform += slots_uniform(ctx->windows[ind_begin + jp.jobs[j].ind].flags) ? 1 : 0;
+    const int fast_per_cu = n_uniform == 0       ? ctx->fast_blocks_per_cu
+                            : n_uniform < n_fast ? std::max(ctx->fast_blocks_per_cu, ctx->uni_blocks_per_cu)
+                                                 : ctx->uni_blocks_per_cu;
+    if (!plan_sweep_grids(ctx->n_cu, fast_per_cu, ctx->blocks_per_cu, ctx->reserve_blocks, std::max(n_fast, n_packed),
                           n_general, free_b, ctx->d_spill.cap * sizeof(double), mlen, &grid_fast, &grid_gen))
         return fail(ctx, CNF2_ERR_NOMEM, "a chromosome of %d markers needs %zu MB of spill per block, %zu MB free", mlen,
                     spill_block_bytes(mlen) >> 20, free_b >> 20);
@@ -800,11 +810,17 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         p.n_pjobs = (int)n_packed;
         KernelParams pp = p;
         if (pp.job_next) pp.job_next = ctx->d_jobnext + 2;    // (the fast kernel behind it on the stream zeroes its own)
-        launch_fb_packed(pp, grid_for(n_packed, grid_fast), ctx->stream);
+        launch_fb_packed(pp, std::min(grid_for(n_packed, grid_fast), resident_blocks(ctx->n_cu, ctx->fast_blocks_per_cu, ctx->reserve_blocks)),
+                         ctx->stream);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (n_fast > 0) {
-        const int gf = grid_for(n_fast, grid_fast);
+        // (grid_fast covers the occupancy of whichever instantiations run; each takes what is resident of its own)
+        const int gf = std::min(grid_for(n_fast, grid_fast), resident_blocks(ctx->n_cu, ctx->fast_blocks_per_cu, ctx->reserve_blocks));
+        FastVariant plain_half{SW_PLAIN, half, half && (flags & CNF2_XPOSE)};
+        plain_half.n_uniform        = (int)n_uniform;
+        plain_half.grid_uniform     = std::min(grid_for(n_uniform, grid_fast), resident_blocks(ctx->n_cu, ctx->uni_blocks_per_cu, ctx->reserve_blocks));
+        plain_half.job_next_uniform = ctx->d_jobnext + 3;
         p.clock_out = ctx->d_clock;
         if (mode.variant == SW_VITERBI) {
             // the likelihoods from cnf2_sweep's own launch without rows (the Viterbi instantiation runs the same recursion,
@@ -812,12 +828,13 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
             // the Viterbi instantiation in the same spill slots with its likelihoods to scratch
             KernelParams pl = p;
             pl.flags = KP_NO_DOSAGE;
-            HIP_TRY(ctx, launch_fb_fast(pl, gf, {SW_PLAIN, half}, ctx->stream));
+            HIP_TRY(ctx, launch_fb_fast(pl, gf, plain_half, ctx->stream));
             KernelParams pv = p;
             pv.clock_out = nullptr;
             likelihoods_to_scratch(&pv);
             HIP_TRY(ctx, launch_fb_fast(pv, gf, {SW_VITERBI, half}, ctx->stream));
-        } else HIP_TRY(ctx, launch_fb_fast(p, gf, {mode.variant, half, half && (flags & CNF2_XPOSE)}, ctx->stream));
+        } else if (plain) HIP_TRY(ctx, launch_fb_fast(p, gf, plain_half, ctx->stream));
+        else HIP_TRY(ctx, launch_fb_fast(p, gf, {mode.variant, half, half && (flags & CNF2_XPOSE)}, ctx->stream));
         p.clock_out = nullptr;
     }
     if (n_general > 0) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev2, 0));
@@ -1022,7 +1039,7 @@ static int mode_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         HIP_TRY(ctx, hipMemsetAsync(mode.xo_sum, 0, (size_t)ctx->n_markers * 6 * sizeof(double), ctx->stream));
         HIP_TRY(ctx, hipMemsetAsync(mode.xo_cnt, 0, (size_t)ctx->n_chrom * sizeof(int32_t), ctx->stream));
     }
-    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL | CNF2_ALL_STATES);
     return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, mode);
 }
 
@@ -1534,7 +1551,7 @@ int cnf2_sweep_place(cnf2_ctx* ctx, int ind_begin, int ind_end, int n_cand, cons
         const bool own = !tied_any && ((flags & PLACE_OWN_LIKELIHOODS) || (PLACE_OWN_DEFAULT && !(flags & PLACE_SWEEP_LIKELIHOODS)));
         const size_t nf = (size_t)n * C * 8, nl = (size_t)n * C;
         if (!own) {
-            const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+            const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL | CNF2_ALL_STATES);
             RC_TRY(sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass | CNF2_NO_DOSAGE, SweepMode()));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));     // (the job list and the spill are replaced below)
         } else if (!dev) {

@@ -18,7 +18,8 @@ enum { KP_NO_DOSAGE = 1, KP_RAW_DOSAGE = 2, KP_NO_TIES = 4,
        KP_ACC_TABLE = 8,      // accumulate: the table-form kernel does every window
        KP_ACC_ATTOP = 16,     // accumulate: the batch holds windows whose root is the top of its lines (table form)
        KP_ACC_LANES = 32,     // accumulate: path form with one lane per path (acc_paths_kernel) instead of the tile form
-       KP_FLUSH_TINY = 64 };  // general sweep kernel: a state under 1e-300 of its vector is set to 0 before the emission (cnF2freq.cpp:1607-1611)
+       KP_FLUSH_TINY = 64,    // general sweep kernel: a state under 1e-300 of its vector is set to 0 before the emission (cnF2freq.cpp:1607-1611)
+       KP_SKIP_UNIFORM = 128 }; // fast kernel, plain half-spill sweep: the jobs of uniform windows (slots_uniform) belong to the UNI instantiation's launch
 
 // What a sweep kernel leaves behind besides the likelihoods: the STOREW template argument of fb_kernel / fb_fast_kernel
 // (an int there, so that the kernels' names stay what the tools and logs in profiles/ match on)
@@ -230,9 +231,14 @@ void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t strea
 // CNF2_FULL_SPILL); xpose: the transposing variant of the plain sweep; tied: the tile producer with a pass per tie
 // combination (windows with tie groups).  SW_WEIGHTS forms no per-locus rows: windows with tie groups can take it untied
 // (the posterior weights do not see the tie rule).
+// n_uniform ({SW_PLAIN, half} only): how many of the launch's jobs belong to windows with slots_uniform (cnf2_emission.h);
+// they are swept by the UNI instantiation (grid_uniform blocks, job counter job_next_uniform), the rest -- if any -- by the
+// ordinary one behind it on the stream.  0 (CNF2_ALL_STATES): every job through the ordinary instantiation.
 struct FastVariant {
     SweepVariant storew;
     bool         half = true, xpose = false, tied = false;
+    int          n_uniform = 0, grid_uniform = 0;
+    int*         job_next_uniform = nullptr;
 };
 // Zeroes the launch's job counter, launches the instantiation (asking once for the tied instantiations' dynamic LDS) and
 // the kernel that takes the logarithms of its likelihoods.  Returns the launches' error; a combination that is not
@@ -242,6 +248,7 @@ void launch_fb_packed(const KernelParams& p, int grid, hipStream_t stream);
 void launch_row_flags(const uint8_t* allele8, const double2* sure, int n_rows, int n_markers, uint8_t* flags,
                       hipStream_t stream);
 int  fb_fast_blocks_per_cu();
+int  fb_fast_uniform_blocks_per_cu();
 void launch_emission(const KernelParams& p, int ind, int marker, double* out, hipStream_t stream);
 void launch_emission_paths(const KernelParams& p, int marker, double* out, hipStream_t stream);
 void launch_xor_selftest(double* out, hipStream_t stream);

@@ -57,6 +57,17 @@ struct LineCfg {
 // (derived from the data, not from the pedigree): its two allele indices are then interchangeable
 enum { SLOT_PRESENT = 1, SLOT_FOUNDER = 2, SLOT_RESTRICT0 = 4, SLOT_HOM = 8 };
 
+// Classes of a window that its seven slot flags (Window::flags, cnf2_window.h) guarantee, for the kernels and for the host
+// that routes the jobs.  homleaf: the four grandparents are present and SLOT_HOM.  uniform: both parents are SLOT_HOM as
+// well -- any cross of inbred lines with empty or homozygous F1 parents.  The unrestricted emission table of such a window
+// does not depend on the four grandparental state bits (1, 2, 4, 5), so neither do alpha and beta.
+CNF2_HD bool slots_homleaf(const uint8_t* f)
+{
+    const int gp = f[2] & f[3] & f[5] & f[6];
+    return (gp & SLOT_HOM) && (gp & SLOT_PRESENT);
+}
+CNF2_HD bool slots_uniform(const uint8_t* f) { return (f[1] & f[4] & SLOT_HOM) && slots_homleaf(f); }
+
 // Terms of one table entry.  For parent allele fp and grandparent allele fg:
 //   value = sum_fp base[fp] * (sum_fg ot[fp][fg]) * (sum_fg tr[fp][fg])
 // trtwo[fp][fg] = tr[fp][fg] where the allele at the top of the traced line is 2, else 0.

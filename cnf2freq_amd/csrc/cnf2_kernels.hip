@@ -146,25 +146,28 @@ __device__ __forceinline__ void transition(double (&a)[8], double r0, double r1)
 #endif
 #pragma unroll
     for (int j = 0; j < 8; j++) a[j] = k0 * a[j] + r0 * q[j];
-    // bits 3..5: registers
+    // bits 3..5: registers.  The multiply-add is written out, the same form for both elements of a pair: left to the
+    // compiler, the two were fused differently (fma(k, x, r y) for one, fma(r, x, k y) for the other), so that two states
+    // holding the same bits -- the grandparental bits of a cross of inbred lines -- came out an ulp apart in the
+    // reference-layout store (tests/test_gpu_uniform_states.py: the premise)
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
         double x = a[j], y = a[j + 1];
-        a[j]     = k1 * x + r1 * y;
-        a[j + 1] = k1 * y + r1 * x;
+        a[j]     = fma(r1, y, k1 * x);
+        a[j + 1] = fma(r1, x, k1 * y);
     }
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         if (j & 2) continue;
         double x = a[j], y = a[j + 2];
-        a[j]     = k0 * x + r0 * y;
-        a[j + 2] = k0 * y + r0 * x;
+        a[j]     = fma(r0, y, k0 * x);
+        a[j + 2] = fma(r0, x, k0 * y);
     }
 #pragma unroll
     for (int j = 0; j < 4; j++) {
         double x = a[j], y = a[j + 4];
-        a[j]     = k0 * x + r0 * y;
-        a[j + 4] = k0 * y + r0 * x;
+        a[j]     = fma(r0, y, k0 * x);
+        a[j + 4] = fma(r0, x, k0 * y);
     }
 }
 
@@ -209,6 +212,52 @@ __device__ __forceinline__ void transition_scaled(double (&a)[8], double t0, dou
         const double x = a[j], y = a[j + 4];
         a[j]     = fma(t0, y, x);
         a[j + 4] = fma(t0, x, y);
+    }
+}
+
+// transition_scaled for a vector that does not depend on the four grandparental state bits (the t0 stages: lane stages b1
+// and b2, register-index bits 1 and 2 -- a window with slots_uniform, cnf2_emission.h): the partner such a stage would fetch
+// is the lane's own value, so the stage is a[j] = fma(t0, a[j], a[j]) -- the same FMA on the same operands, the same bits,
+// and no exchange.  N = 8: all eight registers are carried (they hold two distinct numbers); N = 2: only register bit 0,
+// and the two register stages on the uniform bits become the same self-FMA.
+template <int N>
+__device__ __forceinline__ void transition_uniform(double (&a)[N], double t0, double t1)
+{
+    static_assert(N == 8 || N == 2, "all eight registers of a lane, or the two that differ");
+    double q[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) q[j] = lane_xor1(a[j]);
+#pragma unroll
+    for (int j = 0; j < N; j++) a[j] = fma(t1, q[j], a[j]);
+#pragma unroll
+    for (int j = 0; j < N; j++) a[j] = fma(t0, a[j], a[j]);
+#pragma unroll
+    for (int j = 0; j < N; j++) a[j] = fma(t0, a[j], a[j]);
+#pragma unroll
+    for (int j = 0; j < N; j += 2) {
+        const double x = a[j], y = a[j + 1];
+        a[j]     = fma(t1, y, x);
+        a[j + 1] = fma(t1, x, y);
+    }
+    if constexpr (N == 8) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            if (j & 2) continue;
+            const double x = a[j], y = a[j + 2];
+            a[j]     = fma(t0, y, x);
+            a[j + 2] = fma(t0, x, y);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const double x = a[j], y = a[j + 4];
+            a[j]     = fma(t0, y, x);
+            a[j + 4] = fma(t0, x, y);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; j++) a[j] = fma(t0, a[j], a[j]);
+#pragma unroll
+        for (int j = 0; j < N; j++) a[j] = fma(t0, a[j], a[j]);
     }
 }
 
@@ -359,10 +408,36 @@ __device__ __forceinline__ double fast_rcp(double x)
     return r;
 }
 
-__device__ __forceinline__ double scale_chain(double (&v)[8], double* mant, int* expo, bool* dead, double* inv_out = nullptr)
+// Sum of a chain's 64 states: over the lane's registers, then over the chain's 8 lanes.  UNI: the vector does not depend on
+// the four grandparental state bits (transition_uniform).  With N = 2 the tree's four pair sums are one number s and the
+// tree is (s + s) + (s + s); the two lane steps over uniform bits add a value to itself.  Doubling is exact: the same bits
+// as the full tree and the three exchanges.
+template <bool UNI, int N>
+__device__ __forceinline__ double chain_total(const double (&v)[N])
 {
-    double sum = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    sum        = chain_sum(sum);
+    if constexpr (N == 8) {
+        double sum = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
+        if (!UNI) return chain_sum(sum);
+        sum += lane_xor1(sum);
+        sum += sum;
+        sum += sum;
+        return sum;
+    } else {
+        static_assert(UNI && N == 2, "two registers per lane: uniform windows only");
+        double sum = v[0] + v[1];
+        sum += sum;
+        sum += sum;
+        sum += lane_xor1(sum);
+        sum += sum;
+        sum += sum;
+        return sum;
+    }
+}
+
+template <bool UNI = false, int N>
+__device__ __forceinline__ double scale_chain(double (&v)[N], double* mant, int* expo, bool* dead, double* inv_out = nullptr)
+{
+    const double sum = chain_total<UNI>(v);
     // sum <= 0: probs stay as they are (they are all zero), factor = MINFACTOR (cnF2freq.cpp:1656-1660);
     // written branch-free: a dead step scales by 1 and leaves the running scale alone
     const bool   ok  = sum > 0.0;
@@ -371,7 +446,7 @@ __device__ __forceinline__ double scale_chain(double (&v)[8], double* mant, int*
     if (!ok) *dead = true;
     if (inv_out) *inv_out = inv;
 #pragma unroll
-    for (int j = 0; j < 8; j++) v[j] *= inv;
+    for (int j = 0; j < N; j++) v[j] *= inv;
     int    ex;
     double mm = frexp(*mant * ss, &ex);
     *mant     = mm;
@@ -382,10 +457,10 @@ __device__ __forceinline__ double scale_chain(double (&v)[8], double* mant, int*
 // Same bookkeeping, but the vector is left as it is: returns the reciprocal for the caller to fold into
 // the next emission product (it is a per-chain scalar and every step is linear), which takes the
 // reduction -> reciprocal chain off the critical path and saves six of the eight multiplies.
-__device__ __forceinline__ double chain_normaliser(const double (&v)[8], double* mant, int* expo, bool* dead)
+template <bool UNI = false, int N>
+__device__ __forceinline__ double chain_normaliser(const double (&v)[N], double* mant, int* expo, bool* dead)
 {
-    double sum = ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
-    sum        = chain_sum(sum);
+    const double sum = chain_total<UNI>(v);
     const bool   ok  = sum > 0.0;
     const double ss  = ok ? sum : 1.0;
     const double inv = fast_rcp(ss);
@@ -1147,20 +1222,24 @@ __device__ __forceinline__ void produce_row2(const FastCtx& c, double* tab, bool
         if (c.part == 0) *(double2*)(row + TAB_T) = raw.tq;
     }
 }
-__device__ __forceinline__ void emission_from_row(const double* row, const FastCtx& c, double (&e)[8], double k = 1.0)
+// (N = 2: a window whose tables do not depend on register-index bits 1 and 2 -- B0[j] = B0[j & 1] -- keeps two registers)
+template <int N>
+__device__ __forceinline__ void emission_from_row(const double* row, const FastCtx& c, double (&e)[N], double k = 1.0)
 {
     const double cA0 = row[TAB_C + 0 + c.s0] * row[(0 << 5) | (0 << 4) | (c.s1 << 3) | c.lo] * k;
     const double cA1 = row[TAB_C + 2 + c.s0] * row[(0 << 5) | (1 << 4) | (c.s1 << 3) | c.lo] * k;
     const double* B0 = row + ((1 << 5) | (0 << 4) | (c.s2 << 3));
     const double* B1 = row + ((1 << 5) | (1 << 4) | (c.s2 << 3));
 #pragma unroll
-    for (int j = 0; j < 8; j++) e[j] = cA0 * B0[j] + cA1 * B1[j];
+    for (int j = 0; j < N; j++) e[j] = cA0 * B0[j] + cA1 * B1[j];
 }
 
 // The same in the transposed layout of an odd marker (XPOSE variant): the lane holds state bits 3-5 (its low lane bits
 // index the B half of the table), the registers state bits 0-2 (the A half).
-__device__ __forceinline__ void emission_from_row_t(const double* row, const FastCtx& c, double (&e)[8], double k = 1.0)
+template <int N>
+__device__ __forceinline__ void emission_from_row_t(const double* row, const FastCtx& c, double (&e)[N], double k = 1.0)
 {
+    static_assert(N == 8, "the transposed layout keeps all eight registers");
     const double cB0 = row[TAB_C + 0 + c.s0] * row[(1 << 5) | (0 << 4) | (c.s2 << 3) | c.lo] * k;
     const double cB1 = row[TAB_C + 2 + c.s0] * row[(1 << 5) | (1 << 4) | (c.s2 << 3) | c.lo] * k;
     const double* A0 = row + ((0 << 5) | (0 << 4) | (c.s1 << 3));
@@ -1172,15 +1251,16 @@ __device__ __forceinline__ void emission_from_row_t(const double* row, const Fas
 // Running state of the backward pass of one lane (kept in one struct so that the per-marker body can be
 // instantiated for even and odd markers without a merge of differently-defined values between them).
 #define CNF2_LI_K __attribute__((always_inline))
+template <int N = 8>       // registers per lane (2: fb_fast_kernel's UNI instantiation)
 struct BwdState {
-    double b[8];          // beta
-    double am[8];         // alpha-minus of the row in flight (HALF: of the even marker of the pair)
+    double b[N];          // beta
+    double am[N];         // alpha-minus of the row in flight (HALF: of the even marker of the pair)
     double inv_even;      // reciprocal normaliser stored with that row
     double inv_odd;       // HALF: the one of an unrescaled odd last marker (else 1)
     double bmant, fmant;
     int    bexpo, fexpo;
     bool   bdead;
-    double ec[8];         // emission of the even marker of the pair: formed for the odd marker's rebuild, reused when
+    double ec[N];         // emission of the even marker of the pair: formed for the odd marker's rebuild, reused when
                           // the even marker itself is reached (it is the next one; measured +2.2 %)
     double eb[8];         // crossover mode: e . beta of the marker above (the vector the last beta step transitioned)
 };
@@ -1196,9 +1276,22 @@ struct BwdState {
 // pass over a tile starts from the tile's state (beta, scales: kept in LDS; spill row and tile inputs: asked for again)
 // and the tile epilogue adds the passes up before it writes the rows.  The tables are dynamic LDS (84 KB a block, see the
 // declaration): a block shares a CU with a block of the untied windows' kernel, not with another of its own.
-template <bool HALF, int STOREW = 0, bool XPOSE = false, bool TIED = false>
+// UNI: the plain half-spill sweep of the windows with slots_uniform (cnf2_emission.h) -- every cross of inbred lines.  Their
+// unrestricted tables, and so alpha and beta, do not depend on the four grandparental state bits: the transition's stages on
+// those bits need no exchange (transition_uniform), and a lane carries CNF2_UNI_REGS registers per vector: the two that
+// differ (register bit 0), or all 8 (A/B: the exchanges alone).  Same operations on the same numbers: the bits of the
+// ordinary instantiation.  Jobs of other windows are skipped (the ordinary instantiation skips these under KP_SKIP_UNIFORM
+// when both run over one job list).  The restricted tables do depend on those bits and are read in full.
+#ifndef CNF2_UNI_REGS
+#define CNF2_UNI_REGS 2
+#endif
+template <bool HALF, int STOREW = 0, bool XPOSE = false, bool TIED = false, bool UNI = false>
 __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
 {
+    static_assert(!UNI || (HALF && STOREW == SW_PLAIN && !XPOSE && !TIED), "the uniform-state variant exists for the plain half-spill sweep");
+    static_assert(CNF2_UNI_REGS == 2 || CNF2_UNI_REGS == 8, "registers per lane and vector of the uniform-state variant");
+    constexpr int  NR   = UNI ? CNF2_UNI_REGS : 8;      // registers per lane and vector
+    constexpr bool PAIR = HALF && STOREW == SW_PLAIN && !XPOSE && !TIED && !UNI;    // the instantiation UNI may run beside
     static_assert(!XPOSE || (HALF && STOREW == SW_PLAIN), "the transposing variant exists for the plain half-spill sweep");
     // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_SAMPLING); by value:
     // STOREW: 0 plain sweep; 1 accumulate mode (also stores the posterior weights wg); 2 turn-scan mode (stores alpha e, beta
@@ -1219,7 +1312,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
     static_assert(!SMP || (!XPOSE && !TIED), "the sampling mode is an instantiation of the untied DPP kernel");
     static_assert(!TIED || (!XPOSE && ROWS), "tie combinations only matter to the rows");
     // Spill row (528 doubles): [k = 0..3][lane][2] = registers 2k, 2k+1 of every lane (one 16-byte access
-    // per lane and k), then [chain][2] = reciprocal normaliser of the (even) marker and, HALF only, of
+    // per lane and k; NR = 2: k = 0 alone, the rest of the slot stays unused), then [chain][2] = reciprocal normaliser of the (even) marker and, HALF only, of
     // an odd last marker.
     constexpr int ROW = 528;
     // TIED: the restricted tables of TWO tie combinations per row (the second pair TIE_KOFF doubles behind the first)
@@ -1272,14 +1365,12 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         c.idx_k10   = part_entry_index(c.part, 2) - c.idx_base;
         c.row_root  = w.row[0];
         int hom = 0;
-        if (w.flags[1] & w.flags[4] & SLOT_HOM) {
-            hom = 1;
-            const int gp = w.flags[2] & w.flags[3] & w.flags[5] & w.flags[6];
-            if ((gp & SLOT_HOM) && (gp & SLOT_PRESENT)) hom = 2;
-        }
+        if (w.flags[1] & w.flags[4] & SLOT_HOM) hom = slots_uniform(w.flags) ? 2 : 1;
         if (hom == 0 && w.flag2ignore == 0) hom = 3;
         if (TIED) hom = 0;
         hom = __builtin_amdgcn_readfirstlane(hom);
+        if (UNI && hom != 2) continue;
+        if (PAIR && (p.flags & KP_SKIP_UNIFORM) && hom == 2) continue;
         const int n_combo = TIED ? __builtin_amdgcn_readfirstlane(1 << w.n_groups) : 1;
         // TIED: the tie groups of this lane's three slots (part_forces), one byte each, so that the window itself need not
         // stay live for the combinations' loop
@@ -1305,9 +1396,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         using even_t = std::integral_constant<bool, false>;
 
         // ---------------------------------------------------------------- forward
-        double a[8];
+        double a[NR];
 #pragma unroll
-        for (int j = 0; j < 8; j++) a[j] = 1.0 / 64.0;
+        for (int j = 0; j < NR; j++) a[j] = 1.0 / 64.0;
         double mant = 1.0;
         int    expo = 0;
         bool   dead = false;
@@ -1327,8 +1418,8 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         // cnF2freq.cpp:1664-1668; only the bookkeeping of the scale differs, not the normalised values).
         auto fwd_step = [&](auto odd_tag, const double* row, int m) {
             constexpr bool ODD = decltype(odd_tag)::value;
-            double         e[8];
-            if (XPOSE && ODD) emission_from_row_t(row, c, e, pend);
+            double         e[NR];
+            if constexpr (XPOSE && ODD) emission_from_row_t(row, c, e, pend);
             else emission_from_row(row, c, e, pend);
             const double2 r  = *(const double2*)(row + TAB_T);
             const int     ml = m - first;
@@ -1336,7 +1427,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             if (!ODD && !VIT) {
 #ifndef CNF2_X_NOSTORE   /* timing ablation only: results are wrong */
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
+                for (int k = 0; k < NR / 2; k++) {
                     // written once, read once a whole chromosome later: streaming (nt) accesses keep the rows
                     // from churning L2 (measured: -2 %)
                     const d2v v = {a[2 * k], a[2 * k + 1]};
@@ -1345,8 +1436,8 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
 #endif
             }
 #pragma unroll
-            for (int j = 0; j < 8; j++) a[j] *= e[j];
-            if (VIT) {
+            for (int j = 0; j < NR; j++) a[j] *= e[j];
+            if constexpr (VIT) {
 #pragma unroll
                 for (int j = 0; j < 8; j++) vt[j] *= e[j];
                 if (!ODD) {
@@ -1368,19 +1459,20 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 // rebuild the forward scale before each marker without a reduction (and redo the forward step)
                 double inv;
                 if (HALF) {
-                    inv  = chain_normaliser(a, &mant, &expo, &dead);
+                    inv  = chain_normaliser<UNI>(a, &mant, &expo, &dead);
                     pend = inv;
                     // data that loses > 150 decades in one stretch: keep the vectors in range by rescaling densely
                     if (__ballot(inv > CNF2_RESCALE_GUARD)) rmask = 1;
                 } else {
-                    scale_chain(a, &mant, &expo, &dead, &inv);     // full spill: the stored rows are normalised at once
+                    scale_chain<UNI>(a, &mant, &expo, &dead, &inv);     // full spill: the stored rows are normalised at once
                 }
                 if (c.lo == 0 && !VIT) sp[512 + 2 * s + (ODD ? 1 : 0)] = inv;
             } else if (!ODD && !VIT) {
                 if (c.lo == 0) sp[512 + 2 * s] = 1.0;
             }
             if (m < last) {
-                if (XPOSE) transition_xpose(a, r.x, r.y, xb, lane);
+                if constexpr (XPOSE) transition_xpose(a, r.x, r.y, xb, lane);
+                else if constexpr (UNI) transition_uniform(a, r.x, r.y);
                 else transition_scaled(a, r.x, r.y);
                 if (VIT) {
                     const unsigned long long d = vit_transition(vt, r.x, r.y);
@@ -1653,9 +1745,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         // Bsuf(m) the backward ones, val summed over paths of class d and states is
         //     exp(-factor) * Fpre_s(m) * Bsuf_s(m) * sum_g alphaminus_s(g) beta_s(g) e^{(d)}_s(g).
         // Scales are carried as mantissa * 2^exponent; Fpre is rebuilt from the stored reciprocals.
-        BwdState S;
+        BwdState<NR> S;
 #pragma unroll
-        for (int j = 0; j < 8; j++) S.b[j] = 1.0;
+        for (int j = 0; j < NR; j++) S.b[j] = 1.0;
         S.bmant = 1.0;
         S.bexpo = 0;
         S.bdead = false;
@@ -1674,7 +1766,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             if (idx >= 0) return;
 #endif
 #pragma unroll
-            for (int k = 0; k < 4; k++) {
+            for (int k = 0; k < NR / 2; k++) {
                 const d2v v = __builtin_nontemporal_load((const d2v*)(sp + k * 128 + lane * 2));
                 S.am[2 * k]     = v.x;
                 S.am[2 * k + 1] = v.y;
@@ -1692,46 +1784,49 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         auto marker = [&](auto odd_tag, double* row, int m, bool carried = false) {
             constexpr bool ODD = decltype(odd_tag)::value;
             const int      ml  = m - first;
-            double         wj[8];
+            double         wj[NR];
             double         aw[STOREW == 2 || STOREW == 4 ? 8 : 1];  // turn-scan / crossover mode: alpha-minus of this marker, unscaled
             const double2 r_m = *(const double2*)(row + TAB_T);     // gap m-1 -> m
             double        inv_m;
             if (ODD) {
                 // odd marker: alpha-minus(m) = T( alpha-minus(m-1) * e(m-1) * inv(m-1) ), exactly the
                 // forward step (cnF2freq.cpp:2238-2367); marker m-1 is the previous row of this tile
-                double ep[8];
+                double ep[NR];
                 emission_from_row(row - TS, c, ep);
                 if (!TIED && STOREW != 4) {        // (TIED, crossover mode: the 16 registers are needed elsewhere; the even marker forms its own)
 #pragma unroll
-                    for (int j = 0; j < 8; j++) S.ec[j] = ep[j];
+                    for (int j = 0; j < NR; j++) S.ec[j] = ep[j];
                 }
 #pragma unroll
-                for (int j = 0; j < 8; j++) wj[j] = S.am[j] * ep[j];
+                for (int j = 0; j < NR; j++) wj[j] = S.am[j] * ep[j];
                 // the normaliser inv(m-1) is a per-chain scalar and everything below is linear in wj:
                 // it is applied to the three class sums (`scale`) instead of to the eight states
-                if (XPOSE) transition_xpose(wj, r_m.x, r_m.y, xb, lane);
+                if constexpr (XPOSE) transition_xpose(wj, r_m.x, r_m.y, xb, lane);
+                else if constexpr (UNI) transition_uniform(wj, r_m.x, r_m.y);
                 else transition_scaled(wj, r_m.x, r_m.y);
-                if (STOREW == 2 || STOREW == 4) {
+                if constexpr (STOREW == 2 || STOREW == 4) {
 #pragma unroll
                     for (int j = 0; j < 8; j++) aw[j] = wj[j];
                 }
 #pragma unroll
-                for (int j = 0; j < 8; j++) wj[j] *= S.b[j];
+                for (int j = 0; j < NR; j++) wj[j] *= S.b[j];
                 inv_m = S.inv_odd;
             } else {
-                if (STOREW == 2 || STOREW == 4) {
+                if constexpr (STOREW == 2 || STOREW == 4) {
 #pragma unroll
                     for (int j = 0; j < 8; j++) aw[j] = S.am[j];
                 }
 #pragma unroll
-                for (int j = 0; j < 8; j++) wj[j] = S.am[j] * S.b[j];
+                for (int j = 0; j < NR; j++) wj[j] = S.am[j] * S.b[j];
                 inv_m = S.inv_even;
                 // the row is used up: request the one below it (clamped at the chromosome start, where the
                 // reload is harmless) so that a whole marker, or two, of arithmetic covers the latency.
                 // The empty asm pins "last use, then reload" in that order: otherwise the loads are hoisted
                 // above the products, land in fresh registers and are copied (and waited for) at once.
-                asm volatile("" : "+v"(wj[0]), "+v"(wj[1]), "+v"(wj[2]), "+v"(wj[3]), "+v"(wj[4]), "+v"(wj[5]),
-                             "+v"(wj[6]), "+v"(wj[7]), "+v"(inv_m) : : "memory");
+                if constexpr (NR == 8)
+                    asm volatile("" : "+v"(wj[0]), "+v"(wj[1]), "+v"(wj[2]), "+v"(wj[3]), "+v"(wj[4]), "+v"(wj[5]),
+                                 "+v"(wj[6]), "+v"(wj[7]), "+v"(inv_m) : : "memory");
+                else asm volatile("" : "+v"(wj[0]), "+v"(wj[1]), "+v"(inv_m) : : "memory");
                 const int idx = HALF ? (ml >> 1) - 1 : ml - 1;
                 load_row(idx < 0 ? 0 : idx);
             }
@@ -1765,9 +1860,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 const double  av = cf * row[ko + TAB_R + ia], a1 = cf * row[ko + TAB_2 + ia];
                 double        sb = 0.0, sb1 = 0.0;
 #pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    sb += wj[j] * Br[j];
-                    sb1 += wj[j] * B1[j];
+                for (int j = 0; j < 8; j++) {      // (NR = 2: the weights repeat over register bits 1 and 2, the restricted tables do not)
+                    sb += wj[j & (NR - 1)] * Br[j];
+                    sb1 += wj[j & (NR - 1)] * B1[j];
                 }
                 n_tot += av * sb;
                 n_a1 += a1 * sb;
@@ -1836,7 +1931,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 if ((lane & 16) == 0) wp[64 + ((lane >> 3) & 1) * 16 + (c.s2 << 3) + (lane & 7)] = h1v;
             }
 #else
-            if (WG && (!TIED || cur_combo == 0)) {
+            if constexpr (WG) if (!TIED || cur_combo == 0) {
                 // accumulate mode: wg(s, g) = exp(scales - factor) alphaminus beta for the batched HOT LOOP 2 kernel
                 // (the same in every tie combination)
                 double* wp = p.wbuf + ((size_t)job * p.wstride + ml) * 512;
@@ -1847,7 +1942,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 }
             }
 #endif
-            if (STOREW == 4) {
+            if constexpr (STOREW == 4) {
                 // crossover mode, gap m -> m+1: al = alpha-minus e (up to a per-chain scalar), S.b = T' eb exactly, so the
                 // normaliser D = <al, S.b> and the flipped masses carry the same scalars and the same dropped (1 - r)
                 // constants; the flipped factor of bit t is t_t = r_t / (1 - r_t) of the gap (p.tq[m])
@@ -1869,14 +1964,14 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             }
             // this marker's own emission is only needed for the beta step: formed here, after the sums, so
             // that it does not occupy registers across them
-            double e[8];
-            if (XPOSE && ODD) emission_from_row_t(row, c, e);
+            double e[NR];
+            if constexpr (XPOSE && ODD) emission_from_row_t(row, c, e);
             else if (!ODD && carried) {
 #pragma unroll
-                for (int j = 0; j < 8; j++) e[j] = S.ec[j];
+                for (int j = 0; j < NR; j++) e[j] = S.ec[j];
             }
             else emission_from_row(row, c, e);
-            if (POST) {
+            if constexpr (POST) {
                 // placement mode: gamma(s, g) = wg e, the posterior of state g in mode s at this marker, where the accumulate
                 // mode stores wg (same row, same layout); sums to the weight of the modes the rows count
                 double* wp = p.wbuf + ((size_t)job * p.wstride + ml) * 512;
@@ -1887,7 +1982,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                     __builtin_nontemporal_store(v, (d2v*)(wp + k * 128 + lane * 2));
                 }
             }
-            if (STOREW == 2) {
+            if constexpr (STOREW == 2) {
                 // turn-scan mode: A = alphaminus e and B = beta as held here, with the log2 of the scales that make them
                 // absolute (alphaminus: Fpre, and the stored normaliser of the even neighbour for a rebuilt odd marker)
                 double* wp = p.wbuf + ((size_t)job * p.wstride + ml) * CNF2_TURN_ROW;
@@ -1913,15 +2008,16 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             }
             // beta(m-1) = T( beta(m) * e(m) ); at the first marker the result is never used
 #pragma unroll
-            for (int j = 0; j < 8; j++) S.b[j] *= e[j];
+            for (int j = 0; j < NR; j++) S.b[j] *= e[j];
             // (deferring this normaliser like the forward one was measured slower here: the row scale and the
             // emission of the next step would both wait for the reciprocal)
             if (!HALF || (!ODD && (ml & bmask) == 0)) {
-                const double bsum = scale_chain(S.b, &S.bmant, &S.bexpo, &S.bdead);
+                const double bsum = scale_chain<UNI>(S.b, &S.bmant, &S.bexpo, &S.bdead);
                 if (HALF && __ballot(bsum > 0.0 && bsum * CNF2_RESCALE_GUARD < 1.0)) bmask = 1;
             }
-            if (STOREW == 4) xo_copy(S.eb, S.b);
-            if (XPOSE) transition_xpose(S.b, r_m.x, r_m.y, xb, lane);
+            if constexpr (STOREW == 4) xo_copy(S.eb, S.b);
+            if constexpr (XPOSE) transition_xpose(S.b, r_m.x, r_m.y, xb, lane);
+            else if constexpr (UNI) transition_uniform(S.b, r_m.x, r_m.y);
             else transition_scaled(S.b, r_m.x, r_m.y);
         };
         load_raw<-1>(p, c, first + (ntile - 1) * 8, first, last, &raw);
@@ -1931,7 +2027,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             // LDS, the spill row in flight by asking for it again
             const int bmask0 = bmask;
             const bool bdead0 = S.bdead;
-            if (TIED) {
+            if constexpr (TIED) {
                 double* sv = tsave[wib] + lane;
 #pragma unroll
                 for (int j = 0; j < 8; j++) sv[j * 64] = S.b[j];
@@ -1969,7 +2065,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             }
             wave_lds_fence();
             const int mend = (m0 + 7 < last) ? m0 + 7 : last;
-            if (TIED) {
+            if constexpr (TIED) {
                 // (for the first combination too: nothing of the backward state is then live across the producer, whose tie
                 // form needs the registers)
                 const double* sv = tsave[wib] + lane;
@@ -2223,7 +2319,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_packed_kernel(KernelParams p
         if (p.flags & KP_NO_DOSAGE) continue;
 
         // ---------------------------------------------------------------- backward + rows
-        BwdState S;
+        BwdState<> S;
 #pragma unroll
         for (int j = 0; j < 8; j++) S.b[j] = 1.0;
         S.bmant = 1.0;
@@ -4255,10 +4351,10 @@ void launch_fb_packed(const KernelParams& p, int grid, hipStream_t stream)
 
 // dynamic LDS of the tied instantiations: 8 table rows per wave, each with the restricted tables of two tie combinations
 #define CNF2_TIED_LDS_BYTES (CNF2_WAVES_PER_BLOCK * 8 * (TAB_STRIDE + 128) * (int)sizeof(double))
-template <bool HALF, int STOREW, bool XPOSE = false, bool TIED = false>
+template <bool HALF, int STOREW, bool XPOSE = false, bool TIED = false, bool UNI = false>
 static void launch_fast_as(const KernelParams& p, int grid, hipStream_t stream)
 {
-    const auto kernel = fb_fast_kernel<HALF, STOREW, XPOSE, TIED>;
+    const auto kernel = fb_fast_kernel<HALF, STOREW, XPOSE, TIED, UNI>;
     static bool asked = false;       // (per instantiation; more than 64 KB of dynamic LDS has to be asked for once)
     if (TIED && !asked) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CNF2_TIED_LDS_BYTES);
@@ -4272,9 +4368,26 @@ static constexpr int fast_key(int storew, bool half, bool xpose = false, bool ti
 }
 hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStream_t stream)
 {
-    zero_job_counter(p, stream);
-    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the sixteen instantiations there are
-    case fast_key(SW_PLAIN, true): launch_fast_as<true, SW_PLAIN>(p, grid, stream); break;
+    // the plain half-spill sweep: the uniform windows' jobs through the UNI instantiation, the others through the ordinary
+    // one; a list that holds both is swept by both, one after the other in the same spill slots, each skipping the other
+    // class and each with its own job counter.  The logarithms are taken once, after both
+    const bool plain_half = fast_key(v.storew, v.half, v.xpose, v.tied) == fast_key(SW_PLAIN, true);
+    const int  n_uni      = plain_half ? v.n_uniform : 0;
+    if (n_uni > 0) {
+        KernelParams pu = p;
+        if (pu.job_next) pu.job_next = v.job_next_uniform;
+        zero_job_counter(pu, stream);
+        launch_fast_as<true, SW_PLAIN, false, false, true>(pu, v.grid_uniform > 0 ? v.grid_uniform : grid, stream);
+        if (n_uni >= p.n_jobs) {
+            launch_likelihood_logs(p, stream);
+            return hipGetLastError();
+        }
+    }
+    KernelParams po = p;
+    if (n_uni > 0) po.flags |= KP_SKIP_UNIFORM;
+    zero_job_counter(po, stream);
+    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the sixteen instantiations there are (and UNI above)
+    case fast_key(SW_PLAIN, true): launch_fast_as<true, SW_PLAIN>(po, grid, stream); break;
     case fast_key(SW_PLAIN, false): launch_fast_as<false, SW_PLAIN>(p, grid, stream); break;
     case fast_key(SW_PLAIN, true, true): launch_fast_as<true, SW_PLAIN, true>(p, grid, stream); break;
     case fast_key(SW_PLAIN, true, false, true): launch_fast_as<true, SW_PLAIN, false, true>(p, grid, stream); break;
@@ -4881,6 +4994,12 @@ int fb_fast_blocks_per_cu()
 {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fb_fast_kernel<true>, CNF2_BLOCK, 0) != hipSuccess) n = 2;
+    return n < 1 ? 1 : n;
+}
+int fb_fast_uniform_blocks_per_cu()
+{
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fb_fast_kernel<true, SW_PLAIN, false, false, true>, CNF2_BLOCK, 0) != hipSuccess) n = 2;
     return n < 1 ? 1 : n;
 }
 

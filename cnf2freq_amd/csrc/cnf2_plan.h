@@ -67,10 +67,7 @@ inline JobPlan plan_jobs(const Window* windows, const int32_t* chromstarts, int 
     };
     // a group shares the producer's instantiation: windows whose grandparents are all present and homozygous everywhere
     // (SLOT_HOM) are grouped apart from the others
-    auto homleaf = [](const Window& w) {
-        const int gp = w.flags[2] & w.flags[3] & w.flags[5] & w.flags[6];
-        return (gp & SLOT_HOM) && (gp & SLOT_PRESENT);
-    };
+    auto homleaf = [](const Window& w) { return slots_homleaf(w.flags); };
     std::vector<uint8_t> packed(merge ? n : 0, 0);
     for (int cls = 0; merge && cls < 2; cls++) {
         std::vector<int> el;

@@ -109,6 +109,11 @@ enum {
                                      blocks are resident share the job list evenly, whatever the chromosomes' lengths and
                                      however the kernels of the tied and the untied windows share the machine).  Same results
                                      to the bit: a job's arithmetic does not depend on the wave that runs it. */
+    CNF2_ALL_STATES   = 1u << 21, /* cnf2_sweep and its modes: the windows of crosses of inbred lines (both parents and all four
+                                     grandparents homozygous with equal sure everywhere) through the fast kernel's ordinary
+                                     instantiation, which carries all 64 states of a chain, instead of the instantiation that
+                                     keeps the states their tables make equal only once.  Same results to the bit; A/B switch
+                                     and cross-check.  Ignored where that instantiation is not used */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
                                     registers by a transpose through LDS instead of being exchanged by DPP moves (same
