@@ -43,7 +43,7 @@ SYMBOLS = [
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
-    "cnf2_sweep_place",
+    "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows",
 ]
 
 
@@ -110,6 +110,8 @@ def load():
         L.cnf2_sweep_viterbi.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_sample.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_place.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_sweep_loo.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_loo_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -439,6 +441,44 @@ class Context:
                                           C.c_void_p(d_place) if d_place else None, C.c_void_p(d_place_sum),
                                           C.c_void_p(d_n_zero), C.c_void_p(d_null), C.c_void_p(d_n_contrib),
                                           flags | OUT_DEVICE), "cnf2_sweep_place")
+
+    def loo_rows(self, ind, chrom=0):
+        """[mc][2] = (loo, unlinked) of one individual and chromosome from the alpha/beta store, brute force (the
+        cross-check of sweep_loo); IGNORED where the individual is skipped."""
+        mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])
+        v = np.zeros((mc, 2))
+        self._chk(self.L.cnf2_loo_rows(self.h, ind, chrom, _p(v)), "cnf2_loo_rows")
+        return v
+
+    def sweep_loo(self, ind_begin=0, ind_end=None, rows=True, full_spill=False, ties_general=False, static_jobs=False):
+        """cnf2_sweep_loo: factors / loglik as sweep(); loo[n][M], the cost in nats of the data at marker m given the
+        individual's data at every other marker of the chromosome, and unlinked[n][M], the cost of the same data with
+        the marker off the map (both IGNORED where skipped; None with rows=False); their sums over the range's
+        individuals loo_sum[M] / unlinked_sum[M] and the contributing individuals per chromosome.  qc.marker_report and
+        qc.flag_genotypes read them."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        loo = np.zeros((n, self.n_markers)) if rows else None
+        unl = np.zeros((n, self.n_markers)) if rows else None
+        ls = np.zeros(self.n_markers)
+        us = np.zeros(self.n_markers)
+        cnt = np.zeros(self.n_chrom, np.int32)
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0))
+        self._chk(self.L.cnf2_sweep_loo(self.h, ind_begin, ind_end, _p(factors), _p(loglik), _p(loo) if rows else None,
+                                        _p(unl) if rows else None, _p(ls), _p(us), _p(cnt), flags), "cnf2_sweep_loo")
+        return dict(factors=factors, loglik=loglik, loo=loo, unlinked=unl, loo_sum=ls, unlinked_sum=us, n_contrib=cnt)
+
+    def sweep_loo_device(self, ind_begin, ind_end, d_factors, d_loglik, d_loo, d_unlinked, d_loo_sum, d_unlinked_sum,
+                         d_n_contrib, flags=0):
+        """Device-pointer form (ints; d_loo / d_unlinked may be None: the rows then stay in the context)."""
+        self._chk(self.L.cnf2_sweep_loo(self.h, ind_begin, ind_end, C.c_void_p(d_factors), C.c_void_p(d_loglik),
+                                        C.c_void_p(d_loo) if d_loo else None,
+                                        C.c_void_p(d_unlinked) if d_unlinked else None, C.c_void_p(d_loo_sum),
+                                        C.c_void_p(d_unlinked_sum), C.c_void_p(d_n_contrib), flags | OUT_DEVICE),
+                  "cnf2_sweep_loo")
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

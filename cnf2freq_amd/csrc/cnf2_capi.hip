@@ -127,6 +127,10 @@ struct cnf2_ctx {
     DevBuf<int32_t> d_smp_sh;             // [n][K][n_chrom]
     DevBuf<double>  d_smp_lp;             // [n][K][n_chrom]
 
+    // leave-one-marker-out rows (cnf2_sweep_loo): the rows a call did not hand device memory for, and its staged sums
+    DevBuf<double>  d_loo, d_unl;         // [n][n_markers]
+    DevBuf<double>  d_loo_sum, d_unl_sum; // [n_markers]
+
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
     DevBuf<double2> d_pl_sure;
@@ -636,11 +640,14 @@ static JobPlan job_plan(const cnf2_ctx* ctx, int ind_begin, int n, uint32_t flag
 
 // What a sweep leaves besides the likelihoods: its mode with that mode's device outputs
 struct SweepMode {
-    SweepVariant variant = SW_PLAIN;   // SW_PLAIN (cnf2_sweep: the rows), SW_CROSSOVERS, SW_VITERBI or SW_SAMPLING
+    SweepVariant variant = SW_PLAIN;   // SW_PLAIN (cnf2_sweep: the rows), SW_CROSSOVERS, SW_VITERBI, SW_SAMPLING or SW_LOO
     // SW_CROSSOVERS (cnf2_sweep_crossovers)
     double*  xo = nullptr;             // [n][n_markers][6] or null
     double*  xo_sum = nullptr;         // [n_markers][6], zeroed by the caller
-    int32_t* xo_cnt = nullptr;         // [n_chrom], zeroed by the caller
+    int32_t* xo_cnt = nullptr;         // [n_chrom], zeroed by the caller (SW_LOO too)
+    // SW_LOO (cnf2_sweep_loo): what the sweep leaves for loo_finish_kernel
+    double*  loo = nullptr;            // [n][n_markers]
+    double*  unl = nullptr;            // [n][n_markers]
     // SW_VITERBI (cnf2_sweep_viterbi) and, with a leading [K] of draws per individual, SW_SAMPLING (cnf2_sweep_sample)
     uint8_t* state = nullptr;          // [n][n_markers]
     int32_t* shift = nullptr;          // [n][n_chrom]
@@ -655,7 +662,8 @@ struct SweepMode {
 // forms them) and then the general kernel's crossover instantiation (their posteriors).  Viterbi mode: the same routing,
 // with the fast kernel's Viterbi instantiation in place of both crossover instantiations.  Sampling mode: the untied windows
 // through the fast kernel's sampling instantiation (one pass: likelihoods and draws), the tied ones through the tied kernel
-// without rows (likelihoods) and then the same sampling instantiation (draws)
+// without rows (likelihoods) and then the same sampling instantiation (draws).  Leave-one-out mode: sampling's routing with
+// the fast kernel's leave-one-out instantiation
 static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
                       uint32_t flags, const SweepMode& mode)
 {
@@ -758,6 +766,13 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         p.smp_ind0  = ind_begin;
         follow_per_cu = ctx->fast_blocks_per_cu;
         break;
+    case SW_LOO:
+        p.flags  = KP_NO_DOSAGE;    // (no rows; the instantiation makes its backward pass all the same)
+        p.loo    = mode.loo;
+        p.unl    = mode.unl;
+        p.xo_cnt = mode.xo_cnt;
+        follow_per_cu = ctx->fast_blocks_per_cu;
+        break;
     default: break;
     }
     if (flags & CNF2_LOG_PATHS) {
@@ -794,9 +809,9 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         else HIP_TRY(ctx, launch_fb_fast(pt, grid_gen, {SW_PLAIN, true, false, true}, ctx->stream2));
         if (!plain) {
             // the mode's instantiation over the tied jobs in the same spill slots (after the pass above on this stream): the
-            // general kernel's for the crossovers; the fast kernel's for Viterbi and sampling (the forward pass, the
-            // max-product recursion and the draws do not see the tie rule).  Its own likelihoods go to scratch (the ones
-            // reported are the tied kernel's); its occupancy is its own
+            // general kernel's for the crossovers; the fast kernel's for Viterbi, sampling and leave-one-out (the forward
+            // pass, the max-product recursion, the draws and alpha beta do not see the tie rule).  Its own likelihoods go to
+            // scratch (the ones reported are the tied kernel's); its occupancy is its own
             KernelParams px = pt;
             likelihoods_to_scratch(&px);
             const int gx = std::min(resident_blocks(ctx->n_cu, follow_per_cu, ctx->reserve_blocks), grid_gen);
@@ -1035,10 +1050,9 @@ static int mode_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
 {
     const size_t n = (size_t)(ind_end - ind_begin);
     RC_TRY(ctx->d_xo_f.ensure(ctx, n * ctx->n_chrom * 9 + 1));
-    if (mode.variant == SW_CROSSOVERS) {
+    if (mode.variant == SW_CROSSOVERS)
         HIP_TRY(ctx, hipMemsetAsync(mode.xo_sum, 0, (size_t)ctx->n_markers * 6 * sizeof(double), ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(mode.xo_cnt, 0, (size_t)ctx->n_chrom * sizeof(int32_t), ctx->stream));
-    }
+    if (mode.xo_cnt) HIP_TRY(ctx, hipMemsetAsync(mode.xo_cnt, 0, (size_t)ctx->n_chrom * sizeof(int32_t), ctx->stream));
     const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL | CNF2_ALL_STATES);
     return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, mode);
 }
@@ -1070,6 +1084,56 @@ int cnf2_sweep_crossovers(cnf2_ctx* ctx, int ind_begin, int ind_end, double* fac
     RC_TRY(fetch_out(ctx, xo_sum_out, m.xo_sum, M * 6));
     RC_TRY(fetch_out(ctx, n_contrib_out, m.xo_cnt, C));
     RC_TRY(fetch_out(ctx, xo_out, m.xo, nx));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+int cnf2_loo_rows(cnf2_ctx* ctx, int ind, int chrom, double* rows_out)
+{
+    if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad loo_rows arguments");
+    return stage2_rows(ctx, ind, chrom, 2, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_loo_rows(q, d_out, ctx->stream); });
+}
+
+// one pass of sweep_impl's leave-one-out mode, then loo_finish_kernel on the context's stream: the logarithms in place and
+// the column sums (an empty range reports them as zeros).  The rows the caller gave no device memory for live in the
+// context's own buffers
+int cnf2_sweep_loo(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* loo_out,
+                   double* unlinked_out, double* loo_sum_out, double* unlinked_sum_out, int32_t* n_contrib_out, uint32_t flags)
+{
+    RC_TRY(ready(ctx));
+    if (!factors_out || !loglik_out || !loo_sum_out || !unlinked_sum_out || !n_contrib_out)
+        return fail(ctx, CNF2_ERR_ARG, "only loo_out and unlinked_out may be NULL");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    n = ind_end - ind_begin;
+    const size_t M = ctx->n_markers, C = ctx->n_chrom, nr = (size_t)n * M;
+    SweepMode    m;
+    m.variant = SW_LOO;
+    double *d_lsum, *d_usum;
+    RC_TRY(stage_out(ctx, dev, loo_sum_out, ctx->d_loo_sum, M, &d_lsum));
+    RC_TRY(stage_out(ctx, dev, unlinked_sum_out, ctx->d_unl_sum, M, &d_usum));
+    RC_TRY(stage_out(ctx, dev, n_contrib_out, ctx->d_xo_cnt, C, &m.xo_cnt));
+    m.loo = (dev && loo_out) ? loo_out : nullptr;
+    m.unl = (dev && unlinked_out) ? unlinked_out : nullptr;
+    if (!m.loo && nr > 0) {
+        RC_TRY(ctx->d_loo.ensure(ctx, nr));
+        m.loo = ctx->d_loo;
+    }
+    if (!m.unl && nr > 0) {
+        RC_TRY(ctx->d_unl.ensure(ctx, nr));
+        m.unl = ctx->d_unl;
+    }
+    RC_TRY(mode_sweep(ctx, ind_begin, ind_end, factors_out, loglik_out, flags & ~(uint32_t)CNF2_ALL_STATES, m));
+    launch_loo_finish(m.loo, m.unl, n, (int)M, d_lsum, d_usum, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));       // (the timed span of cnf2_last_kernel_ms covers the finish)
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, loo_sum_out, d_lsum, M));
+    RC_TRY(fetch_out(ctx, unlinked_sum_out, d_usum, M));
+    RC_TRY(fetch_out(ctx, n_contrib_out, m.xo_cnt, C));
+    if (loo_out) RC_TRY(fetch_out(ctx, loo_out, m.loo, nr));
+    if (unlinked_out) RC_TRY(fetch_out(ctx, unlinked_out, m.unl, nr));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
 }

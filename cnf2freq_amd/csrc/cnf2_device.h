@@ -31,8 +31,11 @@ enum SweepVariant : int {
     SW_CROSSOVERS   = 4,   // posterior probability of a flip of every state bit across every gap (p.xo / p.xo_sum / p.xo_cnt); no rows
     SW_VITERBI      = 5,   // max-product recursion and backtrace in place of the backward pass (p.vit_*); no rows
     SW_SAMPLING     = 6,   // whole paths drawn from the posterior, one draw per lane (p.smp_*); no beta, no rows
-    SW_POSTERIOR    = 7    // placement mode: the state posteriors gamma = wg e of every marker into p.wbuf (SW_WEIGHTS' row and
+    SW_POSTERIOR    = 7,   // placement mode: the state posteriors gamma = wg e of every marker into p.wbuf (SW_WEIGHTS' row and
                            // layout), the jobs with a likelihood counted in p.xo_cnt; no rows
+    SW_LOO          = 8    // leave-one-marker-out mode: per marker the likelihood ratio without the marker's emission (p.loo) and
+                           // the marker's unlinked emission mean (p.unl), over every mode with a likelihood; the jobs with a
+                           // likelihood counted in p.xo_cnt; no rows
 };
 
 struct KernelParams {
@@ -93,6 +96,10 @@ struct KernelParams {
     unsigned long long smp_seed;   // sampling mode: the generator's seed
     int            smp_draws;  // sampling mode: draws per individual and chromosome (1..1024)
     int            smp_ind0;   // sampling mode: absolute index of the individual at windows[0] (the generator's i)
+    double*        loo;        // leave-one-out mode: [n_ind][n_markers] sum_s L_s,-m / L as the sweep leaves it (-1: skipped);
+                               // loo_finish_kernel takes the logarithm in place
+    double*        unl;        // leave-one-out mode: [n_ind][n_markers] mean over the analysed modes of (1/64) sum_g e_s,m(g),
+                               // likewise (-1: skipped); minus its logarithm after loo_finish_kernel
 };
 #define CNF2_LEXP_IGNORED (-2147483647 - 1)   /* shift mode not analysed: CNF2_IGNORED_D */
 #define CNF2_LEXP_DEAD    (-2147483647)       /* no likelihood left: CNF2_MINFACTOR_F */
@@ -227,6 +234,12 @@ void launch_addvariance(const KernelParams& p, int first, int len, double* out, 
 hipError_t launch_fb(const KernelParams& p, int grid, SweepVariant variant, hipStream_t stream, bool debug_store = false);
 int  fb_xo_blocks_per_cu();
 void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream);
+// out[len][2] = (loo, unlinked) of cnf2_sweep_loo from the store, brute force
+void launch_loo_rows(const Stage2Params& q, double* out, hipStream_t stream);
+// What a leave-one-out sweep (SW_LOO) left in loo / unl [n_ind][n_markers] becomes loo = log(ratio) and unlinked = -log(mean)
+// in place (CNF2_IGNORED where skipped); loo_sum / unl_sum [n_markers] = their sums over the n_ind individuals in ascending
+// order, one thread per marker (no atomics: the same bits on every call)
+void launch_loo_finish(double* loo, double* unl, int n_ind, int n_markers, double* loo_sum, double* unl_sum, hipStream_t stream);
 // Which instantiation of fb_fast_kernel a launch takes.  half: alpha-minus spilled at every second marker (not
 // CNF2_FULL_SPILL); xpose: the transposing variant of the plain sweep; tied: the tile producer with a pass per tie
 // combination (windows with tie groups).  SW_WEIGHTS forms no per-locus rows: windows with tie groups can take it untied

@@ -1293,7 +1293,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
     constexpr int  NR   = UNI ? CNF2_UNI_REGS : 8;      // registers per lane and vector
     constexpr bool PAIR = HALF && STOREW == SW_PLAIN && !XPOSE && !TIED && !UNI;    // the instantiation UNI may run beside
     static_assert(!XPOSE || (HALF && STOREW == SW_PLAIN), "the transposing variant exists for the plain half-spill sweep");
-    // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_SAMPLING); by value:
+    // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_LOO); by value:
     // STOREW: 0 plain sweep; 1 accumulate mode (also stores the posterior weights wg); 2 turn-scan mode (stores alpha e, beta
     // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only); 4 crossover
     // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows);
@@ -1301,12 +1301,16 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
     // slot, and a backtrace replaces the backward pass: p.vit_logmax / p.vit_state / p.vit_shift; no rows); 6 sampling mode
     // (the plain forward pass; backward walks that rebuild alpha and draw whole paths from the posterior, one draw per
     // lane: p.smp_state / p.smp_shift / p.smp_logp; no beta, no rows); 7 placement mode (stores the state posteriors
-    // gamma = wg e of every marker where the accumulate mode stores wg; counts the jobs with a likelihood in p.xo_cnt; no rows)
+    // gamma = wg e of every marker where the accumulate mode stores wg; counts the jobs with a likelihood in p.xo_cnt; no rows);
+    // 8 leave-one-out mode (per marker sum_s L_s,-m / L over every mode with a likelihood and the marker's unlinked emission
+    // mean into p.loo / p.unl, their logarithms left to loo_finish_kernel; counts the jobs with a likelihood in p.xo_cnt; no rows)
     constexpr bool ROWS = STOREW == SW_PLAIN || STOREW == SW_WEIGHTS_ROWS;      // class sums, restricted tables, tile epilogue, p.dosage
     constexpr bool WG   = STOREW == SW_WEIGHTS_ROWS || STOREW == SW_WEIGHTS;
     constexpr bool VIT  = STOREW == SW_VITERBI;
     constexpr bool SMP  = STOREW == SW_SAMPLING;
     constexpr bool POST = STOREW == SW_POSTERIOR;
+    constexpr bool LOO  = STOREW == SW_LOO;
+    static_assert(!LOO || (!XPOSE && !TIED), "the leave-one-out mode is an instantiation of the untied DPP kernel");
     static_assert(!POST || (!XPOSE && !TIED), "the placement mode is an instantiation of the untied DPP kernel");
     static_assert(!VIT || (!XPOSE && !TIED), "the Viterbi mode is an instantiation of the untied DPP kernel");
     static_assert(!SMP || (!XPOSE && !TIED), "the sampling mode is an instantiation of the untied DPP kernel");
@@ -1532,7 +1536,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 p.lexp[e]   = any_alive ? emax : CNF2_LEXP_DEAD;
             }
         }
-        if ((STOREW == 4 || POST) && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
+        if ((STOREW == 4 || POST || LOO) && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
         if (VIT) {
             // ------------------------------------------------------------ Viterbi: logmax, MAP mode, backtrace
             // logmax_s = log(max-product) + the chromosome's dropped butterfly constants, as likelihood_logs_kernel finishes
@@ -1737,7 +1741,19 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             }
             continue;
         }
-        if (p.flags & KP_NO_DOSAGE) continue;
+        // (the leave-one-out mode forms no rows and is launched for its backward pass: it runs with KP_NO_DOSAGE, as the
+        // general kernel's crossover instantiation does)
+        if (!LOO && (p.flags & KP_NO_DOSAGE)) continue;
+        if (LOO && !any_alive) {
+            // skipped, as the sweep skips it: both rows marked for loo_finish_kernel (CNF2_IGNORED, left out of the sums)
+            double* lo = p.loo + (size_t)jb.ind * p.n_markers + first;
+            double* un = p.unl + (size_t)jb.ind * p.n_markers + first;
+            for (int ml = lane; ml <= last - first; ml += 64) {
+                lo[ml] = -1.0;
+                un[ml] = -1.0;
+            }
+            continue;
+        }
 
         // ---------------------------------------------------------------- backward + rows
         // Row of the reference: sum over (g, s, path) of val = exp(query - factor) by class
@@ -1756,7 +1772,11 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
         // exp(-factor) = xm * 2^xe; a job without a live chain has no rows (cnF2freq.cpp:5403)
         const double xm  = any_alive ? 1.0 / T : 0.0;
         const int    xe  = -emax;
-        const bool   chain_on = alive && !(tmine * 2.3538526683701998e17 < T);        // factor - fs > 40: cnF2freq.cpp:5420-5421
+        // (leave-one-out mode: every mode with a likelihood counts -- a marker that alone pushes a mode out of the band is what
+        // the mode looks for)
+        const bool   chain_on = alive && (LOO || !(tmine * 2.3538526683701998e17 < T));        // factor - fs > 40: cnF2freq.cpp:5420-5421
+        // leave-one-out mode: 1 / (64 x analysed modes), the unlinked mean's divisor
+        const double loo_k = LOO ? 1.0 / (double)(64 * (__builtin_popcountll(__ballot(c.active)) >> 3)) : 0.0;
         const double xo_w     = (STOREW == 4 && chain_on) ? tmine * xm : 0.0;           // crossover mode: P(mode s | data)
         // software pipeline: the spill row (and its reciprocals) is requested one row ahead, straight into
         // the registers it is used from; nothing else in the marker loop is a vector memory operation
@@ -1971,6 +1991,20 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 for (int j = 0; j < NR; j++) e[j] = S.ec[j];
             }
             else emission_from_row(row, c, e);
+            if constexpr (LOO) {
+                // leave-one-out mode: sum_g alphaminus beta with the row scale is L_s,-m / L, the mode's likelihood with this
+                // marker's emission replaced by 1 over the total; the emission's own sum over the analysed modes is the
+                // unlinked term.  The logarithms: loo_finish_kernel
+                const double sw  = ((wj[0] + wj[1]) + (wj[2] + wj[3])) + ((wj[4] + wj[5]) + (wj[6] + wj[7]));
+                const double rat = across_chains_sum(chain_sum(scale != 0.0 ? scale * sw : 0.0));    // (a chain that is off: 0, whatever it holds)
+                const double es  = chain_sum(((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7])));
+                const double tot = across_chains_sum(c.active ? es : 0.0);
+                if (lane == 0) {
+                    const size_t o = (size_t)jb.ind * p.n_markers + m;
+                    p.loo[o] = rat;
+                    p.unl[o] = tot * loo_k;
+                }
+            }
             if constexpr (POST) {
                 // placement mode: gamma(s, g) = wg e, the posterior of state g in mode s at this marker, where the accumulate
                 // mode stores wg (same row, same layout); sums to the weight of the modes the rows count
@@ -2184,6 +2218,35 @@ __global__ __launch_bounds__(256) void likelihood_logs_kernel(KernelParams p)
 static void launch_likelihood_logs(const KernelParams& p, hipStream_t stream)
 {
     if (p.n_jobs > 0) hipLaunchKernelGGL(likelihood_logs_kernel, dim3((p.n_jobs * 8 + 255) / 256), dim3(256), 0, stream, p);
+}
+
+// The logarithms of what a leave-one-out sweep left (the sweep kernel takes none): thread t is marker t and walks the
+// individuals in ascending order -- coalesced across markers, and sums that are the same bits on every call.  A skipped
+// individual's cells (-1 from the sweep) become CNF2_IGNORED and stay out of the sums.
+__global__ __launch_bounds__(256) void loo_finish_kernel(double* loo, double* unl, int n_ind, int n_markers, double* loo_sum,
+                                                         double* unl_sum)
+{
+    const int m = blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= n_markers) return;
+    double sl = 0.0, su = 0.0;
+    for (int i = 0; i < n_ind; i++) {
+        const size_t o = (size_t)i * n_markers + m;
+        const double r = loo[o], u = unl[o];
+        const bool   skipped = r < 0.0;
+        const double lr = skipped ? CNF2_IGNORED_D : log(r), lu = skipped ? CNF2_IGNORED_D : -log(u);
+        loo[o] = lr;
+        unl[o] = lu;
+        sl += skipped ? 0.0 : lr;
+        su += skipped ? 0.0 : lu;
+    }
+    loo_sum[m] = sl;
+    unl_sum[m] = su;
+}
+void launch_loo_finish(double* loo, double* unl, int n_ind, int n_markers, double* loo_sum, double* unl_sum, hipStream_t stream)
+{
+    if (n_markers > 0)
+        hipLaunchKernelGGL(loo_finish_kernel, dim3((n_markers + 255) / 256), dim3(256), 0, stream, loo, unl, n_ind, n_markers,
+                           loo_sum, unl_sum);
 }
 
 // =====================================================================================
@@ -2763,6 +2826,60 @@ __global__ __launch_bounds__(64) void crossover_rows_kernel(Stage2Params q, doub
         }
     }
     if (g < 6) out[(size_t)ml * 6 + g] = xi[g];
+}
+
+
+// The leave-one-out rows from the store, brute force (the cross-check of the sweep's leave-one-out mode): one block per
+// marker ml, thread g.  loo = log sum over the analysed modes with a likelihood of sum_g alphaminus(g) beta(g) (slots 0 and
+// 1 with their cumulative scales) - factor; the same sum with slot 2 in place of slot 0 is the mode's likelihood itself, and
+// a mode whose own is 0 has none.  unlinked = -log of the mean over the analysed modes of (1 / 64) sum_g e(g), e through the
+// sweep's producer / consumer code (as emission_kernel).  out[len][2]; both CNF2_IGNORED where no mode has a likelihood.
+__global__ __launch_bounds__(64) void loo_rows_kernel(Stage2Params q, double* out)
+{
+    __shared__ double tab[64];
+    const int    g  = threadIdx.x;
+    const int    ml = blockIdx.x;
+    const int    m  = q.first + ml;
+    const Window w  = q.kp.windows[0];
+    const double factor = q.loglik[0];
+    double acc = 0.0;
+    bool   any = false;
+    for (int s = 0; s < 8; s++) {
+        if ((s & w.shiftignore) || s >= w.shiftend) continue;
+        const double b    = s2_fw(q, s, ml, 1, g);
+        const double own  = across_chains_sum(chain_sum(s2_fw(q, s, ml, 2, g) * b));
+        if (!(own > 0.0) || !(q.factors[s] > (double)CNF2_MINFACTOR_F)) continue;
+        any = true;
+        const double part = across_chains_sum(chain_sum(s2_fw(q, s, ml, 0, g) * b));
+        acc += part * exp(s2_ff(q, s, ml, 0) + s2_ff(q, s, ml, 1) - factor);
+    }
+    LaneCtx c;
+    make_lane(w, g, &c.L);
+    c.row_root   = w.row[0];
+    c.root_attop = (w.flags[0] & SLOT_FOUNDER) != 0;
+    const int sl = g >> 3;
+    c.s0 = sl & 1;
+    c.s1 = (sl >> 1) & 1;
+    c.s2 = (sl >> 2) & 1;
+    c.lo = state_lo(g);
+    c.active  = true;
+    c.n_combo = 1;
+    const Slot root = load_slot(q.kp, c.row_root, m);
+    LineTerms  T;
+    tab[g] = produce_entry(q.kp, c, root, m, &T);
+    __syncthreads();
+    double c0, c1, e[8];
+    root_weights(c, root, &c0, &c1);
+    emission_from_table(tab, c, c0, c1, e);
+    const bool   on   = !(sl & w.shiftignore) && sl < w.shiftend;
+    const double mine = chain_sum(((e[0] + e[1]) + (e[2] + e[3])) + ((e[4] + e[5]) + (e[6] + e[7])));
+    const double tot  = across_chains_sum(on ? mine : 0.0);
+    const int    n_on = __builtin_popcountll(__ballot(on)) >> 3;
+    if (g == 0) {
+        const bool skip = !any || isnan(factor);
+        out[(size_t)ml * 2 + 0] = skip ? CNF2_IGNORED_D : log(acc);
+        out[(size_t)ml * 2 + 1] = skip ? CNF2_IGNORED_D : -log(tot / (64.0 * n_on));
+    }
 }
 
 
@@ -4364,7 +4481,7 @@ static void launch_fast_as(const KernelParams& p, int grid, hipStream_t stream)
 }
 static constexpr int fast_key(int storew, bool half, bool xpose = false, bool tied = false)
 {
-    return storew | (half ? 8 : 0) | (xpose ? 16 : 0) | (tied ? 32 : 0);
+    return storew | (half ? 16 : 0) | (xpose ? 32 : 0) | (tied ? 64 : 0);
 }
 hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStream_t stream)
 {
@@ -4386,7 +4503,7 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     KernelParams po = p;
     if (n_uni > 0) po.flags |= KP_SKIP_UNIFORM;
     zero_job_counter(po, stream);
-    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the sixteen instantiations there are (and UNI above)
+    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the eighteen instantiations there are (and UNI above)
     case fast_key(SW_PLAIN, true): launch_fast_as<true, SW_PLAIN>(po, grid, stream); break;
     case fast_key(SW_PLAIN, false): launch_fast_as<false, SW_PLAIN>(p, grid, stream); break;
     case fast_key(SW_PLAIN, true, true): launch_fast_as<true, SW_PLAIN, true>(p, grid, stream); break;
@@ -4403,6 +4520,8 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     case fast_key(SW_SAMPLING, false): launch_fast_as<false, SW_SAMPLING>(p, grid, stream); break;
     case fast_key(SW_POSTERIOR, true): launch_fast_as<true, SW_POSTERIOR>(p, grid, stream); break;
     case fast_key(SW_POSTERIOR, false): launch_fast_as<false, SW_POSTERIOR>(p, grid, stream); break;
+    case fast_key(SW_LOO, true): launch_fast_as<true, SW_LOO>(p, grid, stream); break;
+    case fast_key(SW_LOO, false): launch_fast_as<false, SW_LOO>(p, grid, stream); break;
     default: return hipErrorInvalidValue;
     }
     launch_likelihood_logs(p, stream);
@@ -5006,6 +5125,11 @@ int fb_fast_uniform_blocks_per_cu()
 void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t stream)
 {
     hipLaunchKernelGGL(crossover_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
+}
+
+void launch_loo_rows(const Stage2Params& q, double* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(loo_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
 }
 
 void launch_emission(const KernelParams& p, int ind, int marker, double* out, hipStream_t stream)

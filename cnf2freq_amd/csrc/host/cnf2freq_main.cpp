@@ -2,7 +2,8 @@
 // (demo.sh:37):
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
 //            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
-//            [--place F --place-genfile G --place-markers Q] [--remap F [--remap-iterations K]]
+//            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]]
+//            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
 // haplotyping sweep (doit) before its dump.  Rows of the last round go to --output, earlier ones to stdout; every
@@ -43,6 +44,15 @@
 // impossible, the LOD there against "unlinked", the positions that bound the contiguous stretch within 1 LOD of it on that
 // chromosome, and that fewest number; after a blank line the LOD at every marker of the map, one "%.5lf" tab-separated
 // line per candidate.  --output is the same with or without it.  Single GPU only.
+//
+// --loo F [--loo-threshold X] (not flags of the reference): after the last round, and before a --remap changes the map,
+// the leave-one-marker-out costs of the last round's state (cnf2_sweep_loo).  F holds one line per marker,
+// "chrom<TAB>pos<TAB>contributors<TAB>mean cost<TAB>LOD": the chromosome (from 1), the position, the individuals with a
+// likelihood on that chromosome, the mean over them of the cost in nats of their data at the marker given the rest of the
+// chromosome ("%.5lf"; "-" where nobody contributes), and the LOD of the marker's own position against "off the map"; after
+// a blank line the cells whose cost is at least X nats (default 5), "name<TAB>chrom<TAB>marker<TAB>pos<TAB>cost<TAB>unlinked"
+// with the marker's map index (from 0) and the cost of the same data with the marker off the map, by individual, then
+// marker.  --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
 // has no compute path of its own and fails if no GPU is present.  Out of scope: the toulbar2
@@ -97,6 +107,9 @@ struct Options {
     bool        draws_set = false, seed_set = false;
     std::string place, place_genfile;    // --place F --place-genfile G: where the Q markers of G go on the map
     int         place_markers = 0;       // --place-markers Q
+    std::string loo;                     // --loo F: leave-one-marker-out costs of the last round's state
+    double      loo_threshold = 5.0;     // --loo-threshold X: cells at or above X nats are listed
+    bool        loo_threshold_set = false;
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
     int         remap_iterations = 1;
     bool        remap_iterations_set = false;
@@ -156,6 +169,17 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--place") o.place = val();
         else if (a == "--place-genfile") o.place_genfile = val();
         else if (a == "--place-markers") o.place_markers = atoi(val().c_str());
+        else if (a == "--loo") o.loo = val();
+        else if (a == "--loo-threshold") {
+            const std::string t = val();
+            char*             end = nullptr;
+            o.loo_threshold     = strtod(t.c_str(), &end);
+            o.loo_threshold_set = true;
+            if (t.empty() || *end != 0 || o.loo_threshold != o.loo_threshold) {
+                fprintf(stderr, "--loo-threshold needs a number, not \"%s\"\n", t.c_str());
+                exit(2);
+            }
+        }
         else if (a == "--remap") o.remap = val();
         else if (a == "--remap-iterations") {
             o.remap_iterations = atoi(val().c_str());
@@ -173,6 +197,7 @@ static void crossovers_and_remap(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
 static void viterbi_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -261,6 +286,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.viterbi.empty()) viterbi_paths(opt, P, ctx);
     if (world == 1 && !opt.sample.empty()) sample_paths(opt, P, ctx);
     if (world == 1 && !opt.place.empty()) place_markers(opt, P, ctx);
+    if (world == 1 && !opt.loo.empty()) loo_costs(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -433,6 +459,33 @@ static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.place);
 }
 
+// --loo after the last round (single GPU), like --viterbi
+static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    std::vector<double>  f((size_t)N * C * 8), ll((size_t)N * C), loo((size_t)N * M), unl((size_t)N * M), ls(M), us(M);
+    std::vector<int32_t> cnt(C);
+    if (cnf2_sweep_loo(ctx, 0, N, f.data(), ll.data(), loo.data(), unl.data(), ls.data(), us.data(), cnt.data(), 0) != CNF2_OK)
+        throw EngineError(CNF2_ERR_STATE, std::string("cnf2_sweep_loo: ") + cnf2_last_error(ctx));
+    FILE* out = fopen(opt.loo.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.loo);
+    const double ln10 = 2.30258509299404568402;
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+            if (cnt[c] > 0) fprintf(out, "%d\t%.5lf\t%d\t%.5lf\t%.5lf\n", c + 1, P.pos[m], (int)cnt[c], ls[m] / cnt[c], (us[m] - ls[m]) / ln10);
+            else fprintf(out, "%d\t%.5lf\t0\t-\t%.5lf\n", c + 1, P.pos[m], (us[m] - ls[m]) / ln10);
+        }
+    fprintf(out, "\n");
+    for (int j = 0; j < N; j++)
+        for (int c = 0; c < C; c++)
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const double v = loo[(size_t)j * M + m];
+                if (v != (double)CNF2_IGNORED && v >= opt.loo_threshold)
+                    fprintf(out, "%s\t%d\t%d\t%.5lf\t%.5lf\t%.5lf\n", P.inds[P.dous[j]].name.c_str(), c + 1, m, P.pos[m], v, unl[(size_t)j * M + m]);
+            }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.loo);
+}
+
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
 // reduce-scatter, all-gather, the hit-counter sum, a barrier and the host broadcast on the context's exchange buffer, through
 // the same entry the engine calls.  (Two ranks need two GPUs: RCCL refuses two ranks on one device.)
@@ -543,6 +596,14 @@ int main(int argc, char** argv)
     }
     if (opt.gpus > 1 && !opt.place.empty()) {
         fprintf(stderr, "--place needs a single GPU (--gpus 1): the ranks' sums are not reduced\n");
+        return 2;
+    }
+    if (opt.gpus > 1 && !opt.loo.empty()) {
+        fprintf(stderr, "--loo needs a single GPU (--gpus 1): the ranks' sums are not reduced\n");
+        return 2;
+    }
+    if (opt.loo_threshold_set && opt.loo.empty()) {
+        fprintf(stderr, "--loo-threshold needs --loo FILE\n");
         return 2;
     }
     if (opt.place.empty() != opt.place_genfile.empty() || opt.place.empty() != (opt.place_markers == 0)) {

@@ -359,6 +359,45 @@ int cnf2_sweep_place(cnf2_ctx *ctx, int ind_begin, int ind_end, int n_cand, cons
                      double *place_out, double *place_sum_out, int32_t *n_zero_out, double *null_out,
                      int32_t *n_contrib_out, uint32_t flags);
 
+/* Leave-one-marker-out: what does the data at one marker cost an individual's likelihood?  The multipoint analogue of an
+ * error LOD: it finds genotypes that imply a double crossover and markers that do not belong where the map has them.  For
+ * analysed individual i, chromosome c and marker m on c, with L_s the likelihood of shift mode s and L = sum_s L_s (loglik):
+ *   loo[i][m]      = log( sum_s L_s,-m ) - log L,  L_s,-m = mode s's likelihood with marker m's emission replaced by 1:
+ *                    the surprisal, in nats, of the window's data at m given its data at every other marker of c
+ *   unlinked[i][m] = -log( mean over the individual's analysed modes of (1/64) sum_g e_s,m(g) ): the surprisal of the same
+ *                    data with the marker off the map, the per-individual term of cnf2_sweep_place's null
+ * unlinked - loo is the log-likelihood the marker gains by sitting where the map has it; summed over individuals and divided
+ * by ln 10 it is the LOD of the marker's own position.  The sum over s runs over EVERY mode with a likelihood, not only
+ * those within the 40 log-units of the dosage rows (a marker that alone pushes a mode out of that band is what the call
+ * looks for); a mode without a likelihood on the full map contributes nothing.  The map is Haldane, so two adjacent gaps
+ * compose exactly: loo[i][m] equals loglik of cnf2_sweep with column m taken off the map (the others' positions kept) minus
+ * loglik on the full map; on a chromosome of one marker, where nothing is left, log(the modes with a likelihood) - loglik.
+ * Ties, CNF2_NO_TIES and ignoreflag2 do not enter.
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal (the same forward passes; tied windows from the tied kernel)
+ *   loo_out          [n][n_markers] or NULL
+ *   unlinked_out     [n][n_markers] or NULL; both CNF2_IGNORED where the individual is skipped on the chromosome (no mode
+ *                    with a likelihood).  Rows that are not asked for, and host rows, live whole in a buffer of the
+ *                    context (CNF2_ERR_NOMEM if it cannot be had: split the individual range)
+ *   loo_sum_out      [n_markers] the sum of loo over the individuals of the range that are not skipped
+ *   unlinked_sum_out [n_markers] likewise.  Both are reduced on the device in ascending order of the individuals, without
+ *                    atomics: the same bits on every call, and the sums of loo_out / unlinked_out added in that order
+ *   n_contrib_out    [n_chrom] (int32) individuals of the range with a likelihood on that chromosome (not skipped)
+ * Outputs are overwritten, not accumulated; a range split [a,b) + [b,c) adds up to [a,c) (sums to rounding, counts and rows
+ * exactly).  Bad arguments (a NULL pointer other than the two rows, a range out of bounds) write nothing.
+ * One pass: untied windows through the fast kernel's leave-one-out instantiation (likelihoods, then a backward pass without
+ * rows that leaves the two ratios per marker), tied windows through the tied kernel without rows (likelihoods) and then the
+ * same instantiation; a finish kernel takes the logarithms in place and reduces the columns.
+ * Flags: CNF2_OUT_DEVICE (all seven output pointers are device pointers), CNF2_STATIC_JOBS, CNF2_FULL_SPILL and
+ * CNF2_TIES_GENERAL as in cnf2_sweep_crossovers; CNF2_MERGE_MODES, CNF2_XPOSE, CNF2_FLUSH_TINY and the dosage flags are
+ * ignored.  The call synchronises the context's stream once (the job list), also with CNF2_OUT_DEVICE. */
+int cnf2_sweep_loo(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out,
+                   double *loo_out, double *unlinked_out, double *loo_sum_out, double *unlinked_sum_out,
+                   int32_t *n_contrib_out, uint32_t flags);
+/*  cnf2_loo_rows        rows_out[mc][2] = (loo, unlinked) of cnf2_sweep_loo for one individual and chromosome, from the
+ *                       store by brute force (one thread per state on slots 0, 1 and 2 with their cumulative scales): the
+ *                       cross-check of the sweep's fused form. */
+int cnf2_loo_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every
