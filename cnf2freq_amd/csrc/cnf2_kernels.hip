@@ -1281,12 +1281,18 @@ struct BwdState {
 // those bits need no exchange (transition_uniform), and a lane carries CNF2_UNI_REGS registers per vector: the two that
 // differ (register bit 0), or all 8 (A/B: the exchanges alone).  Same operations on the same numbers: the bits of the
 // ordinary instantiation.  Jobs of other windows are skipped (the ordinary instantiation skips these under KP_SKIP_UNIFORM
-// when both run over one job list).  The restricted tables do depend on those bits and are read in full.
+// when both run over one job list).  The restricted tables do depend on those bits and are read in full -- once per group of
+// four lanes that would form the same class sums (the `marker` lambda of the backward pass).
 #ifndef CNF2_UNI_REGS
 #define CNF2_UNI_REGS 2
 #endif
+// blocks per CU the UNI instantiation is compiled for (the others, and its A/B form with 8 registers a vector: 2).  3: at most
+// 168 registers a lane
+#ifndef CNF2_UNI_MIN_BLOCKS
+#define CNF2_UNI_MIN_BLOCKS 3
+#endif
 template <bool HALF, int STOREW = 0, bool XPOSE = false, bool TIED = false, bool UNI = false>
-__global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
+__global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MIN_BLOCKS : 2) void fb_fast_kernel(KernelParams p)
 {
     static_assert(!UNI || (HALF && STOREW == SW_PLAIN && !XPOSE && !TIED), "the uniform-state variant exists for the plain half-spill sweep");
     static_assert(CNF2_UNI_REGS == 2 || CNF2_UNI_REGS == 8, "registers per lane and vector of the uniform-state variant");
@@ -1865,6 +1871,28 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
             // TIED: the sums of the pair of tie combinations whose restricted tables the row holds (everything else at this
             // marker -- the posterior weights wj, the scale -- is the same for every combination)
             // (no rows asked for: no class sums, no restricted tables, no epilogue)
+            // UNI, two registers: the four B-side class sums below (sb and sb1 for f = 0, 1) depend on the lane only through
+            // its chain and state bit 0 -- wj does not depend on state bits 1 and 2, the tables are indexed by (f, s2, j) --
+            // so the four lanes of a chain that share bit 0 would form the same four sums.  Lane kq (its state bits 1 and 2)
+            // forms sum kq alone, the same multiply-adds on the same operands, and fetches the other three: cs[t] is sum
+            // t = 2 f + (TAB_2 ? 1 : 0).  Every lane takes part, whatever its chain holds.
+            double cs[4];
+            if constexpr (UNI && NR == 2) {
+                const int     kq = (c.lo >> 1) & 3;
+                const double* Bk = row + ((kq & 1) ? TAB_2 : TAB_R) + ((1 << 5) | ((kq >> 1) << 4) | (c.s2 << 3));
+                double        z  = 0.0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) z += wj[j & 1] * Bk[j];
+                // the pair (sums kq & 2 and kq & 2 | 1) first, then the other pair from the lane across state bit 2
+                const bool   b0 = (kq & 1) != 0, b1 = (kq & 2) != 0;
+                const double z1 = lane_flip_b1(z);
+                const double pe = b0 ? z1 : z, po = b0 ? z : z1;
+                const double qe = lane_flip_b2(pe), qo = lane_flip_b2(po);
+                cs[0] = b1 ? qe : pe;
+                cs[1] = b1 ? qo : po;
+                cs[2] = b1 ? pe : qe;
+                cs[3] = b1 ? po : qo;
+            }
 #pragma unroll 1
             for (int ko = 0; ko < (!ROWS ? 0 : (TIED ? 2 * TIE_KOFF : 1)); ko += TIE_KOFF)
 #pragma unroll
@@ -1879,10 +1907,15 @@ __global__ __launch_bounds__(CNF2_BLOCK, 2) void fb_fast_kernel(KernelParams p)
                 const double  cf = row[TAB_C + f * 2 + c.s0];
                 const double  av = cf * row[ko + TAB_R + ia], a1 = cf * row[ko + TAB_2 + ia];
                 double        sb = 0.0, sb1 = 0.0;
+                if constexpr (UNI && NR == 2) {
+                    sb  = cs[2 * f];
+                    sb1 = cs[2 * f + 1];
+                } else {
 #pragma unroll
-                for (int j = 0; j < 8; j++) {      // (NR = 2: the weights repeat over register bits 1 and 2, the restricted tables do not)
-                    sb += wj[j & (NR - 1)] * Br[j];
-                    sb1 += wj[j & (NR - 1)] * B1[j];
+                    for (int j = 0; j < 8; j++) {
+                        sb += wj[j] * Br[j];
+                        sb1 += wj[j] * B1[j];
+                    }
                 }
                 n_tot += av * sb;
                 n_a1 += a1 * sb;
