@@ -43,7 +43,7 @@ SYMBOLS = [
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
-    "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows",
+    "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
 ]
 
 
@@ -112,6 +112,8 @@ def load():
         L.cnf2_sweep_place.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_loo.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_loo_rows.argtypes = [vp, i32, i32, vp]
+        L.cnf2_sweep_origins.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_origin_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -479,6 +481,45 @@ class Context:
                                         C.c_void_p(d_unlinked) if d_unlinked else None, C.c_void_p(d_loo_sum),
                                         C.c_void_p(d_unlinked_sum), C.c_void_p(d_n_contrib), flags | OUT_DEVICE),
                   "cnf2_sweep_loo")
+
+    def origin_rows(self, ind, chrom=0):
+        """[mc][10] = origin[4], bits[6] of one individual and chromosome from the alpha/beta store, brute force (the
+        cross-check of sweep_origins); zeros where the individual is skipped."""
+        mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])
+        v = np.zeros((mc, 10))
+        self._chk(self.L.cnf2_origin_rows(self.h, ind, chrom, _p(v)), "cnf2_origin_rows")
+        return v
+
+    def sweep_origins(self, ind_begin=0, ind_end=None, rows=True, full_spill=False, ties_general=False, static_jobs=False,
+                      all_states=False):
+        """cnf2_sweep_origins: factors / loglik as sweep(); origin[n][M][4], the probabilities that the alleles from the
+        first and the second parent descend from those parents' (first, first), (second, first), (first, second) and
+        (second, second) parent -- AA, BA, AB, BB by side in an F2 whose F1s list line A first -- and bits[n][M][6],
+        P(meiosis bit t = 1) (both all zero where skipped; None with rows=False); origin_sum[M][4], their sum over the
+        range's individuals, and the contributing individuals per chromosome.  The frame is absolute (include/cnf2hip.h).
+        cnf2freq_amd/origins.py reads them.  all_states (CNF2_ALL_STATES) is accepted and changes nothing."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        origin = np.zeros((n, self.n_markers, 4)) if rows else None
+        bits = np.zeros((n, self.n_markers, 6)) if rows else None
+        osum = np.zeros((self.n_markers, 4))
+        cnt = np.zeros(self.n_chrom, np.int32)
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0))
+        self._chk(self.L.cnf2_sweep_origins(self.h, ind_begin, ind_end, _p(factors), _p(loglik),
+                                            _p(origin) if rows else None, _p(bits) if rows else None, _p(osum), _p(cnt),
+                                            flags), "cnf2_sweep_origins")
+        return dict(factors=factors, loglik=loglik, origin=origin, bits=bits, origin_sum=osum, n_contrib=cnt)
+
+    def sweep_origins_device(self, ind_begin, ind_end, d_factors, d_loglik, d_origin, d_bits, d_origin_sum, d_n_contrib,
+                             flags=0):
+        """Device-pointer form (ints; d_origin / d_bits may be None: the rows then stay in the context)."""
+        self._chk(self.L.cnf2_sweep_origins(self.h, ind_begin, ind_end, C.c_void_p(d_factors), C.c_void_p(d_loglik),
+                                            C.c_void_p(d_origin) if d_origin else None,
+                                            C.c_void_p(d_bits) if d_bits else None, C.c_void_p(d_origin_sum),
+                                            C.c_void_p(d_n_contrib), flags | OUT_DEVICE), "cnf2_sweep_origins")
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

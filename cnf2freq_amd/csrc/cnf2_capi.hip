@@ -131,6 +131,11 @@ struct cnf2_ctx {
     DevBuf<double>  d_loo, d_unl;         // [n][n_markers]
     DevBuf<double>  d_loo_sum, d_unl_sum; // [n_markers]
 
+    // origin rows (cnf2_sweep_origins): the rows a call did not hand device memory for, and its staged sums
+    DevBuf<double>  d_org;                // [n][n_markers][4]
+    DevBuf<double>  d_obits;              // [n][n_markers][6]
+    DevBuf<double>  d_org_sum;            // [n_markers][4]
+
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
     DevBuf<double2> d_pl_sure;
@@ -640,14 +645,17 @@ static JobPlan job_plan(const cnf2_ctx* ctx, int ind_begin, int n, uint32_t flag
 
 // What a sweep leaves besides the likelihoods: its mode with that mode's device outputs
 struct SweepMode {
-    SweepVariant variant = SW_PLAIN;   // SW_PLAIN (cnf2_sweep: the rows), SW_CROSSOVERS, SW_VITERBI, SW_SAMPLING or SW_LOO
+    SweepVariant variant = SW_PLAIN;   // SW_PLAIN (cnf2_sweep: the rows), SW_CROSSOVERS, SW_VITERBI, SW_SAMPLING, SW_LOO or SW_ORIGINS
     // SW_CROSSOVERS (cnf2_sweep_crossovers)
     double*  xo = nullptr;             // [n][n_markers][6] or null
     double*  xo_sum = nullptr;         // [n_markers][6], zeroed by the caller
-    int32_t* xo_cnt = nullptr;         // [n_chrom], zeroed by the caller (SW_LOO too)
+    int32_t* xo_cnt = nullptr;         // [n_chrom], zeroed by the caller (SW_LOO and SW_ORIGINS too)
     // SW_LOO (cnf2_sweep_loo): what the sweep leaves for loo_finish_kernel
     double*  loo = nullptr;            // [n][n_markers]
     double*  unl = nullptr;            // [n][n_markers]
+    // SW_ORIGINS (cnf2_sweep_origins)
+    double*  org = nullptr;            // [n][n_markers][4]
+    double*  obits = nullptr;          // [n][n_markers][6]
     // SW_VITERBI (cnf2_sweep_viterbi) and, with a leading [K] of draws per individual, SW_SAMPLING (cnf2_sweep_sample)
     uint8_t* state = nullptr;          // [n][n_markers]
     int32_t* shift = nullptr;          // [n][n_chrom]
@@ -662,8 +670,8 @@ struct SweepMode {
 // forms them) and then the general kernel's crossover instantiation (their posteriors).  Viterbi mode: the same routing,
 // with the fast kernel's Viterbi instantiation in place of both crossover instantiations.  Sampling mode: the untied windows
 // through the fast kernel's sampling instantiation (one pass: likelihoods and draws), the tied ones through the tied kernel
-// without rows (likelihoods) and then the same sampling instantiation (draws).  Leave-one-out mode: sampling's routing with
-// the fast kernel's leave-one-out instantiation
+// without rows (likelihoods) and then the same sampling instantiation (draws).  Leave-one-out and origin mode: sampling's
+// routing with the fast kernel's leave-one-out / origin instantiation
 static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
                       uint32_t flags, const SweepMode& mode)
 {
@@ -773,6 +781,13 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         p.xo_cnt = mode.xo_cnt;
         follow_per_cu = ctx->fast_blocks_per_cu;
         break;
+    case SW_ORIGINS:
+        p.flags  = KP_NO_DOSAGE;    // (no rows; the instantiation makes its backward pass all the same)
+        p.org    = mode.org;
+        p.obits  = mode.obits;
+        p.xo_cnt = mode.xo_cnt;
+        follow_per_cu = ctx->fast_blocks_per_cu;
+        break;
     default: break;
     }
     if (flags & CNF2_LOG_PATHS) {
@@ -809,8 +824,8 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         else HIP_TRY(ctx, launch_fb_fast(pt, grid_gen, {SW_PLAIN, true, false, true}, ctx->stream2));
         if (!plain) {
             // the mode's instantiation over the tied jobs in the same spill slots (after the pass above on this stream): the
-            // general kernel's for the crossovers; the fast kernel's for Viterbi, sampling and leave-one-out (the forward
-            // pass, the max-product recursion, the draws and alpha beta do not see the tie rule).  Its own likelihoods go to
+            // general kernel's for the crossovers; the fast kernel's for Viterbi, sampling, leave-one-out and origins (the
+            // forward pass, the max-product recursion, the draws and alpha beta do not see the tie rule).  Its own likelihoods go to
             // scratch (the ones reported are the tied kernel's); its occupancy is its own
             KernelParams px = pt;
             likelihoods_to_scratch(&px);
@@ -1134,6 +1149,53 @@ int cnf2_sweep_loo(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_ou
     RC_TRY(fetch_out(ctx, n_contrib_out, m.xo_cnt, C));
     if (loo_out) RC_TRY(fetch_out(ctx, loo_out, m.loo, nr));
     if (unlinked_out) RC_TRY(fetch_out(ctx, unlinked_out, m.unl, nr));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+int cnf2_origin_rows(cnf2_ctx* ctx, int ind, int chrom, double* rows_out)
+{
+    if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad origin_rows arguments");
+    return stage2_rows(ctx, ind, chrom, 10, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_origin_rows(q, d_out, ctx->stream); });
+}
+
+// one pass of sweep_impl's origin mode, then origin_finish_kernel on the context's stream: the column sums (an empty range
+// reports them as zeros).  The rows the caller gave no device memory for live in the context's own buffers
+int cnf2_sweep_origins(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* origin_out,
+                       double* bits_out, double* origin_sum_out, int32_t* n_contrib_out, uint32_t flags)
+{
+    RC_TRY(ready(ctx));
+    if (!factors_out || !loglik_out || !origin_sum_out || !n_contrib_out)
+        return fail(ctx, CNF2_ERR_ARG, "only origin_out and bits_out may be NULL");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    n = ind_end - ind_begin;
+    const size_t M = ctx->n_markers, C = ctx->n_chrom, nr = (size_t)n * M;
+    SweepMode    m;
+    m.variant = SW_ORIGINS;
+    double* d_sum;
+    RC_TRY(stage_out(ctx, dev, origin_sum_out, ctx->d_org_sum, M * 4, &d_sum));
+    RC_TRY(stage_out(ctx, dev, n_contrib_out, ctx->d_xo_cnt, C, &m.xo_cnt));
+    m.org   = (dev && origin_out) ? origin_out : nullptr;
+    m.obits = (dev && bits_out) ? bits_out : nullptr;
+    if (!m.org && nr > 0) {
+        RC_TRY(ctx->d_org.ensure(ctx, nr * 4));
+        m.org = ctx->d_org;
+    }
+    if (!m.obits && nr > 0) {
+        RC_TRY(ctx->d_obits.ensure(ctx, nr * 6));
+        m.obits = ctx->d_obits;
+    }
+    RC_TRY(mode_sweep(ctx, ind_begin, ind_end, factors_out, loglik_out, flags & ~(uint32_t)CNF2_ALL_STATES, m));
+    launch_origin_finish(m.org, n, (int)M, d_sum, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));       // (the timed span of cnf2_last_kernel_ms covers the finish)
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, origin_sum_out, d_sum, M * 4));
+    RC_TRY(fetch_out(ctx, n_contrib_out, m.xo_cnt, C));
+    if (origin_out) RC_TRY(fetch_out(ctx, origin_out, m.org, nr * 4));
+    if (bits_out) RC_TRY(fetch_out(ctx, bits_out, m.obits, nr * 6));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
 }

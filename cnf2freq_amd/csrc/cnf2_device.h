@@ -33,9 +33,12 @@ enum SweepVariant : int {
     SW_SAMPLING     = 6,   // whole paths drawn from the posterior, one draw per lane (p.smp_*); no beta, no rows
     SW_POSTERIOR    = 7,   // placement mode: the state posteriors gamma = wg e of every marker into p.wbuf (SW_WEIGHTS' row and
                            // layout), the jobs with a likelihood counted in p.xo_cnt; no rows
-    SW_LOO          = 8    // leave-one-marker-out mode: per marker the likelihood ratio without the marker's emission (p.loo) and
+    SW_LOO          = 8,   // leave-one-marker-out mode: per marker the likelihood ratio without the marker's emission (p.loo) and
                            // the marker's unlinked emission mean (p.unl), over every mode with a likelihood; the jobs with a
                            // likelihood counted in p.xo_cnt; no rows
+    SW_ORIGINS      = 9    // origin mode: per marker the four grandparental-origin probabilities (p.org) and P(bit t = 1) of the
+                           // six meiosis bits (p.obits), masked sums of the state posterior over the modes the rows count; the
+                           // jobs with a likelihood counted in p.xo_cnt; no rows
 };
 
 struct KernelParams {
@@ -100,6 +103,8 @@ struct KernelParams {
                                // loo_finish_kernel takes the logarithm in place
     double*        unl;        // leave-one-out mode: [n_ind][n_markers] mean over the analysed modes of (1/64) sum_g e_s,m(g),
                                // likewise (-1: skipped); minus its logarithm after loo_finish_kernel
+    double*        org;        // origin mode: [n_ind][n_markers][4] P(bit 0 + 2 bit 3 = k), each row summing to 1 (0: skipped)
+    double*        obits;      // origin mode: [n_ind][n_markers][6] P(bit t = 1) (0: skipped)
 };
 #define CNF2_LEXP_IGNORED (-2147483647 - 1)   /* shift mode not analysed: CNF2_IGNORED_D */
 #define CNF2_LEXP_DEAD    (-2147483647)       /* no likelihood left: CNF2_MINFACTOR_F */
@@ -240,6 +245,12 @@ void launch_loo_rows(const Stage2Params& q, double* out, hipStream_t stream);
 // in place (CNF2_IGNORED where skipped); loo_sum / unl_sum [n_markers] = their sums over the n_ind individuals in ascending
 // order, one thread per marker (no atomics: the same bits on every call)
 void launch_loo_finish(double* loo, double* unl, int n_ind, int n_markers, double* loo_sum, double* unl_sum, hipStream_t stream);
+// out[len][10] = origin[4], bits[6] of cnf2_sweep_origins from the store, brute force
+void launch_origin_rows(const Stage2Params& q, double* out, hipStream_t stream);
+// org_sum [n_markers][4] = the origin rows an origin sweep (SW_ORIGINS) left in org [n_ind][n_markers][4], added over the n_ind
+// individuals in ascending order, one thread per column (no atomics: the same bits on every call; a skipped individual's
+// rows are zeros)
+void launch_origin_finish(const double* org, int n_ind, int n_markers, double* org_sum, hipStream_t stream);
 // Which instantiation of fb_fast_kernel a launch takes.  half: alpha-minus spilled at every second marker (not
 // CNF2_FULL_SPILL); xpose: the transposing variant of the plain sweep; tied: the tile producer with a pass per tie
 // combination (windows with tie groups).  SW_WEIGHTS forms no per-locus rows: windows with tie groups can take it untied

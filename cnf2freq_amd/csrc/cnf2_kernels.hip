@@ -1299,7 +1299,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
     constexpr int  NR   = UNI ? CNF2_UNI_REGS : 8;      // registers per lane and vector
     constexpr bool PAIR = HALF && STOREW == SW_PLAIN && !XPOSE && !TIED && !UNI;    // the instantiation UNI may run beside
     static_assert(!XPOSE || (HALF && STOREW == SW_PLAIN), "the transposing variant exists for the plain half-spill sweep");
-    // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_LOO); by value:
+    // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_ORIGINS); by value:
     // STOREW: 0 plain sweep; 1 accumulate mode (also stores the posterior weights wg); 2 turn-scan mode (stores alpha e, beta
     // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only); 4 crossover
     // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows);
@@ -1309,13 +1309,18 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
     // lane: p.smp_state / p.smp_shift / p.smp_logp; no beta, no rows); 7 placement mode (stores the state posteriors
     // gamma = wg e of every marker where the accumulate mode stores wg; counts the jobs with a likelihood in p.xo_cnt; no rows);
     // 8 leave-one-out mode (per marker sum_s L_s,-m / L over every mode with a likelihood and the marker's unlinked emission
-    // mean into p.loo / p.unl, their logarithms left to loo_finish_kernel; counts the jobs with a likelihood in p.xo_cnt; no rows)
+    // mean into p.loo / p.unl, their logarithms left to loo_finish_kernel; counts the jobs with a likelihood in p.xo_cnt; no rows);
+    // 9 origin mode (per marker eight masked sums of the state posterior gamma = wg e over the modes the rows count, normalised
+    // by their total: the four origin cells into p.org, P(bit t = 1) into p.obits; counts the jobs with a likelihood in
+    // p.xo_cnt; no rows)
     constexpr bool ROWS = STOREW == SW_PLAIN || STOREW == SW_WEIGHTS_ROWS;      // class sums, restricted tables, tile epilogue, p.dosage
     constexpr bool WG   = STOREW == SW_WEIGHTS_ROWS || STOREW == SW_WEIGHTS;
     constexpr bool VIT  = STOREW == SW_VITERBI;
     constexpr bool SMP  = STOREW == SW_SAMPLING;
     constexpr bool POST = STOREW == SW_POSTERIOR;
     constexpr bool LOO  = STOREW == SW_LOO;
+    constexpr bool ORG  = STOREW == SW_ORIGINS;
+    static_assert(!ORG || (!XPOSE && !TIED), "the origin mode is an instantiation of the untied DPP kernel");
     static_assert(!LOO || (!XPOSE && !TIED), "the leave-one-out mode is an instantiation of the untied DPP kernel");
     static_assert(!POST || (!XPOSE && !TIED), "the placement mode is an instantiation of the untied DPP kernel");
     static_assert(!VIT || (!XPOSE && !TIED), "the Viterbi mode is an instantiation of the untied DPP kernel");
@@ -1542,7 +1547,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
                 p.lexp[e]   = any_alive ? emax : CNF2_LEXP_DEAD;
             }
         }
-        if ((STOREW == 4 || POST || LOO) && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
+        if ((STOREW == 4 || POST || LOO || ORG) && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
         if (VIT) {
             // ------------------------------------------------------------ Viterbi: logmax, MAP mode, backtrace
             // logmax_s = log(max-product) + the chromosome's dropped butterfly constants, as likelihood_logs_kernel finishes
@@ -1747,9 +1752,18 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
             }
             continue;
         }
-        // (the leave-one-out mode forms no rows and is launched for its backward pass: it runs with KP_NO_DOSAGE, as the
-        // general kernel's crossover instantiation does)
-        if (!LOO && (p.flags & KP_NO_DOSAGE)) continue;
+        // (the leave-one-out and origin modes form no rows and are launched for their backward pass: they run with
+        // KP_NO_DOSAGE, as the general kernel's crossover instantiation does)
+        if (!LOO && !ORG && (p.flags & KP_NO_DOSAGE)) continue;
+        if (ORG && !any_alive) {
+            // skipped, as the sweep skips it: all-zero rows, as the dosage rows are (origin_finish_kernel adds them as they are)
+            double* og = p.org + ((size_t)jb.ind * p.n_markers + first) * 4;
+            double* ob = p.obits + ((size_t)jb.ind * p.n_markers + first) * 6;
+            const int len = last - first + 1;
+            for (int k = lane; k < len * 4; k += 64) og[k] = 0.0;
+            for (int k = lane; k < len * 6; k += 64) ob[k] = 0.0;
+            continue;
+        }
         if (LOO && !any_alive) {
             // skipped, as the sweep skips it: both rows marked for loo_finish_kernel (CNF2_IGNORED, left out of the sums)
             double* lo = p.loo + (size_t)jb.ind * p.n_markers + first;
@@ -2038,6 +2052,48 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
                     p.unl[o] = tot * loo_k;
                 }
             }
+            if constexpr (ORG) {
+                // origin mode: gamma(s, g) = wg e as the placement mode stores it, summed here instead.  The register index j is
+                // state bits 3-5, c.lo the lane's state bits 0-2 (state_lo, not the raw lane number).  A lane's four sums over
+                // its registers: all of them, and those with bit 3, 4, 5 set; bits 0-2 select per lane.  Eight reductions over
+                // the wave; the total of the four cells is the weight of the modes the rows count, and dividing by it is the
+                // definition's renormalisation over those modes
+                double gs = 0.0, g3 = 0.0, g4 = 0.0, g5 = 0.0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const double g = scale != 0.0 ? scale * wj[j] * e[j] : 0.0;    // (a chain that is off: 0, whatever it holds)
+                    gs += g;
+                    if (j & 1) g3 += g;
+                    if (j & 2) g4 += g;
+                    if (j & 4) g5 += g;
+                }
+                const bool   b0 = (c.lo & 1) != 0, b1 = (c.lo & 2) != 0, b2 = (c.lo & 4) != 0;
+                const double g03 = gs - g3;
+                const double k0 = across_chains_sum(chain_sum(b0 ? 0.0 : g03));
+                const double k1 = across_chains_sum(chain_sum(b0 ? g03 : 0.0));
+                const double k2 = across_chains_sum(chain_sum(b0 ? 0.0 : g3));
+                const double k3 = across_chains_sum(chain_sum(b0 ? g3 : 0.0));
+                const double t1 = across_chains_sum(chain_sum(b1 ? gs : 0.0));
+                const double t2 = across_chains_sum(chain_sum(b2 ? gs : 0.0));
+                const double t4 = across_chains_sum(chain_sum(g4));
+                const double t5 = across_chains_sum(chain_sum(g5));
+                if (lane == 0) {
+                    const double tot = (k0 + k1) + (k2 + k3);
+                    const double inv = tot > 0.0 ? 1.0 / tot : 0.0;
+                    double*      og  = p.org + ((size_t)jb.ind * p.n_markers + m) * 4;
+                    double*      ob  = p.obits + ((size_t)jb.ind * p.n_markers + m) * 6;
+                    og[0] = k0 * inv;
+                    og[1] = k1 * inv;
+                    og[2] = k2 * inv;
+                    og[3] = k3 * inv;
+                    ob[0] = (k1 + k3) * inv;
+                    ob[1] = t1 * inv;
+                    ob[2] = t2 * inv;
+                    ob[3] = (k2 + k3) * inv;
+                    ob[4] = t4 * inv;
+                    ob[5] = t5 * inv;
+                }
+            }
             if constexpr (POST) {
                 // placement mode: gamma(s, g) = wg e, the posterior of state g in mode s at this marker, where the accumulate
                 // mode stores wg (same row, same layout); sums to the weight of the modes the rows count
@@ -2280,6 +2336,23 @@ void launch_loo_finish(double* loo, double* unl, int n_ind, int n_markers, doubl
     if (n_markers > 0)
         hipLaunchKernelGGL(loo_finish_kernel, dim3((n_markers + 255) / 256), dim3(256), 0, stream, loo, unl, n_ind, n_markers,
                            loo_sum, unl_sum);
+}
+
+// The column sums of an origin sweep's rows: thread t is column t of [n_markers][4] and walks the individuals in ascending
+// order -- coalesced across columns, and sums that are the same bits on every call.  A skipped individual's rows are zeros.
+__global__ __launch_bounds__(256) void origin_finish_kernel(const double* org, int n_ind, int n_cols, double* org_sum)
+{
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_cols) return;
+    double s = 0.0;
+    for (int i = 0; i < n_ind; i++) s += org[(size_t)i * n_cols + t];
+    org_sum[t] = s;
+}
+void launch_origin_finish(const double* org, int n_ind, int n_markers, double* org_sum, hipStream_t stream)
+{
+    const int n_cols = n_markers * 4;
+    if (n_cols > 0)
+        hipLaunchKernelGGL(origin_finish_kernel, dim3((n_cols + 255) / 256), dim3(256), 0, stream, org, n_ind, n_cols, org_sum);
 }
 
 // =====================================================================================
@@ -2913,6 +2986,39 @@ __global__ __launch_bounds__(64) void loo_rows_kernel(Stage2Params q, double* ou
         out[(size_t)ml * 2 + 0] = skip ? CNF2_IGNORED_D : log(acc);
         out[(size_t)ml * 2 + 1] = skip ? CNF2_IGNORED_D : -log(tot / (64.0 * n_on));
     }
+}
+
+
+// The origin rows from the store, brute force (the cross-check of the sweep's origin mode): one block per marker ml, thread g.
+// gamma(g) = sum_s w_s gamma_s(g) / sum_s w_s with gamma_s = slot 2 (alpha after the emission) x slot 1 (beta) normalised
+// within the mode and w_s = exp(factors[s] - factor), over the analysed modes with a likelihood that are not 40 below the
+// total; then the ten masked sums.  out[len][10] = origin[4], bits[6]; zeros where no mode has a likelihood.
+__global__ __launch_bounds__(64) void origin_rows_kernel(Stage2Params q, double* out)
+{
+    const int    g  = threadIdx.x;
+    const int    ml = blockIdx.x;
+    const Window w  = q.kp.windows[0];
+    const double factor = q.loglik[0];
+    double acc = 0.0, wsum = 0.0;
+    for (int s = 0; s < 8; s++) {
+        if ((s & w.shiftignore) || s >= w.shiftend) continue;
+        const double fs = q.factors[s];
+        if (!(fs > (double)CNF2_MINFACTOR_F) || factor - fs > 40.0) continue;
+        const double gam = s2_fw(q, s, ml, 2, g) * s2_fw(q, s, ml, 1, g);
+        const double own = across_chains_sum(chain_sum(gam));
+        if (!(own > 0.0)) continue;
+        const double ws = exp(fs - factor);
+        acc += ws * (gam / own);
+        wsum += ws;
+    }
+    const bool   skip = !(wsum > 0.0) || isnan(factor);
+    const double ga = skip ? 0.0 : acc / wsum;
+    auto total = [&](bool on) { return across_chains_sum(chain_sum(on ? ga : 0.0)); };
+    double r[10];
+    for (int k = 0; k < 4; k++) r[k] = total(((g & 1) | ((g >> 2) & 2)) == k);
+    for (int t = 0; t < 6; t++) r[4 + t] = total(((g >> t) & 1) != 0);
+    if (g == 0)
+        for (int k = 0; k < 10; k++) out[(size_t)ml * 10 + k] = r[k];
 }
 
 
@@ -4536,7 +4642,7 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     KernelParams po = p;
     if (n_uni > 0) po.flags |= KP_SKIP_UNIFORM;
     zero_job_counter(po, stream);
-    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the eighteen instantiations there are (and UNI above)
+    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the twenty instantiations there are (and UNI above)
     case fast_key(SW_PLAIN, true): launch_fast_as<true, SW_PLAIN>(po, grid, stream); break;
     case fast_key(SW_PLAIN, false): launch_fast_as<false, SW_PLAIN>(p, grid, stream); break;
     case fast_key(SW_PLAIN, true, true): launch_fast_as<true, SW_PLAIN, true>(p, grid, stream); break;
@@ -4555,6 +4661,8 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     case fast_key(SW_POSTERIOR, false): launch_fast_as<false, SW_POSTERIOR>(p, grid, stream); break;
     case fast_key(SW_LOO, true): launch_fast_as<true, SW_LOO>(p, grid, stream); break;
     case fast_key(SW_LOO, false): launch_fast_as<false, SW_LOO>(p, grid, stream); break;
+    case fast_key(SW_ORIGINS, true): launch_fast_as<true, SW_ORIGINS>(p, grid, stream); break;
+    case fast_key(SW_ORIGINS, false): launch_fast_as<false, SW_ORIGINS>(p, grid, stream); break;
     default: return hipErrorInvalidValue;
     }
     launch_likelihood_logs(p, stream);
@@ -5163,6 +5271,11 @@ void launch_crossover_rows(const Stage2Params& q, double* out, hipStream_t strea
 void launch_loo_rows(const Stage2Params& q, double* out, hipStream_t stream)
 {
     hipLaunchKernelGGL(loo_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
+}
+
+void launch_origin_rows(const Stage2Params& q, double* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(origin_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
 }
 
 void launch_emission(const KernelParams& p, int ind, int marker, double* out, hipStream_t stream)

@@ -35,6 +35,24 @@ static int guarded(F&& f)
     }
 }
 
+// context, engine and upload of a run whose pedigree is filled; deletes the run where that fails
+static cnf2h_run* start(cnf2h_run* run, int device, int quiet)
+{
+    if (cnf2_ctx_create(device, &run->ctx) != CNF2_OK) {
+        g_err = cnf2_last_error(nullptr);
+        delete run;
+        return nullptr;
+    }
+    EngineOptions eo;
+    eo.quiet = quiet != 0;
+    run->E = new Engine(run->P, run->ctx, eo);
+    if (guarded([&] { run->E->upload(); }) != 0) {
+        cnf2h_destroy(run);
+        return nullptr;
+    }
+    return run;
+}
+
 extern "C" {
 
 const char* cnf2h_last_error(void) { return g_err.c_str(); }
@@ -83,19 +101,39 @@ cnf2h_run* cnf2h_create_on(int device, int n_rec, const int32_t* par, const uint
     }
     for (int r = 0; r < n_rec; r++) P.index[P.inds[r].name] = r;
     P.dous.assign(dous, dous + n_dous);
-    if (cnf2_ctx_create(device, &run->ctx) != CNF2_OK) {
-        g_err = cnf2_last_error(nullptr);
-        delete run;
+    return start(run, device, quiet);
+}
+
+cnf2h_run* cnf2h_create_from_files(int device, const char* mapfile, const char* pedfile, const char* genfile, int quiet)
+{
+    if (!mapfile || !pedfile || !genfile) {
+        g_err = "bad arguments";
         return nullptr;
     }
-    EngineOptions eo;
-    eo.quiet = quiet != 0;
-    run->E = new Engine(P, run->ctx, eo);
-    if (guarded([&] { run->E->upload(); }) != 0) {
-        cnf2h_destroy(run);
-        return nullptr;
+    cnf2h_run* run = new cnf2h_run();
+    bool (*const readers[3])(FILE*, Pedigree&) = {read_alpha_map, read_alpha_ped, read_alpha_gen};
+    const char* const paths[3] = {mapfile, pedfile, genfile};
+    for (int k = 0; k < 3; k++) {
+        FILE* f = fopen(paths[k], "rt");
+        const bool ok = f && readers[k](f, run->P);
+        if (f) fclose(f);
+        if (!ok) {
+            g_err = std::string("cannot read ") + paths[k];
+            delete run;
+            return nullptr;
+        }
     }
-    return run;
+    return start(run, device, quiet);
+}
+
+int cnf2h_get_dims(cnf2h_run* run, int32_t* out4)
+{
+    if (!run || !out4) return -2;
+    out4[0] = (int32_t)run->P.inds.size();
+    out4[1] = run->P.n_markers();
+    out4[2] = (int32_t)run->P.chromstarts.size() - 1;
+    out4[3] = (int32_t)run->P.dous.size();
+    return 0;
 }
 
 void cnf2h_destroy(cnf2h_run* run)

@@ -2,7 +2,7 @@
 // (demo.sh:37):
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
 //            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
-//            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]]
+//            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]] [--origins F]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -53,6 +53,14 @@
 // a blank line the cells whose cost is at least X nats (default 5), "name<TAB>chrom<TAB>marker<TAB>pos<TAB>cost<TAB>unlinked"
 // with the marker's map index (from 0) and the cost of the same data with the marker off the map, by individual, then
 // marker.  --output is the same with or without it.  Single GPU only.
+//
+// --origins F (not a flag of the reference): after the last round, and before a --remap changes the map, the grandparental
+// origin probabilities of the last round's state (cnf2_sweep_origins).  Per chromosome and analysed individual a header
+// "name:chrom", then one line per marker of the four probabilities ("%.6lf", tab separated, k = 0..3: the alleles from the
+// first / second parent descend from those parents' first-first, second-first, first-second, second-second parent; four
+// "-" where the individual is skipped on the chromosome), then a blank line.  After the last individual one line per marker,
+// "chrom<TAB>pos<TAB>contributors<TAB>" and the four column sums ("%.5lf"): the expected class counts.  --output is the
+// same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
 // has no compute path of its own and fails if no GPU is present.  Out of scope: the toulbar2
@@ -110,6 +118,7 @@ struct Options {
     std::string loo;                     // --loo F: leave-one-marker-out costs of the last round's state
     double      loo_threshold = 5.0;     // --loo-threshold X: cells at or above X nats are listed
     bool        loo_threshold_set = false;
+    std::string origins;                 // --origins F: grandparental origin probabilities of the last round's state
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
     int         remap_iterations = 1;
     bool        remap_iterations_set = false;
@@ -180,6 +189,7 @@ static bool parse(int argc, char** argv, Options& o)
                 exit(2);
             }
         }
+        else if (a == "--origins") o.origins = val();
         else if (a == "--remap") o.remap = val();
         else if (a == "--remap-iterations") {
             o.remap_iterations = atoi(val().c_str());
@@ -198,6 +208,7 @@ static void viterbi_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -287,6 +298,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.sample.empty()) sample_paths(opt, P, ctx);
     if (world == 1 && !opt.place.empty()) place_markers(opt, P, ctx);
     if (world == 1 && !opt.loo.empty()) loo_costs(opt, P, ctx);
+    if (world == 1 && !opt.origins.empty()) origin_rows(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -486,6 +498,34 @@ static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.loo);
 }
 
+// --origins after the last round (single GPU), like --viterbi
+static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    std::vector<double>  f((size_t)N * C * 8), ll((size_t)N * C), og((size_t)N * M * 4), os((size_t)M * 4);
+    std::vector<int32_t> cnt(C);
+    if (cnf2_sweep_origins(ctx, 0, N, f.data(), ll.data(), og.data(), nullptr, os.data(), cnt.data(), 0) != CNF2_OK)
+        throw EngineError(CNF2_ERR_STATE, std::string("cnf2_sweep_origins: ") + cnf2_last_error(ctx));
+    FILE* out = fopen(opt.origins.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.origins);
+    for (int c = 0; c < C; c++)
+        for (int j = 0; j < N; j++) {
+            fprintf(out, "%s:%d\n", P.inds[P.dous[j]].name.c_str(), c + 1);
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const double* r = &og[((size_t)j * M + m) * 4];
+                // (a skipped individual's rows are all zero; every other row sums to 1)
+                if (r[0] == 0.0 && r[1] == 0.0 && r[2] == 0.0 && r[3] == 0.0) fprintf(out, "-\t-\t-\t-\n");
+                else fprintf(out, "%.6lf\t%.6lf\t%.6lf\t%.6lf\n", r[0], r[1], r[2], r[3]);
+            }
+            fprintf(out, "\n");
+        }
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++)
+            fprintf(out, "%d\t%.5lf\t%d\t%.5lf\t%.5lf\t%.5lf\t%.5lf\n", c + 1, P.pos[m], (int)cnt[c], os[(size_t)m * 4], os[(size_t)m * 4 + 1],
+                    os[(size_t)m * 4 + 2], os[(size_t)m * 4 + 3]);
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.origins);
+}
+
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
 // reduce-scatter, all-gather, the hit-counter sum, a barrier and the host broadcast on the context's exchange buffer, through
 // the same entry the engine calls.  (Two ranks need two GPUs: RCCL refuses two ranks on one device.)
@@ -600,6 +640,10 @@ int main(int argc, char** argv)
     }
     if (opt.gpus > 1 && !opt.loo.empty()) {
         fprintf(stderr, "--loo needs a single GPU (--gpus 1): the ranks' sums are not reduced\n");
+        return 2;
+    }
+    if (opt.gpus > 1 && !opt.origins.empty()) {
+        fprintf(stderr, "--origins needs a single GPU (--gpus 1): the ranks' sums are not reduced\n");
         return 2;
     }
     if (opt.loo_threshold_set && opt.loo.empty()) {

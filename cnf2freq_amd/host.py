@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # CNF2HOST_LIB: a copy of the host library next to another build of libcnf2hip.so (kernel A/B timing: it binds the libcnf2hip.so of its own directory)
 LIB_PATH = os.environ.get("CNF2HOST_LIB") or os.path.join(_HERE, "libcnf2host.so")
 
-SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_destroy", "cnf2h_last_error", "cnf2h_postmarkerdata", "cnf2h_iteration",
+SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_get_dims", "cnf2h_destroy", "cnf2h_last_error", "cnf2h_postmarkerdata", "cnf2h_iteration",
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map"]
 
@@ -32,6 +32,9 @@ def load():
         L.cnf2h_create.restype = vp
         L.cnf2h_create_on.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32]
         L.cnf2h_create_on.restype = vp
+        L.cnf2h_create_from_files.argtypes = [i32, C.c_char_p, C.c_char_p, C.c_char_p, i32]
+        L.cnf2h_create_from_files.restype = vp
+        L.cnf2h_get_dims.argtypes = [vp, vp]
         L.cnf2h_set_block.argtypes = [vp, i32, i32]
         L.cnf2h_balanced_block.argtypes = [vp, i32, i32, vp, vp]
         L.cnf2h_set_partition.argtypes = [vp, i32, i32, EXCHANGE_FN, vp]
@@ -97,7 +100,6 @@ class Run:
             a, s, h = ped.allele[1:], ped.sure[1:], ped.hw[1:]       # one row per record already: no copies (bench-scale inputs)
         else:
             a, s, h = ped.dense()
-        self.n_rec, self.M = ped.n_rec, ped.n_markers
         hp = (1 - np.asarray(ped.empty)).astype(np.uint8) if has_prior is None else np.ascontiguousarray(has_prior, np.uint8)
         args = [np.ascontiguousarray(ped.par, np.int32), np.ascontiguousarray(ped.empty, np.uint8),
                 np.ascontiguousarray(ped.gen, np.int32), hp, np.ascontiguousarray(a, np.uint8),
@@ -105,11 +107,28 @@ class Run:
                 np.ascontiguousarray(ped.pos, np.float64)]
         cs = np.ascontiguousarray(ped.chromstarts, np.int32)
         dous = np.ascontiguousarray(ped.dous, np.int32)
-        self.n_chrom = len(cs) - 1
-        self.h = self.L.cnf2h_create_on(device, ped.n_rec, *[_p(x) for x in args[:8]], self.M, _p(cs), len(cs) - 1, _p(dous),
-                                        len(dous), 1 if quiet else 0)
+        self._adopt(self.L.cnf2h_create_on(device, ped.n_rec, *[_p(x) for x in args[:8]], ped.n_markers, _p(cs), len(cs) - 1,
+                                           _p(dous), len(dous), 1 if quiet else 0), "cnf2h_create")
+
+    @classmethod
+    def from_files(cls, mapfile, pedfile, genfile, quiet=True, device=0):
+        """cnf2h_create_from_files: a run over PlantImpute-format files, read by the executable's own readers; n_dous is
+        the number of analysed individuals"""
+        self = cls.__new__(cls)
+        self.L = load()
+        self._adopt(self.L.cnf2h_create_from_files(device, os.fsencode(mapfile), os.fsencode(pedfile), os.fsencode(genfile),
+                                                   1 if quiet else 0), "cnf2h_create_from_files")
+        return self
+
+    def _adopt(self, handle, what):
+        """the one place where a run's attributes are set, for every constructor: the handle and, from cnf2h_get_dims,
+        n_rec, M, n_chrom, n_dous"""
+        self.h = handle
         if not self.h:
-            raise RuntimeError("cnf2h_create: %s" % self.L.cnf2h_last_error().decode())
+            raise RuntimeError("%s: %s" % (what, self.L.cnf2h_last_error().decode()))
+        dims = np.zeros(4, np.int32)
+        self._chk(self.L.cnf2h_get_dims(self.h, _p(dims)), "cnf2h_get_dims")
+        self.n_rec, self.M, self.n_chrom, self.n_dous = (int(v) for v in dims)
 
     def close(self):
         if getattr(self, "h", None):

@@ -1,0 +1,110 @@
+"""Reading the origin sweep of Context.sweep_origins (cnf2_sweep_origins): from which grandparent does each of an individual's
+two alleles descend at every marker?
+
+origin[i][m][k], k = bit 0 + 2 bit 3, is the probability that the allele from the first parent descends from that parent's
+first (bit 0 = 0) or second (bit 0 = 1) parent, and likewise bit 3 for the second parent's side.  The frame is absolute
+(include/cnf2hip.h): with F1 parents that list line A first, k = 0 / 3 are AA / BB and k = 1, 2 the two heterozygotes by
+side.  These rows are what a QTL scan regresses on; their sums over individuals are the segregation check of a cross."""
+import copy
+import math
+
+import numpy as np
+
+_erfc = np.vectorize(math.erfc, otypes=[np.float64])
+
+
+def line_genotypes(origin):
+    """[..., 4] -> [..., 3] = (k0, k1 + k2, k3): both alleles from the parents' first parent, one from each, both from the
+    second -- AA, AB, BB in an F2."""
+    o = np.asarray(origin, np.float64)
+    assert o.shape[-1] == 4
+    return np.stack([o[..., 0], o[..., 1] + o[..., 2], o[..., 3]], axis=-1)
+
+
+def segregation_report(origin_sum, n_contrib, chromstarts):
+    """Per marker, from the sums of a sweep_origins call: a dict of arrays of length M (expected / collapsed: [M][4], [M][3]) with
+      n             the individuals that contribute (n_contrib of the marker's chromosome),
+      expected      origin_sum, the expected count of each of the four classes,
+      collapsed     line_genotypes(origin_sum), the expected counts of the three unphased classes,
+      ratio_first   the share of the first parents' gametes that carry their second parent's allele (bit 0): the
+                    transmission ratio of that side, 0.5 without distortion; ratio_second likewise for bit 3,
+      chi2_4        the chi-square statistic of `expected` against 1:1:1:1 (3 d.f.), p_4 its upper tail,
+      chi2_3        the statistic of `collapsed` against 1:2:1 (2 d.f.), p_3 its upper tail.
+    The counts are sums of probabilities, not of observations: the statistics are conservative where the data say little.
+    Markers of a chromosome without contributors report NaN (n stays 0)."""
+    s = np.asarray(origin_sum, np.float64)
+    cs = np.asarray(chromstarts, np.int64)
+    M = s.shape[0]
+    assert s.shape == (M, 4) and cs[0] == 0 and cs[-1] == M and len(n_contrib) == len(cs) - 1
+    n = np.repeat(np.asarray(n_contrib, np.int64), np.diff(cs))
+    nn = np.where(n > 0, n, 1).astype(np.float64)
+    none = n == 0
+    col = line_genotypes(s)
+    e4 = nn[:, None] * np.array([0.25, 0.25, 0.25, 0.25])
+    e3 = nn[:, None] * np.array([0.25, 0.5, 0.25])
+    chi4 = ((s - e4) ** 2 / e4).sum(axis=1)
+    chi3 = ((col - e3) ** 2 / e3).sum(axis=1)
+    # upper tails in closed form: 2 d.f. exp(-x/2); 3 d.f. erfc(sqrt(x/2)) + sqrt(2x/pi) exp(-x/2)
+    p3 = np.exp(-chi3 / 2.0)
+    p4 = _erfc(np.sqrt(chi4 / 2.0)) + np.sqrt(2.0 * chi4 / np.pi) * np.exp(-chi4 / 2.0)
+    nan = lambda a: np.where(none.reshape((M,) + (1,) * (a.ndim - 1)), np.nan, a)
+    return dict(n=n, expected=nan(s), collapsed=nan(col), ratio_first=nan((s[:, 1] + s[:, 3]) / nn),
+                ratio_second=nan((s[:, 2] + s[:, 3]) / nn), chi2_4=nan(chi4), p_4=nan(p4), chi2_3=nan(chi3), p_3=nan(p3))
+
+
+def information_content(origin):
+    """Per marker Var_i(a_i) / 0.5 with a = k3 - k0, the additive information content of line-origin probabilities: the
+    variance over the individuals of the expected additive coefficient against the 0.5 it has in an F2 whose origins are
+    known.  origin[n][M][4]; skipped individuals (all-zero rows) are left out; NaN where nobody is left."""
+    o = np.asarray(origin, np.float64)
+    assert o.ndim == 3 and o.shape[2] == 4
+    a = o[:, :, 3] - o[:, :, 0]
+    there = o.sum(axis=2) > 0
+    cnt = there.sum(axis=0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(there, a, 0.0).sum(axis=0) / cnt
+        var = np.where(there, (a - mean) ** 2, 0.0).sum(axis=0) / cnt
+    return var / 0.5
+
+
+def with_positions(ped, positions_cM_per_chrom):
+    """(ped2, is_marker): the pedigree with a column without data (alleles 0, sure 0, hw 0.5 in every row) inserted at every
+    position of positions_cM_per_chrom[c] on chromosome c, and is_marker[M2], False at the inserted columns.  The origin
+    rows of ped2 at the inserted columns are the posteriors at those positions: the map is Haldane, so the gaps compose
+    exactly, and a column without data has a constant emission -- the rows of the real markers do not change.
+    Positions outside a chromosome's first and last marker are refused (ValueError), and so is a position equal to a
+    marker's (ask for the marker) or given twice."""
+    cs = np.asarray(ped.chromstarts, np.int64)
+    pos = np.asarray(ped.pos, np.float64)
+    C = len(cs) - 1
+    if len(positions_cM_per_chrom) != C:
+        raise ValueError("one list of positions per chromosome: %d, not %d" % (C, len(positions_cM_per_chrom)))
+    new_pos, src, starts = [], [], [0]
+    for c in range(C):
+        p = pos[cs[c]:cs[c + 1]]
+        add = np.sort(np.asarray(positions_cM_per_chrom[c], np.float64).reshape(-1))
+        if len(add):
+            if not np.isfinite(add).all() or add[0] < p[0] or add[-1] > p[-1]:
+                raise ValueError("chromosome %d: positions must lie between its first and last marker (%g .. %g cM)" % (c, p[0], p[-1]))
+            if np.isin(add, p).any():
+                raise ValueError("chromosome %d: a position equals a marker's: ask for the marker" % c)
+            if (np.diff(add) == 0).any():
+                raise ValueError("chromosome %d: a position is given twice" % c)
+        allp = np.concatenate([p, add])
+        idx = np.concatenate([np.arange(cs[c], cs[c + 1]), np.full(len(add), -1, np.int64)])
+        order = np.argsort(allp, kind="stable")
+        new_pos.append(allp[order])
+        src.append(idx[order])
+        starts.append(starts[-1] + len(allp))
+    src = np.concatenate(src)
+    is_marker = src >= 0
+    take = np.where(is_marker, src, 0)
+    ped2 = copy.copy(ped)
+    ped2.pos = np.concatenate(new_pos)
+    ped2.chromstarts = np.asarray(starts, np.int32)
+    ped2.allele = np.where(is_marker[None, :, None], np.asarray(ped.allele)[:, take], 0).astype(np.uint8)
+    ped2.sure = np.where(is_marker[None, :, None], np.asarray(ped.sure)[:, take], 0.0)
+    ped2.hw = np.where(is_marker[None, :], np.asarray(ped.hw)[:, take], 0.5)
+    if ped.truth is not None:
+        ped2.truth = None         # (the generator does not know the inserted columns)
+    return ped2, is_marker

@@ -398,6 +398,53 @@ int cnf2_sweep_loo(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_ou
  *                       cross-check of the sweep's fused form. */
 int cnf2_loo_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
 
+/* Origin sweep: from which grandparent does each of the individual's two alleles descend at every marker, and with what
+ * probability?  In an F2 that is P(AA), P(AB), P(BA), P(BB), the quantity a QTL scan regresses on and the segregation check
+ * of a cross.  For analysed individual i and marker m, with g = j*8 + lo as in cnf2_state_posterior and bit t of g the
+ * meiosis of column t of cnf2_sweep_crossovers:
+ *   gamma_i,m(g)    = sum_s w_s gamma_s,m(g) / sum_s w_s
+ *   origin[i][m][k] = sum_g gamma(g) [ bit0(g) + 2 bit3(g) == k ]      k = 0..3
+ *   bits[i][m][t]   = sum_g gamma(g) bit_t(g)                          t = 0..5
+ * gamma_s,m and w_s are those of cnf2_sweep_place: gamma_s,m is alpha after the emission x beta, normalised within the mode,
+ * w_s = exp(factors[s] - loglik) over the modes the dosage rows count (active, with a likelihood, not 40 log-units below the
+ * total).  Ties, CNF2_NO_TIES and ignoreflag2 do not enter.  Each origin row sums to 1; bits[0] = origin[1] + origin[3],
+ * bits[3] = origin[2] + origin[3].
+ * THE FRAME IS ABSOLUTE, not relative to a phase the sweep chose: bit 0 = 1 means that the allele the individual has from
+ * its first parent (pedigree column par[.][0]) descends from that parent's par[.][1], bit 0 = 0 from that parent's
+ * par[.][0]; bit 3 says the same of the allele from the second parent (par[.][1]).  So k = 0 is "both alleles from the
+ * parents' first parent", k = 3 "both from the parents' second parent" -- in an F2 whose F1 parents list line A first, AA
+ * and BB -- and k = 1, 2 the two heterozygotes by the side that carries the second grandparent's allele.  Swapping the two
+ * grandparents in a parent's pedigree entry swaps bit = 0 and bit = 1 of that side.  Bits 1, 2 (first parent's side) and 4,
+ * 5 (second parent's side) are the grandparents' own meioses, labelled relative to each grandparent's phase: they carry
+ * information only where the grandparents are heterozygous, and sit at 0.5 in a cross of inbred lines.
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal (the same forward passes; tied windows from the tied kernel)
+ *   origin_out      [n][n_markers][4] or NULL
+ *   bits_out        [n][n_markers][6] or NULL; both all zero where the individual is skipped on the chromosome (no mode
+ *                   with a likelihood), as the dosage rows are.  Rows that are not asked for, and host rows, live whole in
+ *                   a buffer of the context (CNF2_ERR_NOMEM if it cannot be had: split the individual range)
+ *   origin_sum_out  [n_markers][4] the sum of origin over the individuals of the range that are not skipped: the expected
+ *                   class counts.  Reduced on the device in ascending order of the individuals, without atomics: the same
+ *                   bits on every call, and the sum of origin_out added in that order
+ *   n_contrib_out   [n_chrom] (int32) individuals of the range with a likelihood on that chromosome (not skipped)
+ * Outputs are overwritten, not accumulated; a range split [a,b) + [b,c) adds up to [a,c) (sums to rounding, counts and rows
+ * exactly).  Bad arguments (a NULL pointer other than the two rows, a range out of bounds) write nothing.
+ * Posteriors at positions between markers: add a column without data there (alleles 0, sure 0, hw 0.5 in every row) -- the
+ * map is Haldane, so the gaps compose exactly and the rows of the real markers do not change (origins.with_positions).
+ * One pass: untied windows through the fast kernel's origin instantiation (likelihoods, then a backward pass without rows
+ * that reduces eight masked sums of the state posterior per marker in the wave), tied windows through the tied kernel
+ * without rows (likelihoods) and then the same instantiation; a finish kernel reduces the columns.  Uniform windows
+ * (crosses of inbred lines) take the same instantiation.
+ * Flags: CNF2_OUT_DEVICE (all six output pointers are device pointers), CNF2_STATIC_JOBS, CNF2_FULL_SPILL and
+ * CNF2_TIES_GENERAL as in cnf2_sweep_loo; CNF2_MERGE_MODES, CNF2_XPOSE, CNF2_FLUSH_TINY, CNF2_ALL_STATES and the dosage
+ * flags are ignored.  The call synchronises the context's stream once (the job list), also with CNF2_OUT_DEVICE. */
+int cnf2_sweep_origins(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out,
+                       double *origin_out, double *bits_out, double *origin_sum_out, int32_t *n_contrib_out,
+                       uint32_t flags);
+/*  cnf2_origin_rows     rows_out[mc][10] = origin[4], bits[6] of cnf2_sweep_origins for one individual and chromosome, from
+ *                       the store by brute force (one thread per state on slots 1 and 2, every mode normalised on its own
+ *                       and weighted with exp(factors[s] - loglik)): the cross-check of the sweep's fused form. */
+int cnf2_origin_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every

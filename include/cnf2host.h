@@ -30,6 +30,11 @@ cnf2h_run *cnf2h_create(int n_rec, const int32_t *par, const uint8_t *empty, con
 cnf2h_run *cnf2h_create_on(int device, int n_rec, const int32_t *par, const uint8_t *empty, const int32_t *gen,
                            const uint8_t *has_prior, const uint8_t *allele, const double *sure, const double *hw, const double *pos,
                            int n_markers, const int32_t *chromstarts, int n_chrom, const int32_t *dous, int n_dous, int quiet);
+/* the same from PlantImpute-format files, through the readers of the `cnF2freq` executable (map, pedigree, genotypes with
+ * read-count tokens): the run's state is the executable's after reading, before postmarkerdata.  NULL (text in
+ * cnf2h_last_error) where a file cannot be read.  cnf2h_get_dims: out4 = records, markers, chromosomes, analysed individuals */
+cnf2h_run *cnf2h_create_from_files(int device, const char *mapfile, const char *pedfile, const char *genfile, int quiet);
+int        cnf2h_get_dims(cnf2h_run *run, int32_t *out4);
 void       cnf2h_destroy(cnf2h_run *run);
 const char *cnf2h_last_error(void);
 
