@@ -42,11 +42,15 @@ def transition(r):
     return T, diff
 
 
-def oracle_xi(o, ind, gen, pos, first, last):
+FLIPS = [(((BITS[:, None] ^ BITS[None, :]) >> t) & 1) == 1 for t in range(6)]      # [t][g, g']: bit t differs
+
+
+def oracle_xi(o, ind, gen, pos, first, last, Ts=None):
     """xi[len][6] of one individual and chromosome from the oracle's store: for every shift mode the pairwise posterior
     P(g at m, g' at m+1) = alpha_m(g) T(g, g') gamma_{m+1}(g') / (T^t alpha_m)(g'), gamma = posterior of the state; modes
     weighted by exp(factors[s] - factor) with the 40-log-unit rule.  Also returns the largest deviation of the pairwise
-    posterior's margin over g' from the state posterior at m."""
+    posterior's margin over g' from the state posterior at m.  Ts: a dict that keeps the transition of every gap for the
+    next call on the same map."""
     res = o.sweep_ind(int(ind), gen, first=first, last=last, mode=2, keep_store=True)
     nm = last - first + 1
     xi = np.zeros((nm, 6))
@@ -65,7 +69,12 @@ def oracle_xi(o, ind, gen, pos, first, last):
             r = rates(pos, m)
             if not r.any():
                 continue
-            T, diff = transition(r)
+            if Ts is None:
+                T = transition(r)[0]
+            else:
+                if m not in Ts:
+                    Ts[m] = transition(r)[0]
+                T = Ts[m]
             al = fw[s, m, 2]
             gam = fw[s, m + 1, 2] * fw[s, m + 1, 1]
             if gam.sum() <= 0:
@@ -75,7 +84,7 @@ def oracle_xi(o, ind, gen, pos, first, last):
             cond = np.where(am > 0, gam / np.where(am > 0, am, 1.0), 0.0)
             J = al[:, None] * T * cond[None, :]
             for t in range(6):
-                xi[k, t] += ws * J[((diff >> t) & 1) == 1].sum()
+                xi[k, t] += ws * J[FLIPS[t]].sum()
             st = fw[s, m, 2] * fw[s, m, 1]
             if st.sum() > 0:
                 worst = max(worst, np.abs(J.sum(axis=1) - st / st.sum()).max())
@@ -87,23 +96,38 @@ def summed_loglik(ll):
     return ll[ok].sum()
 
 
-def check_against_oracle(ctx, ped):
+def oracle_xi_all(ped):
+    """xi[n][M][6] of every analysed individual on every chromosome (oracle_xi; zeros where the oracle skips the pair)"""
     o = oracle_ped(ped)
-    got = ctx.sweep_crossovers()
     cs = ped.chromstarts
-    checked = 0
+    want = np.zeros((len(ped.dous), ped.n_markers, 6))
+    Ts = {}
     for j, ind in enumerate(ped.dous):
-        gen = int(ped.gen[ind])
         for c in range(len(cs) - 1):
             first, last = int(cs[c]), int(cs[c + 1]) - 1
-            want, worst = oracle_xi(o, ind, gen, ped.pos, first, last)
+            want[j, first:last + 1], worst = oracle_xi(o, ind, int(ped.gen[ind]), ped.pos, first, last, Ts)
             assert worst < 1e-10, "pairwise posterior does not sum to the state posterior"
-            rows = ctx.crossover_rows(j, c)
+    return want
+
+
+def check_against_oracle(ctx, ped, got=None, want=None, rows=True):
+    """every individual and chromosome of `got` (default: a plain cnf2_sweep_crossovers call) and, with `rows`, of
+    cnf2_crossover_rows against oracle_xi (`want`: oracle_xi_all(ped) computed earlier)"""
+    got = ctx.sweep_crossovers() if got is None else got
+    want = oracle_xi_all(ped) if want is None else want
+    cs = ped.chromstarts
+    checked, worst = 0, 0.0
+    for j in range(len(ped.dous)):
+        for c in range(len(cs) - 1):
+            first, last = int(cs[c]), int(cs[c + 1]) - 1
             fused = got["xo"][j, first:last + 1]
-            np.testing.assert_allclose(fused, want, rtol=1e-9, atol=1e-12)
-            np.testing.assert_allclose(rows, want, rtol=1e-9, atol=1e-12)
+            np.testing.assert_allclose(fused, want[j, first:last + 1], rtol=1e-9, atol=1e-12)
+            if rows:
+                np.testing.assert_allclose(ctx.crossover_rows(j, c), want[j, first:last + 1], rtol=1e-9, atol=1e-12)
             assert np.all(fused[-1] == 0.0)
-            checked += int(want.any())
+            checked += int(want[j, first:last + 1].any())
+            worst = max(worst, np.abs(fused - want[j, first:last + 1]).max())
+    print("xi against the oracle: largest difference %.3g over %d (individual, chromosome) pairs with crossovers" % (worst, checked))
     assert checked > 0
     return got
 

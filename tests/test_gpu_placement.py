@@ -92,7 +92,7 @@ def oracle_emission(ped, ca, csr, ch):
 def oracle_place(capi, base, E):
     """place[n][Q][M] by contracting the oracle's store with E: the weights and the 40-log-unit rule of oracle_xi in
     tests/test_gpu_crossovers.py.  Returns (place, the (individual, chromosome) pairs compared in numbers: those the oracle
-    does not skip)."""
+    does not skip and that have a mode with a likelihood)."""
     o = oracle_ped(base)
     cs = np.asarray(base.chromstarts)
     n, Q, M = len(base.dous), E.shape[1], base.n_markers
@@ -104,7 +104,7 @@ def oracle_place(capi, base, E):
             first, last = int(cs[c]), int(cs[c + 1]) - 1
             res = o.sweep_ind(int(ind), gen, first=first, last=last, mode=2, keep_store=True)
             factor = res["factor"]
-            if not res["ok"] or not (factor >= -1e15):
+            if not res["ok"] or not (factor >= -1e15) or not (res["factors"] > -1e14).any():
                 out[j, :, first:last + 1] = capi.IGNORED
                 continue
             compared += 1

@@ -77,7 +77,7 @@ def replay(ped, got, seed, inds=None, ind0=0, o=None, Ts=None):
             path = got["state"][j, :, first:last + 1].astype(np.int64)
             lp = got["logp"][j, :, c]
             res = o.sweep_ind(ind, int(ped.gen[ind]), first=first, last=last, mode=2, keep_store=True)
-            if not res["ok"] or not (res["factor"] >= -1e15):
+            if not res["ok"] or not (res["factor"] >= -1e15) or not (res["factors"] > -1e14).any():
                 assert np.all(sh == -1) and np.all(path == 0xFF) and np.all(np.isnan(lp)), (j, c)
                 continue
             assert np.all((sh >= 0) & (sh < 8)) and np.all(path < 64), (j, c)

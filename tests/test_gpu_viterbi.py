@@ -73,11 +73,13 @@ def path_score(E, Ts, path):
     return s
 
 
-def check_against_oracle(ctx, ped):
-    o = oracle_ped(ped)
-    got = ctx.sweep_viterbi()
+def check_against_oracle(ctx, ped, got=None, o=None):
+    """every individual and chromosome of `got` (default: a plain cnf2_sweep_viterbi call) against the oracle's store (`o`:
+    the pedigree's oracle, where the caller keeps one)"""
+    o = oracle_ped(ped) if o is None else o
+    got = ctx.sweep_viterbi() if got is None else got
     cs = ped.chromstarts
-    checked = 0
+    checked, worst = 0, 0.0
     for j, ind in enumerate(ped.dous):
         gen = int(ped.gen[ind])
         for c in range(len(cs) - 1):
@@ -85,7 +87,7 @@ def check_against_oracle(ctx, ped):
             res = o.sweep_ind(int(ind), gen, first=first, last=last, mode=2, keep_store=True)
             sstar = int(got["shift"][j, c])
             path = got["state"][j, first:last + 1].astype(np.int64)
-            if not res["ok"] or not (res["factor"] >= -1e15):
+            if not res["ok"] or not (res["factor"] >= -1e15) or not (res["factors"] > -1e14).any():
                 assert sstar == -1 and np.all(path == 0xFF)
                 continue
             assert 0 <= sstar < 8 and np.all(path < 64)
@@ -104,12 +106,14 @@ def check_against_oracle(ctx, ped):
                     continue
                 d = lmax - lsum
                 assert abs((got["logmax"][j, c, s] - fs) - d) <= 1e-8 * (1 + abs(d)), (j, c, s)
+                worst = max(worst, abs((got["logmax"][j, c, s] - fs) - d) / (1 + abs(d)))
                 if s == sstar:
                     best = (E, lmax, d)
             assert best is not None
             E, lmax, d = best
             assert abs(path_score(E, Ts, path) - lmax) <= 1e-8 * (1 + abs(d)), (j, c)
             checked += 1
+    print("logmax - factors against the oracle: largest difference %.3g of (1 + |value|) over %d (individual, chromosome) pairs" % (worst, checked))
     assert checked > 0
     return got
 

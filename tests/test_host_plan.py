@@ -280,3 +280,22 @@ def test_batches(shim):
                     int(rng.integers(1, 2000000)), int(rng.integers(0, 3)) * int(rng.integers(1, 5000)), need,
                     int(rng.integers(0, need + 1)))[0] == FITS
     assert 100 < fits < 300
+
+
+def test_job_order_of_the_persistent_mode_fixtures(shim):
+    """tests/test_gpu_persistent_modes.py works out which wave of one block takes which job from its own statement of the job
+    order (job_lists): for each of its fixtures that statement is the planner's list, with the tie rule (the modes) and without
+    (the placement sweep)"""
+    import test_gpu_persistent_modes as pm
+    for name in pm.FIXTURES:
+        fx = pm.fixture(name)
+        ped = fx.ped
+        row_hom = ((ped.allele[:, :, 0] == ped.allele[:, :, 1]) & (ped.sure[:, :, 0] == ped.sure[:, :, 1])).all(axis=1).astype(np.uint8)
+        win = windows_of(shim, ped, row_hom)
+        for flags in (0, capi.NO_TIES):
+            tied = (win["n_groups"] > 0) & (flags == 0)
+            paths = np.where(tied, pm.PATH_TIED, 0)[:, None].repeat(fx.C, axis=1)
+            untied, tied_jobs = pm.job_lists(fx, paths)
+            jobs, n_fast, pjobs = plan_jobs(shim, win, ped.chromstarts, 0, fx.n, flags, row_hom)
+            assert [(j[0], j[3]) for j in jobs] == untied + tied_jobs and n_fast == len(untied) and pjobs == []
+        assert (len(tied_jobs) == 0) and (win["n_groups"] > 0).sum() * fx.C == (70 if name == "tied_mixed" else 0)

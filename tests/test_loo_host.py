@@ -23,7 +23,8 @@ def oracle_loo(ped, threads=None):
     """(loo[n][M], loglik[n][C], pairs compared) from the oracle's alpha / beta store in numpy:
     loo = log sum_s exp(fs - factor) sum_g fw[s,m,0] fw[s,m,1] exp(ff[s,m,0] - ff[s,m,2]) / sum_g fw[s,m,2] fw[s,m,1]
     over the modes with a likelihood (slot 0 alpha before the emission, 1 beta, 2 alpha after it; ff their cumulative log
-    scales): each term is L_s,-m / L_s, weighted with L_s / L.  CNF2_IGNORED where the oracle skips the individual."""
+    scales): each term is L_s,-m / L_s, weighted with L_s / L.  CNF2_IGNORED where the oracle skips the individual or leaves
+    every mode at the floor (an impossible genotype: no mode has a likelihood)."""
     o = oracle_ped(ped)
     cs = np.asarray(ped.chromstarts)
     n, M, C = len(ped.dous), ped.n_markers, len(cs) - 1
@@ -38,7 +39,7 @@ def oracle_loo(ped, threads=None):
             res = o.sweep_ind(ind, int(ped.gen[ind]), first=first, last=last, mode=2, dosage=False, keep_store=True)
             factor = res["factor"]
             ll[j, c] = factor
-            if not res["ok"] or not (factor >= -1e15):
+            if not res["ok"] or not (factor >= -1e15) or not (res["factors"] > -1e14).any():
                 out[j, first:last + 1] = IGNORED
                 continue
             ok[j, c] = True
