@@ -26,6 +26,8 @@ DETERMINISTIC = 16384
 TURN_VALU = 32768
 FLUSH_TINY = 1 << 20              # cnf2_sweep: general kernel with adjustprobs' 1e-300 rule (the reference's behaviour to the letter)
 ALL_STATES = 1 << 21              # windows of crosses of inbred lines through the fast kernel's ordinary instantiation (A/B, cross-check)
+QTL_ADDITIVE = 1 << 22            # cnf2_qtl_scan / cnf2_sweep_qtl: the dominance column is always dropped
+QTL_ORIGIN_DEVICE = 1 << 23       # cnf2_qtl_scan: the origin rows are a device pointer
 STATIC_JOBS = 1 << 18             # wave w sweeps jobs w, w + waves, ... instead of taking jobs from the launch's counter (A/B)
 MINFACTOR = float(np.float32(-1e15))
 IGNORED = -1e30
@@ -44,6 +46,7 @@ SYMBOLS = [
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
     "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
+    "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns",
 ]
 
 
@@ -114,6 +117,9 @@ def load():
         L.cnf2_loo_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_sweep_origins.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_origin_rows.argtypes = [vp, i32, i32, vp]
+        L.cnf2_qtl_scan.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_sweep_qtl.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_set_qtl_columns.argtypes = [vp, i32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -178,12 +184,30 @@ class Context:
         if rc != 0:
             raise Cnf2Error("cnf2_ctx_create: %s" % self.L.cnf2_last_error(None).decode())
         self.h = h
+        self.device = device
+        self.owned = True          # close() destroys the handle (False: Context.borrowed)
         self.n_markers = self.n_chrom = self.n_ind = self.n_rec = 0
         self.chromstarts = None
 
+    @classmethod
+    def borrowed(cls, handle, n_markers, chromstarts, n_ind, n_rec=0, device=0):
+        """A Context over a cnf2_ctx handle that someone else owns and has uploaded to -- host.Run.context(), whose run read
+        the files and holds the state of its rounds -- so that the analysis calls and cnf2freq_amd/qtl.py work on that state.
+        The caller states what the owner uploaded (markers, chromstarts, analysed individuals) and the handle's device;
+        close() leaves the handle alone, and the Context must not be used after its owner is closed."""
+        self = cls.__new__(cls)
+        self.L = load()
+        self.h = C.c_void_p(handle)
+        self.device = device
+        self.owned = False
+        self.n_markers, self.n_chrom, self.n_ind, self.n_rec = n_markers, len(chromstarts) - 1, n_ind, n_rec
+        self.chromstarts = np.ascontiguousarray(chromstarts, np.int32)
+        return self
+
     def close(self):
         if getattr(self, "h", None):
-            self.L.cnf2_ctx_destroy(self.h)
+            if self.owned:
+                self.L.cnf2_ctx_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -520,6 +544,104 @@ class Context:
                                             C.c_void_p(d_origin) if d_origin else None,
                                             C.c_void_p(d_bits) if d_bits else None, C.c_void_p(d_origin_sum),
                                             C.c_void_p(d_n_contrib), flags | OUT_DEVICE), "cnf2_sweep_origins")
+
+    # -- QTL scan ----------------------------------------------------------------
+    def set_qtl_columns(self, cap):
+        """Cap on the phenotype columns per tile of qtl_scan / sweep_qtl (0 = what memory allows); results do not depend on it."""
+        self._chk(self.L.cnf2_set_qtl_columns(self.h, cap), "cnf2_set_qtl_columns")
+
+    @staticmethod
+    def _qtl_inputs(n, pheno, cov, use, perm):
+        """the phenotype side of a scan as contiguous arrays: (pheno[n][T], cov[n][K] or None, use[n] or None, perm[P][n] or None)"""
+        pheno = np.ascontiguousarray(pheno, np.float64)
+        if pheno.ndim == 1:
+            pheno = pheno[:, None]
+        if pheno.ndim != 2 or pheno.shape[0] != n:
+            raise ValueError("pheno must be [n][T] with n = %d" % n)
+        if cov is not None:
+            cov = np.ascontiguousarray(cov, np.float64)
+            cov = cov[:, None] if cov.ndim == 1 else cov
+            if cov.ndim != 2 or cov.shape[0] != n:
+                raise ValueError("cov must be [n][K]")
+            if cov.shape[1] == 0:
+                cov = None
+        if use is not None:
+            use = np.ascontiguousarray(np.asarray(use) != 0, np.uint8)
+            if use.shape != (n,):
+                raise ValueError("use must be [n]")
+        if perm is not None:
+            perm = np.ascontiguousarray(perm, np.int32)
+            perm = perm[None, :] if perm.ndim == 1 else perm
+            if perm.ndim != 2 or perm.shape[1] != n:
+                raise ValueError("perm must be [P][n]")
+            if perm.shape[0] == 0:
+                perm = None
+        return pheno, cov, use, perm
+
+    def _qtl_outputs(self, T, P):
+        M, Cn = self.n_markers, self.n_chrom
+        return dict(lod=np.zeros((T, M)), coef=np.zeros((T, M, 2)), rank=np.zeros(M, np.int32), rss0=np.zeros((T, Cn)),
+                    n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn)) if P else None)
+
+    def _qtl_call(self, n, origin_ptr, pheno, cov, use, perm, flags, out=None):
+        """cnf2_qtl_scan with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        o = self._qtl_outputs(T, P) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_qtl_scan(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm), _p(o["lod"]),
+                                       _p(o["coef"]), _p(o["rank"]), _p(o["rss0"]), _p(o["n_used"]), opt(o["perm_max"]),
+                                       flags), "cnf2_qtl_scan")
+        return o
+
+    def qtl_scan(self, origin, pheno, cov=None, use=None, perm=None, additive=False):
+        """cnf2_qtl_scan on host rows origin[n][M][4] (what sweep_origins returns): Haley-Knott regression of pheno[n][T] on
+        the rows at every marker, with fixed-effect covariates cov[n][K], the individuals of use[n] and the permutations
+        perm[P][n].  A dict: lod[T][M], coef[T][M][2] (additive and dominance effect; NaN for a dropped column), rank[M],
+        rss0[T][C], n_used[C], perm_max[P][T][C] (None without permutations).  The model: include/cnf2hip.h;
+        cnf2freq_amd/qtl.py reads the results."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return self._qtl_call(origin.shape[0], _p(origin), pheno, cov, use, perm, QTL_ADDITIVE if additive else 0)
+
+    def qtl_scan_device(self, n, d_origin, pheno, cov=None, use=None, perm=None, additive=False):
+        """The same on device rows (d_origin: an int, the pointer of n x M x 4 doubles aligned to 16 bytes, e.g. the tensor a
+        sweep_origins_device call filled); they are read in place.  Phenotypes and outputs are host arrays.  d_origin None:
+        the rows this context's last sweep_qtl left in it (n that call's; Cnf2Error once anything has been uploaded or
+        another call has used the buffer since)."""
+        return self._qtl_call(n, C.c_void_p(d_origin), pheno, cov, use, perm,
+                              QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0))
+
+    def sweep_qtl(self, pheno, cov=None, use=None, perm=None, additive=False, ind_begin=0, ind_end=None, full_spill=False,
+                  ties_general=False, static_jobs=False):
+        """cnf2_sweep_qtl: the origin sweep of the range with the rows in the context, then the scan on them.  The dict of
+        qtl_scan plus factors / loglik as sweep()."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        o = self._qtl_outputs(T, P)
+        o["factors"] = np.zeros((n, self.n_chrom, 8))
+        o["loglik"] = np.zeros((n, self.n_chrom))
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0) | (QTL_ADDITIVE if additive else 0))
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_sweep_qtl(self.h, ind_begin, ind_end, _p(o["factors"]), _p(o["loglik"]), T, _p(pheno), opt(use),
+                                        K, opt(cov), P, opt(perm), _p(o["lod"]), _p(o["coef"]), _p(o["rank"]), _p(o["rss0"]),
+                                        _p(o["n_used"]), opt(o["perm_max"]), flags), "cnf2_sweep_qtl")
+        return o
+
+    def sweep_qtl_device(self, ind_begin, ind_end, d_factors, d_loglik, pheno, cov, use, perm, d_lod, d_coef, d_rank, d_rss0,
+                         d_n_used, d_perm_max, flags=0):
+        """Device-pointer form (ints; d_perm_max None without permutations); phenotypes stay host arrays."""
+        pheno, cov, use, perm = self._qtl_inputs(ind_end - ind_begin, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_sweep_qtl(self.h, ind_begin, ind_end, C.c_void_p(d_factors), C.c_void_p(d_loglik), T, _p(pheno),
+                                        opt(use), K, opt(cov), P, opt(perm), C.c_void_p(d_lod), C.c_void_p(d_coef),
+                                        C.c_void_p(d_rank), C.c_void_p(d_rss0), C.c_void_p(d_n_used),
+                                        C.c_void_p(d_perm_max) if d_perm_max else None, flags | OUT_DEVICE), "cnf2_sweep_qtl")
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

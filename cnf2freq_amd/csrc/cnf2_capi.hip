@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <cmath>
 #include <stdarg.h>
 #include <chrono>
 #include <stdio.h>
@@ -18,6 +19,7 @@
 #include "cnf2_device.h"
 #include "cnf2_emission.h"
 #include "cnf2_plan.h"
+#include "cnf2_qtl.h"
 
 using namespace cnf2;
 
@@ -135,6 +137,16 @@ struct cnf2_ctx {
     DevBuf<double>  d_org;                // [n][n_markers][4]
     DevBuf<double>  d_obits;              // [n][n_markers][6]
     DevBuf<double>  d_org_sum;            // [n_markers][4]
+
+    // QTL scan (cnf2_qtl_scan, cnf2_sweep_qtl): staged inputs, design, the column image of a tile, staged outputs
+    int             qtl_columns = 0;      // cap on the columns per tile (0 = what memory allows)
+    int             qtl_rows_n = 0;       // individuals whose rows the last cnf2_sweep_qtl left in d_org: 0 (none to vouch for) after
+                                          // every upload of a map, rows or a pedigree and every other use of d_org
+    int             qtl_rows_m = 0;       // ... and the markers of those rows
+    DevBuf<double>  d_q_pheno, d_q_cov, d_q_Y, d_q_null, d_q_mk, d_q_chol, d_q_tilemax;
+    DevBuf<double>  d_q_lod, d_q_coef, d_q_rss0, d_q_pmax;
+    DevBuf<uint8_t> d_q_use, d_q_cmask;
+    DevBuf<int32_t> d_q_perm, d_q_map, d_q_nc, d_q_rank;   // d_q_map: chromstarts, marker -> chromosome, tiles, tile starts
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -348,6 +360,13 @@ int cnf2_set_batch_jobs(cnf2_ctx* ctx, int jobs)
     return CNF2_OK;
 }
 
+int cnf2_set_qtl_columns(cnf2_ctx* ctx, int cap)
+{
+    if (!ctx || cap < 0) return CNF2_ERR_ARG;
+    ctx->qtl_columns = cap;
+    return CNF2_OK;
+}
+
 int cnf2_sync(cnf2_ctx* ctx)
 {
     if (!ctx) return CNF2_ERR_ARG;
@@ -366,6 +385,7 @@ int cnf2_upload_map(cnf2_ctx* ctx, const double* pos, int n_markers, const int32
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (ctx->n_markers != n_markers && (ctx->d_allele8 || ctx->d_sure || ctx->d_hw))
         return fail(ctx, CNF2_ERR_STATE, "marker count changed after rows were uploaded");
+    ctx->qtl_rows_n = 0;               // (the rows a cnf2_sweep_qtl left have the old map's shape)
     ctx->n_markers = n_markers;
     ctx->n_chrom   = n_chrom;
     ctx->chromstarts.assign(chromstarts, chromstarts + n_chrom + 1);
@@ -459,6 +479,7 @@ int cnf2_upload_rows(cnf2_ctx* ctx, int n_rows, const uint8_t* allele, const dou
     RC_TRY(ctx->d_sure.alloc(ctx, cnt));
     RC_TRY(ctx->d_hw.alloc(ctx, cnt));
     ctx->n_rows = n_rows;
+    ctx->qtl_rows_n = 0;               // (the rows a cnf2_sweep_qtl left are no longer this state's)
     ctx->windows_dirty = true;
     ctx->priors_set = false;
     // a pedigree uploaded against a larger table would index past the new one: drop it, it must be uploaded again
@@ -480,6 +501,7 @@ int cnf2_update_rows_device(cnf2_ctx* ctx, int row0, int n, const uint8_t* d_all
     if (row0 < 0 || n < 0 || row0 + n > ctx->n_rows) return fail(ctx, CNF2_ERR_ARG, "row range out of bounds");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t M = ctx->n_markers, cnt = (size_t)n * M;
+    ctx->qtl_rows_n = 0;               // (the rows a cnf2_sweep_qtl left are no longer this state's)
     ctx->windows_dirty = true;
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_allele8 + (size_t)row0 * M, d_allele8, cnt, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sure + (size_t)row0 * M, d_sure, cnt * sizeof(double2), hipMemcpyDeviceToDevice, ctx->stream));
@@ -496,6 +518,7 @@ int cnf2_update_rows(cnf2_ctx* ctx, int row0, int n, const uint8_t* allele, cons
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (n == 0) return CNF2_OK;
+    ctx->qtl_rows_n = 0;               // (the rows a cnf2_sweep_qtl left are no longer this state's)
     ctx->windows_dirty = true;
     return copy_rows(ctx, row0, n, allele, sure, hw);
 }
@@ -525,6 +548,7 @@ int cnf2_upload_pedigree(cnf2_ctx* ctx, int n_rec, const int32_t* par, const uin
     derive_founders(P);
     P.row_hom.clear();
     ctx->windows.assign(n_dous, Window());
+    ctx->qtl_rows_n = 0;               // (the rows a cnf2_sweep_qtl left are no longer this state's)
     ctx->windows_dirty = true;
     ctx->priors_set = false;         // the per-record prior flags belong to the pedigree that was replaced
     return CNF2_OK;
@@ -1169,6 +1193,7 @@ int cnf2_sweep_origins(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factor
     if (!factors_out || !loglik_out || !origin_sum_out || !n_contrib_out)
         return fail(ctx, CNF2_ERR_ARG, "only origin_out and bits_out may be NULL");
     RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    ctx->qtl_rows_n = 0;
     const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
     const int    n = ind_end - ind_begin;
     const size_t M = ctx->n_markers, C = ctx->n_chrom, nr = (size_t)n * M;
@@ -1198,6 +1223,207 @@ int cnf2_sweep_origins(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factor
     if (bits_out) RC_TRY(fetch_out(ctx, bits_out, m.obits, nr * 6));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// QTL scan (cnf2_qtl.h, cnf2_qtl_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+struct QtlArgs {
+    int            n, T, K, P;
+    const double*  pheno;
+    const uint8_t* use;
+    const double*  cov;
+    const int32_t* perm;
+    double *       lod, *coef, *rss0, *pmax;
+    int32_t *      rank, *n_used;
+};
+
+// every check of the phenotype side, before anything is written; use_out[n] = the mask with NULL expanded
+static int qtl_validate(cnf2_ctx* ctx, const QtlArgs& a, std::vector<uint8_t>* use_out)
+{
+    if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
+    if (a.n < 1 || a.T < 1 || !a.pheno) return fail(ctx, CNF2_ERR_ARG, "n and n_traits must be at least 1 and pheno not NULL");
+    if (a.K < 0 || a.K > QTL_MAXK || (a.K > 0 && !a.cov)) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d, with cov", QTL_MAXK);
+    if (a.P < 0 || (a.P > 0) != (a.perm != nullptr) || (a.P > 0) != (a.pmax != nullptr))
+        return fail(ctx, CNF2_ERR_ARG, "perm and perm_max_out must be NULL exactly when n_perm is 0");
+    if (!a.lod || !a.coef || !a.rank || !a.rss0 || !a.n_used) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if ((size_t)a.T * ((size_t)a.P + 1) > (size_t)1 << 30) return fail(ctx, CNF2_ERR_ARG, "too many columns");
+    std::vector<uint8_t>& use = *use_out;
+    use.assign(a.n, 1);
+    if (a.use)
+        for (int i = 0; i < a.n; i++) use[i] = a.use[i] ? 1 : 0;
+    for (int i = 0; i < a.n; i++) {
+        if (!use[i]) continue;
+        for (int t = 0; t < a.T; t++)
+            if (!std::isfinite(a.pheno[(size_t)i * a.T + t]))
+                return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is used and not finite", t, i);
+        for (int k = 0; k < a.K; k++)
+            if (!std::isfinite(a.cov[(size_t)i * a.K + k]))
+                return fail(ctx, CNF2_ERR_ARG, "covariate %d of individual %d is used and not finite", k, i);
+    }
+    std::vector<uint8_t> seen(a.n);
+    for (int p = 0; p < a.P; p++) {
+        std::fill(seen.begin(), seen.end(), 0);
+        const int32_t* row = a.perm + (size_t)p * a.n;
+        for (int i = 0; i < a.n; i++) {
+            const int32_t j = row[i];
+            if (j < 0 || j >= a.n || seen[j]) return fail(ctx, CNF2_ERR_ARG, "row %d of perm is not a permutation of 0 .. n-1", p);
+            seen[j] = 1;
+            if (use[i] && !use[j])
+                return fail(ctx, CNF2_ERR_ARG, "permutation %d gives individual %d, which is used, the unused individual %d", p, i, j);
+        }
+    }
+    return CNF2_OK;
+}
+
+extern "C++" template <class T>
+static int qtl_upload(cnf2_ctx* ctx, DevBuf<T>& buf, const T* src, size_t count)
+{
+    if (count == 0) return CNF2_OK;
+    RC_TRY(buf.ensure(ctx, count));
+    // (complete on return: src is caller or local memory, and a later step may fail and return at once)
+    HIP_TRY(ctx, hipMemcpyAsync(buf.ptr, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// the scan on device rows d_origin[n][M][4]; `a` has been validated and `use` is its expanded mask
+static int qtl_scan_impl(cnf2_ctx* ctx, const double* d_origin, const QtlArgs& a, const std::vector<uint8_t>& use, uint32_t flags)
+{
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    M = ctx->n_markers, C = ctx->n_chrom, nx = a.K + 1;
+    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
+    // the column tile: the image under 1 GB, the tile maxima of a large map bounded, the caller's cap
+    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
+    rt = std::min(std::min(rt, (size_t)4096), R);
+    if (ctx->qtl_columns > 0) rt = std::min(rt, (size_t)ctx->qtl_columns);
+    // the map as the kernels read it: chromstarts, marker -> chromosome, the marker tiles (none straddles a chromosome start)
+    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
+    map.resize((size_t)C + 1 + M);
+    std::vector<int32_t> tiles, tstart(1, 0);
+    for (int c = 0; c < C; c++) {
+        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
+        for (int m = f; m < e; m++) map[(size_t)C + 1 + m] = c;
+        for (int m = f; m < e; m += 16) {
+            const int32_t t4[4] = {c, m, std::min(16, e - m), 0};
+            tiles.insert(tiles.end(), t4, t4 + 4);
+        }
+        tstart.push_back((int32_t)(tiles.size() / 4));
+    }
+    const size_t n_tiles = tiles.size() / 4, o_tiles = map.size();
+    map.insert(map.end(), tiles.begin(), tiles.end());
+    const size_t o_tstart = map.size();
+    map.insert(map.end(), tstart.begin(), tstart.end());
+
+    RC_TRY(qtl_upload(ctx, ctx->d_q_map, map.data(), map.size()));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_use, use.data(), (size_t)a.n));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_q_mk.ensure(ctx, (size_t)M * QTL_MK));
+    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
+    RC_TRY(ctx->d_q_null.ensure(ctx, (size_t)C * (nx + 1) * rt));
+    if (a.P > 0) RC_TRY(ctx->d_q_tilemax.ensure(ctx, n_tiles * rt));
+
+    QtlParams q;
+    memset(&q, 0, sizeof(q));
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.nx = nx;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
+    q.origin = d_origin, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.perm = ctx->d_q_perm;
+    q.cs = ctx->d_q_map, q.mchrom = ctx->d_q_map + (C + 1);
+    q.tiles = ctx->d_q_map + o_tiles, q.tile_start = ctx->d_q_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.cmask = ctx->d_q_cmask, q.chol = ctx->d_q_chol, q.mk = ctx->d_q_mk;
+    q.Y = ctx->d_q_Y, q.nullq = ctx->d_q_null, q.tilemax = ctx->d_q_tilemax, q.rstride = (int)rt;
+    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_q_nc, (size_t)C, &q.nc));
+    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_q_rank, (size_t)M, &q.rank));
+    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_q_lod, (size_t)a.T * M, &q.lod));
+    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_q_coef, (size_t)a.T * M * 2, &q.coef));
+    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_q_rss0, (size_t)a.T * C, &q.rss0));
+    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_q_pmax, (size_t)a.P * a.T * C, &q.pmax));
+
+    launch_qtl_chrom(q, ctx->stream);
+    launch_qtl_design(q, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = (int)r0;
+        q.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(q, ctx->stream);
+        launch_qtl_null(q, ctx->stream);
+        launch_qtl_scan(q, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtl_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dev) {
+        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C));
+        RC_TRY(fetch_out(ctx, a.rank, q.rank, (size_t)M));
+        RC_TRY(fetch_out(ctx, a.lod, q.lod, (size_t)a.T * M));
+        RC_TRY(fetch_out(ctx, a.coef, q.coef, (size_t)a.T * M * 2));
+        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C));
+        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * C));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+int cnf2_qtl_scan(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
+                  const double* cov, int n_perm, const int32_t* perm, double* lod_out, double* coef_out, int32_t* rank_out,
+                  double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
+                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    const QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_validate(ctx, a, &mask));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double* d_origin = kept ? ctx->d_org.ptr : origin;
+    if (flags & CNF2_QTL_ORIGIN_DEVICE) {
+        if ((uintptr_t)d_origin & 15) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+    } else {
+        const size_t cnt = (size_t)n * ctx->n_markers * 4;
+        ctx->qtl_rows_n = 0;
+        RC_TRY(ctx->d_org.ensure(ctx, cnt));
+        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_origin = ctx->d_org;
+    }
+    return qtl_scan_impl(ctx, d_origin, a, mask, flags);
+}
+
+// cnf2_sweep_origins over the range with the rows in the context's buffer, then the scan on them
+int cnf2_sweep_qtl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, int n_traits,
+                   const double* pheno, const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm,
+                   double* lod_out, double* coef_out, int32_t* rank_out, double* rss0_out, int32_t* n_used_out,
+                   double* perm_max_out, uint32_t flags)
+{
+    RC_TRY(ready(ctx));
+    if (!factors_out || !loglik_out) return fail(ctx, CNF2_ERR_ARG, "factors_out and loglik_out must not be NULL");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    const QtlArgs a = {ind_end - ind_begin, n_traits, n_cov, n_perm, pheno, use, cov, perm,
+                       lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_validate(ctx, a, &mask));
+    const uint32_t sweep_flags = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
+    const size_t   M = ctx->n_markers, C = ctx->n_chrom;
+    if (flags & CNF2_OUT_DEVICE) {
+        RC_TRY(ctx->d_org_sum.ensure(ctx, M * 4));
+        RC_TRY(ctx->d_xo_cnt.ensure(ctx, C));
+        RC_TRY(cnf2_sweep_origins(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, nullptr, ctx->d_org_sum, ctx->d_xo_cnt,
+                                  sweep_flags));
+    } else {
+        std::vector<double>  sum(M * 4);
+        std::vector<int32_t> cnt(C);
+        RC_TRY(cnf2_sweep_origins(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, nullptr, sum.data(), cnt.data(),
+                                  sweep_flags));
+    }
+    ctx->qtl_rows_n = a.n;
+    ctx->qtl_rows_m = ctx->n_markers;
+    return qtl_scan_impl(ctx, ctx->d_org, a, mask, flags);
 }
 
 // one pass of sweep_impl's Viterbi mode
@@ -1929,6 +2155,7 @@ static int update_pass_impl(cnf2_ctx* ctx, int chrom, const int32_t* recs, int n
     }
     if (u.n_rec > 0) launch_update_pass(u, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
+    ctx->qtl_rows_n = 0;               // (the rows a cnf2_sweep_qtl left are no longer this state's)
     ctx->windows_dirty = true;          // rows changed: the "homozygous everywhere" flags must be derived again
     HIP_TRY(ctx, hipMemcpyAsync(hits_out, ctx->d_hits, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     if (!acc_dev && given) {
@@ -2087,6 +2314,7 @@ int cnf2_unpack_rows(cnf2_ctx* ctx, const int32_t* recs, int n, const void* d_pa
     launch_copy_rows_u8(q + M * 24, B, nullptr, ctx->d_allele8, M, rows, n, M, ctx->stream);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->qtl_rows_n = 0;               // (the rows a cnf2_sweep_qtl left are no longer this state's)
     ctx->windows_dirty = true;          // rows changed: the "homozygous everywhere" flags must be derived again
     return CNF2_OK;
 }

@@ -7,6 +7,7 @@
 #include <string>
 
 #include "cnf2_engine.h"
+#include "cnf2_qtl_host.h"
 #include "cnf2_remap.h"
 
 using namespace cnf2host;
@@ -298,6 +299,24 @@ int cnf2h_write_map(const char* path, const double* pos, int n_markers, const in
     if (!cnf2host::write_map_checked(path, pos, n_markers, chromstarts, n_chrom, &err)) {
         g_err = err;
         return -3;
+    }
+    return 0;
+}
+
+int cnf2h_qtl_permutations(int n, int n_perm, uint64_t seed, const uint8_t* use, const int32_t* strata, int32_t* perm_out)
+{
+    if (n < 1 || n_perm < 0 || !perm_out) return -2;
+    cnf2host::qtl_permutations(n, n_perm, seed, use, strata, perm_out);
+    return 0;
+}
+
+int cnf2h_qtl_null_residuals(int n, int n_traits, const double* pheno, int n_cov, const double* cov, const uint8_t* use,
+                             double* res_out)
+{
+    if (n < 1 || n_traits < 1 || !pheno || n_cov < 0 || n_cov > 8 || (n_cov > 0 && !cov) || !use || !res_out) return -2;
+    if (!cnf2host::qtl_null_residuals(n, n_traits, pheno, n_cov, cov, use, res_out)) {
+        g_err = "the null design [1, cov] of the used individuals has no full rank";
+        return -2;
     }
     return 0;
 }

@@ -1,0 +1,152 @@
+// cnf2_qtl_host.h -- the host side of `cnF2freq --qtl` (and cnf2h_qtl_permutations of include/cnf2host.h): the phenotype
+// table, the permutations and null-model residuals of a permutation test by the rules of cnf2freq_amd/qtl.py, and the
+// thresholds.  The scan itself is cnf2_qtl_scan / cnf2_sweep_qtl of include/cnf2hip.h; nothing here regresses on markers.
+#ifndef CNF2_QTL_HOST_H
+#define CNF2_QTL_HOST_H
+
+#include <math.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <fstream>
+#include <map>
+#include <numeric>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "../cnf2_qtl.h"
+
+namespace cnf2host {
+
+// value number idx of stream seed: synth.splitmix64 of the Python package
+inline uint64_t qtl_splitmix64(uint64_t seed, uint64_t idx)
+{
+    uint64_t z = seed + (idx + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// perm[P][n] by the rule of qtl.permutations: within every stratum the used individuals, ascending, are ordered by the key
+// splitmix64(seed, p n + i) with a stable sort; unused individuals map to themselves.  use / strata may be null.
+inline void qtl_permutations(int n, int P, uint64_t seed, const uint8_t* use, const int32_t* strata, int32_t* perm)
+{
+    std::map<int32_t, std::vector<int32_t>> groups;
+    for (int i = 0; i < n; i++)
+        if (!use || use[i]) groups[strata ? strata[i] : 0].push_back(i);
+    std::vector<uint64_t> key(n);
+    for (int p = 0; p < P; p++) {
+        int32_t* row = perm + (size_t)p * n;
+        for (int i = 0; i < n; i++) {
+            row[i] = i;
+            key[i] = qtl_splitmix64(seed, (uint64_t)p * (uint64_t)n + (uint64_t)i);
+        }
+        for (const auto& g : groups) {
+            std::vector<int32_t> order(g.second);
+            std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[a] < key[b]; });
+            for (size_t j = 0; j < order.size(); j++) row[g.second[j]] = order[j];
+        }
+    }
+}
+
+// res[n][T]: the residuals of every phenotype column on [1, cov] over the used individuals, 0 for the others
+// (qtl.null_residuals).  false when the null design has no Cholesky factor.
+inline bool qtl_null_residuals(int n, int T, const double* pheno, int K, const double* cov, const uint8_t* use, double* res)
+{
+    using namespace cnf2;
+    const int nx = K + 1;
+    auto      x  = [&](int i, int k) { return k == 0 ? 1.0 : cov[(size_t)i * K + (k - 1)]; };
+    double    S[QTL_NX * QTL_NX] = {0.0};
+    for (int i = 0; i < n; i++)
+        if (use[i])
+            for (int j = 0; j < nx; j++)
+                for (int k = 0; k <= j; k++) S[j * QTL_NX + k] += x(i, j) * x(i, k);
+    std::fill(res, res + (size_t)n * T, 0.0);
+    if (!qtl_cholesky(S, nx)) return false;
+    for (int t = 0; t < T; t++) {
+        double b[QTL_NX] = {0.0};
+        for (int i = 0; i < n; i++)
+            if (use[i])
+                for (int k = 0; k < nx; k++) b[k] += x(i, k) * pheno[(size_t)i * T + t];
+        qtl_chol_solve(S, nx, b);
+        for (int i = 0; i < n; i++)
+            if (use[i]) {
+                double fit = 0.0;
+                for (int k = 0; k < nx; k++) fit += x(i, k) * b[k];
+                res[(size_t)i * T + t] = pheno[(size_t)i * T + t] - fit;
+            }
+    }
+    return true;
+}
+
+// the (1 - alpha) threshold of P maxima (sorted in place): the order statistic number ceil((1 - alpha) P), as qtl.thresholds
+inline double qtl_threshold(std::vector<double>& maxima, double alpha)
+{
+    std::sort(maxima.begin(), maxima.end());
+    const int P = (int)maxima.size();
+    const int k = std::min(P - 1, std::max(0, (int)ceil((1.0 - alpha) * P) - 1));
+    return maxima[k];
+}
+
+// A whitespace table: a header "id name...", then one line per individual; "NA" or "-" is missing (NaN)
+struct PhenoTable {
+    std::vector<std::string>         columns;   // without the id column
+    std::vector<std::string>         ids;
+    std::vector<std::vector<double>> rows;      // [ids][columns]
+};
+
+inline bool read_pheno_table(const std::string& path, PhenoTable& T, std::string* err)
+{
+    std::ifstream in(path);
+    if (!in) {
+        *err = "cannot read " + path;
+        return false;
+    }
+    std::string line, tok;
+    int         lineno = 0;
+    while (std::getline(in, line)) {
+        lineno++;
+        std::istringstream       ss(line);
+        std::vector<std::string> f;
+        while (ss >> tok) f.push_back(tok);
+        if (f.empty()) continue;
+        if (T.columns.empty() && T.ids.empty()) {
+            if (f.size() < 2) {
+                *err = path + ": the header needs an id column and at least one name";
+                return false;
+            }
+            T.columns.assign(f.begin() + 1, f.end());
+            continue;
+        }
+        if (f.size() != T.columns.size() + 1) {
+            *err = path + ": line " + std::to_string(lineno) + " has " + std::to_string(f.size()) + " fields, the header " +
+                   std::to_string(T.columns.size() + 1);
+            return false;
+        }
+        std::vector<double> v;
+        for (size_t k = 1; k < f.size(); k++) {
+            if (f[k] == "NA" || f[k] == "-") {
+                v.push_back(NAN);
+                continue;
+            }
+            char*        end = nullptr;
+            const double x = strtod(f[k].c_str(), &end);
+            if (*end != 0 || !std::isfinite(x)) {
+                *err = path + ": line " + std::to_string(lineno) + ": \"" + f[k] + "\" is not a number, NA or -";
+                return false;
+            }
+            v.push_back(x);
+        }
+        T.ids.push_back(f[0]);
+        T.rows.push_back(v);
+    }
+    if (T.columns.empty()) {
+        *err = path + ": no header";
+        return false;
+    }
+    return true;
+}
+
+} // namespace cnf2host
+#endif

@@ -3,6 +3,7 @@
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
 //            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
 //            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]] [--origins F]
+//            [--qtl F --phenofile P [--qtl-covariates name,name] [--qtl-permutations K] [--qtl-seed S] [--qtl-additive]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -62,6 +63,18 @@
 // "chrom<TAB>pos<TAB>contributors<TAB>" and the four column sums ("%.5lf"): the expected class counts.  --output is the
 // same with or without it.  Single GPU only.
 //
+// --qtl F --phenofile P (not flags of the reference): after the last round, and before a --remap changes the map, a QTL scan
+// of the last round's state (cnf2_sweep_qtl: Haley-Knott regression on the origin rows).  P is a whitespace table: a header
+// "id name...", then one line per individual keyed by the pedigree file's names; NA or - is a missing value.  Every column
+// is a trait unless --qtl-covariates names it (fixed effects, at most 8).  Analysed individuals that are absent from P, or
+// lack a covariate, are not used; a trait's missing values leave their individuals out of that trait's scan.  A name in P
+// that the pedigree does not know, or a covariate that P does not have, is an error that names it.  F: per marker
+// "chrom<TAB>pos<TAB>n<TAB>rank" (n and rank of the first trait's individuals), then per trait "<TAB>LOD<TAB>a<TAB>d" ("%.5lf",
+// "-" for the effect of a dropped column); with --qtl-permutations K > 0, after a blank line, per trait
+// "name<TAB>5 %<TAB>1 %": the genome-wide thresholds from K permutations of the null model's residuals, made from
+// --qtl-seed by the rule of cnf2freq_amd/qtl.py (cnf2h_qtl_permutations).  --qtl-additive drops the dominance column.
+// --output is the same with or without it.  Single GPU only.
+//
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
 // has no compute path of its own and fails if no GPU is present.  Out of scope: the toulbar2
 // bridge and the haplotype inversions it decides, all non-PlantImpute readers.
@@ -80,6 +93,7 @@
 #include <vector>
 
 #include "cnf2_engine.h"
+#include "cnf2_qtl_host.h"
 #include "cnf2_readers.h"
 #include "cnf2_rccl_transport.h"
 #include "cnf2_remap.h"
@@ -119,6 +133,14 @@ struct Options {
     double      loo_threshold = 5.0;     // --loo-threshold X: cells at or above X nats are listed
     bool        loo_threshold_set = false;
     std::string origins;                 // --origins F: grandparental origin probabilities of the last round's state
+    std::string qtl, phenofile;          // --qtl F --phenofile P: QTL scan of the last round's state
+    std::string qtl_covariates;          // --qtl-covariates name,name
+    int         qtl_permutations = 0;    // --qtl-permutations K
+    unsigned long long qtl_seed = 0;     // --qtl-seed S
+    bool        qtl_additive = false;    // --qtl-additive
+    bool        qtl_extra_set = false;   // one of the four above was given
+    PhenoTable  pheno;                   // P as read (main, before any rank starts)
+    std::vector<int> qtl_cov_cols, qtl_trait_cols;     // columns of pheno
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
     int         remap_iterations = 1;
     bool        remap_iterations_set = false;
@@ -190,6 +212,21 @@ static bool parse(int argc, char** argv, Options& o)
             }
         }
         else if (a == "--origins") o.origins = val();
+        else if (a == "--qtl") o.qtl = val();
+        else if (a == "--phenofile") o.phenofile = val();
+        else if (a == "--qtl-covariates") {
+            o.qtl_covariates = val();
+            o.qtl_extra_set  = true;
+        }
+        else if (a == "--qtl-permutations") {
+            o.qtl_permutations = atoi(val().c_str());
+            o.qtl_extra_set    = true;
+        }
+        else if (a == "--qtl-seed") {
+            o.qtl_seed      = strtoull(val().c_str(), nullptr, 0);
+            o.qtl_extra_set = true;
+        }
+        else if (a == "--qtl-additive") o.qtl_additive = o.qtl_extra_set = true;
         else if (a == "--remap") o.remap = val();
         else if (a == "--remap-iterations") {
             o.remap_iterations = atoi(val().c_str());
@@ -209,6 +246,7 @@ static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -299,6 +337,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.place.empty()) place_markers(opt, P, ctx);
     if (world == 1 && !opt.loo.empty()) loo_costs(opt, P, ctx);
     if (world == 1 && !opt.origins.empty()) origin_rows(opt, P, ctx);
+    if (world == 1 && !opt.qtl.empty()) qtl_scan(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -526,6 +565,155 @@ static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.origins);
 }
 
+// --phenofile against the pedigree and --qtl-covariates, before anything runs: false with a message that names what is wrong
+static bool prepare_qtl(Options& opt, const Pedigree& P)
+{
+    std::string err;
+    if (!read_pheno_table(opt.phenofile, opt.pheno, &err)) {
+        fprintf(stderr, "%s\n", err.c_str());
+        return false;
+    }
+    std::string unknown;
+    for (const std::string& id : opt.pheno.ids) {
+        const auto it = P.index.find(id);
+        if (it == P.index.end() || it->second < 0) unknown += " " + id;
+    }
+    if (!unknown.empty()) {
+        fprintf(stderr, "%s: not in the pedigree:%s\n", opt.phenofile.c_str(), unknown.c_str());
+        return false;
+    }
+    std::vector<std::string> want;
+    std::istringstream       ss(opt.qtl_covariates);
+    for (std::string tok; std::getline(ss, tok, ',');)
+        if (!tok.empty()) want.push_back(tok);
+    std::string missing;
+    for (const std::string& w : want) {
+        const auto it = std::find(opt.pheno.columns.begin(), opt.pheno.columns.end(), w);
+        if (it == opt.pheno.columns.end()) missing += " " + w;
+        else opt.qtl_cov_cols.push_back((int)(it - opt.pheno.columns.begin()));
+    }
+    if (!missing.empty()) {
+        fprintf(stderr, "--qtl-covariates: not a column of %s:%s\n", opt.phenofile.c_str(), missing.c_str());
+        return false;
+    }
+    if (opt.qtl_cov_cols.size() > 8) {
+        fprintf(stderr, "--qtl-covariates: at most 8\n");
+        return false;
+    }
+    for (int k = 0; k < (int)opt.pheno.columns.size(); k++)
+        if (std::find(opt.qtl_cov_cols.begin(), opt.qtl_cov_cols.end(), k) == opt.qtl_cov_cols.end()) opt.qtl_trait_cols.push_back(k);
+    if (opt.qtl_trait_cols.empty()) {
+        fprintf(stderr, "%s: every column is a covariate, no trait is left\n", opt.phenofile.c_str());
+        return false;
+    }
+    return true;
+}
+
+// --qtl after the last round (single GPU), like --origins: the traits grouped by their pattern of missing values, the first
+// group through cnf2_sweep_qtl, the others and the permutations on the rows that call left in the context
+static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::vector<double>  lod((size_t)T * M, 0.0), coef((size_t)T * M * 2, NAN), thr((size_t)T * 2, 0.0);
+    std::vector<int32_t> rank0(M, 0), nused0(C, 0);
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    std::vector<std::vector<int>> order;                           // the first trait's group first
+    std::vector<std::vector<uint8_t>> uses;
+    for (const auto& g : groups)
+        if (g.second[0] == 0) order.insert(order.begin(), g.second), uses.insert(uses.begin(), g.first);
+        else order.push_back(g.second), uses.push_back(g.first);
+    const uint32_t flags = opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0;
+    bool swept = false;
+    for (size_t g = 0; g < order.size(); g++) {
+        const std::vector<int>&     tr = order[g];
+        const std::vector<uint8_t>& u  = uses[g];
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M), cf((size_t)Tg * M * 2), rss((size_t)Tg * C);
+        std::vector<int32_t> rk(M), nu(C);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc;
+        if (!swept) {
+            std::vector<double> f((size_t)N * C * 8), ll((size_t)N * C);
+            rc = cnf2_sweep_qtl(ctx, 0, N, f.data(), ll.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                l.data(), cf.data(), rk.data(), rss.data(), nu.data(), nullptr, flags);
+            swept = true;
+        } else
+            rc = cnf2_qtl_scan(ctx, N, nullptr, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr, l.data(), cf.data(),
+                               rk.data(), rss.data(), nu.data(), nullptr, flags | CNF2_QTL_ORIGIN_DEVICE);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl: ") + cnf2_last_error(ctx));
+        if (g == 0) rank0 = rk, nused0 = nu;
+        for (int t = 0; t < Tg; t++) {
+            std::copy(l.begin() + (size_t)t * M, l.begin() + (size_t)(t + 1) * M, lod.begin() + (size_t)tr[t] * M);
+            std::copy(cf.begin() + (size_t)t * M * 2, cf.begin() + (size_t)(t + 1) * M * 2, coef.begin() + (size_t)tr[t] * M * 2);
+        }
+        if (NP > 0) {
+            std::vector<int32_t> perm((size_t)NP * N);
+            std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * C);
+            qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+            // (with fewer than K + 4 individuals nothing is scanned and every maximum is 0, whatever is permuted: the residuals
+            // stay 0; with enough of them a null design without full rank -- a constant covariate -- is an error, not zeros)
+            const int n_u = (int)std::count(u.begin(), u.end(), (uint8_t)1);
+            if (n_u >= K + 4 && !qtl_null_residuals(N, Tg, yg.data(), K, K ? cov.data() : nullptr, u.data(), res.data()))
+                throw EngineError(CNF2_ERR_ARG, "--qtl-permutations: the null design (intercept and covariates) of the individuals used for " +
+                                                    opt.pheno.columns[opt.qtl_trait_cols[tr[0]]] + " has no full rank");
+            rc = cnf2_qtl_scan(ctx, N, nullptr, Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, NP, perm.data(), l.data(),
+                               cf.data(), rk.data(), rss.data(), nu.data(), pm.data(), flags | CNF2_QTL_ORIGIN_DEVICE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl permutations: ") + cnf2_last_error(ctx));
+            for (int t = 0; t < Tg; t++) {
+                std::vector<double> mx(NP, 0.0);
+                for (int p = 0; p < NP; p++)
+                    for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[((size_t)p * Tg + t) * C + c]);
+                thr[(size_t)tr[t] * 2]     = qtl_threshold(mx, 0.05);
+                thr[(size_t)tr[t] * 2 + 1] = qtl_threshold(mx, 0.01);
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtl.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtl);
+    auto effect = [&](double v) {
+        if (v != v) fprintf(out, "\t-");
+        else fprintf(out, "\t%.5lf", v);
+    };
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+            fprintf(out, "%d\t%.5lf\t%d\t%d", c + 1, P.pos[m], (int)nused0[c], (int)rank0[m]);
+            for (int t = 0; t < T; t++) {
+                fprintf(out, "\t%.5lf", lod[(size_t)t * M + m]);
+                effect(coef[((size_t)t * M + m) * 2]);
+                effect(coef[((size_t)t * M + m) * 2 + 1]);
+            }
+            fprintf(out, "\n");
+        }
+    if (NP > 0) {
+        fprintf(out, "\n");
+        for (int t = 0; t < T; t++)
+            fprintf(out, "%s\t%.5lf\t%.5lf\n", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str(), thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtl);
+}
+
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
 // reduce-scatter, all-gather, the hit-counter sum, a barrier and the host broadcast on the context's exchange buffer, through
 // the same entry the engine calls.  (Two ranks need two GPUs: RCCL refuses two ranks on one device.)
@@ -646,6 +834,23 @@ int main(int argc, char** argv)
         fprintf(stderr, "--origins needs a single GPU (--gpus 1): the ranks' sums are not reduced\n");
         return 2;
     }
+    if (opt.gpus > 1 && !opt.qtl.empty()) {
+        fprintf(stderr, "--qtl needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtl.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE\n");
+        return 2;
+    }
+    if (!opt.qtl.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtl FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtl_permutations < 0) {
+        fprintf(stderr, "--qtl-permutations must not be negative\n");
+        return 2;
+    }
+    if (!opt.qtl.empty() && !prepare_qtl(opt, P)) return 2;
     if (opt.loo_threshold_set && opt.loo.empty()) {
         fprintf(stderr, "--loo-threshold needs --loo FILE\n");
         return 2;

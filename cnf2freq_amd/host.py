@@ -12,7 +12,8 @@ LIB_PATH = os.environ.get("CNF2HOST_LIB") or os.path.join(_HERE, "libcnf2host.so
 
 SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_get_dims", "cnf2h_destroy", "cnf2h_last_error", "cnf2h_postmarkerdata", "cnf2h_iteration",
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
-           "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map"]
+           "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
+           "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -56,6 +57,8 @@ def load():
         L.cnf2h_get_state.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_map_mstep.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
         L.cnf2h_write_map.argtypes = [C.c_char_p, vp, i32, vp, i32]
+        L.cnf2h_qtl_permutations.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
+        L.cnf2h_qtl_null_residuals.argtypes = [i32, i32, vp, i32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -77,6 +80,33 @@ def map_mstep(pos, chromstarts, xo_sum, n_contrib, genrec=None):
     rc = L.cnf2h_map_mstep(_p(pos), len(pos), _p(cs), len(cs) - 1, None if g is None else _p(g), _p(xs), _p(cnt), _p(out))
     if rc != 0:
         raise RuntimeError("cnf2h_map_mstep failed (%d)" % rc)
+    return out
+
+
+def qtl_permutations(n, P, seed, use=None, strata=None):
+    """cnf2h_qtl_permutations: perm[P][n] by the rule of cnf2freq_amd.qtl.permutations, as `cnF2freq --qtl` makes them.  CPU only."""
+    L = load()
+    u = None if use is None else np.ascontiguousarray(np.asarray(use) != 0, np.uint8)
+    st = None if strata is None else np.ascontiguousarray(strata, np.int32)
+    out = np.zeros((P, n), np.int32)
+    rc = L.cnf2h_qtl_permutations(n, P, seed, None if u is None else _p(u), None if st is None else _p(st), _p(out))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtl_permutations failed (%d)" % rc)
+    return out
+
+
+def qtl_null_residuals(pheno, cov=None, use=None):
+    """cnf2h_qtl_null_residuals: cnf2freq_amd.qtl.null_residuals as `cnF2freq --qtl` computes them (normal equations).  CPU only."""
+    L = load()
+    y = np.ascontiguousarray(pheno, np.float64)
+    y = np.ascontiguousarray(y[:, None]) if y.ndim == 1 else y
+    n, T = y.shape
+    z = None if cov is None else np.ascontiguousarray(np.asarray(cov, np.float64).reshape(n, -1))
+    u = np.ones(n, np.uint8) if use is None else np.ascontiguousarray(np.asarray(use) != 0, np.uint8)
+    out = np.zeros((n, T))
+    rc = L.cnf2h_qtl_null_residuals(n, T, _p(y), 0 if z is None else z.shape[1], None if z is None else _p(z), _p(u), _p(out))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtl_null_residuals failed (%d): %s" % (rc, (L.cnf2h_last_error() or b"").decode()))
     return out
 
 

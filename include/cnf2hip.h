@@ -114,6 +114,9 @@ enum {
                                      instantiation, which carries all 64 states of a chain, instead of the instantiation that
                                      keeps the states their tables make equal only once.  Same results to the bit; A/B switch
                                      and cross-check.  Ignored where that instantiation is not used */
+    CNF2_QTL_ADDITIVE = 1u << 22, /* cnf2_qtl_scan, cnf2_sweep_qtl: the additive model -- the dominance column is always dropped */
+    CNF2_QTL_ORIGIN_DEVICE = 1u << 23, /* cnf2_qtl_scan: `origin` is a device pointer (aligned to 16 bytes), e.g. the rows a
+                                     cnf2_sweep_origins call with CNF2_OUT_DEVICE filled; they are read in place */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
                                     registers by a transpose through LDS instead of being exchanged by DPP moves (same
@@ -444,6 +447,60 @@ int cnf2_sweep_origins(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factor
  *                       the store by brute force (one thread per state on slots 1 and 2, every mode normalised on its own
  *                       and weighted with exp(factors[s] - loglik)): the cross-check of the sweep's fused form. */
 int cnf2_origin_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
+
+/* QTL scan: where on the map does a trait sit?  Haley-Knott regression of phenotypes on the origin rows of
+ * cnf2_sweep_origins, at every marker, for the observed phenotypes and for permuted ones (the genome-wide threshold of a
+ * peak is a quantile of the permutations' maxima).  One definition for this header, cnf2freq_amd/csrc/cnf2_qtl.h (the small
+ * algebra, shared by host and device code), the kernels and tests/qtl_reference.py:
+ *   origin [n][M][4]   the origin rows; an individual whose row at a chromosome's first marker is all zero is skipped there
+ *   pheno  [n][T]      phenotypes;  use [n] (uint8, NULL = all ones) the individuals to use;  cov [n][K], 0 <= K <= 8, fixed
+ *                      effects.  pheno and cov must be finite where use is set
+ *   perm   [P][n]      (int32) permutations of 0 .. n-1 that give used individuals used ones
+ * Per chromosome c: c_i = use[i] and not skipped, n_c = sum c_i, null design X0 = [c, c z_1 .. c z_K], full design X0 plus
+ * (c a, c d) with a_i = origin[i][m][3] - origin[i][m][0], d_i = origin[i][m][1] + origin[i][m][2] at marker m.
+ * Phenotype columns: R = T (1 + P); column (0, t) is pheno[.][t], column (1 + p, t) is pheno[perm[p][i]][t] at individual
+ * i -- covariates, use and the origin rows stay with i.  Whether raw values or residuals of the null model are permuted is
+ * the caller's choice (cnf2freq_amd/qtl.py permutes residuals: Freedman-Lane).
+ *   S11 = X0'X0, b0 = X0'y, RSS0 = sum c y^2 - b0' S11^-1 b0                                   per chromosome (and column)
+ *   S21 = A'X0, S22 = A'A, G = S21 S11^-1, W = S22 - G S21' (2 x 2)                            per marker
+ *   v = A'y - G b0, dRSS = v' W^-1 v, lod = (n_c / 2) log10(RSS0 / (RSS0 - dRSS)), coef = W^-1 v   per marker and column
+ * Rank rule: W is factored in the order a, d; a column is dropped when its raw diagonal (S22) is 0 or its pivot is below
+ * 1e-8 times that diagonal; CNF2_QTL_ADDITIVE always drops d.  rank[m] (0, 1, 2) depends on the design only.  A dropped
+ * column's coefficient is NaN; rank 0 gives lod = 0 exactly.  A chromosome with n_c < K + 4, or whose X0 has no Cholesky
+ * factor, is not scanned: rank 0, lod 0 and coef NaN at its markers.  A column with RSS0 <= 0 gives lod 0 and coef NaN.  dRSS
+ * is clamped to [0, RSS0 (1 - 2^-52)]: a LOD is finite and not negative.
+ *   lod_out      [T][M]       coef_out [T][M][2] (additive, dominance effect)       rank_out [M] (int32)
+ *   rss0_out     [T][C]       n_used_out [C] (int32) n_c
+ *   perm_max_out [P][T][C]    per permutation, trait and chromosome the largest LOD; NULL exactly when P = 0.  The maximum
+ *                             over C is the genome-wide statistic
+ * cnf2_qtl_scan is the scan alone on rows the caller has: a host array, staged whole (CNF2_ERR_NOMEM if that fails), or with
+ * CNF2_QTL_ORIGIN_DEVICE device memory read in place -- repeated scans (other traits, the permutations, grid positions from
+ * origins.with_positions) then cost the scan only.  n is the number of rows; M and the chromosomes are the uploaded map's.
+ * With CNF2_QTL_ORIGIN_DEVICE and origin NULL the rows are those the context's last cnf2_sweep_qtl left in its buffer (n must
+ * be that call's; CNF2_ERR_STATE when a map, rows or a pedigree have been uploaded or another call has used the buffer
+ * since): further traits and the permutations of a cross without a second sweep and without a device allocation of the
+ * caller's.
+ * cnf2_sweep_qtl sweeps the range as cnf2_sweep_origins does, with the rows in the context's buffer, and scans them:
+ * factors_out / loglik_out are bit-equal to cnf2_sweep, CNF2_STATIC_JOBS, CNF2_FULL_SPILL and CNF2_TIES_GENERAL act as there,
+ * n = ind_end - ind_begin >= 1.  A regression is NOT additive over range splits: scan the individuals of a cross in one call.
+ * pheno, use, cov and perm are host pointers in both calls, also with CNF2_OUT_DEVICE, which makes the outputs (and factors_out
+ * / loglik_out) device pointers.  Outputs are overwritten.  Bad arguments -- a NULL pointer, K or P out of range, a value that
+ * is used and not finite, a row of perm that is no permutation or moves an unused individual -- return CNF2_ERR_ARG and write
+ * nothing.  Both calls synchronise the context's stream, also with CNF2_OUT_DEVICE.
+ * Launches: per call the design (c_i, S11 and its factor per chromosome; S21, S22, G and the pivots per marker, sums over
+ * the individuals in ascending order); per tile of columns the column image Y[n][tile], b0 / RSS0, and the product
+ * C[(m, a|d)][r] = sum_i A(m, i) Y(i, r) on the f64 matrix cores with the epilogue in registers; a finish kernel reduces the
+ * permutations' maxima.  No atomics: a call gives the same bits every time.  The tile holds as many columns as keep the image
+ * under 1 GB (4096 at most); cnf2_set_qtl_columns caps it (0 = no cap) so that several tiles can be exercised at test sizes.
+ * The result does not depend on that cap or on cnf2_set_batch_jobs, to the bit. */
+int cnf2_qtl_scan(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                  int n_cov, const double *cov, int n_perm, const int32_t *perm, double *lod_out, double *coef_out,
+                  int32_t *rank_out, double *rss0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
+int cnf2_sweep_qtl(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out, int n_traits,
+                   const double *pheno, const uint8_t *use, int n_cov, const double *cov, int n_perm, const int32_t *perm,
+                   double *lod_out, double *coef_out, int32_t *rank_out, double *rss0_out, int32_t *n_used_out,
+                   double *perm_max_out, uint32_t flags);
+int cnf2_set_qtl_columns(cnf2_ctx *ctx, int cap);
 
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU

@@ -127,6 +127,19 @@ int cnf2h_map_mstep(const double *pos, int n_markers, const int32_t *chromstarts
  * first position (a new chromosome starts where a value decreases) */
 int cnf2h_write_map(const char *path, const double *pos, int n_markers, const int32_t *chromstarts, int n_chrom);
 
+/* The host side of a QTL permutation test (cnf2_qtl_scan of cnf2hip.h scans; `cnF2freq --qtl` uses these):
+ *  cnf2h_qtl_permutations    perm_out[n_perm][n] (int32): permutation p gives individual i the phenotype of perm[p][i].  Within
+ *                            every stratum (strata[n], NULL = one) the used individuals (use[n], NULL = all), in ascending
+ *                            order idx[0..k), are ordered by the key splitmix64(seed, p n + i) with a stable sort:
+ *                            perm[p][idx[j]] = idx[order[j]]; unused individuals map to themselves.  No sequential generator
+ *                            enters: cnf2freq_amd/qtl.py's permutations() gives the same arrays
+ *  cnf2h_qtl_null_residuals  res_out[n][n_traits]: the residuals of every phenotype column on [1, cov] over the used
+ *                            individuals, 0 for the others: with covariates a permutation test permutes these
+ *                            (Freedman-Lane), not the raw values */
+int cnf2h_qtl_permutations(int n, int n_perm, uint64_t seed, const uint8_t *use, const int32_t *strata, int32_t *perm_out);
+int cnf2h_qtl_null_residuals(int n, int n_traits, const double *pheno, int n_cov, const double *cov, const uint8_t *use,
+                             double *res_out);
+
 #ifdef __cplusplus
 }
 #endif
