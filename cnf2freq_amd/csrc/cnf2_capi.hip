@@ -18,6 +18,7 @@
 
 #include "cnf2_device.h"
 #include "cnf2_emission.h"
+#include "cnf2_emtab.h"
 #include "cnf2_plan.h"
 #include "cnf2_qtl.h"
 
@@ -102,6 +103,22 @@ struct cnf2_ctx {
     int                 reserve_blocks = 0;     // workgroup slots left free for concurrent kernels (RCCL)
     int                 batch_jobs = 0;         // cap on the jobs per batch of the batched consumers (0 = what memory allows)
 
+    // line records of the uniform windows (cnf2_emtab.h): the call's lines, the two lines of every window of the call, the
+    // records; host images and the lookup table are kept so that a call allocates nothing in steady state
+    int                  line_cap = -1;            // cnf2_set_line_records (negative: no cap of its own)
+    int32_t              last_lines[4] = {0, 0, 0, 0};   // cnf2_last_line_records
+    unsigned             windows_gen = 0;          // counts the derivations of `windows`
+    // what h_lines / h_line_keys and their device copies describe: a call with the same windows, range and cap reuses them
+    bool                 lines_valid = false;
+    unsigned             lines_gen = 0;
+    int                  lines_begin = 0, lines_n = 0, lines_cap = 0;
+    int                  lines_fit = 1 << 30;      // lines the memory had room for when the record buffer last had to grow
+    std::vector<LineKey> h_lines;
+    std::vector<int32_t> h_line_keys, h_line_hash;
+    DevBuf<LineKey>      d_lines;
+    DevBuf<int32_t>      d_line_keys;
+    DevBuf<LineRec>      d_line_rec;
+
     // workspace
     DevBuf<Job>       d_jobs;
     DevBuf<PackedJob> d_pjobs;
@@ -109,7 +126,7 @@ struct cnf2_ctx {
     DevBuf<double>    d_factors, d_loglik, d_dosage;
     DevBuf<int32_t>   d_lexp;                  // binary exponents of the fast kernel's likelihoods: [n][C][8] then [n][C]
     DevBuf<unsigned long long> d_clock;        // [4] clock stamps of the last plain fast-kernel launch
-    DevBuf<int>       d_jobnext;               // [4] job counters of the fast-kernel launches in flight (KernelParams::job_next)
+    DevBuf<int>       d_jobnext;               // [5] job counters of the fast-kernel launches in flight (KernelParams::job_next)
     DevBuf<double>    d_scratch;               // small parity buffers
 
     // crossover posteriors (cnf2_sweep_crossovers)
@@ -579,6 +596,8 @@ static int prepare_windows(cnf2_ctx* ctx)
         HIP_TRY(ctx, hipMemcpy(ctx->d_slot_rec, ctx->slot_rec.data(), sizeof(int32_t) * 7 * n_dous, hipMemcpyHostToDevice));
     }
     ctx->windows_dirty = false;
+    ctx->windows_gen++;
+    ctx->lines_fit = 1 << 30;
     return CNF2_OK;
 }
 
@@ -638,7 +657,7 @@ static int ready(cnf2_ctx* ctx)
         RC_TRY(ctx->d_clock.ensure(ctx, (size_t)4));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_clock, 0, 4 * sizeof(unsigned long long), ctx->stream));
     }
-    RC_TRY(ctx->d_jobnext.ensure(ctx, (size_t)4));
+    RC_TRY(ctx->d_jobnext.ensure(ctx, (size_t)5));
     return CNF2_OK;
 }
 
@@ -689,6 +708,97 @@ struct SweepMode {
     unsigned long long seed = 0;       // sampling: the generator's seed
 };
 
+// The lines (cnf2_emtab.h LineKey) of the uniform windows among [ind_begin, ind_begin + n): every distinct one gets a number
+// in order of appearance, up to `cap`; ctx->h_line_keys [n][2] = the numbers of a window's two lines, or -1 -1 where the window
+// keeps the ordinary producer: not uniform, a line beyond the cap, or a founder as root or parent -- with all four
+// grandparents present the parents are present too (derive_window), but a parent whose own parents are empty records is a
+// founder, and so may the root be: those branches of the producer are not in the records.  Returns the number of lines.
+// Linear in n; the lookup is an open-addressing table of 4 * CNF2_MAX_LINES entries the context keeps.
+enum { CNF2_MAX_LINES = 64 };
+static int assign_lines(cnf2_ctx* ctx, int ind_begin, int n, int cap)
+{
+    const int H = 4 * CNF2_MAX_LINES;
+    ctx->h_line_keys.resize((size_t)2 * n);
+    ctx->h_line_hash.assign(H, -1);
+    ctx->h_lines.clear();
+    ctx->h_lines.reserve(CNF2_MAX_LINES);
+    cap = std::min(cap, (int)CNF2_MAX_LINES);
+    LineKey prev[2];             // the last key looked up per side, and what it got: neighbours mostly repeat it
+    int     prev_found[2] = {-1, -1};
+    bool    prev_set[2] = {false, false};
+    for (int i = 0; i < n; i++) {
+        const Window& w = ctx->windows[ind_begin + i];
+        int32_t k[2] = {-1, -1};
+        const bool ok = slots_uniform(w.flags) && !((w.flags[0] | w.flags[1] | w.flags[4]) & SLOT_FOUNDER);
+        for (int P = 0; ok && P < 2; P++) {
+            const int s = 1 + 3 * P;
+            if (w.row[s] < 0 || w.row[s + 1] < 0 || w.row[s + 2] < 0) break;
+            LineKey key;
+            key.row_par = w.row[s];
+            key.row_a   = w.row[s + 1];
+            key.row_b   = w.row[s + 2];
+            key.fl_par  = w.flags[s];
+            key.fl_a    = w.flags[s + 1];
+            key.fl_b    = w.flags[s + 2];
+            key.pad     = 0;
+            if (prev_set[P] && memcmp(&prev[P], &key, sizeof(key)) == 0) {
+                k[P] = prev_found[P];
+                continue;
+            }
+            uint32_t h = (uint32_t)key.row_par * 0x9e3779b1u ^ (uint32_t)key.row_a * 0x85ebca6bu ^ (uint32_t)key.row_b * 0xc2b2ae35u ^
+                         ((uint32_t)key.fl_par << 16 | (uint32_t)key.fl_a << 8 | key.fl_b);
+            h ^= h >> 15;
+            int slot = (int)(h % (uint32_t)H), found = -1;
+            for (;; slot = (slot + 1) % H) {
+                const int e = ctx->h_line_hash[slot];
+                if (e < 0) break;
+                if (memcmp(&ctx->h_lines[e], &key, sizeof(key)) == 0) {
+                    found = e;
+                    break;
+                }
+            }
+            if (found < 0 && (int)ctx->h_lines.size() < cap) {
+                found = (int)ctx->h_lines.size();
+                ctx->h_lines.push_back(key);
+                ctx->h_line_hash[slot] = found;
+            }
+            k[P] = found;
+            prev[P] = key;
+            prev_found[P] = found;
+            prev_set[P] = true;
+        }
+        const bool both = k[0] >= 0 && k[1] >= 0;
+        ctx->h_line_keys[2 * (size_t)i]     = both ? k[0] : -1;
+        ctx->h_line_keys[2 * (size_t)i + 1] = both ? k[1] : -1;
+    }
+    return (int)ctx->h_lines.size();
+}
+// assign_lines and the upload of its two tables, unless the context holds them for these windows, this range and this cap
+// already (the windows change with the rows or the pedigree, not from sweep to sweep).  *n_lines = the number of lines.
+static int prepare_lines(cnf2_ctx* ctx, int ind_begin, int n, int cap, int* n_lines)
+{
+    cap = std::max(0, std::min(cap, (int)CNF2_MAX_LINES));
+    if (!(ctx->lines_valid && ctx->lines_gen == ctx->windows_gen && ctx->lines_begin == ind_begin && ctx->lines_n == n &&
+          ctx->lines_cap == cap)) {
+        ctx->lines_valid = false;
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));      // (an earlier call's copies have read the host tables)
+        const int nl = assign_lines(ctx, ind_begin, n, cap);
+        if (nl > 0) {
+            RC_TRY(ctx->d_lines.ensure(ctx, (size_t)CNF2_MAX_LINES));
+            RC_TRY(ctx->d_line_keys.ensure(ctx, (size_t)2 * n));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_lines, ctx->h_lines.data(), sizeof(LineKey) * nl, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_line_keys, ctx->h_line_keys.data(), sizeof(int32_t) * 2 * n, hipMemcpyHostToDevice, ctx->stream));
+        }
+        ctx->lines_gen   = ctx->windows_gen;
+        ctx->lines_begin = ind_begin;
+        ctx->lines_n     = n;
+        ctx->lines_cap   = cap;
+        ctx->lines_valid = true;
+    }
+    *n_lines = (int)ctx->h_lines.size();
+    return CNF2_OK;
+}
+
 // cnf2_sweep, and its modes.  Crossover mode: the untied windows through the fast kernel's crossover instantiation (one
 // pass: likelihoods and posteriors), the tied ones through the tied kernel without rows (their likelihoods, as cnf2_sweep
 // forms them) and then the general kernel's crossover instantiation (their posteriors).  Viterbi mode: the same routing,
@@ -730,9 +840,26 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
     // the plain half-spill sweep: the fast jobs of uniform windows (slots_uniform: crosses of inbred lines) take the fast
     // kernel's instantiation for them (launch_fb_fast), which has an occupancy of its own; the spill slots cover the larger grid
-    size_t n_uniform = 0;
-    if (!(flags & (CNF2_ALL_STATES | CNF2_FULL_SPILL | CNF2_XPOSE)) && (plain || mode.variant == SW_VITERBI))
-        for (size_t j = 0; j < n_fast; j++) n_uniform += slots_uniform(ctx->windows[ind_begin + jp.jobs[j].ind].flags) ? 1 : 0;
+    // ... and, unless CNF2_NO_LINE_RECORDS, the lines of those windows (numbered once per set of windows, range and cap)
+    size_t n_uniform = 0, n_on_records = 0;
+    int    n_lines = 0;
+    const bool uni_ok = !(flags & (CNF2_ALL_STATES | CNF2_FULL_SPILL | CNF2_XPOSE)) && (plain || mode.variant == SW_VITERBI);
+    const int  want_lines = ctx->line_cap >= 0 ? std::min(ctx->line_cap, ctx->lines_fit) : ctx->lines_fit;
+    auto count_uniform = [&]() {
+        n_uniform = n_on_records = 0;
+        const int32_t* keys = n_lines > 0 ? ctx->h_line_keys.data() : nullptr;
+        for (size_t j = 0; j < n_fast; j++) {
+            const int i = jp.jobs[j].ind;
+            if (!slots_uniform(ctx->windows[ind_begin + i].flags)) continue;
+            n_uniform++;
+            if (keys && keys[2 * (size_t)i] >= 0) n_on_records++;
+        }
+    };
+    memset(ctx->last_lines, 0, sizeof(ctx->last_lines));
+    if (uni_ok) {
+        if (n_fast > 0 && !(flags & CNF2_NO_LINE_RECORDS)) RC_TRY(prepare_lines(ctx, ind_begin, n, want_lines, &n_lines));
+        count_uniform();
+    }
     const int fast_per_cu = n_uniform == 0       ? ctx->fast_blocks_per_cu
                             : n_uniform < n_fast ? std::max(ctx->fast_blocks_per_cu, ctx->uni_blocks_per_cu)
                                                  : ctx->uni_blocks_per_cu;
@@ -756,6 +883,28 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         d_l = ctx->d_loglik;
         d_d = ctx->d_dosage;
     }
+
+    // the records of the call's lines, after the spill slots and the outputs: they take at most half of what is left
+    if (n_on_records == 0) n_lines = 0;
+    if (n_lines > 0) {
+        const size_t line_bytes = (size_t)ctx->n_markers * LINE_VALUES * 2 * sizeof(LineRec);
+        if ((size_t)n_lines * line_bytes > ctx->d_line_rec.cap * sizeof(LineRec)) {
+            // the buffer has to grow (not in steady state): lines beyond what fits keep the ordinary producer, from now on
+            HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+            const size_t fit = (ctx->d_line_rec.cap * sizeof(LineRec) + free_b / 2) / line_bytes;
+            if (fit < (size_t)n_lines) {
+                ctx->lines_fit = (int)fit;
+                RC_TRY(prepare_lines(ctx, ind_begin, n, std::min(want_lines, ctx->lines_fit), &n_lines));
+                count_uniform();
+                if (n_on_records == 0) n_lines = 0;
+            }
+        }
+        if (n_lines > 0) RC_TRY(ctx->d_line_rec.ensure(ctx, (size_t)n_lines * ctx->n_markers * LINE_VALUES * 2));
+    }
+    ctx->last_lines[0] = n_lines;
+    ctx->last_lines[1] = n_lines > 0 ? (int32_t)n_on_records : 0;
+    ctx->last_lines[2] = (int32_t)n_uniform - ctx->last_lines[1];
+    ctx->last_lines[3] = (int32_t)std::min<size_t>((size_t)n_lines * ctx->n_markers * LINE_VALUES * 2 * sizeof(LineRec), 0x7fffffff);
 
     KernelParams p;
     base_params(ctx, &p);
@@ -875,6 +1024,13 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         plain_half.n_uniform        = (int)n_uniform;
         plain_half.grid_uniform     = std::min(grid_for(n_uniform, grid_fast), resident_blocks(ctx->n_cu, ctx->uni_blocks_per_cu, ctx->reserve_blocks));
         plain_half.job_next_uniform = ctx->d_jobnext + 3;
+        if (n_lines > 0) {
+            plain_half.lines   = ctx->d_lines;
+            plain_half.n_lines = n_lines;
+            plain_half.n_uniform_rows = ctx->last_lines[2];
+            p.line_rec         = ctx->d_line_rec;
+            p.line_keys        = ctx->d_line_keys;
+        }
         p.clock_out = ctx->d_clock;
         if (mode.variant == SW_VITERBI) {
             // the likelihoods from cnf2_sweep's own launch without rows (the Viterbi instantiation runs the same recursion,
@@ -909,6 +1065,20 @@ int cnf2_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, d
                uint32_t flags)
 {
     return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, dosage_out, flags, SweepMode());
+}
+
+int cnf2_set_line_records(cnf2_ctx* ctx, int lines)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    ctx->line_cap = lines;
+    return CNF2_OK;
+}
+
+int cnf2_last_line_records(cnf2_ctx* ctx, int32_t* out)
+{
+    if (!ctx || !out) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
+    memcpy(out, ctx->last_lines, sizeof(ctx->last_lines));
+    return CNF2_OK;
 }
 
 int cnf2_last_paths(cnf2_ctx* ctx, int32_t* paths_out, int n)

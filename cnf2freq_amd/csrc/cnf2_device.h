@@ -11,6 +11,9 @@
 
 namespace cnf2 {
 
+struct LineRec;     // cnf2_emtab.h
+struct LineKey;
+
 #define CNF2_MINFACTOR_F (-1e15f)  /* settings.h:29 */
 #define CNF2_IGNORED_D (-1e30)     /* cnF2freq.cpp:5378 */
 
@@ -36,9 +39,10 @@ enum SweepVariant : int {
     SW_LOO          = 8,   // leave-one-marker-out mode: per marker the likelihood ratio without the marker's emission (p.loo) and
                            // the marker's unlinked emission mean (p.unl), over every mode with a likelihood; the jobs with a
                            // likelihood counted in p.xo_cnt; no rows
-    SW_ORIGINS      = 9    // origin mode: per marker the four grandparental-origin probabilities (p.org) and P(bit t = 1) of the
+    SW_ORIGINS      = 9,   // origin mode: per marker the four grandparental-origin probabilities (p.org) and P(bit t = 1) of the
                            // six meiosis bits (p.obits), masked sums of the state posterior over the modes the rows count; the
                            // jobs with a likelihood counted in p.xo_cnt; no rows
+    SW_PLAIN_UNIFORM_ROWS = 10  // fb_fast_kernel's UNI instantiation only: SW_PLAIN for the uniform windows without line records
 };
 
 struct KernelParams {
@@ -105,6 +109,11 @@ struct KernelParams {
                                // likewise (-1: skipped); minus its logarithm after loo_finish_kernel
     double*        org;        // origin mode: [n_ind][n_markers][4] P(bit 0 + 2 bit 3 = k), each row summing to 1 (0: skipped)
     double*        obits;      // origin mode: [n_ind][n_markers][6] P(bit t = 1) (0: skipped)
+    // fast kernel's UNI instantiation: the launch's line records (cnf2_emtab.h; [lines][n_markers][LINE_VALUES][2], built by
+    // line_records_kernel in front of the launch) and the two lines of every window [n_ind][2] (offset like windows), -1 -1 for a
+    // window that keeps the ordinary tile producer; NULL = every window does
+    const LineRec* line_rec;
+    const int32_t* line_keys;
 };
 #define CNF2_LEXP_IGNORED (-2147483647 - 1)   /* shift mode not analysed: CNF2_IGNORED_D */
 #define CNF2_LEXP_DEAD    (-2147483647)       /* no likelihood left: CNF2_MINFACTOR_F */
@@ -263,6 +272,11 @@ struct FastVariant {
     bool         half = true, xpose = false, tied = false;
     int          n_uniform = 0, grid_uniform = 0;
     int*         job_next_uniform = nullptr;
+    // the lines whose records the UNI launch reads (KernelParams::line_rec has room for n_lines of them; 0 = no records), and
+    // how many of the n_uniform jobs belong to windows without their lines among them: those are swept by
+    // the UNI instantiation with SW_PLAIN_UNIFORM_ROWS (job counter job_next_uniform + 1)
+    const LineKey* lines = nullptr;
+    int          n_lines = 0, n_uniform_rows = 0;
 };
 // Zeroes the launch's job counter, launches the instantiation (asking once for the tied instantiations' dynamic LDS) and
 // the kernel that takes the logarithms of its likelihoods.  Returns the launches' error; a combination that is not

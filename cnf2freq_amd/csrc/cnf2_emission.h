@@ -66,6 +66,10 @@ CNF2_HD bool slots_homleaf(const uint8_t* f)
     const int gp = f[2] & f[3] & f[5] & f[6];
     return (gp & SLOT_HOM) && (gp & SLOT_PRESENT);
 }
+// What slots_uniform does NOT guarantee: that the root and the parents are not founders.  With all four grandparents present the
+// parents are present too (derive_window), but a parent whose own parents are empty records is SLOT_FOUNDER (and so may the
+// root be), and an empty record's blank row is SLOT_HOM: the producer's root_attop and founder-parent branches are live in a
+// uniform window.  The line records (cnf2_emtab.h) do not hold them; the host leaves such windows to the ordinary producer.
 CNF2_HD bool slots_uniform(const uint8_t* f) { return (f[1] & f[4] & SLOT_HOM) && slots_homleaf(f); }
 
 // Terms of one table entry.  For parent allele fp and grandparent allele fg:

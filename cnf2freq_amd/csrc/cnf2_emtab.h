@@ -419,6 +419,131 @@ CNF2_HD void emtab_part(const PartCfg& c, const Slot& root, const Slot& par, con
                            [&](int kind, int e, double v) { (kind == 0 ? tot : (kind == 1 ? rtot : two))[e] = v; }, cw);
 }
 
+// ---- Line records (uniform windows).  A line is a parent with its two grandparents: three genotype
+// rows and their slot flags.  In a uniform window (slots_uniform, cnf2_emission.h) whose root and parents are not founders,
+// everything emtab_part_views<..., HOMPAR, HOMLEAF> derives from the three ancestors of a lane's line depends on the line, the
+// marker, firstpar and the allele value the root hands down -- not on the individual.  line_record_make evaluates it once
+// (the same device functions on the same operands), emtab_part_rec combines a record with the root's own terms.
+struct LineKey {
+    int32_t row_par, row_a, row_b;        // genotype rows of the parent and of the grandparents pars[0], pars[1]
+    uint8_t fl_par, fl_a, fl_b, pad;      // their slot flags
+};
+enum { LINE_VALUES = 16 };                // incoming allele values the rows can hold (4 bits an allele)
+enum { LR_LIVE = 1u << 16 };              // bits 0-7: entries of the restricted table that hold the value, bits 8-15: of the
+                                          // class-2 table (entry e = sp*4 + bit_ot*2 + bit_tr); LR_LIVE: the unrestricted ones do
+struct LineRec {
+    double   Bp, Cp, Kp;                  // the parent's match of the incoming value (match_affine)
+    double   t0, t1;                      // the traced grandparent's leaf for the value the parent passes on
+    double   oo;                          // the other grandparent's line, finished (does not depend on the root)
+    uint32_t bits, pad[3];
+};
+static_assert(sizeof(LineRec) == 64, "a line record is 64 bytes");
+// record of (line, marker, firstpar, value): [((line * n_markers + marker) * LINE_VALUES + value) * 2 + firstpar]
+
+// a * b + c * d as the sweep kernel's producer rounds it: the first product fused into the sum, the second rounded on its
+// own (what the compiler makes of emtab_part_views' expressions on the device; the host build has no fused operation)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define CNF2_FMA2(a, b, c, d) __builtin_fma((a), (b), (c) * (d))
+#else
+#define CNF2_FMA2(a, b, c, d) ((a) * (b) + (c) * (d))
+#endif
+
+// fl_*: slot flags of the parent, the traced and the other grandparent; v: the value the root hands to the parent
+CNF2_HD void line_record_make(uint32_t fl_par, uint32_t fl_tr, uint32_t fl_ot, int firstpar, int v, const Slot& par,
+                              const Slot& trs, const Slot& ots, LineRec* r)
+{
+    const SlotDirect vp(par), vt(trs), vo(ots);
+    double Bp, Kp, Cp;
+    int    mv;
+    vp.match(v, 0, &Bp, &Kp, &Cp, &mv);
+    const bool bzero = (Bp == 0.0);
+    Leaf Lt, Lo;
+    leaf_make<true, false, false>(vt, fl_tr, mv, vp.allele(0) == 2, &Lt);
+    leaf_make<true, false, false>(vo, fl_ot, vp.allele(1), false, &Lo);
+    // the unrestricted leaf values: a homozygous leaf's phase weights are 0 and 1, so these are its match terms themselves
+    double t0, t1, o0, o1;
+    leaf_value(Lt, 0, 0, &t0, &t1);
+    leaf_value(Lo, 0, 0, &o0, &o1);
+    const double so_p = vp.sure(1);
+    r->Bp = Bp;
+    r->Cp = Cp;
+    r->Kp = Kp;
+    r->t0 = t0;
+    r->t1 = t1;
+    r->oo = CNF2_FMA2(1.0 - so_p, o0, so_p, o1);
+    // which entries hold the value: every factor the restrictions and the class put on an entry is 0 or 1
+    const double pw0 = vp.w(0), pw1 = vp.w(1);
+    const double wq0 = firstpar ? pw1 : pw0, wq1 = firstpar ? pw0 : pw1;
+    const double pm1 = (fl_par & SLOT_RESTRICT0) ? 0.0 : 1.0;
+    uint32_t bits = 0;
+    if (!bzero && wq0 + wq1 != 0.0) bits |= LR_LIVE;
+#pragma unroll
+    for (int kind = 1; kind < 3; kind++)
+#pragma unroll
+        for (int sp = 0; sp < 2; sp++) {
+            const double w = (sp ? wq1 : wq0) + pm1 * (sp ? wq0 : wq1);
+#pragma unroll
+            for (int bo = 0; bo < 2; bo++)
+#pragma unroll
+                for (int bt = 0; bt < 2; bt++) {
+                    double g0, g1, q0, q1;
+                    leaf_value(Lt, bt, kind, &g0, &g1);
+                    leaf_value(Lo, bo, 1, &q0, &q1);
+                    const bool on = !bzero && w != 0.0 && (g0 != 0.0 || g1 != 0.0) && (q0 != 0.0 || q1 != 0.0);
+                    if (on) bits |= 1u << ((kind - 1) * 8 + sp * 4 + bo * 2 + bt);
+                }
+        }
+    r->bits   = bits;
+    r->pad[0] = r->pad[1] = r->pad[2] = 0;
+}
+
+// The 8 entries per table kind of the lane (P, f) from the root's own data and the record of its line, firstpar and
+// handed-down value (root allele f for P = 0, the other one for P = 1).  Same interface as emtab_part_views.  The traced line's
+// term alpha * t0 + beta * t1 is rounded as the ordinary producer rounds it, which is not the same for every entry: the
+// restricted table's entries with bit_tr = 0 fuse the beta product, all others the alpha product.
+template <bool CLASSES, class Out>
+CNF2_HD void emtab_part_rec(int P, int f, const Slot& root, const LineRec& r, Out&& out, double cw[2])
+{
+    const SlotDirect rv(root);
+    const int    mf = rv.allele(f);
+    const double sf = rv.sure(f), so_r = rv.sure(f ^ 1);
+    const double base_r = 1.0 - sf;
+    const double msv_r  = (mf != 0) ? sf : 0.0;
+    cw[0] = rv.w(f ^ 0);
+    cw[1] = rv.w(f ^ 1);
+    if (base_r == 0.0) cw[0] = cw[1] = 0.0;          // !baseval at the root (cnF2freq.cpp:1271)
+    const double u0 = P ? 1.0 - so_r : base_r;
+    const double u1 = P ? so_r : msv_r;
+    const double alpha = u0 * r.Bp;
+    const double beta  = CNF2_FMA2(u0, r.Cp, u1, r.Kp);
+#ifdef CNF2_LINEREC_PER_ENTRY   /* A/B only: records without the one-value form -- every entry its own W * (OO * G), as the
+                                  ordinary producer forms them (W is 0 or 1: the same bits) */
+    const double ga = CNF2_FMA2(alpha, r.t0, beta, r.t1), gb = CNF2_FMA2(beta, r.t1, alpha, r.t0);
+#pragma unroll
+    for (int e = 0; e < 8; e++) out(0, e, ((r.bits & LR_LIVE) ? 1.0 : 0.0) * (r.oo * ga));
+    if (CLASSES) {
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            out(1, e, (double)((r.bits >> e) & 1) * (r.oo * ((e & 1) ? ga : gb)));
+            out(2, e, (double)((r.bits >> (8 + e)) & 1) * (r.oo * ga));
+        }
+    }
+    return;
+#endif
+    const double va = r.oo * CNF2_FMA2(alpha, r.t0, beta, r.t1);
+    const double v0 = (r.bits & LR_LIVE) ? va : 0.0;
+#pragma unroll
+    for (int e = 0; e < 8; e++) out(0, e, v0);
+    if (CLASSES) {
+        const double vb = r.oo * CNF2_FMA2(beta, r.t1, alpha, r.t0);
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            out(1, e, ((r.bits >> e) & 1) ? ((e & 1) ? va : vb) : 0.0);
+            out(2, e, ((r.bits >> (8 + e)) & 1) ? va : 0.0);
+        }
+    }
+}
+
 // Static part of a lane of the tile producer.  The window's arrays are read with constant indices and the lane's
 // slots chosen by selects: an index that depends on the lane would put a copy of the window into scratch memory.
 CNF2_HD void make_part(const Window& w, int part, PartCfg* c, int32_t* row_par, int32_t* row_tr, int32_t* row_ot)

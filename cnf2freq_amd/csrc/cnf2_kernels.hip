@@ -1151,6 +1151,103 @@ __device__ __forceinline__ void produce_tile(const KernelParams& p, const FastCt
     else produce_row<CLASSES, false, false, false, false, STRIDE>(c, tab, m0 + c.mi <= last, raw);
 }
 
+// ---- The tile producer on line records (UNI instantiation; cnf2_emtab.h): a lane loads the root's data
+// and the record of (its line, the marker, firstpar, the allele the root hands down) instead of four window members.  The
+// record's address depends on the root's allele byte, so that byte is requested one tile earlier than the rest.
+struct RawRec {
+    uint8_t  ap;                          // the root
+    double   s0, s1, hw;
+    double   Bp, Cp, Kp, t0, t1, oo;      // the record (LineRec)
+    uint32_t bits;
+    double   tq0, tq1;                    // scaled recombination odds of the gap this marker's row carries (see produce_tile)
+};
+__device__ __forceinline__ int clamp_marker(int m, int lo_m, int hi_m) { return m < lo_m ? lo_m : (m > hi_m ? hi_m : m); }
+__device__ __forceinline__ uint8_t load_root_allele(const KernelParams& p, const FastCtx& c, int m0, int lo_m, int hi_m)
+{
+    return p.allele8[(size_t)c.row_root * p.n_markers + clamp_marker(m0 + c.mi, lo_m, hi_m)];
+}
+// ap: load_root_allele of the same tile; rec_row: line * n_markers of this lane's line
+template <int TQ_SHIFT>
+__device__ __forceinline__ void load_rec(const KernelParams& p, const FastCtx& c, uint32_t rec_row, int m0, int lo_m, int hi_m,
+                                         uint8_t ap, RawRec* r)
+{
+    const int     m = clamp_marker(m0 + c.mi, lo_m, hi_m);
+    const size_t  i = (size_t)c.row_root * p.n_markers + m;
+    const double2 su = p.sure[i];
+    r->ap = ap;
+    r->s0 = su.x;
+    r->s1 = su.y;
+    r->hw = p.hw[i];
+    // the value handed down: root allele f for the line of parent 0, the other one for parent 1
+    const int v = ((c.pc.P ^ c.pc.f) & 1) ? (ap >> 4) : (ap & 15);
+    const double2* q = (const double2*)(p.line_rec + (((size_t)(rec_row + (uint32_t)m) * LINE_VALUES + v) * 2 + c.pc.firstpar));
+    // (ordinary loads: every wave of the launch reads these records, they should stay in the caches)
+    const double2 q0 = q[0], q1 = q[1], q2 = q[2];
+    r->Bp   = q0.x;
+    r->Cp   = q0.y;
+    r->Kp   = q1.x;
+    r->t0   = q1.y;
+    r->t1   = q2.x;
+    r->oo   = q2.y;
+    r->bits = ((const uint32_t*)q)[12];
+    const int     mt = m + TQ_SHIFT;
+    const double2 tq = p.tq[mt < 0 ? 0 : mt];
+    r->tq0 = tq.x;
+    r->tq1 = tq.y;
+}
+template <bool CLASSES>
+__device__ __forceinline__ void produce_row_rec(const FastCtx& c, double* tab, bool valid, const RawRec& raw)
+{
+    if (valid) {
+        const Slot root = unpack_slot(raw.ap, raw.s0, raw.s1, raw.hw);
+        LineRec rec;
+        rec.Bp   = raw.Bp;
+        rec.Cp   = raw.Cp;
+        rec.Kp   = raw.Kp;
+        rec.t0   = raw.t0;
+        rec.t1   = raw.t1;
+        rec.oo   = raw.oo;
+        rec.bits = raw.bits;
+        double  cw[2];
+        double* row = tab + c.mi * TAB_STRIDE;
+        double* rb  = row + c.idx_base;
+        emtab_part_rec<CLASSES>(c.pc.P, c.pc.f, root, rec,
+                                [&](int kind, int e, double v) {        // (the entry's place: see produce_row)
+                                    const int b = e & 3;
+                                    const int k = b == 0 ? 0 : (b == 1 ? c.idx_k01 : (b == 2 ? c.idx_k10 : 6));
+                                    rb[(kind == 0 ? 0 : (kind == 1 ? TAB_R : TAB_2)) + (e >> 2) * 8 + k] = v;
+                                },
+                                cw);
+        if ((c.part & 5) == 0) {
+            row[TAB_C + c.pc.f * 2 + 0] = cw[0];
+            row[TAB_C + c.pc.f * 2 + 1] = cw[1];
+        }
+        if (c.part == 0) *(double2*)(row + TAB_T) = make_double2(raw.tq0, raw.tq1);
+    }
+}
+// One thread per record of the launch's lines: [line][marker][value][firstpar]
+__global__ __launch_bounds__(256) void line_records_kernel(const LineKey* lines, int n_lines, const uint8_t* allele8,
+                                                           const double2* sure, const double* hw, int n_markers, LineRec* out)
+{
+    const size_t per_line = (size_t)n_markers * LINE_VALUES * 2;
+    const size_t t        = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= per_line * (size_t)n_lines) return;
+    const int     firstpar = (int)(t & 1), v = (int)((t >> 1) & (LINE_VALUES - 1));
+    const size_t  lm = t / (LINE_VALUES * 2);
+    const int     m = (int)(lm % (size_t)n_markers);
+    const LineKey k = lines[lm / (size_t)n_markers];
+    auto slot = [&](int32_t row) {
+        const size_t i = (size_t)row * n_markers + m;
+        const double2 s = sure[i];
+        return unpack_slot(allele8[i], s.x, s.y, hw[i]);
+    };
+    const Slot par = slot(k.row_par), ga = slot(k.row_a), gb = slot(k.row_b);
+    LineRec r;
+    line_record_make(k.fl_par, firstpar ? k.fl_b : k.fl_a, firstpar ? k.fl_a : k.fl_b, firstpar, v, par, firstpar ? gb : ga,
+                     firstpar ? ga : gb, &r);
+    out[t] = r;
+}
+
 // Raw inputs of one lane of the tile producer's first phase (ONE window member at one marker), requested a
 // whole tile ahead.
 struct RawOne {
@@ -1291,9 +1388,16 @@ struct BwdState {
 #ifndef CNF2_UNI_MIN_BLOCKS
 #define CNF2_UNI_MIN_BLOCKS 3
 #endif
-template <bool HALF, int STOREW = 0, bool XPOSE = false, bool TIED = false, bool UNI = false>
+// UNI comes in two forms over the same job list, each skipping the other's jobs.  REC, the instantiation with STOREW =
+// SW_PLAIN: the tile producer on the launch's line records (produce_row_rec), for the windows that have their two lines in
+// p.line_keys.  STOREW = SW_PLAIN_UNIFORM_ROWS: the plain sweep all the same, with the ordinary tile producer, for the uniform
+// windows that have not (all of them when p.line_keys is NULL).
+template <bool HALF, int STOREW_ARG = 0, bool XPOSE = false, bool TIED = false, bool UNI = false>
 __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MIN_BLOCKS : 2) void fb_fast_kernel(KernelParams p)
 {
+    static_assert(UNI || STOREW_ARG != SW_PLAIN_UNIFORM_ROWS, "a form of the uniform-state variant");
+    constexpr int  STOREW = STOREW_ARG == SW_PLAIN_UNIFORM_ROWS ? (int)SW_PLAIN : STOREW_ARG;
+    constexpr bool REC    = UNI && STOREW_ARG != SW_PLAIN_UNIFORM_ROWS;
     static_assert(!UNI || (HALF && STOREW == SW_PLAIN && !XPOSE && !TIED), "the uniform-state variant exists for the plain half-spill sweep");
     static_assert(CNF2_UNI_REGS == 2 || CNF2_UNI_REGS == 8, "registers per lane and vector of the uniform-state variant");
     constexpr int  NR   = UNI ? CNF2_UNI_REGS : 8;      // registers per lane and vector
@@ -1386,6 +1490,18 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
         hom = __builtin_amdgcn_readfirstlane(hom);
         if (UNI && hom != 2) continue;
         if (PAIR && (p.flags & KP_SKIP_UNIFORM) && hom == 2) continue;
+        // UNI: the window's two lines, where the launch holds records for them (wave-uniform); else the ordinary producer
+        uint32_t rec_row = 0;      // line * n_markers of this lane's line
+        uint8_t  ap_next = 0;      // the root's allele byte of the tile after the one whose inputs are in flight
+        if constexpr (UNI) {
+            bool on_rec = false;
+            if (p.line_keys) {
+                const int32_t k0 = p.line_keys[2 * (size_t)jb.ind], k1 = p.line_keys[2 * (size_t)jb.ind + 1];
+                on_rec  = __builtin_amdgcn_readfirstlane((int)(k0 >= 0 && k1 >= 0)) != 0;
+                rec_row = (uint32_t)(c.pc.P ? k1 : k0) * (uint32_t)p.n_markers;
+            }
+            if (on_rec != REC) continue;
+        }
         const int n_combo = TIED ? __builtin_amdgcn_readfirstlane(1 << w.n_groups) : 1;
         // TIED: the tie groups of this lane's three slots (part_forces), one byte each, so that the window itself need not
         // stay live for the combinations' loop
@@ -1496,9 +1612,20 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
             }
         };
         RawSlots raw;
-        load_raw<0>(p, c, first, first, last, &raw);
+        RawRec   rraw;
+        if constexpr (REC) {
+            load_rec<0>(p, c, rec_row, first, first, last, load_root_allele(p, c, first, first, last), &rraw);
+            ap_next = load_root_allele(p, c, first + 8, first, last);
+        } else load_raw<0>(p, c, first, first, last, &raw);
         for (int t = 0; t < ntile; t++) {
             const int m0 = first + t * 8;
+            if constexpr (REC) {
+                produce_row_rec<false>(c, tab, m0 + c.mi <= last, rraw);
+                if (t + 1 < ntile) {
+                    load_rec<0>(p, c, rec_row, m0 + 8, first, last, ap_next, &rraw);
+                    ap_next = load_root_allele(p, c, m0 + 16, first, last);
+                }
+            } else
 #ifdef CNF2_X_NOPRODUCE  /* timing ablation only: results are wrong */
             if (t == 0)
 #endif
@@ -2143,7 +2270,10 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
             else if constexpr (UNI) transition_uniform(S.b, r_m.x, r_m.y);
             else transition_scaled(S.b, r_m.x, r_m.y);
         };
-        load_raw<-1>(p, c, first + (ntile - 1) * 8, first, last, &raw);
+        if constexpr (REC) {
+            load_rec<-1>(p, c, rec_row, first + (ntile - 1) * 8, first, last, load_root_allele(p, c, first + (ntile - 1) * 8, first, last), &rraw);
+            ap_next = load_root_allele(p, c, first + (ntile - 2) * 8, first, last);
+        } else load_raw<-1>(p, c, first + (ntile - 1) * 8, first, last, &raw);
         for (int t = ntile - 1; t >= 0; t--) {
             const int m0 = first + t * 8;
             // TIED: the state at the tile's start, restored for every combination: beta, the mantissas and the exponents from
@@ -2176,6 +2306,15 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
                 if (combo > 0) load_row(HALF ? ((((m0 + 7 < last) ? m0 + 7 : last) - first) >> 1) : (((m0 + 7 < last) ? m0 + 7 : last) - first));
                 forces(combo);
             }
+            if constexpr (REC) {
+                produce_row_rec<ROWS>(c, tab, m0 + c.mi <= last, rraw);
+                // the next tile's inputs a whole tile ahead, as in the forward pass: this form has the registers to hold them
+                // across the marker loop
+                if (t > 0) {
+                    load_rec<-1>(p, c, rec_row, m0 - 8, first, last, ap_next, &rraw);
+                    ap_next = load_root_allele(p, c, m0 - 16, first, last);
+                }
+            } else
 #ifdef CNF2_X_NOPRODUCE  /* timing ablation only: results are wrong */
             if (t == ntile - 1)
 #endif
@@ -2224,6 +2363,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
                 int m0x = (combo + 2 < n_combo) ? m0 : m0 - 8;
                 asm volatile("" : "+s"(m0x));
                 if (t > 0 || combo + 2 < n_combo) load_raw<-1>(p, c, m0x, first, last, &raw);
+            } else if constexpr (REC) {
             } else if (t > 0) load_raw<-1>(p, c, m0 - 8, first, last, &raw);
 #endif
             // tile epilogue: lanes (marker mi = lane >> 3, eighth sub = lane & 7) add up the 3 x 64 partials
@@ -4632,8 +4772,29 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     if (n_uni > 0) {
         KernelParams pu = p;
         if (pu.job_next) pu.job_next = v.job_next_uniform;
-        zero_job_counter(pu, stream);
-        launch_fast_as<true, SW_PLAIN, false, false, true>(pu, v.grid_uniform > 0 ? v.grid_uniform : grid, stream);
+        const int gu = v.grid_uniform > 0 ? v.grid_uniform : grid;
+        // the launch's line records first, on the same stream (rebuilt for every launch: the rows change between sweeps), then
+        // the windows that have their lines among them; then the others (n_uniform_rows of the n_uniform jobs) through the UNI
+        // form with the ordinary producer, in the same spill slots with a job counter of its own
+        const bool records = v.n_lines > 0 && pu.line_rec && pu.line_keys && v.n_uniform_rows < n_uni;
+        if (records) {
+            const size_t n_rec = (size_t)v.n_lines * p.n_markers * LINE_VALUES * 2;
+            hipLaunchKernelGGL(line_records_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, stream, v.lines, v.n_lines,
+                               p.allele8, p.sure, p.hw, p.n_markers, const_cast<LineRec*>(pu.line_rec));
+            zero_job_counter(pu, stream);
+            launch_fast_as<true, SW_PLAIN, false, false, true>(pu, gu, stream);
+        } else {
+            pu.line_rec  = nullptr;
+            pu.line_keys = nullptr;
+        }
+        if (!records || v.n_uniform_rows > 0) {
+            if (records) {
+                pu.clock_out = nullptr;
+                if (pu.job_next) pu.job_next = v.job_next_uniform + 1;
+            }
+            zero_job_counter(pu, stream);
+            launch_fast_as<true, SW_PLAIN_UNIFORM_ROWS, false, false, true>(pu, gu, stream);
+        }
         if (n_uni >= p.n_jobs) {
             launch_likelihood_logs(p, stream);
             return hipGetLastError();

@@ -117,6 +117,10 @@ enum {
     CNF2_QTL_ADDITIVE = 1u << 22, /* cnf2_qtl_scan, cnf2_sweep_qtl: the additive model -- the dominance column is always dropped */
     CNF2_QTL_ORIGIN_DEVICE = 1u << 23, /* cnf2_qtl_scan: `origin` is a device pointer (aligned to 16 bytes), e.g. the rows a
                                      cnf2_sweep_origins call with CNF2_OUT_DEVICE filled; they are read in place */
+    CNF2_NO_LINE_RECORDS = 1u << 24, /* cnf2_sweep and its modes: the instantiation for crosses of inbred lines forms every window's
+                                     emission terms from the window's own seven rows, as the ordinary one does, instead of reading
+                                     what a window's ancestors contribute from the launch's line records (cnf2_last_line_records).
+                                     Same results to the bit; A/B switch and cross-check.  Ignored where no records are used */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
                                     registers by a transpose through LDS instead of being exchanged by DPP moves (same
@@ -682,6 +686,22 @@ int    cnf2_set_grid_reserve(cnf2_ctx *ctx, int blocks);
  * batch size; the knob exists so that the multi-batch path can be exercised at test sizes and memory use bounded by a caller
  * that shares the GPU. */
 int    cnf2_set_batch_jobs(cnf2_ctx *ctx, int jobs);
+/* Line records.  In a window of a cross of inbred lines (class 2 of cnf2_last_paths) whose root and parents are not founders,
+ * what a parent and its two grandparents contribute to the emission tables depends on their three rows and slot flags (a
+ * "line"), the marker and the allele the root hands down, not on the individual.  A sweep gives every distinct line of its
+ * call a number, a small kernel in front of the sweep kernel evaluates the lines' records (64 bytes per line, marker,
+ * allele value 0..15 and grandparent traced: 2 KB per line and marker), and the sweep kernel reads a root's own row and
+ * two records where it read seven rows.  The records live for one launch and are rebuilt by every call; the numbering of the
+ * lines is kept while the windows, the call's range and the cap stay the same.  A call holds at most 64 lines and at most
+ * `lines` of cnf2_set_line_records (negative = no cap of its own, the default; 0 = no records).  The record buffer is
+ * allocated after the spill slots and the call's outputs; when it has to grow it may take half of the memory free at that
+ * moment, and the lines that did not fit then stay without records until the rows or the pedigree change.  The windows
+ * of further lines, windows whose root or a parent is a founder, and every window under CNF2_NO_LINE_RECORDS are swept as
+ * before, to the same bits.
+ * cnf2_last_line_records: out[4] = lines of the last sweep's call, its jobs swept on records, its class-2 jobs swept
+ * without, bytes of records (0 0 0 0 after a call whose mode or flags use no such instantiation). */
+int    cnf2_set_line_records(cnf2_ctx *ctx, int lines);
+int    cnf2_last_line_records(cnf2_ctx *ctx, int32_t *out);
 
 #ifdef __cplusplus
 }
