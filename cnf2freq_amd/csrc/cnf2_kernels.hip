@@ -65,7 +65,7 @@ __device__ __forceinline__ double lane_xor4(double v) { return swizzle_xor<4>(v)
 #ifndef CNF2_XCHG
 #define CNF2_XCHG 0
 #endif
-__device__ __forceinline__ int state_lo(int lane) { return (lane & 7) ^ ((lane & 4) ? 3 : 0); }
+// (state_lo, the lane's low state bits under that map: cnf2_lane.h)
 #if CNF2_XCHG == 0
 __device__ __forceinline__ double lane_flip_b1(double v) { return lane_xor2(v); }
 __device__ __forceinline__ double lane_flip_b2(double v) { return dpp_mov_all<0x141>(v); }
@@ -1431,9 +1431,13 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
     static_assert(!SMP || (!XPOSE && !TIED), "the sampling mode is an instantiation of the untied DPP kernel");
     static_assert(!TIED || (!XPOSE && ROWS), "tie combinations only matter to the rows");
     // Spill row (528 doubles): [k = 0..3][lane][2] = registers 2k, 2k+1 of every lane (one 16-byte access
-    // per lane and k; NR = 2: k = 0 alone, the rest of the slot stays unused), then [chain][2] = reciprocal normaliser of the (even) marker and, HALF only, of
+    // per lane and k), then [chain][2] = reciprocal normaliser of the (even) marker and, HALF only, of
     // an odd last marker.
-    constexpr int ROW = 528;
+    // UNI with two registers per lane: the compact row of cnf2_lane.h (48 doubles: every distinct value once).  The wave's slot
+    // is p.spill_stride doubles whatever the row's size, so an ordinary instantiation may follow in the same slots.
+    constexpr bool URow = UNI && NR == 2;
+    constexpr int  ROW  = URow ? (int)UNI_SPILL_ROW : 528;
+    constexpr int  INV  = URow ? (int)UNI_SPILL_INV : 512;     // the reciprocals' place in a row
     // TIED: the restricted tables of TWO tie combinations per row (the second pair TIE_KOFF doubles behind the first)
     constexpr int TIE_KOFF = 128;
     constexpr int TS = TIED ? TAB_STRIDE + TIE_KOFF : TAB_STRIDE;
@@ -1522,6 +1526,13 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
         c.active = !(s & w.shiftignore) && s < w.shiftend;
         const int first = jb.first, last = jb.last;
         const int ntile = (last - first + 8) >> 3;
+        // compact spill row: the lane's place in it, and whether it writes its pair / its chain's reciprocals there.  A launch
+        // that stops after the forward pass (KP_NO_DOSAGE: the plain sweep forms no rows) reads no spill row, so nobody
+        // writes one: the launch's flag is folded into the lanes' store predicates, no branch in the marker loop
+        const bool uspill = !URow || !(p.flags & KP_NO_DOSAGE);
+        const int  uoff   = URow ? uni_spill_value(lane) : 0;
+        const bool uwr    = URow && uspill && uni_spill_writer(lane);
+        const bool iwr    = c.lo == 0 && !(STOREW == SW_VITERBI) && uspill;
 
         using odd_t  = std::integral_constant<bool, true>;
         using even_t = std::integral_constant<bool, false>;
@@ -1557,12 +1568,18 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
             double*       sp = spill + (size_t)(HALF ? (ml >> 1) : ml) * ROW;
             if (!ODD && !VIT) {
 #ifndef CNF2_X_NOSTORE   /* timing ablation only: results are wrong */
+                if constexpr (URow) {
+                    // the two lanes of a chain that stand for its two classes: 16 lanes, 256 contiguous bytes
+                    const d2v v = {a[0], a[1]};
+                    if (uwr) __builtin_nontemporal_store(v, (d2v*)(sp + uoff));
+                } else {
 #pragma unroll
-                for (int k = 0; k < NR / 2; k++) {
-                    // written once, read once a whole chromosome later: streaming (nt) accesses keep the rows
-                    // from churning L2 (measured: -2 %)
-                    const d2v v = {a[2 * k], a[2 * k + 1]};
-                    __builtin_nontemporal_store(v, (d2v*)(sp + k * 128 + lane * 2));
+                    for (int k = 0; k < NR / 2; k++) {
+                        // written once, read once a whole chromosome later: streaming (nt) accesses keep the rows
+                        // from churning L2 (measured: -2 %)
+                        const d2v v = {a[2 * k], a[2 * k + 1]};
+                        __builtin_nontemporal_store(v, (d2v*)(sp + k * 128 + lane * 2));
+                    }
                 }
 #endif
             }
@@ -1597,9 +1614,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
                 } else {
                     scale_chain<UNI>(a, &mant, &expo, &dead, &inv);     // full spill: the stored rows are normalised at once
                 }
-                if (c.lo == 0 && !VIT) sp[512 + 2 * s + (ODD ? 1 : 0)] = inv;
+                if (iwr) sp[INV + 2 * s + (ODD ? 1 : 0)] = inv;
             } else if (!ODD && !VIT) {
-                if (c.lo == 0) sp[512 + 2 * s] = 1.0;
+                if (iwr) sp[INV + 2 * s] = 1.0;
             }
             if (m < last) {
                 if constexpr (XPOSE) transition_xpose(a, r.x, r.y, xb, lane);
@@ -1927,18 +1944,26 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
         const double xo_w     = (STOREW == 4 && chain_on) ? tmine * xm : 0.0;           // crossover mode: P(mode s | data)
         // software pipeline: the spill row (and its reciprocals) is requested one row ahead, straight into
         // the registers it is used from; nothing else in the marker loop is a vector memory operation
+        // (compact rows: two and three rows ahead, through a queue of registers, measured 2 - 3 % slower than one)
         auto load_row = [&](int idx) {
             const double* sp = spill + (size_t)idx * ROW;
 #ifdef CNF2_X_NOLOAD     /* timing ablation only: results are wrong */
             if (idx >= 0) return;
 #endif
+            if constexpr (URow) {
+                // the pair of the lane's class: four lanes an address, three lines a wave and row
+                const d2v v = __builtin_nontemporal_load((const d2v*)(sp + uoff));
+                S.am[0]     = v.x;
+                S.am[1]     = v.y;
+            } else {
 #pragma unroll
-            for (int k = 0; k < NR / 2; k++) {
-                const d2v v = __builtin_nontemporal_load((const d2v*)(sp + k * 128 + lane * 2));
-                S.am[2 * k]     = v.x;
-                S.am[2 * k + 1] = v.y;
+                for (int k = 0; k < NR / 2; k++) {
+                    const d2v v = __builtin_nontemporal_load((const d2v*)(sp + k * 128 + lane * 2));
+                    S.am[2 * k]     = v.x;
+                    S.am[2 * k + 1] = v.y;
+                }
             }
-            const double2 iv = *(const double2*)(sp + 512 + 2 * s);
+            const double2 iv = *(const double2*)(sp + INV + 2 * s);
             S.inv_even       = iv.x;
             S.inv_odd        = iv.y;
         };

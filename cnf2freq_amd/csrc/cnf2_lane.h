@@ -45,6 +45,23 @@ CNF2_HD void make_lane(const Window& w, int lane, LaneJob* L)
     L->tie_ot  = w.tie[slot_ot];
 }
 
+// The fast kernels' lane order within a chain of 8 lanes: the low state bits (b0, b1, b2) sit in lane b0 ^ 2 b1 ^ 7 b2
+// (flipping b2 is then a row_half_mirror move, see cnf2_kernels.hip).  The map is its own inverse.
+CNF2_HD int state_lo(int lane) { return (lane & 7) ^ ((lane & 4) ? 3 : 0); }
+
+// Spill row of the uniform-state sweep with two registers per lane.  Alpha does not depend on state bits 1, 2, 4, 5 there, so
+// the 8 lanes of a chain hold two distinct register pairs, told apart by state bit 0: a row keeps each once.
+//   [chain 0..7][b0][2] = 32 doubles of values (registers 0, 1 of the lanes with state bit 0 = b0), then
+//   [chain][2]          = 16 doubles: reciprocal normaliser of the (even) marker and of an odd last marker
+// = 48 doubles, three lines of 128 bytes.  The lanes with state bits 1 and 2 clear (lanes 0 and 1 of a chain) write, one
+// 16-byte store each, 256 contiguous bytes a wave; every lane reads the 16 bytes of its class, four lanes an address.
+enum { UNI_SPILL_INV = 32, UNI_SPILL_ROW = 48 };
+CNF2_HD bool uni_spill_writer(int lane) { return (state_lo(lane) & 6) == 0; }
+// offset (doubles) of the lane's register pair in the row: where a writer stores and where every lane loads
+CNF2_HD int uni_spill_value(int lane) { return (lane >> 3) * 4 + (state_lo(lane) & 1) * 2; }
+// offset (doubles) of a chain's two reciprocals
+CNF2_HD int uni_spill_inv(int chain) { return UNI_SPILL_INV + 2 * chain; }
+
 CNF2_HD int tie_force(int8_t tie, int combo)
 {
     return tie < 0 ? -1 : ((combo >> tie) & 1);
