@@ -47,7 +47,7 @@ SYMBOLS = [
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
     "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
-    "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns",
+    "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns",
 ]
 
 
@@ -121,6 +121,8 @@ def load():
         L.cnf2_qtl_scan.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_qtl.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtl_columns.argtypes = [vp, i32]
+        L.cnf2_qtl_scan2.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_set_qtl2_columns.argtypes = [vp, i32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -657,6 +659,51 @@ class Context:
                                         opt(use), K, opt(cov), P, opt(perm), C.c_void_p(d_lod), C.c_void_p(d_coef),
                                         C.c_void_p(d_rank), C.c_void_p(d_rss0), C.c_void_p(d_n_used),
                                         C.c_void_p(d_perm_max) if d_perm_max else None, flags | OUT_DEVICE), "cnf2_sweep_qtl")
+
+    # -- two-QTL pair scan ---------------------------------------------------------
+    QTL2_KEYS = ("lod_add", "lod_full", "rank_add", "rank_full", "rss0", "n_used", "perm_max")
+
+    def set_qtl2_columns(self, cap):
+        """Cap on the phenotype columns per tile of qtl_scan2 (0 = what memory allows); results do not depend on it."""
+        self._chk(self.L.cnf2_set_qtl2_columns(self.h, cap), "cnf2_set_qtl2_columns")
+
+    def _qtl2_outputs(self, T, P, L):
+        Cn = self.n_chrom
+        return dict(lod_add=np.zeros((T, L, L)), lod_full=np.zeros((T, L, L)), rank_add=np.zeros((L, L), np.int32),
+                    rank_full=np.zeros((L, L), np.int32), rss0=np.zeros((T, Cn, Cn)), n_used=np.zeros((Cn, Cn), np.int32),
+                    perm_max=np.zeros((P, T, 3)) if P else None)
+
+    def _qtl2_call(self, n, origin_ptr, sel, pheno, cov, use, perm, flags, out=None):
+        """cnf2_qtl_scan2 with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        sel = np.ascontiguousarray(sel, np.int32)
+        if sel.ndim != 1:
+            raise ValueError("sel must be [L]")
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        o = self._qtl2_outputs(T, P, len(sel)) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_qtl_scan2(self.h, n, origin_ptr, len(sel), _p(sel), T, _p(pheno), opt(use), K, opt(cov), P,
+                                        opt(perm), _p(o["lod_add"]), _p(o["lod_full"]), _p(o["rank_add"]), _p(o["rank_full"]),
+                                        _p(o["rss0"]), _p(o["n_used"]), opt(o["perm_max"]), flags), "cnf2_qtl_scan2")
+        return o
+
+    def qtl_scan2(self, origin, sel, pheno, cov=None, use=None, perm=None, additive=False):
+        """cnf2_qtl_scan2 on host rows origin[n][M][4]: for every pair j < k of the markers sel[L] (strictly ascending) the
+        additive-pair and the full (epistatic) Haley-Knott model of pheno[n][T], with covariates cov[n][K], K <= 6, the
+        individuals of use[n] and the permutations perm[P][n].  A dict: lod_add[T][L][L], lod_full[T][L][L] (NaN for a pair
+        on one chromosome), rank_add[L][L], rank_full[L][L] -- cells j < k only, the others NaN / -1 -- rss0[T][C][C],
+        n_used[C][C], perm_max[P][T][3] (the maxima of lod_add, lod_full and lod_full - lod_add; None without
+        permutations).  The model: include/cnf2hip.h; cnf2freq_amd/qtl.py reads the results."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return self._qtl2_call(origin.shape[0], _p(origin), sel, pheno, cov, use, perm, QTL_ADDITIVE if additive else 0)
+
+    def qtl_scan2_device(self, n, d_origin, sel, pheno, cov=None, use=None, perm=None, additive=False):
+        """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
+        sweep_qtl left in it, which this call leaves valid)."""
+        return self._qtl2_call(n, C.c_void_p(d_origin), sel, pheno, cov, use, perm,
+                               QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0))
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

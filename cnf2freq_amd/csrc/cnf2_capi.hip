@@ -21,6 +21,7 @@
 #include "cnf2_emtab.h"
 #include "cnf2_plan.h"
 #include "cnf2_qtl.h"
+#include "cnf2_qtl2.h"
 
 using namespace cnf2;
 
@@ -164,6 +165,12 @@ struct cnf2_ctx {
     DevBuf<double>  d_q_lod, d_q_coef, d_q_rss0, d_q_pmax;
     DevBuf<uint8_t> d_q_use, d_q_cmask;
     DevBuf<int32_t> d_q_perm, d_q_map, d_q_nc, d_q_rank;   // d_q_map: chromstarts, marker -> chromosome, tiles, tile starts
+
+    // two-QTL pair scan (cnf2_qtl_scan2): its column cap, the per-pair sums of the null design, the chunk maxima, staged
+    // outputs; the staged inputs, the mask and the column image are the single scan's buffers
+    int             qtl2_columns = 0;
+    DevBuf<double>  d_q2_yy, d_q2_chunkmax, d_q2_lod_add, d_q2_lod_full, d_q2_rss0, d_q2_pmax;
+    DevBuf<int32_t> d_q2_map, d_q2_nc, d_q2_rank_add, d_q2_rank_full;   // d_q2_map: chromstarts, sel, the chromosomes of sel
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -374,6 +381,13 @@ int cnf2_set_batch_jobs(cnf2_ctx* ctx, int jobs)
 {
     if (!ctx || jobs < 0) return CNF2_ERR_ARG;
     ctx->batch_jobs = jobs;
+    return CNF2_OK;
+}
+
+int cnf2_set_qtl2_columns(cnf2_ctx* ctx, int cap)
+{
+    if (!ctx || cap < 0) return ctx ? fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative") : CNF2_ERR_ARG;
+    ctx->qtl2_columns = cap;
     return CNF2_OK;
 }
 
@@ -1594,6 +1608,119 @@ int cnf2_sweep_qtl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_ou
     ctx->qtl_rows_n = a.n;
     ctx->qtl_rows_m = ctx->n_markers;
     return qtl_scan_impl(ctx, ctx->d_org, a, mask, flags);
+}
+
+// The pair scan on device rows d_origin[n][M][4]: cnf2_qtl2.h, cnf2_qtl2_kernels.hip.  Everything is checked and every
+// buffer is there before the first launch writes.
+int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const int32_t* sel, int n_traits, const double* pheno,
+                   const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm, double* lod_add_out,
+                   double* lod_full_out, int32_t* rank_add_out, int32_t* rank_full_out, double* rss0_out, int32_t* n_used_out,
+                   double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
+                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    // (the phenotype side is the single scan's; its lod / coef / rank slots stand for this call's four pair outputs)
+    const QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_add_out, lod_full_out, rss0_out, perm_max_out,
+                       rank_add_out, n_used_out};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_validate(ctx, a, &mask));
+    if (!rank_full_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if (n_cov > QTL2_MAXK) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d for the pair scan", QTL2_MAXK);
+    if (n_sel < 2 || n_sel > QTL2_MAXL || !sel) return fail(ctx, CNF2_ERR_ARG, "n_sel must be 2 .. %d, with sel", QTL2_MAXL);
+    const int M = ctx->n_markers, C = ctx->n_chrom, L = n_sel;
+    for (int j = 0; j < L; j++)
+        if (sel[j] < 0 || sel[j] >= M || (j > 0 && sel[j] <= sel[j - 1]))
+            return fail(ctx, CNF2_ERR_ARG, "sel must be strictly ascending marker indices below %d", M);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double* d_origin = kept ? ctx->d_org.ptr : origin;
+    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
+    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t R = (size_t)a.T * ((size_t)a.P + 1), LL = (size_t)L * L;
+    const int    n_chunks = (L - 1 + QTL2_CHUNK - 1) / QTL2_CHUNK;
+    // the column tile: the image under 1 GB, the chunk maxima under 256 MB, the caller's cap
+    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
+    rt = std::min(rt, (size_t)4096);
+    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (24 * (size_t)L * n_chunks)));
+    rt = std::min(rt, R);
+    if (ctx->qtl2_columns > 0) rt = std::min(rt, (size_t)ctx->qtl2_columns);
+    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
+    map.insert(map.end(), sel, sel + L);
+    for (int j = 0, c = 0; j < L; j++) {
+        while (sel[j] >= ctx->chromstarts[c + 1]) c++;
+        map.push_back(c);
+    }
+
+    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
+    Qtl2Params q;
+    memset(&q, 0, sizeof(q));
+    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
+    RC_TRY(ctx->d_q2_map.ensure(ctx, map.size()));
+    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
+    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
+    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
+    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
+    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
+    RC_TRY(ctx->d_q2_yy.ensure(ctx, (size_t)C * C * rt));
+    if (a.P > 0) RC_TRY(ctx->d_q2_chunkmax.ensure(ctx, (size_t)L * n_chunks * 3 * rt));
+    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_q2_nc, (size_t)C * C, &q.nc));
+    RC_TRY(stage_out(ctx, dev, rank_add_out, ctx->d_q2_rank_add, LL, &q.rank_add));
+    RC_TRY(stage_out(ctx, dev, rank_full_out, ctx->d_q2_rank_full, LL, &q.rank_full));
+    RC_TRY(stage_out(ctx, dev, lod_add_out, ctx->d_q2_lod_add, (size_t)a.T * LL, &q.lod_add));
+    RC_TRY(stage_out(ctx, dev, lod_full_out, ctx->d_q2_lod_full, (size_t)a.T * LL, &q.lod_full));
+    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_q2_rss0, (size_t)a.T * C * C, &q.rss0));
+    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_q2_pmax, (size_t)a.P * a.T * 3, &q.pmax));
+    if (staged) {
+        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
+        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_origin = ctx->d_org;
+    }
+    RC_TRY(qtl_upload(ctx, ctx->d_q2_map, map.data(), map.size()));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.L = L;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
+    q.origin = d_origin, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.perm = ctx->d_q_perm;
+    q.cs = ctx->d_q2_map, q.sel = ctx->d_q2_map + (C + 1), q.selchrom = ctx->d_q2_map + (C + 1 + L);
+    q.cmask = ctx->d_q_cmask, q.Y = ctx->d_q_Y, q.yy = ctx->d_q2_yy, q.chunkmax = ctx->d_q2_chunkmax;
+    q.rstride = (int)rt, q.n_chunks = n_chunks;
+    QtlParams g;                           // what qtl_gather_kernel reads
+    memset(&g, 0, sizeof(g));
+    g.n = a.n, g.T = a.T, g.pheno = q.pheno, g.use = q.use, g.perm = q.perm, g.Y = q.Y, g.rstride = q.rstride;
+
+    launch_qtl2_mask(q, ctx->stream);
+    launch_qtl2_fill(q, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = g.r0 = (int)r0;
+        q.rn = g.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(g, ctx->stream);
+        launch_qtl2_null(q, ctx->stream);
+        launch_qtl2_pairs(q, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtl2_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dev) {
+        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C * C));
+        RC_TRY(fetch_out(ctx, rank_add_out, q.rank_add, LL));
+        RC_TRY(fetch_out(ctx, rank_full_out, q.rank_full, LL));
+        RC_TRY(fetch_out(ctx, lod_add_out, q.lod_add, (size_t)a.T * LL));
+        RC_TRY(fetch_out(ctx, lod_full_out, q.lod_full, (size_t)a.T * LL));
+        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C * C));
+        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * 3));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
 }
 
 // one pass of sweep_impl's Viterbi mode

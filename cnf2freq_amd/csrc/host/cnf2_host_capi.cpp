@@ -8,6 +8,7 @@
 
 #include "cnf2_engine.h"
 #include "cnf2_qtl_host.h"
+#include "../cnf2_qtl2.h"
 #include "cnf2_remap.h"
 
 using namespace cnf2host;
@@ -307,6 +308,25 @@ int cnf2h_qtl_permutations(int n, int n_perm, uint64_t seed, const uint8_t* use,
 {
     if (n < 1 || n_perm < 0 || !perm_out) return -2;
     cnf2host::qtl_permutations(n, n_perm, seed, use, strata, perm_out);
+    return 0;
+}
+
+int cnf2h_qtl2_pair(const double* gram, int n_col, const double* xty, const double* yy, int n_c, int n_cov, int additive,
+                    int same_chrom, int32_t* out_rank, double* rss0_out, double* lod_add_out, double* lod_full_out)
+{
+    using namespace cnf2;
+    if (!gram || n_col < 0 || (n_col > 0 && (!xty || !yy || !rss0_out || !lod_add_out || !lod_full_out)) || n_cov < 0 ||
+        n_cov > QTL2_MAXK || !out_rank)
+        return -2;
+    double G[QTL2_W * QTL2_W];
+    std::copy(gram, gram + QTL2_W * QTL2_W, G);
+    const Qtl2Design ds = qtl2_design(n_cov, additive != 0, same_chrom != 0);
+    const Qtl2Factor f  = qtl2_factor(G, QTL2_W, ds, n_c, n_cov, same_chrom != 0);
+    out_rank[0] = f.usable, out_rank[1] = f.rank_add, out_rank[2] = f.rank_full;
+    for (int r = 0; r < n_col; r++) {
+        const Qtl2Cell c = qtl2_cell(G, QTL2_W, ds, f, xty + (size_t)r * QTL2_W, 1, yy[r], n_c, same_chrom != 0);
+        rss0_out[r] = c.rss0, lod_add_out[r] = c.lod_add, lod_full_out[r] = c.lod_full;
+    }
     return 0;
 }
 

@@ -4,6 +4,7 @@
 //            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
 //            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]] [--origins F]
 //            [--qtl F --phenofile P [--qtl-covariates name,name] [--qtl-permutations K] [--qtl-seed S] [--qtl-additive]]
+//            [--qtl2 F [--qtl2-every S] --phenofile P [the --qtl-* options]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -73,6 +74,9 @@
 // "-" for the effect of a dropped column); with --qtl-permutations K > 0, after a blank line, per trait
 // "name<TAB>5 %<TAB>1 %": the genome-wide thresholds from K permutations of the null model's residuals, made from
 // --qtl-seed by the rule of cnf2freq_amd/qtl.py (cnf2h_qtl_permutations).  --qtl-additive drops the dominance column.
+// --qtl2 F [--qtl2-every S] (with --phenofile and the --qtl-* options; not flags of the reference): the two-QTL pair scan
+// (cnf2_qtl_scan2) of every S-th marker of each chromosome, from its first (S = 1 by default; at most 4096 loci), after
+// --qtl where both are given and on the same sweep's rows.  Covariates: at most 6.  F is described at qtl2_scan below.
 // --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
@@ -139,6 +143,9 @@ struct Options {
     unsigned long long qtl_seed = 0;     // --qtl-seed S
     bool        qtl_additive = false;    // --qtl-additive
     bool        qtl_extra_set = false;   // one of the four above was given
+    std::string qtl2;                    // --qtl2 F: pair scan of the last round's state (with --phenofile and the --qtl-* options)
+    int         qtl2_every = 1;          // --qtl2-every S: every S-th marker of each chromosome, from its first
+    bool        qtl2_every_set = false;
     PhenoTable  pheno;                   // P as read (main, before any rank starts)
     std::vector<int> qtl_cov_cols, qtl_trait_cols;     // columns of pheno
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
@@ -213,6 +220,11 @@ static bool parse(int argc, char** argv, Options& o)
         }
         else if (a == "--origins") o.origins = val();
         else if (a == "--qtl") o.qtl = val();
+        else if (a == "--qtl2") o.qtl2 = val();
+        else if (a == "--qtl2-every") {
+            o.qtl2_every     = atoi(val().c_str());
+            o.qtl2_every_set = true;
+        }
         else if (a == "--phenofile") o.phenofile = val();
         else if (a == "--qtl-covariates") {
             o.qtl_covariates = val();
@@ -247,6 +259,7 @@ static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -338,6 +351,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.loo.empty()) loo_costs(opt, P, ctx);
     if (world == 1 && !opt.origins.empty()) origin_rows(opt, P, ctx);
     if (world == 1 && !opt.qtl.empty()) qtl_scan(opt, P, ctx);
+    if (world == 1 && !opt.qtl2.empty()) qtl2_scan(opt, P, ctx, !opt.qtl.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -565,6 +579,15 @@ static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.origins);
 }
 
+// --qtl2-every S: every S-th marker of each chromosome from its first (cnf2freq_amd/qtl.py's select_every)
+static std::vector<int32_t> qtl2_select(const std::vector<int32_t>& chromstarts, int every)
+{
+    std::vector<int32_t> sel;
+    for (size_t c = 0; c + 1 < chromstarts.size(); c++)
+        for (int m = chromstarts[c]; m < chromstarts[c + 1]; m += every) sel.push_back(m);
+    return sel;
+}
+
 // --phenofile against the pedigree and --qtl-covariates, before anything runs: false with a message that names what is wrong
 static bool prepare_qtl(Options& opt, const Pedigree& P)
 {
@@ -714,6 +737,131 @@ static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtl);
 }
 
+// --qtl2 after the last round (single GPU), and after --qtl where both are given: the pair scan (cnf2_qtl_scan2) of every
+// --qtl2-every-th marker on the rows a cnf2_sweep_qtl left in the context -- --qtl's, or one of this function's own.  Traits
+// are grouped by their pattern of missing values as for --qtl.  The file holds, per trait and chromosome pair with a pair of
+// selected loci, the summary of cnf2freq_amd/qtl.py's pair_summary: trait, the two chromosomes, n, the best additive pair
+// (markers, positions, lod_add) and, on different chromosomes, the best full pair (markers, positions, lod_full, the
+// additive LOD there) and lod_int = best full - best additive ("-" on one chromosome).  With --qtl-permutations K > 0, after a
+// blank line, per trait the 5 % and 1 % genome-wide thresholds of lod_add, lod_full and lod_int.
+static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    const std::vector<int32_t> sel = qtl2_select(P.chromstarts, opt.qtl2_every);
+    const int    L  = (int)sel.size();
+    const size_t LL = (size_t)L * L;
+    std::vector<int> sc(L);
+    for (int j = 0, c = 0; j < L; j++) {
+        while (sel[j] >= P.chromstarts[c + 1]) c++;
+        sc[j] = c;
+    }
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    std::vector<double>  la((size_t)T * LL), lf((size_t)T * LL), thr((size_t)T * 6, 0.0);
+    std::vector<int32_t> nused((size_t)T * C * C, 0);
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), a((size_t)Tg * LL), f((size_t)Tg * LL), rss((size_t)Tg * C * C);
+        std::vector<int32_t> ra(LL), rf(LL), nu((size_t)C * C);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc;
+        if (!rows_kept) {          // the sweep, with the rows left in the context; its single-locus scan is not reported
+            std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), l1((size_t)Tg * M), c1((size_t)Tg * M * 2), r1((size_t)Tg * C);
+            std::vector<int32_t> k1(M), n1(C);
+            rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                l1.data(), c1.data(), k1.data(), r1.data(), n1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl2: ") + cnf2_last_error(ctx));
+            rows_kept = true;
+        }
+        rc = cnf2_qtl_scan2(ctx, N, nullptr, L, sel.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr, a.data(),
+                            f.data(), ra.data(), rf.data(), rss.data(), nu.data(), nullptr, flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl2: ") + cnf2_last_error(ctx));
+        for (int t = 0; t < Tg; t++) {
+            std::copy(a.begin() + (size_t)t * LL, a.begin() + (size_t)(t + 1) * LL, la.begin() + (size_t)tr[t] * LL);
+            std::copy(f.begin() + (size_t)t * LL, f.begin() + (size_t)(t + 1) * LL, lf.begin() + (size_t)tr[t] * LL);
+            std::copy(nu.begin(), nu.end(), nused.begin() + (size_t)tr[t] * C * C);
+        }
+        if (NP > 0) {
+            std::vector<int32_t> perm((size_t)NP * N);
+            std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * 3);
+            qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+            // (as for --qtl: with too few individuals nothing is scanned and the residuals stay 0; with enough of them a null
+            // design without full rank is an error)
+            const int n_u = (int)std::count(u.begin(), u.end(), (uint8_t)1);
+            if (n_u >= K + 10 && !qtl_null_residuals(N, Tg, yg.data(), K, K ? cov.data() : nullptr, u.data(), res.data()))
+                throw EngineError(CNF2_ERR_ARG, "--qtl-permutations: the null design (intercept and covariates) of the individuals used for " +
+                                                    opt.pheno.columns[opt.qtl_trait_cols[tr[0]]] + " has no full rank");
+            rc = cnf2_qtl_scan2(ctx, N, nullptr, L, sel.data(), Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, NP, perm.data(),
+                                a.data(), f.data(), ra.data(), rf.data(), rss.data(), nu.data(), pm.data(), flags);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl2 permutations: ") + cnf2_last_error(ctx));
+            for (int t = 0; t < Tg; t++)
+                for (int s = 0; s < 3; s++) {
+                    std::vector<double> mx(NP);
+                    for (int p = 0; p < NP; p++) mx[p] = pm[((size_t)p * Tg + t) * 3 + s];
+                    thr[(size_t)tr[t] * 6 + 2 * s]     = qtl_threshold(mx, 0.05);
+                    thr[(size_t)tr[t] * 6 + 2 * s + 1] = qtl_threshold(mx, 0.01);
+                }
+        }
+    }
+    FILE* out = fopen(opt.qtl2.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtl2);
+    for (int t = 0; t < T; t++)
+        for (int c1 = 0; c1 < C; c1++)
+            for (int c2 = c1; c2 < C; c2++) {
+                int    aj = -1, ak = -1, fj = -1, fk = -1;       // the first pair in (j, k) order wins a tie
+                for (int j = 0; j < L; j++)
+                    for (int k = j + 1; k < L; k++) {
+                        if (sc[j] != c1 || sc[k] != c2) continue;
+                        const size_t o = (size_t)t * LL + (size_t)j * L + k;
+                        if (aj < 0 || la[o] > la[(size_t)t * LL + (size_t)aj * L + ak]) aj = j, ak = k;
+                        if (fj < 0 || lf[o] > lf[(size_t)t * LL + (size_t)fj * L + fk]) fj = j, fk = k;
+                    }
+                if (aj < 0) continue;
+                const double best_add = la[(size_t)t * LL + (size_t)aj * L + ak];
+                fprintf(out, "%s\t%d\t%d\t%d\t%d\t%d\t%.5lf\t%.5lf\t%.5lf", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str(), c1 + 1, c2 + 1,
+                        (int)nused[((size_t)t * C + c1) * C + c2], (int)sel[aj], (int)sel[ak], P.pos[sel[aj]], P.pos[sel[ak]], best_add);
+                if (c1 == c2) fprintf(out, "\t-\t-\t-\t-\t-\t-\t-\n");
+                else {
+                    const size_t o = (size_t)t * LL + (size_t)fj * L + fk;
+                    fprintf(out, "\t%d\t%d\t%.5lf\t%.5lf\t%.5lf\t%.5lf\t%.5lf\n", (int)sel[fj], (int)sel[fk], P.pos[sel[fj]], P.pos[sel[fk]], lf[o],
+                            la[o], lf[o] - best_add);
+                }
+            }
+    if (NP > 0) {
+        fprintf(out, "\n");
+        for (int t = 0; t < T; t++) {
+            fprintf(out, "%s", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str());
+            for (int s = 0; s < 6; s++) fprintf(out, "\t%.5lf", thr[(size_t)t * 6 + s]);
+            fprintf(out, "\n");
+        }
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtl2);
+}
+
 // --rccl-selftest: the RCCL transport with a world of one on GPU 0 -- the communicator's set-up through the shared region, then
 // reduce-scatter, all-gather, the hit-counter sum, a barrier and the host broadcast on the context's exchange buffer, through
 // the same entry the engine calls.  (Two ranks need two GPUs: RCCL refuses two ranks on one device.)
@@ -838,19 +986,47 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
         return 2;
     }
-    if (opt.qtl.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
-        fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE\n");
+    if (opt.gpus > 1 && !opt.qtl2.empty()) {
+        fprintf(stderr, "--qtl2 needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtl.empty() && opt.qtl2.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
+        return 2;
+    }
+    if (opt.qtl2.empty() && opt.qtl2_every_set) {
+        fprintf(stderr, "--qtl2-every needs --qtl2 FILE\n");
         return 2;
     }
     if (!opt.qtl.empty() && opt.phenofile.empty()) {
         fprintf(stderr, "--qtl FILE needs --phenofile FILE\n");
         return 2;
     }
+    if (!opt.qtl2.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtl2 FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtl2_every < 1) {
+        fprintf(stderr, "--qtl2-every must be at least 1\n");
+        return 2;
+    }
+    if (!opt.qtl2.empty()) {
+        const std::vector<int32_t> sel = qtl2_select(P.chromstarts, opt.qtl2_every);
+        if (sel.size() > 4096 || sel.size() < 2) {
+            fprintf(stderr, "--qtl2: --qtl2-every S = %d selects %zu loci, and a pair scan takes 2 to 4096: %s S\n", opt.qtl2_every,
+                    sel.size(), sel.size() < 2 ? "lower" : "raise");
+            return 2;
+        }
+    }
     if (opt.qtl_permutations < 0) {
         fprintf(stderr, "--qtl-permutations must not be negative\n");
         return 2;
     }
-    if (!opt.qtl.empty() && !prepare_qtl(opt, P)) return 2;
+    if ((!opt.qtl.empty() || !opt.qtl2.empty()) && !prepare_qtl(opt, P)) return 2;
+    if (!opt.qtl2.empty() && opt.qtl_cov_cols.size() > 6) {
+        fprintf(stderr, "--qtl2: at most 6 covariates\n");
+        return 2;
+    }
     if (opt.loo_threshold_set && opt.loo.empty()) {
         fprintf(stderr, "--loo-threshold needs --loo FILE\n");
         return 2;

@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("CNF2HOST_LIB") or os.path.join(_HERE, "libcnf2host.so
 SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_get_dims", "cnf2h_destroy", "cnf2h_last_error", "cnf2h_postmarkerdata", "cnf2h_iteration",
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
-           "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals"]
+           "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -59,6 +59,7 @@ def load():
         L.cnf2h_write_map.argtypes = [C.c_char_p, vp, i32, vp, i32]
         L.cnf2h_qtl_permutations.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
         L.cnf2h_qtl_null_residuals.argtypes = [i32, i32, vp, i32, vp, vp, vp]
+        L.cnf2h_qtl2_pair.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -93,6 +94,24 @@ def qtl_permutations(n, P, seed, use=None, strata=None):
     if rc != 0:
         raise RuntimeError("cnf2h_qtl_permutations failed (%d)" % rc)
     return out
+
+
+def qtl2_pair(gram, xty, yy, n_c, n_cov, additive=False, same_chrom=False):
+    """cnf2h_qtl2_pair: the pair scan's factorisation and cells (cnf2_qtl2.h) on a normal matrix gram[16][16], xty[R][16]
+    and yy[R].  A dict: usable, rank_add, rank_full, rss0[R], lod_add[R], lod_full[R].  CPU only."""
+    L = load()
+    g = np.ascontiguousarray(gram, np.float64)
+    b = np.ascontiguousarray(xty, np.float64).reshape(-1, 16)
+    y2 = np.ascontiguousarray(yy, np.float64).reshape(-1)
+    if g.shape != (16, 16) or len(y2) != len(b):
+        raise ValueError("gram must be [16][16], xty [R][16] and yy [R]")
+    R = len(b)
+    rank = np.zeros(3, np.int32)
+    out = [np.zeros(R) for _ in range(3)]
+    rc = L.cnf2h_qtl2_pair(_p(g), R, _p(b), _p(y2), n_c, n_cov, int(additive), int(same_chrom), _p(rank), *[_p(o) for o in out])
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtl2_pair failed (%d)" % rc)
+    return dict(usable=bool(rank[0]), rank_add=int(rank[1]), rank_full=int(rank[2]), rss0=out[0], lod_add=out[1], lod_full=out[2])
 
 
 def qtl_null_residuals(pheno, cov=None, use=None):

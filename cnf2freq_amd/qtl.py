@@ -3,7 +3,10 @@
 The scan is Haley-Knott regression of phenotypes on a = P(BB) - P(AA) and d = P(AB) + P(BA) at every marker (the model:
 include/cnf2hip.h); it runs on the GPU for the observed phenotypes and for every permuted one.  This module makes the
 permutations, the residuals that are permuted when there are covariates (Freedman-Lane), turns the permutations' maxima into
-thresholds and reads peaks with their LOD-drop support intervals off a profile.  Nothing here scans."""
+thresholds and reads peaks with their LOD-drop support intervals off a profile.  Nothing here scans.
+
+The pair scan (Context.qtl_scan2, cnf2_qtl_scan2) asks the next two questions -- is there a second locus, do two loci
+interact -- for every pair of selected markers: scan2, thresholds2 and pair_summary are its counterparts here."""
 import numpy as np
 
 from . import synth
@@ -50,12 +53,116 @@ def null_residuals(pheno, cov=None, use=None):
     return res
 
 
-def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False):
+def origin_rows(ctx):
+    """One origin sweep of the context's pedigree with the rows left on its GPU: a torch tensor [n][M][4] that scan and scan2
+    take as `rows`, so that both run from one sweep."""
+    import torch
+    n, M, C = ctx.n_ind, ctx.n_markers, ctx.n_chrom
+    dev = torch.device("cuda", ctx.device)          # the context's GPU, whatever torch's current one is
+    t = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+    d_f, d_l, d_o, d_s, d_c = t(n, C, 8), t(n, C), t(n, M, 4), t(M, 4), t(C, dtype=torch.int32)
+    ctx.sweep_origins_device(0, n, d_f.data_ptr(), d_l.data_ptr(), d_o.data_ptr(), None, d_s.data_ptr(), d_c.data_ptr())
+    ctx.sync()
+    return d_o
+
+
+def select_every(chromstarts, every=1):
+    """sel: every `every`-th marker of each chromosome, from its first (what `cnF2freq --qtl2-every` selects)"""
+    cs = np.asarray(chromstarts, np.int64)
+    return np.concatenate([np.arange(cs[c], cs[c + 1], every) for c in range(len(cs) - 1)]).astype(np.int32)
+
+
+def scan2(ctx, pheno, sel, cov=None, use=None, permutations=0, seed=0, additive=False, rows=None):
+    """The pair scan of a whole cross on the context's uploaded pedigree, for every pair of the markers sel[L]: one origin
+    sweep with the rows left on the device (or `rows`, the tensor origin_rows returned, e.g. the one a preceding scan used),
+    then per pattern of missing phenotypes (NaN) one observed scan with the pattern's own `use`, and with permutations > 0
+    one more on the permuted residuals of the null model, as scan does.  A dict: lod_add[T][L][L], lod_full[T][L][L],
+    rank_add[T][L][L], rank_full[T][L][L], n_used[T][C][C], perm_max[P][T][3] or None (the maxima of lod_add, lod_full and
+    lod_full - lod_add: thresholds2)."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    sel = np.ascontiguousarray(sel, np.int32)
+    L, C = len(sel), ctx.n_chrom
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod_add=np.zeros((T, L, L)), lod_full=np.zeros((T, L, L)), rank_add=np.zeros((T, L, L), np.int32),
+               rank_full=np.zeros((T, L, L), np.int32), n_used=np.zeros((T, C, C), np.int32),
+               perm_max=np.zeros((permutations, T, 3)) if permutations else None)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = ctx.qtl_scan2_device(n, d_o.data_ptr(), sel, yk, cov=cov, use=u, additive=additive)
+        for key in ("lod_add", "lod_full", "rank_add", "rank_full", "n_used"):
+            out[key][cols] = got[key]
+        if permutations:
+            perm = _permutations(n, permutations, seed, use=u)
+            res = null_residuals(yk, cov, u)
+            out["perm_max"][:, cols] = ctx.qtl_scan2_device(n, d_o.data_ptr(), sel, res, cov=cov, use=u, perm=perm,
+                                                            additive=additive)["perm_max"]
+    return out
+
+
+def thresholds2(perm_max, alpha=(0.05, 0.01)):
+    """From perm_max[P][T][3] of a pair scan: add, full and int, each [len(alpha)][T] -- the genome-wide thresholds of the
+    largest additive-pair LOD, the largest full LOD and the largest lod_full - lod_add, by the order statistic of
+    thresholds()."""
+    pm = np.asarray(perm_max, np.float64)
+    if pm.ndim != 3 or pm.shape[0] == 0 or pm.shape[2] != 3:
+        raise ValueError("perm_max must be [P][T][3] with P >= 1")
+    srt = np.sort(pm, axis=0)
+    idx = [quantile_index(pm.shape[0], a) for a in alpha]
+    return dict(alpha=tuple(alpha), add=srt[idx, :, 0], full=srt[idx, :, 1], int=srt[idx, :, 2])
+
+
+def pair_summary(lod_add, lod_full, sel, chromstarts):
+    """The usual summary of a two-dimensional scan.  Per trait and chromosome pair c1 <= c2 that holds a pair of selected
+    loci, a dict: trait, chrom1, chrom2; add = (marker 1, marker 2) of the best additive pair and lod_add its LOD; and for
+    c1 != c2 full = the best full pair, lod_full its LOD, lod_add_at_full the additive LOD there, and
+    lod_int = lod_full - lod_add, the best full against the best additive model of the chromosome pair.  On one chromosome
+    only the additive model is fitted: full is None and lod_full, lod_add_at_full, lod_int are NaN.  The first pair in
+    (j, k) order wins a tie."""
+    la, lf = np.asarray(lod_add, np.float64), np.asarray(lod_full, np.float64)
+    la, lf = (la[None] if la.ndim == 2 else la), (lf[None] if lf.ndim == 2 else lf)
+    sel = np.asarray(sel, np.int64)
+    L = len(sel)
+    if la.shape[1:] != (L, L) or lf.shape != la.shape:
+        raise ValueError("lod_add and lod_full must be [T][L][L] with L = len(sel)")
+    cs = np.asarray(chromstarts, np.int64)
+    sc = np.searchsorted(cs, sel, side="right") - 1
+    found = []
+    for t in range(la.shape[0]):
+        for c1 in range(len(cs) - 1):
+            for c2 in range(c1, len(cs) - 1):
+                jj, kk = np.flatnonzero(sc == c1), np.flatnonzero(sc == c2)
+                pairs = [(j, k) for j in jj for k in kk if j < k]
+                if not pairs:
+                    continue
+                pj, pk = np.array(pairs).T
+                ia = int(np.argmax(la[t, pj, pk]))
+                r = dict(trait=t, chrom1=c1, chrom2=c2, add=(int(sel[pj[ia]]), int(sel[pk[ia]])), lod_add=float(la[t, pj[ia], pk[ia]]),
+                         full=None, lod_full=np.nan, lod_add_at_full=np.nan, lod_int=np.nan)
+                if c1 != c2:
+                    i = int(np.argmax(lf[t, pj, pk]))
+                    r.update(full=(int(sel[pj[i]]), int(sel[pk[i]])), lod_full=float(lf[t, pj[i], pk[i]]),
+                             lod_add_at_full=float(la[t, pj[i], pk[i]]))
+                    r["lod_int"] = r["lod_full"] - r["lod_add"]
+                found.append(r)
+    return found
+
+
+def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False, rows=None):
     """The scan of a whole cross on the context's uploaded pedigree: one origin sweep with the rows left on the device, then
     per pattern of missing phenotypes (NaN) one observed scan with the pattern's own `use`, and with permutations > 0 one
     more on the permuted residuals of the null model.  A dict: lod[T][M], coef[T][M][2], rank[T][M] (the design, and with
-    it the rank, depends on who is used), n_used[T][C], perm_max[P][T][C] or None."""
-    import torch
+    it the rank, depends on who is used), n_used[T][C], perm_max[P][T][C] or None.  rows: the tensor of origin_rows, instead
+    of a sweep of this call's own (scan and scan2 of one cross from one sweep)."""
     y = np.asarray(pheno, np.float64)
     y = y[:, None] if y.ndim == 1 else y
     n, T = y.shape
@@ -63,11 +170,7 @@ def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False)
         raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
     use = np.ones(n, bool) if use is None else np.asarray(use) != 0
     M, C = ctx.n_markers, ctx.n_chrom
-    dev = torch.device("cuda", ctx.device)          # the context's GPU, whatever torch's current one is
-    t = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
-    d_f, d_l, d_o, d_s, d_c = t(n, C, 8), t(n, C), t(n, M, 4), t(M, 4), t(C, dtype=torch.int32)
-    ctx.sweep_origins_device(0, n, d_f.data_ptr(), d_l.data_ptr(), d_o.data_ptr(), None, d_s.data_ptr(), d_c.data_ptr())
-    ctx.sync()
+    d_o = origin_rows(ctx) if rows is None else rows
     out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, 2), np.nan), rank=np.zeros((T, M), np.int32),
                n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C)) if permutations else None)
     missing = ~np.isfinite(y)

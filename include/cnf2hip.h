@@ -506,6 +506,55 @@ int cnf2_sweep_qtl(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_ou
                    double *perm_max_out, uint32_t flags);
 int cnf2_set_qtl_columns(cnf2_ctx *ctx, int cap);
 
+/* Two-QTL pair scan: is there a second locus, and do two loci interact?  For every pair (j, k), j < k, of the selected
+ * markers sel[L] (strictly ascending, 2 <= L <= 4096; locus 1 = sel[j] on chromosome c1, locus 2 = sel[k] on c2) three nested
+ * Haley-Knott designs are fitted to every phenotype column, observed and permuted.  One definition for this header,
+ * cnf2freq_amd/csrc/cnf2_qtl2.h (host and device), the kernels and tests/qtl2_reference.py.  origin, pheno, use, cov (K <= 6
+ * here: the widest design has 1 + K + 8 <= 15 columns) and perm are cnf2_qtl_scan's.
+ *   mask      c_i = use[i], and the row at c1's first marker is not all zero, and the same at c2's;  n_c = sum c_i.  It
+ *             depends on (c1, c2) only
+ *   null      X0 = [c, c z_1 .. c z_K]
+ *   additive  X0, a1, d1, a2, d2                              with CNF2_QTL_ADDITIVE: X0, a1, a2
+ *   full      additive, then a1 a2, a1 d2, d1 a2, d1 d2       with CNF2_QTL_ADDITIVE: additive, then a1 a2
+ * with a = o[3] - o[0], d = o[1] + o[2] at each locus.  The additive design is linear in each locus's indicators, so the
+ * marginal rows give its exact Haley-Knott regressors and it is fitted for every pair.  The interaction regressors are
+ * E[a1 a2 | data] and the other products: the jobs are individual x chromosome and the posterior factorises across
+ * chromosomes, so for c1 != c2 a product's expectation is the product of the marginal expectations, exactly.  For c1 = c2 it
+ * needs the joint posterior of two loci on one chain, which no sweep produces: the full model is fitted only for pairs on
+ * different chromosomes, and a pair on one chromosome reports lod_full = NaN and rank_full = -1.
+ * One factorisation gives all three: the normal matrix of [full design | y] under the mask, one sequential Cholesky in the
+ * column order above; an added column is dropped (pivot 0) when its raw diagonal is 0 or its pivot is below 1e-8 times its
+ * raw diagonal.  With w = L^-1 X'y over the kept columns
+ *   RSS0 = sum c y^2 - sum_{X0} w^2,  RSS_add = RSS0 - sum_{kept additive} w^2,  RSS_full = RSS_add - sum_{kept interaction} w^2
+ *   lod_x = (n_c / 2) log10(RSS0 / RSS_x), the cumulative reduction clamped to [0, RSS0 (1 - 2^-52)]: every LOD is finite and
+ *   not negative, and lod_full >= lod_add.
+ * rank_add (0 .. 4; 0 .. 2 additive) counts the kept additive columns, rank_full (0 .. 8; 0 .. 3) all kept added columns;
+ * they depend on the design only, and rank 0 gives LOD 0 exactly.  A chromosome pair with n_c < K + 10, or whose X0 has no
+ * Cholesky factor, is not scanned: ranks 0, LODs 0, rss0 0 (lod_full stays NaN and rank_full -1 on one chromosome).  A
+ * column with RSS0 <= 0 gives LOD 0.
+ *   lod_add_out, lod_full_out [T][L][L]    rank_add_out, rank_full_out [L][L] (int32)
+ *       only cells j < k carry results; every other cell is NaN / -1
+ *   rss0_out [T][C][C], n_used_out [C][C] (int32)    symmetric, filled for every chromosome pair, the diagonal included
+ *   perm_max_out [P][T][3]    per permutation and trait the maxima over all pairs of lod_add, and over the pairs with
+ *       c1 != c2 of lod_full and of lod_full - lod_add; 0 where no pair qualifies; NULL exactly when P = 0
+ * CNF2_QTL_ADDITIVE, CNF2_QTL_ORIGIN_DEVICE (also with origin NULL: the rows the last cnf2_sweep_qtl left in the context,
+ * CNF2_ERR_STATE as for cnf2_qtl_scan) and CNF2_OUT_DEVICE act as for cnf2_qtl_scan.  Device rows are read in place and the
+ * call does not invalidate the context's rows: cnf2_qtl_scan and cnf2_qtl_scan2 can follow one sweep in any order.  sel and
+ * the phenotype side are host pointers.  Everything cnf2_qtl_scan refuses, K > 6, and a sel that is unsorted, repeats a
+ * marker or leaves the map return CNF2_ERR_ARG and write nothing; an allocation that fails returns CNF2_ERR_NOMEM before
+ * anything is written.
+ * Launches: the masks; per tile of columns the column image (as cnf2_qtl_scan), per chromosome pair n_c, sum c y^2 and RSS0,
+ * and the pair kernel, a batched small SYRK on the f64 matrix cores -- a wave owns a pair, forms the design entries in
+ * registers from the two origin rows, accumulates X'X and X'Y over the individuals in ascending order, factors the 16 x 16
+ * tile once and lets one lane per column do the substitution; a finish kernel reduces the permutations' maxima.  No atomics
+ * and no split of the individuals: a call gives the same bits every time, for every column cap (cnf2_set_qtl2_columns,
+ * 0 = no cap; the tile keeps the image under 1 GB and the maxima under 256 MB) and from host or device rows. */
+int cnf2_qtl_scan2(cnf2_ctx *ctx, int n, const double *origin, int n_sel, const int32_t *sel, int n_traits,
+                   const double *pheno, const uint8_t *use, int n_cov, const double *cov, int n_perm, const int32_t *perm,
+                   double *lod_add_out, double *lod_full_out, int32_t *rank_add_out, int32_t *rank_full_out,
+                   double *rss0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
+int cnf2_set_qtl2_columns(cnf2_ctx *ctx, int cap);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every

@@ -140,6 +140,13 @@ int cnf2h_qtl_permutations(int n, int n_perm, uint64_t seed, const uint8_t *use,
 int cnf2h_qtl_null_residuals(int n, int n_traits, const double *pheno, int n_cov, const double *cov, const uint8_t *use,
                              double *res_out);
 
+/* The small algebra of the pair scan (cnf2_qtl_scan2 of cnf2hip.h; cnf2freq_amd/csrc/cnf2_qtl2.h) on the host, as its tests
+ * use it: gram[16][16] is the normal matrix of one pair's design in the model's column order (zero past its width; only the
+ * lower triangle is read), xty[n_col][16] and yy[n_col] the columns' X'y and sum c y^2.  Factors once with the rank rule,
+ * then per column the cell: out_rank[3] = usable, rank_add, rank_full; rss0_out, lod_add_out, lod_full_out [n_col]. */
+int cnf2h_qtl2_pair(const double *gram, int n_col, const double *xty, const double *yy, int n_c, int n_cov, int additive,
+                    int same_chrom, int32_t *out_rank, double *rss0_out, double *lod_add_out, double *lod_full_out);
+
 #ifdef __cplusplus
 }
 #endif
