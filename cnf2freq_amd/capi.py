@@ -28,6 +28,7 @@ FLUSH_TINY = 1 << 20              # cnf2_sweep: general kernel with adjustprobs'
 ALL_STATES = 1 << 21              # windows of crosses of inbred lines through the fast kernel's ordinary instantiation (A/B, cross-check)
 QTL_ADDITIVE = 1 << 22            # cnf2_qtl_scan / cnf2_sweep_qtl: the dominance column is always dropped
 QTL_ORIGIN_DEVICE = 1 << 23       # cnf2_qtl_scan: the origin rows are a device pointer
+QTL_IMPRINT = 1 << 25             # cnf2_qtl_scanx: the design gets the imprinting effect i = o[1] - o[2]
 NO_LINE_RECORDS = 1 << 24         # crosses of inbred lines: every window's emission terms from its own rows, not from the launch's line records (A/B, cross-check)
 STATIC_JOBS = 1 << 18             # wave w sweeps jobs w, w + waves, ... instead of taking jobs from the launch's counter (A/B)
 MINFACTOR = float(np.float32(-1e15))
@@ -47,7 +48,7 @@ SYMBOLS = [
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
     "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
-    "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns",
+    "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
 ]
 
 
@@ -123,6 +124,8 @@ def load():
         L.cnf2_set_qtl_columns.argtypes = [vp, i32]
         L.cnf2_qtl_scan2.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtl2_columns.argtypes = [vp, i32]
+        L.cnf2_qtl_scanx.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_set_qtlx_columns.argtypes = [vp, i32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -704,6 +707,50 @@ class Context:
         sweep_qtl left in it, which this call leaves valid)."""
         return self._qtl2_call(n, C.c_void_p(d_origin), sel, pheno, cov, use, perm,
                                QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0))
+
+    # -- extended single-locus scan: imprinting and QTL x covariate interaction ------
+    QTLX_KEYS = ("lod", "coef", "rank", "rss0", "n_used", "perm_max")
+
+    def set_qtlx_columns(self, cap):
+        """Cap on the phenotype columns per tile of qtl_scanx (0 = what memory allows); results do not depend on it."""
+        self._chk(self.L.cnf2_set_qtlx_columns(self.h, cap), "cnf2_set_qtlx_columns")
+
+    def _qtlx_outputs(self, T, P, ncoef):
+        M, Cn = self.n_markers, self.n_chrom
+        return dict(lod=np.zeros((T, M, 3)), coef=np.zeros((T, M, ncoef)), rank=np.zeros((M, 3), np.int32), rss0=np.zeros((T, Cn)),
+                    n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn, 5)) if P else None)
+
+    def _qtlx_call(self, n, origin_ptr, pheno, cov, interactive, use, perm, flags, out=None):
+        """cnf2_qtl_scanx with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        ne = 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
+        o = self._qtlx_outputs(T, P, ne * (1 + max(0, int(interactive)))) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_qtl_scanx(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), int(interactive), P, opt(perm),
+                                        _p(o["lod"]), _p(o["coef"]), _p(o["rank"]), _p(o["rss0"]), _p(o["n_used"]),
+                                        opt(o["perm_max"]), flags), "cnf2_qtl_scanx")
+        return o
+
+    def qtl_scanx(self, origin, pheno, cov=None, interactive=0, imprint=False, use=None, perm=None, additive=False, out=None):
+        """cnf2_qtl_scanx on host rows origin[n][M][4]: per marker the nested Haley-Knott models Mendelian (a, d), imprinting
+        (+ i = o[1] - o[2], with imprint) and interaction (+ the products of every effect with the first `interactive`
+        columns of cov[n][K]) of pheno[n][T], with the individuals of use[n] and the permutations perm[P][n].  A dict:
+        lod[T][M][3] (nested, non-decreasing), coef[T][M][ne (1 + interactive)] (the full model's effects, NaN for a dropped
+        column), rank[M][3] (cumulative), rss0[T][C], n_used[C], perm_max[P][T][C][5] (the maxima of the three LODs, of
+        lod[1] - lod[0] and of lod[2] - lod[1]; None without permutations).  The model: include/cnf2hip.h;
+        cnf2freq_amd/qtl.py reads the results."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return self._qtlx_call(origin.shape[0], _p(origin), pheno, cov, interactive, use, perm,
+                               (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0), out)
+
+    def qtl_scanx_device(self, n, d_origin, pheno, cov=None, interactive=0, imprint=False, use=None, perm=None, additive=False):
+        """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
+        sweep_qtl left in it, which this call leaves valid)."""
+        return self._qtlx_call(n, C.c_void_p(d_origin), pheno, cov, interactive, use, perm,
+                               QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0))
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

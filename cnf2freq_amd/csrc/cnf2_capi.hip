@@ -22,6 +22,7 @@
 #include "cnf2_plan.h"
 #include "cnf2_qtl.h"
 #include "cnf2_qtl2.h"
+#include "cnf2_qtlx.h"
 
 using namespace cnf2;
 
@@ -171,6 +172,12 @@ struct cnf2_ctx {
     int             qtl2_columns = 0;
     DevBuf<double>  d_q2_yy, d_q2_chunkmax, d_q2_lod_add, d_q2_lod_full, d_q2_rss0, d_q2_pmax;
     DevBuf<int32_t> d_q2_map, d_q2_nc, d_q2_rank_add, d_q2_rank_full;   // d_q2_map: chromstarts, sel, the chromosomes of sel
+
+    // extended single-locus scan (cnf2_qtl_scanx): its column cap, sum c y^2 per chromosome, the tile maxima, staged outputs;
+    // the staged inputs, the mask and the column image are the single scan's buffers
+    int             qtlx_columns = 0;
+    DevBuf<double>  d_qx_yy, d_qx_tilemax, d_qx_lod, d_qx_coef, d_qx_rss0, d_qx_pmax;
+    DevBuf<int32_t> d_qx_map, d_qx_nc, d_qx_rank;   // d_qx_map: chromstarts, tiles, tile starts
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -388,6 +395,13 @@ int cnf2_set_qtl2_columns(cnf2_ctx* ctx, int cap)
 {
     if (!ctx || cap < 0) return ctx ? fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative") : CNF2_ERR_ARG;
     ctx->qtl2_columns = cap;
+    return CNF2_OK;
+}
+
+int cnf2_set_qtlx_columns(cnf2_ctx* ctx, int cap)
+{
+    if (!ctx || cap < 0) return ctx ? fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative") : CNF2_ERR_ARG;
+    ctx->qtlx_columns = cap;
     return CNF2_OK;
 }
 
@@ -1718,6 +1732,119 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
         RC_TRY(fetch_out(ctx, lod_full_out, q.lod_full, (size_t)a.T * LL));
         RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C * C));
         if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * 3));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// The extended single-locus scan on device rows d_origin[n][M][4]: cnf2_qtlx.h, cnf2_qtlx_kernels.hip.  Everything is
+// checked and every buffer is there before the first launch writes.
+int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
+                   const double* cov, int n_int, int n_perm, const int32_t* perm, double* lod_out, double* coef_out,
+                   int32_t* rank_out, double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
+                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    const QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_validate(ctx, a, &mask));
+    if (n_int < 0 || n_int > n_cov) return fail(ctx, CNF2_ERR_ARG, "n_int must be 0 .. n_cov");
+    const QtlxDesign ds = qtlx_design(n_cov, n_int, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
+    if (ds.w > QTLX_MAXW)
+        return fail(ctx, CNF2_ERR_ARG, "the design has %d columns (1 + n_cov + effects x (1 + n_int)); at most %d", ds.w, QTLX_MAXW);
+    const int M = ctx->n_markers, C = ctx->n_chrom, ncoef = ds.w - ds.nx;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double* d_origin = kept ? ctx->d_org.ptr : origin;
+    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
+    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
+    // the map as the kernels read it: chromstarts, the marker tiles (none straddles a chromosome start), their starts
+    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
+    std::vector<int32_t> tstart(1, 0);
+    for (int c = 0; c < C; c++) {
+        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
+        for (int m = f; m < e; m += QTLX_TILE) {
+            const int32_t t4[4] = {c, m, std::min(QTLX_TILE, e - m), 0};
+            map.insert(map.end(), t4, t4 + 4);
+        }
+        tstart.push_back((int32_t)((map.size() - (size_t)(C + 1)) / 4));
+    }
+    const size_t n_tiles = (map.size() - (size_t)(C + 1)) / 4, o_tstart = map.size();
+    map.insert(map.end(), tstart.begin(), tstart.end());
+    // the column tile: the image under 1 GB, the tile maxima under 256 MB, the caller's cap
+    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
+    rt = std::min(rt, (size_t)4096);
+    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (8 * QTLX_NSTAT * n_tiles)));
+    rt = std::min(rt, R);
+    if (ctx->qtlx_columns > 0) rt = std::min(rt, (size_t)ctx->qtlx_columns);
+
+    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
+    QtlxParams q;
+    memset(&q, 0, sizeof(q));
+    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
+    RC_TRY(ctx->d_qx_map.ensure(ctx, map.size()));
+    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
+    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
+    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
+    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
+    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
+    RC_TRY(ctx->d_qx_yy.ensure(ctx, (size_t)C * rt));
+    if (a.P > 0) RC_TRY(ctx->d_qx_tilemax.ensure(ctx, n_tiles * QTLX_NSTAT * rt));
+    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_qx_nc, (size_t)C, &q.nc));
+    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_qx_rank, (size_t)M * 3, &q.rank));
+    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_qx_lod, (size_t)a.T * M * 3, &q.lod));
+    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_qx_coef, (size_t)a.T * M * ncoef, &q.coef));
+    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_qx_rss0, (size_t)a.T * C, &q.rss0));
+    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_qx_pmax, (size_t)a.P * a.T * C * QTLX_NSTAT, &q.pmax));
+    if (staged) {
+        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
+        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_origin = ctx->d_org;
+    }
+    RC_TRY(qtl_upload(ctx, ctx->d_qx_map, map.data(), map.size()));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.Ki = n_int;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
+    q.origin = d_origin, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use;
+    q.cs = ctx->d_qx_map, q.tiles = ctx->d_qx_map + (C + 1), q.tile_start = ctx->d_qx_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.cmask = ctx->d_q_cmask, q.Y = ctx->d_q_Y, q.yy = ctx->d_qx_yy, q.tilemax = ctx->d_qx_tilemax, q.rstride = (int)rt;
+    Qtl2Params k;                          // what qtl2_mask_kernel reads and writes
+    memset(&k, 0, sizeof(k));
+    k.n = a.n, k.M = M, k.C = C, k.origin = d_origin, k.use = ctx->d_q_use, k.cs = ctx->d_qx_map, k.cmask = ctx->d_q_cmask;
+    QtlParams g;                           // what qtl_gather_kernel reads
+    memset(&g, 0, sizeof(g));
+    g.n = a.n, g.T = a.T, g.pheno = ctx->d_q_pheno, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm, g.Y = ctx->d_q_Y, g.rstride = q.rstride;
+
+    launch_qtl2_mask(k, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = g.r0 = (int)r0;
+        q.rn = g.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(g, ctx->stream);
+        launch_qtlx_null(q, ctx->stream);
+        launch_qtlx_markers(q, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtlx_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dev) {
+        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C));
+        RC_TRY(fetch_out(ctx, a.rank, q.rank, (size_t)M * 3));
+        RC_TRY(fetch_out(ctx, a.lod, q.lod, (size_t)a.T * M * 3));
+        RC_TRY(fetch_out(ctx, a.coef, q.coef, (size_t)a.T * M * ncoef));
+        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C));
+        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * C * QTLX_NSTAT));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;

@@ -9,6 +9,7 @@
 #include "cnf2_engine.h"
 #include "cnf2_qtl_host.h"
 #include "../cnf2_qtl2.h"
+#include "../cnf2_qtlx.h"
 #include "cnf2_remap.h"
 
 using namespace cnf2host;
@@ -328,6 +329,43 @@ int cnf2h_qtl2_pair(const double* gram, int n_col, const double* xty, const doub
         rss0_out[r] = c.rss0, lod_add_out[r] = c.lod_add, lod_full_out[r] = c.lod_full;
     }
     return 0;
+}
+
+int cnf2h_qtlx_marker(const double* gram, int n_col, const double* xty, const double* yy, int n_c, int n_cov, int n_int,
+                      int additive, int imprint, int32_t* out_rank, double* rss0_out, double* lod_out, double* coef_out)
+{
+    using namespace cnf2;
+    if (!gram || n_col < 0 || (n_col > 0 && (!xty || !yy || !rss0_out || !lod_out || !coef_out)) || n_cov < 0 || n_int < 0 ||
+        n_int > n_cov || !out_rank)
+        return -2;
+    const QtlxDesign ds = qtlx_design(n_cov, n_int, additive != 0, imprint != 0);
+    if (ds.w > QTLX_MAXW) return -2;
+    double G[QTL2_W * QTL2_W];
+    std::copy(gram, gram + QTL2_W * QTL2_W, G);
+    const QtlxFactor f = qtlx_factor(G, QTL2_W, ds, n_c, ds.w);
+    out_rank[0] = f.usable, out_rank[1] = f.rank[0], out_rank[2] = f.rank[1], out_rank[3] = f.rank[2];
+    const int ncoef = ds.w - ds.nx;
+    for (int r = 0; r < n_col; r++) {
+        double beta[QTL2_W];
+        std::copy(xty + (size_t)r * QTL2_W, xty + (size_t)(r + 1) * QTL2_W, beta);
+        const QtlxCell c = qtlx_cell(G, QTL2_W, ds, f, beta, 1, yy[r], n_c, true);
+        rss0_out[r] = c.rss0;
+        for (int s = 0; s < 3; s++) lod_out[(size_t)r * 3 + s] = c.lod[s];
+        for (int e = 0; e < ncoef; e++) coef_out[(size_t)r * ncoef + e] = beta[ds.nx + e];
+    }
+    return 0;
+}
+
+// what column j of the extended scan's design is: the two codes of qtlx_column (cnf2_qtlx.h); the design's width is returned
+int cnf2h_qtlx_column(int n_cov, int n_int, int additive, int imprint, int j, int32_t* effect_out, int32_t* modifier_out)
+{
+    using namespace cnf2;
+    if (n_cov < 0 || n_int < 0 || n_int > n_cov || !effect_out || !modifier_out) return -2;
+    const QtlxDesign ds = qtlx_design(n_cov, n_int, additive != 0, imprint != 0);
+    int e, z;
+    qtlx_column(ds, j, &e, &z);
+    *effect_out = e, *modifier_out = z;
+    return ds.w;
 }
 
 int cnf2h_qtl_null_residuals(int n, int n_traits, const double* pheno, int n_cov, const double* cov, const uint8_t* use,

@@ -5,6 +5,7 @@
 //            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]] [--origins F]
 //            [--qtl F --phenofile P [--qtl-covariates name,name] [--qtl-permutations K] [--qtl-seed S] [--qtl-additive]]
 //            [--qtl2 F [--qtl2-every S] --phenofile P [the --qtl-* options]]
+//            [--qtlx F --phenofile P [--qtl-imprint] [--qtl-interactive name,name] [the --qtl-* options]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -77,6 +78,11 @@
 // --qtl2 F [--qtl2-every S] (with --phenofile and the --qtl-* options; not flags of the reference): the two-QTL pair scan
 // (cnf2_qtl_scan2) of every S-th marker of each chromosome, from its first (S = 1 by default; at most 4096 loci), after
 // --qtl where both are given and on the same sweep's rows.  Covariates: at most 6.  F is described at qtl2_scan below.
+// --qtlx F [--qtl-imprint] [--qtl-interactive name,name] (with --phenofile and the --qtl-* options; not flags of the
+// reference): the extended single-locus scan (cnf2_qtl_scanx) -- per marker the nested models Mendelian (a, d), imprinting
+// (+ i, with --qtl-imprint) and interaction (+ the products of the effects with the named covariates, which must be among
+// --qtl-covariates and are moved to the front of them) -- after --qtl and --qtl2 where they are given, on the same sweep's
+// rows.  The design takes at most 15 columns.  F is described at qtlx_scan below.
 // --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
@@ -98,6 +104,7 @@
 
 #include "cnf2_engine.h"
 #include "cnf2_qtl_host.h"
+#include "../cnf2_qtlx.h"
 #include "cnf2_readers.h"
 #include "cnf2_rccl_transport.h"
 #include "cnf2_remap.h"
@@ -146,6 +153,12 @@ struct Options {
     std::string qtl2;                    // --qtl2 F: pair scan of the last round's state (with --phenofile and the --qtl-* options)
     int         qtl2_every = 1;          // --qtl2-every S: every S-th marker of each chromosome, from its first
     bool        qtl2_every_set = false;
+    std::string qtlx;                    // --qtlx F: extended single-locus scan (with --phenofile and the --qtl-* options)
+    bool        qtl_imprint = false;     // --qtl-imprint
+    std::string qtl_interactive;         // --qtl-interactive name,name
+    bool        qtlx_extra_set = false;  // one of the two above was given
+    std::vector<int> qtlx_cov_cols;      // columns of pheno: the interactive covariates first, then the others
+    int         qtlx_n_int = 0;
     PhenoTable  pheno;                   // P as read (main, before any rank starts)
     std::vector<int> qtl_cov_cols, qtl_trait_cols;     // columns of pheno
     std::string remap;                   // --remap F: the map after --remap-iterations EM steps
@@ -221,6 +234,12 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--origins") o.origins = val();
         else if (a == "--qtl") o.qtl = val();
         else if (a == "--qtl2") o.qtl2 = val();
+        else if (a == "--qtlx") o.qtlx = val();
+        else if (a == "--qtl-imprint") o.qtl_imprint = o.qtlx_extra_set = true;
+        else if (a == "--qtl-interactive") {
+            o.qtl_interactive = val();
+            o.qtlx_extra_set  = true;
+        }
         else if (a == "--qtl2-every") {
             o.qtl2_every     = atoi(val().c_str());
             o.qtl2_every_set = true;
@@ -260,6 +279,7 @@ static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -352,6 +372,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.origins.empty()) origin_rows(opt, P, ctx);
     if (world == 1 && !opt.qtl.empty()) qtl_scan(opt, P, ctx);
     if (world == 1 && !opt.qtl2.empty()) qtl2_scan(opt, P, ctx, !opt.qtl.empty());
+    if (world == 1 && !opt.qtlx.empty()) qtlx_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -579,6 +600,116 @@ static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.origins);
 }
 
+// --qtlx after the last round (single GPU), and after --qtl / --qtl2 where they are given: the extended single-locus scan
+// (cnf2_qtl_scanx) on the rows a cnf2_sweep_qtl left in the context -- theirs, or one of this function's own.  Traits are
+// grouped by their pattern of missing values as for --qtl.  The file holds one table per trait, the tables separated by a
+// blank line: a line "trait" and the name; per marker chromosome, position, n, the three nested LODs (Mendelian, +
+// imprinting, + interaction), lod_imprint = the second less the first, lod_interaction = the third less the second, the three
+// cumulative ranks and the effects of the full model in the design's column order ("-" for a dropped column); with
+// --qtl-permutations K > 0 five lines "threshold", the statistic's name and its 5 % and 1 % genome-wide thresholds.
+static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtlx_cov_cols.size(), Ki = opt.qtlx_n_int, NP = opt.qtl_permutations;
+    const cnf2::QtlxDesign ds = cnf2::qtlx_design(K, Ki, opt.qtl_additive, opt.qtl_imprint);
+    const int NC = ds.w - ds.nx;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtlx_cov_cols[k]];
+            if (row[opt.qtlx_cov_cols[k]] != row[opt.qtlx_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | (opt.qtl_imprint ? CNF2_QTL_IMPRINT : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    std::vector<double>  lod((size_t)T * M * 3), coef((size_t)T * M * NC), thr((size_t)T * 10, 0.0);
+    std::vector<int32_t> rank((size_t)T * M * 3), nused((size_t)T * C);
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M * 3), cf((size_t)Tg * M * NC), rss((size_t)Tg * C);
+        std::vector<int32_t> rk((size_t)M * 3), nu(C);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc;
+        if (!rows_kept) {          // the sweep, with the rows left in the context; its single-locus scan is not reported
+            std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), l1((size_t)Tg * M), c1((size_t)Tg * M * 2), r1((size_t)Tg * C);
+            std::vector<int32_t> k1(M), n1(C);
+            rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                l1.data(), c1.data(), k1.data(), r1.data(), n1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlx: ") + cnf2_last_error(ctx));
+            rows_kept = true;
+        }
+        rc = cnf2_qtl_scanx(ctx, N, nullptr, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, Ki, 0, nullptr, l.data(), cf.data(),
+                            rk.data(), rss.data(), nu.data(), nullptr, flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlx: ") + cnf2_last_error(ctx));
+        for (int t = 0; t < Tg; t++) {
+            std::copy(l.begin() + (size_t)t * M * 3, l.begin() + (size_t)(t + 1) * M * 3, lod.begin() + (size_t)tr[t] * M * 3);
+            std::copy(cf.begin() + (size_t)t * M * NC, cf.begin() + (size_t)(t + 1) * M * NC, coef.begin() + (size_t)tr[t] * M * NC);
+            std::copy(rk.begin(), rk.end(), rank.begin() + (size_t)tr[t] * M * 3);
+            std::copy(nu.begin(), nu.end(), nused.begin() + (size_t)tr[t] * C);
+        }
+        if (NP > 0) {
+            std::vector<int32_t> perm((size_t)NP * N);
+            std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * C * 5);
+            qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+            // (as for --qtl: with too few individuals nothing is scanned and the residuals stay 0; with enough of them a null
+            // design without full rank is an error)
+            const int n_u = (int)std::count(u.begin(), u.end(), (uint8_t)1);
+            if (n_u >= ds.w + 1 && !qtl_null_residuals(N, Tg, yg.data(), K, K ? cov.data() : nullptr, u.data(), res.data()))
+                throw EngineError(CNF2_ERR_ARG, "--qtl-permutations: the null design (intercept and covariates) of the individuals used for " +
+                                                    opt.pheno.columns[opt.qtl_trait_cols[tr[0]]] + " has no full rank");
+            rc = cnf2_qtl_scanx(ctx, N, nullptr, Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, Ki, NP, perm.data(), l.data(),
+                                cf.data(), rk.data(), rss.data(), nu.data(), pm.data(), flags);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlx permutations: ") + cnf2_last_error(ctx));
+            for (int t = 0; t < Tg; t++)
+                for (int s = 0; s < 5; s++) {
+                    std::vector<double> mx(NP, 0.0);
+                    for (int p = 0; p < NP; p++)
+                        for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[(((size_t)p * Tg + t) * C + c) * 5 + s]);
+                    thr[(size_t)tr[t] * 10 + 2 * s]     = qtl_threshold(mx, 0.05);
+                    thr[(size_t)tr[t] * 10 + 2 * s + 1] = qtl_threshold(mx, 0.01);
+                }
+        }
+    }
+    FILE* out = fopen(opt.qtlx.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlx);
+    static const char* const stat[5] = {"lod_mendelian", "lod_imprinting", "lod_full", "lod_imprint", "lod_interaction"};
+    for (int t = 0; t < T; t++) {
+        fprintf(out, "%strait\t%s\n", t ? "\n" : "", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str());
+        for (int c = 0; c < C; c++)
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const double*  l = &lod[((size_t)t * M + m) * 3];
+                const int32_t* r = &rank[((size_t)t * M + m) * 3];
+                fprintf(out, "%d\t%.5lf\t%d\t%.5lf\t%.5lf\t%.5lf\t%.5lf\t%.5lf\t%d\t%d\t%d", c + 1, P.pos[m], (int)nused[(size_t)t * C + c], l[0],
+                        l[1], l[2], l[1] - l[0], l[2] - l[1], (int)r[0], (int)r[1], (int)r[2]);
+                for (int e = 0; e < NC; e++) {
+                    const double v = coef[((size_t)t * M + m) * NC + e];
+                    if (v != v) fprintf(out, "\t-");
+                    else fprintf(out, "\t%.5lf", v);
+                }
+                fprintf(out, "\n");
+            }
+        if (NP > 0)
+            for (int s = 0; s < 5; s++) fprintf(out, "threshold\t%s\t%.5lf\t%.5lf\n", stat[s], thr[(size_t)t * 10 + 2 * s], thr[(size_t)t * 10 + 2 * s + 1]);
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlx);
+}
+
 // --qtl2-every S: every S-th marker of each chromosome from its first (cnf2freq_amd/qtl.py's select_every)
 static std::vector<int32_t> qtl2_select(const std::vector<int32_t>& chromstarts, int every)
 {
@@ -627,6 +758,34 @@ static bool prepare_qtl(Options& opt, const Pedigree& P)
         if (std::find(opt.qtl_cov_cols.begin(), opt.qtl_cov_cols.end(), k) == opt.qtl_cov_cols.end()) opt.qtl_trait_cols.push_back(k);
     if (opt.qtl_trait_cols.empty()) {
         fprintf(stderr, "%s: every column is a covariate, no trait is left\n", opt.phenofile.c_str());
+        return false;
+    }
+    return true;
+}
+
+// --qtl-interactive against --qtl-covariates, and the design's width, before anything runs: false with a message
+static bool prepare_qtlx(Options& opt)
+{
+    std::istringstream ss(opt.qtl_interactive);
+    std::string        missing;
+    for (std::string tok; std::getline(ss, tok, ',');) {
+        if (tok.empty()) continue;
+        const auto it = std::find(opt.pheno.columns.begin(), opt.pheno.columns.end(), tok);
+        const int  k  = it == opt.pheno.columns.end() ? -1 : (int)(it - opt.pheno.columns.begin());
+        if (k < 0 || std::find(opt.qtl_cov_cols.begin(), opt.qtl_cov_cols.end(), k) == opt.qtl_cov_cols.end()) missing += " " + tok;
+        else if (std::find(opt.qtlx_cov_cols.begin(), opt.qtlx_cov_cols.end(), k) == opt.qtlx_cov_cols.end()) opt.qtlx_cov_cols.push_back(k);
+    }
+    if (!missing.empty()) {
+        fprintf(stderr, "--qtl-interactive: not among --qtl-covariates:%s\n", missing.c_str());
+        return false;
+    }
+    opt.qtlx_n_int = (int)opt.qtlx_cov_cols.size();
+    for (int k : opt.qtl_cov_cols)
+        if (std::find(opt.qtlx_cov_cols.begin(), opt.qtlx_cov_cols.end(), k) == opt.qtlx_cov_cols.end()) opt.qtlx_cov_cols.push_back(k);
+    const cnf2::QtlxDesign ds = cnf2::qtlx_design((int)opt.qtlx_cov_cols.size(), opt.qtlx_n_int, opt.qtl_additive, opt.qtl_imprint);
+    if (ds.w > cnf2::QTLX_MAXW) {
+        fprintf(stderr, "--qtlx: the design has %d columns (1 + covariates + effects x (1 + interactive covariates)); at most %d\n", ds.w,
+                cnf2::QTLX_MAXW);
         return false;
     }
     return true;
@@ -990,7 +1149,19 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl2 needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
         return 2;
     }
-    if (opt.qtl.empty() && opt.qtl2.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+    if (opt.gpus > 1 && !opt.qtlx.empty()) {
+        fprintf(stderr, "--qtlx needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlx.empty() && opt.qtlx_extra_set) {
+        fprintf(stderr, "--qtl-imprint and --qtl-interactive need --qtlx FILE\n");
+        return 2;
+    }
+    if (!opt.qtlx.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlx FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -1022,7 +1193,8 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-permutations must not be negative\n");
         return 2;
     }
-    if ((!opt.qtl.empty() || !opt.qtl2.empty()) && !prepare_qtl(opt, P)) return 2;
+    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty()) && !prepare_qtl(opt, P)) return 2;
+    if (!opt.qtlx.empty() && !prepare_qtlx(opt)) return 2;
     if (!opt.qtl2.empty() && opt.qtl_cov_cols.size() > 6) {
         fprintf(stderr, "--qtl2: at most 6 covariates\n");
         return 2;

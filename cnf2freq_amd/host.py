@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("CNF2HOST_LIB") or os.path.join(_HERE, "libcnf2host.so
 SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_get_dims", "cnf2h_destroy", "cnf2h_last_error", "cnf2h_postmarkerdata", "cnf2h_iteration",
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
-           "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair"]
+           "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -60,6 +60,8 @@ def load():
         L.cnf2h_qtl_permutations.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
         L.cnf2h_qtl_null_residuals.argtypes = [i32, i32, vp, i32, vp, vp, vp]
         L.cnf2h_qtl2_pair.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.cnf2h_qtlx_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.cnf2h_qtlx_column.argtypes = [i32, i32, i32, i32, i32, vp, vp]
         _lib = L
     return _lib
 
@@ -112,6 +114,41 @@ def qtl2_pair(gram, xty, yy, n_c, n_cov, additive=False, same_chrom=False):
     if rc != 0:
         raise RuntimeError("cnf2h_qtl2_pair failed (%d)" % rc)
     return dict(usable=bool(rank[0]), rank_add=int(rank[1]), rank_full=int(rank[2]), rss0=out[0], lod_add=out[1], lod_full=out[2])
+
+
+def qtlx_marker(gram, xty, yy, n_c, n_cov, n_int=0, additive=False, imprint=False):
+    """cnf2h_qtlx_marker: the extended scan's factorisation and cells (cnf2_qtlx.h) on a normal matrix gram[16][16],
+    xty[R][16] and yy[R].  A dict: usable, rank[3], rss0[R], lod[R][3], coef[R][ne (1 + n_int)].  CPU only."""
+    L = load()
+    g = np.ascontiguousarray(gram, np.float64)
+    b = np.ascontiguousarray(xty, np.float64).reshape(-1, 16)
+    y2 = np.ascontiguousarray(yy, np.float64).reshape(-1)
+    if g.shape != (16, 16) or len(y2) != len(b):
+        raise ValueError("gram must be [16][16], xty [R][16] and yy [R]")
+    R = len(b)
+    ne = 1 + (0 if additive else 1) + (1 if imprint else 0)
+    rank = np.zeros(4, np.int32)
+    rss0, lod, coef = np.zeros(R), np.zeros((R, 3)), np.zeros((R, ne * (1 + n_int)))
+    rc = L.cnf2h_qtlx_marker(_p(g), R, _p(b), _p(y2), n_c, n_cov, n_int, int(additive), int(imprint), _p(rank), _p(rss0), _p(lod),
+                             _p(coef))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtlx_marker failed (%d)" % rc)
+    return dict(usable=bool(rank[0]), rank=rank[1:].copy(), rss0=rss0, lod=lod, coef=coef)
+
+
+def qtlx_columns(n_cov, n_int=0, additive=False, imprint=False):
+    """cnf2h_qtlx_column for every column of the design: a list of (effect, modifier) codes as cnf2_qtlx.h defines them --
+    effect 0 = 1, 1 = a, 2 = d, 3 = i; modifier 0 = 1, k = covariate k - 1.  CPU only."""
+    L = load()
+    e, z = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    W = L.cnf2h_qtlx_column(n_cov, n_int, int(additive), int(imprint), 0, _p(e), _p(z))
+    if W < 0:
+        raise RuntimeError("cnf2h_qtlx_column failed (%d)" % W)
+    out = []
+    for j in range(W):
+        L.cnf2h_qtlx_column(n_cov, n_int, int(additive), int(imprint), j, _p(e), _p(z))
+        out.append((int(e[0]), int(z[0])))
+    return out
 
 
 def qtl_null_residuals(pheno, cov=None, use=None):

@@ -6,7 +6,10 @@ permutations, the residuals that are permuted when there are covariates (Freedma
 thresholds and reads peaks with their LOD-drop support intervals off a profile.  Nothing here scans.
 
 The pair scan (Context.qtl_scan2, cnf2_qtl_scan2) asks the next two questions -- is there a second locus, do two loci
-interact -- for every pair of selected markers: scan2, thresholds2 and pair_summary are its counterparts here."""
+interact -- for every pair of selected markers: scan2, thresholds2 and pair_summary are its counterparts here.
+
+The extended scan (Context.qtl_scanx, cnf2_qtl_scanx) asks of every marker whether its effect depends on the parent it came
+from (imprinting) and on a covariate (QTL x covariate interaction): scanx, coef_names and thresholdsx."""
 import numpy as np
 
 from . import synth
@@ -188,6 +191,76 @@ def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False,
             res = null_residuals(yk, cov, u)
             out["perm_max"][:, cols] = ctx.qtl_scan_device(n, d_o.data_ptr(), res, cov=cov, use=u, perm=perm,
                                                            additive=additive)["perm_max"]
+    return out
+
+
+def coef_names(interactive=0, imprint=False, additive=False, cov_names=None):
+    """The names of scanx's coef entries in their order: the main effects "a", "d" (unless additive), "i" (with imprint),
+    then for every interactive covariate the same effects as "a:z1", ...; cov_names replaces z1, z2, ..."""
+    eff = ["a"] + ([] if additive else ["d"]) + (["i"] if imprint else [])
+    zs = ["z%d" % (k + 1) for k in range(interactive)] if cov_names is None else list(cov_names)[:interactive]
+    if len(zs) != interactive:
+        raise ValueError("cov_names must name every interactive covariate")
+    return tuple(eff + ["%s:%s" % (e, z) for z in zs for e in eff])
+
+
+def scanx(ctx, pheno, cov=None, interactive=0, imprint=False, use=None, permutations=0, seed=0, additive=False, rows=None):
+    """The extended scan of a whole cross on the context's uploaded pedigree: as scan -- one origin sweep with the rows left on
+    the device (or `rows`, the tensor of origin_rows), per pattern of missing phenotypes (NaN) one observed scan with the
+    pattern's own `use`, and with permutations > 0 one more on the permuted residuals of the null model -- with the nested
+    models Mendelian (a, d), imprinting (+ i, with imprint) and interaction (+ the products with the first `interactive`
+    columns of cov).  A dict: lod[T][M][3], lod_imprint = lod[..., 1] - lod[..., 0], lod_interaction = lod[..., 2] -
+    lod[..., 1] (both [T][M]), coef[T][M][len(coef_names)], coef_names, rank[T][M][3], n_used[T][C],
+    perm_max[P][T][C][5] or None (thresholdsx)."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    K = 0 if cov is None else np.asarray(cov).reshape(n, -1).shape[1]
+    if not 0 <= interactive <= K:
+        raise ValueError("interactive must be 0 .. %d, the number of covariates" % K)
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    names = coef_names(interactive, imprint, additive)
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M, 3)), coef=np.full((T, M, len(names)), np.nan), coef_names=names,
+               rank=np.zeros((T, M, 3), np.int32), n_used=np.zeros((T, C), np.int32),
+               perm_max=np.zeros((permutations, T, C, 5)) if permutations else None)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    kw = dict(cov=cov, interactive=interactive, imprint=imprint, additive=additive)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = ctx.qtl_scanx_device(n, d_o.data_ptr(), yk, use=u, **kw)
+        out["lod"][cols], out["coef"][cols] = got["lod"], got["coef"]
+        out["rank"][cols], out["n_used"][cols] = got["rank"], got["n_used"]
+        if permutations:
+            perm = _permutations(n, permutations, seed, use=u)
+            res = null_residuals(yk, cov, u)
+            out["perm_max"][:, cols] = ctx.qtl_scanx_device(n, d_o.data_ptr(), res, use=u, perm=perm, **kw)["perm_max"]
+    out["lod_imprint"] = out["lod"][..., 1] - out["lod"][..., 0]
+    out["lod_interaction"] = out["lod"][..., 2] - out["lod"][..., 1]
+    return out
+
+
+THRESHOLDSX_KEYS = ("lod0", "lod1", "lod2", "imprint", "interaction")
+
+
+def thresholdsx(perm_max, alpha=(0.05, 0.01)):
+    """From perm_max[P][T][C][5] of the extended scan: per statistic -- lod0, lod1, lod2 (the three nested LODs), imprint
+    (lod[1] - lod[0]) and interaction (lod[2] - lod[1]) -- the dict thresholds() gives for it: genome[len(alpha)][T] and
+    chromosome[len(alpha)][T][C], by the same order statistic."""
+    pm = np.asarray(perm_max, np.float64)
+    if pm.ndim != 4 or pm.shape[0] == 0 or pm.shape[3] != 5:
+        raise ValueError("perm_max must be [P][T][C][5] with P >= 1")
+    out = dict(alpha=tuple(alpha))
+    for s, key in enumerate(THRESHOLDSX_KEYS):
+        th = thresholds(pm[..., s], alpha)
+        out[key] = dict(genome=th["genome"], chromosome=th["chromosome"])
     return out
 
 

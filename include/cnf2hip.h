@@ -121,6 +121,7 @@ enum {
                                      emission terms from the window's own seven rows, as the ordinary one does, instead of reading
                                      what a window's ancestors contribute from the launch's line records (cnf2_last_line_records).
                                      Same results to the bit; A/B switch and cross-check.  Ignored where no records are used */
+    CNF2_QTL_IMPRINT  = 1u << 25, /* cnf2_qtl_scanx: the design gets the parent-of-origin (imprinting) effect i = o[1] - o[2] */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
                                     registers by a transpose through LDS instead of being exchanged by DPP moves (same
@@ -554,6 +555,57 @@ int cnf2_qtl_scan2(cnf2_ctx *ctx, int n, const double *origin, int n_sel, const 
                    double *lod_add_out, double *lod_full_out, int32_t *rank_add_out, int32_t *rank_full_out,
                    double *rss0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
 int cnf2_set_qtl2_columns(cnf2_ctx *ctx, int cap);
+
+/* Extended single-locus scan: does a locus act differently by the parent it came from, and does its effect depend on a
+ * covariate?  Per marker three nested Haley-Knott designs are fitted to every phenotype column, observed and permuted.  One
+ * definition for this header, cnf2freq_amd/csrc/cnf2_qtlx.h (host and device), the kernels and tests/qtlx_reference.py.
+ * origin, pheno, use, cov, perm, the mask c of a chromosome, n_c and the columns R = T (1 + P) are cnf2_qtl_scan's.  The
+ * interactive covariates are the first n_int (= Ki, 0 <= Ki <= K) columns of cov.
+ *   effects   a = o[3] - o[0];  d = o[1] + o[2] (not with CNF2_QTL_ADDITIVE);  i = o[1] - o[2] (only with CNF2_QTL_IMPRINT):
+ *             o[1] is the heterozygote whose allele from the first parent descends from that parent's second grandparent,
+ *             o[2] the same of the second parent, so i is the classical imprinting regressor of line-cross analysis.
+ *             ne = 1, 2 or 3 of them
+ *   null      X0 = [c, c z_1 .. c z_K]
+ *   stage 0   "Mendelian"    a, d
+ *   stage 1   "imprinting"   i
+ *   stage 2   "interaction"  for k = 1 .. Ki: a z_k, d z_k, i z_k (those effects that are present)
+ * The width W = 1 + K + ne (1 + Ki) must be at most 15 (the 16 rows of one matrix instruction less a padding row).
+ * One factorisation gives every stage: the normal matrix of [design | y] under the mask, one sequential Cholesky in the
+ * column order above; a column of X0 needs a positive pivot, an added column is dropped (pivot 0) when its raw diagonal is 0
+ * or its pivot is below 1e-8 times its raw diagonal.  With w = L^-1 X'y over the kept columns
+ *   RSS0 = sum c y^2 - sum_{X0} w^2,  lod[s] = (n_c / 2) log10(RSS0 / (RSS0 - sum of w^2 over the kept columns of stages 0 .. s))
+ * with the cumulative reduction clamped to [0, RSS0 (1 - 2^-52)]: lod[0] <= lod[1] <= lod[2], all finite and not negative; a
+ * stage without columns repeats the previous value exactly.  lod[1] - lod[0] is the imprinting test (the (a, d, i) against
+ * the Mendelian model), lod[2] - lod[1] the interaction test.  rank[s] is the cumulative count of kept added columns; it
+ * depends on the design only and rank 0 gives LOD 0 exactly.  coef holds the effects of the FULL model -- back-substitution
+ * on the kept added columns -- in the column order above, NaN for a dropped column; the effects of a smaller model are had
+ * by a call with n_int = 0 and / or without CNF2_QTL_IMPRINT.  A chromosome with n_c < W + 1, or whose X0 has no Cholesky
+ * factor, is not scanned: ranks 0, LODs 0, coef NaN, rss0 0.  A column with RSS0 <= 0 gives LODs 0 and coef NaN.
+ * The rank rule is relative to a column's own length.  In a cross whose two heterozygotes cannot be told apart (an F2 of
+ * inbred lines: both F1 parents carry the same two lines) o[1] - o[2] is exactly 0 or the sweep's rounding noise; a noise
+ * column that is not exactly 0 is kept, with an effect of the order of 1e16 and the LOD of a random regressor.  The imprinting
+ * effect is for crosses whose founders are outbred; do not set CNF2_QTL_IMPRINT elsewhere.
+ *   lod_out      [T][M][3]    coef_out [T][M][ne (1 + Ki)]    rank_out [M][3] (int32)
+ *   rss0_out     [T][C]       n_used_out [C] (int32) n_c
+ *   perm_max_out [P][T][C][5] per permutation, trait and chromosome the maxima over the chromosome's markers of lod[0],
+ *                             lod[1], lod[2], lod[1] - lod[0] and lod[2] - lod[1] (each difference taken per cell); NULL
+ *                             exactly when P = 0
+ * CNF2_QTL_ADDITIVE, CNF2_QTL_ORIGIN_DEVICE (also with origin NULL: the rows the last cnf2_sweep_qtl left in the context,
+ * CNF2_ERR_STATE as for cnf2_qtl_scan) and CNF2_OUT_DEVICE act as for cnf2_qtl_scan2: device rows are read in place and the
+ * call leaves the context's rows valid.  Everything cnf2_qtl_scan refuses, n_int outside 0 .. K and W > 15 return
+ * CNF2_ERR_ARG and write nothing; an allocation that fails returns CNF2_ERR_NOMEM before anything is written.
+ * Launches: the masks; per tile of columns the column image (as cnf2_qtl_scan), per chromosome n_c, sum c y^2 and RSS0, and
+ * the marker kernel, a batched small SYRK on the f64 matrix cores -- a wave owns a marker, forms the design entries in
+ * registers from the origin row and the covariates, accumulates X'X and X'Y over the individuals in ascending order, factors
+ * the 16 x 16 tile once and lets one lane per column do the substitutions; the waves of a block take adjacent markers of
+ * one chromosome; a finish kernel reduces the permutations' maxima per chromosome.  No atomics and no split of the
+ * individuals: a call gives the same bits every time, for every column cap (cnf2_set_qtlx_columns, 0 = no cap; the tile
+ * keeps the image under 1 GB and the maxima under 256 MB) and from host or device rows. */
+int cnf2_qtl_scanx(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                   int n_cov, const double *cov, int n_int, int n_perm, const int32_t *perm, double *lod_out,
+                   double *coef_out, int32_t *rank_out, double *rss0_out, int32_t *n_used_out, double *perm_max_out,
+                   uint32_t flags);
+int cnf2_set_qtlx_columns(cnf2_ctx *ctx, int cap);
 
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU

@@ -147,6 +147,17 @@ int cnf2h_qtl_null_residuals(int n, int n_traits, const double *pheno, int n_cov
 int cnf2h_qtl2_pair(const double *gram, int n_col, const double *xty, const double *yy, int n_c, int n_cov, int additive,
                     int same_chrom, int32_t *out_rank, double *rss0_out, double *lod_add_out, double *lod_full_out);
 
+/* The small algebra of the extended single-locus scan (cnf2_qtl_scanx of cnf2hip.h; cnf2freq_amd/csrc/cnf2_qtlx.h) on the
+ * host, as its tests use it: gram[16][16] is the normal matrix of one marker's design in the model's column order (zero past
+ * its width; only the lower triangle is read), xty[n_col][16] and yy[n_col] the columns' X'y and sum c y^2.  Factors once
+ * with the rank rule, then per column the cell: out_rank[4] = usable, rank[0 .. 2]; rss0_out [n_col], lod_out [n_col][3],
+ * coef_out [n_col][ne (1 + n_int)].  -2: a bad argument or a design wider than 15 columns.
+ * cnf2h_qtlx_column: the effect code (0 = 1, 1 = a, 2 = d, 3 = i, 4 = none) and the modifier (0 = 1, k = covariate k - 1) of
+ * design column j; returns the design's width W (or -2). */
+int cnf2h_qtlx_marker(const double *gram, int n_col, const double *xty, const double *yy, int n_c, int n_cov, int n_int,
+                      int additive, int imprint, int32_t *out_rank, double *rss0_out, double *lod_out, double *coef_out);
+int cnf2h_qtlx_column(int n_cov, int n_int, int additive, int imprint, int j, int32_t *effect_out, int32_t *modifier_out);
+
 #ifdef __cplusplus
 }
 #endif
