@@ -10,6 +10,7 @@
 #include "cnf2_qtl_host.h"
 #include "../cnf2_qtl2.h"
 #include "../cnf2_qtlx.h"
+#include "../cnf2_qtlem.h"
 #include "cnf2_remap.h"
 
 using namespace cnf2host;
@@ -366,6 +367,18 @@ int cnf2h_qtlx_column(int n_cov, int n_int, int additive, int imprint, int j, in
     qtlx_column(ds, j, &e, &z);
     *effect_out = e, *modifier_out = z;
     return ds.w;
+}
+
+// one (marker, column) fit of the maximum-likelihood scan: qtlem_fit_serial (cnf2_qtlem.h)
+int cnf2h_qtlem_fit(int n, const double* origin, const double* y, int n_cov, const double* cov, const uint8_t* c, int additive,
+                    int imprint, int max_iter, double tol, double* lod_out, double* coef_out, double* sigma2_out,
+                    int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* rss0_out, int32_t* n_used_out)
+{
+    if (!lod_out || !coef_out || !sigma2_out || !iters_out || !status_out || !rank_out || !rss0_out || !n_used_out) return -2;
+    return cnf2::qtlem_fit_serial(n, origin, y, n_cov, cov, c, additive != 0, imprint != 0, max_iter, tol, lod_out, coef_out,
+                                  sigma2_out, iters_out, status_out, rank_out, rss0_out, n_used_out)
+               ? 0
+               : -2;
 }
 
 int cnf2h_qtl_null_residuals(int n, int n_traits, const double* pheno, int n_cov, const double* cov, const uint8_t* use,

@@ -9,7 +9,10 @@ The pair scan (Context.qtl_scan2, cnf2_qtl_scan2) asks the next two questions --
 interact -- for every pair of selected markers: scan2, thresholds2 and pair_summary are its counterparts here.
 
 The extended scan (Context.qtl_scanx, cnf2_qtl_scanx) asks of every marker whether its effect depends on the parent it came
-from (imprinting) and on a covariate (QTL x covariate interaction): scanx, coef_names and thresholdsx."""
+from (imprinting) and on a covariate (QTL x covariate interaction): scanx, coef_names and thresholdsx.
+
+The maximum-likelihood scan (Context.qtl_scan_em, cnf2_qtl_scan_em) fits the normal mixture over the origin classes by EM
+(interval mapping) where Haley-Knott regresses on their expectations: scan_em; thresholds and peaks read it as they read scan."""
 import numpy as np
 
 from . import synth
@@ -244,6 +247,49 @@ def scanx(ctx, pheno, cov=None, interactive=0, imprint=False, use=None, permutat
             out["perm_max"][:, cols] = ctx.qtl_scanx_device(n, d_o.data_ptr(), res, use=u, perm=perm, **kw)["perm_max"]
     out["lod_imprint"] = out["lod"][..., 1] - out["lod"][..., 0]
     out["lod_interaction"] = out["lod"][..., 2] - out["lod"][..., 1]
+    return out
+
+
+def scan_em(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, seed=0, additive=False, max_iter=1000, tol=1e-6,
+            rows=None):
+    """The maximum-likelihood scan of a whole cross on the context's uploaded pedigree: as scan -- one origin sweep with the
+    rows left on the device (or `rows`, the tensor of origin_rows), per pattern of missing phenotypes (NaN) one observed scan
+    with the pattern's own `use`, and with permutations > 0 one more on the permuted residuals of the null model -- with
+    every (marker, trait) fitted by EM from the null start until the log-likelihood gains less than tol LOD or max_iter
+    iterations are done.  A dict: lod[T][M], coef[T][M][len(coef_names)], coef_names ("a", "d" unless additive, "i" with
+    imprint), sigma2[T][M], iters[T][M], status[T][M] (0 = stopped by tol, 1 = by max_iter, 2 = breakdown), rank[T][M],
+    n_used[T][C], perm_max[P][T][C] or None (thresholds)."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    if not 1 <= int(max_iter) <= 10000:
+        raise ValueError("max_iter must be 1 .. 10000")
+    if not np.isfinite(tol):
+        raise ValueError("tol must be finite")
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    names = coef_names(0, imprint, additive)
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, len(names)), np.nan), coef_names=names, sigma2=np.full((T, M), np.nan),
+               iters=np.zeros((T, M), np.int32), status=np.zeros((T, M), np.int32), rank=np.zeros((T, M), np.int32),
+               n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C)) if permutations else None)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    kw = dict(cov=cov, imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = ctx.qtl_scan_em_device(n, d_o.data_ptr(), yk, use=u, **kw)
+        for key in ("lod", "coef", "sigma2", "iters", "status", "rank", "n_used"):
+            out[key][cols] = got[key]
+        if permutations:
+            perm = _permutations(n, permutations, seed, use=u)
+            res = null_residuals(yk, cov, u)
+            out["perm_max"][:, cols] = ctx.qtl_scan_em_device(n, d_o.data_ptr(), res, use=u, perm=perm, **kw)["perm_max"]
     return out
 
 

@@ -607,6 +607,50 @@ int cnf2_qtl_scanx(cnf2_ctx *ctx, int n, const double *origin, int n_traits, con
                    uint32_t flags);
 int cnf2_set_qtlx_columns(cnf2_ctx *ctx, int cap);
 
+/* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
+ * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;
+ * where a row is soft it leaves the within-individual genotype variance in the residual.  One definition for this header,
+ * cnf2freq_amd/csrc/cnf2_qtlem.h (host and device), the kernels and tests/qtlem_reference.py.
+ * origin, pheno, use, cov (0 <= K <= 8), perm, the mask c of a chromosome, n_c, X0 = [c, c z_1 .. c z_K] and the columns
+ * R = T (1 + P) are cnf2_qtl_scan's.
+ *   classes   g = 0 .. 3 = AA, BA, AB, BB in the order of the origin row, priors pi_ig = o_ig / sum_g o_ig at the marker; a class
+ *             with pi = 0 has weight 0 and never enters a logarithm
+ *   effects   a = (-1, 0, 0, 1);  d = (0, 1, 1, 0) (not with CNF2_QTL_ADDITIVE);  i = (0, 1, -1, 0) (only with
+ *             CNF2_QTL_IMPRINT);  ne of them, design width W = 1 + K + ne
+ *   model     y_i | g ~ N(x0_i' gamma + e(g)' beta, sigma^2);  l(theta) = sum_i c_i log sum_g pi_ig phi(y_i; mu_ig, sigma^2), with
+ *             the individual's largest exponent taken out;  l0 = -(n_c / 2)(log(2 pi RSS0 / n_c) + 1), RSS0 as in cnf2_qtl_scan
+ *   rank      from the design only: the prior means sum_g pi_ig e(g) are factored against X0 in the order a, d, i, as
+ *             cnf2_qtl_scanx treats its Mendelian and imprinting columns; an effect is dropped (beta = 0, coefficient NaN) when its
+ *             raw diagonal is 0 or its pivot is below 1e-8 times the diagonal.  rank[m] = the kept effects; rank 0: lod 0, iters
+ *             0, status 0.  A marker whose rows carry no linkage information is not fitted.
+ *   start     the null fit: gamma = S11^-1 b0, beta = 0, sigma^2 = RSS0 / n_c.  Fixed, so a fit is deterministic; EM may stop
+ *             at a local maximum.
+ *   iterate   t = 1, 2, ..: E-step w_ig ~ pi_ig exp(-(y_i - mu_ig)^2 / (2 sigma^2)) at theta_{t-1}; M-step = weighted least
+ *             squares over the expanded data, solved by the Schur complement on the factor of S11; sigma^2_t = the weighted
+ *             residual sum of squares / n_c; l_t = l(theta_t)
+ *   stop      after iteration t when (l_t - l_{t-1}) / ln 10 < tol or t = max_iter (a negative tol: exactly max_iter)
+ *   report    theta_t, lod = max(0, (l_t - l0) / ln 10), iters = t, status 0 (tol), 1 (max_iter) or 2 (breakdown: a kept pivot
+ *             of the M-step's Schur block not positive, or sigma^2_t not positive and finite; the last complete iterate is
+ *             reported)
+ *   not scanned   a chromosome with n_c < max(W + 1, K + 4) or without a factor of X0 (K + 4: RSS0 is cnf2_qtl_scan's):
+ *             rank 0, lod 0, coef and sigma2 NaN, rss0 0; a column with RSS0 <= 0: lod 0, coef and sigma2 NaN, iters 0
+ * max_iter is 1 .. 10 000 and tol finite.  Outputs (host memory, or device memory with CNF2_OUT_DEVICE): lod_out [T][M],
+ * coef_out [T][M][ne], sigma2_out [T][M], iters_out and status_out [T][M] int32, rank_out [M], rss0_out [T][C], n_used_out
+ * [C], perm_max_out [P][T][C] (the permuted columns contribute only there).  CNF2_QTL_ORIGIN_DEVICE: origin is device memory,
+ * or NULL for the rows the last cnf2_sweep_qtl left in the context (CNF2_ERR_STATE where it holds none of n individuals); the
+ * call leaves those rows valid.  Everything cnf2_qtl_scan refuses is refused, and so are max_iter and tol out of range:
+ * CNF2_ERR_ARG, and nothing is written.
+ * One wavefront owns one (marker, column) fit from start to stop: its lanes stride the individuals in ascending order, the
+ * sums of a pass are added across the wave in a fixed order and every lane takes the same step.  The waves of a block take
+ * adjacent markers of one chromosome; a finish kernel reduces the permutations' maxima per chromosome.  No atomics and no
+ * split of the individuals: a call gives the same bits every time, for every column cap (cnf2_set_qtlem_columns, 0 = no cap)
+ * and from host or device rows. */
+int cnf2_qtl_scan_em(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                     int n_cov, const double *cov, int n_perm, const int32_t *perm, int max_iter, double tol,
+                     double *lod_out, double *coef_out, double *sigma2_out, int32_t *iters_out, int32_t *status_out,
+                     int32_t *rank_out, double *rss0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
+int cnf2_set_qtlem_columns(cnf2_ctx *ctx, int cap);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every

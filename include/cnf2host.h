@@ -158,6 +158,16 @@ int cnf2h_qtlx_marker(const double *gram, int n_col, const double *xty, const do
                       int additive, int imprint, int32_t *out_rank, double *rss0_out, double *lod_out, double *coef_out);
 int cnf2h_qtlx_column(int n_cov, int n_int, int additive, int imprint, int j, int32_t *effect_out, int32_t *modifier_out);
 
+/* One (marker, phenotype column) fit of the maximum-likelihood scan (cnf2_qtl_scan_em of cnf2hip.h) on the host, by the
+ * functions of cnf2freq_amd/csrc/cnf2_qtlem.h that the kernels use, the individuals in ascending order: origin[n][4] the
+ * marker's rows, y[n], cov[n][n_cov], c[n] the chromosome's mask.  lod_out, coef_out [ne], sigma2_out, iters_out, status_out,
+ * rank_out, rss0_out and n_used_out receive one cell.  -2: a bad argument (n_cov above 8, max_iter outside 1 .. 10 000, a
+ * tol that is not finite). */
+int cnf2h_qtlem_fit(int n, const double *origin, const double *y, int n_cov, const double *cov, const uint8_t *c,
+                    int additive, int imprint, int max_iter, double tol, double *lod_out, double *coef_out,
+                    double *sigma2_out, int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *rss0_out,
+                    int32_t *n_used_out);
+
 #ifdef __cplusplus
 }
 #endif
