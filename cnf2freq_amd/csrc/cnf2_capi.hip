@@ -1453,7 +1453,7 @@ struct QtlArgs {
 };
 
 // every check of the phenotype side, before anything is written; use_out[n] = the mask with NULL expanded
-static int qtl_validate(cnf2_ctx* ctx, const QtlArgs& a, std::vector<uint8_t>* use_out)
+static int qtl_check(cnf2_ctx* ctx, const QtlArgs& a, std::vector<uint8_t>* use_out)
 {
     if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
     if (a.n < 1 || a.T < 1 || !a.pheno) return fail(ctx, CNF2_ERR_ARG, "n and n_traits must be at least 1 and pheno not NULL");
@@ -1487,6 +1487,43 @@ static int qtl_validate(cnf2_ctx* ctx, const QtlArgs& a, std::vector<uint8_t>* u
                 return fail(ctx, CNF2_ERR_ARG, "permutation %d gives individual %d, which is used, the unused individual %d", p, i, j);
         }
     }
+    return CNF2_OK;
+}
+
+// The model does not depend on the units and offsets of traits and fixed-effect covariates (include/cnf2hip.h); the sums the
+// kernels form -- X0'X0, y'y - b0' S11^-1 b0, A'y - G b0 -- cancel once a column's mean is large against its spread.  So every
+// scan works on columns with their mean over the used individuals subtracted: the intercept of X0 takes the mean up, and
+// LOD, effects, RSS0 and ranks are those of the raw columns.  A permutation maps used individuals to used ones and keeps a
+// column's mean; a constant column becomes exactly 0 (the second pass makes the mean of equal values that value), so a
+// constant trait keeps RSS0 = 0 and a constant covariate still leaves X0 without a factor.  The values of unused individuals
+// are copied as they are: nothing reads them.  `a` has been validated; its pheno and cov point into `store` afterwards.
+struct QtlCentred {
+    std::vector<double> pheno, cov;
+};
+static void qtl_centre_columns(const double* src, int n, int w, const std::vector<uint8_t>& use, std::vector<double>& dst)
+{
+    dst.assign(src, src + (size_t)n * w);
+    for (int k = 0; k < w; k++) {
+        const double mean = qtl_column_mean(src + k, n, w, use.data());
+        for (int i = 0; i < n; i++)
+            if (use[i]) dst[(size_t)i * w + k] = src[(size_t)i * w + k] - mean;
+    }
+}
+static void qtl_centre(QtlArgs& a, const std::vector<uint8_t>& use, QtlCentred& store)
+{
+    qtl_centre_columns(a.pheno, a.n, a.T, use, store.pheno);
+    a.pheno = store.pheno.data();
+    if (a.K > 0) {
+        qtl_centre_columns(a.cov, a.n, a.K, use, store.cov);
+        a.cov = store.cov.data();
+    }
+}
+
+// what every entry point does with the phenotype side before anything is written or uploaded: the checks, then the centring
+static int qtl_validate(cnf2_ctx* ctx, QtlArgs& a, std::vector<uint8_t>* use_out, QtlCentred* store)
+{
+    RC_TRY(qtl_check(ctx, a, use_out));
+    qtl_centre(a, *use_out, *store);
     return CNF2_OK;
 }
 
@@ -1590,9 +1627,10 @@ int cnf2_qtl_scan(cnf2_ctx* ctx, int n, const double* origin, int n_traits, cons
     if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
                  ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
         return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
-    const QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
-    RC_TRY(qtl_validate(ctx, a, &mask));
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const double* d_origin = kept ? ctx->d_org.ptr : origin;
     if (flags & CNF2_QTL_ORIGIN_DEVICE) {
@@ -1618,10 +1656,11 @@ int cnf2_sweep_qtl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_ou
     RC_TRY(ready(ctx));
     if (!factors_out || !loglik_out) return fail(ctx, CNF2_ERR_ARG, "factors_out and loglik_out must not be NULL");
     RC_TRY(mode_range(ctx, ind_begin, ind_end));
-    const QtlArgs a = {ind_end - ind_begin, n_traits, n_cov, n_perm, pheno, use, cov, perm,
-                       lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    QtlArgs a = {ind_end - ind_begin, n_traits, n_cov, n_perm, pheno, use, cov, perm,
+                 lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
-    RC_TRY(qtl_validate(ctx, a, &mask));
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
     const uint32_t sweep_flags = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL);
     const size_t   M = ctx->n_markers, C = ctx->n_chrom;
     if (flags & CNF2_OUT_DEVICE) {
@@ -1654,10 +1693,11 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
                  ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
         return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
     // (the phenotype side is the single scan's; its lod / coef / rank slots stand for this call's four pair outputs)
-    const QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_add_out, lod_full_out, rss0_out, perm_max_out,
-                       rank_add_out, n_used_out};
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_add_out, lod_full_out, rss0_out, perm_max_out,
+                 rank_add_out, n_used_out};
     std::vector<uint8_t> mask;
-    RC_TRY(qtl_validate(ctx, a, &mask));
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
     if (!rank_full_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
     if (n_cov > QTL2_MAXK) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d for the pair scan", QTL2_MAXK);
     if (n_sel < 2 || n_sel > QTL2_MAXL || !sel) return fail(ctx, CNF2_ERR_ARG, "n_sel must be 2 .. %d, with sel", QTL2_MAXL);
@@ -1765,9 +1805,10 @@ int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, con
     if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
                  ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
         return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
-    const QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
-    RC_TRY(qtl_validate(ctx, a, &mask));
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
     if (n_int < 0 || n_int > n_cov) return fail(ctx, CNF2_ERR_ARG, "n_int must be 0 .. n_cov");
     const QtlxDesign ds = qtlx_design(n_cov, n_int, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
     if (ds.w > QTLX_MAXW)
@@ -1806,7 +1847,9 @@ int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, con
     if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
     RC_TRY(ctx->d_qx_map.ensure(ctx, map.size()));
     RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
-    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
+    // (with interactive covariates the raw cov[n][K] follows the centred one: the products are those of the raw values)
+    const size_t n_covs = (size_t)a.n * a.K;
+    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, n_covs * (n_int > 0 ? 2 : 1))));
     RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
     RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
     RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
@@ -1828,13 +1871,18 @@ int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, con
     }
     RC_TRY(qtl_upload(ctx, ctx->d_qx_map, map.data(), map.size()));
     RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, n_covs));
+    if (n_int > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_q_cov.ptr + n_covs, cov, n_covs * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
     RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
     RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
 
     q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.Ki = n_int;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
     q.origin = d_origin, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use;
+    q.cov_raw = n_int > 0 ? ctx->d_q_cov.ptr + n_covs : ctx->d_q_cov.ptr;
     q.cs = ctx->d_qx_map, q.tiles = ctx->d_qx_map + (C + 1), q.tile_start = ctx->d_qx_map + o_tstart, q.n_tiles = (int)n_tiles;
     q.cmask = ctx->d_q_cmask, q.Y = ctx->d_q_Y, q.yy = ctx->d_qx_yy, q.tilemax = ctx->d_qx_tilemax, q.rstride = (int)rt;
     Qtl2Params k;                          // what qtl2_mask_kernel reads and writes
@@ -1880,9 +1928,10 @@ int cnf2_qtl_scan_em(cnf2_ctx* ctx, int n, const double* origin, int n_traits, c
     if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
                  ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
         return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
-    const QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
-    RC_TRY(qtl_validate(ctx, a, &mask));
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
     if (!sigma2_out || !iters_out || !status_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
     if (max_iter < 1 || max_iter > QTLEM_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLEM_MAX_ITER);
     if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");

@@ -42,6 +42,25 @@ constexpr int    QTL_MK    = 24;                     // doubles per marker recor
 constexpr int    QTL_PA    = 2 * QTL_NX, QTL_L = QTL_PA + 1, QTL_PD = QTL_PA + 2;
 constexpr double QTL_PIVOT = 1e-8;                   // a column is dropped when its pivot is below this times its raw diagonal
 
+// The mean of v[i * stride] over the individuals with use[i] != 0 (0 without any), in two passes: the second adds the mean of
+// what the first left, so that the mean of equal values is that value and a constant column minus its mean is exactly 0.
+// The scans subtract it from every trait and every covariate column of X0 before they form a sum (include/cnf2hip.h: they do
+// not depend on units and offsets); the intercept takes it up.
+CNF2_HD double qtl_column_mean(const double* v, int n, int stride, const uint8_t* use)
+{
+    int n_u = 0;
+    for (int i = 0; i < n; i++) n_u += use[i] ? 1 : 0;
+    if (n_u == 0) return 0.0;
+    double mean = 0.0;
+    for (int pass = 0; pass < 2; pass++) {
+        double s = 0.0;
+        for (int i = 0; i < n; i++)
+            if (use[i]) s += v[(size_t)i * stride] - mean;
+        mean += s / n_u;
+    }
+    return mean - mean == 0.0 ? mean : 0.0;       // (finite values whose sum is not: left as they are)
+}
+
 // S = L L' in place on the lower triangle of S[nx][QTL_NX]; false when a pivot is not positive (X0 without full rank)
 CNF2_HD bool qtl_cholesky(double* S, int nx)
 {

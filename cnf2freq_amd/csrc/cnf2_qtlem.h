@@ -27,6 +27,9 @@
 #define CNF2_QTLEM_H
 
 #include "cnf2_qtl.h"
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <vector>
+#endif
 
 namespace cnf2 {
 
@@ -395,14 +398,23 @@ CNF2_HD double qtlem_lod(const QtlemFit& f)
 #if !defined(__HIP_DEVICE_COMPILE__)
 // One (marker, column) fit on the CPU, the individuals in ascending order: o[n][4] the marker's origin rows, y[n], x0 the
 // covariates cov[n][K], c[n] the chromosome's mask.  Mirrors what the kernels do with the functions above.
+// As the scans do, it works on y and the covariates minus their means over the individuals of c (qtl_column_mean).
 // Returns false for bad arguments.  Outputs: lod, coef[ne] (NaN where dropped or not fitted), sigma2, iters, status, rank,
 // rss0 (0 for a chromosome that is not scanned), n_c.
-inline bool qtlem_fit_serial(int n, const double* o, const double* y, int K, const double* cov, const uint8_t* c, bool additive,
-                             bool imprint, int max_iter, double tol, double* lod, double* coef, double* sigma2, int32_t* iters,
-                             int32_t* status, int32_t* rank, double* rss0_out, int32_t* nc_out)
+inline bool qtlem_fit_serial(int n, const double* o, const double* y_raw, int K, const double* cov_raw, const uint8_t* c,
+                             bool additive, bool imprint, int max_iter, double tol, double* lod, double* coef, double* sigma2,
+                             int32_t* iters, int32_t* status, int32_t* rank, double* rss0_out, int32_t* nc_out)
 {
-    if (n < 1 || !o || !y || K < 0 || K > QTL_MAXK || (K > 0 && !cov) || !c) return false;
+    if (n < 1 || !o || !y_raw || K < 0 || K > QTL_MAXK || (K > 0 && !cov_raw) || !c) return false;
     if (max_iter < 1 || max_iter > QTLEM_MAX_ITER || !(tol - tol == 0.0)) return false;
+    std::vector<double> y(y_raw, y_raw + n), cov(cov_raw, cov_raw + (K > 0 ? (size_t)n * K : 0));
+    for (int k = -1; k < K; k++) {
+        double*      col    = k < 0 ? y.data() : cov.data() + k;
+        const int    stride = k < 0 ? 1 : K;
+        const double mean   = qtl_column_mean(col, n, stride, c);
+        for (int i = 0; i < n; i++)
+            if (c[i]) col[(size_t)i * stride] -= mean;
+    }
     const QtlemDesign ds = qtlem_design(K, additive, imprint);
     const int         nx = ds.nx;
     double S[QTL_NX * QTL_NX], b0[QTL_NX], x[QTL_NX], pi[4], yy = 0.0;

@@ -201,7 +201,8 @@ CNF2_QTLX_ROLLED
 struct QtlxParams {
     int n, M, C, T, P, K, Ki, additive, imprint;
     const double*  origin;       // [n][M][4]
-    const double*  cov;          // [n][K]
+    const double*  cov;          // [n][K] the columns of X0: every covariate minus its mean over the used individuals
+    const double*  cov_raw;      // [n][K] the covariates as given: the modifiers z_k of the interaction columns
     const uint8_t* use;          // [n]
     const int32_t* cs;           // [C + 1] chromstarts
     const uint8_t* cmask;        // [C][n]: use[i] and the row at the chromosome's first marker is not all zero (qtl2_mask_kernel)

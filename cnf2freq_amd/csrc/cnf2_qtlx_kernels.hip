@@ -139,7 +139,8 @@ __global__ __launch_bounds__(64 * QTLX_WAVES, 2) void qtlx_marker_kernel(QtlxPar
     const int        ncoef = ds.w - ds.nx;
     int se, sz;
     qtlx_column(ds, oi, &se, &sz);
-    const double* covp = q.cov + (sz > 0 ? sz - 1 : 0);
+    // (a column of X0 reads the centred covariate, an interaction column the raw one: cnf2_qtlx.h)
+    const double* covp = (se == QTLX_ONE ? q.cov : q.cov_raw) + (sz > 0 ? sz - 1 : 0);
     double* G = lds[wib];
     double* B = G + QTL2_W * QTLX_LD;
     int  col[QTLX_NT];

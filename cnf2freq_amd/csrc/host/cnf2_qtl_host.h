@@ -51,12 +51,15 @@ inline void qtl_permutations(int n, int P, uint64_t seed, const uint8_t* use, co
 }
 
 // res[n][T]: the residuals of every phenotype column on [1, cov] over the used individuals, 0 for the others
-// (qtl.null_residuals).  false when the null design has no Cholesky factor.
+// (qtl.null_residuals).  false when the null design has no Cholesky factor.  The normal equations are those of the columns
+// minus their means over the used individuals (qtl_column_mean, as in the scans): the residuals do not depend on offsets.
 inline bool qtl_null_residuals(int n, int T, const double* pheno, int K, const double* cov, const uint8_t* use, double* res)
 {
     using namespace cnf2;
     const int nx = K + 1;
-    auto      x  = [&](int i, int k) { return k == 0 ? 1.0 : cov[(size_t)i * K + (k - 1)]; };
+    double    zmean[QTL_NX] = {0.0};
+    for (int k = 1; k < nx; k++) zmean[k] = qtl_column_mean(cov + (k - 1), n, K, use);
+    auto      x  = [&](int i, int k) { return k == 0 ? 1.0 : cov[(size_t)i * K + (k - 1)] - zmean[k]; };
     double    S[QTL_NX * QTL_NX] = {0.0};
     for (int i = 0; i < n; i++)
         if (use[i])
@@ -65,16 +68,17 @@ inline bool qtl_null_residuals(int n, int T, const double* pheno, int K, const d
     std::fill(res, res + (size_t)n * T, 0.0);
     if (!qtl_cholesky(S, nx)) return false;
     for (int t = 0; t < T; t++) {
-        double b[QTL_NX] = {0.0};
+        const double ymean     = qtl_column_mean(pheno + t, n, T, use);
+        double       b[QTL_NX] = {0.0};
         for (int i = 0; i < n; i++)
             if (use[i])
-                for (int k = 0; k < nx; k++) b[k] += x(i, k) * pheno[(size_t)i * T + t];
+                for (int k = 0; k < nx; k++) b[k] += x(i, k) * (pheno[(size_t)i * T + t] - ymean);
         qtl_chol_solve(S, nx, b);
         for (int i = 0; i < n; i++)
             if (use[i]) {
                 double fit = 0.0;
                 for (int k = 0; k < nx; k++) fit += x(i, k) * b[k];
-                res[(size_t)i * T + t] = pheno[(size_t)i * T + t] - fit;
+                res[(size_t)i * T + t] = (pheno[(size_t)i * T + t] - ymean) - fit;
             }
     }
     return true;

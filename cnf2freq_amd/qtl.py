@@ -54,8 +54,11 @@ def null_residuals(pheno, cov=None, use=None):
         X = np.concatenate([X, z[:, None] if z.ndim == 1 else z], axis=1)
     res = np.zeros_like(y)
     if use.any():
-        beta = np.linalg.lstsq(X[use], y[use], rcond=None)[0]
-        res[use] = y[use] - X[use] @ beta
+        # (the columns minus their means over the used individuals: the residuals do not depend on offsets, the sums do)
+        Xu, yu = X[use], y[use] - y[use].mean(axis=0)
+        Xu[:, 1:] -= Xu[:, 1:].mean(axis=0)
+        beta = np.linalg.lstsq(Xu, yu, rcond=None)[0]
+        res[use] = yu - Xu @ beta
     return res
 
 

@@ -474,6 +474,11 @@ int cnf2_origin_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
  * column's coefficient is NaN; rank 0 gives lod = 0 exactly.  A chromosome with n_c < K + 4, or whose X0 has no Cholesky
  * factor, is not scanned: rank 0, lod 0 and coef NaN at its markers.  A column with RSS0 <= 0 gives lod 0 and coef NaN.  dRSS
  * is clamped to [0, RSS0 (1 - 2^-52)]: a LOD is finite and not negative.
+ * Units and offsets: with the intercept in X0 the model does not depend on them -- under y -> alpha y + beta and
+ * z_k -> gamma_k z_k + delta_k LOD, rank, n_c and perm_max stay, coef scales with alpha and RSS0 with alpha^2 -- and neither do
+ * the results, here and in the three scans below: every call subtracts from each trait and each covariate column of X0 its
+ * mean over the used individuals before any sum is formed (a constant column becomes exactly 0), so no sum cancels a large
+ * mean against a small spread.  An interaction column of cnf2_qtl_scanx is the product with the covariate as given.
  *   lod_out      [T][M]       coef_out [T][M][2] (additive, dominance effect)       rank_out [M] (int32)
  *   rss0_out     [T][C]       n_used_out [C] (int32) n_c
  *   perm_max_out [P][T][C]    per permutation, trait and chromosome the largest LOD; NULL exactly when P = 0.  The maximum

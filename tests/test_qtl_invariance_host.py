@@ -1,0 +1,186 @@
+"""CPU suite: the QTL scans on shifted and rescaled traits and covariates (tests/qtl_invariance.py).  The transforms are exact;
+the maps that carry a base reference over to a transformed problem are proved on the yardsticks themselves, where those are
+accurate (a small shift, pure scalings); the yardsticks' own error on the large shifts is printed, which is why the mapped
+base reference is the reference; and the host library's pieces -- one fit of the maximum-likelihood scan
+(cnf2h_qtlem_fit, the header the device compiles) and the residuals `cnF2freq --qtl*` permutes (cnf2h_qtl_null_residuals),
+with qtl.null_residuals beside them -- are held to ATOL under every transform."""
+import numpy as np
+import pytest
+
+import qtl_invariance as V
+import qtlem_reference as RE
+from cnf2freq_amd import host, qtl
+from qtl_reference import ATOL, reference_scan
+
+TRANSFORM_IDS = sorted(V.TRANSFORMS)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def built():
+    import __graft_entry__ as g
+    g.build()
+
+
+# ------------------------------------------------------------------------------------------------ exactness
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+def test_transforms_are_exact(case):
+    base = V.make_base(case)
+    assert np.all(np.abs(np.nan_to_num(base["pheno"])) < 16) and np.all(np.nan_to_num(base["pheno"]) % V.GRID == 0)
+    assert np.all(np.abs(np.nan_to_num(base["cov"])) < 16) and np.all(np.nan_to_num(base["cov"]) % V.GRID == 0)
+    for name in TRANSFORM_IDS:
+        for tr in (V.TRANSFORMS[name], V.interactive_variant(V.TRANSFORMS[name])):
+            t = V.apply(base, tr)               # (asserts that the inverse returns the base bits)
+            assert np.array_equal(np.isnan(t["pheno"]), np.isnan(base["pheno"]))
+            changed = np.any(tr["alpha"] != 1) or np.any(tr["beta"] != 0) or np.any(tr["gamma"] != 1) or np.any(tr["delta"] != 0)
+            assert changed and not (V.same_bits(t["pheno"], base["pheno"]) and V.same_bits(t["cov"], base["cov"]))
+    s = V.order_of(case[1])
+    assert np.array_equal(np.sort(s), np.arange(case[1])) and not np.array_equal(s, np.arange(case[1]))
+
+
+# ------------------------------------------------------------------------------------------------ the mapping
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", list(V.SCANS))
+def test_mapping_on_the_yardsticks(scan, case):
+    """The yardstick on transforms A (a small shift), F and G (pure scalings) agrees with the mapped base reference within
+    ATOL, by the scan's own comparison; for F and G also in the base problem's units, where that comparison is relative to
+    figures of order 1.  This proves the formulas of map_reference; no product code runs.  (The interactive variant shifts
+    the other covariate by 2^4 here, not 2^14: at 2^14 the yardstick's own effects are off by 1e-9 of their size, which the
+    comparison of F, relative to effects of order 2^100, would count.)"""
+    base, ref, names = V.make_base(case), V.base_reference(case, scan), V.coef_names(scan)
+    if "near" in ref:
+        assert ref["near"].mean() <= 0.01
+    for name in ("A", "F", "G"):
+        tr = V.transform_for(scan, V.TRANSFORMS[name], shift=2.0 ** 4)
+        yard = V.as_got(scan, V.reference(scan, V.apply(base, tr)))
+        want = V.map_reference(ref, tr["alpha"], tr["gamma"], names)
+        what = "yardstick %s %s transform %s" % (scan, case[0], name)
+        print(V.errors_line(what, V.errors(yard, want)))
+        V.check(scan, yard, want, what)
+        if name in "FG":
+            V.check(scan, V.unmap(yard, tr, names), ref, what + " in base units")
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", ["scan", "scanx-int", "scan2", "em-fixed"])
+def test_relabelling_maps_on_the_yardsticks(scan, case):
+    """the relabellings do no arithmetic on the inputs: the yardstick on the relabelled problem agrees with the mapped base"""
+    base, ref, names = V.make_base(case), V.base_reference(case, scan), V.coef_names(scan)
+    for name in V.RELABELLINGS:
+        if name == "covswap" and V.SCANS[scan].get("interactive"):
+            continue
+        inp, flip = V.relabel(base, name)
+        what = "yardstick %s %s relabelling %s" % (scan, case[0], name)
+        V.check(scan, V.as_got(scan, V.reference(scan, inp)), V.map_reference(ref, names=names, flip=flip), what)
+
+
+# ------------------------------------------------------------------------------------------------ the yardsticks' own error
+@pytest.mark.parametrize("scan", ["scan", "scanx", "scan2", "em-fixed"])
+def test_yardstick_error_on_large_shifts(scan):
+    """Printed, not asserted: how far the float64 yardsticks themselves are from the mapped base reference on B, D and E.  They
+    are no reference there."""
+    case = V.CASES[1]
+    base, ref, names = V.make_base(case), V.base_reference(case, scan), V.coef_names(scan)
+    for name in ("B", "D", "E"):
+        tr = V.TRANSFORMS[name]
+        yard = V.unmap(V.as_got(scan, V.reference(scan, V.apply(base, tr))), tr, names)
+        err = V.errors(yard, ref)
+        print(V.errors_line("yardstick's own error %s %s transform %s" % (scan, case[0], name), err))
+        assert all(np.isfinite(v) for v in err.values())
+
+
+# ------------------------------------------------------------------------------------------------ cnf2h_qtlem_fit
+FIT_MARKERS = (3, 20, 70)        # on chromosomes 2, 3 (where the second case skips two individuals) and 5
+FIT = dict(imprint=True, max_iter=300, tol=1e-7)
+
+
+def fit_cells(case, inp):
+    """host.qtlem_fit at FIT_MARKERS x traits on the inputs `inp`"""
+    o = inp["origin"]
+    use = np.ones(o.shape[0], bool) if inp["use"] is None else inp["use"]
+    cells = {}
+    for m in FIT_MARKERS:
+        c = int(np.searchsorted(V.CS, m, side="right") - 1)
+        mask = use & (o[:, V.CS[c]] != 0.0).any(axis=1)
+        for t in range(V.T):
+            cells[m, t] = host.qtlem_fit(o[:, m], np.where(mask, inp["pheno"][:, t], 0.0), np.where(mask[:, None], inp["cov"], 0.0),
+                                         mask, **FIT)
+    return cells
+
+
+_FIT_BASE = {}
+
+
+def fit_base(case):
+    """(the product's fits on the base problem, near[m, t] of the yardstick on the three markers, each a chromosome of its own)"""
+    if case not in _FIT_BASE:
+        base = V.make_base(case)
+        sub = np.ascontiguousarray(base["origin"][:, list(FIT_MARKERS)])
+        ref = RE.reference_scan_em(sub, np.arange(len(FIT_MARKERS) + 1), base["pheno"], base["use"], base["cov"], True, None, False,
+                                   FIT["max_iter"], FIT["tol"])
+        assert ref["near"].mean() <= 0.01 and np.all(ref["rank"] == 3) and np.all(ref["status"] == 0)
+        near = {(m, t): bool(ref["near"][t, j]) for j, m in enumerate(FIT_MARKERS) for t in range(V.T)}
+        cells = fit_cells(case, base)
+        for (m, t), f in cells.items():          # the base fits themselves are the yardstick's
+            j = FIT_MARKERS.index(m)
+            assert abs(f["lod"] - ref["lod"][0, t, j]) <= ATOL and f["rank"] == 3 and f["status"] == 0
+            assert near[m, t] or f["iters"] == ref["iters"][t, j]
+        _FIT_BASE[case] = (cells, near)
+    return _FIT_BASE[case]
+
+
+@pytest.mark.parametrize("name", TRANSFORM_IDS)
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+def test_qtlem_fit(case, name):
+    """one fit of the maximum-likelihood scan under a transform against the same fit of the base problem: lod within ATOL,
+    coef and sigma2 in base units relative to max(1, |.|), rank, status and iterations equal"""
+    tr = V.TRANSFORMS[name]
+    want, near = fit_base(case)
+    got = fit_cells(case, V.apply(V.make_base(case), tr))
+    worst = dict(lod=0.0, coef=0.0, sigma2=0.0, rss0=0.0)
+    for (m, t), g in got.items():
+        w, a = want[m, t], tr["alpha"][t]
+        worst["lod"] = max(worst["lod"], abs(g["lod"] - w["lod"]))
+        worst["coef"] = max(worst["coef"], np.max(np.abs(g["coef"] / a - w["coef"]) / np.maximum(1.0, np.abs(w["coef"]))))
+        worst["sigma2"] = max(worst["sigma2"], abs(g["sigma2"] / a ** 2 - w["sigma2"]) / max(1.0, abs(w["sigma2"])))
+        worst["rss0"] = max(worst["rss0"], abs(g["rss0"] / a ** 2 - w["rss0"]) / max(1.0, abs(w["rss0"])))
+    print(V.errors_line("host.qtlem_fit %s transform %s" % (case[0], name), worst))
+    for (m, t), g in got.items():
+        w = want[m, t]
+        assert (g["rank"], g["status"], g["n_used"]) == (w["rank"], w["status"], w["n_used"]), (m, t)
+        assert near[m, t] or g["iters"] == w["iters"], (m, t, g["iters"], w["iters"])
+    assert worst["lod"] <= ATOL and worst["coef"] <= ATOL and worst["sigma2"] <= ATOL and worst["rss0"] <= ATOL
+
+
+# ------------------------------------------------------------------------------------------------ the residuals that are permuted
+LENS3 = V.CHROM_LENS[:3]         # the small permuted scan of the thresholds: the first 18 markers
+
+
+def thresholds_text(case, res):
+    """the 5-digit thresholds of a permuted Haley-Knott scan (the yardstick) of the residuals `res` on three chromosomes"""
+    base = V.make_base(case)
+    cs = V.chromstarts_of(LENS3)
+    pm = reference_scan(base["origin"][:, :cs[-1]], cs, res, base["use"], base["cov"], base["perm"])["perm_max"]
+    th = qtl.thresholds(pm, alpha=(0.5, 0.05))
+    return ["%.5f" % v for v in np.concatenate([th["genome"].ravel(), th["chromosome"].ravel()])]
+
+
+@pytest.mark.parametrize("name", TRANSFORM_IDS)
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+def test_null_residuals(case, name):
+    """cnf2h_qtl_null_residuals and qtl.null_residuals under a transform: res / alpha within ATOL of the base residuals, and
+    the same printed thresholds from them"""
+    tr = V.TRANSFORMS[name]
+    base = V.make_base(case)
+    use = np.ones(case[1], bool) if base["use"] is None else base["use"]
+    zero = lambda inp: (np.where(use[:, None], inp["pheno"], 0.0), np.where(use[:, None], inp["cov"], 0.0), use)
+    want = qtl.null_residuals(*zero(base))
+    np.testing.assert_allclose(host.qtl_null_residuals(*zero(base)), want, rtol=0, atol=1e-12)
+    want_text = thresholds_text(case, want)
+    t = V.apply(base, tr)
+    for what, f in (("host.qtl_null_residuals", host.qtl_null_residuals), ("qtl.null_residuals", qtl.null_residuals)):
+        res = f(*zero(t)) / tr["alpha"]
+        err = np.abs(res - want).max()
+        print("%s %s transform %s: %.3g" % (what, case[0], name, err))
+        assert np.all(res[~use] == 0.0)
+        assert err <= ATOL, what
+        assert thresholds_text(case, res) == want_text, what
