@@ -24,6 +24,7 @@
 #include "cnf2_qtl2.h"
 #include "cnf2_qtlx.h"
 #include "cnf2_qtlem.h"
+#include "cnf2_qtlbin.h"
 
 using namespace cnf2;
 
@@ -186,6 +187,13 @@ struct cnf2_ctx {
     int             qtlem_columns = 0;
     DevBuf<double>  d_qe_tilemax, d_qe_lod, d_qe_coef, d_qe_sigma2, d_qe_rss0, d_qe_rss0_null, d_qe_pmax;   // _null: what qtl_null_kernel reports
     DevBuf<int32_t> d_qe_map, d_qe_keep, d_qe_nc, d_qe_rank, d_qe_iters, d_qe_status;   // d_qe_map: as d_q_map, tiles of 4
+
+    // binary-trait single-locus scan (cnf2_qtl_scan_binary): its column cap, which effects a marker keeps, which chromosomes
+    // are scanned, the null fits, the tile maxima, staged outputs; the staged inputs, the mask and the column image are the
+    // single scan's buffers (d_q_chol only receives what qtl_chrom_kernel writes beside the mask: this scan does not read it)
+    int             qtlbin_columns = 0;
+    DevBuf<double>  d_qb_null, d_qb_tilemax, d_qb_lod, d_qb_coef, d_qb_ll0, d_qb_pmax;
+    DevBuf<int32_t> d_qb_map, d_qb_keep, d_qb_scan, d_qb_nc, d_qb_rank, d_qb_iters, d_qb_status, d_qb_ones;   // d_qb_map: as d_qe_map
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -418,6 +426,14 @@ int cnf2_set_qtlem_columns(cnf2_ctx* ctx, int cap)
     if (!ctx) return CNF2_ERR_ARG;
     if (cap < 0) return fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative");
     ctx->qtlem_columns = cap;
+    return CNF2_OK;
+}
+
+int cnf2_set_qtlbin_columns(cnf2_ctx* ctx, int cap)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (cap < 0) return fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative");
+    ctx->qtlbin_columns = cap;
     return CNF2_OK;
 }
 
@@ -2042,6 +2058,151 @@ int cnf2_qtl_scan_em(cnf2_ctx* ctx, int n, const double* origin, int n_traits, c
         RC_TRY(fetch_out(ctx, iters_out, (const int32_t*)q.iters, cells));
         RC_TRY(fetch_out(ctx, status_out, (const int32_t*)q.status, cells));
         RC_TRY(fetch_out(ctx, a.rss0, (const double*)q.rss0, (size_t)a.T * C));
+        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, (const double*)q.pmax, (size_t)a.P * a.T * C));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// The binary-trait single-locus scan on device rows d_origin[n][M][4]: cnf2_qtlbin.h, cnf2_qtlbin_kernels.hip.  The masks, n_c
+// and the column image are the kernels of cnf2_qtl_kernels.hip.  The covariates are centred as in every scan; the 0/1 trait
+// is not.  Everything is checked and every buffer is there before the first launch writes.
+int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
+                         const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
+                         double* coef_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out,
+                         int32_t* n_ones_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
+                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, ll0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    QtlCentred           centred;
+    RC_TRY(qtl_check(ctx, a, &mask));
+    if (!iters_out || !status_out || !n_ones_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if (max_iter < 1 || max_iter > QTLBIN_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLBIN_MAX_ITER);
+    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
+    for (int i = 0; i < a.n; i++) {
+        if (!mask[i]) continue;
+        for (int t = 0; t < a.T; t++) {
+            const double y = a.pheno[(size_t)i * a.T + t];
+            if (!(y == 0.0 || y == 1.0)) return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is used and neither 0 nor 1", t, i);
+        }
+    }
+    if (a.K > 0) {
+        qtl_centre_columns(a.cov, a.n, a.K, mask, centred.cov);
+        a.cov = centred.cov.data();
+    }
+    const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
+    const int M = ctx->n_markers, C = ctx->n_chrom;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double* d_origin = kept ? ctx->d_org.ptr : origin;
+    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
+    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
+    // the map as the kernels read it: chromstarts, marker -> chromosome, the marker tiles (none straddles a chromosome start)
+    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
+    map.resize((size_t)C + 1 + M);
+    std::vector<int32_t> tiles, tstart(1, 0);
+    for (int c = 0; c < C; c++) {
+        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
+        for (int m = f; m < e; m++) map[(size_t)C + 1 + m] = c;
+        for (int m = f; m < e; m += QTLBIN_TILE) {
+            const int32_t t4[4] = {c, m, std::min(QTLBIN_TILE, e - m), 0};
+            tiles.insert(tiles.end(), t4, t4 + 4);
+        }
+        tstart.push_back((int32_t)(tiles.size() / 4));
+    }
+    const size_t n_tiles = tiles.size() / 4, o_tiles = map.size();
+    map.insert(map.end(), tiles.begin(), tiles.end());
+    const size_t o_tstart = map.size();
+    map.insert(map.end(), tstart.begin(), tstart.end());
+    // the column tile: the image under 1 GB, the tile maxima under 256 MB, the launch grid's second dimension, the caller's cap
+    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
+    rt = std::min(rt, (size_t)4096);
+    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (8 * std::max<size_t>(1, n_tiles))));
+    rt = std::min(rt, R);
+    if (ctx->qtlbin_columns > 0) rt = std::min(rt, (size_t)ctx->qtlbin_columns);
+
+    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
+    QtlbinParams q;
+    memset(&q, 0, sizeof(q));
+    QtlParams g;                           // what the kernels of cnf2_qtl_kernels.hip read and write
+    memset(&g, 0, sizeof(g));
+    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
+    RC_TRY(ctx->d_qb_map.ensure(ctx, map.size()));
+    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
+    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
+    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
+    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
+    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_qb_keep.ensure(ctx, (size_t)M));
+    RC_TRY(ctx->d_qb_scan.ensure(ctx, (size_t)C));
+    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
+    RC_TRY(ctx->d_qb_null.ensure(ctx, (size_t)C * QTLBIN_NULLQ * rt));
+    if (a.P > 0) RC_TRY(ctx->d_qb_tilemax.ensure(ctx, n_tiles * rt));
+    const size_t cells = (size_t)a.T * M;
+    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_qb_nc, (size_t)C, &g.nc));
+    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_qb_rank, (size_t)M, &q.rank));
+    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_qb_lod, cells, &q.lod));
+    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_qb_coef, cells * ds.ne, &q.coef));
+    RC_TRY(stage_out(ctx, dev, iters_out, ctx->d_qb_iters, cells, &q.iters));
+    RC_TRY(stage_out(ctx, dev, status_out, ctx->d_qb_status, cells, &q.status));
+    RC_TRY(stage_out(ctx, dev, ll0_out, ctx->d_qb_ll0, (size_t)a.T * C, &q.ll0));
+    RC_TRY(stage_out(ctx, dev, n_ones_out, ctx->d_qb_ones, (size_t)a.T * C, &q.n_ones));
+    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_qb_pmax, (size_t)a.P * a.T * C, &q.pmax));
+    if (staged) {
+        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
+        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_origin = ctx->d_org;
+    }
+    RC_TRY(qtl_upload(ctx, ctx->d_qb_map, map.data(), map.size()));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+
+    g.n = a.n, g.M = M, g.C = C, g.T = a.T, g.P = a.P, g.K = a.K, g.nx = ds.nx;
+    g.origin = d_origin, g.pheno = ctx->d_q_pheno, g.cov = ctx->d_q_cov, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm;
+    g.cs = ctx->d_qb_map, g.mchrom = ctx->d_qb_map + (C + 1);
+    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol, g.Y = ctx->d_q_Y, g.rstride = (int)rt;
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
+    q.max_iter = max_iter, q.tol = tol;
+    q.origin = d_origin, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
+    q.tiles = ctx->d_qb_map + o_tiles, q.tile_start = ctx->d_qb_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = ctx->d_qb_keep, q.scan = ctx->d_qb_scan;
+    q.Y = ctx->d_q_Y, q.nullq = ctx->d_qb_null, q.tilemax = ctx->d_qb_tilemax, q.rstride = (int)rt;
+
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_qb_scan.ptr, 0, (size_t)C * sizeof(int32_t), ctx->stream));     // (a chromosome without markers has no thread to say so)
+    launch_qtl_chrom(g, ctx->stream);
+    launch_qtlbin_rank(q, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = g.r0 = (int)r0;
+        q.rn = g.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(g, ctx->stream);
+        launch_qtlbin_null(q, ctx->stream);
+        launch_qtlbin_fit(q, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtlbin_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dev) {
+        RC_TRY(fetch_out(ctx, a.n_used, (const int32_t*)g.nc, (size_t)C));
+        RC_TRY(fetch_out(ctx, a.rank, (const int32_t*)q.rank, (size_t)M));
+        RC_TRY(fetch_out(ctx, a.lod, (const double*)q.lod, cells));
+        RC_TRY(fetch_out(ctx, a.coef, (const double*)q.coef, cells * ds.ne));
+        RC_TRY(fetch_out(ctx, iters_out, (const int32_t*)q.iters, cells));
+        RC_TRY(fetch_out(ctx, status_out, (const int32_t*)q.status, cells));
+        RC_TRY(fetch_out(ctx, ll0_out, (const double*)q.ll0, (size_t)a.T * C));
+        RC_TRY(fetch_out(ctx, n_ones_out, (const int32_t*)q.n_ones, (size_t)a.T * C));
         if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, (const double*)q.pmax, (size_t)a.P * a.T * C));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

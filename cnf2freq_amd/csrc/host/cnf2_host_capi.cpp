@@ -11,6 +11,7 @@
 #include "../cnf2_qtl2.h"
 #include "../cnf2_qtlx.h"
 #include "../cnf2_qtlem.h"
+#include "../cnf2_qtlbin.h"
 #include "cnf2_remap.h"
 
 using namespace cnf2host;
@@ -377,6 +378,18 @@ int cnf2h_qtlem_fit(int n, const double* origin, const double* y, int n_cov, con
     if (!lod_out || !coef_out || !sigma2_out || !iters_out || !status_out || !rank_out || !rss0_out || !n_used_out) return -2;
     return cnf2::qtlem_fit_serial(n, origin, y, n_cov, cov, c, additive != 0, imprint != 0, max_iter, tol, lod_out, coef_out,
                                   sigma2_out, iters_out, status_out, rank_out, rss0_out, n_used_out)
+               ? 0
+               : -2;
+}
+
+// one (marker, column) fit of the binary-trait scan: qtlbin_fit_serial (cnf2_qtlbin.h)
+int cnf2h_qtlbin_fit(int n, const double* origin, const double* y, int n_cov, const double* cov, const uint8_t* c, int additive,
+                     int imprint, int max_iter, double tol, double* lod_out, double* coef_out, int32_t* iters_out,
+                     int32_t* status_out, int32_t* rank_out, double* ll0_out, int32_t* n_ones_out, int32_t* n_used_out)
+{
+    if (!lod_out || !coef_out || !iters_out || !status_out || !rank_out || !ll0_out || !n_ones_out || !n_used_out) return -2;
+    return cnf2::qtlbin_fit_serial(n, origin, y, n_cov, cov, c, additive != 0, imprint != 0, max_iter, tol, lod_out, coef_out,
+                                   iters_out, status_out, rank_out, ll0_out, n_ones_out, n_used_out)
                ? 0
                : -2;
 }

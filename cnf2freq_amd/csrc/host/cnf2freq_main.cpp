@@ -7,6 +7,7 @@
 //            [--qtl2 F [--qtl2-every S] --phenofile P [the --qtl-* options]]
 //            [--qtlx F --phenofile P [--qtl-imprint] [--qtl-interactive name,name] [the --qtl-* options]]
 //            [--qtlem F --phenofile P [--qtl-em-iterations N] [--qtl-em-tol X] [--qtl-imprint] [the --qtl-* options]]
+//            [--qtlbin F --phenofile P [--qtl-binary-iterations N] [--qtl-binary-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -107,6 +108,7 @@
 #include "cnf2_qtl_host.h"
 #include "../cnf2_qtlx.h"
 #include "../cnf2_qtlem.h"
+#include "../cnf2_qtlbin.h"
 #include "cnf2_readers.h"
 #include "cnf2_rccl_transport.h"
 #include "cnf2_remap.h"
@@ -164,6 +166,11 @@ struct Options {
     int         qtlem_iterations = 1000; // --qtl-em-iterations
     double      qtlem_tol = 1e-6;        // --qtl-em-tol
     bool        qtlem_extra_set = false; // one of the two above was given
+    std::string qtlbin;                  // --qtlbin F: binary-trait scan (with --phenofile and the --qtl-* options, --qtl-imprint)
+    int         qtlbin_iterations = 50;  // --qtl-binary-iterations
+    double      qtlbin_tol = 1e-7;       // --qtl-binary-tol
+    bool        qtlbin_extra_set = false; // one of the two above was given
+    std::vector<int> qtlbin_trait_cols;  // columns of pheno: the traits whose values are all 0 or 1
     std::vector<int> qtlx_cov_cols;      // columns of pheno: the interactive covariates first, then the others
     int         qtlx_n_int = 0;
     PhenoTable  pheno;                   // P as read (main, before any rank starts)
@@ -262,6 +269,21 @@ static bool parse(int argc, char** argv, Options& o)
                 exit(2);
             }
         }
+        else if (a == "--qtlbin") o.qtlbin = val();
+        else if (a == "--qtl-binary-iterations") {
+            o.qtlbin_iterations = atoi(val().c_str());
+            o.qtlbin_extra_set  = true;
+        }
+        else if (a == "--qtl-binary-tol") {
+            const std::string t = val();
+            char*             end = nullptr;
+            o.qtlbin_tol       = strtod(t.c_str(), &end);
+            o.qtlbin_extra_set = true;
+            if (t.empty() || *end != 0 || !std::isfinite(o.qtlbin_tol)) {
+                fprintf(stderr, "--qtl-binary-tol needs a finite number, not \"%s\"\n", t.c_str());
+                exit(2);
+            }
+        }
         else if (a == "--qtl2-every") {
             o.qtl2_every     = atoi(val().c_str());
             o.qtl2_every_set = true;
@@ -303,6 +325,7 @@ static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlem_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -397,6 +420,8 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtl2.empty()) qtl2_scan(opt, P, ctx, !opt.qtl.empty());
     if (world == 1 && !opt.qtlx.empty()) qtlx_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty());
     if (world == 1 && !opt.qtlem.empty()) qtlem_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty());
+    if (world == 1 && !opt.qtlbin.empty())
+        qtlbin_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -845,6 +870,123 @@ static void qtlem_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows
         if (NP > 0) fprintf(out, "threshold\tlod\t%.5lf\t%.5lf\n", thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
     }
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlem);
+}
+
+// --qtlbin after the last round (single GPU), and after the other scans where they are given: the binary-trait scan
+// (cnf2_qtl_scan_binary) of the traits whose values are all 0 or 1, on the rows a cnf2_sweep_qtl left in the context -- theirs,
+// or one of this function's own.  Traits are grouped by their pattern of missing values as for --qtl; permutations permute the
+// 0/1 values themselves.  The file holds one table per trait, the tables separated by a blank line: a line "trait" and the
+// name; per marker chromosome, position, n, the rank, the LOD, the iterations, the status (0 = stopped by --qtl-binary-tol,
+// 1 = by --qtl-binary-iterations, 2 = breakdown) and the effects a, d (not with --qtl-additive), i (with --qtl-imprint), "-" for
+// a dropped one or a cell without a fit; with --qtl-permutations K > 0 a line "threshold", "lod" and the 5 % and 1 %
+// genome-wide thresholds.
+static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtlbin_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    const int NC = cnf2::qtlem_design(K, opt.qtl_additive, opt.qtl_imprint).ne;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtlbin_trait_cols[t]];
+    }
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | (opt.qtl_imprint ? CNF2_QTL_IMPRINT : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    std::vector<double>  lod((size_t)T * M), coef((size_t)T * M * NC), thr((size_t)T * 2, 0.0);
+    std::vector<int32_t> rank((size_t)T * M), nused((size_t)T * C), iters((size_t)T * M), status((size_t)T * M);
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M), cf((size_t)Tg * M * NC), l0((size_t)Tg * C), pm((size_t)NP * Tg * C);
+        std::vector<int32_t> rk(M), nu(C), it((size_t)Tg * M), st((size_t)Tg * M), n1((size_t)Tg * C), perm((size_t)NP * N);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc;
+        if (!rows_kept) {          // the sweep, with the rows left in the context; its Haley-Knott scan is not reported
+            std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), l1((size_t)Tg * M), c1((size_t)Tg * M * 2), r1((size_t)Tg * C);
+            std::vector<int32_t> k1(M), m1(C);
+            rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                l1.data(), c1.data(), k1.data(), r1.data(), m1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlbin: ") + cnf2_last_error(ctx));
+            rows_kept = true;
+        }
+        if (NP > 0) qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+        rc = cnf2_qtl_scan_binary(ctx, N, nullptr, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, NP, NP ? perm.data() : nullptr,
+                                  opt.qtlbin_iterations, opt.qtlbin_tol, l.data(), cf.data(), it.data(), st.data(), rk.data(), l0.data(),
+                                  n1.data(), nu.data(), NP ? pm.data() : nullptr, flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlbin: ") + cnf2_last_error(ctx));
+        for (int t = 0; t < Tg; t++) {
+            const size_t from = (size_t)t * M, to = (size_t)tr[t] * M;
+            std::copy(l.begin() + from, l.begin() + from + M, lod.begin() + to);
+            std::copy(it.begin() + from, it.begin() + from + M, iters.begin() + to);
+            std::copy(st.begin() + from, st.begin() + from + M, status.begin() + to);
+            std::copy(cf.begin() + from * NC, cf.begin() + (from + M) * NC, coef.begin() + to * NC);
+            std::copy(rk.begin(), rk.end(), rank.begin() + to);
+            std::copy(nu.begin(), nu.end(), nused.begin() + (size_t)tr[t] * C);
+            if (NP > 0) {
+                std::vector<double> mx(NP, 0.0);
+                for (int p = 0; p < NP; p++)
+                    for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[((size_t)p * Tg + t) * C + c]);
+                thr[(size_t)tr[t] * 2]     = qtl_threshold(mx, 0.05);
+                thr[(size_t)tr[t] * 2 + 1] = qtl_threshold(mx, 0.01);
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtlbin.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlbin);
+    for (int t = 0; t < T; t++) {
+        fprintf(out, "%strait\t%s\n", t ? "\n" : "", opt.pheno.columns[opt.qtlbin_trait_cols[t]].c_str());
+        for (int c = 0; c < C; c++)
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const size_t at = (size_t)t * M + m;
+                fprintf(out, "%d\t%.5lf\t%d\t%d\t%.5lf\t%d\t%d", c + 1, P.pos[m], (int)nused[(size_t)t * C + c], (int)rank[at], lod[at],
+                        (int)iters[at], (int)status[at]);
+                for (int e = 0; e < NC; e++) {
+                    const double v = coef[at * NC + e];
+                    if (v != v) fprintf(out, "\t-");
+                    else fprintf(out, "\t%.5lf", v);
+                }
+                fprintf(out, "\n");
+            }
+        if (NP > 0) fprintf(out, "threshold\tlod\t%.5lf\t%.5lf\n", thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlbin);
+}
+
+// the traits --qtlbin scans: the non-covariate columns whose values, where not missing, are all 0 or 1 (and not all missing)
+static bool prepare_qtlbin(Options& opt)
+{
+    for (int col : opt.qtl_trait_cols) {
+        bool binary = true, any = false;
+        for (const std::vector<double>& row : opt.pheno.rows) {
+            const double v = row[col];
+            if (v != v) continue;
+            any = true;
+            if (!(v == 0.0 || v == 1.0)) binary = false;
+        }
+        if (binary && any) opt.qtlbin_trait_cols.push_back(col);
+    }
+    if (opt.qtlbin_trait_cols.empty()) {
+        fprintf(stderr, "--qtlbin: no column of %s that is not a covariate holds only 0 and 1\n", opt.phenofile.c_str());
+        return false;
+    }
+    return true;
 }
 
 // --qtl2-every S: every S-th marker of each chromosome from its first (cnf2freq_amd/qtl.py's select_every)
@@ -1306,7 +1448,23 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-em-iterations must be 1 .. %d\n", cnf2::QTLEM_MAX_ITER);
         return 2;
     }
-    if (opt.qtlx.empty() && (opt.qtl_interactive_set || (opt.qtlx_extra_set && opt.qtlem.empty()))) {
+    if (opt.gpus > 1 && !opt.qtlbin.empty()) {
+        fprintf(stderr, "--qtlbin needs a single GPU (--gpus 1): a fit is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlbin.empty() && opt.qtlbin_extra_set) {
+        fprintf(stderr, "--qtl-binary-iterations and --qtl-binary-tol need --qtlbin FILE\n");
+        return 2;
+    }
+    if (!opt.qtlbin.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlbin FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtlbin_iterations < 1 || opt.qtlbin_iterations > cnf2::QTLBIN_MAX_ITER) {
+        fprintf(stderr, "--qtl-binary-iterations must be 1 .. %d\n", cnf2::QTLBIN_MAX_ITER);
+        return 2;
+    }
+    if (opt.qtlx.empty() && (opt.qtl_interactive_set || (opt.qtlx_extra_set && opt.qtlem.empty() && opt.qtlbin.empty()))) {
         fprintf(stderr, "--qtl-imprint and --qtl-interactive need --qtlx FILE\n");
         return 2;
     }
@@ -1314,7 +1472,8 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtlx FILE needs --phenofile FILE\n");
         return 2;
     }
-    if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+    if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() &&
+        (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -1346,7 +1505,9 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-permutations must not be negative\n");
         return 2;
     }
-    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty()) && !prepare_qtl(opt, P)) return 2;
+    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty()) && !prepare_qtl(opt, P))
+        return 2;
+    if (!opt.qtlbin.empty() && !prepare_qtlbin(opt)) return 2;
     if (!opt.qtlx.empty() && !prepare_qtlx(opt)) return 2;
     if (!opt.qtl2.empty() && opt.qtl_cov_cols.size() > 6) {
         fprintf(stderr, "--qtl2: at most 6 covariates\n");

@@ -14,7 +14,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
-           "cnf2h_qtlem_fit"]
+           "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -64,6 +64,7 @@ def load():
         L.cnf2h_qtlx_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.cnf2h_qtlx_column.argtypes = [i32, i32, i32, i32, i32, vp, vp]
         L.cnf2h_qtlem_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_qtlbin_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -175,6 +176,30 @@ def qtlem_fit(origin, y, cov=None, c=None, additive=False, imprint=False, max_it
         raise RuntimeError("cnf2h_qtlem_fit failed (%d)" % rc)
     return dict(lod=float(d[0]), coef=coef, sigma2=float(d[1]), iters=int(i3[0]), status=int(i3[1]), rank=int(i3[2]),
                 rss0=float(d[2]), n_used=int(i3[3]))
+
+
+def qtlbin_fit(origin, y, cov=None, c=None, additive=False, imprint=False, max_iter=50, tol=1e-7):
+    """cnf2h_qtlbin_fit: one (marker, column) fit of the binary-trait scan (cnf2_qtlbin.h) on the marker's rows origin[n][4],
+    the 0/1 phenotype y[n], covariates cov[n][K] and the chromosome's mask c[n] (None: everybody).  A dict: lod, coef[ne],
+    iters, status, rank, ll0, n_ones, n_used.  CPU only."""
+    L = load()
+    o = np.ascontiguousarray(origin, np.float64)
+    y = np.ascontiguousarray(y, np.float64).reshape(-1)
+    n = len(y)
+    if o.shape != (n, 4):
+        raise ValueError("origin must be [n][4] and y [n]")
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    ne = 1 + (0 if additive else 1) + (1 if imprint else 0)
+    d, coef, i5 = np.zeros(2), np.zeros(ne), np.zeros(5, np.int32)
+    rc = L.cnf2h_qtlbin_fit(n, _p(o), _p(y), K, None if K == 0 else _p(z), _p(m), int(additive), int(imprint), int(max_iter),
+                            float(tol), _p(d[0:1]), _p(coef), _p(i5[0:1]), _p(i5[1:2]), _p(i5[2:3]), _p(d[1:2]), _p(i5[3:4]),
+                            _p(i5[4:5]))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtlbin_fit failed (%d)" % rc)
+    return dict(lod=float(d[0]), coef=coef, iters=int(i5[0]), status=int(i5[1]), rank=int(i5[2]), ll0=float(d[1]),
+                n_ones=int(i5[3]), n_used=int(i5[4]))
 
 
 def qtl_null_residuals(pheno, cov=None, use=None):

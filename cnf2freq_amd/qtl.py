@@ -12,7 +12,10 @@ The extended scan (Context.qtl_scanx, cnf2_qtl_scanx) asks of every marker wheth
 from (imprinting) and on a covariate (QTL x covariate interaction): scanx, coef_names and thresholdsx.
 
 The maximum-likelihood scan (Context.qtl_scan_em, cnf2_qtl_scan_em) fits the normal mixture over the origin classes by EM
-(interval mapping) where Haley-Knott regresses on their expectations: scan_em; thresholds and peaks read it as they read scan."""
+(interval mapping) where Haley-Knott regresses on their expectations: scan_em; thresholds and peaks read it as they read scan.
+
+The binary-trait scan (Context.qtl_scan_binary, cnf2_qtl_scan_binary) fits a logistic regression of a 0/1 trait per marker:
+scan_binary, read by thresholds and peaks in the same way."""
 import numpy as np
 
 from . import synth
@@ -293,6 +296,55 @@ def scan_em(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, seed=
             perm = _permutations(n, permutations, seed, use=u)
             res = null_residuals(yk, cov, u)
             out["perm_max"][:, cols] = ctx.qtl_scan_em_device(n, d_o.data_ptr(), res, use=u, perm=perm, **kw)["perm_max"]
+    return out
+
+
+def scan_binary(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, seed=0, strata=None, additive=False, max_iter=50,
+                tol=1e-7, rows=None):
+    """The binary-trait scan of a whole cross on the context's uploaded pedigree: as scan_em -- one origin sweep with the rows
+    left on the device (or `rows`, the tensor of origin_rows) and per pattern of missing phenotypes (NaN) one observed scan
+    with the pattern's own `use` -- with every (marker, trait) a logistic regression of the 0/1 trait on the covariates and
+    the effects a, d (unless additive), i (with imprint), fitted by Newton's method from the null fit until the log-likelihood
+    gains less than tol LOD or max_iter iterations are done.  A finite phenotype other than 0 or 1 raises ValueError.
+    With permutations > 0 the raw 0/1 values are permuted (the residuals of Freedman and Lane do not exist for this model),
+    within the strata of `strata` (qtl.permutations): with covariates the permutations are valid only within strata of the
+    covariates, which the caller supplies.  A dict: lod[T][M], coef[T][M][len(coef_names)], coef_names, iters[T][M],
+    status[T][M] (0 = stopped by tol, 1 = by max_iter, 2 = breakdown, e.g. a separated marker), rank[T][M], ll0[T][C] (the
+    null model's log-likelihood, 0 where the trait is not scanned on the chromosome), n_ones[T][C], n_used[T][C],
+    perm_max[P][T][C] or None (thresholds)."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    if not 1 <= int(max_iter) <= 1000:
+        raise ValueError("max_iter must be 1 .. 1000")
+    if not np.isfinite(tol):
+        raise ValueError("tol must be finite")
+    missing = ~np.isfinite(y)
+    if not np.all(missing | (y == 0.0) | (y == 1.0)):
+        raise ValueError("a binary trait is 0 or 1 (NaN where it is missing)")
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    names = coef_names(0, imprint, additive)
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, len(names)), np.nan), coef_names=names,
+               iters=np.zeros((T, M), np.int32), status=np.zeros((T, M), np.int32), rank=np.zeros((T, M), np.int32),
+               ll0=np.zeros((T, C)), n_ones=np.zeros((T, C), np.int32), n_used=np.zeros((T, C), np.int32),
+               perm_max=np.zeros((permutations, T, C)) if permutations else None)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    kw = dict(cov=cov, imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        perm = _permutations(n, permutations, seed, use=u, strata=strata) if permutations else None
+        got = ctx.qtl_scan_binary_device(n, d_o.data_ptr(), yk, use=u, perm=perm, **kw)
+        for key in ("lod", "coef", "iters", "status", "rank", "ll0", "n_ones", "n_used"):
+            out[key][cols] = got[key]
+        if permutations:
+            out["perm_max"][:, cols] = got["perm_max"]
     return out
 
 

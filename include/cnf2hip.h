@@ -656,6 +656,48 @@ int cnf2_qtl_scan_em(cnf2_ctx *ctx, int n, const double *origin, int n_traits, c
                      int32_t *rank_out, double *rss0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
 int cnf2_set_qtlem_columns(cnf2_ctx *ctx, int cap);
 
+/* Binary-trait single-locus scan: logistic regression of a 0/1 trait on the origin rows, fitted per marker and phenotype
+ * column, observed and permuted, by iteratively reweighted least squares (Newton's method).  The four scans above assume a
+ * normally distributed trait.  One definition for this header, cnf2freq_amd/csrc/cnf2_qtlbin.h (host and device), the kernels
+ * and tests/qtlbin_reference.py.
+ * origin, use, cov (0 <= K <= 8, taken minus their means), perm, the mask c of a chromosome, n_c and the columns R = T (1 + P)
+ * are cnf2_qtl_scan's; pheno[n][T] is 0.0 or 1.0 for every used individual (its values are not centred).
+ *   design    per marker that of cnf2_qtl_scanx's models 0 and 1: X0 = [1, z_1 .. z_K], then a = o[3] - o[0], d = o[1] + o[2]
+ *             (not with CNF2_QTL_ADDITIVE), i = o[1] - o[2] (only with CNF2_QTL_IMPRINT); ne effects, width W = 1 + K + ne
+ *   model     eta_i = x_i' theta;  l(theta) = sum_i c_i [ y_i eta_i - softplus(eta_i) ], softplus(eta) = max(eta, 0) +
+ *             log1p(exp(-|eta|)); p and w = p (1 - p) from that one exponential: nothing overflows for a finite eta
+ *   rank      from the design only, cnf2_qtl_scanx's rule: the unweighted columns are factored in the order X0, a, d, i; an
+ *             effect is dropped (beta = 0, coefficient NaN) when its raw diagonal is 0 or its pivot is below 1e-8 times the
+ *             diagonal.  rank[m] = the kept effects = cnf2_qtl_scanx's rank[m][1] with imprinting, rank[m][0] without.
+ *             rank 0: lod 0, iters 0, status 0.
+ *   null fit  per chromosome and column on X0, from gamma = (logit(n_1 / n_c), 0, ..), n_1 the ones among the n_c: at most 50
+ *             iterations, stopped by a gain below 1e-13 LOD.  It gives l0 (ll0_out, always < 0) and gamma0.
+ *   fit       from theta_0 = (gamma0, 0), l_0 = l0.  A pass at theta_t gives l_t, G = X'WX and s = X'(y - p) over the kept
+ *             columns.  After the pass at theta_t, t >= 1: (l_t - l_{t-1}) / ln 10 < tol stops with status 0 (a negative tol:
+ *             never), else t = max_iter stops with status 1.  Otherwise theta_{t+1} = theta_t + G^-1 s by a Cholesky factor; a
+ *             pivot that is not positive or a theta_{t+1} that is not finite is a breakdown, status 2 (where separation ends).
+ *             There is no step-halving: a loss of likelihood stops the fit by the first rule.
+ *   report    theta_t, lod = max(0, (l_t - l0) / ln 10), iters = t, status
+ *   not scanned   a chromosome with n_c < W + 1 or without a factor of X0: rank 0; on a chromosome a column with n_1 = 0 or
+ *             n_1 = n_c, or whose null fit does not stop by its tolerance or breaks down.  Then lod 0, coef NaN, iters 0,
+ *             status 0, ll0 0.
+ * max_iter is 1 .. 1000 and tol finite.  Outputs (host memory, or device memory with CNF2_OUT_DEVICE): lod_out [T][M],
+ * coef_out [T][M][ne], iters_out and status_out [T][M] int32, rank_out [M], ll0_out [T][C], n_ones_out [T][C] int32,
+ * n_used_out [C], perm_max_out [P][T][C] (the permuted columns contribute only there; perm permutes the phenotype only).
+ * CNF2_QTL_ORIGIN_DEVICE: origin is device memory, or NULL for the rows the last cnf2_sweep_qtl left in the context
+ * (CNF2_ERR_STATE where it holds none of n individuals); the call leaves those rows valid.  Everything cnf2_qtl_scan refuses
+ * is refused, and so are max_iter and tol out of range and a used phenotype that is not exactly 0 or 1: CNF2_ERR_ARG, and
+ * nothing is written.
+ * One wavefront owns one (marker, column) fit from start to stop: its lanes stride the individuals in ascending order, the
+ * sums of a pass are added across the wave in a fixed order and every lane takes the same step.  No atomics and no split of
+ * the individuals: a call gives the same bits every time, for every column cap (the setter below, 0 = no cap) and from host
+ * or device rows. */
+int cnf2_qtl_scan_binary(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                         int n_cov, const double *cov, int n_perm, const int32_t *perm, int max_iter, double tol,
+                         double *lod_out, double *coef_out, int32_t *iters_out, int32_t *status_out, int32_t *rank_out,
+                         double *ll0_out, int32_t *n_ones_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
+int cnf2_set_qtlbin_columns(cnf2_ctx *ctx, int cap);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every

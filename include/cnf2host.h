@@ -168,6 +168,16 @@ int cnf2h_qtlem_fit(int n, const double *origin, const double *y, int n_cov, con
                     double *sigma2_out, int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *rss0_out,
                     int32_t *n_used_out);
 
+/* One (marker, phenotype column) fit of the binary-trait scan (cnf2_qtl_scan_binary of cnf2hip.h) on the host, by the
+ * functions of cnf2freq_amd/csrc/cnf2_qtlbin.h that the kernels use, the individuals in ascending order: origin[n][4] the
+ * marker's rows, y[n] (0 or 1 where c is set), cov[n][n_cov], c[n] the chromosome's mask.  lod_out, coef_out [ne], iters_out,
+ * status_out, rank_out, ll0_out, n_ones_out and n_used_out receive one cell.  -2: a bad argument (n_cov above 8, max_iter
+ * outside 1 .. 1000, a tol that is not finite, a y under the mask that is neither 0 nor 1). */
+int cnf2h_qtlbin_fit(int n, const double *origin, const double *y, int n_cov, const double *cov, const uint8_t *c,
+                     int additive, int imprint, int max_iter, double tol, double *lod_out, double *coef_out,
+                     int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *ll0_out, int32_t *n_ones_out,
+                     int32_t *n_used_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,367 @@
+"""The yardstick of the binary-trait scan's tests (tests/test_qtlbin_host.py, tests/test_gpu_qtlbin.py): the logistic
+regression of include/cnf2hip.h per marker and column in numpy, by a route that shares nothing with the product's packed
+Cholesky form (cnf2freq_amd/csrc/cnf2_qtlbin.h).  The design is explicit, with the rows of individuals with c_i = 0 deleted
+and the covariates as given (not centred); softplus, p and w come from np.logaddexp; the step is np.linalg.solve on X'WX.
+Which effects a marker keeps comes from qtlx_reference's sequential pivots: the residual of a column after projection on
+every column before it.
+
+Independent of the stopping rule, `anchor` maximises the same likelihood in longdouble by 60 Newton steps from theta = 0 with
+an elimination of its own; the converged yardstick must agree with it (assert_anchor)."""
+import numpy as np
+
+from cnf2freq_amd import synth
+from qtl_reference import ATOL, CHROM_LENS, PIVOT_DROP, PIVOT_EXACT, PIVOT_WELL, chromstarts_of, columns, noise, reference_scan, skip, soft_rows  # noqa: F401
+from qtlx_reference import certain_rows, effects, reference_scanx  # noqa: F401
+from qtlem_reference import CODES, degenerate_rows  # noqa: F401
+
+LN10 = np.log(10.0)
+NULL_ITER, NULL_TOL = 50, 1e-13
+ETA_MAX = 12.0           # cells whose linear predictor stays within this are compared
+# A deciding gain is the difference of two log-likelihoods that are each compared within ATOL: a gain within ATOL of tol may
+# fall on either side in another arithmetic.  Relative to the tol of the tests (1e-7) that is 1e-2.
+NEAR_TOL = 1e-2
+
+
+def terms(X, y, theta):
+    """l(theta), p, w and the largest |eta|: softplus by np.logaddexp, p = exp(-softplus(-eta)), w = exp(-softplus(eta) - softplus(-eta))"""
+    eta = X @ theta
+    sp, sm = np.logaddexp(0.0, eta), np.logaddexp(0.0, -eta)
+    return float((y * eta - sp).sum()), np.exp(-sm), np.exp(-sp - sm), float(np.abs(eta).max()) if len(eta) else 0.0
+
+
+def irls(X, y, theta, ll_start, max_iter, tol):
+    """Newton's method by the rule of include/cnf2hip.h from theta, whose log-likelihood is ll_start (None: computed).  A dict:
+    ll (the trace l_0 .. l_t), theta, iters, status, gains (of the last two iterations), maxeta."""
+    theta = np.array(theta, np.float64)
+    trace, gains, t, maxeta = [], [], 0, 0.0
+    while True:
+        ll, p, w, me = terms(X, y, theta)
+        maxeta = max(maxeta, me)
+        if t == 0 and ll_start is not None:
+            ll = ll_start
+        if t >= 1:
+            gains.append((ll - trace[-1]) / LN10)
+        trace.append(ll)
+        if t >= 1 and gains[-1] < tol:
+            status = 0
+            break
+        if t >= 1 and t >= max_iter:
+            status = 1
+            break
+        G = X.T @ (X * w[:, None])
+        try:
+            np.linalg.cholesky(G)
+            new = theta + np.linalg.solve(G, X.T @ (y - p))
+        except np.linalg.LinAlgError:
+            status = 2
+            break
+        if not np.isfinite(new).all():
+            status = 2
+            break
+        theta, t = new, t + 1
+    return dict(ll=np.array(trace), theta=theta, iters=t, status=status, gains=gains[-2:], maxeta=maxeta)
+
+
+def null_fit(X0, y):
+    """(l0, gamma0) of a column on X0, or None where the column is not scanned"""
+    n, n1 = len(y), int(y.sum())
+    if n1 == 0 or n1 == n:
+        return None
+    g = np.zeros(X0.shape[1])
+    g[0] = np.log(n1 / (n - n1))
+    f = irls(X0, y, g, None, NULL_ITER, NULL_TOL)
+    if f["status"] != 0 or f["iters"] < 1 or not f["ll"][-1] < 0.0:
+        return None
+    return float(f["ll"][-1]), f["theta"]
+
+
+def solve_ld(G, s):
+    """G^-1 s in longdouble by Gauss-Jordan elimination with partial pivoting (numpy's solvers are double)"""
+    A = np.concatenate([np.array(G, np.longdouble), np.array(s, np.longdouble)[:, None]], axis=1)
+    q = len(s)
+    for j in range(q):
+        p = j + int(np.argmax(np.abs(A[j:, j])))
+        A[[j, p]] = A[[p, j]]
+        A[j] /= A[j, j]
+        others = np.arange(q) != j
+        A[others] -= A[others, j:j + 1] * A[j]
+    return A[:, q]
+
+
+def anchor(X, y, steps=60):
+    """the maximum of l over theta by `steps` Newton steps from theta = 0 in longdouble: no start from the null fit, no
+    stopping rule, no double-precision solver"""
+    X, y = np.array(X, np.longdouble), np.array(y, np.longdouble)
+    theta = np.zeros(X.shape[1], np.longdouble)
+    for _ in range(steps):
+        eta = X @ theta
+        p = 1.0 / (1.0 + np.exp(-eta))
+        w = p * (1.0 - p)
+        theta = theta + solve_ld(X.T @ (X * w[:, None]), X.T @ (y - p))
+    eta = X @ theta
+    return float((y * eta - np.logaddexp(np.longdouble(0.0), eta)).sum())
+
+
+def reference_scan_binary(origin, chromstarts, pheno, use=None, cov=None, imprint=False, perm=None, additive=False, max_iter=50,
+                          tol=1e-7, anchor_every=0):
+    """The model of include/cnf2hip.h.  A dict: lod[1 + P][T][M] (block 0 observed), trace[T][M][max_iter + 1] of the observed
+    columns' LODs after every iteration (the last value repeated), coef[T][M][ne], iters[T][M], status[T][M], near[T][M] (a
+    deciding gain lies within NEAR_TOL of tol), maxeta[T][M] (maxeta_all[1 + P][T][M] with the permuted columns), rank[M], relpivot[M][ne], usable[C], n_used[C], ll0[T][C],
+    n_ones[T][C], perm_max[P][T][C]; with anchor_every = k > 0 also anchor_err, the largest |LOD - anchor's LOD| over the
+    observed cells of every k-th marker that stopped by tol."""
+    o = np.asarray(origin, np.float64)
+    n, M, _ = o.shape
+    cs = np.asarray(chromstarts, np.int64)
+    C = len(cs) - 1
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    Z = np.zeros((n, 0)) if cov is None else np.where(use[:, None], np.asarray(cov, np.float64).reshape(n, -1), 0.0)
+    X0all = np.concatenate([np.ones((n, 1)), Z], axis=1)
+    nx = X0all.shape[1]
+    eff = effects(additive, imprint)
+    ne = len(eff)
+    yy = np.where(use[:, None], np.nan_to_num(np.asarray(pheno, np.float64).reshape(n, -1)), 0.0)
+    hk = reference_scanx(o, cs, yy[:, :1], use, cov, 0, imprint, None, additive)
+    Y = columns(yy, perm)
+    Q, T = Y.shape[1], Y.shape[2]
+    lod = np.zeros((Q, T, M))
+    trace = np.zeros((T, M, max_iter + 1))
+    coef = np.full((T, M, ne), np.nan)
+    iters, status, near = np.zeros((T, M), np.int32), np.zeros((T, M), np.int32), np.zeros((T, M), bool)
+    maxeta = np.zeros((T, M))
+    maxeta_all = np.zeros((Q, T, M))
+    rank = np.zeros(M, np.int32)
+    ll0_out, n_ones = np.zeros((T, C)), np.zeros((T, C), np.int32)
+    anchor_err = 0.0
+    for c in range(C):
+        keep = use & (o[:, cs[c]] != 0.0).any(axis=1)
+        X0 = X0all[keep]
+        n_ones[:, c] = Y[keep, 0].sum(axis=0)
+        if not hk["usable"][c]:
+            continue
+        nulls = [[null_fit(X0, Y[keep, qq, t]) for t in range(T)] for qq in range(Q)]
+        for t in range(T):
+            if nulls[0][t] is not None:
+                ll0_out[t, c] = nulls[0][t][0]
+        for m in range(cs[c], cs[c + 1]):
+            kept = np.nan_to_num(hk["relpivot"][m], nan=0.0) >= PIVOT_DROP
+            rank[m] = int(kept.sum())
+            assert rank[m] == hk["rank"][m][1]
+            if rank[m] == 0:
+                continue
+            om = o[keep, m]
+            val = dict(a=om[:, 3] - om[:, 0], d=om[:, 1] + om[:, 2], i=om[:, 1] - om[:, 2])
+            X = np.column_stack([X0] + [val[e] for e, k in zip(eff, kept) if k])
+            for qq in range(Q):
+                for t in range(T):
+                    if nulls[qq][t] is None:
+                        continue
+                    l0, g0 = nulls[qq][t]
+                    y = Y[keep, qq, t]
+                    f = irls(X, y, np.concatenate([g0, np.zeros(rank[m])]), l0, max_iter, tol)
+                    lod[qq, t, m] = max(0.0, (f["ll"][-1] - l0) / LN10)
+                    maxeta_all[qq, t, m] = f["maxeta"]
+                    if qq == 0:
+                        tr = np.maximum(0.0, (f["ll"] - l0) / LN10)
+                        trace[t, m, :len(tr)] = tr
+                        trace[t, m, len(tr):] = tr[-1]
+                        coef[t, m, kept] = f["theta"][nx:]
+                        iters[t, m], status[t, m], maxeta[t, m] = f["iters"], f["status"], f["maxeta"]
+                        near[t, m] = any(abs(g - tol) <= NEAR_TOL * abs(tol) for g in f["gains"])
+                        if anchor_every and m % anchor_every == 0 and f["status"] == 0 and f["maxeta"] <= ETA_MAX:
+                            anchor_err = max(anchor_err, abs(f["ll"][-1] - anchor(X, y)) / LN10)
+    perm_max = np.zeros((Q - 1, T, C))
+    for c in range(C):
+        perm_max[:, :, c] = lod[1:, :, cs[c]:cs[c + 1]].max(axis=2)
+    return dict(lod=lod, trace=trace, coef=coef, iters=iters, status=status, near=near, maxeta=maxeta, rank=rank,
+                relpivot=hk["relpivot"], usable=hk["usable"], n_used=hk["n_used"], ll0=ll0_out, n_ones=n_ones, perm_max=perm_max,
+                anchor_err=anchor_err, maxeta_all=maxeta_all)
+
+
+def compared_cells(ref, chromstarts, share=0.99, strict=True):
+    """compared[T][M]: the cells of markers whose every effect is either well conditioned (relative pivot at least PIVOT_WELL)
+    or exactly degenerate (at most PIVOT_EXACT, or a raw diagonal of 0), or whose chromosome is not scanned, and whose linear
+    predictor stayed within ETA_MAX.  Asserts on the reference alone what the comparison rests on."""
+    cs = np.asarray(chromstarts, np.int64)
+    rp = ref["relpivot"]
+    fine = np.all(np.isnan(rp) | (rp >= PIVOT_WELL) | (rp <= PIVOT_EXACT), axis=1)
+    on = np.repeat(ref["usable"], np.diff(cs))
+    assert not strict or np.all(fine[on]), "a marker is neither well conditioned nor exactly degenerate: relative pivots %s" % rp[on & ~fine]
+    cells = (fine | ~on)[None, :] & (ref["maxeta"] <= ETA_MAX)
+    if share:
+        assert cells.mean() >= share, "only %.0f %% of the cells are compared" % (100 * cells.mean())
+    return cells
+
+
+def compare_bin(got, ref, chromstarts, what="", share=0.99, strict=True, iters=True):
+    """every output of a scan against the reference at the compared cells: lod and ll0 within ATOL, coef relative to
+    max(1, |coef|) (NaN exactly where the reference has none), perm_max within ATOL; rank (at markers with a compared cell),
+    n_used, n_ones and status with ==, iters with == except where ref["near"].  Prints every figure before it asserts;
+    returns the errors."""
+    cc = compared_cells(ref, chromstarts, share, strict)
+    cm = cc.any(axis=0)
+    err_l = np.abs(got["lod"] - ref["lod"][0])[cc].max()
+    gc, rc = got["coef"][cc], ref["coef"][cc]
+    assert np.array_equal(np.isnan(gc), np.isnan(rc)), what + ": a dropped effect is NaN, a kept one a number"
+    both = ~np.isnan(rc)
+    err_c = (np.abs(gc[both] - rc[both]) / np.maximum(1.0, np.abs(rc[both]))).max() if both.any() else 0.0
+    err_0 = np.abs(got["ll0"] - ref["ll0"]).max()
+    print("%s: lod %.3g over %d of %d cells, coef %.3g, ll0 %.3g, iterations up to %d, near %d, largest |eta| %.3g" %
+          (what, err_l, cc.sum(), cc.size, err_c, err_0, ref["iters"].max(), ref["near"].sum(), ref["maxeta"].max()))
+    assert np.array_equal(got["rank"][cm], ref["rank"][cm]), what + " rank"
+    assert np.array_equal(got["n_used"], ref["n_used"]), what + " n_used"
+    assert np.array_equal(got["n_ones"], ref["n_ones"]), what + " n_ones"
+    assert err_l <= ATOL, what + " lod"
+    assert err_c <= ATOL, what + " coef"
+    assert err_0 <= ATOL, what + " ll0"
+    assert np.array_equal(got["ll0"] == 0.0, ref["ll0"] == 0.0) and np.all(got["ll0"] <= 0.0), what + " ll0 is 0 where nothing is scanned"
+    assert np.isfinite(got["lod"]).all() and np.all(got["lod"] >= 0), what + " lod is finite and not negative"
+    off = ~np.repeat(ref["usable"], np.diff(np.asarray(chromstarts, np.int64)))
+    assert np.all(got["lod"][:, off] == 0.0) and np.isnan(got["coef"][:, off]).all() and np.all(got["rank"][off] == 0)
+    zero = got["rank"] == 0
+    assert np.all(got["lod"][:, zero] == 0.0) and np.all(got["iters"][:, zero] == 0) and np.all(got["status"][:, zero] == 0)
+    assert np.array_equal(got["status"][cc], ref["status"][cc]), what + " status"
+    if iters:
+        ok = cc & ~ref["near"]
+        assert np.array_equal(got["iters"][ok], ref["iters"][ok]), what + " iters"
+    err_p = 0.0
+    if ref["perm_max"].shape[0]:
+        err_p = np.abs(got["perm_max"] - ref["perm_max"]).max()
+        print("%s: perm_max %.3g over %d cells" % (what, err_p, ref["perm_max"].size))
+        assert err_p <= ATOL, what + " perm_max"
+    else:
+        assert got.get("perm_max") is None
+    return dict(lod=err_l, coef=err_c, ll0=err_0, perm_max=err_p)
+
+
+# ------------------------------------------------------------------------------------------------ the cases of the issue
+# fixed iterations (tol = -1); the (n, K) pairs decide the lane walk of 64
+#         n    K  imprint additive seed T  P  mask   skipped max_iter
+CASES = [(41, 2, False, False, 3, 2, 0, False, False, 5),       # less than one round
+         (64, 0, False, False, 4, 1, 1, False, False, 3),       # exactly one round
+         (67, 2, True, False, 7, 1, 1, False, True, 2),         # two individuals skipped on chromosome 3
+         (130, 8, True, False, 9, 2, 5, False, False, 5),       # three rounds, the widest design
+         (41, 2, False, True, 6, 2, 0, True, False, 7)]         # additive, with a `use` mask
+
+
+def bernoulli(eta, seed):
+    """0/1 draws with P(1) = 1 / (1 + exp(-eta)), by synth.uniform"""
+    u = synth.uniform(seed * 16 + 11, np.arange(eta.size)).reshape(eta.shape)
+    return (u < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+
+
+def make_case(n, K, imprint, additive, seed, T, P, mask, skipped, max_iter=None):
+    """(origin, pheno, cov, use, perm) on the map CHROM_LENS: rows soft_rows(n, CHROM_LENS, seed), covariates
+    noise(n, K, seed + 1), 0/1 phenotypes drawn from a logistic model of the true classes plus the first covariate.  With
+    `mask` two individuals are unused and carry NaN phenotypes and covariates; with `skipped` individuals 1 and 4 are skipped
+    on chromosome 3."""
+    from cnf2freq_amd import qtl
+    origin, k = soft_rows(n, CHROM_LENS, seed)
+    M = origin.shape[1]
+    if skipped:
+        origin = skip(origin, [1, 4], 3, CHROM_LENS)
+    use = np.ones(n, bool)
+    if mask:
+        use[[0, n // 2]] = False
+    cov = noise(n, K, seed + 1) if K else None
+    a, d, im = CODES["a"][k], CODES["d"][k], CODES["i"][k]
+    at = [(7 * t + 3) % M for t in range(T)]
+    to = [(11 * t + 40) % M for t in range(T)]
+    eta = 0.2 + 0.9 * a[:, at] + 0.5 * d[:, to] - 0.6 * im[:, to]
+    if K:
+        eta = eta + 1.0 * cov[:, :1]
+        cov = np.where(use[:, None], cov, np.nan)
+    pheno = np.where(use[:, None], bernoulli(eta, seed + 2), np.nan)
+    perm = qtl.permutations(n, P, seed, use=use) if P else None
+    return origin, pheno, cov, (use if mask else None), perm
+
+
+_REFS = {}
+
+
+def case_reference(case, max_iter=None, tol=-1.0):
+    """the reference of one of CASES (at its own max_iter and fixed iterations, or as asked), computed once and shared"""
+    key = (case, max_iter, tol)
+    if key not in _REFS:
+        n, K, imprint, additive, seed, T, P, mask, skipped, mi = case
+        origin, pheno, cov, use, perm = make_case(*case)
+        _REFS[key] = reference_scan_binary(origin, chromstarts_of(CHROM_LENS), pheno, use, cov, imprint, perm, additive,
+                                           mi if max_iter is None else max_iter, tol, anchor_every=0 if tol < 0 else 7)
+    return _REFS[key]
+
+
+def assert_conditions(refs):
+    """what the comparison rests on, over the cells of `refs` together: at least 0.99 compared, at most 0.01 near"""
+    cs = chromstarts_of(CHROM_LENS)
+    cells = np.concatenate([compared_cells(r, cs, share=0, strict=True).reshape(-1) for r in refs])
+    near = np.concatenate([r["near"].reshape(-1) for r in refs])
+    print("compared %.4f of %d cells, near %.4f" % (cells.mean(), cells.size, near.mean()))
+    assert cells.mean() >= 0.99 and near.mean() <= 0.01
+
+
+def assert_anchor(ref, what=""):
+    """the converged yardstick against the longdouble Newton run that knows nothing of the stopping rule"""
+    print("%s: the yardstick's converged LOD against the longdouble anchor: %.3g" % (what, ref["anchor_err"]))
+    assert ref["anchor_err"] <= ATOL
+
+
+# the planted case of the stopping rule and of "not Haley-Knott in disguise"
+# (short: the yardstick's cells stop after 3, 4, 5 and 6 iterations, so both sides of iters > short have cells)
+PLANTED = dict(n=60, seed=5, marker=40, effect=1.5, tol=1e-7, max_iter=50, short=3)
+
+
+def planted_case():
+    """(origin, true classes, pheno, cov): soft rows of 60 individuals, one covariate, an additive effect of 1.5 (log odds) of
+    the true classes at marker 40"""
+    p = PLANTED
+    origin, k = soft_rows(p["n"], CHROM_LENS, p["seed"])
+    z = noise(p["n"], 1, 6)
+    # (an intercept of 1: about 60 % ones, away from the even split at which the linear and the logistic model nearly agree)
+    eta = 1.0 + p["effect"] * CODES["a"][k][:, p["marker"]:p["marker"] + 1] + 0.5 * z
+    return origin, k, bernoulli(eta, 9), z
+
+
+def planted_reference():
+    if "planted" not in _REFS:
+        origin, _, pheno, z = planted_case()
+        _REFS["planted"] = reference_scan_binary(origin, chromstarts_of(CHROM_LENS), pheno, None, z, max_iter=PLANTED["max_iter"],
+                                                 tol=PLANTED["tol"], anchor_every=1)
+    return _REFS["planted"]
+
+
+def planted_linear_reference():
+    """Haley-Knott regression of the same 0/1 column as numbers"""
+    if "planted_hk" not in _REFS:
+        origin, _, pheno, z = planted_case()
+        _REFS["planted_hk"] = reference_scan(origin, chromstarts_of(CHROM_LENS), pheno, None, z)
+    return _REFS["planted_hk"]
+
+
+def assert_planted(ref, hk):
+    """on the references alone: logistic and linear LODs differ by more than 0.2 somewhere and both peak at the planted marker"""
+    lb, ll = ref["lod"][0, 0], hk["lod"][0, 0]
+    print("planted: logistic peak %.2f at %d, linear peak %.2f at %d, largest difference %.2f" %
+          (lb.max(), lb.argmax(), ll.max(), ll.argmax(), np.abs(lb - ll).max()))
+    assert lb.argmax() == PLANTED["marker"] and ll.argmax() == PLANTED["marker"]
+    assert np.abs(lb - ll).max() > 0.2
+    more = (ref["iters"] > PLANTED["short"])[~ref["near"]]
+    print("planted: %d cells need more than %d iterations, %d do not" % (more.sum(), PLANTED["short"], (~more).sum()))
+    assert more.sum() >= 10 and (~more).sum() >= 10, "both stop rules must decide cells at max_iter = short"
+
+
+MONOTONE = (1, 2, 3, 5, 8)
+
+
+def monotone_reference():
+    """the planted case at exactly 8 iterations: its trace holds the LOD after every iteration"""
+    if "monotone" not in _REFS:
+        origin, _, pheno, z = planted_case()
+        _REFS["monotone"] = reference_scan_binary(origin, chromstarts_of(CHROM_LENS), pheno, None, z, max_iter=MONOTONE[-1], tol=-1.0)
+    return _REFS["monotone"]
+
+
+def separated_case(n=17, seed=4):
+    """(origin, pheno, cov) of so few individuals that several markers separate the classes: n = 17, K = 1, for imprint"""
+    origin, k = soft_rows(n, CHROM_LENS, seed)
+    z = noise(n, 1, seed + 1)
+    eta = 0.9 * CODES["a"][k][:, 3:4] + 0.5 * z
+    return origin, bernoulli(eta, seed + 2), z
