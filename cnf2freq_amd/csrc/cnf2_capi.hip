@@ -1525,6 +1525,16 @@ static void qtl_centre_columns(const double* src, int n, int w, const std::vecto
             if (use[i]) dst[(size_t)i * w + k] = src[(size_t)i * w + k] - mean;
     }
 }
+// the same with each difference rounded once (qtl_column_mean2): columns that differ by an exact shift give the same bits
+static void qtl_centre_columns_once(const double* src, int n, int w, const std::vector<uint8_t>& use, std::vector<double>& dst)
+{
+    dst.assign(src, src + (size_t)n * w);
+    for (int k = 0; k < w; k++) {
+        const QtlMean2 mean = qtl_column_mean2(src + k, n, w, use.data());
+        for (int i = 0; i < n; i++)
+            if (use[i]) dst[(size_t)i * w + k] = qtl_minus_mean2(src[(size_t)i * w + k], mean);
+    }
+}
 static void qtl_centre(QtlArgs& a, const std::vector<uint8_t>& use, QtlCentred& store)
 {
     qtl_centre_columns(a.pheno, a.n, a.T, use, store.pheno);
@@ -2065,8 +2075,10 @@ int cnf2_qtl_scan_em(cnf2_ctx* ctx, int n, const double* origin, int n_traits, c
 }
 
 // The binary-trait single-locus scan on device rows d_origin[n][M][4]: cnf2_qtlbin.h, cnf2_qtlbin_kernels.hip.  The masks, n_c
-// and the column image are the kernels of cnf2_qtl_kernels.hip.  The covariates are centred as in every scan; the 0/1 trait
-// is not.  Everything is checked and every buffer is there before the first launch writes.
+// and the column image are the kernels of cnf2_qtl_kernels.hip.  The covariates are centred, each value minus the column's mean
+// rounded once (qtl_centre_columns_once: a shifted covariate gives the same bits, which a fit of a nearly collinear marker
+// needs for the same printed effects); the 0/1 trait is not.  Everything is checked and every buffer is there before the
+// first launch writes.
 int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                          const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
                          double* coef_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out,
@@ -2093,7 +2105,7 @@ int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_trait
         }
     }
     if (a.K > 0) {
-        qtl_centre_columns(a.cov, a.n, a.K, mask, centred.cov);
+        qtl_centre_columns_once(a.cov, a.n, a.K, mask, centred.cov);
         a.cov = centred.cov.data();
     }
     const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);

@@ -61,6 +61,54 @@ CNF2_HD double qtl_column_mean(const double* v, int n, int stride, const uint8_t
     return mean - mean == 0.0 ? mean : 0.0;       // (finite values whose sum is not: left as they are)
 }
 
+// The same mean carried as an unevaluated sum hi + lo of two doubles, for the binary-trait scan (cnf2_qtl_scan_binary).  The
+// mean of n values is in general no double: rounded to one, the mean of z + 16384 is known 2^12 times less finely than that of
+// z, and the two centred columns differ by 1e-12.  A logistic fit of a nearly collinear marker multiplies that by 1e7 and
+// more, into the printed digits of its effects.  Here the sum keeps its rounding errors (two_sum), the quotient its remainder,
+// and v - (hi + lo) is rounded once: the centred value is the true one to the last bit (but for ties of 2^-106), so columns that
+// differ by an exact shift, or by a power of two, give the same centred bits.  The mean of equal values is that value.
+// s + e = a + b exactly
+CNF2_HD void qtl_two_sum(double a, double b, double& s, double& e)
+{
+    s               = a + b;
+    const double bb = s - a;
+    e               = (a - (s - bb)) + (b - bb);
+}
+struct QtlMean2 {
+    double hi, lo;
+};
+CNF2_HD QtlMean2 qtl_column_mean2(const double* v, int n, int stride, const uint8_t* use)
+{
+    QtlMean2 m = {0.0, 0.0};
+    int      n_u = 0;
+    bool     equal = true;
+    double   first = 0.0, s = 0.0, c = 0.0, e;
+    for (int i = 0; i < n; i++) {
+        if (!use[i]) continue;
+        const double x = v[(size_t)i * stride];
+        if (n_u == 0) first = x;
+        equal = equal && x == first;
+        qtl_two_sum(s, x, s, e);
+        c += e;
+        n_u++;
+    }
+    if (n_u == 0 || !(s - s == 0.0)) return m;        // (finite values whose sum is not: left as they are)
+    if (equal) {
+        m.hi = first;
+        return m;
+    }
+    qtl_two_sum(s, c, s, c);
+    const double hi = s / n_u, lo = (fma(-hi, (double)n_u, s) + c) / n_u;
+    qtl_two_sum(hi, lo, m.hi, m.lo);
+    return m;
+}
+CNF2_HD double qtl_minus_mean2(double v, const QtlMean2& m)
+{
+    double t, e;
+    qtl_two_sum(v, -m.hi, t, e);
+    return t + (e - m.lo);
+}
+
 // S = L L' in place on the lower triangle of S[nx][QTL_NX]; false when a pivot is not positive (X0 without full rank)
 CNF2_HD bool qtl_cholesky(double* S, int nx)
 {

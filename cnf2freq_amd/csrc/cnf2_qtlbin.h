@@ -270,7 +270,8 @@ CNF2_HD bool qtlbin_null_ok(const QtlbinFit& f) { return f.status == 0 && f.iter
 #if !defined(__HIP_DEVICE_COMPILE__)
 // One (marker, column) fit on the CPU, the individuals in ascending order: o[n][4] the marker's origin rows, y[n] (0 or 1 where
 // c is set), the covariates cov[n][K], c[n] the chromosome's mask.  Mirrors what the kernels do with the functions above.
-// As the scans do, it works on the covariates minus their means over the individuals of c (qtl_column_mean).
+// As the scan does, it works on the covariates minus their means over the individuals of c, each difference rounded once
+// (qtl_column_mean2, qtl_minus_mean2 of cnf2_qtl.h).
 // Returns false for bad arguments.  Outputs: lod, coef[ne] (NaN where dropped or not fitted), iters, status, rank, ll0 (0 for
 // a column that is not scanned), n_ones, n_c.
 inline bool qtlbin_fit_serial(int n, const double* o, const double* y, int K, const double* cov_raw, const uint8_t* c, bool additive,
@@ -288,9 +289,9 @@ inline bool qtlbin_fit_serial(int n, const double* o, const double* y, int K, co
     }
     std::vector<double> cov(cov_raw, cov_raw + (K > 0 ? (size_t)n * K : 0));
     for (int k = 0; k < K; k++) {
-        const double mean = qtl_column_mean(cov.data() + k, n, K, c);
+        const QtlMean2 mean = qtl_column_mean2(cov.data() + k, n, K, c);
         for (int i = 0; i < n; i++)
-            if (c[i]) cov[(size_t)i * K + k] -= mean;
+            if (c[i]) cov[(size_t)i * K + k] = qtl_minus_mean2(cov[(size_t)i * K + k], mean);
     }
     const QtlemDesign ds = qtlem_design(K, additive, imprint);
     const int         nx = ds.nx;

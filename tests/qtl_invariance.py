@@ -6,10 +6,12 @@ With an intercept in X0 the model of include/cnf2hip.h does not depend on the un
 (y -> alpha y + beta) nor on those of a covariate that is not interactive (z_k -> gamma_k z_k + delta_k): LOD, rank, n_used,
 iterations, status and perm_max stay, the effects scale with alpha (an interaction with z_k with alpha / gamma_k), rss0 and
 sigma2 with alpha^2.  The float64 yardsticks are themselves off by 1e-10 .. 1e-9 on a trait shifted by 2^17, so the reference
-of a transformed problem is the yardstick on the base problem, carried over by map_reference."""
+of a transformed problem is the yardstick on the base problem, carried over by map_reference.  The binary-trait scan has a
+section of its own at the end: covariate transforms, the complement of the trait, the same relabellings, map_bin_reference."""
 import numpy as np
 
 import qtl2_reference as R2
+import qtlbin_reference as RB
 import qtlem_reference as RE
 import qtlx_reference as RX
 from cnf2freq_amd import qtl
@@ -248,12 +250,12 @@ FLOAT_KEYS = ("lod", "lod_add", "lod_full", "coef", "sigma2", "rss0", "perm_max"
 INT_KEYS = ("rank", "rank_add", "rank_full", "n_used", "iters", "status")
 
 
-def errors(got, ref):
+def errors(got, ref, float_keys=FLOAT_KEYS, int_keys=INT_KEYS):
     """Figures for the log, nothing asserted: per float output the largest |got - ref| / max(1, |ref|) over the cells where both
     are numbers (ref: a yardstick's dict, its LODs with the observed block first, or outputs of the product), and per
     integer output the number of cells that differ (iters: outside ref["near"])."""
     out = {}
-    for key in FLOAT_KEYS:
+    for key in float_keys:
         g, r = got.get(key), ref.get(key)
         if g is None or r is None or np.size(r) == 0:
             continue
@@ -261,7 +263,7 @@ def errors(got, ref):
         with np.errstate(invalid="ignore"):
             e = np.abs(g - r) / np.maximum(1.0, np.abs(r))
         out[key] = float(np.nanmax(e)) if np.isfinite(e).any() else 0.0
-    for key in INT_KEYS:
+    for key in int_keys:
         if key in got and key in ref:
             differ = got[key] != ref[key]
             if key == "iters" and "near" in ref:
@@ -274,6 +276,123 @@ def errors_line(tag, err):
     return tag + "  " + "  ".join("%s %.3g" % (k, v) if isinstance(v, float) else "%s_differ %d" % (k, v) for k, v in err.items())
 
 
-def bit_equal(a, b):
+def bit_equal(a, b, keys=FLOAT_KEYS + INT_KEYS):
     """every output of two runs of the product the same bits"""
-    return all((a[k] is None and b[k] is None) or same_bits(a[k], b[k]) for k in FLOAT_KEYS + INT_KEYS if k in a)
+    return all((a[k] is None and b[k] is None) or same_bits(a[k], b[k]) for k in keys if k in a)
+
+
+# ------------------------------------------------------------------------------------------------ the binary-trait scan
+# A 0/1 trait has no units: only the covariates are transformed (alpha = 1, beta = 0).  With an intercept in X0 the logistic
+# model does not depend on z_k -> gamma_k z_k + delta_k at all (no output changes); under the complement y -> 1 - y of the
+# used individuals theta changes sign, so lod, ll0, rank, n_used, iters, status and perm_max stay, every effect changes sign
+# and n_ones -> n_used - n_ones; the relabellings change the sign of a (swap03) or of i (swap12) and nothing else.
+BIN_TRANSFORMS = dict(C=transform(delta=2.0 ** 14),
+                      D=transform(gamma=2.0 ** 3, delta=2.0 ** 14),
+                      E=transform(gamma=2.0 ** -20, delta=2.0 ** -3),
+                      F=transform(gamma=2.0 ** 100),
+                      G=transform(gamma=2.0 ** -100),
+                      H=transform(delta=(2.0 ** 12, 2.0 ** 6)))
+BIN_SMALL_SHIFT = transform(delta=2.0 ** 4)      # a shift at which the float64 yardstick itself is still accurate
+
+BIN_SCANS = {"bin-fixed": dict(imprint=True, tol=-1.0, max_iter=4),
+             "bin-stop": dict(imprint=False, tol=1e-7, max_iter=50)}      # (both with the permutations)
+
+# The strength of the planted effects (log odds per unit of a, d, i and of the first covariate), chosen on the yardstick alone
+# so that each base reference passes the conditions of tests/qtlbin_reference.py (strict, compared >= 0.99, near <= 0.01).
+# Tried, with the shares of compared cells of (n41 bin-fixed, n41 bin-stop, n67 bin-fixed, n67 bin-stop) and the largest share
+# of near cells (41 individuals with two covariates and three effects come close to separation at a marker or two, which
+# takes |eta| past ETA_MAX there):
+#   (a, d, i, z) = (0.9, 0.5, -0.6, 1.0), tests/qtlbin_reference.make_case's:
+#       draw seed + 2: 0.994, 1, 1, 1, near 0.006   seed + 3: 0.994, 1, 1, 1, near 0   seed + 4: 1, 1, 1, 1, near 0.006 (taken)
+#   (0.6, 0.3, -0.4, 0.6):  seed + 2: 1, 1, 1, 1, near 0.006   seed + 3: 0.994, 0.994, 1, 1   seed + 4: 1, 1, 1, 1, near 0
+#   (0.4, 0.2, -0.3, 0.4):  seed + 2: 1, 1, 1, 1   seed + 3: 0.988 (fails), 0.994, 1, 1   seed + 4: 1, 1, 1, 1
+# Every reference was strict.  The taken one leaves the largest |eta| at 7.8 and the iterations of bin-stop at 2 .. 6.
+BIN_EFFECT = dict(intercept=0.2, a=0.9, d=0.5, i=-0.6, z=1.0)
+BIN_SEED = {"n41-mask": 4, "n67-skip": 4}        # added to the case's seed for the Bernoulli draws
+
+BIN_FLOAT_KEYS = ("lod", "coef", "ll0", "perm_max")
+BIN_INT_KEYS = ("rank", "n_used", "n_ones", "iters", "status")
+
+_BIN_BASE = {}
+
+
+def make_bin_base(case):
+    """make_base(case) with 0/1 traits in place of the continuous ones: T columns drawn by RB.bernoulli from a logistic model of
+    the true classes (a at one marker, d and i at another) plus the first covariate; NaN at the unused individuals.  Origin
+    rows, covariates (on the grid), mask and permutations are make_base's own.  Computed once and shared."""
+    if case not in _BIN_BASE:
+        name, n, seed, mask, skipped = case
+        base = make_base(case)
+        _, k = soft_rows(n, CHROM_LENS, seed)
+        M = k.shape[1]
+        a, d, im = RE.CODES["a"][k], RE.CODES["d"][k], RE.CODES["i"][k]
+        at = [(7 * t + 3) % M for t in range(T)]
+        to = [(11 * t + 40) % M for t in range(T)]
+        e = BIN_EFFECT
+        eta = e["intercept"] + e["a"] * a[:, at] + e["d"] * d[:, to] + e["i"] * im[:, to] + e["z"] * np.nan_to_num(base["cov"][:, :1])
+        used = np.ones(n, bool) if base["use"] is None else base["use"]
+        pheno = np.where(used[:, None], RB.bernoulli(eta, seed + BIN_SEED[name]), np.nan)
+        _BIN_BASE[case] = dict(base, pheno=pheno)
+    return _BIN_BASE[case]
+
+
+def complement(base):
+    """the inputs with y -> 1 - y (NaN stays at the unused individuals)"""
+    return dict(base, pheno=1.0 - base["pheno"])
+
+
+def bin_coef_names(scan):
+    return RB.effects(False, BIN_SCANS[scan]["imprint"])
+
+
+def bin_reference(scan, inp):
+    """the binary scan's float64 yardstick on the inputs `inp`"""
+    s = BIN_SCANS[scan]
+    return RB.reference_scan_binary(inp["origin"], CS, inp["pheno"], inp["use"], inp["cov"], s["imprint"], inp["perm"], False,
+                                    s["max_iter"], s["tol"])
+
+
+def bin_run(ctx, scan, inp):
+    """Context.qtl_scan_binary on the inputs `inp`"""
+    s = BIN_SCANS[scan]
+    return ctx.qtl_scan_binary(inp["origin"], inp["pheno"], cov=inp["cov"], use=inp["use"], perm=inp["perm"], imprint=s["imprint"],
+                               max_iter=s["max_iter"], tol=s["tol"])
+
+
+_BIN_REFS = {}
+
+
+def bin_base_reference(case, scan):
+    """the yardstick of a binary scan on a base case, computed once and shared"""
+    if (case, scan) not in _BIN_REFS:
+        _BIN_REFS[case, scan] = bin_reference(scan, make_bin_base(case))
+    return _BIN_REFS[case, scan]
+
+
+def assert_bin_conditions(case, scan):
+    """on the base reference alone: strict pivots, at least 0.99 of the cells compared, at most 0.01 near"""
+    RB.assert_conditions([bin_base_reference(case, scan)])
+
+
+def map_bin_reference(ref, names=(), flip=(), complemented=False):
+    """The expected outputs of a changed problem from a base reference of the binary scan: under a covariate transform nothing
+    changes; an effect in `flip` changes sign; under the complement every effect does and n_ones becomes n_used - n_ones.
+    lod, ll0, rank, n_used, iters, status, perm_max, near, maxeta and relpivot stay."""
+    out = dict(ref)
+    f = np.ones(len(names))
+    for j, name in enumerate(names):
+        if name in flip:
+            f[j] = -f[j]
+    if complemented:
+        f = -f
+        out["n_ones"] = ref["n_used"][None, :] - ref["n_ones"]
+    out["coef"] = ref["coef"] * f
+    return out
+
+
+def bin_errors(got, ref):
+    return errors(got, ref, BIN_FLOAT_KEYS, BIN_INT_KEYS)
+
+
+def bin_bit_equal(a, b):
+    return bit_equal(a, b, BIN_FLOAT_KEYS + BIN_INT_KEYS)

@@ -242,6 +242,25 @@ CASES = [(41, 2, False, False, 3, 2, 0, False, False, 5),       # less than one 
          (130, 8, True, False, 9, 2, 5, False, False, 5),       # three rounds, the widest design
          (41, 2, False, True, 6, 2, 0, True, False, 7)]         # additive, with a `use` mask
 
+# The widths of X0 that CASES leaves out (K = 3 .. 7; the fit kernel is compiled once per K + 1) and the design with the effects
+# (a, i), the only one whose place 1 is i and not d.  Checked on the yardstick alone, at max_iter = 3, tol = -1 and at
+# max_iter = 50, tol = 1e-7: every cell is compared, the largest |eta| is 6.8, every status is 0 at tol 1e-7 after 2 to 6
+# iterations, and `near` is 0 but for 0.012 of the first case's cells at tol 1e-7 (0.0017 of the seven together).
+#                n    K  imprint additive seed T  P  mask   skipped max_iter
+WIDTH_CASES = [(63, 3, True, True, 21, 1, 1, False, False, 3),       # one short of a round; (a, i)
+               (65, 4, False, False, 22, 1, 1, False, False, 3),     # one past a round
+               (96, 5, True, False, 23, 1, 1, False, True, 3),       # 1.5 rounds, skipped individuals
+               (127, 6, False, True, 24, 1, 1, True, False, 3),      # K + 1 = 7, with a `use` mask
+               (129, 7, True, True, 25, 1, 1, False, False, 3),      # one past two rounds; (a, i)
+               (41, 1, True, True, 26, 2, 0, False, False, 3),       # (a, i), two traits, no permutations
+               (64, 0, True, True, 27, 1, 1, False, False, 3)]       # (a, i) without covariates
+WIDTH_STOP = dict(max_iter=50, tol=1e-7)     # the stopping rule the width cases also run under
+
+
+def case_id(c):
+    return "n%d-K%d-%s%s-T%d-P%d-it%d%s" % (c[0], c[1], "i" if c[2] else "m", "-add" if c[3] else "", c[5], c[6], c[9],
+                                            "-mask" if c[7] else "-skip" if c[8] else "")
+
 
 def bernoulli(eta, seed):
     """0/1 draws with P(1) = 1 / (1 + exp(-eta)), by synth.uniform"""
@@ -365,3 +384,72 @@ def separated_case(n=17, seed=4):
     z = noise(n, 1, seed + 1)
     eta = 0.9 * CODES["a"][k][:, 3:4] + 0.5 * z
     return origin, bernoulli(eta, seed + 2), z
+
+
+# ------------------------------------------------------------------------------------------------ two edges of the lane walk
+EMPTY_ROUND = dict(n=130, seed=32, max_iter=50, tol=1e-7, share=0.9)
+
+
+def empty_round_case():
+    """(origin, pheno, cov, use) of 130 individuals of whom 64 .. 127 are not used: every lane's second step of the walk of 64
+    is masked, and the third round holds individuals 128 and 129.  K = 1, effects a and d.  Of the seeds 31 .. 35 tried on the
+    yardstick alone every one leaves all cells compared (66 individuals, largest |eta| 2.4 .. 4.9); 31 has one near cell, 32
+    is taken."""
+    p = EMPTY_ROUND
+    origin, k = soft_rows(p["n"], CHROM_LENS, p["seed"])
+    use = np.ones(p["n"], bool)
+    use[64:128] = False
+    z = noise(p["n"], 1, p["seed"] + 1)
+    eta = 0.2 + 0.9 * CODES["a"][k][:, [3]] + 0.5 * CODES["d"][k][:, [40]] + 1.0 * z
+    return origin, bernoulli(eta, p["seed"] + 2), z, use
+
+
+def empty_round_reference():
+    if "empty_round" not in _REFS:
+        origin, pheno, z, use = empty_round_case()
+        _REFS["empty_round"] = reference_scan_binary(origin, chromstarts_of(CHROM_LENS), pheno, use, z, max_iter=EMPTY_ROUND["max_iter"],
+                                                     tol=EMPTY_ROUND["tol"], anchor_every=7)
+    return _REFS["empty_round"]
+
+
+THRESHOLD = dict(n=24, K=3, seed=10, chrom=4, W=6)     # W = 1 + K + 2 for the effects (a, i)
+
+
+def threshold_case(n_c):
+    """(origin, pheno, cov) of 24 individuals with three covariates of whom only the first n_c are there on chromosome 4 (the
+    others are skipped on it); the first seven phenotypes hold both classes.  For the design (a, i), W = 6: n_c = 7 is
+    scanned there, n_c = 6 is not.  (Seven individuals on six columns separate: on the yardstick the null fit of this draw
+    converges, l0 = -3.3, and every marker's fit reaches the bound -l0 / ln 10.)"""
+    p = THRESHOLD
+    cs = chromstarts_of(CHROM_LENS)
+    origin, _ = soft_rows(p["n"], CHROM_LENS, p["seed"])
+    origin[n_c:, cs[p["chrom"]]:cs[p["chrom"] + 1]] = 0.0
+    y = bernoulli(np.zeros((p["n"], 1)), p["seed"] + 3)
+    y[:7, 0] = [0, 1, 0, 1, 1, 0, 1]
+    return origin, y, noise(p["n"], p["K"], p["seed"] + 4)
+
+
+def assert_threshold(got, n_c, ne=2):
+    """what a scan of threshold_case(n_c) must show, with no comparison of values: the chromosome is scanned exactly when
+    n_c >= W + 1; every LOD finite, not negative and at most -l0 / ln 10 + ATOL; status 0, 1 or 2; NaN exactly at the effects
+    that are dropped, or everywhere where the column is not scanned"""
+    p = THRESHOLD
+    cs = chromstarts_of(CHROM_LENS)
+    c = p["chrom"]
+    on = slice(cs[c], cs[c + 1])
+    assert got["n_used"][c] == n_c and np.all(np.delete(got["n_used"], c) == p["n"])
+    assert got["n_ones"][0, c] == (4 if n_c == 7 else 3)
+    bound = np.repeat(-got["ll0"] / LN10 + ATOL, np.diff(cs), axis=1)
+    assert np.isfinite(got["lod"]).all() and np.all(got["lod"] >= 0) and np.all(got["lod"] <= bound)
+    assert np.isin(got["status"], (0, 1, 2)).all()
+    off = np.delete(np.arange(len(cs) - 1), c)
+    assert np.all(got["ll0"][0, off] < 0) and np.all(np.delete(got["rank"], np.arange(cs[c], cs[c + 1])) > 0)
+    if n_c >= p["W"] + 1:
+        assert np.all(got["rank"][on] > 0)
+    else:
+        assert np.all(got["rank"][on] == 0) and got["ll0"][0, c] == 0.0
+        assert np.all(got["lod"][:, on] == 0.0) and np.all(got["iters"][:, on] == 0) and np.all(got["status"][:, on] == 0)
+    scanned = np.repeat(got["ll0"] < 0, np.diff(cs), axis=1)           # [T][M]
+    missing = np.isnan(got["coef"]).sum(axis=2)
+    assert np.all(missing[scanned] == (ne - np.broadcast_to(got["rank"], scanned.shape))[scanned])
+    assert np.all(missing[~scanned] == ne)

@@ -3,7 +3,26 @@ qtl.scan_binary, cnF2freq --qtlbin).  Logistic regression of every marker and 0/
 against the explicit-design IRLS in numpy (tests/qtlbin_reference.py): a fixed number of iterations on hand-made rows at the
 shapes where the lane walk of 64 can go wrong, the stopping rule, a planted locus where the model must differ from the linear
 scan of the same 0/1 column, the monotone likelihood, certain rows with the closed-form null, degenerate, separated and extreme
-inputs, bit-equality, permutations, refusals, a swept cross and the command line."""
+inputs, bit-equality, permutations, refusals, a swept cross and the command line.
+
+The fit kernel is compiled once per width of X0 (qtlbin_fit_kernel<K + 1>) and the design decides the stride and the order of
+coef.  Which test compares which instance and design with the yardstick's values:
+
+    instance  K  case                                               design
+    <1>       0  CASES[1] n 64;  WIDTH_CASES[6] n 64                (a, d); (a, i)
+    <2>       1  planted, monotone, empty round (n 130, 66 used);   (a, d)
+                 WIDTH_CASES[5] n 41, T 2                           (a, i)
+    <3>       2  CASES[0] n 41; CASES[2] n 67 skipped; CASES[4]     (a, d); (a, d, i); (a)
+    <4>       3  WIDTH_CASES[0] n 63                                (a, i)
+    <5>       4  WIDTH_CASES[1] n 65                                (a, d)
+    <6>       5  WIDTH_CASES[2] n 96, skipped                       (a, d, i)
+    <7>       6  WIDTH_CASES[3] n 127, mask                         (a)
+    <8>       7  WIDTH_CASES[4] n 129                               (a, i)
+    <9>       8  CASES[3] n 130, T 2, P 5                           (a, d, i)
+
+CASES run in test_fixed_iterations, WIDTH_CASES in test_every_width_and_design (fixed iterations and the stopping rule); the
+column tiles across the observed/permuted boundary, the design (a, i) with i dropped, a round of the lane walk with nobody in
+it and the threshold n_c = W + 1 of the design (a, i) have tests of their own at the end."""
 import numpy as np
 import pytest
 
@@ -413,3 +432,138 @@ def test_cli_qtlbin(capi, tmp_path):
             worst = max(worst, abs(float(x[2 + a]) - thr["genome"][a, t]))
     print("file against qtl.scan_binary: %.3g; largest LOD %.2f" % (worst, want["lod"].max()))
     assert worst <= 0.51e-5 and want["lod"].max() > 0.5
+
+
+# ------------------------------------------------------------------------------------- 9. every width of X0, every design
+def width_reference(case, stop):
+    return R.case_reference(case, **(R.WIDTH_STOP if stop else {}))
+
+
+def assert_i_dropped_as_plain(got, plain):
+    """wherever the (a, i) run reports rank 1 with i dropped, lod and the effect a have the bits of the run without imprinting;
+    returns the number of such markers"""
+    dropped = (got["rank"] == 1) & np.isnan(got["coef"][:, :, 1]).all(axis=0) & np.isfinite(got["coef"][:, :, 0]).any(axis=0)
+    assert plain["coef"].shape[2] == 1
+    assert got["lod"][:, dropped].tobytes() == plain["lod"][:, dropped].tobytes()
+    assert got["coef"][:, dropped, 0].tobytes() == plain["coef"][:, dropped, 0].tobytes()
+    assert got["iters"][:, dropped].tobytes() == plain["iters"][:, dropped].tobytes()
+    return int(dropped.sum())
+
+
+@pytest.mark.parametrize("stop", (False, True), ids=("fixed", "stop"))
+@pytest.mark.parametrize("case", R.WIDTH_CASES, ids=R.case_id)
+def test_every_width_and_design(capi, case, stop):
+    """K = 3 .. 7 and the design (a, i), after exactly max_iter iterations and under the stopping rule (tol 1e-7): every output
+    against the yardstick at all 84 markers, rank and n_used as cnf2_qtl_scanx's, the same bits on a second call.  No marker of
+    these draws drops i (every rank of the (a, i) cases is 2, asserted on the reference), so the run without imprinting is
+    compared at no marker here: test_additive_imprint_drops_i does that on the degenerate rows."""
+    n, K, imprint, additive, seed, T, P, mask, skipped, max_iter = case
+    origin, pheno, cov, use, perm = R.make_case(*case)
+    ref = width_reference(case, stop)
+    # on the references alone, before anything runs: over the seven cases together at least 0.99 of the cells are compared
+    # and at most 0.01 are near; this case's own cells are all compared
+    R.assert_conditions([width_reference(c, stop) for c in R.WIDTH_CASES])
+    assert R.compared_cells(ref, CS, share=1.0).all()
+    if stop:
+        R.assert_anchor(ref, R.case_id(case))
+        assert np.all(ref["status"] == 0)
+    ai = imprint and additive
+    if ai:
+        assert np.all(ref["rank"] == 2)
+    ctx, _ = map_context(capi)
+    kw = dict(cov=cov, imprint=imprint, use=use, perm=perm, additive=additive)
+    kw.update(R.WIDTH_STOP if stop else dict(max_iter=max_iter, tol=-1.0))
+    got = ctx.qtl_scan_binary(origin, pheno, **kw)
+    assert got["coef"].shape == (T, CS[-1], len(R.effects(additive, imprint)))
+    R.compare_bin(got, ref, CS, "%s %s" % (R.case_id(case), "to tol 1e-7" if stop else "fixed"), share=1.0)
+    if not stop:
+        fitted = got["rank"] > 0
+        assert np.all(got["iters"][:, fitted] == max_iter) and np.all(got["status"][:, fitted] == 1)
+    x = ctx.qtl_scanx(origin, np.nan_to_num(pheno), cov=cov, imprint=imprint, use=use, additive=additive)
+    assert np.array_equal(got["rank"], x["rank"][:, 1 if imprint else 0]) and np.array_equal(got["n_used"], x["n_used"])
+    if skipped:
+        assert got["n_used"][3] == n - 2 and got["n_used"][0] == n
+    if mask:
+        assert np.all(got["n_used"] == n - 2)
+    same_bits(got, ctx.qtl_scan_binary(origin, pheno, **kw))
+    if ai:
+        assert assert_i_dropped_as_plain(got, ctx.qtl_scan_binary(origin, pheno, **dict(kw, imprint=False))) == 0
+    ctx.close()
+
+
+def test_additive_imprint_drops_i(capi):
+    """The design (a, i) on the degenerate rows, with a covariate: at the homozygous and the symmetric marker i vanishes, the
+    rank is 1 with i dropped (coef[..., 1] NaN), and lod and a have the bits of the additive run without imprinting; where
+    both effects are kept, coef place 1 is i: the yardstick's."""
+    origin, at = R.degenerate_rows()
+    n = origin.shape[0]
+    y = R.bernoulli(np.zeros((n, 1)), 11)
+    z = noise(n, 1, 12)
+    ref = R.reference_scan_binary(origin, CS, y, None, z, imprint=True, additive=True)
+    for m in (at["homozygous"], at["symmetric"]):         # on the reference alone
+        assert ref["rank"][m] == 1 and np.isfinite(ref["coef"][0, m, 0]) and np.isnan(ref["coef"][0, m, 1])
+    assert ref["rank"][at["flat"]] == 0 and ref["rank"][at["zeros"]] == 2
+    ctx, _ = map_context(capi)
+    got = ctx.qtl_scan_binary(origin, y, cov=z, imprint=True, additive=True)
+    plain = ctx.qtl_scan_binary(origin, y, cov=z, additive=True)
+    ctx.close()
+    # (24 individuals separate at some markers; those cells lie outside ETA_MAX, so no share of compared cells is asked for)
+    R.compare_bin(got, ref, CS, "degenerate rows, (a, i)", share=0)
+    for m in (at["homozygous"], at["symmetric"]):
+        assert got["rank"][m] == 1 and np.isfinite(got["coef"][0, m, 0]) and np.isnan(got["coef"][0, m, 1]) and got["lod"][0, m] > 0.0
+    assert assert_i_dropped_as_plain(got, plain) >= 2
+    m = at["flat"]
+    assert got["rank"][m] == 0 and got["lod"][0, m] == 0.0 and np.isnan(got["coef"][0, m]).all()
+
+
+# ------------------------------------------------------------------------------------- 10. column tiles across T
+def test_column_tiles_across_the_permuted_boundary(capi):
+    """T = 2, P = 5: 12 columns, the first two observed.  Caps of 3 and 5 put observed and permuted columns into one launch
+    (columns 0 .. 2, resp. 0 .. 4), a cap of 12 all of them; the bits are those of the default tiling, and of the yardstick."""
+    case = R.CASES[3]
+    n, K, imprint, additive, seed, T, P, mask, skipped, max_iter = case
+    assert (T, P) == (2, 5)
+    origin, pheno, cov, use, perm = R.make_case(*case)
+    ref = R.case_reference(case)
+    R.compared_cells(ref, CS)
+    ctx, _ = map_context(capi)
+    kw = dict(cov=cov, imprint=imprint, use=use, perm=perm, additive=additive, max_iter=max_iter, tol=-1.0)
+    got = ctx.qtl_scan_binary(origin, pheno, **kw)
+    R.compare_bin(got, ref, CS, "12 columns, default tiling")
+    for cap in (3, 5, 12):
+        ctx.set_qtlbin_columns(cap)
+        same_bits(got, ctx.qtl_scan_binary(origin, pheno, **kw))
+    ctx.set_qtlbin_columns(0)
+    same_bits(got, ctx.qtl_scan_binary(origin, pheno, **kw))
+    ctx.close()
+
+
+# ------------------------------------------------------------------------------------- 11. two edges of the lane walk
+def test_a_round_with_nobody_in_it(capi):
+    """n = 130 with individuals 64 .. 127 unused: every lane's second step is masked, the third round holds two individuals"""
+    p = R.EMPTY_ROUND
+    origin, pheno, z, use = R.empty_round_case()
+    ref = R.empty_round_reference()
+    R.assert_anchor(ref, "empty round")                    # on the yardstick alone, before anything of the product runs
+    cc = R.compared_cells(ref, CS, share=p["share"])
+    print("empty round: %.3f of the cells compared, %d near" % (cc.mean(), ref["near"].sum()))
+    assert ref["near"].mean() <= 0.01 and np.all(ref["n_used"] == 66)
+    ctx, _ = map_context(capi)
+    got = ctx.qtl_scan_binary(origin, pheno, cov=z, use=use, max_iter=p["max_iter"], tol=p["tol"])
+    R.compare_bin(got, ref, CS, "n 130, 64 .. 127 unused", share=p["share"])
+    assert np.all(got["n_used"] == 66)
+    same_bits(got, ctx.qtl_scan_binary(origin, pheno, cov=z, use=use, max_iter=p["max_iter"], tol=p["tol"]))
+    ctx.close()
+
+
+@pytest.mark.parametrize("n_c", (7, 6))
+def test_scan_threshold_of_the_additive_imprint_design(capi, n_c):
+    """(a, i) with K = 3, W = 6: a chromosome with 7 individuals is scanned, one with 6 is not.  Seven individuals on six
+    columns separate, so no values are compared: what test_separated asserts"""
+    origin, y, z = R.threshold_case(n_c)
+    ctx, _ = map_context(capi)
+    got = ctx.qtl_scan_binary(origin, y, cov=z, imprint=True, additive=True, max_iter=50, tol=1e-7)
+    x = ctx.qtl_scanx(origin, y, cov=z, imprint=True, additive=True)
+    ctx.close()
+    R.assert_threshold(got, n_c)
+    assert np.array_equal(got["rank"], x["rank"][:, 1]) and np.array_equal(got["n_used"], x["n_used"])

@@ -3,11 +3,16 @@ the maps that carry a base reference over to a transformed problem are proved on
 accurate (a small shift, pure scalings); the yardsticks' own error on the large shifts is printed, which is why the mapped
 base reference is the reference; and the host library's pieces -- one fit of the maximum-likelihood scan
 (cnf2h_qtlem_fit, the header the device compiles) and the residuals `cnF2freq --qtl*` permutes (cnf2h_qtl_null_residuals),
-with qtl.null_residuals beside them -- are held to ATOL under every transform."""
+with qtl.null_residuals beside them -- are held to ATOL under every transform.
+
+The binary-trait scan: its maps (covariate transforms change nothing; the complement and the relabellings change signs and
+n_ones) are proved on the yardstick where that is accurate, the yardstick's own error under the large covariate transforms is
+printed, and every cell through cnf2h_qtlbin_fit is held to the mapped base reference by qtlbin_reference.compare_bin."""
 import numpy as np
 import pytest
 
 import qtl_invariance as V
+import qtlbin_reference as RB
 import qtlem_reference as RE
 from cnf2freq_amd import host, qtl
 from qtl_reference import ATOL, reference_scan
@@ -184,3 +189,154 @@ def test_null_residuals(case, name):
         assert np.all(res[~use] == 0.0)
         assert err <= ATOL, what
         assert thresholds_text(case, res) == want_text, what
+
+
+# ------------------------------------------------------------------------------------------------ the binary-trait scan
+BIN_TRANSFORM_IDS = sorted(V.BIN_TRANSFORMS)
+BIN_SCAN_IDS = list(V.BIN_SCANS)
+
+
+def bin_host_run(scan, inp):
+    """cnf2h_qtlbin_fit at every (marker, column) of the inputs `inp`, in the form of Context.qtl_scan_binary's outputs"""
+    from test_qtlbin_host import host_scan
+    s = V.BIN_SCANS[scan]
+    return host_scan(inp["origin"], inp["pheno"], inp["use"], inp["cov"], inp["perm"], s["imprint"], False, s["max_iter"], s["tol"])
+
+
+def bin_changed(base, change):
+    """(inputs, what map_bin_reference needs) of the complement or one of the relabellings"""
+    if change == "complement":
+        return V.complement(base), dict(complemented=True)
+    inp, flip = V.relabel(base, change)
+    return inp, dict(flip=flip)
+
+
+BIN_CHANGES = ("complement",) + V.RELABELLINGS
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+def test_bin_transforms_are_exact(case):
+    base = V.make_bin_base(case)
+    used = np.ones(case[1], bool) if base["use"] is None else base["use"]
+    y = base["pheno"]
+    assert np.all(np.isin(y[used], (0.0, 1.0))) and np.isnan(y[~used]).all() and V.same_bits(base["cov"], V.make_base(case)["cov"])
+    for t in range(V.T):                         # both classes, so that the complement is a scan too
+        assert 5 <= y[used, t].sum() <= used.sum() - 5
+    for name in BIN_TRANSFORM_IDS + ["small"]:
+        tr = V.BIN_SMALL_SHIFT if name == "small" else V.BIN_TRANSFORMS[name]
+        assert np.all(tr["alpha"] == 1.0) and np.all(tr["beta"] == 0.0)
+        t = V.apply(base, tr)                    # (asserts that the inverse returns the base bits)
+        assert V.same_bits(t["pheno"], y) and not V.same_bits(t["cov"], base["cov"])
+    c = V.complement(base)
+    assert V.same_bits(1.0 - c["pheno"], y) and np.all(c["pheno"][used] + y[used] == 1.0)
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", BIN_SCAN_IDS)
+def test_bin_mapping_on_the_yardstick(scan, case):
+    """The yardstick on a small covariate shift (2^4), on the complement and on the four relabellings agrees with the mapped
+    base reference by RB.compare_bin at ATOL.  This proves map_bin_reference; no product code runs."""
+    V.assert_bin_conditions(case, scan)
+    base, ref, names = V.make_bin_base(case), V.bin_base_reference(case, scan), V.bin_coef_names(scan)
+    problems = [("shift 2^4", V.apply(base, V.BIN_SMALL_SHIFT), {})] + [(c,) + bin_changed(base, c) for c in BIN_CHANGES]
+    for name, inp, how in problems:
+        yard = V.as_got(scan, V.bin_reference(scan, inp))
+        want = V.map_bin_reference(ref, names=names, **how)
+        what = "yardstick %s %s %s" % (scan, case[0], name)
+        print(V.errors_line(what, V.bin_errors(yard, want)))
+        RB.compare_bin(yard, want, V.CS, what)
+        if name == "complement":                 # the map is not the identity
+            assert np.array_equal(yard["n_ones"] + ref["n_ones"], np.broadcast_to(ref["n_used"], ref["n_ones"].shape))
+            assert np.nanmax(np.abs(yard["coef"] + ref["coef"])) <= ATOL and np.nanmax(np.abs(ref["coef"])) > 0.1
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", BIN_SCAN_IDS)
+def test_bin_yardstick_error_on_covariate_transforms(scan, case):
+    """Printed, not asserted: how far the float64 yardstick itself is from the mapped base reference under the covariate
+    transforms.  It works on the covariates as given, so X'WX loses digits to a mean of 2^14 (effects off by up to 1e-7 of
+    their size, by 6e-6 where a spread of 2^-20 sits on a mean of 2^-3) and its rank rule no longer scans anything at
+    gamma = 2^+-100.  The yardstick is no reference there: the mapped base reference is."""
+    base, ref, names = V.make_bin_base(case), V.bin_base_reference(case, scan), V.bin_coef_names(scan)
+    for name in BIN_TRANSFORM_IDS:
+        yard = V.as_got(scan, V.bin_reference(scan, V.apply(base, V.BIN_TRANSFORMS[name])))
+        err = V.bin_errors(yard, V.map_bin_reference(ref, names=names))
+        print(V.errors_line("yardstick's own error %s %s transform %s" % (scan, case[0], name), err))
+        assert all(np.isfinite(v) for v in err.values())
+
+
+_BIN_HOST_BASE = {}
+
+
+def bin_host_base(case, scan):
+    if (case, scan) not in _BIN_HOST_BASE:
+        _BIN_HOST_BASE[case, scan] = bin_host_run(scan, V.make_bin_base(case))
+    return _BIN_HOST_BASE[case, scan]
+
+
+def bin_host_check(scan, case, name, inp, how):
+    """cnf2h_qtlbin_fit on the inputs `inp` against the mapped base reference: RB.compare_bin, unchanged"""
+    V.assert_bin_conditions(case, scan)          # on the reference alone, before the product runs
+    ref, names = V.bin_base_reference(case, scan), V.bin_coef_names(scan)
+    want = V.map_bin_reference(ref, names=names, **how)
+    got = bin_host_run(scan, inp)
+    what = "host %s %s %s" % (scan, case[0], name)
+    print(V.errors_line("INVARIANCE " + what + " | against the mapped base reference:", V.bin_errors(got, want)))
+    back = V.map_bin_reference(got, names=names, **how)          # (each of the maps is its own inverse)
+    print(V.errors_line("INVARIANCE " + what + " | against the base run:", V.bin_errors(back, bin_host_base(case, scan))))
+    RB.compare_bin(got, want, V.CS, what)
+    s = V.BIN_SCANS[scan]
+    if s["tol"] < 0:
+        fitted = got["rank"] > 0
+        assert np.all(got["iters"][:, fitted] == s["max_iter"]) and np.all(got["status"][:, fitted] == 1)
+    return got
+
+
+@pytest.mark.parametrize("name", BIN_TRANSFORM_IDS)
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", BIN_SCAN_IDS)
+def test_bin_host_transform(scan, case, name):
+    """every cell of the binary scan through cnf2h_qtlbin_fit on rescaled and shifted covariates: nothing changes"""
+    got = bin_host_check(scan, case, "transform " + name, V.apply(V.make_bin_base(case), V.BIN_TRANSFORMS[name]), {})
+    if name in "FG":
+        print("INVARIANCE host %s %s transform %s | bit-equal to the base run: %s" %
+              (scan, case[0], name, V.bin_bit_equal(got, bin_host_base(case, scan))))
+
+
+@pytest.mark.parametrize("change", BIN_CHANGES)
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", BIN_SCAN_IDS)
+def test_bin_host_complement_and_relabelling(scan, case, change):
+    """y -> 1 - y, classes 0 and 3 or 1 and 2 exchanged, the covariate columns exchanged, the individuals reordered"""
+    inp, how = bin_changed(V.make_bin_base(case), change)
+    bin_host_check(scan, case, change, inp, how)
+
+
+def test_bin_nearly_collinear_marker_under_a_shift():
+    """13 individuals of classes 1 .. 3 with up to 1e-3 of class 0: a + d is the intercept but for that leak, both effects are
+    kept (relative pivot between QTL_PIVOT and 1e-3) and their estimates run to thousands.  Such a fit multiplies any change
+    of the centred covariate by 1e7 and more: with the mean rounded to one double, age + 16384 moved the effects of 38 of
+    these 40 draws, by up to 1.4.  The centred value is now rounded once from a mean carried in two doubles
+    (qtl_column_mean2), so an exactly shifted covariate gives the same centred bits, and the fit the same bits."""
+    from cnf2freq_amd import synth
+    n, cells, differ, wild = 13, 0, 0, 0
+    for seed in range(40):
+        k = (synth.uniform(3 + seed, np.arange(n)) * 3).astype(int) + 1
+        o = np.zeros((n, 4))
+        o[np.arange(n), k] = 1.0
+        leak = synth.uniform(400 + seed, np.arange(n)) * 1e-3
+        o[:, 0] = leak
+        o[np.arange(n), k] -= leak
+        z = V.on_grid(synth.uniform(50 + seed, np.arange(n)) * 10.0)[:, None]
+        y = RB.bernoulli(0.8 * (o[:, 3] - o[:, 0])[:, None], 2 + seed)[:, 0]
+        assert np.array_equal((z + 16384.0) - 16384.0, z)
+        f = host.qtlbin_fit(o, y, z, max_iter=30, tol=1e-6)
+        g = host.qtlbin_fit(o, y, z + 16384.0, max_iter=30, tol=1e-6)
+        if f["rank"] != 2 or f["ll0"] == 0.0:
+            continue
+        cells += 1
+        wild += bool(np.abs(f["coef"]).max() > 100.0)
+        same = f["lod"] == g["lod"] and V.same_bits(f["coef"], g["coef"]) and (f["iters"], f["status"]) == (g["iters"], g["status"])
+        differ += not same
+    print("nearly collinear markers: %d fits, %d with an effect beyond 100, %d change under age + 16384" % (cells, wild, differ))
+    assert cells >= 30 and wild >= 20 and differ == 0

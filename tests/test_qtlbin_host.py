@@ -1,6 +1,7 @@
 """CPU tests of the binary-trait scan: cnf2_qtlbin.h compiled for the host and run through cnf2h_qtlbin_fit, one (marker,
 column) cell at a time, against the yardstick tests/qtlbin_reference.py; the yardstick's own anchor, scan_binary's argument
-checks, the command line's usage errors for the new flags and the exported symbols."""
+checks, the command line's usage errors for the new flags and the exported symbols; at the end the cases of every width of
+X0 and of the design (a, i), and two edges of the walk over the individuals, as tests/test_gpu_qtlbin.py runs them."""
 import ctypes as C
 import os
 import subprocess
@@ -256,3 +257,67 @@ def test_command_line_usage_errors(tmp_path):
         r = subprocess.run(args, capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
         assert r.returncode == 2 and text in r.stderr, (extra, r.returncode, r.stderr)
         assert not (tmp_path / "q.txt").exists()
+
+
+# ------------------------------------------------------------------------------------- every width of X0, every design
+@pytest.mark.parametrize("stop", (False, True), ids=("fixed", "stop"))
+@pytest.mark.parametrize("case", R.WIDTH_CASES, ids=R.case_id)
+def test_every_width_and_design(case, stop):
+    """K = 3 .. 7 and the design (a, i) through cnf2h_qtlbin_fit, as tests/test_gpu_qtlbin.py runs them on the device: a
+    failure there that does not show here is the kernels', not the model's"""
+    n, K, imprint, additive, seed, T, P, mask, skipped, max_iter = case
+    how = R.WIDTH_STOP if stop else dict(max_iter=max_iter, tol=-1.0)
+    ref = R.case_reference(case, **(R.WIDTH_STOP if stop else {}))
+    # on the references alone, before the product runs
+    R.assert_conditions([R.case_reference(c, **(R.WIDTH_STOP if stop else {})) for c in R.WIDTH_CASES])
+    assert R.compared_cells(ref, CS, share=1.0).all()
+    if stop:
+        R.assert_anchor(ref, R.case_id(case))
+        assert np.all(ref["status"] == 0)
+    origin, pheno, cov, use, perm = R.make_case(*case)
+    got = host_scan(origin, pheno, use, cov, perm, imprint, additive, **how)
+    assert got["coef"].shape[2] == len(R.effects(additive, imprint))
+    R.compare_bin(got, ref, CS, "host %s %s" % (R.case_id(case), "to tol 1e-7" if stop else "fixed"), share=1.0)
+    if not stop:
+        fitted = got["rank"] > 0
+        assert np.all(got["iters"][:, fitted] == max_iter) and np.all(got["status"][:, fitted] == 1)
+
+
+def test_additive_imprint_drops_i():
+    """(a, i) on the degenerate rows: i is dropped at the homozygous and the symmetric marker, and lod and a are the additive
+    fit's without imprinting"""
+    origin, at = R.degenerate_rows()
+    n = origin.shape[0]
+    y = R.bernoulli(np.zeros((n, 1)), 11)[:, 0]
+    z = R.noise(n, 1, 12)
+    for m in (at["homozygous"], at["symmetric"]):
+        f = host.qtlbin_fit(origin[:, m], y, z, additive=True, imprint=True)
+        g = host.qtlbin_fit(origin[:, m], y, z, additive=True)
+        assert f["rank"] == 1 and np.isnan(f["coef"][1]) and f["lod"] == g["lod"] > 0.0 and f["coef"][0] == g["coef"][0]
+        assert f["iters"] == g["iters"] and len(f["coef"]) == 2 and len(g["coef"]) == 1
+    f = host.qtlbin_fit(origin[:, at["zeros"]], y, z, additive=True, imprint=True)
+    assert f["rank"] == 2 and np.isfinite(f["coef"]).all()
+
+
+# ------------------------------------------------------------------------------------- two edges of the walk
+def test_a_round_with_nobody_in_it():
+    p = R.EMPTY_ROUND
+    origin, pheno, z, use = R.empty_round_case()
+    ref = R.empty_round_reference()
+    R.assert_anchor(ref, "empty round")
+    R.compared_cells(ref, CS, share=p["share"])
+    assert ref["near"].mean() <= 0.01 and np.all(ref["n_used"] == 66)
+    got = host_scan(origin, pheno, use, z, max_iter=p["max_iter"], tol=p["tol"])
+    R.compare_bin(got, ref, CS, "host n 130, 64 .. 127 unused", share=p["share"])
+
+
+@pytest.mark.parametrize("n_c", (7, 6))
+def test_scan_threshold_of_the_additive_imprint_design(n_c):
+    """(a, i) with K = 3: W = 6, so a chromosome with 7 individuals is scanned and one with 6 is not"""
+    origin, y, z = R.threshold_case(n_c)
+    ref = R.reference_scan_binary(origin, CS, y, None, z, imprint=True, additive=True, max_iter=50, tol=1e-7)
+    assert ref["usable"][R.THRESHOLD["chrom"]] == (n_c == 7) and ref["usable"].sum() == 5 + (n_c == 7)
+    got = host_scan(origin, y, None, z, imprint=True, additive=True, max_iter=50, tol=1e-7)
+    R.assert_threshold(got, n_c)
+    fine = R.compared_cells(dict(ref, maxeta=np.zeros_like(ref["maxeta"])), CS, share=0.9, strict=False)[0]
+    assert np.array_equal(got["rank"][fine], ref["rank"][fine])
