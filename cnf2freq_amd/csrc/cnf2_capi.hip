@@ -111,6 +111,7 @@ struct cnf2_ctx {
     // records; host images and the lookup table are kept so that a call allocates nothing in steady state
     int                  line_cap = -1;            // cnf2_set_line_records (negative: no cap of its own)
     int32_t              last_lines[4] = {0, 0, 0, 0};   // cnf2_last_line_records
+    int32_t              last_pack[2] = {0, 0};          // cnf2_last_uniform_pack
     unsigned             windows_gen = 0;          // counts the derivations of `windows`
     // what h_lines / h_line_keys and their device copies describe: a call with the same windows, range and cap reuses them
     bool                 lines_valid = false;
@@ -130,7 +131,8 @@ struct cnf2_ctx {
     DevBuf<double>    d_factors, d_loglik, d_dosage;
     DevBuf<int32_t>   d_lexp;                  // binary exponents of the fast kernel's likelihoods: [n][C][8] then [n][C]
     DevBuf<unsigned long long> d_clock;        // [4] clock stamps of the last plain fast-kernel launch
-    DevBuf<int>       d_jobnext;               // [5] job counters of the fast-kernel launches in flight (KernelParams::job_next)
+    DevBuf<PackedJob> d_upjobs;                // the groups of four of fb_unipack_kernel (group_uniform_jobs)
+    DevBuf<int>       d_jobnext;               // [6] job counters of the fast-kernel launches in flight (KernelParams::job_next)
     DevBuf<double>    d_scratch;               // small parity buffers
 
     // crossover posteriors (cnf2_sweep_crossovers)
@@ -717,7 +719,7 @@ static int ready(cnf2_ctx* ctx)
         RC_TRY(ctx->d_clock.ensure(ctx, (size_t)4));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_clock, 0, 4 * sizeof(unsigned long long), ctx->stream));
     }
-    RC_TRY(ctx->d_jobnext.ensure(ctx, (size_t)5));
+    RC_TRY(ctx->d_jobnext.ensure(ctx, (size_t)6));
     return CNF2_OK;
 }
 
@@ -881,16 +883,32 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     if ((size_t)n * ctx->n_chrom > 0x7fffffff) return fail(ctx, CNF2_ERR_ARG, "too many jobs in one call");
-    const JobPlan jp = job_plan(ctx, ind_begin, n, flags);
-    const size_t  n_fast = jp.n_fast, n_general = jp.jobs.size() - n_fast, n_packed = jp.pjobs.size();
+    JobPlan      jp = job_plan(ctx, ind_begin, n, flags);
+    const size_t n_fast = jp.n_fast, n_general = jp.jobs.size() - n_fast, n_packed = jp.pjobs.size();
     RC_TRY(ctx->d_jobs.ensure(ctx, jp.jobs.size() + 1));
-    if (!jp.jobs.empty())
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_jobs, jp.jobs.data(), sizeof(Job) * jp.jobs.size(), hipMemcpyHostToDevice, ctx->stream));
     if (n_packed > 0) {
         RC_TRY(ctx->d_pjobs.ensure(ctx, n_packed));
         HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pjobs, jp.pjobs.data(), sizeof(PackedJob) * n_packed, hipMemcpyHostToDevice, ctx->stream));
     }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copies have read the job vectors)
+    // the uniform jobs on records four to a wave (group_uniform_jobs: they become the tail of the fast jobs), then the list's
+    // upload; again where the call's lines change below
+    std::vector<PackedJob> ugroups;
+    const std::vector<Job> jobs_planned = jp.jobs;
+    auto group_and_upload = [&](const int32_t* keys) -> int {
+        jp.jobs = jobs_planned;
+        ugroups.clear();
+        size_t n_single = n_fast;      // (the jobs in front of the groups': launch_fb_fast forms it from the groups' number)
+        if (keys && !(flags & CNF2_NO_UNIFORM_PACK))
+            ugroups = group_uniform_jobs(jp.jobs, n_fast, ctx->windows.data() + ind_begin, keys, &n_single);
+        if (!jp.jobs.empty())
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_jobs, jp.jobs.data(), sizeof(Job) * jp.jobs.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (!ugroups.empty()) {
+            RC_TRY(ctx->d_upjobs.ensure(ctx, ugroups.size()));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_upjobs, ugroups.data(), sizeof(PackedJob) * ugroups.size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copies have read the job vectors)
+        return CNF2_OK;
+    };
 
     // grids and spill: one slot per resident wave, the fast kernel's slots first
     const int    mlen = longest_chrom(ctx);
@@ -916,10 +934,12 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         }
     };
     memset(ctx->last_lines, 0, sizeof(ctx->last_lines));
+    memset(ctx->last_pack, 0, sizeof(ctx->last_pack));
     if (uni_ok) {
         if (n_fast > 0 && !(flags & CNF2_NO_LINE_RECORDS)) RC_TRY(prepare_lines(ctx, ind_begin, n, want_lines, &n_lines));
         count_uniform();
     }
+    RC_TRY(group_and_upload(uni_ok && n_lines > 0 ? ctx->h_line_keys.data() : nullptr));
     const int fast_per_cu = n_uniform == 0       ? ctx->fast_blocks_per_cu
                             : n_uniform < n_fast ? std::max(ctx->fast_blocks_per_cu, ctx->uni_blocks_per_cu)
                                                  : ctx->uni_blocks_per_cu;
@@ -957,6 +977,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
                 RC_TRY(prepare_lines(ctx, ind_begin, n, std::min(want_lines, ctx->lines_fit), &n_lines));
                 count_uniform();
                 if (n_on_records == 0) n_lines = 0;
+                RC_TRY(group_and_upload(n_lines > 0 ? ctx->h_line_keys.data() : nullptr));
             }
         }
         if (n_lines > 0) RC_TRY(ctx->d_line_rec.ensure(ctx, (size_t)n_lines * ctx->n_markers * LINE_VALUES * 2));
@@ -965,6 +986,9 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     ctx->last_lines[1] = n_lines > 0 ? (int32_t)n_on_records : 0;
     ctx->last_lines[2] = (int32_t)n_uniform - ctx->last_lines[1];
     ctx->last_lines[3] = (int32_t)std::min<size_t>((size_t)n_lines * ctx->n_markers * LINE_VALUES * 2 * sizeof(LineRec), 0x7fffffff);
+    const size_t n_groups = n_lines > 0 ? ugroups.size() : 0;
+    ctx->last_pack[0] = (int32_t)(4 * n_groups);
+    ctx->last_pack[1] = (int32_t)n_groups;
 
     KernelParams p;
     base_params(ctx, &p);
@@ -1081,7 +1105,8 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         // (grid_fast covers the occupancy of whichever instantiations run; each takes what is resident of its own)
         const int gf = std::min(grid_for(n_fast, grid_fast), resident_blocks(ctx->n_cu, ctx->fast_blocks_per_cu, ctx->reserve_blocks));
         FastVariant plain_half{SW_PLAIN, half, half && (flags & CNF2_XPOSE)};
-        plain_half.n_uniform        = (int)n_uniform;
+        // (the packed jobs are uniform jobs on records, the tail of the fast jobs: the UNI launches sweep the others)
+        plain_half.n_uniform        = (int)(n_uniform - 4 * n_groups);
         plain_half.grid_uniform     = std::min(grid_for(n_uniform, grid_fast), resident_blocks(ctx->n_cu, ctx->uni_blocks_per_cu, ctx->reserve_blocks));
         plain_half.job_next_uniform = ctx->d_jobnext + 3;
         if (n_lines > 0) {
@@ -1090,6 +1115,11 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
             plain_half.n_uniform_rows = ctx->last_lines[2];
             p.line_rec         = ctx->d_line_rec;
             p.line_keys        = ctx->d_line_keys;
+            if (n_groups > 0) {
+                plain_half.pack_groups   = ctx->d_upjobs;
+                plain_half.n_pack_groups = (int)n_groups;
+                plain_half.grid_pack     = std::min(grid_for(n_groups, grid_fast), resident_blocks(ctx->n_cu, ctx->uni_blocks_per_cu, ctx->reserve_blocks));
+            }
         }
         p.clock_out = ctx->d_clock;
         if (mode.variant == SW_VITERBI) {
@@ -1138,6 +1168,13 @@ int cnf2_last_line_records(cnf2_ctx* ctx, int32_t* out)
 {
     if (!ctx || !out) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
     memcpy(out, ctx->last_lines, sizeof(ctx->last_lines));
+    return CNF2_OK;
+}
+
+int cnf2_last_uniform_pack(cnf2_ctx* ctx, int32_t* out)
+{
+    if (!ctx || !out) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
+    memcpy(out, ctx->last_pack, sizeof(ctx->last_pack));
     return CNF2_OK;
 }
 

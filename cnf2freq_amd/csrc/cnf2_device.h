@@ -277,6 +277,11 @@ struct FastVariant {
     // the UNI instantiation with SW_PLAIN_UNIFORM_ROWS (job counter job_next_uniform + 1)
     const LineKey* lines = nullptr;
     int          n_lines = 0, n_uniform_rows = 0;
+    // groups of four jobs swept by fb_unipack_kernel in front of the UNI launches (grid_pack blocks, job counter
+    // job_next_uniform + 2).  Their 4 n_pack_groups jobs are the LAST of the launch's p.n_jobs jobs and are not among the n_uniform:
+    // the other kernels sweep the jobs before them, the logarithms are taken of all
+    const PackedJob* pack_groups = nullptr;
+    int          n_pack_groups = 0, grid_pack = 0;
 };
 // Zeroes the launch's job counter, launches the instantiation (asking once for the tied instantiations' dynamic LDS) and
 // the kernel that takes the logarithms of its likelihoods.  Returns the launches' error; a combination that is not

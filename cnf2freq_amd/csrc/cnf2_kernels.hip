@@ -2446,6 +2446,373 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
     }
 }
 
+// =====================================================================================
+// Four uniform windows to a wave: the plain half-spill sweep of fb_fast_kernel's UNI / REC instantiation for groups of four
+// jobs of one chromosome whose windows have their lines among the launch's records (p.pjobs).  In a uniform
+// window the four lanes of a chain that differ in state bits 1 and 2 run the recursion on the same numbers, and
+// transition_uniform, chain_total and the reductions across chains never exchange over those bits: here each of the four carries
+// another job (cnf2_lane.h upk_job).  Per job every floating-point operation is the UNI instantiation's, on the same operands in
+// the same order -- the same bits -- and a wave-wide instruction of the recursion serves four jobs.  What was wave-wide and
+// would tie a job to its neighbours (dense rescaling, the count of analysed modes) is taken per job.
+//   tile:     2 markers x 4 jobs, table row = marker_in_tile << 2 | job (the 8 rows of fb_packed_kernel); the producer lane
+//             (part, row) works on the window of its row's job
+//   rows:     a lane forms the four B-side class sums of its job itself and then stands, one after the other, for the four
+//             lanes (upk_virtual_lane) that form the row partials in the job's own sweep; they are parked in the job's table row
+//             at those lanes' places, and the UNI tile epilogue adds them up in its order
+//   spill:    UPK_SPILL_ROW doubles per marker pair, the four compact rows side by side (the same bytes per unit)
+// =====================================================================================
+__global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_kernel(KernelParams p)
+{
+    constexpr int NR = 2, ROW = UPK_SPILL_ROW, TS = TAB_STRIDE;
+    __shared__ __attribute__((aligned(16))) double lds[CNF2_WAVES_PER_BLOCK][8 * TS];
+
+    const int wib   = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave  = blockIdx.x * CNF2_WAVES_PER_BLOCK + wib;
+    const int nwave = gridDim.x * CNF2_WAVES_PER_BLOCK;
+    double*   spill = p.spill + (size_t)wave * p.spill_stride;
+    const bool stamp = p.clock_out != nullptr && wave == 0;
+    unsigned long long t_shader = 0, t_wall = 0;
+    if (stamp) {
+        t_shader = __builtin_readcyclecounter();
+        t_wall   = wall_clock64();
+    }
+
+    auto take_job = [&](int strided) {
+        if (!p.job_next) return strided;
+        int j = 0;
+        if (fresh_lane() == 0) j = atomicAdd(p.job_next, 1);
+        return __builtin_amdgcn_readfirstlane(j);
+    };
+    for (int job = take_job(wave); job < p.n_pjobs; job = take_job(job + nwave)) {
+        const int       lane = fresh_lane();
+        const PackedJob& pj  = p.pjobs[job];
+        // the wave's tables and the windows, from scalars the compiler cannot see through: as values of the whole kernel their
+        // vector copies would be kept (in scratch) across every job
+        int           wq   = wib;
+        const Window* wins = p.windows;
+        KernelParams  pq   = p;        // (for the producer's loads: the rows' base likewise)
+        asm volatile("" : "+s"(wq), "+s"(wins), "+s"(pq.allele8));
+        double* const tab = lds[wq];
+        const int first = __builtin_amdgcn_readfirstlane(pj.first), last = __builtin_amdgcn_readfirstlane(pj.last);
+        const int chrom = __builtin_amdgcn_readfirstlane(pj.chrom);
+        const int ntile = (last - first + 2) >> 1;
+        // producer role: part x (marker in tile, job) on the window of the row's job
+        FastCtx cp;
+        cp.part = lane >> 3;
+        cp.mi   = lane & 7;
+        const int pmt  = cp.mi >> 2;
+        const int moff = pmt - cp.mi;          // load_rec and load_root_allele look at marker m0 + c.mi: this lane's is m0 + pmt
+        uint32_t  rec_row;                     // line * n_markers of this lane's line
+        {
+            const int    pind = pj.ind[cp.mi & 3];
+            const Window wp   = wins[pind];
+            make_part(wp, cp.part, &cp.pc, &cp.row_par, &cp.row_tr, &cp.row_ot);
+            cp.row_root = wp.row[0];
+            rec_row     = (uint32_t)p.line_keys[2 * (size_t)pind + (cp.pc.P ? 1 : 0)] * (uint32_t)p.n_markers;
+        }
+        cp.idx_base = part_entry_index(cp.part, 0);
+        cp.idx_k01  = part_entry_index(cp.part, 1) - cp.idx_base;
+        cp.idx_k10  = part_entry_index(cp.part, 2) - cp.idx_base;
+        // recursion role: chain s of job rj, class b0 (the tables of a uniform window do not depend on state bits 1 and 2:
+        // the lane reads them at those bits clear)
+        const int s = lane >> 3, rj = upk_job(lane), b0 = state_lo(lane) & 1;
+        const int ind = pj.ind[rj];
+        const int eind = pj.ind[s & 3];        // epilogue role: the individual of table row lane >> 3 = (marker in tile) << 2 | job
+        FastCtx   c;
+        c.s0 = s & 1;
+        c.s1 = (s >> 1) & 1;
+        c.s2 = (s >> 2) & 1;
+        c.lo = b0;
+        {
+            const Window& w = wins[ind];
+            c.active        = !(s & w.shiftignore) && s < w.shiftend;
+        }
+        const size_t je = (size_t)ind * p.n_chrom + chrom;
+        if (p.path_log && s == 0 && b0 == 0) p.path_log[je] = 2;
+        // the lanes of this lane's job, for what the one-job sweep asks of the whole wave: its two places among the 8 lanes of a
+        // chain; a ballot is folded over the chains on the scalar unit first
+        const unsigned jbits = (1u << state_lo(2 * rj)) | (1u << state_lo(2 * rj + 1));
+        auto any_in_job = [&](unsigned long long ballot) {
+            unsigned t = (unsigned)ballot | (unsigned)(ballot >> 32);
+            t |= t >> 16;
+            t |= t >> 8;
+            return (t & jbits) != 0;
+        };
+        double* const myrow0 = tab + rj * TS;            // the job's row of the tile's even marker
+        double* const myrow1 = myrow0 + 4 * TS;          // and of its odd one
+        const bool uspill = !(p.flags & KP_NO_DOSAGE);   // (a launch that forms no rows reads no spill row: nobody writes one)
+        const int  uoff   = upk_spill_value(lane);
+        const int  ioff   = upk_spill_inv(rj, s);
+        const bool iwr    = b0 == 0 && uspill;
+
+        using odd_t  = std::integral_constant<bool, true>;
+        using even_t = std::integral_constant<bool, false>;
+
+        // ---------------------------------------------------------------- forward (fb_fast_kernel's fwd_step, HALF, UNI)
+        double a[NR];
+#pragma unroll
+        for (int j = 0; j < NR; j++) a[j] = 1.0 / 64.0;
+        double mant = 1.0;
+        int    expo = 0;
+        bool   dead = false;
+        double pend = 1.0;
+        int    rmask = CNF2_RESCALE_MASK, bmask = CNF2_RESCALE_MASK;   // per job
+        auto fwd_step = [&](auto odd_tag, const double* row, int m) {
+            constexpr bool ODD = decltype(odd_tag)::value;
+            double         e[NR];
+            emission_from_row(row, c, e, pend);
+            const double2 r  = *(const double2*)(row + TAB_T);
+            const int     ml = m - first;
+            double*       sp = spill + (size_t)(ml >> 1) * ROW;
+            if (!ODD) {
+                const d2v v = {a[0], a[1]};
+                if (uspill) __builtin_nontemporal_store(v, (d2v*)(sp + uoff));
+            }
+#pragma unroll
+            for (int j = 0; j < NR; j++) a[j] *= e[j];
+            pend = 1.0;
+            // a job renormalises exactly where it would alone: every lane computes, the job's lanes take the result
+            const bool norm_here = m == last || (!ODD && (ml & rmask) == 0);
+            if (__ballot(norm_here)) {
+                double       mt = mant;
+                int          ex = expo;
+                bool         dd = dead;
+                const double inv = chain_normaliser<true>(a, &mt, &ex, &dd);
+                mant = norm_here ? mt : mant;
+                expo = norm_here ? ex : expo;
+                dead = norm_here ? dd : dead;
+                pend = norm_here ? inv : 1.0;
+                if (any_in_job(__ballot(norm_here && inv > CNF2_RESCALE_GUARD))) rmask = 1;
+                if (iwr && (!ODD || norm_here)) sp[ioff + (ODD ? 1 : 0)] = pend;
+            } else if (!ODD) {
+                if (iwr) sp[ioff] = 1.0;
+            }
+            if (m < last) transition_uniform(a, r.x, r.y);
+        };
+        RawRec  rraw;
+        uint8_t ap_next;
+        load_rec<0>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rraw);
+        ap_next = load_root_allele(pq, cp, first + 2 + moff, first, last);
+        for (int t = 0; t < ntile; t++) {
+            const int m0 = first + t * 2;
+            produce_row_rec<false>(cp, tab, m0 + pmt <= last, rraw);
+            if (t + 1 < ntile) {
+                load_rec<0>(pq, cp, rec_row, m0 + 2 + moff, first, last, ap_next, &rraw);
+                ap_next = load_root_allele(pq, cp, m0 + 4 + moff, first, last);
+            }
+            wave_lds_fence();
+            fwd_step(even_t(), myrow0, m0);
+            if (m0 < last) fwd_step(odd_t(), myrow1, m0 + 1);
+            wave_lds_fence();
+        }
+
+        // ---------------------------------------------------------------- likelihoods (per job: the reductions across chains
+        // pair lanes of equal lane & 7)
+        const bool   alive  = c.active && !dead;
+        const double emaxd  = across_chains_max(alive ? (double)expo : -1e300);
+        const bool   any_alive = emaxd > -1e299;
+        const int    emax   = any_alive ? (int)emaxd : 0;
+        int          dsh    = expo - emax;
+        dsh                 = dsh < -2000 ? -2000 : dsh;
+        const double tmine  = alive ? ldexp(mant, dsh) : 0.0;
+        const double T      = across_chains_sum(tmine);
+        {
+            const int n_active = __builtin_popcountll(__ballot(c.active) & ((unsigned long long)jbits * 0x0101010101010101ull)) >> 1;
+            if (b0 == 0) {
+                p.factors[je * 8 + s] = mant;
+                p.fexp[je * 8 + s]    = alive ? expo : (c.active ? CNF2_LEXP_DEAD : CNF2_LEXP_IGNORED);
+            }
+            if (s == 0 && b0 == 0) {
+                p.loglik[je] = any_alive ? T : (double)n_active;
+                p.lexp[je]   = any_alive ? emax : CNF2_LEXP_DEAD;
+            }
+        }
+        if (p.flags & KP_NO_DOSAGE) continue;
+
+        // ---------------------------------------------------------------- backward + rows (fb_fast_kernel's marker, HALF, UNI)
+        BwdState<NR> S;
+#pragma unroll
+        for (int j = 0; j < NR; j++) S.b[j] = 1.0;
+        S.bmant = 1.0;
+        S.bexpo = 0;
+        S.bdead = false;
+        S.fmant = mant;
+        S.fexpo = expo;
+        const double xm  = any_alive ? 1.0 / T : 0.0;
+        const int    xe  = -emax;
+        const bool   chain_on = alive && !(tmine * 2.3538526683701998e17 < T);        // factor - fs > 40: cnF2freq.cpp:5420-5421
+        auto load_row = [&](int idx) {
+            const double* sp = spill + (size_t)idx * ROW;
+            const d2v     v  = __builtin_nontemporal_load((const d2v*)(sp + uoff));
+            S.am[0]          = v.x;
+            S.am[1]          = v.y;
+            const double2 iv = *(const double2*)(sp + ioff);
+            S.inv_even       = iv.x;
+            S.inv_odd        = iv.y;
+        };
+        S.inv_odd = 1.0;
+        load_row((last - first) >> 1);
+
+        auto marker = [&](auto odd_tag, double* row, int m, bool carried = false) {
+            constexpr bool ODD = decltype(odd_tag)::value;
+            const int      ml  = m - first;
+            double         wj[NR];
+            const double2  r_m = *(const double2*)(row + TAB_T);     // gap m-1 -> m
+            double         inv_m;
+            if (ODD) {
+                double ep[NR];
+                emission_from_row(row - 4 * TS, c, ep);             // the even marker's row of this job
+#pragma unroll
+                for (int j = 0; j < NR; j++) S.ec[j] = ep[j];
+#pragma unroll
+                for (int j = 0; j < NR; j++) wj[j] = S.am[j] * ep[j];
+                transition_uniform(wj, r_m.x, r_m.y);
+#pragma unroll
+                for (int j = 0; j < NR; j++) wj[j] *= S.b[j];
+                inv_m = S.inv_odd;
+            } else {
+#pragma unroll
+                for (int j = 0; j < NR; j++) wj[j] = S.am[j] * S.b[j];
+                inv_m = S.inv_even;
+                asm volatile("" : "+v"(wj[0]), "+v"(wj[1]), "+v"(inv_m) : : "memory");
+                const int idx = (ml >> 1) - 1;
+                load_row(idx < 0 ? 0 : idx);
+            }
+            if (!ODD || m == last) {
+                int ex;
+                S.fmant = frexp(S.fmant * inv_m, &ex);
+                S.fexpo += ex;
+            }
+            // the four B-side class sums of the job, z[2 f + (TAB_2 ? 1 : 0)]: the chains the UNI instantiation shares out over
+            // the four lanes, each formed here by the one lane
+            double        z[4];
+            const double* Bs = row + ((1 << 5) | (c.s2 << 3));
+#pragma unroll
+            for (int kq = 0; kq < 4; kq++) {
+                const double* Bk = Bs + ((kq & 1) ? TAB_2 : TAB_R) + ((kq >> 1) << 4);
+                double        zz = 0.0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) zz += wj[j & 1] * Bk[j];
+                z[kq] = zz;
+            }
+            const double sc0   = ODD ? xm * S.inv_even : xm;
+            const double scale = chain_on ? ldexp(sc0 * S.fmant * S.bmant, xe + S.fexpo + S.bexpo) : 0.0;
+            const double cf0 = row[TAB_C + 0 + c.s0], cf1 = row[TAB_C + 2 + c.s0];
+            double       q[4][3];
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                double n_tot = 0.0, n_a1 = 0.0, n_b1 = 0.0, n_2 = 0.0;
+#pragma unroll
+                for (int f = 0; f < 2; f++) {
+                    const int    ia = (f << 4) | (c.s1 << 3) | b0 | (v << 1);
+                    const double cf = f ? cf1 : cf0;
+                    const double av = cf * row[TAB_R + ia], a1 = cf * row[TAB_2 + ia];
+                    const double sb = z[2 * f], sb1 = z[2 * f + 1];
+                    n_tot += av * sb;
+                    n_a1 += a1 * sb;
+                    n_b1 += av * sb1;
+                    n_2 += a1 * sb1;
+                }
+                q[v][2] = scale * n_2;
+                q[v][1] = scale * (n_a1 + n_b1 - 2.0 * n_2);
+                q[v][0] = scale * (n_tot - n_a1 - n_b1 + n_2);
+            }
+            double e[NR];
+            if (!ODD && carried) {
+#pragma unroll
+                for (int j = 0; j < NR; j++) e[j] = S.ec[j];
+            }
+            else emission_from_row(row, c, e);
+            // the partials into the job's row, where the lanes of its own sweep would park theirs
+            wave_lds_fence();
+#pragma unroll
+            for (int v = 0; v < 4; v++) {
+                const int vl = upk_virtual_lane(lane, v);
+                row[vl]       = q[v][0];
+                row[64 + vl]  = q[v][1];
+                row[128 + vl] = q[v][2];
+            }
+#pragma unroll
+            for (int j = 0; j < NR; j++) S.b[j] *= e[j];
+            const bool scale_here = !ODD && (ml & bmask) == 0;      // per job
+            if (!ODD && __ballot(scale_here)) {
+                double bb[NR] = {S.b[0], S.b[1]};
+                double bm = S.bmant;
+                int    be = S.bexpo;
+                bool   bd = S.bdead;
+                const double bsum = scale_chain<true>(bb, &bm, &be, &bd);
+#pragma unroll
+                for (int j = 0; j < NR; j++) S.b[j] = scale_here ? bb[j] : S.b[j];
+                S.bmant = scale_here ? bm : S.bmant;
+                S.bexpo = scale_here ? be : S.bexpo;
+                S.bdead = scale_here ? bd : S.bdead;
+                if (any_in_job(__ballot(scale_here && bsum > 0.0 && bsum * CNF2_RESCALE_GUARD < 1.0))) bmask = 1;
+            }
+            transition_uniform(S.b, r_m.x, r_m.y);
+        };
+        {
+            const int mtop = first + (ntile - 1) * 2;
+            load_rec<-1>(pq, cp, rec_row, mtop + moff, first, last, load_root_allele(pq, cp, mtop + moff, first, last), &rraw);
+            ap_next = load_root_allele(pq, cp, mtop - 2 + moff, first, last);
+        }
+        // epilogue role: row mi2 = (marker in tile) << 2 | job
+        const int    mi2 = lane >> 3, sub = lane & 7;
+        for (int t = ntile - 1; t >= 0; t--) {
+            const int m0 = first + t * 2;
+            produce_row_rec<true>(cp, tab, m0 + pmt <= last, rraw);
+            if (t > 0) {
+                load_rec<-1>(pq, cp, rec_row, m0 - 2 + moff, first, last, ap_next, &rraw);
+                ap_next = load_root_allele(pq, cp, m0 - 4 + moff, first, last);
+            }
+            wave_lds_fence();
+            if (m0 < last) {
+                marker(odd_t(), myrow1, m0 + 1);
+                marker(even_t(), myrow0, m0, true);
+            } else marker(even_t(), myrow0, m0);
+            wave_lds_fence();
+            // tile epilogue, as fb_fast_kernel's: lanes (row mi2, eighth sub) add up the 3 x 64 partials of the tile's rows
+            {
+                const double* red = tab + mi2 * TS + sub * 8;
+                double        d0 = 0.0, d1 = 0.0, d2 = 0.0;
+#pragma unroll
+                for (int i2 = 0; i2 < 8; i2++) {
+                    d0 += red[i2];
+                    d1 += red[64 + i2];
+                    d2 += red[128 + i2];
+                }
+                d0 = chain_sum(d0);
+                d1 = chain_sum(d1);
+                d2 = chain_sum(d2);
+                d0 = fmax(d0, 0.0);
+                d1 = fmax(d1, 0.0);
+                d2 = fmax(d2, 0.0);
+                if (sub == 0 && m0 + (mi2 >> 2) <= last) {
+                    if (!(p.flags & KP_RAW_DOSAGE)) {
+                        const double tsum = d0 + d1 + d2;
+                        const double inv  = tsum > 0.0 ? 1.0 / tsum : 0.0;
+                        d0 *= inv;
+                        d1 *= inv;
+                        d2 *= inv;
+                    }
+                    // (the row's address is formed here, from a value the compiler cannot see through: hoisted out of the tile
+                    // loop it would live, in scratch, across the whole backward pass)
+                    int ei = eind;
+                    asm volatile("" : "+v"(ei));
+                    double* out = p.dosage + ((size_t)ei * p.n_markers + (m0 + (mi2 >> 2))) * 3;
+                    out[0] = d0;
+                    out[1] = d1;
+                    out[2] = d2;
+                }
+            }
+            wave_lds_fence();
+        }
+    }
+    if (stamp && fresh_lane() == 0) {
+        p.clock_out[0] = __builtin_readcyclecounter() - t_shader;
+        p.clock_out[1] = wall_clock64() - t_wall;
+    }
+}
+
 // The logarithms of the likelihoods a fast-kernel launch left as mantissa and binary exponent: one thread per (job, shift
 // mode), thread 0 of a job also the job's total.  Adds the chromosome's dropped butterfly constants (chrom_logk).
 __global__ __launch_bounds__(256) void likelihood_logs_kernel(KernelParams p)
@@ -4794,25 +5161,42 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     // class and each with its own job counter.  The logarithms are taken once, after both
     const bool plain_half = fast_key(v.storew, v.half, v.xpose, v.tied) == fast_key(SW_PLAIN, true);
     const int  n_uni      = plain_half ? v.n_uniform : 0;
-    if (n_uni > 0) {
+    // the groups of four of fb_unipack_kernel: their jobs are the list's tail, which no other kernel of the launch sweeps
+    const int  n_pack     = plain_half && v.pack_groups && v.n_lines > 0 && p.line_rec && p.line_keys ? v.n_pack_groups : 0;
+    const int  n_sweep    = p.n_jobs - 4 * n_pack;
+    if (n_sweep < 0) return hipErrorInvalidValue;
+    if (n_uni > 0 || n_pack > 0) {
         KernelParams pu = p;
+        pu.n_jobs = n_sweep;
         if (pu.job_next) pu.job_next = v.job_next_uniform;
         const int gu = v.grid_uniform > 0 ? v.grid_uniform : grid;
         // the launch's line records first, on the same stream (rebuilt for every launch: the rows change between sweeps), then
-        // the windows that have their lines among them; then the others (n_uniform_rows of the n_uniform jobs) through the UNI
-        // form with the ordinary producer, in the same spill slots with a job counter of its own
-        const bool records = v.n_lines > 0 && pu.line_rec && pu.line_keys && v.n_uniform_rows < n_uni;
+        // the groups of four, then the single windows that have their lines among the records; then the others (n_uniform_rows
+        // of the n_uniform jobs) through the UNI form with the ordinary producer -- all in the same spill slots, each with a job
+        // counter of its own
+        const bool records = v.n_lines > 0 && pu.line_rec && pu.line_keys && (v.n_uniform_rows < n_uni || n_pack > 0);
         if (records) {
             const size_t n_rec = (size_t)v.n_lines * p.n_markers * LINE_VALUES * 2;
             hipLaunchKernelGGL(line_records_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, stream, v.lines, v.n_lines,
                                p.allele8, p.sure, p.hw, p.n_markers, const_cast<LineRec*>(pu.line_rec));
-            zero_job_counter(pu, stream);
-            launch_fast_as<true, SW_PLAIN, false, false, true>(pu, gu, stream);
+            if (n_pack > 0) {
+                KernelParams pk = pu;
+                pk.pjobs   = v.pack_groups;
+                pk.n_pjobs = n_pack;
+                if (pk.job_next) pk.job_next = v.job_next_uniform + 2;
+                zero_job_counter(pk, stream);
+                hipLaunchKernelGGL(fb_unipack_kernel, dim3(v.grid_pack > 0 ? v.grid_pack : gu), dim3(CNF2_BLOCK), 0, stream, pk);
+                pu.clock_out = nullptr;
+            }
+            if (v.n_uniform_rows < n_uni) {
+                zero_job_counter(pu, stream);
+                launch_fast_as<true, SW_PLAIN, false, false, true>(pu, gu, stream);
+            }
         } else {
             pu.line_rec  = nullptr;
             pu.line_keys = nullptr;
         }
-        if (!records || v.n_uniform_rows > 0) {
+        if (n_uni > 0 && (!records || v.n_uniform_rows > 0)) {
             if (records) {
                 pu.clock_out = nullptr;
                 if (pu.job_next) pu.job_next = v.job_next_uniform + 1;
@@ -4820,12 +5204,14 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
             zero_job_counter(pu, stream);
             launch_fast_as<true, SW_PLAIN_UNIFORM_ROWS, false, false, true>(pu, gu, stream);
         }
-        if (n_uni >= p.n_jobs) {
+        if (n_uni >= n_sweep) {
             launch_likelihood_logs(p, stream);
             return hipGetLastError();
         }
     }
     KernelParams po = p;
+    po.n_jobs = n_sweep;
+    if (n_pack > 0) po.clock_out = nullptr;
     if (n_uni > 0) po.flags |= KP_SKIP_UNIFORM;
     zero_job_counter(po, stream);
     switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the twenty instantiations there are (and UNI above)

@@ -62,6 +62,20 @@ CNF2_HD int uni_spill_value(int lane) { return (lane >> 3) * 4 + (state_lo(lane)
 // offset (doubles) of a chain's two reciprocals
 CNF2_HD int uni_spill_inv(int chain) { return UNI_SPILL_INV + 2 * chain; }
 
+// Four uniform windows to a wave (fb_unipack_kernel).  The four lanes of a chain that differ only in state bits 1 and 2 run the
+// uniform recursion on the same numbers, so each of them carries another job: a lane's job is those two bits, its class state
+// bit 0, its chain lane >> 3 as ever.  For the rows a lane stands for the four lanes of its job's own sweep that share its chain
+// and class: virtual lane v = 0..3 has state bits 1 and 2 = v (the lane number under state_lo, which is its own inverse).
+CNF2_HD int upk_job(int lane) { return (state_lo(lane) >> 1) & 3; }
+CNF2_HD int upk_virtual_lane(int lane, int v) { return (lane & ~7) | state_lo((state_lo(lane) & 1) | (v << 1)); }
+// Spill row of that kernel: the four jobs' compact rows side by side.
+//   [lane 0..63][2]     = 128 doubles of values: every lane stores and loads its own register pair, one 16-byte access each
+//   [job][chain][2]     = 64 doubles: the reciprocal normalisers of UNI_SPILL_INV, per job
+// = 192 doubles, four times UNI_SPILL_ROW.
+enum { UPK_SPILL_INV = 128, UPK_SPILL_ROW = 192 };
+CNF2_HD int upk_spill_value(int lane) { return 2 * lane; }
+CNF2_HD int upk_spill_inv(int job, int chain) { return UPK_SPILL_INV + 2 * (8 * job + chain); }
+
 CNF2_HD int tie_force(int8_t tie, int combo)
 {
     return tie < 0 ? -1 : ((combo >> tie) & 1);

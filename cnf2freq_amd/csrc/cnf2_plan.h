@@ -105,6 +105,59 @@ inline JobPlan plan_jobs(const Window* windows, const int32_t* chromstarts, int 
     return plan;
 }
 
+// Groups of four for fb_unipack_kernel among the fast jobs [0, n_fast) of a job list (plan_jobs: chromosome by chromosome in
+// chrom_order, the individuals in order within each).  A job can be grouped when its window is uniform (slots_uniform) and has
+// both its lines among the call's records (line_keys [n][2], indexed like the jobs' ind; NULL = nobody has).  Per chromosome
+// the groupable jobs form fours in list order; what does not fill a four stays where it is, as does every other job.  The
+// grouped jobs are moved behind the others of [0, n_fast), group by group (the kernels that sweep single jobs get the front,
+// the logarithms are taken of the whole list); *n_single = how many stay in front.  The groups come in list order, so
+// chromosome by chromosome in chrom_order.  `windows` is indexed by ind.
+inline std::vector<PackedJob> group_uniform_jobs(std::vector<Job>& jobs, size_t n_fast, const Window* windows, const int32_t* line_keys,
+                                                 size_t* n_single)
+{
+    std::vector<PackedJob> groups;
+    std::vector<uint8_t>   taken(n_fast, 0);
+    auto groupable = [&](const Job& jb) {
+        return line_keys && line_keys[2 * (size_t)jb.ind] >= 0 && line_keys[2 * (size_t)jb.ind + 1] >= 0 &&
+               slots_uniform(windows[jb.ind].flags);
+    };
+    for (size_t b = 0; b < n_fast;) {
+        size_t e = b;
+        while (e < n_fast && jobs[e].chrom == jobs[b].chrom) e++;
+        size_t four[4];
+        int    k = 0;
+        for (size_t j = b; j < e; j++) {
+            if (!groupable(jobs[j])) continue;
+            four[k++] = j;
+            if (k < 4) continue;
+            PackedJob pj;
+            for (int i = 0; i < 4; i++) {
+                pj.ind[i]      = jobs[four[i]].ind;
+                taken[four[i]] = 1;
+            }
+            pj.first   = jobs[b].first;
+            pj.last    = jobs[b].last;
+            pj.chrom   = jobs[b].chrom;
+            pj.homleaf = 1;
+            groups.push_back(pj);
+            k = 0;
+        }
+        b = e;
+    }
+    *n_single = n_fast - 4 * groups.size();
+    if (groups.empty()) return groups;
+    std::vector<Job> front, back;
+    front.reserve(*n_single);
+    back.reserve(4 * groups.size());
+    for (size_t j = 0; j < n_fast; j++)
+        if (!taken[j]) front.push_back(jobs[j]);
+    for (const PackedJob& pj : groups)
+        for (int i = 0; i < 4; i++) back.push_back(Job{pj.ind[i], pj.first, pj.last, pj.chrom});
+    std::copy(front.begin(), front.end(), jobs.begin());
+    std::copy(back.begin(), back.end(), jobs.begin() + front.size());
+    return groups;
+}
+
 // ------------------------------------------------------------------------------------------------ grids and spill
 // Doubles of a wave's spill slot per marker of the longest chromosome: covers every layout (520 or 528 doubles per (pair
 // of) marker(s) in the fast kernel, 512 in the general kernel)

@@ -121,6 +121,10 @@ enum {
                                      emission terms from the window's own seven rows, as the ordinary one does, instead of reading
                                      what a window's ancestors contribute from the launch's line records (cnf2_last_line_records).
                                      Same results to the bit; A/B switch and cross-check.  Ignored where no records are used */
+    CNF2_NO_UNIFORM_PACK = 1u << 26, /* cnf2_sweep and its Viterbi mode: every window of a cross of inbred lines is swept by a wave of
+                                     its own, instead of four windows of one chromosome to a wave where four of them have their
+                                     lines among the launch's records (cnf2_last_uniform_pack).  Same results to the bit; A/B
+                                     switch and cross-check.  Ignored where no windows are packed */
     CNF2_QTL_IMPRINT  = 1u << 25, /* cnf2_qtl_scanx: the design gets the parent-of-origin (imprinting) effect i = o[1] - o[2] */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
@@ -894,6 +898,13 @@ int    cnf2_set_batch_jobs(cnf2_ctx *ctx, int jobs);
  * without, bytes of records (0 0 0 0 after a call whose mode or flags use no such instantiation). */
 int    cnf2_set_line_records(cnf2_ctx *ctx, int lines);
 int    cnf2_last_line_records(cnf2_ctx *ctx, int32_t *out);
+/* Four windows to a wave.  The jobs of a call that are swept on line records are taken four at a time, chromosome by
+ * chromosome in the order of the job list, and each group of four is swept by one wavefront: in such a window the recursion does
+ * not depend on four of the six state bits, and the lanes that would repeat it carry the other three jobs instead.  What does
+ * not fill a group of four, and every job under CNF2_NO_UNIFORM_PACK, CNF2_NO_LINE_RECORDS, CNF2_ALL_STATES, CNF2_FULL_SPILL or
+ * CNF2_XPOSE, is swept one job to a wave, to the same bits.  Packed jobs count as swept on records in cnf2_last_line_records.
+ * cnf2_last_uniform_pack: out[2] = the packed jobs of the last sweep's call and their groups (0 0 where nothing was packed). */
+int    cnf2_last_uniform_pack(cnf2_ctx *ctx, int32_t *out);
 
 #ifdef __cplusplus
 }
