@@ -30,6 +30,7 @@ QTL_ADDITIVE = 1 << 22            # cnf2_qtl_scan / cnf2_sweep_qtl: the dominanc
 QTL_ORIGIN_DEVICE = 1 << 23       # cnf2_qtl_scan: the origin rows are a device pointer
 QTL_IMPRINT = 1 << 25             # cnf2_qtl_scanx: the design gets the imprinting effect i = o[1] - o[2]
 NO_UNIFORM_PACK = 1 << 26         # crosses of inbred lines: one window to a wave, not four windows of a chromosome (A/B, cross-check)
+NO_UNIFORM_PACK8 = 1 << 27        # crosses of inbred lines: packed windows four to a wave only, not eight windows of a chromosome (A/B, cross-check)
 NO_LINE_RECORDS = 1 << 24         # crosses of inbred lines: every window's emission terms from its own rows, not from the launch's line records (A/B, cross-check)
 STATIC_JOBS = 1 << 18             # wave w sweeps jobs w, w + waves, ... instead of taking jobs from the launch's counter (A/B)
 MINFACTOR = float(np.float32(-1e15))
@@ -44,7 +45,7 @@ SYMBOLS = [
     "cnf2_turn_scan", "cnf2_turn_scan_rows", "cnf2_state_posterior", "cnf2_haplos", "cnf2_infprobs", "cnf2_infprobs_rows", "cnf2_descendants", "cnf2_accumulate", "cnf2_sweep_accumulate", "cnf2_sweep_turn_scan", "cnf2_fixparents_scan", "cnf2_variances", "cnf2_variances_exact",
     "cnf2_snapshot_priors", "cnf2_update_pass", "cnf2_download_rows", "cnf2_download_accumulators", "cnf2_upload_accumulators", "cnf2_accumulator_ptrs", "cnf2_update_stats", "cnf2_update_stats_guided", "cnf2_addvariance", "cnf2_emission", "cnf2_emission_paths",
     "cnf2_selftest_lane_xor", "cnf2_last_kernel_ms", "cnf2_last_paths", "cnf2_workspace_bytes", "cnf2_reserve_accumulate", "cnf2_clock_probe", "cnf2_sweep_clock", "cnf2_stream",
-    "cnf2_set_grid_reserve", "cnf2_set_batch_jobs", "cnf2_set_line_records", "cnf2_last_line_records", "cnf2_last_uniform_pack", "cnf2_window_table", "cnf2_update_pass_records", "cnf2_exchange_buffer", "cnf2_exchange_download", "cnf2_exchange_upload", "cnf2_exchange_read", "cnf2_exchange_write",
+    "cnf2_set_grid_reserve", "cnf2_set_batch_jobs", "cnf2_set_line_records", "cnf2_last_line_records", "cnf2_last_uniform_pack", "cnf2_last_uniform_pack8", "cnf2_window_table", "cnf2_update_pass_records", "cnf2_exchange_buffer", "cnf2_exchange_download", "cnf2_exchange_upload", "cnf2_exchange_read", "cnf2_exchange_write",
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
@@ -168,6 +169,7 @@ def load():
         L.cnf2_set_line_records.argtypes = [vp, i32]
         L.cnf2_last_line_records.argtypes = [vp, vp]
         L.cnf2_last_uniform_pack.argtypes = [vp, vp]
+        L.cnf2_last_uniform_pack8.argtypes = [vp, vp]
         L.cnf2_window_table.argtypes = [vp, vp]
         L.cnf2_update_pass_records.argtypes = [vp, i32, vp, i32, vp, vp, C.c_double, C.c_double, vp, C.c_uint32]
         L.cnf2_exchange_buffer.argtypes = [vp, C.c_size_t, vp]
@@ -306,7 +308,7 @@ class Context:
     # -- the sweep -------------------------------------------------------------
     def sweep(self, ind_begin=0, ind_end=None, dosage=True, raw=False, ties=True, full_spill=False,
               merge_modes=False, xpose=False, log_paths=False, ties_general=False, static_jobs=False, flush_tiny=False, all_states=False,
-              line_records=True, uniform_pack=True):
+              line_records=True, uniform_pack=True, uniform_pack8=True):
         ind_end = self.n_ind if ind_end is None else ind_end
         n = ind_end - ind_begin
         factors = np.zeros((n, self.n_chrom, 8))
@@ -316,7 +318,7 @@ class Context:
                  | (FULL_SPILL if full_spill else 0) | (MERGE_MODES if merge_modes else 0) | (XPOSE if xpose else 0)
                  | (LOG_PATHS if log_paths else 0) | (TIES_GENERAL if ties_general else 0) | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0)
                  | (FLUSH_TINY if flush_tiny else 0) | (0 if line_records else NO_LINE_RECORDS)
-                 | (0 if uniform_pack else NO_UNIFORM_PACK))
+                 | (0 if uniform_pack else NO_UNIFORM_PACK) | (0 if uniform_pack8 else NO_UNIFORM_PACK8))
         self._chk(self.L.cnf2_sweep(self.h, ind_begin, ind_end, _p(factors), _p(loglik),
                                     _p(dos) if dosage else None, flags), "cnf2_sweep")
         out = dict(factors=factors, loglik=loglik, dosage=dos)
@@ -357,6 +359,12 @@ class Context:
         out = np.zeros(2, np.int32)
         self._chk(self.L.cnf2_last_uniform_pack(self.h, _p(out)), "cnf2_last_uniform_pack")
         return dict(jobs=int(out[0]), groups=int(out[1]))
+
+    def last_uniform_pack8(self):
+        """dict(eights, jobs): the pairs of groups of the last sweep that went eight to a wave, and their jobs (cnf2_last_uniform_pack8)."""
+        out = np.zeros(2, np.int32)
+        self._chk(self.L.cnf2_last_uniform_pack8(self.h, _p(out)), "cnf2_last_uniform_pack8")
+        return dict(eights=int(out[0]), jobs=int(out[1]))
 
     def set_batch_jobs(self, jobs):
         """Cap on the jobs per batch of sweep_accumulate / sweep_turn_scan (0 = what memory allows)."""
@@ -422,7 +430,7 @@ class Context:
         return dict(factors=factors, loglik=loglik, xo=xo, xo_sum=xs, n_contrib=cnt)
 
     def sweep_viterbi(self, ind_begin=0, ind_end=None, full_spill=False, ties_general=False, static_jobs=False, all_states=False,
-                      line_records=True, uniform_pack=True):
+                      line_records=True, uniform_pack=True, uniform_pack8=True):
         """cnf2_sweep_viterbi: factors / loglik as sweep(), logmax[n][C][8], the MAP state path state[n][M] (uint8, 0xFF
         where skipped), the MAP shift mode shift[n][C] (-1 where skipped) and path_logpost[n][C] = logmax[s*] - loglik,
         the log posterior probability of the decoded (mode, path) (NaN where skipped)."""
@@ -435,7 +443,7 @@ class Context:
         shift = np.zeros((n, self.n_chrom), np.int32)
         flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
                  | (STATIC_JOBS if static_jobs else 0) | (ALL_STATES if all_states else 0) | (0 if line_records else NO_LINE_RECORDS)
-                 | (0 if uniform_pack else NO_UNIFORM_PACK))
+                 | (0 if uniform_pack else NO_UNIFORM_PACK) | (0 if uniform_pack8 else NO_UNIFORM_PACK8))
         self._chk(self.L.cnf2_sweep_viterbi(self.h, ind_begin, ind_end, _p(factors), _p(loglik), _p(logmax),
                                             _p(state), _p(shift), flags), "cnf2_sweep_viterbi")
         best = np.take_along_axis(logmax, np.maximum(shift, 0)[..., None], axis=2)[..., 0]

@@ -112,6 +112,7 @@ struct cnf2_ctx {
     int                  line_cap = -1;            // cnf2_set_line_records (negative: no cap of its own)
     int32_t              last_lines[4] = {0, 0, 0, 0};   // cnf2_last_line_records
     int32_t              last_pack[2] = {0, 0};          // cnf2_last_uniform_pack
+    int32_t              last_pack8[2] = {0, 0};         // cnf2_last_uniform_pack8
     unsigned             windows_gen = 0;          // counts the derivations of `windows`
     // what h_lines / h_line_keys and their device copies describe: a call with the same windows, range and cap reuses them
     bool                 lines_valid = false;
@@ -132,7 +133,7 @@ struct cnf2_ctx {
     DevBuf<int32_t>   d_lexp;                  // binary exponents of the fast kernel's likelihoods: [n][C][8] then [n][C]
     DevBuf<unsigned long long> d_clock;        // [4] clock stamps of the last plain fast-kernel launch
     DevBuf<PackedJob> d_upjobs;                // the groups of four of fb_unipack_kernel (group_uniform_jobs)
-    DevBuf<int>       d_jobnext;               // [6] job counters of the fast-kernel launches in flight (KernelParams::job_next)
+    DevBuf<int>       d_jobnext;               // [7] job counters of the fast-kernel launches in flight (KernelParams::job_next)
     DevBuf<double>    d_scratch;               // small parity buffers
 
     // crossover posteriors (cnf2_sweep_crossovers)
@@ -719,7 +720,7 @@ static int ready(cnf2_ctx* ctx)
         RC_TRY(ctx->d_clock.ensure(ctx, (size_t)4));
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_clock, 0, 4 * sizeof(unsigned long long), ctx->stream));
     }
-    RC_TRY(ctx->d_jobnext.ensure(ctx, (size_t)6));
+    RC_TRY(ctx->d_jobnext.ensure(ctx, (size_t)7));
     return CNF2_OK;
 }
 
@@ -902,11 +903,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
             ugroups = group_uniform_jobs(jp.jobs, n_fast, ctx->windows.data() + ind_begin, keys, &n_single);
         if (!jp.jobs.empty())
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_jobs, jp.jobs.data(), sizeof(Job) * jp.jobs.size(), hipMemcpyHostToDevice, ctx->stream));
-        if (!ugroups.empty()) {
-            RC_TRY(ctx->d_upjobs.ensure(ctx, ugroups.size()));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_upjobs, ugroups.data(), sizeof(PackedJob) * ugroups.size(), hipMemcpyHostToDevice, ctx->stream));
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copies have read the job vectors)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copy has read the job vector)
         return CNF2_OK;
     };
 
@@ -935,6 +932,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     };
     memset(ctx->last_lines, 0, sizeof(ctx->last_lines));
     memset(ctx->last_pack, 0, sizeof(ctx->last_pack));
+    memset(ctx->last_pack8, 0, sizeof(ctx->last_pack8));
     if (uni_ok) {
         if (n_fast > 0 && !(flags & CNF2_NO_LINE_RECORDS)) RC_TRY(prepare_lines(ctx, ind_begin, n, want_lines, &n_lines));
         count_uniform();
@@ -989,6 +987,19 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     const size_t n_groups = n_lines > 0 ? ugroups.size() : 0;
     ctx->last_pack[0] = (int32_t)(4 * n_groups);
     ctx->last_pack[1] = (int32_t)n_groups;
+    // the groups' upload, once the call's lines and the grids stand: pairs of groups whose windows have all eight modes analysed
+    // go eight jobs to a wave (pair_uniform_groups: a whole number of rounds of the packed grid's resident waves), in front
+    const int pack_cap = std::min(grid_fast, resident_blocks(ctx->n_cu, ctx->uni_blocks_per_cu, ctx->reserve_blocks));
+    size_t    n_eights = 0;
+    if (n_groups > 0) {
+        if (!(flags & CNF2_NO_UNIFORM_PACK8))
+            n_eights = pair_uniform_groups(ugroups, ctx->windows.data() + ind_begin, (size_t)pack_cap * CNF2_WAVES_PER_BLOCK);
+        RC_TRY(ctx->d_upjobs.ensure(ctx, ugroups.size()));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_upjobs, ugroups.data(), sizeof(PackedJob) * ugroups.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copy has read the vector)
+    }
+    ctx->last_pack8[0] = (int32_t)n_eights;
+    ctx->last_pack8[1] = (int32_t)(8 * n_eights);
 
     KernelParams p;
     base_params(ctx, &p);
@@ -1118,7 +1129,9 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
             if (n_groups > 0) {
                 plain_half.pack_groups   = ctx->d_upjobs;
                 plain_half.n_pack_groups = (int)n_groups;
-                plain_half.grid_pack     = std::min(grid_for(n_groups, grid_fast), resident_blocks(ctx->n_cu, ctx->uni_blocks_per_cu, ctx->reserve_blocks));
+                plain_half.n_pack_eights = (int)n_eights;
+                plain_half.grid_pack     = grid_for(n_groups - 2 * n_eights, pack_cap);
+                plain_half.grid_pack8    = grid_for(n_eights, pack_cap);
             }
         }
         p.clock_out = ctx->d_clock;
@@ -1175,6 +1188,13 @@ int cnf2_last_uniform_pack(cnf2_ctx* ctx, int32_t* out)
 {
     if (!ctx || !out) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
     memcpy(out, ctx->last_pack, sizeof(ctx->last_pack));
+    return CNF2_OK;
+}
+
+int cnf2_last_uniform_pack8(cnf2_ctx* ctx, int32_t* out)
+{
+    if (!ctx || !out) return fail(ctx, CNF2_ERR_ARG, "bad arguments");
+    memcpy(out, ctx->last_pack8, sizeof(ctx->last_pack8));
     return CNF2_OK;
 }
 
@@ -1359,7 +1379,9 @@ static int mode_sweep(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     if (mode.variant == SW_CROSSOVERS)
         HIP_TRY(ctx, hipMemsetAsync(mode.xo_sum, 0, (size_t)ctx->n_markers * 6 * sizeof(double), ctx->stream));
     if (mode.xo_cnt) HIP_TRY(ctx, hipMemsetAsync(mode.xo_cnt, 0, (size_t)ctx->n_chrom * sizeof(int32_t), ctx->stream));
-    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL | CNF2_ALL_STATES);
+    // (the A/B switches of the plain sweep's route: they reach the Viterbi mode's likelihood launch)
+    const uint32_t pass = flags & (CNF2_OUT_DEVICE | CNF2_STATIC_JOBS | CNF2_FULL_SPILL | CNF2_TIES_GENERAL | CNF2_ALL_STATES |
+                                   CNF2_NO_LINE_RECORDS | CNF2_NO_UNIFORM_PACK | CNF2_NO_UNIFORM_PACK8);
     return sweep_impl(ctx, ind_begin, ind_end, factors_out, loglik_out, nullptr, pass, mode);
 }
 

@@ -282,6 +282,9 @@ struct FastVariant {
     // the other kernels sweep the jobs before them, the logarithms are taken of all
     const PackedJob* pack_groups = nullptr;
     int          n_pack_groups = 0, grid_pack = 0;
+    // of which the first 2 n_pack_eights form pairs swept by fb_unipack8_kernel, eight jobs to a wave, in front of the others
+    // (pair_uniform_groups; grid_pack8 blocks, job counter job_next_uniform + 3)
+    int          n_pack_eights = 0, grid_pack8 = 0;
 };
 // Zeroes the launch's job counter, launches the instantiation (asking once for the tied instantiations' dynamic LDS) and
 // the kernel that takes the logarithms of its likelihoods.  Returns the launches' error; a combination that is not

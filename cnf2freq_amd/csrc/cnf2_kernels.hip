@@ -2813,6 +2813,379 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
     }
 }
 
+// =====================================================================================
+// Eight uniform windows to a wave: fb_unipack_kernel's sweep for pairs of its groups (p.pjobs[2 e], p.pjobs[2 e + 1]) whose eight
+// windows have all eight shift modes analysed (shiftignore == 0, shiftend == 8; pair_uniform_groups).  On line records the
+// unrestricted table is one value per part whatever the parent's shift bit, so the chains of a job with equal s0 see the same
+// emissions and carry the same alpha, beta and scales: the lanes that differ in s1 take another job as well (cnf2_lane.h
+// up8_*).  Per job every floating-point operation is fb_unipack_kernel's, on the same operands in the same order.
+//   tile:     1 marker x 8 jobs, table row = job; the producer lane is (part, job), the epilogue's lanes (row, eighth) run once
+//             per marker
+//   rows:     a lane forms the four B-side class sums of (s0, s2) once and the row partials for s1 = 1 and then s1 = 0; they
+//             are parked in the job's row in two steps (up8_park), each over what nobody reads any more
+//   rebuild:  the odd marker's rebuild starts from alpha x emission of the even marker, which the forward pass spills beside
+//             alpha (the even marker's row does not exist yet when the odd one is worked on); the even marker forms its
+//             emission from its own row
+//   spill:    UP8_SPILL_ROW doubles per marker pair, stored by the lanes with s2 = 0
+// =====================================================================================
+static_assert(TAB_R == 72 && TAB_2 == 136 && TAB_STRIDE >= 200, "up8_park (cnf2_lane.h) is written for this row layout");
+__global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_kernel(KernelParams p)
+{
+    constexpr int NR = 2, ROW = UP8_SPILL_ROW, TS = TAB_STRIDE;
+    __shared__ __attribute__((aligned(16))) double lds[CNF2_WAVES_PER_BLOCK][8 * TS];
+
+    const int wib   = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave  = blockIdx.x * CNF2_WAVES_PER_BLOCK + wib;
+    const int nwave = gridDim.x * CNF2_WAVES_PER_BLOCK;
+    double*   spill = p.spill + (size_t)wave * p.spill_stride;
+    const bool stamp = p.clock_out != nullptr && wave == 0;
+    unsigned long long t_shader = 0, t_wall = 0;
+    if (stamp) {
+        t_shader = __builtin_readcyclecounter();
+        t_wall   = wall_clock64();
+    }
+
+    auto take_job = [&](int strided) {
+        if (!p.job_next) return strided;
+        int j = 0;
+        if (fresh_lane() == 0) j = atomicAdd(p.job_next, 1);
+        return __builtin_amdgcn_readfirstlane(j);
+    };
+    for (int job = take_job(wave); job < p.n_pjobs; job = take_job(job + nwave)) {
+        const int        lane = fresh_lane();
+        const PackedJob* pj   = p.pjobs + 2 * (size_t)job;      // the eight's two fours
+        // (scalars the compiler cannot see through, as in fb_unipack_kernel)
+        int           wq   = wib;
+        const Window* wins = p.windows;
+        KernelParams  pq   = p;
+        asm volatile("" : "+s"(wq), "+s"(wins), "+s"(pq.allele8));
+        double* const tab = lds[wq];
+        const int first = __builtin_amdgcn_readfirstlane(pj[0].first), last = __builtin_amdgcn_readfirstlane(pj[0].last);
+        const int chrom = __builtin_amdgcn_readfirstlane(pj[0].chrom);
+        // producer role: part x job, one marker at a time
+        FastCtx cp;
+        cp.part = lane >> 3;
+        cp.mi   = lane & 7;
+        const int moff = -cp.mi;               // load_rec and load_root_allele look at marker m0 + c.mi: this lane's is m0
+        uint32_t  rec_row;                     // line * n_markers of this lane's line
+        {
+            const int    pind = pj[cp.mi >> 2].ind[cp.mi & 3];
+            const Window wp   = wins[pind];
+            make_part(wp, cp.part, &cp.pc, &cp.row_par, &cp.row_tr, &cp.row_ot);
+            cp.row_root = wp.row[0];
+            rec_row     = (uint32_t)p.line_keys[2 * (size_t)pind + (cp.pc.P ? 1 : 0)] * (uint32_t)p.n_markers;
+        }
+        cp.idx_base = part_entry_index(cp.part, 0);
+        cp.idx_k01  = part_entry_index(cp.part, 1) - cp.idx_base;
+        cp.idx_k10  = part_entry_index(cp.part, 2) - cp.idx_base;
+        // recursion role: the chains (s0, s1 = 0 and 1, s2) of job rj, class b0 (the unrestricted table does not depend on a
+        // parent's shift bit: the lane reads it at s1 = 0)
+        const int rj = up8_job(lane), b0 = up8_b0(lane);
+        const int ind = pj[rj >> 2].ind[rj & 3];
+        const int eind = pj[lane >> 5].ind[(lane >> 3) & 3];    // epilogue role: the individual of table row lane >> 3 = job
+        FastCtx   c;
+        c.s0 = up8_s0(lane);
+        c.s1 = 0;
+        c.s2 = up8_s2(lane);
+        c.lo = b0;
+        c.active = true;                       // (eligibility: all eight modes of every window)
+        const size_t je = (size_t)ind * p.n_chrom + chrom;
+        const bool   jlead = c.s0 == 0 && c.s2 == 0 && b0 == 0;
+        if (p.path_log && jlead) p.path_log[je] = 2;
+        // the lanes of this lane's job, for what the one-job sweep asks of the whole wave: its two places among the 8 lanes of
+        // a group, in the groups of its half of the wave; a ballot's halves are folded on the scalar unit first
+        const unsigned jbits = (1u << state_lo(2 * (rj & 3))) | (1u << state_lo(2 * (rj & 3) + 1));
+        auto any_in_job = [&](unsigned long long ballot) {
+            unsigned tl = (unsigned)ballot, th = (unsigned)(ballot >> 32);
+            tl |= tl >> 16;
+            tl |= tl >> 8;
+            th |= th >> 16;
+            th |= th >> 8;
+            return (((rj & 4) ? th : tl) & jbits) != 0;
+        };
+        double* const myrow = tab + rj * TS;             // the job's row
+        const bool uspill = !(p.flags & KP_NO_DOSAGE);   // (a launch that forms no rows reads no spill row: nobody writes one)
+        const int  uoff   = up8_spill_value(lane);
+        const int  ioff   = up8_spill_inv(rj, c.s0);
+        const bool vwr    = up8_spill_writer(lane) && uspill;
+        const bool iwr    = b0 == 0 && vwr;
+
+        using odd_t  = std::integral_constant<bool, true>;
+        using even_t = std::integral_constant<bool, false>;
+
+        // ---------------------------------------------------------------- forward (fb_unipack_kernel's fwd_step)
+        double a[NR];
+#pragma unroll
+        for (int j = 0; j < NR; j++) a[j] = 1.0 / 64.0;
+        double mant = 1.0;
+        int    expo = 0;
+        bool   dead = false;
+        double pend = 1.0;
+        int    rmask = CNF2_RESCALE_MASK, bmask = CNF2_RESCALE_MASK;   // per job
+        auto fwd_step = [&](auto odd_tag, const double* row, int m) {
+            constexpr bool ODD = decltype(odd_tag)::value;
+            double         e[NR];
+            emission_from_row(row, c, e, pend);
+            const double2 r  = *(const double2*)(row + TAB_T);
+            const int     ml = m - first;
+            double*       sp = spill + (size_t)(ml >> 1) * ROW;
+            if (!ODD) {
+                // alpha, and alpha x the marker's emission: what the backward pass's rebuild of the odd marker starts from
+                double ep[NR];
+                emission_from_row(row, c, ep);
+                const d2v v = {a[0], a[1]};
+                const d2v w = {a[0] * ep[0], a[1] * ep[1]};
+                if (vwr) {
+                    __builtin_nontemporal_store(v, (d2v*)(sp + uoff));
+                    __builtin_nontemporal_store(w, (d2v*)(sp + UP8_SPILL_EMIT + uoff));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NR; j++) a[j] *= e[j];
+            pend = 1.0;
+            // a job renormalises exactly where it would alone: every lane computes, the job's lanes take the result
+            const bool norm_here = m == last || (!ODD && (ml & rmask) == 0);
+            if (__ballot(norm_here)) {
+                double       mt = mant;
+                int          ex = expo;
+                bool         dd = dead;
+                const double inv = chain_normaliser<true>(a, &mt, &ex, &dd);
+                mant = norm_here ? mt : mant;
+                expo = norm_here ? ex : expo;
+                dead = norm_here ? dd : dead;
+                pend = norm_here ? inv : 1.0;
+                if (any_in_job(__ballot(norm_here && inv > CNF2_RESCALE_GUARD))) rmask = 1;
+                if (iwr && (!ODD || norm_here)) sp[ioff + (ODD ? 1 : 0)] = pend;
+            } else if (!ODD) {
+                if (iwr) sp[ioff] = 1.0;
+            }
+            if (m < last) transition_uniform(a, r.x, r.y);
+        };
+        RawRec  rraw;
+        uint8_t ap_next;
+        load_rec<0>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rraw);
+        ap_next = load_root_allele(pq, cp, first + 1 + moff, first, last);
+        for (int m = first; m <= last; m++) {
+            produce_row_rec<false>(cp, tab, true, rraw);
+            if (m < last) {
+                load_rec<0>(pq, cp, rec_row, m + 1 + moff, first, last, ap_next, &rraw);
+                ap_next = load_root_allele(pq, cp, m + 2 + moff, first, last);
+            }
+            wave_lds_fence();
+            if ((m - first) & 1) fwd_step(odd_t(), myrow, m);
+            else fwd_step(even_t(), myrow, m);
+            wave_lds_fence();
+        }
+
+        // ---------------------------------------------------------------- likelihoods (per job: its two distinct chains sit
+        // eight lanes apart; the sum over its eight chains doubles their sum twice, which is exact)
+        const bool   alive  = !dead;
+        const double emine  = alive ? (double)expo : -1e300;
+        const double emaxd  = fmax(emine, lane_xor8(emine));
+        const bool   any_alive = emaxd > -1e299;
+        const int    emax   = any_alive ? (int)emaxd : 0;
+        int          dsh    = expo - emax;
+        dsh                 = dsh < -2000 ? -2000 : dsh;
+        const double tmine  = alive ? ldexp(mant, dsh) : 0.0;
+        double       T      = tmine + lane_xor8(tmine);
+        T += T;
+        T += T;
+        if (b0 == 0 && c.s2 == 0) {
+#pragma unroll
+            for (int s1 = 0; s1 < 2; s1++) {
+                const int s = c.s0 | (s1 << 1);
+#pragma unroll
+                for (int s2 = 0; s2 < 2; s2++) {
+                    p.factors[je * 8 + (s | (s2 << 2))] = mant;
+                    p.fexp[je * 8 + (s | (s2 << 2))]    = alive ? expo : CNF2_LEXP_DEAD;
+                }
+            }
+        }
+        if (jlead) {
+            p.loglik[je] = any_alive ? T : 8.0;          // (the count of analysed modes)
+            p.lexp[je]   = any_alive ? emax : CNF2_LEXP_DEAD;
+        }
+        if (p.flags & KP_NO_DOSAGE) continue;
+
+        // ---------------------------------------------------------------- backward + rows (fb_unipack_kernel's marker)
+        BwdState<NR> S;
+#pragma unroll
+        for (int j = 0; j < NR; j++) S.b[j] = 1.0;
+        S.bmant = 1.0;
+        S.bexpo = 0;
+        S.bdead = false;
+        S.fmant = mant;
+        S.fexpo = expo;
+        const double xm  = any_alive ? 1.0 / T : 0.0;
+        const int    xe  = -emax;
+        const bool   chain_on = alive && !(tmine * 2.3538526683701998e17 < T);        // factor - fs > 40: cnF2freq.cpp:5420-5421
+        // S.am holds what the next marker starts from: alpha x emission of the pair's even marker in front of an odd marker,
+        // alpha in front of an even one; each is asked for one marker ahead
+        auto load_value = [&](int idx, int off) {
+            const d2v v = __builtin_nontemporal_load((const d2v*)(spill + (size_t)idx * ROW + off + uoff));
+            S.am[0]     = v.x;
+            S.am[1]     = v.y;
+        };
+        auto load_inv = [&](int idx) {
+            const double2 iv = *(const double2*)(spill + (size_t)idx * ROW + ioff);
+            S.inv_even       = iv.x;
+            S.inv_odd        = iv.y;
+        };
+        load_value((last - first) >> 1, ((last - first) & 1) ? UP8_SPILL_EMIT : 0);
+        load_inv((last - first) >> 1);
+
+        auto marker = [&](auto odd_tag, double* row, int m) {
+            constexpr bool ODD = decltype(odd_tag)::value;
+            const int      ml  = m - first;
+            double         wj[NR];
+            const double2  r_m = *(const double2*)(row + TAB_T);     // gap m-1 -> m
+            double         inv_m;
+            if (ODD) {
+#pragma unroll
+                for (int j = 0; j < NR; j++) wj[j] = S.am[j];
+                asm volatile("" : "+v"(wj[0]), "+v"(wj[1]) : : "memory");
+                load_value(ml >> 1, 0);
+                transition_uniform(wj, r_m.x, r_m.y);
+#pragma unroll
+                for (int j = 0; j < NR; j++) wj[j] *= S.b[j];
+                inv_m = S.inv_odd;
+            } else {
+#pragma unroll
+                for (int j = 0; j < NR; j++) wj[j] = S.am[j] * S.b[j];
+                inv_m = S.inv_even;
+                asm volatile("" : "+v"(wj[0]), "+v"(wj[1]), "+v"(inv_m) : : "memory");
+                const int idx = (ml >> 1) - 1;
+                load_value(idx < 0 ? 0 : idx, UP8_SPILL_EMIT);
+                load_inv(idx < 0 ? 0 : idx);
+            }
+            if (!ODD || m == last) {
+                int ex;
+                S.fmant = frexp(S.fmant * inv_m, &ex);
+                S.fexpo += ex;
+            }
+            // the four B-side class sums of (s0, s2), z[2 f + (TAB_2 ? 1 : 0)]
+            double        z[4];
+            const double* Bs = row + ((1 << 5) | (c.s2 << 3));
+#pragma unroll
+            for (int kq = 0; kq < 4; kq++) {
+                const double* Bk = Bs + ((kq & 1) ? TAB_2 : TAB_R) + ((kq >> 1) << 4);
+                double        zz = 0.0;
+#pragma unroll
+                for (int j = 0; j < 8; j++) zz += wj[j & 1] * Bk[j];
+                z[kq] = zz;
+            }
+            const double sc0   = ODD ? xm * S.inv_even : xm;
+            const double scale = chain_on ? ldexp(sc0 * S.fmant * S.bmant, xe + S.fexpo + S.bexpo) : 0.0;
+            const double cf0 = row[TAB_C + 0 + c.s0], cf1 = row[TAB_C + 2 + c.s0];
+            double e[NR];
+            emission_from_row(row, c, e);
+            // the partials of s1 = 1, then of s1 = 0, into the job's row where the epilogue looks for them
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int s1 = 1 - h;
+                double    q[4][3];
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    double n_tot = 0.0, n_a1 = 0.0, n_b1 = 0.0, n_2 = 0.0;
+#pragma unroll
+                    for (int f = 0; f < 2; f++) {
+                        const int    ia = (f << 4) | (s1 << 3) | b0 | (v << 1);
+                        const double cf = f ? cf1 : cf0;
+                        const double av = cf * row[TAB_R + ia], a1 = cf * row[TAB_2 + ia];
+                        const double sb = z[2 * f], sb1 = z[2 * f + 1];
+                        n_tot += av * sb;
+                        n_a1 += a1 * sb;
+                        n_b1 += av * sb1;
+                        n_2 += a1 * sb1;
+                    }
+                    q[v][2] = scale * n_2;
+                    q[v][1] = scale * (n_a1 + n_b1 - 2.0 * n_2);
+                    q[v][0] = scale * (n_tot - n_a1 - n_b1 + n_2);
+                }
+                wave_lds_fence();
+#pragma unroll
+                for (int v = 0; v < 4; v++) {
+                    const int vl = up8_virtual_lane(lane, s1, v);
+                    row[up8_park(0, vl)] = q[v][0];
+                    row[up8_park(1, vl)] = q[v][1];
+                    row[up8_park(2, vl)] = q[v][2];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < NR; j++) S.b[j] *= e[j];
+            const bool scale_here = !ODD && (ml & bmask) == 0;      // per job
+            if (!ODD && __ballot(scale_here)) {
+                double bb[NR] = {S.b[0], S.b[1]};
+                double bm = S.bmant;
+                int    be = S.bexpo;
+                bool   bd = S.bdead;
+                const double bsum = scale_chain<true>(bb, &bm, &be, &bd);
+#pragma unroll
+                for (int j = 0; j < NR; j++) S.b[j] = scale_here ? bb[j] : S.b[j];
+                S.bmant = scale_here ? bm : S.bmant;
+                S.bexpo = scale_here ? be : S.bexpo;
+                S.bdead = scale_here ? bd : S.bdead;
+                if (any_in_job(__ballot(scale_here && bsum > 0.0 && bsum * CNF2_RESCALE_GUARD < 1.0))) bmask = 1;
+            }
+            transition_uniform(S.b, r_m.x, r_m.y);
+        };
+        load_rec<-1>(pq, cp, rec_row, last + moff, first, last, load_root_allele(pq, cp, last + moff, first, last), &rraw);
+        ap_next = load_root_allele(pq, cp, last - 1 + moff, first, last);
+        // epilogue role: row mi2 = job, chain sub
+        const int mi2 = lane >> 3, sub = lane & 7;
+        for (int m = last; m >= first; m--) {
+            produce_row_rec<true>(cp, tab, true, rraw);
+            if (m > first) {
+                load_rec<-1>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);
+                ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
+            }
+            wave_lds_fence();
+            if ((m - first) & 1) marker(odd_t(), myrow, m);
+            else marker(even_t(), myrow, m);
+            wave_lds_fence();
+            // tile epilogue, as fb_fast_kernel's: lanes (row mi2, eighth sub) add up the 3 x 64 partials of the tile's rows
+            {
+                const double *red0 =tab + mi2 * TS + up8_park(0, sub * 8), *red1 = tab + mi2 * TS + up8_park(1, sub * 8),
+                             *red2 = tab + mi2 * TS + up8_park(2, sub * 8);
+                double        d0 = 0.0, d1 = 0.0, d2 = 0.0;
+#pragma unroll
+                for (int i2 = 0; i2 < 8; i2++) {
+                    d0 += red0[i2];
+                    d1 += red1[i2];
+                    d2 += red2[i2];
+                }
+                d0 = chain_sum(d0);
+                d1 = chain_sum(d1);
+                d2 = chain_sum(d2);
+                d0 = fmax(d0, 0.0);
+                d1 = fmax(d1, 0.0);
+                d2 = fmax(d2, 0.0);
+                if (sub == 0) {
+                    if (!(p.flags & KP_RAW_DOSAGE)) {
+                        const double tsum = d0 + d1 + d2;
+                        const double inv  = tsum > 0.0 ? 1.0 / tsum : 0.0;
+                        d0 *= inv;
+                        d1 *= inv;
+                        d2 *= inv;
+                    }
+                    // (the row's address is formed here, from a value the compiler cannot see through)
+                    int ei = eind;
+                    asm volatile("" : "+v"(ei));
+                    double* out = p.dosage + ((size_t)ei * p.n_markers + m) * 3;
+                    out[0] = d0;
+                    out[1] = d1;
+                    out[2] = d2;
+                }
+            }
+            wave_lds_fence();
+        }
+    }
+    if (stamp && fresh_lane() == 0) {
+        p.clock_out[0] = __builtin_readcyclecounter() - t_shader;
+        p.clock_out[1] = wall_clock64() - t_wall;
+    }
+}
+
 // The logarithms of the likelihoods a fast-kernel launch left as mantissa and binary exponent: one thread per (job, shift
 // mode), thread 0 of a job also the job's total.  Adds the chromosome's dropped butterfly constants (chrom_logk).
 __global__ __launch_bounds__(256) void likelihood_logs_kernel(KernelParams p)
@@ -5171,7 +5544,8 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
         if (pu.job_next) pu.job_next = v.job_next_uniform;
         const int gu = v.grid_uniform > 0 ? v.grid_uniform : grid;
         // the launch's line records first, on the same stream (rebuilt for every launch: the rows change between sweeps), then
-        // the groups of four, then the single windows that have their lines among the records; then the others (n_uniform_rows
+        // the pairs of groups of four (eight jobs to a wave), the groups of four left, then the single windows that have their
+        // lines among the records; then the others (n_uniform_rows
         // of the n_uniform jobs) through the UNI form with the ordinary producer -- all in the same spill slots, each with a job
         // counter of its own
         const bool records = v.n_lines > 0 && pu.line_rec && pu.line_keys && (v.n_uniform_rows < n_uni || n_pack > 0);
@@ -5179,10 +5553,22 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
             const size_t n_rec = (size_t)v.n_lines * p.n_markers * LINE_VALUES * 2;
             hipLaunchKernelGGL(line_records_kernel, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), 0, stream, v.lines, v.n_lines,
                                p.allele8, p.sure, p.hw, p.n_markers, const_cast<LineRec*>(pu.line_rec));
-            if (n_pack > 0) {
+            // (the pairs of groups first, eight jobs to a wave; the groups left behind them four to a wave)
+            const int n_eight = n_pack > 0 ? v.n_pack_eights : 0;
+            if (n_eight < 0 || 2 * n_eight > n_pack) return hipErrorInvalidValue;
+            if (n_eight > 0) {
                 KernelParams pk = pu;
                 pk.pjobs   = v.pack_groups;
-                pk.n_pjobs = n_pack;
+                pk.n_pjobs = n_eight;
+                if (pk.job_next) pk.job_next = v.job_next_uniform + 3;
+                zero_job_counter(pk, stream);
+                hipLaunchKernelGGL(fb_unipack8_kernel, dim3(v.grid_pack8 > 0 ? v.grid_pack8 : gu), dim3(CNF2_BLOCK), 0, stream, pk);
+                pu.clock_out = nullptr;
+            }
+            if (n_pack > 2 * n_eight) {
+                KernelParams pk = pu;
+                pk.pjobs   = v.pack_groups + 2 * n_eight;
+                pk.n_pjobs = n_pack - 2 * n_eight;
                 if (pk.job_next) pk.job_next = v.job_next_uniform + 2;
                 zero_job_counter(pk, stream);
                 hipLaunchKernelGGL(fb_unipack_kernel, dim3(v.grid_pack > 0 ? v.grid_pack : gu), dim3(CNF2_BLOCK), 0, stream, pk);

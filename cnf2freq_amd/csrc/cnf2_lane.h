@@ -76,6 +76,43 @@ enum { UPK_SPILL_INV = 128, UPK_SPILL_ROW = 192 };
 CNF2_HD int upk_spill_value(int lane) { return 2 * lane; }
 CNF2_HD int upk_spill_inv(int job, int chain) { return UPK_SPILL_INV + 2 * (8 * job + chain); }
 
+// Eight uniform windows to a wave (fb_unipack8_kernel), for windows with all eight shift modes analysed.  The unrestricted table
+// of a window on line records does not depend on a parent's shift bit, so the chains of a job with equal s0 run the recursion
+// on the same numbers as well: the lanes that differ in s1 carry another job, too.  A lane is (job 0..7, s0, s2, b0):
+//   lane = job_hi << 5 | s2 << 4 | s0 << 3 | l,  state_lo(l) = b0 | job_lo << 1     (lane ^ 1 flips b0, as the recursion needs it)
+// For the rows a lane forms the B-side class sums of (s0, s2) once and then stands for the eight lanes (s1, v) of the job's own
+// sweep with its s0, s2 and class: virtual lane (s1, v) is lane s * 8 + state_lo(b0 | v << 1) of chain s = s0 | s1 << 1 | s2 << 2.
+CNF2_HD int up8_job(int lane) { return ((lane >> 3) & 4) | ((state_lo(lane) >> 1) & 3); }
+CNF2_HD int up8_s0(int lane) { return (lane >> 3) & 1; }
+CNF2_HD int up8_s2(int lane) { return (lane >> 4) & 1; }
+CNF2_HD int up8_b0(int lane) { return state_lo(lane) & 1; }
+CNF2_HD int up8_virtual_lane(int lane, int s1, int v)
+{
+    return (up8_s0(lane) | (s1 << 1) | (up8_s2(lane) << 2)) * 8 + state_lo(up8_b0(lane) | (v << 1));
+}
+// Where the partial of class cls (0..2) of virtual lane vl is parked in the job's table row (TAB_STRIDE doubles: [0,64) the
+// unrestricted table, [64,72) root weights and gap, [72,136) restricted totals, [136,200) class-2 parts; the A side is the
+// lower half of a table).  The partials of s1 = 1 are parked first, while the A-side entries of s1 = 0 are still to be
+// read: they go over the unrestricted table and the B side of the restricted totals; those of s1 = 0 then go over the rest.
+// The tile epilogue reads chain s of class cls at up8_park(cls, s * 8) + 0..7, in the order it adds them in a one-job sweep.
+CNF2_HD int up8_park(int cls, int vl)
+{
+    const int s = vl >> 3, s1 = (s >> 1) & 1, i4 = (s & 1) | ((s >> 2) << 1);
+    const int base = s1 ? (cls == 0 ? 0 : (cls == 1 ? 32 : 104)) : (cls == 0 ? 72 : (cls == 1 ? 136 : 168));
+    return base + i4 * 8 + (vl & 7);
+}
+// Spill row of that kernel, per marker pair.  What a lane carries does not depend on s2: the lanes with s2 = 0 store, every lane
+// loads by its class w = job_hi << 4 | s0 << 3 | l.
+//   [w 0..31][2]        = 64 doubles: alpha in front of the even marker
+//   [w 0..31][2]        = 64 doubles: that alpha times the even marker's emission (what the odd marker's rebuild starts from)
+//   [job][s0][2]        = 32 doubles: the reciprocal normalisers of the even marker and of an odd last marker
+// = 160 doubles, ten lines of 128 bytes.
+enum { UP8_SPILL_EMIT = 64, UP8_SPILL_INV = 128, UP8_SPILL_ROW = 160 };
+CNF2_HD bool up8_spill_writer(int lane) { return up8_s2(lane) == 0; }
+CNF2_HD int up8_spill_value(int lane) { return 2 * (((lane >> 5) << 4) | (lane & 15)); }
+CNF2_HD int up8_spill_emit(int lane) { return UP8_SPILL_EMIT + up8_spill_value(lane); }
+CNF2_HD int up8_spill_inv(int job, int s0) { return UP8_SPILL_INV + 2 * (2 * job + s0); }
+
 CNF2_HD int tie_force(int8_t tie, int combo)
 {
     return tie < 0 ? -1 : ((combo >> tie) & 1);

@@ -158,6 +158,52 @@ inline std::vector<PackedJob> group_uniform_jobs(std::vector<Job>& jobs, size_t 
     return groups;
 }
 
+// Pairs of those groups for fb_unipack8_kernel: eight windows of a chromosome to a wave.  A four can be paired when every one of
+// its windows has all eight shift modes analysed (shiftignore == 0, shiftend == 8); per chromosome such fours pair up in list
+// order.  The paired fours move to the front of `groups` -- eight e is groups[2 e] and groups[2 e + 1] -- the others follow in
+// the order they had.  All jobs of a chromosome are equally long, and an eight takes longer than a four: with at least as many
+// eights as `waves` (the resident waves of the packed grid, 0 = no such rule) only a whole number of rounds of eights is kept
+// and the last pairs are handed back as fours, which fill the tail behind them.  Returns the number of eights.
+inline size_t pair_uniform_groups(std::vector<PackedJob>& groups, const Window* windows, size_t waves)
+{
+    auto all_modes = [&](const PackedJob& pj) {
+        for (int i = 0; i < 4; i++)
+            if (windows[pj.ind[i]].shiftignore != 0 || windows[pj.ind[i]].shiftend != 8) return false;
+        return true;
+    };
+    std::vector<size_t> firsts, seconds;
+    for (size_t b = 0; b < groups.size();) {
+        size_t e = b;
+        while (e < groups.size() && groups[e].chrom == groups[b].chrom) e++;
+        size_t open = e;                                   // an eligible four waiting for its partner
+        for (size_t g = b; g < e; g++) {
+            if (!all_modes(groups[g])) continue;
+            if (open == e) open = g;
+            else {
+                firsts.push_back(open);
+                seconds.push_back(g);
+                open = e;
+            }
+        }
+        b = e;
+    }
+    size_t n8 = firsts.size();
+    if (waves > 0 && n8 >= waves) n8 = n8 / waves * waves;
+    if (n8 == 0) return 0;
+    std::vector<uint8_t>   paired(groups.size(), 0);
+    std::vector<PackedJob> out;
+    out.reserve(groups.size());
+    for (size_t k = 0; k < n8; k++) {
+        out.push_back(groups[firsts[k]]);
+        out.push_back(groups[seconds[k]]);
+        paired[firsts[k]] = paired[seconds[k]] = 1;
+    }
+    for (size_t g = 0; g < groups.size(); g++)
+        if (!paired[g]) out.push_back(groups[g]);
+    groups.swap(out);
+    return n8;
+}
+
 // ------------------------------------------------------------------------------------------------ grids and spill
 // Doubles of a wave's spill slot per marker of the longest chromosome: covers every layout (520 or 528 doubles per (pair
 // of) marker(s) in the fast kernel, 512 in the general kernel)

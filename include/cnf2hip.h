@@ -125,6 +125,10 @@ enum {
                                      its own, instead of four windows of one chromosome to a wave where four of them have their
                                      lines among the launch's records (cnf2_last_uniform_pack).  Same results to the bit; A/B
                                      switch and cross-check.  Ignored where no windows are packed */
+    CNF2_NO_UNIFORM_PACK8 = 1u << 27, /* cnf2_sweep and its Viterbi mode: the packed windows go four to a wave only, instead of eight
+                                     where two groups of four of a chromosome have all eight shift modes of every window analysed
+                                     (cnf2_last_uniform_pack8).  Same results to the bit; A/B switch and cross-check.  Ignored
+                                     where no windows are packed */
     CNF2_QTL_IMPRINT  = 1u << 25, /* cnf2_qtl_scanx: the design gets the parent-of-origin (imprinting) effect i = o[1] - o[2] */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
@@ -905,6 +909,13 @@ int    cnf2_last_line_records(cnf2_ctx *ctx, int32_t *out);
  * CNF2_XPOSE, is swept one job to a wave, to the same bits.  Packed jobs count as swept on records in cnf2_last_line_records.
  * cnf2_last_uniform_pack: out[2] = the packed jobs of the last sweep's call and their groups (0 0 where nothing was packed). */
 int    cnf2_last_uniform_pack(cnf2_ctx *ctx, int32_t *out);
+/* Eight windows to a wave.  Two groups of four of one chromosome whose eight windows have all eight shift modes analysed are
+ * swept by one wavefront: on line records the recursion of such a window does not depend on the first parent's shift bit
+ * either, and the lanes that would repeat it carry the second group.  With at least as many eights as waves are resident, a
+ * whole number of rounds of eights is formed and the last pairs stay groups of four, swept behind them.  An eight counts as two
+ * groups in cnf2_last_uniform_pack.  Under CNF2_NO_UNIFORM_PACK8, and wherever nothing is packed, there are none.
+ * cnf2_last_uniform_pack8: out[2] = the eights of the last sweep's call and their jobs (0 0 where there were none). */
+int    cnf2_last_uniform_pack8(cnf2_ctx *ctx, int32_t *out);
 
 #ifdef __cplusplus
 }
