@@ -52,6 +52,7 @@ SYMBOLS = [
     "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
+    "cnf2_qtl_scan_cof", "cnf2_set_qtlcof_columns", "cnf2_qtl_kept_rows",
 ]
 
 
@@ -129,6 +130,10 @@ def load():
         L.cnf2_set_qtl2_columns.argtypes = [vp, i32]
         L.cnf2_qtl_scanx.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlx_columns.argtypes = [vp, i32]
+        L.cnf2_qtl_scan_cof.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, i32, vp,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_set_qtlcof_columns.argtypes = [vp, i32]
+        L.cnf2_qtl_kept_rows.argtypes = [vp, i32, i32, vp, vp]
         L.cnf2_qtl_scan_em.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, C.c_double,
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlem_columns.argtypes = [vp, i32]
@@ -776,6 +781,68 @@ class Context:
         sweep_qtl left in it, which this call leaves valid)."""
         return self._qtlx_call(n, C.c_void_p(d_origin), pheno, cov, interactive, use, perm,
                                QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0))
+
+    # -- cofactor scan: composite interval mapping, multi-QTL fits --------------------
+    QTLCOF_KEYS = ("lod", "lod_base", "coef", "rank", "rank_cof", "rss0", "n_used", "perm_max")
+
+    def set_qtlcof_columns(self, cap):
+        """Cap on the phenotype columns per tile of qtl_scan_cof (0 = what memory allows); results do not depend on it."""
+        self._chk(self.L.cnf2_set_qtlcof_columns(self.h, cap), "cnf2_set_qtlcof_columns")
+
+    def _qtlcof_outputs(self, T, P, ne):
+        M, Cn = self.n_markers, self.n_chrom
+        return dict(lod=np.zeros((T, M)), lod_base=np.zeros((T, M)), coef=np.zeros((T, M, ne)), rank=np.zeros(M, np.int32),
+                    rank_cof=np.zeros(M, np.int32), rss0=np.zeros((T, Cn)), n_used=np.zeros(Cn, np.int32),
+                    perm_max=np.zeros((P, T, Cn)) if P else None)
+
+    @staticmethod
+    def _qtlcof_ranges(cof, excl):
+        """(cof, excl_lo, excl_hi) as int32 arrays [Q]; excl None: every cofactor is left out at its own marker only"""
+        cof = np.ascontiguousarray([] if cof is None else cof, np.int32).reshape(-1)
+        lo, hi = (cof, cof) if excl is None else excl
+        lo, hi = np.ascontiguousarray(lo, np.int32).reshape(-1), np.ascontiguousarray(hi, np.int32).reshape(-1)
+        if lo.shape != cof.shape or hi.shape != cof.shape:
+            raise ValueError("excl must be (excl_lo[Q], excl_hi[Q]) with Q = len(cof)")
+        return cof, lo.copy(), hi.copy()
+
+    def _qtlcof_call(self, n, origin_ptr, pheno, cof, excl, cov, use, perm, flags, out=None):
+        """cnf2_qtl_scan_cof with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        cof, lo, hi = self._qtlcof_ranges(cof, excl)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        o = self._qtlcof_outputs(T, P, 1 if flags & QTL_ADDITIVE else 2) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_qtl_scan_cof(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), len(cof), _p(cof), _p(lo),
+                                           _p(hi), P, opt(perm), _p(o["lod"]), _p(o["lod_base"]), _p(o["coef"]), _p(o["rank"]),
+                                           _p(o["rank_cof"]), _p(o["rss0"]), _p(o["n_used"]), opt(o["perm_max"]), flags),
+                  "cnf2_qtl_scan_cof")
+        return o
+
+    def qtl_scan_cof(self, origin, pheno, cof, excl=None, cov=None, use=None, perm=None, additive=False, out=None):
+        """cnf2_qtl_scan_cof on host rows origin[n][M][4]: composite interval mapping.  Every marker is fitted together with
+        the cofactors cof[Q] (marker indices, strictly ascending); cofactor q is left out of the design at the markers
+        excl[0][q] .. excl[1][q] (excl None: at its own marker only; qtl.cofactor_windows makes ranges from a window in map
+        units).  A dict: lod[T][M] (the conditional LOD of the marker given the cofactors), lod_base[T][M] (the cofactors
+        against the null model), coef[T][M][ne] (the marker's effects in the full model, NaN for a dropped one), rank[M],
+        rank_cof[M], rss0[T][C], n_used[C], perm_max[P][T][C] (the maxima over the markers in no range; None without
+        permutations).  The model: include/cnf2hip.h; cnf2freq_amd/qtl.py reads the results."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return self._qtlcof_call(origin.shape[0], _p(origin), pheno, cof, excl, cov, use, perm, QTL_ADDITIVE if additive else 0, out)
+
+    def qtl_scan_cof_device(self, n, d_origin, pheno, cof, excl=None, cov=None, use=None, perm=None, additive=False):
+        """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
+        sweep_qtl left in it, which this call leaves valid)."""
+        return self._qtlcof_call(n, C.c_void_p(d_origin), pheno, cof, excl, cov, use, perm,
+                                 QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0))
+
+    def qtl_kept_rows(self, n, sel):
+        """cnf2_qtl_kept_rows: [len(sel)][n][4], the rows this context's last sweep_qtl left in it at the markers sel"""
+        sel = np.ascontiguousarray(sel, np.int32).reshape(-1)
+        out = np.zeros((len(sel), n, 4))
+        self._chk(self.L.cnf2_qtl_kept_rows(self.h, n, len(sel), _p(sel), _p(out)), "cnf2_qtl_kept_rows")
+        return out
 
     # -- maximum-likelihood single-locus scan: EM interval mapping -------------------
     QTLEM_KEYS = ("lod", "coef", "sigma2", "iters", "status", "rank", "rss0", "n_used", "perm_max")

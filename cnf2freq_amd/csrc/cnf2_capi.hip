@@ -23,6 +23,7 @@
 #include "cnf2_qtl.h"
 #include "cnf2_qtl2.h"
 #include "cnf2_qtlx.h"
+#include "cnf2_qtlcof.h"
 #include "cnf2_qtlem.h"
 #include "cnf2_qtlbin.h"
 
@@ -183,6 +184,12 @@ struct cnf2_ctx {
     int             qtlx_columns = 0;
     DevBuf<double>  d_qx_yy, d_qx_tilemax, d_qx_lod, d_qx_coef, d_qx_rss0, d_qx_pmax;
     DevBuf<int32_t> d_qx_map, d_qx_nc, d_qx_rank;   // d_qx_map: chromstarts, tiles, tile starts
+
+    // cofactor scan (cnf2_qtl_scan_cof): its column cap, the cofactor columns, sum c y^2 per chromosome, the tile maxima,
+    // staged outputs; the staged inputs, the mask and the column image are the single scan's buffers
+    int             qtlcof_columns = 0;
+    DevBuf<double>  d_qc_img, d_qc_yy, d_qc_tilemax, d_qc_lod, d_qc_lod_base, d_qc_coef, d_qc_rss0, d_qc_pmax;
+    DevBuf<int32_t> d_qc_map, d_qc_nc, d_qc_rank, d_qc_rank_cof;   // d_qc_map: chromstarts, tiles, tile starts, cof, their chromosomes' starts, skip words
 
     // maximum-likelihood single-locus scan (cnf2_qtl_scan_em): its column cap, which effects a marker keeps, the tile
     // maxima, staged outputs; the staged inputs, the mask, the factor, the column image and the null fit are the single
@@ -421,6 +428,14 @@ int cnf2_set_qtlx_columns(cnf2_ctx* ctx, int cap)
 {
     if (!ctx || cap < 0) return ctx ? fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative") : CNF2_ERR_ARG;
     ctx->qtlx_columns = cap;
+    return CNF2_OK;
+}
+
+int cnf2_set_qtlcof_columns(cnf2_ctx* ctx, int cap)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (cap < 0) return fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative");
+    ctx->qtlcof_columns = cap;
     return CNF2_OK;
 }
 
@@ -1994,6 +2009,166 @@ int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, con
         RC_TRY(fetch_out(ctx, a.coef, q.coef, (size_t)a.T * M * ncoef));
         RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C));
         if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * C * QTLX_NSTAT));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// rows_out[n_sel][n][4] = the rows the last cnf2_sweep_qtl left in the context at the markers sel: one strided copy per
+// marker.  The rows stay valid.
+int cnf2_qtl_kept_rows(cnf2_ctx* ctx, int n, int n_sel, const int32_t* sel, double* rows_out)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers || ctx->d_org.cap < (size_t)n * ctx->n_markers * 4)
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    if (n_sel < 0 || (n_sel > 0 && (!sel || !rows_out))) return fail(ctx, CNF2_ERR_ARG, "n_sel must not be negative, with sel and rows_out");
+    const int M = ctx->n_markers;
+    for (int j = 0; j < n_sel; j++)
+        if (sel[j] < 0 || sel[j] >= M) return fail(ctx, CNF2_ERR_ARG, "sel must hold marker indices below %d", M);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (int j = 0; j < n_sel; j++)
+        HIP_TRY(ctx, hipMemcpy2DAsync(rows_out + (size_t)j * n * 4, 4 * sizeof(double), ctx->d_org.ptr + (size_t)sel[j] * 4,
+                                      (size_t)M * 4 * sizeof(double), 4 * sizeof(double), (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// The cofactor scan on device rows d_origin[n][M][4]: cnf2_qtlcof.h, cnf2_qtlcof_kernels.hip.  Everything is checked and
+// every buffer is there before the first launch writes.
+int cnf2_qtl_scan_cof(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
+                      const double* cov, int n_cof, const int32_t* cof, const int32_t* excl_lo, const int32_t* excl_hi, int n_perm,
+                      const int32_t* perm, double* lod_out, double* lod_base_out, double* coef_out, int32_t* rank_out,
+                      int32_t* rank_cof_out, double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
+                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
+    if (!lod_base_out || !rank_cof_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if (flags & CNF2_QTL_IMPRINT) return fail(ctx, CNF2_ERR_ARG, "the cofactor scan has no imprinting effect");
+    if (n_cof < 0 || n_cof > QTLCOF_MAXQ || (n_cof > 0 && (!cof || !excl_lo || !excl_hi)))
+        return fail(ctx, CNF2_ERR_ARG, "n_cof must be 0 .. %d, with cof, excl_lo and excl_hi", QTLCOF_MAXQ);
+    const QtlcofDesign ds = qtlcof_design(n_cov, n_cof, (flags & CNF2_QTL_ADDITIVE) != 0);
+    if (ds.w > QTLCOF_MAXW)
+        return fail(ctx, CNF2_ERR_ARG, "the design has %d columns (1 + n_cov + effects x (n_cof + 1)); at most %d", ds.w, QTLCOF_MAXW);
+    const int M = ctx->n_markers, C = ctx->n_chrom, Q = n_cof;
+    std::vector<int32_t> cofstart(Q);
+    for (int k = 0, c = 0; k < Q; k++) {
+        if (cof[k] < 0 || cof[k] >= M || (k > 0 && cof[k] <= cof[k - 1]))
+            return fail(ctx, CNF2_ERR_ARG, "cof must be strictly ascending marker indices below %d", M);
+        while (cof[k] >= ctx->chromstarts[c + 1]) c++;
+        cofstart[k] = ctx->chromstarts[c];
+        if (excl_lo[k] < ctx->chromstarts[c] || excl_hi[k] >= ctx->chromstarts[c + 1] || excl_lo[k] > cof[k] || excl_hi[k] < cof[k])
+            return fail(ctx, CNF2_ERR_ARG, "the range %d .. %d of cofactor %d must lie on its chromosome and contain marker %d", excl_lo[k],
+                        excl_hi[k], k, cof[k]);
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double* d_origin = kept ? ctx->d_org.ptr : origin;
+    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
+    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
+    // the map as the kernels read it: chromstarts, the marker tiles (none straddles a chromosome start), their starts, the
+    // cofactors, the first markers of their chromosomes, and per marker the word of the cofactors left out there
+    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
+    std::vector<int32_t> tstart(1, 0);
+    for (int c = 0; c < C; c++) {
+        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
+        for (int m = f; m < e; m += QTLCOF_TILE) {
+            const int32_t t4[4] = {c, m, std::min(QTLCOF_TILE, e - m), 0};
+            map.insert(map.end(), t4, t4 + 4);
+        }
+        tstart.push_back((int32_t)((map.size() - (size_t)(C + 1)) / 4));
+    }
+    const size_t n_tiles = (map.size() - (size_t)(C + 1)) / 4, o_tstart = map.size();
+    map.insert(map.end(), tstart.begin(), tstart.end());
+    const size_t o_cof = map.size();
+    map.insert(map.end(), cof, cof + Q);
+    const size_t o_cofstart = map.size();
+    map.insert(map.end(), cofstart.begin(), cofstart.end());
+    const size_t o_skipw = map.size();
+    for (int m = 0; m < M; m++) map.push_back((int32_t)qtlcof_skip_word(m, Q, excl_lo, excl_hi));
+    // the column tile: the image under 1 GB, the tile maxima under 256 MB, the caller's cap
+    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
+    rt = std::min(rt, (size_t)4096);
+    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (8 * n_tiles)));
+    rt = std::min(rt, R);
+    if (ctx->qtlcof_columns > 0) rt = std::min(rt, (size_t)ctx->qtlcof_columns);
+
+    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
+    QtlcofParams q;
+    memset(&q, 0, sizeof(q));
+    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
+    RC_TRY(ctx->d_qc_map.ensure(ctx, map.size()));
+    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
+    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
+    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
+    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
+    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
+    RC_TRY(ctx->d_qc_img.ensure(ctx, std::max<size_t>(1, (size_t)a.n * ds.nc)));
+    RC_TRY(ctx->d_qc_yy.ensure(ctx, (size_t)C * rt));
+    if (a.P > 0) RC_TRY(ctx->d_qc_tilemax.ensure(ctx, n_tiles * rt));
+    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_qc_nc, (size_t)C, &q.nc));
+    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_qc_rank, (size_t)M, &q.rank));
+    RC_TRY(stage_out(ctx, dev, rank_cof_out, ctx->d_qc_rank_cof, (size_t)M, &q.rank_cof));
+    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_qc_lod, (size_t)a.T * M, &q.lod));
+    RC_TRY(stage_out(ctx, dev, lod_base_out, ctx->d_qc_lod_base, (size_t)a.T * M, &q.lod_base));
+    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_qc_coef, (size_t)a.T * M * ds.ne, &q.coef));
+    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_qc_rss0, (size_t)a.T * C, &q.rss0));
+    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_qc_pmax, (size_t)a.P * a.T * C, &q.pmax));
+    if (staged) {
+        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
+        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_origin = ctx->d_org;
+    }
+    RC_TRY(qtl_upload(ctx, ctx->d_qc_map, map.data(), map.size()));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.Q = Q;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
+    q.origin = d_origin, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use;
+    q.cs = ctx->d_qc_map, q.tiles = ctx->d_qc_map + (C + 1), q.tile_start = ctx->d_qc_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.cof = ctx->d_qc_map + o_cof, q.cofstart = ctx->d_qc_map + o_cofstart;
+    q.skipw = reinterpret_cast<const uint32_t*>(ctx->d_qc_map.ptr + o_skipw);
+    q.cofimg = ctx->d_qc_img, q.cmask = ctx->d_q_cmask, q.Y = ctx->d_q_Y, q.yy = ctx->d_qc_yy, q.tilemax = ctx->d_qc_tilemax;
+    q.rstride = (int)rt;
+    QtlParams g;                           // what qtl_gather_kernel reads
+    memset(&g, 0, sizeof(g));
+    g.n = a.n, g.T = a.T, g.pheno = ctx->d_q_pheno, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm, g.Y = ctx->d_q_Y, g.rstride = q.rstride;
+
+    launch_qtlcof_mask(q, ctx->stream);
+    launch_qtlcof_gather(q, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = g.r0 = (int)r0;
+        q.rn = g.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(g, ctx->stream);
+        launch_qtlcof_null(q, ctx->stream);
+        launch_qtlcof_markers(q, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtlcof_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dev) {
+        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C));
+        RC_TRY(fetch_out(ctx, a.rank, q.rank, (size_t)M));
+        RC_TRY(fetch_out(ctx, rank_cof_out, q.rank_cof, (size_t)M));
+        RC_TRY(fetch_out(ctx, a.lod, q.lod, (size_t)a.T * M));
+        RC_TRY(fetch_out(ctx, lod_base_out, q.lod_base, (size_t)a.T * M));
+        RC_TRY(fetch_out(ctx, a.coef, q.coef, (size_t)a.T * M * ds.ne));
+        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C));
+        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * C));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;

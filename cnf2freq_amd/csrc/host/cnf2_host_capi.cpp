@@ -10,6 +10,7 @@
 #include "cnf2_qtl_host.h"
 #include "../cnf2_qtl2.h"
 #include "../cnf2_qtlx.h"
+#include "../cnf2_qtlcof.h"
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
 #include "cnf2_remap.h"
@@ -368,6 +369,39 @@ int cnf2h_qtlx_column(int n_cov, int n_int, int additive, int imprint, int j, in
     qtlx_column(ds, j, &e, &z);
     *effect_out = e, *modifier_out = z;
     return ds.w;
+}
+
+// one marker of the cofactor scan from its normal matrix: qtlcof_factor and qtlcof_cell (cnf2_qtlcof.h).  The columns of the
+// cofactors in `skip` are made the zero columns that the kernel feeds for a cofactor left out at the marker
+int cnf2h_qtlcof_marker(const double* gram, int n_col, const double* xty, const double* yy, int n_c, int n_cov, int n_cof,
+                        uint32_t skip, int additive, int32_t* out_rank, double* rss0_out, double* lod_base_out, double* lod_out,
+                        double* coef_out)
+{
+    using namespace cnf2;
+    if (!gram || n_col < 0 || (n_col > 0 && (!xty || !yy || !rss0_out || !lod_base_out || !lod_out || !coef_out)) || n_cov < 0 ||
+        n_cof < 0 || n_cof > QTLCOF_MAXQ || !out_rank)
+        return -2;
+    const QtlcofDesign ds = qtlcof_design(n_cov, n_cof, additive != 0);
+    if (ds.w > QTLCOF_MAXW) return -2;
+    bool zero[QTL2_W];
+    for (int j = 0; j < QTL2_W; j++) {
+        int e, z;
+        qtlcof_column(ds, j, &e, &z);
+        zero[j] = e == QTLX_NONE || (e == QTLCOF_COF && ((skip >> (z / ds.ne)) & 1u));
+    }
+    double G[QTL2_W * QTL2_W];
+    for (int j = 0; j < QTL2_W; j++)
+        for (int k = 0; k < QTL2_W; k++) G[j * QTL2_W + k] = (zero[j] || zero[k]) ? 0.0 : gram[j * QTL2_W + k];
+    const QtlcofFactor f = qtlcof_factor(G, QTL2_W, ds, n_c, ds.w);
+    out_rank[0] = f.usable, out_rank[1] = f.rank_cof, out_rank[2] = f.rank;
+    for (int r = 0; r < n_col; r++) {
+        double beta[QTL2_W];
+        for (int j = 0; j < QTL2_W; j++) beta[j] = zero[j] ? 0.0 : xty[(size_t)r * QTL2_W + j];
+        const QtlcofCell c = qtlcof_cell(G, QTL2_W, ds, f, beta, 1, yy[r], n_c, true);
+        rss0_out[r] = c.rss0, lod_base_out[r] = c.lod_base, lod_out[r] = c.lod;
+        for (int e = 0; e < ds.ne; e++) coef_out[(size_t)r * ds.ne + e] = beta[ds.nx + ds.nc + e];
+    }
+    return 0;
 }
 
 // one (marker, column) fit of the maximum-likelihood scan: qtlem_fit_serial (cnf2_qtlem.h)

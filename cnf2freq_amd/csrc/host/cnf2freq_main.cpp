@@ -8,6 +8,7 @@
 //            [--qtlx F --phenofile P [--qtl-imprint] [--qtl-interactive name,name] [the --qtl-* options]]
 //            [--qtlem F --phenofile P [--qtl-em-iterations N] [--qtl-em-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlbin F --phenofile P [--qtl-binary-iterations N] [--qtl-binary-tol X] [--qtl-imprint] [the --qtl-* options]]
+//            [--qtlcof F --phenofile P --qtl-cofactors i,j,k [--qtl-window X] [the --qtl-* options]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -85,6 +86,12 @@
 // (+ i, with --qtl-imprint) and interaction (+ the products of the effects with the named covariates, which must be among
 // --qtl-covariates and are moved to the front of them) -- after --qtl and --qtl2 where they are given, on the same sweep's
 // rows.  The design takes at most 15 columns.  F is described at qtlx_scan below.
+// --qtlcof F --qtl-cofactors i,j,k [--qtl-window X] (with --phenofile and the --qtl-* options; not flags of the reference):
+// the cofactor scan (cnf2_qtl_scan_cof: composite interval mapping) -- every marker fitted together with the markers i, j, k
+// (map indices from 0, as the other files print them), each of which is left out of the design within X map units of itself
+// (default 0: at its own position only) -- after the other scans where they are given, on the same sweep's rows.  The design
+// takes at most 15 columns: six cofactors less one per two covariates, thirteen with --qtl-additive.  F is described at
+// qtlcof_scan below.
 // --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
@@ -171,6 +178,11 @@ struct Options {
     double      qtlbin_tol = 1e-7;       // --qtl-binary-tol
     bool        qtlbin_extra_set = false; // one of the two above was given
     std::vector<int> qtlbin_trait_cols;  // columns of pheno: the traits whose values are all 0 or 1
+    std::string qtlcof;                  // --qtlcof F: cofactor scan (with --phenofile and the --qtl-* options)
+    std::string qtl_cofactors;           // --qtl-cofactors i,j,k: map indices, from 0
+    double      qtl_window = 0.0;        // --qtl-window X: a cofactor is left out within X map units of itself
+    bool        qtlcof_extra_set = false; // one of the two above was given
+    std::vector<int32_t> qtlcof_cof;     // the cofactors, ascending
     std::vector<int> qtlx_cov_cols;      // columns of pheno: the interactive covariates first, then the others
     int         qtlx_n_int = 0;
     PhenoTable  pheno;                   // P as read (main, before any rank starts)
@@ -269,6 +281,21 @@ static bool parse(int argc, char** argv, Options& o)
                 exit(2);
             }
         }
+        else if (a == "--qtlcof") o.qtlcof = val();
+        else if (a == "--qtl-cofactors") {
+            o.qtl_cofactors    = val();
+            o.qtlcof_extra_set = true;
+        }
+        else if (a == "--qtl-window") {
+            const std::string t = val();
+            char*             end = nullptr;
+            o.qtl_window       = strtod(t.c_str(), &end);
+            o.qtlcof_extra_set = true;
+            if (t.empty() || *end != 0 || !std::isfinite(o.qtl_window)) {
+                fprintf(stderr, "--qtl-window needs a finite number, not \"%s\"\n", t.c_str());
+                exit(2);
+            }
+        }
         else if (a == "--qtlbin") o.qtlbin = val();
         else if (a == "--qtl-binary-iterations") {
             o.qtlbin_iterations = atoi(val().c_str());
@@ -326,6 +353,7 @@ static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
 static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlem_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -422,6 +450,8 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtlem.empty()) qtlem_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty());
     if (world == 1 && !opt.qtlbin.empty())
         qtlbin_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty());
+    if (world == 1 && !opt.qtlcof.empty())
+        qtlcof_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -969,6 +999,231 @@ static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool row
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlbin);
 }
 
+// res[n][T]: the residuals of every phenotype column on the columns X[n][W] and the intercept over the used individuals, 0 for
+// the others -- qtl.null_residuals of the Python package for a null model that holds the cofactors: the columns minus their
+// means, orthogonalised one after the other (twice, for the rounding); a column of which less than QTL_PIVOT of its own
+// length is left depends on those before it and is passed over, as least squares of minimal norm passes over it
+static void qtlcof_null_residuals(int n, int T, const double* pheno, int W, const double* X, const uint8_t* use, double* res)
+{
+    std::vector<int> idx;
+    for (int i = 0; i < n; i++)
+        if (use[i]) idx.push_back(i);
+    const size_t nu = idx.size();
+    std::fill(res, res + (size_t)n * T, 0.0);
+    if (nu == 0) return;
+    auto dot = [&](const std::vector<double>& a, const std::vector<double>& b) {
+        double s = 0.0;
+        for (size_t i = 0; i < nu; i++) s += a[i] * b[i];
+        return s;
+    };
+    auto centre = [&](std::vector<double>& v) {
+        double mean = 0.0;
+        for (double x : v) mean += x;
+        mean /= (double)nu;
+        for (double& x : v) x -= mean;
+    };
+    std::vector<std::vector<double>> basis;
+    for (int k = 0; k < W; k++) {
+        std::vector<double> v(nu);
+        for (size_t i = 0; i < nu; i++) v[i] = X[(size_t)idx[i] * W + k];
+        centre(v);
+        const double raw = dot(v, v);
+        for (int pass = 0; pass < 2; pass++)
+            for (const auto& b : basis) {
+                const double s = dot(b, v);
+                for (size_t i = 0; i < nu; i++) v[i] -= s * b[i];
+            }
+        const double left = dot(v, v);
+        if (!(raw > 0.0) || left < cnf2::QTL_PIVOT * raw) continue;
+        const double inv = 1.0 / sqrt(left);
+        for (double& x : v) x *= inv;
+        basis.push_back(v);
+    }
+    for (int t = 0; t < T; t++) {
+        std::vector<double> v(nu);
+        for (size_t i = 0; i < nu; i++) v[i] = pheno[(size_t)idx[i] * T + t];
+        centre(v);
+        for (int pass = 0; pass < 2; pass++)
+            for (const auto& b : basis) {
+                const double s = dot(b, v);
+                for (size_t i = 0; i < nu; i++) v[i] -= s * b[i];
+            }
+        for (size_t i = 0; i < nu; i++) res[(size_t)idx[i] * T + t] = v[i];
+    }
+}
+
+// --qtlcof after the last round (single GPU), and after the other scans where they are given: the cofactor scan
+// (cnf2_qtl_scan_cof: composite interval mapping) with the markers of --qtl-cofactors as cofactors, each left out of the
+// design within --qtl-window map units of itself, on the rows a cnf2_sweep_qtl left in the context -- theirs, or one of this
+// function's own.  Traits are grouped by their pattern of missing values as for --qtl; with --qtl-permutations K > 0 the
+// residuals of the null model [1, covariates, every cofactor's columns] are permuted, the cofactors' columns coming from the
+// context's rows (cnf2_qtl_kept_rows).  The file holds one table per trait, the tables separated by a blank line: a line
+// "trait" and the name; with permutations a line "threshold", "lod" and the 5 % and 1 % genome-wide thresholds of the
+// conditional LOD over the markers in no cofactor's range; per marker chromosome, position, n, the kept cofactor columns,
+// the LOD of the cofactors against the null model, the rank, the conditional LOD of the marker given the cofactors and its
+// effects a, d (not with --qtl-additive) in the full model, "-" for a dropped one.
+static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    const int Q = (int)opt.qtlcof_cof.size(), NC = opt.qtl_additive ? 1 : 2;
+    // the ranges: the markers of the cofactor's chromosome within --qtl-window of it (qtl.cofactor_windows)
+    std::vector<int32_t> lo(Q), hi(Q);
+    for (int q = 0, c = 0; q < Q; q++) {
+        const int m = opt.qtlcof_cof[q];
+        while (P.chromstarts[c + 1] <= m) c++;
+        lo[q] = hi[q] = m;
+        for (int k = P.chromstarts[c]; k < P.chromstarts[c + 1]; k++)
+            if (fabs(P.pos[k] - P.pos[m]) <= opt.qtl_window) {
+                lo[q] = std::min(lo[q], (int32_t)k);
+                hi[q] = std::max(hi[q], (int32_t)k);
+            }
+    }
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    std::vector<double>  lod((size_t)T * M), lodb((size_t)T * M), coef((size_t)T * M * NC), thr((size_t)T * 2, 0.0);
+    std::vector<int32_t> rank((size_t)T * M), rankc((size_t)T * M), nused((size_t)T * C);
+    std::vector<double>  nullx;            // [N][K + NC Q]: the covariates and the cofactors' columns
+    const int            WN = K + NC * Q;
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M), lb((size_t)Tg * M), cf((size_t)Tg * M * NC), rss((size_t)Tg * C);
+        std::vector<int32_t> rk(M), rkc(M), nu(C);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc;
+        if (!rows_kept) {          // the sweep, with the rows left in the context; its single-locus scan is not reported
+            std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), l1((size_t)Tg * M), c1((size_t)Tg * M * 2), r1((size_t)Tg * C);
+            std::vector<int32_t> k1(M), n1(C);
+            rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                l1.data(), c1.data(), k1.data(), r1.data(), n1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlcof: ") + cnf2_last_error(ctx));
+            rows_kept = true;
+        }
+        rc = cnf2_qtl_scan_cof(ctx, N, nullptr, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, Q, opt.qtlcof_cof.data(), lo.data(),
+                               hi.data(), 0, nullptr, l.data(), lb.data(), cf.data(), rk.data(), rkc.data(), rss.data(), nu.data(), nullptr,
+                               flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlcof: ") + cnf2_last_error(ctx));
+        for (int t = 0; t < Tg; t++) {
+            const size_t from = (size_t)t * M, to = (size_t)tr[t] * M;
+            std::copy(l.begin() + from, l.begin() + from + M, lod.begin() + to);
+            std::copy(lb.begin() + from, lb.begin() + from + M, lodb.begin() + to);
+            std::copy(cf.begin() + from * NC, cf.begin() + (from + M) * NC, coef.begin() + to * NC);
+            std::copy(rk.begin(), rk.end(), rank.begin() + to);
+            std::copy(rkc.begin(), rkc.end(), rankc.begin() + to);
+            std::copy(nu.begin(), nu.end(), nused.begin() + (size_t)tr[t] * C);
+        }
+        if (NP > 0) {
+            if (nullx.empty() && WN > 0) {
+                std::vector<double> rows((size_t)Q * N * 4);
+                if (cnf2_qtl_kept_rows(ctx, N, Q, opt.qtlcof_cof.data(), rows.data()) != CNF2_OK)
+                    throw EngineError(CNF2_ERR_STATE, std::string("--qtlcof: ") + cnf2_last_error(ctx));
+                nullx.assign((size_t)N * WN, 0.0);
+                for (int j = 0; j < N; j++) {
+                    for (int k = 0; k < K; k++) nullx[(size_t)j * WN + k] = cov[(size_t)j * K + k];
+                    for (int q = 0; q < Q; q++) {
+                        const double* o = &rows[((size_t)q * N + j) * 4];
+                        nullx[(size_t)j * WN + K + NC * q] = o[3] - o[0];
+                        if (NC == 2) nullx[(size_t)j * WN + K + NC * q + 1] = o[1] + o[2];
+                    }
+                }
+            }
+            std::vector<int32_t> perm((size_t)NP * N);
+            std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * C);
+            qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+            qtlcof_null_residuals(N, Tg, yg.data(), WN, nullx.data(), u.data(), res.data());
+            rc = cnf2_qtl_scan_cof(ctx, N, nullptr, Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, Q, opt.qtlcof_cof.data(),
+                                   lo.data(), hi.data(), NP, perm.data(), l.data(), lb.data(), cf.data(), rk.data(), rkc.data(), rss.data(),
+                                   nu.data(), pm.data(), flags);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlcof permutations: ") + cnf2_last_error(ctx));
+            for (int t = 0; t < Tg; t++) {
+                std::vector<double> mx(NP, 0.0);
+                for (int p = 0; p < NP; p++)
+                    for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[((size_t)p * Tg + t) * C + c]);
+                thr[(size_t)tr[t] * 2]     = qtl_threshold(mx, 0.05);
+                thr[(size_t)tr[t] * 2 + 1] = qtl_threshold(mx, 0.01);
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtlcof.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlcof);
+    for (int t = 0; t < T; t++) {
+        fprintf(out, "%strait\t%s\n", t ? "\n" : "", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str());
+        if (NP > 0) fprintf(out, "threshold\tlod\t%.5lf\t%.5lf\n", thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
+        for (int c = 0; c < C; c++)
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const size_t at = (size_t)t * M + m;
+                fprintf(out, "%d\t%.5lf\t%d\t%d\t%.5lf\t%d\t%.5lf", c + 1, P.pos[m], (int)nused[(size_t)t * C + c], (int)rankc[at], lodb[at],
+                        (int)rank[at], lod[at]);
+                for (int e = 0; e < NC; e++) {
+                    const double v = coef[at * NC + e];
+                    if (v != v) fprintf(out, "\t-");
+                    else fprintf(out, "\t%.5lf", v);
+                }
+                fprintf(out, "\n");
+            }
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlcof);
+}
+
+// --qtl-cofactors against the map, and the design's width, before anything runs: false with a message
+static bool prepare_qtlcof(Options& opt, const Pedigree& P)
+{
+    const int          M = P.n_markers();
+    std::istringstream ss(opt.qtl_cofactors);
+    for (std::string tok; std::getline(ss, tok, ',');) {
+        if (tok.empty()) continue;
+        char*      end = nullptr;
+        const long m   = strtol(tok.c_str(), &end, 10);
+        if (*end != 0) {
+            fprintf(stderr, "--qtl-cofactors: not a marker index: %s\n", tok.c_str());
+            return false;
+        }
+        if (m < 0 || m >= M) {
+            fprintf(stderr, "--qtl-cofactors: marker %ld is not on the map (0 .. %d)\n", m, M - 1);
+            return false;
+        }
+        if (std::find(opt.qtlcof_cof.begin(), opt.qtlcof_cof.end(), (int32_t)m) != opt.qtlcof_cof.end()) {
+            fprintf(stderr, "--qtl-cofactors: marker %ld is given twice\n", m);
+            return false;
+        }
+        opt.qtlcof_cof.push_back((int32_t)m);
+    }
+    std::sort(opt.qtlcof_cof.begin(), opt.qtlcof_cof.end());
+    if (opt.qtlcof_cof.empty()) {
+        fprintf(stderr, "--qtlcof FILE needs --qtl-cofactors LIST\n");
+        return false;
+    }
+    const int W = 1 + (int)opt.qtl_cov_cols.size() + (opt.qtl_additive ? 1 : 2) * ((int)opt.qtlcof_cof.size() + 1);
+    if (W > cnf2::QTLX_MAXW) {
+        fprintf(stderr, "--qtlcof: the design has %d columns (1 + covariates + effects x (cofactors + 1)); at most %d\n", W, cnf2::QTLX_MAXW);
+        return false;
+    }
+    return true;
+}
+
 // the traits --qtlbin scans: the non-covariate columns whose values, where not missing, are all 0 or 1 (and not all missing)
 static bool prepare_qtlbin(Options& opt)
 {
@@ -1472,7 +1727,27 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtlx FILE needs --phenofile FILE\n");
         return 2;
     }
-    if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() &&
+    if (opt.gpus > 1 && !opt.qtlcof.empty()) {
+        fprintf(stderr, "--qtlcof needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlcof.empty() && opt.qtlcof_extra_set) {
+        fprintf(stderr, "--qtl-cofactors and --qtl-window need --qtlcof FILE\n");
+        return 2;
+    }
+    if (!opt.qtlcof.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlcof FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (!opt.qtlcof.empty() && opt.qtl_cofactors.empty()) {
+        fprintf(stderr, "--qtlcof FILE needs --qtl-cofactors LIST\n");
+        return 2;
+    }
+    if (opt.qtl_window < 0.0) {
+        fprintf(stderr, "--qtl-window must not be negative\n");
+        return 2;
+    }
+    if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() &&
         (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
@@ -1505,8 +1780,10 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-permutations must not be negative\n");
         return 2;
     }
-    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty()) && !prepare_qtl(opt, P))
+    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty()) &&
+        !prepare_qtl(opt, P))
         return 2;
+    if (!opt.qtlcof.empty() && !prepare_qtlcof(opt, P)) return 2;
     if (!opt.qtlbin.empty() && !prepare_qtlbin(opt)) return 2;
     if (!opt.qtlx.empty() && !prepare_qtlx(opt)) return 2;
     if (!opt.qtl2.empty() && opt.qtl_cov_cols.size() > 6) {

@@ -14,7 +14,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
-           "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit"]
+           "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -63,6 +63,7 @@ def load():
         L.cnf2h_qtl2_pair.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
         L.cnf2h_qtlx_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.cnf2h_qtlx_column.argtypes = [i32, i32, i32, i32, i32, vp, vp]
+        L.cnf2h_qtlcof_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, C.c_uint32, i32, vp, vp, vp, vp, vp]
         L.cnf2h_qtlem_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_qtlbin_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
@@ -137,6 +138,26 @@ def qtlx_marker(gram, xty, yy, n_c, n_cov, n_int=0, additive=False, imprint=Fals
     if rc != 0:
         raise RuntimeError("cnf2h_qtlx_marker failed (%d)" % rc)
     return dict(usable=bool(rank[0]), rank=rank[1:].copy(), rss0=rss0, lod=lod, coef=coef)
+
+
+def qtlcof_marker(gram, xty, yy, n_c, n_cov, n_cof, skip=0, additive=False):
+    """cnf2h_qtlcof_marker: the cofactor scan's factorisation and cells (cnf2_qtlcof.h) on a normal matrix gram[16][16] of the
+    design with all n_cof cofactors, xty[R][16] and yy[R]; bit q of `skip` leaves cofactor q out.  A dict: usable, rank_cof,
+    rank, rss0[R], lod_base[R], lod[R], coef[R][ne].  CPU only."""
+    L = load()
+    g = np.ascontiguousarray(gram, np.float64)
+    b = np.ascontiguousarray(xty, np.float64).reshape(-1, 16)
+    y2 = np.ascontiguousarray(yy, np.float64).reshape(-1)
+    if g.shape != (16, 16) or len(y2) != len(b):
+        raise ValueError("gram must be [16][16], xty [R][16] and yy [R]")
+    R = len(b)
+    rank = np.zeros(3, np.int32)
+    rss0, base, lod, coef = np.zeros(R), np.zeros(R), np.zeros(R), np.zeros((R, 1 if additive else 2))
+    rc = L.cnf2h_qtlcof_marker(_p(g), R, _p(b), _p(y2), n_c, n_cov, n_cof, int(skip), int(additive), _p(rank), _p(rss0), _p(base),
+                               _p(lod), _p(coef))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtlcof_marker failed (%d)" % rc)
+    return dict(usable=bool(rank[0]), rank_cof=int(rank[1]), rank=int(rank[2]), rss0=rss0, lod_base=base, lod=lod, coef=coef)
 
 
 def qtlx_columns(n_cov, n_int=0, additive=False, imprint=False):

@@ -15,7 +15,12 @@ The maximum-likelihood scan (Context.qtl_scan_em, cnf2_qtl_scan_em) fits the nor
 (interval mapping) where Haley-Knott regresses on their expectations: scan_em; thresholds and peaks read it as they read scan.
 
 The binary-trait scan (Context.qtl_scan_binary, cnf2_qtl_scan_binary) fits a logistic regression of a 0/1 trait per marker:
-scan_binary, read by thresholds and peaks in the same way."""
+scan_binary, read by thresholds and peaks in the same way.
+
+The cofactor scan (Context.qtl_scan_cof, cnf2_qtl_scan_cof) is composite interval mapping: every marker fitted together with
+the loci found before, each left out inside its own window.  scan_cof with cofactor_windows asks whether there is a further
+QTL, fit_multi (read_multi) reads the multiple-QTL model -- full LOD, drop-one LODs, effects -- off one call, and
+forward_select builds the model a locus at a time against permutation thresholds."""
 import numpy as np
 
 from . import synth
@@ -346,6 +351,166 @@ def scan_binary(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, s
         if permutations:
             out["perm_max"][:, cols] = got["perm_max"]
     return out
+
+
+def cofactor_windows(cof, pos, chromstarts, window=0.0):
+    """(excl_lo[Q], excl_hi[Q]) (int32) for scan_cof: per cofactor the markers of its chromosome within `window` map units
+    of it, as the first and the last of them.  window = 0 gives the cofactor alone (and whatever shares its position)."""
+    cof = np.asarray(cof, np.int64).reshape(-1)
+    pos = np.asarray(pos, np.float64)
+    cs = np.asarray(chromstarts, np.int64)
+    if window < 0:
+        raise ValueError("window must not be negative")
+    if cof.size and (cof.min() < 0 or cof.max() >= len(pos)):
+        raise ValueError("a cofactor is off the map")
+    lo, hi = np.zeros(len(cof), np.int32), np.zeros(len(cof), np.int32)
+    for q, m in enumerate(cof):
+        c = int(np.searchsorted(cs, m, side="right") - 1)
+        near = np.flatnonzero(np.abs(pos[cs[c]:cs[c + 1]] - pos[m]) <= window) + cs[c]
+        lo[q], hi[q] = near.min(), near.max()
+    return lo, hi
+
+
+def cofactor_columns(rows, cof, additive=False):
+    """[n][ne Q] (numpy): the regressors a = o[3] - o[0] and d = o[1] + o[2] (a only with additive) of the markers cof, from
+    the origin rows -- a torch tensor on the device (origin_rows) or an array [n][M][4]"""
+    cof = [int(m) for m in np.asarray(cof, np.int64).reshape(-1)]
+    o = rows[:, cof, :]
+    o = np.asarray(o.cpu().numpy() if hasattr(o, "cpu") else o, np.float64)
+    a, d = o[:, :, 3] - o[:, :, 0], o[:, :, 1] + o[:, :, 2]
+    return a if additive else np.stack([a, d], axis=2).reshape(o.shape[0], -1)
+
+
+def scan_cof(ctx, pheno, cof, excl=None, cov=None, use=None, permutations=0, seed=0, additive=False, rows=None):
+    """The cofactor scan (composite interval mapping) of a whole cross on the context's uploaded pedigree: as scan -- one
+    origin sweep with the rows left on the device (or `rows`, the tensor of origin_rows), per pattern of missing phenotypes
+    (NaN) one observed scan with the pattern's own `use` -- with the markers cof[Q] (strictly ascending) as cofactors, each
+    left out of the design at the markers excl[0][q] .. excl[1][q] (cofactor_windows; None: at its own marker only).  With
+    permutations > 0 one more scan on the permuted Freedman-Lane residuals of the null model [1, cov, every cofactor's
+    columns] (the columns are fetched from the device rows).  A dict: lod[T][M] (conditional on the cofactors), lod_base[T][M],
+    coef[T][M][len(coef_names)], coef_names, rank[T][M], rank_cof[T][M], n_used[T][C], perm_max[P][T][C] or None (the maxima
+    over the markers in no range: thresholds), cof, excl_lo, excl_hi, and candidate[M]: the marker lies in no range."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    cof = np.ascontiguousarray([] if cof is None else cof, np.int32).reshape(-1)
+    lo, hi = (cof.copy(), cof.copy()) if excl is None else (np.ascontiguousarray(e, np.int32).reshape(-1) for e in excl)
+    names = coef_names(0, False, additive)
+    d_o = origin_rows(ctx) if rows is None else rows
+    mk = np.arange(M)
+    candidate = ~np.any((lo[:, None] <= mk[None, :]) & (mk[None, :] <= hi[:, None]), axis=0) if len(cof) else np.ones(M, bool)
+    out = dict(lod=np.zeros((T, M)), lod_base=np.zeros((T, M)), coef=np.full((T, M, len(names)), np.nan), coef_names=names,
+               rank=np.zeros((T, M), np.int32), rank_cof=np.zeros((T, M), np.int32), n_used=np.zeros((T, C), np.int32),
+               perm_max=np.zeros((permutations, T, C)) if permutations else None, cof=cof, excl_lo=lo, excl_hi=hi,
+               candidate=candidate)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    kw = dict(excl=(lo, hi), cov=cov, additive=additive)
+    null_cov = None
+    if permutations:
+        z = None if cov is None else np.asarray(cov, np.float64).reshape(n, -1)
+        parts = ([] if z is None else [z]) + ([cofactor_columns(d_o, cof, additive)] if len(cof) else [])
+        null_cov = np.concatenate(parts, axis=1) if parts else None
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = ctx.qtl_scan_cof_device(n, d_o.data_ptr(), yk, cof, use=u, **kw)
+        for key in ("lod", "lod_base", "coef", "rank", "rank_cof", "n_used"):
+            out[key][cols] = got[key]
+        if permutations:
+            perm = _permutations(n, permutations, seed, use=u)
+            res = null_residuals(yk, null_cov, u)
+            out["perm_max"][:, cols] = ctx.qtl_scan_cof_device(n, d_o.data_ptr(), res, cof, use=u, perm=perm, **kw)["perm_max"]
+    return out
+
+
+def read_multi(out, loci, chromstarts):
+    """A multiple-QTL fit read off a cofactor scan `out` (scan_cof's dict, or arrays of its shapes) that had `loci` as its
+    cofactors, each left out at its own marker only.  At a cofactor's marker the tested marker stands in for it, so per trait:
+    lod_full[T] = lod_base + lod there (the same at every locus; the first is reported), drop_one[T][Q] = lod at locus q,
+    coef[T][Q][ne] its effects in the full model, n[T][Q] the individuals of its chromosome's fit, and the shares of the
+    phenotypic variance 1 - 10^(-2 LOD / n): var_full[T], var_drop[T][Q].  The loci are reported in the order given."""
+    loci = np.asarray(loci, np.int64).reshape(-1)
+    if loci.size == 0:
+        raise ValueError("a multiple-QTL fit needs at least one locus")
+    cs = np.asarray(chromstarts, np.int64)
+    lod, base, coef = np.asarray(out["lod"], np.float64), np.asarray(out["lod_base"], np.float64), np.asarray(out["coef"], np.float64)
+    n_used = np.asarray(out["n_used"])
+    n_used = n_used[None, :] if n_used.ndim == 1 else n_used
+    chrom = np.searchsorted(cs, loci, side="right") - 1
+    nq = np.maximum(n_used[:, chrom], 1).astype(np.float64)
+    drop = lod[:, loci]
+    full = (base[:, loci] + drop)[:, 0]
+    share = lambda l, k: 1.0 - 10.0 ** (-2.0 * l / k)
+    return dict(loci=loci.copy(), lod_full=full, drop_one=drop, coef=coef[:, loci], n=n_used[:, chrom],
+                var_full=share(full, nq[:, 0]), var_drop=share(drop, nq))
+
+
+def fit_multi(ctx, pheno, loci, cov=None, use=None, additive=False, rows=None, scanner=None, chromstarts=None):
+    """The multiple-QTL model of the markers `loci` (any order, no repeats), from one scan_cof call with every locus left
+    out at its own marker only: read_multi's dict -- per trait the full model's LOD, per locus the drop-one LOD, the effects
+    and the shares of variance.  scanner and chromstarts: what forward_select takes."""
+    loci = np.asarray(loci, np.int64).reshape(-1)
+    srt = np.sort(loci).astype(np.int32)
+    if scanner is None:
+        scanner = _cof_scanner(ctx, pheno, cov, use, additive, rows)
+    return read_multi(scanner(srt, (srt, srt), 0, 0), loci, ctx.chromstarts if chromstarts is None else chromstarts)
+
+
+def _cof_scanner(ctx, pheno, cov, use, additive, rows):
+    """scanner(cof, excl, permutations, seed) -> scan_cof's dict, on one set of origin rows for every call"""
+    d_o = origin_rows(ctx) if rows is None else rows
+    return lambda cof, excl, permutations, seed: scan_cof(ctx, pheno, cof, excl=excl, cov=cov, use=use, permutations=permutations,
+                                                          seed=seed, additive=additive, rows=d_o)
+
+
+def forward_select(ctx, pheno, max_loci, window, pos, alpha=0.05, permutations=100, seed=0, cov=None, use=None, additive=False,
+                   rows=None, scanner=None, chromstarts=None):
+    """Forward selection of QTL for ONE trait (pheno[n] or [n][1]).  Each step is a scan_cof with the loci found so far as
+    cofactors, left out within `window` map units of themselves (cofactor_windows on pos), and `permutations` permutations;
+    the candidates are the markers in no range.  The best candidate (the first wins a tie) joins the model when its
+    conditional LOD exceeds that step's genome-wide threshold, thresholds(perm_max, (alpha,)); otherwise, or with max_loci
+    loci, or when one more locus would make the design wider than 15 columns, the selection stops.  One origin sweep (or
+    `rows`) serves every step.  A dict: loci (in order of entry), lod and threshold (their entry LODs and thresholds),
+    stopped (marker, lod, threshold of the candidate that did not enter; None when none was looked at) and fit (fit_multi
+    of the loci; None without loci).  scanner(cof, excl, permutations, seed) replaces scan_cof (a reference of the tests)."""
+    y = np.asarray(pheno, np.float64)
+    if y.ndim == 2 and y.shape[1] != 1:
+        raise ValueError("forward_select works on one trait")
+    if permutations < 1:
+        raise ValueError("forward_select needs permutations for its thresholds")
+    cs = np.asarray(ctx.chromstarts if chromstarts is None else chromstarts, np.int64)
+    pos = np.asarray(pos, np.float64)
+    K = 0 if cov is None else np.asarray(cov).reshape(len(y), -1).shape[1]
+    ne = 1 if additive else 2
+    if scanner is None:
+        scanner = _cof_scanner(ctx, y, cov, use, additive, rows)
+    loci, lods, thrs, stopped = [], [], [], None
+    while len(loci) < max_loci and 1 + K + ne * (len(loci) + 2) <= 15:
+        cof = np.sort(np.asarray(loci, np.int32))
+        out = scanner(cof, cofactor_windows(cof, pos, cs, window), permutations, seed)
+        cand = np.flatnonzero(out["candidate"])
+        if cand.size == 0:
+            break
+        best = int(cand[np.argmax(out["lod"][0, cand])])
+        lod, thr = float(out["lod"][0, best]), float(thresholds(out["perm_max"], (alpha,))["genome"][0, 0])
+        if not lod > thr:
+            stopped = dict(marker=best, lod=lod, threshold=thr)
+            break
+        loci.append(best)
+        lods.append(lod)
+        thrs.append(thr)
+    fit = None
+    if loci:
+        srt = np.sort(np.asarray(loci, np.int32))
+        fit = read_multi(scanner(srt, (srt, srt), 0, 0), loci, cs)
+    return dict(loci=loci, lod=lods, threshold=thrs, stopped=stopped, fit=fit)
 
 
 THRESHOLDSX_KEYS = ("lod0", "lod1", "lod2", "imprint", "interaction")

@@ -620,6 +620,66 @@ int cnf2_qtl_scanx(cnf2_ctx *ctx, int n, const double *origin, int n_traits, con
                    uint32_t flags);
 int cnf2_set_qtlx_columns(cnf2_ctx *ctx, int cap);
 
+/* Cofactor scan: composite interval mapping.  Is there a further QTL given the ones already found, and what does the
+ * multiple-QTL model say about each of them?  Every marker is fitted together with the cofactors -- loci found before --
+ * and each cofactor is left out of the design while the scan passes through its own window.  One definition for this
+ * header, cnf2freq_amd/csrc/cnf2_qtlcof.h (host and device), the kernels and tests/qtlcof_reference.py.
+ * origin, pheno, use, cov, perm and the columns R = T (1 + P) are cnf2_qtl_scan's.  n_cof = Q >= 0 and cof[Q], excl_lo[Q],
+ * excl_hi[Q] (int32, host; NULL only with Q = 0): cof holds marker indices, strictly ascending; cofactor q is left out of the
+ * design at the markers excl_lo[q] <= m <= excl_hi[q].  The range must lie on the cofactor's chromosome and contain cof[q];
+ * ranges of different cofactors may overlap.
+ *   effects   per locus a = o[3] - o[0] and d = o[1] + o[2] (a only with CNF2_QTL_ADDITIVE): ne = 1 or 2, for the cofactors
+ *             and the tested marker alike.  The additive model is linear in each locus's indicators, so the marginal origin
+ *             rows are its exact Haley-Knott regressors: a cofactor on the tested marker's own chromosome is exact
+ *   width     W = 1 + K + ne Q + ne must be at most 15 (cnf2_qtl_scanx's bound, for its reason): six loci with dominance,
+ *             thirteen in the additive model
+ *   mask      c_i = use[i], and i is not skipped on the tested chromosome, and i is not skipped on the chromosome of any
+ *             cofactor, left out here or not: n_c and the mask depend on the chromosome only
+ *   design    X0 = [c, c z_1 .. c z_K], then the cofactors' columns in the order of cof with the left-out ones skipped, then
+ *             the marker's a, d
+ * One factorisation: the normal matrix of [design | y] under the mask, one sequential Cholesky in that column order; a column
+ * of X0 needs a positive pivot, every later column is dropped (pivot 0) when its raw diagonal is 0 or its pivot is below 1e-8
+ * times its raw diagonal.  With w = L^-1 X'y over the kept columns and LOD(s) = (n_c / 2) log10(RSS0 / (RSS0 - s)), s clamped
+ * to [0, RSS0 (1 - 2^-52)]:
+ *   RSS0 = sum c y^2 - sum_{X0} w^2
+ *   lod_base[m] = LOD(sum of w^2 over the kept cofactor columns): the cofactors against X0
+ *   lod[m]      = LOD(sum of w^2 over the kept cofactor and marker columns) - lod_base[m]: the CONDITIONAL LOD of the marker's
+ *                 kept effects against X0 + cofactors; finite, not negative, exactly 0 where rank[m] = 0
+ *   rank[m] = the kept effects of the marker, rank_cof[m] = the kept cofactor columns; both depend on the design only
+ *   coef[t][m][ne] = the marker's effects in the full model, NaN for a dropped one
+ * A chromosome with n_c < W + 1 (W the full width, whatever is left out), or whose X0 has no Cholesky factor, is not scanned:
+ * ranks 0, LODs 0, coef NaN, rss0 0.  A column with RSS0 <= 0 gives LODs 0 and coef NaN.
+ * Reading a multiple-QTL fit off the scan: at m = cof[q] the marker stands in for cofactor q.  With ranges that leave out
+ * only the cofactor itself at its own marker (excl_lo[q] = excl_hi[q] = cof[q]), lod[cof[q]] is the drop-one LOD of locus q in
+ * the Q-locus model, lod_base + lod there is the full model's LOD (the same at every cofactor) and coef there holds locus
+ * q's effects in it.
+ *   lod_out [T][M]   lod_base_out [T][M]   coef_out [T][M][ne]   rank_out [M] (int32)   rank_cof_out [M] (int32)
+ *   rss0_out [T][C]  n_used_out [C] (int32) n_c
+ *   perm_max_out [P][T][C]  per permutation, trait and chromosome the largest conditional LOD over the chromosome's markers
+ *                           that lie in NO exclusion range (inside a range the value is a drop-one statistic of a known
+ *                           locus, not a candidate); 0 where a chromosome has no such marker; NULL exactly when P = 0
+ * CNF2_QTL_ADDITIVE, CNF2_QTL_ORIGIN_DEVICE (also with origin NULL: the rows the last cnf2_sweep_qtl left in the context,
+ * CNF2_ERR_STATE as for cnf2_qtl_scan) and CNF2_OUT_DEVICE act as for cnf2_qtl_scanx: device rows are read in place and the
+ * call leaves the context's rows valid.  Everything cnf2_qtl_scan refuses, W > 15, CNF2_QTL_IMPRINT, a cof that is unsorted,
+ * repeated or off the map, and a range that leaves its chromosome or misses its cofactor return CNF2_ERR_ARG and write
+ * nothing; an allocation that fails returns CNF2_ERR_NOMEM before anything is written.
+ * Launches: the masks; the cofactor columns [n][ne Q], once; per tile of columns the column image (as cnf2_qtl_scan), per
+ * chromosome n_c, sum c y^2 and RSS0, and the marker kernel, cnf2_qtl_scanx's batched small SYRK on the f64 matrix cores with
+ * this design -- a left-out cofactor's columns are fed as exact zeros, so the column order is the same at every marker; a
+ * finish kernel reduces the permutations' maxima per chromosome.  No atomics and no split of the individuals: a call gives
+ * the same bits every time, for every column cap (cnf2_set_qtlcof_columns, 0 = no cap; the tile keeps the image under 1 GB
+ * and the maxima under 256 MB), from host or device rows and into host or device outputs. */
+int cnf2_qtl_scan_cof(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                      int n_cov, const double *cov, int n_cof, const int32_t *cof, const int32_t *excl_lo,
+                      const int32_t *excl_hi, int n_perm, const int32_t *perm, double *lod_out, double *lod_base_out,
+                      double *coef_out, int32_t *rank_out, int32_t *rank_cof_out, double *rss0_out, int32_t *n_used_out,
+                      double *perm_max_out, uint32_t flags);
+int cnf2_set_qtlcof_columns(cnf2_ctx *ctx, int cap);
+/* rows_out[n_sel][n][4] (host) = the origin rows that the last cnf2_sweep_qtl left in the context, at the markers sel[n_sel]:
+ * what a caller needs of them on the host, e.g. the cofactors' columns for the null model whose residuals a permutation test
+ * of the cofactor scan permutes.  CNF2_ERR_STATE where the context holds no such rows of n individuals; the rows stay valid. */
+int cnf2_qtl_kept_rows(cnf2_ctx *ctx, int n, int n_sel, const int32_t *sel, double *rows_out);
+
 /* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
  * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;
  * where a row is soft it leaves the within-individual genotype variance in the residual.  One definition for this header,

@@ -158,6 +158,17 @@ int cnf2h_qtlx_marker(const double *gram, int n_col, const double *xty, const do
                       int additive, int imprint, int32_t *out_rank, double *rss0_out, double *lod_out, double *coef_out);
 int cnf2h_qtlx_column(int n_cov, int n_int, int additive, int imprint, int j, int32_t *effect_out, int32_t *modifier_out);
 
+/* The small algebra of the cofactor scan (cnf2_qtl_scan_cof of cnf2hip.h; cnf2freq_amd/csrc/cnf2_qtlcof.h) on the host, as
+ * its tests use it: gram[16][16] is the normal matrix of one marker's design with ALL n_cof cofactors in the model's column
+ * order -- X0, the cofactors' a, d in the order of cof, the marker's a, d (zero past its width; only the lower triangle is
+ * read) --, xty[n_col][16] and yy[n_col] the columns' X'y and sum c y^2.  Bit q of `skip` leaves cofactor q out: its columns
+ * become the zero columns the kernel feeds there.  Factors once with the rank rule, then per column the cell: out_rank[3] =
+ * usable, rank_cof, rank; rss0_out, lod_base_out, lod_out [n_col], coef_out [n_col][ne].  -2: a bad argument or a design
+ * wider than 15 columns. */
+int cnf2h_qtlcof_marker(const double *gram, int n_col, const double *xty, const double *yy, int n_c, int n_cov, int n_cof,
+                        uint32_t skip, int additive, int32_t *out_rank, double *rss0_out, double *lod_base_out,
+                        double *lod_out, double *coef_out);
+
 /* One (marker, phenotype column) fit of the maximum-likelihood scan (cnf2_qtl_scan_em of cnf2hip.h) on the host, by the
  * functions of cnf2freq_amd/csrc/cnf2_qtlem.h that the kernels use, the individuals in ascending order: origin[n][4] the
  * marker's rows, y[n], cov[n][n_cov], c[n] the chromosome's mask.  lod_out, coef_out [ne], sigma2_out, iters_out, status_out,
