@@ -1164,7 +1164,10 @@ struct RawRec {
 __device__ __forceinline__ int clamp_marker(int m, int lo_m, int hi_m) { return m < lo_m ? lo_m : (m > hi_m ? hi_m : m); }
 __device__ __forceinline__ uint8_t load_root_allele(const KernelParams& p, const FastCtx& c, int m0, int lo_m, int hi_m)
 {
-    return p.allele8[(size_t)c.row_root * p.n_markers + clamp_marker(m0 + c.mi, lo_m, hi_m)];
+    // (device memory, said so: a caller may hand the base over through a register the compiler cannot see through, and a flat
+    // load counts in lgkmcnt as well, where the LDS reads behind it would wait for it)
+    const __attribute__((address_space(1))) uint8_t* a8 = (const __attribute__((address_space(1))) uint8_t*)p.allele8;
+    return a8[(size_t)c.row_root * p.n_markers + clamp_marker(m0 + c.mi, lo_m, hi_m)];
 }
 // ap: load_root_allele of the same tile; rec_row: line * n_markers of this lane's line
 template <int TQ_SHIFT>
@@ -2596,10 +2599,10 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
         for (int t = 0; t < ntile; t++) {
             const int m0 = first + t * 2;
             produce_row_rec<false>(cp, tab, m0 + pmt <= last, rraw);
-            if (t + 1 < ntile) {
-                load_rec<0>(pq, cp, rec_row, m0 + 2 + moff, first, last, ap_next, &rraw);
-                ap_next = load_root_allele(pq, cp, m0 + 4 + moff, first, last);
-            }
+            // (unconditional: behind a window's end the clamps reload its last tile.  Under a condition the loaded values reach
+            // the carried registers through a copy, and that copy waits for every load right here)
+            load_rec<0>(pq, cp, rec_row, m0 + 2 + moff, first, last, ap_next, &rraw);
+            ap_next = load_root_allele(pq, cp, m0 + 4 + moff, first, last);
             wave_lds_fence();
             fwd_step(even_t(), myrow0, m0);
             if (m0 < last) fwd_step(odd_t(), myrow1, m0 + 1);
@@ -2760,10 +2763,8 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
         for (int t = ntile - 1; t >= 0; t--) {
             const int m0 = first + t * 2;
             produce_row_rec<true>(cp, tab, m0 + pmt <= last, rraw);
-            if (t > 0) {
-                load_rec<-1>(pq, cp, rec_row, m0 - 2 + moff, first, last, ap_next, &rraw);
-                ap_next = load_root_allele(pq, cp, m0 - 4 + moff, first, last);
-            }
+            load_rec<-1>(pq, cp, rec_row, m0 - 2 + moff, first, last, ap_next, &rraw);      // (unconditional, as forward)
+            ap_next = load_root_allele(pq, cp, m0 - 4 + moff, first, last);
             wave_lds_fence();
             if (m0 < last) {
                 marker(odd_t(), myrow1, m0 + 1);
@@ -2967,10 +2968,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         ap_next = load_root_allele(pq, cp, first + 1 + moff, first, last);
         for (int m = first; m <= last; m++) {
             produce_row_rec<false>(cp, tab, true, rraw);
-            if (m < last) {
-                load_rec<0>(pq, cp, rec_row, m + 1 + moff, first, last, ap_next, &rraw);
-                ap_next = load_root_allele(pq, cp, m + 2 + moff, first, last);
-            }
+            // (unconditional, as in fb_unipack_kernel: no copy, so no wait, between these loads and the next marker's producer)
+            load_rec<0>(pq, cp, rec_row, m + 1 + moff, first, last, ap_next, &rraw);
+            ap_next = load_root_allele(pq, cp, m + 2 + moff, first, last);
             wave_lds_fence();
             if ((m - first) & 1) fwd_step(odd_t(), myrow, m);
             else fwd_step(even_t(), myrow, m);
@@ -3019,20 +3019,27 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         const double xm  = any_alive ? 1.0 / T : 0.0;
         const int    xe  = -emax;
         const bool   chain_on = alive && !(tmine * 2.3538526683701998e17 < T);        // factor - fs > 40: cnF2freq.cpp:5420-5421
-        // S.am holds what the next marker starts from: alpha x emission of the pair's even marker in front of an odd marker,
-        // alpha in front of an even one; each is asked for one marker ahead
-        auto load_value = [&](int idx, int off) {
-            const d2v v = __builtin_nontemporal_load((const d2v*)(spill + (size_t)idx * ROW + off + uoff));
-            S.am[0]     = v.x;
-            S.am[1]     = v.y;
+        // S.am holds what a marker starts from: alpha x emission of the pair's even marker at an odd marker, alpha at an even
+        // one, and S.inv_* the pair's two reciprocals.  The marker loop asks for them one marker ahead, at one place outside the
+        // odd / even branch, into nx_*: it takes them over at the top of the next iteration, the one place that waits for them
+        // (assigned inside the branches they were awaited at each branch's end, behind the marker that asked for them)
+        double nx_am[NR], nx_inv_even, nx_inv_odd;
+        auto ask_spill = [&](int mn) {          // for marker first + mn (mn = -1 below the window: its first pair again)
+            const double* sp = spill + (size_t)(mn < 0 ? 0 : mn >> 1) * ROW;
+            const d2v     v  = __builtin_nontemporal_load((const d2v*)(sp + ((mn & 1) ? UP8_SPILL_EMIT : 0) + uoff));
+            nx_am[0]         = v.x;
+            nx_am[1]         = v.y;
+            const double2 iv = *(const double2*)(sp + ioff);
+            nx_inv_even      = iv.x;
+            nx_inv_odd       = iv.y;
         };
-        auto load_inv = [&](int idx) {
-            const double2 iv = *(const double2*)(spill + (size_t)idx * ROW + ioff);
-            S.inv_even       = iv.x;
-            S.inv_odd        = iv.y;
+        auto take_spill = [&]() {
+#pragma unroll
+            for (int j = 0; j < NR; j++) S.am[j] = nx_am[j];
+            S.inv_even = nx_inv_even;
+            S.inv_odd  = nx_inv_odd;
         };
-        load_value((last - first) >> 1, ((last - first) & 1) ? UP8_SPILL_EMIT : 0);
-        load_inv((last - first) >> 1);
+        ask_spill(last - first);
 
         auto marker = [&](auto odd_tag, double* row, int m) {
             constexpr bool ODD = decltype(odd_tag)::value;
@@ -3043,8 +3050,6 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
             if (ODD) {
 #pragma unroll
                 for (int j = 0; j < NR; j++) wj[j] = S.am[j];
-                asm volatile("" : "+v"(wj[0]), "+v"(wj[1]) : : "memory");
-                load_value(ml >> 1, 0);
                 transition_uniform(wj, r_m.x, r_m.y);
 #pragma unroll
                 for (int j = 0; j < NR; j++) wj[j] *= S.b[j];
@@ -3053,10 +3058,6 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
 #pragma unroll
                 for (int j = 0; j < NR; j++) wj[j] = S.am[j] * S.b[j];
                 inv_m = S.inv_even;
-                asm volatile("" : "+v"(wj[0]), "+v"(wj[1]), "+v"(inv_m) : : "memory");
-                const int idx = (ml >> 1) - 1;
-                load_value(idx < 0 ? 0 : idx, UP8_SPILL_EMIT);
-                load_inv(idx < 0 ? 0 : idx);
             }
             if (!ODD || m == last) {
                 int ex;
@@ -3134,11 +3135,11 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         // epilogue role: row mi2 = job, chain sub
         const int mi2 = lane >> 3, sub = lane & 7;
         for (int m = last; m >= first; m--) {
+            take_spill();
+            ask_spill(m - first - 1);
             produce_row_rec<true>(cp, tab, true, rraw);
-            if (m > first) {
-                load_rec<-1>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);
-                ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
-            }
+            load_rec<-1>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);       // (unconditional, as forward)
+            ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
             wave_lds_fence();
             if ((m - first) & 1) marker(odd_t(), myrow, m);
             else marker(even_t(), myrow, m);
