@@ -28,6 +28,7 @@ FLUSH_TINY = 1 << 20              # cnf2_sweep: general kernel with adjustprobs'
 ALL_STATES = 1 << 21              # windows of crosses of inbred lines through the fast kernel's ordinary instantiation (A/B, cross-check)
 QTL_ADDITIVE = 1 << 22            # cnf2_qtl_scan / cnf2_sweep_qtl: the dominance column is always dropped
 QTL_ORIGIN_DEVICE = 1 << 23       # cnf2_qtl_scan: the origin rows are a device pointer
+QTL_REG_DEVICE = 1 << 28          # cnf2_qtl_scan_cols: the regressors are a device pointer
 QTL_IMPRINT = 1 << 25             # cnf2_qtl_scanx: the design gets the imprinting effect i = o[1] - o[2]
 NO_UNIFORM_PACK = 1 << 26         # crosses of inbred lines: one window to a wave, not four windows of a chromosome (A/B, cross-check)
 NO_UNIFORM_PACK8 = 1 << 27        # crosses of inbred lines: packed windows four to a wave only, not eight windows of a chromosome (A/B, cross-check)
@@ -53,6 +54,7 @@ SYMBOLS = [
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
     "cnf2_qtl_scan_cof", "cnf2_set_qtlcof_columns", "cnf2_qtl_kept_rows",
+    "cnf2_kinship_sums", "cnf2_qtl_scan_cols",
 ]
 
 
@@ -134,6 +136,8 @@ def load():
                                         vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlcof_columns.argtypes = [vp, i32]
         L.cnf2_qtl_kept_rows.argtypes = [vp, i32, i32, vp, vp]
+        L.cnf2_kinship_sums.argtypes = [vp, i32, vp, i32, i32, vp, vp, C.c_uint32]
+        L.cnf2_qtl_scan_cols.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_em.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, C.c_double,
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlem_columns.argtypes = [vp, i32]
@@ -692,6 +696,72 @@ class Context:
                                         opt(use), K, opt(cov), P, opt(perm), C.c_void_p(d_lod), C.c_void_p(d_coef),
                                         C.c_void_p(d_rank), C.c_void_p(d_rss0), C.c_void_p(d_n_used),
                                         C.c_void_p(d_perm_max) if d_perm_max else None, flags | OUT_DEVICE), "cnf2_sweep_qtl")
+
+    # -- kinship sums and the column scan (the two halves of a mixed-model scan: cnf2freq_amd/qtl.py) ----
+    def kinship_sums(self, origin, chrom_begin=0, chrom_end=None):
+        """cnf2_kinship_sums on host rows origin[n][M][4]: (sum[n][n], markers) with sum[i][j] the sum of a_i(m) a_j(m),
+        a = origin[3] - origin[0], over the markers of the chromosomes chrom_begin .. chrom_end-1 (None: to the last).  The
+        kinship is K = (1 + sum / markers) / 2; leaving a chromosome out is a subtraction of sums (qtl.kinship)."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        n = origin.shape[0]
+        out, cnt = np.zeros((n, n)), np.zeros(1, np.int32)
+        chrom_end = self.n_chrom if chrom_end is None else chrom_end
+        self._chk(self.L.cnf2_kinship_sums(self.h, n, _p(origin), chrom_begin, chrom_end, _p(out), _p(cnt), 0), "cnf2_kinship_sums")
+        return out, int(cnt[0])
+
+    def kinship_sums_device(self, n, d_origin, chrom_begin=0, chrom_end=None, d_sum=None, d_n_markers=None):
+        """The same on device rows (d_origin: an int, the pointer of n x M x 4 doubles aligned to 16 bytes; None: the rows this
+        context's last sweep_qtl left in it), read in place.  With d_sum and d_n_markers (ints: n x n doubles, one int32) the
+        outputs are device memory and the call returns None; else (sum[n][n], markers) as host values."""
+        chrom_end = self.n_chrom if chrom_end is None else chrom_end
+        origin = C.c_void_p(d_origin) if d_origin else None
+        if d_sum:
+            self._chk(self.L.cnf2_kinship_sums(self.h, n, origin, chrom_begin, chrom_end, C.c_void_p(d_sum), C.c_void_p(d_n_markers),
+                                               QTL_ORIGIN_DEVICE | OUT_DEVICE), "cnf2_kinship_sums")
+            return None
+        out, cnt = np.zeros((n, n)), np.zeros(1, np.int32)
+        self._chk(self.L.cnf2_kinship_sums(self.h, n, origin, chrom_begin, chrom_end, _p(out), _p(cnt), QTL_ORIGIN_DEVICE),
+                  "cnf2_kinship_sums")
+        return out, int(cnt[0])
+
+    def _qtl_cols_call(self, n, M, ne, reg_ptr, x0, pheno, scale, perm, flags, out=None):
+        """cnf2_qtl_scan_cols with host outputs (out = None: new arrays) on the regressors behind reg_ptr"""
+        pheno, _, _, perm = self._qtl_inputs(n, pheno, None, None, perm)
+        x0 = np.ascontiguousarray(x0, np.float64)
+        x0 = x0[:, None] if x0.ndim == 1 else x0
+        if x0.ndim != 2 or x0.shape[0] != n:
+            raise ValueError("x0 must be [n][nx]")
+        if scale is not None:
+            scale = np.ascontiguousarray(scale, np.float64)
+            if scale.shape != (n,):
+                raise ValueError("scale must be [n]")
+        T, P = pheno.shape[1], 0 if perm is None else perm.shape[0]
+        o = dict(lod=np.zeros((T, M)), coef=np.zeros((T, M, 2)), rank=np.zeros(M, np.int32), rss0=np.zeros(T),
+                 perm_max=np.zeros((P, T)) if P else None) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_qtl_scan_cols(self.h, n, M, ne, reg_ptr, opt(scale), x0.shape[1], _p(x0), T, _p(pheno), P, opt(perm),
+                                            _p(o["lod"]), _p(o["coef"]), _p(o["rank"]), _p(o["rss0"]), opt(o["perm_max"]), flags),
+                  "cnf2_qtl_scan_cols")
+        return o
+
+    def qtl_scan_cols(self, reg, x0, pheno, scale=None, perm=None, out=None):
+        """cnf2_qtl_scan_cols on host regressors reg[n][M][ne] (ne = 1 or 2): least squares of every column of pheno[n][T],
+        observed and permuted by perm[P][n], on [x0, scale_i reg(i, m)] at every marker of the block.  x0[n][nx] is the whole
+        null design -- no intercept is added and nothing is centred -- and scale[n] (None: ones) multiplies the regressor rows
+        on the fly.  A dict: lod[T][M], coef[T][M][2] (NaN for a dropped column), rank[M], rss0[T], perm_max[P][T] (None
+        without permutations).  The model: include/cnf2hip.h; qtl.scan_lmm uses it on rotated columns."""
+        reg = np.ascontiguousarray(reg, np.float64)
+        reg = reg[:, :, None] if reg.ndim == 2 else reg
+        if reg.ndim != 3 or reg.shape[2] not in (1, 2):
+            raise ValueError("reg must be [n][M][ne] with ne = 1 or 2")
+        return self._qtl_cols_call(reg.shape[0], reg.shape[1], reg.shape[2], _p(reg), x0, pheno, scale, perm, 0, out)
+
+    def qtl_scan_cols_device(self, n, n_mark, ne, d_reg, x0, pheno, scale=None, perm=None):
+        """The same on device regressors (d_reg: an int, the pointer of n x n_mark x ne doubles aligned to 16 bytes), read in
+        place.  x0, pheno, scale, perm and the outputs are host arrays."""
+        return self._qtl_cols_call(n, n_mark, ne, C.c_void_p(d_reg), x0, pheno, scale, perm, QTL_REG_DEVICE)
 
     # -- two-QTL pair scan ---------------------------------------------------------
     QTL2_KEYS = ("lod_add", "lod_full", "rank_add", "rank_full", "rss0", "n_used", "perm_max")

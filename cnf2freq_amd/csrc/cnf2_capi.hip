@@ -26,6 +26,8 @@
 #include "cnf2_qtlcof.h"
 #include "cnf2_qtlem.h"
 #include "cnf2_qtlbin.h"
+#include "cnf2_kinship.h"
+#include "cnf2_qtlcols.h"
 
 using namespace cnf2;
 
@@ -204,6 +206,15 @@ struct cnf2_ctx {
     int             qtlbin_columns = 0;
     DevBuf<double>  d_qb_null, d_qb_tilemax, d_qb_lod, d_qb_coef, d_qb_ll0, d_qb_pmax;
     DevBuf<int32_t> d_qb_map, d_qb_keep, d_qb_scan, d_qb_nc, d_qb_rank, d_qb_iters, d_qb_status, d_qb_ones;   // d_qb_map: as d_qe_map
+
+    // kinship sums (cnf2_kinship_sums): the image a[m_pad][n_pad], the chunks' partial sums of a split range, the staged sum
+    DevBuf<double>  d_kin_image, d_kin_part, d_kin_sum;
+
+    // column scan (cnf2_qtl_scan_cols): staged regressors and inputs, the factor, the marker records, the column image of a
+    // tile, its null fit, the tile maxima, staged outputs; the column cap is the single scan's (cnf2_set_qtl_columns)
+    DevBuf<double>  d_ql_reg, d_ql_scale, d_ql_x0, d_ql_pheno, d_ql_chol, d_ql_mk, d_ql_Y, d_ql_null, d_ql_tilemax;
+    DevBuf<double>  d_ql_lod, d_ql_coef, d_ql_rss0, d_ql_pmax;
+    DevBuf<int32_t> d_ql_perm, d_ql_rank;
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -1777,6 +1788,172 @@ int cnf2_sweep_qtl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_ou
     ctx->qtl_rows_n = a.n;
     ctx->qtl_rows_m = ctx->n_markers;
     return qtl_scan_impl(ctx, ctx->d_org, a, mask, flags);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Kinship sums (cnf2_kinship.h, cnf2_kinship_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+int cnf2_kinship_sums(cnf2_ctx* ctx, int n, const double* origin, int chrom_begin, int chrom_end, double* sum_out,
+                      int32_t* n_markers_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (n < 1 || n > 46340) return fail(ctx, CNF2_ERR_ARG, "n must be 1 .. 46340");
+    if (chrom_begin < 0 || chrom_end > ctx->n_chrom || chrom_begin >= chrom_end)
+        return fail(ctx, CNF2_ERR_ARG, "the chromosome range must be non-empty and within 0 .. %d", ctx->n_chrom);
+    if (!sum_out || !n_markers_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
+                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool    dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const double* d_origin = kept ? ctx->d_org.ptr : origin;
+    if (flags & CNF2_QTL_ORIGIN_DEVICE) {
+        if ((uintptr_t)d_origin & 15) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+    } else {
+        const size_t cnt = (size_t)n * ctx->n_markers * 4;
+        ctx->qtl_rows_n = 0;
+        RC_TRY(ctx->d_org.ensure(ctx, cnt));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_origin = ctx->d_org;
+    }
+    KinParams q;
+    memset(&q, 0, sizeof(q));
+    q.n = n, q.M = ctx->n_markers;
+    q.m_lo   = ctx->chromstarts[chrom_begin];
+    q.n_mark = ctx->chromstarts[chrom_end] - q.m_lo;
+    q.n_pad  = (n + KIN_TILE - 1) / KIN_TILE * KIN_TILE;
+    q.m_pad  = (q.n_mark + KIN_KC - 1) / KIN_KC * KIN_KC;
+    q.origin = d_origin;
+    const size_t  nn = (size_t)n * n;
+    const int32_t n_mark = q.n_mark;
+    const bool    split = kin_is_split(n, q.n_mark);
+    const int     chunks = split ? (q.m_pad + KIN_CHUNK - 1) / KIN_CHUNK : 1;
+    // the chunks summed together in a round: at most KIN_ROUND, their partial sums under 256 MB (the order of the additions
+    // does not depend on it)
+    const int     round = split ? (int)std::max<size_t>(1, std::min<size_t>(std::min(chunks, KIN_ROUND), ((size_t)256 << 20) / (nn * 8))) : 1;
+    RC_TRY(ctx->d_kin_image.ensure(ctx, (size_t)q.m_pad * q.n_pad));
+    if (split) RC_TRY(ctx->d_kin_part.ensure(ctx, (size_t)round * nn));
+    RC_TRY(stage_out(ctx, dev, sum_out, ctx->d_kin_sum, nn, &q.sum));
+    q.image = ctx->d_kin_image;
+    launch_kin_pack(q, ctx->stream);
+    if (!split) {
+        q.k_lo = 0, q.k_len = q.m_pad, q.out = q.sum;
+        launch_kin_syrk(q, 1, ctx->stream);
+    } else {
+        q.out = ctx->d_kin_part, q.k_len = KIN_CHUNK;
+        for (int c0 = 0; c0 < chunks; c0 += round) {
+            q.k_lo = c0 * KIN_CHUNK, q.parts = std::min(round, chunks - c0), q.first = c0 == 0;
+            launch_kin_syrk(q, q.parts, ctx->stream);
+            launch_kin_finish(q, ctx->stream);
+        }
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (dev) {
+        HIP_TRY(ctx, hipMemcpyAsync(n_markers_out, &n_mark, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        RC_TRY(fetch_out(ctx, sum_out, q.sum, nn));
+        *n_markers_out = n_mark;
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Column scan (cnf2_qtlcols.h, cnf2_qtlcols_kernels.hip).  Everything is checked before anything is written or uploaded.
+// ------------------------------------------------------------------------------------------------
+int cnf2_qtl_scan_cols(cnf2_ctx* ctx, int n, int n_mark, int ne, const double* reg, const double* scale, int nx, const double* x0,
+                       int n_traits, const double* pheno, int n_perm, const int32_t* perm, double* lod_out, double* coef_out,
+                       int32_t* rank_out, double* rss0_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (n < 1 || n_mark < 1 || n_traits < 1) return fail(ctx, CNF2_ERR_ARG, "n, n_mark and n_traits must be at least 1");
+    if (ne < 1 || ne > 2) return fail(ctx, CNF2_ERR_ARG, "ne must be 1 or 2");
+    if (nx < 1 || nx > QTL_NX) return fail(ctx, CNF2_ERR_ARG, "nx must be 1 .. %d", QTL_NX);
+    if (!reg || !x0 || !pheno) return fail(ctx, CNF2_ERR_ARG, "reg, x0 and pheno must not be NULL");
+    if (n_perm < 0 || (n_perm > 0) != (perm != nullptr) || (n_perm > 0) != (perm_max_out != nullptr))
+        return fail(ctx, CNF2_ERR_ARG, "perm and perm_max_out must be NULL exactly when n_perm is 0");
+    if (!lod_out || !coef_out || !rank_out || !rss0_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    const size_t R = (size_t)n_traits * ((size_t)n_perm + 1);
+    if (R > (size_t)1 << 30 || (size_t)n * n_mark * ne > (size_t)1 << 40) return fail(ctx, CNF2_ERR_ARG, "too many columns");
+    const bool reg_dev = (flags & CNF2_QTL_REG_DEVICE) != 0;
+    if (reg_dev && ((uintptr_t)reg & 15)) return fail(ctx, CNF2_ERR_ARG, "device regressors must be aligned to 16 bytes");
+    for (size_t e = 0; e < (size_t)n * n_traits; e++)
+        if (!std::isfinite(pheno[e])) return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is not finite", (int)(e % n_traits), (int)(e / n_traits));
+    for (size_t e = 0; e < (size_t)n * nx; e++)
+        if (!std::isfinite(x0[e])) return fail(ctx, CNF2_ERR_ARG, "column %d of x0 is not finite at individual %d", (int)(e % nx), (int)(e / nx));
+    if (scale)
+        for (int i = 0; i < n; i++)
+            if (!std::isfinite(scale[i])) return fail(ctx, CNF2_ERR_ARG, "scale is not finite at individual %d", i);
+    std::vector<uint8_t> seen(n);
+    for (int p = 0; p < n_perm; p++) {
+        std::fill(seen.begin(), seen.end(), 0);
+        const int32_t* row = perm + (size_t)p * n;
+        for (int i = 0; i < n; i++) {
+            const int32_t j = row[i];
+            if (j < 0 || j >= n || seen[j]) return fail(ctx, CNF2_ERR_ARG, "row %d of perm is not a permutation of 0 .. n-1", p);
+            seen[j] = 1;
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    M = n_mark, T = n_traits, P = n_perm;
+    // the column tile: the image under 1 GB, the tile maxima bounded, the caller's cap (cnf2_set_qtl_columns)
+    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)n));
+    rt = std::min(std::min(rt, (size_t)4096), R);
+    if (ctx->qtl_columns > 0) rt = std::min(rt, (size_t)ctx->qtl_columns);
+    const size_t n_tiles = ((size_t)M + 15) / 16;
+
+    QtlColsParams q;
+    memset(&q, 0, sizeof(q));
+    q.n = n, q.M = M, q.ne = ne, q.T = T, q.P = P, q.nx = nx;
+    if (reg_dev) q.reg = reg;
+    else {
+        RC_TRY(qtl_upload(ctx, ctx->d_ql_reg, reg, (size_t)n * M * ne));
+        q.reg = ctx->d_ql_reg;
+    }
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_scale, scale, scale ? (size_t)n : 0));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_x0, x0, (size_t)n * nx));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_pheno, pheno, (size_t)n * T));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_perm, perm, (size_t)P * n));
+    RC_TRY(ctx->d_ql_chol.ensure(ctx, QTL_CHOL));
+    RC_TRY(ctx->d_ql_mk.ensure(ctx, (size_t)M * QTL_MK));
+    RC_TRY(ctx->d_ql_Y.ensure(ctx, (size_t)n * rt));
+    RC_TRY(ctx->d_ql_null.ensure(ctx, (size_t)(nx + 1) * rt));
+    if (P > 0) RC_TRY(ctx->d_ql_tilemax.ensure(ctx, n_tiles * rt));
+    q.scale = scale ? ctx->d_ql_scale.ptr : nullptr;
+    q.x0 = ctx->d_ql_x0, q.pheno = ctx->d_ql_pheno, q.perm = ctx->d_ql_perm;
+    q.chol = ctx->d_ql_chol, q.mk = ctx->d_ql_mk, q.Y = ctx->d_ql_Y, q.nullq = ctx->d_ql_null, q.tilemax = ctx->d_ql_tilemax;
+    q.rstride = (int)rt, q.n_tiles = (int)n_tiles;
+    RC_TRY(stage_out(ctx, dev, rank_out, ctx->d_ql_rank, (size_t)M, &q.rank));
+    RC_TRY(stage_out(ctx, dev, lod_out, ctx->d_ql_lod, (size_t)T * M, &q.lod));
+    RC_TRY(stage_out(ctx, dev, coef_out, ctx->d_ql_coef, (size_t)T * M * 2, &q.coef));
+    RC_TRY(stage_out(ctx, dev, rss0_out, ctx->d_ql_rss0, (size_t)T, &q.rss0));
+    RC_TRY(stage_out(ctx, dev, perm_max_out, ctx->d_ql_pmax, (size_t)P * T, &q.pmax));
+
+    launch_qtlcols_null(q, ctx->stream);
+    launch_qtlcols_design(q, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = (int)r0;
+        q.rn = (int)std::min(rt, R - r0);
+        launch_qtlcols_gather(q, ctx->stream);
+        launch_qtlcols_colnull(q, ctx->stream);
+        launch_qtlcols_scan(q, ctx->stream);
+        if (r0 + q.rn > (size_t)T) launch_qtlcols_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dev) {
+        RC_TRY(fetch_out(ctx, rank_out, q.rank, (size_t)M));
+        RC_TRY(fetch_out(ctx, lod_out, q.lod, (size_t)T * M));
+        RC_TRY(fetch_out(ctx, coef_out, q.coef, (size_t)T * M * 2));
+        RC_TRY(fetch_out(ctx, rss0_out, q.rss0, (size_t)T));
+        if (P > 0) RC_TRY(fetch_out(ctx, perm_max_out, q.pmax, (size_t)P * T));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
 }
 
 // The pair scan on device rows d_origin[n][M][4]: cnf2_qtl2.h, cnf2_qtl2_kernels.hip.  Everything is checked and every

@@ -439,4 +439,81 @@ int cnf2h_qtl_null_residuals(int n, int n_traits, const double* pheno, int n_cov
     return 0;
 }
 
+// cnf2_kinship_sums on the CPU: the same sums, the markers in ascending order, the lower triangle mirrored
+int cnf2h_kinship_sums(int n, int n_markers, const double* origin, const int32_t* chromstarts, int n_chrom, int chrom_begin,
+                       int chrom_end, double* sum_out, int32_t* n_markers_out)
+{
+    if (n < 1 || n_markers < 1 || !origin || !chromstarts || n_chrom < 1 || chrom_begin < 0 || chrom_end > n_chrom ||
+        chrom_begin >= chrom_end || !sum_out || !n_markers_out || chromstarts[0] != 0 || chromstarts[n_chrom] != n_markers)
+        return -2;
+    const int m_lo = chromstarts[chrom_begin], m_hi = chromstarts[chrom_end];
+    if (m_lo < 0 || m_hi > n_markers || m_lo >= m_hi) return -2;
+    auto a = [&](int i, int m) { return origin[((size_t)i * n_markers + m) * 4 + 3] - origin[((size_t)i * n_markers + m) * 4]; };
+#pragma omp parallel for schedule(dynamic)
+    for (int i = 0; i < n; i++)
+        for (int j = 0; j <= i; j++) {
+            double s = 0.0;
+            for (int m = m_lo; m < m_hi; m++) s += a(i, m) * a(j, m);
+            sum_out[(size_t)i * n + j] = sum_out[(size_t)j * n + i] = s;
+        }
+    *n_markers_out = m_hi - m_lo;
+    return 0;
+}
+
+// one marker of cnf2_qtl_scan_cols: the sums in the kernels' order, then qtl_marker_record and qtl_cell (cnf2_qtl.h)
+int cnf2h_qtl_cols_marker(int n, int ne, const double* reg, const double* scale, int nx, const double* x0, int n_col,
+                          const double* y, double* lod_out, double* coef_out, int32_t* rank_out, double* rss0_out)
+{
+    using namespace cnf2;
+    if (n < 1 || ne < 1 || ne > 2 || !reg || nx < 1 || nx > QTL_NX || !x0 || n_col < 0 || (n_col > 0 && (!y || !lod_out || !coef_out || !rss0_out)) ||
+        !rank_out)
+        return -2;
+    double S[QTL_NX * QTL_NX] = {0.0};
+    for (int j = 0; j < nx; j++)
+        for (int k = 0; k <= j; k++) {
+            double s = 0.0;
+            for (int i = 0; i < n; i++) s += x0[(size_t)i * nx + j] * x0[(size_t)i * nx + k];
+            S[j * QTL_NX + k] = s;
+        }
+    const bool usable = qtl_cholesky(S, nx) && n >= nx + 3;
+    double     sa[QTL_NX] = {0.0}, sd[QTL_NX] = {0.0}, saa = 0.0, sad = 0.0, sdd = 0.0;
+    auto       ra = [&](int i) { return (scale ? scale[i] : 1.0) * reg[(size_t)i * ne]; };
+    auto       rd = [&](int i) { return ne == 2 ? (scale ? scale[i] : 1.0) * reg[(size_t)i * ne + 1] : 0.0; };
+    for (int i = 0; i < n; i++) {
+        const double a = ra(i), d = rd(i);
+        for (int k = 0; k < nx; k++) {
+            sa[k] += a * x0[(size_t)i * nx + k];
+            sd[k] += d * x0[(size_t)i * nx + k];
+        }
+        saa += a * a, sad += a * d, sdd += d * d;
+    }
+    double rec[QTL_MK];
+    *rank_out = qtl_marker_record(S, nx, usable, sa, sd, saa, sad, sdd, ne == 1, rec);
+    for (int r = 0; r < n_col; r++) {
+        double b[QTL_NX] = {0.0}, z[QTL_NX], yy = 0.0, va = 0.0, vd = 0.0;
+        for (int i = 0; i < n; i++) {
+            const double v = y[(size_t)i * n_col + r];
+            for (int k = 0; k < nx; k++) b[k] += x0[(size_t)i * nx + k] * v;
+            yy += v * v;
+            va += ra(i) * v;
+            vd += rd(i) * v;
+        }
+        double rss0 = 0.0;
+        if (usable) {
+            for (int k = 0; k < QTL_NX; k++) z[k] = b[k];
+            qtl_chol_solve(S, nx, z);
+            double e = 0.0;
+            for (int k = 0; k < nx; k++) e += b[k] * z[k];
+            rss0 = yy - e;
+        }
+        for (int k = 0; k < nx; k++) {
+            va -= rec[k] * b[k];
+            vd -= rec[QTL_NX + k] * b[k];
+        }
+        const QtlCell c = qtl_cell(va, vd, rec[QTL_PA], rec[QTL_L], rec[QTL_PD], rss0, n, usable);
+        rss0_out[r] = rss0, lod_out[r] = c.lod, coef_out[2 * r] = c.ca, coef_out[2 * r + 1] = c.cd;
+    }
+    return 0;
+}
+
 }  // extern "C"

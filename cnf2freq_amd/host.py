@@ -14,7 +14,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
-           "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker"]
+           "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -66,6 +66,8 @@ def load():
         L.cnf2h_qtlcof_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, C.c_uint32, i32, vp, vp, vp, vp, vp]
         L.cnf2h_qtlem_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_qtlbin_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_kinship_sums.argtypes = [i32, i32, vp, vp, i32, i32, i32, vp, vp]
+        L.cnf2h_qtl_cols_marker.argtypes = [i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -158,6 +160,45 @@ def qtlcof_marker(gram, xty, yy, n_c, n_cov, n_cof, skip=0, additive=False):
     if rc != 0:
         raise RuntimeError("cnf2h_qtlcof_marker failed (%d)" % rc)
     return dict(usable=bool(rank[0]), rank_cof=int(rank[1]), rank=int(rank[2]), rss0=rss0, lod_base=base, lod=lod, coef=coef)
+
+
+def kinship_sums(origin, chromstarts, chrom_begin=0, chrom_end=None):
+    """cnf2h_kinship_sums: (sum[n][n], markers) of the chromosomes chrom_begin .. chrom_end-1 (None: to the last) on origin rows
+    origin[n][M][4] -- what Context.kinship_sums computes on the GPU.  K = (1 + sum / markers) / 2.  CPU only."""
+    L = load()
+    o = np.ascontiguousarray(origin, np.float64)
+    cs = np.ascontiguousarray(chromstarts, np.int32)
+    if o.ndim != 3 or o.shape[2] != 4 or cs[-1] != o.shape[1]:
+        raise ValueError("origin must be [n][M][4] with M the map's markers")
+    n, C = o.shape[0], len(cs) - 1
+    chrom_end = C if chrom_end is None else chrom_end
+    out, cnt = np.zeros((n, n)), np.zeros(1, np.int32)
+    rc = L.cnf2h_kinship_sums(n, o.shape[1], _p(o), _p(cs), C, chrom_begin, chrom_end, _p(out), _p(cnt))
+    if rc != 0:
+        raise ValueError("cnf2h_kinship_sums refused its arguments (%d)" % rc)
+    return out, int(cnt[0])
+
+
+def qtl_cols_marker(reg, x0, y, scale=None):
+    """cnf2h_qtl_cols_marker: one marker of the column scan (cnf2_qtl_scan_cols) on reg[n][ne], x0[n][nx] and the columns
+    y[n][R].  A dict: lod[R], coef[R][2], rank, rss0[R].  CPU only."""
+    L = load()
+    r = np.ascontiguousarray(reg, np.float64)
+    r = r[:, None] if r.ndim == 1 else r
+    x = np.ascontiguousarray(x0, np.float64)
+    v = np.ascontiguousarray(y, np.float64)
+    v = v[:, None] if v.ndim == 1 else v
+    n = r.shape[0]
+    if x.ndim != 2 or x.shape[0] != n or v.shape[0] != n:
+        raise ValueError("reg, x0 and y must have n rows")
+    s = None if scale is None else np.ascontiguousarray(scale, np.float64)
+    R = v.shape[1]
+    lod, coef, rank, rss0 = np.zeros(R), np.zeros((R, 2)), np.zeros(1, np.int32), np.zeros(R)
+    rc = L.cnf2h_qtl_cols_marker(n, r.shape[1], _p(r), None if s is None else _p(s), x.shape[1], _p(x), R, _p(v), _p(lod), _p(coef),
+                                 _p(rank), _p(rss0))
+    if rc != 0:
+        raise ValueError("cnf2h_qtl_cols_marker refused its arguments (%d)" % rc)
+    return dict(lod=lod, coef=coef, rank=int(rank[0]), rss0=rss0)
 
 
 def qtlx_columns(n_cov, n_int=0, additive=False, imprint=False):

@@ -20,7 +20,12 @@ scan_binary, read by thresholds and peaks in the same way.
 The cofactor scan (Context.qtl_scan_cof, cnf2_qtl_scan_cof) is composite interval mapping: every marker fitted together with
 the loci found before, each left out inside its own window.  scan_cof with cofactor_windows asks whether there is a further
 QTL, fit_multi (read_multi) reads the multiple-QTL model -- full LOD, drop-one LODs, effects -- off one call, and
-forward_select builds the model a locus at a time against permutation thresholds."""
+forward_select builds the model a locus at a time against permutation thresholds.
+
+The polygenic scan (Context.kinship_sums, Context.qtl_scan_cols; cnf2_kinship_sums, cnf2_qtl_scan_cols) drops the assumption
+that individuals are independent given the tested locus: kinship makes the realised kinship from the origin rows (also
+leaving one chromosome out), est_herit estimates the heritability, and scan_lmm scans the linear mixed model on columns
+rotated by the kinship's eigenvectors; thresholds and peaks read it as they read scan."""
 import numpy as np
 
 from . import synth
@@ -579,3 +584,210 @@ def peaks(lod, pos, chromstarts, threshold, drop=1.5, coef=None):
                 p["additive"], p["dominance"] = (float(v) for v in np.asarray(coef)[t, m])
             found.append(p)
     return found
+
+
+# ------------------------------------------------------------------------------------------------
+# The polygenic (mixed-model) scan: kinship from the origin rows, heritability, the scan on rotated columns
+# ------------------------------------------------------------------------------------------------
+def kinship(ctx, rows=None, loco=False):
+    """The realised line-origin kinship of the analysed individuals from the origin rows (Context.kinship_sums_device,
+    cnf2_kinship_sums): K = (1 + S / M) / 2 with S[i][j] the sum over the markers of a_i a_j, a = P(BB) - P(AA) -- R/qtl2's
+    allele-probability kinship for two founder lines.  A torch f64 tensor on the context's device: [n][n], or with loco
+    [C][n][n], K_-c = (1 + (S - S_c) / (M - M_c)) / 2, the kinship from every chromosome but c (leave one chromosome out: a
+    locus under test is then not also in the polygenic term).  rows: the tensor of origin_rows (None: one origin sweep).
+    ValueError with loco on a map of one chromosome."""
+    import torch
+    C = ctx.n_chrom
+    if loco and C < 2:
+        raise ValueError("leaving one chromosome out needs at least two chromosomes")
+    d_o = origin_rows(ctx) if rows is None else rows
+    n = d_o.shape[0]
+    dev = d_o.device
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def sums(c0, c1):
+        s = torch.zeros((n, n), dtype=torch.float64, device=dev)
+        ctx.kinship_sums_device(n, d_o.data_ptr(), c0, c1, d_sum=s.data_ptr(), d_n_markers=cnt.data_ptr())
+        ctx.sync()
+        return s, int(cnt.item())
+
+    S, M = sums(0, C)
+    if not loco:
+        return (1.0 + S / M) * 0.5
+    out = torch.zeros((C, n, n), dtype=torch.float64, device=dev)
+    for c in range(C):
+        Sc, Mc = sums(c, c + 1)
+        out[c] = (1.0 + (S - Sc) / (M - Mc)) * 0.5
+    return out
+
+
+_kinship = kinship      # (scan_lmm's argument of the same name is a matrix)
+
+
+def _lmm_objective(h2, y, x, lam, reml):
+    """(log-likelihood, sigma2, w) of the rotated model at h2: weighted least squares of y on x with w = 1 / (h2 lam + 1 - h2)"""
+    w = 1.0 / (h2 * lam + (1.0 - h2))
+    sw = np.sqrt(w)
+    xs, ys = x * sw[:, None], y * sw
+    beta = np.linalg.lstsq(xs, ys, rcond=None)[0]
+    rss = float(((ys - xs @ beta) ** 2).sum())
+    n, nx = x.shape
+    slw = float(np.log(w).sum())
+    rss = max(rss, np.finfo(np.float64).tiny)
+    if not reml:
+        return -(n * np.log(2.0 * np.pi * rss / n) + n - slw) / 2.0, rss / n, w
+    df = n - nx
+    logdet = np.linalg.slogdet(xs.T @ xs)[1]
+    return -(df * np.log(2.0 * np.pi * rss / df) + df - slw + logdet) / 2.0, rss / df, w
+
+
+def est_herit(y, x0, lam, u, reml=True):
+    """(h2, sigma2, loglik): the heritability that maximises the profile log-likelihood of y = x0 b + g + e,
+    g ~ N(0, h2 s K), e ~ N(0, (1 - h2) s I), over h2 in [0, 0.999], in the eigen form: K = u diag(lam) u' (eigenvalues
+    below 0 count as 0), w_i = 1 / (h2 lam_i + 1 - h2), weighted least squares of u'y on u'x0.  ML maximises
+    -(n log(2 pi RSS / n) + n - sum log w) / 2; REML (the default) has n - nx for n and adds log det(x0' u W u' x0) inside
+    the bracket.  The search is deterministic: 21 grid points, then golden section in the bracket around the best one down
+    to a width of 1e-8.  u None: y and x0 are rotated already.  sigma2 is RSS / n (RSS / (n - nx) with reml)."""
+    y = np.asarray(y, np.float64).reshape(-1)
+    x = np.asarray(x0, np.float64).reshape(len(y), -1)
+    lam = np.maximum(np.asarray(lam, np.float64).reshape(-1), 0.0)
+    if u is not None:
+        u = np.asarray(u, np.float64)
+        y, x = u.T @ y, u.T @ x
+    if x.shape[0] <= x.shape[1]:
+        raise ValueError("est_herit needs more individuals than columns of x0")
+    f = lambda h: _lmm_objective(h, y, x, lam, reml)[0]
+    hi = 0.999
+    grid = np.linspace(0.0, hi, 21)
+    vals = [f(h) for h in grid]
+    k = int(np.argmax(vals))
+    a, b = grid[max(k - 1, 0)], grid[min(k + 1, 20)]
+    g = (np.sqrt(5.0) - 1.0) / 2.0
+    c, d = b - g * (b - a), a + g * (b - a)
+    fc, fd = f(c), f(d)
+    while b - a > 1e-8:
+        if fc >= fd:
+            b, d, fd = d, c, fc
+            c = b - g * (b - a)
+            fc = f(c)
+        else:
+            a, c, fc = c, d, fd
+            d = a + g * (b - a)
+            fd = f(d)
+    cands = [(vals[k], grid[k]), (f(0.5 * (a + b)), 0.5 * (a + b))]
+    best = max(cands, key=lambda t: t[0])
+    ll, s2, _ = _lmm_objective(best[1], y, x, lam, reml)
+    return float(best[1]), float(s2), float(ll)
+
+
+def _eigh(K):
+    """(lam, U) of a symmetric torch matrix on its device; numpy where torch refuses"""
+    import torch
+    try:
+        lam, U = torch.linalg.eigh(K)
+        if not bool(torch.isfinite(lam).all()):
+            raise RuntimeError("eigh gave values that are not finite")
+        return lam, U
+    except RuntimeError:
+        lam, U = np.linalg.eigh(K.cpu().numpy())
+        return torch.from_numpy(lam).to(K.device), torch.from_numpy(U).to(K.device)
+
+
+def scan_lmm(ctx, pheno, kinship=None, loco=True, cov=None, use=None, permutations=0, seed=0, additive=False, reml=True, h2=None,
+             rows=None):
+    """The polygenic (mixed-model) scan of a whole cross on the context's uploaded pedigree: y = X0 b + x(m) beta + g + e with
+    g ~ N(0, s_g^2 K), what R/qtl2's scan1 with a kinship does.  It runs once per pattern of missing phenotypes (NaN), on the
+    individuals that are used, have the phenotype and are skipped on no chromosome.  kinship: None (qtl.kinship of the rows,
+    with `loco`), a tensor or array [n][n] (any positive semi-definite matrix, e.g. a pedigree relationship matrix; one
+    model for the genome) or [C][n][n] (one per chromosome).  Per pattern, and per chromosome where the kinship is: the kept
+    submatrix is eigendecomposed (torch.linalg.eigh on the context's device), the centred phenotypes and [1, centred cov] are
+    rotated, per trait h2 is estimated (est_herit; or `h2`, a number or [T], is taken), the chromosome's (a, d) columns are
+    rotated by torch matmuls in chunks, and the block is scanned by Context.qtl_scan_cols_device with x0 and y whitened on the
+    host and scale = sqrt(w).  With permutations > 0 one more scan per trait runs on the permuted whitened residuals of the
+    null model: whitened, they are exchangeable (Freedman-Lane on the whitened model).
+    A dict: lod[T][M], coef[T][M][2], rank[T][M], h2[T][C] and sigma2[T][C] (one value repeated where one model serves the
+    genome), n_used[T], perm_max[P][T][C] or None: thresholds and peaks read it as they read scan."""
+    import torch
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    cs = np.asarray(ctx.chromstarts, np.int64)
+    z = None if cov is None else np.asarray(cov, np.float64).reshape(n, -1)
+    if z is not None and z.shape[1] == 0:
+        z = None
+    d_o = origin_rows(ctx) if rows is None else rows
+    dev = d_o.device
+    if kinship is None:
+        Kall = _kinship(ctx, rows=d_o, loco=loco and C > 1)
+    else:
+        Kall = kinship if isinstance(kinship, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(kinship, np.float64))
+        Kall = Kall.to(device=dev, dtype=torch.float64)
+    per_chrom = Kall.dim() == 3
+    if Kall.shape[-2:] != (n, n) or (per_chrom and Kall.shape[0] != C):
+        raise ValueError("kinship must be [n][n] or [C][n][n] with n = %d, C = %d" % (n, C))
+    h2_given = None if h2 is None else np.broadcast_to(np.asarray(h2, np.float64), (T,))
+    if h2_given is not None and not np.all((h2_given >= 0.0) & (h2_given < 1.0)):
+        raise ValueError("h2 must lie in [0, 1)")
+    ne = 1 if additive else 2
+    present = (d_o[:, torch.from_numpy(cs[:-1]).to(dev), :] != 0).any(dim=2).all(dim=1).cpu().numpy()
+    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, 2), np.nan), rank=np.zeros((T, M), np.int32), h2=np.zeros((T, C)),
+               sigma2=np.zeros((T, C)), n_used=np.zeros(T, np.int32),
+               perm_max=np.zeros((permutations, T, C)) if permutations else None)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]] & present
+        idx = np.flatnonzero(u)
+        nk = len(idx)
+        out["n_used"][cols] = nk
+        x0 = np.ones((nk, 1)) if z is None else np.concatenate([np.ones((nk, 1)), z[idx] - z[idx].mean(axis=0)], axis=1)
+        if nk < x0.shape[1] + 3:
+            continue
+        yk = y[idx][:, cols] - y[idx][:, cols].mean(axis=0)
+        d_idx = torch.from_numpy(idx).to(dev)
+        d_yx = torch.from_numpy(np.concatenate([yk, x0], axis=1)).to(dev)
+        perm = _permutations(nk, permutations, seed) if permutations else None
+        model = None
+        for c in range(C):
+            if per_chrom or model is None:
+                Ksub = (Kall[c] if per_chrom else Kall)[d_idx][:, d_idx]
+                lam_t, U = _eigh(0.5 * (Ksub + Ksub.T))
+                lam = np.maximum(lam_t.cpu().numpy(), 0.0)
+                yx = (U.T @ d_yx).cpu().numpy()
+                yr, xr = yx[:, :len(cols)], yx[:, len(cols):]
+                fits = []
+                for j, t in enumerate(cols):
+                    if h2_given is None:
+                        h, s2, _ = est_herit(yr[:, j], xr, lam, None, reml)
+                    else:
+                        h = float(h2_given[t])
+                        s2 = _lmm_objective(h, yr[:, j], xr, lam, reml)[1]
+                    fits.append((h, s2, np.sqrt(1.0 / (h * lam + (1.0 - h)))))
+                model = (U, yr, xr, fits)
+            U, yr, xr, fits = model
+            m0, m1 = int(cs[c]), int(cs[c + 1])
+            R = torch.empty((nk, m1 - m0, ne), dtype=torch.float64, device=dev)
+            for b0 in range(m0, m1, 4096):                      # the rotation, in chunks of markers: U' [a, d]
+                b1 = min(b0 + 4096, m1)
+                o = d_o[d_idx, b0:b1, :]
+                reg = o[:, :, 3] - o[:, :, 0]
+                reg = reg[:, :, None] if additive else torch.stack([reg, o[:, :, 1] + o[:, :, 2]], dim=2)
+                R[:, b0 - m0:b1 - m0, :] = (U.T @ reg.reshape(nk, -1)).reshape(nk, b1 - b0, ne)
+            torch.cuda.synchronize(dev)
+            for j, t in enumerate(cols):
+                h, s2, sw = fits[j]
+                out["h2"][t, c], out["sigma2"][t, c] = h, s2
+                xs, ys = xr * sw[:, None], yr[:, j] * sw
+                got = ctx.qtl_scan_cols_device(nk, m1 - m0, ne, R.data_ptr(), xs, ys, scale=sw)
+                out["lod"][t, m0:m1], out["coef"][t, m0:m1], out["rank"][t, m0:m1] = got["lod"][0], got["coef"][0], got["rank"]
+                if permutations:
+                    res = ys - xs @ np.linalg.lstsq(xs, ys, rcond=None)[0]
+                    out["perm_max"][:, t, c] = ctx.qtl_scan_cols_device(nk, m1 - m0, ne, R.data_ptr(), xs, res, scale=sw,
+                                                                        perm=perm)["perm_max"][:, 0]
+    return out

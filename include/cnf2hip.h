@@ -129,6 +129,7 @@ enum {
                                      where two groups of four of a chromosome have all eight shift modes of every window analysed
                                      (cnf2_last_uniform_pack8).  Same results to the bit; A/B switch and cross-check.  Ignored
                                      where no windows are packed */
+    CNF2_QTL_REG_DEVICE = 1u << 28, /* cnf2_qtl_scan_cols: `reg` is a device pointer (aligned to 16 bytes); it is read in place */
     CNF2_QTL_IMPRINT  = 1u << 25, /* cnf2_qtl_scanx: the design gets the parent-of-origin (imprinting) effect i = o[1] - o[2] */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
@@ -679,6 +680,55 @@ int cnf2_set_qtlcof_columns(cnf2_ctx *ctx, int cap);
  * what a caller needs of them on the host, e.g. the cofactors' columns for the null model whose residuals a permutation test
  * of the cofactor scan permutes.  CNF2_ERR_STATE where the context holds no such rows of n individuals; the rows stay valid. */
 int cnf2_qtl_kept_rows(cnf2_ctx *ctx, int n, int n_sel, const int32_t *sel, double *rows_out);
+
+/* Kinship from the origin rows, as raw sums: the first half of a polygenic (mixed-model) scan, whose second half is the column
+ * scan below.  origin[n][M][4] are cnf2_qtl_scan's rows -- a host array, staged whole, or with CNF2_QTL_ORIGIN_DEVICE a
+ * device pointer read in place, NULL for the rows the last cnf2_sweep_qtl left in the context (CNF2_ERR_STATE as there; the
+ * call leaves them valid).  With a_i(m) = o[i][m][3] - o[i][m][0], the additive line-origin score in -1 .. 1,
+ *   sum_out[i][j] = sum over the markers m of the chromosomes chrom_begin .. chrom_end-1 of a_i(m) a_j(m)
+ * and *n_markers_out is the number M' of those markers.  An all-zero row (an individual the sweep skipped on the chromosome)
+ * contributes 0.  The kinship itself is the caller's: K = (1 + S / M') / 2, which is R/qtl2's allele-probability kinship for
+ * two founder lines; leaving a chromosome out is then a subtraction of two calls' sums and counts.  With CNF2_OUT_DEVICE
+ * sum_out and n_markers_out are device pointers.  n outside 1 .. 46340, an empty or misplaced chromosome range and a NULL
+ * pointer return CNF2_ERR_ARG and write nothing; an allocation that fails returns CNF2_ERR_NOMEM before anything is written.
+ * Launches: a pack kernel writes the image a[markers][n] (8 bytes per entry, zero-padded to whole tiles); the product is a
+ * SYRK over the markers on the f64 matrix cores, 128 x 128 output tiles on or below the diagonal fed through LDS panels,
+ * the mirror written from the same accumulator: sum_out[i][j] and sum_out[j][i] are the same bits.  No atomics; the markers
+ * are summed in ascending order.  Where the lower triangle has fewer than 128 tiles (n <= 1920) and the range more than 256
+ * markers, every chunk of 256 markers is summed from zero and a finish kernel adds the chunks in ascending order: which of
+ * the two forms runs depends on n and M' alone, so a call gives the same bits every time, on every machine, from host or
+ * device rows and into host or device outputs. */
+int cnf2_kinship_sums(cnf2_ctx *ctx, int n, const double *origin, int chrom_begin, int chrom_end,
+                      double *sum_out /* [n][n] */, int32_t *n_markers_out, uint32_t flags);
+
+/* The Haley-Knott product on prepared columns: ordinary least squares of every phenotype column on
+ * [x0, scale_i reg(i, m, 0 .. ne-1)] at each marker m of one block of n_mark markers.  It is cnf2_qtl_scan with four
+ * differences: there is no implicit intercept and no centring -- x0[n][nx], 1 <= nx <= 9, is the whole null design as
+ * given; the regressors reg[n][n_mark][ne], ne = 1 or 2, are doubles, not origin rows; scale[n] (NULL: ones) multiplies
+ * the regressor rows on the fly; and a call is one block of markers -- no map, no masks, all n rows used, one rss0 per
+ * trait and one maximum per permutation and trait.  After rotation by a kinship's eigenvectors the big operand U'[a, d] is
+ * the same for every trait while the whitening weights depend on the trait's heritability: with scale the big array is read
+ * in place once per trait and never rewritten.
+ * Phenotype columns are cnf2_qtl_scan's: column (0, t) is pheno[i][t], column (1 + p, t) is pheno[perm[p][i]][t]; every row
+ * of perm[n_perm][n] is a permutation of 0 .. n-1.  Every decision about a cell is cnf2freq_amd/csrc/cnf2_qtl.h's, with
+ * n_c = n: the rank rule and its pivot threshold 1e-8 (the second regressor is tested after the first; with ne = 1 it is
+ * the additive model's dropped column), NaN in coef_out for a dropped column, dRSS clamped to [0, RSS0 (1 - 2^-52)],
+ * lod = (n / 2) log10(RSS0 / (RSS0 - dRSS)), lod 0 and coef NaN for a column with RSS0 = 0, and "not scanned" (lod 0, coef
+ * NaN, rank 0, rss0 0) when n < nx + 3 or x0'x0 has no Cholesky factor.
+ * Outputs: lod_out[T][n_mark], coef_out[T][n_mark][2], rank_out[n_mark], rss0_out[T], perm_max_out[P][T] (NULL exactly when
+ * n_perm is 0) -- host pointers, or device pointers with CNF2_OUT_DEVICE.  reg is a host pointer, staged whole, or with
+ * CNF2_QTL_REG_DEVICE a device pointer aligned to 16 bytes, read in place; scale, x0, pheno and perm are host pointers.
+ * Arguments out of range, a value of scale, x0 or pheno that is not finite and a row of perm that is no permutation return
+ * CNF2_ERR_ARG and write nothing.  The call needs no map and does not touch the context's rows.
+ * Launches, in cnf2_qtl_scan's form: the null design's factor; a record per marker; per tile of columns (the cap of
+ * cnf2_set_qtl_columns applies; results do not depend on it, to the bit) the column image, the null fit, the product on the
+ * f64 matrix cores -- marker tiles of 16, the epilogue in registers -- and the maxima's finish.  No atomics, every sum over
+ * the individuals in ascending order: a call gives the same bits every time. */
+int cnf2_qtl_scan_cols(cnf2_ctx *ctx, int n, int n_mark, int ne, const double *reg /* [n][n_mark][ne] */,
+                       const double *scale /* [n] or NULL */, int nx, const double *x0 /* [n][nx] */, int n_traits,
+                       const double *pheno /* [n][T] */, int n_perm, const int32_t *perm, double *lod_out /* [T][n_mark] */,
+                       double *coef_out /* [T][n_mark][2] */, int32_t *rank_out /* [n_mark] */, double *rss0_out /* [T] */,
+                       double *perm_max_out /* [P][T] */, uint32_t flags);
 
 /* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
  * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;

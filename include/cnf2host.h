@@ -189,6 +189,19 @@ int cnf2h_qtlbin_fit(int n, const double *origin, const double *y, int n_cov, co
                      int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *ll0_out, int32_t *n_ones_out,
                      int32_t *n_used_out);
 
+/* cnf2_kinship_sums (cnf2hip.h) on the CPU, for tests and for callers without a GPU: sum_out[n][n] = sum over the markers of
+ * the chromosomes chrom_begin .. chrom_end-1 of a_i(m) a_j(m), a = origin[3] - origin[0], on origin[n][n_markers][4] and the
+ * map's chromstarts[n_chrom + 1]; *n_markers_out the number of those markers.  The markers are added in ascending order
+ * and the lower triangle is mirrored.  -2: a bad argument. */
+int cnf2h_kinship_sums(int n, int n_markers, const double *origin, const int32_t *chromstarts, int n_chrom, int chrom_begin,
+                       int chrom_end, double *sum_out, int32_t *n_markers_out);
+
+/* One marker of cnf2_qtl_scan_cols (cnf2hip.h) through the shared algebra of cnf2_qtl.h: least squares of the columns
+ * y[n][n_col] on [x0, scale_i reg(i, 0 .. ne-1)] with reg[n][ne], scale[n] or NULL, x0[n][nx].  lod_out[n_col],
+ * coef_out[n_col][2], *rank_out, rss0_out[n_col].  -2: a bad argument. */
+int cnf2h_qtl_cols_marker(int n, int ne, const double *reg, const double *scale, int nx, const double *x0, int n_col,
+                          const double *y, double *lod_out, double *coef_out, int32_t *rank_out, double *rss0_out);
+
 #ifdef __cplusplus
 }
 #endif
