@@ -54,7 +54,7 @@ SYMBOLS = [
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
     "cnf2_qtl_scan_cof", "cnf2_set_qtlcof_columns", "cnf2_qtl_kept_rows",
-    "cnf2_kinship_sums", "cnf2_qtl_scan_cols",
+    "cnf2_kinship_sums", "cnf2_qtl_scan_cols", "cnf2_qtl_scan_boot",
 ]
 
 
@@ -138,6 +138,7 @@ def load():
         L.cnf2_qtl_kept_rows.argtypes = [vp, i32, i32, vp, vp]
         L.cnf2_kinship_sums.argtypes = [vp, i32, vp, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_cols.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_qtl_scan_boot.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_em.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, C.c_double,
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlem_columns.argtypes = [vp, i32]
@@ -762,6 +763,50 @@ class Context:
         """The same on device regressors (d_reg: an int, the pointer of n x n_mark x ne doubles aligned to 16 bytes), read in
         place.  x0, pheno, scale, perm and the outputs are host arrays."""
         return self._qtl_cols_call(n, n_mark, ne, C.c_void_p(d_reg), x0, pheno, scale, perm, QTL_REG_DEVICE)
+
+    # -- bootstrap scan --------------------------------------------------------------
+    def _qtl_boot_call(self, n, origin_ptr, pheno, count, chrom_begin, chrom_end, cov, use, profile, flags, out=None):
+        """cnf2_qtl_scan_boot with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
+        pheno, cov, use, _ = self._qtl_inputs(n, pheno, cov, use, None)
+        count = np.ascontiguousarray(count, np.int32)
+        count = count[None, :] if count.ndim == 1 else count
+        if count.ndim != 2 or count.shape[1] != n:
+            raise ValueError("count must be [B][n]")
+        chrom_end = self.n_chrom if chrom_end is None else chrom_end
+        if not 0 <= chrom_begin < chrom_end <= self.n_chrom:
+            raise ValueError("the chromosome range must be non-empty and within 0 .. %d" % self.n_chrom)
+        T, K, B = pheno.shape[1], 0 if cov is None else cov.shape[1], count.shape[0]
+        Cn = chrom_end - chrom_begin
+        Mn = int(self.chromstarts[chrom_end] - self.chromstarts[chrom_begin])
+        o = dict(boot_max=np.zeros((B, T, Cn)), boot_arg=np.zeros((B, T, Cn), np.int32), n_boot=np.zeros((B, Cn), np.int32),
+                 boot_lod=np.zeros((B, T, Mn)) if profile else None) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_qtl_scan_boot(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), chrom_begin, chrom_end, B,
+                                            _p(count), _p(o["boot_max"]), _p(o["boot_arg"]), _p(o["n_boot"]), opt(o["boot_lod"]),
+                                            flags), "cnf2_qtl_scan_boot")
+        return o
+
+    def qtl_scan_boot(self, origin, pheno, count, chrom_begin=0, chrom_end=None, cov=None, use=None, additive=False,
+                      profile=False, out=None):
+        """cnf2_qtl_scan_boot on host rows origin[n][M][4]: the scan of qtl_scan on resampled individuals.  count[B][n] (int32)
+        says how often replicate b draws individual i (qtl.bootstrap_counts); the chromosomes chrom_begin .. chrom_end-1
+        (None: to the last) are scanned.  A dict: boot_max[B][T][C'] the largest LOD of each chromosome, boot_arg[B][T][C']
+        the marker that has it (the lowest among equal ones; -1 and a maximum of 0 where the replicate cannot be fitted),
+        n_boot[B][C'] the individuals drawn, counted as often as drawn, and with profile boot_lod[B][T][M'] (else None).
+        The model: include/cnf2hip.h; qtl.boot_interval reads boot_arg."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return self._qtl_boot_call(origin.shape[0], _p(origin), pheno, count, chrom_begin, chrom_end, cov, use, profile,
+                                   QTL_ADDITIVE if additive else 0, out)
+
+    def qtl_scan_boot_device(self, n, d_origin, pheno, count, chrom_begin=0, chrom_end=None, cov=None, use=None, additive=False,
+                             profile=False, out=None):
+        """The same on device rows (d_origin: an int, the pointer of n x M x 4 doubles aligned to 16 bytes), read in place;
+        d_origin None: the rows this context's last sweep_qtl left in it, which stay valid.  Phenotypes, counts and outputs
+        are host arrays."""
+        return self._qtl_boot_call(n, C.c_void_p(d_origin) if d_origin else None, pheno, count, chrom_begin, chrom_end, cov, use,
+                                   profile, QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0), out)
 
     # -- two-QTL pair scan ---------------------------------------------------------
     QTL2_KEYS = ("lod_add", "lod_full", "rank_add", "rank_full", "rss0", "n_used", "perm_max")

@@ -28,6 +28,7 @@
 #include "cnf2_qtlbin.h"
 #include "cnf2_kinship.h"
 #include "cnf2_qtlcols.h"
+#include "cnf2_qtlboot.h"
 
 using namespace cnf2;
 
@@ -215,6 +216,13 @@ struct cnf2_ctx {
     DevBuf<double>  d_ql_reg, d_ql_scale, d_ql_x0, d_ql_pheno, d_ql_chol, d_ql_mk, d_ql_Y, d_ql_null, d_ql_tilemax;
     DevBuf<double>  d_ql_lod, d_ql_coef, d_ql_rss0, d_ql_pmax;
     DevBuf<int32_t> d_ql_perm, d_ql_rank;
+
+    // bootstrap scan (cnf2_qtl_scan_boot): the counts, the weight image of a replicate tile, the (replicate, chromosome)
+    // records, the tile maxima with their markers, staged outputs; the staged phenotypes, covariates and mask are the single
+    // scan's buffers
+    DevBuf<double>  d_qo_W, d_qo_rec, d_qo_tilemax, d_qo_max, d_qo_lod;
+    DevBuf<int32_t> d_qo_count, d_qo_map, d_qo_tilearg, d_qo_arg, d_qo_nb;   // d_qo_map: first markers, tiles, tile starts
+    DevBuf<uint8_t> d_qo_cmask;
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -1951,6 +1959,138 @@ int cnf2_qtl_scan_cols(cnf2_ctx* ctx, int n, int n_mark, int ne, const double* r
         RC_TRY(fetch_out(ctx, coef_out, q.coef, (size_t)T * M * 2));
         RC_TRY(fetch_out(ctx, rss0_out, q.rss0, (size_t)T));
         if (P > 0) RC_TRY(fetch_out(ctx, perm_max_out, q.pmax, (size_t)P * T));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Bootstrap scan (cnf2_qtlboot.h, cnf2_qtlboot_kernels.hip).  Everything is checked before anything is written or uploaded.
+// ------------------------------------------------------------------------------------------------
+int cnf2_qtl_scan_boot(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
+                       const double* cov, int chrom_begin, int chrom_end, int n_boot, const int32_t* count, double* boot_max_out,
+                       int32_t* boot_arg_out, int32_t* n_boot_out, double* boot_lod_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (n < 1 || n_traits < 1 || !pheno) return fail(ctx, CNF2_ERR_ARG, "n and n_traits must be at least 1 and pheno not NULL");
+    if (n_cov < 0 || n_cov > QTL_MAXK || (n_cov > 0 && !cov)) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d, with cov", QTL_MAXK);
+    if (chrom_begin < 0 || chrom_end > ctx->n_chrom || chrom_begin >= chrom_end)
+        return fail(ctx, CNF2_ERR_ARG, "the chromosome range must be non-empty and within 0 .. %d", ctx->n_chrom);
+    if (n_boot < 1 || !count) return fail(ctx, CNF2_ERR_ARG, "n_boot must be at least 1 and count not NULL");
+    if (!boot_max_out || !boot_arg_out || !n_boot_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    const int    T = n_traits, K = n_cov, B = n_boot, nc = chrom_end - chrom_begin;
+    const int    m_lo = ctx->chromstarts[chrom_begin], n_mark = ctx->chromstarts[chrom_end] - m_lo;
+    if ((size_t)B * T > (size_t)1 << 30 || (size_t)B * T * (size_t)n_mark > (size_t)1 << 40 || T > 65535 || nc > 65535)
+        return fail(ctx, CNF2_ERR_ARG, "too many replicates, traits or chromosomes");
+    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
+                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    std::vector<uint8_t> mask(n, 1);
+    if (use)
+        for (int i = 0; i < n; i++) mask[i] = use[i] ? 1 : 0;
+    for (int i = 0; i < n; i++) {
+        if (!mask[i]) continue;
+        for (int t = 0; t < T; t++)
+            if (!std::isfinite(pheno[(size_t)i * T + t]))
+                return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is used and not finite", t, i);
+        for (int k = 0; k < K; k++)
+            if (!std::isfinite(cov[(size_t)i * K + k]))
+                return fail(ctx, CNF2_ERR_ARG, "covariate %d of individual %d is used and not finite", k, i);
+    }
+    for (int b = 0; b < B; b++)
+        for (int i = 0; i < n; i++) {
+            const int32_t v = count[(size_t)b * n + i];
+            if (v < 0) return fail(ctx, CNF2_ERR_ARG, "count of individual %d in replicate %d is negative", i, b);
+            if (v > 0 && !mask[i]) return fail(ctx, CNF2_ERR_ARG, "replicate %d draws individual %d, which is not used", b, i);
+        }
+    // the columns minus their unweighted means over the used individuals, as every scan (qtl_centre)
+    QtlCentred centred;
+    qtl_centre_columns(pheno, n, T, mask, centred.pheno);
+    if (K > 0) qtl_centre_columns(cov, n, K, mask, centred.cov);
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const double* d_origin = kept ? ctx->d_org.ptr : origin;
+    if (flags & CNF2_QTL_ORIGIN_DEVICE) {
+        if ((uintptr_t)d_origin & 15) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+    } else {
+        const size_t cnt = (size_t)n * ctx->n_markers * 4;
+        ctx->qtl_rows_n = 0;
+        RC_TRY(ctx->d_org.ensure(ctx, cnt));
+        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        d_origin = ctx->d_org;
+    }
+    const bool dev = (flags & CNF2_OUT_DEVICE) != 0;
+    // the map as the kernels read it: the first marker of every scanned chromosome, the marker tiles, the tile starts
+    std::vector<int32_t> map, tiles, tstart(1, 0);
+    for (int cc = 0; cc < nc; cc++) {
+        const int f = ctx->chromstarts[chrom_begin + cc], e = ctx->chromstarts[chrom_begin + cc + 1];
+        map.push_back(f);
+        for (int m = f; m < e; m += 16) {
+            const int32_t t4[4] = {cc, m, std::min(16, e - m), 0};
+            tiles.insert(tiles.end(), t4, t4 + 4);
+        }
+        tstart.push_back((int32_t)(tiles.size() / 4));
+    }
+    const size_t n_tiles = tiles.size() / 4, o_tiles = map.size();
+    map.insert(map.end(), tiles.begin(), tiles.end());
+    const size_t o_tstart = map.size();
+    map.insert(map.end(), tstart.begin(), tstart.end());
+    // the replicate tile: a multiple of 16, the weight image under 1 GB, the tile maxima of a large map bounded
+    size_t bt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)n) / 16 * 16);
+    bt = std::min(std::min(bt, (size_t)4096), ((size_t)B + 15) / 16 * 16);
+    const size_t recd = qtlboot_rec_doubles(T);
+
+    RC_TRY(qtl_upload(ctx, ctx->d_qo_map, map.data(), map.size()));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, centred.pheno.data(), (size_t)n * T));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, centred.cov.data(), (size_t)n * K));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)n));
+    RC_TRY(qtl_upload(ctx, ctx->d_qo_count, count, (size_t)B * n));
+    RC_TRY(ctx->d_qo_cmask.ensure(ctx, (size_t)nc * n));
+    RC_TRY(ctx->d_qo_W.ensure(ctx, (size_t)n * bt));
+    RC_TRY(ctx->d_qo_rec.ensure(ctx, bt * nc * recd));
+    RC_TRY(ctx->d_qo_tilemax.ensure(ctx, n_tiles * bt * T));
+    RC_TRY(ctx->d_qo_tilearg.ensure(ctx, n_tiles * bt * T));
+
+    QtlBootParams q;
+    memset(&q, 0, sizeof(q));
+    q.n = n, q.M = ctx->n_markers, q.T = T, q.K = K, q.nx = K + 1;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
+    q.nc = nc, q.m_lo = m_lo, q.n_mark = n_mark;
+    q.origin = d_origin, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.count = ctx->d_qo_count;
+    q.first = ctx->d_qo_map, q.tiles = ctx->d_qo_map + o_tiles, q.tile_start = ctx->d_qo_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.cmask = ctx->d_qo_cmask, q.W = ctx->d_qo_W, q.rec = ctx->d_qo_rec, q.tilemax = ctx->d_qo_tilemax, q.tilearg = ctx->d_qo_tilearg;
+    RC_TRY(stage_out(ctx, dev, boot_max_out, ctx->d_qo_max, (size_t)B * T * nc, &q.boot_max));
+    RC_TRY(stage_out(ctx, dev, boot_arg_out, ctx->d_qo_arg, (size_t)B * T * nc, &q.boot_arg));
+    RC_TRY(stage_out(ctx, dev, n_boot_out, ctx->d_qo_nb, (size_t)B * nc, &q.n_boot));
+    RC_TRY(stage_out(ctx, dev, boot_lod_out, ctx->d_qo_lod, (size_t)B * T * n_mark, &q.boot_lod));
+
+    const int tc = qtlboot_trait_chunk(T);
+    launch_qtlboot_mask(q, ctx->stream);
+    for (size_t b0 = 0; b0 < (size_t)B; b0 += bt) {
+        q.b0 = (int)b0;
+        q.bn = (int)std::min(bt, (size_t)B - b0);
+        q.bstride = (q.bn + 15) / 16 * 16;
+        launch_qtlboot_gather(q, ctx->stream);
+        launch_qtlboot_design(q, ctx->stream);
+        launch_qtlboot_null(q, ctx->stream);
+        // (every trait chunk repeats the design sums: a cell's bits do not depend on the chunk it falls in)
+        for (int t0 = 0; t0 < T; t0 += tc) {
+            q.t0 = t0, q.tn = std::min(tc, T - t0);
+            launch_qtlboot_scan(q, ctx->stream);
+        }
+        launch_qtlboot_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    if (!dev) {
+        RC_TRY(fetch_out(ctx, boot_max_out, q.boot_max, (size_t)B * T * nc));
+        RC_TRY(fetch_out(ctx, boot_arg_out, q.boot_arg, (size_t)B * T * nc));
+        RC_TRY(fetch_out(ctx, n_boot_out, q.n_boot, (size_t)B * nc));
+        if (boot_lod_out) RC_TRY(fetch_out(ctx, boot_lod_out, q.boot_lod, (size_t)B * T * n_mark));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;

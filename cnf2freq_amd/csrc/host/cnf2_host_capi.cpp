@@ -13,6 +13,7 @@
 #include "../cnf2_qtlcof.h"
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
+#include "../cnf2_qtlboot.h"
 #include "cnf2_remap.h"
 
 using namespace cnf2host;
@@ -514,6 +515,27 @@ int cnf2h_qtl_cols_marker(int n, int ne, const double* reg, const double* scale,
         rss0_out[r] = rss0, lod_out[r] = c.lod, coef_out[2 * r] = c.ca, coef_out[2 * r + 1] = c.cd;
     }
     return 0;
+}
+
+int cnf2h_qtl_bootstrap_counts(int n, int n_boot, uint64_t seed, const uint8_t* use, const int32_t* strata, int32_t* count_out)
+{
+    if (n < 1 || n_boot < 0 || !count_out) return -2;
+    cnf2host::qtl_bootstrap_counts(n, n_boot, seed, use, strata, count_out);
+    return 0;
+}
+
+// one (replicate, marker) cell of cnf2_qtl_scan_boot: qtlboot_marker_serial (cnf2_qtlboot.h)
+int cnf2h_qtl_boot_marker(int n, const double* origin, int n_traits, const double* y, int n_cov, const double* cov, const uint8_t* c,
+                          const int32_t* count, int additive, double* lod_out, double* coef_out, int32_t* rank_out,
+                          double* rss0_out, int32_t* n_bc_out)
+{
+    if (n < 1 || !origin || n_traits < 1 || !y || n_cov < 0 || n_cov > cnf2::QTL_MAXK || (n_cov > 0 && !cov) || !c || !count ||
+        !lod_out || !coef_out || !rank_out || !rss0_out || !n_bc_out)
+        return -2;
+    return cnf2::qtlboot_marker_serial(n, origin, n_traits, y, n_cov, cov, c, count, additive != 0, lod_out, coef_out, rank_out,
+                                       rss0_out, n_bc_out)
+               ? 0
+               : -2;
 }
 
 }  // extern "C"

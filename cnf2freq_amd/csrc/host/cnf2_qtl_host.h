@@ -50,6 +50,27 @@ inline void qtl_permutations(int n, int P, uint64_t seed, const uint8_t* use, co
     }
 }
 
+// count[B][n] by the rule of qtl.bootstrap_counts: within every stratum the k used individuals, ascending, are idx[0..k); draw
+// j of replicate b -- one per used individual j -- picks idx[floor(u k)] of j's stratum with u = (splitmix64(seed, b n + j)
+// >> 11) 2^-53.  Every row sums to the used individuals of each stratum.  use / strata may be null.
+inline void qtl_bootstrap_counts(int n, int B, uint64_t seed, const uint8_t* use, const int32_t* strata, int32_t* count)
+{
+    std::map<int32_t, std::vector<int32_t>> groups;
+    for (int i = 0; i < n; i++)
+        if (!use || use[i]) groups[strata ? strata[i] : 0].push_back(i);
+    std::fill(count, count + (size_t)B * n, 0);
+    for (int b = 0; b < B; b++) {
+        int32_t* row = count + (size_t)b * n;
+        for (const auto& g : groups) {
+            const size_t k = g.second.size();
+            for (int32_t j : g.second) {
+                const double u = (double)(qtl_splitmix64(seed, (uint64_t)b * (uint64_t)n + (uint64_t)j) >> 11) * 0x1p-53;
+                row[g.second[std::min(k - 1, (size_t)floor(u * (double)k))]]++;
+            }
+        }
+    }
+}
+
 // res[n][T]: the residuals of every phenotype column on [1, cov] over the used individuals, 0 for the others
 // (qtl.null_residuals).  false when the null design has no Cholesky factor.  The normal equations are those of the columns
 // minus their means over the used individuals (qtl_column_mean, as in the scans): the residuals do not depend on offsets.

@@ -9,6 +9,7 @@
 //            [--qtlem F --phenofile P [--qtl-em-iterations N] [--qtl-em-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlbin F --phenofile P [--qtl-binary-iterations N] [--qtl-binary-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlcof F --phenofile P --qtl-cofactors i,j,k [--qtl-window X] [the --qtl-* options]]
+//            [--qtlboot F --phenofile P --qtl-boot-chrom C [--qtl-boot-replicates B] [--qtl-covariates, --qtl-seed, --qtl-additive]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -92,6 +93,10 @@
 // (default 0: at its own position only) -- after the other scans where they are given, on the same sweep's rows.  The design
 // takes at most 15 columns: six cofactors less one per two covariates, thirteen with --qtl-additive.  F is described at
 // qtlcof_scan below.
+// --qtlboot F --qtl-boot-chrom C [--qtl-boot-replicates B] (with --phenofile, --qtl-covariates, --qtl-seed and
+// --qtl-additive; not flags of the reference): the bootstrap of the scan on chromosome C (from 1, as the files print it) with
+// B replicates (default 1000; cnf2_qtl_scan_boot) for the confidence interval of a QTL's position, after the other scans
+// where they are given, on the same sweep's rows.  F is described at qtlboot_scan below.
 // --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
@@ -183,6 +188,10 @@ struct Options {
     double      qtl_window = 0.0;        // --qtl-window X: a cofactor is left out within X map units of itself
     bool        qtlcof_extra_set = false; // one of the two above was given
     std::vector<int32_t> qtlcof_cof;     // the cofactors, ascending
+    std::string qtlboot;                 // --qtlboot F: bootstrap of the scan (with --phenofile, --qtl-covariates, --qtl-seed, --qtl-additive)
+    int         qtl_boot_chrom = 0;      // --qtl-boot-chrom C: the chromosome, from 1
+    int         qtl_boot_replicates = 1000;   // --qtl-boot-replicates B
+    bool        qtlboot_extra_set = false; // one of the two above was given
     std::vector<int> qtlx_cov_cols;      // columns of pheno: the interactive covariates first, then the others
     int         qtlx_n_int = 0;
     PhenoTable  pheno;                   // P as read (main, before any rank starts)
@@ -296,6 +305,15 @@ static bool parse(int argc, char** argv, Options& o)
                 exit(2);
             }
         }
+        else if (a == "--qtlboot") o.qtlboot = val();
+        else if (a == "--qtl-boot-chrom") {
+            o.qtl_boot_chrom    = atoi(val().c_str());
+            o.qtlboot_extra_set = true;
+        }
+        else if (a == "--qtl-boot-replicates") {
+            o.qtl_boot_replicates = atoi(val().c_str());
+            o.qtlboot_extra_set   = true;
+        }
         else if (a == "--qtlbin") o.qtlbin = val();
         else if (a == "--qtl-binary-iterations") {
             o.qtlbin_iterations = atoi(val().c_str());
@@ -354,6 +372,7 @@ static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
 static void qtlem_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -452,6 +471,9 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
         qtlbin_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty());
     if (world == 1 && !opt.qtlcof.empty())
         qtlcof_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty());
+    if (world == 1 && !opt.qtlboot.empty())
+        qtlboot_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
+                                      !opt.qtlcof.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1188,6 +1210,106 @@ static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool row
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlcof);
 }
 
+// --qtlboot after the last round (single GPU), and after the other scans where they are given: the non-parametric bootstrap
+// of the scan on chromosome --qtl-boot-chrom (cnf2_qtl_scan_boot) on the rows a cnf2_sweep_qtl left in the context -- theirs,
+// or one of this function's own.  Traits are grouped by their pattern of missing values as for --qtl; a group's replicates
+// draw among its own individuals (cnf2h_qtl_bootstrap_counts' rule with --qtl-seed), and one more replicate, everybody once,
+// is the observed scan.  The file: per trait "name<TAB>marker<TAB>pos<TAB>pos_lo<TAB>pos_hi<TAB>lo<TAB>hi<TAB>V" -- the marker
+// (map index from 0; "-" and "-" where the observed scan cannot be fitted) and position of the observed scan's largest LOD on
+// the chromosome, the 95 % bootstrap interval (qtl.boot_interval: the positions number floor(0.025 V) and ceil(0.975 V) - 1
+// of the V usable replicates' best positions in ascending order) as positions and as markers, four "-" when V is 0, and V;
+// after a blank line per marker of the chromosome "chrom<TAB>pos" and per trait the share of the V replicates that chose it
+// ("%.5lf").
+static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), B = opt.qtl_boot_replicates;
+    const int chrom = opt.qtl_boot_chrom - 1, first = P.chromstarts[chrom], L = P.chromstarts[chrom + 1] - first;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    std::vector<int32_t> peak(T, -1), lo(T, -1), hi(T, -1), V(T, 0);
+    std::vector<double>  share((size_t)T * L, 0.0);
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double> yg((size_t)N * Tg);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc;
+        if (!rows_kept) {          // the sweep, with the rows left in the context; its single-locus scan is not reported
+            const int            M = P.n_markers();
+            std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), l1((size_t)Tg * M), c1((size_t)Tg * M * 2), r1((size_t)Tg * C);
+            std::vector<int32_t> k1(M), n1(C);
+            rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                l1.data(), c1.data(), k1.data(), r1.data(), n1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlboot: ") + cnf2_last_error(ctx));
+            rows_kept = true;
+        }
+        // replicate 0 draws everybody once: the observed scan; the B others follow
+        std::vector<int32_t> count((size_t)(B + 1) * N);
+        for (int j = 0; j < N; j++) count[j] = u[j] ? 1 : 0;
+        qtl_bootstrap_counts(N, B, opt.qtl_seed, u.data(), nullptr, count.data() + N);
+        std::vector<double>  bmax((size_t)(B + 1) * Tg);
+        std::vector<int32_t> barg((size_t)(B + 1) * Tg), nb(B + 1);
+        rc = cnf2_qtl_scan_boot(ctx, N, nullptr, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, chrom, chrom + 1, B + 1,
+                                count.data(), bmax.data(), barg.data(), nb.data(), nullptr, flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlboot: ") + cnf2_last_error(ctx));
+        for (int t = 0; t < Tg; t++) {
+            const int gt = tr[t];
+            peak[gt] = barg[t];
+            std::vector<int32_t> kept;
+            for (int b = 1; b <= B; b++)
+                if (barg[(size_t)b * Tg + t] >= 0) kept.push_back(barg[(size_t)b * Tg + t]);
+            V[gt] = (int32_t)kept.size();
+            if (kept.empty()) continue;
+            std::stable_sort(kept.begin(), kept.end(), [&](int32_t a, int32_t b) { return P.pos[a] < P.pos[b] || (P.pos[a] == P.pos[b] && a < b); });
+            const int n = V[gt];
+            const int k_lo = std::min(n - 1, std::max(0, (int)floor(0.025 * n + 1e-9)));
+            const int k_hi = std::max(k_lo, std::min(n - 1, std::max(0, (int)ceil(0.975 * n - 1e-9) - 1)));
+            lo[gt] = kept[k_lo], hi[gt] = kept[k_hi];
+            for (int32_t m : kept) share[(size_t)gt * L + (m - first)] += 1.0 / n;
+        }
+    }
+    FILE* out = fopen(opt.qtlboot.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlboot);
+    for (int t = 0; t < T; t++) {
+        fprintf(out, "%s", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str());
+        if (peak[t] >= 0) fprintf(out, "\t%d\t%.5lf", (int)peak[t], P.pos[peak[t]]);
+        else fprintf(out, "\t-\t-");
+        if (V[t] > 0) fprintf(out, "\t%.5lf\t%.5lf\t%d\t%d", P.pos[lo[t]], P.pos[hi[t]], (int)lo[t], (int)hi[t]);
+        else fprintf(out, "\t-\t-\t-\t-");
+        fprintf(out, "\t%d\n", (int)V[t]);
+    }
+    fprintf(out, "\n");
+    for (int k = 0; k < L; k++) {
+        fprintf(out, "%d\t%.5lf", chrom + 1, P.pos[first + k]);
+        for (int t = 0; t < T; t++) fprintf(out, "\t%.5lf", share[(size_t)t * L + k]);
+        fprintf(out, "\n");
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlboot);
+}
+
 // --qtl-cofactors against the map, and the design's width, before anything runs: false with a message
 static bool prepare_qtlcof(Options& opt, const Pedigree& P)
 {
@@ -1743,11 +1865,31 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtlcof FILE needs --qtl-cofactors LIST\n");
         return 2;
     }
+    if (opt.gpus > 1 && !opt.qtlboot.empty()) {
+        fprintf(stderr, "--qtlboot needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlboot.empty() && opt.qtlboot_extra_set) {
+        fprintf(stderr, "--qtl-boot-chrom and --qtl-boot-replicates need --qtlboot FILE\n");
+        return 2;
+    }
+    if (!opt.qtlboot.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlboot FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (!opt.qtlboot.empty() && (opt.qtl_boot_chrom < 1 || opt.qtl_boot_chrom > (int)P.chromstarts.size() - 1)) {
+        fprintf(stderr, "--qtlboot FILE needs --qtl-boot-chrom C with C = 1 .. %d, the chromosomes of the map\n", (int)P.chromstarts.size() - 1);
+        return 2;
+    }
+    if (opt.qtl_boot_replicates < 1 || opt.qtl_boot_replicates > 1000000) {
+        fprintf(stderr, "--qtl-boot-replicates must be 1 .. 1000000\n");
+        return 2;
+    }
     if (opt.qtl_window < 0.0) {
         fprintf(stderr, "--qtl-window must not be negative\n");
         return 2;
     }
-    if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() &&
+    if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
         (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
@@ -1780,7 +1922,7 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-permutations must not be negative\n");
         return 2;
     }
-    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty()) &&
+    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
     if (!opt.qtlcof.empty() && !prepare_qtlcof(opt, P)) return 2;

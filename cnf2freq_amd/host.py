@@ -14,7 +14,8 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
-           "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker"]
+           "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
+           "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -68,6 +69,8 @@ def load():
         L.cnf2h_qtlbin_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_kinship_sums.argtypes = [i32, i32, vp, vp, i32, i32, i32, vp, vp]
         L.cnf2h_qtl_cols_marker.argtypes = [i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+        L.cnf2h_qtl_bootstrap_counts.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
+        L.cnf2h_qtl_boot_marker.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -199,6 +202,43 @@ def qtl_cols_marker(reg, x0, y, scale=None):
     if rc != 0:
         raise ValueError("cnf2h_qtl_cols_marker refused its arguments (%d)" % rc)
     return dict(lod=lod, coef=coef, rank=int(rank[0]), rss0=rss0)
+
+
+def qtl_bootstrap_counts(n, B, seed, use=None, strata=None):
+    """cnf2h_qtl_bootstrap_counts: count[B][n] by the rule of cnf2freq_amd.qtl.bootstrap_counts, as `cnF2freq --qtlboot` makes
+    them.  CPU only."""
+    L = load()
+    u = None if use is None else np.ascontiguousarray(np.asarray(use) != 0, np.uint8)
+    st = None if strata is None else np.ascontiguousarray(strata, np.int32)
+    out = np.zeros((B, n), np.int32)
+    rc = L.cnf2h_qtl_bootstrap_counts(n, B, seed, None if u is None else _p(u), None if st is None else _p(st), _p(out))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtl_bootstrap_counts failed (%d)" % rc)
+    return out
+
+
+def qtl_boot_marker(origin, y, count, cov=None, c=None, additive=False):
+    """cnf2h_qtl_boot_marker: one (replicate, marker) cell of the bootstrap scan (cnf2_qtl_scan_boot) on the marker's rows
+    origin[n][4], the columns y[n][T] and cov[n][K] as they enter the sums, the chromosome's mask c[n] (None: all) and the
+    replicate count[n].  A dict: lod[T], coef[T][2], rank, rss0[T], n_bc.  CPU only."""
+    L = load()
+    o = np.ascontiguousarray(origin, np.float64)
+    n = o.shape[0]
+    v = np.ascontiguousarray(y, np.float64).reshape(n, -1)
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    w = np.ascontiguousarray(count, np.int32)
+    if o.shape != (n, 4) or m.shape != (n,) or w.shape != (n,):
+        raise ValueError("origin must be [n][4], c and count [n]")
+    T = v.shape[1]
+    lod, coef, rss0 = np.zeros(T), np.zeros((T, 2)), np.zeros(T)
+    rank, n_bc = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_qtl_boot_marker(n, _p(o), T, _p(v), K, None if K == 0 else _p(z), _p(m), _p(w), int(additive), _p(lod), _p(coef),
+                                 _p(rank), _p(rss0), _p(n_bc))
+    if rc != 0:
+        raise ValueError("cnf2h_qtl_boot_marker refused its arguments (%d)" % rc)
+    return dict(lod=lod, coef=coef, rank=int(rank[0]), rss0=rss0, n_bc=int(n_bc[0]))
 
 
 def qtlx_columns(n_cov, n_int=0, additive=False, imprint=False):

@@ -25,7 +25,12 @@ forward_select builds the model a locus at a time against permutation thresholds
 The polygenic scan (Context.kinship_sums, Context.qtl_scan_cols; cnf2_kinship_sums, cnf2_qtl_scan_cols) drops the assumption
 that individuals are independent given the tested locus: kinship makes the realised kinship from the origin rows (also
 leaving one chromosome out), est_herit estimates the heritability, and scan_lmm scans the linear mixed model on columns
-rotated by the kinship's eigenvectors; thresholds and peaks read it as they read scan."""
+rotated by the kinship's eigenvectors; thresholds and peaks read it as they read scan.
+
+The bootstrap scan (Context.qtl_scan_boot, cnf2_qtl_scan_boot) says where a QTL sits: bootstrap_counts draws the individuals
+with replacement, scan_boot scans a chromosome again for every replicate in one call, and boot_interval turns the
+replicates' best markers into a confidence interval of the position.  bayes_interval is the credible interval read off one
+profile (the 10^LOD posterior); peaks keeps its LOD-drop interval."""
 import numpy as np
 
 from . import synth
@@ -584,6 +589,140 @@ def peaks(lod, pos, chromstarts, threshold, drop=1.5, coef=None):
                 p["additive"], p["dominance"] = (float(v) for v in np.asarray(coef)[t, m])
             found.append(p)
     return found
+
+
+# ------------------------------------------------------------------------------------------------
+# Where a QTL sits: the bootstrap of the scan and the posterior of the position
+# ------------------------------------------------------------------------------------------------
+def bootstrap_counts(n, B, seed, use=None, strata=None):
+    """count[B][n] (int32): how often replicate b draws individual i, for Context.qtl_scan_boot.  Within every stratum the k
+    used individuals, in ascending order, are idx[0..k); draw j of replicate b -- one per used individual j -- picks
+    idx[floor(u * k)] of j's stratum with u = synth.uniform(seed, b * n + j), the keys of permutations().  Every row sums to
+    the used individuals of each stratum and unused individuals get 0.  No sequential generator enters, so the same lines
+    in another language give the same arrays (cnf2h_qtl_bootstrap_counts of the host library, which `cnF2freq --qtlboot`
+    uses)."""
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    strata = np.zeros(n, np.int64) if strata is None else np.asarray(strata)
+    if use.shape != (n,) or strata.shape != (n,):
+        raise ValueError("use and strata must be [n]")
+    count = np.zeros((B, n), np.int32)
+    groups = [np.flatnonzero(use & (strata == s)) for s in np.unique(strata[use])] if use.any() else []
+    for b in range(B):
+        u = synth.uniform(seed, np.uint64(b) * np.uint64(n) + np.arange(n, dtype=np.uint64))
+        for idx in groups:
+            k = len(idx)
+            pick = idx[np.minimum(k - 1, np.floor(u[idx] * k).astype(np.int64))]
+            count[b] += np.bincount(pick, minlength=n).astype(np.int32)
+    return count
+
+
+def scan_boot(ctx, pheno, chrom, replicates=1000, seed=0, cov=None, use=None, strata=None, additive=False, rows=None,
+              profile=False):
+    """The non-parametric bootstrap of the scan on the context's uploaded pedigree (Visscher, Thompson and Haley 1996): the
+    individuals are drawn with replacement (bootstrap_counts, within strata if given), chromosome `chrom` -- or the range
+    (chrom_begin, chrom_end) -- is scanned again for every replicate, and the replicates' best markers are returned for
+    boot_interval.  One origin sweep with the rows left on the device (or `rows`, the tensor of origin_rows), then per pattern
+    of missing phenotypes (NaN) one Context.qtl_scan_boot_device call that draws among the pattern's own individuals.  A
+    dict: boot_max[B][T][C'], boot_arg[B][T][C'] (global marker indices; -1 where a replicate cannot be fitted),
+    n_boot[B][T][C'], count[T][B][n], and with profile boot_lod[B][T][M'] (else None)."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    c0, c1 = (chrom, chrom + 1) if np.ndim(chrom) == 0 else (int(chrom[0]), int(chrom[1]))
+    if not 0 <= c0 < c1 <= ctx.n_chrom:
+        raise ValueError("the chromosome range must be non-empty and within 0 .. %d" % ctx.n_chrom)
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    B, Cn = replicates, c1 - c0
+    Mn = int(ctx.chromstarts[c1] - ctx.chromstarts[c0])
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(boot_max=np.zeros((B, T, Cn)), boot_arg=np.full((B, T, Cn), -1, np.int32), n_boot=np.zeros((B, T, Cn), np.int32),
+               count=np.zeros((T, B, n), np.int32), boot_lod=np.zeros((B, T, Mn)) if profile else None)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        count = bootstrap_counts(n, B, seed, use=u, strata=strata)
+        got = ctx.qtl_scan_boot_device(n, d_o.data_ptr(), yk, count, c0, c1, cov=cov, use=u, additive=additive, profile=profile)
+        out["boot_max"][:, cols], out["boot_arg"][:, cols] = got["boot_max"], got["boot_arg"]
+        out["n_boot"][:, cols], out["count"][cols] = got["n_boot"][:, None, :], count
+        if profile:
+            out["boot_lod"][:, cols] = got["boot_lod"]
+    return out
+
+
+def boot_interval(arg, pos, level=0.95):
+    """The bootstrap confidence interval of a QTL's position from arg[B], the best marker of every replicate on one
+    chromosome (boot_arg of scan_boot for one trait and chromosome).  Replicates with arg = -1 are left out and counted.
+    The positions of the V others, sorted, are p_(0) .. p_(V-1); with alpha = 1 - level the interval runs from
+    p_(floor(alpha/2 * V)) to p_(ceil((1 - alpha/2) * V) - 1) (the products are taken within 1e-9, so that 0.975 * 200 is
+    195).  A dict: pos_lo, pos_hi, lo, hi (their markers; of equal positions the lower marker sorts first), V, left_out,
+    and share[len(pos)], the share of the V replicates that chose each marker.  Without a usable replicate the positions
+    are NaN and the markers -1."""
+    arg = np.asarray(arg, np.int64).ravel()
+    pos = np.asarray(pos, np.float64)
+    if not 0.0 < level < 1.0:
+        raise ValueError("level must lie between 0 and 1")
+    if np.any(arg < -1) or np.any(arg >= len(pos)):
+        raise ValueError("arg must hold marker indices or -1")
+    kept = arg[arg >= 0]
+    V = len(kept)
+    share = np.bincount(kept, minlength=len(pos)) / max(V, 1)
+    r = dict(pos_lo=np.nan, pos_hi=np.nan, lo=-1, hi=-1, V=V, left_out=len(arg) - V, share=share)
+    if V:
+        order = kept[np.lexsort((kept, pos[kept]))]
+        alpha = 1.0 - level
+        k_lo = min(V - 1, max(0, int(np.floor(alpha / 2 * V + 1e-9))))
+        k_hi = min(V - 1, max(0, int(np.ceil((1.0 - alpha / 2) * V - 1e-9)) - 1))
+        lo, hi = int(order[k_lo]), int(order[max(k_hi, k_lo)])
+        r.update(pos_lo=float(pos[lo]), pos_hi=float(pos[hi]), lo=lo, hi=hi)
+    return r
+
+
+def bayes_interval(lod, pos, chromstarts, chrom, prob=0.95):
+    """The Bayes credible interval of a QTL's position on chromosome `chrom` from one trait's profile lod[M]: the posterior
+    of a single QTL under a flat prior along the map is proportional to 10^LOD; every marker stands for the stretch of map
+    nearest to it, half of each gap to its neighbours (the markers of a chromosome without length count alike).  Returned is
+    the shortest run of neighbouring markers, by map length, that holds at least `prob` -- of equally short runs the one
+    with more mass, then the leftmost.  A dict: lo, hi (markers), pos_lo, pos_hi, mass (what the run holds) and
+    posterior[markers of the chromosome]."""
+    lod = np.asarray(lod, np.float64).ravel()
+    pos = np.asarray(pos, np.float64)
+    cs = np.asarray(chromstarts, np.int64)
+    if not 0 <= chrom < len(cs) - 1 or len(lod) != len(pos):
+        raise ValueError("chrom must be a chromosome of the map and lod one value per marker")
+    if not 0.0 < prob <= 1.0:
+        raise ValueError("prob must lie in (0, 1]")
+    f, e = int(cs[chrom]), int(cs[chrom + 1])
+    p, l = pos[f:e], lod[f:e]
+    L = e - f
+    width = np.zeros(L)
+    if L > 1:
+        gap = np.diff(p)
+        width[:-1] += gap / 2
+        width[1:] += gap / 2
+    if not width.sum() > 0:
+        width = np.ones(L)
+    post = width * 10.0 ** (l - l.max())
+    post = post / post.sum()
+    cum = np.concatenate([[0.0], np.cumsum(post)])
+    best = None
+    for i in range(L):
+        for j in range(i, L):
+            mass = cum[j + 1] - cum[i]
+            if mass >= prob - 1e-12:
+                key = (p[j] - p[i], -mass, i)
+                if best is None or key < best[0]:
+                    best = (key, i, j, mass)
+                break
+    if best is None:                  # (rounding alone: the whole chromosome holds 1)
+        best = (None, 0, L - 1, 1.0)
+    _, i, j, mass = best
+    return dict(lo=f + i, hi=f + j, pos_lo=float(p[i]), pos_hi=float(p[j]), mass=float(mass), posterior=post)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -730,6 +730,43 @@ int cnf2_qtl_scan_cols(cnf2_ctx *ctx, int n, int n_mark, int ne, const double *r
                        double *coef_out /* [T][n_mark][2] */, int32_t *rank_out /* [n_mark] */, double *rss0_out /* [T] */,
                        double *perm_max_out /* [P][T] */, uint32_t flags);
 
+/* Bootstrap scan: cnf2_qtl_scan on resampled individuals, for the confidence interval of a QTL's position (Visscher, Thompson
+ * and Haley 1996; scanoneboot of other packages).  A replicate draws the individuals with replacement, the chromosome is
+ * scanned again, and the replicates' best positions form the interval (qtl.boot_interval of the Python package).  One
+ * definition for this header, cnf2freq_amd/csrc/cnf2_qtlboot.h, the kernels and tests/qtlboot_reference.py.
+ * origin, pheno, use, cov (0 <= K <= 8), the mask c of a chromosome (an individual whose row at the chromosome's first marker
+ * is all zero is skipped there), X0, a, d and CNF2_QTL_ADDITIVE are cnf2_qtl_scan's.  The chromosomes chrom_begin ..
+ * chrom_end-1 are scanned, C' = chrom_end - chrom_begin >= 1, M' their markers.  count[B][n] (int32, B >= 1): individual i
+ * occurs count[b][i] times in replicate b; it is >= 0, and 0 where use is 0.
+ * Per replicate b and chromosome c, with the weights w_i = count[b][i] c_i: n_bc = sum w_i, S11 = X0'WX0 with its Cholesky
+ * factor, b0 = X0'Wy, RSS0 = y'Wy - b0' S11^-1 b0.  The replicate is usable there when the factor exists, n_bc >= K + 4, and
+ * no covariate takes one single value on all its individuals with w_i > 0 (compared as values: such a column is a multiple
+ * of the intercept, which rounding alone would leave to the factor's last pivot).  Per replicate and marker S21 = A'WX0,
+ * S22 = A'WA and v = A'Wy - G b0 go through the rank rule (pivot threshold 1e-8), the clamps and the logarithm of
+ * cnf2freq_amd/csrc/cnf2_qtl.h with n_bc for n_c: ordinary least squares on the resampled data set.  Traits and covariates
+ * are centred by their unweighted means over the used individuals, as in every scan; the intercept takes up the rest.
+ * Outputs: boot_max_out[B][T][C'] the largest LOD of the chromosome, 0 when the replicate is unusable there;
+ * boot_arg_out[B][T][C'] (int32) the global index of the marker that has it, the lowest among equal maxima (so the
+ * chromosome's first marker when every LOD is 0), -1 when unusable; n_boot_out[B][C'] (int32) n_bc; boot_lod_out[B][T][M']
+ * or NULL the whole profiles (all 0 where unusable).  Host pointers, or device pointers with CNF2_OUT_DEVICE.  origin is a
+ * host pointer, or with CNF2_QTL_ORIGIN_DEVICE a device pointer read in place -- NULL: the rows the context's last
+ * cnf2_sweep_qtl left, by cnf2_qtl_scan's rules (CNF2_ERR_STATE when there are none for n); the call leaves them valid.
+ * pheno, use, cov and count are host pointers.  A NULL pointer, K, B or the chromosome range out of range, a used value that
+ * is not finite, a negative count and a count on an unused individual return CNF2_ERR_ARG and write nothing.
+ * Launches: the masks; per tile of replicates (a multiple of 16; results do not depend on it) the weight image W[n][B]
+ * (doubles), a record per (replicate, chromosome) and trait, the product, the finish.  The product has cnf2_qtl_scan's
+ * shape with the weight image for the column image: a wave owns 16 markers x 16 replicates, walks the individuals in
+ * ascending order four per v_mfma_f64_16x16x4_f64, and forms the marker operand of every weighted sum (a a, a d, d d, a x_k,
+ * d x_k, a y_t, d y_t) in registers from the origin rows read in place; cell, profile and the tile's (maximum, marker) follow
+ * in registers.  More than four traits are taken in chunks that repeat the design sums.  No atomics, every sum over the
+ * individuals in ascending order: a call gives the same bits every time, with and without boot_lod_out, from host or
+ * device rows, whatever the chunking. */
+int cnf2_qtl_scan_boot(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                       int n_cov, const double *cov, int chrom_begin, int chrom_end, int n_boot,
+                       const int32_t *count /* [B][n] */, double *boot_max_out /* [B][T][C'] */,
+                       int32_t *boot_arg_out /* [B][T][C'] */, int32_t *n_boot_out /* [B][C'] */,
+                       double *boot_lod_out /* [B][T][M'] or NULL */, uint32_t flags);
+
 /* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
  * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;
  * where a row is soft it leaves the within-individual genotype variance in the residual.  One definition for this header,

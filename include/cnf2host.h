@@ -202,6 +202,23 @@ int cnf2h_kinship_sums(int n, int n_markers, const double *origin, const int32_t
 int cnf2h_qtl_cols_marker(int n, int ne, const double *reg, const double *scale, int nx, const double *x0, int n_col,
                           const double *y, double *lod_out, double *coef_out, int32_t *rank_out, double *rss0_out);
 
+/* The host side of the bootstrap scan (cnf2_qtl_scan_boot of cnf2hip.h; `cnF2freq --qtlboot` uses the first):
+ *  cnf2h_qtl_bootstrap_counts  count_out[n_boot][n] (int32): how often replicate b draws individual i.  Within every stratum
+ *                              (strata[n], NULL = one) the k used individuals (use[n], NULL = all), in ascending order, are
+ *                              idx[0..k); draw j of replicate b, one per used individual j, picks idx[floor(u k)] of j's
+ *                              stratum with u = (splitmix64(seed, b n + j) >> 11) 2^-53, the keys cnf2h_qtl_permutations
+ *                              sorts by.  A row sums to the used individuals of every stratum; unused individuals get 0.  No
+ *                              sequential generator enters: cnf2freq_amd/qtl.py's bootstrap_counts() gives the same arrays
+ *  cnf2h_qtl_boot_marker       one (replicate, marker) cell through cnf2freq_amd/csrc/cnf2_qtl.h, the individuals in ascending
+ *                              order: origin[n][4] the marker's rows, y[n][n_traits] and cov[n][n_cov] as they enter the sums
+ *                              (the scan centres them first), c[n] the chromosome's mask, count[n] the replicate.
+ *                              lod_out[n_traits], coef_out[n_traits][2], *rank_out, rss0_out[n_traits], *n_bc_out.
+ * -2: a bad argument (a negative count among them). */
+int cnf2h_qtl_bootstrap_counts(int n, int n_boot, uint64_t seed, const uint8_t *use, const int32_t *strata, int32_t *count_out);
+int cnf2h_qtl_boot_marker(int n, const double *origin, int n_traits, const double *y, int n_cov, const double *cov,
+                          const uint8_t *c, const int32_t *count, int additive, double *lod_out, double *coef_out,
+                          int32_t *rank_out, double *rss0_out, int32_t *n_bc_out);
+
 #ifdef __cplusplus
 }
 #endif
