@@ -501,7 +501,11 @@ CNF2_HD void line_record_make(uint32_t fl_par, uint32_t fl_tr, uint32_t fl_ot, i
 // handed-down value (root allele f for P = 0, the other one for P = 1).  Same interface as emtab_part_views.  The traced line's
 // term alpha * t0 + beta * t1 is rounded as the ordinary producer rounds it, which is not the same for every entry: the
 // restricted table's entries with bit_tr = 0 fuse the beta product, all others the alpha product.
-template <bool CLASSES, class Out>
+// PACKED: the caller is a packed sweep (fb_unipack_kernel, fb_unipack8_kernel), whose lanes read the unrestricted table at the
+// grandparents' bits clear only (emission_from_row with NR = 2: index bits 1 and 2 are 0), that is entries e = 0 and 4
+// (packed_reads_unrestricted); the other six, all the same value, are not handed to `out`.
+CNF2_HD constexpr bool packed_reads_unrestricted(int e) { return (e & 3) == 0; }
+template <bool CLASSES, bool PACKED = false, class Out>
 CNF2_HD void emtab_part_rec(int P, int f, const Slot& root, const LineRec& r, Out&& out, double cw[2])
 {
     const SlotDirect rv(root);
@@ -533,7 +537,8 @@ CNF2_HD void emtab_part_rec(int P, int f, const Slot& root, const LineRec& r, Ou
     const double va = r.oo * CNF2_FMA2(alpha, r.t0, beta, r.t1);
     const double v0 = (r.bits & LR_LIVE) ? va : 0.0;
 #pragma unroll
-    for (int e = 0; e < 8; e++) out(0, e, v0);
+    for (int e = 0; e < 8; e++)
+        if (!PACKED || packed_reads_unrestricted(e)) out(0, e, v0);
     if (CLASSES) {
         const double vb = r.oo * CNF2_FMA2(beta, r.t1, alpha, r.t0);
 #pragma unroll

@@ -1198,7 +1198,8 @@ __device__ __forceinline__ void load_rec(const KernelParams& p, const FastCtx& c
     r->tq0 = tq.x;
     r->tq1 = tq.y;
 }
-template <bool CLASSES>
+// PACKED: the unrestricted entries a packed sweep reads only (cnf2_emtab.h packed_reads_unrestricted)
+template <bool CLASSES, bool PACKED = false>
 __device__ __forceinline__ void produce_row_rec(const FastCtx& c, double* tab, bool valid, const RawRec& raw)
 {
     if (valid) {
@@ -1214,7 +1215,7 @@ __device__ __forceinline__ void produce_row_rec(const FastCtx& c, double* tab, b
         double  cw[2];
         double* row = tab + c.mi * TAB_STRIDE;
         double* rb  = row + c.idx_base;
-        emtab_part_rec<CLASSES>(c.pc.P, c.pc.f, root, rec,
+        emtab_part_rec<CLASSES, PACKED>(c.pc.P, c.pc.f, root, rec,
                                 [&](int kind, int e, double v) {        // (the entry's place: see produce_row)
                                     const int b = e & 3;
                                     const int k = b == 0 ? 0 : (b == 1 ? c.idx_k01 : (b == 2 ? c.idx_k10 : 6));
@@ -2598,7 +2599,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
         ap_next = load_root_allele(pq, cp, first + 2 + moff, first, last);
         for (int t = 0; t < ntile; t++) {
             const int m0 = first + t * 2;
-            produce_row_rec<false>(cp, tab, m0 + pmt <= last, rraw);
+            produce_row_rec<false, true>(cp, tab, m0 + pmt <= last, rraw);
             // (unconditional: behind a window's end the clamps reload its last tile.  Under a condition the loaded values reach
             // the carried registers through a copy, and that copy waits for every load right here)
             load_rec<0>(pq, cp, rec_row, m0 + 2 + moff, first, last, ap_next, &rraw);
@@ -2762,7 +2763,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
         const int    mi2 = lane >> 3, sub = lane & 7;
         for (int t = ntile - 1; t >= 0; t--) {
             const int m0 = first + t * 2;
-            produce_row_rec<true>(cp, tab, m0 + pmt <= last, rraw);
+            produce_row_rec<true, true>(cp, tab, m0 + pmt <= last, rraw);
             load_rec<-1>(pq, cp, rec_row, m0 - 2 + moff, first, last, ap_next, &rraw);      // (unconditional, as forward)
             ap_next = load_root_allele(pq, cp, m0 - 4 + moff, first, last);
             wave_lds_fence();
@@ -2820,8 +2821,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
 // unrestricted table is one value per part whatever the parent's shift bit, so the chains of a job with equal s0 see the same
 // emissions and carry the same alpha, beta and scales: the lanes that differ in s1 take another job as well (cnf2_lane.h
 // up8_*).  Per job every floating-point operation is fb_unipack_kernel's, on the same operands in the same order.
-//   tile:     1 marker x 8 jobs, table row = job; the producer lane is (part, job), the epilogue's lanes (row, eighth) run once
-//             per marker
+//   tile:     backward: 1 marker x 8 jobs, table row = job; the producer lane is (part, job), the epilogue's lanes (row, eighth)
+//             run once per marker.  Forward: CNF2_UP8_FWD_TILE markers x 8 jobs of compact slots (cnf2_lane.h up8_fwd_*), over
+//             the same region
 //   rows:     a lane forms the four B-side class sums of (s0, s2) once and the row partials for s1 = 1 and then s1 = 0; they
 //             are parked in the job's row in two steps (up8_park), each over what nobody reads any more
 //   rebuild:  the odd marker's rebuild starts from alpha x emission of the even marker, which the forward pass spills beside
@@ -2830,6 +2832,85 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
 //   spill:    UP8_SPILL_ROW doubles per marker pair, stored by the lanes with s2 = 0
 // =====================================================================================
 static_assert(TAB_R == 72 && TAB_2 == 136 && TAB_STRIDE >= 200, "up8_park (cnf2_lane.h) is written for this row layout");
+// markers to a forward tile (cnf2_lane.h up8_fwd_*); 1: the forward pass on one table row a marker, as the backward pass (A/B)
+#ifndef CNF2_UP8_FWD_TILE
+#define CNF2_UP8_FWD_TILE 8
+#endif
+// markers of a tile whose slots a recursion lane reads at a time, in front of their steps (ten doubles a marker)
+#ifndef CNF2_UP8_FWD_READ
+#define CNF2_UP8_FWD_READ 2
+#endif
+static_assert(CNF2_UP8_FWD_TILE == 1 || (CNF2_UP8_FWD_TILE >= 2 && CNF2_UP8_FWD_TILE % 2 == 0), "a forward tile holds an even number of markers");
+static_assert(CNF2_UP8_FWD_TILE == 1 || up8_fwd_buffers(CNF2_UP8_FWD_TILE, 8 * TAB_STRIDE) * CNF2_UP8_FWD_TILE * UP8_FWD_MARKER <= 8 * TAB_STRIDE,
+              "the forward tiles live in the wave's eight table rows");
+// The slot of (marker, job) of a forward tile from the root's data and the record of the lane's line: emtab_part_rec's value
+// of the lane's part (one for all eight unrestricted entries), the root weights and the gap's factors, each by the lane that
+// stores it in a table row (produce_row_rec).  slot: the marker's 128 doubles; the lane's job is c.mi.
+__device__ __forceinline__ void produce_slot_rec(const FastCtx& c, double* slot, const RawRec& raw)
+{
+    const Slot root = unpack_slot(raw.ap, raw.s0, raw.s1, raw.hw);
+    LineRec rec;
+    rec.Bp   = raw.Bp;
+    rec.Cp   = raw.Cp;
+    rec.Kp   = raw.Kp;
+    rec.t0   = raw.t0;
+    rec.t1   = raw.t1;
+    rec.oo   = raw.oo;
+    rec.bits = raw.bits;
+    double  cw[2];
+    double* d = slot + up8_fwd_at(0, c.mi, 0);
+    emtab_part_rec<false, true>(c.pc.P, c.pc.f, root, rec,
+                                [&](int, int e, double v) {
+                                    if (e == 0) d[up8_fwd_at(0, 0, up8_fwd_part(c.part))] = v;
+                                },
+                                cw);
+    if ((c.part & 5) == 0) {
+        d[up8_fwd_at(0, 0, up8_fwd_weight(c.pc.f, 0))] = cw[0];
+        d[up8_fwd_at(0, 0, up8_fwd_weight(c.pc.f, 1))] = cw[1];
+    }
+    if (c.part == 0) {
+        d[up8_fwd_at(0, 0, up8_fwd_gap(0))] = raw.tq0;
+        d[up8_fwd_at(0, 0, up8_fwd_gap(1))] = raw.tq1;
+    }
+}
+// What a forward step of the eights reads, from the job's table row or from its slot of a forward tile.  The slot's emission
+// is emission_from_row's expression on the same values (N = 2, s1 = 0, lo = the class): the same products fuse.
+struct Up8FwdRow {
+    const double*  row;
+    const FastCtx& c;
+    __device__ __forceinline__ void emission(double (&e)[2], double k) const { emission_from_row(row, c, e, k); }
+    __device__ __forceinline__ double2 gap() const { return *(const double2*)(row + TAB_T); }
+};
+// (the slot's ten values of the lane are read when the object is made, so that the caller can place the reads of several
+// markers in front of their steps: behind a step's branches each slot is a round trip of its own in the recursion's chain)
+struct Up8FwdSlot {
+    double w0, a0, w1, a1, B0[2], B1[2], g0, g1;
+    Up8FwdSlot() = default;
+    // a, w: parts (f = 0, class) and root weight c_0(s0) of the lane; b: part 4 of the slot
+    __device__ __forceinline__ Up8FwdSlot(const double* a, const double* w, const double* b)
+    {
+        constexpr int F = up8_fwd_at(0, 0, 2);         // from f = 0 to f = 1: two parts, or two weights, on
+        w0 = w[0];
+        a0 = a[0];
+        w1 = w[F];
+        a1 = a[F];
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+            B0[j] = b[up8_fwd_at(0, 0, j)];
+            B1[j] = b[F + up8_fwd_at(0, 0, j)];
+        }
+        g0 = b[up8_fwd_at(0, 0, up8_fwd_gap(0) - 4)];
+        g1 = b[up8_fwd_at(0, 0, up8_fwd_gap(1) - 4)];
+    }
+    __device__ __forceinline__ void emission(double (&e)[2], double k) const
+    {
+        const double cA0 = w0 * a0 * k;
+        const double cA1 = w1 * a1 * k;
+#pragma unroll
+        for (int j = 0; j < 2; j++) e[j] = cA0 * B0[j] + cA1 * B1[j];
+    }
+    __device__ __forceinline__ double2 gap() const { return make_double2(g0, g1); }
+};
 __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_kernel(KernelParams p)
 {
     constexpr int NR = 2, ROW = UP8_SPILL_ROW, TS = TAB_STRIDE;
@@ -2923,17 +3004,17 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         bool   dead = false;
         double pend = 1.0;
         int    rmask = CNF2_RESCALE_MASK, bmask = CNF2_RESCALE_MASK;   // per job
-        auto fwd_step = [&](auto odd_tag, const double* row, int m) {
+        auto fwd_step = [&](auto odd_tag, const auto& src, int m) {
             constexpr bool ODD = decltype(odd_tag)::value;
             double         e[NR];
-            emission_from_row(row, c, e, pend);
-            const double2 r  = *(const double2*)(row + TAB_T);
+            src.emission(e, pend);
+            const double2 r  = src.gap();
             const int     ml = m - first;
             double*       sp = spill + (size_t)(ml >> 1) * ROW;
             if (!ODD) {
                 // alpha, and alpha x the marker's emission: what the backward pass's rebuild of the odd marker starts from
                 double ep[NR];
-                emission_from_row(row, c, ep);
+                src.emission(ep, 1.0);
                 const d2v v = {a[0], a[1]};
                 const d2v w = {a[0] * ep[0], a[1] * ep[1]};
                 if (vwr) {
@@ -2964,17 +3045,75 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         };
         RawRec  rraw;
         uint8_t ap_next;
-        load_rec<0>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rraw);
-        ap_next = load_root_allele(pq, cp, first + 1 + moff, first, last);
-        for (int m = first; m <= last; m++) {
-            produce_row_rec<false>(cp, tab, true, rraw);
-            // (unconditional, as in fb_unipack_kernel: no copy, so no wait, between these loads and the next marker's producer)
-            load_rec<0>(pq, cp, rec_row, m + 1 + moff, first, last, ap_next, &rraw);
-            ap_next = load_root_allele(pq, cp, m + 2 + moff, first, last);
-            wave_lds_fence();
-            if ((m - first) & 1) fwd_step(odd_t(), myrow, m);
-            else fwd_step(even_t(), myrow, m);
-            wave_lds_fence();
+        if constexpr (CNF2_UP8_FWD_TILE == 1) {
+            // A/B form: a table row per marker, as the backward pass keeps them
+            const Up8FwdRow src{myrow, c};
+            load_rec<0>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rraw);
+            ap_next = load_root_allele(pq, cp, first + 1 + moff, first, last);
+            for (int m = first; m <= last; m++) {
+                produce_row_rec<false, true>(cp, tab, true, rraw);
+                // (unconditional, as in fb_unipack_kernel: no copy, so no wait, between these loads and the next marker's producer)
+                load_rec<0>(pq, cp, rec_row, m + 1 + moff, first, last, ap_next, &rraw);
+                ap_next = load_root_allele(pq, cp, m + 2 + moff, first, last);
+                wave_lds_fence();
+                if ((m - first) & 1) fwd_step(odd_t(), src, m);
+                else fwd_step(even_t(), src, m);
+                wave_lds_fence();
+            }
+        } else {
+            // compact tiles of T markers (cnf2_lane.h up8_fwd_*): the producer lanes walk the tile's markers with the records of two
+            // markers in flight, one fence, and the recursion lanes take T steps with none in between (a second fence behind
+            // them where the region holds one tile only).  T is even: the parity of a marker in its window is that of its place
+            // in the tile.  The loads behind a window's end are clamped to its last marker and their slots are never used.
+            constexpr int T = CNF2_UP8_FWD_TILE, REGION = 8 * TS;
+            // the lane's places in the slot of (marker 0 of buffer 0, its job): the A-side parts of its class, the root weights
+            // of its s0, and the B-side parts with the gap's factors behind them
+            const double* const qa = tab + up8_fwd_at(0, rj, up8_fwd_part(b0));
+            const double* const qc = tab + up8_fwd_at(0, rj, up8_fwd_weight(0, c.s0));
+            const double* const qb = tab + up8_fwd_at(0, rj, up8_fwd_part(4));
+            RawRec  rr[2];
+            uint8_t ap[2];
+            load_rec<0>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rr[0]);
+            load_rec<0>(pq, cp, rec_row, first + 1 + moff, first, last, load_root_allele(pq, cp, first + 1 + moff, first, last), &rr[1]);
+            ap[0] = load_root_allele(pq, cp, first + 2 + moff, first, last);
+            ap[1] = load_root_allele(pq, cp, first + 3 + moff, first, last);
+            int tile = 0;
+            for (int m0 = first; m0 <= last; m0 += T, tile++) {
+                const int toff = up8_fwd_tile(T, REGION, tile);
+#pragma unroll
+                for (int t = 0; t < T; t++) {
+                    produce_slot_rec(cp, tab + toff + up8_fwd_at(t, 0, 0), rr[t & 1]);
+                    // (unconditional, as above; what is asked for here is produced two markers on)
+                    load_rec<0>(pq, cp, rec_row, m0 + t + 2 + moff, first, last, ap[t & 1], &rr[t & 1]);
+                    ap[t & 1] = load_root_allele(pq, cp, m0 + t + 4 + moff, first, last);
+                }
+                wave_lds_fence();
+                // (CNF2_UP8_FWD_READ markers' slots are read in front of the steps that use them: every slot of the tile has been
+                // produced, whether its marker is inside the window or not)
+                auto slot_at = [&](int t) {
+                    const int o = toff + up8_fwd_at(t, 0, 0);
+                    return Up8FwdSlot(qa + o, qc + o, qb + o);
+                };
+                constexpr int RD = CNF2_UP8_FWD_READ < T ? CNF2_UP8_FWD_READ : T;
+                static_assert(T % RD == 0, "a forward tile is read in equal parts");
+#pragma unroll
+                for (int t0 = 0; t0 < T; t0 += RD) {
+                    Up8FwdSlot src[RD];
+#pragma unroll
+                    for (int t = 0; t < RD; t++) src[t] = slot_at(t0 + t);
+#pragma unroll
+                    for (int t = 0; t < RD; t++) {
+                        if (t0 + t == 0 || m0 + t0 + t <= last) {
+                            if ((t0 + t) & 1) fwd_step(odd_t(), src[t], m0 + t0 + t);
+                            else fwd_step(even_t(), src[t], m0 + t0 + t);
+                        }
+                    }
+                }
+                // (one buffer: the next tile goes over this one.  Two: over the one before, whose readers are a fence behind)
+                if (up8_fwd_buffers(T, REGION) == 1) wave_lds_fence();
+            }
+            // the tiles' last readers are done: the region goes to the backward pass's rows, or to the next job's first tile
+            if (up8_fwd_buffers(T, REGION) == 2) wave_lds_fence();
         }
 
         // ---------------------------------------------------------------- likelihoods (per job: its two distinct chains sit
@@ -3137,7 +3276,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         for (int m = last; m >= first; m--) {
             take_spill();
             ask_spill(m - first - 1);
-            produce_row_rec<true>(cp, tab, true, rraw);
+            produce_row_rec<true, true>(cp, tab, true, rraw);
             load_rec<-1>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);       // (unconditional, as forward)
             ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
             wave_lds_fence();

@@ -113,6 +113,24 @@ CNF2_HD int up8_spill_value(int lane) { return 2 * (((lane >> 5) << 4) | (lane &
 CNF2_HD int up8_spill_emit(int lane) { return UP8_SPILL_EMIT + up8_spill_value(lane); }
 CNF2_HD int up8_spill_inv(int job, int s0) { return UP8_SPILL_INV + 2 * (2 * job + s0); }
 
+// Forward tile of that kernel: the forward step of (marker, job) needs 14 doubles -- one value per part (on line records the
+// unrestricted table is one value a part), the root weights c_f(s0) and the gap's two butterfly factors -- and takes them from
+// a compact slot instead of a table row.  A tile is T markers x 8 jobs; a slot is 14 values padded to UP8_FWD_SLOT = 16, kept
+// job-minor: value i of (t, job) sits at (t * 16 + i) * 8 + job, so that the 64 producer lanes (part, job) of a marker store 64
+// consecutive doubles and the recursion lanes of the eight jobs read eight consecutive ones (no bank is asked twice).
+//   i = 0..7  part (P << 2 | f << 1 | firstpar);  8 + 2 f + s0  root weight c_f(s0);  12, 13  the gap's factors;  14, 15  unused
+// The wave's region (8 table rows) holds two tiles where 2 T x 128 doubles fit: a tile is produced into the buffer the previous
+// one was not read from, and one fence a tile orders it all (up8_fwd_buffers, up8_fwd_tile).
+enum { UP8_FWD_SLOT = 16, UP8_FWD_VALUES = 14, UP8_FWD_MARKER = 8 * UP8_FWD_SLOT };
+CNF2_HD constexpr int up8_fwd_buffers(int T, int region) { return 2 * T * UP8_FWD_MARKER <= region ? 2 : 1; }
+// first double of tile number `tile` (its buffer) in the wave's region
+CNF2_HD constexpr int up8_fwd_tile(int T, int region, int tile) { return up8_fwd_buffers(T, region) == 2 ? (tile & 1) * T * UP8_FWD_MARKER : 0; }
+// value i of (marker t of the tile, job), from the tile's first double
+CNF2_HD constexpr int up8_fwd_at(int t, int job, int i) { return (t * UP8_FWD_SLOT + i) * 8 + job; }
+CNF2_HD constexpr int up8_fwd_part(int part) { return part; }
+CNF2_HD constexpr int up8_fwd_weight(int f, int s0) { return 8 + 2 * f + s0; }
+CNF2_HD constexpr int up8_fwd_gap(int k) { return 12 + k; }
+
 CNF2_HD int tie_force(int8_t tie, int combo)
 {
     return tie < 0 ? -1 : ((combo >> tie) & 1);
