@@ -7,12 +7,27 @@ With an intercept in X0 the model of include/cnf2hip.h does not depend on the un
 iterations, status and perm_max stay, the effects scale with alpha (an interaction with z_k with alpha / gamma_k), rss0 and
 sigma2 with alpha^2.  The float64 yardsticks are themselves off by 1e-10 .. 1e-9 on a trait shifted by 2^17, so the reference
 of a transformed problem is the yardstick on the base problem, carried over by map_reference.  The binary-trait scan has a
-section of its own at the end: covariate transforms, the complement of the trait, the same relabellings, map_bin_reference."""
+section of its own: covariate transforms, the complement of the trait, the same relabellings, map_bin_reference.
+
+Three newer scans follow it, each with the same base cases, the same eight transforms and four relabellings, and a map of its
+own.  The cofactor scan (cofactors 22 and 60 with +-3 markers left out; 7, 43 and 70 with +-2 under the largest shifts and the
+reordering): map_cof_reference, compared by qtlcof_reference.compare_cof.  The bootstrap scan (21 replicates, a full replicate
+tile and a partial one, all six chromosomes with the profile): the map is the identity, the counts go with their individuals
+under the reordering, and reversing the replicates reverses every output to the bit; compared by qtlboot_reference.compare
+on the cells of its conditions.  The polygenic scan (qtl.scan_lmm with h2 given and a chromosome left out of the kinship, and
+with h2 estimated by REML): the reference is the Cholesky yardstick of the base problem at the given h2, or at the h2 the run
+returned, carried over by map_lmm_reference; the estimated h2 itself is held to the base problem's likelihood grid, not to
+another run (est_herit's golden section ends 1e-8 wide on a likelihood that is flat to rounding over 1e-7).  Last, what the
+polygenic scan is made of: the kinship sums under the relabellings (check_kinship_relabellings) and the column scan, which
+centres nothing and adds no intercept, under the scalings its model is invariant to (cols_problems)."""
 import numpy as np
 
 import qtl2_reference as R2
 import qtlbin_reference as RB
+import qtlboot_reference as RO
+import qtlcof_reference as RC
 import qtlem_reference as RE
+import qtllmm_reference as RL
 import qtlx_reference as RX
 from cnf2freq_amd import qtl
 from qtl_reference import ATOL, CHROM_LENS, chromstarts_of, compare, noise, reference_scan, skip, soft_rows  # noqa: F401
@@ -396,3 +411,321 @@ def bin_errors(got, ref):
 
 def bin_bit_equal(a, b):
     return bit_equal(a, b, BIN_FLOAT_KEYS + BIN_INT_KEYS)
+
+
+# ------------------------------------------------------------------------------------------------ the cofactor scan
+# Composite interval mapping on the base cases: the cofactors' columns join the design, so the model stays invariant as the
+# plain scan's is.  lod, lod_base, rank, rank_cof, n_used and perm_max stay, the marker's effects scale with alpha (a changes
+# sign under swap03; the scan has no i, so swap12 changes nothing), rss0 with alpha^2; covariate transforms change nothing.
+COF_SCANS = {"cof-full": dict(additive=False), "cof-add": dict(additive=True)}
+COF = ((22, 60), 3)              # (cofactors, half-window in markers): chromosomes 4 and 6
+COF3 = ((7, 43, 70), 2)          # none on chromosome 3, where n67-skip skips two individuals: n_used differs by chromosome
+
+COF_FLOAT_KEYS = ("lod", "lod_base", "coef", "rss0", "perm_max")
+COF_INT_KEYS = ("rank", "rank_cof", "n_used")
+
+
+def cof_coef_names(scan):
+    return ("a",) if COF_SCANS[scan]["additive"] else ("a", "d")
+
+
+def cof_run(ctx, scan, inp, config=COF):
+    """Context.qtl_scan_cof on the inputs `inp` with the cofactors and the half-window of `config`"""
+    cof, hw = config
+    return ctx.qtl_scan_cof(inp["origin"], inp["pheno"], cof, excl=RC.windows(cof, hw, CS), cov=inp["cov"], use=inp["use"],
+                            perm=inp["perm"], additive=COF_SCANS[scan]["additive"])
+
+
+def cof_reference(scan, inp, config=COF):
+    """the cofactor scan's float64 yardstick on the inputs `inp`"""
+    cof, hw = config
+    lo, hi = RC.windows(cof, hw, CS)
+    return RC.reference_scan_cof(inp["origin"], CS, inp["pheno"], cof, lo, hi, inp["use"], inp["cov"], inp["perm"],
+                                 COF_SCANS[scan]["additive"])
+
+
+_COF_REFS = {}
+
+
+def cof_base_reference(case, scan, config=COF):
+    """the yardstick of a cofactor scan on a base case, computed once and shared"""
+    if (case, scan, config) not in _COF_REFS:
+        _COF_REFS[case, scan, config] = cof_reference(scan, make_base(case), config)
+    return _COF_REFS[case, scan, config]
+
+
+def map_cof_reference(ref, alpha=1.0, flip=()):
+    """The expected outputs of the transformed problem from a base reference of the cofactor scan (with 1 / alpha: the base
+    form of a transformed problem's outputs): coef[T][M][ne] is multiplied by alpha per trait, and by -1 for a when "a" is in
+    `flip`; rss0[T][C] by alpha^2; everything else stays."""
+    out = dict(ref)
+    alpha = np.broadcast_to(np.asarray(alpha, np.float64), (ref["rss0"].shape[0],))
+    f = np.ones((len(alpha), 1, ref["coef"].shape[2])) * alpha[:, None, None]
+    if "a" in flip:
+        f[:, :, 0] *= -1.0
+    out["coef"] = ref["coef"] * f
+    out["rss0"] = ref["rss0"] * (alpha ** 2)[:, None]
+    return out
+
+
+def cof_as_got(ref):
+    """a yardstick's dict in the form of the product's outputs"""
+    return dict(ref, lod=ref["lod"][0], lod_base=ref["lod_base"][0], perm_max=ref["perm_max"] if ref["perm_max"].shape[0] else None)
+
+
+def cof_errors(got, ref):
+    return errors(got, ref, COF_FLOAT_KEYS, COF_INT_KEYS)
+
+
+def cof_bit_equal(a, b):
+    return bit_equal(a, b, COF_FLOAT_KEYS + COF_INT_KEYS)
+
+
+# ------------------------------------------------------------------------------------------------ the bootstrap scan
+# Every replicate is a scan of resampled individuals, and only LODs and the places of their maxima come out: the map is the
+# identity under every transform and relabelling.  Under the reordering the counts go with their individuals.
+BOOT_SCANS = {"boot-full": dict(additive=False), "boot-add": dict(additive=True)}
+BOOT_B, BOOT_SEED = 21, 5        # one full replicate tile of 16 and a partial one
+
+BOOT_KEYS = ("boot_max", "boot_arg", "n_boot", "boot_lod")
+
+_BOOT_BASE = {}
+
+
+def make_boot_base(case):
+    """make_base(case) with count[B][n] = qtl.bootstrap_counts(n, 21, 5, use=use) added.  Computed once and shared."""
+    if case not in _BOOT_BASE:
+        base = make_base(case)
+        _BOOT_BASE[case] = dict(base, count=qtl.bootstrap_counts(case[1], BOOT_B, BOOT_SEED, use=base["use"]))
+    return _BOOT_BASE[case]
+
+
+def boot_relabel(base, name):
+    """relabel(base, name) of a base with counts: under `reorder` the counts are reordered too, count[:, s]"""
+    inp, _ = relabel(base, name)
+    count = base["count"][:, order_of(base["count"].shape[1])] if name == "reorder" else base["count"]
+    return dict(inp, count=np.ascontiguousarray(count))
+
+
+def boot_run(ctx, scan, inp):
+    """Context.qtl_scan_boot on the inputs `inp`: all six chromosomes, with the profile"""
+    return ctx.qtl_scan_boot(inp["origin"], inp["pheno"], inp["count"], cov=inp["cov"], use=inp["use"],
+                             additive=BOOT_SCANS[scan]["additive"], profile=True)
+
+
+def boot_reference(scan, inp):
+    """the bootstrap scan's yardstick (literally resampled rows) on the inputs `inp`"""
+    return RO.reference_boot(inp["origin"], CS, inp["pheno"], inp["count"], inp["use"], inp["cov"], BOOT_SCANS[scan]["additive"])
+
+
+_BOOT_REFS = {}
+
+
+def boot_base_reference(case, scan):
+    """(the yardstick of a bootstrap scan on a base case, compared[B][T][C] of its conditions), computed once and shared; the
+    conditions are asserted here, on the reference alone"""
+    if (case, scan) not in _BOOT_REFS:
+        ref = boot_reference(scan, make_boot_base(case))
+        _BOOT_REFS[case, scan] = (ref, RO.conditions(ref, K, BOOT_SCANS[scan]["additive"], "%s %s" % (scan, case[0])))
+    return _BOOT_REFS[case, scan]
+
+
+def boot_as_got(ref):
+    """a yardstick's dict in the form of the product's outputs"""
+    return dict(boot_max=ref["boot_max"], boot_arg=ref["boot_arg"], n_boot=ref["n_boot"], boot_lod=ref["lod"])
+
+
+def boot_errors(got, ref, compared=None):
+    """figures for the log: ref a yardstick's dict or outputs of the product; boot_arg counted on the compared cells"""
+    ref = boot_as_got(ref) if "lod" in ref else ref
+    differ = got["boot_arg"] != ref["boot_arg"]
+    return dict(boot_lod=float(np.abs(got["boot_lod"] - ref["boot_lod"]).max()), boot_max=float(np.abs(got["boot_max"] - ref["boot_max"]).max()),
+                boot_arg=int(differ.sum() if compared is None else differ[compared].sum()), n_boot=int((got["n_boot"] != ref["n_boot"]).sum()))
+
+
+def boot_bit_equal(a, b):
+    return bit_equal(a, b, BOOT_KEYS)
+
+
+# ------------------------------------------------------------------------------------------------ the polygenic scan
+# qtl.scan_lmm centres traits and covariates itself (numpy) and hands rotated, whitened columns to cnf2_qtl_scan_cols, which
+# centres nothing.  lod, rank, n_used and h2 stay, the effects scale with alpha (a changes sign under swap03; a_i a_j, hence
+# the kinship, does not), sigma2 with alpha^2.  The reference is always the Cholesky yardstick on the BASE problem, mapped: at
+# the given h2, or at the h2 the run under test returned.
+LMM_SCANS = {"lmm-given": dict(loco=True, h2=(0.3, 0.8), permutations=3),
+             "lmm-est": dict(loco=False, h2=None, permutations=0)}
+LMM_SEED = 4
+LMM_H2_BOUND = 1e-4              # the step of the grid of qtllmm_reference.grid_herit
+
+
+def lmm_keep(inp):
+    """the individuals scan_lmm analyses: used, and skipped on no chromosome"""
+    o = inp["origin"]
+    use = np.ones(o.shape[0], bool) if inp["use"] is None else inp["use"]
+    return use & (o[:, CS[:-1]] != 0.0).any(axis=2).all(axis=1)
+
+
+_LMM_KIN = {}
+
+
+def lmm_base_kinship(case, loco):
+    """K[C][n][n] by the yardstick on the base rows: without chromosome c, or the genome's repeated"""
+    if (case, loco) not in _LMM_KIN:
+        o = make_base(case)["origin"]
+        C = len(CS) - 1
+        _LMM_KIN[case, loco] = np.stack([RL.kinship_ref(o, CS, leave_out=c) for c in range(C)]) if loco else \
+            np.repeat(RL.kinship_ref(o, CS)[None], C, axis=0)
+    return _LMM_KIN[case, loco]
+
+
+def lmm_run(ctx, scan, inp, rows, permutations=None, kinship=None):
+    """qtl.scan_lmm on the inputs `inp` (ctx: a context that holds the map and n_ind; rows: the origin rows as a torch tensor on
+    the device)"""
+    s = LMM_SCANS[scan]
+    return qtl.scan_lmm(ctx, inp["pheno"], kinship=kinship, loco=s["loco"], cov=inp["cov"], use=inp["use"],
+                        permutations=s["permutations"] if permutations is None else permutations, seed=LMM_SEED, reml=True,
+                        h2=s["h2"], rows=rows)
+
+
+def lmm_given_h2(scan):
+    """h2[T][C] of a scan whose h2 is given"""
+    return np.repeat(np.asarray(LMM_SCANS[scan]["h2"], np.float64)[:, None], len(CS) - 1, axis=1)
+
+
+def lmm_design(inp):
+    """(keep, centred traits [nk][T], [1, centred covariates]) as the model has them"""
+    keep = lmm_keep(inp)
+    y = inp["pheno"][keep] - inp["pheno"][keep].mean(axis=0)
+    z = inp["cov"][keep]
+    return keep, y, np.concatenate([np.ones((keep.sum(), 1)), z - z.mean(axis=0)], axis=1)
+
+
+def lmm_reference(inp, kin, h2):
+    """The Cholesky yardstick (qtllmm_reference.reference_lmm) on the inputs `inp` with the kinships kin[C][n][n] at h2[T][C];
+    added to its dict: h2, n_used[T] and sigma2[T][C] = RSS / (n - nx) of the whitened null model"""
+    keep, y, X0 = lmm_design(inp)
+    ref = RL.reference_lmm(inp["origin"], CS, inp["pheno"], inp["cov"], h2, lambda c: kin[c], keep=keep)
+    sigma2 = np.zeros((y.shape[1], len(CS) - 1))
+    for c in range(sigma2.shape[1]):
+        for t in range(sigma2.shape[0]):
+            (ys, xs), _ = RL.chol_whiten(kin[c][np.ix_(keep, keep)], h2[t][c], y[:, t], X0)
+            r = ys - xs @ np.linalg.lstsq(xs, ys, rcond=None)[0]
+            sigma2[t, c] = (r @ r) / (len(ys) - X0.shape[1])
+    return dict(ref, h2=np.asarray(h2, np.float64), sigma2=sigma2, n_used=np.full(y.shape[1], keep.sum(), np.int32))
+
+
+_LMM_REFS = {}
+
+
+def lmm_base_reference(case, scan):
+    """the yardstick of a polygenic scan with given h2 on a base case, computed once and shared"""
+    if (case, scan) not in _LMM_REFS:
+        _LMM_REFS[case, scan] = lmm_reference(make_base(case), lmm_base_kinship(case, LMM_SCANS[scan]["loco"]), lmm_given_h2(scan))
+    return _LMM_REFS[case, scan]
+
+
+_LMM_GRID = {}
+
+
+def lmm_grid_h2(case, t):
+    """the h2 at the maximum of the REML likelihood of trait t of a base case on the grid of step 1e-4, with the genome's
+    kinship (Cholesky route; asserts a single local maximum).  Computed once per case and trait."""
+    if (case, t) not in _LMM_GRID:
+        keep, y, X0 = lmm_design(make_base(case))
+        K0 = lmm_base_kinship(case, False)[0][np.ix_(keep, keep)]
+        _LMM_GRID[case, t] = RL.grid_herit(K0, y[:, t], X0, reml=True)[0]
+    return _LMM_GRID[case, t]
+
+
+def map_lmm_reference(ref, alpha=1.0, flip=()):
+    """The expected outputs of the transformed problem from a base reference of the polygenic scan (with 1 / alpha: the base
+    form of a transformed problem's outputs): coef[T][M][2] is multiplied by alpha per trait, and by -1 for a when "a" is in
+    `flip`; sigma2[T][C] by alpha^2; lod, rank, n_used and h2 stay."""
+    out = dict(ref)
+    alpha = np.broadcast_to(np.asarray(alpha, np.float64), (ref["coef"].shape[0],))
+    f = np.ones((len(alpha), 1, 2)) * alpha[:, None, None]
+    if "a" in flip:
+        f[:, :, 0] *= -1.0
+    out["coef"] = ref["coef"] * f
+    out["sigma2"] = ref["sigma2"] * (alpha ** 2)[:, None]
+    return out
+
+
+def lmm_check(got, want, what):
+    """qtllmm_reference.compare_lmm, unchanged, at ATOL with at least 0.9 of the cells compared; n_used equal; sigma2 within
+    ATOL relative to max(1, |sigma2|)"""
+    RL.compare_lmm(got, want, what, share=0.9)
+    assert np.array_equal(got["n_used"], want["n_used"]), what + " n_used"
+    err_s = (np.abs(got["sigma2"] - want["sigma2"]) / np.maximum(1.0, np.abs(want["sigma2"]))).max()
+    print("%s: sigma2 %.3g" % (what, err_s))
+    assert err_s <= ATOL, what + " sigma2"
+
+
+LMM_FLOAT_KEYS = ("lod", "coef", "sigma2", "h2", "perm_max")
+LMM_INT_KEYS = ("rank", "n_used")
+
+
+def lmm_errors(got, ref):
+    return errors(got, ref, LMM_FLOAT_KEYS, LMM_INT_KEYS)
+
+
+def lmm_bit_equal(a, b):
+    return bit_equal(a, b, LMM_FLOAT_KEYS + LMM_INT_KEYS)
+
+
+# ------------------------------------------------------------------------------------------------ kinship sums, the column scan
+KIN_RANGES = [(0, 6), (3, 4), (2, 5)]
+
+
+def check_kinship_relabellings(sums, case, tag):
+    """sums(origin, chrom_begin, chrom_end) -> (S[n][n], markers) on the base rows of a case, for every range of KIN_RANGES:
+    under swap03 and swap12 the same bits (a_i a_j does not change); under reorder S' = S[s][:, s] within ATOL and S' equal
+    to its transpose to the bit (whether the reordered matrix is also bit-equal is printed)"""
+    base = make_base(case)
+    s = order_of(case[1])
+    for c0, c1 in KIN_RANGES:
+        S, M = sums(base["origin"], c0, c1)
+        want, Mw = RL.kinship_sums_ref(base["origin"], CS, c0, c1)
+        assert M == Mw and (np.abs(S - want) / np.maximum(1.0, np.abs(want))).max() <= RL.ATOL
+        for name in ("swap03", "swap12"):
+            S2, M2 = sums(relabel(base, name)[0]["origin"], c0, c1)
+            assert M2 == M and same_bits(S2, S), "%s: the sums change under %s" % (tag, name)
+        S3, M3 = sums(relabel(base, "reorder")[0]["origin"], c0, c1)
+        err = (np.abs(S3 - S[s][:, s]) / np.maximum(1.0, np.abs(S[s][:, s]))).max()
+        print("INVARIANCE %s %s chromosomes %d..%d reorder: %.3g, bit-equal %s" % (tag, case[0], c0, c1, err, same_bits(S3, S[s][:, s])))
+        assert M3 == M and err <= RL.ATOL
+        assert same_bits(S3, S3.T), tag + ": the reordered sums are not symmetric to the bit"
+
+
+COLS_CASE = (67, 2, 3, 2, 2, "soft", True)       # n, T, P, nx, ne, rows, scaled (qtllmm_reference.cols_case)
+
+_COLS = []
+
+
+def cols_base():
+    """(inputs, reference) of the column scan's case, computed once and shared"""
+    if not _COLS:
+        reg, x0, pheno, scale, perm = RL.cols_case(*COLS_CASE)
+        _COLS.append((dict(reg=reg, x0=x0, pheno=pheno, scale=scale, perm=perm), RL.cols_reference(reg, x0, pheno, scale, perm)))
+    return _COLS[0]
+
+
+def cols_problems():
+    """[(name, inputs, alpha of the traits, divisor of coef)] of the column scan, whose model centres nothing and adds no
+    intercept: the traits times 2^+-100; x0 @ diag(2^3, 2^-5); reg 2^7 with scale / 2^7; reg 2^7 alone (coef / 2^7); the
+    individuals reordered, perm carried as relabel carries it.  Every factor is a power of two: the inputs stay exact."""
+    inp, _ = cols_base()
+    s = order_of(inp["reg"].shape[0])
+    sinv = np.argsort(s)
+    return [("pheno 2^100", dict(inp, pheno=inp["pheno"] * 2.0 ** 100), 2.0 ** 100, 1.0),
+            ("pheno 2^-100", dict(inp, pheno=inp["pheno"] * 2.0 ** -100), 2.0 ** -100, 1.0),
+            ("x0 diag(2^3, 2^-5)", dict(inp, x0=inp["x0"] * np.array([2.0 ** 3, 2.0 ** -5])), 1.0, 1.0),
+            ("reg 2^7, scale 2^-7", dict(inp, reg=inp["reg"] * 2.0 ** 7, scale=inp["scale"] * 2.0 ** -7), 1.0, 1.0),
+            ("reg 2^7", dict(inp, reg=inp["reg"] * 2.0 ** 7), 1.0, 2.0 ** 7),
+            ("reorder", dict(reg=np.ascontiguousarray(inp["reg"][s]), x0=np.ascontiguousarray(inp["x0"][s]), pheno=inp["pheno"][s],
+                             scale=inp["scale"][s], perm=sinv[inp["perm"][:, s]].astype(np.int32)), 1.0, 1.0)]
+
+
+def map_cols(out, alpha=1.0, divisor=1.0):
+    """outputs (or a reference) of the column scan with coef times alpha / divisor and rss0 times alpha^2"""
+    return dict(out, coef=out["coef"] * (alpha / divisor), rss0=out["rss0"] * alpha ** 2)

@@ -16,7 +16,7 @@ from qtl_reference import (ATOL, CHROM_LENS, CLAMP, PIVOT_DROP, PIVOT_EXACT, PIV
                            soft_rows)
 
 __all__ = ["ATOL", "a_columns", "ad_columns", "kinship_sums_ref", "kinship_ref", "cols_columns", "cols_reference", "cols_compared",
-           "cols_compare", "chol_whiten", "lmm_reference", "lmm_loglik", "grid_herit", "gaussian_like", "chromstarts_of", "cols_case", "lmm_inputs"]
+           "cols_compare", "chol_whiten", "lmm_reference", "reference_lmm", "compare_lmm", "lmm_loglik", "grid_herit", "gaussian_like", "chromstarts_of", "cols_case", "lmm_inputs"]
 
 
 def a_columns(origin):
@@ -161,6 +161,39 @@ def lmm_reference(K, y, X0, reg, h2):
     n, m, ne = reg.shape
     (ys, xs, rs), _ = chol_whiten(K, h2, np.asarray(y, np.float64).reshape(n, 1), X0, reg.reshape(n, m * ne))
     return cols_reference(rs.reshape(n, m, ne), xs, ys)
+
+
+def reference_lmm(origin, cs, pheno, cov, h2, kin_of, keep=None, additive=False):
+    """scan_lmm by the Cholesky route: per chromosome c the kinship kin_of(c) of the kept individuals, the centred trait and
+    [1, centred cov], every trait at its h2[t][c].  lod[T][M], coef[T][M][2], rank[T][M], and compared[T][M]"""
+    n, M = origin.shape[:2]
+    keep = np.ones(n, bool) if keep is None else keep
+    y = pheno[keep] - pheno[keep].mean(axis=0)
+    X0 = np.ones((keep.sum(), 1)) if cov is None else np.concatenate([np.ones((keep.sum(), 1)), cov[keep] - cov[keep].mean(axis=0)], axis=1)
+    T = y.shape[1]
+    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, 2), np.nan), rank=np.zeros((T, M), np.int32), compared=np.zeros((T, M), bool))
+    for c in range(len(cs) - 1):
+        sl = slice(cs[c], cs[c + 1])
+        reg = ad_columns(origin[keep][:, sl], additive)
+        K = kin_of(c)[np.ix_(keep, keep)]
+        for t in range(T):
+            ref = lmm_reference(K, y[:, t], X0, reg, h2[t][c])
+            out["lod"][t, sl], out["coef"][t, sl], out["rank"][t, sl] = ref["lod"][0, 0], ref["coef"][0], ref["rank"]
+            out["compared"][t, sl] = cols_compared(ref, share=0)
+    return out
+
+
+def compare_lmm(got, ref, what, share=0.9, traits=None):
+    ts = list(range(ref["lod"].shape[0])) if traits is None else traits
+    err_l = np.abs(got["lod"][ts] - ref["lod"]).max()
+    cmp_ = ref["compared"]
+    gc, rc = got["coef"][ts][cmp_], ref["coef"][cmp_]
+    err_c = (np.abs(gc - rc) / np.maximum(1.0, np.abs(rc))).max()
+    print("%s: lod %.3g over %d cells, coef %.3g over %d of %d cells" % (what, err_l, ref["lod"].size, err_c, cmp_.sum(), cmp_.size))
+    assert cmp_.mean() >= share
+    assert np.array_equal(got["rank"][ts], ref["rank"]), what + " rank"
+    assert err_l <= ATOL, what + " lod"
+    assert err_c <= ATOL, what + " coef"
 
 
 def lmm_loglik(K, y, X0, h2, reml=True):

@@ -7,13 +7,22 @@ with qtl.null_residuals beside them -- are held to ATOL under every transform.
 
 The binary-trait scan: its maps (covariate transforms change nothing; the complement and the relabellings change signs and
 n_ones) are proved on the yardstick where that is accurate, the yardstick's own error under the large covariate transforms is
-printed, and every cell through cnf2h_qtlbin_fit is held to the mapped base reference by qtlbin_reference.compare_bin."""
+printed, and every cell through cnf2h_qtlbin_fit is held to the mapped base reference by qtlbin_reference.compare_bin.
+
+The cofactor, bootstrap and polygenic scans: their maps are proved on their yardsticks (A, F, G and the four relabellings),
+the conditions of each base reference are asserted, the yardsticks' own error on B, D and E is printed; no product scan runs.
+The host counterparts of their kernels (qtlcof_marker, qtl_boot_marker, qtl_cols_marker) take sums or columns that their
+callers have already centred, so units and offsets do not reach them and they are left out.  host.kinship_sums is checked
+under the relabellings, and qtl.est_herit (numpy) against the base problem's likelihood grid under every transform."""
 import numpy as np
 import pytest
 
 import qtl_invariance as V
 import qtlbin_reference as RB
+import qtlboot_reference as RO
+import qtlcof_reference as RC
 import qtlem_reference as RE
+import qtllmm_reference as RL
 from cnf2freq_amd import host, qtl
 from qtl_reference import ATOL, reference_scan
 
@@ -310,6 +319,154 @@ def test_bin_host_complement_and_relabelling(scan, case, change):
     """y -> 1 - y, classes 0 and 3 or 1 and 2 exchanged, the covariate columns exchanged, the individuals reordered"""
     inp, how = bin_changed(V.make_bin_base(case), change)
     bin_host_check(scan, case, change, inp, how)
+
+
+# ------------------------------------------------------------------------------------------------ cofactor, bootstrap, polygenic
+# The maps of the three newer scans, proved on their yardsticks.  No product scan runs here, and the host counterparts of their
+# kernels (qtlcof_marker, qtl_boot_marker, qtl_cols_marker) take sums or columns that their callers have already centred: units
+# and offsets do not reach them, so they are left out.  What does run on the host is host.kinship_sums, under the relabellings,
+# and qtl.est_herit, which is numpy.
+YARD_TRANSFORMS = ("A", "F", "G")
+COF_SCAN_IDS = list(V.COF_SCANS)
+BOOT_SCAN_IDS = list(V.BOOT_SCANS)
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", COF_SCAN_IDS)
+def test_cof_mapping_on_the_yardstick(scan, case):
+    """The cofactor scan's yardstick on A, F and G and on the four relabellings agrees with the mapped base reference by
+    compare_cof at ATOL (share 0.99, strict: every marker of both cases is compared); for F and G also in base units.  The
+    same for the three cofactors of COF3 under A and the reordering.  The conditions of the base references are asserted."""
+    base = V.make_base(case)
+    for config, names in ((V.COF, YARD_TRANSFORMS + V.RELABELLINGS), (V.COF3, ("A", "reorder"))):
+        ref = V.cof_base_reference(case, scan, config)
+        assert RC.compared_markers(ref, V.CS, share=0.99, strict=True).all() and RC.worst_pivot(ref, V.CS) >= 0.115
+        kept = case[1] - 2
+        on3 = [kept if case[3] or c == 3 else case[1] for c in range(len(V.CHROM_LENS))]
+        assert list(ref["n_used"]) == ([kept] * len(V.CHROM_LENS) if config is V.COF else on3)
+        for name in names:
+            if name in V.TRANSFORMS:
+                tr, flip = V.TRANSFORMS[name], ()
+                inp = V.apply(base, tr)
+            else:
+                tr = V.IDENTITY
+                inp, flip = V.relabel(base, name)
+            yard = V.cof_as_got(V.cof_reference(scan, inp, config))
+            want = V.map_cof_reference(ref, tr["alpha"], flip)
+            what = "yardstick %s %s cofactors %s %s" % (scan, case[0], config[0], name)
+            print(V.errors_line(what, V.cof_errors(yard, want)))
+            RC.compare_cof(yard, want, V.CS, what, share=0.99, strict=True)
+            if name in "FG":
+                RC.compare_cof(V.map_cof_reference(yard, 1.0 / tr["alpha"]), ref, V.CS, what + " in base units", share=0.99, strict=True)
+            if name == "swap03":                 # the map is not the identity
+                assert np.nanmax(np.abs(yard["coef"][:, :, 0] + ref["coef"][:, :, 0])) <= ATOL and np.nanmax(np.abs(ref["coef"][:, :, 0])) > 0.1
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+@pytest.mark.parametrize("scan", BOOT_SCAN_IDS)
+def test_boot_mapping_on_the_yardstick(scan, case):
+    """The bootstrap scan's yardstick on A, F and G and on the four relabellings (the counts reordered with the individuals)
+    agrees with the base reference -- the map is the identity -- by qtlboot_reference.compare at ATOL on the cells that
+    conditions(base reference, K = 2) gives, which are asserted first."""
+    base = V.make_boot_base(case)
+    assert base["count"].shape == (V.BOOT_B, case[1]) and np.all(base["count"].sum(axis=1) == case[1] - 2 * case[3])
+    ref, compared = V.boot_base_reference(case, scan)
+    assert compared.all() and ref["gap"].min() >= 2e-4
+    problems = [(name, V.apply(base, V.TRANSFORMS[name])) for name in YARD_TRANSFORMS] + [(name, V.boot_relabel(base, name)) for name in V.RELABELLINGS]
+    for name, inp in problems:
+        yard = V.boot_as_got(V.boot_reference(scan, inp))
+        what = "yardstick %s %s %s" % (scan, case[0], name)
+        print(V.errors_line(what, V.boot_errors(yard, ref, compared)))
+        RO.compare(yard, ref, compared, what)
+    s = V.order_of(case[1])
+    re = V.boot_relabel(base, "reorder")
+    assert np.array_equal(re["count"], base["count"][:, s]) and V.same_bits(re["pheno"], base["pheno"][s])
+
+
+def lmm_yardstick(case, inp, kin):
+    return V.lmm_reference(inp, kin, V.lmm_given_h2("lmm-given"))
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+def test_lmm_mapping_on_the_yardstick(case):
+    """The polygenic scan's Cholesky yardstick at h2 = (0.3, 0.8) with the kinship that leaves a chromosome out, on A, F and G
+    and on the four relabellings (the kinship of the relabelled rows), agrees with the mapped base reference by compare_lmm at
+    ATOL with at least 0.9 of the cells compared (all are), and in sigma2 and n_used; for F and G also in base units."""
+    base = V.make_base(case)
+    ref = V.lmm_base_reference(case, "lmm-given")
+    assert ref["compared"].mean() >= 0.9 and list(ref["n_used"]) == [case[1] - 2] * V.T
+    kin = V.lmm_base_kinship(case, True)
+    for name in YARD_TRANSFORMS + V.RELABELLINGS:
+        if name in V.TRANSFORMS:
+            tr, flip = V.TRANSFORMS[name], ()
+            inp, k = V.apply(base, tr), kin
+        else:
+            tr = V.IDENTITY
+            inp, flip = V.relabel(base, name)
+            k = np.stack([RL.kinship_ref(inp["origin"], V.CS, leave_out=c) for c in range(len(V.CHROM_LENS))])
+        yard = lmm_yardstick(case, inp, k)
+        what = "yardstick lmm-given %s %s" % (case[0], name)
+        want = V.map_lmm_reference(ref, tr["alpha"], flip)
+        print(V.errors_line(what, V.lmm_errors(yard, want)))
+        V.lmm_check(yard, want, what)
+        if name in "FG":
+            V.lmm_check(V.map_lmm_reference(yard, 1.0 / tr["alpha"]), ref, what + " in base units")
+        if name == "swap03":
+            assert np.nanmax(np.abs(yard["coef"][:, :, 0] + ref["coef"][:, :, 0])) <= ATOL and np.nanmax(np.abs(ref["coef"][:, :, 0])) > 0.1
+
+
+def test_new_yardsticks_error_on_large_shifts():
+    """Printed, not asserted: how far the yardsticks of the cofactor, bootstrap and polygenic scans themselves are from the
+    mapped base reference on B, D and E.  They are no reference there."""
+    case = V.CASES[1]
+    for name in ("B", "D", "E"):
+        tr = V.TRANSFORMS[name]
+        ref = V.cof_base_reference(case, "cof-full")
+        yard = V.map_cof_reference(V.cof_as_got(V.cof_reference("cof-full", V.apply(V.make_base(case), tr))), 1.0 / tr["alpha"])
+        err = V.cof_errors(yard, ref)
+        print(V.errors_line("yardstick's own error cof-full %s transform %s" % (case[0], name), err))
+        assert all(np.isfinite(v) for v in err.values())
+        ref, compared = V.boot_base_reference(case, "boot-full")
+        err = V.boot_errors(V.boot_as_got(V.boot_reference("boot-full", V.apply(V.make_boot_base(case), tr))), ref, compared)
+        print(V.errors_line("yardstick's own error boot-full %s transform %s" % (case[0], name), err))
+        assert all(np.isfinite(v) for v in err.values())
+        ref = V.lmm_base_reference(case, "lmm-given")
+        yard = V.map_lmm_reference(lmm_yardstick(case, V.apply(V.make_base(case), tr), V.lmm_base_kinship(case, True)), 1.0 / tr["alpha"])
+        err = V.lmm_errors(yard, ref)
+        print(V.errors_line("yardstick's own error lmm-given %s transform %s" % (case[0], name), err))
+        assert all(np.isfinite(v) for v in err.values())
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+def test_est_herit_under_transforms(case):
+    """qtl.est_herit (numpy) on the eigenvectors of the base kinship, fed the centred traits and covariates of every
+    transformed problem as qtl.scan_lmm centres them: h2 within 1e-4, the grid's step, of the maximum of the Cholesky-route
+    REML likelihood of the BASE problem on the grid (which has a single local maximum); sigma2 in base units within ATOL,
+    relative, of the yardstick's at the returned h2.  How far h2 moves from the base problem's estimate is printed: the
+    likelihood is flat to rounding over the 1e-7 that the golden section's end leaves open."""
+    keep, y0, X0 = V.lmm_design(V.make_base(case))
+    K0 = V.lmm_base_kinship(case, False)[0][np.ix_(keep, keep)]
+    lam, U = np.linalg.eigh(K0)
+    fit = lambda inp: [qtl.est_herit(V.lmm_design(inp)[1][:, t], V.lmm_design(inp)[2], lam, U, reml=True) for t in range(V.T)]
+    at_base = fit(V.make_base(case))
+    for name in ["identity"] + TRANSFORM_IDS:
+        tr = V.IDENTITY if name == "identity" else V.TRANSFORMS[name]
+        for t, (h2, s2, _) in enumerate(fit(V.apply(V.make_base(case), tr))):
+            grid = V.lmm_grid_h2(case, t)
+            print("est_herit %s trait %d transform %s: h2 %.10f, the grid's maximum at %.4f, from the base estimate %.3g" %
+                  (case[0], t, name, h2, grid, abs(h2 - at_base[t][0])))
+            assert abs(h2 - grid) <= V.LMM_H2_BOUND
+            (ys, xs), _ = RL.chol_whiten(K0, h2, y0[:, t], X0)
+            r = ys - xs @ np.linalg.lstsq(xs, ys, rcond=None)[0]
+            want = (r @ r) / (len(ys) - X0.shape[1])
+            assert abs(s2 / tr["alpha"][t] ** 2 - want) <= ATOL * max(1.0, want)
+
+
+@pytest.mark.parametrize("case", V.CASES, ids=V.CASE_IDS)
+def test_host_kinship_sums_relabelled(case):
+    """host.kinship_sums on the base rows over three chromosome ranges: the same bits with classes 0 and 3 or 1 and 2
+    exchanged, the reordered matrix within ATOL under the reordering, and symmetric to the bit"""
+    V.check_kinship_relabellings(lambda o, c0, c1: host.kinship_sums(o, V.CS, c0, c1), case, "host.kinship_sums")
 
 
 def test_bin_nearly_collinear_marker_under_a_shift():
