@@ -2821,17 +2821,26 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack_ke
 // unrestricted table is one value per part whatever the parent's shift bit, so the chains of a job with equal s0 see the same
 // emissions and carry the same alpha, beta and scales: the lanes that differ in s1 take another job as well (cnf2_lane.h
 // up8_*).  Per job every floating-point operation is fb_unipack_kernel's, on the same operands in the same order.
-//   tile:     backward: 1 marker x 8 jobs, table row = job; the producer lane is (part, job), the epilogue's lanes (row, eighth)
-//             run once per marker.  Forward: CNF2_UP8_FWD_TILE markers x 8 jobs of compact slots (cnf2_lane.h up8_fwd_*), over
-//             the same region
-//   rows:     a lane forms the four B-side class sums of (s0, s2) once and the row partials for s1 = 1 and then s1 = 0; they
-//             are parked in the job's row in two steps (up8_park), each over what nobody reads any more
+//   tile:     backward: 1 marker x 8 jobs, table row = job; the producer lane is (part, job).  Forward: CNF2_UP8_FWD_TILE
+//             markers x 8 jobs of compact slots (cnf2_lane.h up8_fwd_*), over the same region
+//   rows:     a lane forms the four B-side class sums of (s0, s2) once, takes its b0 partner's, and adds up the eight partials
+//             of one chain (s0, s1 = its b0, s2) in registers, in the order of a one-job sweep's tile epilogue; the job's eight
+//             chains are then added across lanes (s0, s1, s2: chain_sum's tree) and the job's lead lane stores the row
+//             (cnf2_lane.h up8_sum_*).  Nothing is written to the table rows behind the producer: two fences a marker.
+//             CNF2_UP8_ROW_SUMS == 0 (A/B): a lane forms the partials of its class for s1 = 1 and then s1 = 0, parks them in
+//             the job's row in two steps (up8_park), each over what nobody reads any more, and the lanes (row, eighth) of a
+//             tile epilogue add them up once per marker: five fences a marker
 //   rebuild:  the odd marker's rebuild starts from alpha x emission of the even marker, which the forward pass spills beside
 //             alpha (the even marker's row does not exist yet when the odd one is worked on); the even marker forms its
 //             emission from its own row
 //   spill:    UP8_SPILL_ROW doubles per marker pair, stored by the lanes with s2 = 0
 // =====================================================================================
 static_assert(TAB_R == 72 && TAB_2 == 136 && TAB_STRIDE >= 200, "up8_park (cnf2_lane.h) is written for this row layout");
+static_assert(TAB_R % 2 == 0 && TAB_2 % 2 == 0 && TAB_STRIDE % 2 == 0, "the A-side runs of a chain (up8_sum_run) are read 16 bytes at a time");
+// 1: a lane adds up the row partials of one chain in registers; 0: the partials are parked in the table row for an epilogue (A/B)
+#ifndef CNF2_UP8_ROW_SUMS
+#define CNF2_UP8_ROW_SUMS 1
+#endif
 // markers to a forward tile (cnf2_lane.h up8_fwd_*); 1: the forward pass on one table row a marker, as the backward pass (A/B)
 #ifndef CNF2_UP8_FWD_TILE
 #define CNF2_UP8_FWD_TILE 8
@@ -2964,7 +2973,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         // parent's shift bit: the lane reads it at s1 = 0)
         const int rj = up8_job(lane), b0 = up8_b0(lane);
         const int ind = pj[rj >> 2].ind[rj & 3];
+#if !CNF2_UP8_ROW_SUMS
         const int eind = pj[lane >> 5].ind[(lane >> 3) & 3];    // epilogue role: the individual of table row lane >> 3 = job
+#endif
         FastCtx   c;
         c.s0 = up8_s0(lane);
         c.s1 = 0;
@@ -3219,7 +3230,92 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
             const double cf0 = row[TAB_C + 0 + c.s0], cf1 = row[TAB_C + 2 + c.s0];
             double e[NR];
             emission_from_row(row, c, e);
+#if CNF2_UP8_ROW_SUMS
+            // the b0 pair's class sums by absolute class, and the eight partials of the lane's chain (cnf2_lane.h up8_sum_*),
+            // each formed in front of its addition.  A partial is the parked form's, expression for expression; it is made
+            // opaque before it is added so that its product with `scale` is rounded, as a parked one is.
+            double zb[2][4];
+#pragma unroll
+            for (int kq = 0; kq < 4; kq++) {
+                const double zp = lane_xor1(z[kq]);
+                zb[0][kq] = b0 ? zp : z[kq];
+                zb[1][kq] = b0 ? z[kq] : zp;
+            }
+            const double* const A = row + up8_sum_run(0, up8_sum_s1(lane));
+            double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+#pragma unroll
+            for (int ip = 0; ip < 4; ip++) {
+                // two places that follow each other share v: their entries are the two classes of one 16-byte read a run
+                const int v = up8_place_v(2 * ip);
+                static_assert(up8_place_v(0) == up8_place_v(1) && up8_place_v(2) == up8_place_v(3) && up8_place_v(4) == up8_place_v(5) &&
+                              up8_place_v(6) == up8_place_v(7), "a pair of places is one v");
+                double2 ar[2], a2[2];
+#pragma unroll
+                for (int f = 0; f < 2; f++) {
+                    ar[f] = *(const double2*)(A + TAB_R + (up8_sum_run(f, 0) | (v << 1)));
+                    a2[f] = *(const double2*)(A + TAB_2 + (up8_sum_run(f, 0) | (v << 1)));
+                }
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const int b = up8_place_b(2 * ip + k);
+                    double    n_tot = 0.0, n_a1 = 0.0, n_b1 = 0.0, n_2 = 0.0;
+#pragma unroll
+                    for (int f = 0; f < 2; f++) {
+                        const double cf = f ? cf1 : cf0;
+                        const double av = cf * (b ? ar[f].y : ar[f].x), a1 = cf * (b ? a2[f].y : a2[f].x);
+                        const double sb = zb[b][2 * f], sb1 = zb[b][2 * f + 1];
+                        n_tot += av * sb;
+                        n_a1 += a1 * sb;
+                        n_b1 += av * sb1;
+                        n_2 += a1 * sb1;
+                    }
+                    double q2 = scale * n_2;
+                    double q1 = scale * (n_a1 + n_b1 - 2.0 * n_2);
+                    double q0 = scale * (n_tot - n_a1 - n_b1 + n_2);
+                    asm("" : "+v"(q0), "+v"(q1), "+v"(q2));
+                    d0 += q0;
+                    d1 += q1;
+                    d2 += q2;
+                }
+            }
+            // the job's eight chains, as chain_sum adds the lanes of an epilogue's row: s0, s1, s2, each from the lane
+            // up8_partner(lane, level) of level 0, 1, 2 (cnf2_lane.h; tests/test_uniform_pack8_rows_host.py holds it to that tree)
+            static_assert((up8_partner(0, 0) ^ 0) == 8 && (up8_partner(63, 0) ^ 63) == 8, "level 0 is lane_xor8");
+            static_assert((up8_partner(0, 1) ^ 0) == 1 && (up8_partner(63, 1) ^ 63) == 1, "level 1 is lane_xor1");
+            static_assert((up8_partner(0, 2) ^ 0) == 16 && (up8_partner(63, 2) ^ 63) == 16, "level 2 is lane_xor16");
+            d0 += lane_xor8(d0);
+            d1 += lane_xor8(d1);
+            d2 += lane_xor8(d2);
+            d0 += lane_xor1(d0);
+            d1 += lane_xor1(d1);
+            d2 += lane_xor1(d2);
+            d0 += lane_xor16(d0);
+            d1 += lane_xor16(d1);
+            d2 += lane_xor16(d2);
+            d0 = fmax(d0, 0.0);
+            d1 = fmax(d1, 0.0);
+            d2 = fmax(d2, 0.0);
+            if (jlead) {
+                if (!(p.flags & KP_RAW_DOSAGE)) {
+                    const double tsum = d0 + d1 + d2;
+                    const double inv  = tsum > 0.0 ? 1.0 / tsum : 0.0;
+                    d0 *= inv;
+                    d1 *= inv;
+                    d2 *= inv;
+                }
+                // (the row's address is formed here, from a value the compiler cannot see through)
+                int ei = ind;
+                asm volatile("" : "+v"(ei));
+                double* out = p.dosage + ((size_t)ei * p.n_markers + m) * 3;
+                out[0] = d0;
+                out[1] = d1;
+                out[2] = d2;
+            }
+#else
             // the partials of s1 = 1, then of s1 = 0, into the job's row where the epilogue looks for them
+#ifdef CNF2_X_NOPARK
+            double x_sum[3];
+#endif
 #pragma unroll
             for (int h = 0; h < 2; h++) {
                 const int s1 = 1 - h;
@@ -3241,7 +3337,12 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
                     q[v][2] = scale * n_2;
                     q[v][1] = scale * (n_a1 + n_b1 - 2.0 * n_2);
                     q[v][0] = scale * (n_tot - n_a1 - n_b1 + n_2);
+#ifdef CNF2_X_NOPARK     /* timing ablation only: results are wrong (no parking stores, no read-back, none of their fences) */
+#pragma unroll
+                    for (int k = 0; k < 3; k++) x_sum[k] = (h == 0 && v == 0 ? 0.0 : x_sum[k]) + q[v][k];
+#endif
                 }
+#ifndef CNF2_X_NOPARK
                 wave_lds_fence();
 #pragma unroll
                 for (int v = 0; v < 4; v++) {
@@ -3250,7 +3351,24 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
                     row[up8_park(1, vl)] = q[v][1];
                     row[up8_park(2, vl)] = q[v][2];
                 }
+#endif
             }
+#ifdef CNF2_X_NOPARK
+            {   // (the epilogue below on this lane's own sums, so that they never leave registers)
+                const double d0 = fmax(chain_sum(x_sum[0]), 0.0), d1 = fmax(chain_sum(x_sum[1]), 0.0), d2 = fmax(chain_sum(x_sum[2]), 0.0);
+                const double tsum = d0 + d1 + d2;
+                const double inv  = (p.flags & KP_RAW_DOSAGE) ? 1.0 : (tsum > 0.0 ? 1.0 / tsum : 0.0);
+                if ((lane & 7) == 0) {
+                    int ei = eind;
+                    asm volatile("" : "+v"(ei));
+                    double* out = p.dosage + ((size_t)ei * p.n_markers + m) * 3;
+                    out[0] = d0 * inv;
+                    out[1] = d1 * inv;
+                    out[2] = d2 * inv;
+                }
+            }
+#endif
+#endif
 #pragma unroll
             for (int j = 0; j < NR; j++) S.b[j] *= e[j];
             const bool scale_here = !ODD && (ml & bmask) == 0;      // per job
@@ -3271,17 +3389,20 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         };
         load_rec<-1>(pq, cp, rec_row, last + moff, first, last, load_root_allele(pq, cp, last + moff, first, last), &rraw);
         ap_next = load_root_allele(pq, cp, last - 1 + moff, first, last);
+#if !CNF2_UP8_ROW_SUMS && !defined(CNF2_X_NOPARK)
         // epilogue role: row mi2 = job, chain sub
         const int mi2 = lane >> 3, sub = lane & 7;
+#endif
         for (int m = last; m >= first; m--) {
             take_spill();
             ask_spill(m - first - 1);
             produce_row_rec<true, true>(cp, tab, true, rraw);
             load_rec<-1>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);       // (unconditional, as forward)
             ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
-            wave_lds_fence();
+            wave_lds_fence();                   // the producer lanes' rows are in place for the recursion lanes that read them
             if ((m - first) & 1) marker(odd_t(), myrow, m);
             else marker(even_t(), myrow, m);
+#if !CNF2_UP8_ROW_SUMS && !defined(CNF2_X_NOPARK)
             wave_lds_fence();
             // tile epilogue, as fb_fast_kernel's: lanes (row mi2, eighth sub) add up the 3 x 64 partials of the tile's rows
             {
@@ -3317,6 +3438,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
                     out[2] = d2;
                 }
             }
+#endif
+            // the row's last readers are done (marker() with row sums, the epilogue without): the region goes to the next
+            // marker's producer, or to the first forward tile of the wave's next job
             wave_lds_fence();
         }
     }

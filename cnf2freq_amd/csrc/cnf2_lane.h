@@ -47,7 +47,7 @@ CNF2_HD void make_lane(const Window& w, int lane, LaneJob* L)
 
 // The fast kernels' lane order within a chain of 8 lanes: the low state bits (b0, b1, b2) sit in lane b0 ^ 2 b1 ^ 7 b2
 // (flipping b2 is then a row_half_mirror move, see cnf2_kernels.hip).  The map is its own inverse.
-CNF2_HD int state_lo(int lane) { return (lane & 7) ^ ((lane & 4) ? 3 : 0); }
+CNF2_HD constexpr int state_lo(int lane) { return (lane & 7) ^ ((lane & 4) ? 3 : 0); }
 
 // Spill row of the uniform-state sweep with two registers per lane.  Alpha does not depend on state bits 1, 2, 4, 5 there, so
 // the 8 lanes of a chain hold two distinct register pairs, told apart by state bit 0: a row keeps each once.
@@ -90,6 +90,22 @@ CNF2_HD int up8_virtual_lane(int lane, int s1, int v)
 {
     return (up8_s0(lane) | (s1 << 1) | (up8_s2(lane) << 2)) * 8 + state_lo(up8_b0(lane) | (v << 1));
 }
+// Row sums in registers (CNF2_UP8_ROW_SUMS, the default).  A partial depends on the lane's class only through the B-side class
+// sums, and the two lanes of a b0 pair (lane, lane ^ 1) between them form the eight partials of chain (s0, s1 = 1, s2) and the
+// eight of chain (s0, s1 = 0, s2).  So the pair exchanges its class sums and each lane adds up one whole chain: lane `lane`
+// forms the virtual lanes s * 8 + 0..7 of chain s = s0 | up8_sum_s1(lane) << 1 | s2 in ascending place, place i2 being the
+// partial (b, v) = (up8_place_b(i2), up8_place_v(i2)) with the class sums of class b: the one-job sweep's order inside a chain.
+// The chains of a job are then added as chain_sum adds them, ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7)): level 0 pairs
+// s0, level 1 s1, level 2 s2, every level between two lanes that both hold what they add (up8_partner), so all eight lanes of a
+// job end with the job's sum.  The A-side entries of a chain are the eight doubles from up8_sum_run(f, s1) on in the restricted
+// totals and in the class-2 parts: 16-byte aligned runs.
+CNF2_HD int up8_sum_s1(int lane) { return up8_b0(lane); }
+CNF2_HD constexpr int up8_place_b(int i2) { return state_lo(i2) & 1; }
+CNF2_HD constexpr int up8_place_v(int i2) { return state_lo(i2) >> 1; }
+CNF2_HD constexpr int up8_partner(int lane, int level) { return lane ^ (level == 0 ? 8 : (level == 1 ? 1 : 16)); }
+CNF2_HD int up8_sum_run(int f, int s1) { return (f << 4) | (s1 << 3); }
+// The parked form (CNF2_UP8_ROW_SUMS == 0, kept for A/B timing): a lane forms the partials (s1, v) of its own class for both s1
+// and parks them in the row for the lanes of a tile epilogue.
 // Where the partial of class cls (0..2) of virtual lane vl is parked in the job's table row (TAB_STRIDE doubles: [0,64) the
 // unrestricted table, [64,72) root weights and gap, [72,136) restricted totals, [136,200) class-2 parts; the A side is the
 // lower half of a table).  The partials of s1 = 1 are parked first, while the A-side entries of s1 = 0 are still to be

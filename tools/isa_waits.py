@@ -63,6 +63,14 @@ for head, tail in loops:
         continue
     n_flat = sum(insts[i][1].startswith("flat_load") for i in own)
     print("\nloop %s .. %s: %d instructions, %d loads of its own (%d flat)" % (insts[head][0], insts[tail][0], tail - head + 1, len(own), n_flat))
+    # LDS instructions of the loop's text by kind (both sides of a branch count), and its full drains of the LDS queue
+    kinds = {}
+    for i in range(head, tail + 1):
+        op = insts[i][1].split()[0]
+        if op.startswith("ds_"):
+            kinds[op] = kinds.get(op, 0) + 1
+    drains = sum(1 for i in range(head, tail + 1) if re.match(r"s_waitcnt.*lgkmcnt\(0\)", insts[i][1]))
+    print("  LDS: %s; s_waitcnt lgkmcnt(0): %d" % (", ".join("%s %d" % kv for kv in sorted(kinds.items())) or "none", drains))
     for i in own:
         order = list(range(i + 1, tail + 1)) + list(range(head, i))
         behind, hit = 0, None
