@@ -21,6 +21,7 @@
 #include "cnf2_emtab.h"
 #include "cnf2_plan.h"
 #include "cnf2_qtl.h"
+#include "cnf2_qtlplan.h"
 #include "cnf2_qtl2.h"
 #include "cnf2_qtlx.h"
 #include "cnf2_qtlcof.h"
@@ -76,6 +77,9 @@ struct DevBuf {
     // at least `count` elements: what is held if it suffices, else exactly `count`
     int ensure(cnf2_ctx* ctx, size_t count) { return (cap >= count && ptr) ? CNF2_OK : alloc(ctx, count); }
 };
+
+// the scans whose column tile the caller can cap (cnf2_set_*_columns); the column scan shares the single scan's
+enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_COUNT };
 
 struct cnf2_ctx {
     int         device = -1;
@@ -167,7 +171,7 @@ struct cnf2_ctx {
     DevBuf<double>  d_org_sum;            // [n_markers][4]
 
     // QTL scan (cnf2_qtl_scan, cnf2_sweep_qtl): staged inputs, design, the column image of a tile, staged outputs
-    int             qtl_columns = 0;      // cap on the columns per tile (0 = what memory allows)
+    int             qtl_columns[QTL_CAP_COUNT] = {};   // caps on the columns per tile (cnf2_set_*_columns; 0 = what memory allows)
     int             qtl_rows_n = 0;       // individuals whose rows the last cnf2_sweep_qtl left in d_org: 0 (none to vouch for) after
                                           // every upload of a map, rows or a pedigree and every other use of d_org
     int             qtl_rows_m = 0;       // ... and the markers of those rows
@@ -176,35 +180,30 @@ struct cnf2_ctx {
     DevBuf<uint8_t> d_q_use, d_q_cmask;
     DevBuf<int32_t> d_q_perm, d_q_map, d_q_nc, d_q_rank;   // d_q_map: chromstarts, marker -> chromosome, tiles, tile starts
 
-    // two-QTL pair scan (cnf2_qtl_scan2): its column cap, the per-pair sums of the null design, the chunk maxima, staged
+    // two-QTL pair scan (cnf2_qtl_scan2): the per-pair sums of the null design, the chunk maxima, staged
     // outputs; the staged inputs, the mask and the column image are the single scan's buffers
-    int             qtl2_columns = 0;
     DevBuf<double>  d_q2_yy, d_q2_chunkmax, d_q2_lod_add, d_q2_lod_full, d_q2_rss0, d_q2_pmax;
     DevBuf<int32_t> d_q2_map, d_q2_nc, d_q2_rank_add, d_q2_rank_full;   // d_q2_map: chromstarts, sel, the chromosomes of sel
 
-    // extended single-locus scan (cnf2_qtl_scanx): its column cap, sum c y^2 per chromosome, the tile maxima, staged outputs;
+    // extended single-locus scan (cnf2_qtl_scanx): sum c y^2 per chromosome, the tile maxima, staged outputs;
     // the staged inputs, the mask and the column image are the single scan's buffers
-    int             qtlx_columns = 0;
     DevBuf<double>  d_qx_yy, d_qx_tilemax, d_qx_lod, d_qx_coef, d_qx_rss0, d_qx_pmax;
     DevBuf<int32_t> d_qx_map, d_qx_nc, d_qx_rank;   // d_qx_map: chromstarts, tiles, tile starts
 
-    // cofactor scan (cnf2_qtl_scan_cof): its column cap, the cofactor columns, sum c y^2 per chromosome, the tile maxima,
+    // cofactor scan (cnf2_qtl_scan_cof): the cofactor columns, sum c y^2 per chromosome, the tile maxima,
     // staged outputs; the staged inputs, the mask and the column image are the single scan's buffers
-    int             qtlcof_columns = 0;
     DevBuf<double>  d_qc_img, d_qc_yy, d_qc_tilemax, d_qc_lod, d_qc_lod_base, d_qc_coef, d_qc_rss0, d_qc_pmax;
     DevBuf<int32_t> d_qc_map, d_qc_nc, d_qc_rank, d_qc_rank_cof;   // d_qc_map: chromstarts, tiles, tile starts, cof, their chromosomes' starts, skip words
 
-    // maximum-likelihood single-locus scan (cnf2_qtl_scan_em): its column cap, which effects a marker keeps, the tile
+    // maximum-likelihood single-locus scan (cnf2_qtl_scan_em): which effects a marker keeps, the tile
     // maxima, staged outputs; the staged inputs, the mask, the factor, the column image and the null fit are the single
     // scan's buffers
-    int             qtlem_columns = 0;
     DevBuf<double>  d_qe_tilemax, d_qe_lod, d_qe_coef, d_qe_sigma2, d_qe_rss0, d_qe_rss0_null, d_qe_pmax;   // _null: what qtl_null_kernel reports
     DevBuf<int32_t> d_qe_map, d_qe_keep, d_qe_nc, d_qe_rank, d_qe_iters, d_qe_status;   // d_qe_map: as d_q_map, tiles of 4
 
-    // binary-trait single-locus scan (cnf2_qtl_scan_binary): its column cap, which effects a marker keeps, which chromosomes
+    // binary-trait single-locus scan (cnf2_qtl_scan_binary): which effects a marker keeps, which chromosomes
     // are scanned, the null fits, the tile maxima, staged outputs; the staged inputs, the mask and the column image are the
     // single scan's buffers (d_q_chol only receives what qtl_chrom_kernel writes beside the mask: this scan does not read it)
-    int             qtlbin_columns = 0;
     DevBuf<double>  d_qb_null, d_qb_tilemax, d_qb_lod, d_qb_coef, d_qb_ll0, d_qb_pmax;
     DevBuf<int32_t> d_qb_map, d_qb_keep, d_qb_scan, d_qb_nc, d_qb_rank, d_qb_iters, d_qb_status, d_qb_ones;   // d_qb_map: as d_qe_map
 
@@ -334,6 +333,24 @@ static int fetch_out(cnf2_ctx* ctx, T* user, const T* staged, size_t count)
     return CNF2_OK;
 }
 
+// The outputs of a QTL scan are written down once, as a function `list(each)` that hands `each` the four things of every
+// output -- the caller's pointer, the context's staging buffer, the element count, the kernels' field -- and returns the
+// first status that is not CNF2_OK.  Both walks below go through that one list.  An output the caller did not ask for, or
+// one without elements, has a null field after staging, and fetch_out skips it.
+template <class List>
+static int qtl_stage_outputs(cnf2_ctx* ctx, bool dev, List& list)
+{
+    return list([&](auto* user, auto& buf, size_t count, auto** field) { return stage_out(ctx, dev, user, buf, count, field); });
+}
+// ... back to the caller's host memory (nothing to do for device outputs), then the stream is drained
+template <class List>
+static int qtl_fetch_outputs(cnf2_ctx* ctx, bool dev, List& list)
+{
+    if (!dev) RC_TRY(list([&](auto* user, auto&, size_t count, auto** field) { return fetch_out(ctx, user, *field, count); }));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
 // What the two batched consumers (cnf2_sweep_accumulate, cnf2_sweep_turn_scan) share before their launches: the job list on
 // the device, the plan of grid and batches from the memory that is free (cnf2_plan.h), and the spill slots
 struct Batched {
@@ -436,50 +453,19 @@ int cnf2_set_batch_jobs(cnf2_ctx* ctx, int jobs)
     return CNF2_OK;
 }
 
-int cnf2_set_qtl2_columns(cnf2_ctx* ctx, int cap)
-{
-    if (!ctx || cap < 0) return ctx ? fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative") : CNF2_ERR_ARG;
-    ctx->qtl2_columns = cap;
-    return CNF2_OK;
-}
-
-int cnf2_set_qtlx_columns(cnf2_ctx* ctx, int cap)
-{
-    if (!ctx || cap < 0) return ctx ? fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative") : CNF2_ERR_ARG;
-    ctx->qtlx_columns = cap;
-    return CNF2_OK;
-}
-
-int cnf2_set_qtlcof_columns(cnf2_ctx* ctx, int cap)
+static int set_columns(cnf2_ctx* ctx, QtlCap which, int cap)
 {
     if (!ctx) return CNF2_ERR_ARG;
     if (cap < 0) return fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative");
-    ctx->qtlcof_columns = cap;
+    ctx->qtl_columns[which] = cap;
     return CNF2_OK;
 }
-
-int cnf2_set_qtlem_columns(cnf2_ctx* ctx, int cap)
-{
-    if (!ctx) return CNF2_ERR_ARG;
-    if (cap < 0) return fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative");
-    ctx->qtlem_columns = cap;
-    return CNF2_OK;
-}
-
-int cnf2_set_qtlbin_columns(cnf2_ctx* ctx, int cap)
-{
-    if (!ctx) return CNF2_ERR_ARG;
-    if (cap < 0) return fail(ctx, CNF2_ERR_ARG, "the column cap must not be negative");
-    ctx->qtlbin_columns = cap;
-    return CNF2_OK;
-}
-
-int cnf2_set_qtl_columns(cnf2_ctx* ctx, int cap)
-{
-    if (!ctx || cap < 0) return CNF2_ERR_ARG;
-    ctx->qtl_columns = cap;
-    return CNF2_OK;
-}
+int cnf2_set_qtl_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_SCAN, cap); }
+int cnf2_set_qtl2_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_SCAN2, cap); }
+int cnf2_set_qtlx_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_SCANX, cap); }
+int cnf2_set_qtlcof_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_COF, cap); }
+int cnf2_set_qtlem_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_EM, cap); }
+int cnf2_set_qtlbin_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_BIN, cap); }
 
 int cnf2_sync(cnf2_ctx* ctx)
 {
@@ -1549,7 +1535,11 @@ int cnf2_sweep_origins(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factor
 }
 
 // ------------------------------------------------------------------------------------------------
-// QTL scan (cnf2_qtl.h, cnf2_qtl_kernels.hip)
+// QTL scans (cnf2_qtl.h, cnf2_qtlplan.h, cnf2_qtl_kernels.hip and the scans' own headers and kernels).  Every entry point
+// takes the same steps in the same order: the argument checks; the plan (marker map and column tile, cnf2_qtlplan.h); every
+// allocation -- the origin buffer, the inputs, the workspace, the staged outputs; the copy of host origin rows; the uploads;
+// the launches; the fetches.  So a check or an allocation that fails returns before anything of the caller's is written and
+// before the rows a cnf2_sweep_qtl left in the context are touched.
 // ------------------------------------------------------------------------------------------------
 struct QtlArgs {
     int            n, T, K, P;
@@ -1561,6 +1551,81 @@ struct QtlArgs {
     int32_t *      rank, *n_used;
 };
 
+// Where a scan's origin rows [n][M][4] come from: the caller's host array, staged in d_org; the caller's device array, read
+// in place; or (origin NULL with CNF2_QTL_ORIGIN_DEVICE) the rows the last cnf2_sweep_qtl left in d_org, which stay valid.
+struct QtlOrigin {
+    bool          staged = false;   // host rows: `host` is copied to d_org (qtl_origin_stage)
+    const double* host = nullptr;
+    const double* dev = nullptr;    // what the kernels read; for host rows d_org, once they are staged
+    size_t        count = 0;        // doubles
+};
+
+// the rows kept by the last cnf2_sweep_qtl are those of exactly these n individuals on the map as it is
+static int qtl_kept_check(cnf2_ctx* ctx, int n)
+{
+    if (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers || ctx->d_org.cap < (size_t)n * ctx->n_markers * 4)
+        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    return CNF2_OK;
+}
+
+static int qtl_origin_source(cnf2_ctx* ctx, int n, const double* origin, uint32_t flags, QtlOrigin* out)
+{
+    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);
+    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    if (kept) RC_TRY(qtl_kept_check(ctx, n));
+    out->staged = !(flags & CNF2_QTL_ORIGIN_DEVICE);
+    out->host   = out->staged ? origin : nullptr;
+    out->dev    = kept ? ctx->d_org.ptr : out->staged ? nullptr : origin;
+    out->count  = (size_t)n * ctx->n_markers * 4;
+    if (!out->staged && ((uintptr_t)out->dev & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
+    return CNF2_OK;
+}
+// room for host rows, with a scan's other allocations (kept rows go with a buffer that has to grow)
+static int qtl_origin_reserve(cnf2_ctx* ctx, const QtlOrigin& o)
+{
+    if (!o.staged) return CNF2_OK;
+    if (ctx->d_org.cap < o.count) ctx->qtl_rows_n = 0;
+    return ctx->d_org.ensure(ctx, o.count);
+}
+// ... and the copy, once every allocation has succeeded.  Complete on return: the caller's array is not read after the call,
+// whatever its status.  The buffer holds the caller's rows from here on, so it vouches for no sweep's.
+static int qtl_origin_stage(cnf2_ctx* ctx, QtlOrigin& o)
+{
+    if (!o.staged) return CNF2_OK;
+    RC_TRY(qtl_origin_reserve(ctx, o));
+    ctx->qtl_rows_n = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, o.host, o.count * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    o.dev = ctx->d_org;
+    return CNF2_OK;
+}
+
+// use_out[n] = the mask with NULL expanded; the phenotypes and covariates of the used individuals must be finite
+static int qtl_check_values(cnf2_ctx* ctx, const QtlArgs& a, std::vector<uint8_t>* use_out)
+{
+    std::vector<uint8_t>& use = *use_out;
+    use.assign(a.n, 1);
+    if (a.use)
+        for (int i = 0; i < a.n; i++) use[i] = a.use[i] ? 1 : 0;
+    int i = 0, col = 0;
+    switch (qtl_check_finite(a.n, a.T, a.pheno, a.K, a.cov, use.data(), &i, &col)) {
+    case QTL_PHENO_NOT_FINITE: return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is used and not finite", col, i);
+    case QTL_COV_NOT_FINITE: return fail(ctx, CNF2_ERR_ARG, "covariate %d of individual %d is used and not finite", col, i);
+    }
+    return CNF2_OK;
+}
+// the rows of perm[P][n] are permutations that give a used individual (use[n], NULL = all) a used one
+static int qtl_check_perm(cnf2_ctx* ctx, int n, int P, const int32_t* perm, const uint8_t* use)
+{
+    int p = 0, i = 0, j = 0;
+    switch (qtl_check_permutations(n, P, perm, use, &p, &i, &j)) {
+    case QTL_NOT_A_PERMUTATION: return fail(ctx, CNF2_ERR_ARG, "row %d of perm is not a permutation of 0 .. n-1", p);
+    case QTL_PERM_TAKES_UNUSED:
+        return fail(ctx, CNF2_ERR_ARG, "permutation %d gives individual %d, which is used, the unused individual %d", p, i, j);
+    }
+    return CNF2_OK;
+}
+
 // every check of the phenotype side, before anything is written; use_out[n] = the mask with NULL expanded
 static int qtl_check(cnf2_ctx* ctx, const QtlArgs& a, std::vector<uint8_t>* use_out)
 {
@@ -1571,32 +1636,8 @@ static int qtl_check(cnf2_ctx* ctx, const QtlArgs& a, std::vector<uint8_t>* use_
         return fail(ctx, CNF2_ERR_ARG, "perm and perm_max_out must be NULL exactly when n_perm is 0");
     if (!a.lod || !a.coef || !a.rank || !a.rss0 || !a.n_used) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
     if ((size_t)a.T * ((size_t)a.P + 1) > (size_t)1 << 30) return fail(ctx, CNF2_ERR_ARG, "too many columns");
-    std::vector<uint8_t>& use = *use_out;
-    use.assign(a.n, 1);
-    if (a.use)
-        for (int i = 0; i < a.n; i++) use[i] = a.use[i] ? 1 : 0;
-    for (int i = 0; i < a.n; i++) {
-        if (!use[i]) continue;
-        for (int t = 0; t < a.T; t++)
-            if (!std::isfinite(a.pheno[(size_t)i * a.T + t]))
-                return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is used and not finite", t, i);
-        for (int k = 0; k < a.K; k++)
-            if (!std::isfinite(a.cov[(size_t)i * a.K + k]))
-                return fail(ctx, CNF2_ERR_ARG, "covariate %d of individual %d is used and not finite", k, i);
-    }
-    std::vector<uint8_t> seen(a.n);
-    for (int p = 0; p < a.P; p++) {
-        std::fill(seen.begin(), seen.end(), 0);
-        const int32_t* row = a.perm + (size_t)p * a.n;
-        for (int i = 0; i < a.n; i++) {
-            const int32_t j = row[i];
-            if (j < 0 || j >= a.n || seen[j]) return fail(ctx, CNF2_ERR_ARG, "row %d of perm is not a permutation of 0 .. n-1", p);
-            seen[j] = 1;
-            if (use[i] && !use[j])
-                return fail(ctx, CNF2_ERR_ARG, "permutation %d gives individual %d, which is used, the unused individual %d", p, i, j);
-        }
-    }
-    return CNF2_OK;
+    RC_TRY(qtl_check_values(ctx, a, use_out));
+    return qtl_check_perm(ctx, a.n, a.P, a.perm, use_out->data());
 }
 
 // The model does not depend on the units and offsets of traits and fixed-effect covariates (include/cnf2hip.h); the sums the
@@ -1657,61 +1698,73 @@ static int qtl_upload(cnf2_ctx* ctx, DevBuf<T>& buf, const T* src, size_t count)
     return CNF2_OK;
 }
 
-// the scan on device rows d_origin[n][M][4]; `a` has been validated and `use` is its expanded mask
-static int qtl_scan_impl(cnf2_ctx* ctx, const double* d_origin, const QtlArgs& a, const std::vector<uint8_t>& use, uint32_t flags)
+// The phenotype-side buffers the scans share: the staged phenotypes, covariates (with room for extra_cov more doubles behind
+// them), mask and permutations, the chromosome masks and the column image of a tile of rt columns (rt = 0: a scan without
+// one).  First the room for them ...
+static int qtl_reserve_inputs(cnf2_ctx* ctx, const QtlArgs& a, size_t rt, size_t extra_cov)
 {
-    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const int    M = ctx->n_markers, C = ctx->n_chrom, nx = a.K + 1;
-    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
-    // the column tile: the image under 1 GB, the tile maxima of a large map bounded, the caller's cap
-    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
-    rt = std::min(std::min(rt, (size_t)4096), R);
-    if (ctx->qtl_columns > 0) rt = std::min(rt, (size_t)ctx->qtl_columns);
-    // the map as the kernels read it: chromstarts, marker -> chromosome, the marker tiles (none straddles a chromosome start)
-    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
-    map.resize((size_t)C + 1 + M);
-    std::vector<int32_t> tiles, tstart(1, 0);
-    for (int c = 0; c < C; c++) {
-        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
-        for (int m = f; m < e; m++) map[(size_t)C + 1 + m] = c;
-        for (int m = f; m < e; m += 16) {
-            const int32_t t4[4] = {c, m, std::min(16, e - m), 0};
-            tiles.insert(tiles.end(), t4, t4 + 4);
-        }
-        tstart.push_back((int32_t)(tiles.size() / 4));
-    }
-    const size_t n_tiles = tiles.size() / 4, o_tiles = map.size();
-    map.insert(map.end(), tiles.begin(), tiles.end());
-    const size_t o_tstart = map.size();
-    map.insert(map.end(), tstart.begin(), tstart.end());
-
-    RC_TRY(qtl_upload(ctx, ctx->d_q_map, map.data(), map.size()));
+    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
+    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K + extra_cov)));
+    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
+    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
+    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)ctx->n_chrom * a.n));
+    if (rt > 0) RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
+    return CNF2_OK;
+}
+// ... then what the caller gave, with `use` its expanded mask
+static int qtl_upload_inputs(cnf2_ctx* ctx, const QtlArgs& a, const std::vector<uint8_t>& use)
+{
     RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
     RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
     RC_TRY(qtl_upload(ctx, ctx->d_q_use, use.data(), (size_t)a.n));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
-    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    return qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n);
+}
+// what qtl_gather_kernel reads of them (after qtl_reserve_inputs); r0 and rn are the caller's, per tile
+static QtlParams qtl_gather_params(const cnf2_ctx* ctx, const QtlArgs& a, size_t rt)
+{
+    QtlParams g;
+    memset(&g, 0, sizeof(g));
+    g.n = a.n, g.T = a.T, g.pheno = ctx->d_q_pheno, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm, g.Y = ctx->d_q_Y, g.rstride = (int)rt;
+    return g;
+}
+
+// the scan on the rows `org`; `a` has been validated and `use` is its expanded mask
+static int qtl_scan_impl(cnf2_ctx* ctx, QtlOrigin& org, const QtlArgs& a, const std::vector<uint8_t>& use, uint32_t flags)
+{
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int          M = ctx->n_markers, C = ctx->n_chrom, nx = a.K + 1;
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1);
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, 0, ctx->qtl_columns[QTL_CAP_SCAN]);
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, 16, true, true);
+
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
+    QtlParams q = qtl_gather_params(ctx, a, rt);
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_q_nc, (size_t)C, &q.nc));
+        RC_TRY(each(a.rank, ctx->d_q_rank, (size_t)M, &q.rank));
+        RC_TRY(each(a.lod, ctx->d_q_lod, (size_t)a.T * M, &q.lod));
+        RC_TRY(each(a.coef, ctx->d_q_coef, (size_t)a.T * M * 2, &q.coef));
+        RC_TRY(each(a.rss0, ctx->d_q_rss0, (size_t)a.T * C, &q.rss0));
+        return each(a.pmax, ctx->d_q_pmax, (size_t)a.P * a.T * C, &q.pmax);
+    };
+    RC_TRY(ctx->d_q_map.ensure(ctx, map.image.size()));
     RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
     RC_TRY(ctx->d_q_mk.ensure(ctx, (size_t)M * QTL_MK));
-    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
     RC_TRY(ctx->d_q_null.ensure(ctx, (size_t)C * (nx + 1) * rt));
-    if (a.P > 0) RC_TRY(ctx->d_q_tilemax.ensure(ctx, n_tiles * rt));
+    if (a.P > 0) RC_TRY(ctx->d_q_tilemax.ensure(ctx, map.n_tiles * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_q_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, use));
 
-    QtlParams q;
-    memset(&q, 0, sizeof(q));
-    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.nx = nx;
+    q.M = M, q.C = C, q.P = a.P, q.K = a.K, q.nx = nx;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
-    q.origin = d_origin, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.perm = ctx->d_q_perm;
-    q.cs = ctx->d_q_map, q.mchrom = ctx->d_q_map + (C + 1);
-    q.tiles = ctx->d_q_map + o_tiles, q.tile_start = ctx->d_q_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.origin = org.dev, q.cov = ctx->d_q_cov;
+    q.cs = ctx->d_q_map, q.mchrom = ctx->d_q_map + map.o_mchrom;
+    q.tiles = ctx->d_q_map + map.o_tiles, q.tile_start = ctx->d_q_map + map.o_tstart, q.n_tiles = (int)map.n_tiles;
     q.cmask = ctx->d_q_cmask, q.chol = ctx->d_q_chol, q.mk = ctx->d_q_mk;
-    q.Y = ctx->d_q_Y, q.nullq = ctx->d_q_null, q.tilemax = ctx->d_q_tilemax, q.rstride = (int)rt;
-    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_q_nc, (size_t)C, &q.nc));
-    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_q_rank, (size_t)M, &q.rank));
-    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_q_lod, (size_t)a.T * M, &q.lod));
-    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_q_coef, (size_t)a.T * M * 2, &q.coef));
-    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_q_rss0, (size_t)a.T * C, &q.rss0));
-    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_q_pmax, (size_t)a.P * a.T * C, &q.pmax));
+    q.nullq = ctx->d_q_null, q.tilemax = ctx->d_q_tilemax;
 
     launch_qtl_chrom(q, ctx->stream);
     launch_qtl_design(q, ctx->stream);
@@ -1724,16 +1777,7 @@ static int qtl_scan_impl(cnf2_ctx* ctx, const double* d_origin, const QtlArgs& a
         if (r0 + q.rn > (size_t)a.T) launch_qtl_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C));
-        RC_TRY(fetch_out(ctx, a.rank, q.rank, (size_t)M));
-        RC_TRY(fetch_out(ctx, a.lod, q.lod, (size_t)a.T * M));
-        RC_TRY(fetch_out(ctx, a.coef, q.coef, (size_t)a.T * M * 2));
-        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C));
-        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * C));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
 int cnf2_qtl_scan(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
@@ -1741,29 +1785,14 @@ int cnf2_qtl_scan(cnf2_ctx* ctx, int n, const double* origin, int n_traits, cons
                   double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
     QtlCentred           centred;
     RC_TRY(qtl_validate(ctx, a, &mask, &centred));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    if (flags & CNF2_QTL_ORIGIN_DEVICE) {
-        if ((uintptr_t)d_origin & 15) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
-    } else {
-        const size_t cnt = (size_t)n * ctx->n_markers * 4;
-        ctx->qtl_rows_n = 0;
-        RC_TRY(ctx->d_org.ensure(ctx, cnt));
-        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
-    return qtl_scan_impl(ctx, d_origin, a, mask, flags);
+    return qtl_scan_impl(ctx, org, a, mask, flags);
 }
 
 // cnf2_sweep_origins over the range with the rows in the context's buffer, then the scan on them
@@ -1795,47 +1824,34 @@ int cnf2_sweep_qtl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_ou
     }
     ctx->qtl_rows_n = a.n;
     ctx->qtl_rows_m = ctx->n_markers;
-    return qtl_scan_impl(ctx, ctx->d_org, a, mask, flags);
+    QtlOrigin org;
+    org.dev = ctx->d_org;
+    return qtl_scan_impl(ctx, org, a, mask, flags);
 }
 
 // ------------------------------------------------------------------------------------------------
-// Kinship sums (cnf2_kinship.h, cnf2_kinship_kernels.hip)
+// Kinship sums (cnf2_kinship.h, cnf2_kinship_kernels.hip), in the scans' order of steps
 // ------------------------------------------------------------------------------------------------
 int cnf2_kinship_sums(cnf2_ctx* ctx, int n, const double* origin, int chrom_begin, int chrom_end, double* sum_out,
                       int32_t* n_markers_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
     if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     if (n < 1 || n > 46340) return fail(ctx, CNF2_ERR_ARG, "n must be 1 .. 46340");
     if (chrom_begin < 0 || chrom_end > ctx->n_chrom || chrom_begin >= chrom_end)
         return fail(ctx, CNF2_ERR_ARG, "the chromosome range must be non-empty and within 0 .. %d", ctx->n_chrom);
     if (!sum_out || !n_markers_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool    dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    if (flags & CNF2_QTL_ORIGIN_DEVICE) {
-        if ((uintptr_t)d_origin & 15) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
-    } else {
-        const size_t cnt = (size_t)n * ctx->n_markers * 4;
-        ctx->qtl_rows_n = 0;
-        RC_TRY(ctx->d_org.ensure(ctx, cnt));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
-    KinParams q;
+    const bool dev = (flags & CNF2_OUT_DEVICE) != 0;
+    KinParams  q;
     memset(&q, 0, sizeof(q));
     q.n = n, q.M = ctx->n_markers;
     q.m_lo   = ctx->chromstarts[chrom_begin];
     q.n_mark = ctx->chromstarts[chrom_end] - q.m_lo;
     q.n_pad  = (n + KIN_TILE - 1) / KIN_TILE * KIN_TILE;
     q.m_pad  = (q.n_mark + KIN_KC - 1) / KIN_KC * KIN_KC;
-    q.origin = d_origin;
     const size_t  nn = (size_t)n * n;
     const int32_t n_mark = q.n_mark;
     const bool    split = kin_is_split(n, q.n_mark);
@@ -1843,10 +1859,13 @@ int cnf2_kinship_sums(cnf2_ctx* ctx, int n, const double* origin, int chrom_begi
     // the chunks summed together in a round: at most KIN_ROUND, their partial sums under 256 MB (the order of the additions
     // does not depend on it)
     const int     round = split ? (int)std::max<size_t>(1, std::min<size_t>(std::min(chunks, KIN_ROUND), ((size_t)256 << 20) / (nn * 8))) : 1;
+    auto outputs = [&](auto each) -> int { return each(sum_out, ctx->d_kin_sum, nn, &q.sum); };
+    RC_TRY(qtl_origin_reserve(ctx, org));
     RC_TRY(ctx->d_kin_image.ensure(ctx, (size_t)q.m_pad * q.n_pad));
     if (split) RC_TRY(ctx->d_kin_part.ensure(ctx, (size_t)round * nn));
-    RC_TRY(stage_out(ctx, dev, sum_out, ctx->d_kin_sum, nn, &q.sum));
-    q.image = ctx->d_kin_image;
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    q.origin = org.dev, q.image = ctx->d_kin_image;
     launch_kin_pack(q, ctx->stream);
     if (!split) {
         q.k_lo = 0, q.k_len = q.m_pad, q.out = q.sum;
@@ -1860,18 +1879,13 @@ int cnf2_kinship_sums(cnf2_ctx* ctx, int n, const double* origin, int chrom_begi
         }
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (dev) {
-        HIP_TRY(ctx, hipMemcpyAsync(n_markers_out, &n_mark, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        RC_TRY(fetch_out(ctx, sum_out, q.sum, nn));
-        *n_markers_out = n_mark;
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    if (dev) HIP_TRY(ctx, hipMemcpyAsync(n_markers_out, &n_mark, sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    else *n_markers_out = n_mark;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
 // ------------------------------------------------------------------------------------------------
-// Column scan (cnf2_qtlcols.h, cnf2_qtlcols_kernels.hip).  Everything is checked before anything is written or uploaded.
+// Column scan (cnf2_qtlcols.h, cnf2_qtlcols_kernels.hip), in the scans' order of steps
 // ------------------------------------------------------------------------------------------------
 int cnf2_qtl_scan_cols(cnf2_ctx* ctx, int n, int n_mark, int ne, const double* reg, const double* scale, int nx, const double* x0,
                        int n_traits, const double* pheno, int n_perm, const int32_t* perm, double* lod_out, double* coef_out,
@@ -1896,51 +1910,44 @@ int cnf2_qtl_scan_cols(cnf2_ctx* ctx, int n, int n_mark, int ne, const double* r
     if (scale)
         for (int i = 0; i < n; i++)
             if (!std::isfinite(scale[i])) return fail(ctx, CNF2_ERR_ARG, "scale is not finite at individual %d", i);
-    std::vector<uint8_t> seen(n);
-    for (int p = 0; p < n_perm; p++) {
-        std::fill(seen.begin(), seen.end(), 0);
-        const int32_t* row = perm + (size_t)p * n;
-        for (int i = 0; i < n; i++) {
-            const int32_t j = row[i];
-            if (j < 0 || j >= n || seen[j]) return fail(ctx, CNF2_ERR_ARG, "row %d of perm is not a permutation of 0 .. n-1", p);
-            seen[j] = 1;
-        }
-    }
+    RC_TRY(qtl_check_perm(ctx, n, n_perm, perm, nullptr));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
     const int    M = n_mark, T = n_traits, P = n_perm;
-    // the column tile: the image under 1 GB, the tile maxima bounded, the caller's cap (cnf2_set_qtl_columns)
-    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)n));
-    rt = std::min(std::min(rt, (size_t)4096), R);
-    if (ctx->qtl_columns > 0) rt = std::min(rt, (size_t)ctx->qtl_columns);
-    const size_t n_tiles = ((size_t)M + 15) / 16;
+    const size_t rt = qtl_column_tile(n, R, P, 0, ctx->qtl_columns[QTL_CAP_SCAN]), n_tiles = ((size_t)M + 15) / 16;
+    const size_t n_reg = reg_dev ? 0 : (size_t)n * M * ne, n_scale = scale ? (size_t)n : 0;
 
     QtlColsParams q;
     memset(&q, 0, sizeof(q));
-    q.n = n, q.M = M, q.ne = ne, q.T = T, q.P = P, q.nx = nx;
-    if (reg_dev) q.reg = reg;
-    else {
-        RC_TRY(qtl_upload(ctx, ctx->d_ql_reg, reg, (size_t)n * M * ne));
-        q.reg = ctx->d_ql_reg;
-    }
-    RC_TRY(qtl_upload(ctx, ctx->d_ql_scale, scale, scale ? (size_t)n : 0));
-    RC_TRY(qtl_upload(ctx, ctx->d_ql_x0, x0, (size_t)n * nx));
-    RC_TRY(qtl_upload(ctx, ctx->d_ql_pheno, pheno, (size_t)n * T));
-    RC_TRY(qtl_upload(ctx, ctx->d_ql_perm, perm, (size_t)P * n));
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(rank_out, ctx->d_ql_rank, (size_t)M, &q.rank));
+        RC_TRY(each(lod_out, ctx->d_ql_lod, (size_t)T * M, &q.lod));
+        RC_TRY(each(coef_out, ctx->d_ql_coef, (size_t)T * M * 2, &q.coef));
+        RC_TRY(each(rss0_out, ctx->d_ql_rss0, (size_t)T, &q.rss0));
+        return each(perm_max_out, ctx->d_ql_pmax, (size_t)P * T, &q.pmax);
+    };
+    if (n_reg > 0) RC_TRY(ctx->d_ql_reg.ensure(ctx, n_reg));
+    if (n_scale > 0) RC_TRY(ctx->d_ql_scale.ensure(ctx, n_scale));
+    RC_TRY(ctx->d_ql_x0.ensure(ctx, (size_t)n * nx));
+    RC_TRY(ctx->d_ql_pheno.ensure(ctx, (size_t)n * T));
+    if (P > 0) RC_TRY(ctx->d_ql_perm.ensure(ctx, (size_t)P * n));
     RC_TRY(ctx->d_ql_chol.ensure(ctx, QTL_CHOL));
     RC_TRY(ctx->d_ql_mk.ensure(ctx, (size_t)M * QTL_MK));
     RC_TRY(ctx->d_ql_Y.ensure(ctx, (size_t)n * rt));
     RC_TRY(ctx->d_ql_null.ensure(ctx, (size_t)(nx + 1) * rt));
     if (P > 0) RC_TRY(ctx->d_ql_tilemax.ensure(ctx, n_tiles * rt));
-    q.scale = scale ? ctx->d_ql_scale.ptr : nullptr;
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_reg, reg, n_reg));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_scale, scale, n_scale));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_x0, x0, (size_t)n * nx));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_pheno, pheno, (size_t)n * T));
+    RC_TRY(qtl_upload(ctx, ctx->d_ql_perm, perm, (size_t)P * n));
+
+    q.n = n, q.M = M, q.ne = ne, q.T = T, q.P = P, q.nx = nx;
+    q.reg = reg_dev ? reg : ctx->d_ql_reg.ptr, q.scale = scale ? ctx->d_ql_scale.ptr : nullptr;
     q.x0 = ctx->d_ql_x0, q.pheno = ctx->d_ql_pheno, q.perm = ctx->d_ql_perm;
     q.chol = ctx->d_ql_chol, q.mk = ctx->d_ql_mk, q.Y = ctx->d_ql_Y, q.nullq = ctx->d_ql_null, q.tilemax = ctx->d_ql_tilemax;
     q.rstride = (int)rt, q.n_tiles = (int)n_tiles;
-    RC_TRY(stage_out(ctx, dev, rank_out, ctx->d_ql_rank, (size_t)M, &q.rank));
-    RC_TRY(stage_out(ctx, dev, lod_out, ctx->d_ql_lod, (size_t)T * M, &q.lod));
-    RC_TRY(stage_out(ctx, dev, coef_out, ctx->d_ql_coef, (size_t)T * M * 2, &q.coef));
-    RC_TRY(stage_out(ctx, dev, rss0_out, ctx->d_ql_rss0, (size_t)T, &q.rss0));
-    RC_TRY(stage_out(ctx, dev, perm_max_out, ctx->d_ql_pmax, (size_t)P * T, &q.pmax));
 
     launch_qtlcols_null(q, ctx->stream);
     launch_qtlcols_design(q, ctx->stream);
@@ -1953,19 +1960,11 @@ int cnf2_qtl_scan_cols(cnf2_ctx* ctx, int n, int n_mark, int ne, const double* r
         if (r0 + q.rn > (size_t)T) launch_qtlcols_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, rank_out, q.rank, (size_t)M));
-        RC_TRY(fetch_out(ctx, lod_out, q.lod, (size_t)T * M));
-        RC_TRY(fetch_out(ctx, coef_out, q.coef, (size_t)T * M * 2));
-        RC_TRY(fetch_out(ctx, rss0_out, q.rss0, (size_t)T));
-        if (P > 0) RC_TRY(fetch_out(ctx, perm_max_out, q.pmax, (size_t)P * T));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
 // ------------------------------------------------------------------------------------------------
-// Bootstrap scan (cnf2_qtlboot.h, cnf2_qtlboot_kernels.hip).  Everything is checked before anything is written or uploaded.
+// Bootstrap scan (cnf2_qtlboot.h, cnf2_qtlboot_kernels.hip), in the scans' order of steps
 // ------------------------------------------------------------------------------------------------
 int cnf2_qtl_scan_boot(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                        const double* cov, int chrom_begin, int chrom_end, int n_boot, const int32_t* count, double* boot_max_out,
@@ -1973,8 +1972,8 @@ int cnf2_qtl_scan_boot(cnf2_ctx* ctx, int n, const double* origin, int n_traits,
 {
     if (!ctx) return CNF2_ERR_ARG;
     if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     if (n < 1 || n_traits < 1 || !pheno) return fail(ctx, CNF2_ERR_ARG, "n and n_traits must be at least 1 and pheno not NULL");
     if (n_cov < 0 || n_cov > QTL_MAXK || (n_cov > 0 && !cov)) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d, with cov", QTL_MAXK);
     if (chrom_begin < 0 || chrom_end > ctx->n_chrom || chrom_begin >= chrom_end)
@@ -1985,89 +1984,55 @@ int cnf2_qtl_scan_boot(cnf2_ctx* ctx, int n, const double* origin, int n_traits,
     const int    m_lo = ctx->chromstarts[chrom_begin], n_mark = ctx->chromstarts[chrom_end] - m_lo;
     if ((size_t)B * T > (size_t)1 << 30 || (size_t)B * T * (size_t)n_mark > (size_t)1 << 40 || T > 65535 || nc > 65535)
         return fail(ctx, CNF2_ERR_ARG, "too many replicates, traits or chromosomes");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
-    std::vector<uint8_t> mask(n, 1);
-    if (use)
-        for (int i = 0; i < n; i++) mask[i] = use[i] ? 1 : 0;
-    for (int i = 0; i < n; i++) {
-        if (!mask[i]) continue;
-        for (int t = 0; t < T; t++)
-            if (!std::isfinite(pheno[(size_t)i * T + t]))
-                return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is used and not finite", t, i);
-        for (int k = 0; k < K; k++)
-            if (!std::isfinite(cov[(size_t)i * K + k]))
-                return fail(ctx, CNF2_ERR_ARG, "covariate %d of individual %d is used and not finite", k, i);
-    }
+    // (the phenotype side is the single scan's without permutations; the scan has its own outputs)
+    QtlArgs a = {n, T, K, 0, pheno, use, cov, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_check_values(ctx, a, &mask));
     for (int b = 0; b < B; b++)
         for (int i = 0; i < n; i++) {
             const int32_t v = count[(size_t)b * n + i];
             if (v < 0) return fail(ctx, CNF2_ERR_ARG, "count of individual %d in replicate %d is negative", i, b);
             if (v > 0 && !mask[i]) return fail(ctx, CNF2_ERR_ARG, "replicate %d draws individual %d, which is not used", b, i);
         }
-    // the columns minus their unweighted means over the used individuals, as every scan (qtl_centre)
+    // the columns minus their unweighted means over the used individuals, as every scan
     QtlCentred centred;
-    qtl_centre_columns(pheno, n, T, mask, centred.pheno);
-    if (K > 0) qtl_centre_columns(cov, n, K, mask, centred.cov);
+    qtl_centre(a, mask, centred);
 
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    if (flags & CNF2_QTL_ORIGIN_DEVICE) {
-        if ((uintptr_t)d_origin & 15) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
-    } else {
-        const size_t cnt = (size_t)n * ctx->n_markers * 4;
-        ctx->qtl_rows_n = 0;
-        RC_TRY(ctx->d_org.ensure(ctx, cnt));
-        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, cnt * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
     const bool dev = (flags & CNF2_OUT_DEVICE) != 0;
     // the map as the kernels read it: the first marker of every scanned chromosome, the marker tiles, the tile starts
-    std::vector<int32_t> map, tiles, tstart(1, 0);
-    for (int cc = 0; cc < nc; cc++) {
-        const int f = ctx->chromstarts[chrom_begin + cc], e = ctx->chromstarts[chrom_begin + cc + 1];
-        map.push_back(f);
-        for (int m = f; m < e; m += 16) {
-            const int32_t t4[4] = {cc, m, std::min(16, e - m), 0};
-            tiles.insert(tiles.end(), t4, t4 + 4);
-        }
-        tstart.push_back((int32_t)(tiles.size() / 4));
-    }
-    const size_t n_tiles = tiles.size() / 4, o_tiles = map.size();
-    map.insert(map.end(), tiles.begin(), tiles.end());
-    const size_t o_tstart = map.size();
-    map.insert(map.end(), tstart.begin(), tstart.end());
-    // the replicate tile: a multiple of 16, the weight image under 1 GB, the tile maxima of a large map bounded
-    size_t bt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)n) / 16 * 16);
-    bt = std::min(std::min(bt, (size_t)4096), ((size_t)B + 15) / 16 * 16);
-    const size_t recd = qtlboot_rec_doubles(T);
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), ctx->n_chrom, chrom_begin, chrom_end, 16, false, false);
+    const size_t       n_tiles = map.n_tiles, bt = qtl_replicate_tile(n, B), recd = qtlboot_rec_doubles(T);
 
-    RC_TRY(qtl_upload(ctx, ctx->d_qo_map, map.data(), map.size()));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, centred.pheno.data(), (size_t)n * T));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, centred.cov.data(), (size_t)n * K));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)n));
-    RC_TRY(qtl_upload(ctx, ctx->d_qo_count, count, (size_t)B * n));
+    QtlBootParams q;
+    memset(&q, 0, sizeof(q));
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(boot_max_out, ctx->d_qo_max, (size_t)B * T * nc, &q.boot_max));
+        RC_TRY(each(boot_arg_out, ctx->d_qo_arg, (size_t)B * T * nc, &q.boot_arg));
+        RC_TRY(each(n_boot_out, ctx->d_qo_nb, (size_t)B * nc, &q.n_boot));
+        return each(boot_lod_out, ctx->d_qo_lod, (size_t)B * T * n_mark, &q.boot_lod);
+    };
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, 0, 0));
+    RC_TRY(ctx->d_qo_map.ensure(ctx, map.image.size()));
+    RC_TRY(ctx->d_qo_count.ensure(ctx, (size_t)B * n));
     RC_TRY(ctx->d_qo_cmask.ensure(ctx, (size_t)nc * n));
     RC_TRY(ctx->d_qo_W.ensure(ctx, (size_t)n * bt));
     RC_TRY(ctx->d_qo_rec.ensure(ctx, bt * nc * recd));
     RC_TRY(ctx->d_qo_tilemax.ensure(ctx, n_tiles * bt * T));
     RC_TRY(ctx->d_qo_tilearg.ensure(ctx, n_tiles * bt * T));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qo_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+    RC_TRY(qtl_upload(ctx, ctx->d_qo_count, count, (size_t)B * n));
 
-    QtlBootParams q;
-    memset(&q, 0, sizeof(q));
     q.n = n, q.M = ctx->n_markers, q.T = T, q.K = K, q.nx = K + 1;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
     q.nc = nc, q.m_lo = m_lo, q.n_mark = n_mark;
-    q.origin = d_origin, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.count = ctx->d_qo_count;
-    q.first = ctx->d_qo_map, q.tiles = ctx->d_qo_map + o_tiles, q.tile_start = ctx->d_qo_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.origin = org.dev, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.count = ctx->d_qo_count;
+    q.first = ctx->d_qo_map, q.tiles = ctx->d_qo_map + map.o_tiles, q.tile_start = ctx->d_qo_map + map.o_tstart, q.n_tiles = (int)n_tiles;
     q.cmask = ctx->d_qo_cmask, q.W = ctx->d_qo_W, q.rec = ctx->d_qo_rec, q.tilemax = ctx->d_qo_tilemax, q.tilearg = ctx->d_qo_tilearg;
-    RC_TRY(stage_out(ctx, dev, boot_max_out, ctx->d_qo_max, (size_t)B * T * nc, &q.boot_max));
-    RC_TRY(stage_out(ctx, dev, boot_arg_out, ctx->d_qo_arg, (size_t)B * T * nc, &q.boot_arg));
-    RC_TRY(stage_out(ctx, dev, n_boot_out, ctx->d_qo_nb, (size_t)B * nc, &q.n_boot));
-    RC_TRY(stage_out(ctx, dev, boot_lod_out, ctx->d_qo_lod, (size_t)B * T * n_mark, &q.boot_lod));
 
     const int tc = qtlboot_trait_chunk(T);
     launch_qtlboot_mask(q, ctx->stream);
@@ -2086,29 +2051,18 @@ int cnf2_qtl_scan_boot(cnf2_ctx* ctx, int n, const double* origin, int n_traits,
         launch_qtlboot_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, boot_max_out, q.boot_max, (size_t)B * T * nc));
-        RC_TRY(fetch_out(ctx, boot_arg_out, q.boot_arg, (size_t)B * T * nc));
-        RC_TRY(fetch_out(ctx, n_boot_out, q.n_boot, (size_t)B * nc));
-        if (boot_lod_out) RC_TRY(fetch_out(ctx, boot_lod_out, q.boot_lod, (size_t)B * T * n_mark));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
-// The pair scan on device rows d_origin[n][M][4]: cnf2_qtl2.h, cnf2_qtl2_kernels.hip.  Everything is checked and every
-// buffer is there before the first launch writes.
+// The pair scan on origin rows [n][M][4]: cnf2_qtl2.h, cnf2_qtl2_kernels.hip
 int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const int32_t* sel, int n_traits, const double* pheno,
                    const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm, double* lod_add_out,
                    double* lod_full_out, int32_t* rank_add_out, int32_t* rank_full_out, double* rss0_out, int32_t* n_used_out,
                    double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     // (the phenotype side is the single scan's; its lod / coef / rank slots stand for this call's four pair outputs)
     QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_add_out, lod_full_out, rss0_out, perm_max_out,
                  rank_add_out, n_used_out};
@@ -2123,19 +2077,12 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
         if (sel[j] < 0 || sel[j] >= M || (j > 0 && sel[j] <= sel[j - 1]))
             return fail(ctx, CNF2_ERR_ARG, "sel must be strictly ascending marker indices below %d", M);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
-    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
 
     const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
     const size_t R = (size_t)a.T * ((size_t)a.P + 1), LL = (size_t)L * L;
     const int    n_chunks = (L - 1 + QTL2_CHUNK - 1) / QTL2_CHUNK;
-    // the column tile: the image under 1 GB, the chunk maxima under 256 MB, the caller's cap
-    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
-    rt = std::min(rt, (size_t)4096);
-    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (24 * (size_t)L * n_chunks)));
-    rt = std::min(rt, R);
-    if (ctx->qtl2_columns > 0) rt = std::min(rt, (size_t)ctx->qtl2_columns);
+    const size_t rt = qtl_column_tile(a.n, R, a.P, (size_t)3 * L * n_chunks, ctx->qtl_columns[QTL_CAP_SCAN2]);
+    // the map as the kernels read it: chromstarts, sel, the chromosomes of sel
     std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
     map.insert(map.end(), sel, sel + L);
     for (int j = 0, c = 0; j < L; j++) {
@@ -2143,48 +2090,34 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
         map.push_back(c);
     }
 
-    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
     Qtl2Params q;
     memset(&q, 0, sizeof(q));
-    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_q2_nc, (size_t)C * C, &q.nc));
+        RC_TRY(each(rank_add_out, ctx->d_q2_rank_add, LL, &q.rank_add));
+        RC_TRY(each(rank_full_out, ctx->d_q2_rank_full, LL, &q.rank_full));
+        RC_TRY(each(lod_add_out, ctx->d_q2_lod_add, (size_t)a.T * LL, &q.lod_add));
+        RC_TRY(each(lod_full_out, ctx->d_q2_lod_full, (size_t)a.T * LL, &q.lod_full));
+        RC_TRY(each(a.rss0, ctx->d_q2_rss0, (size_t)a.T * C * C, &q.rss0));
+        return each(a.pmax, ctx->d_q2_pmax, (size_t)a.P * a.T * 3, &q.pmax);
+    };
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
     RC_TRY(ctx->d_q2_map.ensure(ctx, map.size()));
-    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
-    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
-    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
-    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
-    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
-    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
     RC_TRY(ctx->d_q2_yy.ensure(ctx, (size_t)C * C * rt));
     if (a.P > 0) RC_TRY(ctx->d_q2_chunkmax.ensure(ctx, (size_t)L * n_chunks * 3 * rt));
-    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_q2_nc, (size_t)C * C, &q.nc));
-    RC_TRY(stage_out(ctx, dev, rank_add_out, ctx->d_q2_rank_add, LL, &q.rank_add));
-    RC_TRY(stage_out(ctx, dev, rank_full_out, ctx->d_q2_rank_full, LL, &q.rank_full));
-    RC_TRY(stage_out(ctx, dev, lod_add_out, ctx->d_q2_lod_add, (size_t)a.T * LL, &q.lod_add));
-    RC_TRY(stage_out(ctx, dev, lod_full_out, ctx->d_q2_lod_full, (size_t)a.T * LL, &q.lod_full));
-    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_q2_rss0, (size_t)a.T * C * C, &q.rss0));
-    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_q2_pmax, (size_t)a.P * a.T * 3, &q.pmax));
-    if (staged) {
-        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
-        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
     RC_TRY(qtl_upload(ctx, ctx->d_q2_map, map.data(), map.size()));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
 
     q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.L = L;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
-    q.origin = d_origin, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.perm = ctx->d_q_perm;
+    q.origin = org.dev, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.perm = ctx->d_q_perm;
     q.cs = ctx->d_q2_map, q.sel = ctx->d_q2_map + (C + 1), q.selchrom = ctx->d_q2_map + (C + 1 + L);
     q.cmask = ctx->d_q_cmask, q.Y = ctx->d_q_Y, q.yy = ctx->d_q2_yy, q.chunkmax = ctx->d_q2_chunkmax;
     q.rstride = (int)rt, q.n_chunks = n_chunks;
-    QtlParams g;                           // what qtl_gather_kernel reads
-    memset(&g, 0, sizeof(g));
-    g.n = a.n, g.T = a.T, g.pheno = q.pheno, g.use = q.use, g.perm = q.perm, g.Y = q.Y, g.rstride = q.rstride;
+    QtlParams g = qtl_gather_params(ctx, a, rt);
 
     launch_qtl2_mask(q, ctx->stream);
     launch_qtl2_fill(q, ctx->stream);
@@ -2197,31 +2130,17 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
         if (r0 + q.rn > (size_t)a.T) launch_qtl2_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C * C));
-        RC_TRY(fetch_out(ctx, rank_add_out, q.rank_add, LL));
-        RC_TRY(fetch_out(ctx, rank_full_out, q.rank_full, LL));
-        RC_TRY(fetch_out(ctx, lod_add_out, q.lod_add, (size_t)a.T * LL));
-        RC_TRY(fetch_out(ctx, lod_full_out, q.lod_full, (size_t)a.T * LL));
-        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C * C));
-        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * 3));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
-// The extended single-locus scan on device rows d_origin[n][M][4]: cnf2_qtlx.h, cnf2_qtlx_kernels.hip.  Everything is
-// checked and every buffer is there before the first launch writes.
+// The extended single-locus scan on origin rows [n][M][4]: cnf2_qtlx.h, cnf2_qtlx_kernels.hip
 int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                    const double* cov, int n_int, int n_perm, const int32_t* perm, double* lod_out, double* coef_out,
                    int32_t* rank_out, double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
     QtlCentred           centred;
@@ -2232,82 +2151,49 @@ int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, con
         return fail(ctx, CNF2_ERR_ARG, "the design has %d columns (1 + n_cov + effects x (1 + n_int)); at most %d", ds.w, QTLX_MAXW);
     const int M = ctx->n_markers, C = ctx->n_chrom, ncoef = ds.w - ds.nx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
-    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
 
-    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
-    // the map as the kernels read it: chromstarts, the marker tiles (none straddles a chromosome start), their starts
-    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
-    std::vector<int32_t> tstart(1, 0);
-    for (int c = 0; c < C; c++) {
-        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
-        for (int m = f; m < e; m += QTLX_TILE) {
-            const int32_t t4[4] = {c, m, std::min(QTLX_TILE, e - m), 0};
-            map.insert(map.end(), t4, t4 + 4);
-        }
-        tstart.push_back((int32_t)((map.size() - (size_t)(C + 1)) / 4));
-    }
-    const size_t n_tiles = (map.size() - (size_t)(C + 1)) / 4, o_tstart = map.size();
-    map.insert(map.end(), tstart.begin(), tstart.end());
-    // the column tile: the image under 1 GB, the tile maxima under 256 MB, the caller's cap
-    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
-    rt = std::min(rt, (size_t)4096);
-    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (8 * QTLX_NSTAT * n_tiles)));
-    rt = std::min(rt, R);
-    if (ctx->qtlx_columns > 0) rt = std::min(rt, (size_t)ctx->qtlx_columns);
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1);
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLX_TILE, false, true);
+    const size_t       n_tiles = map.n_tiles;
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, QTLX_NSTAT * n_tiles, ctx->qtl_columns[QTL_CAP_SCANX]);
+    // (with interactive covariates the raw cov[n][K] follows the centred one: the products are those of the raw values)
+    const size_t       n_covs = (size_t)a.n * a.K, n_raw = n_int > 0 ? n_covs : 0;
 
-    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
     QtlxParams q;
     memset(&q, 0, sizeof(q));
-    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
-    RC_TRY(ctx->d_qx_map.ensure(ctx, map.size()));
-    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
-    // (with interactive covariates the raw cov[n][K] follows the centred one: the products are those of the raw values)
-    const size_t n_covs = (size_t)a.n * a.K;
-    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, n_covs * (n_int > 0 ? 2 : 1))));
-    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
-    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
-    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
-    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_qx_nc, (size_t)C, &q.nc));
+        RC_TRY(each(a.rank, ctx->d_qx_rank, (size_t)M * 3, &q.rank));
+        RC_TRY(each(a.lod, ctx->d_qx_lod, (size_t)a.T * M * 3, &q.lod));
+        RC_TRY(each(a.coef, ctx->d_qx_coef, (size_t)a.T * M * ncoef, &q.coef));
+        RC_TRY(each(a.rss0, ctx->d_qx_rss0, (size_t)a.T * C, &q.rss0));
+        return each(a.pmax, ctx->d_qx_pmax, (size_t)a.P * a.T * C * QTLX_NSTAT, &q.pmax);
+    };
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, n_raw));
+    RC_TRY(ctx->d_qx_map.ensure(ctx, map.image.size()));
     RC_TRY(ctx->d_qx_yy.ensure(ctx, (size_t)C * rt));
     if (a.P > 0) RC_TRY(ctx->d_qx_tilemax.ensure(ctx, n_tiles * QTLX_NSTAT * rt));
-    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_qx_nc, (size_t)C, &q.nc));
-    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_qx_rank, (size_t)M * 3, &q.rank));
-    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_qx_lod, (size_t)a.T * M * 3, &q.lod));
-    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_qx_coef, (size_t)a.T * M * ncoef, &q.coef));
-    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_qx_rss0, (size_t)a.T * C, &q.rss0));
-    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_qx_pmax, (size_t)a.P * a.T * C * QTLX_NSTAT, &q.pmax));
-    if (staged) {
-        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
-        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
-    RC_TRY(qtl_upload(ctx, ctx->d_qx_map, map.data(), map.size()));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, n_covs));
-    if (n_int > 0) {
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_q_cov.ptr + n_covs, cov, n_covs * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qx_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+    if (n_raw > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_q_cov.ptr + n_covs, cov, n_raw * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
-    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
 
     q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.Ki = n_int;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
-    q.origin = d_origin, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use;
-    q.cov_raw = n_int > 0 ? ctx->d_q_cov.ptr + n_covs : ctx->d_q_cov.ptr;
-    q.cs = ctx->d_qx_map, q.tiles = ctx->d_qx_map + (C + 1), q.tile_start = ctx->d_qx_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.origin = org.dev, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use;
+    q.cov_raw = ctx->d_q_cov.ptr + n_raw;
+    q.cs = ctx->d_qx_map, q.tiles = ctx->d_qx_map + map.o_tiles, q.tile_start = ctx->d_qx_map + map.o_tstart, q.n_tiles = (int)n_tiles;
     q.cmask = ctx->d_q_cmask, q.Y = ctx->d_q_Y, q.yy = ctx->d_qx_yy, q.tilemax = ctx->d_qx_tilemax, q.rstride = (int)rt;
     Qtl2Params k;                          // what qtl2_mask_kernel reads and writes
     memset(&k, 0, sizeof(k));
-    k.n = a.n, k.M = M, k.C = C, k.origin = d_origin, k.use = ctx->d_q_use, k.cs = ctx->d_qx_map, k.cmask = ctx->d_q_cmask;
-    QtlParams g;                           // what qtl_gather_kernel reads
-    memset(&g, 0, sizeof(g));
-    g.n = a.n, g.T = a.T, g.pheno = ctx->d_q_pheno, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm, g.Y = ctx->d_q_Y, g.rstride = q.rstride;
+    k.n = a.n, k.M = M, k.C = C, k.origin = org.dev, k.use = ctx->d_q_use, k.cs = ctx->d_qx_map, k.cmask = ctx->d_q_cmask;
+    QtlParams g = qtl_gather_params(ctx, a, rt);
 
     launch_qtl2_mask(k, ctx->stream);
     for (size_t r0 = 0; r0 < R; r0 += rt) {
@@ -2319,16 +2205,7 @@ int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, con
         if (r0 + q.rn > (size_t)a.T) launch_qtlx_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C));
-        RC_TRY(fetch_out(ctx, a.rank, q.rank, (size_t)M * 3));
-        RC_TRY(fetch_out(ctx, a.lod, q.lod, (size_t)a.T * M * 3));
-        RC_TRY(fetch_out(ctx, a.coef, q.coef, (size_t)a.T * M * ncoef));
-        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C));
-        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * C * QTLX_NSTAT));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
 // rows_out[n_sel][n][4] = the rows the last cnf2_sweep_qtl left in the context at the markers sel: one strided copy per
@@ -2336,8 +2213,7 @@ int cnf2_qtl_scanx(cnf2_ctx* ctx, int n, const double* origin, int n_traits, con
 int cnf2_qtl_kept_rows(cnf2_ctx* ctx, int n, int n_sel, const int32_t* sel, double* rows_out)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    if (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers || ctx->d_org.cap < (size_t)n * ctx->n_markers * 4)
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    RC_TRY(qtl_kept_check(ctx, n));
     if (n_sel < 0 || (n_sel > 0 && (!sel || !rows_out))) return fail(ctx, CNF2_ERR_ARG, "n_sel must not be negative, with sel and rows_out");
     const int M = ctx->n_markers;
     for (int j = 0; j < n_sel; j++)
@@ -2350,19 +2226,15 @@ int cnf2_qtl_kept_rows(cnf2_ctx* ctx, int n, int n_sel, const int32_t* sel, doub
     return CNF2_OK;
 }
 
-// The cofactor scan on device rows d_origin[n][M][4]: cnf2_qtlcof.h, cnf2_qtlcof_kernels.hip.  Everything is checked and
-// every buffer is there before the first launch writes.
+// The cofactor scan on origin rows [n][M][4]: cnf2_qtlcof.h, cnf2_qtlcof_kernels.hip
 int cnf2_qtl_scan_cof(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                       const double* cov, int n_cof, const int32_t* cof, const int32_t* excl_lo, const int32_t* excl_hi, int n_perm,
                       const int32_t* perm, double* lod_out, double* lod_base_out, double* coef_out, int32_t* rank_out,
                       int32_t* rank_cof_out, double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
     QtlCentred           centred;
@@ -2386,85 +2258,53 @@ int cnf2_qtl_scan_cof(cnf2_ctx* ctx, int n, const double* origin, int n_traits, 
                         excl_hi[k], k, cof[k]);
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
-    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
 
     const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
     const size_t R = (size_t)a.T * ((size_t)a.P + 1);
-    // the map as the kernels read it: chromstarts, the marker tiles (none straddles a chromosome start), their starts, the
-    // cofactors, the first markers of their chromosomes, and per marker the word of the cofactors left out there
-    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
-    std::vector<int32_t> tstart(1, 0);
-    for (int c = 0; c < C; c++) {
-        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
-        for (int m = f; m < e; m += QTLCOF_TILE) {
-            const int32_t t4[4] = {c, m, std::min(QTLCOF_TILE, e - m), 0};
-            map.insert(map.end(), t4, t4 + 4);
-        }
-        tstart.push_back((int32_t)((map.size() - (size_t)(C + 1)) / 4));
-    }
-    const size_t n_tiles = (map.size() - (size_t)(C + 1)) / 4, o_tstart = map.size();
-    map.insert(map.end(), tstart.begin(), tstart.end());
-    const size_t o_cof = map.size();
+    // behind the marker map: the cofactors, the first markers of their chromosomes, and per marker the word of the
+    // cofactors left out there
+    QtlMarkerMap          mm = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLCOF_TILE, false, true);
+    std::vector<int32_t>& map = mm.image;
+    const size_t          n_tiles = mm.n_tiles, o_cof = map.size();
     map.insert(map.end(), cof, cof + Q);
     const size_t o_cofstart = map.size();
     map.insert(map.end(), cofstart.begin(), cofstart.end());
     const size_t o_skipw = map.size();
     for (int m = 0; m < M; m++) map.push_back((int32_t)qtlcof_skip_word(m, Q, excl_lo, excl_hi));
-    // the column tile: the image under 1 GB, the tile maxima under 256 MB, the caller's cap
-    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
-    rt = std::min(rt, (size_t)4096);
-    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (8 * n_tiles)));
-    rt = std::min(rt, R);
-    if (ctx->qtlcof_columns > 0) rt = std::min(rt, (size_t)ctx->qtlcof_columns);
+    const size_t rt = qtl_column_tile(a.n, R, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_COF]);
 
-    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
     QtlcofParams q;
     memset(&q, 0, sizeof(q));
-    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_qc_nc, (size_t)C, &q.nc));
+        RC_TRY(each(a.rank, ctx->d_qc_rank, (size_t)M, &q.rank));
+        RC_TRY(each(rank_cof_out, ctx->d_qc_rank_cof, (size_t)M, &q.rank_cof));
+        RC_TRY(each(a.lod, ctx->d_qc_lod, (size_t)a.T * M, &q.lod));
+        RC_TRY(each(lod_base_out, ctx->d_qc_lod_base, (size_t)a.T * M, &q.lod_base));
+        RC_TRY(each(a.coef, ctx->d_qc_coef, (size_t)a.T * M * ds.ne, &q.coef));
+        RC_TRY(each(a.rss0, ctx->d_qc_rss0, (size_t)a.T * C, &q.rss0));
+        return each(a.pmax, ctx->d_qc_pmax, (size_t)a.P * a.T * C, &q.pmax);
+    };
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
     RC_TRY(ctx->d_qc_map.ensure(ctx, map.size()));
-    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
-    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
-    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
-    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
-    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
-    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
     RC_TRY(ctx->d_qc_img.ensure(ctx, std::max<size_t>(1, (size_t)a.n * ds.nc)));
     RC_TRY(ctx->d_qc_yy.ensure(ctx, (size_t)C * rt));
     if (a.P > 0) RC_TRY(ctx->d_qc_tilemax.ensure(ctx, n_tiles * rt));
-    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_qc_nc, (size_t)C, &q.nc));
-    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_qc_rank, (size_t)M, &q.rank));
-    RC_TRY(stage_out(ctx, dev, rank_cof_out, ctx->d_qc_rank_cof, (size_t)M, &q.rank_cof));
-    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_qc_lod, (size_t)a.T * M, &q.lod));
-    RC_TRY(stage_out(ctx, dev, lod_base_out, ctx->d_qc_lod_base, (size_t)a.T * M, &q.lod_base));
-    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_qc_coef, (size_t)a.T * M * ds.ne, &q.coef));
-    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_qc_rss0, (size_t)a.T * C, &q.rss0));
-    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_qc_pmax, (size_t)a.P * a.T * C, &q.pmax));
-    if (staged) {
-        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
-        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
     RC_TRY(qtl_upload(ctx, ctx->d_qc_map, map.data(), map.size()));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
 
     q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.Q = Q;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
-    q.origin = d_origin, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use;
-    q.cs = ctx->d_qc_map, q.tiles = ctx->d_qc_map + (C + 1), q.tile_start = ctx->d_qc_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.origin = org.dev, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use;
+    q.cs = ctx->d_qc_map, q.tiles = ctx->d_qc_map + mm.o_tiles, q.tile_start = ctx->d_qc_map + mm.o_tstart, q.n_tiles = (int)n_tiles;
     q.cof = ctx->d_qc_map + o_cof, q.cofstart = ctx->d_qc_map + o_cofstart;
     q.skipw = reinterpret_cast<const uint32_t*>(ctx->d_qc_map.ptr + o_skipw);
     q.cofimg = ctx->d_qc_img, q.cmask = ctx->d_q_cmask, q.Y = ctx->d_q_Y, q.yy = ctx->d_qc_yy, q.tilemax = ctx->d_qc_tilemax;
     q.rstride = (int)rt;
-    QtlParams g;                           // what qtl_gather_kernel reads
-    memset(&g, 0, sizeof(g));
-    g.n = a.n, g.T = a.T, g.pheno = ctx->d_q_pheno, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm, g.Y = ctx->d_q_Y, g.rstride = q.rstride;
+    QtlParams g = qtl_gather_params(ctx, a, rt);
 
     launch_qtlcof_mask(q, ctx->stream);
     launch_qtlcof_gather(q, ctx->stream);
@@ -2477,34 +2317,19 @@ int cnf2_qtl_scan_cof(cnf2_ctx* ctx, int n, const double* origin, int n_traits, 
         if (r0 + q.rn > (size_t)a.T) launch_qtlcof_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, a.n_used, q.nc, (size_t)C));
-        RC_TRY(fetch_out(ctx, a.rank, q.rank, (size_t)M));
-        RC_TRY(fetch_out(ctx, rank_cof_out, q.rank_cof, (size_t)M));
-        RC_TRY(fetch_out(ctx, a.lod, q.lod, (size_t)a.T * M));
-        RC_TRY(fetch_out(ctx, lod_base_out, q.lod_base, (size_t)a.T * M));
-        RC_TRY(fetch_out(ctx, a.coef, q.coef, (size_t)a.T * M * ds.ne));
-        RC_TRY(fetch_out(ctx, a.rss0, q.rss0, (size_t)a.T * C));
-        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, q.pmax, (size_t)a.P * a.T * C));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
-// The maximum-likelihood single-locus scan on device rows d_origin[n][M][4]: cnf2_qtlem.h, cnf2_qtlem_kernels.hip.  The
-// masks, the factor of S11, the column image and the null fit are the kernels of cnf2_qtl_kernels.hip.  Everything is checked
-// and every buffer is there before the first launch writes.
+// The maximum-likelihood single-locus scan on origin rows [n][M][4]: cnf2_qtlem.h, cnf2_qtlem_kernels.hip.  The masks, the
+// factor of S11, the column image and the null fit are the kernels of cnf2_qtl_kernels.hip.
 int cnf2_qtl_scan_em(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                      const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
                      double* coef_out, double* sigma2_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out,
                      double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
     QtlCentred           centred;
@@ -2515,87 +2340,49 @@ int cnf2_qtl_scan_em(cnf2_ctx* ctx, int n, const double* origin, int n_traits, c
     const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
     const int M = ctx->n_markers, C = ctx->n_chrom, nx = ds.nx;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
-    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
 
-    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
-    // the map as the kernels read it: chromstarts, marker -> chromosome, the marker tiles (none straddles a chromosome start)
-    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
-    map.resize((size_t)C + 1 + M);
-    std::vector<int32_t> tiles, tstart(1, 0);
-    for (int c = 0; c < C; c++) {
-        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
-        for (int m = f; m < e; m++) map[(size_t)C + 1 + m] = c;
-        for (int m = f; m < e; m += QTLEM_TILE) {
-            const int32_t t4[4] = {c, m, std::min(QTLEM_TILE, e - m), 0};
-            tiles.insert(tiles.end(), t4, t4 + 4);
-        }
-        tstart.push_back((int32_t)(tiles.size() / 4));
-    }
-    const size_t n_tiles = tiles.size() / 4, o_tiles = map.size();
-    map.insert(map.end(), tiles.begin(), tiles.end());
-    const size_t o_tstart = map.size();
-    map.insert(map.end(), tstart.begin(), tstart.end());
-    // the column tile: the image under 1 GB, the tile maxima under 256 MB, the caller's cap
-    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
-    rt = std::min(rt, (size_t)4096);
-    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (8 * std::max<size_t>(1, n_tiles))));
-    rt = std::min(rt, R);
-    if (ctx->qtlem_columns > 0) rt = std::min(rt, (size_t)ctx->qtlem_columns);
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLEM_TILE, true, true);
+    const size_t       n_tiles = map.n_tiles;
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_EM]);
 
-    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
     QtlemParams q;
     memset(&q, 0, sizeof(q));
-    QtlParams g;                           // what the kernels of cnf2_qtl_kernels.hip read and write
-    memset(&g, 0, sizeof(g));
-    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
-    RC_TRY(ctx->d_qe_map.ensure(ctx, map.size()));
-    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
-    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
-    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
-    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
-    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    QtlParams g = qtl_gather_params(ctx, a, rt);   // ... and the other kernels of cnf2_qtl_kernels.hip read and write
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_qe_nc, (size_t)C, &g.nc));
+        RC_TRY(each(a.rank, ctx->d_qe_rank, (size_t)M, &q.rank));
+        RC_TRY(each(a.lod, ctx->d_qe_lod, cells, &q.lod));
+        RC_TRY(each(a.coef, ctx->d_qe_coef, cells * ds.ne, &q.coef));
+        RC_TRY(each(sigma2_out, ctx->d_qe_sigma2, cells, &q.sigma2));
+        RC_TRY(each(iters_out, ctx->d_qe_iters, cells, &q.iters));
+        RC_TRY(each(status_out, ctx->d_qe_status, cells, &q.status));
+        RC_TRY(each(a.rss0, ctx->d_qe_rss0, (size_t)a.T * C, &q.rss0));
+        return each(a.pmax, ctx->d_qe_pmax, (size_t)a.P * a.T * C, &q.pmax);
+    };
+    RC_TRY(ctx->d_qe_map.ensure(ctx, map.image.size()));
     RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
     RC_TRY(ctx->d_qe_keep.ensure(ctx, (size_t)M));
-    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
     RC_TRY(ctx->d_q_null.ensure(ctx, (size_t)C * (nx + 1) * rt));
-    if (a.P > 0) RC_TRY(ctx->d_qe_tilemax.ensure(ctx, n_tiles * rt));
-    const size_t cells = (size_t)a.T * M;
-    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_qe_nc, (size_t)C, &g.nc));
-    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_qe_rank, (size_t)M, &q.rank));
-    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_qe_lod, cells, &q.lod));
-    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_qe_coef, cells * ds.ne, &q.coef));
-    RC_TRY(stage_out(ctx, dev, sigma2_out, ctx->d_qe_sigma2, cells, &q.sigma2));
-    RC_TRY(stage_out(ctx, dev, iters_out, ctx->d_qe_iters, cells, &q.iters));
-    RC_TRY(stage_out(ctx, dev, status_out, ctx->d_qe_status, cells, &q.status));
-    RC_TRY(stage_out(ctx, dev, a.rss0, ctx->d_qe_rss0, (size_t)a.T * C, &q.rss0));
     RC_TRY(ctx->d_qe_rss0_null.ensure(ctx, (size_t)a.T * C));
-    g.rss0 = ctx->d_qe_rss0_null;
-    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_qe_pmax, (size_t)a.P * a.T * C, &q.pmax));
-    if (staged) {
-        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
-        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
-    RC_TRY(qtl_upload(ctx, ctx->d_qe_map, map.data(), map.size()));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+    if (a.P > 0) RC_TRY(ctx->d_qe_tilemax.ensure(ctx, n_tiles * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qe_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
 
-    g.n = a.n, g.M = M, g.C = C, g.T = a.T, g.P = a.P, g.K = a.K, g.nx = nx;
-    g.origin = d_origin, g.pheno = ctx->d_q_pheno, g.cov = ctx->d_q_cov, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm;
-    g.cs = ctx->d_qe_map, g.mchrom = ctx->d_qe_map + (C + 1);
-    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol, g.Y = ctx->d_q_Y, g.nullq = ctx->d_q_null, g.rstride = (int)rt;
+    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = nx;
+    g.origin = org.dev, g.cov = ctx->d_q_cov;
+    g.cs = ctx->d_qe_map, g.mchrom = ctx->d_qe_map + map.o_mchrom;
+    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol, g.nullq = ctx->d_q_null, g.rss0 = ctx->d_qe_rss0_null;
     q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
     q.max_iter = max_iter, q.tol = tol;
-    q.origin = d_origin, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
-    q.tiles = ctx->d_qe_map + o_tiles, q.tile_start = ctx->d_qe_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
+    q.tiles = ctx->d_qe_map + map.o_tiles, q.tile_start = ctx->d_qe_map + map.o_tstart, q.n_tiles = (int)n_tiles;
     q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.chol = ctx->d_q_chol, q.keep = ctx->d_qe_keep;
     q.Y = ctx->d_q_Y, q.nullq = ctx->d_q_null, q.tilemax = ctx->d_qe_tilemax, q.rstride = (int)rt;
 
@@ -2610,37 +2397,21 @@ int cnf2_qtl_scan_em(cnf2_ctx* ctx, int n, const double* origin, int n_traits, c
         if (r0 + q.rn > (size_t)a.T) launch_qtlem_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, a.n_used, (const int32_t*)g.nc, (size_t)C));
-        RC_TRY(fetch_out(ctx, a.rank, (const int32_t*)q.rank, (size_t)M));
-        RC_TRY(fetch_out(ctx, a.lod, (const double*)q.lod, cells));
-        RC_TRY(fetch_out(ctx, a.coef, (const double*)q.coef, cells * ds.ne));
-        RC_TRY(fetch_out(ctx, sigma2_out, (const double*)q.sigma2, cells));
-        RC_TRY(fetch_out(ctx, iters_out, (const int32_t*)q.iters, cells));
-        RC_TRY(fetch_out(ctx, status_out, (const int32_t*)q.status, cells));
-        RC_TRY(fetch_out(ctx, a.rss0, (const double*)q.rss0, (size_t)a.T * C));
-        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, (const double*)q.pmax, (size_t)a.P * a.T * C));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
-// The binary-trait single-locus scan on device rows d_origin[n][M][4]: cnf2_qtlbin.h, cnf2_qtlbin_kernels.hip.  The masks, n_c
-// and the column image are the kernels of cnf2_qtl_kernels.hip.  The covariates are centred, each value minus the column's mean
+// The binary-trait single-locus scan on origin rows [n][M][4]: cnf2_qtlbin.h, cnf2_qtlbin_kernels.hip.  The masks, n_c and
+// the column image are the kernels of cnf2_qtl_kernels.hip.  The covariates are centred, each value minus the column's mean
 // rounded once (qtl_centre_columns_once: a shifted covariate gives the same bits, which a fit of a nearly collinear marker
-// needs for the same printed effects); the 0/1 trait is not.  Everything is checked and every buffer is there before the
-// first launch writes.
+// needs for the same printed effects); the 0/1 trait is not.
 int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                          const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
                          double* coef_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out,
                          int32_t* n_ones_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    const bool kept = !origin && (flags & CNF2_QTL_ORIGIN_DEVICE);       // the rows the last cnf2_sweep_qtl left in the context
-    if (!origin && !kept) return fail(ctx, CNF2_ERR_ARG, "origin is NULL");
-    if (kept && (ctx->qtl_rows_n == 0 || n != ctx->qtl_rows_n || ctx->qtl_rows_m != ctx->n_markers ||
-                 ctx->d_org.cap < (size_t)n * ctx->n_markers * 4))
-        return fail(ctx, CNF2_ERR_STATE, "the context holds the rows of %d individuals from cnf2_sweep_qtl, not of %d", ctx->qtl_rows_n, n);
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
     QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, ll0_out, perm_max_out, rank_out, n_used_out};
     std::vector<uint8_t> mask;
     QtlCentred           centred;
@@ -2662,86 +2433,49 @@ int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_trait
     const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
     const int M = ctx->n_markers, C = ctx->n_chrom;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const double* d_origin = kept ? ctx->d_org.ptr : origin;
-    const bool    staged   = !(flags & CNF2_QTL_ORIGIN_DEVICE);
-    if (!staged && ((uintptr_t)d_origin & 15)) return fail(ctx, CNF2_ERR_ARG, "device origin rows must be aligned to 16 bytes");
 
-    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const size_t R = (size_t)a.T * ((size_t)a.P + 1);
-    // the map as the kernels read it: chromstarts, marker -> chromosome, the marker tiles (none straddles a chromosome start)
-    std::vector<int32_t> map(ctx->chromstarts.begin(), ctx->chromstarts.end());
-    map.resize((size_t)C + 1 + M);
-    std::vector<int32_t> tiles, tstart(1, 0);
-    for (int c = 0; c < C; c++) {
-        const int f = ctx->chromstarts[c], e = ctx->chromstarts[c + 1];
-        for (int m = f; m < e; m++) map[(size_t)C + 1 + m] = c;
-        for (int m = f; m < e; m += QTLBIN_TILE) {
-            const int32_t t4[4] = {c, m, std::min(QTLBIN_TILE, e - m), 0};
-            tiles.insert(tiles.end(), t4, t4 + 4);
-        }
-        tstart.push_back((int32_t)(tiles.size() / 4));
-    }
-    const size_t n_tiles = tiles.size() / 4, o_tiles = map.size();
-    map.insert(map.end(), tiles.begin(), tiles.end());
-    const size_t o_tstart = map.size();
-    map.insert(map.end(), tstart.begin(), tstart.end());
-    // the column tile: the image under 1 GB, the tile maxima under 256 MB, the launch grid's second dimension, the caller's cap
-    size_t rt = std::max<size_t>(16, ((size_t)1 << 30) / (8 * (size_t)a.n));
-    rt = std::min(rt, (size_t)4096);
-    if (a.P > 0) rt = std::min(rt, std::max<size_t>(16, ((size_t)1 << 28) / (8 * std::max<size_t>(1, n_tiles))));
-    rt = std::min(rt, R);
-    if (ctx->qtlbin_columns > 0) rt = std::min(rt, (size_t)ctx->qtlbin_columns);
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLBIN_TILE, true, true);
+    const size_t       n_tiles = map.n_tiles;
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_BIN]);
 
-    // every allocation, then the uploads: nothing of the caller's is written before all of them have succeeded
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
     QtlbinParams q;
     memset(&q, 0, sizeof(q));
-    QtlParams g;                           // what the kernels of cnf2_qtl_kernels.hip read and write
-    memset(&g, 0, sizeof(g));
-    if (staged) RC_TRY(ctx->d_org.ensure(ctx, (size_t)n * M * 4));
-    RC_TRY(ctx->d_qb_map.ensure(ctx, map.size()));
-    RC_TRY(ctx->d_q_pheno.ensure(ctx, (size_t)a.n * a.T));
-    RC_TRY(ctx->d_q_cov.ensure(ctx, std::max<size_t>(1, (size_t)a.n * a.K)));
-    RC_TRY(ctx->d_q_use.ensure(ctx, (size_t)a.n));
-    RC_TRY(ctx->d_q_perm.ensure(ctx, std::max<size_t>(1, (size_t)a.P * a.n)));
-    RC_TRY(ctx->d_q_cmask.ensure(ctx, (size_t)C * a.n));
+    QtlParams g = qtl_gather_params(ctx, a, rt);   // ... and qtl_chrom_kernel reads and writes
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_qb_nc, (size_t)C, &g.nc));
+        RC_TRY(each(a.rank, ctx->d_qb_rank, (size_t)M, &q.rank));
+        RC_TRY(each(a.lod, ctx->d_qb_lod, cells, &q.lod));
+        RC_TRY(each(a.coef, ctx->d_qb_coef, cells * ds.ne, &q.coef));
+        RC_TRY(each(iters_out, ctx->d_qb_iters, cells, &q.iters));
+        RC_TRY(each(status_out, ctx->d_qb_status, cells, &q.status));
+        RC_TRY(each(ll0_out, ctx->d_qb_ll0, (size_t)a.T * C, &q.ll0));
+        RC_TRY(each(n_ones_out, ctx->d_qb_ones, (size_t)a.T * C, &q.n_ones));
+        return each(a.pmax, ctx->d_qb_pmax, (size_t)a.P * a.T * C, &q.pmax);
+    };
+    RC_TRY(ctx->d_qb_map.ensure(ctx, map.image.size()));
     RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
     RC_TRY(ctx->d_qb_keep.ensure(ctx, (size_t)M));
     RC_TRY(ctx->d_qb_scan.ensure(ctx, (size_t)C));
-    RC_TRY(ctx->d_q_Y.ensure(ctx, (size_t)a.n * rt));
     RC_TRY(ctx->d_qb_null.ensure(ctx, (size_t)C * QTLBIN_NULLQ * rt));
     if (a.P > 0) RC_TRY(ctx->d_qb_tilemax.ensure(ctx, n_tiles * rt));
-    const size_t cells = (size_t)a.T * M;
-    RC_TRY(stage_out(ctx, dev, a.n_used, ctx->d_qb_nc, (size_t)C, &g.nc));
-    RC_TRY(stage_out(ctx, dev, a.rank, ctx->d_qb_rank, (size_t)M, &q.rank));
-    RC_TRY(stage_out(ctx, dev, a.lod, ctx->d_qb_lod, cells, &q.lod));
-    RC_TRY(stage_out(ctx, dev, a.coef, ctx->d_qb_coef, cells * ds.ne, &q.coef));
-    RC_TRY(stage_out(ctx, dev, iters_out, ctx->d_qb_iters, cells, &q.iters));
-    RC_TRY(stage_out(ctx, dev, status_out, ctx->d_qb_status, cells, &q.status));
-    RC_TRY(stage_out(ctx, dev, ll0_out, ctx->d_qb_ll0, (size_t)a.T * C, &q.ll0));
-    RC_TRY(stage_out(ctx, dev, n_ones_out, ctx->d_qb_ones, (size_t)a.T * C, &q.n_ones));
-    RC_TRY(stage_out(ctx, dev, a.pmax, ctx->d_qb_pmax, (size_t)a.P * a.T * C, &q.pmax));
-    if (staged) {
-        ctx->qtl_rows_n = 0;               // (the buffer holds the caller's rows from here on)
-        // (complete before anything below can return: the caller's array is not read after the call, whatever its status)
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_org.ptr, origin, (size_t)n * M * 4 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        d_origin = ctx->d_org;
-    }
-    RC_TRY(qtl_upload(ctx, ctx->d_qb_map, map.data(), map.size()));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_pheno, a.pheno, (size_t)a.n * a.T));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_cov, a.cov, (size_t)a.n * a.K));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_use, mask.data(), (size_t)a.n));
-    RC_TRY(qtl_upload(ctx, ctx->d_q_perm, a.perm, (size_t)a.P * a.n));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qb_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
 
-    g.n = a.n, g.M = M, g.C = C, g.T = a.T, g.P = a.P, g.K = a.K, g.nx = ds.nx;
-    g.origin = d_origin, g.pheno = ctx->d_q_pheno, g.cov = ctx->d_q_cov, g.use = ctx->d_q_use, g.perm = ctx->d_q_perm;
-    g.cs = ctx->d_qb_map, g.mchrom = ctx->d_qb_map + (C + 1);
-    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol, g.Y = ctx->d_q_Y, g.rstride = (int)rt;
+    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = ds.nx;
+    g.origin = org.dev, g.cov = ctx->d_q_cov;
+    g.cs = ctx->d_qb_map, g.mchrom = ctx->d_qb_map + map.o_mchrom;
+    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol;
     q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
     q.max_iter = max_iter, q.tol = tol;
-    q.origin = d_origin, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
-    q.tiles = ctx->d_qb_map + o_tiles, q.tile_start = ctx->d_qb_map + o_tstart, q.n_tiles = (int)n_tiles;
+    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
+    q.tiles = ctx->d_qb_map + map.o_tiles, q.tile_start = ctx->d_qb_map + map.o_tstart, q.n_tiles = (int)n_tiles;
     q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = ctx->d_qb_keep, q.scan = ctx->d_qb_scan;
     q.Y = ctx->d_q_Y, q.nullq = ctx->d_qb_null, q.tilemax = ctx->d_qb_tilemax, q.rstride = (int)rt;
 
@@ -2757,19 +2491,7 @@ int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_trait
         if (r0 + q.rn > (size_t)a.T) launch_qtlbin_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
-    if (!dev) {
-        RC_TRY(fetch_out(ctx, a.n_used, (const int32_t*)g.nc, (size_t)C));
-        RC_TRY(fetch_out(ctx, a.rank, (const int32_t*)q.rank, (size_t)M));
-        RC_TRY(fetch_out(ctx, a.lod, (const double*)q.lod, cells));
-        RC_TRY(fetch_out(ctx, a.coef, (const double*)q.coef, cells * ds.ne));
-        RC_TRY(fetch_out(ctx, iters_out, (const int32_t*)q.iters, cells));
-        RC_TRY(fetch_out(ctx, status_out, (const int32_t*)q.status, cells));
-        RC_TRY(fetch_out(ctx, ll0_out, (const double*)q.ll0, (size_t)a.T * C));
-        RC_TRY(fetch_out(ctx, n_ones_out, (const int32_t*)q.n_ones, (size_t)a.T * C));
-        if (a.P > 0) RC_TRY(fetch_out(ctx, a.pmax, (const double*)q.pmax, (size_t)a.P * a.T * C));
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CNF2_OK;
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
 // one pass of sweep_impl's Viterbi mode

@@ -14,6 +14,7 @@
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
 #include "../cnf2_qtlboot.h"
+#include "../cnf2_qtlplan.h"
 #include "cnf2_remap.h"
 
 using namespace cnf2host;
@@ -536,6 +537,27 @@ int cnf2h_qtl_boot_marker(int n, const double* origin, int n_traits, const doubl
                                        rss0_out, n_bc_out)
                ? 0
                : -2;
+}
+
+// the scans' marker map and column tile: qtl_marker_map and qtl_column_tile (cnf2_qtlplan.h)
+int64_t cnf2h_qtl_marker_map(const int32_t* chromstarts, int n_chrom, int chrom_begin, int chrom_end, int tile, int with_mchrom,
+                             int whole_map_header, int32_t* image_out, int64_t cap, int64_t* offsets_out)
+{
+    if (!chromstarts || n_chrom < 1 || chrom_begin < 0 || chrom_end > n_chrom || chrom_begin > chrom_end || tile < 1 || !offsets_out)
+        return -2;
+    for (int c = 0; c < n_chrom; c++)
+        if (chromstarts[c] > chromstarts[c + 1]) return -2;
+    const cnf2::QtlMarkerMap m = cnf2::qtl_marker_map(chromstarts, n_chrom, chrom_begin, chrom_end, tile, with_mchrom != 0, whole_map_header != 0);
+    offsets_out[0] = (int64_t)m.o_mchrom, offsets_out[1] = (int64_t)m.o_tiles, offsets_out[2] = (int64_t)m.o_tstart;
+    offsets_out[3] = (int64_t)m.n_tiles;
+    if (image_out && cap >= (int64_t)m.image.size()) std::copy(m.image.begin(), m.image.end(), image_out);
+    return (int64_t)m.image.size();
+}
+
+int64_t cnf2h_qtl_column_tile(int64_t n, int64_t R, int64_t P, int64_t maxima_doubles_per_column, int cap)
+{
+    if (n < 0 || R < 0 || P < 0 || maxima_doubles_per_column < 0 || cap < 0) return -2;
+    return (int64_t)cnf2::qtl_column_tile((size_t)n, (size_t)R, (size_t)P, (size_t)maxima_doubles_per_column, cap);
 }
 
 }  // extern "C"

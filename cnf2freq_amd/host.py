@@ -15,7 +15,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
-           "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker"]
+           "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -71,6 +71,10 @@ def load():
         L.cnf2h_qtl_cols_marker.argtypes = [i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
         L.cnf2h_qtl_bootstrap_counts.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
         L.cnf2h_qtl_boot_marker.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.cnf2h_qtl_marker_map.argtypes = [vp, i32, i32, i32, i32, i32, i32, vp, C.c_int64, vp]
+        L.cnf2h_qtl_marker_map.restype = C.c_int64
+        L.cnf2h_qtl_column_tile.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32]
+        L.cnf2h_qtl_column_tile.restype = C.c_int64
         _lib = L
     return _lib
 
@@ -239,6 +243,30 @@ def qtl_boot_marker(origin, y, count, cov=None, c=None, additive=False):
     if rc != 0:
         raise ValueError("cnf2h_qtl_boot_marker refused its arguments (%d)" % rc)
     return dict(lod=lod, coef=coef, rank=int(rank[0]), rss0=rss0, n_bc=int(n_bc[0]))
+
+
+def qtl_marker_map(chromstarts, tile, chrom_begin=0, chrom_end=None, with_mchrom=False, whole_map_header=True):
+    """cnf2h_qtl_marker_map: the marker map a QTL scan uploads (cnf2_qtlplan.h) as dict(image, o_mchrom, o_tiles, o_tstart,
+    n_tiles) -- the int32 words and the offsets of their blocks.  CPU only."""
+    L = load()
+    cs = np.ascontiguousarray(chromstarts, np.int32)
+    nc = len(cs) - 1
+    args = (_p(cs), nc, chrom_begin, nc if chrom_end is None else chrom_end, tile, int(with_mchrom), int(whole_map_header))
+    off = np.zeros(4, np.int64)
+    words = L.cnf2h_qtl_marker_map(*args, None, 0, _p(off))
+    if words < 0:
+        raise ValueError("cnf2h_qtl_marker_map refused its arguments (%d)" % words)
+    image = np.zeros(words, np.int32)
+    L.cnf2h_qtl_marker_map(*args, _p(image), words, _p(off))
+    return dict(image=image, o_mchrom=int(off[0]), o_tiles=int(off[1]), o_tstart=int(off[2]), n_tiles=int(off[3]))
+
+
+def qtl_column_tile(n, R, P, maxima_doubles_per_column=0, cap=0):
+    """cnf2h_qtl_column_tile: the columns a QTL scan takes per pass (cnf2_qtlplan.h).  CPU only."""
+    rt = load().cnf2h_qtl_column_tile(n, R, P, maxima_doubles_per_column, cap)
+    if rt < 0:
+        raise ValueError("cnf2h_qtl_column_tile refused its arguments (%d)" % rt)
+    return rt
 
 
 def qtlx_columns(n_cov, n_int=0, additive=False, imprint=False):

@@ -219,6 +219,23 @@ int cnf2h_qtl_boot_marker(int n, const double *origin, int n_traits, const doubl
                           const uint8_t *c, const int32_t *count, int additive, double *lod_out, double *coef_out,
                           int32_t *rank_out, double *rss0_out, int32_t *n_bc_out);
 
+/* What the QTL scans of cnf2hip.h plan on the host before they allocate (cnf2freq_amd/csrc/cnf2_qtlplan.h), for tests:
+ *  cnf2h_qtl_marker_map   the marker map a scan uploads, in int32 words: the header -- chromstarts[n_chrom + 1] of the whole
+ *                         map (whole_map_header) or the first marker of every chromosome of chrom_begin .. chrom_end-1;
+ *                         with_mchrom (whole_map_header only) the chromosome of every marker; a record {c, m, len, 0} per
+ *                         tile of at most `tile` markers m .. m+len-1 of the range's chromosomes in order, none across a
+ *                         chromosome start, c counted from 0 (whole_map_header) or from chrom_begin; per chromosome of
+ *                         the range and one past the last the index of its first tile.  offsets_out[4] = the word offsets
+ *                         of the marker chromosomes, the tiles and the tile starts, and the number of tiles.  Returns the
+ *                         words of the image and writes them to image_out where it is not NULL and cap holds them.
+ *  cnf2h_qtl_column_tile  the columns a scan of n individuals takes per pass out of R, with P permutations: the column image
+ *                         under 1 GB, 16 .. 4096; with P > 0 the maxima, maxima_doubles_per_column doubles per column (0 =
+ *                         the scan has no such bound), under 256 MB, at least 16; at most R; at most cap (0 = none).
+ * -2: a bad argument. */
+int64_t cnf2h_qtl_marker_map(const int32_t *chromstarts, int n_chrom, int chrom_begin, int chrom_end, int tile, int with_mchrom,
+                             int whole_map_header, int32_t *image_out, int64_t cap, int64_t *offsets_out);
+int64_t cnf2h_qtl_column_tile(int64_t n, int64_t R, int64_t P, int64_t maxima_doubles_per_column, int cap);
+
 #ifdef __cplusplus
 }
 #endif
