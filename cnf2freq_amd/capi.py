@@ -54,7 +54,7 @@ SYMBOLS = [
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
     "cnf2_qtl_scan_cof", "cnf2_set_qtlcof_columns", "cnf2_qtl_kept_rows",
-    "cnf2_kinship_sums", "cnf2_qtl_scan_cols", "cnf2_qtl_scan_boot",
+    "cnf2_kinship_sums", "cnf2_qtl_scan_cols", "cnf2_qtl_scan_boot", "cnf2_qtl_scan_mv", "cnf2_set_qtlmv_groups",
 ]
 
 
@@ -139,6 +139,8 @@ def load():
         L.cnf2_kinship_sums.argtypes = [vp, i32, vp, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_cols.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_boot.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_qtl_scan_mv.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_set_qtlmv_groups.argtypes = [vp, i32]
         L.cnf2_qtl_scan_em.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, C.c_double,
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlem_columns.argtypes = [vp, i32]
@@ -807,6 +809,46 @@ class Context:
         are host arrays."""
         return self._qtl_boot_call(n, C.c_void_p(d_origin) if d_origin else None, pheno, count, chrom_begin, chrom_end, cov, use,
                                    profile, QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0), out)
+
+    # -- multi-trait scan --------------------------------------------------------------
+    QTLMV_KEYS = ("lod", "rank", "trait_rank", "n_used", "perm_max")
+
+    def set_qtlmv_groups(self, cap):
+        """Cap on the groups (the observed data, every permutation) per tile of qtl_scan_mv (0 = what memory allows); results
+        do not depend on it."""
+        self._chk(self.L.cnf2_set_qtlmv_groups(self.h, cap), "cnf2_set_qtlmv_groups")
+
+    def _qtlmv_call(self, n, origin_ptr, pheno, cov, use, perm, flags, out=None):
+        """cnf2_qtl_scan_mv on the rows behind origin_ptr; out = None: new host arrays, else the outputs (arrays, or with
+        OUT_DEVICE in flags ints, the device pointers)"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        M, Cn = self.n_markers, self.n_chrom
+        o = dict(lod=np.zeros(M), rank=np.zeros(M, np.int32), trait_rank=np.zeros(Cn, np.int32), n_used=np.zeros(Cn, np.int32),
+                 perm_max=np.zeros((P, Cn)) if P else None) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        ptr = (lambda a: C.c_void_p(a) if a else None) if flags & OUT_DEVICE else opt
+        self._chk(self.L.cnf2_qtl_scan_mv(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm),
+                                          *[ptr(o[k]) for k in self.QTLMV_KEYS], flags), "cnf2_qtl_scan_mv")
+        return o
+
+    def qtl_scan_mv(self, origin, pheno, cov=None, use=None, perm=None, additive=False, out=None):
+        """cnf2_qtl_scan_mv on host rows origin[n][M][4]: the joint LOD (Wilks' lambda) of the T <= 16 traits pheno[n][T] on
+        the rows at every marker, with covariates cov[n][K], the individuals of use[n] and the permutations perm[P][n], each of
+        which moves all traits of an individual together.  A dict: lod[M], rank[M], trait_rank[C] (the traits kept),
+        n_used[C], perm_max[P][C] (None without permutations).  The model: include/cnf2hip.h; qtl.scan_mv reads it."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return self._qtlmv_call(origin.shape[0], _p(origin), pheno, cov, use, perm, QTL_ADDITIVE if additive else 0, out)
+
+    def qtl_scan_mv_device(self, n, d_origin, pheno, cov=None, use=None, perm=None, additive=False, d_out=None):
+        """The same on device rows (d_origin: an int, the pointer of n x M x 4 doubles aligned to 16 bytes), read in place;
+        d_origin None: the rows this context's last sweep_qtl left in it, which stay valid.  Phenotypes are host arrays.
+        d_out: a dict of device pointers (ints) under the keys of QTLMV_KEYS, perm_max None without permutations -- the
+        outputs are written there and the call returns d_out; else host arrays as qtl_scan_mv."""
+        flags = QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (OUT_DEVICE if d_out is not None else 0)
+        return self._qtlmv_call(n, C.c_void_p(d_origin) if d_origin else None, pheno, cov, use, perm, flags, d_out)
 
     # -- two-QTL pair scan ---------------------------------------------------------
     QTL2_KEYS = ("lod_add", "lod_full", "rank_add", "rank_full", "rss0", "n_used", "perm_max")

@@ -30,6 +30,7 @@
 #include "cnf2_kinship.h"
 #include "cnf2_qtlcols.h"
 #include "cnf2_qtlboot.h"
+#include "cnf2_qtlmv.h"
 
 using namespace cnf2;
 
@@ -78,8 +79,9 @@ struct DevBuf {
     int ensure(cnf2_ctx* ctx, size_t count) { return (cap >= count && ptr) ? CNF2_OK : alloc(ctx, count); }
 };
 
-// the scans whose column tile the caller can cap (cnf2_set_*_columns); the column scan shares the single scan's
-enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_COUNT };
+// the scans whose column tile the caller can cap (cnf2_set_*_columns); the column scan shares the single scan's, and the
+// multi-trait scan's cap counts groups (cnf2_set_qtlmv_groups)
+enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_COUNT };
 
 struct cnf2_ctx {
     int         device = -1;
@@ -222,6 +224,11 @@ struct cnf2_ctx {
     DevBuf<double>  d_qo_W, d_qo_rec, d_qo_tilemax, d_qo_max, d_qo_lod;
     DevBuf<int32_t> d_qo_count, d_qo_map, d_qo_tilearg, d_qo_arg, d_qo_nb;   // d_qo_map: first markers, tiles, tile starts
     DevBuf<uint8_t> d_qo_cmask;
+
+    // multi-trait scan (cnf2_qtl_scan_mv): the (chromosome, group) records of a group tile, the tile maxima, staged outputs;
+    // the staged inputs, the masks, the factors, the marker records and the image are the single scan's buffers
+    DevBuf<double>  d_qm_rec, d_qm_tilemax, d_qm_lod, d_qm_pmax;
+    DevBuf<int32_t> d_qm_map, d_qm_nc, d_qm_rank, d_qm_trank;   // d_qm_map: as d_q_map
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -466,6 +473,7 @@ int cnf2_set_qtlx_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_
 int cnf2_set_qtlcof_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_COF, cap); }
 int cnf2_set_qtlem_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_EM, cap); }
 int cnf2_set_qtlbin_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_BIN, cap); }
+int cnf2_set_qtlmv_groups(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_MV, cap); }
 
 int cnf2_sync(cnf2_ctx* ctx)
 {
@@ -2049,6 +2057,83 @@ int cnf2_qtl_scan_boot(cnf2_ctx* ctx, int n, const double* origin, int n_traits,
             launch_qtlboot_scan(q, ctx->stream);
         }
         launch_qtlboot_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Multi-trait scan (cnf2_qtlmv.h, cnf2_qtlmv_kernels.hip), in the scans' order of steps
+// ------------------------------------------------------------------------------------------------
+int cnf2_qtl_scan_mv(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
+                     const double* cov, int n_perm, const int32_t* perm, double* lod_out, int32_t* rank_out, int32_t* trait_rank_out,
+                     int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
+    if (n_traits > QTLMV_MAXT) return fail(ctx, CNF2_ERR_ARG, "n_traits must be 1 .. %d", QTLMV_MAXT);
+    if (!trait_rank_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    // (the scan has no effects and no RSS0 to report: the common check sees lod_out in their place)
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, lod_out, lod_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int          M = ctx->n_markers, C = ctx->n_chrom, T = a.T, T4 = qtlmv_width(T);
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, 16, true, true);
+    const size_t       G = (size_t)a.P + 1, n_tiles = map.n_tiles;
+    const size_t       gt = qtl_group_tile(a.n, T, G, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_MV]);
+    const size_t       per_wave = 64 / T4, ystride = (gt + per_wave - 1) / per_wave * 64, gstride = ystride / T4;
+
+    QtlMvParams q;
+    memset(&q, 0, sizeof(q));
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(n_used_out, ctx->d_qm_nc, (size_t)C, &q.nc));
+        RC_TRY(each(rank_out, ctx->d_qm_rank, (size_t)M, &q.rank));
+        RC_TRY(each(trait_rank_out, ctx->d_qm_trank, (size_t)C, &q.trait_rank));
+        RC_TRY(each(lod_out, ctx->d_qm_lod, (size_t)M, &q.lod));
+        return each(perm_max_out, ctx->d_qm_pmax, (size_t)a.P * C, &q.pmax);
+    };
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, ystride, 0));
+    RC_TRY(ctx->d_qm_map.ensure(ctx, map.image.size()));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_q_mk.ensure(ctx, (size_t)M * QTL_MK));
+    RC_TRY(ctx->d_q_rank.ensure(ctx, (size_t)M));
+    RC_TRY(ctx->d_qm_rec.ensure(ctx, (size_t)C * gstride * qtlmv_rec_doubles(T)));
+    if (a.P > 0) RC_TRY(ctx->d_qm_tilemax.ensure(ctx, n_tiles * gstride));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qm_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    // the masks, n_c, the factors of S11 and the marker records: the single scan's kernels (their rank is the design's; the
+    // scan's own also says where a chromosome is not scanned)
+    QtlParams d;
+    memset(&d, 0, sizeof(d));
+    d.n = n, d.M = M, d.C = C, d.T = T, d.P = a.P, d.K = a.K, d.nx = a.K + 1;
+    d.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
+    d.origin = org.dev, d.cov = ctx->d_q_cov, d.use = ctx->d_q_use;
+    d.cs = ctx->d_qm_map, d.mchrom = ctx->d_qm_map + map.o_mchrom;
+    d.cmask = ctx->d_q_cmask, d.nc = q.nc, d.chol = ctx->d_q_chol, d.mk = ctx->d_q_mk, d.rank = ctx->d_q_rank;
+    launch_qtl_chrom(d, ctx->stream);
+    launch_qtl_design(d, ctx->stream);
+
+    q.n = n, q.M = M, q.C = C, q.T = T, q.T4 = T4, q.P = a.P, q.K = a.K, q.nx = a.K + 1;
+    q.ystride = (int)ystride, q.gstride = (int)gstride;
+    q.origin = org.dev, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.perm = ctx->d_q_perm;
+    q.cmask = ctx->d_q_cmask, q.chol = ctx->d_q_chol, q.mk = ctx->d_q_mk;
+    q.tiles = ctx->d_qm_map + map.o_tiles, q.tile_start = ctx->d_qm_map + map.o_tstart, q.n_tiles = (int)n_tiles;
+    q.Y = ctx->d_q_Y, q.rec = ctx->d_qm_rec, q.tilemax = ctx->d_qm_tilemax;
+    for (size_t g0 = 0; g0 < G; g0 += gt) {
+        q.g0 = (int)g0;
+        q.gn = (int)std::min(gt, G - g0);
+        launch_qtlmv_gather(q, ctx->stream);
+        launch_qtlmv_null(q, ctx->stream);
+        launch_qtlmv_scan(q, ctx->stream);
+        if (g0 + q.gn > 1) launch_qtlmv_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
     return qtl_fetch_outputs(ctx, dev, outputs);

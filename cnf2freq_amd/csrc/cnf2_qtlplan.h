@@ -68,6 +68,20 @@ inline size_t qtl_column_tile(size_t n, size_t R, size_t P, size_t maxima_double
     return rt;
 }
 
+// The groups the multi-trait scan takes per pass out of G (the observed data and P permutations, T traits each): the rule
+// above in whole groups.  A group is T columns padded to 4, 8 or 16; as many groups as keep the padded image under 1 GB (16
+// to 4096 columns of it), at least one; with permutations as many as keep the maxima, n_tiles doubles per group, under
+// 256 MB, at least one; at most G; at most the caller's cap (cnf2_set_qtlmv_groups, 0 = none).
+inline size_t qtl_group_tile(size_t n, size_t T, size_t G, size_t P, size_t n_tiles, int cap)
+{
+    const size_t w = T <= 4 ? 4 : (T <= 8 ? 8 : 16);
+    size_t       gt = std::max<size_t>(1, qtl_column_tile(n, std::max<size_t>(1, G) * w, 0, 0, 0) / w);
+    if (P > 0 && n_tiles > 0) gt = std::min(gt, std::max<size_t>(1, ((size_t)1 << 28) / (8 * n_tiles)));
+    gt = std::min(gt, std::max<size_t>(1, G));
+    if (cap > 0) gt = std::min(gt, (size_t)cap);
+    return gt;
+}
+
 // The replicates the bootstrap scan takes per pass: a multiple of 16 that keeps the weight image W[n][tile] under 1 GB, at
 // least 16 and at most 4096; at most the B replicates rounded up to 16.
 inline size_t qtl_replicate_tile(size_t n, size_t B)

@@ -14,6 +14,7 @@
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
 #include "../cnf2_qtlboot.h"
+#include "../cnf2_qtlmv.h"
 #include "../cnf2_qtlplan.h"
 #include "cnf2_remap.h"
 
@@ -558,6 +559,23 @@ int64_t cnf2h_qtl_column_tile(int64_t n, int64_t R, int64_t P, int64_t maxima_do
 {
     if (n < 0 || R < 0 || P < 0 || maxima_doubles_per_column < 0 || cap < 0) return -2;
     return (int64_t)cnf2::qtl_column_tile((size_t)n, (size_t)R, (size_t)P, (size_t)maxima_doubles_per_column, cap);
+}
+
+// one (marker, group) cell of cnf2_qtl_scan_mv: qtlmv_marker_serial (cnf2_qtlmv.h)
+int cnf2h_qtlmv_marker(int n, const double* origin, int n_traits, const double* y, int n_cov, const double* cov, const uint8_t* c,
+                       int additive, double* lod_out, int32_t* rank_out, int32_t* trait_rank_out, int32_t* n_used_out)
+{
+    if (n < 1 || !origin || !y || (n_cov > 0 && !cov) || !c || !lod_out || !rank_out || !trait_rank_out || !n_used_out) return -2;
+    return cnf2::qtlmv_marker_serial(n, origin, n_traits, y, n_cov, cov, c, additive != 0, lod_out, rank_out, trait_rank_out, n_used_out)
+               ? 0
+               : -2;
+}
+
+// the multi-trait scan's group tile: qtl_group_tile (cnf2_qtlplan.h)
+int64_t cnf2h_qtl_group_tile(int64_t n, int64_t T, int64_t G, int64_t P, int64_t n_tiles, int cap)
+{
+    if (n < 0 || T < 1 || T > cnf2::QTLMV_MAXT || G < 1 || P < 0 || n_tiles < 0 || cap < 0) return -2;
+    return (int64_t)cnf2::qtl_group_tile((size_t)n, (size_t)T, (size_t)G, (size_t)P, (size_t)n_tiles, cap);
 }
 
 }  // extern "C"

@@ -10,6 +10,7 @@
 //            [--qtlbin F --phenofile P [--qtl-binary-iterations N] [--qtl-binary-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlcof F --phenofile P --qtl-cofactors i,j,k [--qtl-window X] [the --qtl-* options]]
 //            [--qtlboot F --phenofile P --qtl-boot-chrom C [--qtl-boot-replicates B] [--qtl-covariates, --qtl-seed, --qtl-additive]]
+//            [--qtlmv F --phenofile P [--qtl-traits name,name,..] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -97,6 +98,10 @@
 // --qtl-additive; not flags of the reference): the bootstrap of the scan on chromosome C (from 1, as the files print it) with
 // B replicates (default 1000; cnf2_qtl_scan_boot) for the confidence interval of a QTL's position, after the other scans
 // where they are given, on the same sweep's rows.  F is described at qtlboot_scan below.
+// --qtlmv F [--qtl-traits name,name,..] (with --phenofile and --qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive;
+// not flags of the reference): the multi-trait scan (cnf2_qtl_scan_mv) -- the joint LOD of the named traits (default: every
+// trait of the table; 16 at most) at every marker, on the individuals that have all of them -- after the other scans where
+// they are given, on the same sweep's rows.  F is described at qtlmv_scan below.
 // --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
@@ -121,6 +126,7 @@
 #include "../cnf2_qtlx.h"
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
+#include "../cnf2_qtlmv.h"
 #include "cnf2_readers.h"
 #include "cnf2_rccl_transport.h"
 #include "cnf2_remap.h"
@@ -192,6 +198,10 @@ struct Options {
     int         qtl_boot_chrom = 0;      // --qtl-boot-chrom C: the chromosome, from 1
     int         qtl_boot_replicates = 1000;   // --qtl-boot-replicates B
     bool        qtlboot_extra_set = false; // one of the two above was given
+    std::string qtlmv;                   // --qtlmv F: multi-trait scan (with --phenofile and the shared --qtl-* options)
+    std::string qtl_traits;              // --qtl-traits name,name,..: the traits scanned jointly (default: all)
+    bool        qtl_traits_set = false;
+    std::vector<int> qtlmv_trait_cols;   // columns of pheno, in the order they are scanned
     std::vector<int> qtlx_cov_cols;      // columns of pheno: the interactive covariates first, then the others
     int         qtlx_n_int = 0;
     PhenoTable  pheno;                   // P as read (main, before any rank starts)
@@ -306,6 +316,11 @@ static bool parse(int argc, char** argv, Options& o)
             }
         }
         else if (a == "--qtlboot") o.qtlboot = val();
+        else if (a == "--qtlmv") o.qtlmv = val();
+        else if (a == "--qtl-traits") {
+            o.qtl_traits     = val();
+            o.qtl_traits_set = true;
+        }
         else if (a == "--qtl-boot-chrom") {
             o.qtl_boot_chrom    = atoi(val().c_str());
             o.qtlboot_extra_set = true;
@@ -373,6 +388,7 @@ static void qtlem_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows
 static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -474,6 +490,9 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtlboot.empty())
         qtlboot_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
                                       !opt.qtlcof.empty());
+    if (world == 1 && !opt.qtlmv.empty())
+        qtlmv_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
+                                    !opt.qtlcof.empty() || !opt.qtlboot.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1419,6 +1438,98 @@ static bool prepare_qtl(Options& opt, const Pedigree& P)
     return true;
 }
 
+// --qtl-traits against the traits of the table, and their number, before anything runs: false with a message
+static bool prepare_qtlmv(Options& opt)
+{
+    if (!opt.qtl_traits_set) opt.qtlmv_trait_cols = opt.qtl_trait_cols;
+    std::istringstream ss(opt.qtl_traits);
+    for (std::string tok; std::getline(ss, tok, ',');) {
+        if (tok.empty()) continue;
+        const auto it = std::find(opt.pheno.columns.begin(), opt.pheno.columns.end(), tok);
+        const int  k  = it == opt.pheno.columns.end() ? -1 : (int)(it - opt.pheno.columns.begin());
+        if (k < 0 || std::find(opt.qtl_trait_cols.begin(), opt.qtl_trait_cols.end(), k) == opt.qtl_trait_cols.end()) {
+            fprintf(stderr, "--qtl-traits: the phenotype file has no trait %s\n", tok.c_str());
+            return false;
+        }
+        if (std::find(opt.qtlmv_trait_cols.begin(), opt.qtlmv_trait_cols.end(), k) == opt.qtlmv_trait_cols.end()) opt.qtlmv_trait_cols.push_back(k);
+    }
+    if (opt.qtlmv_trait_cols.empty() || (int)opt.qtlmv_trait_cols.size() > cnf2::QTLMV_MAXT) {
+        fprintf(stderr, "--qtlmv takes 1 .. %d traits, not %zu\n", cnf2::QTLMV_MAXT, opt.qtlmv_trait_cols.size());
+        return false;
+    }
+    return true;
+}
+
+// --qtlmv after the last round (single GPU), and after the other scans where they are given: the multi-trait scan
+// (cnf2_qtl_scan_mv) of the traits of --qtl-traits on the rows a cnf2_sweep_qtl left in the context -- theirs, or one of this
+// function's own.  Complete cases only: an individual is used when the table has it with every covariate and every one of
+// the traits.  The file has the form of --qtl's: per marker "marker<TAB>chrom<TAB>pos<TAB>lod<TAB>rank" -- the map index from 0,
+// the chromosome from 1, the joint LOD and the marker's rank -- and with --qtl-permutations K > 0, after a blank line,
+// "joint<TAB>t5<TAB>t1", the 5 % and 1 % genome-wide thresholds of the joint LOD (the permutations move all traits of an
+// individual together; with covariates the residuals of the null model are permuted, as for --qtl).
+static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtlmv_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, 0.0), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> u(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        u[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (!std::isfinite(row[opt.qtl_cov_cols[k]])) u[j] = 0;
+        }
+        for (int t = 0; t < T; t++)
+            if (!std::isfinite(row[opt.qtlmv_trait_cols[t]])) u[j] = 0;
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = u[j] ? row[opt.qtlmv_trait_cols[t]] : 0.0;
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    int rc;
+    if (!rows_kept) {          // the sweep, with the rows left in the context; its single-locus scan is not reported
+        std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), y1(N), l1(M), c1((size_t)M * 2), r1(C);
+        std::vector<int32_t> k1(M), n1(C);
+        for (int j = 0; j < N; j++) y1[j] = y[(size_t)j * T];
+        rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), 1, y1.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr, l1.data(),
+                            c1.data(), k1.data(), r1.data(), n1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlmv: ") + cnf2_last_error(ctx));
+    }
+    std::vector<double>  lod(M, 0.0), thr(2, 0.0);
+    std::vector<int32_t> rank(M, 0), trank(C, 0), nused(C, 0);
+    rc = cnf2_qtl_scan_mv(ctx, N, nullptr, T, y.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr, lod.data(), rank.data(),
+                          trank.data(), nused.data(), nullptr, flags);
+    if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlmv: ") + cnf2_last_error(ctx));
+    if (NP > 0) {
+        std::vector<int32_t> perm((size_t)NP * N), rk(M), tr(C), nu(C);
+        std::vector<double>  res(y), l(M), pm((size_t)NP * C);
+        qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+        // (as for --qtl: with too few individuals nothing is scanned, whatever is permuted; with enough of them a null design
+        // without full rank is an error, not thresholds of 0)
+        const int n_u = (int)std::count(u.begin(), u.end(), (uint8_t)1);
+        if (K > 0 && n_u >= K + 4 && !qtl_null_residuals(N, T, y.data(), K, cov.data(), u.data(), res.data()))
+            throw EngineError(CNF2_ERR_ARG, "--qtl-permutations: the null design (intercept and covariates) of the individuals used for --qtlmv has no full rank");
+        rc = cnf2_qtl_scan_mv(ctx, N, nullptr, T, res.data(), u.data(), K, K ? cov.data() : nullptr, NP, perm.data(), l.data(), rk.data(),
+                              tr.data(), nu.data(), pm.data(), flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlmv permutations: ") + cnf2_last_error(ctx));
+        std::vector<double> mx(NP, 0.0);
+        for (int p = 0; p < NP; p++)
+            for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[(size_t)p * C + c]);
+        thr[0] = qtl_threshold(mx, 0.05);
+        thr[1] = qtl_threshold(mx, 0.01);
+    }
+    FILE* out = fopen(opt.qtlmv.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlmv);
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++)
+            fprintf(out, "%d\t%d\t%.5lf\t%.5lf\t%d\n", m, c + 1, P.pos[m], lod[m], (int)rank[m]);
+    if (NP > 0) fprintf(out, "\njoint\t%.5lf\t%.5lf\n", thr[0], thr[1]);
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlmv);
+}
+
 // --qtl-interactive against --qtl-covariates, and the design's width, before anything runs: false with a message
 static bool prepare_qtlx(Options& opt)
 {
@@ -1881,6 +1992,18 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtlboot FILE needs --qtl-boot-chrom C with C = 1 .. %d, the chromosomes of the map\n", (int)P.chromstarts.size() - 1);
         return 2;
     }
+    if (opt.gpus > 1 && !opt.qtlmv.empty()) {
+        fprintf(stderr, "--qtlmv needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlmv.empty() && opt.qtl_traits_set) {
+        fprintf(stderr, "--qtl-traits needs --qtlmv FILE\n");
+        return 2;
+    }
+    if (!opt.qtlmv.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlmv FILE needs --phenofile FILE\n");
+        return 2;
+    }
     if (opt.qtl_boot_replicates < 1 || opt.qtl_boot_replicates > 1000000) {
         fprintf(stderr, "--qtl-boot-replicates must be 1 .. 1000000\n");
         return 2;
@@ -1890,7 +2013,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
-        (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        opt.qtlmv.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -1922,9 +2045,11 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-permutations must not be negative\n");
         return 2;
     }
-    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty()) &&
+    if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty() ||
+         !opt.qtlmv.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
+    if (!opt.qtlmv.empty() && !prepare_qtlmv(opt)) return 2;
     if (!opt.qtlcof.empty() && !prepare_qtlcof(opt, P)) return 2;
     if (!opt.qtlbin.empty() && !prepare_qtlbin(opt)) return 2;
     if (!opt.qtlx.empty() && !prepare_qtlx(opt)) return 2;

@@ -15,7 +15,8 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
-           "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile"]
+           "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
+           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -75,6 +76,9 @@ def load():
         L.cnf2h_qtl_marker_map.restype = C.c_int64
         L.cnf2h_qtl_column_tile.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32]
         L.cnf2h_qtl_column_tile.restype = C.c_int64
+        L.cnf2h_qtlmv_marker.argtypes = [i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+        L.cnf2h_qtl_group_tile.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32]
+        L.cnf2h_qtl_group_tile.restype = C.c_int64
         _lib = L
     return _lib
 
@@ -267,6 +271,35 @@ def qtl_column_tile(n, R, P, maxima_doubles_per_column=0, cap=0):
     if rt < 0:
         raise ValueError("cnf2h_qtl_column_tile refused its arguments (%d)" % rt)
     return rt
+
+
+def qtlmv_marker(origin, y, cov=None, c=None, additive=False):
+    """cnf2h_qtlmv_marker: one (marker, group) cell of the multi-trait scan (cnf2_qtl_scan_mv) on the marker's rows
+    origin[n][4], the columns y[n][T] and cov[n][K] as they enter the sums and the chromosome's mask c[n] (None: all).  A
+    dict: lod, rank, trait_rank, n_used.  CPU only."""
+    L = load()
+    o = np.ascontiguousarray(origin, np.float64)
+    n = o.shape[0]
+    v = np.ascontiguousarray(y, np.float64).reshape(n, -1)
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    if o.shape != (n, 4) or m.shape != (n,):
+        raise ValueError("origin must be [n][4] and c [n]")
+    lod, rank, trank, n_c = np.zeros(1), np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_qtlmv_marker(n, _p(o), v.shape[1], _p(v), K, None if K == 0 else _p(z), _p(m), int(additive), _p(lod), _p(rank),
+                              _p(trank), _p(n_c))
+    if rc != 0:
+        raise ValueError("cnf2h_qtlmv_marker refused its arguments (%d)" % rc)
+    return dict(lod=float(lod[0]), rank=int(rank[0]), trait_rank=int(trank[0]), n_used=int(n_c[0]))
+
+
+def qtl_group_tile(n, T, G, P, n_tiles, cap=0):
+    """cnf2h_qtl_group_tile: the groups the multi-trait scan takes per pass (cnf2_qtlplan.h).  CPU only."""
+    gt = load().cnf2h_qtl_group_tile(n, T, G, P, n_tiles, cap)
+    if gt < 0:
+        raise ValueError("cnf2h_qtl_group_tile refused its arguments (%d)" % gt)
+    return gt
 
 
 def qtlx_columns(n_cov, n_int=0, additive=False, imprint=False):

@@ -30,7 +30,10 @@ rotated by the kinship's eigenvectors; thresholds and peaks read it as they read
 The bootstrap scan (Context.qtl_scan_boot, cnf2_qtl_scan_boot) says where a QTL sits: bootstrap_counts draws the individuals
 with replacement, scan_boot scans a chromosome again for every replicate in one call, and boot_interval turns the
 replicates' best markers into a confidence interval of the position.  bayes_interval is the credible interval read off one
-profile (the 10^LOD posterior); peaks keeps its LOD-drop interval."""
+profile (the 10^LOD posterior); peaks keeps its LOD-drop interval.
+
+The multi-trait scan (Context.qtl_scan_mv, cnf2_qtl_scan_mv) asks whether a locus moves several correlated traits jointly
+(Wilks' lambda of multivariate Haley-Knott regression): scan_mv; thresholds and peaks read its one joint profile."""
 import numpy as np
 
 from . import synth
@@ -215,6 +218,32 @@ def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False,
             res = null_residuals(yk, cov, u)
             out["perm_max"][:, cols] = ctx.qtl_scan_device(n, d_o.data_ptr(), res, cov=cov, use=u, perm=perm,
                                                            additive=additive)["perm_max"]
+    return out
+
+
+def scan_mv(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False, rows=None):
+    """The multi-trait scan of a whole cross on the context's uploaded pedigree (Context.qtl_scan_mv_device,
+    cnf2_qtl_scan_mv): is there a locus that moves the T <= 16 traits of pheno[n][T] jointly?  Complete cases only: an
+    individual with any trait that is not finite leaves `use`.  One origin sweep with the rows left on the device (or `rows`,
+    the tensor of origin_rows), the observed scan, and with permutations > 0 one more, on the permuted residuals of the null
+    model where there are covariates (a permutation moves all traits of an individual together).  A dict: lod[M] the joint
+    LOD, rank[M], trait_rank[C] the traits kept, n_used[C], and perm_max[P][1][C] or None -- shaped so that thresholds and
+    peaks read it as they read scan's."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n = y.shape[0]
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    u = (np.ones(n, bool) if use is None else np.asarray(use) != 0) & np.isfinite(y).all(axis=1)
+    d_o = origin_rows(ctx) if rows is None else rows
+    yk = np.where(u[:, None], y, 0.0)
+    got = ctx.qtl_scan_mv_device(n, d_o.data_ptr(), yk, cov=cov, use=u, additive=additive)
+    out = dict(lod=got["lod"], rank=got["rank"], trait_rank=got["trait_rank"], n_used=got["n_used"], perm_max=None)
+    if permutations:
+        perm = _permutations(n, permutations, seed, use=u)
+        res = yk if cov is None else null_residuals(yk, cov, u)
+        out["perm_max"] = ctx.qtl_scan_mv_device(n, d_o.data_ptr(), res, cov=cov, use=u, perm=perm,
+                                                 additive=additive)["perm_max"][:, None, :]
     return out
 
 

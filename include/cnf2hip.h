@@ -767,6 +767,44 @@ int cnf2_qtl_scan_boot(cnf2_ctx *ctx, int n, const double *origin, int n_traits,
                        int32_t *boot_arg_out /* [B][T][C'] */, int32_t *n_boot_out /* [B][C'] */,
                        double *boot_lod_out /* [B][T][M'] or NULL */, uint32_t flags);
 
+/* Multi-trait scan: is there a locus that moves T correlated traits jointly?  Multivariate Haley-Knott regression (Knott and
+ * Haley 2000; Jiang and Zeng 1995): Wilks' lambda of the T traits on (a, d) at every marker, which finds a pleiotropic locus
+ * whose single-trait effects each stay below their threshold.  One definition for this header,
+ * cnf2freq_amd/csrc/cnf2_qtlmv.h (host and device), the kernels and tests/qtlmv_reference.py.
+ * origin, pheno[n][T], use, cov (0 <= K <= 8), perm[P][n], the mask c of a chromosome, n_c, X0 = [c, c z_1 .. c z_K], a, d, G,
+ * W = (pa, l, pd) with the marker rank rule, CNF2_QTL_ADDITIVE and the centring of traits and covariates are cnf2_qtl_scan's.
+ * 1 <= T <= 16.  A group g is the T columns of the observed data (g = 0) or of permutation p (g = 1 + p): a permutation moves
+ * all T traits of an individual together.
+ * Per chromosome and group B0 = X0'Y (nx x T) and E0 = Y'CY - B0' S11^-1 B0 (T x T), factored E0 = L L' in trait order; trait t is
+ * dropped when E0[t][t] <= 0 or its pivot is below 1e-8 times E0[t][t]: its row of L is absent and it contributes nothing.
+ * Per marker and group, with V = A'Y - G B0 (2 x T): Vw = V L^-T, u_t = vwd_t - l vwa_t, and over the kept traits
+ *   qaa = sum vwa_t^2 / pa,  qdd = sum u_t^2 / pd,  qad = sum vwa_t u_t / sqrt(pa pd),
+ *   Lambda = (1 - qaa)(1 - qdd) - qad^2,  lod = -(n_c / 2) log10 Lambda.
+ * A dropped marker column (pivot 0) gives no terms: rank 1 is Lambda = 1 - qaa (or 1 - qdd), rank 0 a LOD of exactly 0.  Lambda
+ * is clamped to [2^-52, 1], and lod is exactly 0 where it is 1.  This is Wilks' det(E1) / det(E0), by
+ * det(I_T - E0^-1 V'W^-1 V) = det(I_2 - W^-1 V E0^-1 V'); for T = 1 it is 1 - dRSS / RSS0, cnf2_qtl_scan's lod.  It does not change
+ * under Y -> Y B + offsets for an invertible B.  A chromosome is not scanned (lod 0, rank 0) when n_c < K + 3 + T, S11 has no
+ * factor, or every trait is dropped.
+ * Outputs: lod_out[M] the joint LOD of the observed group; rank_out[M] the marker's rank, 0 where the chromosome is not
+ * scanned; trait_rank_out[C] the traits kept for the observed group; n_used_out[C] n_c; perm_max_out[P][C] the largest LOD of
+ * permutation p on chromosome c (NULL exactly when P = 0).  Host pointers, or device pointers with CNF2_OUT_DEVICE.  origin
+ * is a host pointer, or with CNF2_QTL_ORIGIN_DEVICE a device pointer read in place -- NULL: the rows the context's last
+ * cnf2_sweep_qtl left, by cnf2_qtl_scan's rules (CNF2_ERR_STATE when there are none for n); the call leaves them valid.
+ * T > 16, K > 8 and everything cnf2_qtl_scan refuses return CNF2_ERR_ARG and write nothing.
+ * Launches: the masks and marker records (cnf2_qtl_scan's kernels); per tile of groups (cnf2_set_qtlmv_groups caps it, 0 =
+ * what memory allows; results do not depend on it) the column image in operand order with the traits padded by zero
+ * columns to 4, 8 or 16, one wave per (chromosome, group) for B0, E0 and its factor, the product, the maxima's finish.  The
+ * product is cnf2_qtl_scan's -- 16 markers x 64 padded columns per wave on v_mfma_f64_16x16x4_f64, operands from global
+ * memory, no LDS -- with the columns assigned to MFMA rows so that a lane's 16 accumulators are whole groups of one marker;
+ * whitening, the three sums, clamp and logarithm follow in the lane's registers.  No atomics, every sum over the
+ * individuals in ascending order: a call gives the same bits every time, for every cap, from host or device rows, into
+ * host or device outputs. */
+int cnf2_qtl_scan_mv(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                     int n_cov, const double *cov, int n_perm, const int32_t *perm, double *lod_out /* [M] */,
+                     int32_t *rank_out /* [M] */, int32_t *trait_rank_out /* [C] */, int32_t *n_used_out /* [C] */,
+                     double *perm_max_out /* [P][C] */, uint32_t flags);
+int cnf2_set_qtlmv_groups(cnf2_ctx *ctx, int cap);
+
 /* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
  * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;
  * where a row is soft it leaves the within-individual genotype variance in the residual.  One definition for this header,

@@ -236,6 +236,21 @@ int64_t cnf2h_qtl_marker_map(const int32_t *chromstarts, int n_chrom, int chrom_
                              int whole_map_header, int32_t *image_out, int64_t cap, int64_t *offsets_out);
 int64_t cnf2h_qtl_column_tile(int64_t n, int64_t R, int64_t P, int64_t maxima_doubles_per_column, int cap);
 
+/* The host side of the multi-trait scan (cnf2_qtl_scan_mv of cnf2hip.h):
+ *  cnf2h_qtlmv_marker     one (marker, group) cell through cnf2freq_amd/csrc/cnf2_qtlmv.h, the individuals in ascending order:
+ *                         origin[n][4] the marker's rows, y[n][n_traits] (1 .. 16 traits) and cov[n][n_cov] as they enter the
+ *                         sums (the scan centres them first), c[n] the chromosome's mask.  *lod_out the joint LOD, *rank_out
+ *                         the marker's rank, *trait_rank_out the traits kept, *n_used_out n_c.
+ *  cnf2h_qtl_group_tile   the groups of T traits a scan of n individuals takes per pass out of G, with P permutations and
+ *                         n_tiles marker tiles: a group is T columns padded to 4, 8 or 16; the padded image under 1 GB (16
+ *                         .. 4096 columns), at least one group; with P > 0 the maxima, n_tiles doubles per group, under
+ *                         256 MB, at least one group; at most G; at most cap (0 = none).
+ * -2: a bad argument. */
+int cnf2h_qtlmv_marker(int n, const double *origin, int n_traits, const double *y, int n_cov, const double *cov,
+                       const uint8_t *c, int additive, double *lod_out, int32_t *rank_out, int32_t *trait_rank_out,
+                       int32_t *n_used_out);
+int64_t cnf2h_qtl_group_tile(int64_t n, int64_t T, int64_t G, int64_t P, int64_t n_tiles, int cap);
+
 #ifdef __cplusplus
 }
 #endif
