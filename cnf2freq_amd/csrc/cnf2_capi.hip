@@ -27,6 +27,7 @@
 #include "cnf2_qtlcof.h"
 #include "cnf2_qtlem.h"
 #include "cnf2_qtlbin.h"
+#include "cnf2_qtlsurv.h"
 #include "cnf2_kinship.h"
 #include "cnf2_qtlcols.h"
 #include "cnf2_qtlboot.h"
@@ -81,7 +82,7 @@ struct DevBuf {
 
 // the scans whose column tile the caller can cap (cnf2_set_*_columns); the column scan shares the single scan's, and the
 // multi-trait scan's cap counts groups (cnf2_set_qtlmv_groups)
-enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_COUNT };
+enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_SURV, QTL_CAP_COUNT };
 
 struct cnf2_ctx {
     int         device = -1;
@@ -208,6 +209,14 @@ struct cnf2_ctx {
     // single scan's buffers (d_q_chol only receives what qtl_chrom_kernel writes beside the mask: this scan does not read it)
     DevBuf<double>  d_qb_null, d_qb_tilemax, d_qb_lod, d_qb_coef, d_qb_ll0, d_qb_pmax;
     DevBuf<int32_t> d_qb_map, d_qb_keep, d_qb_scan, d_qb_nc, d_qb_rank, d_qb_iters, d_qb_status, d_qb_ones;   // d_qb_map: as d_qe_map
+
+    // survival-trait single-locus scan (cnf2_qtl_scan_surv): the order words of a column tile, the waves' work rows, and what
+    // the binary scan keeps under d_qb_*; the staged inputs and the mask are the single scan's buffers (the times are staged
+    // as its phenotypes and read by no kernel)
+    DevBuf<uint32_t> d_qs_ord;
+    DevBuf<double>   d_qs_work, d_qs_null, d_qs_tilemax, d_qs_lod, d_qs_coef, d_qs_ll0, d_qs_pmax;
+    DevBuf<int32_t>  d_qs_map, d_qs_keep, d_qs_scan, d_qs_nc, d_qs_rank, d_qs_iters, d_qs_status, d_qs_events;
+    int              qtlsurv_blocks = 0;      // cnf2_set_qtlsurv_blocks
 
     // kinship sums (cnf2_kinship_sums): the image a[m_pad][n_pad], the chunks' partial sums of a split range, the staged sum
     DevBuf<double>  d_kin_image, d_kin_part, d_kin_sum;
@@ -474,6 +483,14 @@ int cnf2_set_qtlcof_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QT
 int cnf2_set_qtlem_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_EM, cap); }
 int cnf2_set_qtlbin_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_BIN, cap); }
 int cnf2_set_qtlmv_groups(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_MV, cap); }
+int cnf2_set_qtlsurv_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_SURV, cap); }
+int cnf2_set_qtlsurv_blocks(cnf2_ctx* ctx, int cap)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (cap < 0 || cap > 65536) return fail(ctx, CNF2_ERR_ARG, "the block cap must be 0 .. 65536");
+    ctx->qtlsurv_blocks = cap;
+    return CNF2_OK;
+}
 
 int cnf2_sync(cnf2_ctx* ctx)
 {
@@ -2573,6 +2590,118 @@ int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_trait
         launch_qtl_gather(g, ctx->stream);
         launch_qtlbin_null(q, ctx->stream);
         launch_qtlbin_fit(q, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtlbin_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
+}
+
+// The survival-trait single-locus scan on origin rows [n][M][4]: cnf2_qtlsurv.h, cnf2_qtlsurv_kernels.hip.  The masks and n_c
+// are qtl_chrom_kernel's, the rank rule and the maxima of the permuted columns the binary scan's kernels.  No kernel reads a
+// time: the host puts every column of a tile in risk order (qtlsurv_order, the permuted columns as permuted) and the kernels
+// walk the order words.  The covariates are centred as in the binary scan.
+int cnf2_qtl_scan_surv(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* time, const double* status,
+                       const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol,
+                       double* lod_out, double* coef_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out,
+                       int32_t* n_events_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
+    QtlArgs a = {n, n_traits, n_cov, n_perm, time, use, cov, perm, lod_out, coef_out, ll0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    QtlCentred           centred;
+    RC_TRY(qtl_check(ctx, a, &mask));          // (with the times as the phenotypes: a used time must be finite)
+    if (!status || !iters_out || !status_out || !n_events_out) return fail(ctx, CNF2_ERR_ARG, "status or an output pointer is NULL");
+    if ((uint32_t)a.n > QTLSURV_IND) return fail(ctx, CNF2_ERR_ARG, "too many individuals");
+    if (max_iter < 1 || max_iter > QTLSURV_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLSURV_MAX_ITER);
+    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
+    for (int i = 0; i < a.n; i++) {
+        if (!mask[i]) continue;
+        for (int t = 0; t < a.T; t++) {
+            const double d = status[(size_t)i * a.T + t];
+            if (!(d == 0.0 || d == 1.0)) return fail(ctx, CNF2_ERR_ARG, "status %d of individual %d is used and neither 0 nor 1", t, i);
+        }
+    }
+    if (a.K > 0) {
+        qtl_centre_columns_once(a.cov, a.n, a.K, mask, centred.cov);
+        a.cov = centred.cov.data();
+    }
+    const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
+    const int M = ctx->n_markers, C = ctx->n_chrom;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLBIN_TILE, true, true);
+    const size_t       n_tiles = map.n_tiles;
+    // (the order words of a tile, 4 bytes each, stay under the column image's bound)
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_SURV]);
+    // The blocks of a launch: as many as it has cells, at most the cap, and no more than keep the work rows under 256 MB
+    const size_t cap = ctx->qtlsurv_blocks > 0 ? (size_t)ctx->qtlsurv_blocks : 1024;
+    const size_t fit_blocks  = std::max<size_t>(1, std::min(std::min(cap, n_tiles * rt), ((size_t)1 << 28) / (64 * (size_t)a.n)));
+    const size_t null_blocks = std::max<size_t>(1, std::min(fit_blocks, ((size_t)C * rt + QTLSURV_WAVES - 1) / QTLSURV_WAVES));
+
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, 0, 0));
+    QtlsurvParams p;
+    memset(&p, 0, sizeof(p));
+    QtlbinParams& q = p.b;
+    QtlParams     g = qtl_gather_params(ctx, a, rt);   // (what qtl_chrom_kernel reads and writes)
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_qs_nc, (size_t)C, &g.nc));
+        RC_TRY(each(a.rank, ctx->d_qs_rank, (size_t)M, &q.rank));
+        RC_TRY(each(a.lod, ctx->d_qs_lod, cells, &q.lod));
+        RC_TRY(each(a.coef, ctx->d_qs_coef, cells * ds.ne, &q.coef));
+        RC_TRY(each(iters_out, ctx->d_qs_iters, cells, &q.iters));
+        RC_TRY(each(status_out, ctx->d_qs_status, cells, &q.status));
+        RC_TRY(each(ll0_out, ctx->d_qs_ll0, (size_t)a.T * C, &q.ll0));
+        RC_TRY(each(n_events_out, ctx->d_qs_events, (size_t)a.T * C, &q.n_ones));
+        return each(a.pmax, ctx->d_qs_pmax, (size_t)a.P * a.T * C, &q.pmax);
+    };
+    RC_TRY(ctx->d_qs_map.ensure(ctx, map.image.size()));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_qs_keep.ensure(ctx, (size_t)M));
+    RC_TRY(ctx->d_qs_scan.ensure(ctx, (size_t)C));
+    RC_TRY(ctx->d_qs_null.ensure(ctx, (size_t)C * QTLBIN_NULLQ * rt));
+    RC_TRY(ctx->d_qs_ord.ensure(ctx, rt * (size_t)a.n));
+    RC_TRY(ctx->d_qs_work.ensure(ctx, fit_blocks * QTLSURV_WAVES * 2 * (size_t)a.n));
+    if (a.P > 0) RC_TRY(ctx->d_qs_tilemax.ensure(ctx, n_tiles * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qs_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = ds.nx;
+    g.origin = org.dev, g.cov = ctx->d_q_cov;
+    g.cs = ctx->d_qs_map, g.mchrom = ctx->d_qs_map + map.o_mchrom;
+    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol;
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
+    q.max_iter = max_iter, q.tol = tol;
+    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
+    q.tiles = ctx->d_qs_map + map.o_tiles, q.tile_start = ctx->d_qs_map + map.o_tstart, q.n_tiles = (int)n_tiles;
+    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = ctx->d_qs_keep, q.scan = ctx->d_qs_scan;
+    q.nullq = ctx->d_qs_null, q.tilemax = ctx->d_qs_tilemax, q.rstride = (int)rt;
+    p.ord = ctx->d_qs_ord, p.work = ctx->d_qs_work;
+
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_qs_scan.ptr, 0, (size_t)C * sizeof(int32_t), ctx->stream));     // (a chromosome without markers has no thread to say so)
+    launch_qtl_chrom(g, ctx->stream);
+    launch_qtlbin_rank(q, ctx->stream);
+    std::vector<uint32_t> ord(rt * (size_t)a.n);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = (int)r0;
+        q.rn = (int)std::min(rt, R - r0);
+        for (int rr = 0; rr < q.rn; rr++) {
+            const size_t gr = r0 + rr, pq = gr / a.T, t = gr % a.T;
+            qtlsurv_order(a.n, time + t, status + t, (size_t)a.T, pq ? a.perm + (pq - 1) * (size_t)a.n : nullptr, mask.data(),
+                          ord.data() + (size_t)rr * a.n);
+        }
+        RC_TRY(qtl_upload(ctx, ctx->d_qs_ord, ord.data(), (size_t)q.rn * a.n));       // (complete on return: the tile before has been read)
+        p.fit_blocks  = (int)std::min(fit_blocks, n_tiles * (size_t)q.rn);
+        p.null_blocks = (int)std::min(null_blocks, ((size_t)C * q.rn + QTLSURV_WAVES - 1) / QTLSURV_WAVES);
+        launch_qtlsurv_null(p, ctx->stream);
+        launch_qtlsurv_fit(p, ctx->stream);
         if (r0 + q.rn > (size_t)a.T) launch_qtlbin_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());

@@ -13,6 +13,7 @@
 #include "../cnf2_qtlcof.h"
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
+#include "../cnf2_qtlsurv.h"
 #include "../cnf2_qtlboot.h"
 #include "../cnf2_qtlmv.h"
 #include "../cnf2_qtlplan.h"
@@ -427,6 +428,19 @@ int cnf2h_qtlbin_fit(int n, const double* origin, const double* y, int n_cov, co
     if (!lod_out || !coef_out || !iters_out || !status_out || !rank_out || !ll0_out || !n_ones_out || !n_used_out) return -2;
     return cnf2::qtlbin_fit_serial(n, origin, y, n_cov, cov, c, additive != 0, imprint != 0, max_iter, tol, lod_out, coef_out,
                                    iters_out, status_out, rank_out, ll0_out, n_ones_out, n_used_out)
+               ? 0
+               : -2;
+}
+
+// one (marker, column) fit of the survival-trait scan: qtlsurv_fit_serial (cnf2_qtlsurv.h)
+int cnf2h_qtlsurv_fit(int n, const double* origin, const double* time, const double* status, int n_cov, const double* cov,
+                      const uint8_t* c, int additive, int imprint, int max_iter, double tol, double* lod_out, double* coef_out,
+                      int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out, int32_t* n_events_out,
+                      int32_t* n_used_out)
+{
+    if (!lod_out || !coef_out || !iters_out || !status_out || !rank_out || !ll0_out || !n_events_out || !n_used_out) return -2;
+    return cnf2::qtlsurv_fit_serial(n, origin, time, status, n_cov, cov, c, additive != 0, imprint != 0, max_iter, tol, lod_out,
+                                    coef_out, iters_out, status_out, rank_out, ll0_out, n_events_out, n_used_out)
                ? 0
                : -2;
 }

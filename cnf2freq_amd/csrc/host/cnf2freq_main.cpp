@@ -8,6 +8,8 @@
 //            [--qtlx F --phenofile P [--qtl-imprint] [--qtl-interactive name,name] [the --qtl-* options]]
 //            [--qtlem F --phenofile P [--qtl-em-iterations N] [--qtl-em-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlbin F --phenofile P [--qtl-binary-iterations N] [--qtl-binary-tol X] [--qtl-imprint] [the --qtl-* options]]
+//            [--qtlsurv F --phenofile P --qtl-surv-time NAME --qtl-surv-status NAME [--qtl-surv-iterations N] [--qtl-surv-tol X]
+//             [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlcof F --phenofile P --qtl-cofactors i,j,k [--qtl-window X] [the --qtl-* options]]
 //            [--qtlboot F --phenofile P --qtl-boot-chrom C [--qtl-boot-replicates B] [--qtl-covariates, --qtl-seed, --qtl-additive]]
 //            [--qtlmv F --phenofile P [--qtl-traits name,name,..] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
@@ -126,6 +128,7 @@
 #include "../cnf2_qtlx.h"
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
+#include "../cnf2_qtlsurv.h"
 #include "../cnf2_qtlmv.h"
 #include "cnf2_readers.h"
 #include "cnf2_rccl_transport.h"
@@ -189,6 +192,12 @@ struct Options {
     double      qtlbin_tol = 1e-7;       // --qtl-binary-tol
     bool        qtlbin_extra_set = false; // one of the two above was given
     std::vector<int> qtlbin_trait_cols;  // columns of pheno: the traits whose values are all 0 or 1
+    std::string qtlsurv;                 // --qtlsurv F: survival-trait scan (with --phenofile, the two column names and the --qtl-* options)
+    std::string qtlsurv_time, qtlsurv_status;   // --qtl-surv-time, --qtl-surv-status: column names
+    int         qtlsurv_iterations = 50; // --qtl-surv-iterations
+    double      qtlsurv_tol = 1e-7;      // --qtl-surv-tol
+    bool        qtlsurv_extra_set = false; // one of the four above was given
+    int         qtlsurv_time_col = -1, qtlsurv_status_col = -1;   // columns of pheno
     std::string qtlcof;                  // --qtlcof F: cofactor scan (with --phenofile and the --qtl-* options)
     std::string qtl_cofactors;           // --qtl-cofactors i,j,k: map indices, from 0
     double      qtl_window = 0.0;        // --qtl-window X: a cofactor is left out within X map units of itself
@@ -344,6 +353,29 @@ static bool parse(int argc, char** argv, Options& o)
                 exit(2);
             }
         }
+        else if (a == "--qtlsurv") o.qtlsurv = val();
+        else if (a == "--qtl-surv-time") {
+            o.qtlsurv_time      = val();
+            o.qtlsurv_extra_set = true;
+        }
+        else if (a == "--qtl-surv-status") {
+            o.qtlsurv_status    = val();
+            o.qtlsurv_extra_set = true;
+        }
+        else if (a == "--qtl-surv-iterations") {
+            o.qtlsurv_iterations = atoi(val().c_str());
+            o.qtlsurv_extra_set  = true;
+        }
+        else if (a == "--qtl-surv-tol") {
+            const std::string t = val();
+            char*             end = nullptr;
+            o.qtlsurv_tol       = strtod(t.c_str(), &end);
+            o.qtlsurv_extra_set = true;
+            if (t.empty() || *end != 0 || !std::isfinite(o.qtlsurv_tol)) {
+                fprintf(stderr, "--qtl-surv-tol needs a finite number, not \"%s\"\n", t.c_str());
+                exit(2);
+            }
+        }
         else if (a == "--qtl2-every") {
             o.qtl2_every     = atoi(val().c_str());
             o.qtl2_every_set = true;
@@ -386,6 +418,7 @@ static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
 static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlem_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlsurv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
@@ -493,6 +526,9 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtlmv.empty())
         qtlmv_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
                                     !opt.qtlcof.empty() || !opt.qtlboot.empty());
+    if (world == 1 && !opt.qtlsurv.empty())
+        qtlsurv_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
+                                      !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1040,6 +1076,74 @@ static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool row
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlbin);
 }
 
+// --qtlsurv after the last round (single GPU), and after the other scans where they are given: the survival-trait scan
+// (cnf2_qtl_scan_surv) of the pair of columns --qtl-surv-time and --qtl-surv-status (1 = the event was observed at the time,
+// 0 = censored then), on the rows a cnf2_sweep_qtl left in the context -- theirs, or one of this function's own.  An individual
+// is used when its covariates, its time and its status are there; permutations permute the pairs.  The file has --qtlbin's
+// layout: a line "trait", the time's and the status's name; per marker chromosome, position, n, the rank, the LOD, the
+// iterations, the status of the fit (0 = stopped by --qtl-surv-tol, 1 = by --qtl-surv-iterations, 2 = breakdown) and the
+// effects on the log hazard a, d (not with --qtl-additive), i (with --qtl-imprint), "-" for a dropped one or a cell without a
+// fit; with --qtl-permutations K > 0 a line "threshold", "lod" and the 5 % and 1 % genome-wide thresholds.
+static void qtlsurv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    const int NC = cnf2::qtlem_design(K, opt.qtl_additive, opt.qtl_imprint).ne;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  tm(N, 0.0), ev(N, 0.0), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> u(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        const double t = row[opt.qtlsurv_time_col], d = row[opt.qtlsurv_status_col];
+        bool on = t == t && d == d;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) on = false;
+        }
+        u[j] = on ? 1 : 0;
+        if (on) tm[j] = t, ev[j] = d;
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | (opt.qtl_imprint ? CNF2_QTL_IMPRINT : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    std::vector<double>  lod(M), coef((size_t)M * NC), l0(C), pm((size_t)NP * C);
+    std::vector<int32_t> rank(M), nused(C), iters(M), status(M), nev(C), perm((size_t)NP * N);
+    int rc;
+    if (!rows_kept) {          // the sweep, with the rows left in the context; its Haley-Knott scan is not reported
+        std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), l1(M), c1((size_t)M * 2), r1(C);
+        std::vector<int32_t> k1(M), m1(C);
+        rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), 1, tm.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr, l1.data(),
+                            c1.data(), k1.data(), r1.data(), m1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlsurv: ") + cnf2_last_error(ctx));
+    }
+    if (NP > 0) qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+    rc = cnf2_qtl_scan_surv(ctx, N, nullptr, 1, tm.data(), ev.data(), u.data(), K, K ? cov.data() : nullptr, NP, NP ? perm.data() : nullptr,
+                            opt.qtlsurv_iterations, opt.qtlsurv_tol, lod.data(), coef.data(), iters.data(), status.data(), rank.data(),
+                            l0.data(), nev.data(), nused.data(), NP ? pm.data() : nullptr, flags);
+    if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlsurv: ") + cnf2_last_error(ctx));
+    FILE* out = fopen(opt.qtlsurv.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlsurv);
+    fprintf(out, "trait\t%s\t%s\n", opt.qtlsurv_time.c_str(), opt.qtlsurv_status.c_str());
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+            fprintf(out, "%d\t%.5lf\t%d\t%d\t%.5lf\t%d\t%d", c + 1, P.pos[m], (int)nused[c], (int)rank[m], lod[m], (int)iters[m], (int)status[m]);
+            for (int e = 0; e < NC; e++) {
+                const double v = coef[(size_t)m * NC + e];
+                if (v != v) fprintf(out, "\t-");
+                else fprintf(out, "\t%.5lf", v);
+            }
+            fprintf(out, "\n");
+        }
+    if (NP > 0) {
+        std::vector<double> mx(NP, 0.0);
+        for (int p = 0; p < NP; p++)
+            for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[(size_t)p * C + c]);
+        fprintf(out, "threshold\tlod\t%.5lf\t%.5lf\n", qtl_threshold(mx, 0.05), qtl_threshold(mx, 0.01));
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlsurv);
+}
+
 // res[n][T]: the residuals of every phenotype column on the columns X[n][W] and the intercept over the used individuals, 0 for
 // the others -- qtl.null_residuals of the Python package for a null model that holds the cofactors: the columns minus their
 // means, orthogonalised one after the other (twice, for the rounding); a column of which less than QTL_PIVOT of its own
@@ -1381,6 +1485,37 @@ static bool prepare_qtlbin(Options& opt)
     if (opt.qtlbin_trait_cols.empty()) {
         fprintf(stderr, "--qtlbin: no column of %s that is not a covariate holds only 0 and 1\n", opt.phenofile.c_str());
         return false;
+    }
+    return true;
+}
+
+// the two columns --qtlsurv scans: both named, in the table, no covariates, and the status 0 or 1 wherever it is there
+static bool prepare_qtlsurv(Options& opt)
+{
+    const struct { const char* flag; const std::string& name; int* col; } want[2] = {
+        {"--qtl-surv-time", opt.qtlsurv_time, &opt.qtlsurv_time_col}, {"--qtl-surv-status", opt.qtlsurv_status, &opt.qtlsurv_status_col}};
+    for (const auto& w : want) {
+        const auto it = std::find(opt.pheno.columns.begin(), opt.pheno.columns.end(), w.name);
+        if (it == opt.pheno.columns.end()) {
+            fprintf(stderr, "%s: \"%s\" is not a column of %s\n", w.flag, w.name.c_str(), opt.phenofile.c_str());
+            return false;
+        }
+        *w.col = (int)(it - opt.pheno.columns.begin());
+        if (std::find(opt.qtl_cov_cols.begin(), opt.qtl_cov_cols.end(), *w.col) != opt.qtl_cov_cols.end()) {
+            fprintf(stderr, "%s: \"%s\" is a covariate\n", w.flag, w.name.c_str());
+            return false;
+        }
+    }
+    if (opt.qtlsurv_time_col == opt.qtlsurv_status_col) {
+        fprintf(stderr, "--qtl-surv-time and --qtl-surv-status name the same column\n");
+        return false;
+    }
+    for (const std::vector<double>& row : opt.pheno.rows) {
+        const double v = row[opt.qtlsurv_status_col];
+        if (v == v && !(v == 0.0 || v == 1.0)) {
+            fprintf(stderr, "--qtl-surv-status: column \"%s\" holds a value that is neither 0 nor 1\n", opt.qtlsurv_status.c_str());
+            return false;
+        }
     }
     return true;
 }
@@ -1952,7 +2087,27 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-binary-iterations must be 1 .. %d\n", cnf2::QTLBIN_MAX_ITER);
         return 2;
     }
-    if (opt.qtlx.empty() && (opt.qtl_interactive_set || (opt.qtlx_extra_set && opt.qtlem.empty() && opt.qtlbin.empty()))) {
+    if (opt.gpus > 1 && !opt.qtlsurv.empty()) {
+        fprintf(stderr, "--qtlsurv needs a single GPU (--gpus 1): a fit is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlsurv.empty() && opt.qtlsurv_extra_set) {
+        fprintf(stderr, "--qtl-surv-time, --qtl-surv-status, --qtl-surv-iterations and --qtl-surv-tol need --qtlsurv FILE\n");
+        return 2;
+    }
+    if (!opt.qtlsurv.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlsurv FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (!opt.qtlsurv.empty() && (opt.qtlsurv_time.empty() || opt.qtlsurv_status.empty())) {
+        fprintf(stderr, "--qtlsurv FILE needs --qtl-surv-time NAME and --qtl-surv-status NAME\n");
+        return 2;
+    }
+    if (opt.qtlsurv_iterations < 1 || opt.qtlsurv_iterations > cnf2::QTLSURV_MAX_ITER) {
+        fprintf(stderr, "--qtl-surv-iterations must be 1 .. %d\n", cnf2::QTLSURV_MAX_ITER);
+        return 2;
+    }
+    if (opt.qtlx.empty() && (opt.qtl_interactive_set || (opt.qtlx_extra_set && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlsurv.empty()))) {
         fprintf(stderr, "--qtl-imprint and --qtl-interactive need --qtlx FILE\n");
         return 2;
     }
@@ -2013,7 +2168,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
-        opt.qtlmv.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        opt.qtlmv.empty() && opt.qtlsurv.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -2046,12 +2201,13 @@ int main(int argc, char** argv)
         return 2;
     }
     if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty() ||
-         !opt.qtlmv.empty()) &&
+         !opt.qtlmv.empty() || !opt.qtlsurv.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
     if (!opt.qtlmv.empty() && !prepare_qtlmv(opt)) return 2;
     if (!opt.qtlcof.empty() && !prepare_qtlcof(opt, P)) return 2;
     if (!opt.qtlbin.empty() && !prepare_qtlbin(opt)) return 2;
+    if (!opt.qtlsurv.empty() && !prepare_qtlsurv(opt)) return 2;
     if (!opt.qtlx.empty() && !prepare_qtlx(opt)) return 2;
     if (!opt.qtl2.empty() && opt.qtl_cov_cols.size() > 6) {
         fprintf(stderr, "--qtl2: at most 6 covariates\n");

@@ -16,7 +16,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
            "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
-           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile"]
+           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -68,6 +68,7 @@ def load():
         L.cnf2h_qtlcof_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, C.c_uint32, i32, vp, vp, vp, vp, vp]
         L.cnf2h_qtlem_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_qtlbin_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_qtlsurv_fit.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_kinship_sums.argtypes = [i32, i32, vp, vp, i32, i32, i32, vp, vp]
         L.cnf2h_qtl_cols_marker.argtypes = [i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
         L.cnf2h_qtl_bootstrap_counts.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
@@ -363,6 +364,31 @@ def qtlbin_fit(origin, y, cov=None, c=None, additive=False, imprint=False, max_i
         raise RuntimeError("cnf2h_qtlbin_fit failed (%d)" % rc)
     return dict(lod=float(d[0]), coef=coef, iters=int(i5[0]), status=int(i5[1]), rank=int(i5[2]), ll0=float(d[1]),
                 n_ones=int(i5[3]), n_used=int(i5[4]))
+
+
+def qtlsurv_fit(origin, time, status, cov=None, c=None, additive=False, imprint=False, max_iter=50, tol=1e-7):
+    """cnf2h_qtlsurv_fit: one (marker, column) fit of the survival-trait scan (cnf2_qtlsurv.h) on the marker's rows
+    origin[n][4], time[n] and status[n] (1 = event, 0 = censored), covariates cov[n][K] and the chromosome's mask c[n] (None:
+    everybody).  A dict: lod, coef[ne], iters, status, rank, ll0, n_events, n_used.  CPU only."""
+    L = load()
+    o = np.ascontiguousarray(origin, np.float64)
+    t = np.ascontiguousarray(time, np.float64).reshape(-1)
+    s = np.ascontiguousarray(status, np.float64).reshape(-1)
+    n = len(t)
+    if o.shape != (n, 4) or s.shape != (n,):
+        raise ValueError("origin must be [n][4], time and status [n]")
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    ne = 1 + (0 if additive else 1) + (1 if imprint else 0)
+    d, coef, i5 = np.zeros(2), np.zeros(ne), np.zeros(5, np.int32)
+    rc = L.cnf2h_qtlsurv_fit(n, _p(o), _p(t), _p(s), K, None if K == 0 else _p(z), _p(m), int(additive), int(imprint),
+                             int(max_iter), float(tol), _p(d[0:1]), _p(coef), _p(i5[0:1]), _p(i5[1:2]), _p(i5[2:3]), _p(d[1:2]),
+                             _p(i5[3:4]), _p(i5[4:5]))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtlsurv_fit failed (%d)" % rc)
+    return dict(lod=float(d[0]), coef=coef, iters=int(i5[0]), status=int(i5[1]), rank=int(i5[2]), ll0=float(d[1]),
+                n_events=int(i5[3]), n_used=int(i5[4]))
 
 
 def qtl_null_residuals(pheno, cov=None, use=None):

@@ -17,6 +17,9 @@ The maximum-likelihood scan (Context.qtl_scan_em, cnf2_qtl_scan_em) fits the nor
 The binary-trait scan (Context.qtl_scan_binary, cnf2_qtl_scan_binary) fits a logistic regression of a 0/1 trait per marker:
 scan_binary, read by thresholds and peaks in the same way.
 
+The survival-trait scan (Context.qtl_scan_surv, cnf2_qtl_scan_surv) fits Cox's proportional hazards regression of a
+time-to-event trait with censoring per marker: scan_surv, read by thresholds and peaks in the same way.
+
 The cofactor scan (Context.qtl_scan_cof, cnf2_qtl_scan_cof) is composite interval mapping: every marker fitted together with
 the loci found before, each left out inside its own window.  scan_cof with cofactor_windows asks whether there is a further
 QTL, fit_multi (read_multi) reads the multiple-QTL model -- full LOD, drop-one LODs, effects -- off one call, and
@@ -386,6 +389,60 @@ def scan_binary(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, s
         perm = _permutations(n, permutations, seed, use=u, strata=strata) if permutations else None
         got = ctx.qtl_scan_binary_device(n, d_o.data_ptr(), yk, use=u, perm=perm, **kw)
         for key in ("lod", "coef", "iters", "status", "rank", "ll0", "n_ones", "n_used"):
+            out[key][cols] = got[key]
+        if permutations:
+            out["perm_max"][:, cols] = got["perm_max"]
+    return out
+
+
+def scan_surv(ctx, time, status, cov=None, imprint=False, use=None, permutations=0, seed=0, strata=None, additive=False,
+              max_iter=50, tol=1e-7, rows=None):
+    """The survival-trait scan of a whole cross on the context's uploaded pedigree: as scan_binary -- one origin sweep with the
+    rows left on the device (or `rows`, the tensor of origin_rows) and per pattern of missing times (NaN) one scan with the
+    pattern's own `use` -- with every (marker, trait) Cox's proportional hazards regression of (time, status) on the
+    covariates and the effects a, d (unless additive), i (with imprint), the effects on the log hazard, fitted by Newton's
+    method on Breslow's partial likelihood from the null fit until it gains less than tol LOD or max_iter iterations are
+    done.  status is 1 where the event was observed at `time` and 0 where the individual was censored then; where the time
+    is not missing any other status raises ValueError.  With permutations > 0 the raw pairs (time, status) are permuted
+    together, within the strata of `strata` (qtl.permutations): with covariates the permutations are valid only within
+    strata of the covariates, which the caller supplies.  A dict: lod[T][M], coef[T][M][len(coef_names)], coef_names,
+    iters[T][M], status[T][M] (0 = stopped by tol, 1 = by max_iter, 2 = breakdown, e.g. a monotone likelihood), rank[T][M],
+    ll0[T][C] (the null model's log partial likelihood, 0 where the trait is not scanned on the chromosome), n_events[T][C],
+    n_used[T][C], perm_max[P][T][C] or None (thresholds)."""
+    t = np.asarray(time, np.float64)
+    t = t[:, None] if t.ndim == 1 else t
+    d = np.asarray(status, np.float64)
+    d = d[:, None] if d.ndim == 1 else d
+    n, T = t.shape
+    if n != ctx.n_ind:
+        raise ValueError("time must have a row per analysed individual (%d)" % ctx.n_ind)
+    if d.shape != t.shape:
+        raise ValueError("status must have the shape of time")
+    if not 1 <= int(max_iter) <= 1000:
+        raise ValueError("max_iter must be 1 .. 1000")
+    if not np.isfinite(tol):
+        raise ValueError("tol must be finite")
+    missing = ~np.isfinite(t)
+    if not np.all(missing | (d == 0.0) | (d == 1.0)):
+        raise ValueError("a status is 1 (event) or 0 (censored) wherever the time is not missing")
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    names = coef_names(0, imprint, additive)
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, len(names)), np.nan), coef_names=names,
+               iters=np.zeros((T, M), np.int32), status=np.zeros((T, M), np.int32), rank=np.zeros((T, M), np.int32),
+               ll0=np.zeros((T, C)), n_events=np.zeros((T, C), np.int32), n_used=np.zeros((T, C), np.int32),
+               perm_max=np.zeros((permutations, T, C)) if permutations else None)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    kw = dict(cov=cov, imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        tk, dk = np.where(u[:, None], t[:, cols], 0.0), np.where(u[:, None], d[:, cols], 0.0)
+        perm = _permutations(n, permutations, seed, use=u, strata=strata) if permutations else None
+        got = ctx.qtl_scan_surv_device(n, d_o.data_ptr(), tk, dk, use=u, perm=perm, **kw)
+        for key in ("lod", "coef", "iters", "status", "rank", "ll0", "n_events", "n_used"):
             out[key][cols] = got[key]
         if permutations:
             out["perm_max"][:, cols] = got["perm_max"]

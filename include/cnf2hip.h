@@ -891,6 +891,55 @@ int cnf2_qtl_scan_binary(cnf2_ctx *ctx, int n, const double *origin, int n_trait
                          double *ll0_out, int32_t *n_ones_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
 int cnf2_set_qtlbin_columns(cnf2_ctx *ctx, int cap);
 
+/* Survival-trait single-locus scan: Cox's proportional hazards regression of a time-to-event trait with right censoring on
+ * the origin rows, fitted per marker and column, observed and permuted, by Newton's method on Breslow's partial likelihood.
+ * One definition for this header, cnf2freq_amd/csrc/cnf2_qtlsurv.h (host and device), the kernels and
+ * tests/qtlsurv_reference.py.
+ * origin, use, cov (0 <= K <= 8, taken minus their means), perm, the mask c of a chromosome, n_c and the columns R = T (1 + P)
+ * are cnf2_qtl_scan's.  time[n][T] is finite and status[n][T] is 1.0 (the event was observed at `time`) or 0.0 (censored at
+ * `time`) for every used individual; a permutation moves the pair (time, status) of an individual together.  Only the order
+ * of the times enters: a strictly increasing function of them gives the same bits.
+ *   design    no intercept (it is not identifiable): x_i = [z_1 .. z_K, a, d, i], a = o[3] - o[0], d = o[1] + o[2] (not with
+ *             CNF2_QTL_ADDITIVE), i = o[1] - o[2] (only with CNF2_QTL_IMPRINT); the effects are on the log hazard
+ *   model     w_j = exp(x_j' theta), S0(t) = sum_{j: c_j, t_j >= t} w_j;
+ *             l(theta) = sum_{k: c_k, status_k = 1} [ x_k' theta - log S0(t_k) ]  (Breslow's form for tied times)
+ *   rank      cnf2_qtl_scanx's rule on the unweighted columns [1, z, a, d, i] in that order; the intercept takes part in this
+ *             rule only, so that a column that is constant over the individuals of c is dropped.  rank[m] = the kept effects
+ *             = cnf2_qtl_scanx's rank[m][1] with imprinting, rank[m][0] without.  rank 0: lod 0, iters 0, status 0.
+ *   null fit  per chromosome and column on the covariates alone, from theta = 0: at most 50 iterations, stopped by a gain
+ *             below 1e-13 LOD; without covariates the single pass at theta = 0, l0 = -sum_groups ev_g log(n at risk).  It
+ *             gives l0 (ll0_out, never positive) and gamma0.
+ *   fit       from theta_0 = (gamma0, 0), l_0 = l0.  A pass at theta_t gives l_t, the score s and the information G over the
+ *             kept columns.  After the pass at theta_t, t >= 1: (l_t - l_{t-1}) / ln 10 < tol stops with status 0 (a negative
+ *             tol: never), else t = max_iter stops with status 1.  Otherwise theta_{t+1} = theta_t + G^-1 s by a Cholesky
+ *             factor; a pivot that is not positive or a theta_{t+1} that is not finite is a breakdown, status 2, and theta_t,
+ *             l_t are reported.  A pass at theta_t, t >= 1, whose l is not finite (an S0 that overflowed) is a breakdown too:
+ *             theta_{t-1}, l_{t-1} and iters = t - 1 are reported with status 2.  This is where a monotone likelihood ends if
+ *             max_iter does not end it first.  There is no step-halving.
+ *   report    theta_t, lod = max(0, (l_t - l0) / ln 10), iters = t, status
+ *   not scanned   a chromosome with n_c < W + 1, W = 1 + K + ne, or without a factor of [1, z]: rank 0; on a chromosome a
+ *             column without an event among the n_c, or whose null fit does not stop by its tolerance or breaks down.  Then
+ *             lod 0, coef NaN, iters 0, status 0, ll0 0.
+ * max_iter is 1 .. 1000 and tol finite.  Outputs (host memory, or device memory with CNF2_OUT_DEVICE): lod_out [T][M],
+ * coef_out [T][M][ne], iters_out and status_out [T][M] int32, rank_out [M], ll0_out [T][C], n_events_out [T][C] int32 (the
+ * events among the n_c), n_used_out [C], perm_max_out [P][T][C] (the permuted columns contribute only there).
+ * CNF2_QTL_ORIGIN_DEVICE is cnf2_qtl_scan_binary's.  Everything cnf2_qtl_scan refuses is refused, and so are max_iter and tol
+ * out of range, a used status that is not exactly 0 or 1 and a used time that is not finite: CNF2_ERR_ARG, and nothing is
+ * written.
+ * One wavefront owns one (marker, column) fit from start to stop.  The individuals of a column stand in risk order
+ * (descending time, ties by ascending index); the sums over risk sets are running sums along that order, formed in rounds
+ * of 64 positions by wave scans of a fixed order.  No atomics: a call gives the same bits every time, for every column cap
+ * and every block cap (the setters below, 0 = no cap) and from host or device rows. */
+int cnf2_qtl_scan_surv(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *time, const double *status,
+                       const uint8_t *use, int n_cov, const double *cov, int n_perm, const int32_t *perm, int max_iter,
+                       double tol, double *lod_out, double *coef_out, int32_t *iters_out, int32_t *status_out,
+                       int32_t *rank_out, double *ll0_out, int32_t *n_events_out, int32_t *n_used_out, double *perm_max_out,
+                       uint32_t flags);
+int cnf2_set_qtlsurv_columns(cnf2_ctx *ctx, int cap);
+/* cap on the blocks of the scan's null and fit launches (0 = the default, 1024; at most 65536): each block strides over its
+ * cells, and the context owns two work rows of n doubles per wave of the launch */
+int cnf2_set_qtlsurv_blocks(cnf2_ctx *ctx, int cap);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every

@@ -189,6 +189,17 @@ int cnf2h_qtlbin_fit(int n, const double *origin, const double *y, int n_cov, co
                      int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *ll0_out, int32_t *n_ones_out,
                      int32_t *n_used_out);
 
+/* One (marker, column) fit of the survival-trait scan (cnf2_qtl_scan_surv of cnf2hip.h) on the host, by the functions of
+ * cnf2freq_amd/csrc/cnf2_qtlsurv.h that the kernels use, the running sums in the plain order of the risk order: origin[n][4]
+ * the marker's rows, time[n] (finite) and status[n] (0 or 1) where c is set, cov[n][n_cov], c[n] the chromosome's mask.
+ * lod_out, coef_out [ne], iters_out, status_out, rank_out, ll0_out, n_events_out and n_used_out receive one cell.  -2: a bad
+ * argument (n_cov above 8, max_iter outside 1 .. 1000, a tol that is not finite, under the mask a status that is neither 0
+ * nor 1 or a time that is not finite). */
+int cnf2h_qtlsurv_fit(int n, const double *origin, const double *time, const double *status, int n_cov, const double *cov,
+                      const uint8_t *c, int additive, int imprint, int max_iter, double tol, double *lod_out,
+                      double *coef_out, int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *ll0_out,
+                      int32_t *n_events_out, int32_t *n_used_out);
+
 /* cnf2_kinship_sums (cnf2hip.h) on the CPU, for tests and for callers without a GPU: sum_out[n][n] = sum over the markers of
  * the chromosomes chrom_begin .. chrom_end-1 of a_i(m) a_j(m), a = origin[3] - origin[0], on origin[n][n_markers][4] and the
  * map's chromstarts[n_chrom + 1]; *n_markers_out the number of those markers.  The markers are added in ascending order
