@@ -54,6 +54,7 @@ SYMBOLS = [
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
     "cnf2_qtl_scan_surv", "cnf2_set_qtlsurv_columns", "cnf2_set_qtlsurv_blocks",
+    "cnf2_qtl_scan_var", "cnf2_set_qtlvar_columns",
     "cnf2_qtl_scan_cof", "cnf2_set_qtlcof_columns", "cnf2_qtl_kept_rows",
     "cnf2_kinship_sums", "cnf2_qtl_scan_cols", "cnf2_qtl_scan_boot", "cnf2_qtl_scan_mv", "cnf2_set_qtlmv_groups",
 ]
@@ -152,6 +153,9 @@ def load():
                                          vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlsurv_columns.argtypes = [vp, i32]
         L.cnf2_set_qtlsurv_blocks.argtypes = [vp, i32]
+        L.cnf2_qtl_scan_var.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, i32, C.c_double,
+                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_set_qtlvar_columns.argtypes = [vp, i32]
         L.cnf2_haplos.argtypes = [vp, i32, i32, vp, C.c_uint32]
         L.cnf2_infprobs.argtypes = [vp, i32, i32, i32, vp, vp, C.c_uint32]
         L.cnf2_infprobs_rows.argtypes = [vp, i32, i32, vp, C.c_uint32]
@@ -1161,6 +1165,55 @@ class Context:
         return self._qtlsurv_call(n, C.c_void_p(d_origin), time, status, cov, use, perm, max_iter, tol,
                                   flags | QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0),
                                   out)
+
+    # -- variance-QTL single-locus scan: mean and log-variance effects ------------------
+    def set_qtlvar_columns(self, cap):
+        """Cap on the columns per tile of qtl_scan_var (0 = what memory allows); results do not depend on it."""
+        self._chk(self.L.cnf2_set_qtlvar_columns(self.h, cap), "cnf2_set_qtlvar_columns")
+
+    def _qtlvar_outputs(self, T, P, ne):
+        M, Cn = self.n_markers, self.n_chrom
+        return dict(lod=np.zeros((T, M, 3)), coef_mean=np.zeros((T, M, ne)), coef_var=np.zeros((T, M, ne)),
+                    iters=np.zeros((T, M, 3), np.int32), status=np.zeros((T, M, 3), np.int32), rank=np.zeros(M, np.int32),
+                    ll0=np.zeros((T, Cn)), n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn, 3)) if P else None)
+
+    def _qtlvar_call(self, n, origin_ptr, pheno, cov, n_var, use, perm, max_iter, tol, flags, out=None):
+        """cnf2_qtl_scan_var on the rows behind origin_ptr, with host outputs (out = None: new arrays; else a dict of
+        arrays), or with OUT_DEVICE in flags and out a dict of device pointers (ints; perm_max None without permutations)"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        ne = 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
+        o = self._qtlvar_outputs(T, P, ne) if out is None else out
+        opt = lambda a: None if a is None else _p(a)
+        ptr = (lambda a: C.c_void_p(a) if a else None) if flags & OUT_DEVICE else opt
+        self._chk(self.L.cnf2_qtl_scan_var(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), int(n_var), P, opt(perm),
+                                           int(max_iter), float(tol), ptr(o["lod"]), ptr(o["coef_mean"]), ptr(o["coef_var"]),
+                                           ptr(o["iters"]), ptr(o["status"]), ptr(o["rank"]), ptr(o["ll0"]), ptr(o["n_used"]),
+                                           ptr(o["perm_max"]), flags), "cnf2_qtl_scan_var")
+        return o
+
+    def qtl_scan_var(self, origin, pheno, cov=None, n_var=0, imprint=False, use=None, perm=None, additive=False, max_iter=50,
+                     tol=1e-7, out=None, flags=0):
+        """cnf2_qtl_scan_var on host rows origin[n][M][4]: per marker the double generalised linear model of pheno[n][T] --
+        the mean on the covariates cov[n][K], the log variance on the first n_var of them, both on the effects a, d (not with
+        additive) and i (with imprint) -- fitted mean-only, variance-only and in full from the null fit, for the individuals
+        of use[n] and the permutations perm[P][n].  A dict: lod[T][M][3] (joint, mean, variance), coef_mean and
+        coef_var[T][M][ne] of the full fit (NaN for a dropped effect), iters and status[T][M][3] by fit (0 = stopped by tol,
+        1 = by max_iter, 2 = breakdown), rank[M], ll0[T][C], n_used[C], perm_max[P][T][C][3] (None without permutations).
+        The model: include/cnf2hip.h; cnf2freq_amd/qtl.py reads the results."""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return self._qtlvar_call(origin.shape[0], _p(origin), pheno, cov, n_var, use, perm, max_iter, tol,
+                                 flags | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0), out)
+
+    def qtl_scan_var_device(self, n, d_origin, pheno, cov=None, n_var=0, imprint=False, use=None, perm=None, additive=False,
+                            max_iter=50, tol=1e-7, out=None, flags=0):
+        """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
+        sweep_qtl left in it, which this call leaves valid).  With OUT_DEVICE in flags, out is a dict of device pointers."""
+        return self._qtlvar_call(n, C.c_void_p(d_origin), pheno, cov, n_var, use, perm, max_iter, tol,
+                                 flags | QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0),
+                                 out)
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

@@ -28,6 +28,7 @@
 #include "cnf2_qtlem.h"
 #include "cnf2_qtlbin.h"
 #include "cnf2_qtlsurv.h"
+#include "cnf2_qtlvar.h"
 #include "cnf2_kinship.h"
 #include "cnf2_qtlcols.h"
 #include "cnf2_qtlboot.h"
@@ -82,7 +83,7 @@ struct DevBuf {
 
 // the scans whose column tile the caller can cap (cnf2_set_*_columns); the column scan shares the single scan's, and the
 // multi-trait scan's cap counts groups (cnf2_set_qtlmv_groups)
-enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_SURV, QTL_CAP_COUNT };
+enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_SURV, QTL_CAP_VAR, QTL_CAP_COUNT };
 
 struct cnf2_ctx {
     int         device = -1;
@@ -217,6 +218,11 @@ struct cnf2_ctx {
     DevBuf<double>   d_qs_work, d_qs_null, d_qs_tilemax, d_qs_lod, d_qs_coef, d_qs_ll0, d_qs_pmax;
     DevBuf<int32_t>  d_qs_map, d_qs_keep, d_qs_scan, d_qs_nc, d_qs_rank, d_qs_iters, d_qs_status, d_qs_events;
     int              qtlsurv_blocks = 0;      // cnf2_set_qtlsurv_blocks
+
+    // variance-QTL single-locus scan (cnf2_qtl_scan_var): what the binary scan keeps under d_qb_*, with three LODs per cell
+    // and the full fit's coefficients of both parts; the staged inputs, the mask and the column image are the single scan's
+    DevBuf<double>  d_qv_null, d_qv_tilemax, d_qv_lod, d_qv_coef, d_qv_coefv, d_qv_ll0, d_qv_pmax;
+    DevBuf<int32_t> d_qv_map, d_qv_keep, d_qv_scan, d_qv_nc, d_qv_rank, d_qv_iters, d_qv_status;
 
     // kinship sums (cnf2_kinship_sums): the image a[m_pad][n_pad], the chunks' partial sums of a split range, the staged sum
     DevBuf<double>  d_kin_image, d_kin_part, d_kin_sum;
@@ -484,6 +490,7 @@ int cnf2_set_qtlem_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL
 int cnf2_set_qtlbin_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_BIN, cap); }
 int cnf2_set_qtlmv_groups(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_MV, cap); }
 int cnf2_set_qtlsurv_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_SURV, cap); }
+int cnf2_set_qtlvar_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_VAR, cap); }
 int cnf2_set_qtlsurv_blocks(cnf2_ctx* ctx, int cap)
 {
     if (!ctx) return CNF2_ERR_ARG;
@@ -2703,6 +2710,99 @@ int cnf2_qtl_scan_surv(cnf2_ctx* ctx, int n, const double* origin, int n_traits,
         launch_qtlsurv_null(p, ctx->stream);
         launch_qtlsurv_fit(p, ctx->stream);
         if (r0 + q.rn > (size_t)a.T) launch_qtlbin_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
+}
+
+// The variance-QTL single-locus scan on origin rows [n][M][4]: cnf2_qtlvar.h, cnf2_qtlvar_kernels.hip.  The masks, n_c and the
+// column image are the kernels of cnf2_qtl_kernels.hip, the rank rule the binary scan's kernel.  The traits and the covariates
+// are centred, each value minus the column's mean rounded once (qtl_centre_columns_once).
+int cnf2_qtl_scan_var(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
+                      const double* cov, int n_var, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
+                      double* coef_mean_out, double* coef_var_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out,
+                      double* ll0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_mean_out, ll0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    QtlCentred           centred;
+    RC_TRY(qtl_check(ctx, a, &mask));
+    if (!coef_var_out || !iters_out || !status_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if (n_var < 0 || n_var > std::min(a.K, QTLVAR_MAXV))
+        return fail(ctx, CNF2_ERR_ARG, "n_var must be 0 .. min(n_cov, %d)", QTLVAR_MAXV);
+    if (max_iter < 1 || max_iter > QTLVAR_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLVAR_MAX_ITER);
+    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
+    qtl_centre_columns_once(a.pheno, a.n, a.T, mask, centred.pheno);
+    a.pheno = centred.pheno.data();
+    if (a.K > 0) {
+        qtl_centre_columns_once(a.cov, a.n, a.K, mask, centred.cov);
+        a.cov = centred.cov.data();
+    }
+    const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
+    const int M = ctx->n_markers, C = ctx->n_chrom;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLBIN_TILE, true, true);
+    const size_t       n_tiles = map.n_tiles;
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, QTLVAR_NFIT * n_tiles, ctx->qtl_columns[QTL_CAP_VAR]);
+
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
+    QtlvarParams p;
+    memset(&p, 0, sizeof(p));
+    QtlbinParams& q = p.b;
+    QtlParams     g = qtl_gather_params(ctx, a, rt);   // ... and qtl_chrom_kernel reads and writes
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_qv_nc, (size_t)C, &g.nc));
+        RC_TRY(each(a.rank, ctx->d_qv_rank, (size_t)M, &q.rank));
+        RC_TRY(each(a.lod, ctx->d_qv_lod, cells * QTLVAR_NFIT, &q.lod));
+        RC_TRY(each(a.coef, ctx->d_qv_coef, cells * ds.ne, &q.coef));
+        RC_TRY(each(coef_var_out, ctx->d_qv_coefv, cells * ds.ne, &p.coef_var));
+        RC_TRY(each(iters_out, ctx->d_qv_iters, cells * QTLVAR_NFIT, &q.iters));
+        RC_TRY(each(status_out, ctx->d_qv_status, cells * QTLVAR_NFIT, &q.status));
+        RC_TRY(each(ll0_out, ctx->d_qv_ll0, (size_t)a.T * C, &q.ll0));
+        return each(a.pmax, ctx->d_qv_pmax, (size_t)a.P * a.T * C * QTLVAR_NFIT, &q.pmax);
+    };
+    RC_TRY(ctx->d_qv_map.ensure(ctx, map.image.size()));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_qv_keep.ensure(ctx, (size_t)M));
+    RC_TRY(ctx->d_qv_scan.ensure(ctx, (size_t)C));
+    RC_TRY(ctx->d_qv_null.ensure(ctx, (size_t)C * QTLVAR_NULLQ * rt));
+    if (a.P > 0) RC_TRY(ctx->d_qv_tilemax.ensure(ctx, n_tiles * QTLVAR_NFIT * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qv_map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = ds.nx;
+    g.origin = org.dev, g.cov = ctx->d_q_cov;
+    g.cs = ctx->d_qv_map, g.mchrom = ctx->d_qv_map + map.o_mchrom;
+    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol;
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
+    q.max_iter = max_iter, q.tol = tol;
+    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
+    q.tiles = ctx->d_qv_map + map.o_tiles, q.tile_start = ctx->d_qv_map + map.o_tstart, q.n_tiles = (int)n_tiles;
+    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = ctx->d_qv_keep, q.scan = ctx->d_qv_scan;
+    q.Y = ctx->d_q_Y, q.nullq = ctx->d_qv_null, q.tilemax = ctx->d_qv_tilemax, q.rstride = (int)rt;
+    p.n_var = n_var;
+
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_qv_scan.ptr, 0, (size_t)C * sizeof(int32_t), ctx->stream));     // (a chromosome without markers has no thread to say so)
+    launch_qtl_chrom(g, ctx->stream);
+    launch_qtlbin_rank(q, ctx->stream);
+    launch_qtlvar_threshold(p, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = g.r0 = (int)r0;
+        q.rn = g.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(g, ctx->stream);
+        launch_qtlvar_null(p, ctx->stream);
+        launch_qtlvar_fit(p, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtlvar_finish(p, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());
     return qtl_fetch_outputs(ctx, dev, outputs);

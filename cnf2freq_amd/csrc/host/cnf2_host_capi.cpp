@@ -14,6 +14,7 @@
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
 #include "../cnf2_qtlsurv.h"
+#include "../cnf2_qtlvar.h"
 #include "../cnf2_qtlboot.h"
 #include "../cnf2_qtlmv.h"
 #include "../cnf2_qtlplan.h"
@@ -441,6 +442,19 @@ int cnf2h_qtlsurv_fit(int n, const double* origin, const double* time, const dou
     if (!lod_out || !coef_out || !iters_out || !status_out || !rank_out || !ll0_out || !n_events_out || !n_used_out) return -2;
     return cnf2::qtlsurv_fit_serial(n, origin, time, status, n_cov, cov, c, additive != 0, imprint != 0, max_iter, tol, lod_out,
                                     coef_out, iters_out, status_out, rank_out, ll0_out, n_events_out, n_used_out)
+               ? 0
+               : -2;
+}
+
+// one (marker, column) cell of the variance-QTL scan: qtlvar_fit_serial (cnf2_qtlvar.h)
+int cnf2h_qtlvar_fit(int n, const double* origin, const double* y, int n_cov, const double* cov, int n_var, const uint8_t* c,
+                     int additive, int imprint, int max_iter, double tol, double* lod_out, double* coef_mean_out,
+                     double* coef_var_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out,
+                     int32_t* n_used_out)
+{
+    if (!lod_out || !coef_mean_out || !coef_var_out || !iters_out || !status_out || !rank_out || !ll0_out || !n_used_out) return -2;
+    return cnf2::qtlvar_fit_serial(n, origin, y, n_cov, cov, n_var, c, additive != 0, imprint != 0, max_iter, tol, lod_out,
+                                   coef_mean_out, coef_var_out, iters_out, status_out, rank_out, ll0_out, n_used_out)
                ? 0
                : -2;
 }

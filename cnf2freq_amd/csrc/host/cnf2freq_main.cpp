@@ -7,6 +7,7 @@
 //            [--qtl2 F [--qtl2-every S] --phenofile P [the --qtl-* options]]
 //            [--qtlx F --phenofile P [--qtl-imprint] [--qtl-interactive name,name] [the --qtl-* options]]
 //            [--qtlem F --phenofile P [--qtl-em-iterations N] [--qtl-em-tol X] [--qtl-imprint] [the --qtl-* options]]
+//            [--qtlvar F --phenofile P [--qtl-var-covariates name,name] [--qtl-var-iterations N] [--qtl-var-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlbin F --phenofile P [--qtl-binary-iterations N] [--qtl-binary-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlsurv F --phenofile P --qtl-surv-time NAME --qtl-surv-status NAME [--qtl-surv-iterations N] [--qtl-surv-tol X]
 //             [--qtl-imprint] [the --qtl-* options]]
@@ -128,6 +129,7 @@
 #include "../cnf2_qtlx.h"
 #include "../cnf2_qtlem.h"
 #include "../cnf2_qtlbin.h"
+#include "../cnf2_qtlvar.h"
 #include "../cnf2_qtlsurv.h"
 #include "../cnf2_qtlmv.h"
 #include "cnf2_readers.h"
@@ -191,6 +193,13 @@ struct Options {
     int         qtlbin_iterations = 50;  // --qtl-binary-iterations
     double      qtlbin_tol = 1e-7;       // --qtl-binary-tol
     bool        qtlbin_extra_set = false; // one of the two above was given
+    std::string qtlvar;                  // --qtlvar F: variance-QTL scan (with --phenofile and the --qtl-* options, --qtl-imprint)
+    std::string qtlvar_covariates;       // --qtl-var-covariates: names among --qtl-covariates, the variance design's
+    int         qtlvar_iterations = 50;  // --qtl-var-iterations
+    double      qtlvar_tol = 1e-7;       // --qtl-var-tol
+    bool        qtlvar_extra_set = false; // one of the three above was given
+    std::vector<int> qtlvar_cov_cols;    // columns of pheno: the variance covariates first, then the other covariates
+    int         qtlvar_n_var = 0;
     std::vector<int> qtlbin_trait_cols;  // columns of pheno: the traits whose values are all 0 or 1
     std::string qtlsurv;                 // --qtlsurv F: survival-trait scan (with --phenofile, the two column names and the --qtl-* options)
     std::string qtlsurv_time, qtlsurv_status;   // --qtl-surv-time, --qtl-surv-status: column names
@@ -353,6 +362,25 @@ static bool parse(int argc, char** argv, Options& o)
                 exit(2);
             }
         }
+        else if (a == "--qtlvar") o.qtlvar = val();
+        else if (a == "--qtl-var-covariates") {
+            o.qtlvar_covariates = val();
+            o.qtlvar_extra_set  = true;
+        }
+        else if (a == "--qtl-var-iterations") {
+            o.qtlvar_iterations = atoi(val().c_str());
+            o.qtlvar_extra_set  = true;
+        }
+        else if (a == "--qtl-var-tol") {
+            const std::string t = val();
+            char*             end = nullptr;
+            o.qtlvar_tol       = strtod(t.c_str(), &end);
+            o.qtlvar_extra_set = true;
+            if (t.empty() || *end != 0 || !std::isfinite(o.qtlvar_tol)) {
+                fprintf(stderr, "--qtl-var-tol needs a finite number, not \"%s\"\n", t.c_str());
+                exit(2);
+            }
+        }
         else if (a == "--qtlsurv") o.qtlsurv = val();
         else if (a == "--qtl-surv-time") {
             o.qtlsurv_time      = val();
@@ -418,6 +446,7 @@ static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
 static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlem_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlvar_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlsurv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
@@ -529,6 +558,9 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtlsurv.empty())
         qtlsurv_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
                                       !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty());
+    if (world == 1 && !opt.qtlvar.empty())
+        qtlvar_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
+                                     !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty() || !opt.qtlsurv.empty());
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1074,6 +1106,110 @@ static void qtlbin_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool row
         if (NP > 0) fprintf(out, "threshold\tlod\t%.5lf\t%.5lf\n", thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
     }
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlbin);
+}
+
+// --qtlvar after the last round (single GPU), and after the other scans where they are given: the variance-QTL scan
+// (cnf2_qtl_scan_var) of every trait, on the rows a cnf2_sweep_qtl left in the context -- theirs, or one of this function's own.
+// Traits are grouped by their pattern of missing values as for --qtl; permutations permute the phenotypes themselves.  The
+// file holds one table per trait, the tables separated by a blank line: a line "trait" and the name; per marker chromosome,
+// position, n, the rank, the joint, the mean and the variance LOD, the iterations and the status (0 = stopped by
+// --qtl-var-tol, 1 = by --qtl-var-iterations, 2 = breakdown) of the mean-only, the variance-only and the full fit, the full
+// fit's mean effects a, d (not with --qtl-additive), i (with --qtl-imprint) and then its log-variance effects in the same
+// order, "-" for a dropped one or a cell without a fit; with --qtl-permutations K > 0 three lines "threshold", the LOD's name
+// and its 5 % and 1 % genome-wide thresholds.
+static void qtlvar_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtlvar_cov_cols.size(), NP = opt.qtl_permutations;
+    const int NC = cnf2::qtlem_design(K, opt.qtl_additive, opt.qtl_imprint).ne, NF = cnf2::QTLVAR_NFIT;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtlvar_cov_cols[k]];
+            if (row[opt.qtlvar_cov_cols[k]] != row[opt.qtlvar_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | (opt.qtl_imprint ? CNF2_QTL_IMPRINT : 0) | CNF2_QTL_ORIGIN_DEVICE;
+    std::vector<double>  lod((size_t)T * M * NF), cm((size_t)T * M * NC), cv((size_t)T * M * NC), thr((size_t)T * NF * 2, 0.0);
+    std::vector<int32_t> rank((size_t)T * M), nused((size_t)T * C), iters((size_t)T * M * NF), status((size_t)T * M * NF);
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M * NF), fm((size_t)Tg * M * NC), fv((size_t)Tg * M * NC), l0((size_t)Tg * C),
+            pm((size_t)NP * Tg * C * NF);
+        std::vector<int32_t> rk(M), nu(C), it((size_t)Tg * M * NF), st((size_t)Tg * M * NF), perm((size_t)NP * N);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc;
+        if (!rows_kept) {          // the sweep, with the rows left in the context; its Haley-Knott scan is not reported
+            std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), l1((size_t)Tg * M), c1((size_t)Tg * M * 2), r1((size_t)Tg * C);
+            std::vector<int32_t> k1(M), m1(C);
+            rc = cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                l1.data(), c1.data(), k1.data(), r1.data(), m1.data(), nullptr, flags & CNF2_QTL_ADDITIVE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlvar: ") + cnf2_last_error(ctx));
+            rows_kept = true;
+        }
+        if (NP > 0) qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+        rc = cnf2_qtl_scan_var(ctx, N, nullptr, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, opt.qtlvar_n_var, NP,
+                               NP ? perm.data() : nullptr, opt.qtlvar_iterations, opt.qtlvar_tol, l.data(), fm.data(), fv.data(), it.data(),
+                               st.data(), rk.data(), l0.data(), nu.data(), NP ? pm.data() : nullptr, flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlvar: ") + cnf2_last_error(ctx));
+        for (int t = 0; t < Tg; t++) {
+            const size_t from = (size_t)t * M, to = (size_t)tr[t] * M;
+            std::copy(l.begin() + from * NF, l.begin() + (from + M) * NF, lod.begin() + to * NF);
+            std::copy(it.begin() + from * NF, it.begin() + (from + M) * NF, iters.begin() + to * NF);
+            std::copy(st.begin() + from * NF, st.begin() + (from + M) * NF, status.begin() + to * NF);
+            std::copy(fm.begin() + from * NC, fm.begin() + (from + M) * NC, cm.begin() + to * NC);
+            std::copy(fv.begin() + from * NC, fv.begin() + (from + M) * NC, cv.begin() + to * NC);
+            std::copy(rk.begin(), rk.end(), rank.begin() + to);
+            std::copy(nu.begin(), nu.end(), nused.begin() + (size_t)tr[t] * C);
+            for (int f = 0; f < NF && NP > 0; f++) {
+                std::vector<double> mx(NP, 0.0);
+                for (int p = 0; p < NP; p++)
+                    for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[(((size_t)p * Tg + t) * C + c) * NF + f]);
+                thr[((size_t)tr[t] * NF + f) * 2]     = qtl_threshold(mx, 0.05);
+                thr[((size_t)tr[t] * NF + f) * 2 + 1] = qtl_threshold(mx, 0.01);
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtlvar.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlvar);
+    static const char* const lod_names[3] = {"joint", "mean", "variance"};
+    for (int t = 0; t < T; t++) {
+        fprintf(out, "%strait\t%s\n", t ? "\n" : "", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str());
+        for (int c = 0; c < C; c++)
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const size_t at = (size_t)t * M + m;
+                fprintf(out, "%d\t%.5lf\t%d\t%d", c + 1, P.pos[m], (int)nused[(size_t)t * C + c], (int)rank[at]);
+                for (int f = 0; f < NF; f++) fprintf(out, "\t%.5lf", lod[at * NF + f]);
+                for (int f = 0; f < NF; f++) fprintf(out, "\t%d", (int)iters[at * NF + f]);
+                for (int f = 0; f < NF; f++) fprintf(out, "\t%d", (int)status[at * NF + f]);
+                for (int e = 0; e < 2 * NC; e++) {
+                    const double v = e < NC ? cm[at * NC + e] : cv[at * NC + e - NC];
+                    if (v != v) fprintf(out, "\t-");
+                    else fprintf(out, "\t%.5lf", v);
+                }
+                fprintf(out, "\n");
+            }
+        for (int f = 0; f < NF && NP > 0; f++)
+            fprintf(out, "threshold\t%s\t%.5lf\t%.5lf\n", lod_names[f], thr[((size_t)t * NF + f) * 2], thr[((size_t)t * NF + f) * 2 + 1]);
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlvar);
 }
 
 // --qtlsurv after the last round (single GPU), and after the other scans where they are given: the survival-trait scan
@@ -1665,6 +1801,33 @@ static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlmv);
 }
 
+// --qtl-var-covariates against --qtl-covariates, before anything runs: false with a message.  The variance covariates come
+// first in the order given, then the other covariates.
+static bool prepare_qtlvar(Options& opt)
+{
+    std::istringstream ss(opt.qtlvar_covariates);
+    std::string        missing;
+    for (std::string tok; std::getline(ss, tok, ',');) {
+        if (tok.empty()) continue;
+        const auto it = std::find(opt.pheno.columns.begin(), opt.pheno.columns.end(), tok);
+        const int  k  = it == opt.pheno.columns.end() ? -1 : (int)(it - opt.pheno.columns.begin());
+        if (k < 0 || std::find(opt.qtl_cov_cols.begin(), opt.qtl_cov_cols.end(), k) == opt.qtl_cov_cols.end()) missing += " " + tok;
+        else if (std::find(opt.qtlvar_cov_cols.begin(), opt.qtlvar_cov_cols.end(), k) == opt.qtlvar_cov_cols.end()) opt.qtlvar_cov_cols.push_back(k);
+    }
+    if (!missing.empty()) {
+        fprintf(stderr, "--qtl-var-covariates: not among --qtl-covariates:%s\n", missing.c_str());
+        return false;
+    }
+    opt.qtlvar_n_var = (int)opt.qtlvar_cov_cols.size();
+    if (opt.qtlvar_n_var > cnf2::QTLVAR_MAXV) {
+        fprintf(stderr, "--qtl-var-covariates: at most %d\n", cnf2::QTLVAR_MAXV);
+        return false;
+    }
+    for (int k : opt.qtl_cov_cols)
+        if (std::find(opt.qtlvar_cov_cols.begin(), opt.qtlvar_cov_cols.end(), k) == opt.qtlvar_cov_cols.end()) opt.qtlvar_cov_cols.push_back(k);
+    return true;
+}
+
 // --qtl-interactive against --qtl-covariates, and the design's width, before anything runs: false with a message
 static bool prepare_qtlx(Options& opt)
 {
@@ -2107,7 +2270,23 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-surv-iterations must be 1 .. %d\n", cnf2::QTLSURV_MAX_ITER);
         return 2;
     }
-    if (opt.qtlx.empty() && (opt.qtl_interactive_set || (opt.qtlx_extra_set && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlsurv.empty()))) {
+    if (opt.gpus > 1 && !opt.qtlvar.empty()) {
+        fprintf(stderr, "--qtlvar needs a single GPU (--gpus 1): a fit is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlvar.empty() && opt.qtlvar_extra_set) {
+        fprintf(stderr, "--qtl-var-covariates, --qtl-var-iterations and --qtl-var-tol need --qtlvar FILE\n");
+        return 2;
+    }
+    if (!opt.qtlvar.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlvar FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtlvar_iterations < 1 || opt.qtlvar_iterations > cnf2::QTLVAR_MAX_ITER) {
+        fprintf(stderr, "--qtl-var-iterations must be 1 .. %d\n", cnf2::QTLVAR_MAX_ITER);
+        return 2;
+    }
+    if (opt.qtlx.empty() && (opt.qtl_interactive_set || (opt.qtlx_extra_set && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty()))) {
         fprintf(stderr, "--qtl-imprint and --qtl-interactive need --qtlx FILE\n");
         return 2;
     }
@@ -2168,7 +2347,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
-        opt.qtlmv.empty() && opt.qtlsurv.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -2201,13 +2380,14 @@ int main(int argc, char** argv)
         return 2;
     }
     if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty() ||
-         !opt.qtlmv.empty() || !opt.qtlsurv.empty()) &&
+         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
     if (!opt.qtlmv.empty() && !prepare_qtlmv(opt)) return 2;
     if (!opt.qtlcof.empty() && !prepare_qtlcof(opt, P)) return 2;
     if (!opt.qtlbin.empty() && !prepare_qtlbin(opt)) return 2;
     if (!opt.qtlsurv.empty() && !prepare_qtlsurv(opt)) return 2;
+    if (!opt.qtlvar.empty() && !prepare_qtlvar(opt)) return 2;
     if (!opt.qtlx.empty() && !prepare_qtlx(opt)) return 2;
     if (!opt.qtl2.empty() && opt.qtl_cov_cols.size() > 6) {
         fprintf(stderr, "--qtl2: at most 6 covariates\n");

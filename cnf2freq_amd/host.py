@@ -16,7 +16,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
            "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
-           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit"]
+           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -69,6 +69,7 @@ def load():
         L.cnf2h_qtlem_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_qtlbin_fit.argtypes = [i32, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_qtlsurv_fit.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_qtlvar_fit.argtypes = [i32, vp, vp, i32, vp, i32, vp, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_kinship_sums.argtypes = [i32, i32, vp, vp, i32, i32, i32, vp, vp]
         L.cnf2h_qtl_cols_marker.argtypes = [i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
         L.cnf2h_qtl_bootstrap_counts.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
@@ -389,6 +390,32 @@ def qtlsurv_fit(origin, time, status, cov=None, c=None, additive=False, imprint=
         raise RuntimeError("cnf2h_qtlsurv_fit failed (%d)" % rc)
     return dict(lod=float(d[0]), coef=coef, iters=int(i5[0]), status=int(i5[1]), rank=int(i5[2]), ll0=float(d[1]),
                 n_events=int(i5[3]), n_used=int(i5[4]))
+
+
+def qtlvar_fit(origin, y, cov=None, n_var=0, c=None, additive=False, imprint=False, max_iter=50, tol=1e-7):
+    """cnf2h_qtlvar_fit: one (marker, column) cell of the variance-QTL scan (cnf2_qtlvar.h) on the marker's rows origin[n][4],
+    the trait y[n], covariates cov[n][K] of which the first n_var enter the variance design, and the chromosome's mask c[n]
+    (None: everybody).  A dict: lod[3] (joint, mean, variance), coef_mean[ne] and coef_var[ne] of the full fit, iters[3] and
+    status[3] by fit (mean-only, variance-only, full), rank, ll0, n_used.  CPU only."""
+    L = load()
+    o = np.ascontiguousarray(origin, np.float64)
+    y = np.ascontiguousarray(y, np.float64).reshape(-1)
+    n = len(y)
+    if o.shape != (n, 4):
+        raise ValueError("origin must be [n][4] and y [n]")
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    ne = 1 + (0 if additive else 1) + (1 if imprint else 0)
+    lod, cm, cv, d = np.zeros(3), np.zeros(ne), np.zeros(ne), np.zeros(1)
+    iters, status, i2 = np.zeros(3, np.int32), np.zeros(3, np.int32), np.zeros(2, np.int32)
+    rc = L.cnf2h_qtlvar_fit(n, _p(o), _p(y), K, None if K == 0 else _p(z), int(n_var), _p(m), int(additive), int(imprint),
+                            int(max_iter), float(tol), _p(lod), _p(cm), _p(cv), _p(iters), _p(status), _p(i2[0:1]), _p(d),
+                            _p(i2[1:2]))
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtlvar_fit failed (%d)" % rc)
+    return dict(lod=lod, coef_mean=cm, coef_var=cv, iters=iters, status=status, rank=int(i2[0]), ll0=float(d[0]),
+                n_used=int(i2[1]))
 
 
 def qtl_null_residuals(pheno, cov=None, use=None):

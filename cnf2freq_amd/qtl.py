@@ -20,6 +20,9 @@ scan_binary, read by thresholds and peaks in the same way.
 The survival-trait scan (Context.qtl_scan_surv, cnf2_qtl_scan_surv) fits Cox's proportional hazards regression of a
 time-to-event trait with censoring per marker: scan_surv, read by thresholds and peaks in the same way.
 
+The variance-QTL scan (Context.qtl_scan_var, cnf2_qtl_scan_var) fits a mean part and a log-variance part per marker and gives
+a joint, a mean and a variance LOD: scan_var, read by thresholds_var and peaks_var.
+
 The cofactor scan (Context.qtl_scan_cof, cnf2_qtl_scan_cof) is composite interval mapping: every marker fitted together with
 the loci found before, each left out inside its own window.  scan_cof with cofactor_windows asks whether there is a further
 QTL, fit_multi (read_multi) reads the multiple-QTL model -- full LOD, drop-one LODs, effects -- off one call, and
@@ -449,6 +452,66 @@ def scan_surv(ctx, time, status, cov=None, imprint=False, use=None, permutations
     return out
 
 
+VAR_KEYS = ("joint", "mean", "variance")
+
+
+def scan_var(ctx, pheno, cov=None, var_covariates=(), imprint=False, use=None, permutations=0, seed=0, strata=None, additive=False,
+             max_iter=50, tol=1e-7, rows=None):
+    """The variance-QTL scan of a whole cross on the context's uploaded pedigree: as scan_binary -- one origin sweep with the
+    rows left on the device (or `rows`, the tensor of origin_rows) and per pattern of missing phenotypes (NaN) one scan with
+    the pattern's own `use` -- with every (marker, trait) the double generalised linear model: the trait's mean on the
+    covariates and its log variance on the covariates of var_covariates (indices into cov's columns, at most three; they are
+    moved to the front of cov in the order given), both on the effects a, d (unless additive), i (with imprint).  Each cell
+    is fitted mean-only, variance-only and in full from the null fit, until the log-likelihood gains less than tol LOD or
+    max_iter iterations are done.  With permutations > 0 the raw phenotypes are permuted, within the strata of `strata`
+    (qtl.permutations): the null of no effect of either kind, which is exact for the joint LOD.  A dict: lod[T][M][3] and its
+    slices lod_joint, lod_mean, lod_variance [T][M], coef_mean and coef_var[T][M][len(coef_names)] of the full fit (coef_var
+    on the log-variance scale), coef_names, iters and status[T][M][3] by fit (mean-only, variance-only, full; 0 = stopped by
+    tol, 1 = by max_iter, 2 = breakdown), rank[T][M], ll0[T][C], n_used[T][C], perm_max[P][T][C][3] or None
+    (thresholds_var)."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    if not 1 <= int(max_iter) <= 1000:
+        raise ValueError("max_iter must be 1 .. 1000")
+    if not np.isfinite(tol):
+        raise ValueError("tol must be finite")
+    z = None if cov is None else np.asarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    vc = [int(k) for k in var_covariates]
+    if len(vc) > 3 or len(set(vc)) != len(vc) or any(not 0 <= k < K for k in vc):
+        raise ValueError("var_covariates must be at most three different columns of cov")
+    if vc:
+        z = z[:, vc + [k for k in range(K) if k not in vc]]
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    names = coef_names(0, imprint, additive)
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M, 3)), coef_mean=np.full((T, M, len(names)), np.nan),
+               coef_var=np.full((T, M, len(names)), np.nan), coef_names=names, iters=np.zeros((T, M, 3), np.int32),
+               status=np.zeros((T, M, 3), np.int32), rank=np.zeros((T, M), np.int32), ll0=np.zeros((T, C)),
+               n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C, 3)) if permutations else None)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    kw = dict(cov=z, n_var=len(vc), imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        perm = _permutations(n, permutations, seed, use=u, strata=strata) if permutations else None
+        got = ctx.qtl_scan_var_device(n, d_o.data_ptr(), yk, use=u, perm=perm, **kw)
+        for key in ("lod", "coef_mean", "coef_var", "iters", "status", "rank", "ll0", "n_used"):
+            out[key][cols] = got[key]
+        if permutations:
+            out["perm_max"][:, cols] = got["perm_max"]
+    for s, key in enumerate(VAR_KEYS):
+        out["lod_" + key] = out["lod"][..., s]
+    return out
+
+
 def cofactor_windows(cof, pos, chromstarts, window=0.0):
     """(excl_lo[Q], excl_hi[Q]) (int32) for scan_cof: per cofactor the markers of its chromosome within `window` map units
     of it, as the first and the last of them.  window = 0 gives the cofactor alone (and whatever shares its position)."""
@@ -624,6 +687,30 @@ def thresholdsx(perm_max, alpha=(0.05, 0.01)):
         th = thresholds(pm[..., s], alpha)
         out[key] = dict(genome=th["genome"], chromosome=th["chromosome"])
     return out
+
+
+def thresholds_var(perm_max, alpha=(0.05, 0.01)):
+    """From perm_max[P][T][C][3] of the variance-QTL scan: per LOD -- joint, mean, variance -- the dict thresholds() gives for
+    it, as thresholdsx does for its statistics.  The permutations are of the phenotype: the null of no effect of either kind,
+    exact for the joint LOD and conservative in neither direction for the other two."""
+    pm = np.asarray(perm_max, np.float64)
+    if pm.ndim != 4 or pm.shape[0] == 0 or pm.shape[3] != 3:
+        raise ValueError("perm_max must be [P][T][C][3] with P >= 1")
+    out = dict(alpha=tuple(alpha))
+    for s, key in enumerate(VAR_KEYS):
+        th = thresholds(pm[..., s], alpha)
+        out[key] = dict(genome=th["genome"], chromosome=th["chromosome"])
+    return out
+
+
+def peaks_var(out, pos, chromstarts, threshold, drop=1.5):
+    """peaks() on each of scan_var's three profiles: a dict joint / mean / variance of its lists.  threshold is a number,
+    one per trait, or a dict by those keys (e.g. the genome row of thresholds_var at one alpha)."""
+    lod = np.asarray(out["lod"], np.float64)
+    if lod.ndim != 3 or lod.shape[2] != 3:
+        raise ValueError("out must be scan_var's result: lod[T][M][3]")
+    thr = (lambda key: threshold[key]) if isinstance(threshold, dict) else (lambda key: threshold)
+    return {key: peaks(lod[..., s], pos, chromstarts, thr(key), drop) for s, key in enumerate(VAR_KEYS)}
 
 
 def quantile_index(P, alpha):

@@ -940,6 +940,50 @@ int cnf2_set_qtlsurv_columns(cnf2_ctx *ctx, int cap);
  * cells, and the context owns two work rows of n doubles per wave of the launch */
 int cnf2_set_qtlsurv_blocks(cnf2_ctx *ctx, int cap);
 
+/* Variance-QTL single-locus scan: the double generalised linear model of a quantitative trait on the origin rows -- a mean
+ * part and a log-variance part -- fitted per marker and phenotype column, observed and permuted, by maximum likelihood.  It
+ * asks whether a locus moves the trait's level, its variability, or either.  One definition for this header,
+ * cnf2freq_amd/csrc/cnf2_qtlvar.h (host and device), the kernels and tests/qtlvar_reference.py.
+ * origin, use, pheno, cov (0 <= K <= 8), perm, the mask c of a chromosome, n_c and the columns R = T (1 + P) are
+ * cnf2_qtl_scan's; traits and covariates are taken minus their means over the used individuals.  The variance covariates are
+ * the first n_var columns of cov, 0 <= n_var <= min(K, 3).
+ *   designs   mean x_i = [1, z_1 .. z_K, E], variance v_i = [1, z_1 .. z_nvar, E]; E is cnf2_qtl_scan_binary's: a = o[3] - o[0],
+ *             d = o[1] + o[2] (not with CNF2_QTL_ADDITIVE), i = o[1] - o[2] (only with CNF2_QTL_IMPRINT); ne effects
+ *   model     mu_i = x_i' beta, eta_i = v_i' gamma = log sigma_i^2;
+ *             l(beta, gamma) = -1/2 sum_i c_i [ log 2pi + eta_i + (y_i - mu_i)^2 exp(-eta_i) ]
+ *   fits      null (X0, V0) per chromosome and column; per marker fit 0 mean-only (X0 + E, V0), fit 1 variance-only
+ *             (X0, V0 + E), fit 2 full (X0 + E, V0 + E)
+ *   LODs      lod[0] joint = (l_full - l_null) / ln 10, lod[1] mean = (l_full - l_variance-only) / ln 10, lod[2] variance =
+ *             (l_full - l_mean-only) / ln 10; each max(0, .)
+ *   iteration from (beta_t, gamma_t, l_t): w_i = exp(-v_i' gamma_t), beta_{t+1} = (X'WX)^-1 X'Wy by a Cholesky factor;
+ *             r = y - X beta_{t+1}, q_i = w_i r_i^2, delta = (V' diag(q) V)^-1 V'(q - 1); gamma' = gamma_t + 2^-h delta for
+ *             h = 0 .. 8, the first h with (l_t - l(beta_{t+1}, gamma')) / ln 10 <= 1e-9 is taken and gives gamma_{t+1}, l_{t+1}.
+ *             (l_{t+1} - l_t) / ln 10 < tol stops with status 0 (a negative tol: never), else t + 1 = max_iter with status 1.
+ *   breakdown status 2, and (beta_t, gamma_t, l_t) are reported: a pivot of either factor that is not positive; a beta, gamma or
+ *             l that is not finite; an |eta_i| above 700; no h accepted.
+ *   rank      cnf2_qtl_scan_binary's rule on the mean design; an effect dropped there is dropped from the variance design too.
+ *             rank 0: lod 0, iters 0, status 0, coef NaN.
+ *   null fit  the same iteration on (X0, V0) from beta = 0, gamma = (log(sum c y^2 / n_c), 0, ..): at most 50 iterations,
+ *             stopped by a gain below 1e-13 LOD.  The three fits start from (beta0, 0; gamma0, 0) with l_0 = l0.
+ *   not scanned   a chromosome with n_c < (1 + K + ne) + (1 + n_var + ne) + 1 or without a factor of X0: rank 0; on a
+ *             chromosome a column that is constant there, or whose null fit does not stop by its tolerance or breaks down.
+ *             Then lod 0, coef NaN, iters 0, status 0, ll0 0.
+ * max_iter is 1 .. 1000 and tol finite.  Outputs (host memory, or device memory with CNF2_OUT_DEVICE): lod_out [T][M][3],
+ * coef_mean_out and coef_var_out [T][M][ne] of the full fit (coef_var on the log-variance scale; NaN where dropped or not
+ * fitted), iters_out and status_out [T][M][3] int32 by fit, rank_out [M], ll0_out [T][C], n_used_out [C], perm_max_out
+ * [P][T][C][3] (the permuted columns contribute only there; perm permutes the phenotype only).
+ * CNF2_QTL_ORIGIN_DEVICE is cnf2_qtl_scan_binary's.  Everything cnf2_qtl_scan refuses is refused, and so are n_var, max_iter
+ * and tol out of range: CNF2_ERR_ARG, and nothing is written.
+ * One wavefront owns a cell: its three fits in sequence, each from start to stop; its lanes stride the individuals in
+ * ascending order, the sums of a pass are added across the wave in a fixed order and every lane takes the same step.  No
+ * atomics and no split of the individuals: a call gives the same bits every time, for every column cap (the setter below,
+ * 0 = no cap) and from host or device rows. */
+int cnf2_qtl_scan_var(cnf2_ctx *ctx, int n, const double *origin, int n_traits, const double *pheno, const uint8_t *use,
+                      int n_cov, const double *cov, int n_var, int n_perm, const int32_t *perm, int max_iter, double tol,
+                      double *lod_out, double *coef_mean_out, double *coef_var_out, int32_t *iters_out, int32_t *status_out,
+                      int32_t *rank_out, double *ll0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
+int cnf2_set_qtlvar_columns(cnf2_ctx *ctx, int cap);
+
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU
  * (closed forms: cnf2_haplos, cnf2_infprobs_rows) and reduced per individual as the reference does after every

@@ -200,6 +200,17 @@ int cnf2h_qtlsurv_fit(int n, const double *origin, const double *time, const dou
                       double *coef_out, int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *ll0_out,
                       int32_t *n_events_out, int32_t *n_used_out);
 
+/* One (marker, phenotype column) cell of the variance-QTL scan (cnf2_qtl_scan_var of cnf2hip.h) on the host, by the functions
+ * of cnf2freq_amd/csrc/cnf2_qtlvar.h that the kernels use, the individuals in ascending order and one pass per step:
+ * origin[n][4] the marker's rows, y[n], cov[n][n_cov] of which the first n_var enter the variance design, c[n] the
+ * chromosome's mask.  lod_out [3], coef_mean_out and coef_var_out [ne], iters_out and status_out [3], rank_out, ll0_out and
+ * n_used_out receive one cell.  -2: a bad argument (n_cov above 8, n_var outside 0 .. min(n_cov, 3), max_iter outside
+ * 1 .. 1000, a tol that is not finite). */
+int cnf2h_qtlvar_fit(int n, const double *origin, const double *y, int n_cov, const double *cov, int n_var, const uint8_t *c,
+                     int additive, int imprint, int max_iter, double tol, double *lod_out, double *coef_mean_out,
+                     double *coef_var_out, int32_t *iters_out, int32_t *status_out, int32_t *rank_out, double *ll0_out,
+                     int32_t *n_used_out);
+
 /* cnf2_kinship_sums (cnf2hip.h) on the CPU, for tests and for callers without a GPU: sum_out[n][n] = sum over the markers of
  * the chromosomes chrom_begin .. chrom_end-1 of a_i(m) a_j(m), a = origin[3] - origin[0], on origin[n][n_markers][4] and the
  * map's chromstarts[n_chrom + 1]; *n_markers_out the number of those markers.  The markers are added in ascending order
