@@ -30,6 +30,7 @@ QTL_ADDITIVE = 1 << 22            # cnf2_qtl_scan / cnf2_sweep_qtl: the dominanc
 QTL_ORIGIN_DEVICE = 1 << 23       # cnf2_qtl_scan: the origin rows are a device pointer
 QTL_REG_DEVICE = 1 << 28          # cnf2_qtl_scan_cols: the regressors are a device pointer
 QTL_IMPRINT = 1 << 25             # cnf2_qtl_scanx: the design gets the imprinting effect i = o[1] - o[2]
+QTL_STATE_DEVICE = 1 << 29        # cnf2_qtl_scan_imp: the sampled states are a device pointer
 NO_UNIFORM_PACK = 1 << 26         # crosses of inbred lines: one window to a wave, not four windows of a chromosome (A/B, cross-check)
 NO_UNIFORM_PACK8 = 1 << 27        # crosses of inbred lines: packed windows four to a wave only, not eight windows of a chromosome (A/B, cross-check)
 NO_LINE_RECORDS = 1 << 24         # crosses of inbred lines: every window's emission terms from its own rows, not from the launch's line records (A/B, cross-check)
@@ -57,6 +58,7 @@ SYMBOLS = [
     "cnf2_qtl_scan_var", "cnf2_set_qtlvar_columns",
     "cnf2_qtl_scan_cof", "cnf2_set_qtlcof_columns", "cnf2_qtl_kept_rows",
     "cnf2_kinship_sums", "cnf2_qtl_scan_cols", "cnf2_qtl_scan_boot", "cnf2_qtl_scan_mv", "cnf2_set_qtlmv_groups",
+    "cnf2_qtl_scan_imp", "cnf2_set_qtlimp_columns",
 ]
 
 
@@ -142,6 +144,8 @@ def load():
         L.cnf2_qtl_scan_cols.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_boot.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_mv.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_qtl_scan_imp.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_set_qtlimp_columns.argtypes = [vp, i32]
         L.cnf2_set_qtlmv_groups.argtypes = [vp, i32]
         L.cnf2_qtl_scan_em.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, i32, C.c_double,
                                        vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
@@ -708,6 +712,55 @@ class Context:
                                         opt(use), K, opt(cov), P, opt(perm), C.c_void_p(d_lod), C.c_void_p(d_coef),
                                         C.c_void_p(d_rank), C.c_void_p(d_rss0), C.c_void_p(d_n_used),
                                         C.c_void_p(d_perm_max) if d_perm_max else None, flags | OUT_DEVICE), "cnf2_sweep_qtl")
+
+    # -- multiple-imputation scan ------------------------------------------------
+    def set_qtlimp_columns(self, cap):
+        """Cap on the phenotype columns per tile of qtl_scan_imp (0 = what memory allows); results do not depend on it."""
+        self._chk(self.L.cnf2_set_qtlimp_columns(self.h, cap), "cnf2_set_qtlimp_columns")
+
+    def sweep_sample_device(self, ind_begin, ind_end, draws, seed, d_factors, d_loglik, d_state, d_shift, d_logp=None, flags=0):
+        """cnf2_sweep_sample in its device-pointer form (ints; d_logp may be None): the states stay on the GPU, where
+        qtl_scan_imp_device reads them in place."""
+        self._chk(self.L.cnf2_sweep_sample(self.h, ind_begin, ind_end, draws, int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(d_factors),
+                                           C.c_void_p(d_loglik), C.c_void_p(d_state), C.c_void_p(d_shift),
+                                           C.c_void_p(d_logp) if d_logp else None, flags | OUT_DEVICE), "cnf2_sweep_sample")
+
+    QTLIMP_KEYS = ("lod", "coef", "rank", "rss0", "n_used", "perm_max", "draw_lod")
+
+    def _qtlimp_call(self, n, D, state_ptr, pheno, cov, use, perm, draw_lods, flags, out=None):
+        """cnf2_qtl_scan_imp on the states behind state_ptr; out = None: new host arrays, else the outputs (arrays, or with
+        OUT_DEVICE in flags ints, the device pointers; perm_max / draw_lod None where not asked for)"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        if out is None:
+            out = self._qtl_outputs(T, P)
+            out["draw_lod"] = np.zeros((D, T, self.n_markers)) if draw_lods else None
+        opt = lambda a: None if a is None else _p(a)
+        ptr = (lambda a: C.c_void_p(a) if a else None) if flags & OUT_DEVICE else opt
+        self._chk(self.L.cnf2_qtl_scan_imp(self.h, n, D, state_ptr, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm),
+                                           *[ptr(out.get(k)) for k in self.QTLIMP_KEYS], flags), "cnf2_qtl_scan_imp")
+        return out
+
+    def qtl_scan_imp(self, state, pheno, cov=None, use=None, perm=None, additive=False, draw_lods=False, out=None):
+        """cnf2_qtl_scan_imp on host states state[n][D][M] (uint8, what sweep_sample returns): the model of qtl_scan fitted to
+        the hard origin classes of every draw and the draws combined per (marker, column) on the likelihood scale --
+        lod = log10 of the mean of 10^lod_d, coef the mean of the draws' effects weighted with 10^lod_d (NaN once a draw drops
+        the column), rank the smallest over the draws.  The dict of qtl_scan (perm_max[P][T][C] the largest combined LOD) plus
+        draw_lod[D][T][M], the draws' own profiles, with draw_lods (else None).  The model: include/cnf2hip.h."""
+        state = np.ascontiguousarray(state, np.uint8)
+        if state.ndim != 3 or state.shape[2] != self.n_markers:
+            raise ValueError("state must be [n][D][%d]" % self.n_markers)
+        return self._qtlimp_call(state.shape[0], state.shape[1], _p(state), pheno, cov, use, perm, draw_lods,
+                                 QTL_ADDITIVE if additive else 0, out)
+
+    def qtl_scan_imp_device(self, n, draws, d_state, pheno, cov=None, use=None, perm=None, additive=False, draw_lods=False,
+                            d_out=None):
+        """The same on device states (d_state: an int, the pointer of n x draws x M bytes, e.g. the tensor a
+        sweep_sample_device call filled); they are read in place.  Phenotypes are host arrays.  With d_out (a dict of device
+        pointers under QTLIMP_KEYS; perm_max None without permutations, draw_lod None or absent when not wanted) the outputs
+        are written there and the call returns d_out; else host arrays as qtl_scan_imp."""
+        flags = QTL_STATE_DEVICE | (QTL_ADDITIVE if additive else 0) | (OUT_DEVICE if d_out is not None else 0)
+        return self._qtlimp_call(n, draws, C.c_void_p(d_state), pheno, cov, use, perm, draw_lods, flags, d_out)
 
     # -- kinship sums and the column scan (the two halves of a mixed-model scan: cnf2freq_amd/qtl.py) ----
     def kinship_sums(self, origin, chrom_begin=0, chrom_end=None):

@@ -33,6 +33,7 @@
 #include "cnf2_qtlcols.h"
 #include "cnf2_qtlboot.h"
 #include "cnf2_qtlmv.h"
+#include "cnf2_qtlimp.h"
 
 using namespace cnf2;
 
@@ -83,7 +84,7 @@ struct DevBuf {
 
 // the scans whose column tile the caller can cap (cnf2_set_*_columns); the column scan shares the single scan's, and the
 // multi-trait scan's cap counts groups (cnf2_set_qtlmv_groups)
-enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_SURV, QTL_CAP_VAR, QTL_CAP_COUNT };
+enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_SURV, QTL_CAP_VAR, QTL_CAP_IMP, QTL_CAP_COUNT };
 
 struct cnf2_ctx {
     int         device = -1;
@@ -244,6 +245,13 @@ struct cnf2_ctx {
     // the staged inputs, the masks, the factors, the marker records and the image are the single scan's buffers
     DevBuf<double>  d_qm_rec, d_qm_tilemax, d_qm_lod, d_qm_pmax;
     DevBuf<int32_t> d_qm_map, d_qm_nc, d_qm_rank, d_qm_trank;   // d_qm_map: as d_q_map
+
+    // multiple-imputation scan (cnf2_qtl_scan_imp): staged host states, the marker records of every draw, the two words of the
+    // check, the tile maxima, staged outputs; the staged inputs, the masks, the factors, the image and the null fit are the
+    // single scan's buffers
+    DevBuf<uint8_t> d_qi_state;
+    DevBuf<double>  d_qi_mkd, d_qi_tilemax, d_qi_lod, d_qi_coef, d_qi_rss0, d_qi_pmax, d_qi_draw;
+    DevBuf<int32_t> d_qi_map, d_qi_bad, d_qi_nc, d_qi_rank;   // d_qi_map: as d_q_map
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -491,6 +499,7 @@ int cnf2_set_qtlbin_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QT
 int cnf2_set_qtlmv_groups(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_MV, cap); }
 int cnf2_set_qtlsurv_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_SURV, cap); }
 int cnf2_set_qtlvar_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_VAR, cap); }
+int cnf2_set_qtlimp_columns(cnf2_ctx* ctx, int cap) { return set_columns(ctx, QTL_CAP_IMP, cap); }
 int cnf2_set_qtlsurv_blocks(cnf2_ctx* ctx, int cap)
 {
     if (!ctx) return CNF2_ERR_ARG;
@@ -1859,6 +1868,102 @@ int cnf2_sweep_qtl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_ou
     QtlOrigin org;
     org.dev = ctx->d_org;
     return qtl_scan_impl(ctx, org, a, mask, flags);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Multiple-imputation scan (cnf2_qtlimp.h, cnf2_qtlimp_kernels.hip), in the scans' order of steps.  The states are checked
+// before anything is written: host states here, device states by a kernel once every allocation has succeeded.
+// ------------------------------------------------------------------------------------------------
+int cnf2_qtl_scan_imp(cnf2_ctx* ctx, int n, int n_draws, const uint8_t* state, int n_traits, const double* pheno, const uint8_t* use,
+                      int n_cov, const double* cov, int n_perm, const int32_t* perm, double* lod_out, double* coef_out,
+                      int32_t* rank_out, double* rss0_out, int32_t* n_used_out, double* perm_max_out, double* draw_lod_out,
+                      uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    QtlCentred           centred;
+    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
+    if (n_draws < 1 || n_draws > QTLIMP_MAXD) return fail(ctx, CNF2_ERR_ARG, "n_draws must be 1 .. %d", QTLIMP_MAXD);
+    if (!state) return fail(ctx, CNF2_ERR_ARG, "state is NULL");
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0, state_dev = (flags & CNF2_QTL_STATE_DEVICE) != 0;
+    const int    M = ctx->n_markers, C = ctx->n_chrom, nx = a.K + 1, D = n_draws;
+    const size_t n_state = (size_t)n * D * M;
+    if ((size_t)D * a.T * (size_t)M > (size_t)1 << 40) return fail(ctx, CNF2_ERR_ARG, "too many draws, traits or markers");
+    if (!state_dev)
+        for (int i = 0; i < n; i++)
+            for (int c = 0; c < C; c++) {
+                const int first = ctx->chromstarts[c];
+                switch (qtlimp_check_cells(state + (size_t)i * D * M, D, M, first, ctx->chromstarts[c + 1] - first)) {
+                case QTLIMP_STATE_RANGE: return fail(ctx, CNF2_ERR_ARG, "a state of individual %d on chromosome %d is in 64 .. 254", i, c);
+                case QTLIMP_STATE_PARTIAL:
+                    return fail(ctx, CNF2_ERR_ARG, "individual %d is skipped (0xFF) in some cells of chromosome %d and not in all", i, c);
+                }
+            }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1);
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, 0, ctx->qtl_columns[QTL_CAP_IMP]);
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, 16, true, true);
+
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
+    QtlImpParams p;
+    memset(&p, 0, sizeof(p));
+    QtlParams& q = p.q;
+    q = qtl_gather_params(ctx, a, rt);
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, ctx->d_qi_nc, (size_t)C, &q.nc));
+        RC_TRY(each(a.rank, ctx->d_qi_rank, (size_t)M, &q.rank));
+        RC_TRY(each(a.lod, ctx->d_qi_lod, (size_t)a.T * M, &q.lod));
+        RC_TRY(each(a.coef, ctx->d_qi_coef, (size_t)a.T * M * 2, &q.coef));
+        RC_TRY(each(a.rss0, ctx->d_qi_rss0, (size_t)a.T * C, &q.rss0));
+        RC_TRY(each(a.pmax, ctx->d_qi_pmax, (size_t)a.P * a.T * C, &q.pmax));
+        return each(draw_lod_out, ctx->d_qi_draw, (size_t)D * a.T * M, &p.draw_lod);
+    };
+    if (!state_dev) RC_TRY(ctx->d_qi_state.ensure(ctx, n_state));
+    RC_TRY(ctx->d_qi_map.ensure(ctx, map.image.size()));
+    RC_TRY(ctx->d_qi_bad.ensure(ctx, 2));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_qi_mkd.ensure(ctx, (size_t)D * M * QTL_MK));
+    RC_TRY(ctx->d_q_null.ensure(ctx, (size_t)C * (nx + 1) * rt));
+    if (a.P > 0) RC_TRY(ctx->d_qi_tilemax.ensure(ctx, map.n_tiles * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    if (!state_dev) RC_TRY(qtl_upload(ctx, ctx->d_qi_state, state, n_state));
+    RC_TRY(qtl_upload(ctx, ctx->d_qi_map, map.image.data(), map.image.size()));
+
+    q.M = M, q.C = C, q.P = a.P, q.K = a.K, q.nx = nx;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
+    q.cov = ctx->d_q_cov;
+    q.cs = ctx->d_qi_map, q.mchrom = ctx->d_qi_map + map.o_mchrom;
+    q.tiles = ctx->d_qi_map + map.o_tiles, q.tile_start = ctx->d_qi_map + map.o_tstart, q.n_tiles = (int)map.n_tiles;
+    q.cmask = ctx->d_q_cmask, q.chol = ctx->d_q_chol;
+    q.nullq = ctx->d_q_null, q.tilemax = ctx->d_qi_tilemax;
+    p.D = D, p.state = state_dev ? state : ctx->d_qi_state.ptr, p.mkd = ctx->d_qi_mkd, p.bad = ctx->d_qi_bad;
+
+    if (state_dev) {
+        int32_t bad[2] = {0, 0};
+        HIP_TRY(ctx, hipMemsetAsync(p.bad, 0, sizeof(bad), ctx->stream));
+        launch_qtlimp_check(p, ctx->stream);
+        HIP_TRY(ctx, hipGetLastError());
+        HIP_TRY(ctx, hipMemcpyAsync(bad, p.bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (bad[0]) return fail(ctx, CNF2_ERR_ARG, "a state is in 64 .. 254");
+        if (bad[1]) return fail(ctx, CNF2_ERR_ARG, "an individual is skipped (0xFF) in some cells of a chromosome and not in all");
+    }
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    launch_qtlimp_chrom(p, ctx->stream);
+    launch_qtlimp_design(p, ctx->stream);
+    launch_qtlimp_rank(p, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = (int)r0;
+        q.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(q, ctx->stream);
+        launch_qtl_null(q, ctx->stream);
+        launch_qtlimp_scan(p, ctx->stream);
+        if (r0 + q.rn > (size_t)a.T) launch_qtl_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -16,6 +16,7 @@
 #include "../cnf2_qtlsurv.h"
 #include "../cnf2_qtlvar.h"
 #include "../cnf2_qtlboot.h"
+#include "../cnf2_qtlimp.h"
 #include "../cnf2_qtlmv.h"
 #include "../cnf2_qtlplan.h"
 #include "cnf2_remap.h"
@@ -564,6 +565,20 @@ int cnf2h_qtl_boot_marker(int n, const double* origin, int n_traits, const doubl
         return -2;
     return cnf2::qtlboot_marker_serial(n, origin, n_traits, y, n_cov, cov, c, count, additive != 0, lod_out, coef_out, rank_out,
                                        rss0_out, n_bc_out)
+               ? 0
+               : -2;
+}
+
+// one marker's combined cells of cnf2_qtl_scan_imp: qtlimp_marker_serial (cnf2_qtlimp.h)
+int cnf2h_qtlimp_marker(int n, int n_draws, const uint8_t* state, int n_traits, const double* y, int n_cov, const double* cov,
+                        const uint8_t* c, int additive, double* lod_out, double* coef_out, int32_t* rank_out, double* rss0_out,
+                        int32_t* n_used_out, double* draw_lod_out)
+{
+    if (n < 1 || !state || n_traits < 1 || !y || n_cov < 0 || n_cov > cnf2::QTL_MAXK || (n_cov > 0 && !cov) || !c || !lod_out ||
+        !coef_out || !rank_out || !rss0_out || !n_used_out)
+        return -2;
+    return cnf2::qtlimp_marker_serial(n, n_draws, state, n_traits, y, n_cov, cov, c, additive != 0, lod_out, coef_out, rank_out,
+                                      rss0_out, n_used_out, draw_lod_out)
                ? 0
                : -2;
 }

@@ -14,6 +14,7 @@
 //            [--qtlcof F --phenofile P --qtl-cofactors i,j,k [--qtl-window X] [the --qtl-* options]]
 //            [--qtlboot F --phenofile P --qtl-boot-chrom C [--qtl-boot-replicates B] [--qtl-covariates, --qtl-seed, --qtl-additive]]
 //            [--qtlmv F --phenofile P [--qtl-traits name,name,..] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
+//            [--qtlimp F --phenofile P [--qtl-imp-draws D] [--qtl-imp-seed S] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
 // --deserialize of an earlier dump, then --count rounds of which the first only dumps and every later one runs a
@@ -105,6 +106,11 @@
 // not flags of the reference): the multi-trait scan (cnf2_qtl_scan_mv) -- the joint LOD of the named traits (default: every
 // trait of the table; 16 at most) at every marker, on the individuals that have all of them -- after the other scans where
 // they are given, on the same sweep's rows.  F is described at qtlmv_scan below.
+// --qtlimp F [--qtl-imp-draws D] [--qtl-imp-seed S] (with --phenofile and --qtl-covariates, --qtl-permutations, --qtl-seed,
+// --qtl-additive; not flags of the reference): the multiple-imputation scan (cnf2_qtl_scan_imp) -- --qtl's model on D
+// (default 16, at most 1024) inheritance paths per individual drawn from the posterior with seed S (default 0;
+// cnf2_sweep_sample), combined on the likelihood scale -- after the other scans, on a sampling sweep of its own.  F has the
+// format of --qtl's file.
 // --output is the same with or without it.  Single GPU only.
 //
 // Everything numeric goes through the C ABI of include/cnf2hip.h (host bookkeeping in cnf2_engine.cpp); this program
@@ -220,6 +226,10 @@ struct Options {
     std::string qtl_traits;              // --qtl-traits name,name,..: the traits scanned jointly (default: all)
     bool        qtl_traits_set = false;
     std::vector<int> qtlmv_trait_cols;   // columns of pheno, in the order they are scanned
+    std::string qtlimp;                  // --qtlimp F: multiple-imputation scan (with --phenofile and the shared --qtl-* options)
+    int         qtl_imp_draws = 16;      // --qtl-imp-draws D
+    unsigned long long qtl_imp_seed = 0; // --qtl-imp-seed S
+    bool        qtlimp_extra_set = false; // one of the two above was given
     std::vector<int> qtlx_cov_cols;      // columns of pheno: the interactive covariates first, then the others
     int         qtlx_n_int = 0;
     PhenoTable  pheno;                   // P as read (main, before any rank starts)
@@ -335,6 +345,15 @@ static bool parse(int argc, char** argv, Options& o)
         }
         else if (a == "--qtlboot") o.qtlboot = val();
         else if (a == "--qtlmv") o.qtlmv = val();
+        else if (a == "--qtlimp") o.qtlimp = val();
+        else if (a == "--qtl-imp-draws") {
+            o.qtl_imp_draws    = atoi(val().c_str());
+            o.qtlimp_extra_set = true;
+        }
+        else if (a == "--qtl-imp-seed") {
+            o.qtl_imp_seed     = strtoull(val().c_str(), nullptr, 0);
+            o.qtlimp_extra_set = true;
+        }
         else if (a == "--qtl-traits") {
             o.qtl_traits     = val();
             o.qtl_traits_set = true;
@@ -451,6 +470,7 @@ static void qtlsurv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool ro
 static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlimp_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -561,6 +581,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtlvar.empty())
         qtlvar_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
                                      !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty() || !opt.qtlsurv.empty());
+    if (world == 1 && !opt.qtlimp.empty()) qtlimp_scan(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
         fprintf(stderr, "%s\n", e.what());
@@ -1961,6 +1982,105 @@ static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtl);
 }
 
+// --qtlimp after the last round (single GPU) and after the other scans: one sampling sweep (cnf2_sweep_sample) of
+// --qtl-imp-draws paths per individual with --qtl-imp-seed, then per pattern of missing values the multiple-imputation scan
+// (cnf2_qtl_scan_imp) of its traits on those states, and with --qtl-permutations one more on the permuted residuals of the null
+// model, whose maxima are taken over the combined profile.  The table, the grouping and the file are --qtl's (qtl_scan above).
+static void qtlimp_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations, D = opt.qtl_imp_draws;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::vector<uint8_t> st((size_t)N * D * M);
+    {
+        std::vector<double>  f((size_t)N * C * 8), ll((size_t)N * C);
+        std::vector<int32_t> sh((size_t)N * D * C);
+        if (cnf2_sweep_sample(ctx, 0, N, D, (uint64_t)opt.qtl_imp_seed, f.data(), ll.data(), st.data(), sh.data(), nullptr, 0) != CNF2_OK)
+            throw EngineError(CNF2_ERR_STATE, std::string("--qtlimp: ") + cnf2_last_error(ctx));
+    }
+    std::vector<double>  lod((size_t)T * M, 0.0), coef((size_t)T * M * 2, NAN), thr((size_t)T * 2, 0.0);
+    std::vector<int32_t> rank0(M, 0), nused0(C, 0);
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = base[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    const uint32_t flags = opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0;
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M), cf((size_t)Tg * M * 2), rss((size_t)Tg * C);
+        std::vector<int32_t> rk(M), nu(C);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc = cnf2_qtl_scan_imp(ctx, N, D, st.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr, l.data(),
+                                   cf.data(), rk.data(), rss.data(), nu.data(), nullptr, nullptr, flags);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlimp: ") + cnf2_last_error(ctx));
+        if (tr[0] == 0) rank0 = rk, nused0 = nu;                   // the file's design columns are the first trait's
+        for (int t = 0; t < Tg; t++) {
+            std::copy(l.begin() + (size_t)t * M, l.begin() + (size_t)(t + 1) * M, lod.begin() + (size_t)tr[t] * M);
+            std::copy(cf.begin() + (size_t)t * M * 2, cf.begin() + (size_t)(t + 1) * M * 2, coef.begin() + (size_t)tr[t] * M * 2);
+        }
+        if (NP > 0) {
+            std::vector<int32_t> perm((size_t)NP * N);
+            std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * C);
+            qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+            const int n_u = (int)std::count(u.begin(), u.end(), (uint8_t)1);
+            if (n_u >= K + 4 && !qtl_null_residuals(N, Tg, yg.data(), K, K ? cov.data() : nullptr, u.data(), res.data()))
+                throw EngineError(CNF2_ERR_ARG, "--qtl-permutations: the null design (intercept and covariates) of the individuals used for " +
+                                                    opt.pheno.columns[opt.qtl_trait_cols[tr[0]]] + " has no full rank");
+            rc = cnf2_qtl_scan_imp(ctx, N, D, st.data(), Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, NP, perm.data(), l.data(),
+                                   cf.data(), rk.data(), rss.data(), nu.data(), pm.data(), nullptr, flags);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlimp permutations: ") + cnf2_last_error(ctx));
+            for (int t = 0; t < Tg; t++) {
+                std::vector<double> mx(NP, 0.0);
+                for (int p = 0; p < NP; p++)
+                    for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[((size_t)p * Tg + t) * C + c]);
+                thr[(size_t)tr[t] * 2]     = qtl_threshold(mx, 0.05);
+                thr[(size_t)tr[t] * 2 + 1] = qtl_threshold(mx, 0.01);
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtlimp.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlimp);
+    auto effect = [&](double v) {
+        if (v != v) fprintf(out, "\t-");
+        else fprintf(out, "\t%.5lf", v);
+    };
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+            fprintf(out, "%d\t%.5lf\t%d\t%d", c + 1, P.pos[m], (int)nused0[c], (int)rank0[m]);
+            for (int t = 0; t < T; t++) {
+                fprintf(out, "\t%.5lf", lod[(size_t)t * M + m]);
+                effect(coef[((size_t)t * M + m) * 2]);
+                effect(coef[((size_t)t * M + m) * 2 + 1]);
+            }
+            fprintf(out, "\n");
+        }
+    if (NP > 0) {
+        fprintf(out, "\n");
+        for (int t = 0; t < T; t++)
+            fprintf(out, "%s\t%.5lf\t%.5lf\n", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str(), thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlimp);
+}
+
 // --qtl2 after the last round (single GPU), and after --qtl where both are given: the pair scan (cnf2_qtl_scan2) of every
 // --qtl2-every-th marker on the rows a cnf2_sweep_qtl left in the context -- --qtl's, or one of this function's own.  Traits
 // are grouped by their pattern of missing values as for --qtl.  The file holds, per trait and chromosome pair with a pair of
@@ -2338,6 +2458,22 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtlmv FILE needs --phenofile FILE\n");
         return 2;
     }
+    if (opt.gpus > 1 && !opt.qtlimp.empty()) {
+        fprintf(stderr, "--qtlimp needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlimp.empty() && opt.qtlimp_extra_set) {
+        fprintf(stderr, "--qtl-imp-draws and --qtl-imp-seed need --qtlimp FILE\n");
+        return 2;
+    }
+    if (!opt.qtlimp.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlimp FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtl_imp_draws < 1 || opt.qtl_imp_draws > 1024) {
+        fprintf(stderr, "--qtl-imp-draws must be 1 .. 1024\n");
+        return 2;
+    }
     if (opt.qtl_boot_replicates < 1 || opt.qtl_boot_replicates > 1000000) {
         fprintf(stderr, "--qtl-boot-replicates must be 1 .. 1000000\n");
         return 2;
@@ -2347,7 +2483,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
-        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -2380,7 +2516,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty() ||
-         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty()) &&
+         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty() || !opt.qtlimp.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
     if (!opt.qtlmv.empty() && !prepare_qtlmv(opt)) return 2;

@@ -16,7 +16,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
            "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
-           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit"]
+           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit", "cnf2h_qtlimp_marker"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -81,6 +81,7 @@ def load():
         L.cnf2h_qtlmv_marker.argtypes = [i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp]
         L.cnf2h_qtl_group_tile.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32]
         L.cnf2h_qtl_group_tile.restype = C.c_int64
+        L.cnf2h_qtlimp_marker.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -249,6 +250,31 @@ def qtl_boot_marker(origin, y, count, cov=None, c=None, additive=False):
     if rc != 0:
         raise ValueError("cnf2h_qtl_boot_marker refused its arguments (%d)" % rc)
     return dict(lod=lod, coef=coef, rank=int(rank[0]), rss0=rss0, n_bc=int(n_bc[0]))
+
+
+def qtlimp_marker(state, y, cov=None, c=None, additive=False):
+    """cnf2h_qtlimp_marker: one marker of the multiple-imputation scan (cnf2_qtl_scan_imp) on the marker's sampled states
+    state[n][D] (uint8), the columns y[n][T] and cov[n][K] as they enter the sums and the chromosome's mask c[n] (None: all).
+    A dict: lod[T] the combined LOD, coef[T][2], rank (the smallest over the draws), rss0[T], n_used, draw_lod[D][T].
+    CPU only."""
+    L = load()
+    st = np.ascontiguousarray(state, np.uint8)
+    st = st[:, None] if st.ndim == 1 else st
+    n, D = st.shape
+    v = np.ascontiguousarray(y, np.float64).reshape(n, -1)
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    if m.shape != (n,):
+        raise ValueError("state must be [n][D] and c [n]")
+    T = v.shape[1]
+    lod, coef, rss0, draw = np.zeros(T), np.zeros((T, 2)), np.zeros(T), np.zeros((D, T))
+    rank, n_used = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_qtlimp_marker(n, D, _p(st), T, _p(v), K, None if K == 0 else _p(z), _p(m), int(additive), _p(lod), _p(coef),
+                               _p(rank), _p(rss0), _p(n_used), _p(draw))
+    if rc != 0:
+        raise ValueError("cnf2h_qtlimp_marker refused its arguments (%d)" % rc)
+    return dict(lod=lod, coef=coef, rank=int(rank[0]), rss0=rss0, n_used=int(n_used[0]), draw_lod=draw)
 
 
 def qtl_marker_map(chromstarts, tile, chrom_begin=0, chrom_end=None, with_mchrom=False, whole_map_header=True):

@@ -39,7 +39,11 @@ replicates' best markers into a confidence interval of the position.  bayes_inte
 profile (the 10^LOD posterior); peaks keeps its LOD-drop interval.
 
 The multi-trait scan (Context.qtl_scan_mv, cnf2_qtl_scan_mv) asks whether a locus moves several correlated traits jointly
-(Wilks' lambda of multivariate Haley-Knott regression): scan_mv; thresholds and peaks read its one joint profile."""
+(Wilks' lambda of multivariate Haley-Knott regression): scan_mv; thresholds and peaks read its one joint profile.
+
+The multiple-imputation scan (Context.qtl_scan_imp, cnf2_qtl_scan_imp) fits scan's model to hard genotypes sampled from the
+posterior and combines the draws on the likelihood scale: sample_states, sampled_classes and scan_imp; thresholds and peaks
+read it as they read scan."""
 import numpy as np
 
 from . import synth
@@ -224,6 +228,84 @@ def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False,
             res = null_residuals(yk, cov, u)
             out["perm_max"][:, cols] = ctx.qtl_scan_device(n, d_o.data_ptr(), res, cov=cov, use=u, perm=perm,
                                                            additive=additive)["perm_max"]
+    return out
+
+
+def sampled_classes(state):
+    """The origin class k = bit0 + 2 bit3 of sampled states below 64 (uint8, any shape) -- the class whose probability is
+    origin[k] of sweep_origins; 255 (skipped) stays 255.  A value in 64 .. 254 is no state: ValueError."""
+    g = np.asarray(state)
+    if g.dtype != np.uint8:
+        raise ValueError("states are uint8")
+    if ((g >= 64) & (g != 255)).any():
+        raise ValueError("a state is in 64 .. 254")
+    return np.where(g == 255, 255, (g & 1) + ((g >> 2) & 2)).astype(np.uint8)
+
+
+def sample_states(ctx, draws, seed=0):
+    """One sampling sweep of the context's pedigree with the states left on its GPU: a torch tensor [n][draws][M] (uint8) that
+    scan_imp takes as `states`, as origin_rows is to scan."""
+    import torch
+    n, M, C = ctx.n_ind, ctx.n_markers, ctx.n_chrom
+    dev = torch.device("cuda", ctx.device)
+    d_f = torch.zeros((n, C, 8), dtype=torch.float64, device=dev)
+    d_l = torch.zeros((n, C), dtype=torch.float64, device=dev)
+    d_s = torch.zeros((n, draws, M), dtype=torch.uint8, device=dev)
+    d_h = torch.zeros((n, draws, C), dtype=torch.int32, device=dev)
+    ctx.sweep_sample_device(0, n, draws, seed, d_f.data_ptr(), d_l.data_ptr(), d_s.data_ptr(), d_h.data_ptr())
+    ctx.sync()
+    return d_s
+
+
+def scan_imp(ctx, pheno, draws=16, seed=0, cov=None, use=None, permutations=0, perm_seed=0, additive=False, states=None,
+             draw_lods=False):
+    """The multiple-imputation scan of a whole cross on the context's uploaded pedigree (Context.qtl_scan_imp_device,
+    cnf2_qtl_scan_imp): `draws` inheritance paths per individual sampled from the posterior (seed; or `states`, the tensor
+    of sample_states), the model of scan fitted to the hard genotypes of every draw, and the draws combined on the likelihood
+    scale -- the remedy where the origin rows are soft and Haley-Knott regression misjudges the residual variance.  NaN is a
+    missing phenotype; per pattern of missing values one observed scan with the pattern's own `use`, and with permutations
+    > 0 one more on the permuted residuals of the null model (perm_seed), whose maxima are taken over the combined profile.
+    A dict as scan's -- lod[T][M], coef[T][M][2], rank[T][M], n_used[T][C], perm_max[P][T][C] or None -- plus
+    draw_lod[draws][T][M] with draw_lods (else None); thresholds and peaks read it as they read scan's.  Positions between
+    markers need blank columns in the uploaded map (origins.with_positions), so that the sampler visits them."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    if y.ndim != 2 or y.shape[0] != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    n, T = y.shape
+    M, C = ctx.n_markers, ctx.n_chrom
+    if permutations < 0:
+        raise ValueError("permutations must not be negative")
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    if use.shape != (n,):
+        raise ValueError("use must be [n]")
+    if states is None:
+        if not 1 <= int(draws) <= 1024:
+            raise ValueError("draws must be 1 .. 1024")
+        states = sample_states(ctx, int(draws), seed)
+    if tuple(states.shape[::2]) != (n, M) or len(states.shape) != 3 or not 1 <= states.shape[1] <= 1024:
+        raise ValueError("states must be [%d][draws][%d] with 1 .. 1024 draws" % (n, M))
+    D = int(states.shape[1])
+    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, 2), np.nan), rank=np.zeros((T, M), np.int32),
+               n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C)) if permutations else None,
+               draw_lod=np.zeros((D, T, M)) if draw_lods else None)
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(T):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    for cols in patterns.values():
+        u = use & ~missing[:, cols[0]]
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = ctx.qtl_scan_imp_device(n, D, states.data_ptr(), yk, cov=cov, use=u, additive=additive, draw_lods=draw_lods)
+        out["lod"][cols], out["coef"][cols] = got["lod"], got["coef"]
+        out["rank"][cols], out["n_used"][cols] = got["rank"], got["n_used"]
+        if draw_lods:
+            out["draw_lod"][:, cols] = got["draw_lod"]
+        if permutations:
+            perm = _permutations(n, permutations, perm_seed, use=u)
+            res = null_residuals(yk, cov, u)
+            out["perm_max"][:, cols] = ctx.qtl_scan_imp_device(n, D, states.data_ptr(), res, cov=cov, use=u, perm=perm,
+                                                               additive=additive)["perm_max"]
     return out
 
 

@@ -131,6 +131,8 @@ enum {
                                      where no windows are packed */
     CNF2_QTL_REG_DEVICE = 1u << 28, /* cnf2_qtl_scan_cols: `reg` is a device pointer (aligned to 16 bytes); it is read in place */
     CNF2_QTL_IMPRINT  = 1u << 25, /* cnf2_qtl_scanx: the design gets the parent-of-origin (imprinting) effect i = o[1] - o[2] */
+    CNF2_QTL_STATE_DEVICE = 1u << 29, /* cnf2_qtl_scan_imp: `state` is a device pointer, e.g. the states a cnf2_sweep_sample call with
+                                     CNF2_OUT_DEVICE filled; they are read in place */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
                                     registers by a transpose through LDS instead of being exchanged by DPP moves (same
@@ -983,6 +985,46 @@ int cnf2_qtl_scan_var(cnf2_ctx *ctx, int n, const double *origin, int n_traits, 
                       double *lod_out, double *coef_mean_out, double *coef_var_out, int32_t *iters_out, int32_t *status_out,
                       int32_t *rank_out, double *ll0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
 int cnf2_set_qtlvar_columns(cnf2_ctx *ctx, int cap);
+
+/* Multiple-imputation scan: cnf2_qtl_scan on hard genotypes drawn from the posterior instead of on the soft origin rows (Sen
+ * and Churchill 2001; sim.geno with scanone(method = "imp") of other packages).  Where the rows are soft Haley-Knott regression
+ * misjudges the residual variance; every draw of cnf2_sweep_sample has hard classes, every fit is ordinary least squares, and
+ * the draws are combined on the likelihood scale.  One definition for this header, cnf2freq_amd/csrc/cnf2_qtlimp.h (host and
+ * device), the kernels and tests/qtlimp_reference.py.
+ *   state [n][D][M]   (uint8) the layout cnf2_sweep_sample writes, 1 <= D <= 1024.  A state g < 64 has the origin class
+ *                     k = bit0(g) + 2 bit3(g) -- the absolute frame of cnf2_sweep_origins, which takes these two bits the same
+ *                     way in every shift mode; bits 1, 2, 4 and 5 are ignored.  0xFF: skipped
+ * pheno, use, cov (0 <= K <= 8), perm, the columns R = T (1 + P), X0, the centring and CNF2_QTL_ADDITIVE are cnf2_qtl_scan's.
+ * Per chromosome c_i = use[i] and state[i][0][first marker of c] != 0xFF; n_c, S11, its factor, b0 and RSS0 follow as there and
+ * do not depend on the draw.  Per draw d the one-hot row of the class gives a = [k = 3] - [k = 0], d = [k = 1] + [k = 2]
+ * (a d = 0: S22 is diagonal), and S21, G, W, the rank rule (1e-8), v, the clamps and lod_d, coef_d are cnf2_qtl_scan's on
+ * that row.  Per (marker, column), the draws in ascending order through one recurrence:
+ *   m = max_d lod_d,  s = sum_d 10^(lod_d - m),  lod = m + log10(s / D)   the log of the mean likelihood ratio: the draws
+ *                                                                          share the null fit, so the ratios share a denominator
+ *   coef = sum_d 10^(lod_d - m) coef_d / s   kept as a running weighted mean; NaN as soon as one draw drops the column (NaN
+ *                                            propagating through the sum is the definition)
+ * Equal draws give lod = m and the draw's coefficients to the bit.  rank_out[m] is the smallest rank over the draws.
+ *   lod_out [T][M]   coef_out [T][M][2]   rank_out [M]   rss0_out [T][C]   n_used_out [C]      as cnf2_qtl_scan
+ *   perm_max_out [P][T][C]   the largest COMBINED lod of the chromosome (NULL exactly when P = 0): D separate scans cannot
+ *                            give it
+ *   draw_lod_out [D][T][M]   or NULL: lod_d of the observed columns
+ * state is a host pointer, staged whole (CNF2_ERR_NOMEM if that fails), or with CNF2_QTL_STATE_DEVICE device memory read in
+ * place.  Outputs are host pointers, or device pointers with CNF2_OUT_DEVICE; pheno, use, cov and perm are host pointers.
+ * CNF2_ERR_ARG, nothing written: a state in 64 .. 254; an (individual, chromosome) that is 0xFF in some of its D x len cells
+ * and not in all; D out of range; state NULL; whatever cnf2_qtl_scan refuses.  Device states are checked by a kernel before
+ * any output is written.  The call synchronises the context's stream, also with CNF2_OUT_DEVICE.
+ * Launches: the check (device states); the masks and the factor; a record per (draw, marker), 192 bytes each, held for the
+ * call; per tile of columns cnf2_qtl_scan's image and null fit, then the product: a wave owns 16 markers x 16 columns, loops
+ * over the draws in ascending order and per draw over the individuals in ascending order, four per v_mfma_f64_16x16x4_f64,
+ * with the (a, d) operand built in registers from the state bytes read in place; the cell, the recurrence, and the tile's
+ * maximum of the combined lod stay in registers; cnf2_qtl_scan's finish kernel reduces the maxima.  No atomics: a call gives
+ * the same bits every time, from host or device states, whatever the column cap (cnf2_set_qtlimp_columns, 0 = no cap) and
+ * cnf2_set_batch_jobs. */
+int cnf2_qtl_scan_imp(cnf2_ctx *ctx, int n, int n_draws, const uint8_t *state, int n_traits, const double *pheno,
+                      const uint8_t *use, int n_cov, const double *cov, int n_perm, const int32_t *perm, double *lod_out,
+                      double *coef_out, int32_t *rank_out, double *rss0_out, int32_t *n_used_out, double *perm_max_out,
+                      double *draw_lod_out /* [D][T][M] or NULL */, uint32_t flags);
+int cnf2_set_qtlimp_columns(cnf2_ctx *ctx, int cap);
 
 /* HOT LOOP 2 with its reductions: for the analysed individuals
  * [ind_begin, ind_end), in that order, the per-locus accumulators of cnF2freq.cpp:5416-5577 are formed on the GPU

@@ -241,6 +241,16 @@ int cnf2h_qtl_boot_marker(int n, const double *origin, int n_traits, const doubl
                           const uint8_t *c, const int32_t *count, int additive, double *lod_out, double *coef_out,
                           int32_t *rank_out, double *rss0_out, int32_t *n_bc_out);
 
+/* One marker of the multiple-imputation scan (cnf2_qtl_scan_imp of cnf2hip.h) through cnf2freq_amd/csrc/cnf2_qtlimp.h, the
+ * individuals and the draws in ascending order: state[n][n_draws] (uint8) the marker's sampled states, below 64 wherever c is
+ * set; y[n][n_traits] and cov[n][n_cov] as they enter the sums (the scan centres them first); c[n] the chromosome's mask.
+ * lod_out[n_traits] the combined LOD, coef_out[n_traits][2] the weighted mean effects (NaN once a draw drops the column),
+ * *rank_out the smallest rank over the draws, rss0_out[n_traits], *n_used_out n_c, draw_lod_out[n_draws][n_traits] or NULL
+ * the draws' own LODs.  -2: a bad argument (n_draws outside 1 .. 1024 and a state of 64 or more under the mask among them). */
+int cnf2h_qtlimp_marker(int n, int n_draws, const uint8_t *state, int n_traits, const double *y, int n_cov, const double *cov,
+                        const uint8_t *c, int additive, double *lod_out, double *coef_out, int32_t *rank_out, double *rss0_out,
+                        int32_t *n_used_out, double *draw_lod_out);
+
 /* What the QTL scans of cnf2hip.h plan on the host before they allocate (cnf2freq_amd/csrc/cnf2_qtlplan.h), for tests:
  *  cnf2h_qtl_marker_map   the marker map a scan uploads, in int32 words: the header -- chromstarts[n_chrom + 1] of the whole
  *                         map (whole_map_header) or the first marker of every chromosome of chrom_begin .. chrom_end-1;
