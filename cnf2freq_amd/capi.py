@@ -47,7 +47,7 @@ SYMBOLS = [
     "cnf2_turn_scan", "cnf2_turn_scan_rows", "cnf2_state_posterior", "cnf2_haplos", "cnf2_infprobs", "cnf2_infprobs_rows", "cnf2_descendants", "cnf2_accumulate", "cnf2_sweep_accumulate", "cnf2_sweep_turn_scan", "cnf2_fixparents_scan", "cnf2_variances", "cnf2_variances_exact",
     "cnf2_snapshot_priors", "cnf2_update_pass", "cnf2_download_rows", "cnf2_download_accumulators", "cnf2_upload_accumulators", "cnf2_accumulator_ptrs", "cnf2_update_stats", "cnf2_update_stats_guided", "cnf2_addvariance", "cnf2_emission", "cnf2_emission_paths",
     "cnf2_selftest_lane_xor", "cnf2_last_kernel_ms", "cnf2_last_paths", "cnf2_workspace_bytes", "cnf2_reserve_accumulate", "cnf2_clock_probe", "cnf2_sweep_clock", "cnf2_stream",
-    "cnf2_set_grid_reserve", "cnf2_set_batch_jobs", "cnf2_set_line_records", "cnf2_last_line_records", "cnf2_last_uniform_pack", "cnf2_last_uniform_pack8", "cnf2_window_table", "cnf2_update_pass_records", "cnf2_exchange_buffer", "cnf2_exchange_download", "cnf2_exchange_upload", "cnf2_exchange_read", "cnf2_exchange_write",
+    "cnf2_set_grid_reserve", "cnf2_set_batch_jobs", "cnf2_set_line_records", "cnf2_last_line_records", "cnf2_last_uniform_pack", "cnf2_last_uniform_pack8", "cnf2_last_plan_reused", "cnf2_last_plan_ms", "cnf2_window_table", "cnf2_update_pass_records", "cnf2_exchange_buffer", "cnf2_exchange_download", "cnf2_exchange_upload", "cnf2_exchange_read", "cnf2_exchange_write",
     "cnf2_packed_accumulator_doubles", "cnf2_packed_row_bytes", "cnf2_pack_accumulators", "cnf2_unpack_accumulators",
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
@@ -195,6 +195,9 @@ def load():
         L.cnf2_last_line_records.argtypes = [vp, vp]
         L.cnf2_last_uniform_pack.argtypes = [vp, vp]
         L.cnf2_last_uniform_pack8.argtypes = [vp, vp]
+        L.cnf2_last_plan_reused.argtypes = [vp]
+        L.cnf2_last_plan_ms.argtypes = [vp]
+        L.cnf2_last_plan_ms.restype = C.c_float
         L.cnf2_window_table.argtypes = [vp, vp]
         L.cnf2_update_pass_records.argtypes = [vp, i32, vp, i32, vp, vp, C.c_double, C.c_double, vp, C.c_uint32]
         L.cnf2_exchange_buffer.argtypes = [vp, C.c_size_t, vp]
@@ -390,6 +393,14 @@ class Context:
         out = np.zeros(2, np.int32)
         self._chk(self.L.cnf2_last_uniform_pack8(self.h, _p(out)), "cnf2_last_uniform_pack8")
         return dict(eights=int(out[0]), jobs=int(out[1]))
+
+    def last_plan_reused(self):
+        """True if the last sweep took the plan the context kept from the sweep before as it stood (cnf2_last_plan_reused)."""
+        return bool(self.L.cnf2_last_plan_reused(self.h))
+
+    def last_plan_ms(self):
+        """Host milliseconds the last sweep spent before its first launch (cnf2_last_plan_ms)."""
+        return float(self.L.cnf2_last_plan_ms(self.h))
 
     def set_batch_jobs(self, jobs):
         """Cap on the jobs per batch of sweep_accumulate / sweep_turn_scan (0 = what memory allows)."""

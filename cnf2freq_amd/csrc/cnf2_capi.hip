@@ -138,6 +138,17 @@ struct cnf2_ctx {
     DevBuf<int32_t>      d_line_keys;
     DevBuf<LineRec>      d_line_rec;
 
+    // the plan of the last sweep (cnf2_plan.h PlanKey): the job list as grouped, the groups of four, the groups as paired and
+    // the counts formed from them; d_jobs, d_pjobs and d_upjobs hold their device copies.  A sweep with an equal key reuses it
+    unsigned               map_gen = 0;            // counts the uploads of the map
+    bool                   plan_valid = false;
+    PlanKey                plan_key;
+    JobPlan                plan_list;
+    std::vector<PackedJob> plan_fours, plan_groups;
+    size_t                 plan_n_uniform = 0, plan_n_on_records = 0, plan_n_eights = 0;
+    int                    last_plan_reused = 0;   // cnf2_last_plan_reused
+    float                  last_plan_ms = 0.f;     // cnf2_last_plan_ms
+
     // workspace
     DevBuf<Job>       d_jobs;
     DevBuf<PackedJob> d_pjobs;
@@ -530,6 +541,7 @@ int cnf2_upload_map(cnf2_ctx* ctx, const double* pos, int n_markers, const int32
     ctx->n_markers = n_markers;
     ctx->n_chrom   = n_chrom;
     ctx->chromstarts.assign(chromstarts, chromstarts + n_chrom + 1);
+    ctx->map_gen++;
     if (genrec) memcpy(ctx->genrec, genrec, sizeof(ctx->genrec));
     // recombination fraction per gap, exactly as realanalyze forms it (cnF2freq.cpp:2270-2286);
     // a gap with dist <= 0 performs no transition (cnF2freq.cpp:2273) == rho 0
@@ -945,28 +957,72 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     if ((size_t)n * ctx->n_chrom > 0x7fffffff) return fail(ctx, CNF2_ERR_ARG, "too many jobs in one call");
-    JobPlan      jp = job_plan(ctx, ind_begin, n, flags);
-    const size_t n_fast = jp.n_fast, n_general = jp.jobs.size() - n_fast, n_packed = jp.pjobs.size();
-    RC_TRY(ctx->d_jobs.ensure(ctx, jp.jobs.size() + 1));
-    if (n_packed > 0) {
-        RC_TRY(ctx->d_pjobs.ensure(ctx, n_packed));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pjobs, jp.pjobs.data(), sizeof(PackedJob) * n_packed, hipMemcpyHostToDevice, ctx->stream));
-    }
-    // the uniform jobs on records four to a wave (group_uniform_jobs: they become the tail of the fast jobs), then the list's
-    // upload; again where the call's lines change below
-    std::vector<PackedJob> ugroups;
-    const std::vector<Job> jobs_planned = jp.jobs;
-    auto group_and_upload = [&](const int32_t* keys) -> int {
-        jp.jobs = jobs_planned;
-        ugroups.clear();
-        size_t n_single = n_fast;      // (the jobs in front of the groups': launch_fb_fast forms it from the groups' number)
+    const auto t_plan = std::chrono::steady_clock::now();
+    ctx->last_plan_reused = 0;
+    memset(ctx->last_lines, 0, sizeof(ctx->last_lines));
+    memset(ctx->last_pack, 0, sizeof(ctx->last_pack));
+    memset(ctx->last_pack8, 0, sizeof(ctx->last_pack8));
+
+    // the plain half-spill sweep: the fast jobs of uniform windows (slots_uniform: crosses of inbred lines) take the fast
+    // kernel's instantiation for them (launch_fb_fast), which has an occupancy of its own; the spill slots cover the larger grid
+    // ... and, unless CNF2_NO_LINE_RECORDS, the lines of those windows (numbered once per set of windows, range and cap)
+    int        n_lines = 0;
+    const bool uni_ok = !(flags & (CNF2_ALL_STATES | CNF2_FULL_SPILL | CNF2_XPOSE)) && (plain || mode.variant == SW_VITERBI);
+    int        want_lines = ctx->line_cap >= 0 ? std::min(ctx->line_cap, ctx->lines_fit) : ctx->lines_fit;
+    if (uni_ok && !(flags & CNF2_NO_LINE_RECORDS)) RC_TRY(prepare_lines(ctx, ind_begin, n, want_lines, &n_lines));
+
+    // The plan (cnf2_plan.h PlanKey): the job list with the uniform jobs on records four to a wave (group_uniform_jobs: they
+    // become the tail of the fast jobs), the counts, the uploads.  The context keeps it: a call with the key of the last one
+    // builds, copies and uploads nothing and does not wait for the stream.
+    PlanKey key;
+    key.windows_gen       = ctx->windows_gen;
+    key.map_gen           = ctx->map_gen;
+    key.ind_begin         = ind_begin;
+    key.n                 = n;
+    key.flags             = flags & PLAN_KEY_FLAGS;
+    key.uniform_mode      = uni_ok ? 1 : 0;
+    key.reserve_blocks    = ctx->reserve_blocks;
+    key.uni_blocks_per_cu = ctx->uni_blocks_per_cu;
+    auto key_lines = [&]() {
+        key.n_lines   = n_lines;
+        key.lines_cap = want_lines;
+        key.lines_fit = ctx->lines_fit;
+    };
+    key_lines();
+    JobPlan&                jp = ctx->plan_list;
+    std::vector<PackedJob>& fours = ctx->plan_fours;
+    auto build_jobs = [&]() -> int {
+        ctx->plan_valid = false;
+        jp = job_plan(ctx, ind_begin, n, flags);
+        RC_TRY(ctx->d_jobs.ensure(ctx, jp.jobs.size() + 1));
+        if (!jp.pjobs.empty()) {
+            RC_TRY(ctx->d_pjobs.ensure(ctx, jp.pjobs.size()));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pjobs, jp.pjobs.data(), sizeof(PackedJob) * jp.pjobs.size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        const int32_t* keys = uni_ok && n_lines > 0 ? ctx->h_line_keys.data() : nullptr;
+        ctx->plan_n_uniform = ctx->plan_n_on_records = 0;
+        for (size_t j = 0; uni_ok && j < jp.n_fast; j++) {
+            const int i = jp.jobs[j].ind;
+            if (!slots_uniform(ctx->windows[ind_begin + i].flags)) continue;
+            ctx->plan_n_uniform++;
+            if (keys && keys[2 * (size_t)i] >= 0) ctx->plan_n_on_records++;
+        }
+        fours.clear();
+        size_t n_single = jp.n_fast;   // (the jobs in front of the groups': launch_fb_fast forms it from the groups' number)
         if (keys && !(flags & CNF2_NO_UNIFORM_PACK))
-            ugroups = group_uniform_jobs(jp.jobs, n_fast, ctx->windows.data() + ind_begin, keys, &n_single);
+            fours = group_uniform_jobs(jp.jobs, jp.n_fast, ctx->windows.data() + ind_begin, keys, &n_single);
         if (!jp.jobs.empty())
             HIP_TRY(ctx, hipMemcpyAsync(ctx->d_jobs, jp.jobs.data(), sizeof(Job) * jp.jobs.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copy has read the job vector)
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copies have read the lists, which the next plan overwrites)
         return CNF2_OK;
     };
+#ifdef CNF2_NO_PLAN_CACHE   /* A/B only: every call plans and uploads anew */
+    ctx->plan_valid = false;
+#endif
+    bool same_jobs = ctx->plan_valid && plan_key_same_jobs(ctx->plan_key, key);
+    if (!same_jobs) RC_TRY(build_jobs());
+    // (the list's sizes do not depend on the lines: they stand where the lines change below)
+    const size_t n_fast = jp.n_fast, n_general = jp.jobs.size() - n_fast, n_packed = jp.pjobs.size();
 
     // grids and spill: one slot per resident wave, the fast kernel's slots first
     const int    mlen = longest_chrom(ctx);
@@ -974,34 +1030,10 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     int          grid_fast = 0, grid_gen = 0;
     size_t       free_b = 0, total_b = 0;
     HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-    // the plain half-spill sweep: the fast jobs of uniform windows (slots_uniform: crosses of inbred lines) take the fast
-    // kernel's instantiation for them (launch_fb_fast), which has an occupancy of its own; the spill slots cover the larger grid
-    // ... and, unless CNF2_NO_LINE_RECORDS, the lines of those windows (numbered once per set of windows, range and cap)
-    size_t n_uniform = 0, n_on_records = 0;
-    int    n_lines = 0;
-    const bool uni_ok = !(flags & (CNF2_ALL_STATES | CNF2_FULL_SPILL | CNF2_XPOSE)) && (plain || mode.variant == SW_VITERBI);
-    const int  want_lines = ctx->line_cap >= 0 ? std::min(ctx->line_cap, ctx->lines_fit) : ctx->lines_fit;
-    auto count_uniform = [&]() {
-        n_uniform = n_on_records = 0;
-        const int32_t* keys = n_lines > 0 ? ctx->h_line_keys.data() : nullptr;
-        for (size_t j = 0; j < n_fast; j++) {
-            const int i = jp.jobs[j].ind;
-            if (!slots_uniform(ctx->windows[ind_begin + i].flags)) continue;
-            n_uniform++;
-            if (keys && keys[2 * (size_t)i] >= 0) n_on_records++;
-        }
-    };
-    memset(ctx->last_lines, 0, sizeof(ctx->last_lines));
-    memset(ctx->last_pack, 0, sizeof(ctx->last_pack));
-    memset(ctx->last_pack8, 0, sizeof(ctx->last_pack8));
-    if (uni_ok) {
-        if (n_fast > 0 && !(flags & CNF2_NO_LINE_RECORDS)) RC_TRY(prepare_lines(ctx, ind_begin, n, want_lines, &n_lines));
-        count_uniform();
-    }
-    RC_TRY(group_and_upload(uni_ok && n_lines > 0 ? ctx->h_line_keys.data() : nullptr));
-    const int fast_per_cu = n_uniform == 0       ? ctx->fast_blocks_per_cu
-                            : n_uniform < n_fast ? std::max(ctx->fast_blocks_per_cu, ctx->uni_blocks_per_cu)
-                                                 : ctx->uni_blocks_per_cu;
+    const size_t n_uniform0 = ctx->plan_n_uniform;
+    const int fast_per_cu = n_uniform0 == 0       ? ctx->fast_blocks_per_cu
+                            : n_uniform0 < n_fast ? std::max(ctx->fast_blocks_per_cu, ctx->uni_blocks_per_cu)
+                                                  : ctx->uni_blocks_per_cu;
     if (!plan_sweep_grids(ctx->n_cu, fast_per_cu, ctx->blocks_per_cu, ctx->reserve_blocks, std::max(n_fast, n_packed),
                           n_general, free_b, ctx->d_spill.cap * sizeof(double), mlen, &grid_fast, &grid_gen))
         return fail(ctx, CNF2_ERR_NOMEM, "a chromosome of %d markers needs %zu MB of spill per block, %zu MB free", mlen,
@@ -1024,7 +1056,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
     }
 
     // the records of the call's lines, after the spill slots and the outputs: they take at most half of what is left
-    if (n_on_records == 0) n_lines = 0;
+    if (ctx->plan_n_on_records == 0) n_lines = 0;
     if (n_lines > 0) {
         const size_t line_bytes = (size_t)ctx->n_markers * LINE_VALUES * 2 * sizeof(LineRec);
         if ((size_t)n_lines * line_bytes > ctx->d_line_rec.cap * sizeof(LineRec)) {
@@ -1033,32 +1065,45 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
             const size_t fit = (ctx->d_line_rec.cap * sizeof(LineRec) + free_b / 2) / line_bytes;
             if (fit < (size_t)n_lines) {
                 ctx->lines_fit = (int)fit;
-                RC_TRY(prepare_lines(ctx, ind_begin, n, std::min(want_lines, ctx->lines_fit), &n_lines));
-                count_uniform();
-                if (n_on_records == 0) n_lines = 0;
-                RC_TRY(group_and_upload(n_lines > 0 ? ctx->h_line_keys.data() : nullptr));
+                want_lines     = std::min(want_lines, ctx->lines_fit);
+                RC_TRY(prepare_lines(ctx, ind_begin, n, want_lines, &n_lines));
+                key_lines();
+                same_jobs = false;
+                RC_TRY(build_jobs());
+                if (ctx->plan_n_on_records == 0) n_lines = 0;
             }
         }
         if (n_lines > 0) RC_TRY(ctx->d_line_rec.ensure(ctx, (size_t)n_lines * ctx->n_markers * LINE_VALUES * 2));
     }
+    const size_t n_uniform = ctx->plan_n_uniform, n_on_records = ctx->plan_n_on_records;
     ctx->last_lines[0] = n_lines;
     ctx->last_lines[1] = n_lines > 0 ? (int32_t)n_on_records : 0;
     ctx->last_lines[2] = (int32_t)n_uniform - ctx->last_lines[1];
     ctx->last_lines[3] = (int32_t)std::min<size_t>((size_t)n_lines * ctx->n_markers * LINE_VALUES * 2 * sizeof(LineRec), 0x7fffffff);
-    const size_t n_groups = n_lines > 0 ? ugroups.size() : 0;
+    const size_t n_groups = n_lines > 0 ? fours.size() : 0;
     ctx->last_pack[0] = (int32_t)(4 * n_groups);
     ctx->last_pack[1] = (int32_t)n_groups;
     // the groups' upload, once the call's lines and the grids stand: pairs of groups whose windows have all eight modes analysed
     // go eight jobs to a wave (pair_uniform_groups: a whole number of rounds of the packed grid's resident waves), in front
     const int pack_cap = std::min(grid_fast, resident_blocks(ctx->n_cu, ctx->uni_blocks_per_cu, ctx->reserve_blocks));
-    size_t    n_eights = 0;
-    if (n_groups > 0) {
-        if (!(flags & CNF2_NO_UNIFORM_PACK8))
-            n_eights = pair_uniform_groups(ugroups, ctx->windows.data() + ind_begin, (size_t)pack_cap * CNF2_WAVES_PER_BLOCK);
-        RC_TRY(ctx->d_upjobs.ensure(ctx, ugroups.size()));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_upjobs, ugroups.data(), sizeof(PackedJob) * ugroups.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copy has read the vector)
-    }
+    key.pack_cap = pack_cap;
+    if (!(same_jobs && plan_key_same(ctx->plan_key, key))) {
+        std::vector<PackedJob>& ugroups = ctx->plan_groups;
+        ctx->plan_valid    = false;
+        ctx->plan_n_eights = 0;
+        ugroups.clear();
+        if (n_groups > 0) {
+            ugroups = fours;
+            if (!(flags & CNF2_NO_UNIFORM_PACK8))
+                ctx->plan_n_eights = pair_uniform_groups(ugroups, ctx->windows.data() + ind_begin, (size_t)pack_cap * CNF2_WAVES_PER_BLOCK);
+            RC_TRY(ctx->d_upjobs.ensure(ctx, ugroups.size()));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->d_upjobs, ugroups.data(), sizeof(PackedJob) * ugroups.size(), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream)); // (the copy has read the vector)
+        }
+        ctx->plan_key   = key;
+        ctx->plan_valid = true;
+    } else ctx->last_plan_reused = 1;
+    const size_t n_eights = ctx->plan_n_eights;
     ctx->last_pack8[0] = (int32_t)n_eights;
     ctx->last_pack8[1] = (int32_t)(8 * n_eights);
 
@@ -1132,6 +1177,7 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         q->loglik  = ctx->d_xo_f + (size_t)n * ctx->n_chrom * 8;
     };
 
+    ctx->last_plan_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_plan).count();
     HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
     if (n_general > 0) {
         // the tied windows' kernel on a second stream with its own spill slots (behind the fast kernel's) and its own job
@@ -1258,6 +1304,10 @@ int cnf2_last_uniform_pack8(cnf2_ctx* ctx, int32_t* out)
     memcpy(out, ctx->last_pack8, sizeof(ctx->last_pack8));
     return CNF2_OK;
 }
+
+int cnf2_last_plan_reused(cnf2_ctx* ctx) { return ctx ? ctx->last_plan_reused : 0; }
+
+float cnf2_last_plan_ms(cnf2_ctx* ctx) { return ctx ? ctx->last_plan_ms : 0.f; }
 
 int cnf2_last_paths(cnf2_ctx* ctx, int32_t* paths_out, int n)
 {
@@ -3037,6 +3087,7 @@ static int batched_setup(cnf2_ctx* ctx, int ind_begin, int n, uint32_t flags, si
 {
     b->list = job_plan(ctx, ind_begin, n, flags & CNF2_NO_TIES);
     const std::vector<Job>& jobs = b->list.jobs;
+    ctx->plan_valid = false;           // (d_jobs no longer holds the last sweep's list)
     RC_TRY(ctx->d_jobs.ensure(ctx, jobs.size() + 1));
     HIP_TRY(ctx, hipMemcpy(ctx->d_jobs, jobs.data(), sizeof(Job) * jobs.size(), hipMemcpyHostToDevice));
     b->max_len = longest_chrom(ctx);

@@ -20,6 +20,8 @@
 #ifndef CNF2_EMTAB_H
 #define CNF2_EMTAB_H
 
+#include <string.h>
+
 #include "cnf2_emission.h"
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -497,6 +499,28 @@ CNF2_HD void line_record_make(uint32_t fl_par, uint32_t fl_tr, uint32_t fl_ot, i
     r->pad[0] = r->pad[1] = r->pad[2] = 0;
 }
 
+// v where bit e of `bits` is set, +0.0 where it is clear: the same bits as  ((bits >> e) & 1) ? v : 0.0  for every v (-0.0, NaN
+// payloads, infinities and denormals included: the value's bit pattern or all zero bits).  On the device the bit, sign-extended
+// to a word, is ANDed into both halves of the double: two v_and_b32 in place of a compare, the wait for VCC and two selects.
+// The bit field is taken with the builtin: written as -(int)((bits >> e) & 1) the compiler folds the mask back into selects.
+// CNF2_EMTAB_SELECT (A/B only) keeps the select.
+CNF2_HD double keep_if_bit(uint32_t bits, int e, double v)
+{
+#if defined(CNF2_EMTAB_SELECT)
+    return ((bits >> e) & 1) ? v : 0.0;
+#elif defined(__HIP_DEVICE_COMPILE__)
+    const int m = __builtin_amdgcn_sbfe((int)bits, (unsigned)e, 1u);
+    return __hiloint2double(__double2hiint(v) & m, __double2loint(v) & m);
+#else
+    uint64_t u;
+    memcpy(&u, &v, sizeof(u));
+    u &= (uint64_t)0 - (uint64_t)((bits >> e) & 1);
+    double r;
+    memcpy(&r, &u, sizeof(r));
+    return r;
+#endif
+}
+
 // The 8 entries per table kind of the lane (P, f) from the root's own data and the record of its line, firstpar and
 // handed-down value (root allele f for P = 0, the other one for P = 1).  Same interface as emtab_part_views.  The traced line's
 // term alpha * t0 + beta * t1 is rounded as the ordinary producer rounds it, which is not the same for every entry: the
@@ -535,7 +559,7 @@ CNF2_HD void emtab_part_rec(int P, int f, const Slot& root, const LineRec& r, Ou
     return;
 #endif
     const double va = r.oo * CNF2_FMA2(alpha, r.t0, beta, r.t1);
-    const double v0 = (r.bits & LR_LIVE) ? va : 0.0;
+    const double v0 = keep_if_bit(r.bits, 16, va);          // LR_LIVE
 #pragma unroll
     for (int e = 0; e < 8; e++)
         if (!PACKED || packed_reads_unrestricted(e)) out(0, e, v0);
@@ -543,8 +567,8 @@ CNF2_HD void emtab_part_rec(int P, int f, const Slot& root, const LineRec& r, Ou
         const double vb = r.oo * CNF2_FMA2(beta, r.t1, alpha, r.t0);
 #pragma unroll
         for (int e = 0; e < 8; e++) {
-            out(1, e, ((r.bits >> e) & 1) ? ((e & 1) ? va : vb) : 0.0);
-            out(2, e, ((r.bits >> (8 + e)) & 1) ? va : 0.0);
+            out(1, e, keep_if_bit(r.bits, e, (e & 1) ? va : vb));
+            out(2, e, keep_if_bit(r.bits, 8 + e, va));
         }
     }
 }

@@ -204,6 +204,44 @@ inline size_t pair_uniform_groups(std::vector<PackedJob>& groups, const Window* 
     return n8;
 }
 
+// ------------------------------------------------------------------------------------------------ the plan kept across sweeps
+// What the job list of a sweep, its groups of four and eight and their device copies depend on.  The windows change only
+// with the rows or the pedigree, and the engine and every analysis mode sweep the same windows again and again: a context keeps
+// the plan of its last sweep and a call with an equal key takes it as it stands (no list is built, copied or uploaded and
+// the stream is not synchronised in front of the kernels).  The grids are NOT part of the plan: they are formed per call from
+// the memory that is free then.
+struct PlanKey {
+    // the windows and the map (counters of their derivations and uploads) and the call's range
+    unsigned windows_gen = 0, map_gen = 0;
+    int      ind_begin = 0, n = 0;
+    // the flags that enter plan_jobs, group_uniform_jobs and pair_uniform_groups or decide whether the call's lines do
+    // (PLAN_KEY_FLAGS), and whether the call's mode sweeps uniform windows on their own instantiation at all
+    uint32_t flags = 0;
+    int      uniform_mode = 0;
+    // the lines' state: the call's lines, the cap they were numbered under and what the record buffer had room for
+    int      n_lines = 0, lines_cap = 0, lines_fit = 0;
+    // the eights are a whole number of rounds of the packed grid's resident waves: blocks of the packed grid, and what it is
+    // formed from besides the call's own grid
+    int      pack_cap = 0, reserve_blocks = 0, uni_blocks_per_cu = 0;
+};
+constexpr uint32_t PLAN_KEY_FLAGS = CNF2_MERGE_MODES | CNF2_FULL_SPILL | CNF2_FLUSH_TINY | CNF2_NO_TIES | CNF2_NO_UNIFORM_PACK |
+                                    CNF2_NO_UNIFORM_PACK8 | CNF2_NO_LINE_RECORDS | CNF2_ALL_STATES | CNF2_XPOSE;
+
+// the job list and the groups of four of key `a` are those of key `b`: everything but what only the pairing reads
+inline bool plan_key_same_jobs(const PlanKey& a, const PlanKey& b)
+{
+    const uint32_t pairing = CNF2_NO_UNIFORM_PACK8;
+    return a.windows_gen == b.windows_gen && a.map_gen == b.map_gen && a.ind_begin == b.ind_begin && a.n == b.n &&
+           (a.flags & PLAN_KEY_FLAGS & ~pairing) == (b.flags & PLAN_KEY_FLAGS & ~pairing) && a.uniform_mode == b.uniform_mode &&
+           a.n_lines == b.n_lines && a.lines_cap == b.lines_cap && a.lines_fit == b.lines_fit;
+}
+// ... and the eights too: the whole plan
+inline bool plan_key_same(const PlanKey& a, const PlanKey& b)
+{
+    return plan_key_same_jobs(a, b) && (a.flags & PLAN_KEY_FLAGS) == (b.flags & PLAN_KEY_FLAGS) && a.pack_cap == b.pack_cap &&
+           a.reserve_blocks == b.reserve_blocks && a.uni_blocks_per_cu == b.uni_blocks_per_cu;
+}
+
 // ------------------------------------------------------------------------------------------------ grids and spill
 // Doubles of a wave's spill slot per marker of the longest chromosome: covers every layout (520 or 528 doubles per (pair
 // of) marker(s) in the fast kernel, 512 in the general kernel)

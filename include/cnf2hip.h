@@ -1237,6 +1237,16 @@ int    cnf2_last_uniform_pack(cnf2_ctx *ctx, int32_t *out);
  * cnf2_last_uniform_pack8: out[2] = the eights of the last sweep's call and their jobs (0 0 where there were none). */
 int    cnf2_last_uniform_pack8(cnf2_ctx *ctx, int32_t *out);
 
+/* The plan kept across sweeps.  The job list of cnf2_sweep and its modes, the groups of four and eight and their device copies
+ * depend on the windows (the rows and the pedigree), the map's chromosomes, the range, the flags that route windows, the
+ * call's lines and the packed grid (cnf2_set_grid_reserve): the context keeps them from the last sweep, and a call for which
+ * all of that is unchanged builds and uploads no list and does not synchronise the stream in front of its kernels.  The grids
+ * and the spill are formed per call all the same.  Same results to the bit.
+ * cnf2_last_plan_reused: 1 if the last sweep's call took the kept plan as it stood, else 0.
+ * cnf2_last_plan_ms: host milliseconds the last sweep's call spent before its first launch (planning, uploads, allocations). */
+int    cnf2_last_plan_reused(cnf2_ctx *ctx);
+float  cnf2_last_plan_ms(cnf2_ctx *ctx);
+
 #ifdef __cplusplus
 }
 #endif

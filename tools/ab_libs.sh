@@ -1,5 +1,6 @@
 #!/bin/bash
-# A/B timing of library builds (tuning aid, GPU box): bash tools/ab_libs.sh name1 name2 ...  -> kernel_ms of the headline
+# A/B timing of library builds (tuning aid, GPU box): bash tools/ab_libs.sh name1 name2 ...  -> kernel_ms (the launch) and
+# ms_per_step (the step as the host sees it: what the call does around its kernels shows only there) of the headline
 # bench with cnf2freq_amd/libcnf2hip_x_<name>.so in place of the product library ("base" = the product library).  A name that
 # is a directory holding another checkout with its library built (say, the parent commit's tree) runs that tree's own bench.py
 # on its own library: for a parent whose library lacks an export this tree's capi.py asks for.  Repeat names to alternate.
@@ -21,7 +22,7 @@ for v in "$@"; do
 import json, sys
 v = sys.argv[1]
 r = json.loads(open(sys.argv[2]).read().strip().split("\n")[-1])
-print("%-12s kernel_ms %.2f  frac %.4f  loglik_checksum %r  checks %s" % (v, r["roofline"]["kernel_ms"], r["roofline"]["frac"],
+print("%-12s kernel_ms %.2f  ms_per_step %.2f  frac %.4f  loglik_checksum %r  checks %s" % (v, r["roofline"]["kernel_ms"], r["ms_per_step"], r["roofline"]["frac"],
       r.get("loglik_checksum", r.get("checks_detail", {}).get("loglik_checksum")), all(r["checks"].values())))
 PY
 done
