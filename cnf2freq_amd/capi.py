@@ -659,6 +659,22 @@ class Context:
                 perm = None
         return pheno, cov, use, perm
 
+    @staticmethod
+    def _n_effects(flags):
+        """the effects a marker is fitted with: a, d unless QTL_ADDITIVE, i with QTL_IMPRINT"""
+        return 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
+
+    @staticmethod
+    def _fit_flags(flags, additive, imprint):
+        return flags | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0)
+
+    def _origin_rows(self, origin):
+        """origin as a contiguous float64 array [n][M][4], or ValueError"""
+        origin = np.ascontiguousarray(origin, np.float64)
+        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
+            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        return origin
+
     def _qtl_outputs(self, T, P):
         M, Cn = self.n_markers, self.n_chrom
         return dict(lod=np.zeros((T, M)), coef=np.zeros((T, M, 2)), rank=np.zeros(M, np.int32), rss0=np.zeros((T, Cn)),
@@ -681,9 +697,7 @@ class Context:
         perm[P][n].  A dict: lod[T][M], coef[T][M][2] (additive and dominance effect; NaN for a dropped column), rank[M],
         rss0[T][C], n_used[C], perm_max[P][T][C] (None without permutations).  The model: include/cnf2hip.h;
         cnf2freq_amd/qtl.py reads the results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        origin = self._origin_rows(origin)
         return self._qtl_call(origin.shape[0], _p(origin), pheno, cov, use, perm, QTL_ADDITIVE if additive else 0)
 
     def qtl_scan_device(self, n, d_origin, pheno, cov=None, use=None, perm=None, additive=False):
@@ -778,9 +792,7 @@ class Context:
         """cnf2_kinship_sums on host rows origin[n][M][4]: (sum[n][n], markers) with sum[i][j] the sum of a_i(m) a_j(m),
         a = origin[3] - origin[0], over the markers of the chromosomes chrom_begin .. chrom_end-1 (None: to the last).  The
         kinship is K = (1 + sum / markers) / 2; leaving a chromosome out is a subtraction of sums (qtl.kinship)."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        origin = self._origin_rows(origin)
         n = origin.shape[0]
         out, cnt = np.zeros((n, n)), np.zeros(1, np.int32)
         chrom_end = self.n_chrom if chrom_end is None else chrom_end
@@ -869,9 +881,7 @@ class Context:
         the marker that has it (the lowest among equal ones; -1 and a maximum of 0 where the replicate cannot be fitted),
         n_boot[B][C'] the individuals drawn, counted as often as drawn, and with profile boot_lod[B][T][M'] (else None).
         The model: include/cnf2hip.h; qtl.boot_interval reads boot_arg."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        origin = self._origin_rows(origin)
         return self._qtl_boot_call(origin.shape[0], _p(origin), pheno, count, chrom_begin, chrom_end, cov, use, profile,
                                    QTL_ADDITIVE if additive else 0, out)
 
@@ -910,9 +920,7 @@ class Context:
         the rows at every marker, with covariates cov[n][K], the individuals of use[n] and the permutations perm[P][n], each of
         which moves all traits of an individual together.  A dict: lod[M], rank[M], trait_rank[C] (the traits kept),
         n_used[C], perm_max[P][C] (None without permutations).  The model: include/cnf2hip.h; qtl.scan_mv reads it."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        origin = self._origin_rows(origin)
         return self._qtlmv_call(origin.shape[0], _p(origin), pheno, cov, use, perm, QTL_ADDITIVE if additive else 0, out)
 
     def qtl_scan_mv_device(self, n, d_origin, pheno, cov=None, use=None, perm=None, additive=False, d_out=None):
@@ -957,9 +965,7 @@ class Context:
         on one chromosome), rank_add[L][L], rank_full[L][L] -- cells j < k only, the others NaN / -1 -- rss0[T][C][C],
         n_used[C][C], perm_max[P][T][3] (the maxima of lod_add, lod_full and lod_full - lod_add; None without
         permutations).  The model: include/cnf2hip.h; cnf2freq_amd/qtl.py reads the results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        origin = self._origin_rows(origin)
         return self._qtl2_call(origin.shape[0], _p(origin), sel, pheno, cov, use, perm, QTL_ADDITIVE if additive else 0)
 
     def qtl_scan2_device(self, n, d_origin, sel, pheno, cov=None, use=None, perm=None, additive=False):
@@ -984,8 +990,7 @@ class Context:
         """cnf2_qtl_scanx with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
         pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
         T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
-        ne = 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
-        o = self._qtlx_outputs(T, P, ne * (1 + max(0, int(interactive)))) if out is None else out
+        o = self._qtlx_outputs(T, P, self._n_effects(flags) * (1 + max(0, int(interactive)))) if out is None else out
         opt = lambda a: None if a is None else _p(a)
         self._chk(self.L.cnf2_qtl_scanx(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), int(interactive), P, opt(perm),
                                         _p(o["lod"]), _p(o["coef"]), _p(o["rank"]), _p(o["rss0"]), _p(o["n_used"]),
@@ -1000,9 +1005,7 @@ class Context:
         column), rank[M][3] (cumulative), rss0[T][C], n_used[C], perm_max[P][T][C][5] (the maxima of the three LODs, of
         lod[1] - lod[0] and of lod[2] - lod[1]; None without permutations).  The model: include/cnf2hip.h;
         cnf2freq_amd/qtl.py reads the results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        origin = self._origin_rows(origin)
         return self._qtlx_call(origin.shape[0], _p(origin), pheno, cov, interactive, use, perm,
                                (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0), out)
 
@@ -1056,9 +1059,7 @@ class Context:
         against the null model), coef[T][M][ne] (the marker's effects in the full model, NaN for a dropped one), rank[M],
         rank_cof[M], rss0[T][C], n_used[C], perm_max[P][T][C] (the maxima over the markers in no range; None without
         permutations).  The model: include/cnf2hip.h; cnf2freq_amd/qtl.py reads the results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
+        origin = self._origin_rows(origin)
         return self._qtlcof_call(origin.shape[0], _p(origin), pheno, cof, excl, cov, use, perm, QTL_ADDITIVE if additive else 0, out)
 
     def qtl_scan_cof_device(self, n, d_origin, pheno, cof, excl=None, cov=None, use=None, perm=None, additive=False):
@@ -1081,26 +1082,51 @@ class Context:
         """Cap on the phenotype columns per tile of qtl_scan_em (0 = what memory allows); results do not depend on it."""
         self._chk(self.L.cnf2_set_qtlem_columns(self.h, cap), "cnf2_set_qtlem_columns")
 
-    def _qtlem_outputs(self, T, P, ne):
-        M, Cn = self.n_markers, self.n_chrom
-        return dict(lod=np.zeros((T, M)), coef=np.zeros((T, M, ne)), sigma2=np.zeros((T, M)), iters=np.zeros((T, M), np.int32),
-                    status=np.zeros((T, M), np.int32), rank=np.zeros(M, np.int32), rss0=np.zeros((T, Cn)),
-                    n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn)) if P else None)
+    # The four scans that fit a model by iteration per (marker, column) -- EM, binary, survival, variance -- are called on one
+    # path, _qtlfit_call.  Per scan: the C function; the argument it takes beyond the shared ones ("status" behind the
+    # times, "n_var" behind the covariates); its outputs in the order of the C arguments, which is the order of the dict,
+    # each with its shape in letters -- T traits, M markers, C chromosomes, P permutations, E effects, 3 fits -- and dtype
+    _F, _I = np.float64, np.int32
+    _QTLFIT = dict(
+        em=("cnf2_qtl_scan_em", None,
+            (("lod", "TM", _F), ("coef", "TME", _F), ("sigma2", "TM", _F), ("iters", "TM", _I), ("status", "TM", _I),
+             ("rank", "M", _I), ("rss0", "TC", _F), ("n_used", "C", _I), ("perm_max", "PTC", _F))),
+        binary=("cnf2_qtl_scan_binary", None,
+                (("lod", "TM", _F), ("coef", "TME", _F), ("iters", "TM", _I), ("status", "TM", _I), ("rank", "M", _I),
+                 ("ll0", "TC", _F), ("n_ones", "TC", _I), ("n_used", "C", _I), ("perm_max", "PTC", _F))),
+        surv=("cnf2_qtl_scan_surv", "status",
+              (("lod", "TM", _F), ("coef", "TME", _F), ("iters", "TM", _I), ("status", "TM", _I), ("rank", "M", _I),
+               ("ll0", "TC", _F), ("n_events", "TC", _I), ("n_used", "C", _I), ("perm_max", "PTC", _F))),
+        var=("cnf2_qtl_scan_var", "n_var",
+             (("lod", "TM3", _F), ("coef_mean", "TME", _F), ("coef_var", "TME", _F), ("iters", "TM3", _I), ("status", "TM3", _I),
+              ("rank", "M", _I), ("ll0", "TC", _F), ("n_used", "C", _I), ("perm_max", "PTC3", _F))))
 
-    def _qtlem_call(self, n, origin_ptr, pheno, cov, use, perm, max_iter, tol, flags, out=None):
-        """cnf2_qtl_scan_em on the rows behind origin_ptr, with host outputs (out = None: new arrays; else a dict of arrays),
-        or with OUT_DEVICE in flags and out a dict of device pointers (ints; perm_max None without permutations)"""
+    def _qtlfit_call(self, scan, n, origin_ptr, pheno, cov, use, perm, max_iter, tol, flags, out=None, extra=None):
+        """The C function of _QTLFIT[scan] on the rows behind origin_ptr, with host outputs (out = None: new arrays; else a
+        dict of arrays), or with OUT_DEVICE in flags and out a dict of device pointers (ints; perm_max None without
+        permutations).  extra: the scan's own argument (survival: status, with pheno the times; variance: n_var)."""
+        name, own, outputs = self._QTLFIT[scan]
         pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
-        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
-        ne = 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
-        o = self._qtlem_outputs(T, P, ne) if out is None else out
         opt = lambda a: None if a is None else _p(a)
+        args = [self.h, n, origin_ptr, pheno.shape[1], _p(pheno)]
+        if own == "status":
+            extra = np.ascontiguousarray(extra, np.float64)
+            extra = extra[:, None] if extra.ndim == 1 else extra
+            if extra.shape != pheno.shape:
+                raise ValueError("status must have the shape of time")
+            args.append(_p(extra))
+        args += [opt(use), 0 if cov is None else cov.shape[1], opt(cov)]
+        if own == "n_var":
+            args.append(int(extra))
+        P = 0 if perm is None else perm.shape[0]
+        dim = dict(T=pheno.shape[1], M=self.n_markers, C=self.n_chrom, P=P, E=self._n_effects(flags))
+        if out is None:
+            out = {key: np.zeros([dim[c] if c in dim else int(c) for c in shape], dtype) if P or key != "perm_max" else None
+                   for key, shape, dtype in outputs}
         ptr = (lambda a: C.c_void_p(a) if a else None) if flags & OUT_DEVICE else opt
-        self._chk(self.L.cnf2_qtl_scan_em(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm), int(max_iter),
-                                          float(tol), ptr(o["lod"]), ptr(o["coef"]), ptr(o["sigma2"]), ptr(o["iters"]),
-                                          ptr(o["status"]), ptr(o["rank"]), ptr(o["rss0"]), ptr(o["n_used"]), ptr(o["perm_max"]),
-                                          flags), "cnf2_qtl_scan_em")
-        return o
+        self._chk(getattr(self.L, name)(*args, P, opt(perm), int(max_iter), float(tol), *[ptr(out[key]) for key, _, _ in outputs],
+                                        flags), name)
+        return out
 
     def qtl_scan_em(self, origin, pheno, cov=None, imprint=False, use=None, perm=None, additive=False, max_iter=1000, tol=1e-6,
                     out=None, flags=0):
@@ -1110,45 +1136,21 @@ class Context:
         coef[T][M][ne] (NaN for a dropped effect), sigma2[T][M], iters[T][M], status[T][M] (0 = stopped by tol, 1 = by
         max_iter, 2 = breakdown), rank[M], rss0[T][C], n_used[C], perm_max[P][T][C] (None without permutations).  The model:
         include/cnf2hip.h; cnf2freq_amd/qtl.py reads the results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
-        return self._qtlem_call(origin.shape[0], _p(origin), pheno, cov, use, perm, max_iter, tol,
-                                flags | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0), out)
+        origin = self._origin_rows(origin)
+        return self._qtlfit_call("em", origin.shape[0], _p(origin), pheno, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags, additive, imprint), out)
 
     def qtl_scan_em_device(self, n, d_origin, pheno, cov=None, imprint=False, use=None, perm=None, additive=False, max_iter=1000,
                            tol=1e-6, out=None, flags=0):
         """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
         sweep_qtl left in it, which this call leaves valid).  With OUT_DEVICE in flags, out is a dict of device pointers."""
-        return self._qtlem_call(n, C.c_void_p(d_origin), pheno, cov, use, perm, max_iter, tol,
-                                flags | QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0),
-                                out)
+        return self._qtlfit_call("em", n, C.c_void_p(d_origin), pheno, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags | QTL_ORIGIN_DEVICE, additive, imprint), out)
 
     # -- binary-trait single-locus scan: logistic regression --------------------------
     def set_qtlbin_columns(self, cap):
         """Cap on the phenotype columns per tile of qtl_scan_binary (0 = what memory allows); results do not depend on it."""
         self._chk(self.L.cnf2_set_qtlbin_columns(self.h, cap), "cnf2_set_qtlbin_columns")
-
-    def _qtlbin_outputs(self, T, P, ne):
-        M, Cn = self.n_markers, self.n_chrom
-        return dict(lod=np.zeros((T, M)), coef=np.zeros((T, M, ne)), iters=np.zeros((T, M), np.int32),
-                    status=np.zeros((T, M), np.int32), rank=np.zeros(M, np.int32), ll0=np.zeros((T, Cn)),
-                    n_ones=np.zeros((T, Cn), np.int32), n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn)) if P else None)
-
-    def _qtlbin_call(self, n, origin_ptr, pheno, cov, use, perm, max_iter, tol, flags, out=None):
-        """cnf2_qtl_scan_binary on the rows behind origin_ptr, with host outputs (out = None: new arrays; else a dict of
-        arrays), or with OUT_DEVICE in flags and out a dict of device pointers (ints; perm_max None without permutations)"""
-        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
-        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
-        ne = 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
-        o = self._qtlbin_outputs(T, P, ne) if out is None else out
-        opt = lambda a: None if a is None else _p(a)
-        ptr = (lambda a: C.c_void_p(a) if a else None) if flags & OUT_DEVICE else opt
-        self._chk(self.L.cnf2_qtl_scan_binary(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm), int(max_iter),
-                                              float(tol), ptr(o["lod"]), ptr(o["coef"]), ptr(o["iters"]), ptr(o["status"]),
-                                              ptr(o["rank"]), ptr(o["ll0"]), ptr(o["n_ones"]), ptr(o["n_used"]), ptr(o["perm_max"]),
-                                              flags), "cnf2_qtl_scan_binary")
-        return o
 
     def qtl_scan_binary(self, origin, pheno, cov=None, imprint=False, use=None, perm=None, additive=False, max_iter=50, tol=1e-7,
                         out=None, flags=0):
@@ -1158,19 +1160,16 @@ class Context:
         dropped effect), iters[T][M], status[T][M] (0 = stopped by tol, 1 = by max_iter, 2 = breakdown), rank[M], ll0[T][C],
         n_ones[T][C], n_used[C], perm_max[P][T][C] (None without permutations).  The model: include/cnf2hip.h;
         cnf2freq_amd/qtl.py reads the results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
-        return self._qtlbin_call(origin.shape[0], _p(origin), pheno, cov, use, perm, max_iter, tol,
-                                 flags | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0), out)
+        origin = self._origin_rows(origin)
+        return self._qtlfit_call("binary", origin.shape[0], _p(origin), pheno, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags, additive, imprint), out)
 
     def qtl_scan_binary_device(self, n, d_origin, pheno, cov=None, imprint=False, use=None, perm=None, additive=False, max_iter=50,
                                tol=1e-7, out=None, flags=0):
         """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
         sweep_qtl left in it, which this call leaves valid).  With OUT_DEVICE in flags, out is a dict of device pointers."""
-        return self._qtlbin_call(n, C.c_void_p(d_origin), pheno, cov, use, perm, max_iter, tol,
-                                 flags | QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0),
-                                 out)
+        return self._qtlfit_call("binary", n, C.c_void_p(d_origin), pheno, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags | QTL_ORIGIN_DEVICE, additive, imprint), out)
 
     # -- survival-trait single-locus scan: Cox regression ------------------------------
     def set_qtlsurv_columns(self, cap):
@@ -1181,32 +1180,6 @@ class Context:
         """Cap on the blocks of qtl_scan_surv's launches (0 = the default); results do not depend on it."""
         self._chk(self.L.cnf2_set_qtlsurv_blocks(self.h, cap), "cnf2_set_qtlsurv_blocks")
 
-    def _qtlsurv_outputs(self, T, P, ne):
-        M, Cn = self.n_markers, self.n_chrom
-        return dict(lod=np.zeros((T, M)), coef=np.zeros((T, M, ne)), iters=np.zeros((T, M), np.int32),
-                    status=np.zeros((T, M), np.int32), rank=np.zeros(M, np.int32), ll0=np.zeros((T, Cn)),
-                    n_events=np.zeros((T, Cn), np.int32), n_used=np.zeros(Cn, np.int32),
-                    perm_max=np.zeros((P, T, Cn)) if P else None)
-
-    def _qtlsurv_call(self, n, origin_ptr, time, status, cov, use, perm, max_iter, tol, flags, out=None):
-        """cnf2_qtl_scan_surv on the rows behind origin_ptr, with host outputs (out = None: new arrays; else a dict of
-        arrays), or with OUT_DEVICE in flags and out a dict of device pointers (ints; perm_max None without permutations)"""
-        time, cov, use, perm = self._qtl_inputs(n, time, cov, use, perm)
-        status = np.ascontiguousarray(status, np.float64)
-        status = status[:, None] if status.ndim == 1 else status
-        if status.shape != time.shape:
-            raise ValueError("status must have the shape of time")
-        T, K, P = time.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
-        ne = 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
-        o = self._qtlsurv_outputs(T, P, ne) if out is None else out
-        opt = lambda a: None if a is None else _p(a)
-        ptr = (lambda a: C.c_void_p(a) if a else None) if flags & OUT_DEVICE else opt
-        self._chk(self.L.cnf2_qtl_scan_surv(self.h, n, origin_ptr, T, _p(time), _p(status), opt(use), K, opt(cov), P, opt(perm),
-                                            int(max_iter), float(tol), ptr(o["lod"]), ptr(o["coef"]), ptr(o["iters"]),
-                                            ptr(o["status"]), ptr(o["rank"]), ptr(o["ll0"]), ptr(o["n_events"]), ptr(o["n_used"]),
-                                            ptr(o["perm_max"]), flags), "cnf2_qtl_scan_surv")
-        return o
-
     def qtl_scan_surv(self, origin, time, status, cov=None, imprint=False, use=None, perm=None, additive=False, max_iter=50,
                       tol=1e-7, out=None, flags=0):
         """cnf2_qtl_scan_surv on host rows origin[n][M][4]: per marker Cox's proportional hazards regression of the columns
@@ -1216,45 +1189,21 @@ class Context:
         (0 = stopped by tol, 1 = by max_iter, 2 = breakdown), rank[M], ll0[T][C], n_events[T][C], n_used[C],
         perm_max[P][T][C] (None without permutations).  The model: include/cnf2hip.h; cnf2freq_amd/qtl.py reads the
         results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
-        return self._qtlsurv_call(origin.shape[0], _p(origin), time, status, cov, use, perm, max_iter, tol,
-                                  flags | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0), out)
+        origin = self._origin_rows(origin)
+        return self._qtlfit_call("surv", origin.shape[0], _p(origin), time, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags, additive, imprint), out, status)
 
     def qtl_scan_surv_device(self, n, d_origin, time, status, cov=None, imprint=False, use=None, perm=None, additive=False,
                              max_iter=50, tol=1e-7, out=None, flags=0):
         """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
         sweep_qtl left in it, which this call leaves valid).  With OUT_DEVICE in flags, out is a dict of device pointers."""
-        return self._qtlsurv_call(n, C.c_void_p(d_origin), time, status, cov, use, perm, max_iter, tol,
-                                  flags | QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0),
-                                  out)
+        return self._qtlfit_call("surv", n, C.c_void_p(d_origin), time, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags | QTL_ORIGIN_DEVICE, additive, imprint), out, status)
 
     # -- variance-QTL single-locus scan: mean and log-variance effects ------------------
     def set_qtlvar_columns(self, cap):
         """Cap on the columns per tile of qtl_scan_var (0 = what memory allows); results do not depend on it."""
         self._chk(self.L.cnf2_set_qtlvar_columns(self.h, cap), "cnf2_set_qtlvar_columns")
-
-    def _qtlvar_outputs(self, T, P, ne):
-        M, Cn = self.n_markers, self.n_chrom
-        return dict(lod=np.zeros((T, M, 3)), coef_mean=np.zeros((T, M, ne)), coef_var=np.zeros((T, M, ne)),
-                    iters=np.zeros((T, M, 3), np.int32), status=np.zeros((T, M, 3), np.int32), rank=np.zeros(M, np.int32),
-                    ll0=np.zeros((T, Cn)), n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn, 3)) if P else None)
-
-    def _qtlvar_call(self, n, origin_ptr, pheno, cov, n_var, use, perm, max_iter, tol, flags, out=None):
-        """cnf2_qtl_scan_var on the rows behind origin_ptr, with host outputs (out = None: new arrays; else a dict of
-        arrays), or with OUT_DEVICE in flags and out a dict of device pointers (ints; perm_max None without permutations)"""
-        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
-        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
-        ne = 1 + (0 if flags & QTL_ADDITIVE else 1) + (1 if flags & QTL_IMPRINT else 0)
-        o = self._qtlvar_outputs(T, P, ne) if out is None else out
-        opt = lambda a: None if a is None else _p(a)
-        ptr = (lambda a: C.c_void_p(a) if a else None) if flags & OUT_DEVICE else opt
-        self._chk(self.L.cnf2_qtl_scan_var(self.h, n, origin_ptr, T, _p(pheno), opt(use), K, opt(cov), int(n_var), P, opt(perm),
-                                           int(max_iter), float(tol), ptr(o["lod"]), ptr(o["coef_mean"]), ptr(o["coef_var"]),
-                                           ptr(o["iters"]), ptr(o["status"]), ptr(o["rank"]), ptr(o["ll0"]), ptr(o["n_used"]),
-                                           ptr(o["perm_max"]), flags), "cnf2_qtl_scan_var")
-        return o
 
     def qtl_scan_var(self, origin, pheno, cov=None, n_var=0, imprint=False, use=None, perm=None, additive=False, max_iter=50,
                      tol=1e-7, out=None, flags=0):
@@ -1265,19 +1214,16 @@ class Context:
         coef_var[T][M][ne] of the full fit (NaN for a dropped effect), iters and status[T][M][3] by fit (0 = stopped by tol,
         1 = by max_iter, 2 = breakdown), rank[M], ll0[T][C], n_used[C], perm_max[P][T][C][3] (None without permutations).
         The model: include/cnf2hip.h; cnf2freq_amd/qtl.py reads the results."""
-        origin = np.ascontiguousarray(origin, np.float64)
-        if origin.ndim != 3 or origin.shape[1:] != (self.n_markers, 4):
-            raise ValueError("origin must be [n][%d][4]" % self.n_markers)
-        return self._qtlvar_call(origin.shape[0], _p(origin), pheno, cov, n_var, use, perm, max_iter, tol,
-                                 flags | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0), out)
+        origin = self._origin_rows(origin)
+        return self._qtlfit_call("var", origin.shape[0], _p(origin), pheno, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags, additive, imprint), out, n_var)
 
     def qtl_scan_var_device(self, n, d_origin, pheno, cov=None, n_var=0, imprint=False, use=None, perm=None, additive=False,
                             max_iter=50, tol=1e-7, out=None, flags=0):
         """The same on device rows, read in place (d_origin as for qtl_scan_device; None: the rows this context's last
         sweep_qtl left in it, which this call leaves valid).  With OUT_DEVICE in flags, out is a dict of device pointers."""
-        return self._qtlvar_call(n, C.c_void_p(d_origin), pheno, cov, n_var, use, perm, max_iter, tol,
-                                 flags | QTL_ORIGIN_DEVICE | (QTL_ADDITIVE if additive else 0) | (QTL_IMPRINT if imprint else 0),
-                                 out)
+        return self._qtlfit_call("var", n, C.c_void_p(d_origin), pheno, cov, use, perm, max_iter, tol,
+                                 self._fit_flags(flags | QTL_ORIGIN_DEVICE, additive, imprint), out, n_var)
 
     def turn_scan_rows(self, ind, chrom=0):
         mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])

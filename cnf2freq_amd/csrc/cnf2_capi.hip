@@ -82,6 +82,14 @@ struct DevBuf {
     int ensure(cnf2_ctx* ctx, size_t count) { return (cap >= count && ptr) ? CNF2_OK : alloc(ctx, count); }
 };
 
+// What each of the four iteratively fitted scans keeps (qtl_fit_scan): the marker map (chromstarts, marker -> chromosome, tiles
+// of 4, tile starts), which effects a marker keeps, which chromosomes are scanned, the null fits, the tile maxima, and the
+// staged outputs
+struct QtlFitBufs {
+    DevBuf<double>  null, tilemax, lod, coef, ll0, pmax;      // ll0: the EM scan's rss0
+    DevBuf<int32_t> map, keep, scan, nc, rank, iters, status;
+};
+
 // the scans whose column tile the caller can cap (cnf2_set_*_columns); the column scan shares the single scan's, and the
 // multi-trait scan's cap counts groups (cnf2_set_qtlmv_groups)
 enum QtlCap { QTL_CAP_SCAN, QTL_CAP_SCAN2, QTL_CAP_SCANX, QTL_CAP_COF, QTL_CAP_EM, QTL_CAP_BIN, QTL_CAP_MV, QTL_CAP_SURV, QTL_CAP_VAR, QTL_CAP_IMP, QTL_CAP_COUNT };
@@ -211,30 +219,21 @@ struct cnf2_ctx {
     DevBuf<double>  d_qc_img, d_qc_yy, d_qc_tilemax, d_qc_lod, d_qc_lod_base, d_qc_coef, d_qc_rss0, d_qc_pmax;
     DevBuf<int32_t> d_qc_map, d_qc_nc, d_qc_rank, d_qc_rank_cof;   // d_qc_map: chromstarts, tiles, tile starts, cof, their chromosomes' starts, skip words
 
-    // maximum-likelihood single-locus scan (cnf2_qtl_scan_em): which effects a marker keeps, the tile
-    // maxima, staged outputs; the staged inputs, the mask, the factor, the column image and the null fit are the single
-    // scan's buffers
-    DevBuf<double>  d_qe_tilemax, d_qe_lod, d_qe_coef, d_qe_sigma2, d_qe_rss0, d_qe_rss0_null, d_qe_pmax;   // _null: what qtl_null_kernel reports
-    DevBuf<int32_t> d_qe_map, d_qe_keep, d_qe_nc, d_qe_rank, d_qe_iters, d_qe_status;   // d_qe_map: as d_q_map, tiles of 4
-
-    // binary-trait single-locus scan (cnf2_qtl_scan_binary): which effects a marker keeps, which chromosomes
-    // are scanned, the null fits, the tile maxima, staged outputs; the staged inputs, the mask and the column image are the
-    // single scan's buffers (d_q_chol only receives what qtl_chrom_kernel writes beside the mask: this scan does not read it)
-    DevBuf<double>  d_qb_null, d_qb_tilemax, d_qb_lod, d_qb_coef, d_qb_ll0, d_qb_pmax;
-    DevBuf<int32_t> d_qb_map, d_qb_keep, d_qb_scan, d_qb_nc, d_qb_rank, d_qb_iters, d_qb_status, d_qb_ones;   // d_qb_map: as d_qe_map
-
-    // survival-trait single-locus scan (cnf2_qtl_scan_surv): the order words of a column tile, the waves' work rows, and what
-    // the binary scan keeps under d_qb_*; the staged inputs and the mask are the single scan's buffers (the times are staged
-    // as its phenotypes and read by no kernel)
-    DevBuf<uint32_t> d_qs_ord;
-    DevBuf<double>   d_qs_work, d_qs_null, d_qs_tilemax, d_qs_lod, d_qs_coef, d_qs_ll0, d_qs_pmax;
-    DevBuf<int32_t>  d_qs_map, d_qs_keep, d_qs_scan, d_qs_nc, d_qs_rank, d_qs_iters, d_qs_status, d_qs_events;
-    int              qtlsurv_blocks = 0;      // cnf2_set_qtlsurv_blocks
-
-    // variance-QTL single-locus scan (cnf2_qtl_scan_var): what the binary scan keeps under d_qb_*, with three LODs per cell
-    // and the full fit's coefficients of both parts; the staged inputs, the mask and the column image are the single scan's
-    DevBuf<double>  d_qv_null, d_qv_tilemax, d_qv_lod, d_qv_coef, d_qv_coefv, d_qv_ll0, d_qv_pmax;
-    DevBuf<int32_t> d_qv_map, d_qv_keep, d_qv_scan, d_qv_nc, d_qv_rank, d_qv_iters, d_qv_status;
+    // The four scans that fit a model by iteration per (marker, column) -- cnf2_qtl_scan_em, _binary, _surv, _var -- run through
+    // one driver (qtl_fit_scan) on one QtlFitBufs each; what only one of them has stands beside its instance.  The staged
+    // inputs, the mask and the column image are the single scan's buffers, and for the EM scan the factor and the null fit
+    // too (d_q_chol only receives what qtl_chrom_kernel writes beside the mask: the other three do not read it).
+    QtlFitBufs       qe;                             // EM: no scan words, no null fits of its own
+    DevBuf<double>   d_qe_sigma2, d_qe_rss0_null;    // _null: what qtl_null_kernel reports
+    QtlFitBufs       qb;                             // binary
+    DevBuf<int32_t>  d_qb_ones;
+    QtlFitBufs       qs;                             // survival (the times are staged as the phenotypes and read by no kernel)
+    DevBuf<int32_t>  d_qs_events;
+    DevBuf<uint32_t> d_qs_ord;                       // the order words of a column tile
+    DevBuf<double>   d_qs_work;                      // the waves' work rows
+    int              qtlsurv_blocks = 0;             // cnf2_set_qtlsurv_blocks
+    QtlFitBufs       qv;                             // variance: three fits per cell
+    DevBuf<double>   d_qv_coefv;                     // the full fit's coefficients of the variance part
 
     // kinship sums (cnf2_kinship_sums): the image a[m_pad][n_pad], the chunks' partial sums of a split range, the staged sum
     DevBuf<double>  d_kin_image, d_kin_part, d_kin_sum;
@@ -2584,383 +2583,302 @@ int cnf2_qtl_scan_cof(cnf2_ctx* ctx, int n, const double* origin, int n_traits, 
     return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
-// The maximum-likelihood single-locus scan on origin rows [n][M][4]: cnf2_qtlem.h, cnf2_qtlem_kernels.hip.  The masks, the
-// factor of S11, the column image and the null fit are the kernels of cnf2_qtl_kernels.hip.
+// The four single-locus scans on origin rows [n][M][4] that fit a model by iteration per (marker, column) -- EM interval
+// mapping, logistic, Cox and mean-variance regression -- through one driver, qtl_fit_scan.  What a scan says of itself:
+struct QtlFitSpec {
+    QtlCap cap;                 // its column cap
+    int    tile;                // markers per tile
+    int    nfit;                // fits per cell: lod, iters, status, perm_max and the tile maxima carry the factor
+    int    nullq;               // doubles of a null fit per (chromosome, column); unused by the EM scan, which reads the single scan's
+    bool   image;               // it reads the column image (qtl_gather_kernel)
+    bool   extra_behind_coef;   // its one output beyond the shared ones follows coef in its list (else ll0)
+};
+// ... and what the driver tells it of the plan
+struct QtlFitPlan {
+    size_t rt, n_tiles, cells, ne;   // columns per tile, marker tiles, T x M, effects
+};
+static int qtl_fit_reserve_nothing(const QtlFitPlan&) { return CNF2_OK; }
+
+static int qtl_fit_check_iter(cnf2_ctx* ctx, int max_iter, int most, double tol)
+{
+    if (max_iter < 1 || max_iter > most) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", most);
+    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
+    return CNF2_OK;
+}
+// the values v[n][T] (`what`: "phenotype", "status") of the used individuals are 0 or 1
+static int qtl_fit_check_01(cnf2_ctx* ctx, const QtlArgs& a, const std::vector<uint8_t>& use, const double* v, const char* what)
+{
+    for (int i = 0; i < a.n; i++) {
+        if (!use[i]) continue;
+        for (int t = 0; t < a.T; t++) {
+            const double y = v[(size_t)i * a.T + t];
+            if (!(y == 0.0 || y == 1.0)) return fail(ctx, CNF2_ERR_ARG, "%s %d of individual %d is used and neither 0 nor 1", what, t, i);
+        }
+    }
+    return CNF2_OK;
+}
+// qtl_centre with each difference rounded once (qtl_centre_columns_once: a shifted column gives the same bits, which a fit
+// of a nearly collinear marker needs for the same printed effects); the covariates, and with `traits` the traits too
+static void qtl_centre_once(QtlArgs& a, const std::vector<uint8_t>& use, QtlCentred& store, bool traits)
+{
+    if (traits) {
+        qtl_centre_columns_once(a.pheno, a.n, a.T, use, store.pheno);
+        a.pheno = store.pheno.data();
+    }
+    if (a.K > 0) {
+        qtl_centre_columns_once(a.cov, a.n, a.K, use, store.cov);
+        a.cov = store.cov.data();
+    }
+}
+
+// The driver.  q: the scan's QtlemParams (the EM scan: the factor and the null fit are the single scan's, qtl_null_kernel
+// runs per tile, and there are no scan words) or QtlbinParams (the null fits and scan words are the scan's own), zeroed by
+// the caller, who may hold it inside a larger struct.  The callables are the scan's own part of a step: check(a, use,
+// centred) its argument checks behind qtl_check's and its centring; extra(each, plan) its extra output; start() and
+// tile(last), with q.r0 and q.rn set, its launches before the column tiles and per tile; reserve(plan) its own allocations.
+// The masks, n_c, the column image and the EM scan's null fit are launched here (cnf2_qtl_kernels.hip).
+extern "C++" template <class Q, class Check, class Extra, class Start, class Tile, class Reserve = int (*)(const QtlFitPlan&)>
+static int qtl_fit_scan(cnf2_ctx* ctx, const QtlFitSpec& s, QtlFitBufs& b, int n, const double* origin, QtlArgs a, int max_iter,
+                        double tol, int32_t* iters_out, int32_t* status_out, uint32_t flags, Q& q, Check check, Extra extra,
+                        Start start, Tile tile, Reserve reserve = qtl_fit_reserve_nothing)
+{
+    constexpr bool em = std::is_same<Q, QtlemParams>::value;
+    QtlOrigin      org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
+    std::vector<uint8_t> mask;
+    QtlCentred           centred;
+    RC_TRY(qtl_check(ctx, a, &mask));
+    RC_TRY(check(a, mask, centred));
+    const QtlemDesign ds = qtlem_design(a.K, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
+    const int M = ctx->n_markers, C = ctx->n_chrom;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), TC = (size_t)a.T * C;
+    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, s.tile, true, true);
+    const size_t       n_tiles = map.n_tiles, cells = (size_t)a.T * M;
+    const size_t       rt = qtl_column_tile(a.n, R, a.P, s.nfit * n_tiles, ctx->qtl_columns[s.cap]);
+    const QtlFitPlan   plan = {rt, n_tiles, cells, (size_t)ds.ne};
+
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, s.image ? rt : 0, 0));
+    QtlParams g = qtl_gather_params(ctx, a, rt);   // ... and the other kernels of cnf2_qtl_kernels.hip read and write
+    double**  ll0;
+    if constexpr (em) ll0 = &q.rss0;
+    else ll0 = &q.ll0;
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(a.n_used, b.nc, (size_t)C, &g.nc));
+        RC_TRY(each(a.rank, b.rank, (size_t)M, &q.rank));
+        RC_TRY(each(a.lod, b.lod, cells * s.nfit, &q.lod));
+        RC_TRY(each(a.coef, b.coef, cells * ds.ne, &q.coef));
+        if (s.extra_behind_coef) RC_TRY(extra(each, plan));
+        RC_TRY(each(iters_out, b.iters, cells * s.nfit, &q.iters));
+        RC_TRY(each(status_out, b.status, cells * s.nfit, &q.status));
+        RC_TRY(each(a.rss0, b.ll0, TC, ll0));
+        if (!s.extra_behind_coef) RC_TRY(extra(each, plan));
+        return each(a.pmax, b.pmax, (size_t)a.P * TC * s.nfit, &q.pmax);
+    };
+    RC_TRY(b.map.ensure(ctx, map.image.size()));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(b.keep.ensure(ctx, (size_t)M));
+    if constexpr (em) {
+        RC_TRY(ctx->d_q_null.ensure(ctx, (size_t)C * (ds.nx + 1) * rt));
+        RC_TRY(ctx->d_qe_rss0_null.ensure(ctx, TC));
+    } else {
+        RC_TRY(b.scan.ensure(ctx, (size_t)C));
+        RC_TRY(b.null.ensure(ctx, (size_t)C * s.nullq * rt));
+    }
+    RC_TRY(reserve(plan));
+    if (a.P > 0) RC_TRY(b.tilemax.ensure(ctx, n_tiles * s.nfit * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, b.map, map.image.data(), map.image.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = ds.nx;
+    g.origin = org.dev, g.cov = ctx->d_q_cov;
+    g.cs = b.map, g.mchrom = b.map + map.o_mchrom;
+    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol;
+    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
+    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
+    q.max_iter = max_iter, q.tol = tol;
+    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
+    q.tiles = b.map + map.o_tiles, q.tile_start = b.map + map.o_tstart, q.n_tiles = (int)n_tiles;
+    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = b.keep;
+    q.Y = s.image ? ctx->d_q_Y.ptr : nullptr, q.tilemax = b.tilemax, q.rstride = (int)rt;
+    if constexpr (em) {
+        g.nullq = ctx->d_q_null, g.rss0 = ctx->d_qe_rss0_null;
+        q.chol = ctx->d_q_chol, q.nullq = ctx->d_q_null;
+    } else {
+        q.scan = b.scan, q.nullq = b.null;
+        HIP_TRY(ctx, hipMemsetAsync(b.scan.ptr, 0, (size_t)C * sizeof(int32_t), ctx->stream));     // (a chromosome without markers has no thread to say so)
+    }
+
+    launch_qtl_chrom(g, ctx->stream);
+    start();
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = g.r0 = (int)r0;
+        q.rn = g.rn = (int)std::min(rt, R - r0);
+        if (s.image) launch_qtl_gather(g, ctx->stream);
+        if constexpr (em) launch_qtl_null(g, ctx->stream);
+        RC_TRY(tile(r0 + q.rn > (size_t)a.T));
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
+}
+
+// The maximum-likelihood scan: cnf2_qtlem.h, cnf2_qtlem_kernels.hip.  Traits and covariates are centred as in the single scan.
 int cnf2_qtl_scan_em(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                      const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
                      double* coef_out, double* sigma2_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out,
                      double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    QtlOrigin org;
-    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
-    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
-    std::vector<uint8_t> mask;
-    QtlCentred           centred;
-    RC_TRY(qtl_validate(ctx, a, &mask, &centred));
-    if (!sigma2_out || !iters_out || !status_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
-    if (max_iter < 1 || max_iter > QTLEM_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLEM_MAX_ITER);
-    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
-    const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
-    const int M = ctx->n_markers, C = ctx->n_chrom, nx = ds.nx;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
-    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLEM_TILE, true, true);
-    const size_t       n_tiles = map.n_tiles;
-    const size_t       rt = qtl_column_tile(a.n, R, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_EM]);
-
-    RC_TRY(qtl_origin_reserve(ctx, org));
-    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
-    QtlemParams q;
+    const QtlArgs args = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, rss0_out, perm_max_out, rank_out, n_used_out};
+    QtlemParams   q;
     memset(&q, 0, sizeof(q));
-    QtlParams g = qtl_gather_params(ctx, a, rt);   // ... and the other kernels of cnf2_qtl_kernels.hip read and write
-    auto outputs = [&](auto each) -> int {
-        RC_TRY(each(a.n_used, ctx->d_qe_nc, (size_t)C, &g.nc));
-        RC_TRY(each(a.rank, ctx->d_qe_rank, (size_t)M, &q.rank));
-        RC_TRY(each(a.lod, ctx->d_qe_lod, cells, &q.lod));
-        RC_TRY(each(a.coef, ctx->d_qe_coef, cells * ds.ne, &q.coef));
-        RC_TRY(each(sigma2_out, ctx->d_qe_sigma2, cells, &q.sigma2));
-        RC_TRY(each(iters_out, ctx->d_qe_iters, cells, &q.iters));
-        RC_TRY(each(status_out, ctx->d_qe_status, cells, &q.status));
-        RC_TRY(each(a.rss0, ctx->d_qe_rss0, (size_t)a.T * C, &q.rss0));
-        return each(a.pmax, ctx->d_qe_pmax, (size_t)a.P * a.T * C, &q.pmax);
-    };
-    RC_TRY(ctx->d_qe_map.ensure(ctx, map.image.size()));
-    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
-    RC_TRY(ctx->d_qe_keep.ensure(ctx, (size_t)M));
-    RC_TRY(ctx->d_q_null.ensure(ctx, (size_t)C * (nx + 1) * rt));
-    RC_TRY(ctx->d_qe_rss0_null.ensure(ctx, (size_t)a.T * C));
-    if (a.P > 0) RC_TRY(ctx->d_qe_tilemax.ensure(ctx, n_tiles * rt));
-    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
-    RC_TRY(qtl_origin_stage(ctx, org));
-    RC_TRY(qtl_upload(ctx, ctx->d_qe_map, map.image.data(), map.image.size()));
-    RC_TRY(qtl_upload_inputs(ctx, a, mask));
-
-    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = nx;
-    g.origin = org.dev, g.cov = ctx->d_q_cov;
-    g.cs = ctx->d_qe_map, g.mchrom = ctx->d_qe_map + map.o_mchrom;
-    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol, g.nullq = ctx->d_q_null, g.rss0 = ctx->d_qe_rss0_null;
-    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
-    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
-    q.max_iter = max_iter, q.tol = tol;
-    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
-    q.tiles = ctx->d_qe_map + map.o_tiles, q.tile_start = ctx->d_qe_map + map.o_tstart, q.n_tiles = (int)n_tiles;
-    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.chol = ctx->d_q_chol, q.keep = ctx->d_qe_keep;
-    q.Y = ctx->d_q_Y, q.nullq = ctx->d_q_null, q.tilemax = ctx->d_qe_tilemax, q.rstride = (int)rt;
-
-    launch_qtl_chrom(g, ctx->stream);
-    launch_qtlem_rank(q, ctx->stream);
-    for (size_t r0 = 0; r0 < R; r0 += rt) {
-        q.r0 = g.r0 = (int)r0;
-        q.rn = g.rn = (int)std::min(rt, R - r0);
-        launch_qtl_gather(g, ctx->stream);
-        launch_qtl_null(g, ctx->stream);
-        launch_qtlem_fit(q, ctx->stream);
-        if (r0 + q.rn > (size_t)a.T) launch_qtlem_finish(q, ctx->stream);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return qtl_fetch_outputs(ctx, dev, outputs);
+    return qtl_fit_scan(
+        ctx, {QTL_CAP_EM, QTLEM_TILE, 1, 0, true, true}, ctx->qe, n, origin, args, max_iter, tol, iters_out, status_out, flags, q,
+        [&](QtlArgs& a, const std::vector<uint8_t>& mask, QtlCentred& centred) -> int {
+            if (!sigma2_out || !iters_out || !status_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+            RC_TRY(qtl_fit_check_iter(ctx, max_iter, QTLEM_MAX_ITER, tol));
+            qtl_centre(a, mask, centred);
+            return CNF2_OK;
+        },
+        [&](auto each, const QtlFitPlan& plan) -> int { return each(sigma2_out, ctx->d_qe_sigma2, plan.cells, &q.sigma2); },
+        [&] { launch_qtlem_rank(q, ctx->stream); },
+        [&](bool last) -> int {
+            launch_qtlem_fit(q, ctx->stream);
+            if (last) launch_qtlem_finish(q, ctx->stream);
+            return CNF2_OK;
+        });
 }
 
-// The binary-trait single-locus scan on origin rows [n][M][4]: cnf2_qtlbin.h, cnf2_qtlbin_kernels.hip.  The masks, n_c and
-// the column image are the kernels of cnf2_qtl_kernels.hip.  The covariates are centred, each value minus the column's mean
-// rounded once (qtl_centre_columns_once: a shifted covariate gives the same bits, which a fit of a nearly collinear marker
-// needs for the same printed effects); the 0/1 trait is not.
+// The binary-trait scan: cnf2_qtlbin.h, cnf2_qtlbin_kernels.hip.  The covariates are centred, rounded once; the 0/1 trait is not.
 int cnf2_qtl_scan_binary(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                          const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
                          double* coef_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out,
                          int32_t* n_ones_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    QtlOrigin org;
-    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
-    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, ll0_out, perm_max_out, rank_out, n_used_out};
-    std::vector<uint8_t> mask;
-    QtlCentred           centred;
-    RC_TRY(qtl_check(ctx, a, &mask));
-    if (!iters_out || !status_out || !n_ones_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
-    if (max_iter < 1 || max_iter > QTLBIN_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLBIN_MAX_ITER);
-    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
-    for (int i = 0; i < a.n; i++) {
-        if (!mask[i]) continue;
-        for (int t = 0; t < a.T; t++) {
-            const double y = a.pheno[(size_t)i * a.T + t];
-            if (!(y == 0.0 || y == 1.0)) return fail(ctx, CNF2_ERR_ARG, "phenotype %d of individual %d is used and neither 0 nor 1", t, i);
-        }
-    }
-    if (a.K > 0) {
-        qtl_centre_columns_once(a.cov, a.n, a.K, mask, centred.cov);
-        a.cov = centred.cov.data();
-    }
-    const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
-    const int M = ctx->n_markers, C = ctx->n_chrom;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
-    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLBIN_TILE, true, true);
-    const size_t       n_tiles = map.n_tiles;
-    const size_t       rt = qtl_column_tile(a.n, R, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_BIN]);
-
-    RC_TRY(qtl_origin_reserve(ctx, org));
-    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
-    QtlbinParams q;
+    const QtlArgs args = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_out, ll0_out, perm_max_out, rank_out, n_used_out};
+    QtlbinParams  q;
     memset(&q, 0, sizeof(q));
-    QtlParams g = qtl_gather_params(ctx, a, rt);   // ... and qtl_chrom_kernel reads and writes
-    auto outputs = [&](auto each) -> int {
-        RC_TRY(each(a.n_used, ctx->d_qb_nc, (size_t)C, &g.nc));
-        RC_TRY(each(a.rank, ctx->d_qb_rank, (size_t)M, &q.rank));
-        RC_TRY(each(a.lod, ctx->d_qb_lod, cells, &q.lod));
-        RC_TRY(each(a.coef, ctx->d_qb_coef, cells * ds.ne, &q.coef));
-        RC_TRY(each(iters_out, ctx->d_qb_iters, cells, &q.iters));
-        RC_TRY(each(status_out, ctx->d_qb_status, cells, &q.status));
-        RC_TRY(each(ll0_out, ctx->d_qb_ll0, (size_t)a.T * C, &q.ll0));
-        RC_TRY(each(n_ones_out, ctx->d_qb_ones, (size_t)a.T * C, &q.n_ones));
-        return each(a.pmax, ctx->d_qb_pmax, (size_t)a.P * a.T * C, &q.pmax);
-    };
-    RC_TRY(ctx->d_qb_map.ensure(ctx, map.image.size()));
-    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
-    RC_TRY(ctx->d_qb_keep.ensure(ctx, (size_t)M));
-    RC_TRY(ctx->d_qb_scan.ensure(ctx, (size_t)C));
-    RC_TRY(ctx->d_qb_null.ensure(ctx, (size_t)C * QTLBIN_NULLQ * rt));
-    if (a.P > 0) RC_TRY(ctx->d_qb_tilemax.ensure(ctx, n_tiles * rt));
-    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
-    RC_TRY(qtl_origin_stage(ctx, org));
-    RC_TRY(qtl_upload(ctx, ctx->d_qb_map, map.image.data(), map.image.size()));
-    RC_TRY(qtl_upload_inputs(ctx, a, mask));
-
-    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = ds.nx;
-    g.origin = org.dev, g.cov = ctx->d_q_cov;
-    g.cs = ctx->d_qb_map, g.mchrom = ctx->d_qb_map + map.o_mchrom;
-    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol;
-    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
-    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
-    q.max_iter = max_iter, q.tol = tol;
-    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
-    q.tiles = ctx->d_qb_map + map.o_tiles, q.tile_start = ctx->d_qb_map + map.o_tstart, q.n_tiles = (int)n_tiles;
-    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = ctx->d_qb_keep, q.scan = ctx->d_qb_scan;
-    q.Y = ctx->d_q_Y, q.nullq = ctx->d_qb_null, q.tilemax = ctx->d_qb_tilemax, q.rstride = (int)rt;
-
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_qb_scan.ptr, 0, (size_t)C * sizeof(int32_t), ctx->stream));     // (a chromosome without markers has no thread to say so)
-    launch_qtl_chrom(g, ctx->stream);
-    launch_qtlbin_rank(q, ctx->stream);
-    for (size_t r0 = 0; r0 < R; r0 += rt) {
-        q.r0 = g.r0 = (int)r0;
-        q.rn = g.rn = (int)std::min(rt, R - r0);
-        launch_qtl_gather(g, ctx->stream);
-        launch_qtlbin_null(q, ctx->stream);
-        launch_qtlbin_fit(q, ctx->stream);
-        if (r0 + q.rn > (size_t)a.T) launch_qtlbin_finish(q, ctx->stream);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return qtl_fetch_outputs(ctx, dev, outputs);
+    return qtl_fit_scan(
+        ctx, {QTL_CAP_BIN, QTLBIN_TILE, 1, QTLBIN_NULLQ, true, false}, ctx->qb, n, origin, args, max_iter, tol, iters_out, status_out,
+        flags, q,
+        [&](QtlArgs& a, const std::vector<uint8_t>& mask, QtlCentred& centred) -> int {
+            if (!iters_out || !status_out || !n_ones_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+            RC_TRY(qtl_fit_check_iter(ctx, max_iter, QTLBIN_MAX_ITER, tol));
+            RC_TRY(qtl_fit_check_01(ctx, a, mask, a.pheno, "phenotype"));
+            qtl_centre_once(a, mask, centred, false);
+            return CNF2_OK;
+        },
+        [&](auto each, const QtlFitPlan&) -> int { return each(n_ones_out, ctx->d_qb_ones, (size_t)n_traits * ctx->n_chrom, &q.n_ones); },
+        [&] { launch_qtlbin_rank(q, ctx->stream); },
+        [&](bool last) -> int {
+            launch_qtlbin_null(q, ctx->stream);
+            launch_qtlbin_fit(q, ctx->stream);
+            if (last) launch_qtlbin_finish(q, ctx->stream);
+            return CNF2_OK;
+        });
 }
 
-// The survival-trait single-locus scan on origin rows [n][M][4]: cnf2_qtlsurv.h, cnf2_qtlsurv_kernels.hip.  The masks and n_c
-// are qtl_chrom_kernel's, the rank rule and the maxima of the permuted columns the binary scan's kernels.  No kernel reads a
-// time: the host puts every column of a tile in risk order (qtlsurv_order, the permuted columns as permuted) and the kernels
-// walk the order words.  The covariates are centred as in the binary scan.
+// The survival-trait scan: cnf2_qtlsurv.h, cnf2_qtlsurv_kernels.hip.  The rank rule and the maxima of the permuted columns are
+// the binary scan's kernels.  No kernel reads a time (they are checked as the phenotypes: a used time must be finite): the
+// host puts every column of a tile in risk order (qtlsurv_order, the permuted columns as permuted) and the kernels walk the
+// order words, so there is no column image.  The covariates are centred as in the binary scan.
 int cnf2_qtl_scan_surv(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* time, const double* status,
                        const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm, int max_iter, double tol,
                        double* lod_out, double* coef_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out, double* ll0_out,
                        int32_t* n_events_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    QtlOrigin org;
-    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
-    QtlArgs a = {n, n_traits, n_cov, n_perm, time, use, cov, perm, lod_out, coef_out, ll0_out, perm_max_out, rank_out, n_used_out};
-    std::vector<uint8_t> mask;
-    QtlCentred           centred;
-    RC_TRY(qtl_check(ctx, a, &mask));          // (with the times as the phenotypes: a used time must be finite)
-    if (!status || !iters_out || !status_out || !n_events_out) return fail(ctx, CNF2_ERR_ARG, "status or an output pointer is NULL");
-    if ((uint32_t)a.n > QTLSURV_IND) return fail(ctx, CNF2_ERR_ARG, "too many individuals");
-    if (max_iter < 1 || max_iter > QTLSURV_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLSURV_MAX_ITER);
-    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
-    for (int i = 0; i < a.n; i++) {
-        if (!mask[i]) continue;
-        for (int t = 0; t < a.T; t++) {
-            const double d = status[(size_t)i * a.T + t];
-            if (!(d == 0.0 || d == 1.0)) return fail(ctx, CNF2_ERR_ARG, "status %d of individual %d is used and neither 0 nor 1", t, i);
-        }
-    }
-    if (a.K > 0) {
-        qtl_centre_columns_once(a.cov, a.n, a.K, mask, centred.cov);
-        a.cov = centred.cov.data();
-    }
-    const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
-    const int M = ctx->n_markers, C = ctx->n_chrom;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
-    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLBIN_TILE, true, true);
-    const size_t       n_tiles = map.n_tiles;
-    // (the order words of a tile, 4 bytes each, stay under the column image's bound)
-    const size_t       rt = qtl_column_tile(a.n, R, a.P, n_tiles, ctx->qtl_columns[QTL_CAP_SURV]);
-    // The blocks of a launch: as many as it has cells, at most the cap, and no more than keep the work rows under 256 MB
-    const size_t cap = ctx->qtlsurv_blocks > 0 ? (size_t)ctx->qtlsurv_blocks : 1024;
-    const size_t fit_blocks  = std::max<size_t>(1, std::min(std::min(cap, n_tiles * rt), ((size_t)1 << 28) / (64 * (size_t)a.n)));
-    const size_t null_blocks = std::max<size_t>(1, std::min(fit_blocks, ((size_t)C * rt + QTLSURV_WAVES - 1) / QTLSURV_WAVES));
-
-    RC_TRY(qtl_origin_reserve(ctx, org));
-    RC_TRY(qtl_reserve_inputs(ctx, a, 0, 0));
+    const QtlArgs args = {n, n_traits, n_cov, n_perm, time, use, cov, perm, lod_out, coef_out, ll0_out, perm_max_out, rank_out, n_used_out};
     QtlsurvParams p;
     memset(&p, 0, sizeof(p));
-    QtlbinParams& q = p.b;
-    QtlParams     g = qtl_gather_params(ctx, a, rt);   // (what qtl_chrom_kernel reads and writes)
-    auto outputs = [&](auto each) -> int {
-        RC_TRY(each(a.n_used, ctx->d_qs_nc, (size_t)C, &g.nc));
-        RC_TRY(each(a.rank, ctx->d_qs_rank, (size_t)M, &q.rank));
-        RC_TRY(each(a.lod, ctx->d_qs_lod, cells, &q.lod));
-        RC_TRY(each(a.coef, ctx->d_qs_coef, cells * ds.ne, &q.coef));
-        RC_TRY(each(iters_out, ctx->d_qs_iters, cells, &q.iters));
-        RC_TRY(each(status_out, ctx->d_qs_status, cells, &q.status));
-        RC_TRY(each(ll0_out, ctx->d_qs_ll0, (size_t)a.T * C, &q.ll0));
-        RC_TRY(each(n_events_out, ctx->d_qs_events, (size_t)a.T * C, &q.n_ones));
-        return each(a.pmax, ctx->d_qs_pmax, (size_t)a.P * a.T * C, &q.pmax);
-    };
-    RC_TRY(ctx->d_qs_map.ensure(ctx, map.image.size()));
-    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
-    RC_TRY(ctx->d_qs_keep.ensure(ctx, (size_t)M));
-    RC_TRY(ctx->d_qs_scan.ensure(ctx, (size_t)C));
-    RC_TRY(ctx->d_qs_null.ensure(ctx, (size_t)C * QTLBIN_NULLQ * rt));
-    RC_TRY(ctx->d_qs_ord.ensure(ctx, rt * (size_t)a.n));
-    RC_TRY(ctx->d_qs_work.ensure(ctx, fit_blocks * QTLSURV_WAVES * 2 * (size_t)a.n));
-    if (a.P > 0) RC_TRY(ctx->d_qs_tilemax.ensure(ctx, n_tiles * rt));
-    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
-    RC_TRY(qtl_origin_stage(ctx, org));
-    RC_TRY(qtl_upload(ctx, ctx->d_qs_map, map.image.data(), map.image.size()));
-    RC_TRY(qtl_upload_inputs(ctx, a, mask));
-
-    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = ds.nx;
-    g.origin = org.dev, g.cov = ctx->d_q_cov;
-    g.cs = ctx->d_qs_map, g.mchrom = ctx->d_qs_map + map.o_mchrom;
-    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol;
-    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
-    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
-    q.max_iter = max_iter, q.tol = tol;
-    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
-    q.tiles = ctx->d_qs_map + map.o_tiles, q.tile_start = ctx->d_qs_map + map.o_tstart, q.n_tiles = (int)n_tiles;
-    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = ctx->d_qs_keep, q.scan = ctx->d_qs_scan;
-    q.nullq = ctx->d_qs_null, q.tilemax = ctx->d_qs_tilemax, q.rstride = (int)rt;
-    p.ord = ctx->d_qs_ord, p.work = ctx->d_qs_work;
-
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_qs_scan.ptr, 0, (size_t)C * sizeof(int32_t), ctx->stream));     // (a chromosome without markers has no thread to say so)
-    launch_qtl_chrom(g, ctx->stream);
-    launch_qtlbin_rank(q, ctx->stream);
-    std::vector<uint32_t> ord(rt * (size_t)a.n);
-    for (size_t r0 = 0; r0 < R; r0 += rt) {
-        q.r0 = (int)r0;
-        q.rn = (int)std::min(rt, R - r0);
-        for (int rr = 0; rr < q.rn; rr++) {
-            const size_t gr = r0 + rr, pq = gr / a.T, t = gr % a.T;
-            qtlsurv_order(a.n, time + t, status + t, (size_t)a.T, pq ? a.perm + (pq - 1) * (size_t)a.n : nullptr, mask.data(),
-                          ord.data() + (size_t)rr * a.n);
-        }
-        RC_TRY(qtl_upload(ctx, ctx->d_qs_ord, ord.data(), (size_t)q.rn * a.n));       // (complete on return: the tile before has been read)
-        p.fit_blocks  = (int)std::min(fit_blocks, n_tiles * (size_t)q.rn);
-        p.null_blocks = (int)std::min(null_blocks, ((size_t)C * q.rn + QTLSURV_WAVES - 1) / QTLSURV_WAVES);
-        launch_qtlsurv_null(p, ctx->stream);
-        launch_qtlsurv_fit(p, ctx->stream);
-        if (r0 + q.rn > (size_t)a.T) launch_qtlbin_finish(q, ctx->stream);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return qtl_fetch_outputs(ctx, dev, outputs);
+    QtlbinParams&         q = p.b;
+    const int             C = ctx->n_chrom;
+    const uint8_t*        used = nullptr;        // the expanded mask, once it is checked
+    size_t                fit_blocks = 0, null_blocks = 0, n_tiles = 0;
+    std::vector<uint32_t> ord;
+    return qtl_fit_scan(
+        ctx, {QTL_CAP_SURV, QTLBIN_TILE, 1, QTLBIN_NULLQ, false, false}, ctx->qs, n, origin, args, max_iter, tol, iters_out, status_out,
+        flags, q,
+        [&](QtlArgs& a, const std::vector<uint8_t>& mask, QtlCentred& centred) -> int {
+            if (!status || !iters_out || !status_out || !n_events_out) return fail(ctx, CNF2_ERR_ARG, "status or an output pointer is NULL");
+            if ((uint32_t)a.n > QTLSURV_IND) return fail(ctx, CNF2_ERR_ARG, "too many individuals");
+            RC_TRY(qtl_fit_check_iter(ctx, max_iter, QTLSURV_MAX_ITER, tol));
+            RC_TRY(qtl_fit_check_01(ctx, a, mask, status, "status"));
+            qtl_centre_once(a, mask, centred, false);
+            used = mask.data();
+            return CNF2_OK;
+        },
+        [&](auto each, const QtlFitPlan&) -> int { return each(n_events_out, ctx->d_qs_events, (size_t)n_traits * C, &q.n_ones); },
+        [&] { launch_qtlbin_rank(q, ctx->stream); },
+        [&](bool last) -> int {
+            for (int rr = 0; rr < q.rn; rr++) {
+                const size_t gr = (size_t)q.r0 + rr, pq = gr / n_traits, t = gr % n_traits;
+                qtlsurv_order(n, time + t, status + t, (size_t)n_traits, pq ? perm + (pq - 1) * (size_t)n : nullptr, used,
+                              ord.data() + (size_t)rr * n);
+            }
+            RC_TRY(qtl_upload(ctx, ctx->d_qs_ord, ord.data(), (size_t)q.rn * n));       // (complete on return: the tile before has been read)
+            p.fit_blocks  = (int)std::min(fit_blocks, n_tiles * (size_t)q.rn);
+            p.null_blocks = (int)std::min(null_blocks, ((size_t)C * q.rn + QTLSURV_WAVES - 1) / QTLSURV_WAVES);
+            launch_qtlsurv_null(p, ctx->stream);
+            launch_qtlsurv_fit(p, ctx->stream);
+            if (last) launch_qtlbin_finish(q, ctx->stream);
+            return CNF2_OK;
+        },
+        [&](const QtlFitPlan& plan) -> int {
+            // (the order words of a tile, 4 bytes each, stay under the column image's bound)
+            // The blocks of a launch: as many as it has cells, at most the cap, and no more than keep the work rows under 256 MB
+            const size_t cap = ctx->qtlsurv_blocks > 0 ? (size_t)ctx->qtlsurv_blocks : 1024;
+            n_tiles     = plan.n_tiles;
+            fit_blocks  = std::max<size_t>(1, std::min(std::min(cap, n_tiles * plan.rt), ((size_t)1 << 28) / (64 * (size_t)n)));
+            null_blocks = std::max<size_t>(1, std::min(fit_blocks, ((size_t)C * plan.rt + QTLSURV_WAVES - 1) / QTLSURV_WAVES));
+            ord.resize(plan.rt * (size_t)n);
+            RC_TRY(ctx->d_qs_ord.ensure(ctx, plan.rt * (size_t)n));
+            RC_TRY(ctx->d_qs_work.ensure(ctx, fit_blocks * QTLSURV_WAVES * 2 * (size_t)n));
+            p.ord = ctx->d_qs_ord, p.work = ctx->d_qs_work;
+            return CNF2_OK;
+        });
 }
 
-// The variance-QTL single-locus scan on origin rows [n][M][4]: cnf2_qtlvar.h, cnf2_qtlvar_kernels.hip.  The masks, n_c and the
-// column image are the kernels of cnf2_qtl_kernels.hip, the rank rule the binary scan's kernel.  The traits and the covariates
-// are centred, each value minus the column's mean rounded once (qtl_centre_columns_once).
+// The variance-QTL scan: cnf2_qtlvar.h, cnf2_qtlvar_kernels.hip.  The rank rule is the binary scan's kernel.  The traits and the
+// covariates are centred, rounded once.
 int cnf2_qtl_scan_var(cnf2_ctx* ctx, int n, const double* origin, int n_traits, const double* pheno, const uint8_t* use, int n_cov,
                       const double* cov, int n_var, int n_perm, const int32_t* perm, int max_iter, double tol, double* lod_out,
                       double* coef_mean_out, double* coef_var_out, int32_t* iters_out, int32_t* status_out, int32_t* rank_out,
                       double* ll0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
-    QtlOrigin org;
-    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
-    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_mean_out, ll0_out, perm_max_out, rank_out, n_used_out};
-    std::vector<uint8_t> mask;
-    QtlCentred           centred;
-    RC_TRY(qtl_check(ctx, a, &mask));
-    if (!coef_var_out || !iters_out || !status_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
-    if (n_var < 0 || n_var > std::min(a.K, QTLVAR_MAXV))
-        return fail(ctx, CNF2_ERR_ARG, "n_var must be 0 .. min(n_cov, %d)", QTLVAR_MAXV);
-    if (max_iter < 1 || max_iter > QTLVAR_MAX_ITER) return fail(ctx, CNF2_ERR_ARG, "max_iter must be 1 .. %d", QTLVAR_MAX_ITER);
-    if (!std::isfinite(tol)) return fail(ctx, CNF2_ERR_ARG, "tol must be finite");
-    qtl_centre_columns_once(a.pheno, a.n, a.T, mask, centred.pheno);
-    a.pheno = centred.pheno.data();
-    if (a.K > 0) {
-        qtl_centre_columns_once(a.cov, a.n, a.K, mask, centred.cov);
-        a.cov = centred.cov.data();
-    }
-    const QtlemDesign ds = qtlem_design(n_cov, (flags & CNF2_QTL_ADDITIVE) != 0, (flags & CNF2_QTL_IMPRINT) != 0);
-    const int M = ctx->n_markers, C = ctx->n_chrom;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    const bool         dev = (flags & CNF2_OUT_DEVICE) != 0;
-    const size_t       R = (size_t)a.T * ((size_t)a.P + 1), cells = (size_t)a.T * M;
-    const QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, QTLBIN_TILE, true, true);
-    const size_t       n_tiles = map.n_tiles;
-    const size_t       rt = qtl_column_tile(a.n, R, a.P, QTLVAR_NFIT * n_tiles, ctx->qtl_columns[QTL_CAP_VAR]);
-
-    RC_TRY(qtl_origin_reserve(ctx, org));
-    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
-    QtlvarParams p;
+    const QtlArgs args = {n, n_traits, n_cov, n_perm, pheno, use, cov, perm, lod_out, coef_mean_out, ll0_out, perm_max_out, rank_out, n_used_out};
+    QtlvarParams  p;
     memset(&p, 0, sizeof(p));
-    QtlbinParams& q = p.b;
-    QtlParams     g = qtl_gather_params(ctx, a, rt);   // ... and qtl_chrom_kernel reads and writes
-    auto outputs = [&](auto each) -> int {
-        RC_TRY(each(a.n_used, ctx->d_qv_nc, (size_t)C, &g.nc));
-        RC_TRY(each(a.rank, ctx->d_qv_rank, (size_t)M, &q.rank));
-        RC_TRY(each(a.lod, ctx->d_qv_lod, cells * QTLVAR_NFIT, &q.lod));
-        RC_TRY(each(a.coef, ctx->d_qv_coef, cells * ds.ne, &q.coef));
-        RC_TRY(each(coef_var_out, ctx->d_qv_coefv, cells * ds.ne, &p.coef_var));
-        RC_TRY(each(iters_out, ctx->d_qv_iters, cells * QTLVAR_NFIT, &q.iters));
-        RC_TRY(each(status_out, ctx->d_qv_status, cells * QTLVAR_NFIT, &q.status));
-        RC_TRY(each(ll0_out, ctx->d_qv_ll0, (size_t)a.T * C, &q.ll0));
-        return each(a.pmax, ctx->d_qv_pmax, (size_t)a.P * a.T * C * QTLVAR_NFIT, &q.pmax);
-    };
-    RC_TRY(ctx->d_qv_map.ensure(ctx, map.image.size()));
-    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
-    RC_TRY(ctx->d_qv_keep.ensure(ctx, (size_t)M));
-    RC_TRY(ctx->d_qv_scan.ensure(ctx, (size_t)C));
-    RC_TRY(ctx->d_qv_null.ensure(ctx, (size_t)C * QTLVAR_NULLQ * rt));
-    if (a.P > 0) RC_TRY(ctx->d_qv_tilemax.ensure(ctx, n_tiles * QTLVAR_NFIT * rt));
-    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
-    RC_TRY(qtl_origin_stage(ctx, org));
-    RC_TRY(qtl_upload(ctx, ctx->d_qv_map, map.image.data(), map.image.size()));
-    RC_TRY(qtl_upload_inputs(ctx, a, mask));
-
-    g.M = M, g.C = C, g.P = a.P, g.K = a.K, g.nx = ds.nx;
-    g.origin = org.dev, g.cov = ctx->d_q_cov;
-    g.cs = ctx->d_qv_map, g.mchrom = ctx->d_qv_map + map.o_mchrom;
-    g.cmask = ctx->d_q_cmask, g.chol = ctx->d_q_chol;
-    q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K;
-    q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0, q.imprint = (flags & CNF2_QTL_IMPRINT) ? 1 : 0;
-    q.max_iter = max_iter, q.tol = tol;
-    q.origin = org.dev, q.cov = ctx->d_q_cov, q.cs = g.cs, q.mchrom = g.mchrom;
-    q.tiles = ctx->d_qv_map + map.o_tiles, q.tile_start = ctx->d_qv_map + map.o_tstart, q.n_tiles = (int)n_tiles;
-    q.cmask = ctx->d_q_cmask, q.nc = g.nc, q.keep = ctx->d_qv_keep, q.scan = ctx->d_qv_scan;
-    q.Y = ctx->d_q_Y, q.nullq = ctx->d_qv_null, q.tilemax = ctx->d_qv_tilemax, q.rstride = (int)rt;
     p.n_var = n_var;
-
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_qv_scan.ptr, 0, (size_t)C * sizeof(int32_t), ctx->stream));     // (a chromosome without markers has no thread to say so)
-    launch_qtl_chrom(g, ctx->stream);
-    launch_qtlbin_rank(q, ctx->stream);
-    launch_qtlvar_threshold(p, ctx->stream);
-    for (size_t r0 = 0; r0 < R; r0 += rt) {
-        q.r0 = g.r0 = (int)r0;
-        q.rn = g.rn = (int)std::min(rt, R - r0);
-        launch_qtl_gather(g, ctx->stream);
-        launch_qtlvar_null(p, ctx->stream);
-        launch_qtlvar_fit(p, ctx->stream);
-        if (r0 + q.rn > (size_t)a.T) launch_qtlvar_finish(p, ctx->stream);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return qtl_fetch_outputs(ctx, dev, outputs);
+    return qtl_fit_scan(
+        ctx, {QTL_CAP_VAR, QTLBIN_TILE, QTLVAR_NFIT, QTLVAR_NULLQ, true, true}, ctx->qv, n, origin, args, max_iter, tol, iters_out,
+        status_out, flags, p.b,
+        [&](QtlArgs& a, const std::vector<uint8_t>& mask, QtlCentred& centred) -> int {
+            if (!coef_var_out || !iters_out || !status_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+            if (n_var < 0 || n_var > std::min(a.K, QTLVAR_MAXV))
+                return fail(ctx, CNF2_ERR_ARG, "n_var must be 0 .. min(n_cov, %d)", QTLVAR_MAXV);
+            RC_TRY(qtl_fit_check_iter(ctx, max_iter, QTLVAR_MAX_ITER, tol));
+            qtl_centre_once(a, mask, centred, true);
+            return CNF2_OK;
+        },
+        [&](auto each, const QtlFitPlan& plan) -> int { return each(coef_var_out, ctx->d_qv_coefv, plan.cells * plan.ne, &p.coef_var); },
+        [&] {
+            launch_qtlbin_rank(p.b, ctx->stream);
+            launch_qtlvar_threshold(p, ctx->stream);
+        },
+        [&](bool last) -> int {
+            launch_qtlvar_null(p, ctx->stream);
+            launch_qtlvar_fit(p, ctx->stream);
+            if (last) launch_qtlvar_finish(p, ctx->stream);
+            return CNF2_OK;
+        });
 }
 
 // one pass of sweep_impl's Viterbi mode

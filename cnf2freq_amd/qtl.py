@@ -112,6 +112,17 @@ def select_every(chromstarts, every=1):
     return np.concatenate([np.arange(cs[c], cs[c + 1], every) for c in range(len(cs) - 1)]).astype(np.int32)
 
 
+def _patterns(y, use):
+    """The columns of y[n][T] grouped by their pattern of missing (not finite) values, a pattern at the place of its first
+    column: (cols, u) per pattern, u the individuals of use[n] that the pattern does not miss."""
+    missing = ~np.isfinite(y)
+    patterns = {}
+    for k in range(y.shape[1]):
+        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    for cols in patterns.values():
+        yield cols, use & ~missing[:, cols[0]]
+
+
 def scan2(ctx, pheno, sel, cov=None, use=None, permutations=0, seed=0, additive=False, rows=None):
     """The pair scan of a whole cross on the context's uploaded pedigree, for every pair of the markers sel[L]: one origin
     sweep with the rows left on the device (or `rows`, the tensor origin_rows returned, e.g. the one a preceding scan used),
@@ -131,12 +142,7 @@ def scan2(ctx, pheno, sel, cov=None, use=None, permutations=0, seed=0, additive=
     out = dict(lod_add=np.zeros((T, L, L)), lod_full=np.zeros((T, L, L)), rank_add=np.zeros((T, L, L), np.int32),
                rank_full=np.zeros((T, L, L), np.int32), n_used=np.zeros((T, C, C), np.int32),
                perm_max=np.zeros((permutations, T, 3)) if permutations else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
+    for cols, u in _patterns(y, use):
         yk = np.where(u[:, None], y[:, cols], 0.0)
         got = ctx.qtl_scan2_device(n, d_o.data_ptr(), sel, yk, cov=cov, use=u, additive=additive)
         for key in ("lod_add", "lod_full", "rank_add", "rank_full", "n_used"):
@@ -213,12 +219,7 @@ def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False,
     d_o = origin_rows(ctx) if rows is None else rows
     out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, 2), np.nan), rank=np.zeros((T, M), np.int32),
                n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C)) if permutations else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
+    for cols, u in _patterns(y, use):
         yk = np.where(u[:, None], y[:, cols], 0.0)
         got = ctx.qtl_scan_device(n, d_o.data_ptr(), yk, cov=cov, use=u, additive=additive)
         out["lod"][cols], out["coef"][cols] = got["lod"], got["coef"]
@@ -289,12 +290,7 @@ def scan_imp(ctx, pheno, draws=16, seed=0, cov=None, use=None, permutations=0, p
     out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, 2), np.nan), rank=np.zeros((T, M), np.int32),
                n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C)) if permutations else None,
                draw_lod=np.zeros((D, T, M)) if draw_lods else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
+    for cols, u in _patterns(y, use):
         yk = np.where(u[:, None], y[:, cols], 0.0)
         got = ctx.qtl_scan_imp_device(n, D, states.data_ptr(), yk, cov=cov, use=u, additive=additive, draw_lods=draw_lods)
         out["lod"][cols], out["coef"][cols] = got["lod"], got["coef"]
@@ -368,13 +364,8 @@ def scanx(ctx, pheno, cov=None, interactive=0, imprint=False, use=None, permutat
     out = dict(lod=np.zeros((T, M, 3)), coef=np.full((T, M, len(names)), np.nan), coef_names=names,
                rank=np.zeros((T, M, 3), np.int32), n_used=np.zeros((T, C), np.int32),
                perm_max=np.zeros((permutations, T, C, 5)) if permutations else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
     kw = dict(cov=cov, interactive=interactive, imprint=imprint, additive=additive)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
+    for cols, u in _patterns(y, use):
         yk = np.where(u[:, None], y[:, cols], 0.0)
         got = ctx.qtl_scanx_device(n, d_o.data_ptr(), yk, use=u, **kw)
         out["lod"][cols], out["coef"][cols] = got["lod"], got["coef"]
@@ -388,6 +379,58 @@ def scanx(ctx, pheno, cov=None, interactive=0, imprint=False, use=None, permutat
     return out
 
 
+def _fit_columns(ctx, a, what):
+    """a as float64 [n][T] (a vector is one column) with a row per analysed individual"""
+    a = np.asarray(a, np.float64)
+    a = a[:, None] if a.ndim == 1 else a
+    n, T = a.shape
+    if n != ctx.n_ind:
+        raise ValueError("%s must have a row per analysed individual (%d)" % (what, ctx.n_ind))
+    return a
+
+
+def _fit_iterations(max_iter, most, tol):
+    if not 1 <= int(max_iter) <= most:
+        raise ValueError("max_iter must be 1 .. %d" % most)
+    if not np.isfinite(tol):
+        raise ValueError("tol must be finite")
+
+
+def _fit_scan(ctx, call, ys, use, rows, permutations, seed, strata, kw, coef=("coef",), marker=(), chrom=(), fits=(),
+              residuals=False):
+    """What scan_em, scan_binary, scan_surv and scan_var share.  call: the context's method of the scan on device rows, kw
+    its keyword arguments; ys: its column arrays [n][T], the first one's missing values giving the patterns.  The dict:
+    lod[T][M], the arrays of `coef` [T][M][len(coef_names)], coef_names, those of `marker` [T][M], iters, status, rank[T][M],
+    those of `chrom` (key, dtype) [T][C], n_used[T][C], perm_max[P][T][C] or None; lod, iters, status and perm_max with the
+    axes `fits` behind.  Per pattern one call on the pattern's own `use`, copied back by key.  Its permutations (within
+    `strata`) go with that call, which permutes the raw values -- or with residuals, in a second call on the null model's
+    residuals."""
+    n, T = ys[0].shape
+    M, C, P = ctx.n_markers, ctx.n_chrom, permutations
+    names = coef_names(0, kw["imprint"], kw["additive"])
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M) + fits))
+    out.update((key, np.full((T, M, len(names)), np.nan)) for key in coef)
+    out["coef_names"] = names
+    out.update((key, np.full((T, M), np.nan)) for key in marker)
+    out.update(iters=np.zeros((T, M) + fits, np.int32), status=np.zeros((T, M) + fits, np.int32), rank=np.zeros((T, M), np.int32))
+    out.update((key, np.zeros((T, C), dtype)) for key, dtype in chrom)
+    out.update(n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((P, T, C) + fits) if P else None)
+    keys = [key for key in out if key not in ("coef_names", "perm_max")]
+    for cols, u in _patterns(ys[0], use):
+        yk = [np.where(u[:, None], a[:, cols], 0.0) for a in ys]
+        perm = _permutations(n, P, seed, use=u, strata=strata) if P else None
+        got = call(n, d_o.data_ptr(), *yk, use=u, perm=None if residuals else perm, **kw)
+        for key in keys:
+            out[key][cols] = got[key]
+        if P:
+            if residuals:
+                got = call(n, d_o.data_ptr(), null_residuals(yk[0], kw["cov"], u), use=u, perm=perm, **kw)
+            out["perm_max"][:, cols] = got["perm_max"]
+    return out
+
+
 def scan_em(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, seed=0, additive=False, max_iter=1000, tol=1e-6,
             rows=None):
     """The maximum-likelihood scan of a whole cross on the context's uploaded pedigree: as scan -- one origin sweep with the
@@ -397,38 +440,10 @@ def scan_em(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, seed=
     iterations are done.  A dict: lod[T][M], coef[T][M][len(coef_names)], coef_names ("a", "d" unless additive, "i" with
     imprint), sigma2[T][M], iters[T][M], status[T][M] (0 = stopped by tol, 1 = by max_iter, 2 = breakdown), rank[T][M],
     n_used[T][C], perm_max[P][T][C] or None (thresholds)."""
-    y = np.asarray(pheno, np.float64)
-    y = y[:, None] if y.ndim == 1 else y
-    n, T = y.shape
-    if n != ctx.n_ind:
-        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
-    if not 1 <= int(max_iter) <= 10000:
-        raise ValueError("max_iter must be 1 .. 10000")
-    if not np.isfinite(tol):
-        raise ValueError("tol must be finite")
-    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
-    M, C = ctx.n_markers, ctx.n_chrom
-    names = coef_names(0, imprint, additive)
-    d_o = origin_rows(ctx) if rows is None else rows
-    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, len(names)), np.nan), coef_names=names, sigma2=np.full((T, M), np.nan),
-               iters=np.zeros((T, M), np.int32), status=np.zeros((T, M), np.int32), rank=np.zeros((T, M), np.int32),
-               n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C)) if permutations else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
+    y = _fit_columns(ctx, pheno, "pheno")
+    _fit_iterations(max_iter, 10000, tol)
     kw = dict(cov=cov, imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
-        yk = np.where(u[:, None], y[:, cols], 0.0)
-        got = ctx.qtl_scan_em_device(n, d_o.data_ptr(), yk, use=u, **kw)
-        for key in ("lod", "coef", "sigma2", "iters", "status", "rank", "n_used"):
-            out[key][cols] = got[key]
-        if permutations:
-            perm = _permutations(n, permutations, seed, use=u)
-            res = null_residuals(yk, cov, u)
-            out["perm_max"][:, cols] = ctx.qtl_scan_em_device(n, d_o.data_ptr(), res, use=u, perm=perm, **kw)["perm_max"]
-    return out
+    return _fit_scan(ctx, ctx.qtl_scan_em_device, (y,), use, rows, permutations, seed, None, kw, marker=("sigma2",), residuals=True)
 
 
 def scan_binary(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, seed=0, strata=None, additive=False, max_iter=50,
@@ -444,40 +459,13 @@ def scan_binary(ctx, pheno, cov=None, imprint=False, use=None, permutations=0, s
     status[T][M] (0 = stopped by tol, 1 = by max_iter, 2 = breakdown, e.g. a separated marker), rank[T][M], ll0[T][C] (the
     null model's log-likelihood, 0 where the trait is not scanned on the chromosome), n_ones[T][C], n_used[T][C],
     perm_max[P][T][C] or None (thresholds)."""
-    y = np.asarray(pheno, np.float64)
-    y = y[:, None] if y.ndim == 1 else y
-    n, T = y.shape
-    if n != ctx.n_ind:
-        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
-    if not 1 <= int(max_iter) <= 1000:
-        raise ValueError("max_iter must be 1 .. 1000")
-    if not np.isfinite(tol):
-        raise ValueError("tol must be finite")
-    missing = ~np.isfinite(y)
-    if not np.all(missing | (y == 0.0) | (y == 1.0)):
+    y = _fit_columns(ctx, pheno, "pheno")
+    _fit_iterations(max_iter, 1000, tol)
+    if not np.all(~np.isfinite(y) | (y == 0.0) | (y == 1.0)):
         raise ValueError("a binary trait is 0 or 1 (NaN where it is missing)")
-    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
-    M, C = ctx.n_markers, ctx.n_chrom
-    names = coef_names(0, imprint, additive)
-    d_o = origin_rows(ctx) if rows is None else rows
-    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, len(names)), np.nan), coef_names=names,
-               iters=np.zeros((T, M), np.int32), status=np.zeros((T, M), np.int32), rank=np.zeros((T, M), np.int32),
-               ll0=np.zeros((T, C)), n_ones=np.zeros((T, C), np.int32), n_used=np.zeros((T, C), np.int32),
-               perm_max=np.zeros((permutations, T, C)) if permutations else None)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
     kw = dict(cov=cov, imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
-        yk = np.where(u[:, None], y[:, cols], 0.0)
-        perm = _permutations(n, permutations, seed, use=u, strata=strata) if permutations else None
-        got = ctx.qtl_scan_binary_device(n, d_o.data_ptr(), yk, use=u, perm=perm, **kw)
-        for key in ("lod", "coef", "iters", "status", "rank", "ll0", "n_ones", "n_used"):
-            out[key][cols] = got[key]
-        if permutations:
-            out["perm_max"][:, cols] = got["perm_max"]
-    return out
+    return _fit_scan(ctx, ctx.qtl_scan_binary_device, (y,), use, rows, permutations, seed, strata, kw,
+                     chrom=(("ll0", np.float64), ("n_ones", np.int32)))
 
 
 def scan_surv(ctx, time, status, cov=None, imprint=False, use=None, permutations=0, seed=0, strata=None, additive=False,
@@ -494,44 +482,17 @@ def scan_surv(ctx, time, status, cov=None, imprint=False, use=None, permutations
     iters[T][M], status[T][M] (0 = stopped by tol, 1 = by max_iter, 2 = breakdown, e.g. a monotone likelihood), rank[T][M],
     ll0[T][C] (the null model's log partial likelihood, 0 where the trait is not scanned on the chromosome), n_events[T][C],
     n_used[T][C], perm_max[P][T][C] or None (thresholds)."""
-    t = np.asarray(time, np.float64)
-    t = t[:, None] if t.ndim == 1 else t
+    t = _fit_columns(ctx, time, "time")
     d = np.asarray(status, np.float64)
     d = d[:, None] if d.ndim == 1 else d
-    n, T = t.shape
-    if n != ctx.n_ind:
-        raise ValueError("time must have a row per analysed individual (%d)" % ctx.n_ind)
     if d.shape != t.shape:
         raise ValueError("status must have the shape of time")
-    if not 1 <= int(max_iter) <= 1000:
-        raise ValueError("max_iter must be 1 .. 1000")
-    if not np.isfinite(tol):
-        raise ValueError("tol must be finite")
-    missing = ~np.isfinite(t)
-    if not np.all(missing | (d == 0.0) | (d == 1.0)):
+    _fit_iterations(max_iter, 1000, tol)
+    if not np.all(~np.isfinite(t) | (d == 0.0) | (d == 1.0)):
         raise ValueError("a status is 1 (event) or 0 (censored) wherever the time is not missing")
-    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
-    M, C = ctx.n_markers, ctx.n_chrom
-    names = coef_names(0, imprint, additive)
-    d_o = origin_rows(ctx) if rows is None else rows
-    out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, len(names)), np.nan), coef_names=names,
-               iters=np.zeros((T, M), np.int32), status=np.zeros((T, M), np.int32), rank=np.zeros((T, M), np.int32),
-               ll0=np.zeros((T, C)), n_events=np.zeros((T, C), np.int32), n_used=np.zeros((T, C), np.int32),
-               perm_max=np.zeros((permutations, T, C)) if permutations else None)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
     kw = dict(cov=cov, imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
-        tk, dk = np.where(u[:, None], t[:, cols], 0.0), np.where(u[:, None], d[:, cols], 0.0)
-        perm = _permutations(n, permutations, seed, use=u, strata=strata) if permutations else None
-        got = ctx.qtl_scan_surv_device(n, d_o.data_ptr(), tk, dk, use=u, perm=perm, **kw)
-        for key in ("lod", "coef", "iters", "status", "rank", "ll0", "n_events", "n_used"):
-            out[key][cols] = got[key]
-        if permutations:
-            out["perm_max"][:, cols] = got["perm_max"]
-    return out
+    return _fit_scan(ctx, ctx.qtl_scan_surv_device, (t, d), use, rows, permutations, seed, strata, kw,
+                     chrom=(("ll0", np.float64), ("n_events", np.int32)))
 
 
 VAR_KEYS = ("joint", "mean", "variance")
@@ -551,44 +512,18 @@ def scan_var(ctx, pheno, cov=None, var_covariates=(), imprint=False, use=None, p
     on the log-variance scale), coef_names, iters and status[T][M][3] by fit (mean-only, variance-only, full; 0 = stopped by
     tol, 1 = by max_iter, 2 = breakdown), rank[T][M], ll0[T][C], n_used[T][C], perm_max[P][T][C][3] or None
     (thresholds_var)."""
-    y = np.asarray(pheno, np.float64)
-    y = y[:, None] if y.ndim == 1 else y
-    n, T = y.shape
-    if n != ctx.n_ind:
-        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
-    if not 1 <= int(max_iter) <= 1000:
-        raise ValueError("max_iter must be 1 .. 1000")
-    if not np.isfinite(tol):
-        raise ValueError("tol must be finite")
-    z = None if cov is None else np.asarray(cov, np.float64).reshape(n, -1)
+    y = _fit_columns(ctx, pheno, "pheno")
+    _fit_iterations(max_iter, 1000, tol)
+    z = None if cov is None else np.asarray(cov, np.float64).reshape(y.shape[0], -1)
     K = 0 if z is None else z.shape[1]
     vc = [int(k) for k in var_covariates]
     if len(vc) > 3 or len(set(vc)) != len(vc) or any(not 0 <= k < K for k in vc):
         raise ValueError("var_covariates must be at most three different columns of cov")
     if vc:
         z = z[:, vc + [k for k in range(K) if k not in vc]]
-    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
-    M, C = ctx.n_markers, ctx.n_chrom
-    names = coef_names(0, imprint, additive)
-    d_o = origin_rows(ctx) if rows is None else rows
-    out = dict(lod=np.zeros((T, M, 3)), coef_mean=np.full((T, M, len(names)), np.nan),
-               coef_var=np.full((T, M, len(names)), np.nan), coef_names=names, iters=np.zeros((T, M, 3), np.int32),
-               status=np.zeros((T, M, 3), np.int32), rank=np.zeros((T, M), np.int32), ll0=np.zeros((T, C)),
-               n_used=np.zeros((T, C), np.int32), perm_max=np.zeros((permutations, T, C, 3)) if permutations else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
     kw = dict(cov=z, n_var=len(vc), imprint=imprint, additive=additive, max_iter=max_iter, tol=tol)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
-        yk = np.where(u[:, None], y[:, cols], 0.0)
-        perm = _permutations(n, permutations, seed, use=u, strata=strata) if permutations else None
-        got = ctx.qtl_scan_var_device(n, d_o.data_ptr(), yk, use=u, perm=perm, **kw)
-        for key in ("lod", "coef_mean", "coef_var", "iters", "status", "rank", "ll0", "n_used"):
-            out[key][cols] = got[key]
-        if permutations:
-            out["perm_max"][:, cols] = got["perm_max"]
+    out = _fit_scan(ctx, ctx.qtl_scan_var_device, (y,), use, rows, permutations, seed, strata, kw, coef=("coef_mean", "coef_var"),
+                    chrom=(("ll0", np.float64),), fits=(3,))
     for s, key in enumerate(VAR_KEYS):
         out["lod_" + key] = out["lod"][..., s]
     return out
@@ -648,18 +583,13 @@ def scan_cof(ctx, pheno, cof, excl=None, cov=None, use=None, permutations=0, see
                rank=np.zeros((T, M), np.int32), rank_cof=np.zeros((T, M), np.int32), n_used=np.zeros((T, C), np.int32),
                perm_max=np.zeros((permutations, T, C)) if permutations else None, cof=cof, excl_lo=lo, excl_hi=hi,
                candidate=candidate)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
     kw = dict(excl=(lo, hi), cov=cov, additive=additive)
     null_cov = None
     if permutations:
         z = None if cov is None else np.asarray(cov, np.float64).reshape(n, -1)
         parts = ([] if z is None else [z]) + ([cofactor_columns(d_o, cof, additive)] if len(cof) else [])
         null_cov = np.concatenate(parts, axis=1) if parts else None
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
+    for cols, u in _patterns(y, use):
         yk = np.where(u[:, None], y[:, cols], 0.0)
         got = ctx.qtl_scan_cof_device(n, d_o.data_ptr(), yk, cof, use=u, **kw)
         for key in ("lod", "lod_base", "coef", "rank", "rank_cof", "n_used"):
@@ -894,12 +824,7 @@ def scan_boot(ctx, pheno, chrom, replicates=1000, seed=0, cov=None, use=None, st
     d_o = origin_rows(ctx) if rows is None else rows
     out = dict(boot_max=np.zeros((B, T, Cn)), boot_arg=np.full((B, T, Cn), -1, np.int32), n_boot=np.zeros((B, T, Cn), np.int32),
                count=np.zeros((T, B, n), np.int32), boot_lod=np.zeros((B, T, Mn)) if profile else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]]
+    for cols, u in _patterns(y, use):
         yk = np.where(u[:, None], y[:, cols], 0.0)
         count = bootstrap_counts(n, B, seed, use=u, strata=strata)
         got = ctx.qtl_scan_boot_device(n, d_o.data_ptr(), yk, count, c0, c1, cov=cov, use=u, additive=additive, profile=profile)
@@ -1131,12 +1056,7 @@ def scan_lmm(ctx, pheno, kinship=None, loco=True, cov=None, use=None, permutatio
     out = dict(lod=np.zeros((T, M)), coef=np.full((T, M, 2), np.nan), rank=np.zeros((T, M), np.int32), h2=np.zeros((T, C)),
                sigma2=np.zeros((T, C)), n_used=np.zeros(T, np.int32),
                perm_max=np.zeros((permutations, T, C)) if permutations else None)
-    missing = ~np.isfinite(y)
-    patterns = {}
-    for k in range(T):
-        patterns.setdefault(missing[:, k].tobytes(), []).append(k)
-    for cols in patterns.values():
-        u = use & ~missing[:, cols[0]] & present
+    for cols, u in _patterns(y, use & present):
         idx = np.flatnonzero(u)
         nk = len(idx)
         out["n_used"][cols] = nk
