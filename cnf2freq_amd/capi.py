@@ -34,7 +34,8 @@ QTL_STATE_DEVICE = 1 << 29        # cnf2_qtl_scan_imp: the sampled states are a 
 NO_UNIFORM_PACK = 1 << 26         # crosses of inbred lines: one window to a wave, not four windows of a chromosome (A/B, cross-check)
 NO_UNIFORM_PACK8 = 1 << 27        # crosses of inbred lines: packed windows four to a wave only, not eight windows of a chromosome (A/B, cross-check)
 NO_LINE_RECORDS = 1 << 24         # crosses of inbred lines: every window's emission terms from its own rows, not from the launch's line records (A/B, cross-check)
-STATIC_JOBS = 1 << 18             # wave w sweeps jobs w, w + waves, ... instead of taking jobs from the launch's counter (A/B)
+QTL_JOINT_DEVICE = 1 << 30        # cnf2_qtl_scan2_linked: the joint rows are a device pointer
+STATIC_JOBS = 1 << 18            # wave w sweeps jobs w, w + waves, ... instead of taking jobs from the launch's counter (A/B)
 MINFACTOR = float(np.float32(-1e15))
 IGNORED = -1e30
 
@@ -52,6 +53,7 @@ SYMBOLS = [
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
     "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
+    "cnf2_linked_pairs", "cnf2_sweep_pairs", "cnf2_pair_rows", "cnf2_qtl_scan2_linked",
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
     "cnf2_qtl_scan_surv", "cnf2_set_qtlsurv_columns", "cnf2_set_qtlsurv_blocks",
@@ -129,10 +131,14 @@ def load():
         L.cnf2_loo_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_sweep_origins.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_origin_rows.argtypes = [vp, i32, i32, vp]
+        L.cnf2_linked_pairs.argtypes = [vp, i32, vp, vp, vp]
+        L.cnf2_sweep_pairs.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_pair_rows.argtypes = [vp, i32, i32, i32, vp, vp]
         L.cnf2_qtl_scan.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_sweep_qtl.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtl_columns.argtypes = [vp, i32]
         L.cnf2_qtl_scan2.argtypes = [vp, i32, vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_qtl_scan2_linked.argtypes = [vp, i32, vp, vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtl2_columns.argtypes = [vp, i32]
         L.cnf2_qtl_scanx.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_set_qtlx_columns.argtypes = [vp, i32]
@@ -626,6 +632,54 @@ class Context:
                                             C.c_void_p(d_bits) if d_bits else None, C.c_void_p(d_origin_sum),
                                             C.c_void_p(d_n_contrib), flags | OUT_DEVICE), "cnf2_sweep_origins")
 
+    # -- pair posteriors ---------------------------------------------------------
+    def linked_pairs(self, sel):
+        """cnf2_linked_pairs: pairs[n_pairs][2] (int32), the pairs j < k of indices into sel whose markers share a
+        chromosome, in the order of sweep_pairs' rows (ascending j, then ascending k)."""
+        sel = np.ascontiguousarray(sel, np.int32)
+        cnt = np.zeros(1, np.int32)
+        self._chk(self.L.cnf2_linked_pairs(self.h, len(sel), _p(sel), None, _p(cnt)), "cnf2_linked_pairs")
+        pairs = np.zeros((int(cnt[0]), 2), np.int32)
+        if len(pairs):
+            self._chk(self.L.cnf2_linked_pairs(self.h, len(sel), _p(sel), _p(pairs), _p(cnt)), "cnf2_linked_pairs")
+        return pairs
+
+    def pair_rows(self, ind, chrom, sel):
+        """[S (S - 1) / 2][16] the rows of sweep_pairs for one individual and the S markers of sel on one chromosome, from
+        the alpha/beta store by brute force (the cross-check of sweep_pairs); zeros where the individual is skipped."""
+        sel = np.ascontiguousarray(sel, np.int32)
+        S = int(((sel >= self.chromstarts[chrom]) & (sel < self.chromstarts[chrom + 1])).sum())
+        v = np.zeros((S * (S - 1) // 2, 16))
+        self._chk(self.L.cnf2_pair_rows(self.h, ind, chrom, len(sel), _p(sel), _p(v)), "cnf2_pair_rows")
+        return v
+
+    def sweep_pairs(self, sel, ind_begin=0, ind_end=None, rows=True, ties_general=False, static_jobs=False):
+        """cnf2_sweep_pairs: factors / loglik as sweep(); joint[n][n_pairs][16], for every pair of linked_pairs(sel) the joint
+        distribution of the origin classes (u at the first, v at the second locus, cell 4 u + v; the classes and the frame
+        are sweep_origins'; all zero where skipped; None with rows=False); joint_sum[n_pairs][16], their sum over the
+        range's individuals, and the contributing individuals per chromosome.  cnf2freq_amd/origins.py reads them."""
+        sel = np.ascontiguousarray(sel, np.int32)
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        NP = len(self.linked_pairs(sel))
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        joint = np.zeros((n, NP, 16)) if rows else None
+        jsum = np.zeros((NP, 16))
+        cnt = np.zeros(self.n_chrom, np.int32)
+        flags = (TIES_GENERAL if ties_general else 0) | (STATIC_JOBS if static_jobs else 0)
+        self._chk(self.L.cnf2_sweep_pairs(self.h, ind_begin, ind_end, len(sel), _p(sel), _p(factors), _p(loglik),
+                                          _p(joint) if rows else None, _p(jsum), _p(cnt), flags), "cnf2_sweep_pairs")
+        return dict(factors=factors, loglik=loglik, joint=joint, joint_sum=jsum, n_contrib=cnt)
+
+    def sweep_pairs_device(self, ind_begin, ind_end, sel, d_factors, d_loglik, d_joint, d_joint_sum, d_n_contrib, flags=0):
+        """Device-pointer form (ints; d_joint may be None: the rows then stay in the context)."""
+        sel = np.ascontiguousarray(sel, np.int32)
+        self._chk(self.L.cnf2_sweep_pairs(self.h, ind_begin, ind_end, len(sel), _p(sel), C.c_void_p(d_factors),
+                                          C.c_void_p(d_loglik), C.c_void_p(d_joint) if d_joint else None,
+                                          C.c_void_p(d_joint_sum), C.c_void_p(d_n_contrib), flags | OUT_DEVICE),
+                  "cnf2_sweep_pairs")
+
     # -- QTL scan ----------------------------------------------------------------
     def set_qtl_columns(self, cap):
         """Cap on the phenotype columns per tile of qtl_scan / sweep_qtl (0 = what memory allows); results do not depend on it."""
@@ -944,8 +998,9 @@ class Context:
                     rank_full=np.zeros((L, L), np.int32), rss0=np.zeros((T, Cn, Cn)), n_used=np.zeros((Cn, Cn), np.int32),
                     perm_max=np.zeros((P, T, 3)) if P else None)
 
-    def _qtl2_call(self, n, origin_ptr, sel, pheno, cov, use, perm, flags, out=None):
-        """cnf2_qtl_scan2 with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
+    def _qtl2_call(self, n, origin_ptr, sel, pheno, cov, use, perm, flags, out=None, joint_ptr=None):
+        """cnf2_qtl_scan2 -- with joint_ptr cnf2_qtl_scan2_linked -- with host outputs (out = None: new arrays) on the rows
+        behind origin_ptr"""
         pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
         sel = np.ascontiguousarray(sel, np.int32)
         if sel.ndim != 1:
@@ -953,10 +1008,31 @@ class Context:
         T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
         o = self._qtl2_outputs(T, P, len(sel)) if out is None else out
         opt = lambda a: None if a is None else _p(a)
-        self._chk(self.L.cnf2_qtl_scan2(self.h, n, origin_ptr, len(sel), _p(sel), T, _p(pheno), opt(use), K, opt(cov), P,
-                                        opt(perm), _p(o["lod_add"]), _p(o["lod_full"]), _p(o["rank_add"]), _p(o["rank_full"]),
-                                        _p(o["rss0"]), _p(o["n_used"]), opt(o["perm_max"]), flags), "cnf2_qtl_scan2")
+        outs = (_p(o["lod_add"]), _p(o["lod_full"]), _p(o["rank_add"]), _p(o["rank_full"]), _p(o["rss0"]), _p(o["n_used"]),
+                opt(o["perm_max"]), flags)
+        if joint_ptr is None:
+            self._chk(self.L.cnf2_qtl_scan2(self.h, n, origin_ptr, len(sel), _p(sel), T, _p(pheno), opt(use), K, opt(cov), P,
+                                            opt(perm), *outs), "cnf2_qtl_scan2")
+        else:
+            self._chk(self.L.cnf2_qtl_scan2_linked(self.h, n, origin_ptr, joint_ptr, len(sel), _p(sel), T, _p(pheno), opt(use), K,
+                                                   opt(cov), P, opt(perm), *outs), "cnf2_qtl_scan2_linked")
         return o
+
+    def qtl_scan2_linked(self, origin, joint, sel, pheno, cov=None, use=None, perm=None, additive=False):
+        """cnf2_qtl_scan2_linked on host rows origin[n][M][4] and joint[n][n_pairs][16] (sweep_pairs' rows for the same sel):
+        qtl_scan2, with the full model fitted on the pairs of one chromosome too -- there the interaction columns are the
+        expectations of the products under the joint -- and perm_max[..][1], [..][2] over all pairs."""
+        origin = self._origin_rows(origin)
+        joint = np.ascontiguousarray(joint, np.float64)
+        if joint.ndim != 3 or joint.shape[0] != origin.shape[0] or joint.shape[2] != 16:
+            raise ValueError("joint must be [n][n_pairs][16] with n = %d" % origin.shape[0])
+        return self._qtl2_call(origin.shape[0], _p(origin), sel, pheno, cov, use, perm, QTL_ADDITIVE if additive else 0,
+                               joint_ptr=_p(joint))
+
+    def qtl_scan2_linked_device(self, n, d_origin, d_joint, sel, pheno, cov=None, use=None, perm=None, additive=False):
+        """The same on device rows and a device joint, both read in place."""
+        return self._qtl2_call(n, C.c_void_p(d_origin), sel, pheno, cov, use, perm,
+                               QTL_ORIGIN_DEVICE | QTL_JOINT_DEVICE | (QTL_ADDITIVE if additive else 0), joint_ptr=C.c_void_p(d_joint))
 
     def qtl_scan2(self, origin, sel, pheno, cov=None, use=None, perm=None, additive=False):
         """cnf2_qtl_scan2 on host rows origin[n][M][4]: for every pair j < k of the markers sel[L] (strictly ascending) the

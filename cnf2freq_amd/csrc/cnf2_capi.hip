@@ -194,6 +194,12 @@ struct cnf2_ctx {
     DevBuf<double>  d_obits;              // [n][n_markers][6]
     DevBuf<double>  d_org_sum;            // [n_markers][4]
 
+    // pair rows (cnf2_sweep_pairs): the selection as the kernels read it (sel, the chromosomes' ranges in it, the pair
+    // offsets), the rows a call did not hand device memory for, and its staged sums
+    DevBuf<int32_t> d_pair_map;
+    DevBuf<double>  d_pair;               // [n][n_pairs][16]
+    DevBuf<double>  d_pair_sum;           // [n_pairs][16]
+
     // QTL scan (cnf2_qtl_scan, cnf2_sweep_qtl): staged inputs, design, the column image of a tile, staged outputs
     int             qtl_columns[QTL_CAP_COUNT] = {};   // caps on the columns per tile (cnf2_set_*_columns; 0 = what memory allows)
     int             qtl_rows_n = 0;       // individuals whose rows the last cnf2_sweep_qtl left in d_org: 0 (none to vouch for) after
@@ -2317,11 +2323,43 @@ int cnf2_qtl_scan_mv(cnf2_ctx* ctx, int n, const double* origin, int n_traits, c
     return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
-// The pair scan on origin rows [n][M][4]: cnf2_qtl2.h, cnf2_qtl2_kernels.hip
-int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const int32_t* sel, int n_traits, const double* pheno,
-                   const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm, double* lod_add_out,
-                   double* lod_full_out, int32_t* rank_add_out, int32_t* rank_full_out, double* rss0_out, int32_t* n_used_out,
-                   double* perm_max_out, uint32_t flags)
+// The selection of a pair call as the kernels read it.  sel follows cnf2_qtl_scan2's rules (2 .. QTL2_MAXL strictly ascending
+// marker indices); the loci of a chromosome are consecutive in it, so pair (j, k) of one chromosome is row pair_off[j] + k - j - 1
+struct PairSel {
+    std::vector<int32_t> chrom_sel;    // [C + 1] the chromosomes' ranges in sel
+    std::vector<int32_t> pair_off;     // [L]
+    int n_pairs = 0, max_anchors = 0;  // max_anchors: the most selected markers of a chromosome, less one
+};
+static int pair_selection(cnf2_ctx* ctx, int n_sel, const int32_t* sel, PairSel* out)
+{
+    if (n_sel < 2 || n_sel > QTL2_MAXL || !sel) return fail(ctx, CNF2_ERR_ARG, "n_sel must be 2 .. %d, with sel", QTL2_MAXL);
+    const int M = ctx->n_markers, C = ctx->n_chrom;
+    for (int j = 0; j < n_sel; j++)
+        if (sel[j] < 0 || sel[j] >= M || (j > 0 && sel[j] <= sel[j - 1]))
+            return fail(ctx, CNF2_ERR_ARG, "sel must be strictly ascending marker indices below %d", M);
+    out->chrom_sel.assign((size_t)C + 1, 0);
+    out->pair_off.assign((size_t)n_sel, 0);
+    int j = 0, base = 0;
+    for (int c = 0; c < C; c++) {
+        const int j0 = j;
+        while (j < n_sel && sel[j] < ctx->chromstarts[c + 1]) j++;
+        const int S = j - j0;
+        out->chrom_sel[c + 1] = j;
+        for (int a = 0; a < S; a++) out->pair_off[j0 + a] = base + a * (2 * S - a - 1) / 2;
+        base += S * (S - 1) / 2;
+        out->max_anchors = std::max(out->max_anchors, S - 1);
+    }
+    out->n_pairs = base;
+    return CNF2_OK;
+}
+
+// The pair scan on origin rows [n][M][4]: cnf2_qtl2.h, cnf2_qtl2_kernels.hip.  linked (cnf2_qtl_scan2_linked): with the joint
+// rows [n][n_pairs][16] of the pairs on one chromosome -- device memory with CNF2_QTL_JOINT_DEVICE, else staged whole in the
+// pair sweep's buffer -- the pair kernel's linked form fits those pairs the full design too
+static int qtl_scan2_impl(cnf2_ctx* ctx, int n, const double* origin, const double* joint, bool linked, int n_sel,
+                          const int32_t* sel, int n_traits, const double* pheno, const uint8_t* use, int n_cov, const double* cov,
+                          int n_perm, const int32_t* perm, double* lod_add_out, double* lod_full_out, int32_t* rank_add_out,
+                          int32_t* rank_full_out, double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
 {
     if (!ctx) return CNF2_ERR_ARG;
     QtlOrigin org;
@@ -2339,9 +2377,16 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
     for (int j = 0; j < L; j++)
         if (sel[j] < 0 || sel[j] >= M || (j > 0 && sel[j] <= sel[j - 1]))
             return fail(ctx, CNF2_ERR_ARG, "sel must be strictly ascending marker indices below %d", M);
+    PairSel ps;
+    if (linked) {
+        if (!joint) return fail(ctx, CNF2_ERR_ARG, "joint must not be NULL");
+        RC_TRY(pair_selection(ctx, n_sel, sel, &ps));
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
 
     const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const bool   joint_host = linked && ps.n_pairs > 0 && !(flags & CNF2_QTL_JOINT_DEVICE);
+    const size_t nj = (size_t)n * (size_t)ps.n_pairs * 16;
     const size_t R = (size_t)a.T * ((size_t)a.P + 1), LL = (size_t)L * L;
     const int    n_chunks = (L - 1 + QTL2_CHUNK - 1) / QTL2_CHUNK;
     const size_t rt = qtl_column_tile(a.n, R, a.P, (size_t)3 * L * n_chunks, ctx->qtl_columns[QTL_CAP_SCAN2]);
@@ -2352,6 +2397,7 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
         while (sel[j] >= ctx->chromstarts[c + 1]) c++;
         map.push_back(c);
     }
+    if (linked) map.insert(map.end(), ps.pair_off.begin(), ps.pair_off.end());
 
     Qtl2Params q;
     memset(&q, 0, sizeof(q));
@@ -2367,12 +2413,25 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
     RC_TRY(qtl_origin_reserve(ctx, org));
     RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
     RC_TRY(ctx->d_q2_map.ensure(ctx, map.size()));
+    if (joint_host) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+        if (nj > ctx->d_pair.cap && nj * sizeof(double) > free_b + ctx->d_pair.cap * sizeof(double))
+            return fail(ctx, CNF2_ERR_NOMEM, "the joint rows need %zu MB of device memory", (nj * 8) >> 20);
+        RC_TRY(ctx->d_pair.ensure(ctx, nj));
+    }
     RC_TRY(ctx->d_q2_yy.ensure(ctx, (size_t)C * C * rt));
     if (a.P > 0) RC_TRY(ctx->d_q2_chunkmax.ensure(ctx, (size_t)L * n_chunks * 3 * rt));
     RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
     RC_TRY(qtl_origin_stage(ctx, org));
     RC_TRY(qtl_upload(ctx, ctx->d_q2_map, map.data(), map.size()));
     RC_TRY(qtl_upload_inputs(ctx, a, mask));
+    if (joint_host) HIP_TRY(ctx, hipMemcpyAsync(ctx->d_pair, joint, nj * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (linked && ps.n_pairs > 0) {
+        q.joint    = joint_host ? (const double*)ctx->d_pair : joint;
+        q.pair_off = ctx->d_q2_map + (C + 1 + 2 * L);
+        q.n_pairs  = ps.n_pairs;
+    }
 
     q.n = a.n, q.M = M, q.C = C, q.T = a.T, q.P = a.P, q.K = a.K, q.L = L;
     q.additive = (flags & CNF2_QTL_ADDITIVE) ? 1 : 0;
@@ -2394,6 +2453,24 @@ int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const 
     }
     HIP_TRY(ctx, hipGetLastError());
     return qtl_fetch_outputs(ctx, dev, outputs);
+}
+
+int cnf2_qtl_scan2(cnf2_ctx* ctx, int n, const double* origin, int n_sel, const int32_t* sel, int n_traits, const double* pheno,
+                   const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm, double* lod_add_out,
+                   double* lod_full_out, int32_t* rank_add_out, int32_t* rank_full_out, double* rss0_out, int32_t* n_used_out,
+                   double* perm_max_out, uint32_t flags)
+{
+    return qtl_scan2_impl(ctx, n, origin, nullptr, false, n_sel, sel, n_traits, pheno, use, n_cov, cov, n_perm, perm, lod_add_out,
+                          lod_full_out, rank_add_out, rank_full_out, rss0_out, n_used_out, perm_max_out, flags);
+}
+
+int cnf2_qtl_scan2_linked(cnf2_ctx* ctx, int n, const double* origin, const double* joint, int n_sel, const int32_t* sel,
+                          int n_traits, const double* pheno, const uint8_t* use, int n_cov, const double* cov, int n_perm,
+                          const int32_t* perm, double* lod_add_out, double* lod_full_out, int32_t* rank_add_out,
+                          int32_t* rank_full_out, double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    return qtl_scan2_impl(ctx, n, origin, joint, true, n_sel, sel, n_traits, pheno, use, n_cov, cov, n_perm, perm, lod_add_out,
+                          lod_full_out, rank_add_out, rank_full_out, rss0_out, n_used_out, perm_max_out, flags);
 }
 
 // The extended single-locus scan on origin rows [n][M][4]: cnf2_qtlx.h, cnf2_qtlx_kernels.hip
@@ -3289,6 +3366,149 @@ int cnf2_sweep_turn_scan(cnf2_ctx* ctx, int ind_begin, int ind_end, double* rawe
         if (turn_lse_out) HIP_TRY(ctx, hipMemcpyAsync(turn_lse_out, d_lse, (size_t)n * M * 128 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
+    return CNF2_OK;
+}
+
+// The pairs of a selection that lie on one chromosome, in the order of cnf2_sweep_pairs' rows
+int cnf2_linked_pairs(cnf2_ctx* ctx, int n_sel, const int32_t* sel, int32_t* pairs_out, int32_t* n_pairs_out)
+{
+    RC_TRY(ready(ctx));
+    if (!n_pairs_out) return fail(ctx, CNF2_ERR_ARG, "n_pairs_out must not be NULL");
+    PairSel ps;
+    RC_TRY(pair_selection(ctx, n_sel, sel, &ps));
+    if (pairs_out)
+        for (int c = 0; c < ctx->n_chrom; c++)
+            for (int j = ps.chrom_sel[c]; j < ps.chrom_sel[c + 1]; j++)
+                for (int k = j + 1; k < ps.chrom_sel[c + 1]; k++) {
+                    int32_t* o = pairs_out + (size_t)(ps.pair_off[j] + k - j - 1) * 2;
+                    o[0] = j;
+                    o[1] = k;
+                }
+    *n_pairs_out = ps.n_pairs;
+    return CNF2_OK;
+}
+
+// Pair posteriors of the analysed individuals [ind_begin, ind_end): in batches, the sweep kernels in their turn-scan
+// instantiation (alpha after the emission and beta of every marker into the batch buffer), then pair_sweep_kernel on the
+// batch; the column sums by origin_finish_kernel.  The rows the caller gave no device memory for live whole in the context.
+int cnf2_sweep_pairs(cnf2_ctx* ctx, int ind_begin, int ind_end, int n_sel, const int32_t* sel, double* factors_out,
+                     double* loglik_out, double* joint_out, double* joint_sum_out, int32_t* n_contrib_out, uint32_t flags)
+{
+    RC_TRY(ready(ctx));
+    if (!factors_out || !loglik_out || !joint_sum_out || !n_contrib_out)
+        return fail(ctx, CNF2_ERR_ARG, "only joint_out may be NULL");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    PairSel ps;
+    RC_TRY(pair_selection(ctx, n_sel, sel, &ps));
+    if (ps.n_pairs == 0) return fail(ctx, CNF2_ERR_ARG, "no two selected markers share a chromosome");
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    n = ind_end - ind_begin;
+    const size_t M = (size_t)ctx->n_markers, C = (size_t)ctx->n_chrom, L = (size_t)n_sel, NP = (size_t)ps.n_pairs;
+    const size_t nf = (size_t)n * C * 8, nl = (size_t)n * C, nr = (size_t)n * NP * 16;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double *d_f, *d_l, *d_sum, *d_joint = (dev && joint_out) ? joint_out : nullptr;
+    int32_t* d_cnt;
+    if (!d_joint && nr > ctx->d_pair.cap) {
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
+        if (nr * sizeof(double) > free_b + ctx->d_pair.cap * sizeof(double))
+            return fail(ctx, CNF2_ERR_NOMEM, "the pair rows of the range need %zu MB: split the range", (nr * 8) >> 20);
+    }
+    RC_TRY(stage_out(ctx, dev, factors_out, ctx->d_factors, nf ? nf : 1, &d_f));
+    RC_TRY(stage_out(ctx, dev, loglik_out, ctx->d_loglik, nl ? nl : 1, &d_l));
+    RC_TRY(stage_out(ctx, dev, joint_sum_out, ctx->d_pair_sum, NP * 16, &d_sum));
+    RC_TRY(stage_out(ctx, dev, n_contrib_out, ctx->d_xo_cnt, C, &d_cnt));
+    RC_TRY(ctx->d_dosage.ensure(ctx, (size_t)(n > 0 ? n : 1) * M * 3));
+    if (!d_joint && nr > 0) {
+        RC_TRY(ctx->d_pair.ensure(ctx, nr));
+        d_joint = ctx->d_pair;
+    }
+    std::vector<int32_t> map(sel, sel + L);
+    map.insert(map.end(), ps.chrom_sel.begin(), ps.chrom_sel.end());
+    map.insert(map.end(), ps.pair_off.begin(), ps.pair_off.end());
+    RC_TRY(ctx->d_pair_map.ensure(ctx, map.size()));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_pair_map, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (n > 0) {
+        Batched b;
+        RC_TRY(batched_setup(ctx, ind_begin, n, flags, CNF2_TURN_ROW, 0, &b));
+        if (b.plan.fit == BATCH_NO_ROWS) return fail(ctx, CNF2_ERR_NOMEM, "not enough memory for the alpha/beta rows of one job");
+        const int mlen = b.max_len;
+        RC_TRY(ctx->d_wbuf.ensure(ctx, b.plan.batch * (size_t)mlen * CNF2_TURN_ROW));
+        KernelParams p;
+        base_params(ctx, &p);
+        if (flags & CNF2_STATIC_JOBS) p.job_next = nullptr;
+        p.windows      = ctx->d_windows + ind_begin;
+        p.spill        = ctx->d_spill;
+        p.spill_stride = spill_stride(mlen);
+        p.factors      = d_f;
+        p.loglik       = d_l;
+        p.dosage       = ctx->d_dosage;
+        p.flags        = 0;
+        p.wbuf         = ctx->d_wbuf;
+        p.wstride      = (size_t)mlen;
+        PairParams q;
+        memset(&q, 0, sizeof(q));
+        q.max_anchors = ps.max_anchors;
+        q.n_pairs     = ps.n_pairs;
+        q.sel         = ctx->d_pair_map;
+        q.chrom_sel   = ctx->d_pair_map + L;
+        q.pair_off    = ctx->d_pair_map + L + C + 1;
+        q.joint       = d_joint;
+        HIP_TRY(ctx, hipMemsetAsync(d_joint, 0, nr * sizeof(double), ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+        RC_TRY(for_each_batch(ctx, b, &p, [&](int pass, int grid, int) -> int {
+            // alpha and beta do not see the tie rule: tied windows take the tile-producer kernel too (cnf2_sweep_turn_scan)
+            if (pass == 0 || !(flags & CNF2_TIES_GENERAL)) HIP_TRY(ctx, launch_fb_fast(p, grid, {SW_ALPHA_BETA}, ctx->stream));
+            else HIP_TRY(ctx, launch_fb(p, grid, SW_ALPHA_BETA, ctx->stream));
+            q.kp     = p;
+            q.n_jobs = p.n_jobs;
+            launch_pair_sweep(q, ctx->stream);
+            HIP_TRY(ctx, hipGetLastError());
+            return CNF2_OK;
+        }));
+    }
+    launch_pair_count(d_f, d_l, n, (int)C, d_cnt, ctx->stream);
+    if (n > 0) launch_origin_finish(d_joint, n, (int)(NP * 4), d_sum, ctx->stream);
+    else HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, NP * 16 * sizeof(double), ctx->stream));
+    HIP_TRY(ctx, hipGetLastError());
+    if (n > 0) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+        ctx->timed = true;
+    }
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, factors_out, d_f, nf));
+    RC_TRY(fetch_out(ctx, loglik_out, d_l, nl));
+    RC_TRY(fetch_out(ctx, joint_sum_out, d_sum, NP * 16));
+    RC_TRY(fetch_out(ctx, n_contrib_out, d_cnt, C));
+    if (joint_out && nr > 0) RC_TRY(fetch_out(ctx, joint_out, d_joint, nr));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
+// The pair rows of one individual and chromosome from the reference-layout store, brute force: rows_out[S (S - 1) / 2][16] for
+// the S markers of sel on the chromosome, pairs in ascending first, then ascending second locus (nothing where S < 2)
+int cnf2_pair_rows(cnf2_ctx* ctx, int ind, int chrom, int n_sel, const int32_t* sel, double* rows_out)
+{
+    if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad pair_rows arguments");
+    RC_TRY(ready(ctx));
+    if (ind < 0 || ind >= (int)ctx->windows.size() || chrom < 0 || chrom >= ctx->n_chrom)
+        return fail(ctx, CNF2_ERR_ARG, "individual or chromosome out of range");
+    PairSel ps;
+    RC_TRY(pair_selection(ctx, n_sel, sel, &ps));
+    const int j0 = ps.chrom_sel[chrom], S = ps.chrom_sel[chrom + 1] - j0;
+    if (S < 2) return CNF2_OK;
+    std::vector<int32_t> local((size_t)S);
+    for (int a = 0; a < S; a++) local[a] = sel[j0 + a] - ctx->chromstarts[chrom];
+    const size_t nr = (size_t)S * (S - 1) / 2 * 16;
+    Stage2Params q;
+    double*      d_out = nullptr;
+    RC_TRY(run_store(ctx, ind, chrom, &q, nr + (size_t)(S + 1) / 2, &d_out));
+    int32_t* d_sel = (int32_t*)(d_out + nr);
+    HIP_TRY(ctx, hipMemcpyAsync(d_sel, local.data(), sizeof(int32_t) * S, hipMemcpyHostToDevice, ctx->stream));
+    launch_pair_rows(q, d_sel, S, d_out, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(rows_out, d_out, nr * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CNF2_OK;
 }
 

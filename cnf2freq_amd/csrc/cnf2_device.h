@@ -203,6 +203,23 @@ struct TurnParams {
 };
 void launch_turn_rows(const TurnParams& q, hipStream_t stream);
 
+// Inputs of the pair sweep (pair_sweep_kernel): what a turn-scan sweep left in kp.wbuf for the `n_jobs` jobs at kp.jobs (with
+// kp.factors / kp.loglik finished), and the selection.  Pair (j, k) of sel indices j < k on one chromosome is row
+// pair_off[j] + k - j - 1 of an individual's n_pairs rows.
+struct PairParams {
+    KernelParams   kp;
+    int            n_jobs;
+    int            max_anchors;   // the most selected markers of a chromosome, less one (grid.y covers them)
+    int            n_pairs;
+    const int32_t* sel;           // [L] marker indices, strictly ascending
+    const int32_t* chrom_sel;     // [n_chrom + 1] the chromosomes' ranges in sel
+    const int32_t* pair_off;      // [L]
+    double*        joint;         // [n_ind][n_pairs][16]
+};
+void launch_pair_sweep(const PairParams& q, hipStream_t stream);
+// cnt[c] = how many of the n_ind individuals have a shift mode with a likelihood on chromosome c
+void launch_pair_count(const double* factors, const double* loglik, int n_ind, int n_chrom, int32_t* cnt, hipStream_t stream);
+
 // Inputs of the placement kernels: what a placement sweep (SW_POSTERIOR) left in kp.wbuf for the `n_jobs` jobs at kp.jobs,
 // and the candidates' emission tables.  place_emission_kernel fills `emis` for candidates [q0, q0 + qn) of every
 // individual of the call from the candidate rows (a KernelParams whose row pointers are the candidates', n_markers = Q);
@@ -256,6 +273,9 @@ void launch_loo_rows(const Stage2Params& q, double* out, hipStream_t stream);
 void launch_loo_finish(double* loo, double* unl, int n_ind, int n_markers, double* loo_sum, double* unl_sum, hipStream_t stream);
 // out[len][10] = origin[4], bits[6] of cnf2_sweep_origins from the store, brute force
 void launch_origin_rows(const Stage2Params& q, double* out, hipStream_t stream);
+// out[S (S - 1) / 2][16] = the pair rows of cnf2_sweep_pairs for the S selected markers of the chromosome (sel: local indices,
+// ascending, device memory) from the store, brute force
+void launch_pair_rows(const Stage2Params& q, const int32_t* sel, int S, double* out, hipStream_t stream);
 // org_sum [n_markers][4] = the origin rows an origin sweep (SW_ORIGINS) left in org [n_ind][n_markers][4], added over the n_ind
 // individuals in ascending order, one thread per column (no atomics: the same bits on every call; a skipped individual's
 // rows are zeros)

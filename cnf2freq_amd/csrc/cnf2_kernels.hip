@@ -6517,4 +6517,276 @@ int fb_blocks_per_cu()
     return n < 1 ? 1 : n;
 }
 
+// =====================================================================================
+// Pair posteriors (cnf2_sweep_pairs): joint[i][p][4 u + v], the joint origin classes (u at marker j, v at marker k) of two
+// selected markers j < k of one chromosome.  Per shift mode J_s(u, v) = sum_(g, g') [cls g = u] [cls g' = v] A_j(g)
+// Phi(j -> k)(g, g') B_k(g'), Phi the product over the markers j+1 .. k of T diag(e); the modes are normalised each by its own
+// total and weighted like the origin rows (origin_rows_kernel's rule).  A and B come from a turn-scan sweep's batch buffer.
+// =====================================================================================
+// Whether mode s of the window counts, and its weight exp(factors[s] - factor): 0 where it does not
+__device__ __forceinline__ double pair_mode_weight(const Window& w, int s, double fs, double factor)
+{
+    const bool on = !(s & w.shiftignore) && s < w.shiftend && fs > (double)CNF2_MINFACTOR_F && !(factor - fs > 40.0) && !isnan(factor);
+    return on ? exp(fs - factor) : 0.0;
+}
+
+// One wave per (job, anchor): the anchor is the a-th selected marker of the job's chromosome, a = 0 .. S - 2.  The sweep's lane
+// layout (lane = mode x state_lo, register = state bits 3-5): class bit 0 is the lane's state bit 0, class bit 1 the register
+// index's bit 0.  Alpha of the anchor is split by class into four vectors; they walk to the chromosome's last selected marker
+// through the transition (`transition_scaled`) and the marker's emission (formed once, as emission_kernel forms it) with one
+// rescale per mode common to the four, which J_s / Z_s does not see.  At a selected marker the sixteen masked sums against beta: a lane's eight
+// partials (u, register parity) are reduced by halving -- over state bit 1, then state bit 2, a lane keeping half of its
+// values per step -- so that the chain's eight lanes end with two sums each; after the mode's normalisation and weight one
+// more halving step and two plain ones add up the modes, and lanes 0-15 store the row: one 128-byte line.
+__global__ __launch_bounds__(CNF2_BLOCK, 2) void pair_sweep_kernel(PairParams q)
+{
+    __shared__ double tabs[CNF2_WAVES_PER_BLOCK][64];
+    const int lane = threadIdx.x & 63;
+    const int wib  = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int job  = blockIdx.x;
+    const KernelParams& p = q.kp;
+    const Job jb = p.jobs[job];
+    const int sb = q.chrom_sel[jb.chrom], se = q.chrom_sel[jb.chrom + 1];
+    const int a  = blockIdx.y * CNF2_WAVES_PER_BLOCK + wib;
+    if (a >= se - sb - 1) return;                       // (also a chromosome with fewer than two selected markers)
+    const int ja = sb + a;
+    double*   tab = tabs[wib];
+    const Window w = p.windows[jb.ind];
+    LaneCtx   c;
+    make_lane(w, lane, &c.L);
+    c.row_root   = w.row[0];
+    c.root_attop = (w.flags[0] & SLOT_FOUNDER) != 0;
+    const int s  = lane >> 3;
+    c.s0 = s & 1;
+    c.s1 = (s >> 1) & 1;
+    c.s2 = (s >> 2) & 1;
+    c.lo = state_lo(lane);
+    c.active  = true;
+    c.n_combo = 1;
+    const size_t e_ic = (size_t)jb.ind * p.n_chrom + jb.chrom;
+    const double ws   = pair_mode_weight(w, s, p.factors[e_ic * 8 + s], p.loglik[e_ic]);
+    const bool   on   = ws != 0.0;
+    const bool   b0 = (c.lo & 1) != 0, kA = (c.lo & 2) != 0, kB = (c.lo & 4) != 0, kC = (lane & 8) != 0;
+    const int    ma = q.sel[ja], mlast = q.sel[se - 1];
+    const double* wrow = p.wbuf + (size_t)job * p.wstride * CNF2_TURN_ROW;
+
+    double V[4][8];
+    {
+        const double* wp = wrow + (size_t)(ma - jb.first) * CNF2_TURN_ROW;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const d2v t = *(const d2v*)(wp + k * 128 + lane * 2);
+            const double x0 = on ? t.x : 0.0, x1 = on ? t.y : 0.0;      // (a chain that is off: 0, whatever the buffer holds)
+            // register 2k has class bit 1 clear, register 2k + 1 has it set
+            V[0][2 * k] = b0 ? 0.0 : x0;
+            V[1][2 * k] = b0 ? x0 : 0.0;
+            V[2][2 * k] = V[3][2 * k] = 0.0;
+            V[0][2 * k + 1] = V[1][2 * k + 1] = 0.0;
+            V[2][2 * k + 1] = b0 ? 0.0 : x1;
+            V[3][2 * k + 1] = b0 ? x1 : 0.0;
+        }
+    }
+    int kn = ja + 1;
+    int mk = q.sel[kn];
+#pragma unroll 1
+    for (int m = ma + 1; m <= mlast; m++) {
+        // the scaled butterflies of the fast sweep (x' = x + t partner, t = r / (1 - r)): the constant they drop is common to
+        // the four vectors and to every mode, and J_s / Z_s does not see it; a gap of rate 0 has t = 0, the identity to the bit
+        const double2 tq = p.tq[m - 1];
+#pragma unroll
+        for (int u = 0; u < 4; u++) transition_scaled(V[u], tq.x, tq.y);
+        const Slot root = load_slot(p, c.row_root, m);
+        LineTerms  T;
+        wave_lds_fence();                               // the previous marker's reads are done
+        tab[lane] = produce_entry(p, c, root, m, &T);
+        wave_lds_fence();
+        double c0, c1, e[8], t[8];
+        root_weights(c, root, &c0, &c1);
+        emission_from_table(tab, c, c0, c1, e);
+#pragma unroll
+        for (int j = 0; j < 8; j++) {
+            e[j] = on ? e[j] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; u++) V[u][j] *= e[j];
+            t[j] = (V[0][j] + V[1][j]) + (V[2][j] + V[3][j]);
+        }
+        const double sum = chain_total<false>(t);
+        const double inv = fast_rcp(sum > 0.0 ? sum : 1.0);
+#pragma unroll
+        for (int u = 0; u < 4; u++)
+#pragma unroll
+            for (int j = 0; j < 8; j++) V[u][j] *= inv;
+        if (m != mk) continue;
+        // a selected marker: the sixteen sums against beta
+        const double* wp = wrow + (size_t)(m - jb.first) * CNF2_TURN_ROW + 512;
+        double h[8];                                     // [u][parity of the register = class bit 1 of v]
+        {
+            d2v bq[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) bq[k] = *(const d2v*)(wp + k * 128 + lane * 2);
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                h[2 * u]     = (V[u][0] * bq[0].x + V[u][2] * bq[1].x) + (V[u][4] * bq[2].x + V[u][6] * bq[3].x);
+                h[2 * u + 1] = (V[u][1] * bq[0].y + V[u][3] * bq[1].y) + (V[u][5] * bq[2].y + V[u][7] * bq[3].y);
+            }
+        }
+        // halving: the partner over state bit 1 has the same class bit and the other kA: it keeps the other u >> 1 ...
+        double h4[4], h2[2];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const double lo = h[i], hi = h[4 + i];
+            h4[i] = (kA ? hi : lo) + lane_flip_b1(kA ? lo : hi);
+        }
+        // ... the partner over state bit 2 has the same class bit, the same kA and the other kB: it keeps the other u & 1
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+            const double lo = h4[i], hi = h4[2 + i];
+            h2[i] = (kB ? hi : lo) + lane_flip_b2(kB ? lo : hi);
+        }
+        // this lane: J_s(u, v) of u = 2 kA + kB, v = b0 + 2 i
+        const double x0 = on ? h2[0] : 0.0, x1 = on ? h2[1] : 0.0;
+        const double Z  = chain_sum(x0 + x1);
+        const bool   ok = on && Z > 0.0;
+        const double f  = ok ? ws / Z : 0.0;
+        const double wsum = across_chains_sum(ok ? ws : 0.0);
+        const double y0 = x0 * f, y1 = x1 * f;
+        double y = (kC ? y1 : y0) + lane_xor8(kC ? y0 : y1);
+        y += lane_xor16(y);
+        y += lane_xor32(y);
+        if (lane < 16) {
+            const int u = (kA ? 2 : 0) | (kB ? 1 : 0), v = (b0 ? 1 : 0) | (kC ? 2 : 0);
+            double*   row = q.joint + ((size_t)jb.ind * q.n_pairs + q.pair_off[ja] + (kn - ja - 1)) * 16;
+            row[4 * u + v] = wsum > 0.0 ? y / wsum : 0.0;
+        }
+        kn++;
+        mk = kn < se ? q.sel[kn] : -1;
+    }
+}
+void launch_pair_sweep(const PairParams& q, hipStream_t stream)
+{
+    if (q.n_jobs <= 0 || q.max_anchors <= 0) return;
+    dim3 grid(q.n_jobs, (q.max_anchors + CNF2_WAVES_PER_BLOCK - 1) / CNF2_WAVES_PER_BLOCK);
+    hipLaunchKernelGGL(pair_sweep_kernel, grid, dim3(CNF2_BLOCK), 0, stream, q);
+}
+
+// cnt[c] = the individuals of [0, n_ind) with a mode that has a likelihood on chromosome c (those a pair sweep writes rows
+// for), counted in one thread per chromosome
+__global__ __launch_bounds__(64) void pair_count_kernel(const double* factors, const double* loglik, int n_ind, int n_chrom, int32_t* cnt)
+{
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_chrom) return;
+    int k = 0;
+    for (int i = 0; i < n_ind; i++) {
+        const size_t e = (size_t)i * n_chrom + c;
+        bool any = false;
+        for (int s = 0; s < 8; s++) any = any || factors[e * 8 + s] > (double)CNF2_MINFACTOR_F;
+        k += (any && !isnan(loglik[e])) ? 1 : 0;
+    }
+    cnt[c] = k;
+}
+void launch_pair_count(const double* factors, const double* loglik, int n_ind, int n_chrom, int32_t* cnt, hipStream_t stream)
+{
+    if (n_chrom > 0)
+        hipLaunchKernelGGL(pair_count_kernel, dim3((n_chrom + 63) / 64), dim3(64), 0, stream, factors, loglik, n_ind, n_chrom, cnt);
+}
+
+// The pair rows from the store, brute force (the cross-check of the pair sweep): one block per anchor a = 0 .. S - 2 among the
+// S selected markers of the chromosome (sel: their local indices, ascending), thread g.  Every mode's four class-restricted
+// vectors are carried in LDS from marker to marker with the explicit 64 x 64 transition and the emission of all 8 modes
+// through the sweep's producer / consumer code (as crossover_rows_kernel), rescaled per mode by their common total.
+// out[S (S - 1) / 2][16]: the pairs in ascending anchor, then ascending target; zeros where no mode has a likelihood.
+__global__ __launch_bounds__(64) void pair_rows_kernel(Stage2Params q, const int32_t* sel, int S, double* out)
+{
+    __shared__ double tab[64];
+    __shared__ double E[8][64];
+    __shared__ double V[8][4][64];
+    const int    g  = threadIdx.x;
+    const int    a  = blockIdx.x;
+    const Window w  = q.kp.windows[0];
+    const double factor = q.loglik[0];
+    const int    cls = (g & 1) | ((g >> 2) & 2);
+    double ws[8];
+    for (int s = 0; s < 8; s++) {
+        ws[s] = pair_mode_weight(w, s, q.factors[s], factor);
+        for (int u = 0; u < 4; u++) V[s][u][g] = (ws[s] != 0.0 && cls == u) ? s2_fw(q, s, sel[a], 2, g) : 0.0;
+    }
+    LaneCtx c;
+    make_lane(w, g, &c.L);
+    c.row_root   = w.row[0];
+    c.root_attop = (w.flags[0] & SLOT_FOUNDER) != 0;
+    const int sl = g >> 3;
+    c.s0 = sl & 1;
+    c.s1 = (sl >> 1) & 1;
+    c.s2 = (sl >> 2) & 1;
+    c.lo = state_lo(g);
+    c.active  = true;
+    c.n_combo = 1;
+    size_t pair = (size_t)a * (2 * S - a - 1) / 2;
+    int    kn = a + 1;
+    __syncthreads();
+    for (int ml = sel[a] + 1; ml <= sel[S - 1]; ml++) {
+        const int m = q.first + ml;
+        const Slot root = load_slot(q.kp, c.row_root, m);
+        LineTerms  T;
+        tab[g] = produce_entry(q.kp, c, root, m, &T);
+        __syncthreads();
+        double c0, c1, e[8];
+        root_weights(c, root, &c0, &c1);
+        emission_from_table(tab, c, c0, c1, e);
+        // e of mode sl, state j * 8 + lo sits in this lane's register j
+#pragma unroll
+        for (int j = 0; j < 8; j++) E[sl][j * 8 + c.lo] = e[j];
+        __syncthreads();
+        const double2 r = q.kp.rho[m - 1];
+        const double rt[6] = {r.y, r.x, r.x, r.y, r.x, r.x};
+        double acc[8][4];
+        for (int s = 0; s < 8; s++)
+            for (int u = 0; u < 4; u++) acc[s][u] = 0.0;
+        for (int g2 = 0; g2 < 64; g2++) {
+            const int d = g ^ g2;
+            double    tr = 1.0;
+#pragma unroll
+            for (int t = 0; t < 6; t++) tr *= ((d >> t) & 1) ? rt[t] : 1.0 - rt[t];
+            for (int s = 0; s < 8; s++)
+                for (int u = 0; u < 4; u++) acc[s][u] += V[s][u][g2] * tr;
+        }
+        __syncthreads();
+        for (int s = 0; s < 8; s++) {
+            const double eg = ws[s] != 0.0 ? E[s][g] : 0.0;
+            double       mine = 0.0;
+            for (int u = 0; u < 4; u++) {
+                acc[s][u] *= eg;
+                mine += acc[s][u];
+            }
+            const double tot = across_chains_sum(chain_sum(mine));
+            const double inv = tot > 0.0 ? 1.0 / tot : 1.0;
+            for (int u = 0; u < 4; u++) V[s][u][g] = acc[s][u] * inv;
+        }
+        __syncthreads();
+        if (ml != sel[kn]) continue;
+        double row[16], wsum = 0.0;
+        for (int k = 0; k < 16; k++) row[k] = 0.0;
+        for (int s = 0; s < 8; s++) {
+            if (ws[s] == 0.0) continue;
+            const double b = s2_fw(q, s, ml, 1, g);
+            double J[16], Z = 0.0;
+            for (int u = 0; u < 4; u++)
+                for (int v = 0; v < 4; v++) {
+                    J[4 * u + v] = across_chains_sum(chain_sum(cls == v ? V[s][u][g] * b : 0.0));
+                    Z += J[4 * u + v];
+                }
+            if (!(Z > 0.0)) continue;
+            for (int k = 0; k < 16; k++) row[k] += ws[s] * (J[k] / Z);
+            wsum += ws[s];
+        }
+        if (g < 16) out[(pair + (size_t)(kn - a - 1)) * 16 + g] = wsum > 0.0 ? row[g] / wsum : 0.0;
+        kn++;
+        if (kn >= S) break;
+    }
+}
+void launch_pair_rows(const Stage2Params& q, const int32_t* sel, int S, double* out, hipStream_t stream)
+{
+    if (S >= 2) hipLaunchKernelGGL(pair_rows_kernel, dim3(S - 1), dim3(64), 0, stream, q, sel, S, out);
+}
+
 } // namespace cnf2

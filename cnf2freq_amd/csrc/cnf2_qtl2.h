@@ -7,8 +7,10 @@
 //   null      X0 = [c, c z_1 .. c z_K]
 //   additive  X0, a1, d1, a2, d2                                (CNF2_QTL_ADDITIVE: X0, a1, a2)
 //   full      additive, then a1 a2, a1 d2, d1 a2, d1 d2         (CNF2_QTL_ADDITIVE: additive, then a1 a2)
-// with a = origin[3] - origin[0], d = origin[1] + origin[2] at the pair's two loci.  The full design is fitted only where the
-// loci lie on different chromosomes: there the expectation of a product is the product of the expectations.  One Cholesky
+// with a = origin[3] - origin[0], d = origin[1] + origin[2] at the pair's two loci.  cnf2_qtl_scan2 fits the full design only
+// where the loci lie on different chromosomes: there the expectation of a product is the product of the expectations.
+// cnf2_qtl_scan2_linked fits it on one chromosome too, with the interaction columns' expectations taken from the pair's joint
+// row (qtl2_joint_cells below); for the design, the factor and the cell such a pair is then "not on one chromosome".  One Cholesky
 // factor L of the full design's normal matrix in that order gives all three: with w = L^-1 X'y over the kept columns
 //   RSS0 = sum c y^2 - sum_{X0} w^2,  RSS_add = RSS0 - sum_{kept additive} w^2,  RSS_full = RSS_add - sum_{kept interaction} w^2.
 #ifndef CNF2_QTL2_H
@@ -58,6 +60,24 @@ CNF2_HD void qtl2_column(const Qtl2Design& ds, bool additive, int j, int* u, int
         *u = 2 + ((e - 4) >> 1);
         *v = 1 + ((e - 4) & 1);
     }
+}
+
+// A pair on one chromosome with its joint row J[4 u + v] = P(class u at locus 1, class v at locus 2) (cnf2_sweep_pairs;
+// cnf2_qtl_scan2_linked): the expectation of an interaction column under it.  a is +1 on class 3 and -1 on class 0, d is 1 on
+// classes 1 and 2:
+//   E[a1 a2] = J33 + J00 - J30 - J03     E[a1 d2] = J31 + J32 - J01 - J02     E[d1 a2] = J13 + J23 - J10 - J20
+//   E[d1 d2] = J11 + J12 + J21 + J22
+// cell[0 .. 3]: the four cells, of which the last *neg are subtracted; the value is (J[0] + J[1]) -/+ (J[2] + J[3])
+CNF2_HD void qtl2_joint_cells(bool dom1, bool dom2, int (&cell)[4], int* neg)
+{
+    if (dom1 && dom2) cell[0] = 5, cell[1] = 6, cell[2] = 9, cell[3] = 10, *neg = 0;
+    else if (dom1) cell[0] = 7, cell[1] = 11, cell[2] = 4, cell[3] = 8, *neg = 2;
+    else if (dom2) cell[0] = 13, cell[1] = 14, cell[2] = 1, cell[3] = 2, *neg = 2;
+    else cell[0] = 15, cell[1] = 0, cell[2] = 12, cell[3] = 3, *neg = 2;
+}
+CNF2_HD double qtl2_joint_value(double j0, double j1, double j2, double j3, int neg)
+{
+    return neg ? (j0 + j1) - (j2 + j3) : (j0 + j1) + (j2 + j3);
 }
 
 struct Qtl2Factor {
@@ -175,6 +195,11 @@ struct Qtl2Params {
     double*        chunkmax;     // [L][n_chunks][3][rstride]
     double *       lod_add, *lod_full, *rss0, *pmax;
     int32_t *      rank_add, *rank_full;
+    // cnf2_qtl_scan2_linked (null / 0 otherwise): the joint rows of the pairs on one chromosome, pair (j, k) at row
+    // pair_off[j] + k - j - 1 of an individual's n_pairs
+    const double*  joint;        // [n][n_pairs][16]
+    const int32_t* pair_off;     // [L]
+    int            n_pairs;
 };
 constexpr int QTL2_CHUNK = 64;   // second loci per block of the pair kernel
 void launch_qtl2_mask(const Qtl2Params& q, hipStream_t stream);

@@ -7,6 +7,7 @@
 //   (qtl_gather_kernel of cnf2_qtl_kernels.hip makes the column image Y[n][rn] of a tile)
 //   qtl2_null_kernel    per chromosome pair and column: n_c, sum c y^2, RSS0 of the null design
 //   qtl2_pair_kernel    the hot path: per pair the Gram matrix X'X and X'Y on the f64 matrix cores, factored once per pair
+//   qtl2_pair_linked_kernel   the same body with the joint rows of the pairs on one chromosome (cnf2_qtl_scan2_linked)
 //   qtl2_finish_kernel  per permuted column: the three maxima over all pairs
 //
 // No kernel adds with atomics, the individuals are never split between waves and every sum runs over them in ascending
@@ -146,7 +147,12 @@ void launch_qtl2_null(const Qtl2Params& q, hipStream_t stream)
 // Epilogue: the Gram tile and X'Y go through the wave's LDS; lane 0 factors the tile once with the rank rule, then one lane
 // per column does the forward substitution and the cell (cnf2_qtl2.h).  The observed columns are stored; the permuted ones
 // go into three running maxima per lane, reduced over the block's waves in a fixed order: one value per (j, chunk, column).
-__global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Params q)
+// LINKED (cnf2_qtl_scan2_linked): a pair on one chromosome is fitted the full design too.  The lane of an interaction column
+// reads four cells of the pair's 128-byte joint row instead of forming a product from the two origin rows:
+//   E[a1 a2] = J33 - J30 - J03 + J00,  E[a1 d2] = J31 + J32 - J01 - J02,  E[d1 a2] = J13 + J23 - J10 - J20,  E[d1 d2] = J11 + J12 + J21 + J22
+// (J[4 u + v], u the class at locus 1).  Every other column, and every pair on two chromosomes, is formed as without it.
+template <bool LINKED>
+__device__ __forceinline__ void qtl2_pair_body(const Qtl2Params& q)
 {
     __shared__ double lds[QTL2_WAVES][(QTL2_W + 16 * QTL2_NT) * QTL2_LD];
     const int lane = threadIdx.x & 63;
@@ -178,7 +184,8 @@ __global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Param
         const int k = kb + s;
         if (k >= q.L) break;
         const int      m2 = q.sel[k], c2 = q.selchrom[k];
-        const bool     same = c1 == c2;
+        const bool     linked = LINKED && c1 == c2;          // a pair of one chromosome with its joint rows
+        const bool     same = !LINKED && c1 == c2;           // ... without: no full design
         const uint8_t* cm2 = q.cmask + (size_t)c2 * n;
         const int      cp  = c1 * q.C + c2;
         const int      n_c = q.nc[cp];
@@ -186,6 +193,14 @@ __global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Param
         int su, sv;
         qtl2_column(ds, q.additive != 0, oi, &su, &sv);
         const double* covp = q.cov + (su == 1 ? oi - 1 : 0);
+        // LINKED: the four cells of the joint row that this lane's interaction column adds up (cnf2_qtl2.h)
+        const bool inter = linked && su >= 2 && su != 4 && sv >= 1;
+        int        jc[4] = {0, 0, 0, 0}, neg = 0;
+        size_t     prow = 0;
+        if (LINKED && inter) {
+            qtl2_joint_cells(su == 3, sv == 2, jc, &neg);
+            prow = (size_t)(q.pair_off[j] + k - j - 1) * 16;
+        }
         q2d4 accG = q2d4{0.0, 0.0, 0.0, 0.0}, accY[QTL2_NT];
 #pragma unroll
         for (int nt = 0; nt < QTL2_NT; nt++) accY[nt] = q2d4{0.0, 0.0, 0.0, 0.0};
@@ -194,7 +209,7 @@ __global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Param
 #pragma unroll 1
             for (int i0 = 0; i0 < n; i0 += 4 * QTL2_KU) {
                 q2d2   p01[QTL2_KU], p23[QTL2_KU], r01[QTL2_KU], r23[QTL2_KU];
-                double z[QTL2_KU], y[QTL2_KU][QTL2_NT];
+                double z[QTL2_KU], y[QTL2_KU][QTL2_NT], jq[QTL2_KU][4];
                 bool   in[QTL2_KU], on[QTL2_KU];
 #pragma unroll
                 for (int u = 0; u < QTL2_KU; u++) {
@@ -209,6 +224,15 @@ __global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Param
                     r23[u] = *(const q2d2*)(r + 2);
                     on[u]  = in[u] && cm1[ic] != 0 && cm2[ic] != 0;
                     z[u]   = su == 1 ? covp[(size_t)ic * q.K] : 1.0;
+                    if constexpr (LINKED) {
+#pragma unroll
+                        for (int t = 0; t < 4; t++) jq[u][t] = 0.0;
+                        if (inter) {
+                            const double* jr = q.joint + (size_t)ic * q.n_pairs * 16 + prow;
+#pragma unroll
+                            for (int t = 0; t < 4; t++) jq[u][t] = jr[jc[t]];
+                        }
+                    }
 #pragma unroll
                     for (int nt = 0; nt < QTL2_NT; nt++) y[u][nt] = q.Y[(size_t)ic * q.rstride + col[nt]];
                 }
@@ -218,7 +242,10 @@ __global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Param
                     const double a2 = r23[u].y - r01[u].x, d2 = r01[u].y + r23[u].x;
                     const double uu = su == 0 ? 1.0 : (su == 1 ? z[u] : (su == 2 ? a1 : d1));
                     const double vv = sv == 0 ? 1.0 : (sv == 1 ? a2 : d2);
-                    const double x  = (on[u] && su != 4) ? uu * vv : 0.0;
+                    double       x  = (on[u] && su != 4) ? uu * vv : 0.0;
+                    if constexpr (LINKED) {
+                        if (inter) x = on[u] ? qtl2_joint_value(jq[u][0], jq[u][1], jq[u][2], jq[u][3], neg) : 0.0;
+                    }
                     accG = __builtin_amdgcn_mfma_f64_16x16x4f64(x, x, accG, 0, 0, 0);
 #pragma unroll
                     for (int nt = 0; nt < QTL2_NT; nt++) {
@@ -284,10 +311,14 @@ __global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Param
         }
     }
 }
+__global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_kernel(Qtl2Params q) { qtl2_pair_body<false>(q); }
+__global__ __launch_bounds__(64 * QTL2_WAVES, 2) void qtl2_pair_linked_kernel(Qtl2Params q) { qtl2_pair_body<true>(q); }
 void launch_qtl2_pairs(const Qtl2Params& q, hipStream_t stream)
 {
-    const int cols = 16 * QTL2_NT;
-    hipLaunchKernelGGL(qtl2_pair_kernel, dim3(q.L - 1, q.n_chunks, (q.rn + cols - 1) / cols), dim3(64 * QTL2_WAVES), 0, stream, q);
+    const int  cols = 16 * QTL2_NT;
+    const dim3 grid(q.L - 1, q.n_chunks, (q.rn + cols - 1) / cols);
+    if (q.joint) hipLaunchKernelGGL(qtl2_pair_linked_kernel, grid, dim3(64 * QTL2_WAVES), 0, stream, q);
+    else hipLaunchKernelGGL(qtl2_pair_kernel, grid, dim3(64 * QTL2_WAVES), 0, stream, q);
 }
 
 // perm_max[p][t][3]: one thread per permuted column takes the maxima over every first locus and its chunks

@@ -340,6 +340,54 @@ int cnf2h_qtl2_pair(const double* gram, int n_col, const double* xty, const doub
     return 0;
 }
 
+int cnf2h_qtl2_pair_linked(int n, const double* o1, const double* o2, const double* joint, const uint8_t* mask, int n_cov,
+                           const double* cov, int n_col, const double* y, int additive, int32_t* out_rank, double* rss0_out,
+                           double* lod_add_out, double* lod_full_out)
+{
+    using namespace cnf2;
+    if (n < 0 || !o1 || !o2 || !joint || n_col < 0 || (n_col > 0 && (!y || !rss0_out || !lod_add_out || !lod_full_out)) || n_cov < 0 ||
+        n_cov > QTL2_MAXK || (n_cov > 0 && !cov) || !out_rank)
+        return -2;
+    const Qtl2Design ds = qtl2_design(n_cov, additive != 0, false);
+    const int        W  = ds.nx + ds.nadd + ds.nint;
+    double G[QTL2_W * QTL2_W] = {};
+    std::vector<double> B((size_t)n_col * QTL2_W, 0.0), yy((size_t)n_col, 0.0);
+    int n_c = 0;
+    for (int i = 0; i < n; i++) {
+        if (mask && !mask[i]) continue;
+        n_c++;
+        const double *p = o1 + (size_t)i * 4, *r = o2 + (size_t)i * 4, *J = joint + (size_t)i * 16;
+        const double a1 = p[3] - p[0], d1 = p[1] + p[2], a2 = r[3] - r[0], d2 = r[1] + r[2];
+        double x[QTL2_W] = {};
+        for (int j = 0; j < W; j++) {
+            int su, sv;
+            qtl2_column(ds, additive != 0, j, &su, &sv);
+            if (su >= 2 && su != 4 && sv >= 1) {
+                int cell[4], neg;
+                qtl2_joint_cells(su == 3, sv == 2, cell, &neg);
+                x[j] = qtl2_joint_value(J[cell[0]], J[cell[1]], J[cell[2]], J[cell[3]], neg);
+            } else {
+                const double uu = su == 0 ? 1.0 : (su == 1 ? cov[(size_t)i * n_cov + (j - 1)] : (su == 2 ? a1 : d1));
+                x[j] = uu * (sv == 0 ? 1.0 : (sv == 1 ? a2 : d2));
+            }
+        }
+        for (int j = 0; j < W; j++)
+            for (int k = 0; k <= j; k++) G[j * QTL2_W + k] += x[j] * x[k];
+        for (int c = 0; c < n_col; c++) {
+            const double v = y[(size_t)i * n_col + c];
+            for (int j = 0; j < W; j++) B[(size_t)c * QTL2_W + j] += x[j] * v;
+            yy[c] += v * v;
+        }
+    }
+    const Qtl2Factor f = qtl2_factor(G, QTL2_W, ds, n_c, n_cov, false);
+    out_rank[0] = f.usable, out_rank[1] = f.rank_add, out_rank[2] = f.rank_full;
+    for (int c = 0; c < n_col; c++) {
+        const Qtl2Cell cl = qtl2_cell(G, QTL2_W, ds, f, B.data() + (size_t)c * QTL2_W, 1, yy[c], n_c, false);
+        rss0_out[c] = cl.rss0, lod_add_out[c] = cl.lod_add, lod_full_out[c] = cl.lod_full;
+    }
+    return 0;
+}
+
 int cnf2h_qtlx_marker(const double* gram, int n_col, const double* xty, const double* yy, int n_c, int n_cov, int n_int,
                       int additive, int imprint, int32_t* out_rank, double* rss0_out, double* lod_out, double* coef_out)
 {

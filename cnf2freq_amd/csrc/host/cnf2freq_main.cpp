@@ -4,7 +4,7 @@
 //            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
 //            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]] [--origins F]
 //            [--qtl F --phenofile P [--qtl-covariates name,name] [--qtl-permutations K] [--qtl-seed S] [--qtl-additive]]
-//            [--qtl2 F [--qtl2-every S] --phenofile P [the --qtl-* options]]
+//            [--qtl2 F [--qtl2-every S] [--qtl2-linked] --phenofile P [the --qtl-* options]]
 //            [--qtlx F --phenofile P [--qtl-imprint] [--qtl-interactive name,name] [the --qtl-* options]]
 //            [--qtlem F --phenofile P [--qtl-em-iterations N] [--qtl-em-tol X] [--qtl-imprint] [the --qtl-* options]]
 //            [--qtlvar F --phenofile P [--qtl-var-covariates name,name] [--qtl-var-iterations N] [--qtl-var-tol X] [--qtl-imprint] [the --qtl-* options]]
@@ -87,6 +87,8 @@
 // --qtl2 F [--qtl2-every S] (with --phenofile and the --qtl-* options; not flags of the reference): the two-QTL pair scan
 // (cnf2_qtl_scan2) of every S-th marker of each chromosome, from its first (S = 1 by default; at most 4096 loci), after
 // --qtl where both are given and on the same sweep's rows.  Covariates: at most 6.  F is described at qtl2_scan below.
+// --qtl2-linked (only with --qtl2): the full model on the pairs of one chromosome too, from one pair sweep of the selected
+// loci (cnf2_sweep_pairs, cnf2_qtl_scan2_linked).
 // --qtlx F [--qtl-imprint] [--qtl-interactive name,name] (with --phenofile and the --qtl-* options; not flags of the
 // reference): the extended single-locus scan (cnf2_qtl_scanx) -- per marker the nested models Mendelian (a, d), imprinting
 // (+ i, with --qtl-imprint) and interaction (+ the products of the effects with the named covariates, which must be among
@@ -186,6 +188,7 @@ struct Options {
     std::string qtl2;                    // --qtl2 F: pair scan of the last round's state (with --phenofile and the --qtl-* options)
     int         qtl2_every = 1;          // --qtl2-every S: every S-th marker of each chromosome, from its first
     bool        qtl2_every_set = false;
+    bool        qtl2_linked = false;     // --qtl2-linked: the full model on the pairs of one chromosome too (cnf2_sweep_pairs, cnf2_qtl_scan2_linked)
     std::string qtlx;                    // --qtlx F: extended single-locus scan (with --phenofile and the --qtl-* options)
     bool        qtl_imprint = false;     // --qtl-imprint
     std::string qtl_interactive;         // --qtl-interactive name,name
@@ -423,6 +426,7 @@ static bool parse(int argc, char** argv, Options& o)
                 exit(2);
             }
         }
+        else if (a == "--qtl2-linked") o.qtl2_linked = true;
         else if (a == "--qtl2-every") {
             o.qtl2_every     = atoi(val().c_str());
             o.qtl2_every_set = true;
@@ -2088,6 +2092,9 @@ static void qtlimp_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
 // (markers, positions, lod_add) and, on different chromosomes, the best full pair (markers, positions, lod_full, the
 // additive LOD there) and lod_int = best full - best additive ("-" on one chromosome).  With --qtl-permutations K > 0, after a
 // blank line, per trait the 5 % and 1 % genome-wide thresholds of lod_add, lod_full and lod_int.
+// --qtl2-linked: one pair sweep (cnf2_sweep_pairs) of the selected loci after the origin sweep, and the linked scan
+// (cnf2_qtl_scan2_linked) on its rows: a chromosome with itself reports its best full pair like any other chromosome pair, and
+// the thresholds of lod_full and lod_int run over all pairs.
 static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
 {
     const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
@@ -2124,6 +2131,17 @@ static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
     const uint32_t flags = (opt.qtl_additive ? CNF2_QTL_ADDITIVE : 0) | CNF2_QTL_ORIGIN_DEVICE;
     std::vector<double>  la((size_t)T * LL), lf((size_t)T * LL), thr((size_t)T * 6, 0.0);
     std::vector<int32_t> nused((size_t)T * C * C, 0);
+    std::vector<double>  joint;          // --qtl2-linked: [N][n_pairs][16], swept once
+    bool                 linked = false; // ... and the selection holds two loci of one chromosome
+    // the scan of one group of traits: the linked call where there are joint rows
+    auto scan2 = [&](int Tg, const double* ys, const uint8_t* u, int n_perm, const int32_t* perm, double* a, double* f, int32_t* ra,
+                     int32_t* rf, double* rss, int32_t* nu, double* pm) {
+        const double* cv = K ? cov.data() : nullptr;
+        if (linked)
+            return cnf2_qtl_scan2_linked(ctx, N, nullptr, joint.data(), L, sel.data(), Tg, ys, u, K, cv, n_perm, perm, a, f, ra, rf, rss, nu,
+                                         pm, flags);
+        return cnf2_qtl_scan2(ctx, N, nullptr, L, sel.data(), Tg, ys, u, K, cv, n_perm, perm, a, f, ra, rf, rss, nu, pm, flags);
+    };
     for (const auto& g : groups) {
         const std::vector<int>&     tr = g.second;
         const std::vector<uint8_t>& u  = g.first;
@@ -2141,8 +2159,19 @@ static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
             if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl2: ") + cnf2_last_error(ctx));
             rows_kept = true;
         }
-        rc = cnf2_qtl_scan2(ctx, N, nullptr, L, sel.data(), Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr, a.data(),
-                            f.data(), ra.data(), rf.data(), rss.data(), nu.data(), nullptr, flags);
+        if (opt.qtl2_linked && joint.empty()) {
+            int32_t n_pairs = 0;
+            rc = cnf2_linked_pairs(ctx, L, sel.data(), nullptr, &n_pairs);
+            if (rc == CNF2_OK && n_pairs > 0) {
+                std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), js((size_t)n_pairs * 16);
+                std::vector<int32_t> n1(C);
+                joint.assign((size_t)N * n_pairs * 16, 0.0);
+                rc = cnf2_sweep_pairs(ctx, 0, N, L, sel.data(), fa.data(), ll.data(), joint.data(), js.data(), n1.data(), 0);
+                linked = true;
+            }
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl2-linked: ") + cnf2_last_error(ctx));
+        }
+        rc = scan2(Tg, yg.data(), u.data(), 0, nullptr, a.data(), f.data(), ra.data(), rf.data(), rss.data(), nu.data(), nullptr);
         if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl2: ") + cnf2_last_error(ctx));
         for (int t = 0; t < Tg; t++) {
             std::copy(a.begin() + (size_t)t * LL, a.begin() + (size_t)(t + 1) * LL, la.begin() + (size_t)tr[t] * LL);
@@ -2159,8 +2188,7 @@ static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
             if (n_u >= K + 10 && !qtl_null_residuals(N, Tg, yg.data(), K, K ? cov.data() : nullptr, u.data(), res.data()))
                 throw EngineError(CNF2_ERR_ARG, "--qtl-permutations: the null design (intercept and covariates) of the individuals used for " +
                                                     opt.pheno.columns[opt.qtl_trait_cols[tr[0]]] + " has no full rank");
-            rc = cnf2_qtl_scan2(ctx, N, nullptr, L, sel.data(), Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, NP, perm.data(),
-                                a.data(), f.data(), ra.data(), rf.data(), rss.data(), nu.data(), pm.data(), flags);
+            rc = scan2(Tg, res.data(), u.data(), NP, perm.data(), a.data(), f.data(), ra.data(), rf.data(), rss.data(), nu.data(), pm.data());
             if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtl2 permutations: ") + cnf2_last_error(ctx));
             for (int t = 0; t < Tg; t++)
                 for (int s = 0; s < 3; s++) {
@@ -2188,7 +2216,7 @@ static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_
                 const double best_add = la[(size_t)t * LL + (size_t)aj * L + ak];
                 fprintf(out, "%s\t%d\t%d\t%d\t%d\t%d\t%.5lf\t%.5lf\t%.5lf", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str(), c1 + 1, c2 + 1,
                         (int)nused[((size_t)t * C + c1) * C + c2], (int)sel[aj], (int)sel[ak], P.pos[sel[aj]], P.pos[sel[ak]], best_add);
-                if (c1 == c2) fprintf(out, "\t-\t-\t-\t-\t-\t-\t-\n");
+                if (c1 == c2 && !linked) fprintf(out, "\t-\t-\t-\t-\t-\t-\t-\n");
                 else {
                     const size_t o = (size_t)t * LL + (size_t)fj * L + fk;
                     fprintf(out, "\t%d\t%d\t%.5lf\t%.5lf\t%.5lf\t%.5lf\t%.5lf\n", (int)sel[fj], (int)sel[fk], P.pos[sel[fj]], P.pos[sel[fk]], lf[o],
@@ -2485,6 +2513,10 @@ int main(int argc, char** argv)
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
         opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
+        return 2;
+    }
+    if (opt.qtl2.empty() && opt.qtl2_linked) {
+        fprintf(stderr, "--qtl2-linked needs --qtl2 FILE\n");
         return 2;
     }
     if (opt.qtl2.empty() && opt.qtl2_every_set) {

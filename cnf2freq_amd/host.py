@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("CNF2HOST_LIB") or os.path.join(_HERE, "libcnf2host.so
 SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_get_dims", "cnf2h_destroy", "cnf2h_last_error", "cnf2h_postmarkerdata", "cnf2h_iteration",
            "cnf2h_dump", "cnf2h_deserialize", "cnf2h_get_state", "cnf2h_set_block", "cnf2h_balanced_block", "cnf2h_set_partition", "cnf2h_get_partition", "cnf2h_set_update_flags", "cnf2h_reserve", "cnf2h_get_timing",
            "cnf2h_set_deterministic", "cnf2h_context", "cnf2h_get_passes", "cnf2h_map_mstep", "cnf2h_write_map",
-           "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
+           "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtl2_pair_linked", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
            "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
            "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit", "cnf2h_qtlimp_marker"]
@@ -63,6 +63,7 @@ def load():
         L.cnf2h_qtl_permutations.argtypes = [i32, i32, C.c_uint64, vp, vp, vp]
         L.cnf2h_qtl_null_residuals.argtypes = [i32, i32, vp, i32, vp, vp, vp]
         L.cnf2h_qtl2_pair.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+        L.cnf2h_qtl2_pair_linked.argtypes = [i32, vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp]
         L.cnf2h_qtlx_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.cnf2h_qtlx_column.argtypes = [i32, i32, i32, i32, i32, vp, vp]
         L.cnf2h_qtlcof_marker.argtypes = [vp, i32, vp, vp, i32, i32, i32, C.c_uint32, i32, vp, vp, vp, vp, vp]
@@ -133,6 +134,30 @@ def qtl2_pair(gram, xty, yy, n_c, n_cov, additive=False, same_chrom=False):
     rc = L.cnf2h_qtl2_pair(_p(g), R, _p(b), _p(y2), n_c, n_cov, int(additive), int(same_chrom), _p(rank), *[_p(o) for o in out])
     if rc != 0:
         raise RuntimeError("cnf2h_qtl2_pair failed (%d)" % rc)
+    return dict(usable=bool(rank[0]), rank_add=int(rank[1]), rank_full=int(rank[2]), rss0=out[0], lod_add=out[1], lod_full=out[2])
+
+
+def qtl2_pair_linked(o1, o2, joint, y, cov=None, mask=None, additive=False):
+    """cnf2h_qtl2_pair_linked: one pair of loci on one chromosome as cnf2_qtl_scan2_linked fits it -- o1, o2 [n][4] the
+    origin rows at the two loci, joint [n][16] the pair's rows of sweep_pairs, y [n][R], cov [n][K], mask [n].  A dict as
+    qtl2_pair's.  CPU only."""
+    L = load()
+    o1, o2 = np.ascontiguousarray(o1, np.float64), np.ascontiguousarray(o2, np.float64)
+    J = np.ascontiguousarray(joint, np.float64)
+    yv = np.ascontiguousarray(y, np.float64)
+    yv = yv[:, None] if yv.ndim == 1 else yv
+    n = len(o1)
+    if o1.shape != (n, 4) or o2.shape != (n, 4) or J.shape != (n, 16) or len(yv) != n:
+        raise ValueError("o1, o2 must be [n][4], joint [n][16] and y [n][R]")
+    cv = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    mk = None if mask is None else np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+    R = yv.shape[1]
+    rank = np.zeros(3, np.int32)
+    out = [np.zeros(R) for _ in range(3)]
+    rc = L.cnf2h_qtl2_pair_linked(n, _p(o1), _p(o2), _p(J), None if mk is None else _p(mk), 0 if cv is None else cv.shape[1],
+                                  None if cv is None else _p(cv), R, _p(yv), int(additive), _p(rank), *[_p(o) for o in out])
+    if rc != 0:
+        raise RuntimeError("cnf2h_qtl2_pair_linked failed (%d)" % rc)
     return dict(usable=bool(rank[0]), rank_add=int(rank[1]), rank_full=int(rank[2]), rss0=out[0], lod_add=out[1], lod_full=out[2])
 
 

@@ -67,6 +67,49 @@ def information_content(origin):
     return var / 0.5
 
 
+def linked_pairs(sel, chromstarts):
+    """pairs[n_pairs][2] (int32): the pairs j < k of indices into sel (strictly ascending marker indices) whose markers lie on
+    one chromosome, in ascending j, then ascending k -- the rows of Context.sweep_pairs (cnf2_linked_pairs)."""
+    sel = np.asarray(sel, np.int64)
+    cs = np.asarray(chromstarts, np.int64)
+    if sel.ndim != 1 or (np.diff(sel) <= 0).any() or (len(sel) and (sel[0] < 0 or sel[-1] >= cs[-1])):
+        raise ValueError("sel must be strictly ascending marker indices of the map")
+    sc = np.searchsorted(cs, sel, side="right") - 1
+    out = [(j, k) for j in range(len(sel)) for k in range(j + 1, len(sel)) if sc[k] == sc[j]]
+    return np.asarray(out, np.int32).reshape(-1, 2)
+
+
+# the cells 4 u + v of a pair row in which the side's origin differs between the loci: bit 0 of the class (the first parent's
+# gamete), bit 1 (the second parent's)
+_U, _V = np.divmod(np.arange(16), 4)
+RECOMBINANT_FIRST = (_U & 1) != (_V & 1)
+RECOMBINANT_SECOND = (_U >> 1) != (_V >> 1)
+
+
+def pair_recombination(joint_sum, n_contrib, pairs, sel, chromstarts):
+    """Per pair of a sweep_pairs call, from its sums: the expected share of recombinant gametes between the two loci on each
+    side, read from the two-locus table.  A dict of arrays of length n_pairs: marker1, marker2 (map indices), chrom, n (the
+    contributors of the chromosome), table [n_pairs][4][4] = joint_sum / n (rows: class at the first locus), first = the
+    share of the first parents' gametes whose origin differs between the loci (an odd number of crossovers), second
+    likewise for the second parents'.  For adjacent loci these are the means of sweep_crossovers' xi[.][0] and xi[.][3].
+    NaN where a chromosome has no contributors (n stays 0)."""
+    s = np.asarray(joint_sum, np.float64)
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    sel = np.asarray(sel, np.int64)
+    cs = np.asarray(chromstarts, np.int64)
+    if s.shape != (len(pairs), 16) or len(n_contrib) != len(cs) - 1:
+        raise ValueError("joint_sum must be [n_pairs][16] and n_contrib [C]")
+    m1, m2 = sel[pairs[:, 0]], sel[pairs[:, 1]]
+    chrom = np.searchsorted(cs, m1, side="right") - 1
+    if (chrom != np.searchsorted(cs, m2, side="right") - 1).any():
+        raise ValueError("a pair spans two chromosomes")
+    n = np.asarray(n_contrib, np.int64)[chrom]
+    with np.errstate(invalid="ignore", divide="ignore"):
+        table = np.where(n[:, None] > 0, s / n[:, None], np.nan)
+    return dict(marker1=m1, marker2=m2, chrom=chrom, n=n, table=table.reshape(-1, 4, 4),
+                first=table[:, RECOMBINANT_FIRST].sum(axis=1), second=table[:, RECOMBINANT_SECOND].sum(axis=1))
+
+
 def with_positions(ped, positions_cM_per_chrom):
     """(ped2, is_marker): the pedigree with a column without data (alleles 0, sure 0, hw 0.5 in every row) inserted at every
     position of positions_cM_per_chrom[c] on chromosome c, and is_marker[M2], False at the inserted columns.  The origin

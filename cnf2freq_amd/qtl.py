@@ -123,13 +123,31 @@ def _patterns(y, use):
         yield cols, use & ~missing[:, cols[0]]
 
 
-def scan2(ctx, pheno, sel, cov=None, use=None, permutations=0, seed=0, additive=False, rows=None):
+def pair_rows(ctx, sel):
+    """One pair sweep of the context's pedigree for the markers sel[L] with the rows left on its GPU: a torch tensor
+    [n][n_pairs][16] that scan2(linked=True) takes as `joint`."""
+    import torch
+    n, C = ctx.n_ind, ctx.n_chrom
+    NP = len(ctx.linked_pairs(sel))
+    dev = torch.device("cuda", ctx.device)
+    t = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+    d_f, d_l, d_j, d_s, d_c = t(n, C, 8), t(n, C), t(n, max(NP, 1), 16), t(max(NP, 1), 16), t(C, dtype=torch.int32)
+    if NP:
+        ctx.sweep_pairs_device(0, n, sel, d_f.data_ptr(), d_l.data_ptr(), d_j.data_ptr(), d_s.data_ptr(), d_c.data_ptr())
+        ctx.sync()
+    return d_j
+
+
+def scan2(ctx, pheno, sel, cov=None, use=None, permutations=0, seed=0, additive=False, rows=None, linked=False, joint=None):
     """The pair scan of a whole cross on the context's uploaded pedigree, for every pair of the markers sel[L]: one origin
     sweep with the rows left on the device (or `rows`, the tensor origin_rows returned, e.g. the one a preceding scan used),
     then per pattern of missing phenotypes (NaN) one observed scan with the pattern's own `use`, and with permutations > 0
     one more on the permuted residuals of the null model, as scan does.  A dict: lod_add[T][L][L], lod_full[T][L][L],
     rank_add[T][L][L], rank_full[T][L][L], n_used[T][C][C], perm_max[P][T][3] or None (the maxima of lod_add, lod_full and
-    lod_full - lod_add: thresholds2)."""
+    lod_full - lod_add: thresholds2).
+    linked=True: one pair sweep for sel as well, its rows left on the device (or `joint`, the tensor pair_rows returned), and
+    the linked scan (cnf2_qtl_scan2_linked): the full model is fitted on the pairs of one chromosome too, and perm_max's
+    second and third maxima run over all pairs.  The default is the scan without it, to the bit."""
     y = np.asarray(pheno, np.float64)
     y = y[:, None] if y.ndim == 1 else y
     n, T = y.shape
@@ -139,19 +157,23 @@ def scan2(ctx, pheno, sel, cov=None, use=None, permutations=0, seed=0, additive=
     L, C = len(sel), ctx.n_chrom
     use = np.ones(n, bool) if use is None else np.asarray(use) != 0
     d_o = origin_rows(ctx) if rows is None else rows
+    d_j = (pair_rows(ctx, sel) if joint is None else joint) if linked else None
+    if linked:
+        call = lambda ys, **kw: ctx.qtl_scan2_linked_device(n, d_o.data_ptr(), d_j.data_ptr(), sel, ys, cov=cov, additive=additive, **kw)
+    else:
+        call = lambda ys, **kw: ctx.qtl_scan2_device(n, d_o.data_ptr(), sel, ys, cov=cov, additive=additive, **kw)
     out = dict(lod_add=np.zeros((T, L, L)), lod_full=np.zeros((T, L, L)), rank_add=np.zeros((T, L, L), np.int32),
                rank_full=np.zeros((T, L, L), np.int32), n_used=np.zeros((T, C, C), np.int32),
                perm_max=np.zeros((permutations, T, 3)) if permutations else None)
     for cols, u in _patterns(y, use):
         yk = np.where(u[:, None], y[:, cols], 0.0)
-        got = ctx.qtl_scan2_device(n, d_o.data_ptr(), sel, yk, cov=cov, use=u, additive=additive)
+        got = call(yk, use=u)
         for key in ("lod_add", "lod_full", "rank_add", "rank_full", "n_used"):
             out[key][cols] = got[key]
         if permutations:
             perm = _permutations(n, permutations, seed, use=u)
             res = null_residuals(yk, cov, u)
-            out["perm_max"][:, cols] = ctx.qtl_scan2_device(n, d_o.data_ptr(), sel, res, cov=cov, use=u, perm=perm,
-                                                            additive=additive)["perm_max"]
+            out["perm_max"][:, cols] = call(res, use=u, perm=perm)["perm_max"]
     return out
 
 
@@ -172,8 +194,9 @@ def pair_summary(lod_add, lod_full, sel, chromstarts):
     loci, a dict: trait, chrom1, chrom2; add = (marker 1, marker 2) of the best additive pair and lod_add its LOD; and for
     c1 != c2 full = the best full pair, lod_full its LOD, lod_add_at_full the additive LOD there, and
     lod_int = lod_full - lod_add, the best full against the best additive model of the chromosome pair.  On one chromosome
-    only the additive model is fitted: full is None and lod_full, lod_add_at_full, lod_int are NaN.  The first pair in
-    (j, k) order wins a tie."""
+    the plain scan fits only the additive model -- full is None and lod_full, lod_add_at_full, lod_int are NaN -- and the
+    linked scan (scan2(linked=True)) the full one too: where its lod_full is there, the entry is filled like any other.  The
+    first pair in (j, k) order wins a tie."""
     la, lf = np.asarray(lod_add, np.float64), np.asarray(lod_full, np.float64)
     la, lf = (la[None] if la.ndim == 2 else la), (lf[None] if lf.ndim == 2 else lf)
     sel = np.asarray(sel, np.int64)
@@ -194,7 +217,7 @@ def pair_summary(lod_add, lod_full, sel, chromstarts):
                 ia = int(np.argmax(la[t, pj, pk]))
                 r = dict(trait=t, chrom1=c1, chrom2=c2, add=(int(sel[pj[ia]]), int(sel[pk[ia]])), lod_add=float(la[t, pj[ia], pk[ia]]),
                          full=None, lod_full=np.nan, lod_add_at_full=np.nan, lod_int=np.nan)
-                if c1 != c2:
+                if c1 != c2 or not np.isnan(lf[t, pj, pk]).any():
                     i = int(np.argmax(lf[t, pj, pk]))
                     r.update(full=(int(sel[pj[i]]), int(sel[pk[i]])), lod_full=float(lf[t, pj[i], pk[i]]),
                              lod_add_at_full=float(la[t, pj[i], pk[i]]))

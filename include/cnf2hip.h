@@ -133,6 +133,8 @@ enum {
     CNF2_QTL_IMPRINT  = 1u << 25, /* cnf2_qtl_scanx: the design gets the parent-of-origin (imprinting) effect i = o[1] - o[2] */
     CNF2_QTL_STATE_DEVICE = 1u << 29, /* cnf2_qtl_scan_imp: `state` is a device pointer, e.g. the states a cnf2_sweep_sample call with
                                      CNF2_OUT_DEVICE filled; they are read in place */
+    CNF2_QTL_JOINT_DEVICE = 1u << 30, /* cnf2_qtl_scan2_linked: `joint` is a device pointer (aligned to 16 bytes), e.g. the rows a
+                                     cnf2_sweep_pairs call with CNF2_OUT_DEVICE filled; they are read in place */
     CNF2_LOG_PATHS    = 1u << 9, /* cnf2_sweep records which kernel / producer specialisation swept every job (cnf2_last_paths) */
     CNF2_XPOSE        = 1u << 8  /* sweep kernel variant: the three lane-held state bits of the transition are brought into
                                     registers by a transpose through LDS instead of being exchanged by DPP moves (same
@@ -464,6 +466,42 @@ int cnf2_sweep_origins(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factor
  *                       and weighted with exp(factors[s] - loglik)): the cross-check of the sweep's fused form. */
 int cnf2_origin_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
 
+/* Pair posteriors: the joint origin classes of two markers of one chromosome.  The product of two origin rows is the joint
+ * distribution only across chromosomes; on one chain the two loci are linked.  For an analysed individual i, a chromosome
+ * and two selected markers j < k of it, with the classes, the frame, the modes and the weights w_s of cnf2_sweep_origins:
+ *   J_s(u, v)  = sum_(g, g') [cls g = u] [cls g' = v] A_s,j(g) Phi_s(j -> k)(g, g') B_s,k(g'),     cls g = bit0(g) + 2 bit3(g)
+ *   Phi_s(j -> k) = prod_(m = j+1 .. k) T_(m-1 -> m) diag(e_s,m)
+ *   joint[i][p][4 u + v] = sum_s w_s J_s(u, v) / Z_s / sum_s w_s,     Z_s = sum_(u, v) J_s(u, v)
+ * A = alpha after the emission, B = beta, T the transition of the gap (rate rho.y on bits 0 and 3, rho.x on the others; a
+ * gap of rate 0 is the identity), e the path-free emission of cnf2_emission.  A mode with Z_s not above 0 is left out of the
+ * pair and the weights renormalised.  Every row sums to 1; its margins are the origin rows of the two markers; for adjacent
+ * markers the mass with u & 1 != v & 1 is xi[j][0] of cnf2_sweep_crossovers and that with u >> 1 != v >> 1 is xi[j][3].
+ * Ties, CNF2_NO_TIES and ignoreflag2 do not enter.
+ *   sel [n_sel]     cnf2_qtl_scan2's selection: 2 .. 4096 strictly ascending marker indices.  The pairs are those on one
+ *                   chromosome, in ascending first, then ascending second locus: cnf2_linked_pairs lists them as indices into
+ *                   sel (pairs_out [n_pairs][2] int32 or NULL; n_pairs_out their number, 0 where no two loci are linked)
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal
+ *   joint_out       [n][n_pairs][16] or NULL; all zero where the individual is skipped on the chromosome.  Rows that are not
+ *                   asked for, and host rows, live whole in a buffer of the context (CNF2_ERR_NOMEM: split the range)
+ *   joint_sum_out   [n_pairs][16] the rows added over the individuals in ascending order, without atomics
+ *   n_contrib_out   [n_chrom] (int32) individuals of the range with a likelihood on that chromosome
+ * Outputs are overwritten; a range split adds up (rows and counts exactly, sums to rounding).  A NULL pointer other than
+ * joint_out, a range out of bounds, everything cnf2_qtl_scan2 refuses in sel and a selection without a linked pair return
+ * CNF2_ERR_ARG and write nothing.
+ * In batches sized to the free memory (cnf2_set_batch_jobs caps them; the result does not depend on it, to the bit): the
+ * turn-scan instantiation of the sweep leaves alpha and beta of every marker in the batch buffer, then a wave per
+ * (individual x chromosome, first locus) walks four class-restricted copies of alpha to the chromosome's last selected
+ * marker and forms a row at every selected one.  A call gives the same bits every time.
+ * Flags: CNF2_OUT_DEVICE (the five outputs are device pointers), CNF2_STATIC_JOBS and CNF2_TIES_GENERAL as in
+ * cnf2_sweep_origins.  The call synchronises the context's stream (the job list and the selection). */
+int cnf2_linked_pairs(cnf2_ctx *ctx, int n_sel, const int32_t *sel, int32_t *pairs_out, int32_t *n_pairs_out);
+int cnf2_sweep_pairs(cnf2_ctx *ctx, int ind_begin, int ind_end, int n_sel, const int32_t *sel, double *factors_out,
+                     double *loglik_out, double *joint_out, double *joint_sum_out, int32_t *n_contrib_out, uint32_t flags);
+/*  cnf2_pair_rows       rows_out[S (S - 1) / 2][16] = the rows of cnf2_sweep_pairs for one individual and the S markers of sel
+ *                       on one chromosome (nothing is written where S < 2), from the store by brute force: one block per
+ *                       first locus, one thread per state, the explicit 64 x 64 transition. */
+int cnf2_pair_rows(cnf2_ctx *ctx, int ind, int chrom, int n_sel, const int32_t *sel, double *rows_out);
+
 /* QTL scan: where on the map does a trait sit?  Haley-Knott regression of phenotypes on the origin rows of
  * cnf2_sweep_origins, at every marker, for the observed phenotypes and for permuted ones (the genome-wide threshold of a
  * peak is a quantile of the permutations' maxima).  One definition for this header, cnf2freq_amd/csrc/cnf2_qtl.h (the small
@@ -537,8 +575,9 @@ int cnf2_set_qtl_columns(cnf2_ctx *ctx, int cap);
  * marginal rows give its exact Haley-Knott regressors and it is fitted for every pair.  The interaction regressors are
  * E[a1 a2 | data] and the other products: the jobs are individual x chromosome and the posterior factorises across
  * chromosomes, so for c1 != c2 a product's expectation is the product of the marginal expectations, exactly.  For c1 = c2 it
- * needs the joint posterior of two loci on one chain, which no sweep produces: the full model is fitted only for pairs on
- * different chromosomes, and a pair on one chromosome reports lod_full = NaN and rank_full = -1.
+ * needs the joint posterior of two loci on one chain, which the origin rows do not hold: this call fits the full model only
+ * for pairs on different chromosomes, and a pair on one chromosome reports lod_full = NaN and rank_full = -1.
+ * cnf2_qtl_scan2_linked (below) takes that joint posterior from cnf2_sweep_pairs and fits every pair.
  * One factorisation gives all three: the normal matrix of [full design | y] under the mask, one sequential Cholesky in the
  * column order above; an added column is dropped (pivot 0) when its raw diagonal is 0 or its pivot is below 1e-8 times its
  * raw diagonal.  With w = L^-1 X'y over the kept columns
@@ -571,6 +610,22 @@ int cnf2_qtl_scan2(cnf2_ctx *ctx, int n, const double *origin, int n_sel, const 
                    double *lod_add_out, double *lod_full_out, int32_t *rank_add_out, int32_t *rank_full_out,
                    double *rss0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
 int cnf2_set_qtl2_columns(cnf2_ctx *ctx, int cap);
+/* cnf2_qtl_scan2_linked: cnf2_qtl_scan2 with the full (epistatic) model on the pairs of one chromosome too.  joint
+ * [n][n_pairs][16] holds the rows of cnf2_sweep_pairs for the same sel and the same individuals (a host array, staged whole,
+ * or device memory with CNF2_QTL_JOINT_DEVICE; it is not read where sel has no two loci on one chromosome, and must not be
+ * NULL).  For a pair on one chromosome the full design's interaction columns are the expectations of the products under the
+ * pair's row J[4 u + v]:
+ *   E[a1 a2] = J33 - J30 - J03 + J00      E[a1 d2] = (J31 + J32) - (J01 + J02)
+ *   E[d1 a2] = (J13 + J23) - (J10 + J20)  E[d1 d2] = J11 + J12 + J21 + J22          (CNF2_QTL_ADDITIVE: E[a1 a2] alone)
+ * the additive columns come from the origin rows as ever, and the mask, the rank rule, the factorisation, the clamps and the
+ * cell are cnf2_qtl_scan2's: such a pair reports lod_full and rank_full like any other.  Every other output -- lod_add,
+ * rank_add, rss0, n_used, and lod_full / rank_full of the pairs on two chromosomes -- is cnf2_qtl_scan2's to the bit, and
+ * perm_max[..][1] and [..][2] run over all pairs.  Arguments, flags, refusals and launches are cnf2_qtl_scan2's; the lane that
+ * there forms a product from two origin rows reads four cells of the pair's 128-byte row here. */
+int cnf2_qtl_scan2_linked(cnf2_ctx *ctx, int n, const double *origin, const double *joint, int n_sel, const int32_t *sel,
+                          int n_traits, const double *pheno, const uint8_t *use, int n_cov, const double *cov, int n_perm,
+                          const int32_t *perm, double *lod_add_out, double *lod_full_out, int32_t *rank_add_out,
+                          int32_t *rank_full_out, double *rss0_out, int32_t *n_used_out, double *perm_max_out, uint32_t flags);
 
 /* Extended single-locus scan: does a locus act differently by the parent it came from, and does its effect depend on a
  * covariate?  Per marker three nested Haley-Knott designs are fitted to every phenotype column, observed and permuted.  One

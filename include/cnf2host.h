@@ -146,6 +146,14 @@ int cnf2h_qtl_null_residuals(int n, int n_traits, const double *pheno, int n_cov
  * then per column the cell: out_rank[3] = usable, rank_add, rank_full; rss0_out, lod_add_out, lod_full_out [n_col]. */
 int cnf2h_qtl2_pair(const double *gram, int n_col, const double *xty, const double *yy, int n_c, int n_cov, int additive,
                     int same_chrom, int32_t *out_rank, double *rss0_out, double *lod_add_out, double *lod_full_out);
+/* One pair of loci on one chromosome as cnf2_qtl_scan2_linked fits it, on the host: o1, o2 [n][4] the origin rows at the two
+ * loci, joint [n][16] the pair's rows of cnf2_sweep_pairs, mask [n] (uint8; NULL = everyone) the individuals of the
+ * chromosome's mask, cov [n][n_cov], y [n][n_col] the phenotype columns.  Forms the full design -- the interaction columns
+ * from the joint (cnf2_qtl2.h) --, its normal matrix, X'y and sum y^2 over the masked individuals in ascending order, factors
+ * once with the rank rule, then per column the cell: outputs as cnf2h_qtl2_pair's. */
+int cnf2h_qtl2_pair_linked(int n, const double *o1, const double *o2, const double *joint, const uint8_t *mask, int n_cov,
+                           const double *cov, int n_col, const double *y, int additive, int32_t *out_rank, double *rss0_out,
+                           double *lod_add_out, double *lod_full_out);
 
 /* The small algebra of the extended single-locus scan (cnf2_qtl_scanx of cnf2hip.h; cnf2freq_amd/csrc/cnf2_qtlx.h) on the
  * host, as its tests use it: gram[16][16] is the normal matrix of one marker's design in the model's column order (zero past
