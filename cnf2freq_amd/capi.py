@@ -59,7 +59,7 @@ SYMBOLS = [
     "cnf2_qtl_scan_surv", "cnf2_set_qtlsurv_columns", "cnf2_set_qtlsurv_blocks",
     "cnf2_qtl_scan_var", "cnf2_set_qtlvar_columns",
     "cnf2_qtl_scan_cof", "cnf2_set_qtlcof_columns", "cnf2_qtl_kept_rows",
-    "cnf2_kinship_sums", "cnf2_qtl_scan_cols", "cnf2_qtl_scan_boot", "cnf2_qtl_scan_mv", "cnf2_set_qtlmv_groups",
+    "cnf2_kinship_sums", "cnf2_qtl_scan_fam", "cnf2_qtl_scan_cols", "cnf2_qtl_scan_boot", "cnf2_qtl_scan_mv", "cnf2_set_qtlmv_groups",
     "cnf2_qtl_scan_imp", "cnf2_set_qtlimp_columns",
 ]
 
@@ -147,6 +147,7 @@ def load():
         L.cnf2_set_qtlcof_columns.argtypes = [vp, i32]
         L.cnf2_qtl_kept_rows.argtypes = [vp, i32, i32, vp, vp]
         L.cnf2_kinship_sums.argtypes = [vp, i32, vp, i32, i32, vp, vp, C.c_uint32]
+        L.cnf2_qtl_scan_fam.argtypes = [vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_cols.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_boot.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_qtl_scan_mv.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
@@ -313,6 +314,7 @@ class Context:
                                               len(dous)), "cnf2_upload_pedigree")
         self.n_ind = len(dous)
         self.n_rec = len(par)
+        self.par, self.dous = par, dous        # (cnf2freq_amd.qtl.families reads the families off them)
 
     def upload(self, ped, dous=None):
         """Convenience: everything from a cnf2freq_amd.synth.Pedigree."""
@@ -791,6 +793,56 @@ class Context:
                                         opt(use), K, opt(cov), P, opt(perm), C.c_void_p(d_lod), C.c_void_p(d_coef),
                                         C.c_void_p(d_rank), C.c_void_p(d_rss0), C.c_void_p(d_n_used),
                                         C.c_void_p(d_perm_max) if d_perm_max else None, flags | OUT_DEVICE), "cnf2_sweep_qtl")
+
+    # -- within-family scan --------------------------------------------------------
+    QTLFAM_KEYS = ("lod", "df", "slope", "rss0", "n_used", "n_cells", "perm_max")
+
+    def _qtlfam_call(self, n, origin_ptr, side, grp, cell, n_fam, pheno, cov, use, perm, slopes, flags, out=None):
+        """cnf2_qtl_scan_fam with host outputs (out = None: new arrays) on the rows behind origin_ptr"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        grp = np.ascontiguousarray(grp, np.int32)
+        cell = None if cell is None else np.ascontiguousarray(cell, np.int32)
+        if grp.shape != (n,) or (cell is not None and cell.shape != (n,)):
+            raise ValueError("grp and cell must be [n]")
+        M, Cn, F = self.n_markers, self.n_chrom, int(n_fam)
+        o = out
+        if o is None:
+            o = dict(lod=np.zeros((T, M)), df=np.zeros(M, np.int32), slope=np.zeros((T, M, max(F, 0))) if slopes else None,
+                     rss0=np.zeros((T, Cn)), n_used=np.zeros(Cn, np.int32), n_cells=np.zeros(Cn, np.int32),
+                     perm_max=np.zeros((P, T, Cn)) if P else None)
+        opt = lambda a: None if a is None else _p(a)
+        self._chk(self.L.cnf2_qtl_scan_fam(self.h, n, origin_ptr, int(side), _p(grp), opt(cell), F, T, _p(pheno), opt(use), K, opt(cov),
+                                           P, opt(perm), _p(o["lod"]), _p(o["df"]), opt(o["slope"]), _p(o["rss0"]), _p(o["n_used"]),
+                                           _p(o["n_cells"]), opt(o["perm_max"]), flags), "cnf2_qtl_scan_fam")
+        return o
+
+    def qtl_scan_fam(self, origin, side, grp, n_fam, pheno, cell=None, cov=None, use=None, perm=None, slopes=False, out=None):
+        """cnf2_qtl_scan_fam on host rows origin[n][M][4]: the nested half-sib model -- a mean per cell[n] (None: grp) and a
+        substitution effect per slope group grp[n] (0 .. n_fam-1 the F1 parent on the side, < 0 not nested) on bit 0 (side 0) or
+        bit 3 (side 1) of the origin rows.  A dict: lod[T][M], df[M] (the fitted families), slope[T][M][F] with slopes (NaN for
+        a family that is not fitted), rss0[T][C], n_used[C], n_cells[C], perm_max[P][T][C] (None without permutations).  The
+        model: include/cnf2hip.h; cnf2freq_amd/qtl.py (families, scan_fam, fam_fstat) makes the groups and reads the results."""
+        origin = self._origin_rows(origin)
+        return self._qtlfam_call(origin.shape[0], _p(origin), side, grp, cell, n_fam, pheno, cov, use, perm, slopes, 0, out)
+
+    def qtl_scan_fam_device(self, n, d_origin, side, grp, n_fam, pheno, cell=None, cov=None, use=None, perm=None, slopes=False,
+                            d_out=None):
+        """The same on device rows (d_origin as qtl_scan_device's).  d_out: a dict of device pointers (ints) for QTLFAM_KEYS
+        (slope and perm_max None where not asked for) -- the outputs then stay on the GPU and None is returned."""
+        if d_out is None:
+            return self._qtlfam_call(n, C.c_void_p(d_origin), side, grp, cell, n_fam, pheno, cov, use, perm, slopes, QTL_ORIGIN_DEVICE)
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        grp = np.ascontiguousarray(grp, np.int32)
+        cell = None if cell is None else np.ascontiguousarray(cell, np.int32)
+        opt = lambda a: None if a is None else _p(a)
+        dp = lambda k: C.c_void_p(d_out[k]) if d_out.get(k) else None
+        self._chk(self.L.cnf2_qtl_scan_fam(self.h, n, C.c_void_p(d_origin), int(side), _p(grp), opt(cell), int(n_fam), T, _p(pheno),
+                                           opt(use), K, opt(cov), P, opt(perm), dp("lod"), dp("df"), dp("slope"), dp("rss0"),
+                                           dp("n_used"), dp("n_cells"), dp("perm_max"), QTL_ORIGIN_DEVICE | OUT_DEVICE),
+                  "cnf2_qtl_scan_fam")
+        return None
 
     # -- multiple-imputation scan ------------------------------------------------
     def set_qtlimp_columns(self, cap):

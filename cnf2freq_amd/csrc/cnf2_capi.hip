@@ -34,6 +34,7 @@
 #include "cnf2_qtlboot.h"
 #include "cnf2_qtlmv.h"
 #include "cnf2_qtlimp.h"
+#include "cnf2_qtlfam.h"
 
 using namespace cnf2;
 
@@ -268,6 +269,13 @@ struct cnf2_ctx {
     DevBuf<uint8_t> d_qi_state;
     DevBuf<double>  d_qi_mkd, d_qi_tilemax, d_qi_lod, d_qi_coef, d_qi_rss0, d_qi_pmax, d_qi_draw;
     DevBuf<int32_t> d_qi_map, d_qi_bad, d_qi_nc, d_qi_rank;   // d_qi_map: as d_q_map
+
+    // within-family scan (cnf2_qtl_scan_fam): the centred covariates and column image in gather order, the chromosome, family
+    // and marker records, the null fits, the tile maxima, the observed columns' gamma, staged outputs; the staged inputs and
+    // the masks are the single scan's buffers
+    DevBuf<double>  d_qf_Z, d_qf_Y, d_qf_chrom, d_qf_rec, d_qf_hrec, d_qf_null, d_qf_tilemax, d_qf_gamma;
+    DevBuf<double>  d_qf_lod, d_qf_slope, d_qf_rss0, d_qf_pmax;
+    DevBuf<int32_t> d_qf_map, d_qf_nc, d_qf_ncells, d_qf_df;   // d_qf_map: as d_q_map, then the gather list (cnf2_qtlfam.h)
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -1923,6 +1931,120 @@ int cnf2_sweep_qtl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_ou
     QtlOrigin org;
     org.dev = ctx->d_org;
     return qtl_scan_impl(ctx, org, a, mask, flags);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Within-family scan (cnf2_qtlfam.h, cnf2_qtlfam_kernels.hip), in the scans' order of steps.  The individuals it uses are
+// those of `use` with grp >= 0: that mask is what the checks, the centring and the kernels see.
+// ------------------------------------------------------------------------------------------------
+int cnf2_qtl_scan_fam(cnf2_ctx* ctx, int n, const double* origin, int side, const int32_t* grp, const int32_t* cell, int n_fam,
+                      int n_traits, const double* pheno, const uint8_t* use, int n_cov, const double* cov, int n_perm,
+                      const int32_t* perm, double* lod_out, int32_t* df_out, double* slope_out, double* rss0_out,
+                      int32_t* n_used_out, int32_t* n_cells_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    QtlOrigin org;
+    RC_TRY(qtl_origin_source(ctx, n, origin, flags, &org));
+    if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
+    if (n < 1 || n_traits < 1 || !pheno) return fail(ctx, CNF2_ERR_ARG, "n and n_traits must be at least 1 and pheno not NULL");
+    if (side < 0 || side > 1 || !grp || n_fam < 1) return fail(ctx, CNF2_ERR_ARG, "side must be 0 or 1, grp not NULL and n_fam at least 1");
+    if (n_cov < 0 || n_cov > QTL_MAXK || (n_cov > 0 && !cov)) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d, with cov", QTL_MAXK);
+    if (n_perm < 0 || (n_perm > 0) != (perm != nullptr) || (n_perm > 0) != (perm_max_out != nullptr))
+        return fail(ctx, CNF2_ERR_ARG, "perm and perm_max_out must be NULL exactly when n_perm is 0");
+    if (!lod_out || !df_out || !rss0_out || !n_used_out || !n_cells_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if ((size_t)n_traits * ((size_t)n_perm + 1) > (size_t)1 << 30) return fail(ctx, CNF2_ERR_ARG, "too many columns");
+    std::vector<uint8_t> nested(n);
+    for (int i = 0; i < n; i++) nested[i] = ((!use || use[i]) && grp[i] >= 0) ? 1 : 0;
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, nested.data(), cov, perm, lod_out, nullptr, rss0_out, perm_max_out, df_out, n_used_out};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_check_values(ctx, a, &mask));
+    RC_TRY(qtl_check_perm(ctx, n, n_perm, perm, mask.data()));
+    QtlFamLayout lay;
+    int          bad_i = 0, bad_row = 0;
+    switch (qtlfam_layout(n, mask.data(), grp, cell, n_fam, &lay, &bad_i)) {
+    case QTLFAM_GRP_RANGE: return fail(ctx, CNF2_ERR_ARG, "grp of individual %d is not below n_fam = %d", bad_i, n_fam);
+    case QTLFAM_CELL_NEGATIVE: return fail(ctx, CNF2_ERR_ARG, "cell of individual %d, which is used, is negative", bad_i);
+    case QTLFAM_CELL_SPLIT: return fail(ctx, CNF2_ERR_ARG, "the cell of individual %d has members of two slope groups", bad_i);
+    }
+    if (qtlfam_check_permutations(n, n_perm, perm, lay, &bad_row, &bad_i) != QTLFAM_OK)
+        return fail(ctx, CNF2_ERR_ARG, "permutation %d takes individual %d out of its cell", bad_row, bad_i);
+    QtlCentred centred;
+    qtl_centre(a, mask, centred);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    M = ctx->n_markers, C = ctx->n_chrom, K = n_cov, T = n_traits, F = n_fam, S = lay.S;
+    const size_t R = (size_t)T * ((size_t)n_perm + 1), slots = std::max(1, S);
+    const size_t rt = qtl_column_tile(slots * C, R, n_perm, 0, ctx->qtl_columns[QTL_CAP_SCAN]);
+    QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, 16, true, true);
+    // the gather list behind the marker map: gidx, cellslot, famcell, stepend, folds
+    std::vector<int32_t>& img = map.image;
+    const size_t o_gidx = img.size();
+    img.insert(img.end(), lay.gidx.begin(), lay.gidx.end());
+    const size_t o_cellslot = img.size();
+    img.insert(img.end(), lay.cellslot.begin(), lay.cellslot.end());
+    const size_t o_famcell = img.size();
+    img.insert(img.end(), lay.famcell.begin(), lay.famcell.end());
+    const size_t o_stepend = img.size();
+    img.insert(img.end(), lay.stepend.begin(), lay.stepend.end());
+    const size_t o_folds = img.size();
+    img.insert(img.end(), lay.folds.begin(), lay.folds.end());
+
+    RC_TRY(qtl_origin_reserve(ctx, org));
+    RC_TRY(qtl_reserve_inputs(ctx, a, 0, 0));
+    QtlFamParams q;
+    memset(&q, 0, sizeof(q));
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(n_used_out, ctx->d_qf_nc, (size_t)C, &q.nc));
+        RC_TRY(each(n_cells_out, ctx->d_qf_ncells, (size_t)C, &q.ncells));
+        RC_TRY(each(df_out, ctx->d_qf_df, (size_t)M, &q.df));
+        RC_TRY(each(lod_out, ctx->d_qf_lod, (size_t)T * M, &q.lod));
+        RC_TRY(each(slope_out, ctx->d_qf_slope, (size_t)T * M * F, &q.slope));
+        RC_TRY(each(rss0_out, ctx->d_qf_rss0, (size_t)T * C, &q.rss0));
+        return each(perm_max_out, ctx->d_qf_pmax, (size_t)n_perm * T * C, &q.pmax);
+    };
+    const size_t n_tri = (size_t)K * (K + 1) / 2;
+    RC_TRY(ctx->d_qf_map.ensure(ctx, img.size()));
+    RC_TRY(ctx->d_qf_Z.ensure(ctx, (size_t)C * slots * QTL_MAXK));
+    RC_TRY(ctx->d_qf_Y.ensure(ctx, (size_t)C * slots * rt));
+    RC_TRY(ctx->d_qf_chrom.ensure(ctx, (size_t)C * QTLFAM_CHROM));
+    RC_TRY(ctx->d_qf_rec.ensure(ctx, (size_t)F * (1 + K) * M));
+    RC_TRY(ctx->d_qf_hrec.ensure(ctx, (n_tri + 1) * M));
+    RC_TRY(ctx->d_qf_null.ensure(ctx, (size_t)C * (K + 2) * rt));
+    if (n_perm > 0) RC_TRY(ctx->d_qf_tilemax.ensure(ctx, map.n_tiles * rt));
+    if (slope_out) RC_TRY(ctx->d_qf_gamma.ensure(ctx, std::max<size_t>(1, (size_t)T * M * K)));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    RC_TRY(qtl_origin_stage(ctx, org));
+    RC_TRY(qtl_upload(ctx, ctx->d_qf_map, img.data(), img.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    q.n = n, q.M = M, q.C = C, q.T = T, q.P = n_perm, q.K = K, q.F = F, q.side = side, q.S = S, q.Q = lay.Q;
+    q.origin = org.dev, q.pheno = ctx->d_q_pheno, q.cov = ctx->d_q_cov, q.use = ctx->d_q_use, q.perm = ctx->d_q_perm;
+    q.cs = ctx->d_qf_map, q.mchrom = ctx->d_qf_map + map.o_mchrom;
+    q.tiles = ctx->d_qf_map + map.o_tiles, q.tile_start = ctx->d_qf_map + map.o_tstart, q.n_tiles = (int)map.n_tiles;
+    q.gidx = ctx->d_qf_map + o_gidx, q.cellslot = ctx->d_qf_map + o_cellslot, q.famcell = ctx->d_qf_map + o_famcell;
+    q.stepend = ctx->d_qf_map + o_stepend, q.folds = ctx->d_qf_map + o_folds;
+    q.cmask = ctx->d_q_cmask, q.Z = ctx->d_qf_Z, q.Y = ctx->d_qf_Y, q.chrom = ctx->d_qf_chrom, q.rec = ctx->d_qf_rec;
+    q.hrec = ctx->d_qf_hrec, q.nullq = ctx->d_qf_null, q.tilemax = ctx->d_qf_tilemax;
+    q.gamma = slope_out ? ctx->d_qf_gamma.ptr : nullptr;
+    q.rstride = (int)rt;
+
+    launch_qtlfam_mask(q, ctx->stream);
+    launch_qtlfam_image(q, true, ctx->stream);
+    launch_qtlfam_chrom(q, ctx->stream);
+    launch_qtlfam_design(q, ctx->stream);
+    launch_qtlfam_marker(q, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = (int)r0;
+        q.rn = (int)std::min(rt, R - r0);
+        launch_qtlfam_image(q, false, ctx->stream);
+        launch_qtlfam_null(q, ctx->stream);
+        launch_qtlfam_scan(q, ctx->stream);
+        if (r0 + q.rn > (size_t)T) launch_qtlfam_finish(q, ctx->stream);
+    }
+    if (q.slope) launch_qtlfam_slope(q, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@
 #include "../cnf2_qtlboot.h"
 #include "../cnf2_qtlimp.h"
 #include "../cnf2_qtlmv.h"
+#include "../cnf2_qtlfam.h"
 #include "../cnf2_qtlplan.h"
 #include "cnf2_remap.h"
 
@@ -667,6 +668,35 @@ int64_t cnf2h_qtl_group_tile(int64_t n, int64_t T, int64_t G, int64_t P, int64_t
 {
     if (n < 0 || T < 1 || T > cnf2::QTLMV_MAXT || G < 1 || P < 0 || n_tiles < 0 || cap < 0) return -2;
     return (int64_t)cnf2::qtl_group_tile((size_t)n, (size_t)T, (size_t)G, (size_t)P, (size_t)n_tiles, cap);
+}
+
+// one marker of cnf2_qtl_scan_fam: qtlfam_marker_serial (cnf2_qtlfam.h)
+int cnf2h_qtlfam_marker(int n, const double* origin, int side, const int32_t* grp, const int32_t* cell, int n_fam, int n_traits,
+                        const double* y, int n_cov, const double* cov, const uint8_t* c, double* lod_out, int32_t* df_out,
+                        double* slope_out, double* rss0_out, int32_t* n_used_out, int32_t* n_cells_out)
+{
+    if (n < 1 || !origin || !grp || n_traits < 1 || !y || n_cov < 0 || n_cov > cnf2::QTL_MAXK || (n_cov > 0 && !cov) || !c || !lod_out ||
+        !df_out || !rss0_out || !n_used_out || !n_cells_out)
+        return -2;
+    return cnf2::qtlfam_marker_serial(n, origin, side, grp, cell, n_fam, n_traits, y, n_cov, cov, c, lod_out, df_out, slope_out,
+                                      rss0_out, n_used_out, n_cells_out)
+               ? 0
+               : -2;
+}
+
+// grp / cell of the analysed individuals from the pedigree's parents: the parent on the side and the pair of parents, both
+// numbered in ascending order of the records; -1 where the parent on the side is missing or has no recorded parents
+int cnf2h_qtl_families(int n_rec, const int32_t* par, int n, const int32_t* dous, int side, int32_t* grp_out, int32_t* cell_out,
+                       int32_t* n_fam_out)
+{
+    if (n_rec < 1 || !par || n < 1 || !dous || side < 0 || side > 1 || !grp_out || !cell_out || !n_fam_out) return -2;
+    for (int r = 0; r < n_rec; r++)
+        for (int s = 0; s < 2; s++)
+            if (par[2 * r + s] >= n_rec) return -2;
+    for (int i = 0; i < n; i++)
+        if (dous[i] < 0 || dous[i] >= n_rec) return -2;
+    *n_fam_out = cnf2host::qtl_families(par, n, dous, side, grp_out, cell_out);
+    return 0;
 }
 
 }  // extern "C"

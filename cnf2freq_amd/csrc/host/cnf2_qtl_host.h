@@ -105,6 +105,62 @@ inline bool qtl_null_residuals(int n, int T, const double* pheno, int K, const d
     return true;
 }
 
+// grp[n] / cell[n] of the analysed records dous[n] for the within-family scan (cnf2_qtl_scan_fam; qtl.families): the parent on
+// the side (par[.][side]) and the pair of parents, both numbered from 0 in ascending order of the records; -1 where the
+// parent on the side is missing or has no recorded parents.  par[n_rec][2], -1 = none.  Returns the parents counted.
+inline int qtl_families(const int32_t* par, int n, const int32_t* dous, int side, int32_t* grp, int32_t* cell)
+{
+    std::vector<int32_t>                     parents;
+    std::vector<std::pair<int32_t, int32_t>> pairs;
+    for (int i = 0; i < n; i++) {
+        const int32_t p = par[2 * dous[i] + side];
+        grp[i]          = (p >= 0 && (par[2 * p] >= 0 || par[2 * p + 1] >= 0)) ? p : -1;
+        if (grp[i] >= 0) {
+            parents.push_back(p);
+            pairs.push_back({par[2 * dous[i]], par[2 * dous[i] + 1]});
+        }
+    }
+    std::sort(parents.begin(), parents.end());
+    parents.erase(std::unique(parents.begin(), parents.end()), parents.end());
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    for (int i = 0; i < n; i++) {
+        cell[i] = -1;
+        if (grp[i] < 0) continue;
+        const std::pair<int32_t, int32_t> pr = {par[2 * dous[i]], par[2 * dous[i] + 1]};
+        grp[i]  = (int32_t)(std::lower_bound(parents.begin(), parents.end(), grp[i]) - parents.begin());
+        cell[i] = (int32_t)(std::lower_bound(pairs.begin(), pairs.end(), pr) - pairs.begin());
+    }
+    return (int)parents.size();
+}
+
+// res[n][T]: the residuals of every phenotype column on a mean per cell[n] and cov over the used individuals, 0 for the
+// others (qtl.cell_residuals): every column minus its mean over the used members of the cell, then qtl_null_residuals, whose
+// intercept finds nothing left.  false when the centred covariates have no Cholesky factor.
+inline bool qtl_cell_residuals(int n, int T, const double* pheno, int K, const double* cov, const uint8_t* use, const int32_t* cell,
+                               double* res)
+{
+    std::vector<double>                  y(pheno, pheno + (size_t)n * T), z(cov, cov + (size_t)n * K);
+    std::map<int32_t, std::vector<int>> members;
+    for (int i = 0; i < n; i++)
+        if (use[i]) members[cell[i]].push_back(i);
+    auto centre = [&](std::vector<double>& v, int w) {
+        for (const auto& m : members)
+            for (int k = 0; k < w; k++) {
+                double mean = 0.0;
+                for (int pass = 0; pass < 2; pass++) {
+                    double s = 0.0;
+                    for (int i : m.second) s += v[(size_t)i * w + k] - mean;
+                    mean += s / (double)m.second.size();
+                }
+                for (int i : m.second) v[(size_t)i * w + k] -= mean;
+            }
+    };
+    centre(y, T);
+    centre(z, K);
+    return qtl_null_residuals(n, T, y.data(), K, z.data(), use, res);
+}
+
 // the (1 - alpha) threshold of P maxima (sorted in place): the order statistic number ceil((1 - alpha) P), as qtl.thresholds
 inline double qtl_threshold(std::vector<double>& maxima, double alpha)
 {

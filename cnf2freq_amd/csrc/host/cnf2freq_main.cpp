@@ -14,6 +14,7 @@
 //            [--qtlcof F --phenofile P --qtl-cofactors i,j,k [--qtl-window X] [the --qtl-* options]]
 //            [--qtlboot F --phenofile P --qtl-boot-chrom C [--qtl-boot-replicates B] [--qtl-covariates, --qtl-seed, --qtl-additive]]
 //            [--qtlmv F --phenofile P [--qtl-traits name,name,..] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
+//            [--qtlfam F --phenofile P [--qtl-fam-side first|second|both] [--qtl-cell parent|pair] [--qtl-covariates, --qtl-permutations, --qtl-seed]]
 //            [--qtlimp F --phenofile P [--qtl-imp-draws D] [--qtl-imp-seed S] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
@@ -108,6 +109,10 @@
 // not flags of the reference): the multi-trait scan (cnf2_qtl_scan_mv) -- the joint LOD of the named traits (default: every
 // trait of the table; 16 at most) at every marker, on the individuals that have all of them -- after the other scans where
 // they are given, on the same sweep's rows.  F is described at qtlmv_scan below.
+// --qtlfam F [--qtl-fam-side first|second|both] [--qtl-cell parent|pair] (with --phenofile and --qtl-covariates,
+// --qtl-permutations, --qtl-seed; not flags of the reference): the within-family scan (cnf2_qtl_scan_fam) -- a mean per
+// cell and a substitution effect per F1 parent on the side -- after the scans above where they are given, on the same
+// sweep's rows.  F is described at qtlfam_scan below.
 // --qtlimp F [--qtl-imp-draws D] [--qtl-imp-seed S] (with --phenofile and --qtl-covariates, --qtl-permutations, --qtl-seed,
 // --qtl-additive; not flags of the reference): the multiple-imputation scan (cnf2_qtl_scan_imp) -- --qtl's model on D
 // (default 16, at most 1024) inheritance paths per individual drawn from the posterior with seed S (default 0;
@@ -229,6 +234,10 @@ struct Options {
     std::string qtl_traits;              // --qtl-traits name,name,..: the traits scanned jointly (default: all)
     bool        qtl_traits_set = false;
     std::vector<int> qtlmv_trait_cols;   // columns of pheno, in the order they are scanned
+    std::string qtlfam;                  // --qtlfam F: within-family scan (with --phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed)
+    std::string qtl_fam_side = "both";   // --qtl-fam-side first|second|both
+    std::string qtl_cell = "pair";       // --qtl-cell parent|pair: a mean per parent on the side, or per pair of parents
+    bool        qtlfam_extra_set = false; // one of the two above was given
     std::string qtlimp;                  // --qtlimp F: multiple-imputation scan (with --phenofile and the shared --qtl-* options)
     int         qtl_imp_draws = 16;      // --qtl-imp-draws D
     unsigned long long qtl_imp_seed = 0; // --qtl-imp-seed S
@@ -349,6 +358,15 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--qtlboot") o.qtlboot = val();
         else if (a == "--qtlmv") o.qtlmv = val();
         else if (a == "--qtlimp") o.qtlimp = val();
+        else if (a == "--qtlfam") o.qtlfam = val();
+        else if (a == "--qtl-fam-side") {
+            o.qtl_fam_side     = val();
+            o.qtlfam_extra_set = true;
+        }
+        else if (a == "--qtl-cell") {
+            o.qtl_cell         = val();
+            o.qtlfam_extra_set = true;
+        }
         else if (a == "--qtl-imp-draws") {
             o.qtl_imp_draws    = atoi(val().c_str());
             o.qtlimp_extra_set = true;
@@ -475,6 +493,7 @@ static void qtlcof_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool row
 static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlimp_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void qtlfam_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -585,6 +604,9 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtlvar.empty())
         qtlvar_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
                                      !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty() || !opt.qtlsurv.empty());
+    if (world == 1 && !opt.qtlfam.empty())
+        qtlfam_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
+                                     !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty());
     if (world == 1 && !opt.qtlimp.empty()) qtlimp_scan(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
@@ -1986,6 +2008,119 @@ static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtl);
 }
 
+// --qtlfam after the last round (single GPU) and after the scans above: per side of --qtl-fam-side and per pattern of missing
+// values the within-family scan (cnf2_qtl_scan_fam) of its traits on the rows a cnf2_sweep_qtl left in the context -- theirs,
+// or one of this function's own.  The slope group of an individual is its parent on the side and its mean cell that parent
+// (--qtl-cell parent) or its pair of parents (--qtl-cell pair, the default), by cnf2h_qtl_families' rule; an individual whose
+// parent on the side has no recorded parents is not used.  With --qtl-permutations the residuals of the null model -- cell
+// means and covariates -- are permuted inside the cells.  The file has the form of --qtl's: per marker
+// "chrom<TAB>pos", then per side "n_used<TAB>n_cells<TAB>df" of the first trait's pattern -- the individuals used on the
+// chromosome, the cells among them, the fitted families -- and per trait its LOD; after a blank line per trait
+// "name<TAB>t5<TAB>t1" per side.  The table and the grouping are --qtl's (qtl_scan above).
+static void qtlfam_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    if (!rows_kept) {          // the sweep, with the rows left in the context; its single-locus scan is not reported
+        std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C), y1(N, 0.0), l1(M), c1((size_t)M * 2), r1(C);
+        std::vector<int32_t> k1(M), n1(C);
+        if (cnf2_sweep_qtl(ctx, 0, N, fa.data(), ll.data(), 1, y1.data(), nullptr, 0, nullptr, 0, nullptr, l1.data(), c1.data(), k1.data(),
+                           r1.data(), n1.data(), nullptr, 0) != CNF2_OK)
+            throw EngineError(CNF2_ERR_STATE, std::string("--qtlfam: ") + cnf2_last_error(ctx));
+    }
+    std::vector<int32_t> par((size_t)P.inds.size() * 2), dous(P.dous.begin(), P.dous.end());
+    for (size_t r = 0; r < P.inds.size(); r++) par[2 * r] = P.inds[r].pars[0], par[2 * r + 1] = P.inds[r].pars[1];
+    std::vector<int> sides;
+    if (opt.qtl_fam_side != "second") sides.push_back(0);
+    if (opt.qtl_fam_side != "first") sides.push_back(1);
+    const int NS = (int)sides.size();
+    std::vector<double>  lod((size_t)NS * T * M, 0.0), thr((size_t)NS * T * 2, 0.0);
+    std::vector<int32_t> df0((size_t)NS * M, 0), nused0((size_t)NS * C, 0), ncells0((size_t)NS * C, 0);
+    for (int s = 0; s < NS; s++) {
+        std::vector<int32_t> grp(N), pairs(N);
+        const int            F = std::max(1, qtl_families(par.data(), N, dous.data(), sides[s], grp.data(), pairs.data()));
+        const std::vector<int32_t>& cell = opt.qtl_cell == "pair" ? pairs : grp;
+        std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+        for (int t = 0; t < T; t++) {
+            std::vector<uint8_t> u(N);
+            for (int j = 0; j < N; j++) u[j] = base[j] && grp[j] >= 0 && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+            groups[u].push_back(t);
+        }
+        for (const auto& g : groups) {
+            const std::vector<int>&     tr = g.second;
+            const std::vector<uint8_t>& u  = g.first;
+            const int                   Tg = (int)tr.size();
+            std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M), rss((size_t)Tg * C);
+            std::vector<int32_t> df(M), nu(C), nq(C);
+            for (int j = 0; j < N; j++)
+                for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+            int rc = cnf2_qtl_scan_fam(ctx, N, nullptr, sides[s], grp.data(), cell.data(), F, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr,
+                                       0, nullptr, l.data(), df.data(), nullptr, rss.data(), nu.data(), nq.data(), nullptr, CNF2_QTL_ORIGIN_DEVICE);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlfam: ") + cnf2_last_error(ctx));
+            if (tr[0] == 0) {
+                std::copy(df.begin(), df.end(), df0.begin() + (size_t)s * M);
+                std::copy(nu.begin(), nu.end(), nused0.begin() + (size_t)s * C);
+                std::copy(nq.begin(), nq.end(), ncells0.begin() + (size_t)s * C);
+            }
+            for (int t = 0; t < Tg; t++) std::copy(l.begin() + (size_t)t * M, l.begin() + (size_t)(t + 1) * M, lod.begin() + ((size_t)s * T + tr[t]) * M);
+            if (NP > 0) {
+                std::vector<int32_t> perm((size_t)NP * N);
+                std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * C);
+                qtl_permutations(N, NP, opt.qtl_seed, u.data(), cell.data(), perm.data());
+                // (a null design without full rank -- a covariate constant within every cell -- leaves the residuals 0: nothing
+                // is scanned then, and every maximum is 0 whatever is permuted)
+                qtl_cell_residuals(N, Tg, yg.data(), K, cov.data(), u.data(), cell.data(), res.data());
+                rc = cnf2_qtl_scan_fam(ctx, N, nullptr, sides[s], grp.data(), cell.data(), F, Tg, res.data(), u.data(), K, K ? cov.data() : nullptr,
+                                       NP, perm.data(), l.data(), df.data(), nullptr, rss.data(), nu.data(), nq.data(), pm.data(),
+                                       CNF2_QTL_ORIGIN_DEVICE);
+                if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlfam permutations: ") + cnf2_last_error(ctx));
+                for (int t = 0; t < Tg; t++) {
+                    std::vector<double> mx(NP, 0.0);
+                    for (int p = 0; p < NP; p++)
+                        for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[((size_t)p * Tg + t) * C + c]);
+                    thr[((size_t)s * T + tr[t]) * 2]     = qtl_threshold(mx, 0.05);
+                    thr[((size_t)s * T + tr[t]) * 2 + 1] = qtl_threshold(mx, 0.01);
+                }
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtlfam.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlfam);
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+            fprintf(out, "%d\t%.5lf", c + 1, P.pos[m]);
+            for (int s = 0; s < NS; s++) {
+                fprintf(out, "\t%d\t%d\t%d", (int)nused0[(size_t)s * C + c], (int)ncells0[(size_t)s * C + c], (int)df0[(size_t)s * M + m]);
+                for (int t = 0; t < T; t++) fprintf(out, "\t%.5lf", lod[((size_t)s * T + t) * M + m]);
+            }
+            fprintf(out, "\n");
+        }
+    if (NP > 0) {
+        fprintf(out, "\n");
+        for (int t = 0; t < T; t++) {
+            fprintf(out, "%s", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str());
+            for (int s = 0; s < NS; s++) fprintf(out, "\t%.5lf\t%.5lf", thr[((size_t)s * T + t) * 2], thr[((size_t)s * T + t) * 2 + 1]);
+            fprintf(out, "\n");
+        }
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlfam);
+}
+
 // --qtlimp after the last round (single GPU) and after the other scans: one sampling sweep (cnf2_sweep_sample) of
 // --qtl-imp-draws paths per individual with --qtl-imp-seed, then per pattern of missing values the multiple-imputation scan
 // (cnf2_qtl_scan_imp) of its traits on those states, and with --qtl-permutations one more on the permuted residuals of the null
@@ -2486,6 +2621,26 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtlmv FILE needs --phenofile FILE\n");
         return 2;
     }
+    if (opt.gpus > 1 && !opt.qtlfam.empty()) {
+        fprintf(stderr, "--qtlfam needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlfam.empty() && opt.qtlfam_extra_set) {
+        fprintf(stderr, "--qtl-fam-side and --qtl-cell need --qtlfam FILE\n");
+        return 2;
+    }
+    if (!opt.qtlfam.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlfam FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtl_fam_side != "first" && opt.qtl_fam_side != "second" && opt.qtl_fam_side != "both") {
+        fprintf(stderr, "--qtl-fam-side must be first, second or both\n");
+        return 2;
+    }
+    if (opt.qtl_cell != "parent" && opt.qtl_cell != "pair") {
+        fprintf(stderr, "--qtl-cell must be parent or pair\n");
+        return 2;
+    }
     if (opt.gpus > 1 && !opt.qtlimp.empty()) {
         fprintf(stderr, "--qtlimp needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
         return 2;
@@ -2511,7 +2666,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
-        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && opt.qtlfam.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -2548,7 +2703,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty() ||
-         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty() || !opt.qtlimp.empty()) &&
+         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty() || !opt.qtlimp.empty() || !opt.qtlfam.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
     if (!opt.qtlmv.empty() && !prepare_qtlmv(opt)) return 2;

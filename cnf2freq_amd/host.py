@@ -16,7 +16,8 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_qtl_permutations", "cnf2h_qtl_null_residuals", "cnf2h_qtl2_pair", "cnf2h_qtl2_pair_linked", "cnf2h_qtlx_marker", "cnf2h_qtlx_column",
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
            "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
-           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit", "cnf2h_qtlimp_marker"]
+           "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit", "cnf2h_qtlimp_marker",
+           "cnf2h_qtlfam_marker", "cnf2h_qtl_families"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -83,6 +84,8 @@ def load():
         L.cnf2h_qtl_group_tile.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32]
         L.cnf2h_qtl_group_tile.restype = C.c_int64
         L.cnf2h_qtlimp_marker.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_qtlfam_marker.argtypes = [i32, vp, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_qtl_families.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -300,6 +303,44 @@ def qtlimp_marker(state, y, cov=None, c=None, additive=False):
     if rc != 0:
         raise ValueError("cnf2h_qtlimp_marker refused its arguments (%d)" % rc)
     return dict(lod=lod, coef=coef, rank=int(rank[0]), rss0=rss0, n_used=int(n_used[0]), draw_lod=draw)
+
+
+def qtlfam_marker(origin, side, grp, n_fam, y, cell=None, cov=None, c=None, slopes=True):
+    """cnf2h_qtlfam_marker: one marker of the within-family scan (cnf2_qtl_scan_fam) on the marker's rows origin[n][4], the
+    slope groups grp[n] (< 0: not nested), the mean cells cell[n] (None: grp), y[n][T] and cov[n][K] as they enter the sums and
+    the chromosome's mask c[n].  A dict: lod[T], df, slope[T][F] (None without slopes), rss0[T], n_used, n_cells.  CPU only."""
+    L = load()
+    o = np.ascontiguousarray(origin, np.float64).reshape(-1, 4)
+    n = o.shape[0]
+    g = np.ascontiguousarray(grp, np.int32)
+    q = None if cell is None else np.ascontiguousarray(cell, np.int32)
+    v = np.ascontiguousarray(y, np.float64).reshape(n, -1)
+    T = v.shape[1]
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    lod, rss0, slope = np.zeros(T), np.zeros(T), np.zeros((T, n_fam)) if slopes else None
+    df, n_used, n_cells = np.zeros(1, np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_qtlfam_marker(n, _p(o), int(side), _p(g), None if q is None else _p(q), int(n_fam), T, _p(v), K,
+                               None if K == 0 else _p(z), _p(m), _p(lod), _p(df), None if slope is None else _p(slope), _p(rss0),
+                               _p(n_used), _p(n_cells))
+    if rc != 0:
+        raise ValueError("cnf2h_qtlfam_marker refused its arguments (%d)" % rc)
+    return dict(lod=lod, df=int(df[0]), slope=slope, rss0=rss0, n_used=int(n_used[0]), n_cells=int(n_cells[0]))
+
+
+def qtl_families(par, dous, side):
+    """cnf2h_qtl_families: (grp[n], cell[n], F) of the analysed records dous[n] from the pedigree's par[n_rec][2] -- the parent
+    on the side (0: the first, 1: the second) and the pair of parents, numbered from 0; -1 where that parent is missing or has
+    no recorded parents.  CPU only."""
+    L = load()
+    par = np.ascontiguousarray(par, np.int32).reshape(-1, 2)
+    dous = np.ascontiguousarray(dous, np.int32)
+    grp, cell, F = np.zeros(len(dous), np.int32), np.zeros(len(dous), np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_qtl_families(len(par), _p(par), len(dous), _p(dous), int(side), _p(grp), _p(cell), _p(F))
+    if rc != 0:
+        raise ValueError("cnf2h_qtl_families refused its arguments (%d)" % rc)
+    return grp, cell, int(F[0])
 
 
 def qtl_marker_map(chromstarts, tile, chrom_begin=0, chrom_end=None, with_mchrom=False, whole_map_header=True):

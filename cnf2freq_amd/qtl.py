@@ -43,7 +43,15 @@ The multi-trait scan (Context.qtl_scan_mv, cnf2_qtl_scan_mv) asks whether a locu
 
 The multiple-imputation scan (Context.qtl_scan_imp, cnf2_qtl_scan_imp) fits scan's model to hard genotypes sampled from the
 posterior and combines the draws on the likelihood scale: sample_states, sampled_classes and scan_imp; thresholds and peaks
-read it as they read scan."""
+read it as they read scan.
+
+The within-family scan (Context.qtl_scan_fam, cnf2_qtl_scan_fam) drops the assumption that the founder lines are fixed for
+different QTL alleles, which an outbred cross does not meet: every F1 parent on a side gets its own mean and its own
+substitution effect on the bit of the origin rows that says which of its two alleles an offspring received (the nested
+half-sib model of Knott, Elsen and Haley 1996).  families makes the slope groups and mean cells from a pedigree, scan_fam
+scans one side or both with permutations inside the cells, and fam_fstat turns a profile into F statistics: the number of
+fitted families varies along the map, so a bare LOD is not comparable between markers without it.  thresholds and peaks read
+a side's profile as they read scan."""
 import numpy as np
 
 from . import synth
@@ -253,6 +261,108 @@ def scan(ctx, pheno, cov=None, use=None, permutations=0, seed=0, additive=False,
             out["perm_max"][:, cols] = ctx.qtl_scan_device(n, d_o.data_ptr(), res, cov=cov, use=u, perm=perm,
                                                            additive=additive)["perm_max"]
     return out
+
+
+def families(ped, side):
+    """(grp[n], cell[n], F) of the analysed individuals of a pedigree (anything with par[R][2] and dous[n]: a
+    synth.Pedigree, a Context after upload) for the within-family scan: grp the F1 parent on the side (0 or "first": par[.][0],
+    1 or "second": par[.][1]) and cell the pair of parents, both numbered from 0 in ascending order of the records; -1 where
+    that parent is missing or has no recorded parents, so that its bit of the origin rows has no meaning.  F the parents
+    counted.  (cnf2h_qtl_families of the host library, which `cnF2freq --qtlfam` uses.)"""
+    from . import host
+    return host.qtl_families(ped.par, ped.dous, _side(side))
+
+
+def _side(side):
+    if side in (0, 1):
+        return int(side)
+    if side in ("first", "second"):
+        return 0 if side == "first" else 1
+    raise ValueError("side must be 0, 1, 'first', 'second' or 'both'")
+
+
+def cell_residuals(pheno, cell, cov=None, use=None):
+    """null_residuals of the within-family scan's null model: a mean per cell[n] and the covariates, over the used
+    individuals (0 for the others).  These are what scan_fam permutes inside the cells."""
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n = y.shape[0]
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    cell = np.asarray(cell)
+    res = np.zeros_like(y)
+    if use.any():
+        ids = np.unique(cell[use])
+        X = (cell[use][:, None] == ids[None, :]).astype(np.float64)
+        if cov is not None:
+            z = np.asarray(cov, np.float64).reshape(n, -1)[use]
+            X = np.concatenate([X, z - z.mean(axis=0)], axis=1)
+        yu = y[use] - y[use].mean(axis=0)
+        res[use] = yu - X @ np.linalg.lstsq(X, yu, rcond=None)[0]
+    return res
+
+
+def scan_fam(ctx, pheno, side="both", grp=None, cell=None, cov=None, use=None, permutations=0, seed=0, rows=None, slopes=False):
+    """The within-family scan of a whole cross on the context's uploaded pedigree: one origin sweep with the rows left on the
+    device (or `rows`, the tensor of origin_rows), then per pattern of missing phenotypes (NaN) one observed scan with the
+    pattern's own `use`, and with permutations > 0 one more on the residuals of the cell-centred null model (cell_residuals),
+    permuted inside the cells (permutations(..., strata=cell)).  grp / cell: the slope groups and mean cells (None: families
+    of the uploaded pedigree -- the parent on the side and the pair of parents).  A dict: lod[T][M], df[T][M] (the design, and
+    with it df, depends on who is used), slope[T][M][F] with slopes, rss0[T][C], n_used[T][C], n_cells[T][C], n_fam,
+    perm_max[P][T][C] or None.  side "both": two calls, {"first": dict, "second": dict}; grp and cell are then pairs."""
+    if side == "both":
+        pair = lambda a: (None, None) if a is None else a
+        d_o = origin_rows(ctx) if rows is None else rows
+        return {name: scan_fam(ctx, pheno, name, pair(grp)[k], pair(cell)[k], cov, use, permutations, seed, d_o, slopes)
+                for k, name in enumerate(("first", "second"))}
+    side = _side(side)
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    if grp is None:
+        grp, fam_cell, F = families(ctx, side)
+        cell = fam_cell if cell is None else cell
+    else:
+        grp = np.asarray(grp, np.int32)
+        F = int(grp.max()) + 1 if (grp >= 0).any() else 1
+    cell = grp if cell is None else np.asarray(cell, np.int32)
+    use = (np.ones(n, bool) if use is None else np.asarray(use) != 0) & (grp >= 0)
+    M, C = ctx.n_markers, ctx.n_chrom
+    d_o = origin_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M)), df=np.zeros((T, M), np.int32), slope=np.full((T, M, F), np.nan) if slopes else None,
+               rss0=np.zeros((T, C)), n_used=np.zeros((T, C), np.int32), n_cells=np.zeros((T, C), np.int32), n_fam=F,
+               perm_max=np.zeros((permutations, T, C)) if permutations else None)
+    call = lambda ys, u, **kw: ctx.qtl_scan_fam_device(n, d_o.data_ptr(), side, grp, F, ys, cell=cell, cov=cov, use=u, **kw)
+    for cols, u in _patterns(y, use):
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = call(yk, u, slopes=slopes)
+        out["lod"][cols], out["df"][cols], out["rss0"][cols] = got["lod"], got["df"], got["rss0"]
+        out["n_used"][cols], out["n_cells"][cols] = got["n_used"], got["n_cells"]
+        if slopes:
+            out["slope"][cols] = got["slope"]
+        if permutations:
+            perm = _permutations(n, permutations, seed, use=u, strata=cell)
+            out["perm_max"][:, cols] = call(cell_residuals(yk, cell, cov, u), u, perm=perm)["perm_max"]
+    return out
+
+
+def fam_fstat(lod, df, n_used, n_cells, K, chromstarts=None):
+    """(F, df1, df2) of a within-family profile: lod[T][M] and df[M] or [T][M] of scan_fam, n_used and n_cells per marker
+    (anything that broadcasts against lod) or, with chromstarts, per chromosome ([C] or [T][C]).  RSS0 / RSS1 = 10^(2 lod /
+    n_c), df1 = df, df2 = n_c - n_cells - K - df and F = (RSS0 / RSS1 - 1) df2 / df1: under the null an F(df1, df2) variate
+    at every marker, whatever its number of fitted families.  NaN, with df2 = 0, where nothing is fitted."""
+    lod = np.asarray(lod, np.float64)
+    df1 = np.broadcast_to(np.asarray(df), lod.shape).astype(np.int64)
+    if chromstarts is not None:
+        reps = np.diff(np.asarray(chromstarts, np.int64))
+        n_used, n_cells = np.repeat(np.asarray(n_used), reps, axis=-1), np.repeat(np.asarray(n_cells), reps, axis=-1)
+    n_c = np.broadcast_to(np.asarray(n_used), lod.shape).astype(np.int64)
+    df2 = np.where(df1 > 0, n_c - np.broadcast_to(np.asarray(n_cells), lod.shape) - K - df1, 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = 10.0 ** (2.0 * lod / np.maximum(n_c, 1))
+        F = np.where(df1 > 0, (ratio - 1.0) * df2 / np.maximum(df1, 1), np.nan)
+    return F, df1, df2
 
 
 def sampled_classes(state):

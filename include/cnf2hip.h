@@ -862,6 +862,57 @@ int cnf2_qtl_scan_mv(cnf2_ctx *ctx, int n, const double *origin, int n_traits, c
                      double *perm_max_out /* [P][C] */, uint32_t flags);
 int cnf2_set_qtlmv_groups(cnf2_ctx *ctx, int cap);
 
+/* Within-family scan: the nested (half-sib) model of Knott, Elsen and Haley (1996).  Every scan above regresses on
+ * a = P(BB) - P(AA), which assumes that the two founder lines are fixed for different QTL alleles.  In an outbred cross an F1
+ * parent may be heterozygous or homozygous at the QTL, and the sign of "allele from its first parent" against "allele from its
+ * second" differs from parent to parent: a line-cross scan averages the signs away.  Here every F1 parent on one side gets
+ * its own mean and its own substitution effect, fitted on its offspring.  The regressor is bit 0 (side 0) or bit 3 (side 1)
+ * of the origin sweep's absolute frame -- the allele from par[.][side] descends from that parent's par[.][1] -- which is the
+ * same labelling for every offspring of the parent and a linear function of the origin row: P(bit0 = 1) = o[1] + o[3],
+ * P(bit3 = 1) = o[2] + o[3].  One definition for this header, cnf2freq_amd/csrc/cnf2_qtlfam.h (host and device), the kernels and
+ * tests/qtlfam_reference.py.
+ * Inputs: origin[n][M][4], pheno[n][T], use, cov[n][K] (0 <= K <= 8) and perm[P][n] are cnf2_qtl_scan's, as are
+ * CNF2_QTL_ORIGIN_DEVICE and the centring of traits and covariates over the used individuals.  side is 0 or 1.  grp[n] is the
+ * slope group of individual i: 0 .. n_fam-1 the F1 parent on the side, < 0 not nested, not used.  cell[n] (NULL: grp) is the
+ * mean cell -- typically sire slopes and full-sib family means; all members of a cell must share one grp.  perm must keep
+ * every used individual inside its cell.
+ * Per chromosome c: c_i = use[i] and grp[i] >= 0 and the row at c's first marker is not all zero; n_c = sum c_i.  Every column
+ * v -- a trait, a permuted trait, a covariate -- is centred within cells: v~_i = c_i (v_i - mean of v over the used members of
+ * cell(i)).  S11 = Z~'Z~ (K x K), b0 = Z~'y~, yy = y~'y~, RSS0 = yy - b0' S11^-1 b0.  A chromosome is not scanned when S11 has no
+ * Cholesky factor or n_c - n_cells_used - K < 2: its markers get df 0, lod 0 and slopes NaN.
+ * Per marker m: x_i = c_i (o1 + o3 - o0 - o2) for side 0 and c_i (o2 + o3 - o0 - o1) for side 1.  For every family p, the sums
+ * over its used members:
+ *   d_p = sum over the cells q of p (sum x^2 - (sum x)^2 / n_q),  raw_p = sum x^2,  u_p = sum x_i z~_i,  r_p = sum x_i y~_i.
+ * A family is fitted when raw_p > 0 and d_p >= 1e-8 raw_p; df[m] is the number of fitted families.  The diagonal slope block
+ * is eliminated:
+ *   H = S11 - sum_fitted u_p u_p' / d_p,  g = b0 - sum_fitted u_p r_p / d_p,  gamma = H^-1 g,
+ *   RSS1 = yy - sum_fitted r_p^2 / d_p - g' gamma,  slope_p = (r_p - u_p' gamma) / d_p
+ * (K = 0: no H).  dRSS = RSS0 - RSS1 is clamped to [0, RSS0 (1 - 2^-52)] and lod = (n_c / 2) log10(RSS0 / (RSS0 - dRSS)).  If H has
+ * no factor under cnf2_qtl.h's relative-pivot rule against S11's diagonal (a pivot below 1e-8 times it), or if
+ * n_c - n_cells_used - K - df[m] < 1: df 0, lod 0, slopes NaN.  df varies along the map, so a bare LOD is not comparable
+ * between markers without it (cnf2freq_amd.qtl.fam_fstat).
+ * Outputs: lod_out[T][M]; df_out[M], which depends on the design only; slope_out[T][M][n_fam] of the observed columns (NULL:
+ * not asked for), NaN for a family that is not fitted; rss0_out[T][C]; n_used_out[C] n_c; n_cells_out[C] the cells with a used
+ * member; perm_max_out[P][T][C] (NULL exactly when P = 0).  Host pointers, or device pointers with CNF2_OUT_DEVICE.
+ * Everything cnf2_qtl_scan refuses, a side other than 0 or 1, n_fam < 1, a grp of n_fam or more, a negative cell of a used
+ * individual, a cell with members of two groups and a permutation that takes a used individual out of its cell return
+ * CNF2_ERR_ARG and write nothing.
+ * Launches: on the host the gather list -- the used individuals ordered by (grp, cell, index), every cell padded to a
+ * multiple of 4 slots; per chromosome the mask, the centred covariates in gather order, S11 and its factor; per (marker,
+ * family) the record (1 / d_p or 0, u_p); per marker H's factor and df; per column tile (cnf2_set_qtl_columns caps it; results
+ * do not depend on it) the centred column image in gather order, the null fits, the product and the maxima's finish; the
+ * slopes.  The product is cnf2_qtl_scan's -- 16 markers x 64 columns per wave (32 with more than 2 covariates) on
+ * v_mfma_f64_16x16x4_f64, the marker operand formed in registers from the 32-byte rows read in place through the gather
+ * list, no LDS -- segmented by family: at every family end the accumulators r_p are folded into sum r_p^2 / d_p and into g in
+ * registers and cleared; the solve, clamp and logarithm follow in the lane's registers.  No atomics, every sum in ascending
+ * order of the individuals within a family and of the families within a marker: a call gives the same bits every time,
+ * for every cap, from host or device rows, into host or device outputs. */
+int cnf2_qtl_scan_fam(cnf2_ctx *ctx, int n, const double *origin, int side, const int32_t *grp, const int32_t *cell, int n_fam,
+                      int n_traits, const double *pheno, const uint8_t *use, int n_cov, const double *cov, int n_perm,
+                      const int32_t *perm, double *lod_out /* [T][M] */, int32_t *df_out /* [M] */,
+                      double *slope_out /* [T][M][n_fam] or NULL */, double *rss0_out /* [T][C] */, int32_t *n_used_out /* [C] */,
+                      int32_t *n_cells_out /* [C] */, double *perm_max_out /* [P][T][C] */, uint32_t flags);
+
 /* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
  * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;
  * where a row is soft it leaves the within-individual genotype variance in the residual.  One definition for this header,

@@ -291,6 +291,26 @@ int cnf2h_qtlmv_marker(int n, const double *origin, int n_traits, const double *
                        int32_t *n_used_out);
 int64_t cnf2h_qtl_group_tile(int64_t n, int64_t T, int64_t G, int64_t P, int64_t n_tiles, int cap);
 
+/* The host side of the within-family scan (cnf2_qtl_scan_fam of cnf2hip.h):
+ *  cnf2h_qtlfam_marker    one marker through cnf2freq_amd/csrc/cnf2_qtlfam.h, by the steps and in the order of the kernels:
+ *                         origin[n][4] the marker's rows, side 0 or 1, grp[n] and cell[n] (NULL: grp) as the scan takes
+ *                         them, y[n][n_traits] and cov[n][n_cov] as they enter the sums (the scan centres them over the
+ *                         used individuals first; the centring within cells is done here), c[n] the chromosome's mask
+ *                         (an individual with grp < 0 is taken out here).  lod_out[n_traits], *df_out,
+ *                         slope_out[n_traits][n_fam] (NULL: not asked for), rss0_out[n_traits], *n_used_out n_c,
+ *                         *n_cells_out the cells with a used member.
+ *  cnf2h_qtl_families     grp_out[n] / cell_out[n] of the analysed individuals dous[n] (records) from the pedigree's
+ *                         par[n_rec][2]: grp the parent on the side (par[.][side]) and cell the pair (par0, par1), both
+ *                         numbered from 0 in ascending order of the records; -1 where the parent on the side is missing or
+ *                         has no recorded parents -- its bit of the origin rows has no meaning there.  *n_fam_out the
+ *                         parents counted.
+ * -2: a bad argument. */
+int cnf2h_qtlfam_marker(int n, const double *origin, int side, const int32_t *grp, const int32_t *cell, int n_fam, int n_traits,
+                        const double *y, int n_cov, const double *cov, const uint8_t *c, double *lod_out, int32_t *df_out,
+                        double *slope_out, double *rss0_out, int32_t *n_used_out, int32_t *n_cells_out);
+int cnf2h_qtl_families(int n_rec, const int32_t *par, int n, const int32_t *dous, int side, int32_t *grp_out, int32_t *cell_out,
+                       int32_t *n_fam_out);
+
 #ifdef __cplusplus
 }
 #endif
