@@ -1170,7 +1170,9 @@ __device__ __forceinline__ uint8_t load_root_allele(const KernelParams& p, const
     return a8[(size_t)c.row_root * p.n_markers + clamp_marker(m0 + c.mi, lo_m, hi_m)];
 }
 // ap: load_root_allele of the same tile; rec_row: line * n_markers of this lane's line
-template <int TQ_SHIFT>
+// ONE_MARKER: every lane of the wave looks at the same marker (the eights: c.mi is the job), so the gap's factors are one
+// value for the wave and come through the scalar cache instead of a vector load of 64 equal addresses (CNF2_UP8_SCALAR_GAP)
+template <int TQ_SHIFT, bool ONE_MARKER = false>
 __device__ __forceinline__ void load_rec(const KernelParams& p, const FastCtx& c, uint32_t rec_row, int m0, int lo_m, int hi_m,
                                          uint8_t ap, RawRec* r)
 {
@@ -1193,10 +1195,19 @@ __device__ __forceinline__ void load_rec(const KernelParams& p, const FastCtx& c
     r->t1   = q2.x;
     r->oo   = q2.y;
     r->bits = ((const uint32_t*)q)[12];
-    const int     mt = m + TQ_SHIFT;
-    const double2 tq = p.tq[mt < 0 ? 0 : mt];
-    r->tq0 = tq.x;
-    r->tq1 = tq.y;
+    const int mt = m + TQ_SHIFT;
+    if (ONE_MARKER) {
+        // (constant address space: nothing writes the map's factors while a sweep runs, and the index is the wave's)
+        typedef double sd2 __attribute__((ext_vector_type(2)));
+        const int mu = __builtin_amdgcn_readfirstlane(mt < 0 ? 0 : mt);
+        const sd2 tq = ((const __attribute__((address_space(4))) sd2*)p.tq)[mu];
+        r->tq0 = tq.x;
+        r->tq1 = tq.y;
+    } else {
+        const double2 tq = p.tq[mt < 0 ? 0 : mt];
+        r->tq0 = tq.x;
+        r->tq1 = tq.y;
+    }
 }
 // PACKED: the unrestricted entries a packed sweep reads only (cnf2_emtab.h packed_reads_unrestricted)
 template <bool CLASSES, bool PACKED = false>
@@ -2841,6 +2852,10 @@ static_assert(TAB_R % 2 == 0 && TAB_2 % 2 == 0 && TAB_STRIDE % 2 == 0, "the A-si
 #ifndef CNF2_UP8_ROW_SUMS
 #define CNF2_UP8_ROW_SUMS 1
 #endif
+// 1: the gap's factors of the wave's marker through the scalar cache; 0: a vector load, every lane the same address (A/B)
+#ifndef CNF2_UP8_SCALAR_GAP
+#define CNF2_UP8_SCALAR_GAP 1
+#endif
 // markers to a forward tile (cnf2_lane.h up8_fwd_*); 1: the forward pass on one table row a marker, as the backward pass (A/B)
 #ifndef CNF2_UP8_FWD_TILE
 #define CNF2_UP8_FWD_TILE 8
@@ -2922,7 +2937,8 @@ struct Up8FwdSlot {
 };
 __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_kernel(KernelParams p)
 {
-    constexpr int NR = 2, ROW = UP8_SPILL_ROW, TS = TAB_STRIDE;
+    constexpr int  NR = 2, ROW = UP8_SPILL_ROW, TS = TAB_STRIDE;
+    constexpr bool SG = CNF2_UP8_SCALAR_GAP != 0;
     __shared__ __attribute__((aligned(16))) double lds[CNF2_WAVES_PER_BLOCK][8 * TS];
 
     const int wib   = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -3059,12 +3075,12 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         if constexpr (CNF2_UP8_FWD_TILE == 1) {
             // A/B form: a table row per marker, as the backward pass keeps them
             const Up8FwdRow src{myrow, c};
-            load_rec<0>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rraw);
+            load_rec<0, SG>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rraw);
             ap_next = load_root_allele(pq, cp, first + 1 + moff, first, last);
             for (int m = first; m <= last; m++) {
                 produce_row_rec<false, true>(cp, tab, true, rraw);
                 // (unconditional, as in fb_unipack_kernel: no copy, so no wait, between these loads and the next marker's producer)
-                load_rec<0>(pq, cp, rec_row, m + 1 + moff, first, last, ap_next, &rraw);
+                load_rec<0, SG>(pq, cp, rec_row, m + 1 + moff, first, last, ap_next, &rraw);
                 ap_next = load_root_allele(pq, cp, m + 2 + moff, first, last);
                 wave_lds_fence();
                 if ((m - first) & 1) fwd_step(odd_t(), src, m);
@@ -3084,8 +3100,8 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
             const double* const qb = tab + up8_fwd_at(0, rj, up8_fwd_part(4));
             RawRec  rr[2];
             uint8_t ap[2];
-            load_rec<0>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rr[0]);
-            load_rec<0>(pq, cp, rec_row, first + 1 + moff, first, last, load_root_allele(pq, cp, first + 1 + moff, first, last), &rr[1]);
+            load_rec<0, SG>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rr[0]);
+            load_rec<0, SG>(pq, cp, rec_row, first + 1 + moff, first, last, load_root_allele(pq, cp, first + 1 + moff, first, last), &rr[1]);
             ap[0] = load_root_allele(pq, cp, first + 2 + moff, first, last);
             ap[1] = load_root_allele(pq, cp, first + 3 + moff, first, last);
             int tile = 0;
@@ -3095,7 +3111,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
                 for (int t = 0; t < T; t++) {
                     produce_slot_rec(cp, tab + toff + up8_fwd_at(t, 0, 0), rr[t & 1]);
                     // (unconditional, as above; what is asked for here is produced two markers on)
-                    load_rec<0>(pq, cp, rec_row, m0 + t + 2 + moff, first, last, ap[t & 1], &rr[t & 1]);
+                    load_rec<0, SG>(pq, cp, rec_row, m0 + t + 2 + moff, first, last, ap[t & 1], &rr[t & 1]);
                     ap[t & 1] = load_root_allele(pq, cp, m0 + t + 4 + moff, first, last);
                 }
                 wave_lds_fence();
@@ -3387,7 +3403,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
             }
             transition_uniform(S.b, r_m.x, r_m.y);
         };
-        load_rec<-1>(pq, cp, rec_row, last + moff, first, last, load_root_allele(pq, cp, last + moff, first, last), &rraw);
+        load_rec<-1, SG>(pq, cp, rec_row, last + moff, first, last, load_root_allele(pq, cp, last + moff, first, last), &rraw);
         ap_next = load_root_allele(pq, cp, last - 1 + moff, first, last);
 #if !CNF2_UP8_ROW_SUMS && !defined(CNF2_X_NOPARK)
         // epilogue role: row mi2 = job, chain sub
@@ -3397,7 +3413,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
             take_spill();
             ask_spill(m - first - 1);
             produce_row_rec<true, true>(cp, tab, true, rraw);
-            load_rec<-1>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);       // (unconditional, as forward)
+            load_rec<-1, SG>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);       // (unconditional, as forward)
             ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
             wave_lds_fence();                   // the producer lanes' rows are in place for the recursion lanes that read them
             if ((m - first) & 1) marker(odd_t(), myrow, m);
