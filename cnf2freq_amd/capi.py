@@ -53,6 +53,7 @@ SYMBOLS = [
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
     "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
+    "cnf2_sweep_descent", "cnf2_descent_rows", "cnf2_qtl_scan_hap",
     "cnf2_linked_pairs", "cnf2_sweep_pairs", "cnf2_pair_rows", "cnf2_qtl_scan2_linked",
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
@@ -131,6 +132,9 @@ def load():
         L.cnf2_loo_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_sweep_origins.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_origin_rows.argtypes = [vp, i32, i32, vp]
+        L.cnf2_sweep_descent.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_descent_rows.argtypes = [vp, i32, i32, vp]
+        L.cnf2_qtl_scan_hap.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_linked_pairs.argtypes = [vp, i32, vp, vp, vp]
         L.cnf2_sweep_pairs.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_pair_rows.argtypes = [vp, i32, i32, i32, vp, vp]
@@ -634,6 +638,39 @@ class Context:
                                             C.c_void_p(d_bits) if d_bits else None, C.c_void_p(d_origin_sum),
                                             C.c_void_p(d_n_contrib), flags | OUT_DEVICE), "cnf2_sweep_origins")
 
+    # -- descent rows ------------------------------------------------------------
+    def descent_rows(self, ind, chrom=0):
+        """[mc][8], the descent row of one individual and chromosome from the alpha/beta store, brute force (the cross-check
+        of sweep_descent); zeros where the individual is skipped."""
+        mc = int(self.chromstarts[chrom + 1] - self.chromstarts[chrom])
+        v = np.zeros((mc, 8))
+        self._chk(self.L.cnf2_descent_rows(self.h, ind, chrom, _p(v)), "cnf2_descent_rows")
+        return v
+
+    def sweep_descent(self, ind_begin=0, ind_end=None, rows=True, full_spill=False, ties_general=False, static_jobs=False):
+        """cnf2_sweep_descent: factors / loglik as sweep(); descent[n][M][8], per side (0..3 the first parent's, 4..7 the
+        second parent's) the probabilities of the classes 2 w + b -- the allele from that parent descends from the parent's
+        par[.][w], strand b of that grandparent, the strand labelled by the grandparent's own record (allele order and hw;
+        include/cnf2hip.h).  All zero where skipped; None with rows=False.  n_contrib: the contributing individuals per
+        chromosome.  cnf2freq_amd/origins.py reads them (DESCENT_MASK, descent_columns, descent_calls)."""
+        ind_end = self.n_ind if ind_end is None else ind_end
+        n = ind_end - ind_begin
+        factors = np.zeros((n, self.n_chrom, 8))
+        loglik = np.zeros((n, self.n_chrom))
+        descent = np.zeros((n, self.n_markers, 8)) if rows else None
+        cnt = np.zeros(self.n_chrom, np.int32)
+        flags = ((FULL_SPILL if full_spill else 0) | (TIES_GENERAL if ties_general else 0)
+                 | (STATIC_JOBS if static_jobs else 0))
+        self._chk(self.L.cnf2_sweep_descent(self.h, ind_begin, ind_end, _p(factors), _p(loglik),
+                                            _p(descent) if rows else None, _p(cnt), flags), "cnf2_sweep_descent")
+        return dict(factors=factors, loglik=loglik, descent=descent, n_contrib=cnt)
+
+    def sweep_descent_device(self, ind_begin, ind_end, d_factors, d_loglik, d_descent, d_n_contrib, flags=0):
+        """Device-pointer form (ints; d_descent may be None: the rows then stay in the context)."""
+        self._chk(self.L.cnf2_sweep_descent(self.h, ind_begin, ind_end, C.c_void_p(d_factors), C.c_void_p(d_loglik),
+                                            C.c_void_p(d_descent) if d_descent else None, C.c_void_p(d_n_contrib),
+                                            flags | OUT_DEVICE), "cnf2_sweep_descent")
+
     # -- pair posteriors ---------------------------------------------------------
     def linked_pairs(self, sel):
         """cnf2_linked_pairs: pairs[n_pairs][2] (int32), the pairs j < k of indices into sel whose markers share a
@@ -843,6 +880,48 @@ class Context:
                                            dp("n_used"), dp("n_cells"), dp("perm_max"), QTL_ORIGIN_DEVICE | OUT_DEVICE),
                   "cnf2_qtl_scan_fam")
         return None
+
+    # -- founder-haplotype scan ---------------------------------------------------
+    QTLHAP_KEYS = ("lod", "df", "coef", "rss0", "n_used", "perm_max")
+
+    def _qtlhap_call(self, n, descent_ptr, col, H, pheno, cov, use, perm, coef, flags, d_out=None):
+        """cnf2_qtl_scan_hap on the rows behind descent_ptr, with new host outputs or (d_out) device pointers"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        col = np.ascontiguousarray(col, np.int32)
+        if col.shape != (n, 8):
+            raise ValueError("col must be [n][8]")
+        M, Cn, H = self.n_markers, self.n_chrom, int(H)
+        opt = lambda a: None if a is None else _p(a)
+        if d_out is not None:
+            dp = lambda k: C.c_void_p(d_out[k]) if d_out.get(k) else None
+            self._chk(self.L.cnf2_qtl_scan_hap(self.h, n, descent_ptr, _p(col), H, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm),
+                                               dp("lod"), dp("df"), dp("coef"), dp("rss0"), dp("n_used"), dp("perm_max"),
+                                               flags | OUT_DEVICE), "cnf2_qtl_scan_hap")
+            return None
+        o = dict(lod=np.zeros((T, M)), df=np.zeros(M, np.int32), coef=np.zeros((T, M, max(H, 0))) if coef else None,
+                 rss0=np.zeros((T, Cn)), n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn)) if P else None)
+        self._chk(self.L.cnf2_qtl_scan_hap(self.h, n, descent_ptr, _p(col), H, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm),
+                                           _p(o["lod"]), _p(o["df"]), opt(o["coef"]), _p(o["rss0"]), _p(o["n_used"]),
+                                           opt(o["perm_max"]), flags), "cnf2_qtl_scan_hap")
+        return o
+
+    def qtl_scan_hap(self, descent, col, n_columns, pheno, cov=None, use=None, perm=None, coef=True):
+        """cnf2_qtl_scan_hap on host rows descent[n][M][8] (what sweep_descent returns): the regression of pheno[n][T] on the
+        expected dosage of the n_columns (1 .. 32) founder haplotypes that col[n][8] (origins.descent_columns) assigns the cells
+        of a row to.  A dict: lod[T][M], df[M] (the columns kept), coef[T][M][H] with coef (NaN for a dropped column), rss0[T][C],
+        n_used[C], perm_max[P][T][C] (None without permutations).  The model: include/cnf2hip.h; cnf2freq_amd/qtl.py (scan_hap,
+        hap_fstat) makes the columns and reads the results."""
+        descent = np.ascontiguousarray(descent, np.float64)
+        if descent.ndim != 3 or descent.shape[1:] != (self.n_markers, 8):
+            raise ValueError("descent must be [n][%d][8]" % self.n_markers)
+        return self._qtlhap_call(descent.shape[0], _p(descent), col, n_columns, pheno, cov, use, perm, coef, 0)
+
+    def qtl_scan_hap_device(self, n, d_descent, col, n_columns, pheno, cov=None, use=None, perm=None, coef=True, d_out=None):
+        """The same on device rows (d_descent: an int, the pointer of n x M x 8 doubles aligned to 16 bytes, e.g. the tensor a
+        sweep_descent_device call filled); they are read in place.  d_out: a dict of device pointers (ints) for QTLHAP_KEYS
+        (coef and perm_max None where not asked for) -- the outputs then stay on the GPU and None is returned."""
+        return self._qtlhap_call(n, C.c_void_p(d_descent), col, n_columns, pheno, cov, use, perm, coef, QTL_ORIGIN_DEVICE, d_out)
 
     # -- multiple-imputation scan ------------------------------------------------
     def set_qtlimp_columns(self, cap):

@@ -35,6 +35,7 @@
 #include "cnf2_qtlmv.h"
 #include "cnf2_qtlimp.h"
 #include "cnf2_qtlfam.h"
+#include "cnf2_qtlhap.h"
 
 using namespace cnf2;
 
@@ -193,6 +194,7 @@ struct cnf2_ctx {
     // origin rows (cnf2_sweep_origins): the rows a call did not hand device memory for, and its staged sums
     DevBuf<double>  d_org;                // [n][n_markers][4]
     DevBuf<double>  d_obits;              // [n][n_markers][6]
+    DevBuf<double>  d_descent;            // descent rows (cnf2_sweep_descent) a call did not hand device memory for: [n][n_markers][8]
     DevBuf<double>  d_org_sum;            // [n_markers][4]
 
     // pair rows (cnf2_sweep_pairs): the selection as the kernels read it (sel, the chromosomes' ranges in it, the pair
@@ -276,6 +278,13 @@ struct cnf2_ctx {
     DevBuf<double>  d_qf_Z, d_qf_Y, d_qf_chrom, d_qf_rec, d_qf_hrec, d_qf_null, d_qf_tilemax, d_qf_gamma;
     DevBuf<double>  d_qf_lod, d_qf_slope, d_qf_rss0, d_qf_pmax;
     DevBuf<int32_t> d_qf_map, d_qf_nc, d_qf_ncells, d_qf_df;   // d_qf_map: as d_q_map, then the gather list (cnf2_qtlfam.h)
+
+    // founder-haplotype scan (cnf2_qtl_scan_hap): the marker records (packed factor and G), the kept masks, the null fits, the
+    // tile maxima, staged outputs; host descent rows are staged in d_descent; the staged inputs, the masks, the Cholesky
+    // factors and the column image are the single scan's buffers
+    DevBuf<double>   d_qh_rec, d_qh_null, d_qh_tilemax, d_qh_lod, d_qh_coef, d_qh_rss0, d_qh_pmax;
+    DevBuf<uint32_t> d_qh_kept;
+    DevBuf<int32_t>  d_qh_map, d_qh_nc, d_qh_df;   // d_qh_map: as d_q_map on tiles of two markers, then col and the gather list (cnf2_qtlhap.h)
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -837,16 +846,16 @@ static JobPlan job_plan(const cnf2_ctx* ctx, int ind_begin, int n, uint32_t flag
 
 // What a sweep leaves besides the likelihoods: its mode with that mode's device outputs
 struct SweepMode {
-    SweepVariant variant = SW_PLAIN;   // SW_PLAIN (cnf2_sweep: the rows), SW_CROSSOVERS, SW_VITERBI, SW_SAMPLING, SW_LOO or SW_ORIGINS
+    SweepVariant variant = SW_PLAIN;   // SW_PLAIN (cnf2_sweep: the rows), SW_CROSSOVERS, SW_VITERBI, SW_SAMPLING, SW_LOO, SW_ORIGINS or SW_DESCENT
     // SW_CROSSOVERS (cnf2_sweep_crossovers)
     double*  xo = nullptr;             // [n][n_markers][6] or null
     double*  xo_sum = nullptr;         // [n_markers][6], zeroed by the caller
-    int32_t* xo_cnt = nullptr;         // [n_chrom], zeroed by the caller (SW_LOO and SW_ORIGINS too)
+    int32_t* xo_cnt = nullptr;         // [n_chrom], zeroed by the caller (SW_LOO, SW_ORIGINS and SW_DESCENT too)
     // SW_LOO (cnf2_sweep_loo): what the sweep leaves for loo_finish_kernel
     double*  loo = nullptr;            // [n][n_markers]
     double*  unl = nullptr;            // [n][n_markers]
     // SW_ORIGINS (cnf2_sweep_origins)
-    double*  org = nullptr;            // [n][n_markers][4]
+    double*  org = nullptr;            // [n][n_markers][4]; SW_DESCENT (cnf2_sweep_descent): [n][n_markers][8]
     double*  obits = nullptr;          // [n][n_markers][6]
     // SW_VITERBI (cnf2_sweep_viterbi) and, with a leading [K] of draws per individual, SW_SAMPLING (cnf2_sweep_sample)
     uint8_t* state = nullptr;          // [n][n_markers]
@@ -953,8 +962,8 @@ static int prepare_lines(cnf2_ctx* ctx, int ind_begin, int n, int cap, int* n_li
 // forms them) and then the general kernel's crossover instantiation (their posteriors).  Viterbi mode: the same routing,
 // with the fast kernel's Viterbi instantiation in place of both crossover instantiations.  Sampling mode: the untied windows
 // through the fast kernel's sampling instantiation (one pass: likelihoods and draws), the tied ones through the tied kernel
-// without rows (likelihoods) and then the same sampling instantiation (draws).  Leave-one-out and origin mode: sampling's
-// routing with the fast kernel's leave-one-out / origin instantiation
+// without rows (likelihoods) and then the same sampling instantiation (draws).  Leave-one-out, origin and descent mode:
+// sampling's routing with the fast kernel's leave-one-out / origin / descent instantiation
 static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* dosage_out,
                       uint32_t flags, const SweepMode& mode)
 {
@@ -1172,6 +1181,12 @@ static int sweep_impl(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors
         p.flags  = KP_NO_DOSAGE;    // (no rows; the instantiation makes its backward pass all the same)
         p.org    = mode.org;
         p.obits  = mode.obits;
+        p.xo_cnt = mode.xo_cnt;
+        follow_per_cu = ctx->fast_blocks_per_cu;
+        break;
+    case SW_DESCENT:
+        p.flags  = KP_NO_DOSAGE;    // (no rows; the instantiation makes its backward pass all the same)
+        p.org    = mode.org;
         p.xo_cnt = mode.xo_cnt;
         follow_per_cu = ctx->fast_blocks_per_cu;
         break;
@@ -1638,6 +1653,40 @@ int cnf2_sweep_origins(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factor
     return CNF2_OK;
 }
 
+int cnf2_descent_rows(cnf2_ctx* ctx, int ind, int chrom, double* rows_out)
+{
+    if (!ctx || !rows_out) return fail(ctx, CNF2_ERR_ARG, "bad descent_rows arguments");
+    return stage2_rows(ctx, ind, chrom, 8, rows_out,
+                       [&](const Stage2Params& q, double* d_out) { launch_descent_rows(q, d_out, ctx->stream); });
+}
+
+// one pass of sweep_impl's descent mode.  The rows the caller gave no device memory for live in the context's own buffer
+// (not the origin rows': a scan's kept rows stay what they are)
+int cnf2_sweep_descent(cnf2_ctx* ctx, int ind_begin, int ind_end, double* factors_out, double* loglik_out, double* descent_out,
+                       int32_t* n_contrib_out, uint32_t flags)
+{
+    RC_TRY(ready(ctx));
+    if (!factors_out || !loglik_out || !n_contrib_out) return fail(ctx, CNF2_ERR_ARG, "only descent_out may be NULL");
+    RC_TRY(mode_range(ctx, ind_begin, ind_end));
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    n = ind_end - ind_begin;
+    const size_t M = ctx->n_markers, C = ctx->n_chrom, nr = (size_t)n * M;
+    SweepMode    m;
+    m.variant = SW_DESCENT;
+    RC_TRY(stage_out(ctx, dev, n_contrib_out, ctx->d_xo_cnt, C, &m.xo_cnt));
+    m.org = (dev && descent_out) ? descent_out : nullptr;
+    if (!m.org && nr > 0) {
+        RC_TRY(ctx->d_descent.ensure(ctx, nr * 8));
+        m.org = ctx->d_descent;
+    }
+    RC_TRY(mode_sweep(ctx, ind_begin, ind_end, factors_out, loglik_out, flags & ~(uint32_t)CNF2_ALL_STATES, m));
+    if (dev) return CNF2_OK;
+    RC_TRY(fetch_out(ctx, n_contrib_out, m.xo_cnt, C));
+    if (descent_out) RC_TRY(fetch_out(ctx, descent_out, m.org, nr * 8));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CNF2_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // QTL scans (cnf2_qtl.h, cnf2_qtlplan.h, cnf2_qtl_kernels.hip and the scans' own headers and kernels).  Every entry point
 // takes the same steps in the same order: the argument checks; the plan (marker map and column tile, cnf2_qtlplan.h); every
@@ -2043,6 +2092,112 @@ int cnf2_qtl_scan_fam(cnf2_ctx* ctx, int n, const double* origin, int side, cons
         if (r0 + q.rn > (size_t)T) launch_qtlfam_finish(q, ctx->stream);
     }
     if (q.slope) launch_qtlfam_slope(q, ctx->stream);
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Founder-haplotype scan (cnf2_qtlhap.h, cnf2_qtlhap_kernels.hip), in the scans' order of steps.  The individuals it uses are
+// those of `use` with all eight columns in [0, H): that mask is what the checks, the centring and the kernels see.
+// ------------------------------------------------------------------------------------------------
+int cnf2_qtl_scan_hap(cnf2_ctx* ctx, int n, const double* descent, const int32_t* col, int n_columns, int n_traits,
+                      const double* pheno, const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm,
+                      double* lod_out, int32_t* df_out, double* coef_out, double* rss0_out, int32_t* n_used_out,
+                      double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
+    if (n < 1 || n_traits < 1 || !pheno) return fail(ctx, CNF2_ERR_ARG, "n and n_traits must be at least 1 and pheno not NULL");
+    if (!descent || !col) return fail(ctx, CNF2_ERR_ARG, "descent and col must not be NULL");
+    if (n_columns < 1 || n_columns > QTLHAP_MAXH) return fail(ctx, CNF2_ERR_ARG, "n_columns must be 1 .. %d", QTLHAP_MAXH);
+    if (n_cov < 0 || n_cov > QTL_MAXK || (n_cov > 0 && !cov)) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d, with cov", QTL_MAXK);
+    if (n_perm < 0 || (n_perm > 0) != (perm != nullptr) || (n_perm > 0) != (perm_max_out != nullptr))
+        return fail(ctx, CNF2_ERR_ARG, "perm and perm_max_out must be NULL exactly when n_perm is 0");
+    if (!lod_out || !df_out || !rss0_out || !n_used_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if ((size_t)n_traits * ((size_t)n_perm + 1) > (size_t)1 << 30) return fail(ctx, CNF2_ERR_ARG, "too many columns");
+    const bool rows_dev = (flags & CNF2_QTL_ORIGIN_DEVICE) != 0;
+    if (rows_dev && ((uintptr_t)descent & 15)) return fail(ctx, CNF2_ERR_ARG, "device descent rows must be aligned to 16 bytes");
+    std::vector<uint8_t> inmodel(n);
+    const int            bad = qtlhap_mask(n, use, col, n_columns, inmodel.data());
+    if (bad >= 0) return fail(ctx, CNF2_ERR_ARG, "a column of individual %d is not in -1 .. %d", bad, n_columns - 1);
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, inmodel.data(), cov, perm, lod_out, nullptr, rss0_out, perm_max_out, df_out, n_used_out};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_check_values(ctx, a, &mask));
+    RC_TRY(qtl_check_perm(ctx, n, n_perm, perm, mask.data()));
+    QtlHapLayout lay;
+    qtlhap_layout(n, mask.data(), col, &lay);
+    QtlCentred centred;
+    qtl_centre(a, mask, centred);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    M = ctx->n_markers, C = ctx->n_chrom, K = n_cov, T = n_traits, H = n_columns, nx = K + 1;
+    const size_t R = (size_t)T * ((size_t)n_perm + 1);
+    const size_t rt = qtl_column_tile(n, R, n_perm, 0, ctx->qtl_columns[QTL_CAP_SCAN]);
+    QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, 2, true, true);
+    // col and the gather list behind the marker map: gidx, steppat, stepend, patcol (a word each where they are empty)
+    std::vector<int32_t>& img = map.image;
+    auto append = [&](const int32_t* v, size_t count) {
+        const size_t o = img.size();
+        img.insert(img.end(), v, v + count);
+        if (count == 0) img.push_back(0);
+        return o;
+    };
+    const size_t o_col = append(col, (size_t)n * 8), o_gidx = append(lay.gidx.data(), lay.gidx.size());
+    const size_t o_steppat = append(lay.steppat.data(), lay.steppat.size()), o_stepend = append(lay.stepend.data(), lay.stepend.size());
+    const size_t o_patcol = append(lay.patcol.data(), lay.patcol.size());
+
+    const size_t n_rows = (size_t)n * M * 8;
+    if (!rows_dev) RC_TRY(ctx->d_descent.ensure(ctx, n_rows));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
+    QtlHapParams p;
+    memset(&p, 0, sizeof(p));
+    QtlParams& q = p.q;
+    q = qtl_gather_params(ctx, a, rt);
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(n_used_out, ctx->d_qh_nc, (size_t)C, &q.nc));
+        RC_TRY(each(df_out, ctx->d_qh_df, (size_t)M, &p.df));
+        RC_TRY(each(lod_out, ctx->d_qh_lod, (size_t)T * M, &q.lod));
+        RC_TRY(each(coef_out, ctx->d_qh_coef, (size_t)T * M * H, &p.coef));
+        RC_TRY(each(rss0_out, ctx->d_qh_rss0, (size_t)T * C, &q.rss0));
+        return each(perm_max_out, ctx->d_qh_pmax, (size_t)n_perm * T * C, &q.pmax);
+    };
+    RC_TRY(ctx->d_qh_map.ensure(ctx, img.size()));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_qh_rec.ensure(ctx, (size_t)M * qtlhap_rec_size(H, nx)));
+    RC_TRY(ctx->d_qh_kept.ensure(ctx, (size_t)M));
+    RC_TRY(ctx->d_qh_null.ensure(ctx, (size_t)C * (nx + 1) * rt));
+    if (n_perm > 0) RC_TRY(ctx->d_qh_tilemax.ensure(ctx, map.n_tiles * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    if (!rows_dev) {
+        // (complete on return: the caller's array is not read after the call)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_descent.ptr, descent, n_rows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    RC_TRY(qtl_upload(ctx, ctx->d_qh_map, img.data(), img.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    q.M = M, q.C = C, q.P = n_perm, q.K = K, q.nx = nx;
+    q.cov = ctx->d_q_cov;
+    q.cs = ctx->d_qh_map, q.mchrom = ctx->d_qh_map + map.o_mchrom;
+    q.tiles = ctx->d_qh_map + map.o_tiles, q.tile_start = ctx->d_qh_map + map.o_tstart, q.n_tiles = (int)map.n_tiles;
+    q.cmask = ctx->d_q_cmask, q.chol = ctx->d_q_chol, q.nullq = ctx->d_qh_null, q.tilemax = ctx->d_qh_tilemax;
+    p.H = H, p.S = lay.S;
+    p.descent = rows_dev ? descent : ctx->d_descent.ptr;
+    p.col = ctx->d_qh_map + o_col, p.gidx = ctx->d_qh_map + o_gidx, p.steppat = ctx->d_qh_map + o_steppat;
+    p.stepend = ctx->d_qh_map + o_stepend, p.patcol = ctx->d_qh_map + o_patcol;
+    p.rec = ctx->d_qh_rec, p.kept = ctx->d_qh_kept;
+
+    launch_qtlhap_chrom(p, ctx->stream);
+    launch_qtlhap_design(p, ctx->stream);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = (int)r0;
+        q.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(q, ctx->stream);
+        launch_qtl_null(q, ctx->stream);
+        launch_qtlhap_scan(p, ctx->stream);
+        if (r0 + q.rn > (size_t)T) launch_qtl_finish(q, ctx->stream);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return qtl_fetch_outputs(ctx, dev, outputs);
 }

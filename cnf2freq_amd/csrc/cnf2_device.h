@@ -42,7 +42,10 @@ enum SweepVariant : int {
     SW_ORIGINS      = 9,   // origin mode: per marker the four grandparental-origin probabilities (p.org) and P(bit t = 1) of the
                            // six meiosis bits (p.obits), masked sums of the state posterior over the modes the rows count; the
                            // jobs with a likelihood counted in p.xo_cnt; no rows
-    SW_PLAIN_UNIFORM_ROWS = 10  // fb_fast_kernel's UNI instantiation only: SW_PLAIN for the uniform windows without line records
+    SW_PLAIN_UNIFORM_ROWS = 10, // fb_fast_kernel's UNI instantiation only: SW_PLAIN for the uniform windows without line records
+    SW_DESCENT      = 11   // descent mode: per marker the eight descent classes, four per side -- which grandparent and which of
+                           // its strands an allele descends from -- as masked sums of the same posterior (p.org, eight to a
+                           // row); the jobs with a likelihood counted in p.xo_cnt; no rows
 };
 
 struct KernelParams {
@@ -108,6 +111,7 @@ struct KernelParams {
     double*        unl;        // leave-one-out mode: [n_ind][n_markers] mean over the analysed modes of (1/64) sum_g e_s,m(g),
                                // likewise (-1: skipped); minus its logarithm after loo_finish_kernel
     double*        org;        // origin mode: [n_ind][n_markers][4] P(bit 0 + 2 bit 3 = k), each row summing to 1 (0: skipped)
+                               // descent mode: [n_ind][n_markers][8], the first side's four classes, then the second side's
     double*        obits;      // origin mode: [n_ind][n_markers][6] P(bit t = 1) (0: skipped)
     // fast kernel's UNI instantiation: the launch's line records (cnf2_emtab.h; [lines][n_markers][LINE_VALUES][2], built by
     // line_records_kernel in front of the launch) and the two lines of every window [n_ind][2] (offset like windows), -1 -1 for a
@@ -273,6 +277,8 @@ void launch_loo_rows(const Stage2Params& q, double* out, hipStream_t stream);
 void launch_loo_finish(double* loo, double* unl, int n_ind, int n_markers, double* loo_sum, double* unl_sum, hipStream_t stream);
 // out[len][10] = origin[4], bits[6] of cnf2_sweep_origins from the store, brute force
 void launch_origin_rows(const Stage2Params& q, double* out, hipStream_t stream);
+// out[len][8] = the descent row of cnf2_sweep_descent from the store, brute force
+void launch_descent_rows(const Stage2Params& q, double* out, hipStream_t stream);
 // out[S (S - 1) / 2][16] = the pair rows of cnf2_sweep_pairs for the S selected markers of the chromosome (sel: local indices,
 // ascending, device memory) from the store, brute force
 void launch_pair_rows(const Stage2Params& q, const int32_t* sel, int S, double* out, hipStream_t stream);

@@ -1418,7 +1418,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
     constexpr int  NR   = UNI ? CNF2_UNI_REGS : 8;      // registers per lane and vector
     constexpr bool PAIR = HALF && STOREW == SW_PLAIN && !XPOSE && !TIED && !UNI;    // the instantiation UNI may run beside
     static_assert(!XPOSE || (HALF && STOREW == SW_PLAIN), "the transposing variant exists for the plain half-spill sweep");
-    // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_ORIGINS); by value:
+    // STOREW is a SweepVariant (cnf2_device.h: SW_PLAIN .. SW_DESCENT); by value:
     // STOREW: 0 plain sweep; 1 accumulate mode (also stores the posterior weights wg); 2 turn-scan mode (stores alpha e, beta
     // and their scales; no rows); 3 accumulate mode of a call that did not ask for the per-locus rows (wg only); 4 crossover
     // mode (posterior probability of a flip of every state bit across every gap into p.xo / p.xo_sum / p.xo_cnt; no rows);
@@ -1431,7 +1431,8 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
     // mean into p.loo / p.unl, their logarithms left to loo_finish_kernel; counts the jobs with a likelihood in p.xo_cnt; no rows);
     // 9 origin mode (per marker eight masked sums of the state posterior gamma = wg e over the modes the rows count, normalised
     // by their total: the four origin cells into p.org, P(bit t = 1) into p.obits; counts the jobs with a likelihood in
-    // p.xo_cnt; no rows)
+    // p.xo_cnt; no rows); 11 descent mode (the origin mode's posterior and normaliser; per marker the eight descent classes,
+    // four per side, eight to a row of p.org; counts the jobs with a likelihood in p.xo_cnt; no rows)
     constexpr bool ROWS = STOREW == SW_PLAIN || STOREW == SW_WEIGHTS_ROWS;      // class sums, restricted tables, tile epilogue, p.dosage
     constexpr bool WG   = STOREW == SW_WEIGHTS_ROWS || STOREW == SW_WEIGHTS;
     constexpr bool VIT  = STOREW == SW_VITERBI;
@@ -1439,7 +1440,9 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
     constexpr bool POST = STOREW == SW_POSTERIOR;
     constexpr bool LOO  = STOREW == SW_LOO;
     constexpr bool ORG  = STOREW == SW_ORIGINS;
+    constexpr bool DSC  = STOREW == SW_DESCENT;
     static_assert(!ORG || (!XPOSE && !TIED), "the origin mode is an instantiation of the untied DPP kernel");
+    static_assert(!DSC || (!XPOSE && !TIED), "the descent mode is an instantiation of the untied DPP kernel");
     static_assert(!LOO || (!XPOSE && !TIED), "the leave-one-out mode is an instantiation of the untied DPP kernel");
     static_assert(!POST || (!XPOSE && !TIED), "the placement mode is an instantiation of the untied DPP kernel");
     static_assert(!VIT || (!XPOSE && !TIED), "the Viterbi mode is an instantiation of the untied DPP kernel");
@@ -1706,7 +1709,7 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
                 p.lexp[e]   = any_alive ? emax : CNF2_LEXP_DEAD;
             }
         }
-        if ((STOREW == 4 || POST || LOO || ORG) && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
+        if ((STOREW == 4 || POST || LOO || ORG || DSC) && lane == 0 && any_alive) atomicAdd(&p.xo_cnt[jb.chrom], 1);
         if (VIT) {
             // ------------------------------------------------------------ Viterbi: logmax, MAP mode, backtrace
             // logmax_s = log(max-product) + the chromosome's dropped butterfly constants, as likelihood_logs_kernel finishes
@@ -1911,9 +1914,16 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
             }
             continue;
         }
-        // (the leave-one-out and origin modes form no rows and are launched for their backward pass: they run with
+        // (the leave-one-out, origin and descent modes form no rows and are launched for their backward pass: they run with
         // KP_NO_DOSAGE, as the general kernel's crossover instantiation does)
-        if (!LOO && !ORG && (p.flags & KP_NO_DOSAGE)) continue;
+        if (!LOO && !ORG && !DSC && (p.flags & KP_NO_DOSAGE)) continue;
+        if (DSC && !any_alive) {
+            // skipped, as the sweep skips it: all-zero rows, as the origin mode leaves them
+            double* dr = p.org + ((size_t)jb.ind * p.n_markers + first) * 8;
+            const int len = last - first + 1;
+            for (int k = lane; k < len * 8; k += 64) dr[k] = 0.0;
+            continue;
+        }
         if (ORG && !any_alive) {
             // skipped, as the sweep skips it: all-zero rows, as the dosage rows are (origin_finish_kernel adds them as they are)
             double* og = p.org + ((size_t)jb.ind * p.n_markers + first) * 4;
@@ -2260,6 +2270,44 @@ __global__ __launch_bounds__(CNF2_BLOCK, UNI && CNF2_UNI_REGS == 2 ? CNF2_UNI_MI
                     ob[4] = t4 * inv;
                     ob[5] = t5 * inv;
                 }
+            }
+            if constexpr (DSC) {
+                // descent mode: the origin mode's gamma(s, g) = wg e and its normaliser.  Per side a class k = 2 w + b: the
+                // allele descends from that parent's par[.][w], strand b of that grandparent.  w is the parent's own meiosis
+                // bit (0 or 3) and b the meiosis bit of the grandparent it selected (1 or 2 on the first side, 4 or 5 on the
+                // second).  The register index j is state bits 3-5: a lane's four sums over its registers are the second
+                // side's classes; its own state bits 0-2 (c.lo, not the raw lane number) select the one first-side class all
+                // eight registers belong to.  The eight values are reduced together by halving: lane bit 0 keeps the odd or
+                // the even ones and sends the others to its neighbour, then bit 1, then bit 2 (4 + 2 + 1 exchanges), which
+                // leaves lane l of a chain with value l & 7 added over the chain's lanes; three more exchanges add the chains.
+                // Lanes 0-7 then hold the row and store it, one value each
+                double s2[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const double g = scale != 0.0 ? scale * wj[j] * e[j] : 0.0;    // (a chain that is off: 0, whatever it holds)
+                    s2[(j & 1) ? 2 + ((j >> 2) & 1) : ((j >> 1) & 1)] += g;
+                }
+                const double gs = (s2[0] + s2[1]) + (s2[2] + s2[3]);
+                const int    k1 = (c.lo & 1) ? 2 + ((c.lo >> 2) & 1) : ((c.lo >> 1) & 1);
+                auto halve = [&](double a, double b, bool bit, int which) CNF2_LI_K {
+                    const double keep = bit ? b : a, send = bit ? a : b;
+                    return keep + (which == 0 ? lane_xor1(send) : (which == 1 ? lane_xor2(send) : lane_xor4(send)));
+                };
+                double h4[4], h2[2];
+                h4[0] = halve(k1 == 0 ? gs : 0.0, k1 == 1 ? gs : 0.0, (lane & 1) != 0, 0);
+                h4[1] = halve(k1 == 2 ? gs : 0.0, k1 == 3 ? gs : 0.0, (lane & 1) != 0, 0);
+                h4[2] = halve(s2[0], s2[1], (lane & 1) != 0, 0);
+                h4[3] = halve(s2[2], s2[3], (lane & 1) != 0, 0);
+                h2[0] = halve(h4[0], h4[1], (lane & 2) != 0, 1);
+                h2[1] = halve(h4[2], h4[3], (lane & 2) != 0, 1);
+                const double dv = across_chains_sum(halve(h2[0], h2[1], (lane & 4) != 0, 2));
+                // the normaliser is the origin mode's, the total of the first side's four cells: lanes 0-3 of a group of
+                // eight add theirs, lanes 4-7 take it from lanes 3-0 (row_half_mirror)
+                double tot = dv + lane_xor1(dv);
+                tot += lane_xor2(tot);
+                const double tmir = dpp_mov_all<0x141>(tot);
+                if (lane & 4) tot = tmir;
+                if (lane < 8) p.org[((size_t)jb.ind * p.n_markers + m) * 8 + lane] = tot > 0.0 ? dv * (1.0 / tot) : 0.0;
             }
             if constexpr (POST) {
                 // placement mode: gamma(s, g) = wg e, the posterior of state g in mode s at this marker, where the accumulate
@@ -4206,6 +4254,37 @@ __global__ __launch_bounds__(64) void origin_rows_kernel(Stage2Params q, double*
         for (int k = 0; k < 10; k++) out[(size_t)ml * 10 + k] = r[k];
 }
 
+// The descent rows from the store, brute force (the cross-check of the sweep's descent mode): origin_rows_kernel's gamma(g) and
+// normaliser, then the eight masked sums: first side k = 2 bit0 + (bit0 ? bit2 : bit1), second side k = 2 bit3 + (bit3 ? bit5 :
+// bit4) of the state g.  out[len][8]; zeros where no mode has a likelihood.
+__global__ __launch_bounds__(64) void descent_rows_kernel(Stage2Params q, double* out)
+{
+    const int    g  = threadIdx.x;
+    const int    ml = blockIdx.x;
+    const Window w  = q.kp.windows[0];
+    const double factor = q.loglik[0];
+    double acc = 0.0, wsum = 0.0;
+    for (int s = 0; s < 8; s++) {
+        if ((s & w.shiftignore) || s >= w.shiftend) continue;
+        const double fs = q.factors[s];
+        if (!(fs > (double)CNF2_MINFACTOR_F) || factor - fs > 40.0) continue;
+        const double gam = s2_fw(q, s, ml, 2, g) * s2_fw(q, s, ml, 1, g);
+        const double own = across_chains_sum(chain_sum(gam));
+        if (!(own > 0.0)) continue;
+        const double ws = exp(fs - factor);
+        acc += ws * (gam / own);
+        wsum += ws;
+    }
+    const bool   skip = !(wsum > 0.0) || isnan(factor);
+    const double ga = skip ? 0.0 : acc / wsum;
+    const int    k1 = (g & 1) ? 2 + ((g >> 2) & 1) : ((g >> 1) & 1);
+    const int    k2 = (g & 8) ? 2 + ((g >> 5) & 1) : ((g >> 4) & 1);
+    for (int k = 0; k < 8; k++) {
+        const double r = across_chains_sum(chain_sum((k < 4 ? k1 == k : k2 == k - 4) ? ga : 0.0));
+        if (g == 0) out[(size_t)ml * 8 + k] = r;
+    }
+}
+
 
 // HAPLOS accumulators of HOT LOOP 2 (cnF2freq.cpp:5554-5556 -> updatehaplo 1561-1575 -> trackpossible<HAPLOS>
 // 1347-1350), per marker and window slot: out[len][7][2], out[..][k][phase] = sum of val over states,
@@ -5880,7 +5959,7 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     if (n_pack > 0) po.clock_out = nullptr;
     if (n_uni > 0) po.flags |= KP_SKIP_UNIFORM;
     zero_job_counter(po, stream);
-    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the twenty instantiations there are (and UNI above)
+    switch (fast_key(v.storew, v.half, v.xpose, v.tied)) {       // the twenty-two instantiations there are (and UNI above)
     case fast_key(SW_PLAIN, true): launch_fast_as<true, SW_PLAIN>(po, grid, stream); break;
     case fast_key(SW_PLAIN, false): launch_fast_as<false, SW_PLAIN>(p, grid, stream); break;
     case fast_key(SW_PLAIN, true, true): launch_fast_as<true, SW_PLAIN, true>(p, grid, stream); break;
@@ -5901,6 +5980,8 @@ hipError_t launch_fb_fast(const KernelParams& p, int grid, FastVariant v, hipStr
     case fast_key(SW_LOO, false): launch_fast_as<false, SW_LOO>(p, grid, stream); break;
     case fast_key(SW_ORIGINS, true): launch_fast_as<true, SW_ORIGINS>(p, grid, stream); break;
     case fast_key(SW_ORIGINS, false): launch_fast_as<false, SW_ORIGINS>(p, grid, stream); break;
+    case fast_key(SW_DESCENT, true): launch_fast_as<true, SW_DESCENT>(p, grid, stream); break;
+    case fast_key(SW_DESCENT, false): launch_fast_as<false, SW_DESCENT>(p, grid, stream); break;
     default: return hipErrorInvalidValue;
     }
     launch_likelihood_logs(p, stream);
@@ -6514,6 +6595,10 @@ void launch_loo_rows(const Stage2Params& q, double* out, hipStream_t stream)
 void launch_origin_rows(const Stage2Params& q, double* out, hipStream_t stream)
 {
     hipLaunchKernelGGL(origin_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
+}
+void launch_descent_rows(const Stage2Params& q, double* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(descent_rows_kernel, dim3(q.len), dim3(64), 0, stream, q, out);
 }
 
 void launch_emission(const KernelParams& p, int ind, int marker, double* out, hipStream_t stream)

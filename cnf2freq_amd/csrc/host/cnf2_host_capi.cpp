@@ -19,6 +19,7 @@
 #include "../cnf2_qtlimp.h"
 #include "../cnf2_qtlmv.h"
 #include "../cnf2_qtlfam.h"
+#include "../cnf2_qtlhap.h"
 #include "../cnf2_qtlplan.h"
 #include "cnf2_remap.h"
 
@@ -696,6 +697,33 @@ int cnf2h_qtl_families(int n_rec, const int32_t* par, int n, const int32_t* dous
     for (int i = 0; i < n; i++)
         if (dous[i] < 0 || dous[i] >= n_rec) return -2;
     *n_fam_out = cnf2host::qtl_families(par, n, dous, side, grp_out, cell_out);
+    return 0;
+}
+
+// one marker of cnf2_qtl_scan_hap: qtlhap_marker_serial (cnf2_qtlhap.h)
+int cnf2h_qtlhap_marker(int n, const double* descent, const int32_t* col, int n_columns, int n_traits, const double* y, int n_cov,
+                        const double* cov, const uint8_t* c, double* lod_out, int32_t* df_out, double* coef_out, double* rss0_out,
+                        int32_t* n_used_out)
+{
+    if (n < 1 || !descent || !col || n_traits < 1 || !y || n_cov < 0 || n_cov > cnf2::QTL_MAXK || (n_cov > 0 && !cov) || !c || !lod_out ||
+        !df_out || !rss0_out || !n_used_out)
+        return -2;
+    return cnf2::qtlhap_marker_serial(n, descent, col, n_columns, n_traits, y, n_cov, cov, c, lod_out, df_out, coef_out, rss0_out,
+                                      n_used_out)
+               ? 0
+               : -2;
+}
+
+// col[n][8] of the descent rows from the pedigree's parents: descent_columns (cnf2_qtl_host.h)
+int cnf2h_descent_columns(int n_rec, const int32_t* par, int n, const int32_t* dous, int by, int32_t* col_out, int32_t* n_grand_out)
+{
+    if (n_rec < 1 || !par || n < 1 || !dous || by < 0 || by > 2 || !col_out || !n_grand_out) return -2;
+    for (int r = 0; r < n_rec; r++)
+        for (int s = 0; s < 2; s++)
+            if (par[2 * r + s] >= n_rec) return -2;
+    for (int i = 0; i < n; i++)
+        if (dous[i] < 0 || dous[i] >= n_rec) return -2;
+    *n_grand_out = cnf2host::descent_columns(par, n, dous, by, col_out);
     return 0;
 }
 

@@ -134,6 +134,36 @@ inline int qtl_families(const int32_t* par, int n, const int32_t* dous, int side
     return (int)parents.size();
 }
 
+// col[n][8] of the analysed records dous[n] for the founder-haplotype scan (cnf2_qtl_scan_hap; origins.descent_columns): cell
+// 4 s + 2 w + b of a descent row belongs to grandparent par[par[dous[i]][s]][w], strand b.  The distinct grandparents are
+// numbered g from 0 in ascending order of the records.  by 0 "haplotype": column 2 g + b; 1 "founder": column g; 2 "line":
+// column w.  A side whose parent is missing or has no two recorded parents gets -1 in its four cells.  Returns the
+// grandparents counted.
+inline int descent_columns(const int32_t* par, int n, const int32_t* dous, int by, int32_t* col)
+{
+    std::vector<int32_t> grand;
+    auto gp = [&](int i, int s, int w) -> int32_t {
+        const int32_t p = par[2 * dous[i] + s];
+        if (p < 0 || par[2 * p] < 0 || par[2 * p + 1] < 0) return -1;
+        return par[2 * p + w];
+    };
+    for (int i = 0; i < n; i++)
+        for (int s = 0; s < 2; s++)
+            for (int w = 0; w < 2; w++)
+                if (gp(i, s, w) >= 0) grand.push_back(gp(i, s, w));
+    std::sort(grand.begin(), grand.end());
+    grand.erase(std::unique(grand.begin(), grand.end()), grand.end());
+    for (int i = 0; i < n; i++)
+        for (int s = 0; s < 2; s++)
+            for (int w = 0; w < 2; w++) {
+                const int32_t r = gp(i, s, w);
+                const int32_t g = r < 0 ? -1 : (int32_t)(std::lower_bound(grand.begin(), grand.end(), r) - grand.begin());
+                for (int b = 0; b < 2; b++)
+                    col[8 * i + 4 * s + 2 * w + b] = r < 0 ? -1 : by == 0 ? 2 * g + b : by == 1 ? g : w;
+            }
+    return (int)grand.size();
+}
+
 // res[n][T]: the residuals of every phenotype column on a mean per cell[n] and cov over the used individuals, 0 for the
 // others (qtl.cell_residuals): every column minus its mean over the used members of the cell, then qtl_null_residuals, whose
 // intercept finds nothing left.  false when the centred covariates have no Cholesky factor.

@@ -2,7 +2,7 @@
 // (demo.sh:37):
 //   cnF2freq --mapfile F --pedfile F --genfile F --output F --count N [--limit n] [--capmarker n] [--tmppath d]
 //            [--deserialize F] [--gpus N] [--crossovers F] [--viterbi F] [--sample F [--draws K] [--seed S]]
-//            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]] [--origins F]
+//            [--place F --place-genfile G --place-markers Q] [--loo F [--loo-threshold X]] [--origins F] [--descent F]
 //            [--qtl F --phenofile P [--qtl-covariates name,name] [--qtl-permutations K] [--qtl-seed S] [--qtl-additive]]
 //            [--qtl2 F [--qtl2-every S] [--qtl2-linked] --phenofile P [the --qtl-* options]]
 //            [--qtlx F --phenofile P [--qtl-imprint] [--qtl-interactive name,name] [the --qtl-* options]]
@@ -15,6 +15,7 @@
 //            [--qtlboot F --phenofile P --qtl-boot-chrom C [--qtl-boot-replicates B] [--qtl-covariates, --qtl-seed, --qtl-additive]]
 //            [--qtlmv F --phenofile P [--qtl-traits name,name,..] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
 //            [--qtlfam F --phenofile P [--qtl-fam-side first|second|both] [--qtl-cell parent|pair] [--qtl-covariates, --qtl-permutations, --qtl-seed]]
+//            [--qtlhap F --phenofile P [--qtl-hap-by haplotype|founder|line] [--qtl-covariates, --qtl-permutations, --qtl-seed]]
 //            [--qtlimp F --phenofile P [--qtl-imp-draws D] [--qtl-imp-seed S] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
@@ -66,6 +67,13 @@
 // a blank line the cells whose cost is at least X nats (default 5), "name<TAB>chrom<TAB>marker<TAB>pos<TAB>cost<TAB>unlinked"
 // with the marker's map index (from 0) and the cost of the same data with the marker off the map, by individual, then
 // marker.  --output is the same with or without it.  Single GPU only.
+//
+// --descent F (not a flag of the reference): after the last round, like --origins, the descent rows of the last round's state
+// (cnf2_sweep_descent): from which grandparent and which of its strands each allele descends.  Per chromosome and analysed
+// individual a header "name:chrom", then one line per marker of the eight probabilities ("%.6lf", tab separated: the first
+// parent's side, classes 2 w + b = 0..3 -- that parent's par[.][w], strand b as the grandparent's record labels it -- then
+// the second parent's side; eight "-" where the individual is skipped on the chromosome), then a blank line.  After the last
+// individual one line per chromosome, "chrom<TAB>contributors".  --output is the same with or without it.  Single GPU only.
 //
 // --origins F (not a flag of the reference): after the last round, and before a --remap changes the map, the grandparental
 // origin probabilities of the last round's state (cnf2_sweep_origins).  Per chromosome and analysed individual a header
@@ -184,6 +192,7 @@ struct Options {
     double      loo_threshold = 5.0;     // --loo-threshold X: cells at or above X nats are listed
     bool        loo_threshold_set = false;
     std::string origins;                 // --origins F: grandparental origin probabilities of the last round's state
+    std::string descent;                 // --descent F: descent rows (grandparent and strand) of the last round's state
     std::string qtl, phenofile;          // --qtl F --phenofile P: QTL scan of the last round's state
     std::string qtl_covariates;          // --qtl-covariates name,name
     int         qtl_permutations = 0;    // --qtl-permutations K
@@ -235,6 +244,9 @@ struct Options {
     bool        qtl_traits_set = false;
     std::vector<int> qtlmv_trait_cols;   // columns of pheno, in the order they are scanned
     std::string qtlfam;                  // --qtlfam F: within-family scan (with --phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed)
+    std::string qtlhap;                  // --qtlhap F: founder-haplotype scan (with --phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed)
+    std::string qtl_hap_by = "haplotype"; // --qtl-hap-by haplotype|founder|line: what a model column stands for
+    bool        qtlhap_extra_set = false;
     std::string qtl_fam_side = "both";   // --qtl-fam-side first|second|both
     std::string qtl_cell = "pair";       // --qtl-cell parent|pair: a mean per parent on the side, or per pair of parents
     bool        qtlfam_extra_set = false; // one of the two above was given
@@ -317,6 +329,7 @@ static bool parse(int argc, char** argv, Options& o)
             }
         }
         else if (a == "--origins") o.origins = val();
+        else if (a == "--descent") o.descent = val();
         else if (a == "--qtl") o.qtl = val();
         else if (a == "--qtl2") o.qtl2 = val();
         else if (a == "--qtlx") o.qtlx = val();
@@ -359,6 +372,11 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--qtlmv") o.qtlmv = val();
         else if (a == "--qtlimp") o.qtlimp = val();
         else if (a == "--qtlfam") o.qtlfam = val();
+        else if (a == "--qtlhap") o.qtlhap = val();
+        else if (a == "--qtl-hap-by") {
+            o.qtl_hap_by       = val();
+            o.qtlhap_extra_set = true;
+        }
         else if (a == "--qtl-fam-side") {
             o.qtl_fam_side     = val();
             o.qtlfam_extra_set = true;
@@ -482,6 +500,7 @@ static void sample_paths(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void place_markers(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void loo_costs(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void descent_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtl_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtl2_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlx_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
@@ -494,6 +513,7 @@ static void qtlboot_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool ro
 static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlimp_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtlfam_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
+static void qtlhap_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -584,6 +604,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.place.empty()) place_markers(opt, P, ctx);
     if (world == 1 && !opt.loo.empty()) loo_costs(opt, P, ctx);
     if (world == 1 && !opt.origins.empty()) origin_rows(opt, P, ctx);
+    if (world == 1 && !opt.descent.empty()) descent_rows(opt, P, ctx);
     if (world == 1 && !opt.qtl.empty()) qtl_scan(opt, P, ctx);
     if (world == 1 && !opt.qtl2.empty()) qtl2_scan(opt, P, ctx, !opt.qtl.empty());
     if (world == 1 && !opt.qtlx.empty()) qtlx_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty());
@@ -607,6 +628,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
     if (world == 1 && !opt.qtlfam.empty())
         qtlfam_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
                                      !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty());
+    if (world == 1 && !opt.qtlhap.empty()) qtlhap_scan(opt, P, ctx);
     if (world == 1 && !opt.qtlimp.empty()) qtlimp_scan(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
@@ -833,6 +855,35 @@ static void origin_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
             fprintf(out, "%d\t%.5lf\t%d\t%.5lf\t%.5lf\t%.5lf\t%.5lf\n", c + 1, P.pos[m], (int)cnt[c], os[(size_t)m * 4], os[(size_t)m * 4 + 1],
                     os[(size_t)m * 4 + 2], os[(size_t)m * 4 + 3]);
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.origins);
+}
+
+// --descent after the last round (single GPU), like --origins
+static void descent_rows(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    std::vector<double>  f((size_t)N * C * 8), ll((size_t)N * C), ds((size_t)N * M * 8);
+    std::vector<int32_t> cnt(C);
+    if (cnf2_sweep_descent(ctx, 0, N, f.data(), ll.data(), ds.data(), cnt.data(), 0) != CNF2_OK)
+        throw EngineError(CNF2_ERR_STATE, std::string("cnf2_sweep_descent: ") + cnf2_last_error(ctx));
+    FILE* out = fopen(opt.descent.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.descent);
+    for (int c = 0; c < C; c++)
+        for (int j = 0; j < N; j++) {
+            fprintf(out, "%s:%d\n", P.inds[P.dous[j]].name.c_str(), c + 1);
+            for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+                const double* r = &ds[((size_t)j * M + m) * 8];
+                // (a skipped individual's rows are all zero; every other row's sides sum to 1 each)
+                bool zero = true;
+                for (int k = 0; k < 8; k++) zero = zero && r[k] == 0.0;
+                for (int k = 0; k < 8; k++) {
+                    if (zero) fprintf(out, "-%c", k == 7 ? '\n' : '\t');
+                    else fprintf(out, "%.6lf%c", r[k], k == 7 ? '\n' : '\t');
+                }
+            }
+            fprintf(out, "\n");
+        }
+    for (int c = 0; c < C; c++) fprintf(out, "%d\t%d\n", c + 1, (int)cnt[c]);
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.descent);
 }
 
 // --qtlx after the last round (single GPU), and after --qtl / --qtl2 where they are given: the extended single-locus scan
@@ -2121,6 +2172,109 @@ static void qtlfam_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool row
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlfam);
 }
 
+// --qtlhap after the last round (single GPU) and after the scans above: one descent sweep (cnf2_sweep_descent), the column map
+// of --qtl-hap-by (cnf2h_descent_columns' rule: haplotype, the default, an effect per founder haplotype; founder; line), then
+// per pattern of missing values the founder-haplotype scan (cnf2_qtl_scan_hap) of its traits, and with --qtl-permutations one
+// more on the permuted residuals of the null model.  An individual with a parent without two recorded parents is not used.
+// More than 16 phased grandparents (32 columns) are refused: the within-family scan (--qtlfam) is the tool then.  The file
+// has the form of --qtl's: per marker "chrom<TAB>pos<TAB>n_used<TAB>df" of the first trait's pattern -- the individuals used
+// on the chromosome, the columns kept -- and per trait its LOD; after a blank line per trait "name<TAB>t5<TAB>t1".
+static void qtlhap_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::vector<double> rows((size_t)N * M * 8);
+    {
+        std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C);
+        std::vector<int32_t> cnt(C);
+        if (cnf2_sweep_descent(ctx, 0, N, fa.data(), ll.data(), rows.data(), cnt.data(), 0) != CNF2_OK)
+            throw EngineError(CNF2_ERR_STATE, std::string("--qtlhap: ") + cnf2_last_error(ctx));
+    }
+    std::vector<int32_t> par((size_t)P.inds.size() * 2), dous(P.dous.begin(), P.dous.end()), col((size_t)N * 8);
+    for (size_t r = 0; r < P.inds.size(); r++) par[2 * r] = P.inds[r].pars[0], par[2 * r + 1] = P.inds[r].pars[1];
+    const int by = opt.qtl_hap_by == "haplotype" ? 0 : opt.qtl_hap_by == "founder" ? 1 : 2;
+    const int G  = descent_columns(par.data(), N, dous.data(), by, col.data());
+    const int H  = std::max(1, by == 0 ? 2 * G : by == 1 ? G : 2);
+    if (H > 32)
+        throw EngineError(CNF2_ERR_STATE, "--qtlhap: " + std::to_string(G) + " grandparents give " + std::to_string(H) +
+                                              " columns, and the scan takes 32: use --qtl-hap-by founder or line, or --qtlfam");
+    std::vector<uint8_t> inmodel(N);
+    for (int j = 0; j < N; j++) {
+        inmodel[j] = base[j];
+        for (int k = 0; k < 8; k++) inmodel[j] = inmodel[j] && col[(size_t)j * 8 + k] >= 0;
+    }
+    std::vector<double>  lod((size_t)T * M, 0.0), thr((size_t)T * 2, 0.0);
+    std::vector<int32_t> df0(M, 0), nused0(C, 0);
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = inmodel[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M), rss((size_t)Tg * C);
+        std::vector<int32_t> df(M), nu(C);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc = cnf2_qtl_scan_hap(ctx, N, rows.data(), col.data(), H, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                   l.data(), df.data(), nullptr, rss.data(), nu.data(), nullptr, 0);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlhap: ") + cnf2_last_error(ctx));
+        if (tr[0] == 0) {
+            df0    = df;
+            nused0 = nu;
+        }
+        for (int t = 0; t < Tg; t++) std::copy(l.begin() + (size_t)t * M, l.begin() + (size_t)(t + 1) * M, lod.begin() + (size_t)tr[t] * M);
+        if (NP > 0) {
+            std::vector<int32_t> perm((size_t)NP * N);
+            std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * C);
+            qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+            qtl_null_residuals(N, Tg, yg.data(), K, cov.data(), u.data(), res.data());
+            rc = cnf2_qtl_scan_hap(ctx, N, rows.data(), col.data(), H, Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, NP, perm.data(),
+                                   l.data(), df.data(), nullptr, rss.data(), nu.data(), pm.data(), 0);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlhap permutations: ") + cnf2_last_error(ctx));
+            for (int t = 0; t < Tg; t++) {
+                std::vector<double> mx(NP, 0.0);
+                for (int p = 0; p < NP; p++)
+                    for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[((size_t)p * Tg + t) * C + c]);
+                thr[(size_t)tr[t] * 2]     = qtl_threshold(mx, 0.05);
+                thr[(size_t)tr[t] * 2 + 1] = qtl_threshold(mx, 0.01);
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtlhap.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlhap);
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+            fprintf(out, "%d\t%.5lf\t%d\t%d", c + 1, P.pos[m], (int)nused0[c], (int)df0[m]);
+            for (int t = 0; t < T; t++) fprintf(out, "\t%.5lf", lod[(size_t)t * M + m]);
+            fprintf(out, "\n");
+        }
+    if (NP > 0) {
+        fprintf(out, "\n");
+        for (int t = 0; t < T; t++)
+            fprintf(out, "%s\t%.5lf\t%.5lf\n", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str(), thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlhap);
+}
+
 // --qtlimp after the last round (single GPU) and after the other scans: one sampling sweep (cnf2_sweep_sample) of
 // --qtl-imp-draws paths per individual with --qtl-imp-seed, then per pattern of missing values the multiple-imputation scan
 // (cnf2_qtl_scan_imp) of its traits on those states, and with --qtl-permutations one more on the permuted residuals of the null
@@ -2489,6 +2643,10 @@ int main(int argc, char** argv)
         fprintf(stderr, "--origins needs a single GPU (--gpus 1): the ranks' sums are not reduced\n");
         return 2;
     }
+    if (opt.gpus > 1 && !opt.descent.empty()) {
+        fprintf(stderr, "--descent needs a single GPU (--gpus 1): the ranks' counts are not reduced\n");
+        return 2;
+    }
     if (opt.gpus > 1 && !opt.qtl.empty()) {
         fprintf(stderr, "--qtl needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
         return 2;
@@ -2641,6 +2799,22 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-cell must be parent or pair\n");
         return 2;
     }
+    if (opt.gpus > 1 && !opt.qtlhap.empty()) {
+        fprintf(stderr, "--qtlhap needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlhap.empty() && opt.qtlhap_extra_set) {
+        fprintf(stderr, "--qtl-hap-by needs --qtlhap FILE\n");
+        return 2;
+    }
+    if (!opt.qtlhap.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlhap FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtl_hap_by != "haplotype" && opt.qtl_hap_by != "founder" && opt.qtl_hap_by != "line") {
+        fprintf(stderr, "--qtl-hap-by must be haplotype, founder or line\n");
+        return 2;
+    }
     if (opt.gpus > 1 && !opt.qtlimp.empty()) {
         fprintf(stderr, "--qtlimp needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
         return 2;
@@ -2666,7 +2840,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
-        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && opt.qtlfam.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && opt.qtlfam.empty() && opt.qtlhap.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -2703,7 +2877,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty() ||
-         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty() || !opt.qtlimp.empty() || !opt.qtlfam.empty()) &&
+         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty() || !opt.qtlimp.empty() || !opt.qtlfam.empty() || !opt.qtlhap.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
     if (!opt.qtlmv.empty() && !prepare_qtlmv(opt)) return 2;

@@ -17,7 +17,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
            "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
            "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit", "cnf2h_qtlimp_marker",
-           "cnf2h_qtlfam_marker", "cnf2h_qtl_families"]
+           "cnf2h_qtlfam_marker", "cnf2h_qtl_families", "cnf2h_descent_columns", "cnf2h_qtlhap_marker"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -86,6 +86,8 @@ def load():
         L.cnf2h_qtlimp_marker.argtypes = [i32, i32, vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
         L.cnf2h_qtlfam_marker.argtypes = [i32, vp, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cnf2h_qtl_families.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp]
+        L.cnf2h_descent_columns.argtypes = [i32, vp, i32, vp, i32, vp, vp]
+        L.cnf2h_qtlhap_marker.argtypes = [i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -341,6 +343,42 @@ def qtl_families(par, dous, side):
     if rc != 0:
         raise ValueError("cnf2h_qtl_families refused its arguments (%d)" % rc)
     return grp, cell, int(F[0])
+
+
+def qtlhap_marker(descent, col, n_columns, y, cov=None, c=None, coef=True):
+    """cnf2h_qtlhap_marker: one marker of the founder-haplotype scan (cnf2_qtl_scan_hap) on the marker's rows descent[n][8],
+    the columns col[n][8], y[n][T] and cov[n][K] as they enter the sums and the chromosome's mask c[n].  A dict: lod[T], df,
+    coef[T][H] (None without coef), rss0[T], n_used.  CPU only."""
+    L = load()
+    d = np.ascontiguousarray(descent, np.float64).reshape(-1, 8)
+    n = d.shape[0]
+    q = np.ascontiguousarray(col, np.int32).reshape(n, 8)
+    v = np.ascontiguousarray(y, np.float64).reshape(n, -1)
+    T, H = v.shape[1], int(n_columns)
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    lod, rss0, co = np.zeros(T), np.zeros(T), np.zeros((T, max(H, 0))) if coef else None
+    df, n_used = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_qtlhap_marker(n, _p(d), _p(q), H, T, _p(v), K, None if K == 0 else _p(z), _p(m), _p(lod), _p(df),
+                               None if co is None else _p(co), _p(rss0), _p(n_used))
+    if rc != 0:
+        raise ValueError("cnf2h_qtlhap_marker refused its arguments (%d)" % rc)
+    return dict(lod=lod, df=int(df[0]), coef=co, rss0=rss0, n_used=int(n_used[0]))
+
+
+def descent_columns(par, dous, by="haplotype"):
+    """cnf2h_descent_columns: (col[n][8], G), the model column of every cell of the analysed records' descent rows by
+    "haplotype", "founder" or "line" (origins.descent_columns' rule, which `cnF2freq --qtlhap` uses) and the number of distinct
+    grandparents.  CPU only."""
+    L = load()
+    par = np.ascontiguousarray(par, np.int32).reshape(-1, 2)
+    dous = np.ascontiguousarray(dous, np.int32)
+    col, G = np.zeros((len(dous), 8), np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_descent_columns(len(par), _p(par), len(dous), _p(dous), ("haplotype", "founder", "line").index(by), _p(col), _p(G))
+    if rc != 0:
+        raise ValueError("cnf2h_descent_columns refused its arguments (%d)" % rc)
+    return col, int(G[0])
 
 
 def qtl_marker_map(chromstarts, tile, chrom_begin=0, chrom_end=None, with_mchrom=False, whole_map_header=True):

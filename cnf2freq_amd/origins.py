@@ -110,6 +110,57 @@ def pair_recombination(joint_sum, n_contrib, pairs, sel, chromstarts):
                 first=table[:, RECOMBINANT_FIRST].sum(axis=1), second=table[:, RECOMBINANT_SECOND].sum(axis=1))
 
 
+# The descent rows of Context.sweep_descent (cnf2_sweep_descent): per side a class k = 2 w + b, "the allele from this parent
+# descends from that parent's par[.][w], strand b of that grandparent" -- first side k = 2 bit0 + (bit0 ? bit2 : bit1), second
+# side k = 2 bit3 + (bit3 ? bit5 : bit4).  DESCENT_MASK[j][g]: state g belongs to cell j of the row (0..3 first side, 4..7 second)
+_G = np.arange(64)
+_B = [(_G >> t) & 1 for t in range(6)]
+_K1 = 2 * _B[0] + np.where(_B[0] == 1, _B[2], _B[1])
+_K2 = 2 * _B[3] + np.where(_B[3] == 1, _B[5], _B[4])
+DESCENT_MASK = np.stack([_K1 == k for k in range(4)] + [_K2 == k for k in range(4)])
+
+
+def descent_columns(par, dous, by="haplotype"):
+    """(col[n][8] int32, grandparents): the model column of every cell of the analysed individuals' descent rows, and the records
+    of the distinct grandparents in ascending order (their numbers g are the positions in that list).  Cell 4 s + 2 w + b of
+    individual i belongs to grandparent par[par[dous[i]][s]][w], strand b:
+      by="haplotype"   column 2 g + b: one effect per founder haplotype,
+      by="founder"     column g: one effect per founder (unphased or inbred founders),
+      by="line"        column w, the grandparent's position in its child's par entry.
+    A side whose parent is missing or has no two recorded parents gets -1 in its four cells."""
+    if by not in ("haplotype", "founder", "line"):
+        raise ValueError("by must be 'haplotype', 'founder' or 'line'")
+    par = np.asarray(par, np.int64).reshape(-1, 2)
+    dous = np.asarray(dous, np.int64).reshape(-1)
+    gp = np.full((len(dous), 2, 2), -1, np.int64)
+    for s in range(2):
+        p = par[dous, s]
+        ok = p >= 0
+        g = np.where(ok[:, None], par[np.maximum(p, 0)], -1)
+        gp[:, s] = np.where((g >= 0).all(axis=1)[:, None], g, -1)
+    grand = np.unique(gp[gp >= 0])
+    num = np.searchsorted(grand, np.maximum(gp, 0))
+    col = np.full((len(dous), 8), -1, np.int32)
+    for s in range(2):
+        for w in range(2):
+            for b in range(2):
+                c = {"haplotype": 2 * num[:, s, w] + b, "founder": num[:, s, w], "line": np.full(len(dous), w)}[by]
+                col[:, 4 * s + 2 * w + b] = np.where(gp[:, s, w] >= 0, c, -1)
+    return col, grand.astype(np.int32)
+
+
+def descent_calls(descent):
+    """(cls[..., 2], prob[..., 2]) from descent rows [..., 8]: per side the most probable class 2 w + b (int8; the lowest on
+    a tie) and its probability.  A skipped individual's all-zero rows call class -1 with probability 0."""
+    d = np.asarray(descent, np.float64)
+    assert d.shape[-1] == 8
+    sides = d.reshape(d.shape[:-1] + (2, 4))
+    cls = sides.argmax(axis=-1).astype(np.int8)
+    prob = sides.max(axis=-1)
+    cls[~(sides.sum(axis=-1) > 0)] = -1
+    return cls, prob
+
+
 def with_positions(ped, positions_cM_per_chrom):
     """(ped2, is_marker): the pedigree with a column without data (alleles 0, sure 0, hw 0.5 in every row) inserted at every
     position of positions_cM_per_chrom[c] on chromosome c, and is_marker[M2], False at the inserted columns.  The origin

@@ -347,6 +347,68 @@ def scan_fam(ctx, pheno, side="both", grp=None, cell=None, cov=None, use=None, p
     return out
 
 
+def descent_rows(ctx):
+    """One descent sweep of the context's pedigree with the rows left on its GPU: a torch tensor [n][M][8] that scan_hap takes
+    as `rows`."""
+    import torch
+    n, M, C = ctx.n_ind, ctx.n_markers, ctx.n_chrom
+    dev = torch.device("cuda", ctx.device)
+    t = lambda *shape, dtype=torch.float64: torch.zeros(shape, dtype=dtype, device=dev)
+    d_f, d_l, d_d, d_c = t(n, C, 8), t(n, C), t(n, M, 8), t(C, dtype=torch.int32)
+    ctx.sweep_descent_device(0, n, d_f.data_ptr(), d_l.data_ptr(), d_d.data_ptr(), d_c.data_ptr())
+    ctx.sync()
+    return d_d
+
+
+def scan_hap(ctx, ped, pheno, cov=None, by="haplotype", use=None, permutations=0, seed=0, rows=None, col=None, n_columns=None,
+             coef=True):
+    """The founder-haplotype scan of a whole cross on the context's uploaded pedigree `ped` (anything with par[R][2] and dous[n]):
+    one descent sweep with the rows left on the device (or `rows`, the tensor of descent_rows), the column map
+    origins.descent_columns(ped.par, ped.dous, by) -- "haplotype": an effect per founder haplotype, "founder": per founder, "line":
+    per position in the parents' entries -- or col[n][8] with n_columns, then per pattern of missing phenotypes (NaN) one observed
+    scan with the pattern's own `use`, and with permutations > 0 one more on the permuted residuals of the null model, as scan
+    does.  A dict: lod[T][M], df[T][M] (the design, and with it df, depends on who is used), coef[T][M][H] with coef (NaN for a
+    dropped column), rss0[T][C], n_used[T][C], col, n_columns, perm_max[P][T][C] or None."""
+    from . import origins
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    if col is None:
+        col, grand = origins.descent_columns(ped.par, ped.dous, by)
+        H = {"haplotype": 2 * len(grand), "founder": len(grand), "line": 2}[by]
+    else:
+        col = np.ascontiguousarray(col, np.int32)
+        H = int(col.max()) + 1 if n_columns is None else int(n_columns)
+    H = max(H, 1)
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    d_d = descent_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M)), df=np.zeros((T, M), np.int32), coef=np.full((T, M, H), np.nan) if coef else None,
+               rss0=np.zeros((T, C)), n_used=np.zeros((T, C), np.int32), col=col, n_columns=H,
+               perm_max=np.zeros((permutations, T, C)) if permutations else None)
+    call = lambda ys, u, **kw: ctx.qtl_scan_hap_device(n, d_d.data_ptr(), col, H, ys, cov=cov, use=u, **kw)
+    for cols, u in _patterns(y, use):
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = call(yk, u, coef=coef)
+        out["lod"][cols], out["df"][cols], out["rss0"][cols], out["n_used"][cols] = got["lod"], got["df"], got["rss0"], got["n_used"]
+        if coef:
+            out["coef"][cols] = got["coef"]
+        if permutations:
+            in_model = u & (col >= 0).all(axis=1)
+            perm = _permutations(n, permutations, seed, use=in_model)
+            out["perm_max"][:, cols] = call(null_residuals(yk, cov, in_model), in_model, perm=perm, coef=False)["perm_max"]
+    return out
+
+
+def hap_fstat(lod, df, n_used, K, chromstarts=None):
+    """(F, df1, df2) of a founder-haplotype profile: lod[T][M] and df[M] or [T][M] of scan_hap, n_used per marker or, with
+    chromstarts, per chromosome.  df1 = df, df2 = n_c - 1 - K - df: fam_fstat with the intercept as the one cell.  df varies
+    along the map, so a bare LOD is not comparable between markers without it."""
+    return fam_fstat(lod, df, n_used, np.ones_like(np.asarray(n_used)), K, chromstarts)
+
+
 def fam_fstat(lod, df, n_used, n_cells, K, chromstarts=None):
     """(F, df1, df2) of a within-family profile: lod[T][M] and df[M] or [T][M] of scan_fam, n_used and n_cells per marker
     (anything that broadcasts against lod) or, with chromstarts, per chromosome ([C] or [T][C]).  RSS0 / RSS1 = 10^(2 lod /

@@ -292,6 +292,78 @@ def make_outbred3(n_fam, kids_per_fam, markers_per_chrom, n_chrom=1, seed=777, m
     return ped
 
 
+def make_founder_cross(n_fam, kids_per_fam, markers_per_chrom, n_chrom=1, seed=777, missing=0.2, phase=0.98,
+                       sure=0.02, chrom_cm=100.0):
+    """(ped, descent_truth): make_outbred3's pedigree, law and random streams with phased founders that the families share.
+    Every family's two parents are children of family 0's four grandparents (parent k of a family: records 2k, 2k + 1; the
+    other families' grandparent records stay, unused), and a grandparent's hw is `phase` where it is heterozygous and its
+    true strand 0 carries allele 1, 1 - phase where it carries allele 2, 0.5 where it is homozygous.
+    descent_truth[N][2][M] (uint8) is the true descent class 2 w + b of every analysed child, side and marker from the
+    generator's meiosis indicators: the allele from parent `side` descends from that parent's par[.][w], strand b of that
+    grandparent (the classes of Context.sweep_descent)."""
+    pos, starts = make_map(n_chrom, markers_per_chrom, chrom_cm)
+    M = len(pos)
+    per = 6 + kids_per_fam
+    R = n_fam * per
+    names, par = [], np.full((R, 2), -1, np.int32)
+    gen = np.zeros(R, np.int32)
+    empty = np.zeros(R, np.uint8)
+    row_of = np.arange(1, R + 1, dtype=np.int32)
+    hap = np.zeros((R, M, 2), np.uint8)  # true phased alleles
+    freq = 0.1 + 0.8 * uniform(seed, (np.uint64(9) << np.uint64(40)) + np.arange(M, dtype=np.uint64))
+    dous = []
+    stream = 20
+    for f in range(n_fam):
+        base = f * per
+        for k in range(4):
+            r = base + k
+            names.append("G%d_%d" % (f, k))
+            u = uniform(seed, (np.uint64(10) << np.uint64(40)) + np.uint64(r) * np.uint64(2 * M)
+                        + np.arange(2 * M, dtype=np.uint64)).reshape(M, 2)
+            hap[r] = 1 + (u < freq[:, None])
+        for k in range(2):
+            r = base + 4 + k
+            names.append("P%d_%d" % (f, k))
+            par[r] = (2 * k, 2 * k + 1)
+            gen[r] = 1
+        for k in range(kids_per_fam):
+            r = base + 6 + k
+            names.append("K%d_%d" % (f, k))
+            par[r] = (base + 4, base + 5)
+            gen[r] = 2
+            dous.append(r)
+    prows = np.array([f * per + 4 + k for f in range(n_fam) for k in range(2)])
+    krows = np.array(dous)
+    gp = [_meiosis(seed, stream + s, len(prows), pos, starts) for s in range(2)]
+    gk = [_meiosis(seed, stream + 2 + s, len(krows), pos, starts) for s in range(2)]
+    for rows, g in ((prows, gp), (krows, gk)):
+        for s in range(2):
+            src = par[rows, s]
+            hap[rows, :, s] = np.where(g[s] == 0, hap[src, :, 0], hap[src, :, 1])
+    pidx = {int(r): i for i, r in enumerate(prows)}
+    truth = np.zeros((len(krows), 2, M), np.uint8)
+    for s in range(2):
+        at = np.array([pidx[int(p)] for p in par[krows, s]])
+        w = gk[s]
+        truth[:, s] = 2 * w + np.where(w == 0, gp[0][at], gp[1][at])
+
+    d = (hap == 2).sum(axis=2)
+    allele = np.zeros((R + 1, M, 2), np.uint8)
+    allele[1:, :, 0] = np.where(d == 2, 2, 1)
+    allele[1:, :, 1] = np.where(d == 0, 1, 2)
+    miss = uniform(seed, (np.uint64(11) << np.uint64(40)) + np.arange(R * M, dtype=np.uint64)).reshape(R, M) < missing
+    allele[1:][miss] = 0
+    sr = np.zeros((R + 1, M, 2))
+    sr[1:] = np.where(allele[1:] != 0, sure, 0.0)
+    hw = np.full((R + 1, M), 0.5)
+    for r in range(4):
+        hw[1 + r] = np.where(hap[r, :, 0] == hap[r, :, 1], 0.5, np.where(hap[r, :, 0] == 1, phase, 1.0 - phase))
+    ped = Pedigree(names, par, gen, empty, row_of, allele, sr, hw, pos, starts, np.array(dous, np.int32))
+    ped.founder_flags()
+    ped.truth = d.astype(np.uint8)
+    return ped, truth
+
+
 def _make_outbred3_fast(n_fam, kids_per_fam, markers_per_chrom, n_chrom, seed, missing, sure, chrom_cm):
     """make_outbred3 with vectorised draws (same pedigree layout, same law)."""
     pos, starts = make_map(n_chrom, markers_per_chrom, chrom_cm)

@@ -466,6 +466,37 @@ int cnf2_sweep_origins(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factor
  *                       and weighted with exp(factors[s] - loglik)): the cross-check of the sweep's fused form. */
 int cnf2_origin_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
 
+/* Descent rows: from which grandparent AND which of that grandparent's two strands does each of an individual's alleles
+ * descend, per marker.  The origin rows answer the first half; the joint of a parent's meiosis with the meiosis of the
+ * grandparent it selected cannot be had from the marginals bits[], so it is summed here.  gamma_i,m(g), the modes, the
+ * weights w_s, the 40-log-unit rule and the renormalisation are exactly those of cnf2_sweep_origins.  Per side a class
+ * k = 0..3:
+ *   first parent's side    k = 2 bit0(g) + (bit0(g) ? bit2(g) : bit1(g))
+ *   second parent's side   k = 2 bit3(g) + (bit3(g) ? bit5(g) : bit4(g))
+ *   descent[i][m][0..3] = sum_g gamma(g) [ first side's class == k ],  descent[i][m][4..7] the same of the second side
+ * A row is 64 bytes; each side sums to 1; a skipped individual's rows are all zero.
+ * Class 2 w + b reads "the allele from this parent descends from that parent's par[.][w], strand b of that grandparent".
+ * THE STRAND IS LABELLED BY THE GRANDPARENT'S OWN RECORD, that is by its stored allele order and hw: with hw near 1 where a
+ * heterozygous grandparent's strand 0 carries the first stored allele and near 0 where it carries the second, b is that
+ * strand; with the two values exchanged along the chromosome b names the other strand, and the two strand cells of that
+ * grandparent change places.  Where a grandparent is homozygous (hw 0.5 in a cross of inbred lines) its two strand cells
+ * are equal.  Identities with cnf2_sweep_origins: d0 + d1 = 1 - bits[0], d2 + d3 = bits[0], d4 + d5 = 1 - bits[3],
+ * d6 + d7 = bits[3].
+ *   factors_out / loglik_out  as cnf2_sweep: bit-equal
+ *   descent_out     [n][n_markers][8] or NULL.  Rows that are not asked for, and host rows, live whole in a buffer of the
+ *                   context of their own (CNF2_ERR_NOMEM if it cannot be had: split the individual range)
+ *   n_contrib_out   [n_chrom] (int32) individuals of the range with a likelihood on that chromosome (not skipped)
+ * Outputs are overwritten; a range split gives the same rows and counts.  Bad arguments (a NULL pointer other than
+ * descent_out, a range out of bounds) write nothing.  Positions between markers: as for cnf2_sweep_origins.
+ * Routing, tied windows and flags (CNF2_OUT_DEVICE: all four output pointers are device pointers; CNF2_STATIC_JOBS,
+ * CNF2_FULL_SPILL, CNF2_TIES_GENERAL) are cnf2_sweep_origins'; the fast kernel's descent instantiation reduces the eight
+ * values of a marker together by halving and eight lanes store the row.  Uniform windows take the same instantiation. */
+int cnf2_sweep_descent(cnf2_ctx *ctx, int ind_begin, int ind_end, double *factors_out, double *loglik_out,
+                       double *descent_out, int32_t *n_contrib_out, uint32_t flags);
+/*  cnf2_descent_rows    rows_out[mc][8] = the descent row of cnf2_sweep_descent for one individual and chromosome, from the
+ *                       store by brute force as cnf2_origin_rows: the cross-check of the sweep's fused form. */
+int cnf2_descent_rows(cnf2_ctx *ctx, int ind, int chrom, double *rows_out);
+
 /* Pair posteriors: the joint origin classes of two markers of one chromosome.  The product of two origin rows is the joint
  * distribution only across chromosomes; on one chain the two loci are linked.  For an analysed individual i, a chromosome
  * and two selected markers j < k of it, with the classes, the frame, the modes and the weights w_s of cnf2_sweep_origins:
@@ -912,6 +943,49 @@ int cnf2_qtl_scan_fam(cnf2_ctx *ctx, int n, const double *origin, int side, cons
                       const int32_t *perm, double *lod_out /* [T][M] */, int32_t *df_out /* [M] */,
                       double *slope_out /* [T][M][n_fam] or NULL */, double *rss0_out /* [T][C] */, int32_t *n_used_out /* [C] */,
                       int32_t *n_cells_out /* [C] */, double *perm_max_out /* [P][T][C] */, uint32_t flags);
+
+/* Founder-haplotype scan for outbred crosses: the founder-allele regression of multi-parent and outbred-F2 analyses.  The
+ * line-cross scans regress on the line origin of an allele and assume the lines fixed for the QTL alleles; the within-family
+ * scan above gives every F1 parent a slope of its own.  This model sits between the two: the trait is regressed on the
+ * expected dosage of every founder haplotype, QTL alleles being shared by all families that descend from the same founder
+ * chromosome -- far fewer parameters than a slope per F1 parent, and no assumption about the lines.  One definition for this
+ * header, cnf2freq_amd/csrc/cnf2_qtlhap.h (host and device), the kernels and tests/qtlhap_reference.py.
+ * Inputs: descent[n][M][8] are cnf2_sweep_descent's rows -- a host array, staged whole, or with CNF2_QTL_ORIGIN_DEVICE a device
+ * pointer (aligned to 16 bytes) read in place.  col[n][8] (int32) assigns every cell of an individual's row to a model column
+ * 0 .. n_columns-1, or to -1 (cnf2h_descent_columns of cnf2host.h, origins.descent_columns).  n_columns H is 1 .. 32: the cap
+ * is 16 phased grandparents; for more founders than that the within-family scan is the tool.  pheno[n][T], use, cov[n][K]
+ * (0 <= K <= 8), perm[P][n], the columns R = T (1 + P), X0, the centring of traits and covariates over the used individuals,
+ * S11, b0 and RSS0 per chromosome and column, the clamp of dRSS and the LOD formula are cnf2_qtl_scan's.
+ * Per chromosome c: c_i = use[i] and all eight col[i][k] in [0, H) and the descent row at c's first marker is not all zero;
+ * n_c = sum c_i.  Per marker m
+ *   Z[i][h] = c_i sum_k [col[i][k] == h] descent[i][m][k]                the expected dosage of column h, 0 .. 2
+ *   S22 = Z'Z,  S21 = Z'X0,  W = S22 - S21 S11^-1 S21',  v = Z'y - S21 S11^-1 X0'y.
+ * W is factored in ascending column order; column h is dropped when S22[h][h] == 0 or its pivot is below 1e-8 times
+ * S22[h][h]; df[m] is the number of columns kept.  The rows of Z add up to 2 c_i (with one column per strand each side adds
+ * up to c_i), so the rule acts at every marker: it is the normal path, and which of the dependent columns is dropped -- the
+ * last of them in column order -- is part of the definition.  dRSS = |L^-1 v|^2 over the kept columns, lod = (n_c / 2)
+ * log10(RSS0 / (RSS0 - dRSS)), coef = W_kept^-1 v, NaN where dropped: effects relative to the dropped columns.  A chromosome is
+ * not scanned under cnf2_qtl_scan's conditions (S11 without a Cholesky factor, n_c < K + 4); a marker with
+ * n_c - 1 - K - df < 1 reports df 0, lod 0 and coef NaN.  df varies along the map (cnf2freq_amd.qtl.hap_fstat).
+ * Outputs: lod_out[T][M]; df_out[M] (int32), which depends on the design only; coef_out[T][M][H] of the observed columns (NULL:
+ * not asked for); rss0_out[T][C]; n_used_out[C] n_c; perm_max_out[P][T][C] (NULL exactly when P = 0).  Host pointers, or device
+ * pointers with CNF2_OUT_DEVICE.  Everything cnf2_qtl_scan refuses, a NULL descent or col, n_columns outside 1 .. 32 and a col
+ * value >= n_columns or < -1 return CNF2_ERR_ARG and write nothing.
+ * Launches: on the host the gather list -- the used individuals ordered by their col row (a pattern: in a cross from few
+ * founders one per pair of F1 parents), every pattern padded to 4 slots; per chromosome the mask, S11 and its factor; per
+ * marker, a wave: S22 and S21 over the individuals in ascending order, W's packed factor in LDS (528 doubles at H = 32), the kept
+ * mask and df; per column tile (cnf2_set_qtl_columns caps it; results do not depend on it) cnf2_qtl_scan's column image and
+ * null fits, the product and the maxima's finish.  The product takes two markers x 32 columns per wave on
+ * v_mfma_f64_16x16x4_f64: the eight cells of a row at two markers are sixteen consecutive doubles, the operand as they lie in
+ * memory; at a pattern's end the 8 x 32 block per marker is added into the wave's G[H][32] in LDS at the rows the pattern's
+ * columns name.  The epilogue forms v, substitutes through the marker's factor, and forms the cell, the coefficients and the
+ * tile's maximum.  No atomics, every sum in a fixed order: a call gives the same bits every time, for every cap, from host or
+ * device rows, into host or device outputs. */
+int cnf2_qtl_scan_hap(cnf2_ctx *ctx, int n, const double *descent, const int32_t *col, int n_columns, int n_traits,
+                      const double *pheno, const uint8_t *use, int n_cov, const double *cov, int n_perm, const int32_t *perm,
+                      double *lod_out /* [T][M] */, int32_t *df_out /* [M] */, double *coef_out /* [T][M][H] or NULL */,
+                      double *rss0_out /* [T][C] */, int32_t *n_used_out /* [C] */, double *perm_max_out /* [P][T][C] */,
+                      uint32_t flags);
 
 /* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
  * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;

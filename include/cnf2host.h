@@ -311,6 +311,26 @@ int cnf2h_qtlfam_marker(int n, const double *origin, int side, const int32_t *gr
 int cnf2h_qtl_families(int n_rec, const int32_t *par, int n, const int32_t *dous, int side, int32_t *grp_out, int32_t *cell_out,
                        int32_t *n_fam_out);
 
+/* The host side of the descent rows and the founder-haplotype scan (cnf2_sweep_descent of cnf2hip.h):
+ *  cnf2h_descent_columns  col_out[n][8] of the analysed individuals dous[n] (records) from the pedigree's par[n_rec][2]: the
+ *                         model column of every cell of a descent row.  Cell 4 s + 2 w + b belongs to grandparent
+ *                         par[par[dous[i]][s]][w], strand b; the distinct grandparents are numbered g from 0 in ascending
+ *                         order of the records.  by 0 (haplotype): column 2 g + b; 1 (founder): column g; 2 (line): column w.
+ *                         -1 in the four cells of a side whose parent is missing or has no two recorded parents.
+ *                         *n_grand_out the grandparents counted.
+ *  cnf2h_qtlhap_marker    one marker of the founder-haplotype scan (cnf2_qtl_scan_hap of cnf2hip.h) through
+ *                         cnf2freq_amd/csrc/cnf2_qtlhap.h, by the steps and in the order of the kernels: descent[n][8] the
+ *                         marker's rows, col[n][8] and n_columns as the scan takes them, y[n][n_traits] and cov[n][n_cov] as
+ *                         they enter the sums (the scan centres them over the used individuals first), c[n] the chromosome's
+ *                         mask (an individual with a column outside 0 .. n_columns-1 is taken out here).  lod_out[n_traits],
+ *                         *df_out, coef_out[n_traits][n_columns] (NULL: not asked for), rss0_out[n_traits], *n_used_out n_c.
+ * -2: a bad argument. */
+int cnf2h_qtlhap_marker(int n, const double *descent, const int32_t *col, int n_columns, int n_traits, const double *y, int n_cov,
+                        const double *cov, const uint8_t *c, double *lod_out, int32_t *df_out, double *coef_out, double *rss0_out,
+                        int32_t *n_used_out);
+int cnf2h_descent_columns(int n_rec, const int32_t *par, int n, const int32_t *dous, int by, int32_t *col_out,
+                          int32_t *n_grand_out);
+
 #ifdef __cplusplus
 }
 #endif
