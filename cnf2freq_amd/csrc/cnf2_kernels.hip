@@ -1169,20 +1169,48 @@ __device__ __forceinline__ uint8_t load_root_allele(const KernelParams& p, const
     const __attribute__((address_space(1))) uint8_t* a8 = (const __attribute__((address_space(1))) uint8_t*)p.allele8;
     return a8[(size_t)c.row_root * p.n_markers + clamp_marker(m0 + c.mi, lo_m, hi_m)];
 }
+#ifndef CNF2_X_ROOTONCE
+#define CNF2_X_ROOTONCE 0
+#endif
+#if CNF2_X_ROOTONCE      /* timing ablation only (bit 0: the eights' forward pass, bit 1: their backward pass): results are wrong */
+struct RawRoot {
+    uint8_t ap;
+    double  s0, s1, hw;
+    __device__ __forceinline__ void into(RawRec* r) const
+    {
+        r->ap = ap;
+        r->s0 = s0;
+        r->s1 = s1;
+        r->hw = hw;
+    }
+};
+__device__ __forceinline__ void load_root(const KernelParams& p, const FastCtx& c, int m0, int lo_m, int hi_m, RawRoot* r)
+{
+    const size_t  i  = (size_t)c.row_root * p.n_markers + clamp_marker(m0 + c.mi, lo_m, hi_m);
+    const double2 su = p.sure[i];
+    r->ap = load_root_allele(p, c, m0, lo_m, hi_m);
+    r->s0 = su.x;
+    r->s1 = su.y;
+    r->hw = p.hw[i];
+}
+#endif
 // ap: load_root_allele of the same tile; rec_row: line * n_markers of this lane's line
 // ONE_MARKER: every lane of the wave looks at the same marker (the eights: c.mi is the job), so the gap's factors are one
 // value for the wave and come through the scalar cache instead of a vector load of 64 equal addresses (CNF2_UP8_SCALAR_GAP)
-template <int TQ_SHIFT, bool ONE_MARKER = false>
+// ROOT: the root's own data (sure, hw) is loaded here; false: the caller has it from elsewhere and r keeps what it holds
+template <int TQ_SHIFT, bool ONE_MARKER = false, bool ROOT = true>
 __device__ __forceinline__ void load_rec(const KernelParams& p, const FastCtx& c, uint32_t rec_row, int m0, int lo_m, int hi_m,
                                          uint8_t ap, RawRec* r)
 {
     const int     m = clamp_marker(m0 + c.mi, lo_m, hi_m);
-    const size_t  i = (size_t)c.row_root * p.n_markers + m;
-    const double2 su = p.sure[i];
     r->ap = ap;
-    r->s0 = su.x;
-    r->s1 = su.y;
-    r->hw = p.hw[i];
+    if (ROOT) {
+        const size_t  i = (size_t)c.row_root * p.n_markers + m;
+        const double2 su = p.sure[i];
+        r->s0 = su.x;
+        r->s1 = su.y;
+        r->hw = p.hw[i];
+    }
     // the value handed down: root allele f for the line of parent 0, the other one for parent 1
     const int v = ((c.pc.P ^ c.pc.f) & 1) ? (ap >> 4) : (ap & 15);
     const double2* q = (const double2*)(p.line_rec + (((size_t)(rec_row + (uint32_t)m) * LINE_VALUES + v) * 2 + c.pc.firstpar));
@@ -2904,6 +2932,17 @@ static_assert(TAB_R % 2 == 0 && TAB_2 % 2 == 0 && TAB_STRIDE % 2 == 0, "the A-si
 #ifndef CNF2_UP8_SCALAR_GAP
 #define CNF2_UP8_SCALAR_GAP 1
 #endif
+// 1: the root's sure, hw and allele byte are loaded once a tile of eight markers and staged in the LDS (cnf2_lane.h
+// up8_stage_*); 0: every producer lane loads them at every marker (A/B).  _FWD, _BWD: each pass alone (A/B)
+#ifndef CNF2_UP8_ROOT_STAGE
+#define CNF2_UP8_ROOT_STAGE 1
+#endif
+#ifndef CNF2_UP8_ROOT_STAGE_FWD
+#define CNF2_UP8_ROOT_STAGE_FWD CNF2_UP8_ROOT_STAGE
+#endif
+#ifndef CNF2_UP8_ROOT_STAGE_BWD
+#define CNF2_UP8_ROOT_STAGE_BWD CNF2_UP8_ROOT_STAGE
+#endif
 // markers to a forward tile (cnf2_lane.h up8_fwd_*); 1: the forward pass on one table row a marker, as the backward pass (A/B)
 #ifndef CNF2_UP8_FWD_TILE
 #define CNF2_UP8_FWD_TILE 8
@@ -2945,6 +2984,38 @@ __device__ __forceinline__ void produce_slot_rec(const FastCtx& c, double* slot,
         d[up8_fwd_at(0, 0, up8_fwd_gap(1))] = raw.tq1;
     }
 }
+// Root staging (cnf2_lane.h up8_stage_*): what lane (t = c.part, job = c.mi) loads once a tile for the
+// producer lanes of (marker t of the tile, job), clamped to the window as load_rec clamps, and where it goes in the LDS
+struct StagedRoot {
+    double2  su;
+    double   hw;
+    uint32_t ap;
+};
+__device__ __forceinline__ void load_stage(const KernelParams& p, const FastCtx& c, int m, int lo_m, int hi_m, StagedRoot* s)
+{
+    const __attribute__((address_space(1))) uint8_t* a8 = (const __attribute__((address_space(1))) uint8_t*)p.allele8;
+    const size_t i = (size_t)c.row_root * p.n_markers + clamp_marker(m, lo_m, hi_m);
+    s->su = p.sure[i];
+    s->hw = p.hw[i];
+    s->ap = a8[i];
+}
+// forward: e = the entry of (t, job)
+__device__ __forceinline__ void store_stage_fwd(double* e, const StagedRoot& s)
+{
+    *(double2*)(e + UP8_STAGE_SURE)    = s.su;
+    e[UP8_STAGE_HW]                    = s.hw;
+    *(uint32_t*)(e + UP8_STAGE_ALLELE) = s.ap;
+}
+// backward: row = the job's table row
+__device__ __forceinline__ void store_stage_bwd(double* row, int buf, int t, const StagedRoot& s)
+{
+    *(double2*)(row + (buf ? up8_stage_bwd_sure(1, 0) : up8_stage_bwd_sure(0, 0)) + 8 * t) = s.su;
+    row[(buf ? up8_stage_bwd_hw(1, 0) : up8_stage_bwd_hw(0, 0)) + 8 * t]                   = s.hw;
+    ((uint8_t*)(row + up8_stage_bwd_alleles(0) + buf))[t]                                  = (uint8_t)s.ap;
+}
+static_assert(up8_stage_bwd_sure(0, 3) == up8_stage_bwd_sure(0, 0) + 24 && up8_stage_bwd_hw(1, 3) == up8_stage_bwd_hw(1, 0) + 24 &&
+              up8_stage_bwd_alleles(1) == up8_stage_bwd_alleles(0) + 1, "store_stage_bwd and the staged readers step by marker and by buffer");
+static_assert(up8_stage_bwd_alleles(1) < TAB_R && up8_stage_bwd_alleles(0) >= TAB_T + 2, "the allele bytes sit behind the gap's factors");
 // What a forward step of the eights reads, from the job's table row or from its slot of a forward tile.  The slot's emission
 // is emission_from_row's expression on the same values (N = 2, s1 = 0, lo = the class): the same products fuse.
 struct Up8FwdRow {
@@ -3146,23 +3217,91 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
             const double* const qa = tab + up8_fwd_at(0, rj, up8_fwd_part(b0));
             const double* const qc = tab + up8_fwd_at(0, rj, up8_fwd_weight(0, c.s0));
             const double* const qb = tab + up8_fwd_at(0, rj, up8_fwd_part(4));
-            RawRec  rr[2];
-            uint8_t ap[2];
-            load_rec<0, SG>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rr[0]);
-            load_rec<0, SG>(pq, cp, rec_row, first + 1 + moff, first, last, load_root_allele(pq, cp, first + 1 + moff, first, last), &rr[1]);
-            ap[0] = load_root_allele(pq, cp, first + 2 + moff, first, last);
-            ap[1] = load_root_allele(pq, cp, first + 3 + moff, first, last);
+            // root staging (cnf2_lane.h up8_stage_*): tile k's root data sits in buffer k & 1 behind the tile.  As a staging lane
+            // this one is (marker cp.part of a tile, job cp.mi); as a producer it reads the entries of its job
+            constexpr bool STAGE = CNF2_UP8_ROOT_STAGE_FWD != 0 && T == UP8_STAGE_T && up8_fwd_buffers(T, REGION) == 1 &&
+                                   up8_stage_fwd_room(T, REGION) >= 2 * UP8_STAGE_BUFFER;
+            constexpr int SB = UP8_STAGE_BUFFER, SM = 8 * UP8_STAGE_ENTRY;      // from buffer to buffer, from marker to marker
+            double* const       sgw = tab + up8_stage_fwd_at(T, REGION, 0, cp.part, cp.mi);
+            const double* const sgr = tab + up8_stage_fwd_at(T, REGION, 0, 0, cp.mi);
+            auto allele_at = [&](const double* e) { return (uint8_t) * (const uint32_t*)(e + UP8_STAGE_ALLELE); };
+            StagedRoot sg;
+            RawRec     rr[2];
+            uint8_t    ap[2];
+            if constexpr (STAGE) {
+                // (the region is the wave's to write: the job before ended behind a fence)
+                StagedRoot sg1;
+                load_stage(pq, cp, first + cp.part, first, last, &sg);
+                load_stage(pq, cp, first + T + cp.part, first, last, &sg1);
+                store_stage_fwd(sgw, sg);
+                store_stage_fwd(sgw + SB, sg1);
+                load_stage(pq, cp, first + 2 * T + cp.part, first, last, &sg);
+                wave_lds_fence();
+                load_rec<0, SG, false>(pq, cp, rec_row, first + moff, first, last, allele_at(sgr), &rr[0]);
+                load_rec<0, SG, false>(pq, cp, rec_row, first + 1 + moff, first, last, allele_at(sgr + SM), &rr[1]);
+                ap[0] = allele_at(sgr + 2 * SM);
+                ap[1] = allele_at(sgr + 3 * SM);
+            } else {
+                load_rec<0, SG>(pq, cp, rec_row, first + moff, first, last, load_root_allele(pq, cp, first + moff, first, last), &rr[0]);
+                load_rec<0, SG>(pq, cp, rec_row, first + 1 + moff, first, last, load_root_allele(pq, cp, first + 1 + moff, first, last), &rr[1]);
+                ap[0] = load_root_allele(pq, cp, first + 2 + moff, first, last);
+                ap[1] = load_root_allele(pq, cp, first + 3 + moff, first, last);
+            }
+#if CNF2_X_ROOTONCE & 1    /* timing ablation only: results are wrong (a tile's markers all take the root's data of its first) */
+            static_assert(!STAGE, "the ablation is of the per-marker loads");
+            RawRoot rt_cur, rt_nxt;
+            load_root(pq, cp, first + moff, first, last, &rt_cur);
+            load_root(pq, cp, first + T + moff, first, last, &rt_nxt);
+#endif
             int tile = 0;
             for (int m0 = first; m0 <= last; m0 += T, tile++) {
                 const int toff = up8_fwd_tile(T, REGION, tile);
+                if constexpr (STAGE) {
+                    // the root of marker t + 1 is read in front of marker t's stores, the allele byte that the record's address
+                    // takes four markers ahead as the byte's load was: in this tile's buffer or, from its end on, in the next one's
+                    const double* const cur = sgr + (tile & 1) * SB;
+                    const double* const nxt = sgr + ((tile & 1) ^ 1) * SB;
+                    double2 su = *(const double2*)(cur + UP8_STAGE_SURE);
+                    double  hw = cur[UP8_STAGE_HW];
 #pragma unroll
-                for (int t = 0; t < T; t++) {
-                    produce_slot_rec(cp, tab + toff + up8_fwd_at(t, 0, 0), rr[t & 1]);
-                    // (unconditional, as above; what is asked for here is produced two markers on)
-                    load_rec<0, SG>(pq, cp, rec_row, m0 + t + 2 + moff, first, last, ap[t & 1], &rr[t & 1]);
-                    ap[t & 1] = load_root_allele(pq, cp, m0 + t + 4 + moff, first, last);
+                    for (int t = 0; t < T; t++) {
+                        rr[t & 1].s0 = su.x;
+                        rr[t & 1].s1 = su.y;
+                        rr[t & 1].hw = hw;
+                        if (t + 1 < T) {
+                            su = *(const double2*)(cur + (t + 1) * SM + UP8_STAGE_SURE);
+                            hw = cur[(t + 1) * SM + UP8_STAGE_HW];
+                        }
+                        produce_slot_rec(cp, tab + toff + up8_fwd_at(t, 0, 0), rr[t & 1]);
+                        load_rec<0, SG, false>(pq, cp, rec_row, m0 + t + 2 + moff, first, last, ap[t & 1], &rr[t & 1]);
+                        ap[t & 1] = allele_at(t + 4 < T ? cur + (t + 4) * SM : nxt + (t + 4 - T) * SM);
+                    }
+                } else {
+#pragma unroll
+                    for (int t = 0; t < T; t++) {
+#if CNF2_X_ROOTONCE & 1
+                        rt_cur.into(&rr[t & 1]);
+                        produce_slot_rec(cp, tab + toff + up8_fwd_at(t, 0, 0), rr[t & 1]);
+                        load_rec<0, SG, false>(pq, cp, rec_row, m0 + t + 2 + moff, first, last, rt_cur.ap, &rr[t & 1]);
+#else
+                        produce_slot_rec(cp, tab + toff + up8_fwd_at(t, 0, 0), rr[t & 1]);
+                        // (unconditional, as above; what is asked for here is produced two markers on)
+                        load_rec<0, SG>(pq, cp, rec_row, m0 + t + 2 + moff, first, last, ap[t & 1], &rr[t & 1]);
+                        ap[t & 1] = load_root_allele(pq, cp, m0 + t + 4 + moff, first, last);
+#endif
+                    }
                 }
+#if CNF2_X_ROOTONCE & 1
+                rt_cur = rt_nxt;
+                load_root(pq, cp, m0 + 2 * T + moff, first, last, &rt_nxt);
+#endif
                 wave_lds_fence();
+                if constexpr (STAGE) {
+                    // tile + 2 goes where this tile's root data was, its readers a fence behind and its own a fence (the one
+                    // behind the steps) ahead; tile + 3 has the steps and a tile's producer to arrive
+                    store_stage_fwd(sgw + (tile & 1) * SB, sg);
+                    load_stage(pq, cp, m0 + 3 * T + cp.part, first, last, &sg);
+                }
                 // (CNF2_UP8_FWD_READ markers' slots are read in front of the steps that use them: every slot of the tile has been
                 // produced, whether its marker is inside the window or not)
                 auto slot_at = [&](int t) {
@@ -3451,8 +3590,40 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
             }
             transition_uniform(S.b, r_m.x, r_m.y);
         };
-        load_rec<-1, SG>(pq, cp, rec_row, last + moff, first, last, load_root_allele(pq, cp, last + moff, first, last), &rraw);
-        ap_next = load_root_allele(pq, cp, last - 1 + moff, first, last);
+        // root staging (cnf2_lane.h up8_stage_bwd_*): the marker d below `last` is marker d & 7 of tile d >> 3, whose root data
+        // sits in buffer (d >> 3) & 1 of the job's row, in places the packed producer leaves alone and marker() does not read
+        // (with the parked row sums the partials go over them).  As a staging lane this one is (marker cp.part of a tile, job
+        // cp.mi); as a producer it reads its job's
+        constexpr bool STAGE_B = CNF2_UP8_ROOT_STAGE_BWD != 0 && CNF2_UP8_ROW_SUMS != 0;
+        double* const prow = tab + cp.mi * TS;
+        auto staged_sure = [&](int d) {
+            return *(const double2*)(prow + (((d >> 3) & 1) ? up8_stage_bwd_sure(1, 0) : up8_stage_bwd_sure(0, 0)) + 8 * (d & 7));
+        };
+        auto staged_hw = [&](int d) { return prow[(((d >> 3) & 1) ? up8_stage_bwd_hw(1, 0) : up8_stage_bwd_hw(0, 0)) + 8 * (d & 7)]; };
+        auto staged_allele = [&](int d) { return ((const uint8_t*)(prow + up8_stage_bwd_alleles(0) + ((d >> 3) & 1)))[d & 7]; };
+        StagedRoot sgb;
+        double2    su_n;
+        double     hw_n;
+        if constexpr (STAGE_B) {
+            // (the forward pass ended behind a fence: the region is the wave's to write)
+            load_stage(pq, cp, last - cp.part, first, last, &sgb);
+            store_stage_bwd(prow, 0, cp.part, sgb);
+            load_stage(pq, cp, last - 8 - cp.part, first, last, &sgb);
+            wave_lds_fence();
+            load_rec<-1, SG, false>(pq, cp, rec_row, last + moff, first, last, staged_allele(0), &rraw);
+            ap_next = staged_allele(1);
+            su_n    = staged_sure(0);
+            hw_n    = staged_hw(0);
+        } else {
+            load_rec<-1, SG>(pq, cp, rec_row, last + moff, first, last, load_root_allele(pq, cp, last + moff, first, last), &rraw);
+            ap_next = load_root_allele(pq, cp, last - 1 + moff, first, last);
+        }
+#if CNF2_X_ROOTONCE & 2
+        static_assert(!STAGE_B, "the ablation is of the per-marker loads");
+        RawRoot rt_cur, rt_nxt;
+        load_root(pq, cp, last + moff, first, last, &rt_cur);
+        load_root(pq, cp, last - 8 + moff, first, last, &rt_nxt);
+#endif
 #if !CNF2_UP8_ROW_SUMS && !defined(CNF2_X_NOPARK)
         // epilogue role: row mi2 = job, chain sub
         const int mi2 = lane >> 3, sub = lane & 7;
@@ -3460,10 +3631,41 @@ __global__ __launch_bounds__(CNF2_BLOCK, CNF2_UNI_MIN_BLOCKS) void fb_unipack8_k
         for (int m = last; m >= first; m--) {
             take_spill();
             ask_spill(m - first - 1);
+#if CNF2_X_ROOTONCE & 2    /* timing ablation only: results are wrong (eight markers take the root's data of the first of them) */
+            rt_cur.into(&rraw);
             produce_row_rec<true, true>(cp, tab, true, rraw);
-            load_rec<-1, SG>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);       // (unconditional, as forward)
-            ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
+            load_rec<-1, SG, false>(pq, cp, rec_row, m - 1 + moff, first, last, rt_cur.ap, &rraw);
+            if (((last - m) & 7) == 7) {
+                rt_cur = rt_nxt;
+                load_root(pq, cp, m - 9 + moff, first, last, &rt_nxt);
+            }
+#else
+            if constexpr (STAGE_B) {
+                const int d = last - m;
+                rraw.s0 = su_n.x;
+                rraw.s1 = su_n.y;
+                rraw.hw = hw_n;
+                produce_row_rec<true, true>(cp, tab, true, rraw);
+                load_rec<-1, SG, false>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);
+                // (read a marker, and the byte two markers, ahead as they were loaded: from the next tile's buffer at a tile's end)
+                ap_next = staged_allele(d + 2);
+                su_n    = staged_sure(d + 1);
+                hw_n    = staged_hw(d + 1);
+            } else {
+                produce_row_rec<true, true>(cp, tab, true, rraw);
+                load_rec<-1, SG>(pq, cp, rec_row, m - 1 + moff, first, last, ap_next, &rraw);       // (unconditional, as forward)
+                ap_next = load_root_allele(pq, cp, m - 2 + moff, first, last);
+            }
+#endif
             wave_lds_fence();                   // the producer lanes' rows are in place for the recursion lanes that read them
+            if constexpr (STAGE_B) {
+                // at a tile's first marker the next tile goes into the other buffer: its last readers (the marker before) are
+                // a fence behind, its first (this tile's seventh marker) fences ahead; the tile after that has eight markers to arrive
+                if (((last - m) & 7) == 0) {
+                    store_stage_bwd(prow, (((last - m) >> 3) + 1) & 1, cp.part, sgb);
+                    load_stage(pq, cp, m - 16 - cp.part, first, last, &sgb);
+                }
+            }
             if ((m - first) & 1) marker(odd_t(), myrow, m);
             else marker(even_t(), myrow, m);
 #if !CNF2_UP8_ROW_SUMS && !defined(CNF2_X_NOPARK)

@@ -147,6 +147,29 @@ CNF2_HD constexpr int up8_fwd_part(int part) { return part; }
 CNF2_HD constexpr int up8_fwd_weight(int f, int s0) { return 8 + 2 * f + s0; }
 CNF2_HD constexpr int up8_fwd_gap(int k) { return 12 + k; }
 
+// Root staging of that kernel (CNF2_UP8_ROOT_STAGE): the eight producer lanes (part, job) of a marker all need the root's
+// sure (two doubles), hw and allele byte of (marker, job), and eight consecutive markers share a line of each array.  So once a
+// tile of UP8_STAGE_T = 8 markers lane (t = lane >> 3, job = lane & 7) loads them for (marker t of the tile, job) and stores them
+// in the wave's LDS region, where the producer lanes read them, eight lanes an address.  Two buffers: tile k sits in buffer k & 1.
+//   forward:  behind the forward tiles; entry (t, job) is UP8_STAGE_ENTRY = 4 doubles: sure, hw, the allele byte (a 32-bit word)
+//   backward: the rows fill the region, but of a row's 64 unrestricted entries the packed producer stores and the eights read
+//             only 8 k + 0, 1 (cnf2_emtab.h packed_reads_unrestricted): the six doubles behind them hold marker t = k of the
+//             job's two buffers (sure 16-byte aligned in both), and the tile's eight allele bytes are the bytes of one double
+//             a buffer, behind the gap's factors (doubles 70, 71 of the row, which nobody else uses)
+enum { UP8_STAGE_T = 8, UP8_STAGE_ENTRY = 4, UP8_STAGE_BUFFER = UP8_STAGE_T * 8 * UP8_STAGE_ENTRY };
+// doubles of the region the forward tiles of T markers leave for staging
+CNF2_HD constexpr int up8_stage_fwd_room(int T, int region) { return region - up8_fwd_buffers(T, region) * T * UP8_FWD_MARKER; }
+// first double of entry (t, job) of buffer buf in the wave's region, forward
+CNF2_HD constexpr int up8_stage_fwd_at(int T, int region, int buf, int t, int job)
+{
+    return up8_fwd_buffers(T, region) * T * UP8_FWD_MARKER + buf * UP8_STAGE_BUFFER + (t * 8 + job) * UP8_STAGE_ENTRY;
+}
+enum { UP8_STAGE_SURE = 0, UP8_STAGE_HW = 2, UP8_STAGE_ALLELE = 3 };       // doubles from an entry's first, forward
+// backward, in the job's table row: double of sure (two) and of hw of (buffer, marker t), and the double of a buffer's allele bytes
+CNF2_HD constexpr int up8_stage_bwd_sure(int buf, int t) { return 8 * t + (buf ? 6 : 2); }
+CNF2_HD constexpr int up8_stage_bwd_hw(int buf, int t) { return 8 * t + (buf ? 5 : 4); }
+CNF2_HD constexpr int up8_stage_bwd_alleles(int buf) { return 70 + buf; }
+
 CNF2_HD int tie_force(int8_t tie, int combo)
 {
     return tie < 0 ? -1 : ((combo >> tie) & 1);
