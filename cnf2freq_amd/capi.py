@@ -53,7 +53,7 @@ SYMBOLS = [
     "cnf2_pack_rows", "cnf2_unpack_rows",
     "cnf2_crossover_rows", "cnf2_sweep_crossovers", "cnf2_sweep_viterbi", "cnf2_sweep_sample",
     "cnf2_sweep_place", "cnf2_sweep_loo", "cnf2_loo_rows", "cnf2_sweep_origins", "cnf2_origin_rows",
-    "cnf2_sweep_descent", "cnf2_descent_rows", "cnf2_qtl_scan_hap",
+    "cnf2_sweep_descent", "cnf2_descent_rows", "cnf2_qtl_scan_hap", "cnf2_qtl_scan_vc",
     "cnf2_linked_pairs", "cnf2_sweep_pairs", "cnf2_pair_rows", "cnf2_qtl_scan2_linked",
     "cnf2_qtl_scan", "cnf2_sweep_qtl", "cnf2_set_qtl_columns", "cnf2_qtl_scan2", "cnf2_set_qtl2_columns", "cnf2_qtl_scanx", "cnf2_set_qtlx_columns",
     "cnf2_qtl_scan_em", "cnf2_set_qtlem_columns", "cnf2_qtl_scan_binary", "cnf2_set_qtlbin_columns",
@@ -135,6 +135,7 @@ def load():
         L.cnf2_sweep_descent.argtypes = [vp, i32, i32, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_descent_rows.argtypes = [vp, i32, i32, vp]
         L.cnf2_qtl_scan_hap.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
+        L.cnf2_qtl_scan_vc.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_linked_pairs.argtypes = [vp, i32, vp, vp, vp]
         L.cnf2_sweep_pairs.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, C.c_uint32]
         L.cnf2_pair_rows.argtypes = [vp, i32, i32, i32, vp, vp]
@@ -922,6 +923,48 @@ class Context:
         sweep_descent_device call filled); they are read in place.  d_out: a dict of device pointers (ints) for QTLHAP_KEYS
         (coef and perm_max None where not asked for) -- the outputs then stay on the GPU and None is returned."""
         return self._qtlhap_call(n, C.c_void_p(d_descent), col, n_columns, pheno, cov, use, perm, coef, QTL_ORIGIN_DEVICE, d_out)
+
+    # -- variance-component scan ---------------------------------------------------
+    QTLVC_KEYS = ("lod", "h", "sigma2", "blup", "eval", "rank", "rss0", "n_used", "perm_max")
+
+    def _qtlvc_call(self, n, descent_ptr, col, H, pheno, cov, use, perm, blup, evals, flags, d_out=None):
+        """cnf2_qtl_scan_vc on the rows behind descent_ptr, with new host outputs or (d_out) device pointers"""
+        pheno, cov, use, perm = self._qtl_inputs(n, pheno, cov, use, perm)
+        T, K, P = pheno.shape[1], 0 if cov is None else cov.shape[1], 0 if perm is None else perm.shape[0]
+        col = np.ascontiguousarray(col, np.int32)
+        if col.shape != (n, 8):
+            raise ValueError("col must be [n][8]")
+        M, Cn, H = self.n_markers, self.n_chrom, int(H)
+        opt = lambda a: None if a is None else _p(a)
+        if d_out is not None:
+            dp = lambda k: C.c_void_p(d_out[k]) if d_out.get(k) else None
+            self._chk(self.L.cnf2_qtl_scan_vc(self.h, n, descent_ptr, _p(col), H, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm),
+                                              *[dp(k) for k in self.QTLVC_KEYS], flags | OUT_DEVICE), "cnf2_qtl_scan_vc")
+            return None
+        Hs = max(H, 0)
+        o = dict(lod=np.zeros((T, M)), h=np.zeros((T, M)), sigma2=np.zeros((T, M)), blup=np.zeros((T, M, Hs)) if blup else None,
+                 eval=np.zeros((M, Hs)) if evals else None, rank=np.zeros(M, np.int32), rss0=np.zeros((T, Cn)),
+                 n_used=np.zeros(Cn, np.int32), perm_max=np.zeros((P, T, Cn)) if P else None)
+        self._chk(self.L.cnf2_qtl_scan_vc(self.h, n, descent_ptr, _p(col), H, T, _p(pheno), opt(use), K, opt(cov), P, opt(perm),
+                                          *[opt(o[k]) for k in self.QTLVC_KEYS], flags), "cnf2_qtl_scan_vc")
+        return o
+
+    def qtl_scan_vc(self, descent, col, n_columns, pheno, cov=None, use=None, perm=None, blup=True, evals=True):
+        """cnf2_qtl_scan_vc on host rows descent[n][M][8] (what sweep_descent returns): the variance-component scan of pheno[n][T]
+        with random effects of the n_columns (1 .. 64) founder haplotypes that col[n][8] (origins.descent_columns) assigns the
+        cells of a row to.  A dict: lod[T][M], h[T][M] (s_u^2 / (s_u^2 + s_e^2)), sigma2[T][M] (s_e^2), blup[T][M][H] with blup,
+        eval[M][H] with evals (the eigenvalues of the marker's W, descending), rank[M], rss0[T][C], n_used[C], perm_max[P][T][C]
+        (None without permutations).  The model: include/cnf2hip.h; cnf2freq_amd/qtl.py (scan_vc) makes the columns."""
+        descent = np.ascontiguousarray(descent, np.float64)
+        if descent.ndim != 3 or descent.shape[1:] != (self.n_markers, 8):
+            raise ValueError("descent must be [n][%d][8]" % self.n_markers)
+        return self._qtlvc_call(descent.shape[0], _p(descent), col, n_columns, pheno, cov, use, perm, blup, evals, 0)
+
+    def qtl_scan_vc_device(self, n, d_descent, col, n_columns, pheno, cov=None, use=None, perm=None, blup=True, evals=True, d_out=None):
+        """The same on device rows (d_descent: an int, the pointer of n x M x 8 doubles aligned to 16 bytes); they are read in
+        place.  d_out: a dict of device pointers (ints) for QTLVC_KEYS (blup, eval and perm_max None where not asked for) -- the
+        outputs then stay on the GPU and None is returned."""
+        return self._qtlvc_call(n, C.c_void_p(d_descent), col, n_columns, pheno, cov, use, perm, blup, evals, QTL_ORIGIN_DEVICE, d_out)
 
     # -- multiple-imputation scan ------------------------------------------------
     def set_qtlimp_columns(self, cap):

@@ -36,6 +36,7 @@
 #include "cnf2_qtlimp.h"
 #include "cnf2_qtlfam.h"
 #include "cnf2_qtlhap.h"
+#include "cnf2_qtlvc.h"
 
 using namespace cnf2;
 
@@ -285,6 +286,11 @@ struct cnf2_ctx {
     DevBuf<double>   d_qh_rec, d_qh_null, d_qh_tilemax, d_qh_lod, d_qh_coef, d_qh_rss0, d_qh_pmax;
     DevBuf<uint32_t> d_qh_kept;
     DevBuf<int32_t>  d_qh_map, d_qh_nc, d_qh_df;   // d_qh_map: as d_q_map on tiles of two markers, then col and the gather list (cnf2_qtlhap.h)
+
+    // variance-component scan (cnf2_qtl_scan_vc): the marker records (eigenvalues, Qt, G, grid tables), the null fits, the tile
+    // maxima, staged outputs; the rest as in the founder-haplotype scan
+    DevBuf<double>  d_qv_rec, d_qv_null, d_qv_tilemax, d_qv_lod, d_qv_h, d_qv_sigma2, d_qv_blup, d_qv_eval, d_qv_rss0, d_qv_pmax;
+    DevBuf<int32_t> d_qv_map, d_qv_nc, d_qv_rank;   // d_qv_map: as d_qh_map
 
     // marker placement (cnf2_sweep_place)
     DevBuf<uint8_t> d_pl_allele8;         // [n_rows][Q] candidate rows
@@ -2196,6 +2202,114 @@ int cnf2_qtl_scan_hap(cnf2_ctx* ctx, int n, const double* descent, const int32_t
         launch_qtl_gather(q, ctx->stream);
         launch_qtl_null(q, ctx->stream);
         launch_qtlhap_scan(p, ctx->stream);
+        if (r0 + q.rn > (size_t)T) launch_qtl_finish(q, ctx->stream);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return qtl_fetch_outputs(ctx, dev, outputs);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Variance-component scan (cnf2_qtlvc.h, cnf2_qtlvc_kernels.hip), in the founder-haplotype scan's order of steps and on its
+// mask: the individuals of `use` with all eight columns in [0, H).
+// ------------------------------------------------------------------------------------------------
+int cnf2_qtl_scan_vc(cnf2_ctx* ctx, int n, const double* descent, const int32_t* col, int n_columns, int n_traits,
+                     const double* pheno, const uint8_t* use, int n_cov, const double* cov, int n_perm, const int32_t* perm,
+                     double* lod_out, double* h_out, double* sigma2_out, double* blup_out, double* eval_out, int32_t* rank_out,
+                     double* rss0_out, int32_t* n_used_out, double* perm_max_out, uint32_t flags)
+{
+    if (!ctx) return CNF2_ERR_ARG;
+    if (ctx->n_markers <= 0) return fail(ctx, CNF2_ERR_STATE, "the map must be uploaded first");
+    if (n < 1 || n_traits < 1 || !pheno) return fail(ctx, CNF2_ERR_ARG, "n and n_traits must be at least 1 and pheno not NULL");
+    if (!descent || !col) return fail(ctx, CNF2_ERR_ARG, "descent and col must not be NULL");
+    if (n_columns < 1 || n_columns > QTLVC_MAXH) return fail(ctx, CNF2_ERR_ARG, "n_columns must be 1 .. %d", QTLVC_MAXH);
+    if (n_cov < 0 || n_cov > QTL_MAXK || (n_cov > 0 && !cov)) return fail(ctx, CNF2_ERR_ARG, "n_cov must be 0 .. %d, with cov", QTL_MAXK);
+    if (n_perm < 0 || (n_perm > 0) != (perm != nullptr) || (n_perm > 0) != (perm_max_out != nullptr))
+        return fail(ctx, CNF2_ERR_ARG, "perm and perm_max_out must be NULL exactly when n_perm is 0");
+    if (!lod_out || !h_out || !sigma2_out || !rank_out || !rss0_out || !n_used_out) return fail(ctx, CNF2_ERR_ARG, "an output pointer is NULL");
+    if ((size_t)n_traits * ((size_t)n_perm + 1) > (size_t)1 << 30) return fail(ctx, CNF2_ERR_ARG, "too many columns");
+    const bool rows_dev = (flags & CNF2_QTL_ORIGIN_DEVICE) != 0;
+    if (rows_dev && ((uintptr_t)descent & 15)) return fail(ctx, CNF2_ERR_ARG, "device descent rows must be aligned to 16 bytes");
+    std::vector<uint8_t> inmodel(n);
+    const int            bad = qtlhap_mask(n, use, col, n_columns, inmodel.data());
+    if (bad >= 0) return fail(ctx, CNF2_ERR_ARG, "a column of individual %d is not in -1 .. %d", bad, n_columns - 1);
+    QtlArgs a = {n, n_traits, n_cov, n_perm, pheno, inmodel.data(), cov, perm, lod_out, nullptr, rss0_out, perm_max_out, rank_out, n_used_out};
+    std::vector<uint8_t> mask;
+    RC_TRY(qtl_check_values(ctx, a, &mask));
+    RC_TRY(qtl_check_perm(ctx, n, n_perm, perm, mask.data()));
+    QtlHapLayout lay;
+    qtlhap_layout(n, mask.data(), col, &lay);
+    QtlCentred centred;
+    qtl_centre(a, mask, centred);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const bool   dev = (flags & CNF2_OUT_DEVICE) != 0;
+    const int    M = ctx->n_markers, C = ctx->n_chrom, K = n_cov, T = n_traits, H = n_columns, nx = K + 1;
+    const size_t R = (size_t)T * ((size_t)n_perm + 1);
+    const size_t rt = qtl_column_tile(n, R, n_perm, 0, ctx->qtl_columns[QTL_CAP_SCAN]);
+    QtlMarkerMap map = qtl_marker_map(ctx->chromstarts.data(), C, 0, C, 2, true, true);
+    // col and the gather list behind the marker map, as the founder-haplotype scan lays them out
+    std::vector<int32_t>& img = map.image;
+    auto append = [&](const int32_t* v, size_t count) {
+        const size_t o = img.size();
+        img.insert(img.end(), v, v + count);
+        if (count == 0) img.push_back(0);
+        return o;
+    };
+    const size_t o_col = append(col, (size_t)n * 8), o_gidx = append(lay.gidx.data(), lay.gidx.size());
+    const size_t o_steppat = append(lay.steppat.data(), lay.steppat.size()), o_stepend = append(lay.stepend.data(), lay.stepend.size());
+    const size_t o_patcol = append(lay.patcol.data(), lay.patcol.size());
+
+    const size_t n_rows = (size_t)n * M * 8;
+    if (!rows_dev) RC_TRY(ctx->d_descent.ensure(ctx, n_rows));
+    RC_TRY(qtl_reserve_inputs(ctx, a, rt, 0));
+    QtlVcParams p;
+    memset(&p, 0, sizeof(p));
+    QtlParams& q = p.q;
+    q = qtl_gather_params(ctx, a, rt);
+    auto outputs = [&](auto each) -> int {
+        RC_TRY(each(n_used_out, ctx->d_qv_nc, (size_t)C, &q.nc));
+        RC_TRY(each(rank_out, ctx->d_qv_rank, (size_t)M, &p.rank));
+        RC_TRY(each(lod_out, ctx->d_qv_lod, (size_t)T * M, &q.lod));
+        RC_TRY(each(h_out, ctx->d_qv_h, (size_t)T * M, &p.h));
+        RC_TRY(each(sigma2_out, ctx->d_qv_sigma2, (size_t)T * M, &p.sigma2));
+        RC_TRY(each(blup_out, ctx->d_qv_blup, (size_t)T * M * H, &p.blup));
+        RC_TRY(each(eval_out, ctx->d_qv_eval, (size_t)M * H, &p.eval));
+        RC_TRY(each(rss0_out, ctx->d_qv_rss0, (size_t)T * C, &q.rss0));
+        return each(perm_max_out, ctx->d_qv_pmax, (size_t)n_perm * T * C, &q.pmax);
+    };
+    RC_TRY(ctx->d_qv_map.ensure(ctx, img.size()));
+    RC_TRY(ctx->d_q_chol.ensure(ctx, (size_t)C * QTL_CHOL));
+    RC_TRY(ctx->d_qv_rec.ensure(ctx, (size_t)M * qtlvc_rec_size(H, nx)));
+    RC_TRY(ctx->d_qv_null.ensure(ctx, (size_t)C * (nx + 1) * rt));
+    if (n_perm > 0) RC_TRY(ctx->d_qv_tilemax.ensure(ctx, map.n_tiles * rt));
+    RC_TRY(qtl_stage_outputs(ctx, dev, outputs));
+    if (!rows_dev) {
+        // (complete on return: the caller's array is not read after the call)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_descent.ptr, descent, n_rows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    RC_TRY(qtl_upload(ctx, ctx->d_qv_map, img.data(), img.size()));
+    RC_TRY(qtl_upload_inputs(ctx, a, mask));
+
+    q.M = M, q.C = C, q.P = n_perm, q.K = K, q.nx = nx;
+    q.cov = ctx->d_q_cov;
+    q.cs = ctx->d_qv_map, q.mchrom = ctx->d_qv_map + map.o_mchrom;
+    q.tiles = ctx->d_qv_map + map.o_tiles, q.tile_start = ctx->d_qv_map + map.o_tstart, q.n_tiles = (int)map.n_tiles;
+    q.cmask = ctx->d_q_cmask, q.chol = ctx->d_q_chol, q.nullq = ctx->d_qv_null, q.tilemax = ctx->d_qv_tilemax;
+    p.H = H, p.S = lay.S;
+    p.descent = rows_dev ? descent : ctx->d_descent.ptr;
+    p.col = ctx->d_qv_map + o_col, p.gidx = ctx->d_qv_map + o_gidx, p.steppat = ctx->d_qv_map + o_steppat;
+    p.stepend = ctx->d_qv_map + o_stepend, p.patcol = ctx->d_qv_map + o_patcol;
+    p.rec = ctx->d_qv_rec;
+
+    launch_qtlvc_chrom(p, ctx->stream);
+    if (!launch_qtlvc_design(p, ctx->stream)) return fail(ctx, CNF2_ERR_NOMEM, "the design kernel's LDS for %d columns was refused", H);
+    for (size_t r0 = 0; r0 < R; r0 += rt) {
+        q.r0 = (int)r0;
+        q.rn = (int)std::min(rt, R - r0);
+        launch_qtl_gather(q, ctx->stream);
+        launch_qtl_null(q, ctx->stream);
+        if (!launch_qtlvc_scan(p, ctx->stream)) return fail(ctx, CNF2_ERR_NOMEM, "the scan kernel's LDS for %d columns was refused", H);
         if (r0 + q.rn > (size_t)T) launch_qtl_finish(q, ctx->stream);
     }
     HIP_TRY(ctx, hipGetLastError());

@@ -20,6 +20,7 @@
 #include "../cnf2_qtlmv.h"
 #include "../cnf2_qtlfam.h"
 #include "../cnf2_qtlhap.h"
+#include "../cnf2_qtlvc.h"
 #include "../cnf2_qtlplan.h"
 #include "cnf2_remap.h"
 
@@ -710,6 +711,20 @@ int cnf2h_qtlhap_marker(int n, const double* descent, const int32_t* col, int n_
         return -2;
     return cnf2::qtlhap_marker_serial(n, descent, col, n_columns, n_traits, y, n_cov, cov, c, lod_out, df_out, coef_out, rss0_out,
                                       n_used_out)
+               ? 0
+               : -2;
+}
+
+// one marker of cnf2_qtl_scan_vc: qtlvc_marker_serial (cnf2_qtlvc.h)
+int cnf2h_qtlvc_marker(int n, const double* descent, const int32_t* col, int n_columns, int n_traits, const double* y, int n_cov,
+                       const double* cov, const uint8_t* c, double* lod_out, double* h_out, double* sigma2_out, double* blup_out,
+                       double* eval_out, int32_t* rank_out, double* rss0_out, int32_t* n_used_out)
+{
+    if (n < 1 || !descent || !col || n_traits < 1 || !y || n_cov < 0 || n_cov > cnf2::QTL_MAXK || (n_cov > 0 && !cov) || !c || !lod_out ||
+        !h_out || !sigma2_out || !rank_out || !rss0_out || !n_used_out)
+        return -2;
+    return cnf2::qtlvc_marker_serial(n, descent, col, n_columns, n_traits, y, n_cov, cov, c, lod_out, h_out, sigma2_out, blup_out,
+                                     eval_out, rank_out, rss0_out, n_used_out)
                ? 0
                : -2;
 }

@@ -16,6 +16,7 @@
 //            [--qtlmv F --phenofile P [--qtl-traits name,name,..] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
 //            [--qtlfam F --phenofile P [--qtl-fam-side first|second|both] [--qtl-cell parent|pair] [--qtl-covariates, --qtl-permutations, --qtl-seed]]
 //            [--qtlhap F --phenofile P [--qtl-hap-by haplotype|founder|line] [--qtl-covariates, --qtl-permutations, --qtl-seed]]
+//            [--qtlvc F --phenofile P [--qtl-vc-by haplotype|founder|line] [--qtl-covariates, --qtl-permutations, --qtl-seed]]
 //            [--qtlimp F --phenofile P [--qtl-imp-draws D] [--qtl-imp-seed S] [--qtl-covariates, --qtl-permutations, --qtl-seed, --qtl-additive]]
 //            [--remap F [--remap-iterations K]]
 // Flag names and semantics follow main() (cnF2freq.cpp:7954-7972, 8083-8195): postmarkerdata, an optional
@@ -247,6 +248,9 @@ struct Options {
     std::string qtlhap;                  // --qtlhap F: founder-haplotype scan (with --phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed)
     std::string qtl_hap_by = "haplotype"; // --qtl-hap-by haplotype|founder|line: what a model column stands for
     bool        qtlhap_extra_set = false;
+    std::string qtlvc;                   // --qtlvc F: variance-component scan (with --phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed)
+    std::string qtl_vc_by = "haplotype"; // --qtl-vc-by haplotype|founder|line: what a random effect stands for
+    bool        qtlvc_extra_set = false;
     std::string qtl_fam_side = "both";   // --qtl-fam-side first|second|both
     std::string qtl_cell = "pair";       // --qtl-cell parent|pair: a mean per parent on the side, or per pair of parents
     bool        qtlfam_extra_set = false; // one of the two above was given
@@ -373,6 +377,11 @@ static bool parse(int argc, char** argv, Options& o)
         else if (a == "--qtlimp") o.qtlimp = val();
         else if (a == "--qtlfam") o.qtlfam = val();
         else if (a == "--qtlhap") o.qtlhap = val();
+        else if (a == "--qtlvc") o.qtlvc = val();
+        else if (a == "--qtl-vc-by") {
+            o.qtl_vc_by       = val();
+            o.qtlvc_extra_set = true;
+        }
         else if (a == "--qtl-hap-by") {
             o.qtl_hap_by       = val();
             o.qtlhap_extra_set = true;
@@ -514,6 +523,7 @@ static void qtlmv_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows
 static void qtlimp_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 static void qtlfam_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx, bool rows_kept);
 static void qtlhap_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
+static void qtlvc_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx);
 
 // One rank of a run: GPU `rank` (or 0), the whole pedigree, its block of the analysed individuals.  rank 0 writes the output.
 static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmRegion* region)
@@ -629,6 +639,7 @@ static int run_rank(const Options& opt, Pedigree& P, int rank, int world, ShmReg
         qtlfam_scan(opt, P, ctx, !opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() ||
                                      !opt.qtlcof.empty() || !opt.qtlboot.empty() || !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty());
     if (world == 1 && !opt.qtlhap.empty()) qtlhap_scan(opt, P, ctx);
+    if (world == 1 && !opt.qtlvc.empty()) qtlvc_scan(opt, P, ctx);
     if (world == 1 && !opt.qtlimp.empty()) qtlimp_scan(opt, P, ctx);
     if (world == 1 && (!opt.crossovers.empty() || !opt.remap.empty())) crossovers_and_remap(opt, P, ctx);
     } catch (const EngineError& e) {
@@ -2275,6 +2286,113 @@ static void qtlhap_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
     if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlhap);
 }
 
+// --qtlvc after the last round (single GPU) and after the scans above: one descent sweep, the column map of --qtl-vc-by
+// (cnf2h_descent_columns' rule), then per pattern of missing values the variance-component scan (cnf2_qtl_scan_vc: random
+// founder-haplotype effects, one variance component per locus) of its traits, and with --qtl-permutations one more on the
+// permuted residuals of the null model.  An individual with a parent without two recorded parents is not used.  More than 32
+// phased grandparents (64 columns) are refused with the count.  The file has the form of --qtl's: per marker
+// "chrom<TAB>pos<TAB>n_used<TAB>rank" of the first trait's pattern -- the individuals used on the chromosome, the rank of the
+// marker's design -- and per trait its LOD and h, the locus' share of the variance; after a blank line per trait
+// "name<TAB>t5<TAB>t1".
+static void qtlvc_scan(const Options& opt, Pedigree& P, cnf2_ctx* ctx)
+{
+    const int N = (int)P.dous.size(), M = P.n_markers(), C = (int)P.chromstarts.size() - 1;
+    const int T = (int)opt.qtl_trait_cols.size(), K = (int)opt.qtl_cov_cols.size(), NP = opt.qtl_permutations;
+    std::map<std::string, int> row_of;
+    for (size_t r = 0; r < opt.pheno.ids.size(); r++) row_of[opt.pheno.ids[r]] = (int)r;
+    std::vector<double>  y((size_t)N * T, NAN), cov((size_t)N * K, 0.0);
+    std::vector<uint8_t> base(N, 0);
+    for (int j = 0; j < N; j++) {
+        const auto it = row_of.find(P.inds[P.dous[j]].name);
+        if (it == row_of.end()) continue;
+        const std::vector<double>& row = opt.pheno.rows[it->second];
+        base[j] = 1;
+        for (int k = 0; k < K; k++) {
+            cov[(size_t)j * K + k] = row[opt.qtl_cov_cols[k]];
+            if (row[opt.qtl_cov_cols[k]] != row[opt.qtl_cov_cols[k]]) base[j] = 0;
+        }
+        for (int t = 0; t < T; t++) y[(size_t)j * T + t] = row[opt.qtl_trait_cols[t]];
+    }
+    std::vector<int32_t> par((size_t)P.inds.size() * 2), dous(P.dous.begin(), P.dous.end()), col((size_t)N * 8);
+    for (size_t r = 0; r < P.inds.size(); r++) par[2 * r] = P.inds[r].pars[0], par[2 * r + 1] = P.inds[r].pars[1];
+    const int by = opt.qtl_vc_by == "haplotype" ? 0 : opt.qtl_vc_by == "founder" ? 1 : 2;
+    const int G  = descent_columns(par.data(), N, dous.data(), by, col.data());
+    const int H  = std::max(1, by == 0 ? 2 * G : by == 1 ? G : 2);
+    if (H > 64)
+        throw EngineError(CNF2_ERR_STATE, "--qtlvc: " + std::to_string(G) + " grandparents give " + std::to_string(H) +
+                                              " columns, and the scan takes 64: use --qtl-vc-by founder or line");
+    std::vector<double> rows((size_t)N * M * 8);
+    {
+        std::vector<double>  fa((size_t)N * C * 8), ll((size_t)N * C);
+        std::vector<int32_t> cnt(C);
+        if (cnf2_sweep_descent(ctx, 0, N, fa.data(), ll.data(), rows.data(), cnt.data(), 0) != CNF2_OK)
+            throw EngineError(CNF2_ERR_STATE, std::string("--qtlvc: ") + cnf2_last_error(ctx));
+    }
+    std::vector<uint8_t> inmodel(N);
+    for (int j = 0; j < N; j++) {
+        inmodel[j] = base[j];
+        for (int k = 0; k < 8; k++) inmodel[j] = inmodel[j] && col[(size_t)j * 8 + k] >= 0;
+    }
+    std::vector<double>  lod((size_t)T * M, 0.0), hh((size_t)T * M, 0.0), thr((size_t)T * 2, 0.0);
+    std::vector<int32_t> rank0(M, 0), nused0(C, 0);
+    std::map<std::vector<uint8_t>, std::vector<int>> groups;      // pattern of use -> traits
+    for (int t = 0; t < T; t++) {
+        std::vector<uint8_t> u(N);
+        for (int j = 0; j < N; j++) u[j] = inmodel[j] && y[(size_t)j * T + t] == y[(size_t)j * T + t];
+        groups[u].push_back(t);
+    }
+    for (const auto& g : groups) {
+        const std::vector<int>&     tr = g.second;
+        const std::vector<uint8_t>& u  = g.first;
+        const int                   Tg = (int)tr.size();
+        std::vector<double>  yg((size_t)N * Tg), l((size_t)Tg * M), h((size_t)Tg * M), s2((size_t)Tg * M), rss((size_t)Tg * C);
+        std::vector<int32_t> rk(M), nu(C);
+        for (int j = 0; j < N; j++)
+            for (int t = 0; t < Tg; t++) yg[(size_t)j * Tg + t] = u[j] ? y[(size_t)j * T + tr[t]] : 0.0;
+        int rc = cnf2_qtl_scan_vc(ctx, N, rows.data(), col.data(), H, Tg, yg.data(), u.data(), K, K ? cov.data() : nullptr, 0, nullptr,
+                                  l.data(), h.data(), s2.data(), nullptr, nullptr, rk.data(), rss.data(), nu.data(), nullptr, 0);
+        if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlvc: ") + cnf2_last_error(ctx));
+        if (tr[0] == 0) {
+            rank0  = rk;
+            nused0 = nu;
+        }
+        for (int t = 0; t < Tg; t++) {
+            std::copy(l.begin() + (size_t)t * M, l.begin() + (size_t)(t + 1) * M, lod.begin() + (size_t)tr[t] * M);
+            std::copy(h.begin() + (size_t)t * M, h.begin() + (size_t)(t + 1) * M, hh.begin() + (size_t)tr[t] * M);
+        }
+        if (NP > 0) {
+            std::vector<int32_t> perm((size_t)NP * N);
+            std::vector<double>  res((size_t)N * Tg, 0.0), pm((size_t)NP * Tg * C);
+            qtl_permutations(N, NP, opt.qtl_seed, u.data(), nullptr, perm.data());
+            qtl_null_residuals(N, Tg, yg.data(), K, cov.data(), u.data(), res.data());
+            rc = cnf2_qtl_scan_vc(ctx, N, rows.data(), col.data(), H, Tg, res.data(), u.data(), K, K ? cov.data() : nullptr, NP, perm.data(),
+                                  l.data(), h.data(), s2.data(), nullptr, nullptr, rk.data(), rss.data(), nu.data(), pm.data(), 0);
+            if (rc != CNF2_OK) throw EngineError(CNF2_ERR_STATE, std::string("--qtlvc permutations: ") + cnf2_last_error(ctx));
+            for (int t = 0; t < Tg; t++) {
+                std::vector<double> mx(NP, 0.0);
+                for (int p = 0; p < NP; p++)
+                    for (int c = 0; c < C; c++) mx[p] = std::max(mx[p], pm[((size_t)p * Tg + t) * C + c]);
+                thr[(size_t)tr[t] * 2]     = qtl_threshold(mx, 0.05);
+                thr[(size_t)tr[t] * 2 + 1] = qtl_threshold(mx, 0.01);
+            }
+        }
+    }
+    FILE* out = fopen(opt.qtlvc.c_str(), "w");
+    if (!out) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlvc);
+    for (int c = 0; c < C; c++)
+        for (int m = P.chromstarts[c]; m < P.chromstarts[c + 1]; m++) {
+            fprintf(out, "%d\t%.5lf\t%d\t%d", c + 1, P.pos[m], (int)nused0[c], (int)rank0[m]);
+            for (int t = 0; t < T; t++) fprintf(out, "\t%.5lf\t%.5lf", lod[(size_t)t * M + m], hh[(size_t)t * M + m]);
+            fprintf(out, "\n");
+        }
+    if (NP > 0) {
+        fprintf(out, "\n");
+        for (int t = 0; t < T; t++)
+            fprintf(out, "%s\t%.5lf\t%.5lf\n", opt.pheno.columns[opt.qtl_trait_cols[t]].c_str(), thr[(size_t)t * 2], thr[(size_t)t * 2 + 1]);
+    }
+    if (fclose(out) != 0) throw EngineError(CNF2_ERR_STATE, "cannot write " + opt.qtlvc);
+}
+
 // --qtlimp after the last round (single GPU) and after the other scans: one sampling sweep (cnf2_sweep_sample) of
 // --qtl-imp-draws paths per individual with --qtl-imp-seed, then per pattern of missing values the multiple-imputation scan
 // (cnf2_qtl_scan_imp) of its traits on those states, and with --qtl-permutations one more on the permuted residuals of the null
@@ -2815,6 +2933,22 @@ int main(int argc, char** argv)
         fprintf(stderr, "--qtl-hap-by must be haplotype, founder or line\n");
         return 2;
     }
+    if (opt.gpus > 1 && !opt.qtlvc.empty()) {
+        fprintf(stderr, "--qtlvc needs a single GPU (--gpus 1): a mixed model is not additive over the ranks' blocks\n");
+        return 2;
+    }
+    if (opt.qtlvc.empty() && opt.qtlvc_extra_set) {
+        fprintf(stderr, "--qtl-vc-by needs --qtlvc FILE\n");
+        return 2;
+    }
+    if (!opt.qtlvc.empty() && opt.phenofile.empty()) {
+        fprintf(stderr, "--qtlvc FILE needs --phenofile FILE\n");
+        return 2;
+    }
+    if (opt.qtl_vc_by != "haplotype" && opt.qtl_vc_by != "founder" && opt.qtl_vc_by != "line") {
+        fprintf(stderr, "--qtl-vc-by must be haplotype, founder or line\n");
+        return 2;
+    }
     if (opt.gpus > 1 && !opt.qtlimp.empty()) {
         fprintf(stderr, "--qtlimp needs a single GPU (--gpus 1): a regression is not additive over the ranks' blocks\n");
         return 2;
@@ -2840,7 +2974,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (opt.qtl.empty() && opt.qtl2.empty() && opt.qtlx.empty() && opt.qtlem.empty() && opt.qtlbin.empty() && opt.qtlcof.empty() && opt.qtlboot.empty() &&
-        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && opt.qtlfam.empty() && opt.qtlhap.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
+        opt.qtlmv.empty() && opt.qtlsurv.empty() && opt.qtlvar.empty() && opt.qtlimp.empty() && opt.qtlfam.empty() && opt.qtlhap.empty() && opt.qtlvc.empty() && (opt.qtl_extra_set || !opt.phenofile.empty())) {
         fprintf(stderr, "--phenofile, --qtl-covariates, --qtl-permutations, --qtl-seed and --qtl-additive need --qtl FILE or --qtl2 FILE\n");
         return 2;
     }
@@ -2877,7 +3011,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if ((!opt.qtl.empty() || !opt.qtl2.empty() || !opt.qtlx.empty() || !opt.qtlem.empty() || !opt.qtlbin.empty() || !opt.qtlcof.empty() || !opt.qtlboot.empty() ||
-         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty() || !opt.qtlimp.empty() || !opt.qtlfam.empty() || !opt.qtlhap.empty()) &&
+         !opt.qtlmv.empty() || !opt.qtlsurv.empty() || !opt.qtlvar.empty() || !opt.qtlimp.empty() || !opt.qtlfam.empty() || !opt.qtlhap.empty() || !opt.qtlvc.empty()) &&
         !prepare_qtl(opt, P))
         return 2;
     if (!opt.qtlmv.empty() && !prepare_qtlmv(opt)) return 2;

@@ -17,7 +17,7 @@ SYMBOLS = ["cnf2h_create", "cnf2h_create_on", "cnf2h_create_from_files", "cnf2h_
            "cnf2h_qtlem_fit", "cnf2h_qtlbin_fit", "cnf2h_qtlcof_marker", "cnf2h_kinship_sums", "cnf2h_qtl_cols_marker",
            "cnf2h_qtl_bootstrap_counts", "cnf2h_qtl_boot_marker", "cnf2h_qtl_marker_map", "cnf2h_qtl_column_tile",
            "cnf2h_qtlmv_marker", "cnf2h_qtl_group_tile", "cnf2h_qtlsurv_fit", "cnf2h_qtlvar_fit", "cnf2h_qtlimp_marker",
-           "cnf2h_qtlfam_marker", "cnf2h_qtl_families", "cnf2h_descent_columns", "cnf2h_qtlhap_marker"]
+           "cnf2h_qtlfam_marker", "cnf2h_qtl_families", "cnf2h_descent_columns", "cnf2h_qtlhap_marker", "cnf2h_qtlvc_marker"]
 
 # int fn(void *user, int op, void *buf, size_t count, size_t seg) -- the transport of a multi-process run (cnf2host.h)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t)
@@ -88,6 +88,7 @@ def load():
         L.cnf2h_qtl_families.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp]
         L.cnf2h_descent_columns.argtypes = [i32, vp, i32, vp, i32, vp, vp]
         L.cnf2h_qtlhap_marker.argtypes = [i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+        L.cnf2h_qtlvc_marker.argtypes = [i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -365,6 +366,29 @@ def qtlhap_marker(descent, col, n_columns, y, cov=None, c=None, coef=True):
     if rc != 0:
         raise ValueError("cnf2h_qtlhap_marker refused its arguments (%d)" % rc)
     return dict(lod=lod, df=int(df[0]), coef=co, rss0=rss0, n_used=int(n_used[0]))
+
+
+def qtlvc_marker(descent, col, n_columns, y, cov=None, c=None, blup=True):
+    """cnf2h_qtlvc_marker: one marker of the variance-component scan (cnf2_qtl_scan_vc), the arguments of qtlhap_marker with up to
+    64 columns.  A dict: lod[T], h[T], sigma2[T], blup[T][H] (None without blup), eval[H], rank (-1: the Jacobi iteration did not
+    converge), rss0[T], n_used.  CPU only."""
+    L = load()
+    d = np.ascontiguousarray(descent, np.float64).reshape(-1, 8)
+    n = d.shape[0]
+    q = np.ascontiguousarray(col, np.int32).reshape(n, 8)
+    v = np.ascontiguousarray(y, np.float64).reshape(n, -1)
+    T, H = v.shape[1], int(n_columns)
+    z = None if cov is None else np.ascontiguousarray(cov, np.float64).reshape(n, -1)
+    K = 0 if z is None else z.shape[1]
+    m = np.ones(n, np.uint8) if c is None else np.ascontiguousarray(np.asarray(c) != 0, np.uint8)
+    lod, h, s2, rss0 = np.zeros(T), np.zeros(T), np.zeros(T), np.zeros(T)
+    bl, ev = np.zeros((T, max(H, 0))) if blup else None, np.zeros(max(H, 0))
+    rank, n_used = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    rc = L.cnf2h_qtlvc_marker(n, _p(d), _p(q), H, T, _p(v), K, None if K == 0 else _p(z), _p(m), _p(lod), _p(h), _p(s2),
+                              None if bl is None else _p(bl), _p(ev), _p(rank), _p(rss0), _p(n_used))
+    if rc != 0:
+        raise ValueError("cnf2h_qtlvc_marker refused its arguments (%d)" % rc)
+    return dict(lod=lod, h=h, sigma2=s2, blup=bl, eval=ev, rank=int(rank[0]), rss0=rss0, n_used=int(n_used[0]))
 
 
 def descent_columns(par, dous, by="haplotype"):

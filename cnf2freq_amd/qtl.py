@@ -402,6 +402,52 @@ def scan_hap(ctx, ped, pheno, cov=None, by="haplotype", use=None, permutations=0
     return out
 
 
+def scan_vc(ctx, ped, pheno, cov=None, by="haplotype", use=None, permutations=0, seed=0, rows=None, col=None, n_columns=None,
+            blup=True):
+    """The variance-component scan of a whole cross on the context's uploaded pedigree `ped`, in the shape of scan_hap: random
+    effects of the founder haplotypes (up to 64 columns), one variance component per locus (cnf2_qtl_scan_vc).  One descent sweep
+    with the rows left on the device (or `rows`), the column map of `by` or col[n][8] with n_columns, then per pattern of missing
+    phenotypes (NaN) one observed scan with the pattern's own `use`, and with permutations > 0 one more on the permuted
+    residuals of the null model.  A dict: lod[T][M], h[T][M] the locus' share of the variance, sigma2_e[T][M],
+    sigma2_u[T][M] = h / (1 - h) sigma2_e, blup[T][M][H] with blup (the predicted founder-allele effects, 0 where the LOD is 0),
+    rank[T][M] and eval[T][M][H] (the design, and with it both, depends on who is used), rss0[T][C], n_used[T][C], col,
+    n_columns, perm_max[P][T][C] or None.  thresholds and peaks read it as they read scan."""
+    from . import origins
+    y = np.asarray(pheno, np.float64)
+    y = y[:, None] if y.ndim == 1 else y
+    n, T = y.shape
+    if n != ctx.n_ind:
+        raise ValueError("pheno must have a row per analysed individual (%d)" % ctx.n_ind)
+    if col is None:
+        col, grand = origins.descent_columns(ped.par, ped.dous, by)
+        H = {"haplotype": 2 * len(grand), "founder": len(grand), "line": 2}[by]
+    else:
+        col = np.ascontiguousarray(col, np.int32)
+        H = int(col.max()) + 1 if n_columns is None else int(n_columns)
+    H = max(H, 1)
+    use = np.ones(n, bool) if use is None else np.asarray(use) != 0
+    M, C = ctx.n_markers, ctx.n_chrom
+    d_d = descent_rows(ctx) if rows is None else rows
+    out = dict(lod=np.zeros((T, M)), h=np.zeros((T, M)), sigma2_e=np.zeros((T, M)), sigma2_u=np.zeros((T, M)),
+               blup=np.zeros((T, M, H)) if blup else None, rank=np.zeros((T, M), np.int32), eval=np.zeros((T, M, H)),
+               rss0=np.zeros((T, C)), n_used=np.zeros((T, C), np.int32), col=col, n_columns=H,
+               perm_max=np.zeros((permutations, T, C)) if permutations else None)
+    call = lambda ys, u, **kw: ctx.qtl_scan_vc_device(n, d_d.data_ptr(), col, H, ys, cov=cov, use=u, **kw)
+    for cols, u in _patterns(y, use):
+        yk = np.where(u[:, None], y[:, cols], 0.0)
+        got = call(yk, u, blup=blup)
+        out["lod"][cols], out["h"][cols], out["sigma2_e"][cols] = got["lod"], got["h"], got["sigma2"]
+        out["sigma2_u"][cols] = got["h"] / (1.0 - got["h"]) * got["sigma2"]
+        out["rank"][cols], out["eval"][cols], out["rss0"][cols], out["n_used"][cols] = got["rank"], got["eval"], got["rss0"], got["n_used"]
+        if blup:
+            out["blup"][cols] = got["blup"]
+        if permutations:
+            in_model = u & (col >= 0).all(axis=1)
+            perm = _permutations(n, permutations, seed, use=in_model)
+            out["perm_max"][:, cols] = call(null_residuals(yk, cov, in_model), in_model, perm=perm, blup=False, evals=False)["perm_max"]
+    return out
+
+
 def hap_fstat(lod, df, n_used, K, chromstarts=None):
     """(F, df1, df2) of a founder-haplotype profile: lod[T][M] and df[M] or [T][M] of scan_hap, n_used per marker or, with
     chromstarts, per chromosome.  df1 = df, df2 = n_c - 1 - K - df: fam_fstat with the intercept as the one cell.  df varies

@@ -987,6 +987,50 @@ int cnf2_qtl_scan_hap(cnf2_ctx *ctx, int n, const double *descent, const int32_t
                       double *rss0_out /* [T][C] */, int32_t *n_used_out /* [C] */, double *perm_max_out /* [P][T][C] */,
                       uint32_t flags);
 
+/* Variance-component scan for outbred crosses: random founder-haplotype effects, the flexible intercross analysis of
+ * Ronnegard, Besnier and Carlborg (2008).  The founder-haplotype scan above fits the founder alleles as fixed effects: it pays
+ * a degree of freedom per column, needs a drop rule at every marker and stops at 32 columns.  Here y = X0 b + Z u + e with
+ * u ~ N(0, s_u^2 I_H) and e ~ N(0, s_e^2 I): one variance component per locus, whatever the number of founders, no drop rule,
+ * and BLUPs of the founder-allele effects that show which alleles differ.  (Not the polygenic scan, which has one kinship
+ * matrix for the whole genome and fixed locus effects: here the variance component is the locus.)  One definition for this
+ * header, cnf2freq_amd/csrc/cnf2_qtlvc.h (host and device), the kernels and tests/qtlvc_reference.py.
+ * Inputs: cnf2_qtl_scan_hap's, with n_columns H in 1 .. 64; the mask c_i, n_c, Z[i][h], X0 = [1, centred cov], the centring,
+ * S11, b0, RSS0 and the conditions under which a chromosome is not scanned are that scan's.  Per marker m
+ *   W = Z'Z - S21 S11^-1 S21',  v = Z'y - S21 S11^-1 X0'y,  nu = n_c - 1 - K,
+ *   W = Q diag(d) Q' (eigenvalues below 0 count as 0),  rank[m] = the number of d_k > 1e-10 d_max,  t = Q'v,
+ * and only the terms of the rank enter the sums below.  The rows of Z add up to 2 c_i, so W always has null directions: they
+ * are the normal path and need no rule beyond this one.  The restricted likelihood is the likelihood of A'y with
+ * A A' = I - X0 (X0'X0)^-1 X0', so log|I + g A'ZZ'A| = log|I_H + g W| and by Woodbury the quadratic form is
+ * RSS0 - g v'(I + g W)^-1 v.  With g = h / (1 - h) and h in [0, 0.999]:
+ *   q(h) = RSS0 - sum_k g t_k^2 / (1 + g d_k)          clamped below at RSS0 2^-52
+ *   f(h) = ( nu log10(RSS0 / q(h)) - sum_k log10(1 + g d_k) ) / 2,     f(0) = 0.
+ * The search is deterministic: 41 grid points h_j = 0.999 j / 40, j* the first arg-max, h^ the maximiser of f on
+ * [h_max(j*-1,0), h_min(j*+1,40)] located within 1e-7 (21 bisections on the sign of f'(h), which needs no logarithm; where f
+ * does not rise into the bracket from an end, between h_j* and the other end, or h_j* itself: never below the grid's maximum), lod = max(f(h^), 0), and h^ = 0 wherever the LOD is 0.
+ * The eigenvalues come from a cyclic Jacobi iteration with a fixed round-robin order of disjoint pairs; it stops when every
+ * |W_pq| <= 2^-52 sqrt(|W_pp W_qq|), or after 30 sweeps: a marker that has not converged reports rank -1 and lod 0.
+ * Outputs: lod_out[T][M]; h_out[T][M]; sigma2_out[T][M] the residual variance q(h^) / nu (s_u^2 = g s_e^2);
+ * blup_out[T][M][H] (NULL: not asked for) u^ = Q diag(g / (1 + g d_k)) t, all zero at h^ = 0; eval_out[M][H] (NULL: not asked
+ * for) the clamped eigenvalues in descending order and rank_out[M] (int32), which depend on the design only; rss0_out[T][C];
+ * n_used_out[C]; perm_max_out[P][T][C] (NULL exactly when P = 0).  Host pointers, or device pointers with CNF2_OUT_DEVICE.  A
+ * marker with nu < 2 or rank 0 reports lod 0, h 0 and blup 0.  Everything cnf2_qtl_scan_hap refuses, and n_columns outside
+ * 1 .. 64, return CNF2_ERR_ARG and write nothing; CNF2_ERR_NOMEM when the marker records (about 60 KB each at H = 64) do not fit.
+ * Launches: the gather list, the chromosome kernel, the column image, the null fits and the finish are the founder-haplotype
+ * scan's.  Per marker, a wave: S22, S21 and W as that scan forms them, then the Jacobi iteration in the same wave with W and
+ * Q in LDS, and the marker's record: d, Q, G = S11^-1 S21', and for the 41 grid points the column-independent tables
+ * 10^(-sum_k log10(1 + g_j d_k) / nu) and g_j / (1 + g_j d_k), so that the grid pass of a cell has no logarithm and no division.
+ * The product is that scan's (two markers x 32 columns per wave on v_mfma_f64_16x16x4_f64, the wave's G[2][H][32] in LDS); the
+ * epilogue, a lane per (marker, column), forms v, rotates it, walks the grid, bisects and forms the cell, the BLUP of an
+ * observed column and the tile's maximum of a permuted one.  No atomics, every sum in a fixed order, every loop bounded: a
+ * call gives the same bits every time, for every cnf2_set_qtl_columns cap, from host or device rows, into host or device
+ * outputs. */
+int cnf2_qtl_scan_vc(cnf2_ctx *ctx, int n, const double *descent, const int32_t *col, int n_columns, int n_traits,
+                     const double *pheno, const uint8_t *use, int n_cov, const double *cov, int n_perm, const int32_t *perm,
+                     double *lod_out /* [T][M] */, double *h_out /* [T][M] */, double *sigma2_out /* [T][M] */,
+                     double *blup_out /* [T][M][H] or NULL */, double *eval_out /* [M][H] or NULL */, int32_t *rank_out /* [M] */,
+                     double *rss0_out /* [T][C] */, int32_t *n_used_out /* [C] */, double *perm_max_out /* [P][T][C] */,
+                     uint32_t flags);
+
 /* Maximum-likelihood single-locus scan: Lander and Botstein's interval mapping, the normal mixture over the four origin
  * classes fitted by EM.  Haley-Knott regression (the three scans above) is exact only where the origin rows are certain;
  * where a row is soft it leaves the within-individual genotype variance in the residual.  One definition for this header,

@@ -331,6 +331,17 @@ int cnf2h_qtlhap_marker(int n, const double *descent, const int32_t *col, int n_
 int cnf2h_descent_columns(int n_rec, const int32_t *par, int n, const int32_t *dous, int by, int32_t *col_out,
                           int32_t *n_grand_out);
 
+/* The host side of the variance-component scan (cnf2_qtl_scan_vc of cnf2hip.h):
+ *  cnf2h_qtlvc_marker     one marker through cnf2freq_amd/csrc/cnf2_qtlvc.h, by the steps and in the order of the kernels (the
+ *                         Jacobi schedule, the grid tables, the bisection): the inputs of cnf2h_qtlhap_marker with n_columns
+ *                         1 .. 64.  lod_out[n_traits], h_out[n_traits], sigma2_out[n_traits], blup_out[n_traits][n_columns]
+ *                         (NULL: not asked for), eval_out[n_columns] (NULL: not asked for), *rank_out (-1: the iteration did
+ *                         not converge), rss0_out[n_traits], *n_used_out n_c.
+ * -2: a bad argument. */
+int cnf2h_qtlvc_marker(int n, const double *descent, const int32_t *col, int n_columns, int n_traits, const double *y, int n_cov,
+                       const double *cov, const uint8_t *c, double *lod_out, double *h_out, double *sigma2_out, double *blup_out,
+                       double *eval_out, int32_t *rank_out, double *rss0_out, int32_t *n_used_out);
+
 #ifdef __cplusplus
 }
 #endif

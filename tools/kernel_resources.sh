@@ -13,7 +13,7 @@ for f in "$HERE"/cnf2freq_amd/csrc/cnf2_kernels.hip "$HERE"/cnf2freq_amd/csrc/cn
          "$HERE"/cnf2freq_amd/csrc/cnf2_qtlboot_kernels.hip "$HERE"/cnf2freq_amd/csrc/cnf2_qtlmv_kernels.hip \
          "$HERE"/cnf2freq_amd/csrc/cnf2_qtlsurv_kernels.hip "$HERE"/cnf2freq_amd/csrc/cnf2_qtlvar_kernels.hip \
          "$HERE"/cnf2freq_amd/csrc/cnf2_qtlimp_kernels.hip "$HERE"/cnf2freq_amd/csrc/cnf2_qtlfam_kernels.hip \
-         "$HERE"/cnf2freq_amd/csrc/cnf2_qtlhap_kernels.hip; do
+         "$HERE"/cnf2freq_amd/csrc/cnf2_qtlhap_kernels.hip "$HERE"/cnf2freq_amd/csrc/cnf2_qtlvc_kernels.hip; do
     b=$(basename "$f" .hip)
     (cd "$HERE/cnf2freq_amd/csrc" && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics --cuda-device-only \
         --no-gpu-bundle-output $CNF2_EXTRA_FLAGS -c -o "$TMP/$b.o" "$f" 2>/dev/null)
