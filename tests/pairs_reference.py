@@ -21,9 +21,11 @@ def linked(sel, chromstarts):
     return [(j, k) for j in range(len(sel)) for k in range(j + 1, len(sel)) if sc[j] == sc[k]]
 
 
-def oracle_pairs(ped, sel=None, threads=None):
+def oracle_pairs(ped, sel=None, threads=None, emissions=None):
     """(joint[n][n_pairs][16], pairs[n_pairs][2], (individual, chromosome) jobs compared) for the markers sel (default: all);
-    zeros where the oracle skips the individual on the chromosome"""
+    zeros where the oracle skips the individual on the chromosome.  emissions: a dict the caller keeps for this pedigree, in
+    which the oracle's emission vectors (per individual, mode and marker: they do not depend on sel) are remembered from one
+    selection to the next"""
     o = oracle_ped(ped)
     cs = np.asarray(ped.chromstarts)
     n, M, C = len(ped.dous), ped.n_markers, len(cs) - 1
@@ -54,7 +56,7 @@ def oracle_pairs(ped, sel=None, threads=None):
                     continue
                 any_mode = True
                 w = np.exp(fs - factor)
-                e = {}
+                e = {} if emissions is None else emissions.setdefault((ind, s), {})
                 for ia, a in enumerate(mine[:-1]):
                     V = fw[s, sel[a], 2][None, :] * ORIGIN_MASK
                     tot = V.sum()

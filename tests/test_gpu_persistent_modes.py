@@ -11,7 +11,9 @@ a chromosome of 64 markers before chromosomes of 1 to 17, tied after untied pass
 8-mode ones, a skipped job before a live one.  The assignment of jobs to waves is the planner's (cnf2_plan.h: untied windows'
 jobs first, chromosomes longest first, individuals ascending; with CNF2_STATIC_JOBS wave w takes jobs w, w + 4, ...): it is
 restated here (job_lists, held against the planner itself by tests/test_host_plan.py) and what the tests rely on is asserted.  One block must equal the full grid to the bit (sums that the header documents as f64 atomics
-in order of arrival: to the bar tests/test_gpu_uniform_states.py sets for them) and the oracle at each mode's own tolerance."""
+in order of arrival: to the bar tests/test_gpu_uniform_states.py sets for them) and the oracle at each mode's own tolerance.
+The descent and the pair sweep, which came after these six, go through the same loop on the same fixtures in
+tests/test_gpu_persistent_rows.py, which imports this file's fixtures and helpers."""
 import ctypes as C
 
 import numpy as np
